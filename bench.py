@@ -8,10 +8,15 @@ A "step" is one full frame INCLUDING its way back to the host (SURVEY 8d / BASEL
 read-back / RCCL gather included"): the scene, the BVH and the frame constants are resident in HBM
 before the timed region; every step renders into one of two device surfaces and copies it into one
 of two pinned host surfaces on a copy stream, so the read-back of frame k overlaps the rendering of
-frame k + 1; the timed region ends when the last frame has arrived on the host.  The rate with the
-frame left in HBM is reported beside it (`hbm_resident`).
+frame k + 1; the timed region ends when the last frame has arrived on the host.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else: an untimed prelude of
+frames before the timed region (`--prelude-s`) and, after it, the blocking drop-in call, the rate with the frame left in HBM
+(`hbm_resident`), per-kernel times and the rooflines, the primary-only rate, the surface passes, the CPU baseline and, for N > 1,
+the per-rank figures, the other gather and the frame verified against a single-GPU render.  `--dump-outputs DIR` writes the
+frame of the last timed step as float arrays (dump_outputs), so that two builds can be compared output for output.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): the frame is row-tiled in interleaved
 16-row strips, every rank renders its strips into a compact device buffer and ONE RCCL gather over
@@ -108,6 +113,30 @@ def make_frame(args, strips=None):
         make_frame.zero = np.zeros(3)
         f.area_light_offsets = make_frame.zero.ctypes.data
     return f
+
+
+DUMP_SAMPLE = 1 << 21       # pixels whose channels --dump-outputs writes: 32 MiB of channels + 16 MiB of indices (64 MB at most in all)
+
+
+def dump_outputs(out_dir, pixels, width):
+    """What a caller of the timed path receives -- the frame on the host, packed 0xAARRGGBB pixels -- as float arrays, identical
+    from run to run for the same arguments:
+      frame_row_xor.npy      float64 [rows]       XOR of every row's packed pixels (exact in float64): the whole frame
+      frame_pixels.npy       float32 [S, 4]       the A, R, G, B bytes of a fixed, seeded sample of S pixels (every pixel, in
+                                                  order, when the frame has at most DUMP_SAMPLE of them)
+      frame_pixel_index.npy  float64 [S]          the row-major index of each sampled pixel"""
+    px = np.ascontiguousarray(pixels).view(np.uint32)
+    n = px.size
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(12345).permutation(n)[:DUMP_SAMPLE])
+    s = px[idx]
+    channels = np.stack([(s >> np.uint32(k)) & np.uint32(0xff) for k in (24, 16, 8, 0)], axis=1).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_row_xor.npy"), np.bitwise_xor.reduce(px.reshape(-1, width), axis=1).astype(np.float64))
+    np.save(os.path.join(out_dir, "frame_pixels.npy"), channels)
+    np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
 
 
 def host_cores():
@@ -355,16 +384,19 @@ def main():
     ap.add_argument("--strip-rows", type=int, default=16)
     ap.add_argument("--device-build", action="store_true", help="(the default since round 3) build the BVH on the GPU (LBVH)")
     ap.add_argument("--host-build", action="store_true", help="build the BVH with the host's binned-SAH builder instead of the device LBVH")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (kernel times, counters, primary-only, surface passes)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline line: the prelude before the timed steps, the measurements and checks after them (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step to DIR/*.npy (float32 / float64, see dump_outputs; bench_out/ is git-ignored)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (drop-in call, kernel times, counters, primary-only, surface passes)")
     ap.add_argument("--exact-shadow-tests", action="store_true", help="k_shadow_test (every pair in FP64) instead of the fp32-classified k_shadow_cls")
     ap.add_argument("--dbg", action="append", default=[], metavar="KEY=VALUE", help="sr_debug_set hook, e.g. --dbg 1=16 (SR_DBG_ROUND_CAP0 = 16)")
     ap.add_argument("--in-library", action="store_true", help="single process: --gpus N devices behind sr_create_multi instead of one rank per GPU")
     ap.add_argument("--same-device", action="store_true", help="with --in-library: list device 0 N times (rehearsal on a one-GPU box)")
-    ap.add_argument("--prelude-s", type=float, default=6.0, help="untimed seconds of continuous frames before the timed region (lets GPU-busy samplers see the GPU phase)")
+    ap.add_argument("--prelude-s", type=float, default=None, help="untimed seconds of continuous frames before the timed region (lets GPU-busy samplers "
+                                                                   "see the GPU phase; default 6 with --full, 0 without)")
     ap.add_argument("--verify", action="store_true", help="after timing: rank 0 re-renders the whole frame alone and compares it with the one that arrived on the host")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU rehearsals)")
-    ap.add_argument("--no-verify", action="store_true", help="N > 1 verifies the gathered frame against a single-GPU render by default; this turns it off")
+    ap.add_argument("--no-verify", action="store_true", help="N > 1 with --full verifies the gathered frame against a single-GPU render by default; this turns it off")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the ranks a plain `--gpus N` run spawns (0 = pick a free one)")
     ap.add_argument("--gather", default="torch", choices=["torch", "rccl"],
                     help="N > 1: the strip gather inside the timed region -- torch.distributed.gather, or the library's own grouped ncclSend / ncclRecv "
@@ -372,6 +404,8 @@ def main():
     ap.add_argument("--micro", action="store_true", help="instead of the frame benchmark: the reference's IntersectRay micro-benchmarks (BASELINE.md 1), device-resident")
     ap.add_argument("--micro-rays", type=int, default=1 << 22)
     args = ap.parse_args()
+    if args.prelude_s is None:
+        args.prelude_s = 6.0 if args.full else 0.0
 
     # ---- plain `python bench.py --gpus N` (no launcher): become the launcher.  BEFORE anything touches the GPU this process starts
     #      `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD (never exec: see the environment notes) and
@@ -557,6 +591,8 @@ def main():
     value = primary_rays * args.steps / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
     last_host_frame = host[(state["k"] - 1) % 2].numpy().copy() if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_host_frame, args.res)
 
     out = None
     if rank == 0:
@@ -582,12 +618,13 @@ def main():
             out["frame_crc"] = int(np.bitwise_xor.reduce(last_host_frame.view(np.uint32)))
 
     if world > 1:
-        # ---- what a reader needs to cross-check the N > 1 line against N = 1 (all untimed, after the timed region): who took
-        #      part, every rank's own render time for its strips, and the three steps that follow the render on rank 0 ----
         for p in pending:
             if p is not None:
                 p.wait()
         torch.cuda.synchronize(dev)
+    if world > 1 and args.full:
+        # ---- what a reader needs to cross-check the N > 1 line against N = 1 (all untimed, after the timed region): who took
+        #      part, every rank's own render time for its strips, and the three steps that follow the render on rank 0 ----
         reps = 3
         dist.barrier()
         t1 = time.perf_counter()
@@ -679,7 +716,7 @@ def main():
                         "each step alone, max over ranks, best of %d; in the timed region they overlap the next frame's rendering" % (reps, reps),
             }
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         # ---- the drop-in call: what the reference's synchronous Renderer.Render() maps to (Renderer.cs:701-778, caller-owned int[] :593):
         #      a BLOCKING sr_render into a plain, pageable, already-touched numpy array; wall time per call ----
         plain = np.zeros(full_px, dtype=np.int32)
@@ -696,7 +733,7 @@ def main():
                                "note": "blocking sr_render(scene, frame, int32* pixels, NULL) into pageable host memory: the frame is enqueued on the library's own "
                                        "stream, every row band is copied back on a copy stream as soon as it is final, the caller's surface is pinned for the call"}
 
-    extras = world == 1 and not in_library and not args.no_extras
+    extras = world == 1 and not in_library and args.full and not args.no_extras
     if extras:
         # ---- the same steps with the frame left in HBM (no read-back) ----
         state["readback"] = False
@@ -857,9 +894,9 @@ def main():
             "anti_alias_2x": {"ms": aa_ms, "achieved_GBps": 5.0 * n / (aa_ms * 1e-3) / 1e9, "bytes": "4 B/source pixel + 4 B/destination pixel"},
             "peak_GBps": 8000.0,
         }
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, v9, argb, bmin, bmax)
-    if (args.verify or (n_gpus > 1 and not args.no_verify)) and rank == 0:
+    if (args.verify or (n_gpus > 1 and args.full and not args.no_verify)) and rank == 0:
         ref_scene = g
         if in_library:
             ref_scene = sa.GpuScene(0)

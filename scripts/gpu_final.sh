@@ -8,13 +8,13 @@ bash scripts/gpu_profile.sh $TAG > gpurun_out/prof_$TAG.log 2>&1 || exit 1
 bash scripts/gpu_sq_counters.sh $TAG > gpurun_out/sq_$TAG.log 2>&1 || exit 1
 bash scripts/gpu_lane_util.sh $TAG > gpurun_out/lanes_$TAG.log 2>&1 || exit 1
 python scripts/collect_profile.py $TAG $DIR > /dev/null || exit 1
-timeout -k 10 400 python bench.py > $DIR/bench_default.json 2> gpurun_out/bench_default.err || exit 1
+timeout -k 10 400 python bench.py --full > $DIR/bench_default.json || exit 1
 timeout -k 10 250 python scripts/gpu_strip_balance.py > $DIR/strip_balance.json 2>/dev/null || exit 1
 timeout -k 10 300 python scripts/gpu_configs.py > $DIR/configs_c1_c2_c3.jsonl 2>/dev/null || exit 1
-timeout -k 10 200 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 2 2>/dev/null | grep '^{' > $DIR/bench_2ranks_gloo_one_gpu.json || exit 1
-timeout -k 10 200 python bench.py --gpus 8 --in-library --same-device --steps 5 --warmup 2 --prelude-s 0 --verify > $DIR/bench_in_library_8_same_device.json 2>/dev/null || exit 1
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps 5 --tris 10000000 --extent 0.02 > $DIR/bench_c5_scene_shadows.json 2>/dev/null || exit 1
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps 5 --tris 10000000 --extent 0.02 --shadows 0 --bounces 4 > $DIR/bench_c5_four_bounces.json 2>/dev/null || exit 1
+timeout -k 10 200 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 2 2>/dev/null | grep '^{' > $DIR/bench_2ranks_gloo_one_gpu.json || exit 1
+timeout -k 10 200 python bench.py --full --gpus 8 --in-library --same-device --steps 5 --warmup 2 --prelude-s 0 --verify > $DIR/bench_in_library_8_same_device.json 2>/dev/null || exit 1
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 5 --tris 10000000 --extent 0.02 > $DIR/bench_c5_scene_shadows.json 2>/dev/null || exit 1
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 5 --tris 10000000 --extent 0.02 --shadows 0 --bounces 4 > $DIR/bench_c5_four_bounces.json 2>/dev/null || exit 1
 cp profiles/hbm_traffic.json gpurun_out/hbm_traffic.json
 rm -rf gpurun_out/profiles_final && cp -r $DIR gpurun_out/profiles_final
 python - $DIR <<'PY'

@@ -1,5 +1,5 @@
 """bench.py's N > 1 launch paths.  A plain `python bench.py --gpus N` must fan out to N ranks by itself (child processes,
-started before anything touches the GPU) and print ONE line whose frame is verified against the single-GPU frame.
+started before anything touches the GPU) and print ONE line; with --full its frame is verified against the single-GPU frame.
 * one-GPU box: 2 ranks share the GPU over gloo (RCCL refuses two ranks on one device);
 * a box with >= 2 GPUs: the real thing, 2 ranks over nccl (= RCCL over xGMI) -- skipped otherwise, so the first multi-GPU
   machine that runs the suite validates the RCCL gather by itself (Engine3D/Renderer.cs:1655-1680 is the split it replaces)."""
@@ -31,7 +31,7 @@ def _bench(*extra):
 @pytest.mark.gpu
 def test_plain_gpus2_fans_out_over_gloo_on_one_gpu():
     one = _bench("--gpus", "1", "--no-extras", "--verify")
-    two = _bench("--gpus", "2", "--backend", "gloo")
+    two = _bench("--gpus", "2", "--backend", "gloo", "--full")
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["verify"]["full_frame_equal"]
     assert two["frame_crc"] == two["verify"]["crc"] == one["verify"]["crc"]
@@ -44,7 +44,7 @@ def test_plain_gpus2_fans_out_over_gloo_on_one_gpu():
 @pytest.mark.gpu
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs: 2 ranks over nccl (RCCL)")
 def test_two_ranks_over_rccl_match_single_gpu_frame():
-    two = _bench("--gpus", "2")
+    two = _bench("--gpus", "2", "--full")
     assert two["n_gpus"] == 2 and two["verify"]["full_frame_equal"]
     m = two["multi_gpu"]
     assert m["backend"] == "nccl" and m["rccl_ranks"] == 2 and m["distinct_devices"] == 2

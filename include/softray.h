@@ -401,7 +401,11 @@ int  sr_debug_set(sr_scene*, int32_t key, int64_t value);
 
 /* Diagnostics only: the pipeline's device counters of the last frame, summed over its concurrent part-frame pipelines (last row band of each)
  * {hit-queue entries (on the shaft path: the padded tile-queue slot count, not the hits), per-lane shadow work head, hit points that needed the long (round-2) candidate list,
- *  hit points sent to the exact per-lane fallback, fallback work head, 0, 0, 0}. */
+ *  hit points sent to the exact per-lane fallback, fallback work head,
+ *  then host bookkeeping of the last frame: [5] the axes on which the ordered node copies the frame walked hold (near, far) planes
+ *  (bits 0-2: the light-ordered copy of the shaft walk, bits 4-6: the camera-ordered copy of the packet primary walk; or-ed over the
+ *  parts of a multi-device scene), [6] launches of the shaft walk in its persistent form, [7] those of them that walked the longest-first
+ *  tile order an earlier frame's walk lengths made}. */
 int  sr_debug_counters(sr_scene*, uint32_t out[8]);
 
 const char* sr_last_error(void);

@@ -106,6 +106,10 @@ struct sr_scene {
     bool   part_valid = false, part_cam = false, part_light = false;
     double part_origin[3] = {0, 0, 0}, part_lightpos[3] = {0, 0, 0}, part_radius = 0;
     double b4_light[3] = {0, 0, 0};      // light position the order of d_b4light was made for
+    double b4_light_radius = 0;          // ... and the light radius (which axes the light's ball lies outside of depends on it)
+    // sr_debug_counters [5..7] of the last frame, host bookkeeping: {b4light_known | b4cam_known << 4 of the ordered copies the frame walked,
+    // persistent shaft walks launched, those of them that walked a tile order made by an earlier frame}
+    uint32_t dbg_frame[3] = {0, 0, 0};
     // the per-origin / per-light records above are written on whatever stream the frame that needs them runs on: `pre_ready` is
     // recorded after every rewrite and waited for by every frame (another stream may use them next), `pre_used` is recorded at the
     // end of every frame that read them and waited for before the next rewrite
@@ -190,12 +194,14 @@ int use_device(sr_scene* s) {
     return SR_OK;
 }
 
-// axes on which `p` lies outside the root box's slab (by more than the shadow probe offset and the boxes' padding): known = those axes,
-// beyond = those of them on which p lies ABOVE the box
-void point_outside_axes(const sr::RootBox& root, const double p[3], int& known, int& beyond) {
+// axes on which the ball of `radius` about `p` lies outside the root box's slab (by more than the shadow probe offset and the boxes'
+// padding): known = those axes, beyond = those of them on which p lies ABOVE the box.  The camera is a point (radius 0); a light's ball
+// is its area-light samples: a sample that reaches back into the slab makes the shafts' direction along that axis depend on the hit
+// point (extra geometry can lie beyond the light), so that axis is not known
+void point_outside_axes(const sr::RootBox& root, const double p[3], double radius, int& known, int& beyond) {
     known = beyond = 0;
     for (int a = 0; a < 3; ++a) {
-        const double margin = 0.01 + 1e-3 * (root.max[a] - root.min[a]);
+        const double margin = 0.01 + 1e-3 * (root.max[a] - root.min[a]) + radius;
         if (p[a] > root.max[a] + margin) { known |= 1 << a; beyond |= 1 << a; }
         else if (p[a] < root.min[a] - margin) known |= 1 << a;
     }
@@ -399,6 +405,7 @@ int next_events(sr_scene* s, int k, hipEvent_t& a, hipEvent_t& b) {
 }
 
 int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats) {
+    for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = prepare_frame(s, f, fc);
     if (rc) return rc;
@@ -557,7 +564,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         if (wide && !s->b4cam_valid) {                                // the four-wide nodes, children front to back for this origin
             rewrote = true;
             int known, swap;                                      // (a camera ABOVE the box on an axis looks towards smaller coordinates: hi first)
-            point_outside_axes(s->root, fc.start_world, known, swap);
+            point_outside_axes(s->root, fc.start_world, 0.0, known, swap);
             // the camera-ordered copy holds (near, far) planes only when that is true on ALL axes (one extra instantiation of k_primary, not seven)
             if (known != 7 || s->dbg[SR_DBG_KERNEL_SWITCH] == 61) known = swap = 0;
             SR_HIP(sr::launch_order_nodes((const sr::Bvh4Node*)s->d_b4.p, (sr::Bvh4Node*)s->d_b4cam.p, (int)s->b4_num, s->root, fc.start_world, false, swap,
@@ -565,21 +572,25 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             s->b4cam_known = known;
             s->b4cam_valid = true;
         }
+        if (wide) s->dbg_frame[0] |= (uint32_t)s->b4cam_known << 4;
     }
     if (wide && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT)) {
-        const bool same_light = s->b4_light[0] == fc.light_pos_model[0] && s->b4_light[1] == fc.light_pos_model[1] && s->b4_light[2] == fc.light_pos_model[2];
+        const bool same_light = s->b4_light[0] == fc.light_pos_model[0] && s->b4_light[1] == fc.light_pos_model[1] && s->b4_light[2] == fc.light_pos_model[2] &&
+                                s->b4_light_radius == fc.light_radius;
         if (!s->b4light_valid || !same_light) {                       // ... and nearest-to-the-surface first for this light
             rewrote = true;
             s->b4light_valid = false;
             int known, beyond;                                    // (a light BELOW the box on an axis: every shaft travels towards smaller coordinates there, hi first)
-            point_outside_axes(s->root, fc.light_pos_model, known, beyond);
+            point_outside_axes(s->root, fc.light_pos_model, fc.light_radius, known, beyond);
             if (s->dbg[SR_DBG_KERNEL_SWITCH] == 62) known = 0;                    // (hook: (lo, hi) planes on every axis)
             SR_HIP(sr::launch_order_nodes((const sr::Bvh4Node*)s->d_b4.p, (sr::Bvh4Node*)s->d_b4light.p, (int)s->b4_num, s->root, fc.light_pos_model, true, known & ~beyond,
                                           (s->part_valid && s->part_light) ? s->d_rng_light.p : nullptr, stream));
             s->b4light_known = known;
             for (int i = 0; i < 3; ++i) s->b4_light[i] = fc.light_pos_model[i];
+            s->b4_light_radius = fc.light_radius;
             s->b4light_valid = true;
         }
+        s->dbg_frame[0] |= (uint32_t)s->b4light_known;
     }
     if (rewrote) {
         if (!s->pre_ready) SR_HIP(hipEventCreateWithFlags(&s->pre_ready, hipEventDisableTiming));
@@ -729,6 +740,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.tile_cost = order_tiles ? (unsigned int*)B.tile_cost.p : nullptr;
         P.tile_order = order_tiles ? (unsigned int*)B.tile_order.p : nullptr;
         P.tile_order_tag = order_tiles ? &B.tile_order_tag : nullptr;
+        P.shaft_launches = &s->dbg_frame[1];
         P.static_hits = static_shadows ? s->d_static_hits.p : nullptr;
         P.static_claim = static_shadows ? (unsigned long long*)s->d_static_claim.p : nullptr;
         P.static_concurrency = f->concurrency;
@@ -1720,7 +1732,10 @@ int sr_anti_alias(sr_scene* s, const int32_t* src, int32_t dst_width, int32_t ds
 int sr_debug_counters(sr_scene* s, uint32_t out[8]) {
     if (s && !s->parts.empty() && out) {
         for (int i = 0; i < 8; ++i) out[i] = 0;
-        for (sr_scene* q : s->parts) { uint32_t c[8]; int rc = sr_debug_counters(q, c); if (rc) return rc; for (int i = 0; i < 8; ++i) out[i] += c[i]; }
+        for (sr_scene* q : s->parts) {                              // (the known-axes masks of slot 5 are or-ed, the rest summed)
+            uint32_t c[8]; int rc = sr_debug_counters(q, c); if (rc) return rc;
+            for (int i = 0; i < 8; ++i) out[i] = i == 5 ? (out[i] | c[i]) : out[i] + c[i];
+        }
         return SR_OK;
     }
     /* diagnostics: the pipeline's device counters after the last band of the last frame:
@@ -1734,8 +1749,9 @@ int sr_debug_counters(sr_scene* s, uint32_t out[8]) {
         if (!sc.counters.p || !sc.used_last_frame) continue;
         uint32_t c[8];
         SR_HIP(hipMemcpy(c, sc.counters.p, 32, hipMemcpyDeviceToHost));
-        for (int i = 0; i < 8; ++i) out[i] += c[i];
+        for (int i = 0; i < 5; ++i) out[i] += c[i];
     }
+    for (int i = 0; i < 3; ++i) out[5 + i] = s->dbg_frame[i];      // host bookkeeping of the last frame (include/softray.h)
     return SR_OK;
 }
 

@@ -113,6 +113,7 @@ struct PipelineLaunch {
     unsigned int* tile_cost;
     unsigned int* tile_order;
     unsigned long long* tile_order_tag;
+    uint32_t* shaft_launches;   // host [2] or nullptr: += persistent launches of the shaft walk, += those that walked tile_order (sr_debug_counters [6], [7])
     hipStream_t stream;
     void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);   // optional per-launch timing
     // optional: called when every kernel of a row band has been enqueued on `stream` -- compact rows [row_begin, row_begin + row_count)

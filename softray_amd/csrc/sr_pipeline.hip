@@ -3558,6 +3558,7 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
                     default: go_known(std::integral_constant<int, 0>()); break;
                 }
                 if (keep_cost) { order_items = (vblocks >> 3) * 4u; order_new_tag = order_tag; }
+                if (heads && L.shaft_launches) { L.shaft_launches[0] += 1; if (order) L.shaft_launches[1] += 1; }
             } else if (first && !(L.per_lane_shaft & 1)) {
                 // round 1 on the binary tree (cross-check): one packet walk per 64 consecutive queue entries (one 8x8-pixel tile when the queue is tile-aligned)
                 size_t lds = ((size_t)levels * 4 + (size_t)levels * 64 * 2) * 4;

@@ -153,3 +153,51 @@ def leaf_face_scene():
     v9 = np.array([t, t2, t3], dtype=np.float64)
     argb = np.array([0xFFFF0000, 0xFF00FF00, 0xFF0000FF], dtype=np.uint32)
     return v9, argb, np.array([-2.0, -2.0, -4.0]), np.array([2.0, 2.0, 4.0])
+
+
+# ---- lights just outside the root box, with extra geometry beyond them (tests/test_edge_lights.py, tests/test_gpu_sequences.py) ----
+EDGE_SIGNS = ((1, 0, 0), (0, -1, 0), (1, 0, -1), (-1, 1, 0), (1, 1, -1), (-1, -1, -1))   # per axis: light above (+1) / below (-1) / inside (0)
+EDGE_GAPS = (0.02, 0.1)                 # the light centre's distance from the unit cube: past the 0.011 margin on every axis, within the 0.2 radius
+EDGE_RADII = (0.0, 0.2, 0.6)            # the offset table's radius (0: hard shadows, the control)
+
+
+def edge_light_case(signs, gap, radius, samples=17):
+    """Model-space light position, extra geometry beyond it (a plane facing the box, a sphere, an AxisAlignedBox), an offset table of
+    the given radius and a camera pose that sees the extra geometry from the side, for the unit-cube scene (box [-0.5, 0.5]^3)."""
+    s = np.array(signs, dtype=np.float64)
+    d = s / np.linalg.norm(s)
+    light = s * 0.5 + d * gap                               # `gap` from the box's face / edge / corner
+    up = np.array([0.0, 1.0, 0.0]) if abs(d[1]) < 0.9 else np.array([0.0, 0.0, 1.0])
+    side = np.cross(d, up)
+    side /= np.linalg.norm(side)
+    prims = [(1, 0xFFC0C0C0, list(light + 0.3 * d) + list(-d)),                    # Plane {point, normal}: faces the box
+             (0, 0xFF20A0FF, list(light + 0.16 * d + 0.22 * side) + [0.07]),
+             (4, 0, list(light + 0.12 * d - 0.24 * side - 0.06) + list(light + 0.12 * d - 0.24 * side + 0.06))]
+    table = orc.area_light_offsets(1234567890, samples)
+    table = table * (radius / np.sqrt((table * table).sum(axis=1)).max())
+    cam = side + 0.15 * d - 0.2 * up
+    cam /= np.linalg.norm(cam)
+    yaw = math.degrees(math.atan2(-cam[0], -cam[2]))
+    pitch = math.degrees(math.asin(-cam[1]))
+    return dict(signs=tuple(signs), gap=gap, radius=radius, light=light, prims=prims, table=np.ascontiguousarray(table), yaw=yaw, pitch=pitch,
+                depth=2.4, samples=samples)
+
+
+def edge_light_frame(c, res_w, res_h):
+    """The frame of an edge_light_case: shadows from the point light at c["light"] with c["table"] as its offsets (keep c alive)."""
+    f = make_frame(res_w, res_h, shadows=True, yaw_deg=c["yaw"], pitch_deg=c["pitch"], depth=c["depth"], shadow_samples=c["samples"])
+    t = [f.transform[i] for i in range(12)]
+    m = c["light"]
+    for r in range(3):
+        f.light_pos_view[r] = t[4 * r] * m[0] + t[4 * r + 1] * m[1] + t[4 * r + 2] * m[2] + t[4 * r + 3]
+    f.area_light_offsets = c["table"].ctypes.data
+    return f
+
+
+def camera_rays(f):
+    """Model-space origin and directions of the frame's one-sample-per-pixel camera rays (Renderer.cs:1718-1723), row-major."""
+    it = np.array([f.inv_transform[i] for i in range(12)]).reshape(3, 4)
+    rows, cols = np.mgrid[0:f.height, 0:f.width]
+    dv = np.stack([-(cols / f.width - 0.5), -(rows / f.height - 0.5) * (f.height / f.width), np.full(cols.shape, f.fov_depth)], axis=-1)
+    dirs = dv.reshape(-1, 3) @ it[:, :3].T
+    return it[:, :3] @ np.array([0.0, 0.0, -f.position_z]), dirs

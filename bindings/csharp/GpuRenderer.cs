@@ -108,6 +108,10 @@ namespace Engine3D.Hip
     public sealed class SoftrayHip : IDisposable
     {
         public const uint F_SHADING = 1, F_SHADOWS = 2, F_FOCAL_BLUR = 4, F_POINT_LIGHT = 8, F_SPECULAR = 16, F_STATIC_SHADOWS = 32;
+        /// rayTracePathTracing (Renderer.cs:1613-1618): pass it in `flags` together with rayTraceRandomSeed and rayTraceConcurrency
+        /// (the row blocks that each restart the random sequence).  Not together with F_SHADOWS: the library answers
+        /// SR_ERR_UNSUPPORTED, which Check turns into InvalidOperationException.
+        public const uint F_PATH_TRACING = 1u << 6;
         const uint F_PRIMARY_STATS_ONLY = 1u << 12;     // Num* count primary rays (Renderer.cs:1916-1923): no counting in the shadow stage
         public const int MODE_REF_TREE = 0, MODE_BRUTE = 1, MODE_BVH = 2;
         /// How NumGeometryTests / NumNodeVisits / NumLeafNodeVisits (Renderer.cs:476-504) are answered -- an explicit choice of the
@@ -271,7 +275,7 @@ namespace Engine3D.Hip
             }
             frame.width = width; frame.height = height; frame.start_row = startRow; frame.end_row = endRow; frame.sub_pixel_res = subPixelRes;
             frame.background_argb = backgroundColor; frame.flags = flags | F_PRIMARY_STATS_ONLY; frame.random_seed = randomSeed; frame.shadow_samples = 0; frame.trace_mode = mode;
-            frame.concurrency = concurrency;                                 // rayTraceConcurrency: fill order of the static shadow cache
+            frame.concurrency = concurrency;                                 // rayTraceConcurrency: fill order of the static shadow cache, row blocks of the path tracer
             frame.position_z = instance.Position.z; frame.fov_depth = fieldOfViewDepth; frame.focal_depth = focalDepth;
             frame.focal_blur_strength = focalBlurStrength; frame.ambient = ambient; frame.shininess = shininess;
             frame.light_dir_view[0] = lightDirView.x; frame.light_dir_view[1] = lightDirView.y; frame.light_dir_view[2] = lightDirView.z;

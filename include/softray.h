@@ -65,6 +65,19 @@ enum {
                                      advance in lock step -- row r of every block, blocks ascending, before row r + 1;
                                      columns ascending; sub-samples in loop order.  Needs the whole frame in one call:
                                      SR_ERR_UNSUPPORTED with strips, mirror bounces or SR_F_SINGLE_KERNEL            */
+    SR_F_PATH_TRACING = 1u << 6,  /* rayTracePathTracing -> PathTracingMethod.Enabled (Renderer.cs:1613-1618, PathTracingMethod.cs):
+                                     every camera sample that hits fires ONE second ray in a random direction of the hemisphere
+                                     about its normal, from pos + n * 0.001 through the same geometry, and stores
+                                     incoming * (n . d) + own colour (normalised when a channel exceeds 1.0).  The direction is made
+                                     of three NextDouble() of Random(random_seed); the reference restarts that sequence for every
+                                     one of its `concurrency` row blocks (Renderer.cs:1655-1666) and draws in scan order (row,
+                                     column, subX, subY) for the samples that hit, so sample number k (counting hits only) of a
+                                     block uses draws 3k .. 3k + 2: the library finds k with a segmented prefix sum over the hit
+                                     flags and looks the draws up in a table the scene keeps per (seed, length) -- 12 bytes per
+                                     sample of the largest row block, SR_ERR_UNSUPPORTED above 256 MiB.  Reads random_seed and
+                                     concurrency.  SR_ERR_UNSUPPORTED together with SR_F_SHADOWS (dynamic or static),
+                                     max_bounces > 0, SR_F_SINGLE_KERNEL and strip_count > 1 (a rank would need the hit counts
+                                     of rows it does not render); a multi-device scene renders such a frame on its first device */
     SR_F_SINGLE_KERNEL = 1u << 8, /* library option, not a Renderer field: trace the frame with the one-kernel
                                      renderer (k_render) instead of the k_primary/k_shadow/k_resolve pipeline.
                                      Pixels are identical; kept as an independent cross-check               */
@@ -139,8 +152,9 @@ typedef struct {
                                         parity unpinned): mirror bounces r = dir - n*(2 dir.n) from pos + n*0.001,
                                         each level coloured by the same shading/shadow chain, colours blended per
                                         channel ((s*(255-k))>>8) + ((r*k)>>8), k = (byte)(reflectivity*255)       */
-    int32_t  concurrency;            /* rayTraceConcurrency (:92), <= 0 => 4.  Only read with SR_F_STATIC_SHADOWS: it fixes
-                                        the order in which the shadow cache is filled (see that flag)               */
+    int32_t  concurrency;            /* rayTraceConcurrency (:92), <= 0 => 4.  Only read with SR_F_STATIC_SHADOWS (it fixes
+                                        the order in which the shadow cache is filled, see that flag) and with
+                                        SR_F_PATH_TRACING (the row blocks that each restart the random sequence)     */
     int32_t  reserved0;              /* 0 */
     double   transform[12];          /* rows 0..2 of Instance._transform        (Instance.cs:134)        */
     double   inv_transform[12];      /* rows 0..2 of Instance._inverseTransform (Instance.cs:135)        */
@@ -301,7 +315,8 @@ int  sr_kernel_times(sr_scene*, sr_kernel_time* out, int32_t cap);
  * in fp32, [13] pairs it had to decide with the exact FP64 test, [14] / [15] the part of [6] / [10] that came from private per-lane
  * shaft walks (later rounds) rather than from the packet walk; [16..19] the exact fallback's any-hit rays on their own {rays,
  * FP64 triangle records tested, nodes fetched per lane, leaves} (also contained in [4..7]); [20..23] the same for the mirror
- * rays of the bounce pipeline.  These are the counters the roofline's algorithmic bytes are priced from (DESIGN.md "Measurement"). */
+ * rays of the bounce pipeline (and for the second rays of a path-traced SR_MODE_BVH frame, which take the same walk; in every mode they
+ * are counted in [4..7] unless SR_F_PRIMARY_STATS_ONLY is set).  These are the counters the roofline's algorithmic bytes are priced from (DESIGN.md "Measurement"). */
 int  sr_last_ray_stats(const sr_scene*, uint64_t out[SR_STATS_COUNT]);
 
 /* Seeded synthetic triangle soup = SpatialSubdivisionTests.MakeRandomTriangles
@@ -372,7 +387,8 @@ enum {
     SR_DBG_KERNEL_SWITCH  = 6,   /* A/B switch of single optimisations, same pixels (0 = production): 31 the bounce pipeline walks its rays in
                                     queue order (no per-level ray sort); 61 the camera-ordered node copy keeps (lo, hi) planes; 71 no facing
                                     partition (the packet walks see every record of a leaf); 7 counts umbra decisions of the private shaft walk;
-                                    32 a mirror-bounce level as ONE kernel (k_bounce) instead of prepare / walk / finish; 100 + T: the walk kernel
+                                    32 a mirror-bounce level as ONE kernel (k_bounce) instead of prepare / walk / finish; 33 the second rays of a path-traced SR_MODE_BVH frame with
+                                    private per-lane walks (k_pt_finish) instead of the mirror extension's prepare / walk route; 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid
                                     too (its loop form spills registers: opt-in); 84 the persistent shaft walk hands its tiles out in natural order

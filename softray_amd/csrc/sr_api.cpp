@@ -116,6 +116,11 @@ struct sr_scene {
     hipEvent_t pre_ready = nullptr, pre_used = nullptr;
     bool pre_ready_set = false, pre_used_set = false;
     DBuf d_shadow_cache, d_static_claim, d_static_hits;
+    // path tracing (SR_F_PATH_TRACING): the InternalSample() ints of Random(pt_table_seed), 3 per sample of the largest row block a frame
+    // has asked for so far; made once per (seed, length) and kept for later frames
+    DBuf d_pt_table;
+    int32_t pt_table_seed = 0;
+    size_t  pt_table_samples = 0;
     bool shadow_cache_empty = true;      // the device cache must be zeroed before its next use
     DBuf d_pixels, d_aa, d_stats, d_io[9];
     // per-frame tables (area-light offsets + row map): pinned host staging and device copies, double-buffered; a slot is
@@ -134,6 +139,7 @@ struct sr_scene {
     static constexpr int kMaxSplit = 4;
     struct BandScratch {
         DBuf hits, hits2, bounce_levels, bounce_nlev, bounce_prep, bounce_res, bounce_stack, samples, counters, fallback, fallback_state, fallback_rays, fallback_ovf, ray_sort, ray_sort_temp;
+        DBuf pt_flags, pt_index, pt_totals, pt_carry;   // path tracing: hit flags, hit-index scan, row-block carries (sr_pipeline.hip k_pt_*)
         DBuf accum;                        // escape counts per sample index of a chunked (> 128 samples) shadow stage; zero between frames
         DBuf tile_cost, tile_order;        // walk length per 8x8 tile of the last shaft launch / the next one's longest-first lists
         unsigned long long tile_order_tag = 0;   // the tile grid tile_order was made for (0: none)
@@ -143,7 +149,7 @@ struct sr_scene {
         bool used_last_frame = false;
         void release() {
             tile_cost.release(); tile_order.release(); tile_order_tag = 0;
-            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum};
+            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &pt_flags, &pt_index, &pt_totals, &pt_carry};
             for (DBuf* x : b) x->release();
             for (int r = 0; r < sr::kShaftRounds; ++r) { rlist[r].release(); rstate[r].release(); rcount[r].release(); rcand[r].release(); }
             if (stream) (void)hipStreamDestroy(stream);
@@ -186,6 +192,7 @@ struct sr_scene {
 namespace {
 
 const int kMaxShaftSamples = 1024;       // area-light samples the shaft path takes (in chunks of 128); more: one lane per hit point (k_shadow)
+const long long kMaxPathTable = 256ll << 20;   // bytes of the path tracer's random table (include/softray.h SR_F_PATH_TRACING)
 const int kMaxTreeDepth = 62;            // (depth + 2) stack levels x 256 lanes x 4 B = 64 KB of LDS per workgroup
 
 int use_device(sr_scene* s) {
@@ -298,6 +305,16 @@ bool row_owned(const sr_frame* f, int r) {
     return ((r / f->strip_rows) % f->strip_count) == f->strip_index;
 }
 
+// SR_F_PATH_TRACING: the combinations the reference would allow and the library does not build (include/softray.h)
+int check_path_tracing(const sr_frame* f) {
+    if (!(f->flags & SR_F_PATH_TRACING)) return SR_OK;
+    if (f->flags & SR_F_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "path tracing together with shadows (dynamic or static) is not supported");
+    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "path tracing together with mirror bounces (max_bounces > 0) is not supported");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "path tracing is not built into the one-kernel renderer (SR_F_SINGLE_KERNEL)");
+    if (f->strip_count > 1) return fail(SR_ERR_UNSUPPORTED, "path tracing with row strips: a rank would need the hit counts of rows it does not render");
+    return SR_OK;
+}
+
 int validate_frame(const sr_frame* f) {
     if (!f) return fail(SR_ERR_INVALID_ARG, "frame is NULL");
     if (f->width <= 0 || f->height <= 0) return fail(SR_ERR_INVALID_ARG, "surface size must be positive");
@@ -308,7 +325,7 @@ int validate_frame(const sr_frame* f) {
     if ((long long)f->width * f->sub_pixel_res > (1ll << 24) || (long long)f->height > (1ll << 24)) return fail(SR_ERR_INVALID_ARG, "surface too large");
     if (f->max_bounces < 0 || f->max_bounces > 16 || !(f->reflectivity >= 0.0 && f->reflectivity <= 1.0))
         return fail(SR_ERR_INVALID_ARG, "max_bounces must be 0..16 and reflectivity 0..1");
-    return SR_OK;
+    return check_path_tracing(f);
 }
 
 void clamp_rows(const sr_frame* f, int& a, int& b) {                  // Renderer.cs:1652-1653
@@ -407,8 +424,9 @@ int next_events(sr_scene* s, int k, hipEvent_t& a, hipEvent_t& b) {
 int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats) {
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
-    int rc = prepare_frame(s, f, fc);
+    int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
     if (rc) return rc;
+    if ((rc = prepare_frame(s, f, fc))) return rc;
     if ((rc = sync_geometry(s, (uint32_t)f->trace_mode))) return rc;
     if (fc.num_rows == 0) return SR_OK;
     // ---- frames of one scene run in submission order whatever streams they are given: the scene's scratch (hit queues, candidate
@@ -654,11 +672,49 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         if (!s->fork) SR_HIP(hipEventCreateWithFlags(&s->fork, hipEventDisableTiming));
         SR_HIP(hipEventRecord(s->fork, stream));                    // the halves start after the caller's earlier work
     }
+    // ---- path tracing: the row blocks that each restart Random(random_seed) (Renderer.cs:1655-1666) and the table of its draws ----
+    const bool path = (f->flags & SR_F_PATH_TRACING) != 0;
+    int pt_block_height = 0, pt_blocks = 0;
+    if (path) {
+        const long long conc = f->concurrency > 0 ? f->concurrency : 4;
+        pt_block_height = (int)(((long long)fc.num_rows - 1 + conc) / conc);
+        pt_blocks = (fc.num_rows + pt_block_height - 1) / pt_block_height;
+        const long long block_samples = (long long)pt_block_height * fc.width * n2;
+        if (block_samples * 12 > kMaxPathTable)
+            return fail(SR_ERR_UNSUPPORTED, "path tracing: the random table of the largest row block (12 bytes per sample) exceeds 256 MiB; raise concurrency or render row ranges");
+        if (!s->d_pt_table.p || s->pt_table_seed != f->random_seed || s->pt_table_samples < (size_t)block_samples) {
+            if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still read the old table
+            std::vector<int32_t> ints((size_t)block_samples * 3);
+            sr::NetRandom random(f->random_seed);
+            for (int32_t& v : ints) v = random.next();
+            s->pt_table_samples = 0;
+            SR_HIP(s->d_pt_table.upload(ints));
+            s->pt_table_seed = f->random_seed;
+            s->pt_table_samples = (size_t)block_samples;
+        }
+    }
+    const bool path_walk = path && f->trace_mode == SR_MODE_BVH;
     for (auto& sc : s->scratch) sc.used_last_frame = false;
     for (int h = 0; h < halves; ++h) {
         sr_scene::BandScratch& B = s->scratch[h];
         B.used_last_frame = true;
-        if (shadows || bounce_pipe) SR_HIP(B.hits.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
+        if (shadows || bounce_pipe || path) SR_HIP(B.hits.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
+        if (path) {
+            SR_HIP(B.hits2.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
+            SR_HIP(B.pt_flags.reserve((size_t)band_samples));
+            SR_HIP(B.pt_index.reserve((size_t)band_samples * 4));
+            SR_HIP(B.pt_totals.reserve(((size_t)band_samples / (size_t)sr::pipeline_pt_chunk() + 2) * 4));
+            SR_HIP(B.pt_carry.reserve((size_t)pt_blocks * 4));
+        }
+        if (path_walk) {
+            // the second rays of a SR_MODE_BVH frame take the incoherent-ray route of the mirror extension: the same scratch
+            SR_HIP(B.bounce_prep.reserve((size_t)band_samples * 64));
+            SR_HIP(B.bounce_res.reserve((size_t)band_samples * 16));
+            const long long deep = std::max(3 * (long long)s->b4_depth + 2, (long long)s->bvh.depth + 2) - sr::pipeline_bounce_lds_levels();
+            if (deep > 0) SR_HIP(B.bounce_stack.reserve((size_t)deep * (size_t)s->num_cus * 8 * 256 * 4));
+            SR_HIP(B.ray_sort.reserve((size_t)band_samples * 4 * 4));
+            SR_HIP(B.ray_sort_temp.reserve(sr::ray_sort_temp_bytes((unsigned)band_samples)));
+        }
         if (bounce_pipe) {
             // level colours are indexed like the sample buffer: the frame (or compact strip buffer) for one sample per pixel, band-local otherwise
             const size_t idx_space = n2 == 1 ? (size_t)(f->strip_count > 0 ? fc.num_rows : fc.height) * fc.width : (size_t)band_samples;
@@ -726,16 +782,23 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.pixels = d_pixels;
         P.samples = (uint32_t*)B.samples.p;
         P.hits = B.hits.p;
-        P.hits2 = bounce_pipe ? B.hits2.p : nullptr;
-        P.ray_sort_buf = bounce_pipe ? (unsigned int*)B.ray_sort.p : nullptr;
-        P.ray_sort_temp = bounce_pipe ? B.ray_sort_temp.p : nullptr;
-        P.ray_sort_temp_bytes = bounce_pipe ? sr::ray_sort_temp_bytes((unsigned)band_samples) : 0;
+        P.hits2 = (bounce_pipe || path) ? B.hits2.p : nullptr;
+        P.pt_flags = path ? (uint8_t*)B.pt_flags.p : nullptr;
+        P.pt_index = path ? (uint32_t*)B.pt_index.p : nullptr;
+        P.pt_totals = path ? (uint32_t*)B.pt_totals.p : nullptr;
+        P.pt_carry = path ? (uint32_t*)B.pt_carry.p : nullptr;
+        P.pt_table = path ? (const int32_t*)s->d_pt_table.p : nullptr;
+        P.pt_block_height = pt_block_height;
+        P.pt_blocks = pt_blocks;
+        P.ray_sort_buf = (bounce_pipe || path_walk) ? (unsigned int*)B.ray_sort.p : nullptr;
+        P.ray_sort_temp = (bounce_pipe || path_walk) ? B.ray_sort_temp.p : nullptr;
+        P.ray_sort_temp_bytes = (bounce_pipe || path_walk) ? sr::ray_sort_temp_bytes((unsigned)band_samples) : 0;
         P.bounce_levels = bounce_pipe ? (uint32_t*)B.bounce_levels.p : nullptr;
         P.bounce_nlev = bounce_pipe ? (uint8_t*)B.bounce_nlev.p : nullptr;
-        P.bounce_prep = bounce_pipe ? B.bounce_prep.p : nullptr;
-        P.bounce_res = bounce_pipe ? B.bounce_res.p : nullptr;
-        P.bounce_stack = bounce_pipe ? (int32_t*)B.bounce_stack.p : nullptr;
-        P.bounce_stack_bytes = bounce_pipe ? B.bounce_stack.cap : 0;
+        P.bounce_prep = (bounce_pipe || path_walk) ? B.bounce_prep.p : nullptr;
+        P.bounce_res = (bounce_pipe || path_walk) ? B.bounce_res.p : nullptr;
+        P.bounce_stack = (bounce_pipe || path_walk) ? (int32_t*)B.bounce_stack.p : nullptr;
+        P.bounce_stack_bytes = (bounce_pipe || path_walk) ? B.bounce_stack.cap : 0;
         P.counters = (unsigned int*)B.counters.p;
         P.tile_cost = order_tiles ? (unsigned int*)B.tile_cost.p : nullptr;
         P.tile_order = order_tiles ? (unsigned int*)B.tile_order.p : nullptr;
@@ -854,7 +917,7 @@ hipError_t copy_runs(const std::vector<StripRun>& runs, int n, int width, const 
 }
 
 // frames that cannot be split (one global fill order) are rendered whole by the first part
-bool multi_splittable(const sr_frame* f) { return !((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) && f->strip_count <= 0; }
+bool multi_splittable(const sr_frame* f) { return !((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) && !(f->flags & SR_F_PATH_TRACING) && f->strip_count <= 0; }
 
 // a part of a multi-device scene takes the first part's model by reference: counts, box and flags here, the arrays stay with `src`
 // (sync_geometry uploads from them); nothing of the size of the model is copied on the host
@@ -960,7 +1023,7 @@ void sr_destroy(sr_scene* s) {
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab,
-                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_pixels, &s->d_aa, &s->d_stats};
+                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_pt_table, &s->d_pixels, &s->d_aa, &s->d_stats};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
         for (auto& t : s->tables) { t.dev.release(); if (t.host) (void)hipHostFree(t.host); if (t.used) (void)hipEventDestroy(t.used); if (t.ready) (void)hipEventDestroy(t.ready); }

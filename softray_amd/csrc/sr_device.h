@@ -40,7 +40,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_COUNT = 12 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_COUNT = 13 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -85,6 +85,13 @@ struct PipelineLaunch {
     void*         bounce_res;   // device [band samples] x 16 B: nearest hit of every such ray (k_bounce_walk)
     int32_t*      bounce_stack; // device: the part of k_bounce_walk's per-lane stacks that does not live in LDS ([level][lane])
     size_t        bounce_stack_bytes;
+    // path tracing (SR_F_PATH_TRACING; all nullptr / 0 otherwise).  The second rays are queued in hits2
+    uint8_t*      pt_flags;     // device [band samples]: hit flag per scan position
+    uint32_t*     pt_index;     // device [band samples]: hits before the position inside its chunk of pipeline_pt_chunk() positions
+    uint32_t*     pt_totals;    // device [chunks + 1]: hits before each chunk, the band's hit count behind them
+    uint32_t*     pt_carry;     // device [pt_blocks]: hits of every row block in the bands rendered so far (zeroed by launch_pipeline)
+    const int32_t* pt_table;    // device: InternalSample() ints of Random(random_seed), 3 per sample of the largest row block
+    int32_t       pt_block_height, pt_blocks;   // rows per row block and their number (Renderer.cs:1655-1666)
     void*         static_hits;  // device HitRec[min(band samples, 128^3)]: generators of a static-shadow frame
     unsigned long long* static_claim; // device [128^3]: smallest order key that asked for an empty cell
     int32_t       static_concurrency; // rayTraceConcurrency of the frame
@@ -140,6 +147,7 @@ size_t pipeline_static_cells();
 int pipeline_round_cap(int round);
 int pipeline_round_cap_max(int round);
 int pipeline_bounce_lds_levels();      // stack levels per lane k_bounce_walk keeps in LDS (deeper ones live in PipelineLaunch::bounce_stack)
+int pipeline_pt_chunk();               // scan positions per workgroup of the path tracer's hit-index scan
 size_t pipeline_round_state_bytes();
 size_t pipeline_counter_bytes();
 size_t pipeline_tile_items(int width, int rows, int n2);

@@ -3184,6 +3184,216 @@ __global__ __launch_bounds__(256) void k_fold(FrameConst fc, long long nsamples,
 }
 
 // --------------------------------------------------------------------------------------------------
+// Path tracing (SR_F_PATH_TRACING; PathTracingMethod.cs, Renderer.cs:1613-1618, 1700-1829).  Every camera sample that hits fires one
+// second ray whose direction is made of three NextDouble() of the row block's Random: the reference draws them in scan order (row,
+// column, subX, subY) for the samples that hit, so sample number k of its block -- counting hits only -- uses draws 3k .. 3k + 2.
+//   k_primary         as for a shadowed frame: shaded sample colours + the compacted queue of hit records (any order)
+//   k_pt_mark         hit flag per scan position of the band (the sample buffer IS in scan order: the frame's rows for one sample
+//                     per pixel, band-local [row][col][sub-sample] otherwise)
+//   k_pt_scan         exclusive prefix sum of the flags inside chunks of kPtChunk positions (one workgroup per chunk: __ballot +
+//                     __popcll within a wave, the four wave counts through LDS) + the chunk's total
+//   k_pt_scan_totals  one workgroup: exclusive prefix sum of the chunk totals, in place; the grand total behind them
+//   k_pt_prep         lane = queued hit: k = hits of its block in earlier bands (carry) + prefix(position) - prefix(first position of
+//                     the block in this band), the three draws from the table, direction, offset origin -> the second ray's queue
+//   k_pt_carry        adds the band's hits to the blocks' carries (after k_pt_prep has read them)
+//   k_pt_finish       lane = second ray: nearest hit through the same geometry in the frame's trace mode (root_intersect, as the
+//                     camera ray of a per-lane primary pass), shading, incoming * (n . d) + own colour -> the sample
+// Nothing depends on the order of the hit queue or on an atomic's arrival order: the frame is deterministic.
+// --------------------------------------------------------------------------------------------------
+constexpr int kPtChunk = 4096;           // scan positions per workgroup of k_pt_scan (16 passes of 256)
+
+struct PtBand {
+    uint32_t n;              // samples (= scan positions) of the band
+    uint32_t row_samples;    // width * sub_pixel_res^2
+    uint32_t sample_base;    // sample-buffer index of scan position 0
+    int32_t  row_begin;      // the band's first row, counted from the frame's first rendered row
+    int32_t  block_height;   // rows per row block (Renderer.cs:1661)
+};
+
+// hits before scan position p of the band (p == n: all of them)
+__device__ __forceinline__ uint32_t pt_before(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ totals, uint32_t n, uint32_t p) {
+    return p < n ? idx[p] + totals[p / (uint32_t)kPtChunk] : totals[(n + (uint32_t)kPtChunk - 1u) / (uint32_t)kPtChunk];
+}
+
+__global__ __launch_bounds__(256) void k_pt_mark(PtBand band, const HitRec* __restrict__ hits, const unsigned int* __restrict__ count, uint8_t* __restrict__ flags) {
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    for (unsigned int r = blockIdx.x * 256u + threadIdx.x; r < total; r += stride) {
+        const uint32_t p = hits[r].sample - band.sample_base;
+        if (p < band.n) flags[p] = 1;
+    }
+}
+
+// (LDS: 32 bytes -- the four wave counts of a pass, double-buffered so that one barrier per pass is enough)
+__global__ __launch_bounds__(256) void k_pt_scan(const uint8_t* __restrict__ flags, uint32_t n, uint32_t* __restrict__ idx, uint32_t* __restrict__ totals) {
+    __shared__ uint32_t s_wave[2][4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * (uint32_t)kPtChunk;
+    uint32_t running = 0;
+    for (int pass = 0; pass < kPtChunk / 256; ++pass) {
+        const uint32_t p = p0 + (uint32_t)pass * 256u + threadIdx.x;
+        const bool f = p < n && flags[p] != 0;
+        const unsigned long long m = __ballot(f);
+        if (lane == 0u) s_wave[pass & 1][wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; ++w) {
+            const uint32_t c = s_wave[pass & 1][w];
+            if (w < wave) before += c;
+            all += c;
+        }
+        if (p < n) idx[p] = running + before + (uint32_t)__popcll(m & lanemask_lt());
+        running += all;
+    }
+    if (threadIdx.x == 0u) totals[blockIdx.x] = running;
+}
+
+// (LDS: 1 KB)
+__global__ __launch_bounds__(256) void k_pt_scan_totals(uint32_t* __restrict__ totals, uint32_t chunks) {
+    __shared__ uint32_t s_sum[256];
+    const uint32_t per = (chunks + 255u) / 256u;
+    const uint32_t a = min(threadIdx.x * per, chunks), b = min(a + per, chunks);
+    uint32_t sum = 0;
+    for (uint32_t i = a; i < b; ++i) sum += totals[i];
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    uint32_t base = 0;
+    for (uint32_t t = 0; t < threadIdx.x; ++t) base += s_sum[t];
+    for (uint32_t i = a; i < b; ++i) { const uint32_t v = totals[i]; totals[i] = base; base += v; }
+    if (threadIdx.x == 255u) totals[chunks] = base;
+}
+
+__global__ __launch_bounds__(256) void k_pt_prep(PtBand band, const HitRec* __restrict__ hits, const unsigned int* __restrict__ count,
+                                                 const uint32_t* __restrict__ idx, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ carry,
+                                                 const int32_t* __restrict__ table, HitRec* __restrict__ rays) {
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    for (unsigned int r = blockIdx.x * 256u + threadIdx.x; r < total; r += stride) {
+        const HitRec h = hits[r];
+        const uint32_t p = h.sample - band.sample_base;
+        const int32_t block = (band.row_begin + (int32_t)(p / band.row_samples)) / band.block_height;
+        const int32_t first = block * band.block_height - band.row_begin;            // the block's first row, band-local (< 0: an earlier band)
+        const uint32_t p0 = first > 0 ? (uint32_t)first * band.row_samples : 0u;
+        const size_t k = (size_t)carry[block] + (size_t)(pt_before(idx, totals, band.n, p) - pt_before(idx, totals, band.n, p0));
+        // RandomRayInHemisphere (PathTracingMethod.cs:98-103); NextDouble() = InternalSample() * (1.0 / int.MaxValue)
+        const double ux = table[3 * k] * (1.0 / 2147483647.0), uy = table[3 * k + 1] * (1.0 / 2147483647.0), uz = table[3 * k + 2] * (1.0 / 2147483647.0);
+        const D3 n = mk(h.nrm[0], h.nrm[1], h.nrm[2]);
+        D3 d = mk(ux * 2 - 1, uy * 2 - 1, uz * 2 - 1);
+        if (dot(d, n) < 0.0) d = neg(d);
+        d = normalise(d);
+        const D3 org = mk(h.pos[0], h.pos[1], h.pos[2]) + n * 0.001;                 // raySurfaceOffset
+        HitRec o;
+        o.pos[0] = org.x; o.pos[1] = org.y; o.pos[2] = org.z;
+        o.nrm[0] = d.x; o.nrm[1] = d.y; o.nrm[2] = d.z;
+        o.sample = h.sample;
+        o.pad[0] = o.pad[1] = o.pad[2] = 0;
+        rays[r] = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pt_carry(PtBand band, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ totals, uint32_t* __restrict__ carry,
+                                                  int nblocks) {
+    const int b = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (b >= nblocks) return;
+    const int rows = (int)(band.n / band.row_samples);
+    const int r0 = max(b * band.block_height - band.row_begin, 0), r1 = min((b + 1) * band.block_height - band.row_begin, rows);
+    if (r1 > r0) carry[b] += pt_before(idx, totals, band.n, (uint32_t)r1 * band.row_samples) - pt_before(idx, totals, band.n, (uint32_t)r0 * band.row_samples);
+}
+
+// (LDS: the per-lane traversal stacks of root_intersect, stack levels x 256 lanes x 4 bytes, as k_shadow)
+template <int MODE, bool EXTRA, bool STATS>
+__global__ __launch_bounds__(256) void k_pt_finish(DevScene sc, FrameConst fc, const HitRec* __restrict__ hits, const HitRec* __restrict__ rays,
+                                                   const unsigned int* __restrict__ count, uint32_t* __restrict__ samples, unsigned long long* stats) {
+    const int tid = threadIdx.x;
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    Ctr sec = {0, 0, 0, 0};
+    for (unsigned int r = blockIdx.x * 256u + tid; r < total; r += stride) {
+        const HitRec q = rays[r];
+        const D3 s = mk(q.pos[0], q.pos[1], q.pos[2]), d = mk(q.nrm[0], q.nrm[1], q.nrm[2]);
+        Hit h;
+        sec.rays++;
+        const bool ok = root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, s, d, h, sec);
+        uint32_t incoming = 0u;                                                       // Color.Black
+        if (ok) incoming = (fc.flags & 1u) ? shade(fc, h.pos, h.nrm, h.color) : h.color;
+        const D3 n = mk(hits[r].nrm[0], hits[r].nrm[1], hits[r].nrm[2]);
+        const double frac = dot(n, d);                                                // BRDF: surfaceNormal.DotProduct(newRayDir)
+        const uint32_t own = samples[q.sample];
+        // new Color(uint): bytes / 255.0; incoming * frac + emission; Normalise when a channel exceeds 1.0; ToARGB truncates
+        double cr = (double)((incoming >> 16) & 0xffu) / 255.0 * frac + (double)((own >> 16) & 0xffu) / 255.0;
+        double cg = (double)((incoming >> 8) & 0xffu) / 255.0 * frac + (double)((own >> 8) & 0xffu) / 255.0;
+        double cb = (double)(incoming & 0xffu) / 255.0 * frac + (double)(own & 0xffu) / 255.0;
+        if (cr > 1.0 || cg > 1.0 || cb > 1.0) {
+            const double inv = 1.0 / sqrt(cr * cr + cg * cg + cb * cb);
+            cr *= inv; cg *= inv; cb *= inv;
+        }
+        samples[q.sample] = (255u << 24) + (to_byte(cr * 255.0) << 16) + (to_byte(cg * 255.0) << 8) + to_byte(cb * 255.0);
+    }
+    if (STATS) {
+        uint32_t a = wave_sum(sec.rays), b = wave_sum(sec.geom), c2 = wave_sum(sec.nodes), d2 = wave_sum(sec.leaves);
+        if ((tid & 63) == 0) { stat_add(&stats[4], a); stat_add(&stats[5], b); stat_add(&stats[6], c2); stat_add(&stats[7], d2); }
+    }
+}
+
+// SR_MODE_BVH: the second rays are incoherent rays on the own BVH -- the workload of the mirror extension -- and take its route:
+// k_bounce_prep (clip to the root box), k_bounce_walk (persistent lanes on the four-wide tree), both exactly as a mirror level
+// runs them, in the (origin cell, direction octant) order of ray_sort; this kernel is k_bounce_finish's hit selection (extra
+// geometry from the unclipped origin first, strict '<', then the walk's triangle) followed by k_pt_finish's colour step.
+// lane = ray in walk order; `order` (nullable) maps it to its entry of the hit / ray queues.  No LDS.
+template <bool EXTRA, bool STATS>
+__global__ __launch_bounds__(256) void k_pt_finish_walked(DevScene sc, FrameConst fc, const HitRec* __restrict__ hits, const HitRec* __restrict__ rays,
+                                                          const unsigned int* __restrict__ count, const unsigned int* __restrict__ order,
+                                                          const BounceRay* __restrict__ prep, const BounceHit* __restrict__ res,
+                                                          uint32_t* __restrict__ samples, unsigned long long* stats) {
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    uint32_t n_geom = 0;
+    for (unsigned int r = blockIdx.x * 256u + threadIdx.x; r < total; r += stride) {
+        const BounceRay p = prep[r];
+        const BounceHit h = res[r];
+        const unsigned int qi = order ? order[r] : r;
+        const D3 s = mk(p.s[0], p.s[1], p.s[2]), d = mk(p.d[0], p.d[1], p.d[2]);
+        double ex_t = DBL_MAX;
+        D3 hpos = mk(0, 0, 0), hnrm = mk(0, 0, 0);
+        uint32_t hcol = 0;
+        bool hit = false;
+        if (EXTRA) {
+            const D3 s0 = mk(rays[qi].pos[0], rays[qi].pos[1], rays[qi].pos[2]);
+            for (int i = 0; i < sc.nextra; ++i) {
+                const Rec128* e = &sc.extra[i];
+                double t; D3 pos, nrm;
+                uint32_t tests;
+                const bool ok = extra_hit(e, s0, d, t, pos, nrm, tests);
+                n_geom += tests;
+                if (ok && t < ex_t) { ex_t = t; hpos = pos; hnrm = nrm; hcol = e->color; hit = true; }
+            }
+        }
+        if (p.offset >= 0.0 && h.bestK >= 0 && (h.best + p.offset) < ex_t) {
+            const Rec128* t = &sc.btris[h.bestK];
+            hit = true;
+            hpos = s + d * h.best;
+            hnrm = mk(t->p[0], t->p[1], t->p[2]);
+            hcol = t->color;
+        }
+        uint32_t incoming = 0u;
+        if (hit) incoming = (fc.flags & 1u) ? shade(fc, hpos, hnrm, hcol) : hcol;
+        const D3 n = mk(hits[qi].nrm[0], hits[qi].nrm[1], hits[qi].nrm[2]);
+        const double frac = dot(n, d);
+        const uint32_t own = samples[p.sample];
+        double cr = (double)((incoming >> 16) & 0xffu) / 255.0 * frac + (double)((own >> 16) & 0xffu) / 255.0;
+        double cg = (double)((incoming >> 8) & 0xffu) / 255.0 * frac + (double)((own >> 8) & 0xffu) / 255.0;
+        double cb = (double)(incoming & 0xffu) / 255.0 * frac + (double)(own & 0xffu) / 255.0;
+        if (cr > 1.0 || cg > 1.0 || cb > 1.0) {
+            const double inv = 1.0 / sqrt(cr * cr + cg * cg + cb * cb);
+            cr *= inv; cg *= inv; cb *= inv;
+        }
+        samples[p.sample] = (255u << 24) + (to_byte(cr * 255.0) << 16) + (to_byte(cg * 255.0) << 8) + to_byte(cb * 255.0);
+    }
+    if (STATS && EXTRA) {
+        const uint32_t b = wave_sum(n_geom);
+        if ((threadIdx.x & 63) == 0) { stat_add(&stats[5], b); stat_add(&stats[21], b); }
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // rayTraceShadowsStatic (ShadowMethod.cs:75-83,103-108, Texture3DCache.cs:95-135): the light fraction of a surface
 // point is looked up in a 128^3 byte texture over the unit cube; an empty cell is generated by whoever asks first.
 // The reference's worker tasks race for that; the CPU checker pins a deterministic order against the reference's two
@@ -3659,10 +3869,89 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
     return hipSuccess;
 }
 
+// the path-tracing stage of one row band (see k_pt_mark): counters [0] = the band's hit count, left by k_primary
+template <int MODE, bool EXTRA>
+static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples) {
+    const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
+    hipError_t e;
+    hipEvent_t e0, e1;
+    pipe_events(L, K_PATHTRACE, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    PtBand band;
+    band.n = (uint32_t)((long long)row_count * L.fc.width * n2);
+    band.row_samples = (uint32_t)(L.fc.width * n2);
+    // one sample per pixel: the sample buffer is the frame (image rows, or the compact rows of a one-strip frame)
+    band.sample_base = n2 == 1 ? (uint32_t)((long long)((L.fc.strip_count > 0 ? 0 : L.fc.first_row) + row_begin) * L.fc.width) : 0u;
+    band.row_begin = row_begin;
+    band.block_height = L.pt_block_height;
+    const uint32_t chunks = (band.n + (uint32_t)kPtChunk - 1u) / (uint32_t)kPtChunk;
+    const unsigned blocks = (unsigned)std::min<long long>(((long long)band.n + 255) / 256, (long long)L.persistent_blocks);
+    const HitRec* hits = (const HitRec*)L.hits;
+    HitRec* rays = (HitRec*)L.hits2;
+    if ((e = hipMemsetAsync(L.pt_flags, 0, band.n, L.stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_pt_mark, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, L.pt_flags);
+    hipLaunchKernelGGL(k_pt_scan, dim3(chunks), dim3(256), 0, L.stream, (const uint8_t*)L.pt_flags, band.n, L.pt_index, L.pt_totals);
+    hipLaunchKernelGGL(k_pt_scan_totals, dim3(1), dim3(256), 0, L.stream, L.pt_totals, chunks);
+    hipLaunchKernelGGL(k_pt_prep, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                       (const uint32_t*)L.pt_carry, L.pt_table, rays);
+    hipLaunchKernelGGL(k_pt_carry, dim3((unsigned)((L.pt_blocks + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                       L.pt_carry, (int)L.pt_blocks);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
+    if constexpr (MODE == MODE_BVH) {
+        // the second rays on the incoherent-ray route of the mirror extension (see k_pt_finish_walked); SR_DBG_KERNEL_SWITCH 33 keeps
+        // the per-lane form below (same pixels: cross-check)
+        if (L.bounce_prep && L.bounce_res && L.fc.debug != 33) {
+            const bool wide = L.sc.b4 != nullptr && !L.bvh2_packets;
+            const size_t wlds = (size_t)(wide ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE_BVH)) * 256 * 4;
+            const unsigned int* order = nullptr;
+            if (L.ray_sort_buf && L.fc.debug != 31) {
+                const unsigned cap = band.n;
+                unsigned int* b = L.ray_sort_buf;
+                if ((e = ray_sort(rays, L.counters, cap, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
+                order = b + 3 * (size_t)cap;
+            }
+            BounceRay* prep = (BounceRay*)L.bounce_prep;
+            BounceHit* res = (BounceHit*)L.bounce_res;
+            hipLaunchKernelGGL(k_bounce_prep, dim3(blocks), dim3(256), 0, L.stream, L.sc, (const HitRec*)rays, L.counters, order, prep, res);
+            const int levels_all = (int)(wlds / (256 * 4));
+            int lds_levels = std::max(1, std::min(kBounceLdsLevels, levels_all));
+            if ((size_t)(levels_all - lds_levels) * (size_t)blocks * 256 * 4 > L.bounce_stack_bytes || !L.bounce_stack) lds_levels = levels_all;
+            const auto walk = [&](auto kern) {                         // counters [2]: the walk's work head (zero since the band's reset)
+                hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), (size_t)lds_levels * 256 * 4, L.stream, L.sc, (const BounceRay*)prep, L.counters, L.counters + 2, res, sec_stats,
+                                   kWalkRefillAt, L.bounce_stack, lds_levels, kWalkNodeBurst, kWalkLeafBurst);
+            };
+            if (wide) { if (sec_stats) walk(k_bounce_walk<true, true>); else walk(k_bounce_walk<false, true>); }
+            else { if (sec_stats) walk(k_bounce_walk<true, false>); else walk(k_bounce_walk<false, false>); }
+            const auto finw = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, L.sc, L.fc, hits, (const HitRec*)rays, L.counters, order, (const BounceRay*)prep,
+                                   (const BounceHit*)res, samples, sec_stats);
+            };
+            if (sec_stats) finw(k_pt_finish_walked<EXTRA, true>); else finw(k_pt_finish_walked<EXTRA, false>);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+            return hipSuccess;
+        }
+    }
+    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+    const auto fin = [&](auto kern, unsigned long long* stats) {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, hits, (const HitRec*)rays, L.counters, samples, stats);
+    };
+    if (sec_stats) fin(k_pt_finish<MODE, EXTRA, true>, sec_stats); else fin(k_pt_finish<MODE, EXTRA, false>, nullptr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
 template <int MODE, bool EXTRA>
 static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     const bool shadows = (L.fc.flags & 2u) != 0;
+    const bool path = (L.fc.flags & kFlagPathTracing) != 0;          // (sr_api.cpp: never together with shadows or mirror bounces)
+    if (path) {
+        hipError_t e = hipMemsetAsync(L.pt_carry, 0, (size_t)L.pt_blocks * sizeof(uint32_t), L.stream);
+        if (e != hipSuccess) return e;
+    }
     // rows are processed in bands so that the hit queue / sample buffer stay within their allocation
     for (int row_begin = L.row_first; row_begin < L.row_limit; row_begin += L.band_rows) {
         int row_count = std::min(L.band_rows, L.row_limit - row_begin);
@@ -3676,6 +3965,13 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
         // the shaft path of a dynamic-shadow frame reads the hit queue tile by tile (k_shaft_pkt): 64-aligned entries
         const bool shaft_frame = (MODE != MODE_BVH && L.shadows_on_bvh) ? shaft_path<MODE_BVH>(L) : shaft_path<MODE>(L);
         const int pad_tiles = (shadows && !(L.fc.flags & 32u) && L.fc.max_bounces == 0 && shaft_frame) ? 1 : 0;
+        if (path) {
+            // the primary pass of a shadowed frame is what the path tracer needs: shaded sample colours + the compacted hit queue
+            PipelineLaunch Q = L;
+            Q.fc.flags |= 2u;
+            e = L.fc.sub_pixel_res > 1 ? launch_primary_s<MODE, EXTRA, true>(Q, row_begin, row_count, samples, 0)
+                                       : launch_primary_s<MODE, EXTRA, false>(Q, row_begin, row_count, samples, 0);
+        } else
         e = L.fc.sub_pixel_res > 1 ? launch_primary_s<MODE, EXTRA, true>(L, row_begin, row_count, samples, pad_tiles)
                                    : launch_primary_s<MODE, EXTRA, false>(L, row_begin, row_count, samples, pad_tiles);
         if (e == hipSuccess && pad_tiles) {
@@ -3798,6 +4094,8 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
                 hipLaunchKernelGGL(k_accum_finish, dim3(blocks), dim3(256), 0, L.stream, T.fc, (const HitRec*)L.hits, L.counters, samples, S);
                 if ((e = hipGetLastError()) != hipSuccess) return e;
             }
+        } else if (path) {
+            if ((e = launch_pathtrace_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
         }
         if (n2 > 1) {
             e0 = e1 = nullptr;
@@ -3832,6 +4130,7 @@ int pipeline_round_cap(int round) { return kRoundCap[round]; }   // default list
 // registers of one wave; the later rounds of the default path (k_shaft_coop, k_shadow_cls) read and write it in chunks
 int pipeline_round_cap_max(int round) { return round == 0 ? 64 : 1024; }
 int pipeline_bounce_lds_levels() { return kBounceLdsLevels; }
+int pipeline_pt_chunk() { return kPtChunk; }
 size_t pipeline_round_state_bytes() { return sizeof(RoundState); }
 size_t pipeline_counter_bytes() { return (size_t)kCounterWords * sizeof(unsigned int); }
 // 8x8-pixel tiles (one wave's work items) of the padded super-tile grid of a band, all sub-samples

@@ -6,15 +6,16 @@ parity tests read like Engine3D-Tests/Raytrace/RendererTests.cs.  Nothing is com
 ray is traced by libsoftray_hip.so on the MI355X; this module only copies public fields into an
 `sr_frame` exactly the way Renderer.RaytraceGeometry does (Renderer.cs:1501-1687).
 
-Out of scope: the scan-line rasteriser, static-shadow / AO / light-field caches,
-path tracing and voxels.  Asking for them raises NotImplementedError instead of silently differing.
+Out of scope: the scan-line rasteriser, AO / light-field caches and voxels.  Asking
+for them raises NotImplementedError instead of silently differing; so does path tracing together
+with shadows (rayTracePathTracing alone runs on the device: SR_F_PATH_TRACING).
 """
 import math
 
 import numpy as np
 
 from . import _lib
-from ._lib import (F_FOCAL_BLUR, F_POINT_LIGHT, F_SHADING, F_SHADOWS, F_SPECULAR, F_STATIC_SHADOWS, MODE_BRUTE, MODE_BVH,
+from ._lib import (F_FOCAL_BLUR, F_PATH_TRACING, F_POINT_LIGHT, F_SHADING, F_SHADOWS, F_SPECULAR, F_STATIC_SHADOWS, MODE_BRUTE, MODE_BVH,
                    MODE_REF_TREE, Frame)
 from .scene import GpuScene, default_fov_depth, instance_matrices
 
@@ -245,7 +246,8 @@ class Renderer:
         self.rayTraceFocalBlur = True
         self.rayTraceFocalDepth = 1.5
         self.rayTraceFocalBlurStrength = 10.0
-        self.rayTraceConcurrency = 4          # kept for API compatibility; the GPU renders exact row ranges
+        self.rayTraceConcurrency = 4          # the GPU renders exact row ranges; the row blocks still fix the static shadow cache's
+                                              # fill order and where path tracing restarts its random sequence
         self.rayTraceSubPixelRes = 1
         self.rayTraceRandomSeed = 1234567890
         self.rayTraceStartRow = 0
@@ -432,9 +434,11 @@ class Renderer:
             raise NotImplementedError("the scan-line rasteriser is out of scope of the MI355X hot path (SURVEY.md 2, row 21)")
         if not self._PinModel():
             return                                                 # silently, Renderer.cs:736-739
-        for name in ("rayTraceAmbientOcclusion", "rayTraceLightField", "rayTracePathTracing", "rayTraceVoxels"):
+        for name in ("rayTraceAmbientOcclusion", "rayTraceLightField", "rayTraceVoxels"):
             if getattr(self, name):
                 raise NotImplementedError("%s is out of scope (RNG-order / racy-cache dependent in the reference; SURVEY.md 2)" % name)
+        if self.rayTracePathTracing and self.rayTraceShadows:
+            raise NotImplementedError("rayTracePathTracing together with rayTraceShadows is out of scope (include/softray.h SR_F_PATH_TRACING)")
         for instance in self.Instances:
             instance.FieldOfViewDepth = self._fieldOfViewDepth     # Renderer.cs:749
             self._RaytraceGeometry(instance)
@@ -484,6 +488,8 @@ class Renderer:
             flags |= F_SHADOWS
             if self.rayTraceShadowsStatic:
                 flags |= F_STATIC_SHADOWS                         # Renderer.cs:1625; cache lives in the GpuScene
+        if self.rayTracePathTracing:
+            flags |= F_PATH_TRACING                           # Renderer.cs:1613-1618; reads random_seed and concurrency
         if self.rayTraceFocalBlur:
             flags |= F_FOCAL_BLUR
         if self.pointLighting:
@@ -509,7 +515,7 @@ class Renderer:
         for i, v in enumerate(self.positionalLight_pos):
             f.light_pos_view[i] = v
         f.max_bounces = self.gpuMaxBounces
-        f.concurrency = self.rayTraceConcurrency                 # fixes the static-shadow cache fill order
+        f.concurrency = self.rayTraceConcurrency                 # the static-shadow cache's fill order, the path tracer's row blocks
         f.reflectivity = self.gpuReflectivity
         f.area_light_offsets = None
         return f

@@ -316,7 +316,8 @@ int  sr_kernel_times(sr_scene*, sr_kernel_time* out, int32_t cap);
  * shaft walks (later rounds) rather than from the packet walk; [16..19] the exact fallback's any-hit rays on their own {rays,
  * FP64 triangle records tested, nodes fetched per lane, leaves} (also contained in [4..7]); [20..23] the same for the mirror
  * rays of the bounce pipeline (and for the second rays of a path-traced SR_MODE_BVH frame, which take the same walk; in every mode they
- * are counted in [4..7] unless SR_F_PRIMARY_STATS_ONLY is set).  These are the counters the roofline's algorithmic bytes are priced from (DESIGN.md "Measurement"). */
+ * are counted in [4..7] unless SR_F_PRIMARY_STATS_ONLY is set; with SR_DBG_KERNEL_SWITCH 94 / 95 [22] and [23] hold the shadow classification's census
+ * instead: hit points classified with / without the interior-triangle shortcut).  These are the counters the roofline's algorithmic bytes are priced from (DESIGN.md "Measurement"). */
 int  sr_last_ray_stats(const sr_scene*, uint64_t out[SR_STATS_COUNT]);
 
 /* Seeded synthetic triangle soup = SpatialSubdivisionTests.MakeRandomTriangles
@@ -393,7 +394,11 @@ enum {
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid
                                     too (its loop form spills registers: opt-in); 84 the persistent shaft walk hands its tiles out in natural order
                                     (no longest-first lists); 830 + n: n resident workgroups per CU for it; 840 + q: a walk is long at q / 4 x the
-                                    mean; 91 the first classification round on k_shadow_cls instead of k_shadow_cls_g                      */
+                                    mean; 91 the first classification round on k_shadow_cls instead of k_shadow_cls_g; 93 the shadow classification
+                                    computes the per-sample box exits for every hit point (no shortcut for candidate lists whose triangles all lie
+                                    inside the root box); 94 production path, and a frame rendered with ray statistics leaves the census of that
+                                    shortcut in statistics [22] (hit points classified with the shortcut) and [23] (with the per-sample box exits)
+                                    instead of the mirror rays' figures; 95 = 93 and 94 together                                           */
     SR_DBG_KERNEL_TIMING  = 7,   /* > 0: record a HIP event pair around every launch (sr_kernel_times); default off           */
     SR_DBG_EXACT_SHADOW_TESTS = 8, /* > 0: k_shadow_test decides every (sample, triangle) pair with the FP64 arithmetic (no
                                     fp32 classification): an independent schedule of the same result, kept as a cross-check */

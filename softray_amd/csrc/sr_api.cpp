@@ -95,6 +95,8 @@ struct sr_scene {
     DBuf d_tris, d_extra, d_rnodes, d_rboxes, d_rleaf, d_bnodes, d_btris, d_bslab, d_v9, d_bcam;
     double cam_origin[3] = {0, 0, 0};    // ray origin the camera-cone records in d_bcam (and the node order of d_b4cam) were made for
     bool   cam_valid = false;
+    DBuf   d_binter;                     // interior byte of every BVH record (k_interior_flags); follows the records' positions like d_bcam
+    bool   interior_valid = false;
     // four-wide tree of the packet walks: build-order nodes + the two per-frame ordered copies (camera origin / point light)
     DBuf d_b4, d_b4cam, d_b4light;
     size_t b4_num = 0;
@@ -230,7 +232,7 @@ int upload_wide_tree(sr_scene* s, const sr::BvhNode* nodes, size_t num_nodes) {
 
 int sync_geometry(sr_scene* s, uint32_t need_mode) {
     const sr_scene* h = s->host_src ? s->host_src : s;              // where the host arrays are
-    if (s->tris_dirty) { SR_HIP(s->d_tris.upload(h->tri_recs)); SR_HIP(s->d_v9.upload(h->v9)); s->tris_dirty = false; s->cam_valid = false; }
+    if (s->tris_dirty) { SR_HIP(s->d_tris.upload(h->tri_recs)); SR_HIP(s->d_v9.upload(h->v9)); s->tris_dirty = false; s->cam_valid = false; s->interior_valid = false; }
     if (s->extra_dirty) { SR_HIP(s->d_extra.upload(s->extra_recs)); s->extra_dirty = false; }
     if (need_mode == SR_MODE_REF_TREE && s->ref_dirty) {
         SR_HIP(s->d_rnodes.upload(h->ref.nodes));
@@ -256,7 +258,7 @@ int sync_geometry(sr_scene* s, uint32_t need_mode) {
         d_slab.release();
         s->bvh_num_nodes = h->bvh.nodes.size();
         s->bvh_dirty = false;
-        s->cam_valid = false;
+        s->cam_valid = false; s->interior_valid = false;
         int rc = upload_wide_tree(s, h->bvh.nodes.data(), h->bvh.nodes.size());
         if (rc) return rc;
     }
@@ -271,6 +273,7 @@ sr::DevScene dev_scene(const sr_scene* s) {
     d.rdepth = s->ref.tree_depth;
     d.bnodes = (const sr::BvhNode*)s->d_bnodes.p; d.btris = (const sr::Rec128*)s->d_btris.p; d.bdepth = s->bvh.depth;
     d.bslab = (const sr::TriSlab*)s->d_bslab.p;
+    d.binter = (const uint8_t*)s->d_binter.p;
     d.bcam = s->cam_valid ? (const sr::CamCone*)s->d_bcam.p : nullptr;
     d.v9 = (const double*)s->d_v9.p;
     // the four-wide walks stack up to three entries per level: a private walk needs (3 depth + 2) x 1 KB of LDS per workgroup, a packet
@@ -557,6 +560,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             rewrote = true;
             s->part_valid = false;
             s->cam_valid = false; s->b4cam_valid = false; s->b4light_valid = false;      // the records move: cone records and both copies are re-made
+            s->interior_valid = false;                                                   // ... and the interior bytes
             SR_HIP(sr::launch_facing_partition((const sr::Bvh4Node*)s->d_b4.p, (int)s->b4_num, (sr::Rec128*)s->d_btris.p, (sr::TriSlab*)s->d_bslab.p,
                                                fc.start_world, want_cam, fc.light_pos_model, fc.light_radius, want_light, s->d_rng_cam.p, s->d_rng_light.p, stream));
             s->part_cam = want_cam; s->part_light = want_light;
@@ -566,6 +570,13 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         }
     } else if (s->part_valid && s->dbg[SR_DBG_KERNEL_SWITCH] == 71) {
         s->part_valid = false; s->b4cam_valid = false; s->b4light_valid = false;        // (hook: no live runs -- the copies are re-made without them)
+    }
+    // ---- interior bytes of the records in their final order (the shadow classification's umax shortcut) ----
+    if (bvh_walks && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT) && s->d_bslab.p && !s->interior_valid) {
+        SR_HIP(s->d_binter.reserve(s->ntris));
+        rewrote = true;
+        SR_HIP(sr::launch_interior_flags(dev_scene(s), (int)s->ntris, (uint8_t*)s->d_binter.p, stream));
+        s->interior_valid = true;
     }
     if (pkt_primary) {
         const size_t nt = s->ntris;
@@ -931,7 +942,7 @@ void share_host_model(sr_scene* d, const sr_scene* src) {
     d->shadow_cache_empty = true;
     d->ref = sr::RefTree(); d->bvh = sr::Bvh(); d->bvh_on_device = false;
     d->tris_dirty = d->ref_dirty = d->bvh_dirty = true;
-    d->cam_valid = false;
+    d->cam_valid = false; d->interior_valid = false;
 }
 // ... and its host-built structures: the numbers a part needs (built / depth / counts), not the node arrays
 void share_ref_tree(sr_scene* d, const sr_scene* src) {
@@ -1022,7 +1033,7 @@ void sr_destroy(sr_scene* s) {
         return;
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
-        DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab,
+        DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
                         &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_pt_table, &s->d_pixels, &s->d_aa, &s->d_stats};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
@@ -1177,7 +1188,7 @@ int sr_build(sr_scene* s, uint32_t modes, int32_t max_depth, int32_t max_per_lea
         s->bvh_num_nodes = (size_t)nn;
         s->bvh_on_device = true;
         s->bvh_dirty = false;
-        s->cam_valid = false;
+        s->cam_valid = false; s->interior_valid = false;
         {   // the four-wide tree of the packet walks, collapsed where the binary nodes are
             if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still be walking the old tree's copies
             s->b4cam_valid = s->b4light_valid = false;

@@ -37,6 +37,7 @@ struct DevScene {
     int32_t        b4cam_known, b4light_known;
     RootBox        root;
     uint8_t*       shadow_cache; // static soft-shadow cache, 128^3 bytes, 0 = empty cell (SR_F_STATIC_SHADOWS frames)
+    const uint8_t* binter;      // 1: the record's triangle lies inside the shrunk root box (k_interior_flags), same order as btris
 };
 
 constexpr int kShaftRounds = 2;
@@ -142,6 +143,8 @@ hipError_t launch_facing_partition(const Bvh4Node* base, int num_nodes, Rec128* 
                                    const double light[3], double light_radius, bool use_light, void* cam_rng, void* light_rng, hipStream_t stream);
 // per-frame pre-pass: camera-cone records of every BVH triangle for the ray origin `origin` (model space)
 hipError_t launch_cam_cones(const DevScene& sc, int ntris, const double origin[3], CamCone* out, hipStream_t stream);
+// per-tree pre-pass (re-made when the records move): the interior byte of every BVH triangle record, DevScene::binter
+hipError_t launch_interior_flags(const DevScene& sc, int ntris, uint8_t* out, hipStream_t stream);
 size_t pipeline_hit_record_bytes();
 size_t pipeline_static_cells();
 int pipeline_round_cap(int round);

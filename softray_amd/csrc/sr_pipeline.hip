@@ -1608,6 +1608,46 @@ __device__ __forceinline__ ClsFrame cls_frame(const DevScene& sc, const FrameCon
     return c;
 }
 
+// "E' lies inside the root box shrunk by 4 pm" (pm: the fp32 position error bound of the hit point's frame)
+__device__ __forceinline__ bool cls_start_inside(const ClsFrame& cf, float pm, float efx, float efy, float efz) {
+    return fabsf(efx) < cf.hbx - 4.0f * pm && fabsf(efy) < cf.hby - 4.0f * pm && fabsf(efz) < cf.hbz - 4.0f * pm;
+}
+
+// SR_DBG_KERNEL_SWITCH values of the interior shortcut below: 93 / 95 every hit point takes the generic block (same pixels), 94 / 95 the
+// STATS instantiations leave the census of the two paths in ray statistics [22] (shortcut) and [23] (generic block)
+constexpr uint32_t kClsStartInside = 1u << 16;   // item table of k_shadow_cls_g, list-length word: cls_start_inside of the hit point
+__device__ __forceinline__ bool cls_force_generic(const FrameConst& fc) { return fc.debug == 93 || fc.debug == 95; }
+__device__ __forceinline__ bool cls_census(const FrameConst& fc) { return fc.debug == 94 || fc.debug == 95; }
+
+// umax of a hit point's samples, packed over the lane's two samples (the ONE place both classification kernels get it from).
+// umax_i stands for two of the reference's conditions on a crossing (tri_blocks: q inside [lo, hi] of the root box, and at or
+// behind the clipped start) -- the BLOCKED verdict asks for u_c < umax_i.
+//   generic:   the exit parameter of the ray from a box shrunk by 4 pm (any approximation will do: fast reciprocals), capped at
+//              0.999999; then the point E' + umax_i D_i is VERIFIED to lie inside the root box by more than pm, and so is E'
+//              (`ein`), so by convexity every crossing with u_c < umax_i lies inside the box.
+//   interior:  (wave-uniform) every candidate the hit point's pair loop will see has its three FP64 vertices inside the root box
+//              shrunk by 1e-5 x its largest extent (k_interior_flags).  A BLOCKED pair's exact crossing lies inside all three
+//              edges, i.e. it is a point of the triangle, and a point of a triangle whose vertices lie in a convex box lies in
+//              that box: the box condition holds with a margin ten orders of magnitude above the FP64 rounding of the
+//              reference's own q, the ray meets the box (so its clip succeeds) and the crossing comes after the clipped start.
+//              What is left of umax_i is its cap: the crossing lies in front of the sample's start.
+__device__ __forceinline__ f2 cls_umax(const ClsFrame& cf, bool interior, bool ein, float pm, float efx, float efy, float efz,
+                                       float dlx, float dly, float dlz, f2 OX, f2 OY, f2 OZ) {
+    if (interior) return ein ? splat(0.999999f) : splat(-1.0f);
+    const float sx = cf.hbx - 4.0f * pm, sy = cf.hby - 4.0f * pm, sz = cf.hbz - 4.0f * pm;
+    const f2 dxv = OX + splat(dlx), dyv = OY + splat(dly), dzv = OZ + splat(dlz);
+    const f2 rx = {__builtin_amdgcn_rcpf(dxv.x), __builtin_amdgcn_rcpf(dxv.y)}, ry = {__builtin_amdgcn_rcpf(dyv.x), __builtin_amdgcn_rcpf(dyv.y)},
+             rz = {__builtin_amdgcn_rcpf(dzv.x), __builtin_amdgcn_rcpf(dzv.y)};
+    const f2 tx = ((f2){__builtin_copysignf(sx, dxv.x), __builtin_copysignf(sx, dxv.y)} - splat(efx)) * rx;
+    const f2 ty = ((f2){__builtin_copysignf(sy, dyv.x), __builtin_copysignf(sy, dyv.y)} - splat(efy)) * ry;
+    const f2 tz = ((f2){__builtin_copysignf(sz, dzv.x), __builtin_copysignf(sz, dzv.y)} - splat(efz)) * rz;
+    const f2 ut = {fminf(fminf(fminf(tx.x, ty.x), tz.x), 0.999999f), fminf(fminf(fminf(tx.y, ty.y), tz.y), 0.999999f)};
+    const f2 px = pk_fma(ut, dxv, splat(efx)), py = pk_fma(ut, dyv, splat(efy)), pz = pk_fma(ut, dzv, splat(efz));
+    const bool ok0 = ein && ut.x > 0.0f && fabsf(px.x) < cf.hbx - pm && fabsf(py.x) < cf.hby - pm && fabsf(pz.x) < cf.hbz - pm;
+    const bool ok1 = ein && ut.y > 0.0f && fabsf(px.y) < cf.hbx - pm && fabsf(py.y) < cf.hby - pm && fabsf(pz.y) < cf.hbz - pm;
+    return (f2){ok0 ? ut.x : -1.0f, ok1 ? ut.y : -1.0f};
+}
+
 // TAIL: compile the tail layout in.  It pays for the later rounds (few undecided samples from the start); in the first round the
 // 30 registers it costs (162 instead of 128 VGPRs = 3 instead of 4 waves/SIMD) lose more than its shorter candidate loop gains.
 template <bool EXTRA, bool STATS, bool TAIL>
@@ -1659,7 +1699,7 @@ __global__ __launch_bounds__(256) void k_shadow_cls(DevScene sc, FrameConst fc, 
         OY = (f2){(float)offsets[3 * j0 + 1], (float)offsets[3 * j1 + 1]};
         OZ = (f2){(float)offsets[3 * j0 + 2], (float)offsets[3 * j1 + 2]};
     }
-    uint32_t n_rays = 0, n_items = 0, n_recs = 0, n_cls = 0, n_exact = 0;
+    uint32_t n_rays = 0, n_items = 0, n_recs = 0, n_cls = 0, n_exact = 0, n_fast = 0, n_gen = 0;
     const unsigned int nwaves = gridDim.x * 4u;
     const unsigned int s0 = blockIdx.x * 4u + (unsigned)wave;
     // software pipeline over this wave's items: hit index two items ahead, hit record / list head one item ahead
@@ -1729,25 +1769,16 @@ __global__ __launch_bounds__(256) void k_shadow_cls(DevScene sc, FrameConst fc, 
                 else alive[q] = work;
             }
         }
-        // umax_i: the exit parameter of the ray from a box shrunk by 4 pm (any approximation will do: fast reciprocals), then
-        // the point E' + umax_i D_i is VERIFIED to lie inside the root box by more than pm, and so is E'.  Packed over the
-        // lane's two samples.
-        f2 UM;
-        {
-            const float sx = cf.hbx - 4.0f * pm, sy = cf.hby - 4.0f * pm, sz = cf.hbz - 4.0f * pm;
-            const bool ein = fabsf(efx) < sx && fabsf(efy) < sy && fabsf(efz) < sz;
-            const f2 dxv = OX + splat(dlx), dyv = OY + splat(dly), dzv = OZ + splat(dlz);
-            const f2 rx = {__builtin_amdgcn_rcpf(dxv.x), __builtin_amdgcn_rcpf(dxv.y)}, ry = {__builtin_amdgcn_rcpf(dyv.x), __builtin_amdgcn_rcpf(dyv.y)},
-                     rz = {__builtin_amdgcn_rcpf(dzv.x), __builtin_amdgcn_rcpf(dzv.y)};
-            const f2 tx = ((f2){__builtin_copysignf(sx, dxv.x), __builtin_copysignf(sx, dxv.y)} - splat(efx)) * rx;
-            const f2 ty = ((f2){__builtin_copysignf(sy, dyv.x), __builtin_copysignf(sy, dyv.y)} - splat(efy)) * ry;
-            const f2 tz = ((f2){__builtin_copysignf(sz, dzv.x), __builtin_copysignf(sz, dzv.y)} - splat(efz)) * rz;
-            const f2 ut = {fminf(fminf(fminf(tx.x, ty.x), tz.x), 0.999999f), fminf(fminf(fminf(tx.y, ty.y), tz.y), 0.999999f)};
-            const f2 px = pk_fma(ut, dxv, splat(efx)), py = pk_fma(ut, dyv, splat(efy)), pz = pk_fma(ut, dzv, splat(efz));
-            const bool ok0 = ein && ut.x > 0.0f && fabsf(px.x) < cf.hbx - pm && fabsf(py.x) < cf.hby - pm && fabsf(pz.x) < cf.hbz - pm;
-            const bool ok1 = ein && ut.y > 0.0f && fabsf(px.y) < cf.hbx - pm && fabsf(py.y) < cf.hby - pm && fabsf(pz.y) < cf.hbz - pm;
-            UM = (f2){ok0 ? ut.x : -1.0f, ok1 ? ut.y : -1.0f};
+        // umax_i (cls_umax): the shortcut applies when every record of the hit point's list is interior (an empty list has no pair to decide)
+        bool interior = !cls_force_generic(fc);
+        if (interior) {
+            bool all = true;
+            for (int b0 = 0; b0 < ntri; b0 += 64)
+                if (b0 + lane < ntri) all = all && sc.binter[list[b0 + lane]] != 0;
+            interior = __all(all) != 0;
         }
+        if (STATS) { if (interior) n_fast++; else n_gen++; }
+        const f2 UM = cls_umax(cf, interior, cls_start_inside(cf, pm, efx, efy, efz), pm, efx, efy, efz, dlx, dly, dlz, OX, OY, OZ);
         const float hbm = cf.a0 + a1;
         if (TAIL) { wum[lane] = UM.x; wum[lane + 64] = UM.y; }            // (the tail layout fetches a sample's umax by its index)
         bool have = __any(alive[0] || alive[1]);
@@ -2000,6 +2031,7 @@ __global__ __launch_bounds__(256) void k_shadow_cls(DevScene sc, FrameConst fc, 
             stat_add(&stats[8], n_recs);             // wave-level: fp32 triangle records read
             stat_add(&stats[9], n_items);            // wave-level: hit points processed
             stat_add(&stats[12], b); stat_add(&stats[13], c);
+            if (cls_census(fc)) { stat_add(&stats[22], n_fast); stat_add(&stats[23], n_gen); }   // wave-level: hit points by umax path (cls_umax)
         }
     }
 }
@@ -2015,6 +2047,8 @@ __global__ __launch_bounds__(256) void k_shadow_cls(DevScene sc, FrameConst fc, 
 //             path for undecided pairs, the pixel -- k_shadow_cls' code, with the hit point's constants read from the item table
 // Same arithmetic per (hit point, candidate, sample) as k_shadow_cls<.., TAIL = false>, same verdicts, same pixels; the later rounds
 // (long lists, few hit points) keep k_shadow_cls.  SR_DBG_KERNEL_SWITCH 91 runs the first round on k_shadow_cls (cross-check, A/B).
+// The umax of a hit point's samples is cls_umax': a hit point whose list holds interior records only (one ballot over the fill's bytes) skips
+// the per-sample box exits; SR_DBG_KERNEL_SWITCH 93 computes them for every hit point (same pixels, A/B).
 // --------------------------------------------------------------------------------------------------
 constexpr int kGrpItems = 16;            // hit points prepared together (one lane each)
 constexpr int kGrpRecs = 64;             // candidate records staged per fill (one lane each) >= the longest first-round list
@@ -2066,7 +2100,7 @@ __global__ __launch_bounds__(256, 5) void k_shadow_cls_g(DevScene sc, FrameConst
         OY = (f2){(float)offsets[3 * j0 + 1], (float)offsets[3 * j1 + 1]};
         OZ = (f2){(float)offsets[3 * j0 + 2], (float)offsets[3 * j1 + 2]};
     }
-    uint32_t n_rays = 0, n_items = 0, n_recs = 0, n_cls = 0, n_exact = 0;
+    uint32_t n_rays = 0, n_items = 0, n_recs = 0, n_cls = 0, n_exact = 0, n_fast = 0, n_gen = 0;
     int qn = 0;                                                          // (wave-uniform) undecided pairs waiting in wqueue
     // The reference's FP64 arithmetic for the pairs the fp32 bounds could not decide (0.1 % of them), one pair per lane, for a whole
     // group of hit points at once: inline it ran with one or two lanes active for ~400 instructions whenever a hit point had such a
@@ -2115,9 +2149,12 @@ __global__ __launch_bounds__(256, 5) void k_shadow_cls_g(DevScene sc, FrameConst
             const float dmax = __builtin_amdgcn_sqrtf(dlx * dlx + dly * dly + dlz * dlz) * 1.0001f + cf.R;   // an upper bound is all it has to be
             const uint32_t shaded = (fc.flags & 32u) ? 0u : samples[rec.sample];
             my_ntri = (int)(cc & 0xffffu);
+            // (E' inside the shrunk root box depends on the hit point only: one bit of the list-length word, so that cls_umax' shortcut does no
+            //  per-hit-point float work for it)
+            const uint32_t ein = cls_start_inside(cf, 5e-7f * (cf.s0 + dmax), efx, efy, efz) ? kClsStartInside : 0u;
             witem[lane * kGrpItemF4 + 0] = make_float4(efx, efy, efz, dlx);
             witem[lane * kGrpItemF4 + 1] = make_float4(dly, dlz, dmax, __uint_as_float(shaded));
-            witem[lane * kGrpItemF4 + 2] = make_float4(__uint_as_float(h), __uint_as_float(rec.sample), __uint_as_float(rec.pad[0]), __uint_as_float(cc));
+            witem[lane * kGrpItemF4 + 2] = make_float4(__uint_as_float(h), __uint_as_float(rec.sample), __uint_as_float(rec.pad[0]), __uint_as_float(cc | ein));
             witem[lane * kGrpItemF4 + 5] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);     // FP64 verdicts (flush_queue ORs into them): blocked samples,
             witem[lane * kGrpItemF4 + 6] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);     // samples whose ray misses the root box
         }
@@ -2140,6 +2177,7 @@ __global__ __launch_bounds__(256, 5) void k_shadow_cls_g(DevScene sc, FrameConst
             while (jb < nitems && __builtin_amdgcn_readlane(incl, jb) - base <= kGrpRecs) ++jb;
             const int npairs = __builtin_amdgcn_readlane(incl, jb - 1) - base;
             // ---- fill, lane = (hit point, candidate): cone planes through E' and their margins (see k_shadow_cls) ----
+            bool inter = false;                                           // this lane's record is interior (k_interior_flags)
             if (lane < npairs) {
                 int jj = ja, ofs = 0;
                 for (int j = ja + 1; j < jb; ++j) {
@@ -2151,6 +2189,7 @@ __global__ __launch_bounds__(256, 5) void k_shadow_cls_g(DevScene sc, FrameConst
                 const unsigned int hj = __float_as_uint(i2.x);
                 const int32_t ent = cand[(size_t)hj * cap + (lane - ofs)];
                 const TriSlab slab = sc.bslab[ent];
+                inter = sc.binter[ent] != 0;
                 const f2 edx = {efx, dlx}, edy = {efy, dly}, edz = {efz, dlz};
                 const f2 cn = {-slab.d, 0.0f}, c1 = {-slab.c1, 0.0f}, c2 = {-slab.c2, 0.0f}, c3 = {-slab.c3, 0.0f};
                 const f2 N = pk_fma(splat(slab.n[0]), edx, pk_fma(splat(slab.n[1]), edy, pk_fma(splat(slab.n[2]), edz, cn)));    // (G0, n.(L - E'))
@@ -2178,6 +2217,9 @@ __global__ __launch_bounds__(256, 5) void k_shadow_cls_g(DevScene sc, FrameConst
                 w[4] = make_float4(G0, G0 <= -cf.a0 ? mc : 1e30f, G0 >= cf.a0 ? -1e30f : mc, 0.0f);
                 wrecidx[lane] = ent;
             }
+            // (a first-round list never spans two fills -- kGrpRecs >= the list cap -- so a hit point's run of bits below is the whole list its
+            //  pair loop sees.  A truncated list goes on to the next round with its saved masks: BLOCKED verdicts are final, whatever comes later)
+            const unsigned long long imask = cls_force_generic(fc) ? 0ull : __ballot(inter);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             n_recs += (uint32_t)npairs;
@@ -2213,22 +2255,11 @@ __global__ __launch_bounds__(256, 5) void k_shadow_cls_g(DevScene sc, FrameConst
                         else alive[q] = work;
                     }
                 }
-                f2 UM;
-                {
-                    const float sx = cf.hbx - 4.0f * pm, sy = cf.hby - 4.0f * pm, sz = cf.hbz - 4.0f * pm;
-                    const bool ein = fabsf(efx) < sx && fabsf(efy) < sy && fabsf(efz) < sz;
-                    const f2 dxv = OX + splat(dlx), dyv = OY + splat(dly), dzv = OZ + splat(dlz);
-                    const f2 rx = {__builtin_amdgcn_rcpf(dxv.x), __builtin_amdgcn_rcpf(dxv.y)}, ry = {__builtin_amdgcn_rcpf(dyv.x), __builtin_amdgcn_rcpf(dyv.y)},
-                             rz = {__builtin_amdgcn_rcpf(dzv.x), __builtin_amdgcn_rcpf(dzv.y)};
-                    const f2 tx = ((f2){__builtin_copysignf(sx, dxv.x), __builtin_copysignf(sx, dxv.y)} - splat(efx)) * rx;
-                    const f2 ty = ((f2){__builtin_copysignf(sy, dyv.x), __builtin_copysignf(sy, dyv.y)} - splat(efy)) * ry;
-                    const f2 tz = ((f2){__builtin_copysignf(sz, dzv.x), __builtin_copysignf(sz, dzv.y)} - splat(efz)) * rz;
-                    const f2 ut = {fminf(fminf(fminf(tx.x, ty.x), tz.x), 0.999999f), fminf(fminf(fminf(tx.y, ty.y), tz.y), 0.999999f)};
-                    const f2 px = pk_fma(ut, dxv, splat(efx)), py = pk_fma(ut, dyv, splat(efy)), pz = pk_fma(ut, dzv, splat(efz));
-                    const bool ok0 = ein && ut.x > 0.0f && fabsf(px.x) < cf.hbx - pm && fabsf(py.x) < cf.hby - pm && fabsf(pz.x) < cf.hbz - pm;
-                    const bool ok1 = ein && ut.y > 0.0f && fabsf(px.y) < cf.hbx - pm && fabsf(py.y) < cf.hby - pm && fabsf(pz.y) < cf.hbz - pm;
-                    UM = (f2){ok0 ? ut.x : -1.0f, ok1 ? ut.y : -1.0f};
-                }
+                // umax_i (cls_umax): all of the list's records interior <=> the hit point's run of bits in the fill's mask is all ones
+                const unsigned long long run = ntri > 0 ? (~0ull >> (64 - ntri)) : 0ull;
+                const bool interior = ntri > 0 ? ((imask >> off_local) & run) == run : !cls_force_generic(fc);   // (an empty list has no pair to decide)
+                if (STATS) { if (interior) n_fast++; else n_gen++; }
+                const f2 UM = cls_umax(cf, interior, (cc & kClsStartInside) != 0u, pm, efx, efy, efz, dlx, dly, dlz, OX, OY, OZ);
                 const float hbm = cf.a0 + a1;
                 bool have = __any(alive[0] || alive[1]);
                 const f4* wc4 = reinterpret_cast<const f4*>(wc) + (size_t)off_local * 5;
@@ -2346,6 +2377,7 @@ __global__ __launch_bounds__(256, 5) void k_shadow_cls_g(DevScene sc, FrameConst
             stat_add(&stats[8], n_recs);             // wave-level: fp32 triangle records read
             stat_add(&stats[9], n_items);            // wave-level: hit points processed
             stat_add(&stats[12], b); stat_add(&stats[13], c);
+            if (cls_census(fc)) { stat_add(&stats[22], n_fast); stat_add(&stats[23], n_gen); }   // wave-level: hit points by umax path (cls_umax)
         }
     }
 }
@@ -3487,6 +3519,32 @@ __global__ __launch_bounds__(256) void k_cam_cones(const Rec128* __restrict__ bt
         c.m3n[1] = k8u * 1.0001f;
     }
     out[i] = c;
+}
+
+// --------------------------------------------------------------------------------------------------
+// k_interior_flags: one byte per BVH triangle record, in record order (beside the TriSlab, which is a full 64-byte line): 1 when the
+// three FP64 vertices lie inside the root box shrunk on every face by 1e-5 x its largest extent -- the classification's shortcut for
+// umax (cls_umax).  A degenerate record (all-zero TriSlab) is never interior.  Depends on the scene and the root box only, never on
+// camera or light, but follows the records' positions: re-made like the camera-cone records after k_facing_partition moved them.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_interior_flags(const Rec128* __restrict__ btris, const TriSlab* __restrict__ bslab,
+                                                        const double* __restrict__ v9, int n, RootBox root, uint8_t* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const TriSlab sl = bslab[i];
+    bool in = !(sl.n[0] == 0.0f && sl.n[1] == 0.0f && sl.n[2] == 0.0f);
+    const double ext = fmax(fmax(root.max[0] - root.min[0], root.max[1] - root.min[1]), root.max[2] - root.min[2]);
+    const double delta = 1e-5 * ext;
+    const double* v = v9 + (size_t)btris[i].aux * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) in = in && v[k] >= root.min[k % 3] + delta && v[k] <= root.max[k % 3] - delta;
+    out[i] = in ? 1 : 0;
+}
+
+hipError_t launch_interior_flags(const DevScene& sc, int ntris, uint8_t* out, hipStream_t stream) {
+    if (ntris <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_interior_flags, dim3((unsigned)((ntris + 255) / 256)), dim3(256), 0, stream, sc.btris, sc.bslab, sc.v9, ntris, sc.root, out);
+    return hipGetLastError();
 }
 
 // --------------------------------------------------------------------------------------------------

@@ -188,4 +188,23 @@ struct TraceLaunch {
 hipError_t launch_trace(const TraceLaunch& L);
 hipError_t launch_shade_points(const FrameConst& fc, long long n, const double* pos, const double* nrm, const uint32_t* color, uint32_t* out, hipStream_t stream);
 
+// --------------------------------------------------------------------------------------------------
+// Wave votes of the packet walks.  THE RULE: a vote is a test of an INTEGER, and __ballot only ever sees ONE comparison.
+// A lane predicate that is only voted on or used to gate per-lane work lives as a 64-bit mask in a scalar register pair:
+//   vote(a < b)                one v_cmp that writes the SGPR pair itself -- nothing else
+//   m0 & m1 & ~done_m          s_and_b64 / s_andn2_b64; `m == 0` is s_cmp_eq_u64 (or the SCC of the last s_and) + s_cbranch
+//   lane_of(m)                 the mask as this lane's predicate again: the selector of a v_cndmask / the exec mask of a branch, no instruction
+// __ballot(a && b && !done) instead is lowered as s_and_b64 (the conjunction IS a mask already) -> v_cndmask_b32 v, 0, 1 -> v_cmp_ne_u32 0, v:
+// two vector instructions per vote in kernels that are bound by vector issue, and a loop-carried `bool` takes the same round trip through a
+// VGPR at every use.  NaN: ballot the comparison AS WRITTEN and complement the mask -- !(a < b) is `lanes & ~vote(a < b)`, never vote(a >= b).
+// Every vote sits where all 64 lanes execute (the walks' control flow is wave-uniform); lane_of needs a wave-uniform mask, which the
+// result of votes and scalar algebra is.  Do not move a comparison into the body of an `if (lane_of(..))`: its vote would miss lanes.
+// --------------------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+typedef unsigned long long lanemask;
+__device__ __forceinline__ lanemask vote(bool one_comparison) { return __builtin_amdgcn_ballot_w64(one_comparison); }
+__device__ __forceinline__ lanemask lanes_if(bool wave_uniform) { return wave_uniform ? ~0ull : 0ull; }      // a scalar condition as a mask (s_cselect_b64)
+__device__ __forceinline__ bool lane_of(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+#endif
+
 }  // namespace sr

@@ -543,10 +543,7 @@ __device__ __forceinline__ ShaftRay make_shaft_ray(const DevScene& sc, const Fra
 
 // returns 0: no sample ray can hit the triangle; 1: candidate; 2: UMBRA.  Straight-line code (the kernels that call it are
 // bound by instruction issue, scalar bookkeeping of nested branches included); `want`: lanes whose verdict is looked at.
-// STAGED (the packet walks: all lanes test the SAME triangle with the shafts of one 8x8-pixel tile): the wave leaves after the
-// first edge plane that has every lane's shaft on its outside.  Census of the headline frame: of 16.0 M wave-level filters 9.9 M get
-// past the plane stage; 5.6 M of those end at the first edge, 1.5 M at the second, 0.9 M at the third, 1.9 M leave a candidate.
-template <bool STAGED = false>
+// The per-lane form of k_shaft / k_shaft_coop (their lanes test DIFFERENT triangles); the packet walks use shaft_touches_wave below.
 __device__ __forceinline__ int shaft_touches(const TriSlab s, const ShaftRay& sr, bool want) {
     // (f0, f1) of the plane and the three edge planes along the centre ray, two lanes per packed FMA
     f2 cn = {-s.d, 0.0f}, c1 = {-s.c1, 0.0f}, c2 = {-s.c2, 0.0f}, c3 = {-s.c3, 0.0f};
@@ -562,15 +559,12 @@ __device__ __forceinline__ int shaft_touches(const TriSlab s, const ShaftRay& sr
     const f2 P = pk_fma(splat(s.m1[0]), sr.edx, pk_fma(splat(s.m1[1]), sr.edy, pk_fma(splat(s.m1[2]), sr.edz, c1)));
     const float A1 = __builtin_fmaf(P.x, N1, -(G0 * P.y)), L1 = sr.Rm * __builtin_amdgcn_sqrtf(__builtin_fmaf(P.x, P.x, g2)), e1 = __builtin_fmaf(sr.c1, fabsf(P.x) + ag, sr.c0);
     const bool ok1 = plane_ok && !(A1 + L1 + e1 < 0.0f);
-    if (STAGED && __ballot(ok1) == 0ull) return 0;
     const f2 Q = pk_fma(splat(s.m2[0]), sr.edx, pk_fma(splat(s.m2[1]), sr.edy, pk_fma(splat(s.m2[2]), sr.edz, c2)));
     const float A2 = __builtin_fmaf(Q.x, N1, -(G0 * Q.y)), L2 = sr.Rm * __builtin_amdgcn_sqrtf(__builtin_fmaf(Q.x, Q.x, g2)), e2 = __builtin_fmaf(sr.c1, fabsf(Q.x) + ag, sr.c0);
     const bool ok2 = ok1 && !(A2 + L2 + e2 < 0.0f);
-    if (STAGED && __ballot(ok2) == 0ull) return 0;
     const f2 T = pk_fma(splat(s.m3[0]), sr.edx, pk_fma(splat(s.m3[1]), sr.edy, pk_fma(splat(s.m3[2]), sr.edz, c3)));
     const float A3 = __builtin_fmaf(T.x, N1, -(G0 * T.y)), L3 = sr.Rm * __builtin_amdgcn_sqrtf(__builtin_fmaf(T.x, T.x, g2)), e3 = __builtin_fmaf(sr.c1, fabsf(T.x) + ag, sr.c0);
     const bool cand = ok2 && !(A3 + L3 + e3 < 0.0f);
-    if (STAGED && __ballot(cand) == 0ull) return 0;
     // ---- umbra: every direction of the ball inside every edge ----
     const bool pre = cand && fminf(fminf(A1 - L1 - e1, A2 - L2 - e2), A3 - L3 - e3) > 0.0f && N1 > 2.0f * sr.Rm + sr.a01 && G0 < -4.0f * sr.a0;
     bool umbra = false;
@@ -585,6 +579,44 @@ __device__ __forceinline__ int shaft_touches(const TriSlab s, const ShaftRay& sr
                 fmaxf(fabsf(Z.x), fabsf(Z.y)) + margin < sr.hbz;
     }
     return umbra ? 2 : (cand ? 1 : 0);
+}
+
+// The same filter for the packet walks: all 64 lanes test the SAME triangle with the shafts of one 8x8-pixel tile, and must all call it.
+// The arithmetic per lane is shaft_touches', expression for expression; the verdicts are lane masks (vote helpers, sr_device.h):
+// touch = the lanes of `want` for which the triangle is a candidate, umbra (a subset of touch) = the lanes it shadows completely.
+// Staged: the wave leaves after the first stage that no lane passes, on a scalar test.  Census of the headline frame: of 16.0 M wave-level
+// filters 9.9 M get past the plane stage; 5.6 M of those end at the first edge, 1.5 M at the second, 0.9 M at the third, 1.9 M leave a candidate.
+__device__ __forceinline__ void shaft_touches_wave(const TriSlab s, const ShaftRay& sr, const lanemask want, lanemask& touch, lanemask& umbra) {
+    touch = 0ull; umbra = 0ull;
+    f2 cn = {-s.d, 0.0f}, c1 = {-s.c1, 0.0f}, c2 = {-s.c2, 0.0f}, c3 = {-s.c3, 0.0f};
+    const f2 N = pk_fma(splat(s.n[0]), sr.edx, pk_fma(splat(s.n[1]), sr.edy, pk_fma(splat(s.n[2]), sr.edz, cn)));
+    const float G0 = N.x, N1 = N.y;
+    const lanemask plane_ok = want & ~vote(N1 < -sr.backface) & ~vote(G0 > sr.a0) & ~vote(G0 + N1 + sr.R < -sr.a01);
+    if (plane_ok == 0ull) return;
+    const float g2 = G0 * G0, ag = fabsf(G0);
+    const f2 P = pk_fma(splat(s.m1[0]), sr.edx, pk_fma(splat(s.m1[1]), sr.edy, pk_fma(splat(s.m1[2]), sr.edz, c1)));
+    const float A1 = __builtin_fmaf(P.x, N1, -(G0 * P.y)), L1 = sr.Rm * __builtin_amdgcn_sqrtf(__builtin_fmaf(P.x, P.x, g2)), e1 = __builtin_fmaf(sr.c1, fabsf(P.x) + ag, sr.c0);
+    const lanemask ok1 = plane_ok & ~vote(A1 + L1 + e1 < 0.0f);
+    if (ok1 == 0ull) return;
+    const f2 Q = pk_fma(splat(s.m2[0]), sr.edx, pk_fma(splat(s.m2[1]), sr.edy, pk_fma(splat(s.m2[2]), sr.edz, c2)));
+    const float A2 = __builtin_fmaf(Q.x, N1, -(G0 * Q.y)), L2 = sr.Rm * __builtin_amdgcn_sqrtf(__builtin_fmaf(Q.x, Q.x, g2)), e2 = __builtin_fmaf(sr.c1, fabsf(Q.x) + ag, sr.c0);
+    const lanemask ok2 = ok1 & ~vote(A2 + L2 + e2 < 0.0f);
+    if (ok2 == 0ull) return;
+    const f2 T = pk_fma(splat(s.m3[0]), sr.edx, pk_fma(splat(s.m3[1]), sr.edy, pk_fma(splat(s.m3[2]), sr.edz, c3)));
+    const float A3 = __builtin_fmaf(T.x, N1, -(G0 * T.y)), L3 = sr.Rm * __builtin_amdgcn_sqrtf(__builtin_fmaf(T.x, T.x, g2)), e3 = __builtin_fmaf(sr.c1, fabsf(T.x) + ag, sr.c0);
+    const lanemask cand = ok2 & ~vote(A3 + L3 + e3 < 0.0f);
+    if (cand == 0ull) return;
+    touch = cand;
+    // ---- umbra: every direction of the ball inside every edge ----
+    const lanemask pre = cand & vote(fminf(fminf(A1 - L1 - e1, A2 - L2 - e2), A3 - L3 - e3) > 0.0f) & vote(N1 > 2.0f * sr.Rm + sr.a01) & vote(G0 < -4.0f * sr.a0);
+    if (pre != 0ull) {
+        const float ulo = -G0 * __builtin_amdgcn_rcpf(N1 + sr.Rm) * 0.999998f, uhi = -G0 * __builtin_amdgcn_rcpf(N1 - sr.Rm) * 1.000002f;
+        const float margin = __builtin_fmaf(sr.Rm, uhi, sr.umargin);
+        const f2 U = {ulo, uhi};
+        const f2 X = pk_fma(U, splat(sr.edx.y), splat(sr.edx.x)), Y = pk_fma(U, splat(sr.edy.y), splat(sr.edy.x)), Z = pk_fma(U, splat(sr.edz.y), splat(sr.edz.x));
+        umbra = pre & vote(ulo > 1e-6f) & vote(uhi < 0.5f) & vote(fmaxf(fabsf(X.x), fabsf(X.y)) + margin < sr.hbx) & vote(fmaxf(fabsf(Y.x), fabsf(Y.y)) + margin < sr.hby) &
+                vote(fmaxf(fabsf(Z.x), fabsf(Z.y)) + margin < sr.hbz);
+    }
 }
 
 template <bool STATS>
@@ -943,12 +975,13 @@ __global__ __launch_bounds__(256, 7) void k_shaft_pkt(DevScene sc, FrameConst fc
                 for (int q = 0; q < cn; ++q) {
                     const TriSlab s = sc.bslab[cc + q];               // scalar load
                     const bool live_q = hc && !done;
-                    const int touch = shaft_touches<true>(s, sr, live_q);
-                    const bool take = live_q && touch != 0, room = count < cap;
+                    lanemask touch_m, umbra_m;
+                    shaft_touches_wave(s, sr, __ballot(live_q), touch_m, umbra_m);
+                    const bool take = lane_of(touch_m), room = count < cap;
                     if (take && room) out[count] = cc + q;
                     count += (take && room) ? 1 : 0;
                     truncated = truncated || (take && !room);
-                    umbra = umbra || (live_q && touch == 2);
+                    umbra = umbra || lane_of(umbra_m);
                     done = done || truncated || umbra;
                 }
             }
@@ -1077,8 +1110,9 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
     const ShaftRay sr = make_shaft_ray(sc, fc, E, lpos);
     int32_t* out = cand + (size_t)slot_i * cap;
     int count = 0;
-    bool truncated = false, umbra = false;
-    bool done = !valid;
+    // lane masks in scalar registers (vote helpers, sr_device.h): lanes whose list overflowed / that lie in a triangle's umbra / that have their verdict
+    lanemask trunc_m = 0ull, umbra_m = 0ull;
+    lanemask done_m = ~vote(rec.sample != kInvalidHit);
     int sp = 0;                      // wave-uniform: entries in LDS
     // the TOP of the stack lives in registers (node: wave-uniform, bound: one encoded 16-bit value per lane): most nodes of the lowest inner level
     // have leaf children only, so every other step ends in a pop -- two dependent LDS reads (the lanes' bounds, then the node) before the next node
@@ -1090,8 +1124,8 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
     float nu = valid ? 1.0f : -1.0f; // this lane's u bound inside the current subtree; < 0: the lane's shaft misses it
     auto enc = [](float fb) { return fb < 0.0f ? (uint16_t)0 : (uint16_t)min(65535, (int)(fminf(fb, 1.0f) * 65534.0f) + 2); };
     for (;;) {
-        if (__ballot(!done && nu >= 0.0f) == 0ull) {
-            if (__ballot(!done) == 0ull) break;                        // every lane has its verdict: nothing on the stack matters
+        if ((vote(nu >= 0.0f) & ~done_m) == 0ull) {
+            if (~done_m == 0ull) break;                                // every lane has its verdict: nothing on the stack matters
             // nobody wants the current subtree: pop until a live lane wants one
             bool found = false;
             while (has_top) {
@@ -1100,7 +1134,7 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
                 if (sp > 0) { --sp; top_b = wbound[sp * 64]; top_ni = wnode[sp]; }      // (the entry below: needed at the next pop, so nothing waits for these two reads here)
                 else has_top = false;
                 const float bu = qb ? (float)(qb - 1u) * (1.0f / 65534.0f) * 1.000001f : -1.0f;
-                if (__ballot(!done && bu >= 0.0f) != 0ull) { ni = __builtin_amdgcn_readfirstlane(qn); nu = bu; found = true; break; }
+                if ((vote(bu >= 0.0f) & ~done_m) != 0ull) { ni = __builtin_amdgcn_readfirstlane(qn); nu = bu; found = true; break; }
             }
             if (!found) break;
         }
@@ -1121,26 +1155,27 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
         shaft_slabs<KNOWN>(n.ch[2], Ixy, Izz, B0, B1, B2, a2, b2);
         shaft_slabs<KNOWN>(n.ch[3], Ixy, Izz, B0, B1, B2, a3, b3);
         b0 = fminf(b0, nu); b1 = fminf(b1, nu); b2 = fminf(b2, nu); b3 = fminf(b3, nu);
-        const bool h0 = !done && n.ch[0].n >= 0 && fmaxf(a0, umin) <= b0, h1 = !done && n.ch[1].n >= 0 && fmaxf(a1, umin) <= b1;
-        const bool h2 = !done && n.ch[2].n >= 0 && fmaxf(a2, umin) <= b2, h3 = !done && n.ch[3].n >= 0 && fmaxf(a3, umin) <= b3;
+        // the lanes whose shaft touches child k's box; `& ~done_m` where a mask is used: lanes drop out in the leaves
+        const lanemask h0 = lanes_if(n.ch[0].n >= 0) & vote(fmaxf(a0, umin) <= b0), h1 = lanes_if(n.ch[1].n >= 0) & vote(fmaxf(a1, umin) <= b1);
+        const lanemask h2 = lanes_if(n.ch[2].n >= 0) & vote(fmaxf(a2, umin) <= b2), h3 = lanes_if(n.ch[3].n >= 0) & vote(fmaxf(a3, umin) <= b3);
         // ---- leaf children in slot order: every interested lane filters the (broadcast) triangles with its own shaft.  Four copies of
         //      the filter loop (one per slot, everything static) rather than one loop over a slot index: selecting a slot's count, link
         //      and lane mask by a run-time index costs a chain of scalar branches per slot and step ----
-        const auto leaf = [&](const int cn, const int cc, const bool hc) __attribute__((always_inline)) {
-            if (__ballot(hc && !done) == 0ull) return;
+        const auto leaf = [&](const int cn, const int cc, const lanemask hc) __attribute__((always_inline)) {
+            if ((hc & ~done_m) == 0ull) return;
             leaves++;
             slabs += (uint32_t)cn;
             if (PERSIST) walk += (uint32_t)cn;
             for (int q = 0; q < cn; ++q) {
                 const TriSlab s = load_uniform(&sc_arg.bslab[cc + q]); // scalar load
-                const bool live_q = hc && !done;
-                const int touch = shaft_touches<true>(s, sr, live_q);
-                const bool take = live_q && touch != 0, room = count < cap;
-                if (take && room) out[count] = cc + q;
-                count += (take && room) ? 1 : 0;
-                truncated = truncated || (take && !room);
-                umbra = umbra || (live_q && touch == 2);
-                done = done || truncated || umbra;
+                lanemask take_m, in_umbra_m;
+                shaft_touches_wave(s, sr, hc & ~done_m, take_m, in_umbra_m);
+                const lanemask room_m = vote(count < cap);
+                if (lane_of(take_m & room_m)) out[count] = cc + q;
+                count += lane_of(take_m & room_m) ? 1 : 0;
+                trunc_m |= take_m & ~room_m;
+                umbra_m |= in_umbra_m;
+                done_m |= trunc_m | umbra_m;
             }
         };
         if (n.ch[0].n > 0) leaf(n.ch[0].n, n.ch[0].c, h0);
@@ -1155,27 +1190,28 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
             top_ni = pn; top_b = (uint32_t)enc(pu); has_top = true;
         };
         {
-            const bool w3 = h3 && !done && n.ch[3].n == 0;
-            if (__ballot(w3) != 0ull) { next = n.ch[3].c; next_u = w3 ? b3 : -1.0f; }
-            const bool w2 = h2 && !done && n.ch[2].n == 0;
-            if (__ballot(w2) != 0ull) {
+            const lanemask w3 = lanes_if(n.ch[3].n == 0) & h3 & ~done_m;
+            if (w3 != 0ull) { next = n.ch[3].c; next_u = lane_of(w3) ? b3 : -1.0f; }
+            const lanemask w2 = lanes_if(n.ch[2].n == 0) & h2 & ~done_m;
+            if (w2 != 0ull) {
                 if (next >= 0) push(next, next_u);
-                next = n.ch[2].c; next_u = w2 ? b2 : -1.0f;
+                next = n.ch[2].c; next_u = lane_of(w2) ? b2 : -1.0f;
             }
-            const bool w1 = h1 && !done && n.ch[1].n == 0;
-            if (__ballot(w1) != 0ull) {
+            const lanemask w1 = lanes_if(n.ch[1].n == 0) & h1 & ~done_m;
+            if (w1 != 0ull) {
                 if (next >= 0) push(next, next_u);
-                next = n.ch[1].c; next_u = w1 ? b1 : -1.0f;
+                next = n.ch[1].c; next_u = lane_of(w1) ? b1 : -1.0f;
             }
-            const bool w0 = h0 && !done && n.ch[0].n == 0;
-            if (__ballot(w0) != 0ull) {
+            const lanemask w0 = lanes_if(n.ch[0].n == 0) & h0 & ~done_m;
+            if (w0 != 0ull) {
                 if (next >= 0) push(next, next_u);
-                next = n.ch[0].c; next_u = w0 ? b0 : -1.0f;
+                next = n.ch[0].c; next_u = lane_of(w0) ? b0 : -1.0f;
             }
         }
         if (next >= 0) { ni = next; nu = next_u; }
         else nu = -1.0f;                                               // leaf-only / dead end: pop at the top of the loop
     }
+    const bool umbra = lane_of(umbra_m), truncated = lane_of(trunc_m);
     if (valid) {
         const DevScene sc = tile_arg<PERSIST>(sc_arg, offsetof(SceneFrameArgs, sc));      // (epilogue: shadow cache, extra geometry count)
         const FrameConst fc = tile_arg<PERSIST>(fc_arg, offsetof(SceneFrameArgs, fc));  // (epilogue: flags, sample count)

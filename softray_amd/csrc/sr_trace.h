@@ -492,6 +492,14 @@ __device__ __forceinline__ bool cone_rejects(const CamCone& cm, f2 dxx, f2 dyy, 
     return fminf(fminf(c12.x + m12.x, c12.y + m12.y), c3n.x + m3n.x) < 0.0f || c3n.y > m3n.y;
 }
 
+// the packet walk's form (all 64 lanes call it): the lanes that reject, as a lane mask (vote helpers, sr_device.h); same comparisons
+__device__ __forceinline__ lanemask cone_rejects_wave(const CamCone& cm, f2 dxx, f2 dyy, f2 dzz, float dl) {
+    const f2 c12 = pk_fma((f2){cm.w12x[0], cm.w12x[1]}, dxx, pk_fma((f2){cm.w12y[0], cm.w12y[1]}, dyy, (f2){cm.w12z[0], cm.w12z[1]} * dzz));
+    const f2 c3n = pk_fma((f2){cm.w3nx[0], cm.w3nx[1]}, dxx, pk_fma((f2){cm.w3ny[0], cm.w3ny[1]}, dyy, (f2){cm.w3nz[0], cm.w3nz[1]} * dzz));
+    const f2 m12 = (f2){cm.m12[0], cm.m12[1]} * splat(dl), m3n = (f2){cm.m3n[0], cm.m3n[1]} * splat(dl);
+    return vote(fminf(fminf(c12.x + m12.x, c12.y + m12.y), c3n.x + m3n.x) < 0.0f) | vote(c3n.y > m3n.y);
+}
+
 template <bool FILTER>
 __device__ bool bvh_packet_nearest(const DevScene& sc, int32_t* wnode, bool live, D3 s, D3 d, Hit& out, Ctr& c) {
     D3 end = s + d * 10000.0;
@@ -641,8 +649,11 @@ __device__ bool bvh4_packet_nearest(const DevScene& sc, int32_t* wnode, bool liv
     int32_t bestIdx = 0x7fffffff, bestK = -1;
     int sp = 0;                      // wave-uniform
     int32_t ni = 0;                  // wave-uniform
-    const bool counter_lane = act && (__ffsll((long long)__ballot(act)) - 1) == (int)(threadIdx.x & 63u);
-    if (__ballot(act) != 0ull) {
+    // lane predicates of the walk are lane masks in scalar registers (vote helpers, sr_device.h)
+    const lanemask act_m = __ballot(act);
+    const int lane = (int)(threadIdx.x & 63u);
+    const bool counter_lane = (__ffsll((long long)act_m) - 1) == lane;      // (Ctr bookkeeping: dead code unless the caller reads the counters)
+    if (act_m != 0ull) {
         for (;;) {
             const Bvh4Node n = load_uniform(&sc.b4cam[ni]);            // wave-uniform address: scalar loads
             if (counter_lane) c.nodes++;                               // (per WAVE: 128-byte nodes fetched)
@@ -651,25 +662,25 @@ __device__ bool bvh4_packet_nearest(const DevScene& sc, int32_t* wnode, bool liv
             child_slabs<KNOWN>(n.ch[1], I01, I20, I12, B0, B1, B2, t1, x1);
             child_slabs<KNOWN>(n.ch[2], I01, I20, I12, B0, B1, B2, t2, x2);
             child_slabs<KNOWN>(n.ch[3], I01, I20, I12, B0, B1, B2, t3, x3);
-            const bool h0 = act && n.ch[0].n >= 0 && t0 <= x0 && x0 >= 0.0f, h1 = act && n.ch[1].n >= 0 && t1 <= x1 && x1 >= 0.0f;
-            const bool h2 = act && n.ch[2].n >= 0 && t2 <= x2 && x2 >= 0.0f, h3 = act && n.ch[3].n >= 0 && t3 <= x3 && x3 >= 0.0f;
+            const lanemask h0 = act_m & lanes_if(n.ch[0].n >= 0) & vote(t0 <= x0) & vote(x0 >= 0.0f), h1 = act_m & lanes_if(n.ch[1].n >= 0) & vote(t1 <= x1) & vote(x1 >= 0.0f);
+            const lanemask h2 = act_m & lanes_if(n.ch[2].n >= 0) & vote(t2 <= x2) & vote(x2 >= 0.0f), h3 = act_m & lanes_if(n.ch[3].n >= 0) & vote(t3 <= x3) & vote(x3 >= 0.0f);
             // ---- leaf children in slot order (front to back for this origin).  One copy of the triangle loop per slot, everything
             //      static: picking a slot's count / link / lane mask by a run-time index costs a chain of scalar branches per slot ----
-            const auto leaf = [&](const int cn, const int cc, const bool h, const float t) __attribute__((always_inline)) {
-                const bool hc = h && t <= tlim;                                      // tlim may have shrunk in an earlier leaf
-                if (__ballot(hc) == 0ull) return;
-                const bool hc_first = hc && (__ffsll((long long)__ballot(hc)) - 1) == (int)(threadIdx.x & 63u);
+            const auto leaf = [&](const int cn, const int cc, const lanemask h, const float t) __attribute__((always_inline)) {
+                const lanemask hc = h & vote(t <= tlim);                             // tlim may have shrunk in an earlier leaf
+                if (hc == 0ull) return;
+                const bool hc_first = (__ffsll((long long)hc) - 1) == lane;
                 for (int q = cc; q < cc + cn; ++q) {
-                    bool cand = hc;
+                    lanemask cand = hc;
                     if (FILTER) {
                         const CamCone cm = load_uniform(&sc.bcam[q]);                // scalar load
-                        cand = hc && !cone_rejects(cm, dxx, dyy, dzz, dl);
+                        cand = hc & ~cone_rejects_wave(cm, dxx, dyy, dzz, dl);
                     }
                     if (hc_first) c.geom++;
-                    if (__ballot(cand) != 0ull) {
+                    if (cand != 0ull) {
                         const Rec128* r = &sc.btris[q];                               // wave-uniform address
-                        if (cand && (__ffsll((long long)__ballot(cand)) - 1) == (int)(threadIdx.x & 63u)) c.leaves++;
-                        if (cand) {
+                        if ((__ffsll((long long)cand) - 1) == lane) c.leaves++;
+                        if (lane_of(cand)) {
                             double tt; D3 pos;
                             if (tri_hit(r->p, s, d, tt, pos) && inside(sc.root.lo, sc.root.hi, pos)) {
                                 const int32_t idx = r->aux;
@@ -688,10 +699,10 @@ __device__ bool bvh4_packet_nearest(const DevScene& sc, int32_t* wnode, bool liv
             if (n.ch[3].n > 0) leaf(n.ch[3].n, n.ch[3].c, h3, t3);
             // ---- inner children: far to near; the nearest one some lane wants is entered, the others wait on the stack ----
             int32_t next = -1;
-            if (n.ch[3].n == 0 && __ballot(h3 && t3 <= tlim) != 0ull) next = n.ch[3].c;
-            if (n.ch[2].n == 0 && __ballot(h2 && t2 <= tlim) != 0ull) { if (next >= 0) wnode[sp++] = next; next = n.ch[2].c; }
-            if (n.ch[1].n == 0 && __ballot(h1 && t1 <= tlim) != 0ull) { if (next >= 0) wnode[sp++] = next; next = n.ch[1].c; }
-            if (n.ch[0].n == 0 && __ballot(h0 && t0 <= tlim) != 0ull) { if (next >= 0) wnode[sp++] = next; next = n.ch[0].c; }
+            if (n.ch[3].n == 0 && (h3 & vote(t3 <= tlim)) != 0ull) next = n.ch[3].c;
+            if (n.ch[2].n == 0 && (h2 & vote(t2 <= tlim)) != 0ull) { if (next >= 0) wnode[sp++] = next; next = n.ch[2].c; }
+            if (n.ch[1].n == 0 && (h1 & vote(t1 <= tlim)) != 0ull) { if (next >= 0) wnode[sp++] = next; next = n.ch[1].c; }
+            if (n.ch[0].n == 0 && (h0 & vote(t0 <= tlim)) != 0ull) { if (next >= 0) wnode[sp++] = next; next = n.ch[0].c; }
             if (next >= 0) ni = next;
             else {
                 if (sp == 0) break;

@@ -70,6 +70,7 @@ namespace Engine3D.Hip
         const string Lib = "softray_hip";
         [DllImport(Lib)] public static extern int sr_create(int device, out IntPtr scene);
         [DllImport(Lib)] public static extern int sr_create_multi([In] int[] devices, int n, out IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_last_frame_parts(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_set_gather(IntPtr scene, int kind);                  // 0 peer copies (default), 1 grouped ncclSend / ncclRecv
         [DllImport(Lib)] public static extern int sr_render_device(IntPtr scene, ref SrFrame frame, IntPtr dPixels, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern void sr_destroy(IntPtr scene);
@@ -157,6 +158,9 @@ namespace Engine3D.Hip
             Native.Check(Native.sr_create_multi(devices, devices.Length, out scene));
             if (gatherOverRccl) Native.Check(Native.sr_set_gather(scene, 1));
         }
+
+        /// <summary>How many parts (devices) rendered rows of the last frame: 1 when the first device rendered it whole.</summary>
+        public int LastFrameParts => Native.sr_last_frame_parts(scene);
 
         /// PreCalculate() (Renderer.cs:673-699): MakeRayTracableGeometry_simple (:1452-1469) flattened, then the structure for
         /// `mode`.  Like the reference (geometry_* == null guards, :684-696) nothing is rebuilt while the model and the mode

@@ -76,8 +76,11 @@ enum {
                                      flags and looks the draws up in a table the scene keeps per (seed, length) -- 12 bytes per
                                      sample of the largest row block, SR_ERR_UNSUPPORTED above 256 MiB.  Reads random_seed and
                                      concurrency.  SR_ERR_UNSUPPORTED together with SR_F_SHADOWS (dynamic or static),
-                                     max_bounces > 0, SR_F_SINGLE_KERNEL and strip_count > 1 (a rank would need the hit counts
-                                     of rows it does not render); a multi-device scene renders such a frame on its first device */
+                                     max_bounces > 0 and SR_F_SINGLE_KERNEL.  A multi-device scene splits the frame like any other: its
+                                     parts exchange the hit counts of their rows between the primary pass and the second rays, and
+                                     the row blocks stay those of the whole row range.  Caller-made strips (strip_count > 1, also
+                                     through sr_rccl_render) stay SR_ERR_UNSUPPORTED: one call on one scene cannot know how many
+                                     samples hit in the rows the other ranks render */
     SR_F_SINGLE_KERNEL = 1u << 8, /* library option, not a Renderer field: trace the frame with the one-kernel
                                      renderer (k_render) instead of the k_primary/k_shadow/k_resolve pipeline.
                                      Pixels are identical; kept as an independent cross-check               */
@@ -199,9 +202,12 @@ int  sr_create(int32_t device, sr_scene** out);
  * and the strips are copied straight into the caller's surface (device -> host over each device's own link, or peer-to-peer over
  * xGMI into the device surface, which lives on devices[0]).  The pixels do not depend on n (no reduction, no RNG).  This is
  * how a single-process host -- the C# Renderer -- uses a whole node.  Frames that need one global order (SR_F_STATIC_SHADOWS)
- * or that already carry strip_* fields are rendered by devices[0] alone.  The same ordinal may appear more than once. */
+ * or that already carry strip_* fields are rendered by devices[0] alone (sr_last_frame_parts tells).  The same ordinal may appear more than once. */
 int  sr_create_multi(const int32_t* devices, int32_t n, sr_scene** out);
 int32_t sr_device_count(const sr_scene*);
+/* How many parts (devices) rendered rows of the scene's last frame: 1 for a single-device scene and for a frame that devices[0]
+ * rendered whole (static shadows, caller-made strips), otherwise the number of parts that owned at least one row of the range. */
+int32_t sr_last_frame_parts(const sr_scene*);
 void sr_destroy(sr_scene*);
 
 /* MakeRayTracableGeometry_simple (Renderer.cs:1452-1469): v9 = [n][3 vertices][xyz] in model space

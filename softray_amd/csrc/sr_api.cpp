@@ -123,6 +123,13 @@ struct sr_scene {
     DBuf d_pt_table;
     int32_t pt_table_seed = 0;
     size_t  pt_table_samples = 0;
+    // (part of a multi-device scene, path tracing) hits per image row of the frame's row range: the part's own rows after the first phase,
+    // every part's after the exchange (multi_render); the hits that precede each of the part's compact rows inside its row block
+    DBuf d_pt_row_hits, d_pt_row_k0;
+    hipEvent_t pt_counted = nullptr;     // ... the part's counts of the current frame have reached pt_counts_host of the multi scene
+    // (multi-device scene) where the parts' row counts meet: portable pinned host memory, one word per row of the range
+    void* pt_counts_host = nullptr; size_t pt_counts_cap = 0;
+    int32_t last_parts = 1;              // sr_last_frame_parts
     bool shadow_cache_empty = true;      // the device cache must be zeroed before its next use
     DBuf d_pixels, d_aa, d_stats, d_io[9];
     // per-frame tables (area-light offsets + row map): pinned host staging and device copies, double-buffered; a slot is
@@ -314,7 +321,6 @@ int check_path_tracing(const sr_frame* f) {
     if (f->flags & SR_F_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "path tracing together with shadows (dynamic or static) is not supported");
     if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "path tracing together with mirror bounces (max_bounces > 0) is not supported");
     if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "path tracing is not built into the one-kernel renderer (SR_F_SINGLE_KERNEL)");
-    if (f->strip_count > 1) return fail(SR_ERR_UNSUPPORTED, "path tracing with row strips: a rank would need the hit counts of rows it does not render");
     return SR_OK;
 }
 
@@ -424,11 +430,16 @@ int next_events(sr_scene* s, int k, hipEvent_t& a, hipEvent_t& b) {
     return SR_OK;
 }
 
-int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats) {
+// pt_phase: 0, or the phase (1, 2) of a part of a path-traced frame that multi_render has split (sr_device.h PipelineLaunch::pt_phase)
+int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0) {
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
     if (rc) return rc;
+    // strips that the caller (or sr_rccl_render) made: this one call on this one scene cannot know how many samples hit in the rows the other
+    // ranks render.  The strips of a multi-device scene are the library's own: multi_render exchanges the counts between the two phases
+    if ((f->flags & SR_F_PATH_TRACING) && f->strip_count > 1 && !pt_phase)
+        return fail(SR_ERR_UNSUPPORTED, "path tracing with row strips: a rank would need the hit counts of rows it does not render");
     if ((rc = prepare_frame(s, f, fc))) return rc;
     if ((rc = sync_geometry(s, (uint32_t)f->trace_mode))) return rc;
     if (fc.num_rows == 0) return SR_OK;
@@ -686,10 +697,16 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     // ---- path tracing: the row blocks that each restart Random(random_seed) (Renderer.cs:1655-1666) and the table of its draws ----
     const bool path = (f->flags & SR_F_PATH_TRACING) != 0;
     int pt_block_height = 0, pt_blocks = 0;
+    int pt_range_first = 0, pt_range_rows = 0;
     if (path) {
         const long long conc = f->concurrency > 0 ? f->concurrency : 4;
-        pt_block_height = (int)(((long long)fc.num_rows - 1 + conc) / conc);
-        pt_blocks = (fc.num_rows + pt_block_height - 1) / pt_block_height;
+        // (a part of a split frame: the blocks are those of the whole row range, not of the rows the part owns)
+        int ra, rb;
+        clamp_rows(f, ra, rb);
+        pt_range_first = ra; pt_range_rows = rb - ra + 1;
+        const int block_rows = pt_phase ? pt_range_rows : fc.num_rows;
+        pt_block_height = (int)(((long long)block_rows - 1 + conc) / conc);
+        pt_blocks = (block_rows + pt_block_height - 1) / pt_block_height;
         const long long block_samples = (long long)pt_block_height * fc.width * n2;
         if (block_samples * 12 > kMaxPathTable)
             return fail(SR_ERR_UNSUPPORTED, "path tracing: the random table of the largest row block (12 bytes per sample) exceeds 256 MiB; raise concurrency or render row ranges");
@@ -705,6 +722,13 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         }
     }
     const bool path_walk = path && f->trace_mode == SR_MODE_BVH;
+    // (path tracing never runs as two halves: the part's rows are one band when they fit the budget)
+    const bool pt_reuse = pt_phase && band_rows >= fc.num_rows;
+    if (pt_phase) {
+        SR_HIP(s->d_pt_row_hits.reserve((size_t)pt_range_rows * 4));
+        SR_HIP(s->d_pt_row_k0.reserve((size_t)fc.num_rows * 4));
+        if (pt_phase == 1) SR_HIP(hipMemsetAsync(s->d_pt_row_hits.p, 0, (size_t)pt_range_rows * 4, stream));
+    }
     for (auto& sc : s->scratch) sc.used_last_frame = false;
     for (int h = 0; h < halves; ++h) {
         sr_scene::BandScratch& B = s->scratch[h];
@@ -801,6 +825,12 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.pt_table = path ? (const int32_t*)s->d_pt_table.p : nullptr;
         P.pt_block_height = pt_block_height;
         P.pt_blocks = pt_blocks;
+        P.pt_phase = path ? pt_phase : 0;
+        P.pt_reuse = pt_reuse;
+        P.pt_row_hits = pt_phase ? (uint32_t*)s->d_pt_row_hits.p : nullptr;
+        P.pt_row_k0 = pt_phase ? (uint32_t*)s->d_pt_row_k0.p : nullptr;
+        P.pt_range_first = pt_range_first;
+        P.pt_range_rows = pt_range_rows;
         P.ray_sort_buf = (bounce_pipe || path_walk) ? (unsigned int*)B.ray_sort.p : nullptr;
         P.ray_sort_temp = (bounce_pipe || path_walk) ? B.ray_sort_temp.p : nullptr;
         P.ray_sort_temp_bytes = (bounce_pipe || path_walk) ? sr::ray_sort_temp_bytes((unsigned)band_samples) : 0;
@@ -846,7 +876,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.shadows_on_bvh = shadows_on_bvh;
         P.primary_stats_only = (f->flags & SR_F_PRIMARY_STATS_ONLY) != 0;
         P.round2_node_budget = s->dbg[SR_DBG_ROUND2_NODES] >= 0 ? (int32_t)std::min<int64_t>(s->dbg[SR_DBG_ROUND2_NODES], 1 << 30) : 0;
-        P.stats = d_stats;
+        P.stats = (pt_phase == 1 && !pt_reuse) ? nullptr : d_stats;      // (a counting pass that phase 2 repeats: its rays are counted there)
         P.stream = bs;
         P.user = s;
         P.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
@@ -905,7 +935,8 @@ std::vector<StripRun> strip_runs(int a, int b, int n, int g) {
 
 // copy the runs of one part to the full surface `dst` (host or device memory): the full strips between the (possibly
 // partial) first and last one form an arithmetic progression -> ONE strided 2-D copy; the edges are copied on their own
-hipError_t copy_runs(const std::vector<StripRun>& runs, int n, int width, const uint32_t* src, uint32_t* dst, hipMemcpyKind kind, hipStream_t st) {
+// (src_strided: the source is laid out like the destination -- compact_row == image_row -- so its full strips are n strips apart too)
+hipError_t copy_runs(const std::vector<StripRun>& runs, int n, int width, const uint32_t* src, uint32_t* dst, hipMemcpyKind kind, hipStream_t st, bool src_strided = false) {
     const size_t row_bytes = (size_t)width * 4;
     size_t i = 0;
     while (i < runs.size()) {
@@ -914,7 +945,7 @@ hipError_t copy_runs(const std::vector<StripRun>& runs, int n, int width, const 
                runs[j + 1].image_row - runs[j].image_row == (int64_t)n * kMultiStripRows) ++j;
         if (j > i) {
             const size_t strip_bytes = row_bytes * kMultiStripRows;
-            hipError_t e = hipMemcpy2DAsync(dst + runs[i].image_row * width, strip_bytes * n, src + runs[i].compact_row * width, strip_bytes,
+            hipError_t e = hipMemcpy2DAsync(dst + runs[i].image_row * width, strip_bytes * n, src + runs[i].compact_row * width, src_strided ? strip_bytes * n : strip_bytes,
                                             strip_bytes, j - i + 1, kind, st);
             if (e != hipSuccess) return e;
             i = j + 1;
@@ -928,7 +959,7 @@ hipError_t copy_runs(const std::vector<StripRun>& runs, int n, int width, const 
 }
 
 // frames that cannot be split (one global fill order) are rendered whole by the first part
-bool multi_splittable(const sr_frame* f) { return !((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) && !(f->flags & SR_F_PATH_TRACING) && f->strip_count <= 0; }
+bool multi_splittable(const sr_frame* f) { return !((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) && f->strip_count <= 0; }
 
 // a part of a multi-device scene takes the first part's model by reference: counts, box and flags here, the arrays stay with `src`
 // (sync_geometry uploads from them); nothing of the size of the model is copied on the host
@@ -1017,6 +1048,7 @@ int sr_create_multi(const int32_t* devices, int32_t n, sr_scene** out) {
 }
 
 int32_t sr_device_count(const sr_scene* s) { return !s ? 0 : (s->parts.empty() ? (s->device >= 0 ? 1 : 0) : (int32_t)s->parts.size()); }
+int32_t sr_last_frame_parts(const sr_scene* s) { return !s ? 0 : (s->parts.empty() ? 1 : s->last_parts); }
 
 void sr_destroy(sr_scene* s) {
     if (!s) return;
@@ -1028,13 +1060,14 @@ void sr_destroy(sr_scene* s) {
         }
         if (s->multi_done && use_device(s->parts[0]) == SR_OK) (void)hipEventDestroy(s->multi_done);
         if (use_device(s->parts[0]) == SR_OK) s->d_gather.release();
-        for (sr_scene* q : s->parts) sr_destroy(q);
+        for (sr_scene* q : s->parts) sr_destroy(q);                 // (frees device memory: whatever still read the pinned counts has run)
+        if (s->pt_counts_host) (void)hipHostFree(s->pt_counts_host);
         delete s;
         return;
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
-                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_pt_table, &s->d_pixels, &s->d_aa, &s->d_stats};
+                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
         for (auto& t : s->tables) { t.dev.release(); if (t.host) (void)hipHostFree(t.host); if (t.used) (void)hipEventDestroy(t.used); if (t.ready) (void)hipEventDestroy(t.ready); }
@@ -1047,6 +1080,7 @@ void sr_destroy(sr_scene* s) {
         if (s->pre_ready) (void)hipEventDestroy(s->pre_ready);
         if (s->pre_used) (void)hipEventDestroy(s->pre_used);
         if (s->multi_done) (void)hipEventDestroy(s->multi_done);
+        if (s->pt_counted) (void)hipEventDestroy(s->pt_counted);
         for (DBuf& b : s->d_io) b.release();
         s->d_gather.release();
         if (s->comm) { const sr::RcclApi* api = sr::rccl_api(nullptr); if (api) (void)api->CommDestroy(s->comm); s->comm = nullptr; }
@@ -1291,6 +1325,7 @@ static int multi_render(sr_scene* m, const sr_frame* f, int32_t* host_pixels, vo
     if (rc) return rc;
     if (d_stats) return fail(SR_ERR_UNSUPPORTED, "device-side statistics are per device: use sr_render / sr_last_ray_stats with a multi-device scene");
     const int n = (int)m->parts.size();
+    m->last_parts = 1;
     if (!multi_splittable(f)) {                                     // static shadow cache / caller-made strips: the first part renders it
         rc = host_pixels ? sr_render(m->parts[0], f, host_pixels, stats4) : sr_render_device(m->parts[0], f, d_pixels, user_stream, nullptr);
         std::memcpy(m->last_stats, m->parts[0]->last_stats, sizeof(m->last_stats));     // sr_last_ray_stats(multi scene) reports this frame
@@ -1299,14 +1334,31 @@ static int multi_render(sr_scene* m, const sr_frame* f, int32_t* host_pixels, vo
     if ((rc = check_mode(m->parts[0], f->trace_mode))) return rc;
     int a, b;
     clamp_rows(f, a, b);
-    if (b < a) { if (stats4) std::memset(stats4, 0, 4 * sizeof(uint64_t)); return SR_OK; }
+    if (b < a) { m->last_parts = 0; if (stats4) std::memset(stats4, 0, 4 * sizeof(uint64_t)); return SR_OK; }
     // ---- every part enqueues its strips on its own device and stream (nothing below waits for a GPU until all have been enqueued) ----
     std::vector<sr_frame> fg(n, *f);
     std::vector<int64_t> counts(n, 0);
+    m->last_parts = 0;
     for (int g = 0; g < n; ++g) {
-        sr_scene* q = m->parts[g];
         fg[g].strip_rows = kMultiStripRows; fg[g].strip_count = n; fg[g].strip_index = g;
         counts[g] = sr_frame_pixel_count(&fg[g]);
+        if (counts[g]) m->last_parts++;
+    }
+    // a path-traced frame runs in two phases per part, with the exchange of the rows' hit counts between them (sr_pipeline.hip k_pt_row_hits)
+    const bool path = (f->flags & SR_F_PATH_TRACING) != 0;
+    const size_t range_rows = (size_t)(b - a + 1);
+    if (path && range_rows * 4 > m->pt_counts_cap) {
+        if (m->pt_counts_host) {                                    // an earlier frame's copies may still read the old array
+            for (sr_scene* q : m->parts) if (q->io_stream) { if ((rc = use_device(q))) return rc; SR_HIP(hipStreamSynchronize(q->io_stream)); }
+            SR_HIP(hipHostFree(m->pt_counts_host));
+        }
+        m->pt_counts_host = nullptr; m->pt_counts_cap = 0;
+        SR_HIP(hipHostMalloc(&m->pt_counts_host, range_rows * 4, hipHostMallocPortable));
+        m->pt_counts_cap = range_rows * 4;
+    }
+    std::vector<hipEvent_t> exchanged(n, nullptr);                 // (SR_DBG_KERNEL_TIMING) stop events of the parts' exchange
+    for (int g = 0; g < n; ++g) {
+        sr_scene* q = m->parts[g];
         if (counts[g] == 0) continue;
         if ((rc = check_mode(q, f->trace_mode))) return rc;
         if ((rc = use_device(q))) return rc;
@@ -1320,9 +1372,38 @@ static int multi_render(sr_scene* m, const sr_frame* f, int32_t* host_pixels, vo
             SR_HIP(hipMemsetAsync(q->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), q->io_stream));
             ds = (unsigned long long*)q->d_stats.p;
         }
+        if (path) {
+            // phase 1, then the part's own rows of the counts travel to the pinned array (the rows of the other parts stay theirs)
+            if ((rc = render_common(q, &fg[g], (uint32_t*)q->d_pixels.p, q->io_stream, ds, 1))) return rc;
+            std::vector<StripRun> runs = strip_runs(a, b, n, g);
+            for (StripRun& r : runs) { r.image_row -= a; r.compact_row = r.image_row; }
+            hipEvent_t x0 = nullptr;                                // the exchange as this part sees it: its copy out, the wait for the others, the copy back
+            if ((rc = next_events(q, sr::K_PT_EXCHANGE, x0, exchanged[g]))) return rc;
+            if (x0) SR_HIP(hipEventRecord(x0, q->io_stream));
+            SR_HIP(copy_runs(runs, n, 1, (const uint32_t*)q->d_pt_row_hits.p, (uint32_t*)m->pt_counts_host, hipMemcpyDeviceToHost, q->io_stream, true));
+            if (!q->pt_counted) SR_HIP(hipEventCreateWithFlags(&q->pt_counted, hipEventDisableTiming));
+            SR_HIP(hipEventRecord(q->pt_counted, q->io_stream));
+            continue;
+        }
         if ((rc = render_common(q, &fg[g], (uint32_t*)q->d_pixels.p, q->io_stream, ds))) return rc;
         if (!q->multi_done) SR_HIP(hipEventCreateWithFlags(&q->multi_done, hipEventDisableTiming));
         SR_HIP(hipEventRecord(q->multi_done, q->io_stream));
+    }
+    if (path) {
+        // every part's first phase is enqueued: now each part waits for all the counts (events only), takes the complete array and goes on.
+        // The rows of a part that owns none stay zero.  Through host memory whatever the devices can read of each other: 4 bytes per row
+        // (every row of the range has exactly one owner, so the array is rewritten whole each frame; a part without rows records no event)
+        for (int g = 0; g < n; ++g) {
+            sr_scene* q = m->parts[g];
+            if (counts[g] == 0) continue;
+            if ((rc = use_device(q))) return rc;
+            for (int h = 0; h < n; ++h) if (h != g && counts[h]) SR_HIP(hipStreamWaitEvent(q->io_stream, m->parts[h]->pt_counted, 0));
+            SR_HIP(hipMemcpyAsync(q->d_pt_row_hits.p, m->pt_counts_host, range_rows * 4, hipMemcpyHostToDevice, q->io_stream));
+            if (exchanged[g]) SR_HIP(hipEventRecord(exchanged[g], q->io_stream));
+            if ((rc = render_common(q, &fg[g], (uint32_t*)q->d_pixels.p, q->io_stream, stats4 ? (unsigned long long*)q->d_stats.p : nullptr, 2))) return rc;
+            if (!q->multi_done) SR_HIP(hipEventCreateWithFlags(&q->multi_done, hipEventDisableTiming));
+            SR_HIP(hipEventRecord(q->multi_done, q->io_stream));
+        }
     }
     // ---- the strips go straight to the caller's surface ----
     if (host_pixels) {

@@ -41,7 +41,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_COUNT = 13 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_COUNT = 15 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -93,6 +93,14 @@ struct PipelineLaunch {
     uint32_t*     pt_carry;     // device [pt_blocks]: hits of every row block in the bands rendered so far (zeroed by launch_pipeline)
     const int32_t* pt_table;    // device: InternalSample() ints of Random(random_seed), 3 per sample of the largest row block
     int32_t       pt_block_height, pt_blocks;   // rows per row block and their number (Renderer.cs:1655-1666)
+    // a part of a path-traced frame that a multi-device scene has split (0 / nullptr otherwise): the row blocks are those of the whole
+    // row range [pt_range_first, pt_range_first + pt_range_rows), of which this launch renders the rows of row_map
+    int32_t       pt_phase;     // 0: a whole frame.  1: primary pass + hit-index scan + the rows' hit counts -> pt_row_hits, no pixels.
+                                // 2: pt_row_k0 from the merged pt_row_hits, then the second rays and the pixels
+    bool          pt_reuse;     // the part's rows are one band: phase 2 starts from the queue, flags and scan phase 1 left (it repeats them otherwise)
+    uint32_t*     pt_row_hits;  // device [pt_range_rows]: hits per image row of the range (phase 1 writes the part's rows, phase 2 reads all)
+    uint32_t*     pt_row_k0;    // device [fc.num_rows]: hits of any part that precede the compact row inside its row block
+    int32_t       pt_range_first, pt_range_rows;
     void*         static_hits;  // device HitRec[min(band samples, 128^3)]: generators of a static-shadow frame
     unsigned long long* static_claim; // device [128^3]: smallest order key that asked for an empty cell
     int32_t       static_concurrency; // rayTraceConcurrency of the frame

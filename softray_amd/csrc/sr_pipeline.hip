@@ -3331,6 +3331,67 @@ __global__ __launch_bounds__(256) void k_pt_scan_totals(uint32_t* __restrict__ t
     if (threadIdx.x == 255u) totals[chunks] = base;
 }
 
+// A part of a frame that a multi-device scene has split (the part renders interleaved strips of the row range, sr_api.cpp multi_render):
+// the hit index of a sample counts the hits of ALL parts that precede it in its row block, and the blocks are those of the whole range,
+// so a block boundary may lie inside a strip and a strip may straddle blocks.
+//   k_pt_row_hits     hits of every compact row of the band -> row_hits[image row - first row of the range] (owned rows only; the
+//                     array is zeroed at the start of the frame, the parts' arrays are merged by the host layer)
+//   k_pt_row_base     from the complete per-row counts: exclusive prefix sum that restarts at every block boundary, gathered into
+//                     row_k0[compact row] through the part's row map
+//   k_pt_prep<true>   k = row_k0[compact row] + prefix(position) - prefix(first position of the row)
+// Counts are only ever stored or summed in a fixed order: no atomic decides anything.
+__global__ __launch_bounds__(256) void k_pt_row_hits(PtBand band, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ totals,
+                                                     const int32_t* __restrict__ row_map, int32_t range_first, uint32_t* __restrict__ row_hits) {
+    const uint32_t rows = band.n / band.row_samples;
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= rows) return;
+    row_hits[row_map[band.row_begin + (int32_t)j] - range_first] =
+        pt_before(idx, totals, band.n, (j + 1u) * band.row_samples) - pt_before(idx, totals, band.n, j * band.row_samples);
+}
+
+// one workgroup per row block: passes of 256 rows, each an inclusive __shfl_up scan inside the wave, the four wave totals through LDS
+// (double-buffered: one barrier per pass), a running base from pass to pass.  The row map is sorted: a binary search finds the compact
+// row of an image row, or that the part does not own it.  (LDS: 32 bytes)
+__global__ __launch_bounds__(256) void k_pt_row_base(const uint32_t* __restrict__ row_hits, int32_t range_rows, int32_t block_height, int32_t range_first,
+                                                     const int32_t* __restrict__ row_map, int32_t num_rows, uint32_t* __restrict__ row_k0) {
+    __shared__ uint32_t s_wave[2][4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * block_height, r1 = min(r0 + (int64_t)block_height, (int64_t)range_rows);
+    uint32_t running = 0;
+    int pass = 0;
+    for (int64_t base = r0; base < r1; base += 256, ++pass) {                          // (wave-uniform trip count: the barrier is safe)
+        const int64_t i = base + threadIdx.x;
+        const uint32_t v = i < r1 ? row_hits[i] : 0u;
+        uint32_t incl = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= (uint32_t)d) incl += up;
+        }
+        if (lane == 63u) s_wave[pass & 1][wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; ++w) {
+            const uint32_t c = s_wave[pass & 1][w];
+            if (w < wave) before += c;
+            all += c;
+        }
+        if (i < r1) {
+            const int32_t row = range_first + (int32_t)i;
+            int32_t lo = 0, hi = num_rows;                                             // first compact row whose image row is >= row
+            while (lo < hi) {
+                const int32_t mid = lo + ((hi - lo) >> 1);
+                if (row_map[mid] < row) lo = mid + 1; else hi = mid;
+            }
+            if (lo < num_rows && row_map[lo] == row) row_k0[lo] = running + before + incl - v;
+        }
+        running += all;
+    }
+}
+
+// STRIP: the part of a split frame (row_k0, see above); `carry` is then not read
+template <bool STRIP>
 __global__ __launch_bounds__(256) void k_pt_prep(PtBand band, const HitRec* __restrict__ hits, const unsigned int* __restrict__ count,
                                                  const uint32_t* __restrict__ idx, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ carry,
                                                  const int32_t* __restrict__ table, HitRec* __restrict__ rays) {
@@ -3338,10 +3399,16 @@ __global__ __launch_bounds__(256) void k_pt_prep(PtBand band, const HitRec* __re
     for (unsigned int r = blockIdx.x * 256u + threadIdx.x; r < total; r += stride) {
         const HitRec h = hits[r];
         const uint32_t p = h.sample - band.sample_base;
-        const int32_t block = (band.row_begin + (int32_t)(p / band.row_samples)) / band.block_height;
-        const int32_t first = block * band.block_height - band.row_begin;            // the block's first row, band-local (< 0: an earlier band)
-        const uint32_t p0 = first > 0 ? (uint32_t)first * band.row_samples : 0u;
-        const size_t k = (size_t)carry[block] + (size_t)(pt_before(idx, totals, band.n, p) - pt_before(idx, totals, band.n, p0));
+        size_t k;
+        if constexpr (STRIP) {
+            const uint32_t row = p / band.row_samples;                               // band-local compact row; carry = row_k0
+            k = (size_t)carry[band.row_begin + (int32_t)row] + (size_t)(pt_before(idx, totals, band.n, p) - pt_before(idx, totals, band.n, row * band.row_samples));
+        } else {
+            const int32_t block = (band.row_begin + (int32_t)(p / band.row_samples)) / band.block_height;
+            const int32_t first = block * band.block_height - band.row_begin;        // the block's first row, band-local (< 0: an earlier band)
+            const uint32_t p0 = first > 0 ? (uint32_t)first * band.row_samples : 0u;
+            k = (size_t)carry[block] + (size_t)(pt_before(idx, totals, band.n, p) - pt_before(idx, totals, band.n, p0));
+        }
         // RandomRayInHemisphere (PathTracingMethod.cs:98-103); NextDouble() = InternalSample() * (1.0 / int.MaxValue)
         const double ux = table[3 * k] * (1.0 / 2147483647.0), uy = table[3 * k + 1] * (1.0 / 2147483647.0), uz = table[3 * k + 2] * (1.0 / 2147483647.0);
         const D3 n = mk(h.nrm[0], h.nrm[1], h.nrm[2]);
@@ -3969,7 +4036,7 @@ static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     hipError_t e;
     hipEvent_t e0, e1;
-    pipe_events(L, K_PATHTRACE, e0, e1);
+    pipe_events(L, L.pt_phase == 1 ? K_PT_COUNT : K_PATHTRACE, e0, e1);
     if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
     PtBand band;
     band.n = (uint32_t)((long long)row_count * L.fc.width * n2);
@@ -3982,14 +4049,30 @@ static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int
     const unsigned blocks = (unsigned)std::min<long long>(((long long)band.n + 255) / 256, (long long)L.persistent_blocks);
     const HitRec* hits = (const HitRec*)L.hits;
     HitRec* rays = (HitRec*)L.hits2;
-    if ((e = hipMemsetAsync(L.pt_flags, 0, band.n, L.stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pt_mark, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, L.pt_flags);
-    hipLaunchKernelGGL(k_pt_scan, dim3(chunks), dim3(256), 0, L.stream, (const uint8_t*)L.pt_flags, band.n, L.pt_index, L.pt_totals);
-    hipLaunchKernelGGL(k_pt_scan_totals, dim3(1), dim3(256), 0, L.stream, L.pt_totals, chunks);
-    hipLaunchKernelGGL(k_pt_prep, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
-                       (const uint32_t*)L.pt_carry, L.pt_table, rays);
-    hipLaunchKernelGGL(k_pt_carry, dim3((unsigned)((L.pt_blocks + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
-                       L.pt_carry, (int)L.pt_blocks);
+    // a part of a split frame (L.pt_phase, sr_device.h): phase 1 ends with the rows' hit counts; phase 2 starts from the scan that
+    // phase 1 left when the part is one band (L.pt_reuse), and reads row_k0 where the whole frame reads the blocks' carries
+    if (L.pt_phase != 2 || !L.pt_reuse) {
+        if ((e = hipMemsetAsync(L.pt_flags, 0, band.n, L.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_pt_mark, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, L.pt_flags);
+        hipLaunchKernelGGL(k_pt_scan, dim3(chunks), dim3(256), 0, L.stream, (const uint8_t*)L.pt_flags, band.n, L.pt_index, L.pt_totals);
+        hipLaunchKernelGGL(k_pt_scan_totals, dim3(1), dim3(256), 0, L.stream, L.pt_totals, chunks);
+    }
+    if (L.pt_phase == 1) {
+        hipLaunchKernelGGL(k_pt_row_hits, dim3((unsigned)((row_count + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                           L.row_map, L.pt_range_first, L.pt_row_hits);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        return hipSuccess;
+    }
+    if (L.pt_phase == 2) {
+        hipLaunchKernelGGL(k_pt_prep<true>, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                           (const uint32_t*)L.pt_row_k0, L.pt_table, rays);
+    } else {
+        hipLaunchKernelGGL(k_pt_prep<false>, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                           (const uint32_t*)L.pt_carry, L.pt_table, rays);
+        hipLaunchKernelGGL(k_pt_carry, dim3((unsigned)((L.pt_blocks + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                           L.pt_carry, (int)L.pt_blocks);
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
     if constexpr (MODE == MODE_BVH) {
@@ -4037,20 +4120,48 @@ static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int
     return hipSuccess;
 }
 
+static hipError_t launch_resolve(const PipelineLaunch& L, int row_begin, int row_count) {
+    hipError_t e;
+    hipEvent_t e0, e1;
+    pipe_events(L, K_RESOLVE, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    long long npx = (long long)row_count * L.fc.width;
+    hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, row_count,
+                       (const uint32_t*)L.samples, L.pixels);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
 template <int MODE, bool EXTRA>
 static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     const bool shadows = (L.fc.flags & 2u) != 0;
     const bool path = (L.fc.flags & kFlagPathTracing) != 0;          // (sr_api.cpp: never together with shadows or mirror bounces)
-    if (path) {
+    if (path && L.pt_phase == 0) {
         hipError_t e = hipMemsetAsync(L.pt_carry, 0, (size_t)L.pt_blocks * sizeof(uint32_t), L.stream);
         if (e != hipSuccess) return e;
     }
+    if (path && L.pt_phase == 2) {
+        // the part's row bases from the merged per-row counts of all parts: one workgroup per row block of the range
+        const unsigned nblocks = (unsigned)((L.pt_range_rows + L.pt_block_height - 1) / L.pt_block_height);
+        hipLaunchKernelGGL(k_pt_row_base, dim3(nblocks), dim3(256), 0, L.stream, (const uint32_t*)L.pt_row_hits, L.pt_range_rows, L.pt_block_height, L.pt_range_first,
+                           L.row_map, L.fc.num_rows, L.pt_row_k0);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    const bool pt_second_pass = path && L.pt_phase == 2 && L.pt_reuse;       // the band's primary pass and scan are phase 1's
     // rows are processed in bands so that the hit queue / sample buffer stay within their allocation
     for (int row_begin = L.row_first; row_begin < L.row_limit; row_begin += L.band_rows) {
         int row_count = std::min(L.band_rows, L.row_limit - row_begin);
         uint32_t* samples = (n2 == 1) ? L.pixels : L.samples;
         hipError_t e;
+        if (pt_second_pass) {
+            if ((e = launch_pathtrace_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
+            if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
+            if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);
+            continue;
+        }
         e = hipMemsetAsync(L.counters, 0, kCounterWords * sizeof(unsigned int), L.stream);   // the band's counters and both kernels' tile heads
         if (e != hipSuccess) return e;
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -4190,18 +4301,9 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
             }
         } else if (path) {
             if ((e = launch_pathtrace_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
+            if (L.pt_phase == 1) continue;                           // the counting pass of a split frame: its pixels are phase 2's
         }
-        if (n2 > 1) {
-            e0 = e1 = nullptr;
-            if (L.get_events) L.get_events(L.user, K_RESOLVE, &e0, &e1);
-            if (e0) { e = hipEventRecord(e0, L.stream); if (e != hipSuccess) return e; }
-            long long npx = (long long)row_count * L.fc.width;
-            hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, row_count,
-                               (const uint32_t*)L.samples, L.pixels);
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            if (e1) { e = hipEventRecord(e1, L.stream); if (e != hipSuccess) return e; }
-        }
+        if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
         if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);
     }
     return hipSuccess;

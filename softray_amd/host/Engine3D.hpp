@@ -210,6 +210,7 @@ public:
     Renderer(const Renderer&) = delete;
     Renderer& operator=(const Renderer&) = delete;
     void Dispose() { if (scene_) { sr_destroy(scene_); scene_ = nullptr; } }   // Renderer.cs:236
+    int gpuLastFrameParts() const { return scene_ ? sr_last_frame_parts(scene_) : 0; }   // parts (devices) that rendered rows of the last frame
 
     uint32_t BackgroundColor() const { return backgroundColor_; }
     void BackgroundColor(uint32_t v) { backgroundColor_ = v & 0x00FFFFFFu; }   // Renderer.cs:308-321

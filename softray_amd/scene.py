@@ -40,6 +40,10 @@ class GpuScene:
     def device_count(self):
         return int(_lib.lib().sr_device_count(self._h))
 
+    def last_frame_parts(self):
+        """How many parts of the scene rendered rows of the last frame (1: a single-device scene, or a frame the first device rendered whole)."""
+        return int(_lib.lib().sr_last_frame_parts(self._h))
+
     def close(self):
         if getattr(self, "_h", None):
             try:

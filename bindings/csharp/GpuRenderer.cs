@@ -113,6 +113,10 @@ namespace Engine3D.Hip
         /// (the row blocks that each restart the random sequence).  Not together with F_SHADOWS: the library answers
         /// SR_ERR_UNSUPPORTED, which Check turns into InvalidOperationException.
         public const uint F_PATH_TRACING = 1u << 6;
+        /// rayTraceVoxels (Renderer.cs:1568-1588) = SR_F_VOXELS: the library walks its own 64^3 grid of the uploaded triangles instead of the
+        /// model's tree and the extra geometry; trace_mode is ignored and nothing needs building.  Not together with F_SHADOWS,
+        /// F_PATH_TRACING or mirror bounces (SR_ERR_UNSUPPORTED -> InvalidOperationException): keep the CPU chain for those.
+        public const uint F_VOXELS = 1u << 7;
         const uint F_PRIMARY_STATS_ONLY = 1u << 12;     // Num* count primary rays (Renderer.cs:1916-1923): no counting in the shadow stage
         public const int MODE_REF_TREE = 0, MODE_BRUTE = 1, MODE_BVH = 2;
         /// How NumGeometryTests / NumNodeVisits / NumLeafNodeVisits (Renderer.cs:476-504) are answered -- an explicit choice of the
@@ -165,7 +169,8 @@ namespace Engine3D.Hip
         /// PreCalculate() (Renderer.cs:673-699): MakeRayTracableGeometry_simple (:1452-1469) flattened, then the structure for
         /// `mode`.  Like the reference (geometry_* == null guards, :684-696) nothing is rebuilt while the model and the mode
         /// stay the same -- Renderer.Render() calls PreCalculate() every frame.
-        public void Upload(Model model, int mode)
+        /// voxels: the frames will carry F_VOXELS (rayTraceVoxels): only the triangles are needed, no structure is built.
+        public void Upload(Model model, int mode, bool voxels = false)
         {
             if (!ReferenceEquals(model, uploaded))
             {
@@ -186,6 +191,7 @@ namespace Engine3D.Hip
                 uploaded = model;
                 builtModes = 0;
             }
+            if (voxels) return;                                                                      // SR_F_VOXELS ignores trace_mode
             uint bit = 1u << mode;
             if (mode == MODE_REF_TREE && UsesOwnBvh(model)) bit = 1u << MODE_BVH;                    // large model (or Off): only the own BVH is needed
             else if (mode == MODE_REF_TREE && model.Triangles.Count > 0) bit |= 1u << MODE_BVH;      // shadow rays of a tree frame take the shaft path

@@ -81,6 +81,16 @@ enum {
                                      the row blocks stay those of the whole row range.  Caller-made strips (strip_count > 1, also
                                      through sr_rccl_render) stay SR_ERR_UNSUPPORTED: one call on one scene cannot know how many
                                      samples hit in the rows the other ranks render */
+    SR_F_VOXELS      = 1u << 7,   /* rayTraceVoxels (Renderer.cs:1568-1588): rootGeometry = the model as a 64^3 VoxelGrid instead of the model's tree AND
+                                     the extra geometry (both ignored); the decorators above it stay.  A ray is clipped to the box (-1,-1,-1)..(1,1,1),
+                                     scaled to grid coordinates and walked in fixed steps of 0.1 along its longest axis (VoxelGrid.cs:125-177,
+                                     LineWalker3D.cs:17-35); the first non-empty cell is the hit: its colour (the average of the colours of the triangles
+                                     whose box of cells holds it) and the normal of its lowest-index triangle, pos = (0,0,0), rayFrac = 0.  Ignores
+                                     trace_mode and needs no sr_build, only triangles: the first such frame calls sr_build_voxels.  Works with
+                                     SR_F_SHADING, the lights, sub_pixel_res, SR_F_FOCAL_BLUR, row ranges, strips, multi-device scenes and
+                                     sr_rccl_render.  Statistics: one ray and one geometry test per camera sample, no nodes, no leaves.
+                                     SR_ERR_UNSUPPORTED together with SR_F_SHADOWS (dynamic or static), SR_F_PATH_TRACING, max_bounces > 0 and
+                                     SR_F_SINGLE_KERNEL: the reference's result there is an artefact of rayFrac = 0 that nothing pins */
     SR_F_SINGLE_KERNEL = 1u << 8, /* library option, not a Renderer field: trace the frame with the one-kernel
                                      renderer (k_render) instead of the k_primary/k_shadow/k_resolve pipeline.
                                      Pixels are identical; kept as an independent cross-check               */
@@ -231,6 +241,17 @@ int  sr_build(sr_scene*, uint32_t modes, int32_t max_depth, int32_t max_per_leaf
  * SR_BUILD_ON_DEVICE insists on the device (SR_ERR_NO_DEVICE for a host-only scene). */
 #define SR_BUILD_ON_DEVICE 0x100u
 #define SR_BUILD_ON_HOST   0x200u
+/* TriMeshToVoxelGrid.Convert(triangles, 64, grid) (TriMeshToVoxelGrid.cs:14-114, Renderer.cs:1570): the voxel grid SR_F_VOXELS frames and
+ * SR_TARGET_VOXELS walk, made from the triangles in index order.  Cell (x,y,z) spans [k/64 - 0.5, (k+1)/64 - 0.5] per axis; a triangle is in
+ * every cell of the box of cells its vertex ranges touch; a cell's colour is the average of its triangles' colours (summed in ascending
+ * triangle index, truncated to bytes, alpha 255; 0 = empty), its normal the plane normal of its lowest-index triangle.  Idempotent; called
+ * implicitly by the first voxel frame; sr_set_triangles / sr_load_3ds drop the grid.  A scene with a device builds it there (from the device
+ * triangle records: (cell, triangle) pairs, a stable sort, one sum per cell; SR_ERR_UNSUPPORTED beyond 2^30 pairs), a host-only scene with a
+ * plain host loop -- two independent implementations of one grid.  The reference's on-disk cache of the grid is not reproduced. */
+int  sr_build_voxels(sr_scene*);
+/* read-back of the grid in [x][y][z] order: colors[64*64*64], normals[64*64*64][3] (either may be NULL); works for a host-only scene;
+ * SR_ERR_NOT_BUILT before sr_build_voxels / the first voxel frame */
+int  sr_get_voxels(sr_scene*, uint32_t* colors, double* normals);
 /* out = TreeDepth, NumNodes, NumLeafNodes, NumInternalNodes (SpatialSubdivision.cs:317-335) */
 int  sr_tree_stats(const sr_scene*, int32_t out[4]);
 /* the library's own BVH: out = depth, inner nodes, triangles, 1 if it was built on the device */
@@ -267,6 +288,9 @@ int64_t sr_frame_pixel_count(const sr_frame*);
  * SR_TARGET_ROOT = the root geometry of the chain (extra geometry + model in `mode`, Renderer.cs:1536-1549).
  * Host arrays; outputs may be NULL.  counters[n][3] = NumRayTests, NumNodesVisited, NumLeafNodesVisited. */
 #define SR_TARGET_ROOT 0x100
+/* target = SR_TARGET_VOXELS: VoxelGrid.IntersectRay (see SR_F_VOXELS): hit, colour and normal; ray_frac and pos are 0, tri_index is -1,
+ * counters are {1, 0, 0} (VoxelGrid.NumRayTests == 1).  Builds the grid when there is none. */
+#define SR_TARGET_VOXELS 0x200
 int  sr_trace_rays(sr_scene*, int32_t target, int64_t n, const double* starts, const double* dirs,
                    uint8_t* hit, double* ray_frac, double* pos, double* normal, uint32_t* color,
                    int32_t* tri_index, int32_t* counters);

@@ -16,6 +16,7 @@ SR_ERR_INVALID_ARG, SR_ERR_OUT_OF_RANGE, SR_ERR_NO_MODEL, SR_ERR_NOT_BUILT = -1,
 SR_ERR_UNSUPPORTED, SR_ERR_NO_DEVICE, SR_ERR_HIP, SR_ERR_FORMAT = -5, -6, -7, -8
 F_SHADING, F_SHADOWS, F_FOCAL_BLUR, F_POINT_LIGHT, F_SPECULAR, F_STATIC_SHADOWS = 1, 2, 4, 8, 16, 32
 F_PATH_TRACING = 1 << 6
+F_VOXELS = 1 << 7
 F_SINGLE_KERNEL = 1 << 8
 F_PER_LANE_SHADOWS = 1 << 9
 F_NO_SPLIT = 1 << 10
@@ -23,6 +24,7 @@ F_LITERAL_SECONDARY = 1 << 11
 F_PRIMARY_STATS_ONLY = 1 << 12
 MODE_REF_TREE, MODE_BRUTE, MODE_BVH = 0, 1, 2
 TARGET_ROOT = 0x100
+TARGET_VOXELS = 0x200
 BUILD_ON_DEVICE = 0x100
 BUILD_ON_HOST = 0x200
 STYLE_STANDARD, STYLE_COLOR_SHUFFLE, STYLE_NEGATIVE, STYLE_DEPTH_SMOOTH, STYLE_DEPTH_BANDED = 0, 1, 2, 3, 4
@@ -36,7 +38,7 @@ SYMBOLS = [
     "sr_post_process", "sr_post_process_device", "sr_anti_alias", "sr_anti_alias_device", "sr_reset_shadow_cache",
     "sr_debug_set", "sr_bvh_stats", "sr_bvh_digest", "sr_wide_tree_stats", "sr_create_multi", "sr_device_count", "sr_last_frame_parts", "sr_shade_points",
     "sr_trace_rays_device", "sr_rccl_unique_id", "sr_rccl_init", "sr_rccl_render", "sr_rccl_gather", "sr_set_gather",
-    "sr_net_random_doubles",
+    "sr_net_random_doubles", "sr_build_voxels", "sr_get_voxels",
 ]
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
@@ -149,6 +151,8 @@ def lib():
     L.sr_rccl_render.restype = i32; L.sr_rccl_render.argtypes = [vp, vp, vp, vp]
     L.sr_rccl_gather.restype = i32; L.sr_rccl_gather.argtypes = [vp, vp, vp, vp, vp]
     L.sr_set_gather.restype = i32; L.sr_set_gather.argtypes = [vp, i32]
+    L.sr_build_voxels.restype = i32; L.sr_build_voxels.argtypes = [vp]
+    L.sr_get_voxels.restype = i32; L.sr_get_voxels.argtypes = [vp, vp, vp]
     L.sr_net_random_doubles.restype = None; L.sr_net_random_doubles.argtypes = [i32, i64, i64, vp]
     L.sr_last_error.restype = C.c_char_p; L.sr_last_error.argtypes = []
     L.sr_abi_version.restype = i32; L.sr_abi_version.argtypes = []

@@ -130,6 +130,13 @@ struct sr_scene {
     // (multi-device scene) where the parts' row counts meet: portable pinned host memory, one word per row of the range
     void* pt_counts_host = nullptr; size_t pt_counts_cap = 0;
     int32_t last_parts = 1;              // sr_last_frame_parts
+    // rayTraceVoxels (SR_F_VOXELS): the 64^3 grid of the current model, made by sr_build_voxels / the first voxel frame and dropped by
+    // sr_set_triangles.  A scene with a device keeps it there (colours, normals, occupancy bits); a host-only scene on the host
+    DBuf d_vox_colors, d_vox_normals, d_vox_mask;
+    std::vector<uint32_t> vox_colors_host;
+    std::vector<double>   vox_normals_host;
+    bool vox_valid = false;
+    sr::RootBox vox_box{};               // AxisAlignedBox((-1,-1,-1), (1,1,1)), VoxelGrid.cs:38
     bool shadow_cache_empty = true;      // the device cache must be zeroed before its next use
     DBuf d_pixels, d_aa, d_stats, d_io[9];
     // per-frame tables (area-light offsets + row map): pinned host staging and device copies, double-buffered; a slot is
@@ -324,6 +331,25 @@ int check_path_tracing(const sr_frame* f) {
     return SR_OK;
 }
 
+// SR_F_VOXELS: the decorators whose result on a voxel hit is the reference's rayFrac = 0 artefact (unpinned) and the one-kernel renderer
+int check_voxels(const sr_frame* f) {
+    if (!(f->flags & SR_F_VOXELS)) return SR_OK;
+    if (f->flags & SR_F_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "voxel rendering together with shadows (dynamic or static) is not supported");
+    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "voxel rendering together with path tracing is not supported");
+    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "voxel rendering together with mirror bounces (max_bounces > 0) is not supported");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "voxel rendering is not built into the one-kernel renderer (SR_F_SINGLE_KERNEL)");
+    return SR_OK;
+}
+
+// what the frame's geometry needs: a voxel frame only triangles (it ignores trace_mode), any other frame its trace mode's structure
+int check_frame_mode(const sr_scene* s, const sr_frame* f) {
+    if (f->flags & SR_F_VOXELS) {
+        if (!s->have_model || s->ntris == 0) return fail(SR_ERR_NO_MODEL, "no model: Render() returns without drawing (Renderer.cs:736-739)");
+        return SR_OK;
+    }
+    return check_mode(s, f->trace_mode);
+}
+
 int validate_frame(const sr_frame* f) {
     if (!f) return fail(SR_ERR_INVALID_ARG, "frame is NULL");
     if (f->width <= 0 || f->height <= 0) return fail(SR_ERR_INVALID_ARG, "surface size must be positive");
@@ -334,7 +360,8 @@ int validate_frame(const sr_frame* f) {
     if ((long long)f->width * f->sub_pixel_res > (1ll << 24) || (long long)f->height > (1ll << 24)) return fail(SR_ERR_INVALID_ARG, "surface too large");
     if (f->max_bounces < 0 || f->max_bounces > 16 || !(f->reflectivity >= 0.0 && f->reflectivity <= 1.0))
         return fail(SR_ERR_INVALID_ARG, "max_bounces must be 0..16 and reflectivity 0..1");
-    return check_path_tracing(f);
+    int rc = check_voxels(f);
+    return rc ? rc : check_path_tracing(f);
 }
 
 void clamp_rows(const sr_frame* f, int& a, int& b) {                  // Renderer.cs:1652-1653
@@ -430,18 +457,75 @@ int next_events(sr_scene* s, int k, hipEvent_t& a, hipEvent_t& b) {
     return SR_OK;
 }
 
+// TriMeshToVoxelGrid.Convert for the scene's model, once per model.  A scene with a device runs sr_voxels.hip's voxeliser from the device triangle
+// records (on `stream`; the call waits for it: the number of (cell, triangle) pairs sizes the sort's buffers); a host-only scene runs the plain
+// host loop (sr_host.cpp voxelise_host)
+const long long kMaxVoxelPairs = 1ll << 30;
+int ensure_voxels(sr_scene* s, hipStream_t stream) {
+    if (s->vox_valid) return SR_OK;
+    const size_t cells = (size_t)sr::kVoxelGrid * sr::kVoxelGrid * sr::kVoxelGrid;
+    const double lo[3] = {-1, -1, -1}, hi[3] = {1, 1, 1};
+    s->vox_box = sr::make_root_box(lo, hi);
+    if (s->device < 0) {
+        s->vox_colors_host.assign(cells, 0u);
+        s->vox_normals_host.assign(cells * 3, 0.0);
+        sr::voxelise_host(s->v9.data(), s->tri_recs.data(), s->ntris, s->vox_colors_host.data(), s->vox_normals_host.data());
+        s->vox_valid = true;
+        return SR_OK;
+    }
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still walk the old grid
+    SR_HIP(s->d_vox_colors.reserve(cells * 4));
+    SR_HIP(s->d_vox_normals.reserve(cells * 3 * sizeof(double)));
+    SR_HIP(s->d_vox_mask.reserve(cells / 8));
+    const int n = (int)s->ntris;
+    DBuf counts, offsets, temp, pairs, first_last;
+    struct Free { DBuf* b[5]; ~Free() { for (DBuf* x : b) x->release(); } } free_all{{&counts, &offsets, &temp, &pairs, &first_last}};
+    size_t scan_bytes = 0;
+    SR_HIP(sr::voxel_count_cells(nullptr, n, nullptr, nullptr, nullptr, &scan_bytes, stream));
+    SR_HIP(counts.reserve((size_t)n * 8));
+    SR_HIP(offsets.reserve((size_t)n * 8));
+    SR_HIP(temp.reserve(scan_bytes));
+    SR_HIP(first_last.reserve(cells * 2 * 4));
+    hipEvent_t e0, e1;
+    int rc = next_events(s, sr::K_VOXELISE, e0, e1);
+    if (rc) return rc;
+    if (e0) SR_HIP(hipEventRecord(e0, stream));
+    SR_HIP(sr::voxel_count_cells((const double*)s->d_v9.p, n, (unsigned long long*)counts.p, (unsigned long long*)offsets.p, temp.p, &scan_bytes, stream));
+    unsigned long long tail[2] = {0, 0};
+    SR_HIP(hipMemcpyAsync(&tail[0], (const unsigned long long*)offsets.p + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(&tail[1], (const unsigned long long*)counts.p + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
+    const unsigned long long npairs = tail[0] + tail[1];
+    if (npairs > (unsigned long long)kMaxVoxelPairs)
+        return fail(SR_ERR_UNSUPPORTED, "voxel grid: the triangles' boxes of cells hold more than 2^30 (cell, triangle) pairs");
+    const size_t sort_bytes = npairs ? sr::voxel_sort_temp_bytes((unsigned int)npairs) : 0;
+    if (npairs) {
+        SR_HIP(pairs.reserve((size_t)npairs * 4 * 4));
+        if (sort_bytes > temp.cap) SR_HIP(temp.reserve(sort_bytes));
+    }
+    const sr::VoxelGridDev grid{(uint32_t*)s->d_vox_colors.p, (double*)s->d_vox_normals.p, (uint32_t*)s->d_vox_mask.p};
+    SR_HIP(sr::voxel_fill_grid((const double*)s->d_v9.p, (const sr::Rec128*)s->d_tris.p, n, (const unsigned long long*)offsets.p, (unsigned int)npairs,
+                               (unsigned int*)pairs.p, temp.p, sort_bytes, (unsigned int*)first_last.p, grid, stream));
+    if (e1) SR_HIP(hipEventRecord(e1, stream));
+    SR_HIP(hipStreamSynchronize(stream));                                 // the scratch is freed on return
+    s->vox_valid = true;
+    return SR_OK;
+}
+
 // pt_phase: 0, or the phase (1, 2) of a part of a path-traced frame that multi_render has split (sr_device.h PipelineLaunch::pt_phase)
 int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0) {
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
     if (rc) return rc;
+    const bool voxels = (f->flags & SR_F_VOXELS) != 0;                // (the voxel grid replaces the model's tree AND the extra geometry, Renderer.cs:1568-1588)
     // strips that the caller (or sr_rccl_render) made: this one call on this one scene cannot know how many samples hit in the rows the other
     // ranks render.  The strips of a multi-device scene are the library's own: multi_render exchanges the counts between the two phases
     if ((f->flags & SR_F_PATH_TRACING) && f->strip_count > 1 && !pt_phase)
         return fail(SR_ERR_UNSUPPORTED, "path tracing with row strips: a rank would need the hit counts of rows it does not render");
     if ((rc = prepare_frame(s, f, fc))) return rc;
-    if ((rc = sync_geometry(s, (uint32_t)f->trace_mode))) return rc;
+    if ((rc = sync_geometry(s, voxels ? ~0u : (uint32_t)f->trace_mode))) return rc;
+    if (voxels && (rc = ensure_voxels(s, stream))) return rc;
     if (fc.num_rows == 0) return SR_OK;
     // ---- frames of one scene run in submission order whatever streams they are given: the scene's scratch (hit queues, candidate
     //      lists, counters) and its per-origin / per-light records belong to one frame at a time.  `pre_used` is recorded when everything
@@ -495,6 +579,40 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             if (hipEventRecord(t.used, st) == hipSuccess) t.in_flight = true;
         }
     } mark_used{FT, stream};
+    if (voxels) {
+        // ---- one walk kernel per row band (+ k_resolve with sub-pixel samples); the rows are independent: strips and parts need no exchange ----
+        const long long n2v = (long long)fc.sub_pixel_res * fc.sub_pixel_res;
+        const long long budget = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? s->dbg[SR_DBG_BAND_SAMPLES] : (32ll << 20);
+        long long rows = std::max<long long>(16, (budget / ((long long)fc.width * n2v)) / 16 * 16);
+        rows = std::min<long long>(rows, ((long long)fc.num_rows + 15) / 16 * 16);
+        sr_scene::BandScratch& B = s->scratch[0];
+        if (n2v > 1) SR_HIP(B.samples.reserve((size_t)(rows * fc.width * n2v) * 4));
+        if (!s->num_cus) {
+            hipDeviceProp_t prop;
+            SR_HIP(hipGetDeviceProperties(&prop, s->device));
+            s->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        }
+        sr::VoxelLaunch V{};
+        V.fc = fc;
+        V.box = s->vox_box;
+        V.grid = sr::VoxelGridDev{(uint32_t*)s->d_vox_colors.p, (double*)s->d_vox_normals.p, (uint32_t*)s->d_vox_mask.p};
+        V.row_map = d_rowmap;
+        V.pixels = d_pixels;
+        V.samples = (uint32_t*)B.samples.p;
+        V.band_rows = (int32_t)rows;
+        V.persistent_blocks = s->num_cus * 3;                         // 3 workgroups x 32 KB of occupancy bits per CU (137 VGPRs: 3 waves per SIMD)
+        V.global_table = s->dbg[SR_DBG_KERNEL_SWITCH] == 41;          // (hook: no LDS mask, a step reads the colour table)
+        V.stats = d_stats;
+        V.stream = stream;
+        V.user = s;
+        V.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
+            hipEvent_t x = nullptr, y = nullptr;
+            if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
+            *a = x; *b = y;
+        };
+        SR_HIP(sr::launch_voxel_frame(V));
+        return SR_OK;
+    }
     const bool static_shadows = (f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS);
     if (static_shadows) {
         if ((f->flags & SR_F_SINGLE_KERNEL) || f->max_bounces > 0 || f->strip_count > 1)
@@ -971,6 +1089,7 @@ void share_host_model(sr_scene* d, const sr_scene* src) {
     d->have_model = src->have_model;
     d->root = src->root;
     d->shadow_cache_empty = true;
+    d->vox_valid = false;
     d->ref = sr::RefTree(); d->bvh = sr::Bvh(); d->bvh_on_device = false;
     d->tris_dirty = d->ref_dirty = d->bvh_dirty = true;
     d->cam_valid = false; d->interior_valid = false;
@@ -1067,7 +1186,8 @@ void sr_destroy(sr_scene* s) {
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
-                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats};
+                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
+                        &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
         for (auto& t : s->tables) { t.dev.release(); if (t.host) (void)hipHostFree(t.host); if (t.used) (void)hipEventDestroy(t.used); if (t.ready) (void)hipEventDestroy(t.ready); }
@@ -1099,6 +1219,7 @@ int sr_set_triangles(sr_scene* s, const double* v9, const uint32_t* argb, int64_
     if (!s || n < 0 || (n > 0 && (!v9 || !argb)) || !box_min || !box_max) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_triangles");
     if (n > 0x7fffff00) return fail(SR_ERR_INVALID_ARG, "too many triangles");
     s->shadow_cache_empty = true;                         // new model: what a new ShadowMethod starts with
+    s->vox_valid = false;                                 // ... and a new VoxelGrid
     s->v9.assign(v9, v9 + 9 * n);
     s->argb.assign(argb, argb + n);
     for (int a = 0; a < 3; ++a) { s->bmin[a] = box_min[a]; s->bmax[a] = box_max[a]; }
@@ -1253,6 +1374,38 @@ int sr_build(sr_scene* s, uint32_t modes, int32_t max_depth, int32_t max_per_lea
     return SR_OK;
 }
 
+int sr_build_voxels(sr_scene* s) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_build_voxels");
+    if (!s->parts.empty()) {
+        for (sr_scene* q : s->parts) { int rc = sr_build_voxels(q); if (rc) return rc; }
+        return SR_OK;
+    }
+    if (!s->have_model || s->ntris == 0) return fail(SR_ERR_NO_MODEL, "no model");
+    if (s->vox_valid) return SR_OK;
+    if (s->device < 0) return ensure_voxels(s, nullptr);
+    int rc = use_device(s);
+    if (rc) return rc;
+    if ((rc = sync_geometry(s, ~0u))) return rc;
+    return ensure_voxels(s, nullptr);
+}
+
+int sr_get_voxels(sr_scene* s, uint32_t* colors, double* normals) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_get_voxels");
+    if (!s->vox_valid) return fail(SR_ERR_NOT_BUILT, "no voxel grid: call sr_build_voxels (or render a SR_F_VOXELS frame) after setting the triangles");
+    const size_t cells = (size_t)sr::kVoxelGrid * sr::kVoxelGrid * sr::kVoxelGrid;
+    if (s->device < 0) {
+        if (colors) std::memcpy(colors, s->vox_colors_host.data(), cells * 4);
+        if (normals) std::memcpy(normals, s->vox_normals_host.data(), cells * 3 * sizeof(double));
+        return SR_OK;
+    }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (colors) SR_HIP(hipMemcpy(colors, s->d_vox_colors.p, cells * 4, hipMemcpyDeviceToHost));
+    if (normals) SR_HIP(hipMemcpy(normals, s->d_vox_normals.p, cells * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
 int sr_tree_stats(const sr_scene* s, int32_t out[4]) {
     if (s && !s->parts.empty()) s = s->parts[0];
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "bad argument");
@@ -1331,7 +1484,7 @@ static int multi_render(sr_scene* m, const sr_frame* f, int32_t* host_pixels, vo
         std::memcpy(m->last_stats, m->parts[0]->last_stats, sizeof(m->last_stats));     // sr_last_ray_stats(multi scene) reports this frame
         return rc;
     }
-    if ((rc = check_mode(m->parts[0], f->trace_mode))) return rc;
+    if ((rc = check_frame_mode(m->parts[0], f))) return rc;
     int a, b;
     clamp_rows(f, a, b);
     if (b < a) { m->last_parts = 0; if (stats4) std::memset(stats4, 0, 4 * sizeof(uint64_t)); return SR_OK; }
@@ -1360,7 +1513,7 @@ static int multi_render(sr_scene* m, const sr_frame* f, int32_t* host_pixels, vo
     for (int g = 0; g < n; ++g) {
         sr_scene* q = m->parts[g];
         if (counts[g] == 0) continue;
-        if ((rc = check_mode(q, f->trace_mode))) return rc;
+        if ((rc = check_frame_mode(q, f))) return rc;
         if ((rc = use_device(q))) return rc;
         if ((rc = ensure_io_streams(q))) return rc;
         // the previous frame's gather may still be reading this part's strips (sr_render_device returns before the copies have run)
@@ -1508,7 +1661,7 @@ int sr_render_device(sr_scene* s, const sr_frame* f, void* d_pixels, void* hip_s
     if (!s || !d_pixels) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_render_device");
     int rc = validate_frame(f);
     if (rc) return rc;
-    if ((rc = check_mode(s, f->trace_mode))) return rc;
+    if ((rc = check_frame_mode(s, f))) return rc;
     if ((rc = use_device(s))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
@@ -1523,7 +1676,7 @@ int sr_render(sr_scene* s, const sr_frame* f, int32_t* pixels, uint64_t stats[4]
     if (!s || !pixels) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_render");
     int rc = validate_frame(f);
     if (rc) return rc;
-    if ((rc = check_mode(s, f->trace_mode))) return rc;
+    if ((rc = check_frame_mode(s, f))) return rc;
     if ((rc = use_device(s))) return rc;
     int64_t count = sr_frame_pixel_count(f);
     {
@@ -1588,6 +1741,13 @@ static int trace_prepare(sr_scene*& s, int32_t target, int64_t n, bool have_rays
     mode = target & 0xff;
     if (!s->have_model) return fail(SR_ERR_NO_MODEL, "no model");
     int rc;
+    if (target == SR_TARGET_VOXELS) {                               // VoxelGrid.IntersectRay: needs triangles only
+        mode = -1; with_extra = false;
+        if (s->ntris == 0) return fail(SR_ERR_NO_MODEL, "no model");
+        if ((rc = use_device(s))) return rc;
+        if ((rc = sync_geometry(s, ~0u))) return rc;
+        return ensure_voxels(s, nullptr);
+    }
     if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* empty model is fine for brute force */ }
     else if ((rc = check_mode(s, mode))) return rc;
     if ((rc = use_device(s))) return rc;
@@ -1610,6 +1770,11 @@ int sr_trace_rays_device(sr_scene* s, int32_t target, int64_t n, const double* d
     hipEvent_t e0, e1;
     if ((rc = next_events(s, sr::K_TRACE, e0, e1))) return rc;
     if (e0) SR_HIP(hipEventRecord(e0, L.stream));
+    if (mode < 0) {
+        if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(L.stream, s->pre_used, 0));
+        const sr::VoxelGridDev grid{(uint32_t*)s->d_vox_colors.p, (double*)s->d_vox_normals.p, (uint32_t*)s->d_vox_mask.p};
+        SR_HIP(sr::launch_voxel_trace(L, s->vox_box, grid, 256 * 4));
+    } else
     SR_HIP(sr::launch_trace(L));
     if (e1) SR_HIP(hipEventRecord(e1, L.stream));
     return SR_OK;

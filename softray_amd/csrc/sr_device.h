@@ -41,7 +41,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_COUNT = 15 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_COUNT = 17 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -194,6 +194,42 @@ struct TraceLaunch {
     hipStream_t stream;
 };
 hipError_t launch_trace(const TraceLaunch& L);
+// k_resolve for the compact rows [row_begin, row_begin + row_count) of a band-local sample buffer (sr_pipeline.hip)
+hipError_t launch_resolve_rows(const FrameConst& fc, const int32_t* row_map, int row_begin, int row_count, const uint32_t* samples, uint32_t* pixels, hipStream_t stream);
+
+// ---- rayTraceVoxels (SR_F_VOXELS; sr_voxels.hip): the model as a 64^3 grid of coloured cells, [x][y][z] order ----
+constexpr int kVoxelGrid = 64;                    // Renderer.cs:1570
+struct VoxelGridDev {
+    uint32_t* colors;       // device [64^3]: 0 = empty cell
+    double*   normals;      // device [64^3][3]
+    uint32_t* mask;         // device [64^3 / 32]: bit (cell & 31) of word (cell >> 5) = the cell's colour is not 0
+};
+// The voxeliser in three steps, because the number of (cell, triangle) pairs decides what the second one needs:
+// (1) cells per triangle and their exclusive scan (d_temp == nullptr: only the scan's scratch size -> *temp_bytes);
+// (2) the caller reads offsets[n - 1] + counts[n - 1] back and provides d_pairs (4 x npairs words) and the sort's scratch;
+// (3) pairs -> stable sort by cell -> per-cell sums in ascending triangle order -> colours, normals, occupancy bits.
+// d_first_last: 2 x 64^3 words of scratch.
+hipError_t voxel_count_cells(const double* d_v9, int ntris, unsigned long long* d_counts, unsigned long long* d_offsets, void* d_temp, size_t* temp_bytes, hipStream_t stream);
+size_t voxel_sort_temp_bytes(unsigned int npairs);
+hipError_t voxel_fill_grid(const double* d_v9, const Rec128* d_tris, int ntris, const unsigned long long* d_offsets, unsigned int npairs, unsigned int* d_pairs,
+                           void* d_temp, size_t temp_bytes, unsigned int* d_first_last, const VoxelGridDev& grid, hipStream_t stream);
+struct VoxelLaunch {
+    FrameConst  fc;
+    RootBox     box;            // AxisAlignedBox((-1,-1,-1), (1,1,1)), VoxelGrid.cs:38
+    VoxelGridDev grid;
+    const int32_t* row_map;     // device [fc.num_rows]
+    uint32_t*   pixels;         // device output frame (full surface or compact strips)
+    uint32_t*   samples;        // device [band_rows * width * n^2] (sub_pixel_res > 1 only)
+    int32_t     band_rows;
+    int32_t     persistent_blocks;
+    bool        global_table;   // a step reads the colour table instead of the occupancy bits in LDS (A/B measurement, same pixels)
+    unsigned long long* stats;  // device [4..] or nullptr
+    hipStream_t stream;
+    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
+    void*       user;
+};
+hipError_t launch_voxel_frame(const VoxelLaunch& L);
+hipError_t launch_voxel_trace(const TraceLaunch& L, const RootBox& box, const VoxelGridDev& grid, int max_blocks);
 hipError_t launch_shade_points(const FrameConst& fc, long long n, const double* pos, const double* nrm, const uint32_t* color, uint32_t* out, hipStream_t stream);
 
 // --------------------------------------------------------------------------------------------------

@@ -835,4 +835,48 @@ std::string load_3ds(const uint8_t* data, size_t len, LoadedModel& out) {
     return std::string();
 }
 
+// ------------------------------------------------------------------------------------------------
+// TriMeshToVoxelGrid.Convert (TriMeshToVoxelGrid.cs:14-114), grid 64: the plain loop
+// ------------------------------------------------------------------------------------------------
+// Triangles in index order; every triangle tests all 64 cells of every axis with the reference's two plane comparisons
+// (FindTrianglesInsidePlanes: v.n >= d for axis normals, i.e. max >= k/64 - 0.5 and min <= (k+1)/64 - 0.5) and adds its colour to the
+// cells of the resulting box, so every cell sums in ascending triangle index like the reference's list walk.
+void voxelise_host(const double* v9, const Rec128* recs, size_t ntris, uint32_t* colors, double* normals) {
+    const int G = 64;
+    const size_t cells = (size_t)G * G * G;
+    std::vector<double> sum(cells * 3, 0.0);
+    std::vector<int32_t> count(cells, 0);
+    std::memset(normals, 0, cells * 3 * sizeof(double));
+    for (size_t t = 0; t < ntris; ++t) {
+        const double* v = v9 + 9 * t;
+        int lo[3], hi[3];
+        bool any = true;
+        for (int a = 0; a < 3; ++a) {
+            const double mn = std::min(v[a], std::min(v[3 + a], v[6 + a])), mx = std::max(v[a], std::max(v[3 + a], v[6 + a]));
+            lo[a] = G; hi[a] = -1;
+            for (int k = 0; k < G; ++k) {
+                const double p0 = (double)k / G - 0.5, p1 = (double)(k + 1) / G - 0.5;
+                if (mx >= p0 && mn <= p1) { lo[a] = std::min(lo[a], k); hi[a] = std::max(hi[a], k); }
+            }
+            any = any && hi[a] >= lo[a];
+        }
+        if (!any) continue;
+        const uint32_t c = recs[t].color;
+        const double r = (double)((c >> 16) & 0xffu) / 255.0, g = (double)((c >> 8) & 0xffu) / 255.0, b = (double)(c & 0xffu) / 255.0;   // Color.cs:31-36
+        for (int x = lo[0]; x <= hi[0]; ++x)
+            for (int y = lo[1]; y <= hi[1]; ++y)
+                for (int z = lo[2]; z <= hi[2]; ++z) {
+                    const size_t cell = ((size_t)x * G + y) * G + z;
+                    if (count[cell]++ == 0) { normals[3 * cell] = recs[t].p[0]; normals[3 * cell + 1] = recs[t].p[1]; normals[3 * cell + 2] = recs[t].p[2]; }
+                    sum[3 * cell] = sum[3 * cell] + r; sum[3 * cell + 1] = sum[3 * cell + 1] + g; sum[3 * cell + 2] = sum[3 * cell + 2] + b;
+                }
+    }
+    for (size_t cell = 0; cell < cells; ++cell) {
+        if (!count[cell]) { colors[cell] = 0u; continue; }
+        const double n = (double)count[cell];
+        const double r = sum[3 * cell] / n, g = sum[3 * cell + 1] / n, b = sum[3 * cell + 2] / n;
+        colors[cell] = (255u << 24) + (((uint32_t)(int)(r * 255.0) & 0xffu) << 16) + (((uint32_t)(int)(g * 255.0) & 0xffu) << 8) + ((uint32_t)(int)(b * 255.0) & 0xffu);   // Color.ToARGB
+    }
+}
+
 }  // namespace sr

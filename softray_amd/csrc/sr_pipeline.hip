@@ -4133,6 +4133,12 @@ static hipError_t launch_resolve(const PipelineLaunch& L, int row_begin, int row
     return hipSuccess;
 }
 
+hipError_t launch_resolve_rows(const FrameConst& fc, const int32_t* row_map, int row_begin, int row_count, const uint32_t* samples, uint32_t* pixels, hipStream_t stream) {
+    const long long npx = (long long)row_count * fc.width;
+    hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, fc, row_map, row_begin, row_count, samples, pixels);
+    return hipGetLastError();
+}
+
 template <int MODE, bool EXTRA>
 static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;

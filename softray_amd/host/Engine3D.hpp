@@ -270,6 +270,7 @@ public:
         }
         int mode = Mode();
         uint32_t want = mode == SR_MODE_BRUTE ? 0u : (1u << mode);
+        if (rayTraceVoxels) want = 0u;                     // a voxel frame walks the grid the library makes from the triangles (SR_F_VOXELS)
         if (mode == SR_MODE_REF_TREE && rayTraceShadows && !rayTraceShadowsStatic && !model_->argb.empty())
             want |= 1u << SR_MODE_BVH;                     // a tree frame's shadow rays take the BVH's shaft path
         if (want & ~built_) {
@@ -280,8 +281,10 @@ public:
     void Render() {                                        // Renderer.cs:701-778
         if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
         if (!PinModel()) return;                           // silently, :736-739
-        if (rayTraceAmbientOcclusion || rayTraceLightField || rayTraceVoxels)
-            throw std::logic_error("AO / light field / voxels are out of scope (racy or RNG-order dependent in the reference)");
+        if (rayTraceAmbientOcclusion || rayTraceLightField)
+            throw std::logic_error("AO / light field are out of scope (racy or RNG-order dependent in the reference)");
+        if (rayTraceVoxels && (rayTraceShadows || rayTracePathTracing || gpuMaxBounces > 0))   // SR_F_VOXELS: the reference's result there is a rayFrac = 0 artefact
+            throw std::logic_error("rayTraceVoxels together with rayTraceShadows, rayTracePathTracing or mirror bounces is out of scope (SR_F_VOXELS)");
         if (rayTracePathTracing && rayTraceShadows)
             throw std::logic_error("rayTracePathTracing together with rayTraceShadows is out of scope (SR_F_PATH_TRACING)");
         for (auto& inst : Instances) {
@@ -308,6 +311,7 @@ public:
                   (rayTraceShadows && rayTraceShadowsStatic ? SR_F_STATIC_SHADOWS : 0u) |      // Renderer.cs:1625; the cache lives in the scene
                   (rayTraceFocalBlur ? SR_F_FOCAL_BLUR : 0u) |
                   (rayTracePathTracing ? SR_F_PATH_TRACING : 0u) |                                 // Renderer.cs:1613-1618; reads random_seed, concurrency
+                  (rayTraceVoxels ? SR_F_VOXELS : 0u) |                                            // Renderer.cs:1568-1588: the grid replaces tree and extra geometry
                   (pointLighting ? SR_F_POINT_LIGHT : 0u) | (specularLighting ? SR_F_SPECULAR : 0u) |
                   SR_F_PRIMARY_STATS_ONLY;                 // Num* count primary rays (Renderer.cs:1916-1923)
         f.random_seed = rayTraceRandomSeed;
@@ -374,7 +378,7 @@ private:
         rayTraceEndRow = std::min(std::max(0, rayTraceEndRow), height_ - 1);
         sr_frame f = BuildFrame(instance);
         if (!pixels_) throw InvalidOperationException("SetRenderingSurface must be called before Render");
-        if (f.trace_mode != SR_MODE_BVH) {                 // the literal tree (or brute force): the reference's counters
+        if (f.trace_mode != SR_MODE_BVH || rayTraceVoxels) {   // the literal tree, brute force or the voxel grid: the reference's counters
             sr_check(sr_render(scene_, &f, pixels_, stats_));
             haveCounters_ = true;
         } else {                                           // the own BVH does not produce them: reading one throws

@@ -115,6 +115,18 @@ class GpuScene:
         _check(_lib.lib().sr_bvh_digest(self._h, _p(out)))
         return tuple(int(x) for x in out)
 
+    # ---- rayTraceVoxels (SR_F_VOXELS frames, TARGET_VOXELS rays) ----
+    def build_voxels(self):
+        """TriMeshToVoxelGrid.Convert for the current triangles (idempotent; the first voxel frame calls it itself)."""
+        _check(_lib.lib().sr_build_voxels(self._h))
+
+    def get_voxels(self):
+        """(colors uint32 [64, 64, 64], normals float64 [64, 64, 64, 3]) of the grid, [x][y][z]; also for a host-only scene."""
+        colors = np.zeros((64, 64, 64), dtype=np.uint32)
+        normals = np.zeros((64, 64, 64, 3))
+        _check(_lib.lib().sr_get_voxels(self._h, _p(colors), _p(normals)))
+        return colors, normals
+
     # ---- Render() ----
     @staticmethod
     def pixel_count(frame):
@@ -181,8 +193,8 @@ class GpuScene:
 
     def kernel_times(self):
         """{kernel: (total ms, launches)} since reset_kernel_times() -- HIP events on the launch stream."""
-        arr = (KernelTime * 16)()
-        n = _lib.lib().sr_kernel_times(self._h, arr, 16)
+        arr = (KernelTime * 32)()
+        n = _lib.lib().sr_kernel_times(self._h, arr, 32)
         return {arr[i].name.decode(): (float(arr[i].ms), int(arr[i].launches)) for i in range(n)}
 
     def shade_points(self, frame, pos, normal, color):

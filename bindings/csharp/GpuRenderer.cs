@@ -80,6 +80,9 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_tree_stats(IntPtr scene, [Out] int[] out4);
         [DllImport(Lib)] public static extern int sr_render(IntPtr scene, ref SrFrame frame, [In, Out] int[] pixels, [Out] ulong[] stats4);
         [DllImport(Lib)] public static extern int sr_reset_shadow_cache(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_reset_ao_cache(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_get_ao_cache(IntPtr scene, [Out] byte[] out128Cubed);
+        [DllImport(Lib)] public static extern int sr_set_ao_cache(IntPtr scene, [In] byte[] in128Cubed);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -117,6 +120,13 @@ namespace Engine3D.Hip
         /// model's tree and the extra geometry; trace_mode is ignored and nothing needs building.  Not together with F_SHADOWS,
         /// F_PATH_TRACING or mirror bounces (SR_ERR_UNSUPPORTED -> InvalidOperationException): keep the CPU chain for those.
         public const uint F_VOXELS = 1u << 7;
+        /// rayTraceAmbientOcclusion (Renderer.cs:1631-1638) = SR_F_AMBIENT_OCCLUSION: pass it in `flags` together with rayTraceRandomSeed and
+        /// rayTraceConcurrency; F_AO_UNCACHED (with it) = AmbientOcclusionMethod.EnableCache = false.  Not together with F_PATH_TRACING,
+        /// F_VOXELS, F_STATIC_SHADOWS or mirror bounces (SR_ERR_UNSUPPORTED -> InvalidOperationException).  The cache lives in the
+        /// scene: ResetAmbientOcclusionCache() is what a new Renderer starts with, Get / SetAmbientOcclusionCache move the bytes of
+        /// the reference's .ao file (AmbientOcclusion.cs:232-309; the file itself stays the host's business).
+        public const uint F_AMBIENT_OCCLUSION = 1u << 13, F_AO_UNCACHED = 1u << 14;
+        public const int AoCacheBytes = 128 * 128 * 128;
         const uint F_PRIMARY_STATS_ONLY = 1u << 12;     // Num* count primary rays (Renderer.cs:1916-1923): no counting in the shadow stage
         public const int MODE_REF_TREE = 0, MODE_BRUTE = 1, MODE_BVH = 2;
         /// How NumGeometryTests / NumNodeVisits / NumLeafNodeVisits (Renderer.cs:476-504) are answered -- an explicit choice of the
@@ -308,6 +318,21 @@ namespace Engine3D.Hip
 
         /// A new Renderer starts with an empty static shadow cache (ShadowMethod.cs:75-83)
         public void ResetShadowCache() { Native.Check(Native.sr_reset_shadow_cache(scene)); }
+
+        /// A new Renderer starts with an empty ambient-occlusion cache (AmbientOcclusion.cs:60-75)
+        public void ResetAmbientOcclusionCache() { Native.Check(Native.sr_reset_ao_cache(scene)); }
+        /// The cache as the reference's .ao file holds it: 128^3 bytes, [x][y][z], 0 = empty cell
+        public byte[] GetAmbientOcclusionCache()
+        {
+            var data = new byte[AoCacheBytes];
+            Native.Check(Native.sr_get_ao_cache(scene, data));
+            return data;
+        }
+        public void SetAmbientOcclusionCache(byte[] data)
+        {
+            if (data == null || data.Length != AoCacheBytes) throw new ArgumentException("the ambient-occlusion cache is 128^3 bytes");
+            Native.Check(Native.sr_set_ao_cache(scene, data));
+        }
 
         /// PostProcessImage's colour functions (Renderer.cs:819-865): style = (int)Renderer.Style for Standard..DepthBanded.
         public void PostProcess(int[] pixels, int style, uint backgroundColor)

@@ -106,6 +106,32 @@ enum {
                                      library's BVH (shaft path): "is there a hit with rayFrac <= 1.0" has the same answer, and the
                                      four statistics of sr_render count the primary rays, which keep the literal traversal either
                                      way.  With the flag the secondary counters of sr_last_ray_stats are the reference tree's  */
+    SR_F_AMBIENT_OCCLUSION = 1u << 13, /* rayTraceAmbientOcclusion -> AmbientOcclusionMethod.Enabled (Renderer.cs:1631-1638, AmbientOcclusionMethod.cs:65-99,
+                                     AmbientOcclusion.cs:101-230): after shading and (dynamic) shadows, the colour of every camera sample that hits the root
+                                     geometry is modulated with a byte 1..255 = (byte)(escapes / 100.0 * 254 + 1), where `escapes` counts the probes, out of
+                                     100 fired from pos + n * 0.001 into the hemisphere about the normal, that hit nothing or hit beyond rayFrac 2.0.  pos is
+                                     the surface point CLAMPED to the cube [-0.5, 0.5]^3 (extra geometry outside it probes from the cube's surface: literal
+                                     reference behaviour).  A probe direction is (2u0 - 1, 2u1 - 1, 2u2 - 1), not normalised, negated when it points below the
+                                     surface; the u are NextDouble() of Random(random_seed), which the reference restarts for every one of its `concurrency`
+                                     row blocks and draws in scan order (row, column, subX, subY): generator number k of a block uses draws 300 k .. 300 k + 299,
+                                     looked up in the table path tracing uses (kept per (seed, length): 1200 bytes per generator of the row block that has the
+                                     most, SR_ERR_UNSUPPORTED above 256 MiB).  The byte lives in a 128^3 texture over the unit cube that the scene keeps for
+                                     later frames (sr_reset_ao_cache = a new Renderer; sr_get_ao_cache / sr_set_ao_cache = the reference's .ao file): an empty
+                                     cell is generated by whoever asks first.  The reference's worker tasks race for the cells; the library takes the
+                                     deterministic order of SR_F_STATIC_SHADOWS -- row r of every block, blocks ascending, before row r + 1; columns ascending;
+                                     sub-samples in loop order -- and a generator's k is the number of generators before it in scan order inside its own block.
+                                     With concurrency = 1 that IS the reference's frame; with more blocks the order is the library's and no golden pins it
+                                     (the reference's own tests switch AO off for that reason, RendererTests.cs:402-405), as with the mirror-bounce extension.
+                                     Reads random_seed and concurrency.  Works with SR_F_SHADING, SR_F_SHADOWS (dynamic), sub_pixel_res, SR_F_FOCAL_BLUR, row
+                                     ranges, extra geometry and all three trace modes.  The frame runs as one pipeline (as with SR_F_NO_SPLIT) and the call
+                                     waits for the device once, also sr_render_device: the host sizes the table by the generators found.  A multi-device
+                                     scene renders it on devices[0] alone.  SR_ERR_UNSUPPORTED together with SR_F_PATH_TRACING (same Random), SR_F_VOXELS (a
+                                     voxel hit has no position), SR_F_STATIC_SHADOWS with SR_F_SHADOWS (the probes would fill that cache), max_bounces > 0,
+                                     SR_F_SINGLE_KERNEL, caller-made strips (strip_count > 0), sr_rccl_render, and a row range that does not fit one row band.
+                                     Statistics: the probes are secondary rays -- sr_last_ray_stats [4] grows by 100 per generator, [5..7] by what their walks
+                                     count (not with SR_F_PRIMARY_STATS_ONLY); [0..3] are unchanged                                     */
+    SR_F_AO_UNCACHED = 1u << 14,  /* with SR_F_AMBIENT_OCCLUSION only: AmbientOcclusionMethod.EnableCache = false (Renderer.cs:74) -- every hit sample
+                                     generates its own byte, nothing is read from or stored in the cache                                */
     SR_F_PRIMARY_STATS_ONLY = 1u << 12 /* library option: with `stats`, count the primary rays only -- the four statistics of sr_render
                                      (NumRaysFired, NumGeometryTests, NumNodeVisits, NumLeafNodeVisits).  The shadow stage then runs
                                      its uncounted kernels (counting costs atomics per hit point: obj.3DS 1024^2 + shadows 2.3 -> 1.1 ms)
@@ -166,8 +192,9 @@ typedef struct {
                                         each level coloured by the same shading/shadow chain, colours blended per
                                         channel ((s*(255-k))>>8) + ((r*k)>>8), k = (byte)(reflectivity*255)       */
     int32_t  concurrency;            /* rayTraceConcurrency (:92), <= 0 => 4.  Only read with SR_F_STATIC_SHADOWS (it fixes
-                                        the order in which the shadow cache is filled, see that flag) and with
-                                        SR_F_PATH_TRACING (the row blocks that each restart the random sequence)     */
+                                        the order in which the shadow cache is filled, see that flag), with
+                                        SR_F_PATH_TRACING (the row blocks that each restart the random sequence) and with
+                                        SR_F_AMBIENT_OCCLUSION (both)                                                */
     int32_t  reserved0;              /* 0 */
     double   transform[12];          /* rows 0..2 of Instance._transform        (Instance.cs:134)        */
     double   inv_transform[12];      /* rows 0..2 of Instance._inverseTransform (Instance.cs:135)        */
@@ -216,7 +243,7 @@ int  sr_create(int32_t device, sr_scene** out);
 int  sr_create_multi(const int32_t* devices, int32_t n, sr_scene** out);
 int32_t sr_device_count(const sr_scene*);
 /* How many parts (devices) rendered rows of the scene's last frame: 1 for a single-device scene and for a frame that devices[0]
- * rendered whole (static shadows, caller-made strips), otherwise the number of parts that owned at least one row of the range. */
+ * rendered whole (static shadows, ambient occlusion, caller-made strips), otherwise the number of parts that owned at least one row of the range. */
 int32_t sr_last_frame_parts(const sr_scene*);
 void sr_destroy(sr_scene*);
 
@@ -273,6 +300,13 @@ int  sr_wide_tree_stats(const sr_scene*, int64_t out[5]);
 int  sr_render(sr_scene*, const sr_frame*, int32_t* pixels, uint64_t stats[4]);
 /* forget the static shadow cache (what a new Renderer / ShadowMethod starts with); sr_set_triangles does it too */
 int  sr_reset_shadow_cache(sr_scene*);
+/* rayTraceAmbientOcclusion's cache (SR_F_AMBIENT_OCCLUSION): 128^3 bytes in [x][y][z] order, 0 = empty cell -- exactly the array the
+ * reference persists to its .ao file (AmbientOcclusion.cs:232-309), so a host can save and load that file itself (the library does no file
+ * I/O).  sr_reset_ao_cache: what a new Renderer starts with; sr_set_triangles / sr_load_3ds drop the cache too.  All three work on a
+ * host-only scene; a scene that never rendered an AO frame reads back zeros. */
+int  sr_reset_ao_cache(sr_scene*);
+int  sr_get_ao_cache(sr_scene*, uint8_t out[128 * 128 * 128]);
+int  sr_set_ao_cache(sr_scene*, const uint8_t in[128 * 128 * 128]);
 /* Same, but `d_pixels` is DEVICE memory on the scene's device (e.g. a torch tensor's data_ptr) and the
  * work is enqueued on `hip_stream` (a hipStream_t; NULL = the null stream) without host sync. */
 /* Ordering: the work is enqueued behind everything already on `hip_stream` and `hip_stream` continues only after it; a
@@ -419,7 +453,8 @@ enum {
                                     queue order (no per-level ray sort); 61 the camera-ordered node copy keeps (lo, hi) planes; 71 no facing
                                     partition (the packet walks see every record of a leaf); 7 counts umbra decisions of the private shaft walk;
                                     32 a mirror-bounce level as ONE kernel (k_bounce) instead of prepare / walk / finish; 33 the second rays of a path-traced SR_MODE_BVH frame with
-                                    private per-lane walks (k_pt_finish) instead of the mirror extension's prepare / walk route; 100 + T: the walk kernel
+                                    private per-lane walks (k_pt_finish) instead of the mirror extension's prepare / walk route; 34 the ambient-occlusion probes of a
+                                    SR_MODE_BVH frame as nearest-hit walks instead of any-hit walks with the limit 2.0; 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid
                                     too (its loop form spills registers: opt-in); 84 the persistent shaft walk hands its tiles out in natural order
@@ -446,7 +481,9 @@ enum {
     SR_DBG_LITERAL_SHADOWS = 15, /* > 0: no shortcut for ShadowMethod -- a directional light's samples are traced one by one although all of
                                     them provably escape, and a SR_MODE_REF_TREE frame traces its shadow rays through the reference tree
                                     (as with SR_F_LITERAL_SECONDARY); cross-checks of both shortcuts                                  */
-    SR_DBG_COUNT          = 16
+    SR_DBG_AO_TABLE_BYTES = 16,  /* > 0: the limit of an ambient-occlusion frame's draw table in bytes (default 256 MiB): small values let a small frame
+                                    reach the refusal                                                                                  */
+    SR_DBG_COUNT          = 17
 };
 int  sr_debug_set(sr_scene*, int32_t key, int64_t value);
 

@@ -22,6 +22,9 @@ F_PER_LANE_SHADOWS = 1 << 9
 F_NO_SPLIT = 1 << 10
 F_LITERAL_SECONDARY = 1 << 11
 F_PRIMARY_STATS_ONLY = 1 << 12
+F_AMBIENT_OCCLUSION = 1 << 13
+F_AO_UNCACHED = 1 << 14
+AO_RES = 128
 MODE_REF_TREE, MODE_BRUTE, MODE_BVH = 0, 1, 2
 TARGET_ROOT = 0x100
 TARGET_VOXELS = 0x200
@@ -38,14 +41,14 @@ SYMBOLS = [
     "sr_post_process", "sr_post_process_device", "sr_anti_alias", "sr_anti_alias_device", "sr_reset_shadow_cache",
     "sr_debug_set", "sr_bvh_stats", "sr_bvh_digest", "sr_wide_tree_stats", "sr_create_multi", "sr_device_count", "sr_last_frame_parts", "sr_shade_points",
     "sr_trace_rays_device", "sr_rccl_unique_id", "sr_rccl_init", "sr_rccl_render", "sr_rccl_gather", "sr_set_gather",
-    "sr_net_random_doubles", "sr_build_voxels", "sr_get_voxels",
+    "sr_net_random_doubles", "sr_build_voxels", "sr_get_voxels", "sr_reset_ao_cache", "sr_get_ao_cache", "sr_set_ao_cache",
 ]
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
 # sr_debug_set keys (include/softray.h)
 (DBG_BAND_SAMPLES, DBG_ROUND_CAP0, DBG_ROUND_CAP1, DBG_SPLIT, DBG_FB_RAY_CAP, DBG_BVH_LEAF, DBG_KERNEL_SWITCH,
  DBG_KERNEL_TIMING, DBG_EXACT_SHADOW_TESTS, DBG_PER_LANE_SHAFT, DBG_PER_LANE_PRIMARY, DBG_ROUND2_NODES, DBG_BUILD_THREADS,
- DBG_BVH2_PACKETS, DBG_NO_PEER, DBG_LITERAL_SHADOWS) = range(16)
+ DBG_BVH2_PACKETS, DBG_NO_PEER, DBG_LITERAL_SHADOWS, DBG_AO_TABLE_BYTES) = range(17)
 
 
 class Prim(C.Structure):
@@ -153,6 +156,9 @@ def lib():
     L.sr_set_gather.restype = i32; L.sr_set_gather.argtypes = [vp, i32]
     L.sr_build_voxels.restype = i32; L.sr_build_voxels.argtypes = [vp]
     L.sr_get_voxels.restype = i32; L.sr_get_voxels.argtypes = [vp, vp, vp]
+    L.sr_reset_ao_cache.restype = i32; L.sr_reset_ao_cache.argtypes = [vp]
+    L.sr_get_ao_cache.restype = i32; L.sr_get_ao_cache.argtypes = [vp, vp]
+    L.sr_set_ao_cache.restype = i32; L.sr_set_ao_cache.argtypes = [vp, vp]
     L.sr_net_random_doubles.restype = None; L.sr_net_random_doubles.argtypes = [i32, i64, i64, vp]
     L.sr_last_error.restype = C.c_char_p; L.sr_last_error.argtypes = []
     L.sr_abi_version.restype = i32; L.sr_abi_version.argtypes = []

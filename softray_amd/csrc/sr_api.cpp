@@ -118,8 +118,15 @@ struct sr_scene {
     hipEvent_t pre_ready = nullptr, pre_used = nullptr;
     bool pre_ready_set = false, pre_used_set = false;
     DBuf d_shadow_cache, d_static_claim, d_static_hits;
-    // path tracing (SR_F_PATH_TRACING): the InternalSample() ints of Random(pt_table_seed), 3 per sample of the largest row block a frame
-    // has asked for so far; made once per (seed, length) and kept for later frames
+    // rayTraceAmbientOcclusion (SR_F_AMBIENT_OCCLUSION): the 128^3 cache a Renderer keeps for its life and the claim words of one frame.  A host-only
+    // scene keeps the bytes sr_set_ao_cache gave it on the host (empty vector: all zeros)
+    DBuf d_ao_cache, d_ao_claim;
+    bool ao_cache_empty = true;          // the device cache must be zeroed before its next use (a new Renderer / a new model)
+    std::vector<uint8_t> ao_cache_host;
+    int32_t ao_table_seed = 0;           // random_seed of the frame being enqueued (read by PipelineLaunch::ao_table)
+    int  ao_table_rc = SR_OK;            // why the frame's draw table was refused (PipelineLaunch::ao_table)
+    // path tracing (SR_F_PATH_TRACING) and ambient occlusion: the InternalSample() ints of Random(pt_table_seed), 3 per sample of the largest row
+    // block (300 per generator of the fullest one) a frame has asked for so far; made once per (seed, length) and kept for later frames
     DBuf d_pt_table;
     int32_t pt_table_seed = 0;
     size_t  pt_table_samples = 0;
@@ -156,6 +163,7 @@ struct sr_scene {
     struct BandScratch {
         DBuf hits, hits2, bounce_levels, bounce_nlev, bounce_prep, bounce_res, bounce_stack, samples, counters, fallback, fallback_state, fallback_rays, fallback_ovf, ray_sort, ray_sort_temp;
         DBuf pt_flags, pt_index, pt_totals, pt_carry;   // path tracing: hit flags, hit-index scan, row-block carries (sr_pipeline.hip k_pt_*)
+        DBuf ao_escapes;                   // ambient occlusion: escaped probes, then the byte, per generator (sr_pipeline.hip k_ao_*)
         DBuf accum;                        // escape counts per sample index of a chunked (> 128 samples) shadow stage; zero between frames
         DBuf tile_cost, tile_order;        // walk length per 8x8 tile of the last shaft launch / the next one's longest-first lists
         unsigned long long tile_order_tag = 0;   // the tile grid tile_order was made for (0: none)
@@ -165,7 +173,7 @@ struct sr_scene {
         bool used_last_frame = false;
         void release() {
             tile_cost.release(); tile_order.release(); tile_order_tag = 0;
-            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &pt_flags, &pt_index, &pt_totals, &pt_carry};
+            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &ao_escapes, &pt_flags, &pt_index, &pt_totals, &pt_carry};
             for (DBuf* x : b) x->release();
             for (int r = 0; r < sr::kShaftRounds; ++r) { rlist[r].release(); rstate[r].release(); rcount[r].release(); rcand[r].release(); }
             if (stream) (void)hipStreamDestroy(stream);
@@ -209,6 +217,8 @@ namespace {
 
 const int kMaxShaftSamples = 1024;       // area-light samples the shaft path takes (in chunks of 128); more: one lane per hit point (k_shadow)
 const long long kMaxPathTable = 256ll << 20;   // bytes of the path tracer's random table (include/softray.h SR_F_PATH_TRACING)
+const int kAoRes = 128;                  // staticShadowRes, the resolution Renderer hands AmbientOcclusionMethod (Renderer.cs:1635)
+const size_t kAoCells = (size_t)kAoRes * kAoRes * kAoRes;
 const int kMaxTreeDepth = 62;            // (depth + 2) stack levels x 256 lanes x 4 B = 64 KB of LDS per workgroup
 
 int use_device(sr_scene* s) {
@@ -331,6 +341,20 @@ int check_path_tracing(const sr_frame* f) {
     return SR_OK;
 }
 
+// SR_F_AMBIENT_OCCLUSION: what draws from the same Random, fills another cache with the probes' hit points, or has no surface point
+// (include/softray.h); the one-band rule is checked where the bands are laid out (render_common)
+int check_ambient_occlusion(const sr_frame* f) {
+    if (!(f->flags & SR_F_AMBIENT_OCCLUSION)) return SR_OK;
+    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "ambient occlusion together with path tracing is not supported (both draw from the row block's Random)");
+    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "ambient occlusion together with voxel rendering is not supported (a voxel hit has no position)");
+    if ((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS))
+        return fail(SR_ERR_UNSUPPORTED, "ambient occlusion together with static shadows is not supported (the probes' hit points would fill the shadow cache)");
+    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "ambient occlusion together with mirror bounces (max_bounces > 0) is not supported");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "ambient occlusion is not built into the one-kernel renderer (SR_F_SINGLE_KERNEL)");
+    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "ambient occlusion with row strips: the cache is filled in one order over the whole frame");
+    return SR_OK;
+}
+
 // SR_F_VOXELS: the decorators whose result on a voxel hit is the reference's rayFrac = 0 artefact (unpinned) and the one-kernel renderer
 int check_voxels(const sr_frame* f) {
     if (!(f->flags & SR_F_VOXELS)) return SR_OK;
@@ -360,7 +384,8 @@ int validate_frame(const sr_frame* f) {
     if ((long long)f->width * f->sub_pixel_res > (1ll << 24) || (long long)f->height > (1ll << 24)) return fail(SR_ERR_INVALID_ARG, "surface too large");
     if (f->max_bounces < 0 || f->max_bounces > 16 || !(f->reflectivity >= 0.0 && f->reflectivity <= 1.0))
         return fail(SR_ERR_INVALID_ARG, "max_bounces must be 0..16 and reflectivity 0..1");
-    int rc = check_voxels(f);
+    int rc = check_ambient_occlusion(f);
+    if (!rc) rc = check_voxels(f);
     return rc ? rc : check_path_tracing(f);
 }
 
@@ -509,6 +534,21 @@ int ensure_voxels(sr_scene* s, hipStream_t stream) {
     if (e1) SR_HIP(hipEventRecord(e1, stream));
     SR_HIP(hipStreamSynchronize(stream));                                 // the scratch is freed on return
     s->vox_valid = true;
+    return SR_OK;
+}
+
+// the table of Random(seed)'s InternalSample() ints, at least 3 * triples of them (path tracing: 3 per sample, ambient occlusion: 300 per
+// generator -- the same sequence); kept per (seed, length)
+int ensure_draw_table(sr_scene* s, int32_t seed, size_t triples) {
+    if (s->d_pt_table.p && s->pt_table_seed == seed && s->pt_table_samples >= triples) return SR_OK;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still read the old table
+    std::vector<int32_t> ints(triples * 3);
+    sr::NetRandom random(seed);
+    for (int32_t& v : ints) v = random.next();
+    s->pt_table_samples = 0;
+    SR_HIP(s->d_pt_table.upload(ints));
+    s->pt_table_seed = seed;
+    s->pt_table_samples = triples;
     return SR_OK;
 }
 
@@ -780,7 +820,8 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     // frame (one global fill order) and shadow-less frames (one kernel) stay whole on the first set.
     int want_split = 2;
     if (s->dbg[SR_DBG_SPLIT] > 0) want_split = (int)std::min<int64_t>(s->dbg[SR_DBG_SPLIT], (int)sr_scene::kMaxSplit);   // experiment hook
-    const bool split = (shadows || bounce_pipe) && !static_shadows && want_split > 1 && fc.num_rows >= 32 * want_split && !(f->flags & SR_F_NO_SPLIT);
+    const bool ao = (f->flags & SR_F_AMBIENT_OCCLUSION) != 0, ao_uncached = ao && (f->flags & SR_F_AO_UNCACHED);
+    const bool split = (shadows || bounce_pipe) && !static_shadows && !ao && want_split > 1 && fc.num_rows >= 32 * want_split && !(f->flags & SR_F_NO_SPLIT);
     const int halves = split ? want_split : 1;
     const int rows_half = split ? (int)((((long long)fc.num_rows + halves - 1) / halves + 15) / 16 * 16) : fc.num_rows;
     const long long budget = kMaxBandSamples / halves;
@@ -828,15 +869,21 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         const long long block_samples = (long long)pt_block_height * fc.width * n2;
         if (block_samples * 12 > kMaxPathTable)
             return fail(SR_ERR_UNSUPPORTED, "path tracing: the random table of the largest row block (12 bytes per sample) exceeds 256 MiB; raise concurrency or render row ranges");
-        if (!s->d_pt_table.p || s->pt_table_seed != f->random_seed || s->pt_table_samples < (size_t)block_samples) {
-            if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still read the old table
-            std::vector<int32_t> ints((size_t)block_samples * 3);
-            sr::NetRandom random(f->random_seed);
-            for (int32_t& v : ints) v = random.next();
-            s->pt_table_samples = 0;
-            SR_HIP(s->d_pt_table.upload(ints));
-            s->pt_table_seed = f->random_seed;
-            s->pt_table_samples = (size_t)block_samples;
+        if ((rc = ensure_draw_table(s, f->random_seed, (size_t)block_samples))) return rc;
+    }
+    // ---- ambient occlusion: the same row blocks; the stage sees every hit record of the frame, so the frame is one pipeline and one band ----
+    if (ao) {
+        if (band_rows < fc.num_rows) return fail(SR_ERR_UNSUPPORTED, "ambient occlusion: the row range does not fit one row band");
+        const long long conc = f->concurrency > 0 ? f->concurrency : 4;
+        pt_block_height = (int)(((long long)fc.num_rows - 1 + conc) / conc);
+        pt_blocks = (fc.num_rows + pt_block_height - 1) / pt_block_height;
+        if (!ao_uncached) {
+            SR_HIP(s->d_ao_cache.reserve(kAoCells));
+            SR_HIP(s->d_ao_claim.reserve(kAoCells * 8));
+            if (s->ao_cache_empty) {
+                SR_HIP(hipMemsetAsync(s->d_ao_cache.p, 0, kAoCells, stream));
+                s->ao_cache_empty = false;
+            }
         }
     }
     const bool path_walk = path && f->trace_mode == SR_MODE_BVH;
@@ -851,8 +898,9 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     for (int h = 0; h < halves; ++h) {
         sr_scene::BandScratch& B = s->scratch[h];
         B.used_last_frame = true;
-        if (shadows || bounce_pipe || path) SR_HIP(B.hits.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
-        if (path) {
+        if (shadows || bounce_pipe || path || ao) SR_HIP(B.hits.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
+        if (ao) SR_HIP(B.ao_escapes.reserve((size_t)band_samples * 4));
+        if (path || ao) {
             SR_HIP(B.hits2.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
             SR_HIP(B.pt_flags.reserve((size_t)band_samples));
             SR_HIP(B.pt_index.reserve((size_t)band_samples * 4));
@@ -935,11 +983,26 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.pixels = d_pixels;
         P.samples = (uint32_t*)B.samples.p;
         P.hits = B.hits.p;
-        P.hits2 = (bounce_pipe || path) ? B.hits2.p : nullptr;
-        P.pt_flags = path ? (uint8_t*)B.pt_flags.p : nullptr;
-        P.pt_index = path ? (uint32_t*)B.pt_index.p : nullptr;
-        P.pt_totals = path ? (uint32_t*)B.pt_totals.p : nullptr;
-        P.pt_carry = path ? (uint32_t*)B.pt_carry.p : nullptr;
+        P.hits2 = (bounce_pipe || path || ao) ? B.hits2.p : nullptr;
+        P.pt_flags = (path || ao) ? (uint8_t*)B.pt_flags.p : nullptr;
+        P.pt_index = (path || ao) ? (uint32_t*)B.pt_index.p : nullptr;
+        P.pt_totals = (path || ao) ? (uint32_t*)B.pt_totals.p : nullptr;
+        P.pt_carry = (path || ao) ? (uint32_t*)B.pt_carry.p : nullptr;
+        P.ao_cache = (ao && !ao_uncached) ? (uint8_t*)s->d_ao_cache.p : nullptr;
+        P.ao_claim = (ao && !ao_uncached) ? (unsigned long long*)s->d_ao_claim.p : nullptr;
+        P.ao_escapes = ao ? (uint32_t*)B.ao_escapes.p : nullptr;
+        s->ao_table_seed = f->random_seed;
+        s->ao_table_rc = SR_OK;
+        P.ao_table = !ao ? nullptr : [](void* user, unsigned long long generators) -> const int32_t* {
+            sr_scene* sc = (sr_scene*)user;
+            const unsigned long long limit = sc->dbg[SR_DBG_AO_TABLE_BYTES] > 0 ? (unsigned long long)sc->dbg[SR_DBG_AO_TABLE_BYTES] : (unsigned long long)kMaxPathTable;
+            if (generators * 1200ull > limit) {
+                sc->ao_table_rc = fail(SR_ERR_UNSUPPORTED, "ambient occlusion: the random table of the row block with the most generators (1200 bytes each) exceeds 256 MiB; raise concurrency or render row ranges");
+                return nullptr;
+            }
+            if ((sc->ao_table_rc = ensure_draw_table(sc, sc->ao_table_seed, (size_t)generators * 100))) return nullptr;
+            return (const int32_t*)sc->d_pt_table.p;
+        };
         P.pt_table = path ? (const int32_t*)s->d_pt_table.p : nullptr;
         P.pt_block_height = pt_block_height;
         P.pt_blocks = pt_blocks;
@@ -1015,7 +1078,11 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             sc->band_recs.push_back({e, band, row_begin, row_count});
         };
         if (accum_fresh) SR_HIP(hipMemsetAsync(B.accum.p, 0, B.accum.cap, bs));
-        if (P.row_first < P.row_limit) SR_HIP(sr::launch_pipeline(P));
+        if (P.row_first < P.row_limit) {
+            const hipError_t pe = sr::launch_pipeline(P);
+            if (pe == hipErrorNotSupported && s->ao_table_rc) return s->ao_table_rc;      // (the message is the callback's)
+            SR_HIP(pe);
+        }
         if (split && !sequential_parts) {
             SR_HIP(hipEventRecord(B.done, bs));
             SR_HIP(hipStreamWaitEvent(stream, B.done, 0));          // the caller's stream continues after both halves
@@ -1077,7 +1144,9 @@ hipError_t copy_runs(const std::vector<StripRun>& runs, int n, int width, const 
 }
 
 // frames that cannot be split (one global fill order) are rendered whole by the first part
-bool multi_splittable(const sr_frame* f) { return !((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) && f->strip_count <= 0; }
+bool multi_splittable(const sr_frame* f) {
+    return !((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) && !(f->flags & SR_F_AMBIENT_OCCLUSION) && f->strip_count <= 0;
+}
 
 // a part of a multi-device scene takes the first part's model by reference: counts, box and flags here, the arrays stay with `src`
 // (sync_geometry uploads from them); nothing of the size of the model is copied on the host
@@ -1089,6 +1158,7 @@ void share_host_model(sr_scene* d, const sr_scene* src) {
     d->have_model = src->have_model;
     d->root = src->root;
     d->shadow_cache_empty = true;
+    d->ao_cache_empty = true; d->ao_cache_host.clear();
     d->vox_valid = false;
     d->ref = sr::RefTree(); d->bvh = sr::Bvh(); d->bvh_on_device = false;
     d->tris_dirty = d->ref_dirty = d->bvh_dirty = true;
@@ -1186,7 +1256,7 @@ void sr_destroy(sr_scene* s) {
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
-                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
+                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
                         &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
@@ -1219,6 +1289,7 @@ int sr_set_triangles(sr_scene* s, const double* v9, const uint32_t* argb, int64_
     if (!s || n < 0 || (n > 0 && (!v9 || !argb)) || !box_min || !box_max) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_triangles");
     if (n > 0x7fffff00) return fail(SR_ERR_INVALID_ARG, "too many triangles");
     s->shadow_cache_empty = true;                         // new model: what a new ShadowMethod starts with
+    s->ao_cache_empty = true; s->ao_cache_host.clear();   // ... and a new AmbientOcclusion
     s->vox_valid = false;                                 // ... and a new VoxelGrid
     s->v9.assign(v9, v9 + 9 * n);
     s->argb.assign(argb, argb + n);
@@ -1470,6 +1541,43 @@ int sr_reset_shadow_cache(sr_scene* s) {
     if (s && !s->parts.empty()) { for (sr_scene* q : s->parts) q->shadow_cache_empty = true; return SR_OK; }
     if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_reset_shadow_cache");
     s->shadow_cache_empty = true;
+    return SR_OK;
+}
+
+int sr_reset_ao_cache(sr_scene* s) {
+    if (s && !s->parts.empty()) s = s->parts[0];                    // (a multi-device scene renders its AO frames on the first part)
+    if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_reset_ao_cache");
+    s->ao_cache_empty = true;
+    s->ao_cache_host.clear();
+    return SR_OK;
+}
+
+int sr_get_ao_cache(sr_scene* s, uint8_t* out) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_get_ao_cache");
+    if (s->device < 0) {
+        if (s->ao_cache_host.empty()) std::memset(out, 0, kAoCells);
+        else std::memcpy(out, s->ao_cache_host.data(), kAoCells);
+        return SR_OK;
+    }
+    if (s->ao_cache_empty || !s->d_ao_cache.p) { std::memset(out, 0, kAoCells); return SR_OK; }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still be filling cells
+    SR_HIP(hipMemcpy(out, s->d_ao_cache.p, kAoCells, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_set_ao_cache(sr_scene* s, const uint8_t* in) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !in) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_ao_cache");
+    if (s->device < 0) { s->ao_cache_host.assign(in, in + kAoCells); return SR_OK; }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still read the old bytes
+    SR_HIP(s->d_ao_cache.reserve(kAoCells));
+    SR_HIP(hipMemcpy(s->d_ao_cache.p, in, kAoCells, hipMemcpyHostToDevice));
+    s->ao_cache_empty = false;
     return SR_OK;
 }
 
@@ -1904,6 +2012,7 @@ int sr_rccl_render(sr_scene* s, const sr_frame* f, void* d_full, void* hip_strea
     if (rc) return rc;
     if (f->strip_count > 0) return fail(SR_ERR_INVALID_ARG, "sr_rccl_render splits the frame itself: strip_count must be 0");
     if ((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) return fail(SR_ERR_UNSUPPORTED, "static shadows need the whole frame on one device");
+    if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "ambient occlusion needs the whole frame on one device (sr_rccl_render splits it into strips)");
     if ((rc = use_device(s))) return rc;
     sr_frame fg = *f;
     fg.strip_rows = kMultiStripRows; fg.strip_count = s->rccl_world; fg.strip_index = s->rccl_rank;

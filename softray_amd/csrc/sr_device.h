@@ -41,7 +41,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_COUNT = 17 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_COUNT = 19 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -101,6 +101,14 @@ struct PipelineLaunch {
     uint32_t*     pt_row_hits;  // device [pt_range_rows]: hits per image row of the range (phase 1 writes the part's rows, phase 2 reads all)
     uint32_t*     pt_row_k0;    // device [fc.num_rows]: hits of any part that precede the compact row inside its row block
     int32_t       pt_range_first, pt_range_rows;
+    // ambient occlusion (SR_F_AMBIENT_OCCLUSION; all nullptr otherwise).  The stage runs on the band's hit queue after the shadow stage; it uses
+    // pt_flags / pt_index / pt_totals / pt_carry and pt_block_height / pt_blocks for the generators' scan and hits2 for the generator list
+    uint8_t*      ao_cache;     // device [128^3]: the scene's AO cache, 0 = empty cell (read and written in cached mode only)
+    unsigned long long* ao_claim; // device [128^3]: smallest order key that asked for an empty cell (cached mode)
+    uint32_t*     ao_escapes;   // device [band samples]: escaped probes per generator, then its byte
+    // called once the number of generators is known (the stream has been waited for): the table of the seed's InternalSample() ints that
+    // holds 300 draws for each of `generators` generators of one row block, or nullptr when the host refuses it
+    const int32_t* (*ao_table)(void* user, unsigned long long generators);
     void*         static_hits;  // device HitRec[min(band samples, 128^3)]: generators of a static-shadow frame
     unsigned long long* static_claim; // device [128^3]: smallest order key that asked for an empty cell
     int32_t       static_concurrency; // rayTraceConcurrency of the frame

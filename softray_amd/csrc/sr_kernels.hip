@@ -153,6 +153,8 @@ const char* kernel_name(int id) {
         case K_PATHTRACE: return "k_pathtrace";
         case K_PT_COUNT: return "k_pathtrace_count";          // a part of a split frame: hit-index scan + the rows' hit counts (first phase)
         case K_PT_EXCHANGE: return "pathtrace_exchange";      // ... its counts out, the wait for the other parts, all counts back (copies, no kernel)
+        case K_AO: return "ambient_occlusion";                // the whole stage of one frame: claim, scan, select, probes, store, apply
+        case K_AO_PROBE: return "k_ao_probe";
         case K_VOXEL_WALK: return "k_voxel_walk";
         case K_VOXELISE: return "voxelise";                   // count, scan, emit, sort, per-cell sums of one sr_build_voxels
         case K_SHAFT2: return "k_shaft_round2";

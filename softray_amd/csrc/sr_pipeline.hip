@@ -3590,6 +3590,172 @@ __global__ __launch_bounds__(256) void k_static_apply(const uint8_t* __restrict_
 }
 
 // --------------------------------------------------------------------------------------------------
+// rayTraceAmbientOcclusion (SR_F_AMBIENT_OCCLUSION; AmbientOcclusionMethod.cs:65-99, AmbientOcclusion.cs:101-230): the colour of every
+// camera sample that hits is modulated, after shading and shadows, with a byte 1..255 that says how many of 100 probe rays from the
+// surface point leave its neighbourhood.  The byte lives in a 128^3 texture over the unit cube (the surface point clamped to it) and an
+// empty cell is generated by whoever asks first; with the cache off every hit sample generates.  A generator's probes are made of 300
+// NextDouble() of its row block's Random, drawn in the block's scan order, so generator number k of a block uses draws 300 k .. 300 k + 299.
+// The two mechanisms this file already has, put together:
+//   k_ao_claim        (cached) every hit sample whose cell is empty claims it with an atomicMin on its order key (static_key: the
+//                     deterministic order of the static shadow cache)
+//   k_ao_mark         (cached) flag per scan position: the sample won its cell.  Uncached: k_pt_mark, every hit sample is a generator
+//   k_pt_scan, k_pt_scan_totals, k_pt_carry     the generators' exclusive prefix sum in scan order and their number per row block
+//   k_ao_select       generator list in scan order (no atomics): clamped position, normal, sample, cell, k
+//   k_ao_probe        lane = (generator, probe): direction from the table, nearest hit through the root geometry in the frame's trace
+//                     mode (SR_MODE_BVH: any hit with rayFrac <= 2.0), escape = no hit or rayFrac > 2.0; the escapes are counted per
+//                     generator with ballots
+//   k_ao_store        count -> (byte)(count / 100.0 * 254 + 1), into the cache (cached) and the generator's slot
+//   k_ao_apply        every hit sample: modulate with its cell's byte (cached) or its own (uncached)
+// Escape counts are integers: no order of the adds changes a byte.
+// --------------------------------------------------------------------------------------------------
+constexpr int kAoProbes = 100;           // ambientOcclusionQuality, AmbientOcclusion.cs:21
+constexpr double kAoProbeOffset = 0.001, kAoProbeDist = 2.0;   // :22-23
+
+__device__ __forceinline__ double ao_clamp1(double x) {                   // Math.Min(Math.Max(-0.5, x), 0.5)
+    const double a = -0.5 > x ? -0.5 : x;
+    return a < 0.5 ? a : 0.5;
+}
+__device__ __forceinline__ D3 ao_clamp(const double* pos) { return mk(ao_clamp1(pos[0]), ao_clamp1(pos[1]), ao_clamp1(pos[2])); }
+__device__ __forceinline__ uint32_t ao_cell(D3 p) {                        // AmbientOcclusion.cs:118-120 (scale = 1.0)
+    const int n = kStaticRes;
+    return (uint32_t)((int)((p.x * 1.0 + 0.5) * (n - 1)) * n * n + (int)((p.y * 1.0 + 0.5) * (n - 1)) * n + (int)((p.z * 1.0 + 0.5) * (n - 1)));
+}
+
+__global__ __launch_bounds__(256) void k_ao_claim(FrameConst fc, const uint8_t* __restrict__ cache, const HitRec* __restrict__ hits,
+                                                  const unsigned int* __restrict__ count, unsigned long long* __restrict__ claim,
+                                                  int block_height, int nblocks) {
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    for (unsigned int h = blockIdx.x * 256u + threadIdx.x; h < total; h += stride) {
+        const uint32_t sample = hits[h].sample;
+        if (sample == kInvalidHit) continue;
+        const uint32_t cell = ao_cell(ao_clamp(hits[h].pos));
+        if (cache[cell] == 0) atomicMin(&claim[cell], static_key(fc, sample, block_height, nblocks));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ao_mark(FrameConst fc, PtBand band, const uint8_t* __restrict__ cache, const HitRec* __restrict__ hits,
+                                                 const unsigned int* __restrict__ count, const unsigned long long* __restrict__ claim,
+                                                 int block_height, int nblocks, uint8_t* __restrict__ flags) {
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    for (unsigned int h = blockIdx.x * 256u + threadIdx.x; h < total; h += stride) {
+        const uint32_t sample = hits[h].sample;
+        if (sample == kInvalidHit) continue;
+        const uint32_t cell = ao_cell(ao_clamp(hits[h].pos));
+        const uint32_t p = sample - band.sample_base;
+        if (p < band.n && cache[cell] == 0 && claim[cell] == static_key(fc, sample, block_height, nblocks)) flags[p] = 1;
+    }
+}
+
+// gen[g] for the g-th generator of the band in scan order: pos = the clamped surface point, pad[0] = cell, pad[1] = k inside its row block
+__global__ __launch_bounds__(256) void k_ao_select(PtBand band, const HitRec* __restrict__ hits, const unsigned int* __restrict__ count,
+                                                   const uint8_t* __restrict__ flags, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ totals,
+                                                   HitRec* __restrict__ gen) {
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    for (unsigned int h = blockIdx.x * 256u + threadIdx.x; h < total; h += stride) {
+        HitRec r = hits[h];
+        if (r.sample == kInvalidHit) continue;
+        const uint32_t p = r.sample - band.sample_base;
+        if (p >= band.n || !flags[p]) continue;
+        const int32_t block = (band.row_begin + (int32_t)(p / band.row_samples)) / band.block_height;
+        const int32_t first = block * band.block_height - band.row_begin;
+        const uint32_t p0 = first > 0 ? (uint32_t)first * band.row_samples : 0u;
+        const uint32_t g = pt_before(idx, totals, band.n, p);
+        const D3 c = ao_clamp(r.pos);
+        r.pos[0] = c.x; r.pos[1] = c.y; r.pos[2] = c.z;
+        r.pad[0] = ao_cell(c);
+        r.pad[1] = g - pt_before(idx, totals, band.n, p0);
+        r.pad[2] = 0;
+        gen[g] = r;
+    }
+}
+
+// lane = (generator, probe) pair number blockIdx.x * 256 + threadIdx.x (+ the grid's stride): all 64 lanes of every wave but the last
+// carry a probe.  A wave's 64 pairs belong to at most two generators (100 > 64): two ballots, at most two atomicAdds per wave.
+// (LDS: the per-lane traversal stacks of root_intersect, stack levels x 256 lanes x 4 bytes, as k_pt_finish)
+// ANYHIT (SR_MODE_BVH only): "no hit or the nearest hit's rayFrac > 2.0" is "no hit with rayFrac <= 2.0", which the any-hit walk answers
+// at the first such hit it meets (fl(t + offset) is monotone in t, so the nearest hit qualifies iff any does); false keeps the nearest-hit walk
+template <int MODE, bool EXTRA, bool STATS, bool ANYHIT>
+__global__ __launch_bounds__(256) void k_ao_probe(DevScene sc, const HitRec* __restrict__ gen, unsigned int ngen, const int32_t* __restrict__ table,
+                                                  uint32_t* __restrict__ escapes, unsigned long long* stats) {
+    const int tid = threadIdx.x;
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    const unsigned long long items = (unsigned long long)ngen * (unsigned long long)kAoProbes, stride = (unsigned long long)gridDim.x * 256ull;
+    Ctr sec = {0, 0, 0, 0};
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 256ull; base < items; base += stride) {     // (block-uniform trip count)
+        const unsigned long long item = base + (unsigned long long)tid;
+        const bool live = item < items;
+        const unsigned int g = (unsigned int)(item / (unsigned long long)kAoProbes);
+        bool escaped = false;
+        if (live) {
+            const unsigned int i = (unsigned int)(item - (unsigned long long)g * (unsigned long long)kAoProbes);
+            const HitRec q = gen[g];
+            const int32_t* u = table + ((size_t)q.pad[1] * (size_t)(3 * kAoProbes) + (size_t)(3u * i));
+            // NextDouble() = InternalSample() * (1.0 / int.MaxValue); not normalised (AmbientOcclusion.cs:189-192)
+            const double ux = u[0] * (1.0 / 2147483647.0), uy = u[1] * (1.0 / 2147483647.0), uz = u[2] * (1.0 / 2147483647.0);
+            const D3 n = mk(q.nrm[0], q.nrm[1], q.nrm[2]);
+            D3 d = mk(ux * 2 - 1, uy * 2 - 1, uz * 2 - 1);
+            if (dot(d, n) < 0.0) d = neg(d);
+            const D3 s = mk(q.pos[0], q.pos[1], q.pos[2]) + n * kAoProbeOffset;
+            Hit h;
+            sec.rays++;
+            if constexpr (MODE == MODE_BVH && ANYHIT) {
+                bool occluded = false;
+                if (EXTRA) {
+                    for (int e = 0; e < sc.nextra && !occluded; ++e) {
+                        double t; D3 pos, nrm;
+                        uint32_t tests;
+                        const bool ok = extra_hit(&sc.extra[e], s, d, t, pos, nrm, tests);
+                        sec.geom += tests;
+                        occluded = ok && t <= kAoProbeDist;
+                    }
+                }
+                escaped = !occluded && !bvh_intersect<true>(sc, st, s, d, h, sec, kAoProbeDist);
+            } else {
+                const bool ok = root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, s, d, h, sec);
+                escaped = !ok || h.t > kAoProbeDist;
+            }
+        }
+        const unsigned int g0 = __shfl(g, 0, 64);                                 // lane 0 holds the wave's lowest pair
+        const unsigned long long m0 = __ballot(escaped && g == g0), m1 = __ballot(escaped && g != g0);
+        if ((tid & 63) == 0) {
+            if (m0) atomicAdd(&escapes[g0], (uint32_t)__popcll(m0));
+            if (m1) atomicAdd(&escapes[g0 + 1u], (uint32_t)__popcll(m1));
+        }
+    }
+    if (STATS) {
+        uint32_t a = wave_sum(sec.rays), b = wave_sum(sec.geom), c2 = wave_sum(sec.nodes), d2 = wave_sum(sec.leaves);
+        if ((tid & 63) == 0) { stat_add(&stats[4], a); stat_add(&stats[5], b); stat_add(&stats[6], c2); stat_add(&stats[7], d2); }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ao_store(const HitRec* __restrict__ gen, unsigned int ngen, uint32_t* __restrict__ escapes, uint8_t* __restrict__ cache) {
+    const unsigned int g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= ngen) return;
+    const uint32_t v = to_byte((double)escapes[g] / (double)kAoProbes * 254 + 1);          // AmbientOcclusion.cs:135,151
+    escapes[g] = v;
+    if (cache) cache[gen[g].pad[0]] = (uint8_t)v;
+}
+
+// cache != nullptr: the cell's byte (non-zero for every hit cell by now); nullptr: every hit sample is a generator, number pt_before(p)
+__global__ __launch_bounds__(256) void k_ao_apply(PtBand band, const uint8_t* __restrict__ cache, const HitRec* __restrict__ hits,
+                                                  const unsigned int* __restrict__ count, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ totals,
+                                                  const uint32_t* __restrict__ bytes, uint32_t* __restrict__ samples) {
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    for (unsigned int h = blockIdx.x * 256u + threadIdx.x; h < total; h += stride) {
+        const uint32_t sample = hits[h].sample;
+        if (sample == kInvalidHit) continue;
+        uint32_t amount;
+        if (cache) amount = cache[ao_cell(ao_clamp(hits[h].pos))];
+        else {
+            const uint32_t p = sample - band.sample_base;
+            if (p >= band.n) continue;
+            amount = bytes[pt_before(idx, totals, band.n, p)];
+        }
+        samples[sample] = modulate(samples[sample], amount);                               // AmbientOcclusionMethod.cs:97
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_cam_cones: per-frame pre-pass of the packet primary walk -- the CamCone record (sr_types.h) of every BVH triangle for
 // the frame's ray origin O: FP64 cross products of the FP64 vertices, rounded once to fp32.  64 B written + 72 B (gathered)
 // + 8 B read per triangle: 0.15 GB at 1 M triangles; re-run only when the origin or the tree changed.
@@ -4120,6 +4286,85 @@ static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int
     return hipSuccess;
 }
 
+// the ambient-occlusion stage of a frame's one row band (see k_ao_claim): `count` = the entries of the band's hit queue (invalid
+// entries of a tile-indexed queue are skipped).  Waits for the stream once: the host sizes the draw table by the largest number of
+// generators in a row block.  hipErrorNotSupported: the host refused the table (L.ao_table has left the reason)
+template <int MODE, bool EXTRA>
+static hipError_t launch_ao_t(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples, long long max_hits) {
+    const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
+    const bool cached = !(L.fc.flags & kFlagAoUncached);
+    hipError_t e;
+    hipEvent_t e0, e1;
+    pipe_events(L, K_AO, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    PtBand band;
+    band.n = (uint32_t)((long long)row_count * L.fc.width * n2);
+    band.row_samples = (uint32_t)(L.fc.width * n2);
+    band.sample_base = n2 == 1 ? (uint32_t)((long long)(L.fc.first_row + row_begin) * L.fc.width) : 0u;      // (no strips: sr_api.cpp)
+    band.row_begin = row_begin;
+    band.block_height = L.pt_block_height;
+    const uint32_t chunks = (band.n + (uint32_t)kPtChunk - 1u) / (uint32_t)kPtChunk;
+    const unsigned blocks = (unsigned)std::min<long long>((max_hits + 255) / 256, (long long)L.persistent_blocks);
+    const HitRec* hits = (const HitRec*)L.hits;
+    HitRec* gen = (HitRec*)L.hits2;
+    const unsigned int* count = L.counters;
+    if ((e = hipMemsetAsync(L.pt_flags, 0, band.n, L.stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(L.pt_carry, 0, (size_t)L.pt_blocks * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
+    if (cached) {
+        if ((e = hipMemsetAsync(L.ao_claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ao_claim, dim3(blocks), dim3(256), 0, L.stream, L.fc, (const uint8_t*)L.ao_cache, hits, count, L.ao_claim, L.pt_block_height, L.pt_blocks);
+        hipLaunchKernelGGL(k_ao_mark, dim3(blocks), dim3(256), 0, L.stream, L.fc, band, (const uint8_t*)L.ao_cache, hits, count, (const unsigned long long*)L.ao_claim,
+                           L.pt_block_height, L.pt_blocks, L.pt_flags);
+    } else {
+        hipLaunchKernelGGL(k_pt_mark, dim3(blocks), dim3(256), 0, L.stream, band, hits, count, L.pt_flags);
+    }
+    hipLaunchKernelGGL(k_pt_scan, dim3(chunks), dim3(256), 0, L.stream, (const uint8_t*)L.pt_flags, band.n, L.pt_index, L.pt_totals);
+    hipLaunchKernelGGL(k_pt_scan_totals, dim3(1), dim3(256), 0, L.stream, L.pt_totals, chunks);
+    hipLaunchKernelGGL(k_pt_carry, dim3((unsigned)((L.pt_blocks + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                       L.pt_carry, (int)L.pt_blocks);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    // ---- how many generators, and how many in the fullest row block? ----
+    std::vector<uint32_t> per_block((size_t)L.pt_blocks + 1, 0u);
+    if ((e = hipMemcpyAsync(per_block.data(), L.pt_carry, (size_t)L.pt_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(&per_block[(size_t)L.pt_blocks], L.pt_totals + chunks, sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(L.stream)) != hipSuccess) return e;
+    const unsigned int ngen = per_block[(size_t)L.pt_blocks];
+    const unsigned int block_max = *std::max_element(per_block.begin(), per_block.end() - 1);
+    if (ngen > 0) {
+        const int32_t* table = L.ao_table ? L.ao_table(L.user, block_max) : nullptr;
+        if (!table) {
+            if (e1) (void)hipEventRecord(e1, L.stream);                       // (the stage's event pair stays a pair)
+            return hipErrorNotSupported;
+        }
+        if ((e = hipMemsetAsync(L.ao_escapes, 0, (size_t)ngen * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ao_select, dim3(blocks), dim3(256), 0, L.stream, band, hits, count, (const uint8_t*)L.pt_flags, (const uint32_t*)L.pt_index,
+                           (const uint32_t*)L.pt_totals, gen);
+        const unsigned long long items = (unsigned long long)ngen * (unsigned long long)kAoProbes;
+        const unsigned pblocks = (unsigned)std::min<unsigned long long>((items + 255) / 256, (unsigned long long)L.persistent_blocks);
+        const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+        unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
+        hipEvent_t p0, p1;
+        pipe_events(L, K_AO_PROBE, p0, p1);
+        if (p0 && (e = hipEventRecord(p0, L.stream)) != hipSuccess) return e;
+        const auto probe = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), lds, L.stream, L.sc, (const HitRec*)gen, ngen, table, L.ao_escapes, sec_stats);
+        };
+        if (MODE == MODE_BVH && L.fc.debug != 34) {                                   // (hook 34: nearest-hit walks, same bytes)
+            if (sec_stats) probe(k_ao_probe<MODE, EXTRA, true, true>); else probe(k_ao_probe<MODE, EXTRA, false, true>);
+        } else {
+            if (sec_stats) probe(k_ao_probe<MODE, EXTRA, true, false>); else probe(k_ao_probe<MODE, EXTRA, false, false>);
+        }
+        if (p1 && (e = hipEventRecord(p1, L.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ao_store, dim3((ngen + 255u) / 256u), dim3(256), 0, L.stream, (const HitRec*)gen, ngen, L.ao_escapes, cached ? L.ao_cache : nullptr);
+    }
+    if (cached || ngen > 0)
+        hipLaunchKernelGGL(k_ao_apply, dim3(blocks), dim3(256), 0, L.stream, band, cached ? (const uint8_t*)L.ao_cache : nullptr, hits, count,
+                           (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals, (const uint32_t*)L.ao_escapes, samples);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
 static hipError_t launch_resolve(const PipelineLaunch& L, int row_begin, int row_count) {
     hipError_t e;
     hipEvent_t e0, e1;
@@ -4144,6 +4389,7 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     const bool shadows = (L.fc.flags & 2u) != 0;
     const bool path = (L.fc.flags & kFlagPathTracing) != 0;          // (sr_api.cpp: never together with shadows or mirror bounces)
+    const bool ao = (L.fc.flags & kFlagAmbientOcclusion) != 0;       // (sr_api.cpp: one band, never with path tracing, the static cache or mirror bounces)
     if (path && L.pt_phase == 0) {
         hipError_t e = hipMemsetAsync(L.pt_carry, 0, (size_t)L.pt_blocks * sizeof(uint32_t), L.stream);
         if (e != hipSuccess) return e;
@@ -4176,8 +4422,9 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
         // the shaft path of a dynamic-shadow frame reads the hit queue tile by tile (k_shaft_pkt): 64-aligned entries
         const bool shaft_frame = (MODE != MODE_BVH && L.shadows_on_bvh) ? shaft_path<MODE_BVH>(L) : shaft_path<MODE>(L);
         const int pad_tiles = (shadows && !(L.fc.flags & 32u) && L.fc.max_bounces == 0 && shaft_frame) ? 1 : 0;
-        if (path) {
-            // the primary pass of a shadowed frame is what the path tracer needs: shaded sample colours + the compacted hit queue
+        if (path || (ao && !shadows)) {
+            // the primary pass of a shadowed frame is what the path tracer (and the ambient-occlusion stage of a frame without shadow rays)
+            // needs: shaded sample colours + the compacted hit queue
             PipelineLaunch Q = L;
             Q.fc.flags |= 2u;
             e = L.fc.sub_pixel_res > 1 ? launch_primary_s<MODE, EXTRA, true>(Q, row_begin, row_count, samples, 0)
@@ -4308,6 +4555,11 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
         } else if (path) {
             if ((e = launch_pathtrace_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
             if (L.pt_phase == 1) continue;                           // the counting pass of a split frame: its pixels are phase 2's
+        }
+        if (ao) {
+            // after ShadowMethod has finished the samples (AmbientOcclusionMethod wraps it, Renderer.cs:1631-1638); the queue is the band's
+            const long long max_hits = (long long)((row_count + 15) / 16 * 16) * ((L.fc.width + 15) / 16 * 16) * n2;
+            if ((e = launch_ao_t<MODE, EXTRA>(L, row_begin, row_count, samples, max_hits)) != hipSuccess) return e;
         }
         if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
         if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);

@@ -383,8 +383,9 @@ __device__ __forceinline__ uint32_t leaf_survivors(const DevScene& sc, int32_t f
     return m;
 }
 
+// ANY: is there a hit with rayFrac <= any_limit?  (1.0: a shadow sample ray ends at the light; the ambient-occlusion probes pass 2.0)
 template <bool ANY>
-__device__ bool bvh_intersect(const DevScene& sc, Stack st, D3 s, D3 d, Hit& out, Ctr& c) {
+__device__ bool bvh_intersect(const DevScene& sc, Stack st, D3 s, D3 d, Hit& out, Ctr& c, double any_limit = 1.0) {
     D3 end = s + d * 10000.0;
     D3 original = s;
     if (!clip_segment<false>(sc.root, s, end)) return false;
@@ -397,8 +398,8 @@ __device__ bool bvh_intersect(const DevScene& sc, Stack st, D3 s, D3 d, Hit& out
     const float kInfl = 1.0f + 9.5367431640625e-7f;          // 1 + 2^-20
     float tlim = FLT_MAX;
     if (ANY) {
-        // occluder <=> fl(t + offset) <= 1.0 ; nothing beyond t = 1 - offset (inflated) can qualify
-        double lim = 1.0 - offset;
+        // occluder <=> fl(t + offset) <= any_limit ; nothing beyond t = any_limit - offset (inflated) can qualify
+        double lim = any_limit - offset;
         if (lim < 0.0) return false;
         tlim = (float)lim * kInfl + 1e-30f;
     }
@@ -450,7 +451,7 @@ __device__ bool bvh_intersect(const DevScene& sc, Stack st, D3 s, D3 d, Hit& out
                 c.geom++;
                 if (tri_hit(r->p, s, d, t, pos) && inside(sc.root.lo, sc.root.hi, pos)) {
                     if (ANY) {
-                        if (t + offset <= 1.0) { out.t = t + offset; out.tri = k; return true; }   // out.tri = record position: the caller's blocker cache
+                        if (t + offset <= any_limit) { out.t = t + offset; out.tri = k; return true; }   // out.tri = record position: the caller's blocker cache
                     } else {
                         const int32_t idx = r->aux;
                         if (t < best || (t == best && idx < bestIdx)) {

@@ -177,6 +177,7 @@ public:
     bool rayTrace = false, rayTraceShading = true, rayTraceShadows = false, rayTraceShadowsStatic = false;
     bool rayTraceAmbientOcclusion = false, rayTraceLightField = false, rayTraceSubdivision = true;
     bool rayTracePathTracing = false, rayTraceVoxels = false, rayTraceFocalBlur = true;
+    bool ambientOcclusionEnableCache = true;               // AmbientOcclusionMethod.EnableCache (Renderer.cs:74 TODO, RendererTests.cs:405); false = SR_F_AO_UNCACHED
     double rayTraceFocalDepth = 1.5, rayTraceFocalBlurStrength = 10.0;
     int rayTraceConcurrency = 4, rayTraceSubPixelRes = 1, rayTraceRandomSeed = 1234567890;
     int rayTraceStartRow = 0, rayTraceEndRow = 0;
@@ -210,6 +211,7 @@ public:
     Renderer(const Renderer&) = delete;
     Renderer& operator=(const Renderer&) = delete;
     void Dispose() { if (scene_) { sr_destroy(scene_); scene_ = nullptr; } }   // Renderer.cs:236
+    void ResetAmbientOcclusionCache() { sr_check(sr_reset_ao_cache(scene_)); }   // what a new Renderer's AmbientOcclusionMethod starts with
     int gpuLastFrameParts() const { return scene_ ? sr_last_frame_parts(scene_) : 0; }   // parts (devices) that rendered rows of the last frame
 
     uint32_t BackgroundColor() const { return backgroundColor_; }
@@ -281,8 +283,15 @@ public:
     void Render() {                                        // Renderer.cs:701-778
         if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
         if (!PinModel()) return;                           // silently, :736-739
-        if (rayTraceAmbientOcclusion || rayTraceLightField)
-            throw std::logic_error("AO / light field are out of scope (racy or RNG-order dependent in the reference)");
+        if (rayTraceLightField)
+            throw std::logic_error("rayTraceLightField is out of scope (a disk-backed cache the reference's own tests ignore)");
+        if (rayTraceAmbientOcclusion) {                    // SR_F_AMBIENT_OCCLUSION: the pairs the library refuses, by name
+            if (rayTracePathTracing) throw std::logic_error("rayTraceAmbientOcclusion together with rayTracePathTracing is out of scope (SR_F_AMBIENT_OCCLUSION)");
+            if (rayTraceVoxels) throw std::logic_error("rayTraceAmbientOcclusion together with rayTraceVoxels is out of scope (SR_F_AMBIENT_OCCLUSION)");
+            if (rayTraceShadows && rayTraceShadowsStatic)
+                throw std::logic_error("rayTraceAmbientOcclusion together with rayTraceShadowsStatic is out of scope (SR_F_AMBIENT_OCCLUSION)");
+            if (gpuMaxBounces > 0) throw std::logic_error("rayTraceAmbientOcclusion together with gpuMaxBounces is out of scope (SR_F_AMBIENT_OCCLUSION)");
+        }
         if (rayTraceVoxels && (rayTraceShadows || rayTracePathTracing || gpuMaxBounces > 0))   // SR_F_VOXELS: the reference's result there is a rayFrac = 0 artefact
             throw std::logic_error("rayTraceVoxels together with rayTraceShadows, rayTracePathTracing or mirror bounces is out of scope (SR_F_VOXELS)");
         if (rayTracePathTracing && rayTraceShadows)
@@ -311,13 +320,15 @@ public:
                   (rayTraceShadows && rayTraceShadowsStatic ? SR_F_STATIC_SHADOWS : 0u) |      // Renderer.cs:1625; the cache lives in the scene
                   (rayTraceFocalBlur ? SR_F_FOCAL_BLUR : 0u) |
                   (rayTracePathTracing ? SR_F_PATH_TRACING : 0u) |                                 // Renderer.cs:1613-1618; reads random_seed, concurrency
+                  (rayTraceAmbientOcclusion ? SR_F_AMBIENT_OCCLUSION : 0u) |                       // Renderer.cs:1631-1638; reads random_seed, concurrency
+                  (rayTraceAmbientOcclusion && !ambientOcclusionEnableCache ? SR_F_AO_UNCACHED : 0u) |
                   (rayTraceVoxels ? SR_F_VOXELS : 0u) |                                            // Renderer.cs:1568-1588: the grid replaces tree and extra geometry
                   (pointLighting ? SR_F_POINT_LIGHT : 0u) | (specularLighting ? SR_F_SPECULAR : 0u) |
                   SR_F_PRIMARY_STATS_ONLY;                 // Num* count primary rays (Renderer.cs:1916-1923)
         f.random_seed = rayTraceRandomSeed;
         f.trace_mode = Mode();
         f.max_bounces = gpuMaxBounces;
-        f.concurrency = rayTraceConcurrency;              // the fill order of the static shadow cache, the path tracer's row blocks
+        f.concurrency = rayTraceConcurrency;              // the fill order of the static shadow / AO caches, the row blocks of path tracing and AO
         f.reflectivity = gpuReflectivity;
         double pos[3] = {instance.Position.x, instance.Position.y, instance.Position.z};
         sr_instance_matrices(pos, instance.Yaw, instance.Pitch, instance.Roll, f.transform, f.inv_transform);   // Instance.cs:134-135

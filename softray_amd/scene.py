@@ -173,6 +173,23 @@ class GpuScene:
         """Forget the static shadow cache (SR_F_STATIC_SHADOWS): what a new Renderer starts with."""
         _check(_lib.lib().sr_reset_shadow_cache(self._h))
 
+    # ---- rayTraceAmbientOcclusion (SR_F_AMBIENT_OCCLUSION frames) ----
+    def reset_ao_cache(self):
+        """Forget the ambient-occlusion cache: what a new Renderer starts with."""
+        _check(_lib.lib().sr_reset_ao_cache(self._h))
+
+    def get_ao_cache(self):
+        """The cache as uint8 [128, 128, 128] in x, y, z order (0 = empty cell): the array the reference persists to its .ao file."""
+        out = np.zeros((_lib.AO_RES,) * 3, dtype=np.uint8)
+        _check(_lib.lib().sr_get_ao_cache(self._h, _p(out)))
+        return out
+
+    def set_ao_cache(self, cache):
+        cache = np.ascontiguousarray(cache, dtype=np.uint8)
+        if cache.size != _lib.AO_RES ** 3:
+            raise ValueError("the ambient-occlusion cache is %d^3 bytes" % _lib.AO_RES)
+        _check(_lib.lib().sr_set_ao_cache(self._h, _p(cache)))
+
     def ray_stats(self):
         """primary {rays, tests, nodes, leaves} + secondary {rays, tests, nodes, leaves} of the last render(stats=True)."""
         out = np.zeros(24, dtype=np.uint64)                           # SR_STATS_COUNT

@@ -83,6 +83,11 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_reset_ao_cache(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_get_ao_cache(IntPtr scene, [Out] byte[] out128Cubed);
         [DllImport(Lib)] public static extern int sr_set_ao_cache(IntPtr scene, [In] byte[] in128Cubed);
+        [DllImport(Lib)] public static extern int sr_set_light_field_res(IntPtr scene, int n);
+        [DllImport(Lib)] public static extern int sr_get_light_field_res(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_reset_light_field(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_get_light_field(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
+        [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -127,6 +132,12 @@ namespace Engine3D.Hip
         /// the reference's .ao file (AmbientOcclusion.cs:232-309; the file itself stays the host's business).
         public const uint F_AMBIENT_OCCLUSION = 1u << 13, F_AO_UNCACHED = 1u << 14;
         public const int AoCacheBytes = 128 * 128 * 128;
+        /// rayTraceLightField with LightFieldStoresTriangles = false (Renderer.cs:1640-1649) = SR_F_LIGHT_FIELD: pass it in `flags`.  Not together
+        /// with F_SHADOWS, F_AMBIENT_OCCLUSION, F_PATH_TRACING, F_VOXELS or mirror bounces (SR_ERR_UNSUPPORTED -> InvalidOperationException);
+        /// LightFieldStoresTriangles = true (LightFieldTriMethod) keeps the CPU chain.  The table of 4 N^4 uint entries lives in the scene:
+        /// LightFieldResolution is N (default 64 = lightFieldRes), ResetLightField() is what a new Renderer starts with (call it when
+        /// LightFieldStoresTriangles changes, Renderer.cs:420-445), Get / SetLightField move ranges of the reference's .cache file.
+        public const uint F_LIGHT_FIELD = 1u << 15;
         const uint F_PRIMARY_STATS_ONLY = 1u << 12;     // Num* count primary rays (Renderer.cs:1916-1923): no counting in the shadow stage
         public const int MODE_REF_TREE = 0, MODE_BRUTE = 1, MODE_BVH = 2;
         /// How NumGeometryTests / NumNodeVisits / NumLeafNodeVisits (Renderer.cs:476-504) are answered -- an explicit choice of the
@@ -332,6 +343,26 @@ namespace Engine3D.Hip
         {
             if (data == null || data.Length != AoCacheBytes) throw new ArgumentException("the ambient-occlusion cache is 128^3 bytes");
             Native.Check(Native.sr_set_ao_cache(scene, data));
+        }
+
+        /// N of the light field's 4 N^4 entries, 1..128; another value drops the table
+        public int LightFieldResolution
+        {
+            get { return Native.sr_get_light_field_res(scene); }
+            set { Native.Check(Native.sr_set_light_field_res(scene, value)); }
+        }
+        /// A new Renderer starts with an empty light field (LightFieldColorMethod.cs:101-115)
+        public void ResetLightField() { Native.Check(Native.sr_reset_light_field(scene)); }
+        /// Entries first .. first + entries.Length - 1 of the table (0 = empty): ranges, so that the 256 MiB of N = 64 can be streamed
+        public void GetLightField(uint[] entries, ulong first)
+        {
+            if (entries == null) throw new ArgumentNullException("entries");
+            Native.Check(Native.sr_get_light_field(scene, entries, first, (ulong)entries.Length));
+        }
+        public void SetLightField(uint[] entries, ulong first)
+        {
+            if (entries == null) throw new ArgumentNullException("entries");
+            Native.Check(Native.sr_set_light_field(scene, entries, first, (ulong)entries.Length));
         }
 
         /// PostProcessImage's colour functions (Renderer.cs:819-865): style = (int)Renderer.Style for Standard..DepthBanded.

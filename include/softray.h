@@ -132,6 +132,32 @@ enum {
                                      count (not with SR_F_PRIMARY_STATS_ONLY); [0..3] are unchanged                                     */
     SR_F_AO_UNCACHED = 1u << 14,  /* with SR_F_AMBIENT_OCCLUSION only: AmbientOcclusionMethod.EnableCache = false (Renderer.cs:74) -- every hit sample
                                      generates its own byte, nothing is read from or stored in the cache                                */
+    SR_F_LIGHT_FIELD = 1u << 15,  /* rayTraceLightField with LightFieldStoresTriangles = false -> LightFieldColorMethod.Enabled (Renderer.cs:1640-1649,
+                                     LightFieldColorMethod.cs:92-217, LightField4D.cs:175-206, 253-273, 304-344, Sphere.cs:69-142): the colour of a camera sample is
+                                     the entry of a 4-D table of 4 N^4 uint32 (N = sr_set_light_field_res, default 64) that its line falls into.  In model space,
+                                     with R = 0.866 about the origin: d = dir * (1.0 / |dir|), proj = start . d, term = proj * proj - start . start + R * R;
+                                     term < 1e-10 is the background colour (nothing checks whether the start lies inside the sphere).  Otherwise the two
+                                     points start + d * (-proj -/+ sqrt(term)) give h = atan2(x, z), w = asin(y / R) (not clamped) and the coordinates
+                                     u = h1 / pi * 0.5 + 0.5, v = w1 / pi + 0.5, s, t likewise; the cell is ((byte)(u * (2N - 1)), (byte)(v * (N - 1)),
+                                     (byte)(s * (2N - 1)), (byte)(t * (N - 1))) (a NaN coordinate counts as 0) and the entry's index u * N*N*N*2 + v * N*N*2 +
+                                     s * N + t.  A non-zero entry is the sample's colour.  An empty (0) entry is filled first: the cell's CANONICAL ray, from
+                                     the centre of patch (u, v) towards the centre of patch (s, t) -- P(i, j) = (sin H cos W R, sin W R, cos H cos W R) with
+                                     H = ((i + 0.5) / (2N - 1) - 0.5) 2 pi, W = ((j + 0.5) / (N - 1) - 0.5) pi, tabulated on the host -- is traced through the
+                                     frame's root geometry (extra geometry + the model in trace_mode), shaded with SR_F_SHADING, and its colour (the
+                                     background on a miss; 0 is stored as 1) is stored.  Within a frame the colour of a cell depends on the cell alone, so the result
+                                     does not depend on which sample fills it or in which order (a later frame reads what an earlier one stored, shaded with
+                                     the earlier frame's pose and lights, as in the reference); no camera ray touches geometry.  The table lives in the scene for later
+                                     frames (sr_reset_light_field = a new Renderer; sr_get_light_field / sr_set_light_field = the reference's .cache file).
+                                     Everything before atan2 / asin is exact FP64 in the reference's operand order; the two angles are the device
+                                     library's, so a sample whose scaled coordinate lies within an ulp or so of an integer may fall into the neighbouring cell.
+                                     Works with SR_F_SHADING, the lights, sub_pixel_res, SR_F_FOCAL_BLUR, row ranges, extra geometry, all three trace modes,
+                                     host- and device-built BVH and frames of more than one row band.  The frame runs as one pipeline (as with SR_F_NO_SPLIT);
+                                     a multi-device scene renders it on devices[0] alone.  SR_ERR_UNSUPPORTED together with SR_F_SHADOWS (dynamic or static),
+                                     SR_F_AMBIENT_OCCLUSION, SR_F_PATH_TRACING, SR_F_VOXELS, max_bounces > 0, SR_F_SINGLE_KERNEL, strip_count > 0 and
+                                     sr_rccl_render.  Not covered: LightFieldStoresTriangles = true (LightFieldTriMethod) and quad-linear interpolation
+                                     (LightFieldColorMethod.Interpolate, hard-wired false in the reference).
+                                     Statistics: stats[0] = the camera samples, [1..3] = 0; sr_last_ray_stats [4] grows by one per filled cell, [5..7] by what
+                                     the canonical rays' walks count (not with SR_F_PRIMARY_STATS_ONLY)                                  */
     SR_F_PRIMARY_STATS_ONLY = 1u << 12 /* library option: with `stats`, count the primary rays only -- the four statistics of sr_render
                                      (NumRaysFired, NumGeometryTests, NumNodeVisits, NumLeafNodeVisits).  The shadow stage then runs
                                      its uncounted kernels (counting costs atomics per hit point: obj.3DS 1024^2 + shadows 2.3 -> 1.1 ms)
@@ -243,7 +269,7 @@ int  sr_create(int32_t device, sr_scene** out);
 int  sr_create_multi(const int32_t* devices, int32_t n, sr_scene** out);
 int32_t sr_device_count(const sr_scene*);
 /* How many parts (devices) rendered rows of the scene's last frame: 1 for a single-device scene and for a frame that devices[0]
- * rendered whole (static shadows, ambient occlusion, caller-made strips), otherwise the number of parts that owned at least one row of the range. */
+ * rendered whole (static shadows, ambient occlusion, light field, caller-made strips), otherwise the number of parts that owned at least one row of the range. */
 int32_t sr_last_frame_parts(const sr_scene*);
 void sr_destroy(sr_scene*);
 
@@ -307,6 +333,17 @@ int  sr_reset_shadow_cache(sr_scene*);
 int  sr_reset_ao_cache(sr_scene*);
 int  sr_get_ao_cache(sr_scene*, uint8_t out[128 * 128 * 128]);
 int  sr_set_ao_cache(sr_scene*, const uint8_t in[128 * 128 * 128]);
+/* rayTraceLightField's table (SR_F_LIGHT_FIELD): 4 N^4 uint32 entries, 0 = empty -- the array the reference persists to its .cache file
+ * (LightField4D.cs), so a host can save and load that file itself; `first` / `count` address a range of entries so that the 256 MiB of
+ * N = 64 can be streamed.  sr_set_light_field_res: N in 1..128 (default 64, the reference's regression value; 128 is 4 GiB), SR_ERR_INVALID_ARG
+ * outside; a change of N drops the table.  sr_reset_light_field: what a new Renderer starts with; sr_set_triangles / sr_load_3ds drop the
+ * table too.  The table is allocated on first use (the first SR_F_LIGHT_FIELD frame or sr_set_light_field); a scene that never rendered
+ * such a frame reads back zeros.  All of them work on a host-only scene, which keeps a host copy of what sr_set_light_field gave it. */
+int  sr_set_light_field_res(sr_scene*, int32_t n);
+int32_t sr_get_light_field_res(const sr_scene*);
+int  sr_reset_light_field(sr_scene*);
+int  sr_get_light_field(sr_scene*, uint32_t* out, uint64_t first, uint64_t count);
+int  sr_set_light_field(sr_scene*, const uint32_t* in, uint64_t first, uint64_t count);
 /* Same, but `d_pixels` is DEVICE memory on the scene's device (e.g. a torch tensor's data_ptr) and the
  * work is enqueued on `hip_stream` (a hipStream_t; NULL = the null stream) without host sync. */
 /* Ordering: the work is enqueued behind everything already on `hip_stream` and `hip_stream` continues only after it; a

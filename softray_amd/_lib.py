@@ -24,6 +24,7 @@ F_LITERAL_SECONDARY = 1 << 11
 F_PRIMARY_STATS_ONLY = 1 << 12
 F_AMBIENT_OCCLUSION = 1 << 13
 F_AO_UNCACHED = 1 << 14
+F_LIGHT_FIELD = 1 << 15
 AO_RES = 128
 MODE_REF_TREE, MODE_BRUTE, MODE_BVH = 0, 1, 2
 TARGET_ROOT = 0x100
@@ -42,6 +43,7 @@ SYMBOLS = [
     "sr_debug_set", "sr_bvh_stats", "sr_bvh_digest", "sr_wide_tree_stats", "sr_create_multi", "sr_device_count", "sr_last_frame_parts", "sr_shade_points",
     "sr_trace_rays_device", "sr_rccl_unique_id", "sr_rccl_init", "sr_rccl_render", "sr_rccl_gather", "sr_set_gather",
     "sr_net_random_doubles", "sr_build_voxels", "sr_get_voxels", "sr_reset_ao_cache", "sr_get_ao_cache", "sr_set_ao_cache",
+    "sr_set_light_field_res", "sr_get_light_field_res", "sr_reset_light_field", "sr_get_light_field", "sr_set_light_field",
 ]
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
@@ -159,6 +161,11 @@ def lib():
     L.sr_reset_ao_cache.restype = i32; L.sr_reset_ao_cache.argtypes = [vp]
     L.sr_get_ao_cache.restype = i32; L.sr_get_ao_cache.argtypes = [vp, vp]
     L.sr_set_ao_cache.restype = i32; L.sr_set_ao_cache.argtypes = [vp, vp]
+    L.sr_set_light_field_res.restype = i32; L.sr_set_light_field_res.argtypes = [vp, i32]
+    L.sr_get_light_field_res.restype = i32; L.sr_get_light_field_res.argtypes = [vp]
+    L.sr_reset_light_field.restype = i32; L.sr_reset_light_field.argtypes = [vp]
+    L.sr_get_light_field.restype = i32; L.sr_get_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
+    L.sr_set_light_field.restype = i32; L.sr_set_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
     L.sr_net_random_doubles.restype = None; L.sr_net_random_doubles.argtypes = [i32, i64, i64, vp]
     L.sr_last_error.restype = C.c_char_p; L.sr_last_error.argtypes = []
     L.sr_abi_version.restype = i32; L.sr_abi_version.argtypes = []

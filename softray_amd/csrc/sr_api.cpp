@@ -125,6 +125,14 @@ struct sr_scene {
     std::vector<uint8_t> ao_cache_host;
     int32_t ao_table_seed = 0;           // random_seed of the frame being enqueued (read by PipelineLaunch::ao_table)
     int  ao_table_rc = SR_OK;            // why the frame's draw table was refused (PipelineLaunch::ao_table)
+    // rayTraceLightField (SR_F_LIGHT_FIELD): the 4 N^4 uint32 entries a Renderer's LightFieldColorMethod keeps for its life (allocated on first use),
+    // one claim bit per entry (all zero between frames) and the 2N x N patch centres of the canonical rays.  A host-only scene keeps the
+    // entries sr_set_light_field gave it on the host (empty vector: all zeros)
+    DBuf d_lf_cache, d_lf_claim, d_lf_points;
+    int32_t lf_res = 64;                 // lightFieldRes, Renderer.cs:93
+    int32_t lf_points_res = 0;           // the resolution d_lf_points was made for (0: none)
+    bool lf_cache_empty = true;          // the device cache (and the claim bits) must be zeroed before their next use
+    std::vector<uint32_t> lf_cache_host;
     // path tracing (SR_F_PATH_TRACING) and ambient occlusion: the InternalSample() ints of Random(pt_table_seed), 3 per sample of the largest row
     // block (300 per generator of the fullest one) a frame has asked for so far; made once per (seed, length) and kept for later frames
     DBuf d_pt_table;
@@ -164,6 +172,7 @@ struct sr_scene {
         DBuf hits, hits2, bounce_levels, bounce_nlev, bounce_prep, bounce_res, bounce_stack, samples, counters, fallback, fallback_state, fallback_rays, fallback_ovf, ray_sort, ray_sort_temp;
         DBuf pt_flags, pt_index, pt_totals, pt_carry;   // path tracing: hit flags, hit-index scan, row-block carries (sr_pipeline.hip k_pt_*)
         DBuf ao_escapes;                   // ambient occlusion: escaped probes, then the byte, per generator (sr_pipeline.hip k_ao_*)
+        DBuf lf_cells, lf_list;            // light field: cache index per sample, the cells the band fills (sr_pipeline.hip k_lf_*)
         DBuf accum;                        // escape counts per sample index of a chunked (> 128 samples) shadow stage; zero between frames
         DBuf tile_cost, tile_order;        // walk length per 8x8 tile of the last shaft launch / the next one's longest-first lists
         unsigned long long tile_order_tag = 0;   // the tile grid tile_order was made for (0: none)
@@ -173,7 +182,7 @@ struct sr_scene {
         bool used_last_frame = false;
         void release() {
             tile_cost.release(); tile_order.release(); tile_order_tag = 0;
-            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &ao_escapes, &pt_flags, &pt_index, &pt_totals, &pt_carry};
+            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &ao_escapes, &lf_cells, &lf_list, &pt_flags, &pt_index, &pt_totals, &pt_carry};
             for (DBuf* x : b) x->release();
             for (int r = 0; r < sr::kShaftRounds; ++r) { rlist[r].release(); rstate[r].release(); rcount[r].release(); rcand[r].release(); }
             if (stream) (void)hipStreamDestroy(stream);
@@ -219,6 +228,8 @@ const int kMaxShaftSamples = 1024;       // area-light samples the shaft path ta
 const long long kMaxPathTable = 256ll << 20;   // bytes of the path tracer's random table (include/softray.h SR_F_PATH_TRACING)
 const int kAoRes = 128;                  // staticShadowRes, the resolution Renderer hands AmbientOcclusionMethod (Renderer.cs:1635)
 const size_t kAoCells = (size_t)kAoRes * kAoRes * kAoRes;
+const int kMaxLightFieldRes = 128;       // 4 N^4 entries: 4 GiB at 128 (and the reference's coordinates are bytes: 2 N - 1 <= 255)
+size_t lf_entries(int n) { return (size_t)4 * n * n * n * n; }
 const int kMaxTreeDepth = 62;            // (depth + 2) stack levels x 256 lanes x 4 B = 64 KB of LDS per workgroup
 
 int use_device(sr_scene* s) {
@@ -355,6 +366,20 @@ int check_ambient_occlusion(const sr_frame* f) {
     return SR_OK;
 }
 
+// SR_F_LIGHT_FIELD: the colour light field replaces the camera rays' walk; the decorators that need a surface point per camera sample (or
+// whose caches the canonical rays would fill) are not composable with it in one sitting (include/softray.h)
+int check_light_field(const sr_frame* f) {
+    if (!(f->flags & SR_F_LIGHT_FIELD)) return SR_OK;
+    if (f->flags & SR_F_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "light field together with shadows (dynamic or static) is not supported (a cell stores a colour, not a surface point)");
+    if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "light field together with ambient occlusion is not supported (a cell stores a colour, not a surface point)");
+    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "light field together with path tracing is not supported (a cell stores a colour, not a surface point)");
+    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "light field together with voxel rendering is not supported");
+    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "light field together with mirror bounces (max_bounces > 0) is not supported");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "light field is not built into the one-kernel renderer (SR_F_SINGLE_KERNEL)");
+    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "light field with row strips: the cache lives on one device and is filled by the whole frame");
+    return SR_OK;
+}
+
 // SR_F_VOXELS: the decorators whose result on a voxel hit is the reference's rayFrac = 0 artefact (unpinned) and the one-kernel renderer
 int check_voxels(const sr_frame* f) {
     if (!(f->flags & SR_F_VOXELS)) return SR_OK;
@@ -384,7 +409,8 @@ int validate_frame(const sr_frame* f) {
     if ((long long)f->width * f->sub_pixel_res > (1ll << 24) || (long long)f->height > (1ll << 24)) return fail(SR_ERR_INVALID_ARG, "surface too large");
     if (f->max_bounces < 0 || f->max_bounces > 16 || !(f->reflectivity >= 0.0 && f->reflectivity <= 1.0))
         return fail(SR_ERR_INVALID_ARG, "max_bounces must be 0..16 and reflectivity 0..1");
-    int rc = check_ambient_occlusion(f);
+    int rc = check_light_field(f);
+    if (!rc) rc = check_ambient_occlusion(f);
     if (!rc) rc = check_voxels(f);
     return rc ? rc : check_path_tracing(f);
 }
@@ -717,7 +743,8 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     const bool wide = bvh_walks && s->b4_num > 0 && s->dbg[SR_DBG_BVH2_PACKETS] <= 0;
     bool rewrote = false;                                             // (frames enqueued earlier have been waited for: see pre_used above)
     // ---- which records can the frame's camera rays / shadow sample rays hit at all?  (k_facing_partition, sr_pipeline.hip) ----
-    const bool pkt_primary = f->trace_mode == SR_MODE_BVH && s->dbg[SR_DBG_PER_LANE_PRIMARY] <= 0 && !((f->flags & SR_F_FOCAL_BLUR) && f->sub_pixel_res > 1);
+    const bool lf = (f->flags & SR_F_LIGHT_FIELD) != 0;              // (no camera ray is walked: none of the packet walk's per-origin records is needed)
+    const bool pkt_primary = f->trace_mode == SR_MODE_BVH && s->dbg[SR_DBG_PER_LANE_PRIMARY] <= 0 && !((f->flags & SR_F_FOCAL_BLUR) && f->sub_pixel_res > 1) && !lf;
     const bool want_cam = wide && pkt_primary, want_light = wide && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT);
     if ((want_cam || want_light) && s->dbg[SR_DBG_KERNEL_SWITCH] != 71) {
         const auto same3 = [](const double* a, const double* b) { return a[0] == b[0] && a[1] == b[1] && a[2] == b[2]; };
@@ -886,6 +913,37 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             }
         }
     }
+    // ---- light field: the scene's cache (allocated on first use), its claim bits and the patch centres of this resolution ----
+    if (lf) {
+        const int N = s->lf_res;
+        const size_t entries = lf_entries(N), claim_bytes = (entries + 31) / 32 * 4;
+        if (!s->d_lf_cache.p || !s->d_lf_claim.p) s->lf_cache_empty = true;
+        SR_HIP(s->d_lf_cache.reserve(entries * 4));
+        SR_HIP(s->d_lf_claim.reserve(claim_bytes));
+        if (s->lf_cache_empty) {
+            SR_HIP(hipMemsetAsync(s->d_lf_cache.p, 0, entries * 4, stream));
+            SR_HIP(hipMemsetAsync(s->d_lf_claim.p, 0, claim_bytes, stream));
+            s->lf_cache_empty = false;
+        }
+        if (s->lf_points_res != N) {
+            // Coord4DToRay + Sphere.ConvertLine (LightField4D.cs:253-273, Sphere.cs:122-142) with the host's sin / cos: the device calls neither
+            std::vector<double> pts((size_t)2 * N * N * 3);
+            const double max_h = (double)(N * 2 - 1), max_w = (double)(N - 1), radius = 0.866, pi = 3.14159265358979323846;
+            for (int i = 0; i < 2 * N; ++i) {
+                const double h = (((double)i + 0.5) / max_h - 0.5) * pi * 2;
+                for (int j = 0; j < N; ++j) {
+                    const double w = (((double)j + 0.5) / max_w - 0.5) * pi;
+                    const double horiz = std::cos(w) * radius;
+                    double* p = &pts[((size_t)i * N + j) * 3];
+                    p[0] = std::sin(h) * horiz; p[1] = std::sin(w) * radius; p[2] = std::cos(h) * horiz;
+                }
+            }
+            if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still read the old table
+            s->lf_points_res = 0;
+            SR_HIP(s->d_lf_points.upload(pts));
+            s->lf_points_res = N;
+        }
+    }
     const bool path_walk = path && f->trace_mode == SR_MODE_BVH;
     // (path tracing never runs as two halves: the part's rows are one band when they fit the budget)
     const bool pt_reuse = pt_phase && band_rows >= fc.num_rows;
@@ -900,6 +958,10 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         B.used_last_frame = true;
         if (shadows || bounce_pipe || path || ao) SR_HIP(B.hits.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
         if (ao) SR_HIP(B.ao_escapes.reserve((size_t)band_samples * 4));
+        if (lf) {
+            SR_HIP(B.lf_cells.reserve((size_t)band_samples * 4));
+            SR_HIP(B.lf_list.reserve((size_t)band_samples * 4));
+        }
         if (path || ao) {
             SR_HIP(B.hits2.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
             SR_HIP(B.pt_flags.reserve((size_t)band_samples));
@@ -991,6 +1053,13 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.ao_cache = (ao && !ao_uncached) ? (uint8_t*)s->d_ao_cache.p : nullptr;
         P.ao_claim = (ao && !ao_uncached) ? (unsigned long long*)s->d_ao_claim.p : nullptr;
         P.ao_escapes = ao ? (uint32_t*)B.ao_escapes.p : nullptr;
+        P.lf_cache = lf ? (uint32_t*)s->d_lf_cache.p : nullptr;
+        P.lf_claim = lf ? (uint32_t*)s->d_lf_claim.p : nullptr;
+        P.lf_points = lf ? (const double*)s->d_lf_points.p : nullptr;
+        P.lf_res = lf ? s->lf_res : 0;
+        P.lf_entries = lf ? (uint32_t)lf_entries(s->lf_res) : 0u;
+        P.lf_cells = lf ? (uint32_t*)B.lf_cells.p : nullptr;
+        P.lf_list = lf ? (uint32_t*)B.lf_list.p : nullptr;
         s->ao_table_seed = f->random_seed;
         s->ao_table_rc = SR_OK;
         P.ao_table = !ao ? nullptr : [](void* user, unsigned long long generators) -> const int32_t* {
@@ -1145,7 +1214,7 @@ hipError_t copy_runs(const std::vector<StripRun>& runs, int n, int width, const 
 
 // frames that cannot be split (one global fill order) are rendered whole by the first part
 bool multi_splittable(const sr_frame* f) {
-    return !((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) && !(f->flags & SR_F_AMBIENT_OCCLUSION) && f->strip_count <= 0;
+    return !((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) && !(f->flags & (SR_F_AMBIENT_OCCLUSION | SR_F_LIGHT_FIELD)) && f->strip_count <= 0;
 }
 
 // a part of a multi-device scene takes the first part's model by reference: counts, box and flags here, the arrays stay with `src`
@@ -1159,6 +1228,7 @@ void share_host_model(sr_scene* d, const sr_scene* src) {
     d->root = src->root;
     d->shadow_cache_empty = true;
     d->ao_cache_empty = true; d->ao_cache_host.clear();
+    d->lf_cache_empty = true; d->lf_cache_host.clear();
     d->vox_valid = false;
     d->ref = sr::RefTree(); d->bvh = sr::Bvh(); d->bvh_on_device = false;
     d->tris_dirty = d->ref_dirty = d->bvh_dirty = true;
@@ -1256,7 +1326,7 @@ void sr_destroy(sr_scene* s) {
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
-                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
+                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
                         &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
@@ -1290,6 +1360,7 @@ int sr_set_triangles(sr_scene* s, const double* v9, const uint32_t* argb, int64_
     if (n > 0x7fffff00) return fail(SR_ERR_INVALID_ARG, "too many triangles");
     s->shadow_cache_empty = true;                         // new model: what a new ShadowMethod starts with
     s->ao_cache_empty = true; s->ao_cache_host.clear();   // ... and a new AmbientOcclusion
+    s->lf_cache_empty = true; s->lf_cache_host.clear();   // ... and a new LightFieldColorMethod
     s->vox_valid = false;                                 // ... and a new VoxelGrid
     s->v9.assign(v9, v9 + 9 * n);
     s->argb.assign(argb, argb + n);
@@ -1578,6 +1649,81 @@ int sr_set_ao_cache(sr_scene* s, const uint8_t* in) {
     SR_HIP(s->d_ao_cache.reserve(kAoCells));
     SR_HIP(hipMemcpy(s->d_ao_cache.p, in, kAoCells, hipMemcpyHostToDevice));
     s->ao_cache_empty = false;
+    return SR_OK;
+}
+
+int sr_set_light_field_res(sr_scene* s, int32_t n) {
+    if (s && !s->parts.empty()) s = s->parts[0];                    // (a multi-device scene renders its light-field frames on the first part)
+    if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_light_field_res");
+    if (n < 1 || n > kMaxLightFieldRes) return fail(SR_ERR_INVALID_ARG, "light field resolution must be 1..128");
+    if (n == s->lf_res) return SR_OK;
+    if (s->device >= 0 && s->d_lf_cache.p) {                        // another resolution is another table: the old one goes (4 GiB at 128)
+        int rc = use_device(s);
+        if (rc) return rc;
+        if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));
+        s->d_lf_cache.release(); s->d_lf_claim.release();
+    }
+    s->lf_res = n;
+    s->lf_cache_empty = true;
+    s->lf_cache_host.clear();
+    return SR_OK;
+}
+
+int32_t sr_get_light_field_res(const sr_scene* s) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    return s ? s->lf_res : 0;
+}
+
+int sr_reset_light_field(sr_scene* s) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_reset_light_field");
+    s->lf_cache_empty = true;
+    s->lf_cache_host.clear();
+    return SR_OK;
+}
+
+int sr_get_light_field(sr_scene* s, uint32_t* out, uint64_t first, uint64_t count) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || (!out && count)) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_get_light_field");
+    const uint64_t entries = lf_entries(s->lf_res);
+    if (first > entries || count > entries - first) return fail(SR_ERR_INVALID_ARG, "sr_get_light_field: the range exceeds the 4 N^4 entries");
+    if (count == 0) return SR_OK;
+    if (s->device < 0) {
+        if (s->lf_cache_host.empty()) std::memset(out, 0, (size_t)count * 4);
+        else std::memcpy(out, s->lf_cache_host.data() + first, (size_t)count * 4);
+        return SR_OK;
+    }
+    if (s->lf_cache_empty || !s->d_lf_cache.p) { std::memset(out, 0, (size_t)count * 4); return SR_OK; }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still be filling cells
+    SR_HIP(hipMemcpy(out, (const uint32_t*)s->d_lf_cache.p + first, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_set_light_field(sr_scene* s, const uint32_t* in, uint64_t first, uint64_t count) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || (!in && count)) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_light_field");
+    const uint64_t entries = lf_entries(s->lf_res);
+    if (first > entries || count > entries - first) return fail(SR_ERR_INVALID_ARG, "sr_set_light_field: the range exceeds the 4 N^4 entries");
+    if (count == 0) return SR_OK;
+    if (s->device < 0) {
+        if (s->lf_cache_host.empty()) s->lf_cache_host.assign((size_t)entries, 0u);
+        std::memcpy(s->lf_cache_host.data() + first, in, (size_t)count * 4);
+        return SR_OK;
+    }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still read the old entries
+    if (!s->d_lf_cache.p || !s->d_lf_claim.p) s->lf_cache_empty = true;
+    SR_HIP(s->d_lf_cache.reserve((size_t)entries * 4));
+    SR_HIP(s->d_lf_claim.reserve((size_t)((entries + 31) / 32 * 4)));
+    if (s->lf_cache_empty) {                                             // the entries outside the range are those of a new Renderer
+        SR_HIP(hipMemset(s->d_lf_cache.p, 0, (size_t)entries * 4));
+        SR_HIP(hipMemset(s->d_lf_claim.p, 0, (size_t)((entries + 31) / 32 * 4)));
+        s->lf_cache_empty = false;
+    }
+    SR_HIP(hipMemcpy((uint32_t*)s->d_lf_cache.p + first, in, (size_t)count * 4, hipMemcpyHostToDevice));
     return SR_OK;
 }
 
@@ -2013,6 +2159,7 @@ int sr_rccl_render(sr_scene* s, const sr_frame* f, void* d_full, void* hip_strea
     if (f->strip_count > 0) return fail(SR_ERR_INVALID_ARG, "sr_rccl_render splits the frame itself: strip_count must be 0");
     if ((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) return fail(SR_ERR_UNSUPPORTED, "static shadows need the whole frame on one device");
     if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "ambient occlusion needs the whole frame on one device (sr_rccl_render splits it into strips)");
+    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "light field needs the whole frame on one device (sr_rccl_render splits it into strips)");
     if ((rc = use_device(s))) return rc;
     sr_frame fg = *f;
     fg.strip_rows = kMultiStripRows; fg.strip_count = s->rccl_world; fg.strip_index = s->rccl_rank;

@@ -41,7 +41,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_COUNT = 19 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_COUNT = 22 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -109,6 +109,15 @@ struct PipelineLaunch {
     // called once the number of generators is known (the stream has been waited for): the table of the seed's InternalSample() ints that
     // holds 300 draws for each of `generators` generators of one row block, or nullptr when the host refuses it
     const int32_t* (*ao_table)(void* user, unsigned long long generators);
+    // colour light field (SR_F_LIGHT_FIELD; all nullptr / 0 otherwise): the frame runs k_lf_lookup / k_lf_fill / k_lf_apply per row band instead of
+    // the primary walk; counters[0] is the length of the band's fill list
+    uint32_t*     lf_cache;     // device [lf_entries]: the scene's light field, 0 = empty entry
+    uint32_t*     lf_claim;     // device [(lf_entries + 31) / 32]: one bit per entry, set while a cell waits in a fill list; all zero between frames
+    const double* lf_points;    // device [2 lf_res][lf_res][3]: the patch centres P(i, j) of the canonical rays, made on the host
+    int32_t       lf_res;       // N
+    uint32_t      lf_entries;   // 4 N^4
+    uint32_t*     lf_cells;     // device [band samples]: cache index per sample, 0xFFFFFFFF = the sample's line misses the sphere
+    uint32_t*     lf_list;      // device [band samples]: the cells the band fills
     void*         static_hits;  // device HitRec[min(band samples, 128^3)]: generators of a static-shadow frame
     unsigned long long* static_claim; // device [128^3]: smallest order key that asked for an empty cell
     int32_t       static_concurrency; // rayTraceConcurrency of the frame

@@ -155,6 +155,9 @@ const char* kernel_name(int id) {
         case K_PT_EXCHANGE: return "pathtrace_exchange";      // ... its counts out, the wait for the other parts, all counts back (copies, no kernel)
         case K_AO: return "ambient_occlusion";                // the whole stage of one frame: claim, scan, select, probes, store, apply
         case K_AO_PROBE: return "k_ao_probe";
+        case K_LF_LOOKUP: return "k_lf_lookup";
+        case K_LF_FILL: return "k_lf_fill";
+        case K_LF_APPLY: return "k_lf_apply";
         case K_VOXEL_WALK: return "k_voxel_walk";
         case K_VOXELISE: return "voxelise";                   // count, scan, emit, sort, per-cell sums of one sr_build_voxels
         case K_SHAFT2: return "k_shaft_round2";

@@ -3756,6 +3756,154 @@ __global__ __launch_bounds__(256) void k_ao_apply(PtBand band, const uint8_t* __
 }
 
 // --------------------------------------------------------------------------------------------------
+// rayTraceLightField with LightFieldStoresTriangles = false (SR_F_LIGHT_FIELD; LightFieldColorMethod.cs:92-217, LightField4D.cs:175-206,
+// 253-273, 304-344, Sphere.cs:69-142): the colour of a camera sample is the colour of the CELL of a 4-D table its line falls into -- the
+// two points where the line pierces the sphere of radius 0.866 about the model's origin, each as (longitude, latitude) in 2N x N patches.
+// An empty cell is filled with the colour of its CANONICAL ray (patch centre to patch centre), traced through the root geometry and
+// shaded as the frame says, so within a frame the colour of a cell depends on the cell alone: which sample fills it, and in which order,
+// does not matter.
+// No camera ray touches geometry.  Per row band:
+//   k_lf_lookup   lane = camera sample: ray -> cell index (kLfMiss: the line misses the sphere) into a per-sample buffer; a sample whose
+//                 cell is empty claims it in a bitmap (atomicOr: one winner per cell and frame) and the winners of a wave append their
+//                 cells to the fill list with one atomicAdd
+//   k_lf_fill     lane = listed cell: canonical ray from the table of patch centres (made on the host: the device calls no sin / cos),
+//                 nearest hit in the frame's trace mode, shade, store (0 is stored as 1, LightField4D.cs:337-339), clear the claim bit
+//   k_lf_apply    every sample takes its cell's entry, or the background
+// Everything before atan2 / asin is + - * / sqrt in FP64 in the reference's operand order; the two angles are the device library's.
+// --------------------------------------------------------------------------------------------------
+constexpr double kLfRadius = 0.866;                      // LightField4D's bounding sphere (centre 0)
+constexpr double kLfEpsilon = 1e-10;                     // Sphere.IntersectLine
+constexpr double kLfPi = 3.14159265358979323846;         // Math.PI
+constexpr uint32_t kLfMiss = 0xffffffffu;
+
+// the camera ray of sample `si` of pixel (col, row), set up exactly as k_primary does it (Renderer.cs:1717-1790)
+__device__ __forceinline__ void lf_camera_ray(const FrameConst& fc, int col, int row, int si, D3& ss, D3& dw) {
+    const int n = fc.sub_pixel_res, width = fc.width, height = fc.height;
+    const D3 start = mk(fc.start_world[0], fc.start_world[1], fc.start_world[2]);
+    ss = start;
+    if (n == 1) {
+        const D3 dv = mk(-((double)col / width - 0.5), -((double)row / height - 0.5) * fc.aspect, fc.fov_depth);
+        dw = mul3x3(fc.it, dv);
+        return;
+    }
+    const int sx = si / n, sy = si - sx * n;                                 // subX outer, subY inner
+    const double fx = (double)sx / (n - 1) - 0.5;
+    const double fy = (double)sy / (n - 1) - 0.5;
+    if (fc.flags & 4u) {
+        const D3 dv = mk(-((double)col / width - 0.5), -((double)row / height - 0.5) * fc.aspect, fc.fov_depth);
+        const D3 focal = mul3x3(fc.it, dv) * fc.focal_depth + start;
+        const D3 sv = mk(fx / width * fc.focal_blur_strength, fy / height * fc.focal_blur_strength, -fc.position_z);
+        ss = mul3x3(fc.it, sv);
+        dw = focal - ss;
+    } else {
+        const D3 dv = mk(-((col + fx) / width - 0.5), -((row + fy) / height - 0.5) * fc.aspect, fc.fov_depth);
+        dw = mul3x3(fc.it, dv);
+    }
+}
+
+// (byte) of a scaled coordinate: in range by construction, a NaN (asin of a value beyond 1) -> 0
+__device__ __forceinline__ uint32_t lf_coord(double x) { return x == x ? ((uint32_t)(int32_t)x & 0xffu) : 0u; }
+
+// Sphere.IntersectLine + LightField4D.RayToCoord4D + the index of ReadCache / WriteCache; kLfMiss: the line misses the sphere (or the
+// index would lie outside the table, which an angle outside its mathematical range could cause: no access is made then)
+__device__ __forceinline__ uint32_t lf_cell(D3 start, D3 dir, int N, uint32_t entries) {
+    const D3 d = normalise(dir);
+    const double proj = dot(start, d);
+    const double term = proj * proj - dot(start, start) + kLfRadius * kLfRadius;
+    if (term < kLfEpsilon) return kLfMiss;
+    const double root = sqrt(term);
+    const D3 p1 = start + d * (-proj - root), p2 = start + d * (-proj + root);
+    const double u = atan2(p1.x, p1.z) / kLfPi * 0.5 + 0.5, v = asin(p1.y / kLfRadius) / kLfPi + 0.5;
+    const double s = atan2(p2.x, p2.z) / kLfPi * 0.5 + 0.5, t = asin(p2.y / kLfRadius) / kLfPi + 0.5;
+    const uint32_t n = (uint32_t)N;
+    const uint32_t cell = lf_coord(u * (N * 2 - 1)) * n * n * n * 2u + lf_coord(v * (N - 1)) * n * n * 2u + lf_coord(s * (N * 2 - 1)) * n + lf_coord(t * (N - 1));
+    return cell < entries ? cell : kLfMiss;
+}
+
+// grid: one lane per sample of the band, id = (band row * width + column) * n^2 + sub-sample (the order of the sample buffer)
+__global__ __launch_bounds__(256) void k_lf_lookup(FrameConst fc, const int32_t* __restrict__ row_map, int row_begin, uint32_t nsamples, int N, uint32_t entries,
+                                                   const uint32_t* __restrict__ cache, uint32_t* __restrict__ claim, uint32_t* __restrict__ cells,
+                                                   uint32_t* __restrict__ list, unsigned int* __restrict__ list_count, unsigned long long* stats) {
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+    const bool live = id < nsamples;
+    uint32_t cell = kLfMiss;
+    bool won = false;
+    if (live) {
+        const uint32_t n2 = (uint32_t)(fc.sub_pixel_res * fc.sub_pixel_res);
+        const uint32_t pix = id / n2, si = id - pix * n2;
+        const uint32_t brow = pix / (uint32_t)fc.width, col = pix - brow * (uint32_t)fc.width;
+        D3 ss, dw;
+        lf_camera_ray(fc, (int)col, row_map[row_begin + (int)brow], (int)si, ss, dw);
+        cell = lf_cell(ss, dw, N, entries);
+        cells[id] = cell;
+        if (cell != kLfMiss && cache[cell] == 0u) {
+            const uint32_t bit = 1u << (cell & 31u);
+            won = !(atomicOr(&claim[cell >> 5], bit) & bit);
+        }
+    }
+    const unsigned long long m = __ballot(won);
+    if (m) {
+        unsigned int base = 0;
+        const int leader = __ffsll((long long)m) - 1;
+        if ((int)(threadIdx.x & 63u) == leader) base = atomicAdd(list_count, (unsigned int)__popcll(m));
+        base = __shfl(base, leader, 64);
+        if (won) list[base + (unsigned int)__popcll(m & lanemask_lt())] = cell;
+    }
+    if (stats) {                                                             // NumRaysFired counts the camera samples; none of them walks anything
+        const unsigned long long lm = __ballot(live);
+        if ((threadIdx.x & 63u) == 0u) stat_add(&stats[0], (uint32_t)__popcll(lm));
+    }
+}
+
+// points: [2N][N][3] doubles, the patch centres P(i, j) (Coord4DToRay + Sphere.ConvertLine).  The index is injective for coordinates in
+// range, which lf_cell guarantees: it is taken apart again here.
+// (LDS: the per-lane traversal stacks of root_intersect, stack levels x 256 lanes x 4 bytes, as k_ao_probe)
+template <int MODE, bool EXTRA, bool STATS>
+__global__ __launch_bounds__(256) void k_lf_fill(DevScene sc, FrameConst fc, const double* __restrict__ points, int N, const uint32_t* __restrict__ list,
+                                                 const unsigned int* __restrict__ list_count, uint32_t* __restrict__ cache, uint32_t* __restrict__ claim,
+                                                 unsigned long long* stats) {
+    const int tid = threadIdx.x;
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    const unsigned int total = *list_count, stride = gridDim.x * 256u;
+    const uint32_t n = (uint32_t)N;
+    Ctr sec = {0, 0, 0, 0};
+    for (unsigned int r = blockIdx.x * 256u + tid; r < total; r += stride) {
+        const uint32_t cell = list[r];
+        const uint32_t t = cell % n, s = (cell / n) % (2u * n), v = (cell / (2u * n * n)) % n, u = cell / (2u * n * n * n);
+        const double* a = points + (size_t)(u * n + v) * 3, * b = points + (size_t)(s * n + t) * 3;
+        const D3 start = mk(a[0], a[1], a[2]);
+        const D3 d = mk(b[0] - a[0], b[1] - a[1], b[2] - a[2]);           // dir = P(s, t) - P(u, v), not normalised
+        uint32_t color = fc.background;
+        const double chk = (start.x + start.y + start.z) + (d.x + d.y + d.z);
+        if (chk == chk) {                                                    // (N = 1 has no latitude: its patch centres are NaN and nothing is hit)
+            Hit h;
+            sec.rays++;
+            if (root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, start, d, h, sec)) color = (fc.flags & 1u) ? shade(fc, h.pos, h.nrm, h.color) : h.color;
+        }
+        cache[cell] = color ? color : 1u;
+        atomicAnd(&claim[cell >> 5], ~(1u << (cell & 31u)));
+    }
+    if (STATS) {
+        uint32_t a = wave_sum(sec.rays), b = wave_sum(sec.geom), c2 = wave_sum(sec.nodes), d2 = wave_sum(sec.leaves);
+        if ((tid & 63) == 0) { stat_add(&stats[4], a); stat_add(&stats[5], b); stat_add(&stats[6], c2); stat_add(&stats[7], d2); }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lf_apply(FrameConst fc, const int32_t* __restrict__ row_map, int row_begin, uint32_t nsamples,
+                                                  const uint32_t* __restrict__ cells, const uint32_t* __restrict__ cache, uint32_t* __restrict__ samples) {
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= nsamples) return;
+    const uint32_t cell = cells[id];
+    const uint32_t color = cell == kLfMiss ? fc.background : cache[cell];
+    if (fc.sub_pixel_res == 1) {                                             // the sample buffer is the frame itself
+        const uint32_t brow = id / (uint32_t)fc.width, col = id - brow * (uint32_t)fc.width;
+        samples[(size_t)row_map[row_begin + (int)brow] * fc.width + col] = color;
+    } else {
+        samples[id] = color;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_cam_cones: per-frame pre-pass of the packet primary walk -- the CamCone record (sr_types.h) of every BVH triangle for
 // the frame's ray origin O: FP64 cross products of the FP64 vertices, rounded once to fp32.  64 B written + 72 B (gathered)
 // + 8 B read per triangle: 0.15 GB at 1 M triangles; re-run only when the origin or the tree changed.
@@ -4365,6 +4513,42 @@ static hipError_t launch_ao_t(const PipelineLaunch& L, int row_begin, int row_co
     return hipSuccess;
 }
 
+// the three light-field kernels of one row band (see k_lf_lookup); counters[0] is the length of the band's fill list.  Nothing waits
+// for the device: k_lf_fill reads the length itself
+template <int MODE, bool EXTRA>
+static hipError_t launch_lightfield_t(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples) {
+    const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
+    const uint32_t nsamples = (uint32_t)((long long)row_count * L.fc.width * n2);
+    const unsigned blocks = (nsamples + 255u) / 256u;
+    hipError_t e;
+    hipEvent_t e0, e1;
+    if ((e = hipMemsetAsync(L.counters, 0, sizeof(unsigned int), L.stream)) != hipSuccess) return e;
+    pipe_events(L, K_LF_LOOKUP, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_lf_lookup, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, L.lf_entries, (const uint32_t*)L.lf_cache, L.lf_claim,
+                       L.lf_cells, L.lf_list, L.counters, L.stats);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    pipe_events(L, K_LF_FILL, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    const unsigned fblocks = std::min(blocks, (unsigned)L.persistent_blocks);
+    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+    unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
+    const auto fill = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(fblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)L.counters, L.lf_cache,
+                           L.lf_claim, sec_stats);
+    };
+    if (sec_stats) fill(k_lf_fill<MODE, EXTRA, true>); else fill(k_lf_fill<MODE, EXTRA, false>);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    pipe_events(L, K_LF_APPLY, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_lf_apply, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, (const uint32_t*)L.lf_cells, (const uint32_t*)L.lf_cache, samples);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
 static hipError_t launch_resolve(const PipelineLaunch& L, int row_begin, int row_count) {
     hipError_t e;
     hipEvent_t e0, e1;
@@ -4410,6 +4594,13 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
         hipError_t e;
         if (pt_second_pass) {
             if ((e = launch_pathtrace_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
+            if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
+            if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);
+            continue;
+        }
+        if (L.fc.flags & kFlagLightField) {
+            // no camera ray touches geometry: the band is lookup, fill, apply (sr_api.cpp: never with shadows, AO, path tracing or mirror bounces)
+            if ((e = launch_lightfield_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
             if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
             if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);
             continue;

@@ -111,6 +111,7 @@ constexpr uint32_t kFlagAllSamplesEscape = 1u << 30;
 constexpr uint32_t kFlagPathTracing = 1u << 6;           // = SR_F_PATH_TRACING (include/softray.h)
 constexpr uint32_t kFlagAmbientOcclusion = 1u << 13;     // = SR_F_AMBIENT_OCCLUSION
 constexpr uint32_t kFlagAoUncached = 1u << 14;           // = SR_F_AO_UNCACHED
+constexpr uint32_t kFlagLightField = 1u << 15;           // = SR_F_LIGHT_FIELD
 
 // Per-frame constants, passed by value as a kernel argument (lives in SGPRs / the kernarg segment).
 struct FrameConst {

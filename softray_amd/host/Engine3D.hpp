@@ -212,6 +212,16 @@ public:
     Renderer& operator=(const Renderer&) = delete;
     void Dispose() { if (scene_) { sr_destroy(scene_); scene_ = nullptr; } }   // Renderer.cs:236
     void ResetAmbientOcclusionCache() { sr_check(sr_reset_ao_cache(scene_)); }   // what a new Renderer's AmbientOcclusionMethod starts with
+    // Renderer.cs:420-446: true (the default, as in the reference) = LightFieldTriMethod, which Render() refuses; false = the colour light
+    // field, passed on as SR_F_LIGHT_FIELD.  Setting another value disposes of both methods: the light field starts empty again
+    bool LightFieldStoresTriangles() const { return lightFieldHasTris_; }
+    void LightFieldStoresTriangles(bool value) {
+        if (value != lightFieldHasTris_) ResetLightField();
+        lightFieldHasTris_ = value;
+    }
+    void ResetLightField() { sr_check(sr_reset_light_field(scene_)); }           // what a new Renderer's LightFieldColorMethod starts with
+    int LightFieldResolution() const { return (int)sr_get_light_field_res(scene_); }   // lightFieldRes (Renderer.cs:93): 64
+    void LightFieldResolution(int n) { sr_check(sr_set_light_field_res(scene_, n)); }
     int gpuLastFrameParts() const { return scene_ ? sr_last_frame_parts(scene_) : 0; }   // parts (devices) that rendered rows of the last frame
 
     uint32_t BackgroundColor() const { return backgroundColor_; }
@@ -283,8 +293,15 @@ public:
     void Render() {                                        // Renderer.cs:701-778
         if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
         if (!PinModel()) return;                           // silently, :736-739
-        if (rayTraceLightField)
-            throw std::logic_error("rayTraceLightField is out of scope (a disk-backed cache the reference's own tests ignore)");
+        if (rayTraceLightField) {                          // SR_F_LIGHT_FIELD: the colour light field; what the library refuses, by name
+            if (lightFieldHasTris_)
+                throw std::logic_error("rayTraceLightField with LightFieldStoresTriangles = true (LightFieldTriMethod) is out of scope: set it to false (SR_F_LIGHT_FIELD)");
+            if (rayTraceShadows) throw std::logic_error("rayTraceLightField together with rayTraceShadows is out of scope (SR_F_LIGHT_FIELD)");
+            if (rayTraceAmbientOcclusion) throw std::logic_error("rayTraceLightField together with rayTraceAmbientOcclusion is out of scope (SR_F_LIGHT_FIELD)");
+            if (rayTracePathTracing) throw std::logic_error("rayTraceLightField together with rayTracePathTracing is out of scope (SR_F_LIGHT_FIELD)");
+            if (rayTraceVoxels) throw std::logic_error("rayTraceLightField together with rayTraceVoxels is out of scope (SR_F_LIGHT_FIELD)");
+            if (gpuMaxBounces > 0) throw std::logic_error("rayTraceLightField together with gpuMaxBounces is out of scope (SR_F_LIGHT_FIELD)");
+        }
         if (rayTraceAmbientOcclusion) {                    // SR_F_AMBIENT_OCCLUSION: the pairs the library refuses, by name
             if (rayTracePathTracing) throw std::logic_error("rayTraceAmbientOcclusion together with rayTracePathTracing is out of scope (SR_F_AMBIENT_OCCLUSION)");
             if (rayTraceVoxels) throw std::logic_error("rayTraceAmbientOcclusion together with rayTraceVoxels is out of scope (SR_F_AMBIENT_OCCLUSION)");
@@ -323,6 +340,7 @@ public:
                   (rayTraceAmbientOcclusion ? SR_F_AMBIENT_OCCLUSION : 0u) |                       // Renderer.cs:1631-1638; reads random_seed, concurrency
                   (rayTraceAmbientOcclusion && !ambientOcclusionEnableCache ? SR_F_AO_UNCACHED : 0u) |
                   (rayTraceVoxels ? SR_F_VOXELS : 0u) |                                            // Renderer.cs:1568-1588: the grid replaces tree and extra geometry
+                  (rayTraceLightField && !lightFieldHasTris_ ? SR_F_LIGHT_FIELD : 0u) |            // Renderer.cs:1640-1649: LightFieldColorMethod
                   (pointLighting ? SR_F_POINT_LIGHT : 0u) | (specularLighting ? SR_F_SPECULAR : 0u) |
                   SR_F_PRIMARY_STATS_ONLY;                 // Num* count primary rays (Renderer.cs:1916-1923)
         f.random_seed = rayTraceRandomSeed;
@@ -403,6 +421,7 @@ private:
 
     sr_scene* scene_ = nullptr;
     uint32_t backgroundColor_ = 0;
+    bool lightFieldHasTris_ = true;                        // Renderer.cs:446
     double fieldOfViewDepth_ = 0;
     int width_ = 1, height_ = 1;
     int32_t* pixels_ = nullptr;

@@ -430,7 +430,8 @@ class Renderer:
 
     def Render(self):
         """Renderer.cs:701-778.  (The C ABI has rayTraceAmbientOcclusion -- SR_F_AMBIENT_OCCLUSION, GpuScene.reset_ao_cache / get_ao_cache /
-        set_ao_cache -- and rayTraceVoxels; this mirror keeps refusing both switches, the C++ mirror passes them on.)"""
+        set_ao_cache --, rayTraceLightField -- SR_F_LIGHT_FIELD, GpuScene.light_field_res / reset_light_field / get_light_field / set_light_field --
+        and rayTraceVoxels; this mirror keeps refusing the three switches, the C++ mirror passes them on.)"""
         if not self.rayTrace:
             raise NotImplementedError("the scan-line rasteriser is out of scope of the MI355X hot path (SURVEY.md 2, row 21)")
         if not self._PinModel():

@@ -190,6 +190,33 @@ class GpuScene:
             raise ValueError("the ambient-occlusion cache is %d^3 bytes" % _lib.AO_RES)
         _check(_lib.lib().sr_set_ao_cache(self._h, _p(cache)))
 
+    # ---- rayTraceLightField (SR_F_LIGHT_FIELD frames) ----
+    @property
+    def light_field_res(self):
+        """N of the light field's 4 N^4 entries (default 64, the reference's lightFieldRes); setting another value drops the table."""
+        return int(_lib.lib().sr_get_light_field_res(self._h))
+
+    @light_field_res.setter
+    def light_field_res(self, n):
+        _check(_lib.lib().sr_set_light_field_res(self._h, int(n)))
+
+    def reset_light_field(self):
+        """Forget the light field: what a new Renderer starts with."""
+        _check(_lib.lib().sr_reset_light_field(self._h))
+
+    def get_light_field(self, first=0, count=None):
+        """Entries first .. first + count - 1 (default: all 4 N^4) as uint32, 0 = empty: the array the reference persists to its .cache file."""
+        total = 4 * self.light_field_res ** 4
+        if count is None:
+            count = total - first
+        out = np.zeros(int(count), dtype=np.uint32)
+        _check(_lib.lib().sr_get_light_field(self._h, _p(out), int(first), int(count)))
+        return out
+
+    def set_light_field(self, entries, first=0):
+        entries = np.ascontiguousarray(entries, dtype=np.uint32).reshape(-1)
+        _check(_lib.lib().sr_set_light_field(self._h, _p(entries), int(first), int(entries.size)))
+
     def ray_stats(self):
         """primary {rays, tests, nodes, leaves} + secondary {rays, tests, nodes, leaves} of the last render(stats=True)."""
         out = np.zeros(24, dtype=np.uint64)                           # SR_STATS_COUNT

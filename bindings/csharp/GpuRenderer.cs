@@ -88,6 +88,7 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_reset_light_field(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_get_light_field(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
+        [DllImport(Lib)] public static extern int sr_bake_light_field(IntPtr scene, ref SrFrame frame, ulong first, ulong count, out ulong filled);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -278,11 +279,11 @@ namespace Engine3D.Hip
             Native.Check(Native.sr_set_extra_geometry(scene, prims, n));
         }
 
-        /// The host half of RaytraceGeometry (Renderer.cs:1510-1528, 1652-1653): copy public fields into sr_frame.
-        public void Render(int width, int height, int[] pixels, Instance instance, Matrix transform, Matrix inverseTransform,
-                           uint backgroundColor, uint flags, int mode, int startRow, int endRow, int subPixelRes, int randomSeed,
-                           double fieldOfViewDepth, double focalDepth, double focalBlurStrength, double ambient, double shininess,
-                           Vector lightDirView, Vector lightPosView, ulong[] stats4, int concurrency = 4)
+        /// The frame of a call (Renderer.cs:1510-1528): the arguments copied into the reused sr_frame, the area-light offsets of the seed
+        void FillFrame(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform,
+                       uint backgroundColor, uint flags, int mode, int startRow, int endRow, int subPixelRes, int randomSeed,
+                       double fieldOfViewDepth, double focalDepth, double focalBlurStrength, double ambient, double shininess,
+                       Vector lightDirView, Vector lightPosView, int concurrency)
         {
             if (areaLightOffsets == null || offsetsSeed != randomSeed)
             {
@@ -313,6 +314,37 @@ namespace Engine3D.Hip
             frame.light_pos_view[0] = lightPosView.x; frame.light_pos_view[1] = lightPosView.y; frame.light_pos_view[2] = lightPosView.z;
             frame.area_light_offsets = offsetsPin.AddrOfPinnedObject();
             for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) { frame.transform[4 * r + c] = transform[r, c]; frame.inv_transform[4 * r + c] = inverseTransform[r, c]; }
+        }
+
+        /// Pre-compute the colour light field (sr_bake_light_field): every entry of first .. first + count - 1 that is still empty gets the colour
+        /// of its cell's canonical ray, traced and shaded with the frame these arguments describe (the same as Render's; `flags` must hold
+        /// F_LIGHT_FIELD; the surface size, rows and sub-pixel samples are validated and otherwise unused).  Frames rendered afterwards look
+        /// their colours up and trace nothing.  Blocks; returns the number of entries written.  count = ulong.MaxValue: to the end of the table.
+        public ulong BakeLightField(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform,
+                                    uint backgroundColor, uint flags, int mode, int subPixelRes, int randomSeed,
+                                    double fieldOfViewDepth, double focalDepth, double focalBlurStrength, double ambient, double shininess,
+                                    Vector lightDirView, Vector lightPosView, ulong first = 0, ulong count = ulong.MaxValue)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, backgroundColor, flags, mode, 0, height - 1, subPixelRes, randomSeed,
+                      fieldOfViewDepth, focalDepth, focalBlurStrength, ambient, shininess, lightDirView, lightPosView, 4);
+            if (count == ulong.MaxValue)
+            {
+                ulong n = (ulong)LightFieldResolution, total = 4 * n * n * n * n;
+                count = first <= total ? total - first : 1;          // (beyond the table: the library says so)
+            }
+            ulong filled;
+            Native.Check(Native.sr_bake_light_field(scene, ref frame, first, count, out filled));
+            return filled;
+        }
+
+        /// The host half of RaytraceGeometry (Renderer.cs:1510-1528, 1652-1653): copy public fields into sr_frame.
+        public void Render(int width, int height, int[] pixels, Instance instance, Matrix transform, Matrix inverseTransform,
+                           uint backgroundColor, uint flags, int mode, int startRow, int endRow, int subPixelRes, int randomSeed,
+                           double fieldOfViewDepth, double focalDepth, double focalBlurStrength, double ambient, double shininess,
+                           Vector lightDirView, Vector lightPosView, ulong[] stats4, int concurrency = 4)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, backgroundColor, flags, mode, startRow, endRow, subPixelRes, randomSeed,
+                      fieldOfViewDepth, focalDepth, focalBlurStrength, ambient, shininess, lightDirView, lightPosView, concurrency);
             // blocking; `pixels` is only touched during the call (the library pins it for the call and copies row bands into it while
             // later bands still render).  The literal tree (and brute force) produce the reference's counters; the own BVH does not:
             // stats4 then gets the rays fired only and CountersAvailable turns false

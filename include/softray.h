@@ -344,6 +344,18 @@ int32_t sr_get_light_field_res(const sr_scene*);
 int  sr_reset_light_field(sr_scene*);
 int  sr_get_light_field(sr_scene*, uint32_t* out, uint64_t first, uint64_t count);
 int  sr_set_light_field(sr_scene*, const uint32_t* in, uint64_t first, uint64_t count);
+/* Pre-compute the table: every entry of [first, first + count) that is 0 gets exactly what a light-field frame would store for its cell -- the
+ * colour of the canonical ray from patch centre P(u, v) towards P(s, t), traced through `frame`'s root geometry (extra geometry + the model in
+ * frame->trace_mode), shaded with the frame's transform and lights when SR_F_SHADING is set, background_argb | 0xFF000000 on a miss (and for the
+ * NaN rays of N = 1, which are not traced), 0 stored as 1.  Non-zero entries stay as they are; *filled (may be NULL) = entries written.  A complete
+ * table turns every later light-field frame into look-ups that never touch geometry.  `frame` must carry SR_F_LIGHT_FIELD (SR_ERR_INVALID_ARG
+ * otherwise) and passes sr_render's validation (the same SR_ERR_UNSUPPORTED refusals); its camera fields (surface, rows, sub-pixel samples, focal
+ * blur) are validated and otherwise unused.  A range beyond the 4 N^4 entries: SR_ERR_INVALID_ARG; count == 0: SR_OK.  Arguments and frame are
+ * checked before the device is looked at; a host-only scene then returns SR_ERR_NO_DEVICE.  The call blocks like sr_render, orders itself after a
+ * frame in flight, and allocates / zeroes the table as a frame does.  The range is cut into kernel launches of at most 2^24 cells, with no host
+ * synchronisation in between.  A multi-device scene bakes on its first device, where the table lives.  sr_last_ray_stats afterwards: [0..3] = 0,
+ * [4] = canonical rays traced (one per entry written, none for NaN rays), [5..7] = what their walks counted (0 with SR_F_PRIMARY_STATS_ONLY). */
+int  sr_bake_light_field(sr_scene*, const sr_frame* frame, uint64_t first, uint64_t count, uint64_t* filled /* or NULL */);
 /* Same, but `d_pixels` is DEVICE memory on the scene's device (e.g. a torch tensor's data_ptr) and the
  * work is enqueued on `hip_stream` (a hipStream_t; NULL = the null stream) without host sync. */
 /* Ordering: the work is enqueued behind everything already on `hip_stream` and `hip_stream` continues only after it; a
@@ -491,7 +503,9 @@ enum {
                                     partition (the packet walks see every record of a leaf); 7 counts umbra decisions of the private shaft walk;
                                     32 a mirror-bounce level as ONE kernel (k_bounce) instead of prepare / walk / finish; 33 the second rays of a path-traced SR_MODE_BVH frame with
                                     private per-lane walks (k_pt_finish) instead of the mirror extension's prepare / walk route; 34 the ambient-occlusion probes of a
-                                    SR_MODE_BVH frame as nearest-hit walks instead of any-hit walks with the limit 2.0; 100 + T: the walk kernel
+                                    SR_MODE_BVH frame as nearest-hit walks instead of any-hit walks with the limit 2.0; 35 sr_bake_light_field on a
+                                    SR_MODE_BVH frame with one packet walk per wave of 64 same-origin canonical rays instead of private per-lane
+                                    walks (same table; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid
                                     too (its loop form spills registers: opt-in); 84 the persistent shaft walk hands its tiles out in natural order

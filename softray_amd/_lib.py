@@ -44,6 +44,7 @@ SYMBOLS = [
     "sr_trace_rays_device", "sr_rccl_unique_id", "sr_rccl_init", "sr_rccl_render", "sr_rccl_gather", "sr_set_gather",
     "sr_net_random_doubles", "sr_build_voxels", "sr_get_voxels", "sr_reset_ao_cache", "sr_get_ao_cache", "sr_set_ao_cache",
     "sr_set_light_field_res", "sr_get_light_field_res", "sr_reset_light_field", "sr_get_light_field", "sr_set_light_field",
+    "sr_bake_light_field",
 ]
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
@@ -166,6 +167,7 @@ def lib():
     L.sr_reset_light_field.restype = i32; L.sr_reset_light_field.argtypes = [vp]
     L.sr_get_light_field.restype = i32; L.sr_get_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
     L.sr_set_light_field.restype = i32; L.sr_set_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
+    L.sr_bake_light_field.restype = i32; L.sr_bake_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp]
     L.sr_net_random_doubles.restype = None; L.sr_net_random_doubles.argtypes = [i32, i64, i64, vp]
     L.sr_last_error.restype = C.c_char_p; L.sr_last_error.argtypes = []
     L.sr_abi_version.restype = i32; L.sr_abi_version.argtypes = []

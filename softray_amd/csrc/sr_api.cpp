@@ -578,6 +578,40 @@ int ensure_draw_table(sr_scene* s, int32_t seed, size_t triples) {
     return SR_OK;
 }
 
+// the scene's light field on the device: the table and its claim bits (allocated on first use, zeroed on `stream` when the scene starts
+// as a new Renderer) and the patch centres of the current resolution.  What a light-field frame and sr_bake_light_field begin with
+int ensure_light_field(sr_scene* s, hipStream_t stream) {
+    const int N = s->lf_res;
+    const size_t entries = lf_entries(N), claim_bytes = (entries + 31) / 32 * 4;
+    if (!s->d_lf_cache.p || !s->d_lf_claim.p) s->lf_cache_empty = true;
+    SR_HIP(s->d_lf_cache.reserve(entries * 4));
+    SR_HIP(s->d_lf_claim.reserve(claim_bytes));
+    if (s->lf_cache_empty) {
+        SR_HIP(hipMemsetAsync(s->d_lf_cache.p, 0, entries * 4, stream));
+        SR_HIP(hipMemsetAsync(s->d_lf_claim.p, 0, claim_bytes, stream));
+        s->lf_cache_empty = false;
+    }
+    if (s->lf_points_res != N) {
+        // Coord4DToRay + Sphere.ConvertLine (LightField4D.cs:253-273, Sphere.cs:122-142) with the host's sin / cos: the device calls neither
+        std::vector<double> pts((size_t)2 * N * N * 3);
+        const double max_h = (double)(N * 2 - 1), max_w = (double)(N - 1), radius = 0.866, pi = 3.14159265358979323846;
+        for (int i = 0; i < 2 * N; ++i) {
+            const double h = (((double)i + 0.5) / max_h - 0.5) * pi * 2;
+            for (int j = 0; j < N; ++j) {
+                const double w = (((double)j + 0.5) / max_w - 0.5) * pi;
+                const double horiz = std::cos(w) * radius;
+                double* p = &pts[((size_t)i * N + j) * 3];
+                p[0] = std::sin(h) * horiz; p[1] = std::sin(w) * radius; p[2] = std::cos(h) * horiz;
+            }
+        }
+        if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still read the old table
+        s->lf_points_res = 0;
+        SR_HIP(s->d_lf_points.upload(pts));
+        s->lf_points_res = N;
+    }
+    return SR_OK;
+}
+
 // pt_phase: 0, or the phase (1, 2) of a part of a path-traced frame that multi_render has split (sr_device.h PipelineLaunch::pt_phase)
 int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0) {
     for (uint32_t& c : s->dbg_frame) c = 0;
@@ -914,36 +948,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         }
     }
     // ---- light field: the scene's cache (allocated on first use), its claim bits and the patch centres of this resolution ----
-    if (lf) {
-        const int N = s->lf_res;
-        const size_t entries = lf_entries(N), claim_bytes = (entries + 31) / 32 * 4;
-        if (!s->d_lf_cache.p || !s->d_lf_claim.p) s->lf_cache_empty = true;
-        SR_HIP(s->d_lf_cache.reserve(entries * 4));
-        SR_HIP(s->d_lf_claim.reserve(claim_bytes));
-        if (s->lf_cache_empty) {
-            SR_HIP(hipMemsetAsync(s->d_lf_cache.p, 0, entries * 4, stream));
-            SR_HIP(hipMemsetAsync(s->d_lf_claim.p, 0, claim_bytes, stream));
-            s->lf_cache_empty = false;
-        }
-        if (s->lf_points_res != N) {
-            // Coord4DToRay + Sphere.ConvertLine (LightField4D.cs:253-273, Sphere.cs:122-142) with the host's sin / cos: the device calls neither
-            std::vector<double> pts((size_t)2 * N * N * 3);
-            const double max_h = (double)(N * 2 - 1), max_w = (double)(N - 1), radius = 0.866, pi = 3.14159265358979323846;
-            for (int i = 0; i < 2 * N; ++i) {
-                const double h = (((double)i + 0.5) / max_h - 0.5) * pi * 2;
-                for (int j = 0; j < N; ++j) {
-                    const double w = (((double)j + 0.5) / max_w - 0.5) * pi;
-                    const double horiz = std::cos(w) * radius;
-                    double* p = &pts[((size_t)i * N + j) * 3];
-                    p[0] = std::sin(h) * horiz; p[1] = std::sin(w) * radius; p[2] = std::cos(h) * horiz;
-                }
-            }
-            if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still read the old table
-            s->lf_points_res = 0;
-            SR_HIP(s->d_lf_points.upload(pts));
-            s->lf_points_res = N;
-        }
-    }
+    if (lf && (rc = ensure_light_field(s, stream))) return rc;
     const bool path_walk = path && f->trace_mode == SR_MODE_BVH;
     // (path tracing never runs as two halves: the part's rows are one band when they fit the budget)
     const bool pt_reuse = pt_phase && band_rows >= fc.num_rows;
@@ -1724,6 +1729,75 @@ int sr_set_light_field(sr_scene* s, const uint32_t* in, uint64_t first, uint64_t
         s->lf_cache_empty = false;
     }
     SR_HIP(hipMemcpy((uint32_t*)s->d_lf_cache.p + first, in, (size_t)count * 4, hipMemcpyHostToDevice));
+    return SR_OK;
+}
+
+// cells per k_lf_bake launch: 2^24 (2048 origin patches at N = 64, four launches for that table).  Measured on 1 M triangles: 38 ms per
+// launch, and the launches' event times add up to the call's time within 0.1 ms -- the cut costs nothing measurable
+const uint64_t kBakeLaunchCells = 1ull << 24;
+
+int sr_bake_light_field(sr_scene* m, const sr_frame* f, uint64_t first, uint64_t count, uint64_t* filled) {
+    sr_scene* s = (m && !m->parts.empty()) ? m->parts[0] : m;       // (a multi-device scene keeps its light field on the first part)
+    if (!s || !f) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_bake_light_field");
+    if (!(f->flags & SR_F_LIGHT_FIELD)) return fail(SR_ERR_INVALID_ARG, "sr_bake_light_field: the frame must carry SR_F_LIGHT_FIELD");
+    const uint64_t entries = lf_entries(s->lf_res);
+    if (first > entries || count > entries - first) return fail(SR_ERR_INVALID_ARG, "sr_bake_light_field: the range exceeds the 4 N^4 entries");
+    int rc = validate_frame(f);
+    if (rc) return rc;
+    if ((rc = check_frame_mode(s, f))) return rc;
+    if ((rc = use_device(s))) return rc;
+    if (filled) *filled = 0;
+    for (uint64_t& v : s->last_stats) v = 0;
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    if (count == 0) return SR_OK;
+    if ((rc = ensure_io_streams(s))) return rc;
+    hipStream_t stream = s->io_stream;
+    sr::FrameConst fc;
+    if ((rc = prepare_frame(s, f, fc))) return rc;
+    if ((rc = sync_geometry(s, (uint32_t)f->trace_mode))) return rc;
+    // [0 .. SR_STATS_COUNT) the ray statistics, [SR_STATS_COUNT] the entries written
+    uint64_t back[SR_STATS_COUNT + 1];
+    SR_HIP(s->d_stats.reserve(sizeof(back)));
+    {
+        // ordered like a frame: after whatever frame is in flight (it may be filling cells), and the next frame after the bake
+        if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
+        struct MarkPreUsed {
+            sr_scene* s; hipStream_t st;
+            ~MarkPreUsed() {
+                if (!s->pre_used && hipEventCreateWithFlags(&s->pre_used, hipEventDisableTiming) != hipSuccess) return;
+                if (hipEventRecord(s->pre_used, st) == hipSuccess) s->pre_used_set = true;
+            }
+        } mark_pre_used{s, stream};
+        SR_HIP(hipMemsetAsync(s->d_stats.p, 0, sizeof(back), stream));
+        if ((rc = ensure_light_field(s, stream))) return rc;
+        sr::BakeLaunch B{};
+        B.sc = dev_scene(s);
+        B.fc = fc;
+        B.mode = f->trace_mode;
+        B.points = (const double*)s->d_lf_points.p;
+        B.res = s->lf_res;
+        B.cache = (uint32_t*)s->d_lf_cache.p;
+        B.first = first; B.count = count;
+        B.launch_cells = kBakeLaunchCells;
+        B.packet = s->dbg[SR_DBG_KERNEL_SWITCH] == 35;              // (hook 35: the measured-and-rejected packet walk, same table)
+        B.walk_stats = !(f->flags & SR_F_PRIMARY_STATS_ONLY);
+        B.stats = (unsigned long long*)s->d_stats.p;
+        B.filled = (unsigned long long*)s->d_stats.p + SR_STATS_COUNT;
+        B.stream = stream;
+        B.user = s;
+        B.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
+            hipEvent_t x = nullptr, y = nullptr;
+            if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
+            *a = x; *b = y;
+        };
+        const hipError_t e = sr::launch_lf_bake(B);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(stream); SR_HIP(e); }
+    }
+    SR_HIP(hipMemcpyAsync(back, s->d_stats.p, sizeof(back), hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
+    std::memcpy(s->last_stats, back, sizeof(s->last_stats));
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    if (filled) *filled = back[SR_STATS_COUNT];
     return SR_OK;
 }
 

@@ -41,7 +41,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_COUNT = 22 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_COUNT = 23 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -155,6 +155,26 @@ struct PipelineLaunch {
     void*       user;
 };
 hipError_t launch_pipeline(const PipelineLaunch& L);
+
+// sr_bake_light_field: the dense fill of entries [first, first + count) of the light field (k_lf_bake, sr_pipeline.hip)
+struct BakeLaunch {
+    DevScene    sc;
+    FrameConst  fc;
+    int32_t     mode;
+    const double* points;       // device [2 res][res][3]: the patch centres
+    int32_t     res;            // N
+    uint32_t*   cache;          // device [4 N^4]: the scene's light field
+    uint64_t    first, count;   // the range, inside the table
+    uint64_t    launch_cells;   // cells per launch (rounded down to whole origin patches, at least one)
+    bool        packet;         // SR_MODE_BVH with one packet walk per wave instead of private per-lane walks (cross-check, A/B measurement)
+    bool        walk_stats;     // count what the walks do in stats[5..7] too
+    unsigned long long* stats;  // device [8] or nullptr: [4] += canonical rays traced, [5..7] += the walks' counters
+    unsigned long long* filled; // device: += entries written
+    hipStream_t stream;
+    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);   // optional per-launch timing
+    void*       user;
+};
+hipError_t launch_lf_bake(const BakeLaunch& L);
 // per-frame pre-pass: a copy of the four-wide nodes with every node's children sorted by the distance of their box centres from
 // `point` (model space), nearest first (camera origin) or farthest first (light: nearest to the surface points first)
 // swap_mask (bit a): exchange lo and hi on axis a in the copy (the rays of the frame travel towards smaller coordinates there)

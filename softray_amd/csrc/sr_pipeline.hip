@@ -3904,6 +3904,67 @@ __global__ __launch_bounds__(256) void k_lf_apply(FrameConst fc, const int32_t* 
 }
 
 // --------------------------------------------------------------------------------------------------
+// k_lf_bake (sr_bake_light_field): the DENSE fill of the table -- every entry of [lo, hi) that is still 0 gets what k_lf_fill would store
+// for it.  Work item = one wave = one origin patch (u, v) x an 8x8 tile of target patches (s0 .. s0 + 7, t0 .. t0 + 7) clipped to 2N x N;
+// items are numbered origin-major, t tiles fastest.  Lane l holds the target (s0 + (l >> 3), t0 + (l & 7)): t is the fastest index of the
+// table, so a tile stores eight runs of eight consecutive entries.  The 64 canonical rays of a wave start at the same point P(u, v) (one
+// scalar-addressed load) and aim at neighbouring patches.
+// !PKT (every mode; the default): the private per-lane walk of k_lf_fill, root_intersect<MODE, false, EXTRA>, in this tile order.
+// PKT (SR_MODE_BVH under hook 35): one walk per wave, bvh_packet_nearest without a camera-cone filter (the records are per origin) but with
+// the private walks' TriSlab pre-test -- per lane the nearest hit with the lowest-index tie-break, i.e. the same table.  It lost the
+// measurement (a tile of 8x8 patches spans 22.5 degrees each way at N = 64, the wave visits the union of 64 divergent walks).
+// No claim bits: a bake gives every cell exactly one lane, and the host orders it against frames.  One atomic per wave and counter.
+// (LDS: as k_lf_fill -- the per-lane stacks; the packet walk's per-wave node stack uses the first levels x 4 words of it)
+// --------------------------------------------------------------------------------------------------
+template <int MODE, bool EXTRA, bool STATS, bool PKT>
+__global__ __launch_bounds__(256) void k_lf_bake(DevScene sc, FrameConst fc, const double* __restrict__ points, int N, uint32_t item_first, uint32_t item_count,
+                                                 uint32_t lo, uint32_t hi, uint32_t* __restrict__ cache, unsigned long long* stats, unsigned long long* filled,
+                                                 int levels) {
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const uint32_t local = blockIdx.x * 4u + (uint32_t)wave;
+    if (local >= item_count) return;                                         // (whole waves: nothing below synchronises the workgroup)
+    const uint32_t item = item_first + local;
+    const uint32_t n = (uint32_t)N, tiles_t = (n + 7u) / 8u, tiles = ((2u * n + 7u) / 8u) * tiles_t;
+    const uint32_t origin = item / tiles, tile = item - origin * tiles;       // origin = u * N + v: the row of `points`
+    const uint32_t s = (tile / tiles_t) * 8u + ((uint32_t)lane >> 3), t = (tile % tiles_t) * 8u + ((uint32_t)lane & 7u);
+    const bool inside = s < 2u * n && t < n;
+    const uint32_t cell = origin * (2u * n * n) + s * n + t;                 // < 4 N^4 <= 2^30 for a target inside the table
+    const bool active = inside && cell >= lo && cell < hi && cache[cell] == 0u;
+    const unsigned long long am = __ballot(active);
+    if (am == 0ull) return;
+    const double* a = points + (size_t)origin * 3, * b = active ? points + (size_t)(s * n + t) * 3 : a;
+    const D3 start = mk(a[0], a[1], a[2]);
+    const D3 d = mk(b[0] - a[0], b[1] - a[1], b[2] - a[2]);               // dir = P(s, t) - P(u, v), not normalised
+    const double chk = (start.x + start.y + start.z) + (d.x + d.y + d.z);
+    const bool traced = active && chk == chk;                                // (N = 1: the patch centres are NaN and nothing is traced)
+    Ctr sec = {0, 0, 0, 0};
+    Hit h;
+    bool ok = false;
+    if (traced) sec.rays++;
+    if (PKT) {
+        int32_t* wnode = reinterpret_cast<int32_t*>(lds_pipe) + (size_t)wave * levels;
+        ok = root_intersect_pkt<EXTRA, false, 0, true>(sc, sc.extra, wnode, traced, start, d, h, sec);  // all 64 lanes take part
+    } else if (traced) {
+        Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+        ok = root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, start, d, h, sec);
+    }
+    if (active) {
+        uint32_t color = fc.background;
+        if (ok) color = (fc.flags & 1u) ? shade(fc, h.pos, h.nrm, h.color) : h.color;
+        cache[cell] = color ? color : 1u;
+    }
+    if (lane == 0) atomicAdd(filled, (unsigned long long)__popcll(am));
+    if (STATS) {
+        uint32_t r = (uint32_t)__popcll(__ballot(traced)), g = wave_sum(sec.geom), c2 = wave_sum(sec.nodes), d2 = wave_sum(sec.leaves);
+        if (lane == 0) { stat_add(&stats[4], r); stat_add(&stats[5], g); stat_add(&stats[6], c2); stat_add(&stats[7], d2); }
+    } else if (stats) {
+        const uint32_t r = (uint32_t)__popcll(__ballot(traced));
+        if (lane == 0) stat_add(&stats[4], r);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_cam_cones: per-frame pre-pass of the packet primary walk -- the CamCone record (sr_types.h) of every BVH triangle for
 // the frame's ray origin O: FP64 cross products of the FP64 vertices, rounded once to fp32.  64 B written + 72 B (gathered)
 // + 8 B read per triangle: 0.15 GB at 1 M triangles; re-run only when the origin or the tree changed.
@@ -4547,6 +4608,49 @@ static hipError_t launch_lightfield_t(const PipelineLaunch& L, int row_begin, in
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
     return hipSuccess;
+}
+
+// sr_bake_light_field: entries [first, first + count) of the table in launches of at most L.launch_cells cells (whole origin patches; at
+// least one), one after the other on the stream with nothing in between: no single kernel runs long, and the host never waits
+template <int MODE, bool EXTRA>
+static hipError_t launch_lf_bake_t(const BakeLaunch& L) {
+    const uint64_t n = (uint64_t)L.res, per_origin = 2 * n * n, tiles = ((2 * n + 7) / 8) * ((n + 7) / 8);
+    const uint64_t o_first = L.first / per_origin, o_last = (L.first + L.count - 1) / per_origin;
+    const uint64_t step = std::max<uint64_t>(1, L.launch_cells / per_origin);
+    const int levels = pipe_stack_levels(L.sc, MODE);
+    const size_t lds = (size_t)levels * 256 * 4;
+    const bool pkt = MODE == MODE_BVH && L.packet;
+    hipError_t e;
+    for (uint64_t o = o_first; o <= o_last; o += step) {
+        const uint64_t origins = std::min(step, o_last - o + 1);
+        const uint32_t item_first = (uint32_t)(o * tiles), item_count = (uint32_t)(origins * tiles);      // (2 N^2 x tiles <= 2^24 items in all)
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_LF_BAKE, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        const auto bake = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((item_count + 3u) / 4u), dim3(256), lds, L.stream, L.sc, L.fc, L.points, L.res, item_first, item_count, (uint32_t)L.first,
+                               (uint32_t)(L.first + L.count), L.cache, L.stats, L.filled, levels);
+        };
+        if (MODE == MODE_BVH && pkt) {
+            if (L.walk_stats) bake(k_lf_bake<MODE_BVH, EXTRA, true, true>); else bake(k_lf_bake<MODE_BVH, EXTRA, false, true>);
+        } else {
+            if (L.walk_stats) bake(k_lf_bake<MODE, EXTRA, true, false>); else bake(k_lf_bake<MODE, EXTRA, false, false>);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_lf_bake(const BakeLaunch& L) {
+    if (L.count == 0) return hipSuccess;
+    const bool extra = L.sc.nextra > 0;
+    switch (L.mode) {
+        case MODE_REF: return extra ? launch_lf_bake_t<MODE_REF, true>(L) : launch_lf_bake_t<MODE_REF, false>(L);
+        case MODE_BRUTE: return extra ? launch_lf_bake_t<MODE_BRUTE, true>(L) : launch_lf_bake_t<MODE_BRUTE, false>(L);
+        case MODE_BVH: return extra ? launch_lf_bake_t<MODE_BVH, true>(L) : launch_lf_bake_t<MODE_BVH, false>(L);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 static hipError_t launch_resolve(const PipelineLaunch& L, int row_begin, int row_count) {

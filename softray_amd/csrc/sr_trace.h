@@ -501,13 +501,17 @@ __device__ __forceinline__ lanemask cone_rejects_wave(const CamCone& cm, f2 dxx,
     return vote(fminf(fminf(c12.x + m12.x, c12.y + m12.y), c3n.x + m3n.x) < 0.0f) | vote(c3n.y > m3n.y);
 }
 
-template <bool FILTER>
+// SLAB (walks that have no camera-cone records: the origin is not the frame's camera): a lane consults the triangle's 64-byte TriSlab
+// record first (slab_rejects, the pre-test of the private walks: it only rejects what the FP64 test cannot turn into a hit that counts)
+template <bool FILTER, bool SLAB = false>
 __device__ bool bvh_packet_nearest(const DevScene& sc, int32_t* wnode, bool live, D3 s, D3 d, Hit& out, Ctr& c) {
     D3 end = s + d * 10000.0;
     D3 original = s;
     bool act = live;
     if (act) act = clip_segment<false>(sc.root, s, end);
     const double offset = act ? length(original - s) / length(d) : 0.0;
+    RayF rf;
+    if (SLAB) rf = make_ray_f(sc, s, d);
     const float ox = (float)(s.x - sc.root.centre[0]), oy = (float)(s.y - sc.root.centre[1]), oz = (float)(s.z - sc.root.centre[2]);
     const float dfx = (float)d.x, dfy = (float)d.y, dfz = (float)d.z;
     const float ix = slab_inv(dfx), iy = slab_inv(dfy), iz = slab_inv(dfz);
@@ -544,6 +548,10 @@ __device__ bool bvh_packet_nearest(const DevScene& sc, int32_t* wnode, bool live
                         if (FILTER) {
                             const CamCone cm = sc.bcam[k];                       // scalar load
                             cand = hc && !cone_rejects(cm, dxx, dyy, dzz, dl);
+                        }
+                        if (SLAB) {
+                            const TriSlab sl = sc.bslab[k];                      // scalar load
+                            cand = cand && !slab_rejects(sl, rf, tlim);
                         }
                         if (hc_first) c.geom++;
                         if (__ballot(cand) != 0ull) {
@@ -723,7 +731,7 @@ __device__ bool bvh4_packet_nearest(const DevScene& sc, int32_t* wnode, bool liv
 
 // root of the chain for a wavefront of rays with a common origin: extra geometry per lane, then the packet walk
 // (WIDE: on the four-wide tree's camera-ordered copy)
-template <bool EXTRA, bool FILTER, int WIDE = 0>     // WIDE: 0 binary tree, 1 four-wide tree, 2 four-wide tree with (near, far) planes on all axes
+template <bool EXTRA, bool FILTER, int WIDE = 0, bool SLAB = false>     // WIDE: 0 binary tree, 1 four-wide tree, 2 four-wide tree with (near, far) planes on all axes; SLAB: binary tree only
 __device__ bool root_intersect_pkt(const DevScene& sc, const Rec128* extra, int32_t* wnode, bool live, D3 s, D3 d, Hit& out, Ctr& c) {
     bool any = false;
     double best = DBL_MAX;
@@ -742,7 +750,7 @@ __device__ bool root_intersect_pkt(const DevScene& sc, const Rec128* extra, int3
     }
     Hit mh;
     const bool model = WIDE == 2 ? bvh4_packet_nearest<FILTER, 7>(sc, wnode, live, s, d, mh, c)
-                     : (WIDE == 1 ? bvh4_packet_nearest<FILTER, 0>(sc, wnode, live, s, d, mh, c) : bvh_packet_nearest<FILTER>(sc, wnode, live, s, d, mh, c));
+                     : (WIDE == 1 ? bvh4_packet_nearest<FILTER, 0>(sc, wnode, live, s, d, mh, c) : bvh_packet_nearest<FILTER, SLAB>(sc, wnode, live, s, d, mh, c));
     if (model && mh.t < best) { out = mh; any = true; }
     return any;
 }

@@ -293,15 +293,7 @@ public:
     void Render() {                                        // Renderer.cs:701-778
         if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
         if (!PinModel()) return;                           // silently, :736-739
-        if (rayTraceLightField) {                          // SR_F_LIGHT_FIELD: the colour light field; what the library refuses, by name
-            if (lightFieldHasTris_)
-                throw std::logic_error("rayTraceLightField with LightFieldStoresTriangles = true (LightFieldTriMethod) is out of scope: set it to false (SR_F_LIGHT_FIELD)");
-            if (rayTraceShadows) throw std::logic_error("rayTraceLightField together with rayTraceShadows is out of scope (SR_F_LIGHT_FIELD)");
-            if (rayTraceAmbientOcclusion) throw std::logic_error("rayTraceLightField together with rayTraceAmbientOcclusion is out of scope (SR_F_LIGHT_FIELD)");
-            if (rayTracePathTracing) throw std::logic_error("rayTraceLightField together with rayTracePathTracing is out of scope (SR_F_LIGHT_FIELD)");
-            if (rayTraceVoxels) throw std::logic_error("rayTraceLightField together with rayTraceVoxels is out of scope (SR_F_LIGHT_FIELD)");
-            if (gpuMaxBounces > 0) throw std::logic_error("rayTraceLightField together with gpuMaxBounces is out of scope (SR_F_LIGHT_FIELD)");
-        }
+        if (rayTraceLightField) CheckLightField();         // SR_F_LIGHT_FIELD: the colour light field; what the library refuses, by name
         if (rayTraceAmbientOcclusion) {                    // SR_F_AMBIENT_OCCLUSION: the pairs the library refuses, by name
             if (rayTracePathTracing) throw std::logic_error("rayTraceAmbientOcclusion together with rayTracePathTracing is out of scope (SR_F_AMBIENT_OCCLUSION)");
             if (rayTraceVoxels) throw std::logic_error("rayTraceAmbientOcclusion together with rayTraceVoxels is out of scope (SR_F_AMBIENT_OCCLUSION)");
@@ -319,6 +311,26 @@ public:
         }
         PostProcessImage();                                // :765
         AntiAliasImage();                                  // :767
+    }
+    // Pre-compute the colour light field (sr_bake_light_field): every entry that is still empty gets the colour of its cell's canonical ray, with
+    // the frame Render() would build for the first instance -- its geometry, shading, pose and lights.  Frames rendered afterwards look their
+    // colours up and trace nothing.  The same refusals as Render(); returns the number of entries written (0 without a model)
+    uint64_t BakeLightField() {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!rayTraceLightField) throw std::logic_error("BakeLightField needs rayTraceLightField (with LightFieldStoresTriangles = false)");
+        if (!PinModel()) return 0;
+        CheckLightField();
+        if (Instances.empty()) throw InvalidOperationException("BakeLightField: no instance to take the pose from");
+        Instance& inst = *Instances.front();
+        inst.FieldOfViewDepth = fieldOfViewDepth_;
+        PreCalculate();
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_frame f = BuildFrame(inst);
+        const uint64_t n = (uint64_t)LightFieldResolution();
+        uint64_t filled = 0;
+        sr_check(sr_bake_light_field(scene_, &f, 0, 4 * n * n * n * n, &filled));
+        return filled;
     }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
@@ -376,6 +388,15 @@ private:
     void AntiAliasImage() {                                // Renderer.cs:937-978
         if (antiAliasResolution_ < 2) return;
         sr_check(sr_anti_alias(scene_, pixels_, aaWidth_, aaHeight_, antiAliasResolution_, aaPixels_));
+    }
+    void CheckLightField() const {
+        if (lightFieldHasTris_)
+            throw std::logic_error("rayTraceLightField with LightFieldStoresTriangles = true (LightFieldTriMethod) is out of scope: set it to false (SR_F_LIGHT_FIELD)");
+        if (rayTraceShadows) throw std::logic_error("rayTraceLightField together with rayTraceShadows is out of scope (SR_F_LIGHT_FIELD)");
+        if (rayTraceAmbientOcclusion) throw std::logic_error("rayTraceLightField together with rayTraceAmbientOcclusion is out of scope (SR_F_LIGHT_FIELD)");
+        if (rayTracePathTracing) throw std::logic_error("rayTraceLightField together with rayTracePathTracing is out of scope (SR_F_LIGHT_FIELD)");
+        if (rayTraceVoxels) throw std::logic_error("rayTraceLightField together with rayTraceVoxels is out of scope (SR_F_LIGHT_FIELD)");
+        if (gpuMaxBounces > 0) throw std::logic_error("rayTraceLightField together with gpuMaxBounces is out of scope (SR_F_LIGHT_FIELD)");
     }
     int64_t Counter(int i, const char* name) const {
         if (!haveCounters_)

@@ -217,6 +217,15 @@ class GpuScene:
         entries = np.ascontiguousarray(entries, dtype=np.uint32).reshape(-1)
         _check(_lib.lib().sr_set_light_field(self._h, _p(entries), int(first), int(entries.size)))
 
+    def bake_light_field(self, frame, first=0, count=None):
+        """Fill every empty entry of first .. first + count - 1 (default: to the end of the table) with the colour of its cell's canonical ray, as a
+        light-field frame with `frame`'s geometry, shading and lights would; returns the number of entries written (sr_bake_light_field)."""
+        if count is None:
+            count = 4 * self.light_field_res ** 4 - int(first)
+        filled = C.c_uint64(0)
+        _check(_lib.lib().sr_bake_light_field(self._h, C.byref(frame), int(first), int(count), C.byref(filled)))
+        return int(filled.value)
+
     def ray_stats(self):
         """primary {rays, tests, nodes, leaves} + secondary {rays, tests, nodes, leaves} of the last render(stats=True)."""
         out = np.zeros(24, dtype=np.uint64)                           # SR_STATS_COUNT

@@ -85,6 +85,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_set_ao_cache(IntPtr scene, [In] byte[] in128Cubed);
         [DllImport(Lib)] public static extern int sr_set_light_field_res(IntPtr scene, int n);
         [DllImport(Lib)] public static extern int sr_get_light_field_res(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_set_voxel_res(IntPtr scene, int n);
+        [DllImport(Lib)] public static extern int sr_get_voxel_res(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_reset_light_field(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_get_light_field(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
@@ -377,6 +379,14 @@ namespace Engine3D.Hip
             Native.Check(Native.sr_set_ao_cache(scene, data));
         }
 
+        /// N of the N^3 voxel grid that F_VOXELS frames walk (VoxelGrid(N, ...), TriMeshToVoxelGrid.Convert(tris, N, grid)), 1..256, default 64 =
+        /// voxelGridSize (Renderer.cs:1570); another value drops the grid, which the next voxel frame makes again.  The reference's cache file
+        /// name carries it as _res{N}.
+        public int VoxelResolution
+        {
+            get { return Native.sr_get_voxel_res(scene); }
+            set { Native.Check(Native.sr_set_voxel_res(scene, value)); }
+        }
         /// N of the light field's 4 N^4 entries, 1..128; another value drops the table
         public int LightFieldResolution
         {

@@ -81,9 +81,9 @@ enum {
                                      the row blocks stay those of the whole row range.  Caller-made strips (strip_count > 1, also
                                      through sr_rccl_render) stay SR_ERR_UNSUPPORTED: one call on one scene cannot know how many
                                      samples hit in the rows the other ranks render */
-    SR_F_VOXELS      = 1u << 7,   /* rayTraceVoxels (Renderer.cs:1568-1588): rootGeometry = the model as a 64^3 VoxelGrid instead of the model's tree AND
+    SR_F_VOXELS      = 1u << 7,   /* rayTraceVoxels (Renderer.cs:1568-1588): rootGeometry = the model as an N^3 VoxelGrid (N = sr_set_voxel_res, default 64) instead of the model's tree AND
                                      the extra geometry (both ignored); the decorators above it stay.  A ray is clipped to the box (-1,-1,-1)..(1,1,1),
-                                     scaled to grid coordinates and walked in fixed steps of 0.1 along its longest axis (VoxelGrid.cs:125-177,
+                                     scaled to grid coordinates (p = (p * 0.5 + 0.5) * ((double)N - 0.001)) and walked in fixed steps of 0.1 along its longest axis (VoxelGrid.cs:125-177,
                                      LineWalker3D.cs:17-35); the first non-empty cell is the hit: its colour (the average of the colours of the triangles
                                      whose box of cells holds it) and the normal of its lowest-index triangle, pos = (0,0,0), rayFrac = 0.  Ignores
                                      trace_mode and needs no sr_build, only triangles: the first such frame calls sr_build_voxels.  Works with
@@ -294,17 +294,26 @@ int  sr_build(sr_scene*, uint32_t modes, int32_t max_depth, int32_t max_per_leaf
  * SR_BUILD_ON_DEVICE insists on the device (SR_ERR_NO_DEVICE for a host-only scene). */
 #define SR_BUILD_ON_DEVICE 0x100u
 #define SR_BUILD_ON_HOST   0x200u
-/* TriMeshToVoxelGrid.Convert(triangles, 64, grid) (TriMeshToVoxelGrid.cs:14-114, Renderer.cs:1570): the voxel grid SR_F_VOXELS frames and
- * SR_TARGET_VOXELS walk, made from the triangles in index order.  Cell (x,y,z) spans [k/64 - 0.5, (k+1)/64 - 0.5] per axis; a triangle is in
+/* TriMeshToVoxelGrid.Convert(triangles, N, grid) (TriMeshToVoxelGrid.cs:14-114; N = sr_set_voxel_res, default 64 = Renderer.cs:1570): the voxel grid
+ * SR_F_VOXELS frames and SR_TARGET_VOXELS walk, made from the triangles in index order.  Cell (x,y,z) spans [k/N - 0.5, (k+1)/N - 0.5] per axis
+ * (each plane a division, then a subtraction, in FP64: TriMeshToVoxelGrid.cs:28-29); a triangle is in
  * every cell of the box of cells its vertex ranges touch; a cell's colour is the average of its triangles' colours (summed in ascending
  * triangle index, truncated to bytes, alpha 255; 0 = empty), its normal the plane normal of its lowest-index triangle.  Idempotent; called
  * implicitly by the first voxel frame; sr_set_triangles / sr_load_3ds drop the grid.  A scene with a device builds it there (from the device
  * triangle records: (cell, triangle) pairs, a stable sort, one sum per cell; SR_ERR_UNSUPPORTED beyond 2^30 pairs), a host-only scene with a
  * plain host loop -- two independent implementations of one grid.  The reference's on-disk cache of the grid is not reproduced. */
 int  sr_build_voxels(sr_scene*);
-/* read-back of the grid in [x][y][z] order: colors[64*64*64], normals[64*64*64][3] (either may be NULL); works for a host-only scene;
- * SR_ERR_NOT_BUILT before sr_build_voxels / the first voxel frame */
+/* read-back of the grid in [x][y][z] order: colors[N*N*N], normals[N*N*N][3] (either may be NULL) -- the caller sizes its buffers by
+ * sr_get_voxel_res; works for a host-only scene; SR_ERR_NOT_BUILT before sr_build_voxels / the first voxel frame */
 int  sr_get_voxels(sr_scene*, uint32_t* colors, double* normals);
+/* The grid size N of VoxelGrid(N, ...) / TriMeshToVoxelGrid.Convert(tris, N, grid): 1..256, default 64 = Renderer.cs:1570 (the reference's own
+ * voxel tests run at 32); SR_ERR_INVALID_ARG outside 1..256 (three 8-bit coordinates make the 24-bit sort key of the device voxeliser).  A
+ * value different from the current one drops the grid: sr_get_voxels answers SR_ERR_NOT_BUILT until the next sr_build_voxels or voxel frame;
+ * the same value keeps it.  A multi-device scene forwards the call to its parts; a host-only scene accepts it too.  N <= 64 walks the
+ * cells' occupancy bits in LDS, N > 64 a two-level grid (one bit per brick of 4x4x4 cells in LDS, one 64-bit word per brick in memory):
+ * the same positions and the same first filled cell at every size. */
+int     sr_set_voxel_res(sr_scene*, int32_t n);
+int32_t sr_get_voxel_res(const sr_scene*);
 /* out = TreeDepth, NumNodes, NumLeafNodes, NumInternalNodes (SpatialSubdivision.cs:317-335) */
 int  sr_tree_stats(const sr_scene*, int32_t out[4]);
 /* the library's own BVH: out = depth, inner nodes, triangles, 1 if it was built on the device */
@@ -371,7 +380,7 @@ int64_t sr_frame_pixel_count(const sr_frame*);
  * SR_TARGET_ROOT = the root geometry of the chain (extra geometry + model in `mode`, Renderer.cs:1536-1549).
  * Host arrays; outputs may be NULL.  counters[n][3] = NumRayTests, NumNodesVisited, NumLeafNodesVisited. */
 #define SR_TARGET_ROOT 0x100
-/* target = SR_TARGET_VOXELS: VoxelGrid.IntersectRay (see SR_F_VOXELS): hit, colour and normal; ray_frac and pos are 0, tri_index is -1,
+/* target = SR_TARGET_VOXELS: VoxelGrid.IntersectRay on the N^3 grid (see SR_F_VOXELS, sr_set_voxel_res): hit, colour and normal; ray_frac and pos are 0, tri_index is -1,
  * counters are {1, 0, 0} (VoxelGrid.NumRayTests == 1).  Builds the grid when there is none. */
 #define SR_TARGET_VOXELS 0x200
 int  sr_trace_rays(sr_scene*, int32_t target, int64_t n, const double* starts, const double* dirs,
@@ -514,7 +523,9 @@ enum {
                                     computes the per-sample box exits for every hit point (no shortcut for candidate lists whose triangles all lie
                                     inside the root box); 94 production path, and a frame rendered with ray statistics leaves the census of that
                                     shortcut in statistics [22] (hit points classified with the shortcut) and [23] (with the per-sample box exits)
-                                    instead of the mirror rays' figures; 95 = 93 and 94 together                                           */
+                                    instead of the mirror rays' figures; 95 = 93 and 94 together; 41 a voxel walk on a grid of at most 64 reads the
+                                    colour table instead of the occupancy bits in LDS; 42 a voxel walk on a grid above 64 reads the row-major
+                                    occupancy bits in global memory, one level, instead of the two-level walk                              */
     SR_DBG_KERNEL_TIMING  = 7,   /* > 0: record a HIP event pair around every launch (sr_kernel_times); default off           */
     SR_DBG_EXACT_SHADOW_TESTS = 8, /* > 0: k_shadow_test decides every (sample, triangle) pair with the FP64 arithmetic (no
                                     fp32 classification): an independent schedule of the same result, kept as a cross-check */

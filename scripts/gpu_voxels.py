@@ -1,7 +1,12 @@
 """Voxel-grid rendering (SR_F_VOXELS) measured on the GPU: the voxeliser on the unit-cube scene and the 4096^2 voxel frame (shading on,
 one sample per pixel and 2x2 sub-pixel samples) next to the plain SR_MODE_BVH frame of the same scene from the same run.
 
-    python scripts/gpu_voxels.py [--out profiles/voxels.json]
+    python scripts/gpu_voxels.py [--voxel-res N] [--out profiles/voxel_res/res<N>.json]
+
+--voxel-res N (default 64; `--res` is the frame's edge) sets the grid size with sr_set_voxel_res.  Above 64 the second schedule of the walk
+is SR_DBG_KERNEL_SWITCH 42 (one level, the row-major occupancy bits in global memory) instead of 41 (the colour table).
+--only voxelise|frames runs one of the steps on --triangles, --no-plain leaves the SR_MODE_BVH frames (and their sr_build) out, and
+--root DIR imports softray_amd from another checkout: the parent commit's build next to this one for an A/B at 64.
 
 Every step is a child process of its own with a time limit of its own, and a step that fails or runs out of time ends the script (nothing
 more is started on the GPU after it):
@@ -14,7 +19,8 @@ Voxelisation: `reps` builds, each after sr_set_triangles has dropped the grid; p
 device synchronise and includes the first build's upload of the triangles) and the library's own HIP event pair around the voxeliser
 (count, scan, the read-back of the pair count, emit, sort, per-cell sums).  Frames: device frames (sr_render_device into a torch tensor),
 variants alternating, HIP events around each frame, warm-up first, median and spread over the repetitions.  The walk is measured twice:
-with the occupancy bits staged in LDS (the default) and reading the colour table in global memory at every step (SR_DBG_KERNEL_SWITCH 41).
+on its default schedule (occupancy bits in LDS; two levels above 64) and on the second one (SR_DBG_KERNEL_SWITCH 41: the colour table in global
+memory at every step; above 64, 42: the row-major occupancy bits in global memory).
 Reads neither the reference nor anything the oracle built: the scene comes from the library's seeded generator.
 """
 import argparse
@@ -31,9 +37,35 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--res", type=int, default=4096)
 ap.add_argument("--triangles", type=int, default=1_000_000)
 ap.add_argument("--reps", type=int, default=15)
+ap.add_argument("--voxel-res", type=int, default=64, help="N of the N^3 grid (sr_set_voxel_res)")
+ap.add_argument("--only", default=None, choices=["voxelise", "frames"], help="run only this step (on --triangles)")
+ap.add_argument("--no-plain", action="store_true", help="no SR_MODE_BVH frames next to the voxel frames")
+ap.add_argument("--root", default=None, help="import softray_amd from this checkout instead of the script's own")
 ap.add_argument("--out", default=None)
 ap.add_argument("--step", default=None, choices=["voxelise", "frames"], help="(internal) run one step in this process")
 args = ap.parse_args()
+if args.root:
+    sys.path.insert(0, os.path.abspath(args.root))
+HOOK = 42 if args.voxel_res > 64 else 41
+HOOK_NAME = "flat_mask" if args.voxel_res > 64 else "global_table"
+
+
+def set_res(g):
+    if args.voxel_res != 64:                                          # (64 is the default: a library without sr_set_voxel_res runs the script too)
+        g.voxel_res = args.voxel_res
+
+
+def pair_count(v9, n):
+    """(cell, triangle) pairs of the grid: per axis the cells with max >= plane(k) and min <= plane(k + 1), planes as FP64 computes k / n - 0.5."""
+    import numpy as np
+    planes = np.arange(n + 1, dtype=np.float64) / np.float64(n) - 0.5
+    v = np.asarray(v9, dtype=np.float64).reshape(-1, 3, 3)
+    total = np.ones(v.shape[0], dtype=np.int64)
+    for a in range(3):
+        hi = np.minimum(np.searchsorted(planes, v[:, :, a].max(axis=1), side="right") - 1, n - 1)
+        lo = np.searchsorted(planes[1:], v[:, :, a].min(axis=1), side="left")
+        total *= np.maximum(0, hi - lo + 1)
+    return int(total.sum())
 
 
 def stats(xs):
@@ -47,6 +79,7 @@ def step_voxelise():
     import softray_amd as sa
     v9, argb, bmin, bmax = sa.unit_cube_scene(args.triangles)
     g = sa.GpuScene(0)
+    set_res(g)
     g.debug_set(sa._lib.DBG_KERNEL_TIMING, 1)
     wall, dev = [], []
     for i in range(args.reps + 1):                                    # the first build also uploads the triangles and loads the code objects: warm-up
@@ -61,7 +94,8 @@ def step_voxelise():
         else:
             first = (t1 - t0) * 1e3
     colors, _ = g.get_voxels()
-    return {"triangles": args.triangles, "filled_cells": int(np.count_nonzero(colors)), "first_build_wall_ms": round(first, 3),
+    return {"triangles": args.triangles, "voxel_res": args.voxel_res, "pairs": pair_count(v9, args.voxel_res), "filled_cells": int(np.count_nonzero(colors)),
+            "first_build_wall_ms": round(first, 3),
             "build_wall_ms": stats(wall), "voxeliser_events_ms": stats(dev)}
 
 
@@ -72,12 +106,15 @@ def step_frames():
     res = args.res
     g = sa.GpuScene(0)
     g.set_triangles(*sa.unit_cube_scene(args.triangles))
-    g.build((sa.MODE_BVH,))
+    set_res(g)
+    if not args.no_plain:
+        g.build((sa.MODE_BVH,))
     g.build_voxels()
-    table = sa.GpuScene(0)                                            # the same grid walked without the LDS mask
+    table = sa.GpuScene(0)                                            # the same grid on the walk's second schedule (hook 41 / 42)
     table.set_triangles(*sa.unit_cube_scene(args.triangles))
+    set_res(table)
     table.build_voxels()
-    table.debug_set(sa._lib.DBG_KERNEL_SWITCH, 41)
+    table.debug_set(sa._lib.DBG_KERNEL_SWITCH, HOOK)
 
     def frame(voxels, sub):
         f = sa.Frame()
@@ -103,8 +140,9 @@ def step_frames():
         return f
 
     variants = [("voxels_1spp", g, frame(True, 1)), ("voxels_2x2", g, frame(True, 2)),
-                ("voxels_1spp_global_table", table, frame(True, 1)), ("voxels_2x2_global_table", table, frame(True, 2)),
-                ("plain_bvh_1spp", g, frame(False, 1)), ("plain_bvh_2x2", g, frame(False, 2))]
+                ("voxels_1spp_" + HOOK_NAME, table, frame(True, 1)), ("voxels_2x2_" + HOOK_NAME, table, frame(True, 2))]
+    if not args.no_plain:
+        variants += [("plain_bvh_1spp", g, frame(False, 1)), ("plain_bvh_2x2", g, frame(False, 2))]
     surface = torch.zeros(res * res, dtype=torch.int32, device="cuda:0")
     stream = torch.cuda.current_stream().cuda_stream
     images = {}
@@ -113,8 +151,8 @@ def step_frames():
             s.render_device(f, surface.data_ptr(), stream)
             torch.cuda.synchronize()
             images[n] = surface.cpu().numpy().copy()
-    same = bool(np.array_equal(images["voxels_1spp"], images["voxels_1spp_global_table"]) and
-                np.array_equal(images["voxels_2x2"], images["voxels_2x2_global_table"]))
+    same = bool(np.array_equal(images["voxels_1spp"], images["voxels_1spp_" + HOOK_NAME]) and
+                np.array_equal(images["voxels_2x2"], images["voxels_2x2_" + HOOK_NAME]))
     shown = float(np.count_nonzero(images["voxels_1spp"].view(np.uint32) != 0xffff00ff)) / images["voxels_1spp"].size
     times = {n: [] for n, _, _ in variants}
     for _ in range(args.reps):
@@ -125,8 +163,11 @@ def step_frames():
             b.record()
             b.synchronize()
             times[n].append(a.elapsed_time(b))
-    return {"res": res, "triangles": args.triangles, "frames_ms": {n: stats(times[n]) for n, _, _ in variants},
-            "lds_mask_and_global_table_frames_identical": same, "voxel_frame_non_background_share": round(shown, 4)}
+    import zlib
+    return {"res": res, "triangles": args.triangles, "voxel_res": args.voxel_res, "second_schedule_hook": HOOK,
+            "frames_ms": {n: stats(times[n]) for n, _, _ in variants},
+            "frame_crc": {n: zlib.crc32(images[n].tobytes()) & 0xFFFFFFFF for n in ("voxels_1spp", "voxels_2x2")},
+            "both_schedules_frames_identical": same, "voxel_frame_non_background_share": round(shown, 4)}
 
 
 if args.step:
@@ -135,7 +176,8 @@ if args.step:
 
 
 def child(step, triangles, limit):
-    cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--triangles", str(triangles), "--res", str(args.res), "--reps", str(args.reps)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--triangles", str(triangles), "--res", str(args.res), "--reps", str(args.reps),
+           "--voxel-res", str(args.voxel_res)] + (["--no-plain"] if args.no_plain else []) + (["--root", args.root] if args.root else [])
     print("step: %s, %d triangles, time limit %.0f s" % (step, triangles, limit), flush=True)
     t0 = time.perf_counter()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)          # TimeoutExpired ends the script: nothing is started after it
@@ -150,10 +192,15 @@ def child(step, triangles, limit):
 
 
 doc = {}
-doc["voxelise_200k"] = child("voxelise", 200_000, 300.0)
-limit = 120.0 + 20.0 * doc["voxelise_200k"]["build_wall_ms"]["median"] / 1e3
-doc["voxelise_%d" % args.triangles] = child("voxelise", args.triangles, limit)
-doc["frames"] = child("frames", args.triangles, 600.0)
+if args.only == "voxelise":
+    doc["voxelise_%d" % args.triangles] = child("voxelise", args.triangles, 300.0)
+elif args.only == "frames":
+    doc["frames"] = child("frames", args.triangles, 600.0)
+else:
+    doc["voxelise_200k"] = child("voxelise", 200_000, 300.0)
+    limit = 120.0 + 20.0 * doc["voxelise_200k"]["build_wall_ms"]["median"] / 1e3
+    doc["voxelise_%d" % args.triangles] = child("voxelise", args.triangles, limit)
+    doc["frames"] = child("frames", args.triangles, 600.0)
 print(json.dumps(doc))
 if args.out:
     with open(args.out, "w") as fh:

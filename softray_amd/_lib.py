@@ -44,7 +44,7 @@ SYMBOLS = [
     "sr_trace_rays_device", "sr_rccl_unique_id", "sr_rccl_init", "sr_rccl_render", "sr_rccl_gather", "sr_set_gather",
     "sr_net_random_doubles", "sr_build_voxels", "sr_get_voxels", "sr_reset_ao_cache", "sr_get_ao_cache", "sr_set_ao_cache",
     "sr_set_light_field_res", "sr_get_light_field_res", "sr_reset_light_field", "sr_get_light_field", "sr_set_light_field",
-    "sr_bake_light_field",
+    "sr_bake_light_field", "sr_set_voxel_res", "sr_get_voxel_res",
 ]
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
@@ -159,6 +159,8 @@ def lib():
     L.sr_set_gather.restype = i32; L.sr_set_gather.argtypes = [vp, i32]
     L.sr_build_voxels.restype = i32; L.sr_build_voxels.argtypes = [vp]
     L.sr_get_voxels.restype = i32; L.sr_get_voxels.argtypes = [vp, vp, vp]
+    L.sr_set_voxel_res.restype = i32; L.sr_set_voxel_res.argtypes = [vp, i32]
+    L.sr_get_voxel_res.restype = i32; L.sr_get_voxel_res.argtypes = [vp]
     L.sr_reset_ao_cache.restype = i32; L.sr_reset_ao_cache.argtypes = [vp]
     L.sr_get_ao_cache.restype = i32; L.sr_get_ao_cache.argtypes = [vp, vp]
     L.sr_set_ao_cache.restype = i32; L.sr_set_ao_cache.argtypes = [vp, vp]

@@ -145,9 +145,11 @@ struct sr_scene {
     // (multi-device scene) where the parts' row counts meet: portable pinned host memory, one word per row of the range
     void* pt_counts_host = nullptr; size_t pt_counts_cap = 0;
     int32_t last_parts = 1;              // sr_last_frame_parts
-    // rayTraceVoxels (SR_F_VOXELS): the 64^3 grid of the current model, made by sr_build_voxels / the first voxel frame and dropped by
+    // rayTraceVoxels (SR_F_VOXELS): the N^3 grid (N = vox_res) of the current model, made by sr_build_voxels / the first voxel frame and dropped by
     // sr_set_triangles.  A scene with a device keeps it there (colours, normals, occupancy bits); a host-only scene on the host
     DBuf d_vox_colors, d_vox_normals, d_vox_mask;
+    DBuf d_vox_bricks, d_vox_coarse;     // N > 64: one 64-bit word per brick of 4x4x4 cells, one bit per brick (sr_voxels.hip k_vox_bricks)
+    int32_t vox_res = sr::kVoxelGrid;    // sr_set_voxel_res; 64 = Renderer.cs:1570
     std::vector<uint32_t> vox_colors_host;
     std::vector<double>   vox_normals_host;
     bool vox_valid = false;
@@ -512,27 +514,39 @@ int next_events(sr_scene* s, int k, hipEvent_t& a, hipEvent_t& b) {
 // records (on `stream`; the call waits for it: the number of (cell, triangle) pairs sizes the sort's buffers); a host-only scene runs the plain
 // host loop (sr_host.cpp voxelise_host)
 const long long kMaxVoxelPairs = 1ll << 30;
+sr::VoxelGridDev voxel_grid_dev(const sr_scene* s) {
+    const bool two = s->vox_res > sr::kVoxelGrid;
+    return sr::VoxelGridDev{(uint32_t*)s->d_vox_colors.p, (double*)s->d_vox_normals.p, (uint32_t*)s->d_vox_mask.p,
+                            two ? (unsigned long long*)s->d_vox_bricks.p : nullptr, two ? (uint32_t*)s->d_vox_coarse.p : nullptr, s->vox_res,
+                            (s->vox_res + 3) / 4};
+}
 int ensure_voxels(sr_scene* s, hipStream_t stream) {
     if (s->vox_valid) return SR_OK;
-    const size_t cells = (size_t)sr::kVoxelGrid * sr::kVoxelGrid * sr::kVoxelGrid;
+    const int N = s->vox_res;
+    const size_t cells = (size_t)N * N * N;
     const double lo[3] = {-1, -1, -1}, hi[3] = {1, 1, 1};
     s->vox_box = sr::make_root_box(lo, hi);
     if (s->device < 0) {
         s->vox_colors_host.assign(cells, 0u);
         s->vox_normals_host.assign(cells * 3, 0.0);
-        sr::voxelise_host(s->v9.data(), s->tri_recs.data(), s->ntris, s->vox_colors_host.data(), s->vox_normals_host.data());
+        sr::voxelise_host(s->v9.data(), s->tri_recs.data(), s->ntris, N, s->vox_colors_host.data(), s->vox_normals_host.data());
         s->vox_valid = true;
         return SR_OK;
     }
     if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still walk the old grid
     SR_HIP(s->d_vox_colors.reserve(cells * 4));
     SR_HIP(s->d_vox_normals.reserve(cells * 3 * sizeof(double)));
-    SR_HIP(s->d_vox_mask.reserve(cells / 8));
+    SR_HIP(s->d_vox_mask.reserve(sr::voxel_mask_words(N) * 4));
+    if (N > sr::kVoxelGrid) {
+        const int nb = (N + 3) / 4;
+        SR_HIP(s->d_vox_bricks.reserve((size_t)nb * nb * nb * 8));
+        SR_HIP(s->d_vox_coarse.reserve(sr::voxel_mask_words(nb) * 4));
+    }
     const int n = (int)s->ntris;
     DBuf counts, offsets, temp, pairs, first_last;
     struct Free { DBuf* b[5]; ~Free() { for (DBuf* x : b) x->release(); } } free_all{{&counts, &offsets, &temp, &pairs, &first_last}};
     size_t scan_bytes = 0;
-    SR_HIP(sr::voxel_count_cells(nullptr, n, nullptr, nullptr, nullptr, &scan_bytes, stream));
+    SR_HIP(sr::voxel_count_cells(nullptr, n, N, nullptr, nullptr, nullptr, &scan_bytes, stream));
     SR_HIP(counts.reserve((size_t)n * 8));
     SR_HIP(offsets.reserve((size_t)n * 8));
     SR_HIP(temp.reserve(scan_bytes));
@@ -541,7 +555,7 @@ int ensure_voxels(sr_scene* s, hipStream_t stream) {
     int rc = next_events(s, sr::K_VOXELISE, e0, e1);
     if (rc) return rc;
     if (e0) SR_HIP(hipEventRecord(e0, stream));
-    SR_HIP(sr::voxel_count_cells((const double*)s->d_v9.p, n, (unsigned long long*)counts.p, (unsigned long long*)offsets.p, temp.p, &scan_bytes, stream));
+    SR_HIP(sr::voxel_count_cells((const double*)s->d_v9.p, n, N, (unsigned long long*)counts.p, (unsigned long long*)offsets.p, temp.p, &scan_bytes, stream));
     unsigned long long tail[2] = {0, 0};
     SR_HIP(hipMemcpyAsync(&tail[0], (const unsigned long long*)offsets.p + (n - 1), 8, hipMemcpyDeviceToHost, stream));
     SR_HIP(hipMemcpyAsync(&tail[1], (const unsigned long long*)counts.p + (n - 1), 8, hipMemcpyDeviceToHost, stream));
@@ -549,12 +563,12 @@ int ensure_voxels(sr_scene* s, hipStream_t stream) {
     const unsigned long long npairs = tail[0] + tail[1];
     if (npairs > (unsigned long long)kMaxVoxelPairs)
         return fail(SR_ERR_UNSUPPORTED, "voxel grid: the triangles' boxes of cells hold more than 2^30 (cell, triangle) pairs");
-    const size_t sort_bytes = npairs ? sr::voxel_sort_temp_bytes((unsigned int)npairs) : 0;
+    const size_t sort_bytes = npairs ? sr::voxel_sort_temp_bytes((unsigned int)npairs, sr::voxel_key_bits(N)) : 0;
     if (npairs) {
         SR_HIP(pairs.reserve((size_t)npairs * 4 * 4));
         if (sort_bytes > temp.cap) SR_HIP(temp.reserve(sort_bytes));
     }
-    const sr::VoxelGridDev grid{(uint32_t*)s->d_vox_colors.p, (double*)s->d_vox_normals.p, (uint32_t*)s->d_vox_mask.p};
+    const sr::VoxelGridDev grid = voxel_grid_dev(s);
     SR_HIP(sr::voxel_fill_grid((const double*)s->d_v9.p, (const sr::Rec128*)s->d_tris.p, n, (const unsigned long long*)offsets.p, (unsigned int)npairs,
                                (unsigned int*)pairs.p, temp.p, sort_bytes, (unsigned int*)first_last.p, grid, stream));
     if (e1) SR_HIP(hipEventRecord(e1, stream));
@@ -695,13 +709,14 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         sr::VoxelLaunch V{};
         V.fc = fc;
         V.box = s->vox_box;
-        V.grid = sr::VoxelGridDev{(uint32_t*)s->d_vox_colors.p, (double*)s->d_vox_normals.p, (uint32_t*)s->d_vox_mask.p};
+        V.grid = voxel_grid_dev(s);
         V.row_map = d_rowmap;
         V.pixels = d_pixels;
         V.samples = (uint32_t*)B.samples.p;
         V.band_rows = (int32_t)rows;
         V.persistent_blocks = s->num_cus * 3;                         // 3 workgroups x 32 KB of occupancy bits per CU (137 VGPRs: 3 waves per SIMD)
         V.global_table = s->dbg[SR_DBG_KERNEL_SWITCH] == 41;          // (hook: no LDS mask, a step reads the colour table)
+        V.flat_mask = s->dbg[SR_DBG_KERNEL_SWITCH] == 42;             // (hook, N > 64: one level, a step reads the occupancy bits in global memory)
         V.stats = d_stats;
         V.stream = stream;
         V.user = s;
@@ -1332,7 +1347,7 @@ void sr_destroy(sr_scene* s) {
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
                         &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
-                        &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask};
+                        &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
         for (auto& t : s->tables) { t.dev.release(); if (t.host) (void)hipHostFree(t.host); if (t.used) (void)hipEventDestroy(t.used); if (t.ready) (void)hipEventDestroy(t.ready); }
@@ -1540,7 +1555,7 @@ int sr_get_voxels(sr_scene* s, uint32_t* colors, double* normals) {
     if (s && !s->parts.empty()) s = s->parts[0];
     if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_get_voxels");
     if (!s->vox_valid) return fail(SR_ERR_NOT_BUILT, "no voxel grid: call sr_build_voxels (or render a SR_F_VOXELS frame) after setting the triangles");
-    const size_t cells = (size_t)sr::kVoxelGrid * sr::kVoxelGrid * sr::kVoxelGrid;
+    const size_t cells = (size_t)s->vox_res * s->vox_res * s->vox_res;
     if (s->device < 0) {
         if (colors) std::memcpy(colors, s->vox_colors_host.data(), cells * 4);
         if (normals) std::memcpy(normals, s->vox_normals_host.data(), cells * 3 * sizeof(double));
@@ -1551,6 +1566,24 @@ int sr_get_voxels(sr_scene* s, uint32_t* colors, double* normals) {
     if (colors) SR_HIP(hipMemcpy(colors, s->d_vox_colors.p, cells * 4, hipMemcpyDeviceToHost));
     if (normals) SR_HIP(hipMemcpy(normals, s->d_vox_normals.p, cells * 3 * sizeof(double), hipMemcpyDeviceToHost));
     return SR_OK;
+}
+
+int sr_set_voxel_res(sr_scene* s, int32_t n) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_voxel_res");
+    if (n < 1 || n > sr::kVoxelGridMax) return fail(SR_ERR_INVALID_ARG, "voxel grid resolution must be 1..256");
+    if (!s->parts.empty()) {                                         // every part builds its own grid
+        for (sr_scene* q : s->parts) { int rc = sr_set_voxel_res(q, n); if (rc) return rc; }
+        return SR_OK;
+    }
+    if (n == s->vox_res) return SR_OK;                                // the same value keeps the grid
+    s->vox_res = n;
+    s->vox_valid = false;                                             // another size is another grid: the next build or voxel frame makes it
+    return SR_OK;
+}
+
+int32_t sr_get_voxel_res(const sr_scene* s) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    return s ? s->vox_res : 0;
 }
 
 int sr_tree_stats(const sr_scene* s, int32_t out[4]) {
@@ -2100,8 +2133,7 @@ int sr_trace_rays_device(sr_scene* s, int32_t target, int64_t n, const double* d
     if (e0) SR_HIP(hipEventRecord(e0, L.stream));
     if (mode < 0) {
         if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(L.stream, s->pre_used, 0));
-        const sr::VoxelGridDev grid{(uint32_t*)s->d_vox_colors.p, (double*)s->d_vox_normals.p, (uint32_t*)s->d_vox_mask.p};
-        SR_HIP(sr::launch_voxel_trace(L, s->vox_box, grid, 256 * 4));
+        SR_HIP(sr::launch_voxel_trace(L, s->vox_box, voxel_grid_dev(s), 256 * 4, s->dbg[SR_DBG_KERNEL_SWITCH] == 42));
     } else
     SR_HIP(sr::launch_trace(L));
     if (e1) SR_HIP(hipEventRecord(e1, L.stream));

@@ -234,20 +234,29 @@ hipError_t launch_trace(const TraceLaunch& L);
 // k_resolve for the compact rows [row_begin, row_begin + row_count) of a band-local sample buffer (sr_pipeline.hip)
 hipError_t launch_resolve_rows(const FrameConst& fc, const int32_t* row_map, int row_begin, int row_count, const uint32_t* samples, uint32_t* pixels, hipStream_t stream);
 
-// ---- rayTraceVoxels (SR_F_VOXELS; sr_voxels.hip): the model as a 64^3 grid of coloured cells, [x][y][z] order ----
-constexpr int kVoxelGrid = 64;                    // Renderer.cs:1570
+// ---- rayTraceVoxels (SR_F_VOXELS; sr_voxels.hip): the model as an N^3 grid of coloured cells, [x][y][z] order, N = sr_set_voxel_res ----
+constexpr int kVoxelGrid = 64;                    // the default N, Renderer.cs:1570
+constexpr int kVoxelGridMax = 256;                // three 8-bit coordinates: a 24-bit sort key
 struct VoxelGridDev {
-    uint32_t* colors;       // device [64^3]: 0 = empty cell
-    double*   normals;      // device [64^3][3]
-    uint32_t* mask;         // device [64^3 / 32]: bit (cell & 31) of word (cell >> 5) = the cell's colour is not 0
+    uint32_t* colors;       // device [N^3]: 0 = empty cell
+    double*   normals;      // device [N^3][3]
+    uint32_t* mask;         // device [voxel_mask_words(N)]: bit (cell & 31) of word (cell >> 5) = the cell's colour is not 0; the tail is 0
+    // N > 64 only (nullptr otherwise): bricks of 4x4x4 cells, brick index ((x>>2) * nb + (y>>2)) * nb + (z>>2), nb = (N + 3) / 4
+    unsigned long long* bricks;   // device [nb^3]: bit (x&3)*16 + (y&3)*4 + (z&3) = the cell is filled; cells beyond N are 0
+    uint32_t* coarse;       // device [voxel_mask_words(nb)]: bit (brick & 31) of word (brick >> 5) = the brick's word is not 0
+    int32_t   n;            // N
+    int32_t   nb;           // bricks per axis
 };
+// words of a bit mask over g^3 items: whole waves' ballots (64 bits) and whole uint4 for the staging loop
+constexpr size_t voxel_mask_words(int g) { return (((size_t)g * g * g + 127) / 128) * 4; }
 // The voxeliser in three steps, because the number of (cell, triangle) pairs decides what the second one needs:
 // (1) cells per triangle and their exclusive scan (d_temp == nullptr: only the scan's scratch size -> *temp_bytes);
 // (2) the caller reads offsets[n - 1] + counts[n - 1] back and provides d_pairs (4 x npairs words) and the sort's scratch;
 // (3) pairs -> stable sort by cell -> per-cell sums in ascending triangle order -> colours, normals, occupancy bits.
-// d_first_last: 2 x 64^3 words of scratch.
-hipError_t voxel_count_cells(const double* d_v9, int ntris, unsigned long long* d_counts, unsigned long long* d_offsets, void* d_temp, size_t* temp_bytes, hipStream_t stream);
-size_t voxel_sort_temp_bytes(unsigned int npairs);
+// d_first_last: 2 x N^3 words of scratch.  The sort key has voxel_key_bits(N) = ceil(log2(N^3)) bits (18 at N = 64).
+int voxel_key_bits(int n);
+hipError_t voxel_count_cells(const double* d_v9, int ntris, int n, unsigned long long* d_counts, unsigned long long* d_offsets, void* d_temp, size_t* temp_bytes, hipStream_t stream);
+size_t voxel_sort_temp_bytes(unsigned int npairs, int key_bits);
 hipError_t voxel_fill_grid(const double* d_v9, const Rec128* d_tris, int ntris, const unsigned long long* d_offsets, unsigned int npairs, unsigned int* d_pairs,
                            void* d_temp, size_t temp_bytes, unsigned int* d_first_last, const VoxelGridDev& grid, hipStream_t stream);
 struct VoxelLaunch {
@@ -260,13 +269,14 @@ struct VoxelLaunch {
     int32_t     band_rows;
     int32_t     persistent_blocks;
     bool        global_table;   // a step reads the colour table instead of the occupancy bits in LDS (A/B measurement, same pixels)
+    bool        flat_mask;      // N > 64: a step reads the row-major occupancy bits in global memory instead of the two-level walk (A/B, same pixels)
     unsigned long long* stats;  // device [4..] or nullptr
     hipStream_t stream;
     void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
     void*       user;
 };
 hipError_t launch_voxel_frame(const VoxelLaunch& L);
-hipError_t launch_voxel_trace(const TraceLaunch& L, const RootBox& box, const VoxelGridDev& grid, int max_blocks);
+hipError_t launch_voxel_trace(const TraceLaunch& L, const RootBox& box, const VoxelGridDev& grid, int max_blocks, bool flat_mask);
 hipError_t launch_shade_points(const FrameConst& fc, long long n, const double* pos, const double* nrm, const uint32_t* color, uint32_t* out, hipStream_t stream);
 
 // --------------------------------------------------------------------------------------------------

@@ -836,13 +836,13 @@ std::string load_3ds(const uint8_t* data, size_t len, LoadedModel& out) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// TriMeshToVoxelGrid.Convert (TriMeshToVoxelGrid.cs:14-114), grid 64: the plain loop
+// TriMeshToVoxelGrid.Convert (TriMeshToVoxelGrid.cs:14-114), grid n: the plain loop
 // ------------------------------------------------------------------------------------------------
-// Triangles in index order; every triangle tests all 64 cells of every axis with the reference's two plane comparisons
-// (FindTrianglesInsidePlanes: v.n >= d for axis normals, i.e. max >= k/64 - 0.5 and min <= (k+1)/64 - 0.5) and adds its colour to the
+// Triangles in index order; every triangle tests all n cells of every axis with the reference's two plane comparisons
+// (FindTrianglesInsidePlanes: v.n >= d for axis normals, i.e. max >= k/n - 0.5 and min <= (k+1)/n - 0.5, the planes computed as a division and then a subtraction) and adds its colour to the
 // cells of the resulting box, so every cell sums in ascending triangle index like the reference's list walk.
-void voxelise_host(const double* v9, const Rec128* recs, size_t ntris, uint32_t* colors, double* normals) {
-    const int G = 64;
+void voxelise_host(const double* v9, const Rec128* recs, size_t ntris, int n, uint32_t* colors, double* normals) {
+    const int G = n;
     const size_t cells = (size_t)G * G * G;
     std::vector<double> sum(cells * 3, 0.0);
     std::vector<int32_t> count(cells, 0);
@@ -855,7 +855,7 @@ void voxelise_host(const double* v9, const Rec128* recs, size_t ntris, uint32_t*
             const double mn = std::min(v[a], std::min(v[3 + a], v[6 + a])), mx = std::max(v[a], std::max(v[3 + a], v[6 + a]));
             lo[a] = G; hi[a] = -1;
             for (int k = 0; k < G; ++k) {
-                const double p0 = (double)k / G - 0.5, p1 = (double)(k + 1) / G - 0.5;
+                const double p0 = (double)k / (double)G - 0.5, p1 = (double)(k + 1) / (double)G - 0.5;
                 if (mx >= p0 && mn <= p1) { lo[a] = std::min(lo[a], k); hi[a] = std::max(hi[a], k); }
             }
             any = any && hi[a] >= lo[a];
@@ -873,8 +873,8 @@ void voxelise_host(const double* v9, const Rec128* recs, size_t ntris, uint32_t*
     }
     for (size_t cell = 0; cell < cells; ++cell) {
         if (!count[cell]) { colors[cell] = 0u; continue; }
-        const double n = (double)count[cell];
-        const double r = sum[3 * cell] / n, g = sum[3 * cell + 1] / n, b = sum[3 * cell + 2] / n;
+        const double cnt = (double)count[cell];
+        const double r = sum[3 * cell] / cnt, g = sum[3 * cell + 1] / cnt, b = sum[3 * cell + 2] / cnt;
         colors[cell] = (255u << 24) + (((uint32_t)(int)(r * 255.0) & 0xffu) << 16) + (((uint32_t)(int)(g * 255.0) & 0xffu) << 8) + ((uint32_t)(int)(b * 255.0) & 0xffu);   // Color.ToARGB
     }
 }

@@ -62,8 +62,8 @@ void build_bvh(const std::vector<double>& v9, const RootBox& root, Bvh& out, int
 // the BVH2's, so both trees describe the same hierarchy of the same records.  Returns the depth (root = 1).
 int collapse_bvh4(const BvhNode* nodes, size_t num_nodes, std::vector<Bvh4Node>& out);
 
-// ---- voxel grid (TriMeshToVoxelGrid.Convert, grid 64): colors[64^3], normals[64^3][3] in [x][y][z] order ----
-void voxelise_host(const double* v9, const Rec128* recs, size_t ntris, uint32_t* colors, double* normals);
+// ---- voxel grid (TriMeshToVoxelGrid.Convert, grid n): colors[n^3], normals[n^3][3] in [x][y][z] order ----
+void voxelise_host(const double* v9, const Rec128* recs, size_t ntris, int n, uint32_t* colors, double* normals);
 
 // ---- Instance / Renderer helpers ----
 void instance_matrices(const double position[3], double yaw, double pitch, double roll,

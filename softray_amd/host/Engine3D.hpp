@@ -222,6 +222,10 @@ public:
     void ResetLightField() { sr_check(sr_reset_light_field(scene_)); }           // what a new Renderer's LightFieldColorMethod starts with
     int LightFieldResolution() const { return (int)sr_get_light_field_res(scene_); }   // lightFieldRes (Renderer.cs:93): 64
     void LightFieldResolution(int n) { sr_check(sr_set_light_field_res(scene_, n)); }
+    // library extension: the reference has a constant there (voxelGridSize = 64, Renderer.cs:1570).  1..256; another value drops the grid,
+    // which the next voxel frame makes again (sr_set_voxel_res)
+    int VoxelGridSize() const { return (int)sr_get_voxel_res(scene_); }
+    void VoxelGridSize(int n) { sr_check(sr_set_voxel_res(scene_, n)); }
     int gpuLastFrameParts() const { return scene_ ? sr_last_frame_parts(scene_) : 0; }   // parts (devices) that rendered rows of the last frame
 
     uint32_t BackgroundColor() const { return backgroundColor_; }

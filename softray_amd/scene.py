@@ -120,10 +120,20 @@ class GpuScene:
         """TriMeshToVoxelGrid.Convert for the current triangles (idempotent; the first voxel frame calls it itself)."""
         _check(_lib.lib().sr_build_voxels(self._h))
 
+    @property
+    def voxel_res(self):
+        """N of the N^3 voxel grid (VoxelGrid(N, ...)): 1..256, default 64 (Renderer.cs:1570).  Another value drops the grid."""
+        return int(_lib.lib().sr_get_voxel_res(self._h))
+
+    @voxel_res.setter
+    def voxel_res(self, n):
+        _check(_lib.lib().sr_set_voxel_res(self._h, int(n)))
+
     def get_voxels(self):
-        """(colors uint32 [64, 64, 64], normals float64 [64, 64, 64, 3]) of the grid, [x][y][z]; also for a host-only scene."""
-        colors = np.zeros((64, 64, 64), dtype=np.uint32)
-        normals = np.zeros((64, 64, 64, 3))
+        """(colors uint32 [N, N, N], normals float64 [N, N, N, 3]) of the grid, [x][y][z], N = voxel_res; also for a host-only scene."""
+        n = self.voxel_res
+        colors = np.zeros((n, n, n), dtype=np.uint32)
+        normals = np.zeros((n, n, n, 3))
         _check(_lib.lib().sr_get_voxels(self._h, _p(colors), _p(normals)))
         return colors, normals
 

@@ -284,7 +284,14 @@ int  sr_set_extra_geometry(sr_scene*, const sr_prim* prims, int32_t n);
 /* PreCalculate() (Renderer.cs:673-699).  modes = bit mask (1 << SR_MODE_*) of the structures to build:
  * REF_TREE: new SpatialSubdivision(geom, box, max_depth, max_per_leaf) (SpatialSubdivision.cs:267-315;
  * <=0 => the defaults 15 / 25, :269-270; SR_ERR_OUT_OF_RANGE if a vertex is outside the box);
- * BVH: the library's own BVH; BRUTE needs nothing.  Host work + H2D copies. */
+ * BVH: the library's own BVH; BRUTE needs nothing.  Host work + H2D copies.
+ * The traversal stacks live in LDS, one entry per tree level: an own BVH deeper than 62 levels (a pathological scene, e.g. a chain of
+ * triangles that halve in size towards one point; 10 M well-spread triangles give about 30) is refused with SR_ERR_UNSUPPORTED.  A
+ * refused build of the own BVH leaves the scene with NO own BVH, whatever an earlier sr_build had made (the device build has
+ * overwritten the old tree's buffers by then, and a scene never mixes two trees): sr_bvh_stats, sr_bvh_digest, sr_wide_tree_stats and
+ * SR_MODE_BVH frames / rays answer SR_ERR_NOT_BUILT, a SR_MODE_REF_TREE frame traces its shadow rays through the reference tree as on
+ * a scene that never built the BVH, SR_MODE_BRUTE and the reference tree are untouched (a REF_TREE asked for in the same call has been
+ * built).  Every part of a multi-device scene ends up in that state.  A later accepted sr_build works as on a fresh scene. */
 int  sr_build(sr_scene*, uint32_t modes, int32_t max_depth, int32_t max_per_leaf);
 /* Where the library's own BVH is built.  Default (a scene with a device, more than 64 triangles): ON THE GPU -- Morton-ordered LBVH
  * (sr_lbvh.hip) collapsed to the four-wide form the packet walks traverse, 0.01 s for 1 M and 0.08 s for 10 M triangles (host
@@ -321,9 +328,10 @@ int  sr_bvh_stats(const sr_scene*, int64_t out[4]);
 /* diagnostics: FNV-1a hashes of the host-built BVH's node array and of its leaf-ordered triangle indices (the host build must not
  * depend on the number of threads it ran on); SR_ERR_NOT_BUILT for a device-built tree */
 int  sr_bvh_digest(const sr_scene*, uint64_t out[2]);
-/* diagnostics: the four-children-per-node form of the host-built BVH that the wave-cooperative packet walks traverse (collapsed
+/* diagnostics: the four-children-per-node form of the own BVH that the wave-cooperative packet walks traverse (collapsed
  * from the binary tree: same boxes, same leaves, same leaf order): out = depth, nodes, child slots in use, leaves, triangles
- * in leaves; SR_ERR_NOT_BUILT for a device-built tree, SR_ERR_UNSUPPORTED if a link is broken */
+ * in leaves; a device-built tree's nodes are read back from the device; SR_ERR_NOT_BUILT without an own BVH, SR_ERR_UNSUPPORTED
+ * if a link is broken */
 int  sr_wide_tree_stats(const sr_scene*, int64_t out[5]);
 
 /* Renderer.Render() for one Instance, raytrace path (Renderer.cs:701-778 -> RaytraceGeometry :1501 ->

@@ -315,7 +315,9 @@ sr::DevScene dev_scene(const sr_scene* s) {
     d.v9 = (const double*)s->d_v9.p;
     // the four-wide walks stack up to three entries per level: a private walk needs (3 depth + 2) x 1 KB of LDS per workgroup, a packet
     // walk (3 depth + 2) x 528 B; a tree too deep for that is walked in its binary form (a pathological scene, not a large one:
-    // 10 M triangles give depth 14)
+    // 10 M triangles give depth 14).  Seen so far: private walks off the wide tree (b4depth >= 21) from a chain of shrinking triangles
+    // at one per leaf and from the device build's deepest accepted tree; packet walks off it (b4depth >= 41) from no tree that sr_build
+    // accepts (depth <= 62) -- a path of the binary tree collapses three levels into one -- though nothing excludes it
     const size_t lv4 = (size_t)(3 * s->b4_depth + 2);
     const bool wide_private = s->b4_num > 0 && lv4 * 1024 <= 65536, wide_packets = s->b4_num > 0 && lv4 * 528 <= 65536;
     d.b4 = wide_private ? (const sr::Bvh4Node*)s->d_b4.p : nullptr;
@@ -1267,6 +1269,17 @@ void share_host_bvh(sr_scene* d, const sr_scene* src) {
     d->bvh_on_device = false;
     d->bvh_dirty = true;
 }
+// the scene has no own BVH (any more): what sr_set_triangles leaves, and what a refused sr_build leaves (include/softray.h sr_build).
+// Nothing on the device describes a tree after this: no wide tree, no per-origin copies, no cone / interior / partition records
+void drop_bvh(sr_scene* s) {
+    s->bvh = sr::Bvh();
+    s->bvh_on_device = false;
+    s->bvh_num_nodes = 0;
+    s->bvh_dirty = true;
+    s->b4_num = 0; s->b4_depth = 0;
+    s->b4cam_valid = s->b4light_valid = false;
+    s->cam_valid = s->interior_valid = s->part_valid = false;
+}
 
 }  // namespace
 
@@ -1462,6 +1475,15 @@ int sr_build(sr_scene* s, uint32_t modes, int32_t max_depth, int32_t max_per_lea
             if (modes & (1u << SR_MODE_BVH)) if ((rc = sync_geometry(q, SR_MODE_BVH))) break;
             rc = sync_geometry(q, SR_MODE_BRUTE);
         }
+        if (rc && (modes & (1u << SR_MODE_BVH))) {
+            // a part that refused the own BVH has none left: no part keeps the tree of an earlier build (the parts render one frame together)
+            bool refused = false;
+            for (sr_scene* q : s->parts) refused = refused || !q->bvh.built;
+            if (refused) for (sr_scene* q : s->parts) drop_bvh(q);
+            // ... and the reference tree that the first part built in the same call stands, as in a scene of one device
+            if (refused && rc == SR_ERR_UNSUPPORTED && (modes & (1u << SR_MODE_REF_TREE)) && s->parts[0]->ref.built)
+                for (size_t i = 1; i < s->parts.size(); ++i) share_ref_tree(s->parts[i], s->parts[0]);
+        }
         return rc;
     }
     if (!s) return fail(SR_ERR_INVALID_ARG, "scene is NULL");
@@ -1493,6 +1515,8 @@ int sr_build(sr_scene* s, uint32_t modes, int32_t max_depth, int32_t max_per_lea
         SR_HIP(s->d_btris.reserve(n * sizeof(sr::Rec128)));
         SR_HIP(s->d_bslab.reserve(n * sizeof(sr::TriSlab)));
         int nn = 0, depth = 0;
+        if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));          // a frame in flight may still be walking the old tree
+        drop_bvh(s);                                                          // the build overwrites the old tree's buffers: from here on the scene has no tree until this one is accepted
         hipError_t e = sr::build_bvh_device((const double*)d_v9.p, (int)n, s->root, (const sr::Rec128*)s->d_tris.p, (const sr::TriSlab*)d_slab.p,
                                             (sr::BvhNode*)s->d_bnodes.p, (sr::Rec128*)s->d_btris.p, (sr::TriSlab*)s->d_bslab.p, &nn, &depth, nullptr,
                                             s->dbg[SR_DBG_BVH_LEAF] > 0 ? (int)std::min<int64_t>(15, s->dbg[SR_DBG_BVH_LEAF]) : 0);
@@ -1505,26 +1529,23 @@ int sr_build(sr_scene* s, uint32_t modes, int32_t max_depth, int32_t max_per_lea
         s->bvh_num_nodes = (size_t)nn;
         s->bvh_on_device = true;
         s->bvh_dirty = false;
-        s->cam_valid = false; s->interior_valid = false;
         {   // the four-wide tree of the packet walks, collapsed where the binary nodes are
-            if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still be walking the old tree's copies
-            s->b4cam_valid = s->b4light_valid = false;
-            s->part_valid = false;
             SR_HIP(s->d_b4.reserve((size_t)nn * sizeof(sr::Bvh4Node)));
             int n4 = 0, d4 = 0;
             e = sr::collapse_bvh4_device((const sr::BvhNode*)s->d_bnodes.p, nn, (sr::Bvh4Node*)s->d_b4.p, &n4, &d4, nullptr);
-            if (e != hipSuccess) return hip_fail(e, "collapse_bvh4_device");
+            if (e != hipSuccess) { drop_bvh(s); return hip_fail(e, "collapse_bvh4_device"); }
             s->b4_num = (size_t)n4;
             s->b4_depth = d4;
             SR_HIP(s->d_b4cam.reserve((size_t)n4 * sizeof(sr::Bvh4Node)));
             SR_HIP(s->d_b4light.reserve((size_t)n4 * sizeof(sr::Bvh4Node)));
         }
     } else if (modes & (1u << SR_MODE_BVH)) {
-        sr::build_bvh(s->v9, s->root, s->bvh, s->dbg[SR_DBG_BVH_LEAF] > 0 ? (int)std::min<int64_t>(15, s->dbg[SR_DBG_BVH_LEAF]) : 4,
+        sr::Bvh built;                                                         // moved into the scene only once it is accepted
+        sr::build_bvh(s->v9, s->root, built, s->dbg[SR_DBG_BVH_LEAF] > 0 ? (int)std::min<int64_t>(15, s->dbg[SR_DBG_BVH_LEAF]) : 4,
                       s->dbg[SR_DBG_BUILD_THREADS] > 0 ? (int)std::min<int64_t>(64, s->dbg[SR_DBG_BUILD_THREADS]) : 0);
-        if (s->bvh.depth > kMaxTreeDepth) return fail(SR_ERR_UNSUPPORTED, "BVH deeper than 62 levels does not fit the LDS traversal stacks");
-        s->bvh_on_device = false;
-        s->bvh_dirty = true;
+        drop_bvh(s);                                                           // (an earlier tree, host- or device-built, goes either way)
+        if (built.depth > kMaxTreeDepth) return fail(SR_ERR_UNSUPPORTED, "BVH deeper than 62 levels does not fit the LDS traversal stacks");
+        s->bvh = std::move(built);
     }
     if (s->device >= 0) {
         int rc = use_device(s);
@@ -1605,9 +1626,17 @@ int sr_bvh_stats(const sr_scene* s, int64_t out[4]) {
 int sr_wide_tree_stats(const sr_scene* s, int64_t out[5]) {
     if (s && !s->parts.empty()) s = s->parts[0];
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "bad argument");
-    if (!s->bvh.built || s->bvh_on_device) return fail(SR_ERR_NOT_BUILT, "no host-built BVH");
+    if (!s->bvh.built) return fail(SR_ERR_NOT_BUILT, "BVH not built");
     std::vector<sr::Bvh4Node> wide;
-    out[0] = sr::collapse_bvh4(s->bvh.nodes.data(), s->bvh.nodes.size(), wide);
+    if (s->bvh_on_device) {                                            // collapsed on the device: its nodes are read back
+        SR_HIP(hipSetDevice(s->device));
+        wide.resize(s->b4_num);
+        SR_HIP(hipDeviceSynchronize());
+        if (s->b4_num) SR_HIP(hipMemcpy(wide.data(), s->d_b4.p, s->b4_num * sizeof(sr::Bvh4Node), hipMemcpyDeviceToHost));
+        out[0] = s->b4_depth;
+    } else {
+        out[0] = sr::collapse_bvh4(s->bvh.nodes.data(), s->bvh.nodes.size(), wide);
+    }
     out[1] = (int64_t)wide.size();
     out[2] = out[3] = out[4] = 0;
     std::vector<char> linked(wide.size(), 0);

@@ -104,7 +104,7 @@ class GpuScene:
         return tuple(int(x) for x in out)
 
     def wide_tree_stats(self):
-        """(depth, nodes, child slots in use, leaves, triangles in leaves) of the four-wide form of the host-built BVH."""
+        """(depth, nodes, child slots in use, leaves, triangles in leaves) of the four-wide form of the own BVH (host- or device-built)."""
         out = np.zeros(5, dtype=np.int64)
         _check(_lib.lib().sr_wide_tree_stats(self._h, _p(out)))
         return tuple(int(x) for x in out)

@@ -75,6 +75,7 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_render_device(IntPtr scene, ref SrFrame frame, IntPtr dPixels, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern void sr_destroy(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_set_triangles(IntPtr scene, double[] v9, uint[] argb, long n, double[] boxMin, double[] boxMax);
+        [DllImport(Lib)] public static extern int sr_set_triangles_device(IntPtr scene, IntPtr dV9, IntPtr dArgb, long n, double[] boxMin, double[] boxMax, IntPtr hipStream);
         [DllImport(Lib)] public static extern int sr_set_extra_geometry(IntPtr scene, [In] SrPrim[] prims, int n);
         [DllImport(Lib)] public static extern int sr_build(IntPtr scene, uint modes, int maxDepth, int maxPerLeaf);
         [DllImport(Lib)] public static extern int sr_tree_stats(IntPtr scene, [Out] int[] out4);
@@ -224,6 +225,27 @@ namespace Engine3D.Hip
                 Native.Check(Native.sr_build(scene, bit & ~builtModes, 0, 0));                       // SpatialSubdivision defaults 15 / 25
                 builtModes |= bit;
             }
+        }
+
+        /// The triangles from DEVICE memory (sr_set_triangles_device): v9 = double[n][3][3] and argb = uint[n] on the scene's device
+        /// (of a multi-device scene: on its first device), copied and turned into records by kernels on `stream`; argb == IntPtr.Zero
+        /// keeps every triangle's colour (same n as before).  A Model is host data in the reference, so this has no counterpart there:
+        /// the scene no longer mirrors a Model afterwards (the next Upload sends its model again), and the structure of `mode` is
+        /// built by BuildStructure, not by Upload.
+        public void SetTrianglesDevice(IntPtr v9, IntPtr argb, long n, double[] min, double[] max, IntPtr stream)
+        {
+            Native.Check(Native.sr_set_triangles_device(scene, v9, argb, n, min, max, stream));
+            uploaded = null;
+            builtModes = 0;
+        }
+
+        /// sr_build for the triangles that SetTrianglesDevice left (MODE_BVH above 64 triangles is built where they are: on the device)
+        public void BuildStructure(int mode)
+        {
+            uint bit = 1u << mode;
+            if (mode == MODE_BRUTE || (builtModes & bit) == bit) return;
+            Native.Check(Native.sr_build(scene, bit, 0, 0));
+            builtModes |= bit;
         }
 
         bool UsesOwnBvh(Model model)

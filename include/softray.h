@@ -278,6 +278,24 @@ void sr_destroy(sr_scene*);
  * box = AxisAlignedBox(model.Min, model.Max) (:1487).  TriangleIndex = position in the array (:1465). */
 int  sr_set_triangles(sr_scene*, const double* v9, const uint32_t* argb, int64_t n,
                       const double box_min[3], const double box_max[3]);
+/* The same from DEVICE memory: d_v9 and d_argb are arrays on the scene's device (of a multi-device scene: on devices[0]; every part
+ * copies them to its own device), box_min / box_max are host arrays.  The arrays are COPIED (the library keeps no caller pointer) and the
+ * triangle records and the bounds of the vertices are computed by kernels (k_tri_records: the very text sr_set_triangles compiles for the
+ * host, so the records agree bit for bit), enqueued on `hip_stream` behind what is there and behind a frame of the scene in flight on
+ * any stream, which keeps the old geometry.  The call waits for the stream ONCE (it reads the six doubles of the bounds back) and makes no
+ * host copy of the geometry: that is made only when something needs the host arrays (sr_get_triangles, the reference-tree build, the
+ * host's SAH build, i.e. SR_BUILD_ON_HOST or n <= 64).  Everything sr_set_triangles drops is dropped: the trees (frames answer
+ * SR_ERR_NOT_BUILT until the next sr_build), the static-shadow, AO and light-field caches, the voxel grid.
+ * Only frames and bakes are ordered for the caller: a sr_trace_rays_device batch of this scene still in flight on ANOTHER stream is the
+ * caller's to order before this call (as before sr_build).  A HIP error after the kernels were enqueued leaves the scene without a model
+ * (SR_ERR_NO_MODEL until the next set), every part of a multi-device scene alike.
+ * d_argb == NULL: every triangle keeps its colour (a mesh that only moves; a model that sr_set_triangles / sr_load_3ds has not
+ * uploaded yet is uploaded first); allowed only when n == sr_num_triangles(scene) and the scene has a model, SR_ERR_INVALID_ARG
+ * otherwise (n == 0 needs neither array, as in sr_set_triangles).  n < 0, d_v9 == NULL with n > 0, a NULL box and n > 0x7fffff00 are
+ * SR_ERR_INVALID_ARG too, and the arguments are checked before the device is looked at: a host-only scene then answers
+ * SR_ERR_NO_DEVICE. */
+int  sr_set_triangles_device(sr_scene*, const double* d_v9, const uint32_t* d_argb, int64_t n,
+                             const double box_min[3], const double box_max[3], void* hip_stream);
 /* ExtraGeometryToRaytrace (Renderer.cs:460); n == 0 clears */
 int  sr_set_extra_geometry(sr_scene*, const sr_prim* prims, int32_t n);
 

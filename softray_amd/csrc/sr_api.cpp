@@ -84,6 +84,9 @@ struct sr_scene {
     // (part of a multi-device scene) the scene whose HOST arrays -- vertices, records, reference tree, SAH nodes and order -- this
     // part uploads from: the model lives once on the host however many devices render it
     const sr_scene* host_src = nullptr;
+    // sr_set_triangles_device: the model is on the device only -- v9, argb and tri_recs are empty (and tris_dirty is false: sync_geometry
+    // must not upload them) until a consumer of the host arrays asks for them (ensure_host_model)
+    bool host_model_stale = false;
     std::vector<sr::Rec128> tri_recs;      // geometry_simple, Renderer.cs:1452-1469
     std::vector<sr::Rec128> extra_recs;    // ExtraGeometryToRaytrace
     sr::RootBox root{};
@@ -93,6 +96,7 @@ struct sr_scene {
     size_t      bvh_num_nodes = 0;
     // device state
     DBuf d_tris, d_extra, d_rnodes, d_rboxes, d_rleaf, d_bnodes, d_btris, d_bslab, d_v9, d_bcam;
+    DBuf d_bounds;                       // sr_set_triangles_device: the bounds kernels' partials, the six doubles of the result in front
     double cam_origin[3] = {0, 0, 0};    // ray origin the camera-cone records in d_bcam (and the node order of d_b4cam) were made for
     bool   cam_valid = false;
     DBuf   d_binter;                     // interior byte of every BVH record (k_interior_flags); follows the records' positions like d_bcam
@@ -1244,6 +1248,7 @@ bool multi_splittable(const sr_frame* f) {
 void share_host_model(sr_scene* d, const sr_scene* src) {
     d->host_src = src;
     d->v9.clear(); d->argb.clear(); d->tri_recs.clear();
+    d->host_model_stale = false;
     d->ntris = src->ntris;
     for (int a = 0; a < 3; ++a) { d->bmin[a] = src->bmin[a]; d->bmax[a] = src->bmax[a]; d->vmin[a] = src->vmin[a]; d->vmax[a] = src->vmax[a]; }
     d->have_model = src->have_model;
@@ -1279,6 +1284,125 @@ void drop_bvh(sr_scene* s) {
     s->b4_num = 0; s->b4_depth = 0;
     s->b4cam_valid = s->b4light_valid = false;
     s->cam_valid = s->interior_valid = s->part_valid = false;
+}
+
+// The host arrays of a model that sr_set_triangles_device left on the device only: vertices and records are read back (the colours
+// come from the records).  Called by whatever reads s->v9 / s->argb / s->tri_recs -- the reference-tree build, the host's SAH build,
+// sr_get_triangles; a scene that is only ever built on the device and rendered never gets here.  A part of a multi-device scene
+// refills the part that holds the host arrays.
+int ensure_host_model(sr_scene* s) {
+    sr_scene* h = s->host_src ? const_cast<sr_scene*>(s->host_src) : s;
+    if (!h->host_model_stale) return SR_OK;
+    int rc = use_device(h);
+    if (rc) return rc;
+    const size_t n = h->ntris;
+    h->v9.resize(9 * n);
+    h->tri_recs.resize(n);
+    h->argb.resize(n);
+    if (n) {
+        SR_HIP(hipMemcpy(h->v9.data(), h->d_v9.p, 9 * n * sizeof(double), hipMemcpyDeviceToHost));
+        SR_HIP(hipMemcpy(h->tri_recs.data(), h->d_tris.p, n * sizeof(sr::Rec128), hipMemcpyDeviceToHost));
+    }
+    for (size_t i = 0; i < n; ++i) h->argb[i] = h->tri_recs[i].color;
+    h->host_model_stale = false;
+    if (h != s && s->device >= 0) SR_HIP(hipSetDevice(s->device));
+    return SR_OK;
+}
+
+// sr_set_triangles_device for one scene with a device.  src_*: arrays on device `src_device`; `copy_first`: they are copied to this
+// scene's device before the kernels read them (a part of a multi-device scene other than the first; a peer copy also when the
+// ordinals are equal).  `stream` belongs to this scene's device.
+int set_triangles_from_device_enqueue(sr_scene* s, const double* src_v9, const uint32_t* src_argb, int64_t n, const double box_min[3],
+                                      const double box_max[3], hipStream_t stream, int src_device, bool copy_first) {
+    int rc = SR_OK;
+    DBuf tmp_v9, tmp_argb;
+    struct Free { DBuf* b[2]; ~Free() { for (DBuf* x : b) x->release(); } } free_tmp{{&tmp_v9, &tmp_argb}};
+    if (copy_first && n > 0) {
+        SR_HIP(tmp_v9.reserve((size_t)n * 9 * sizeof(double)));
+        SR_HIP(hipMemcpyPeerAsync(tmp_v9.p, s->device, src_v9, src_device, (size_t)n * 9 * sizeof(double), stream));
+        src_v9 = (const double*)tmp_v9.p;
+        if (src_argb) {
+            SR_HIP(tmp_argb.reserve((size_t)n * sizeof(uint32_t)));
+            SR_HIP(hipMemcpyPeerAsync(tmp_argb.p, s->device, src_argb, src_device, (size_t)n * sizeof(uint32_t), stream));
+            src_argb = (const uint32_t*)tmp_argb.p;
+        }
+    }
+    double bounds[6];
+    for (int a = 0; a < 3; ++a) { bounds[a] = box_min[a]; bounds[3 + a] = box_max[a]; }
+    if (n > 0) {
+        const size_t rec_bytes = (size_t)n * sizeof(sr::Rec128), v9_bytes = (size_t)n * 9 * sizeof(double);
+        // a frame in flight keeps the old geometry: the kernels below run behind it (its event, waited for by the STREAM); only buffers
+        // that have to grow are freed, and those the host waits for
+        if (s->pre_used_set) {
+            if (rec_bytes > s->d_tris.cap || v9_bytes > s->d_v9.cap) SR_HIP(hipEventSynchronize(s->pre_used));
+            SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
+        }
+        SR_HIP(s->d_tris.reserve(rec_bytes));
+        SR_HIP(s->d_v9.reserve(v9_bytes));
+        SR_HIP(s->d_bounds.reserve(sr::tri_bounds_scratch_bytes()));
+        hipEvent_t e0, e1;
+        if ((rc = next_events(s, sr::K_TRI_RECORDS, e0, e1))) return rc;
+        if (e0) SR_HIP(hipEventRecord(e0, stream));
+        SR_HIP(sr::tri_records_device(src_v9, src_argb, (int)n, (double*)s->d_v9.p, (sr::Rec128*)s->d_tris.p, stream));
+        if (e1) SR_HIP(hipEventRecord(e1, stream));
+        if ((rc = next_events(s, sr::K_TRI_BOUNDS, e0, e1))) return rc;
+        if (e0) SR_HIP(hipEventRecord(e0, stream));
+        SR_HIP(sr::tri_bounds_device((const double*)s->d_v9.p, (int)n, box_min, box_max, (double*)s->d_bounds.p, stream));
+        if (e1) SR_HIP(hipEventRecord(e1, stream));
+        SR_HIP(hipMemcpyAsync(bounds, s->d_bounds.p, sizeof(bounds), hipMemcpyDeviceToHost, stream));
+        SR_HIP(hipStreamSynchronize(stream));                          // the call's one host wait: the six doubles (and the temporaries are freed on return)
+    }
+    s->shadow_cache_empty = true;                         // a new model: what sr_set_triangles drops
+    s->ao_cache_empty = true; s->ao_cache_host.clear();
+    s->lf_cache_empty = true; s->lf_cache_host.clear();
+    s->vox_valid = false;
+    std::vector<double>().swap(s->v9);
+    std::vector<uint32_t>().swap(s->argb);
+    std::vector<sr::Rec128>().swap(s->tri_recs);
+    s->host_src = nullptr;
+    s->host_model_stale = true;
+    for (int a = 0; a < 3; ++a) { s->bmin[a] = box_min[a]; s->bmax[a] = box_max[a]; s->vmin[a] = bounds[a]; s->vmax[a] = bounds[3 + a]; }
+    s->root = sr::make_root_box(box_min, box_max);
+    s->ntris = (size_t)n;
+    s->have_model = true;
+    s->ref = sr::RefTree();
+    s->ref_dirty = true;
+    drop_bvh(s);
+    s->tris_dirty = false;                                // the device arrays ARE the model: nothing to upload
+    return SR_OK;
+}
+
+// the scene has no model (any more): what a device set that failed half way leaves -- its kernels may have overwritten or reallocated
+// the device arrays while the host state still described the old model, which is gone either way
+void drop_model(sr_scene* s) {
+    std::vector<double>().swap(s->v9);
+    std::vector<uint32_t>().swap(s->argb);
+    std::vector<sr::Rec128>().swap(s->tri_recs);
+    s->host_src = nullptr;
+    s->host_model_stale = false;
+    s->have_model = false;
+    s->ntris = 0;
+    s->ref = sr::RefTree();
+    s->ref_dirty = true;
+    drop_bvh(s);
+    s->shadow_cache_empty = s->ao_cache_empty = s->lf_cache_empty = true;
+    s->vox_valid = false;
+    s->tris_dirty = true;
+}
+
+int set_triangles_from_device(sr_scene* s, const double* src_v9, const uint32_t* src_argb, int64_t n, const double box_min[3],
+                              const double box_max[3], hipStream_t stream, int src_device, bool copy_first) {
+    int rc = use_device(s);                               // (a scene without a device is refused with nothing changed)
+    if (rc) return rc;
+    rc = set_triangles_from_device_enqueue(s, src_v9, src_argb, n, box_min, box_max, stream, src_device, copy_first);
+    if (rc) {
+        const std::string why = g_err;
+        (void)hipStreamSynchronize(stream);               // nothing of the failed call is left running on the arrays
+        (void)hipGetLastError();
+        drop_model(s);
+        g_err = why;
+    }
+    return rc;
 }
 
 }  // namespace
@@ -1360,7 +1484,7 @@ void sr_destroy(sr_scene* s) {
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
                         &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
-                        &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse};
+                        &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse, &s->d_bounds};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
         for (auto& t : s->tables) { t.dev.release(); if (t.host) (void)hipHostFree(t.host); if (t.used) (void)hipEventDestroy(t.used); if (t.ready) (void)hipEventDestroy(t.ready); }
@@ -1395,6 +1519,7 @@ int sr_set_triangles(sr_scene* s, const double* v9, const uint32_t* argb, int64_
     s->ao_cache_empty = true; s->ao_cache_host.clear();   // ... and a new AmbientOcclusion
     s->lf_cache_empty = true; s->lf_cache_host.clear();   // ... and a new LightFieldColorMethod
     s->vox_valid = false;                                 // ... and a new VoxelGrid
+    s->host_model_stale = false;
     s->v9.assign(v9, v9 + 9 * n);
     s->argb.assign(argb, argb + n);
     for (int a = 0; a < 3; ++a) { s->bmin[a] = box_min[a]; s->bmax[a] = box_max[a]; }
@@ -1414,6 +1539,41 @@ int sr_set_triangles(sr_scene* s, const double* v9, const uint32_t* argb, int64_
     s->bvh_on_device = false;
     s->tris_dirty = s->ref_dirty = s->bvh_dirty = true;
     return SR_OK;
+}
+
+int sr_set_triangles_device(sr_scene* s, const double* d_v9, const uint32_t* d_argb, int64_t n, const double box_min[3], const double box_max[3],
+                            void* hip_stream) {
+    if (!s || n < 0 || (n > 0 && !d_v9) || !box_min || !box_max) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_triangles_device");
+    if (n > 0x7fffff00) return fail(SR_ERR_INVALID_ARG, "too many triangles");
+    sr_scene* first = s->parts.empty() ? s : s->parts[0];
+    if (n > 0 && !d_argb && (!first->have_model || (int64_t)first->ntris != n))      // (n == 0 needs no array, as in sr_set_triangles)
+        return fail(SR_ERR_INVALID_ARG, "sr_set_triangles_device without colours needs a model of the same number of triangles");
+    // keep-colours reads the colours out of the device records: a model that sr_set_triangles / sr_load_3ds left on the host only (the
+    // upload waits for the next sr_build or frame) is uploaded first -- by every part, before the first part's host arrays are dropped
+    if (!d_argb && n > 0) {
+        std::vector<sr_scene*> one{s};
+        for (sr_scene* q : s->parts.empty() ? one : s->parts) {
+            if (!q->tris_dirty) continue;
+            int rc = use_device(q);
+            if (rc) return rc;
+            if (q->pre_used_set) SR_HIP(hipEventSynchronize(q->pre_used));   // (the upload may free the arrays a frame in flight reads)
+            if ((rc = sync_geometry(q, SR_MODE_BRUTE))) return rc;
+        }
+    }
+    if (s->parts.empty()) return set_triangles_from_device(s, d_v9, d_argb, n, box_min, box_max, (hipStream_t)hip_stream, s->device, false);
+    // the arrays live on the first part's device: it takes them on the caller's stream (and waits for it: they are complete then);
+    // every other part copies them to its own device and makes its own records
+    int rc = set_triangles_from_device(first, d_v9, d_argb, n, box_min, box_max, (hipStream_t)hip_stream, first->device, false);
+    for (size_t i = 1; i < s->parts.size() && !rc; ++i) {
+        rc = set_triangles_from_device(s->parts[i], d_v9, d_argb, n, box_min, box_max, nullptr, first->device, true);
+        if (!rc) s->parts[i]->host_src = first;                  // the host arrays, once something asks for them, live with the first part
+    }
+    if (rc) {                                                    // no part keeps a model the others do not have
+        const std::string why = g_err;
+        for (sr_scene* q : s->parts) drop_model(q);
+        g_err = why;
+    }
+    return rc;
 }
 
 int sr_set_extra_geometry(sr_scene* s, const sr_prim* prims, int32_t n) {
@@ -1491,6 +1651,12 @@ int sr_build(sr_scene* s, uint32_t modes, int32_t max_depth, int32_t max_per_lea
     // leaves are packed as (first record | count << 27) and traversal stack words as (node | bound << bits): 2^28 records / 2^26 nodes
     if ((modes & (1u << SR_MODE_BVH)) && s->ntris >= (1u << 26))
         return fail(SR_ERR_UNSUPPORTED, "the library's BVH holds at most 2^26 - 1 triangles");
+    const bool on_device = s->device >= 0 && !(modes & SR_BUILD_ON_HOST) && s->ntris > 64;
+    // the reference tree and the SAH tree are built by the host from the host arrays: a model set from device memory is read back first
+    if ((modes & (1u << SR_MODE_REF_TREE)) || ((modes & (1u << SR_MODE_BVH)) && !on_device)) {
+        int rc = ensure_host_model(s);
+        if (rc) return rc;
+    }
     if (modes & (1u << SR_MODE_REF_TREE)) {
         int md = max_depth > 0 ? max_depth : 15, mg = max_per_leaf > 0 ? max_per_leaf : 25;   // SpatialSubdivision.cs:269-270
         if (!sr::build_ref_tree(s->v9, s->bmin, s->bmax, md, mg, s->ref))
@@ -1500,7 +1666,6 @@ int sr_build(sr_scene* s, uint32_t modes, int32_t max_depth, int32_t max_per_lea
     // the own BVH is built where the triangles are: on the device (LBVH, sr_lbvh.hip), unless the scene has none, is tiny, or the
     // caller asks for the host's binned-SAH builder (SR_BUILD_ON_HOST)
     if ((modes & SR_BUILD_ON_DEVICE) && s->device < 0) return fail(SR_ERR_NO_DEVICE, "SR_BUILD_ON_DEVICE needs a HIP device");
-    const bool on_device = s->device >= 0 && !(modes & SR_BUILD_ON_HOST) && s->ntris > 64;
     if ((modes & (1u << SR_MODE_BVH)) && on_device) {
         // ---- LBVH built by the GPU (sr_lbvh.hip) ----
         int rc = use_device(s);
@@ -2343,6 +2508,7 @@ int64_t sr_num_triangles(const sr_scene* s) { if (s && !s->parts.empty()) s = s-
 int sr_get_triangles(const sr_scene* s, double* v9, uint32_t* argb, double box_min[3], double box_max[3]) {
     if (s && !s->parts.empty()) s = s->parts[0];
     if (!s || !s->have_model) return fail(SR_ERR_NO_MODEL, "no model");
+    if (v9 || argb) { int rc = ensure_host_model(const_cast<sr_scene*>(s)); if (rc) return rc; }
     if (v9) std::memcpy(v9, s->v9.data(), s->v9.size() * sizeof(double));
     if (argb) std::memcpy(argb, s->argb.data(), s->argb.size() * sizeof(uint32_t));
     for (int a = 0; a < 3; ++a) { if (box_min) box_min[a] = s->bmin[a]; if (box_max) box_max[a] = s->bmax[a]; }

@@ -41,7 +41,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_COUNT = 23 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_COUNT = 25 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -216,6 +216,13 @@ hipError_t collapse_bvh4_device(const BvhNode* d_nodes, int num_nodes, Bvh4Node*
 
 // fp32 TriSlab records of n triangles (TriangleIndex order) computed on the device from the FP64 vertices (sr_lbvh.hip)
 hipError_t make_slabs_device(const double* d_v9, int n, const RootBox& root, TriSlab* d_out, hipStream_t stream);
+
+// sr_set_triangles_device (sr_lbvh.hip): the scene's vertex and record arrays (TriangleIndex order, n entries each) from the caller's
+// device arrays -- d_src_argb == nullptr keeps the colour of the record that is in d_tris -- and the bounds of the vertices folded
+// with the caller's box: six doubles {vmin, vmax} at the start of d_scratch (tri_bounds_scratch_bytes() bytes)
+hipError_t tri_records_device(const double* d_src_v9, const uint32_t* d_src_argb, int n, double* d_v9, Rec128* d_tris, hipStream_t stream);
+size_t tri_bounds_scratch_bytes();
+hipError_t tri_bounds_device(const double* d_v9, int n, const double box_min[3], const double box_max[3], double* d_scratch, hipStream_t stream);
 
 // Surface passes (sr_post.hip): PostProcessImage colour functions and AntiAliasImage, Renderer.cs:819-978.
 hipError_t launch_post_process(uint32_t* d_pixels, long long count, int style, uint32_t background, int num_cus, hipStream_t stream);

@@ -79,20 +79,8 @@ double NetRandom::next_double() { return sample() * (1.0 / 2147483647); }
 // primitive records
 // ------------------------------------------------------------------------------------------------
 Rec128 make_triangle_record(Vec3 v1, Vec3 v2, Vec3 v3, uint32_t color, int32_t aux) {
-    Rec128 r;
-    Vec3 e1 = sub(v2, v1), e2 = sub(v3, v1);
-    Vec3 n = cross(e1, e2);
-    if (is_zero_vector(n)) n = {1, 0, 0};                   // Triangle.cs:42-43
-    Vec3 un = unit(n);                                      // Plane ctor, Plane.cs:25-27
-    double d = dot(v1, un);
-    Vec3 e1p = cross(e1, n), e2p = cross(e2, n);            // with the UN-normalised normal, Triangle.cs:49-50
-    r.p[0] = un.x; r.p[1] = un.y; r.p[2] = un.z; r.p[3] = d;
-    r.p[4] = v1.x; r.p[5] = v1.y; r.p[6] = v1.z;
-    r.p[7] = e2p.x; r.p[8] = e2p.y; r.p[9] = e2p.z; r.p[10] = dot(e1, e2p);   // Triangle.cs:91
-    r.p[11] = e1p.x; r.p[12] = e1p.y; r.p[13] = e1p.z; r.p[14] = dot(e2, e1p); // Triangle.cs:96
-    r.color = color;
-    r.aux = aux;
-    return r;
+    const double v[9] = {v1.x, v1.y, v1.z, v2.x, v2.y, v2.z, v3.x, v3.y, v3.z};
+    return triangle_record(v, color, aux);                  // sr_types.h: the text the device compiles too
 }
 Rec128 make_sphere_record(Vec3 c, double radius, uint32_t color) {
     Rec128 r;

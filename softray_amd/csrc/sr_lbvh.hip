@@ -226,6 +226,64 @@ __global__ void k_make_slabs(const double* __restrict__ v9, int n, double cx, do
     out[i] = ok ? t : zero;
 }
 
+// ---- sr_set_triangles_device: the model's two TriangleIndex-order arrays made on the device from the caller's device arrays ----
+// One lane per triangle: the caller's 72 bytes go into the scene's vertex array (the device-to-device copy, fused) and the
+// 128-byte FP64 record -- sr_types.h triangle_record, the text the host compiles for sr_set_triangles -- into the record array.
+// src_argb == nullptr: the triangle keeps the colour of the record that is there (a mesh that only moves).
+__global__ void __launch_bounds__(256) k_tri_records(const double* __restrict__ src_v9, const uint32_t* __restrict__ src_argb, int n,
+                                                     double* __restrict__ dst_v9, Rec128* dst_tris) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n) return;
+    double v[9];
+    for (int k = 0; k < 9; ++k) v[k] = src_v9[i * 9 + k];
+    const uint32_t color = src_argb ? src_argb[i] : dst_tris[i].color;
+    for (int k = 0; k < 9; ++k) dst_v9[i * 9 + k] = v[k];
+    dst_tris[i] = triangle_record(v, color, (int32_t)i);
+}
+
+// min / max over the lanes of a wave, then over the waves of the workgroup (LDS); the result is valid in thread 0
+constexpr int kBoundsThreads = 256, kBoundsMaxBlocks = 1024;
+__device__ __forceinline__ void block_minmax(double lo[3], double hi[3], double (*sh)[6]) {
+    for (int off = 32; off >= 1; off >>= 1)
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fmin(lo[a], __shfl_xor(lo[a], off));
+            hi[a] = fmax(hi[a], __shfl_xor(hi[a], off));
+        }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int a = 0; a < 3; ++a) { sh[wave][a] = lo[a]; sh[wave][3 + a] = hi[a]; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < kBoundsThreads / 64; ++w)
+            for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], sh[w][a]); hi[a] = fmax(hi[a], sh[w][3 + a]); }
+}
+
+// bounds of the vertices, step 1: every workgroup strides over the vertices and leaves its min / max in partials[block][6]
+// (no atomics: DESIGN.md 10)
+__global__ void __launch_bounds__(kBoundsThreads) k_tri_bounds(const double* __restrict__ v9, long long nverts, double* __restrict__ partials) {
+    __shared__ double sh[kBoundsThreads / 64][6];
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < nverts; j += stride)
+        for (int a = 0; a < 3; ++a) { const double x = v9[j * 3 + a]; lo[a] = fmin(lo[a], x); hi[a] = fmax(hi[a], x); }
+    block_minmax(lo, hi, sh);
+    if (threadIdx.x == 0)
+        for (int a = 0; a < 3; ++a) { partials[(size_t)blockIdx.x * 6 + a] = lo[a]; partials[(size_t)blockIdx.x * 6 + 3 + a] = hi[a]; }
+}
+
+// step 2, one workgroup: the partials and the caller's box folded into out[6] = {vmin, vmax}, what the host loop of
+// sr_set_triangles leaves (min / max do not depend on the order for finite input)
+struct Box6 { double v[6]; };
+__global__ void __launch_bounds__(kBoundsThreads) k_tri_bounds_fold(const double* __restrict__ partials, int nparts, Box6 box, double* __restrict__ out) {
+    __shared__ double sh[kBoundsThreads / 64][6];
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int j = threadIdx.x; j < nparts; j += kBoundsThreads)
+        for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], partials[(size_t)j * 6 + a]); hi[a] = fmax(hi[a], partials[(size_t)j * 6 + 3 + a]); }
+    block_minmax(lo, hi, sh);
+    if (threadIdx.x == 0)
+        for (int a = 0; a < 3; ++a) { out[a] = fmin(box.v[a], lo[a]); out[3 + a] = fmax(box.v[3 + a], hi[a]); }
+}
+
 // ---- the four-wide tree of the packet walks, collapsed on the device (same rule as sr_host.cpp collapse_bvh4: a node takes its two
 //      children and, while it has fewer than four, replaces the inner child with the largest box by that child's two children) ----
 // One launch per level of the wide tree: every item (binary node, wide-node slot) writes its wide node and appends its inner
@@ -316,6 +374,26 @@ hipError_t collapse_bvh4_device(const BvhNode* d_nodes, int num_nodes, Bvh4Node*
 hipError_t make_slabs_device(const double* d_v9, int n, const RootBox& root, TriSlab* d_out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_make_slabs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_v9, n, root.centre[0], root.centre[1], root.centre[2], d_out);
+    return hipGetLastError();
+}
+
+size_t tri_bounds_scratch_bytes() { return ((size_t)kBoundsMaxBlocks * 6 + 6) * sizeof(double); }
+
+hipError_t tri_records_device(const double* d_src_v9, const uint32_t* d_src_argb, int n, double* d_v9, Rec128* d_tris, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_tri_records, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, stream, d_src_v9, d_src_argb, n, d_v9, d_tris);
+    return hipGetLastError();
+}
+
+// d_scratch: tri_bounds_scratch_bytes(); the six doubles {vmin, vmax} are left in its first 48 bytes
+hipError_t tri_bounds_device(const double* d_v9, int n, const double box_min[3], const double box_max[3], double* d_scratch, hipStream_t stream) {
+    const long long nverts = (long long)n * 3;
+    const int blocks = (int)std::min<long long>(kBoundsMaxBlocks, std::max<long long>(1, (nverts + kBoundsThreads - 1) / kBoundsThreads));
+    Box6 box;
+    for (int a = 0; a < 3; ++a) { box.v[a] = box_min[a]; box.v[3 + a] = box_max[a]; }
+    hipLaunchKernelGGL(k_tri_bounds, dim3(blocks), dim3(kBoundsThreads), 0, stream, d_v9, nverts, d_scratch + 6);
+    LB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_tri_bounds_fold, dim3(1), dim3(kBoundsThreads), 0, stream, (const double*)(d_scratch + 6), blocks, box, d_scratch);
     return hipGetLastError();
 }
 

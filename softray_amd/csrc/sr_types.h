@@ -1,7 +1,15 @@
 // sr_types.h -- records shared by the host scene builder and the gfx950 kernels.
 // Layouts are the HBM layouts described in DESIGN.md ("Data layout in HBM").
 #pragma once
+#include <math.h>
 #include <stdint.h>
+
+// functions that the host scene builder and the gfx950 kernels compile from the same text (both with -ffp-contract=off)
+#if defined(__HIPCC__)
+#define SR_HOST_DEVICE __host__ __device__
+#else
+#define SR_HOST_DEVICE
+#endif
 
 namespace sr {
 
@@ -21,6 +29,31 @@ struct alignas(16) Rec128 {
     int32_t  aux;
 };
 static_assert(sizeof(Rec128) == 128, "Rec128 must be 128 bytes");
+
+// The triangle record of v = {v1, v2, v3} (Triangle.cs:29-57): sr_set_triangles computes it on the host, k_tri_records
+// (sr_lbvh.hip, sr_set_triangles_device) on the device, and the two must agree bit for bit -- one text, no contraction, FP64
+// + - * / sqrt correctly rounded on both sides.  Every expression keeps the reference's operand order (Engine3D/Vector.cs).
+SR_HOST_DEVICE inline Rec128 triangle_record(const double v[9], uint32_t color, int32_t aux) {
+    Rec128 r;
+    const double e1x = v[3] - v[0], e1y = v[4] - v[1], e1z = v[5] - v[2];             // edge1 = v2 - v1
+    const double e2x = v[6] - v[0], e2y = v[7] - v[1], e2z = v[8] - v[2];             // edge2 = v3 - v1
+    double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;   // Vector.cs:104
+    const double e = 1e-10;                                                           // Vector.IsZeroVector, Vector.cs:140
+    if (-e < nx && nx < e && -e < ny && ny < e && -e < nz && nz < e) { nx = 1; ny = 0; nz = 0; }   // Triangle.cs:42-43
+    const double len = sqrt(nx * nx + ny * ny + nz * nz);                             // Vector.cs:177-185 (Plane ctor, Plane.cs:25-27)
+    const double inv = 1.0 / len;
+    const double ux = nx * inv, uy = ny * inv, uz = nz * inv;
+    // the edge perpendiculars with the UN-normalised normal, Triangle.cs:49-50
+    const double p1x = e1y * nz - e1z * ny, p1y = e1z * nx - e1x * nz, p1z = e1x * ny - e1y * nx;   // edge1 x n
+    const double p2x = e2y * nz - e2z * ny, p2y = e2z * nx - e2x * nz, p2z = e2x * ny - e2y * nx;   // edge2 x n
+    r.p[0] = ux; r.p[1] = uy; r.p[2] = uz; r.p[3] = v[0] * ux + v[1] * uy + v[2] * uz;
+    r.p[4] = v[0]; r.p[5] = v[1]; r.p[6] = v[2];
+    r.p[7] = p2x; r.p[8] = p2y; r.p[9] = p2z; r.p[10] = e1x * p2x + e1y * p2y + e1z * p2z;          // Triangle.cs:91
+    r.p[11] = p1x; r.p[12] = p1y; r.p[13] = p1z; r.p[14] = e2x * p1x + e2y * p1y + e2z * p1z;       // Triangle.cs:96
+    r.color = color;
+    r.aux = aux;
+    return r;
+}
 
 // Reference tree node (SpatialSubdivision.Node flattened, SpatialSubdivision.cs:22-46), 32 B.
 //   internal: axis 0..2, split = splittingPlane.DistanceToOrigin, a = normalSide index, b = backSide index

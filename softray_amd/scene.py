@@ -62,6 +62,41 @@ class GpuScene:
         bmax = np.ascontiguousarray(bmax, dtype=np.float64)
         _check(_lib.lib().sr_set_triangles(self._h, _p(v9), _p(argb), v9.shape[0], _p(bmin), _p(bmax)))
 
+    def set_triangles_device(self, v9, argb, bmin, bmax, stream=0, n=None):
+        """sr_set_triangles_device: the model from DEVICE memory, copied and turned into records by kernels on `stream` (a raw
+        hipStream_t or a torch.cuda.Stream); no host copy of the geometry is made.  v9: a contiguous float64 torch tensor [n, 3, 3] on
+        the scene's device, or a raw device pointer with `n`; argb: an int32 / uint32 tensor [n] (or pointer), None = every triangle
+        keeps its colour (same n as the current model).  bmin / bmax are host values."""
+        def device_array(x, what, dtypes, shape_ok):
+            if x is None:
+                return None, None
+            if isinstance(x, int):
+                if n is None:
+                    raise ValueError("%s is a raw device pointer: n is needed" % what)
+                return x, int(n)
+            if not (hasattr(x, "data_ptr") and hasattr(x, "is_cuda")):
+                raise ValueError("%s must be a torch tensor on the scene's device or a raw device pointer" % what)
+            if not x.is_cuda or x.device.index != self.device:
+                raise ValueError("%s is on %s, the scene on device %d" % (what, x.device, self.device))
+            if str(x.dtype).replace("torch.", "") not in dtypes:
+                raise ValueError("%s must be %s, not %s" % (what, " / ".join(dtypes), x.dtype))
+            if not shape_ok(tuple(x.shape)) or not x.is_contiguous():
+                raise ValueError("%s has shape %s%s" % (what, tuple(x.shape), "" if x.is_contiguous() else " and is not contiguous"))
+            return x.data_ptr(), int(x.shape[0])
+        pv, nv = device_array(v9, "v9", ("float64",), lambda s: len(s) == 3 and s[1:] == (3, 3))
+        if nv is None:
+            raise ValueError("v9 is needed")
+        pa, na = device_array(argb, "argb", ("int32", "uint32"), lambda s: len(s) == 1)
+        if na is not None and na != nv:
+            raise ValueError("argb has %d entries for %d triangles" % (na, nv))
+        bmin = np.ascontiguousarray(bmin, dtype=np.float64)
+        bmax = np.ascontiguousarray(bmax, dtype=np.float64)
+        if bmin.size != 3 or bmax.size != 3:
+            raise ValueError("bmin and bmax are three doubles each")
+        st = getattr(stream, "cuda_stream", stream)
+        _check(_lib.lib().sr_set_triangles_device(self._h, C.c_void_p(pv) if pv else None, C.c_void_p(pa) if pa else None, nv,
+                                                  _p(bmin), _p(bmax), C.c_void_p(st) if st else None))
+
     def load_3ds(self, data):
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
         _check(_lib.lib().sr_load_3ds(self._h, _p(buf), buf.size))

@@ -275,7 +275,12 @@ void sr_destroy(sr_scene*);
 
 /* MakeRayTracableGeometry_simple (Renderer.cs:1452-1469): v9 = [n][3 vertices][xyz] in model space
  * (after Model.PostProcessGeometry), argb[n] = Surface.PackColorAndAlpha(diffuse, 1.0) (:1463),
- * box = AxisAlignedBox(model.Min, model.Max) (:1487).  TriangleIndex = position in the array (:1465). */
+ * box = AxisAlignedBox(model.Min, model.Max) (:1487).  TriangleIndex = position in the array (:1465).
+ * The box may lie anywhere and need not be the vertex bounds: frames are the reference's bit for bit while |box centre| <= 1e6 x the
+ * box's largest extent (beyond that the noise of the reference's FP64 arithmetic on absolute coordinates is no longer covered by the
+ * margins of the fp32 shadow classification; tests/test_gpu_placement.py renders at 6e4 and at 2.5e5).
+ * The features the reference defines over the unit cube assume the normalised model of Model.PostProcessGeometry (box [-0.5, 0.5]^3
+ * about the origin): the static-shadow and ambient-occlusion caches, the light field's 0.866 sphere and the voxel grid's k / N - 0.5 planes. */
 int  sr_set_triangles(sr_scene*, const double* v9, const uint32_t* argb, int64_t n,
                       const double box_min[3], const double box_max[3]);
 /* The same from DEVICE memory: d_v9 and d_argb are arrays on the scene's device (of a multi-device scene: on devices[0]; every part

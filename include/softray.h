@@ -554,7 +554,8 @@ enum {
                                     computes the per-sample box exits for every hit point (no shortcut for candidate lists whose triangles all lie
                                     inside the root box); 94 production path, and a frame rendered with ray statistics leaves the census of that
                                     shortcut in statistics [22] (hit points classified with the shortcut) and [23] (with the per-sample box exits)
-                                    instead of the mirror rays' figures; 95 = 93 and 94 together; 41 a voxel walk on a grid of at most 64 reads the
+                                    instead of the mirror rays' figures; 95 = 93 and 94 together; 96 the packet shaft walk filters its triangles with the
+                                    TriSlab records (shaft_touches_wave) instead of the per-light penumbra planes (LightCone); 41 a voxel walk on a grid of at most 64 reads the
                                     colour table instead of the occupancy bits in LDS; 42 a voxel walk on a grid above 64 reads the row-major
                                     occupancy bits in global memory, one level, instead of the two-level walk                              */
     SR_DBG_KERNEL_TIMING  = 7,   /* > 0: record a HIP event pair around every launch (sr_kernel_times); default off           */

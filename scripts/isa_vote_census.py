@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "softray_amd", "csrc")
 KERNELS = ("k_shaft_pkt4", "k_primary", "k_shadow_cls_g")
 # the instantiations the default frames run (every KNOWN subset of the light / both forms of the camera-ordered copy): listed pair by pair
-HEADLINE = re.compile(r"^(k_shaft_pkt4<false, 6, true, \d>|k_primary<2, false, false, false, [23], false>|k_shadow_cls_g<false, false>)$")
+HEADLINE = re.compile(r"^(k_shaft_pkt4<false, 6, true, \d(?:, (?:true|false))?>|k_primary<2, false, false, false, [23], false>|k_shadow_cls_g<false, false>)$")
 
 
 def makefile_flags():

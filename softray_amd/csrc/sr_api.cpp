@@ -99,6 +99,11 @@ struct sr_scene {
     DBuf d_bounds;                       // sr_set_triangles_device: the bounds kernels' partials, the six doubles of the result in front
     double cam_origin[3] = {0, 0, 0};    // ray origin the camera-cone records in d_bcam (and the node order of d_b4cam) were made for
     bool   cam_valid = false;
+    // penumbra-plane records of the packet shaft walk (k_light_cones): made for one (tree, record order, light ball); like d_bcam they follow
+    // the records' positions, so they are invalidated wherever cam_valid and b4light_valid are
+    DBuf   d_blight;
+    bool   blight_valid = false;
+    double blight_pos[3] = {0, 0, 0}, blight_radius = 0;
     DBuf   d_binter;                     // interior byte of every BVH record (k_interior_flags); follows the records' positions like d_bcam
     bool   interior_valid = false;
     // four-wide tree of the packet walks: build-order nodes + the two per-frame ordered copies (camera origin / point light)
@@ -263,6 +268,7 @@ int upload_wide_tree(sr_scene* s, const sr::BvhNode* nodes, size_t num_nodes) {
     s->b4_depth = sr::collapse_bvh4(nodes, num_nodes, wide);
     s->b4_num = wide.size();
     s->b4cam_valid = s->b4light_valid = false;
+    s->blight_valid = false;
     s->part_valid = false;
     if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still be walking the old tree's copies
     SR_HIP(s->d_b4.upload(wide));
@@ -273,7 +279,7 @@ int upload_wide_tree(sr_scene* s, const sr::BvhNode* nodes, size_t num_nodes) {
 
 int sync_geometry(sr_scene* s, uint32_t need_mode) {
     const sr_scene* h = s->host_src ? s->host_src : s;              // where the host arrays are
-    if (s->tris_dirty) { SR_HIP(s->d_tris.upload(h->tri_recs)); SR_HIP(s->d_v9.upload(h->v9)); s->tris_dirty = false; s->cam_valid = false; s->interior_valid = false; }
+    if (s->tris_dirty) { SR_HIP(s->d_tris.upload(h->tri_recs)); SR_HIP(s->d_v9.upload(h->v9)); s->tris_dirty = false; s->cam_valid = false; s->blight_valid = false; s->interior_valid = false; }
     if (s->extra_dirty) { SR_HIP(s->d_extra.upload(s->extra_recs)); s->extra_dirty = false; }
     if (need_mode == SR_MODE_REF_TREE && s->ref_dirty) {
         SR_HIP(s->d_rnodes.upload(h->ref.nodes));
@@ -299,7 +305,7 @@ int sync_geometry(sr_scene* s, uint32_t need_mode) {
         d_slab.release();
         s->bvh_num_nodes = h->bvh.nodes.size();
         s->bvh_dirty = false;
-        s->cam_valid = false; s->interior_valid = false;
+        s->cam_valid = false; s->blight_valid = false; s->interior_valid = false;
         int rc = upload_wide_tree(s, h->bvh.nodes.data(), h->bvh.nodes.size());
         if (rc) return rc;
     }
@@ -316,6 +322,7 @@ sr::DevScene dev_scene(const sr_scene* s) {
     d.bslab = (const sr::TriSlab*)s->d_bslab.p;
     d.binter = (const uint8_t*)s->d_binter.p;
     d.bcam = s->cam_valid ? (const sr::CamCone*)s->d_bcam.p : nullptr;
+    d.blight = s->blight_valid ? (const sr::LightCone*)s->d_blight.p : nullptr;
     d.v9 = (const double*)s->d_v9.p;
     // the four-wide walks stack up to three entries per level: a private walk needs (3 depth + 2) x 1 KB of LDS per workgroup, a packet
     // walk (3 depth + 2) x 528 B; a tree too deep for that is walked in its binary form (a pathological scene, not a large one:
@@ -811,6 +818,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             rewrote = true;
             s->part_valid = false;
             s->cam_valid = false; s->b4cam_valid = false; s->b4light_valid = false;      // the records move: cone records and both copies are re-made
+            s->blight_valid = false;
             s->interior_valid = false;                                                   // ... and the interior bytes
             SR_HIP(sr::launch_facing_partition((const sr::Bvh4Node*)s->d_b4.p, (int)s->b4_num, (sr::Rec128*)s->d_btris.p, (sr::TriSlab*)s->d_bslab.p,
                                                fc.start_world, want_cam, fc.light_pos_model, fc.light_radius, want_light, s->d_rng_cam.p, s->d_rng_light.p, stream));
@@ -821,6 +829,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         }
     } else if (s->part_valid && s->dbg[SR_DBG_KERNEL_SWITCH] == 71) {
         s->part_valid = false; s->b4cam_valid = false; s->b4light_valid = false;        // (hook: no live runs -- the copies are re-made without them)
+        s->blight_valid = false;
     }
     // ---- interior bytes of the records in their final order (the shadow classification's umax shortcut) ----
     if (bvh_walks && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT) && s->d_bslab.p && !s->interior_valid) {
@@ -872,6 +881,31 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         }
         s->dbg_frame[0] |= (uint32_t)s->b4light_known;
     }
+    // ---- penumbra-plane records of the packet shaft walk's triangle filter: one pre-pass per (tree, record order, light ball) ----
+    const bool shadows = (fc.flags & SR_F_SHADOWS) != 0;
+    // (more than 128 samples: the shaft path runs in chunks of 128, escape counts summed per hit point; not for the static cache)
+    const bool shaft = shadows && bvh_walks && (fc.flags & SR_F_POINT_LIGHT) && !(f->flags & SR_F_PER_LANE_SHADOWS) &&
+                       (fc.shadow_samples <= 128 || (fc.shadow_samples <= kMaxShaftSamples && !static_shadows));
+    if (shaft && wide && s->b4light_valid && dev_scene(s).b4light && !(s->dbg[SR_DBG_PER_LANE_SHAFT] > 0 && (s->dbg[SR_DBG_PER_LANE_SHAFT] & 1)) &&
+        s->dbg[SR_DBG_KERNEL_SWITCH] != 96) {
+        const bool same_ball = s->blight_pos[0] == fc.light_pos_model[0] && s->blight_pos[1] == fc.light_pos_model[1] && s->blight_pos[2] == fc.light_pos_model[2] &&
+                               s->blight_radius == fc.light_radius;
+        if (!s->blight_valid || !same_ball) {
+            s->blight_valid = false;
+            // (a refused reservation is no error: the frame filters with the TriSlab records, like SR_DBG_KERNEL_SWITCH 96)
+            if (s->d_blight.reserve(s->ntris * sizeof(sr::LightCone)) == hipSuccess) {
+                rewrote = true;
+                SR_HIP(sr::launch_light_cones(dev_scene(s), (int)s->ntris, fc.light_pos_model, fc.light_radius, (sr::LightCone*)s->d_blight.p, stream));
+                for (int i = 0; i < 3; ++i) s->blight_pos[i] = fc.light_pos_model[i];
+                s->blight_radius = fc.light_radius;
+                s->blight_valid = true;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    } else if (s->dbg[SR_DBG_KERNEL_SWITCH] == 96) {
+        s->blight_valid = false;                                      // (hook: this frame's dev_scene carries no records)
+    }
     if (rewrote) {
         if (!s->pre_ready) SR_HIP(hipEventCreateWithFlags(&s->pre_ready, hipEventDisableTiming));
         SR_HIP(hipEventRecord(s->pre_ready, stream));
@@ -881,10 +915,6 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     }
     // ---- default: the primary / shadow / resolve pipeline, in row bands ----
     const long long n2 = (long long)fc.sub_pixel_res * fc.sub_pixel_res;
-    const bool shadows = (fc.flags & SR_F_SHADOWS) != 0;
-    // (more than 128 samples: the shaft path runs in chunks of 128, escape counts summed per hit point; not for the static cache)
-    const bool shaft = shadows && bvh_walks && (fc.flags & SR_F_POINT_LIGHT) && !(f->flags & SR_F_PER_LANE_SHADOWS) &&
-                       (fc.shadow_samples <= 128 || (fc.shadow_samples <= kMaxShaftSamples && !static_shadows));
     const bool chunked_shadows = shaft && fc.shadow_samples > 128;
     // samples per band: bounds the hit queue (64 B/sample) and, on the shaft path, the candidate lists (256 B/sample for
     // round 0 + 1/4 of the hits x 1 KB for round 1): 16 Mi samples = one 4096^2 frame = 10 GB of scratch in HBM
@@ -1259,7 +1289,7 @@ void share_host_model(sr_scene* d, const sr_scene* src) {
     d->vox_valid = false;
     d->ref = sr::RefTree(); d->bvh = sr::Bvh(); d->bvh_on_device = false;
     d->tris_dirty = d->ref_dirty = d->bvh_dirty = true;
-    d->cam_valid = false; d->interior_valid = false;
+    d->cam_valid = false; d->blight_valid = false; d->interior_valid = false;
 }
 // ... and its host-built structures: the numbers a part needs (built / depth / counts), not the node arrays
 void share_ref_tree(sr_scene* d, const sr_scene* src) {
@@ -1283,7 +1313,7 @@ void drop_bvh(sr_scene* s) {
     s->bvh_dirty = true;
     s->b4_num = 0; s->b4_depth = 0;
     s->b4cam_valid = s->b4light_valid = false;
-    s->cam_valid = s->interior_valid = s->part_valid = false;
+    s->cam_valid = s->blight_valid = s->interior_valid = s->part_valid = false;
 }
 
 // The host arrays of a model that sr_set_triangles_device left on the device only: vertices and records are read back (the colours
@@ -1483,7 +1513,7 @@ void sr_destroy(sr_scene* s) {
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
-                        &s->d_v9, &s->d_bcam, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
+                        &s->d_v9, &s->d_bcam, &s->d_blight, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
                         &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse, &s->d_bounds};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();

@@ -23,6 +23,7 @@ struct DevScene {
     const Rec128*  btris;       // triangle records gathered in leaf order (aux = TriangleIndex)
     const TriSlab* bslab;       // fp32 shaft-prefilter records, same order as btris
     const CamCone* bcam;        // fp32 camera-cone records of the current frame's ray origin, same order (nullptr: none)
+    const LightCone* blight;    // fp32 penumbra-plane records of the current frame's light ball, same order (nullptr: k_shaft_pkt4 filters with bslab)
     const double*  v9;          // model vertices [ntris][3][3], TriangleIndex order
     int32_t        bdepth;
     int32_t        bnode_bits;  // bits needed for a BVH node index (stack words pack node | bound)
@@ -188,6 +189,9 @@ hipError_t launch_facing_partition(const Bvh4Node* base, int num_nodes, Rec128* 
                                    const double light[3], double light_radius, bool use_light, void* cam_rng, void* light_rng, hipStream_t stream);
 // per-frame pre-pass: camera-cone records of every BVH triangle for the ray origin `origin` (model space)
 hipError_t launch_cam_cones(const DevScene& sc, int ntris, const double origin[3], CamCone* out, hipStream_t stream);
+// k_light_cones: the LightCone record of every BVH triangle record for the light ball (light, light_radius); re-run when the light, the
+// tree or the records' order changed
+hipError_t launch_light_cones(const DevScene& sc, int ntris, const double light[3], double light_radius, LightCone* out, hipStream_t stream);
 // per-tree pre-pass (re-made when the records move): the interior byte of every BVH triangle record, DevScene::binter
 hipError_t launch_interior_flags(const DevScene& sc, int ntris, uint8_t* out, hipStream_t stream);
 size_t pipeline_hit_record_bytes();

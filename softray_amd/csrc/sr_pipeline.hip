@@ -12,6 +12,7 @@
 // Results are identical to the one-kernel renderer (k_render, sr_kernels.hip) by construction: the same
 // device functions of sr_trace.h do all result-affecting arithmetic.
 #include "sr_trace.h"
+#include "sr_light_cone.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -619,6 +620,55 @@ __device__ __forceinline__ void shaft_touches_wave(const TriSlab s, const ShaftR
     }
 }
 
+// The packet walk's filter on the frame's penumbra planes (LightCone, sr_light_cone.h): per (light, triangle) the edge
+// conditions of shaft_touches_wave are ONE fixed plane each, so a lane evaluates four planes at E' -- (-G0, o_1) and (o_2, o_3), one
+// chain of three packed FMAs per pair -- where shaft_touches_wave rebuilds K0, K1, A_k, L_k and eps_k per edge.  Same contract: all 64
+// lanes call it for the same record; touch / umbra as there.  The plane stage's other two rejections are per-triangle facts here
+// (GL + R < 0: k_light_cones stores a plane nobody passes; N1 + R < 0 with G0 <= 0 implies it).  Two exits, after each pair, on a
+// scalar test; the record's second line (inner planes, GL) is only fetched when some lane is a candidate.
+#ifndef SR_LC_STAGES
+#define SR_LC_STAGES 2          // 1: one exit after all four planes (measured: profiles/r07_lightcones)
+#endif
+template <int W0, int W1>
+__device__ __forceinline__ void load_cone_words(const LightCone* p, LightCone& out) {
+    typedef const uint32_t __attribute__((address_space(4))) CW4;
+    CW4* w = (CW4*)(const void*)p;
+    uint32_t* o = reinterpret_cast<uint32_t*>(&out);
+#pragma unroll
+    for (int i = W0; i < W1; ++i) o[i] = w[i];
+}
+__device__ __forceinline__ void shaft_cones_wave(const LightCone* rec, const ShaftRay& sr, const lanemask want, lanemask& touch, lanemask& umbra) {
+    touch = 0ull; umbra = 0ull;
+    LightCone c;
+    load_cone_words<0, 16>(rec, c);                                    // scalar load: the first line
+    const float ex = sr.edx.x, ey = sr.edy.x, ez = sr.edz.x, lim = -sr.a0;
+    const LcPair A = lc_stage_a(c, ex, ey, ez);
+    lanemask cand;
+    if (SR_LC_STAGES == 2) {
+        const lanemask ok_a = want & ~vote(fminf(A.a, A.b) < lim);
+        if (ok_a == 0ull) return;
+        const LcPair B = lc_stage_b(c, ex, ey, ez);
+        cand = ok_a & ~vote(fminf(B.a, B.b) < lim);
+    } else {
+        const LcPair B = lc_stage_b(c, ex, ey, ez);
+        cand = want & ~vote(fminf(fminf(A.a, A.b), fminf(B.a, B.b)) < lim);
+    }
+    if (cand == 0ull) return;
+    touch = cand;
+    // ---- umbra: inside every inner plane; the other conditions are shaft_touches_wave's with N1 = GL - G0 ----
+    load_cone_words<16, 32>(rec, c);                                   // the second line
+    const float G0 = -A.a, N1 = c.GL - G0;
+    const lanemask pre = cand & vote(lc_inner_min(c, ex, ey, ez) > sr.a0) & vote(N1 > 2.0f * sr.Rm + sr.a01) & vote(G0 < -4.0f * sr.a0);
+    if (pre != 0ull) {
+        const float ulo = -G0 * __builtin_amdgcn_rcpf(N1 + sr.Rm) * 0.999998f, uhi = -G0 * __builtin_amdgcn_rcpf(N1 - sr.Rm) * 1.000002f;
+        const float margin = __builtin_fmaf(sr.Rm, uhi, sr.umargin);
+        const f2 U = {ulo, uhi};
+        const f2 X = pk_fma(U, splat(sr.edx.y), splat(sr.edx.x)), Y = pk_fma(U, splat(sr.edy.y), splat(sr.edy.x)), Z = pk_fma(U, splat(sr.edz.y), splat(sr.edz.x));
+        umbra = pre & vote(ulo > 1e-6f) & vote(uhi < 0.5f) & vote(fmaxf(fabsf(X.x), fabsf(X.y)) + margin < sr.hbx) & vote(fmaxf(fabsf(Y.x), fabsf(Y.y)) + margin < sr.hby) &
+                vote(fmaxf(fabsf(Z.x), fabsf(Z.y)) + margin < sr.hbz);
+    }
+}
+
 template <bool STATS>
 __global__ __launch_bounds__(256) void k_shaft(DevScene sc, FrameConst fc, const HitRec* __restrict__ hits,
                                                const unsigned int* __restrict__ hit_count, unsigned int count_cap,
@@ -1046,7 +1096,9 @@ __device__ __forceinline__ void shaft_slabs(const Bvh4Child& ch, f2 Ixy, f2 Izz,
 // the candidate lists may differ in order and in which candidates a truncated list holds, which no later stage depends on.
 // LDS per wave: [levels] node words + [levels][64] 16-bit bounds, levels = 3 * b4depth + 2.
 // --------------------------------------------------------------------------------------------------
-template <bool STATS, int WAVES, bool PERSIST, int KNOWN = 0>
+// CONES: the triangle filter reads the frame's LightCone records (shaft_cones_wave) instead of the TriSlab records (shaft_touches_wave;
+// SR_DBG_KERNEL_SWITCH 96, or no room for the records): same verdicts where it matters -- a superset of the hitting pairs, umbra only where proven.
+template <bool STATS, int WAVES, bool PERSIST, int KNOWN = 0, bool CONES = false>
 __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, FrameConst fc_arg, const HitRec* __restrict__ hits,
                                                     const unsigned int* __restrict__ hit_count, int cap, int levels, int tile_n2, int tile_rows,
                                                     unsigned int* __restrict__ cand_count, int32_t* __restrict__ cand,
@@ -1167,9 +1219,12 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
             slabs += (uint32_t)cn;
             if (PERSIST) walk += (uint32_t)cn;
             for (int q = 0; q < cn; ++q) {
-                const TriSlab s = load_uniform(&sc_arg.bslab[cc + q]); // scalar load
                 lanemask take_m, in_umbra_m;
-                shaft_touches_wave(s, sr, hc & ~done_m, take_m, in_umbra_m);
+                if constexpr (CONES) shaft_cones_wave(&sc_arg.blight[cc + q], sr, hc & ~done_m, take_m, in_umbra_m);
+                else {
+                    const TriSlab s = load_uniform(&sc_arg.bslab[cc + q]); // scalar load
+                    shaft_touches_wave(s, sr, hc & ~done_m, take_m, in_umbra_m);
+                }
                 const lanemask room_m = vote(count < cap);
                 if (lane_of(take_m & room_m)) out[count] = cc + q;
                 count += lane_of(take_m & room_m) ? 1 : 0;
@@ -4019,6 +4074,37 @@ __global__ __launch_bounds__(256) void k_interior_flags(const Rec128* __restrict
     out[i] = in ? 1 : 0;
 }
 
+// --------------------------------------------------------------------------------------------------
+// k_light_cones: per-light pre-pass of the packet shaft walk -- the LightCone record (sr_types.h) of every BVH triangle record for the
+// frame's light ball: FP64 from the FP64 vertices, rounded once (light_cone_record, sr_light_cone.h).  128 B written + 72 B (gathered)
+// + 8 B read per triangle: 0.21 GB at 1 M triangles; re-run only when the light, the tree or the records' order changed.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_light_cones(const Rec128* __restrict__ btris, const TriSlab* __restrict__ bslab,
+                                                     const double* __restrict__ v9, int n, RootBox root, double lx, double ly, double lz, double radius,
+                                                     LightCone* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const TriSlab sl = bslab[i];
+    const bool degenerate = sl.n[0] == 0.0f && sl.n[1] == 0.0f && sl.n[2] == 0.0f;   // k_make_slabs: no usable planes
+    const double* vp = v9 + (size_t)btris[i].aux * 9;
+    double v[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = vp[k];
+    const double L[3] = {lx, ly, lz};
+    const LightCone c = light_cone_record(v, root.centre, L, radius, degenerate);
+    const uint4* src = reinterpret_cast<const uint4*>(&c);
+    uint4* dst = reinterpret_cast<uint4*>(&out[i]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dst[k] = src[k];
+}
+
+hipError_t launch_light_cones(const DevScene& sc, int ntris, const double light[3], double light_radius, LightCone* out, hipStream_t stream) {
+    if (ntris <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_light_cones, dim3((unsigned)((ntris + 255) / 256)), dim3(256), 0, stream, sc.btris, sc.bslab, sc.v9, ntris, sc.root,
+                       light[0], light[1], light[2], light_radius, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_interior_flags(const DevScene& sc, int ntris, uint8_t* out, hipStream_t stream) {
     if (ntris <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_interior_flags, dim3((unsigned)((ntris + 255) / 256)), dim3(256), 0, stream, sc.btris, sc.bslab, sc.v9, ntris, sc.root, out);
@@ -4290,7 +4376,10 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
                 // one instantiation per set of axes on which the light-ordered copy holds (near, far) planes (the light lies outside the root box there)
                 const auto go_known = [&](auto known) {
                     constexpr int K = decltype(known)::value;
-                    if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K>); else go(k_shaft_pkt4<false, 6, true, K>); }
+                    if (L.sc.blight) {                         // the frame's penumbra-plane records are there: filter with them
+                        if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K, true>); else go(k_shaft_pkt4<false, 6, true, K, true>); }
+                        else { if (L.stats) go(k_shaft_pkt4<true, 6, false, K, true>); else go(k_shaft_pkt4<false, 6, false, K, true>); }
+                    } else if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K>); else go(k_shaft_pkt4<false, 6, true, K>); }
                     else { if (L.stats) go(k_shaft_pkt4<true, 6, false, K>); else go(k_shaft_pkt4<false, 6, false, K>); }
                 };
                 switch (L.sc.b4light_known & 7) {

@@ -130,6 +130,25 @@ struct alignas(16) CamCone {
 };
 static_assert(sizeof(CamCone) == 64, "CamCone must be 64 bytes");
 
+// fp32 description of one triangle as seen from ONE light ball (centre L, radius R: the point light of a frame and its area-light
+// offsets), 128 B = two lines, BVH-leaf order, parallel to the TriSlab array; coordinates relative to the root-box centre, every plane
+// a unit normal (x, y, z) and an offset d with value(p) = x p.x + y p.y + z p.z + d, laid out in pairs for packed FMAs
+// (sr_light_cone.h makes and evaluates it).  Only k_shaft_pkt4 reads it.
+//   first line  -- all a candidate decision needs: the NEGATED triangle plane (value = -G0 = d - n.p) and the three OUTER tangent planes
+//                  o_k of the ball through the edge lines: some sample ray can pass inside edge k only if o_k(E') >= 0;
+//   second line -- read when some lane is a candidate: the three INNER tangent planes i_k (every sample ray passes inside edge k
+//                  if i_k(E') > 0) and GL = n.L - d (N1 = GL - G0).
+// A zero normal with offset +-1e30 is a plane that every / no point passes (the conservative classes and degenerate triangles).
+struct alignas(16) LightCone {
+    float gx_o1x[2], gy_o1y[2], gz_o1z[2], gd_o1d[2];   // (-n, o1)
+    float o23x[2], o23y[2], o23z[2], o23d[2];           // (o2, o3)
+    float i12x[2], i12y[2], i12z[2], i12d[2];           // (i1, i2)
+    float i3[4];                                        // i3: x, y, z, d
+    float GL;
+    float pad[3];
+};
+static_assert(sizeof(LightCone) == 128, "LightCone must be 128 bytes");
+
 // Root box as the clip needs it (AxisAlignedBox.cs:16-28,143-149)
 struct RootBox {
     double min[3], max[3];       // model.Min / model.Max

@@ -76,6 +76,7 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern void sr_destroy(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_set_triangles(IntPtr scene, double[] v9, uint[] argb, long n, double[] boxMin, double[] boxMax);
         [DllImport(Lib)] public static extern int sr_set_triangles_device(IntPtr scene, IntPtr dV9, IntPtr dArgb, long n, double[] boxMin, double[] boxMax, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int sr_refit_triangles_device(IntPtr scene, IntPtr dV9, IntPtr dArgb, long n, double[] boxMin, double[] boxMax, IntPtr hipStream);
         [DllImport(Lib)] public static extern int sr_set_extra_geometry(IntPtr scene, [In] SrPrim[] prims, int n);
         [DllImport(Lib)] public static extern int sr_build(IntPtr scene, uint modes, int maxDepth, int maxPerLeaf);
         [DllImport(Lib)] public static extern int sr_tree_stats(IntPtr scene, [Out] int[] out4);
@@ -237,6 +238,17 @@ namespace Engine3D.Hip
             Native.Check(Native.sr_set_triangles_device(scene, v9, argb, n, min, max, stream));
             uploaded = null;
             builtModes = 0;
+        }
+
+        /// New vertices for a mesh that only moves (sr_refit_triangles_device): arguments as SetTrianglesDevice, same n as the model.  The
+        /// own BVH that BuildStructure(MODE_BVH) built on the device is REFIT -- no new build; every other structure is dropped as by
+        /// SetTrianglesDevice.  The tree keeps the shape of its build: after a large deformation frames get slower, never wrong, and the
+        /// caller decides when to BuildStructure again.
+        public void RefitTrianglesDevice(IntPtr v9, IntPtr argb, long n, double[] min, double[] max, IntPtr stream)
+        {
+            Native.Check(Native.sr_refit_triangles_device(scene, v9, argb, n, min, max, stream));
+            uploaded = null;
+            builtModes &= 1u << 2;                                                                   // SR_MODE_BVH stays built
         }
 
         /// sr_build for the triangles that SetTrianglesDevice left (MODE_BVH above 64 triangles is built where they are: on the device)

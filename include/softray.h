@@ -298,9 +298,29 @@ int  sr_set_triangles(sr_scene*, const double* v9, const uint32_t* argb, int64_t
  * uploaded yet is uploaded first); allowed only when n == sr_num_triangles(scene) and the scene has a model, SR_ERR_INVALID_ARG
  * otherwise (n == 0 needs neither array, as in sr_set_triangles).  n < 0, d_v9 == NULL with n > 0, a NULL box and n > 0x7fffff00 are
  * SR_ERR_INVALID_ARG too, and the arguments are checked before the device is looked at: a host-only scene then answers
- * SR_ERR_NO_DEVICE. */
+ * SR_ERR_NO_DEVICE.  A mesh that keeps its triangle count and only moves can keep its tree: sr_refit_triangles_device, below. */
 int  sr_set_triangles_device(sr_scene*, const double* d_v9, const uint32_t* d_argb, int64_t n,
                              const double box_min[3], const double box_max[3], void* hip_stream);
+/* New vertices for a mesh that only MOVES, without a new build: the scene's own BVH -- built on the device -- is REFIT.  Arguments and
+ * conventions are those of sr_set_triangles_device (the arrays are copied, everything runs on `hip_stream` behind a frame of the scene in
+ * flight on any stream, one host wait for the six doubles of the vertex bounds, d_argb == NULL keeps the colours), and so is everything
+ * that is dropped -- the reference tree (SR_MODE_REF_TREE answers SR_ERR_NOT_BUILT until the next sr_build), the static-shadow, AO and
+ * light-field caches, the voxel grid, the host arrays -- EXCEPT the own BVH: its topology, leaf order and node numbering stay, and
+ * everything in it that describes geometry is re-made by kernels from the new vertices and the new box: the leaf-order records and shaft
+ * records, the fp32 boxes of the binary and of the four-wide nodes (bottom-up, by the build's own rounding), and the per-origin /
+ * per-light records of the next frame.  Afterwards SR_MODE_BVH frames and ray batches answer exactly as after sr_set_triangles_device +
+ * sr_build(1 << SR_MODE_BVH): pixels never depend on the tree.  sr_bvh_stats and sr_wide_tree_stats are unchanged.
+ * A REFIT TREE IS ONLY AS GOOD AS THE BUILD IT CAME FROM.  The tree keeps the neighbourhoods of the vertices it was built for: after a
+ * large deformation the boxes of its nodes overlap and frames get slower -- never wrong.  The library does not measure that and never
+ * rebuilds by itself: the caller decides when to call sr_set_triangles_device + sr_build (or just sr_build) again.
+ * Refused before anything is enqueued, the scene untouched, in this order: bad arguments (as sr_set_triangles_device) SR_ERR_INVALID_ARG;
+ * a host-only scene SR_ERR_NO_DEVICE; n != sr_num_triangles(scene) SR_ERR_INVALID_ARG (a change of topology is sr_set_triangles_device +
+ * sr_build); no model SR_ERR_NO_MODEL; no own BVH (never built, dropped by a set, refused by sr_build) SR_ERR_NOT_BUILT; an own BVH the
+ * HOST built (SR_BUILD_ON_HOST, or n <= 64) SR_ERR_UNSUPPORTED -- its host copy of the nodes and sr_bvh_digest would go stale: rebuild.
+ * A HIP error after the first kernel was enqueued leaves the scene without a model, every part of a multi-device scene alike; a
+ * multi-device scene forwards to its parts with the peer copy sr_set_triangles_device makes. */
+int  sr_refit_triangles_device(sr_scene*, const double* d_v9, const uint32_t* d_argb, int64_t n,
+                               const double box_min[3], const double box_max[3], void* hip_stream);
 /* ExtraGeometryToRaytrace (Renderer.cs:460); n == 0 clears */
 int  sr_set_extra_geometry(sr_scene*, const sr_prim* prims, int32_t n);
 

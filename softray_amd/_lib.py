@@ -45,6 +45,7 @@ SYMBOLS = [
     "sr_net_random_doubles", "sr_build_voxels", "sr_get_voxels", "sr_reset_ao_cache", "sr_get_ao_cache", "sr_set_ao_cache",
     "sr_set_light_field_res", "sr_get_light_field_res", "sr_reset_light_field", "sr_get_light_field", "sr_set_light_field",
     "sr_bake_light_field", "sr_set_voxel_res", "sr_get_voxel_res", "sr_set_triangles_device",
+    "sr_refit_triangles_device",
 ]
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
@@ -120,6 +121,7 @@ def lib():
     L.sr_destroy.restype = None; L.sr_destroy.argtypes = [vp]
     L.sr_set_triangles.restype = i32; L.sr_set_triangles.argtypes = [vp, vp, vp, i64, vp, vp]
     L.sr_set_triangles_device.restype = i32; L.sr_set_triangles_device.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    L.sr_refit_triangles_device.restype = i32; L.sr_refit_triangles_device.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     L.sr_set_extra_geometry.restype = i32; L.sr_set_extra_geometry.argtypes = [vp, vp, i32]
     L.sr_build.restype = i32; L.sr_build.argtypes = [vp, u32, i32, i32]
     L.sr_tree_stats.restype = i32; L.sr_tree_stats.argtypes = [vp, vp]

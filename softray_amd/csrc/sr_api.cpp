@@ -97,6 +97,11 @@ struct sr_scene {
     // device state
     DBuf d_tris, d_extra, d_rnodes, d_rboxes, d_rleaf, d_bnodes, d_btris, d_bslab, d_v9, d_bcam;
     DBuf d_bounds;                       // sr_set_triangles_device: the bounds kernels' partials, the six doubles of the result in front
+    // sr_refit_triangles_device (a device-built own BVH only): the wide tree's level ranges (collapse_bvh4_device), the binary nodes'
+    // depths (a byte each, made at the tree's first refit) and the triangles' fp32 boxes in leaf order; all belong to one tree
+    std::vector<int> b4_level_first;
+    DBuf d_bdepth, d_tbox;
+    bool bdepth_valid = false;
     double cam_origin[3] = {0, 0, 0};    // ray origin the camera-cone records in d_bcam (and the node order of d_b4cam) were made for
     bool   cam_valid = false;
     // penumbra-plane records of the packet shaft walk (k_light_cones): made for one (tree, record order, light ball); like d_bcam they follow
@@ -1312,6 +1317,8 @@ void drop_bvh(sr_scene* s) {
     s->bvh_num_nodes = 0;
     s->bvh_dirty = true;
     s->b4_num = 0; s->b4_depth = 0;
+    s->b4_level_first.clear();
+    s->bdepth_valid = false;
     s->b4cam_valid = s->b4light_valid = false;
     s->cam_valid = s->blight_valid = s->interior_valid = s->part_valid = false;
 }
@@ -1435,6 +1442,88 @@ int set_triangles_from_device(sr_scene* s, const double* src_v9, const uint32_t*
     return rc;
 }
 
+// sr_refit_triangles_device for one scene with a device whose own BVH was built there (the caller has checked that).  Arguments as
+// set_triangles_from_device_enqueue.  Nothing grows: the model keeps its count, so a frame in flight is only waited for by the STREAM.
+int refit_from_device_enqueue(sr_scene* s, const double* src_v9, const uint32_t* src_argb, int64_t n, const double box_min[3],
+                              const double box_max[3], hipStream_t stream, int src_device, bool copy_first) {
+    int rc = SR_OK;
+    DBuf tmp_v9, tmp_argb;
+    struct Free { DBuf* b[2]; ~Free() { for (DBuf* x : b) x->release(); } } free_tmp{{&tmp_v9, &tmp_argb}};
+    const size_t v9_bytes = (size_t)n * 9 * sizeof(double);
+    if (copy_first) {
+        SR_HIP(tmp_v9.reserve(v9_bytes));
+        SR_HIP(hipMemcpyPeerAsync(tmp_v9.p, s->device, src_v9, src_device, v9_bytes, stream));
+        src_v9 = (const double*)tmp_v9.p;
+        if (src_argb) {
+            SR_HIP(tmp_argb.reserve((size_t)n * sizeof(uint32_t)));
+            SR_HIP(hipMemcpyPeerAsync(tmp_argb.p, s->device, src_argb, src_device, (size_t)n * sizeof(uint32_t), stream));
+            src_argb = (const uint32_t*)tmp_argb.p;
+        }
+    }
+    SR_HIP(s->d_bounds.reserve(sr::tri_bounds_scratch_bytes()));
+    SR_HIP(s->d_tbox.reserve((size_t)n * sr::refit_box_bytes()));
+    SR_HIP(s->d_bdepth.reserve(s->bvh_num_nodes));
+    // a frame in flight keeps the old geometry and the old boxes: everything below runs behind it
+    if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
+    double bounds[6];
+    hipEvent_t e0, e1;
+    if ((rc = next_events(s, sr::K_TRI_RECORDS, e0, e1))) return rc;
+    if (e0) SR_HIP(hipEventRecord(e0, stream));
+    SR_HIP(sr::tri_records_device(src_v9, src_argb, (int)n, (double*)s->d_v9.p, (sr::Rec128*)s->d_tris.p, stream));
+    if (e1) SR_HIP(hipEventRecord(e1, stream));
+    if ((rc = next_events(s, sr::K_TRI_BOUNDS, e0, e1))) return rc;
+    if (e0) SR_HIP(hipEventRecord(e0, stream));
+    SR_HIP(sr::tri_bounds_device((const double*)s->d_v9.p, (int)n, box_min, box_max, (double*)s->d_bounds.p, stream));
+    if (e1) SR_HIP(hipEventRecord(e1, stream));
+    SR_HIP(hipMemcpyAsync(bounds, s->d_bounds.p, sizeof(bounds), hipMemcpyDeviceToHost, stream));
+    const sr::RootBox root = sr::make_root_box(box_min, box_max);
+    struct Ev { sr_scene* s; int rc; } evu{s, SR_OK};
+    SR_HIP(sr::refit_bvh_device((const double*)s->d_v9.p, (const sr::Rec128*)s->d_tris.p, (int)n, root, (sr::Rec128*)s->d_btris.p,
+                                (sr::TriSlab*)s->d_bslab.p, (sr::BvhNode*)s->d_bnodes.p, (int)s->bvh_num_nodes, s->bvh.depth,
+                                (sr::Bvh4Node*)s->d_b4.p, (int)s->b4_num, s->b4_level_first, s->d_tbox.p, (uint8_t*)s->d_bdepth.p,
+                                &s->bdepth_valid, stream,
+                                [](void* user, int phase, hipEvent_t* a, hipEvent_t* b) {
+                                    hipEvent_t x = nullptr, y = nullptr;
+                                    if (next_events(((Ev*)user)->s, phase == 0 ? sr::K_REFIT_LEAVES : sr::K_REFIT_NODES, x, y) != SR_OK) x = y = nullptr;
+                                    *a = x; *b = y;
+                                }, &evu));
+    SR_HIP(hipStreamSynchronize(stream));                          // the call's one host wait: the six doubles (and the temporaries are freed on return)
+    // ---- the geometry is new, the tree is the old one: everything made FROM the records or the boxes is stale ----
+    s->b4cam_valid = s->b4light_valid = false;
+    s->cam_valid = s->blight_valid = s->interior_valid = s->part_valid = false;
+    s->bvh_dirty = false;                                 // (kept: b4_num, b4_depth, bvh.built, bvh.depth, bvh_num_nodes, bvh_on_device)
+    s->tris_dirty = false;
+    s->shadow_cache_empty = true;                         // a new model: what sr_set_triangles_device drops
+    s->ao_cache_empty = true; s->ao_cache_host.clear();
+    s->lf_cache_empty = true; s->lf_cache_host.clear();
+    s->vox_valid = false;
+    std::vector<double>().swap(s->v9);
+    std::vector<uint32_t>().swap(s->argb);
+    std::vector<sr::Rec128>().swap(s->tri_recs);
+    s->host_src = nullptr;
+    s->host_model_stale = true;
+    for (int a = 0; a < 3; ++a) { s->bmin[a] = box_min[a]; s->bmax[a] = box_max[a]; s->vmin[a] = bounds[a]; s->vmax[a] = bounds[3 + a]; }
+    s->root = root;
+    s->ref = sr::RefTree();                               // SR_MODE_REF_TREE answers SR_ERR_NOT_BUILT until the next sr_build
+    s->ref_dirty = true;
+    return SR_OK;
+}
+
+int refit_from_device(sr_scene* s, const double* src_v9, const uint32_t* src_argb, int64_t n, const double box_min[3],
+                      const double box_max[3], hipStream_t stream, int src_device, bool copy_first) {
+    int rc = use_device(s);
+    if (rc) return rc;
+    rc = refit_from_device_enqueue(s, src_v9, src_argb, n, box_min, box_max, stream, src_device, copy_first);
+    if (rc) {
+        const std::string why = g_err;
+        (void)hipStreamSynchronize(stream);               // nothing of the failed call is left running on the arrays
+        (void)hipGetLastError();
+        drop_model(s);
+        g_err = why;
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1514,7 +1603,7 @@ void sr_destroy(sr_scene* s) {
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
                         &s->d_v9, &s->d_bcam, &s->d_blight, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
-                        &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse, &s->d_bounds};
+                        &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse, &s->d_bounds, &s->d_bdepth, &s->d_tbox};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
         for (auto& t : s->tables) { t.dev.release(); if (t.host) (void)hipHostFree(t.host); if (t.used) (void)hipEventDestroy(t.used); if (t.ready) (void)hipEventDestroy(t.ready); }
@@ -1601,6 +1690,39 @@ int sr_set_triangles_device(sr_scene* s, const double* d_v9, const uint32_t* d_a
     if (rc) {                                                    // no part keeps a model the others do not have
         const std::string why = g_err;
         for (sr_scene* q : s->parts) drop_model(q);
+        g_err = why;
+    }
+    return rc;
+}
+
+int sr_refit_triangles_device(sr_scene* s, const double* d_v9, const uint32_t* d_argb, int64_t n, const double box_min[3], const double box_max[3],
+                              void* hip_stream) {
+    if (!s || n < 0 || (n > 0 && !d_v9) || !box_min || !box_max) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_refit_triangles_device");
+    if (n > 0x7fffff00) return fail(SR_ERR_INVALID_ARG, "too many triangles");
+    if (s->parts.empty() && s->device < 0) return fail(SR_ERR_NO_DEVICE, "host-only scene: no HIP device bound (compute is never emulated on the CPU)");
+    std::vector<sr_scene*> one{s};
+    const std::vector<sr_scene*>& parts = s->parts.empty() ? one : s->parts;
+    sr_scene* first = parts[0];
+    // ---- every refusal before anything is enqueued: the scene stays as it is ----
+    if ((int64_t)first->ntris != n) return fail(SR_ERR_INVALID_ARG, "sr_refit_triangles_device: n differs from the model's triangle count (a refit keeps the topology)");
+    if (!first->have_model || n == 0) return fail(SR_ERR_NO_MODEL, "sr_refit_triangles_device before sr_set_triangles");
+    for (const sr_scene* q : parts)
+        if (!q->bvh.built || (q->bvh_on_device && (q->bvh_num_nodes == 0 || q->b4_num == 0 || q->d_btris.cap < (size_t)n * sizeof(sr::Rec128))))
+            return fail(SR_ERR_NOT_BUILT, "sr_refit_triangles_device: the scene has no own BVH (sr_build(1 << SR_MODE_BVH) first)");
+    for (const sr_scene* q : parts)
+        if (!q->bvh_on_device || q->bvh_dirty || q->tris_dirty || q->b4_level_first.size() < 2)
+            return fail(SR_ERR_UNSUPPORTED, "sr_refit_triangles_device: the own BVH was built on the host (SR_BUILD_ON_HOST, or n <= 64): rebuild instead");
+    if (parts.size() == 1) return refit_from_device(first, d_v9, d_argb, n, box_min, box_max, (hipStream_t)hip_stream, first->device, false);
+    // as in sr_set_triangles_device: the first part takes the arrays on the caller's stream (and waits for it), every other part copies
+    // them to its own device and refits its own tree
+    int rc = refit_from_device(first, d_v9, d_argb, n, box_min, box_max, (hipStream_t)hip_stream, first->device, false);
+    for (size_t i = 1; i < parts.size() && !rc; ++i) {
+        rc = refit_from_device(parts[i], d_v9, d_argb, n, box_min, box_max, nullptr, first->device, true);
+        if (!rc) parts[i]->host_src = first;
+    }
+    if (rc) {                                                    // no part keeps a model the others do not have
+        const std::string why = g_err;
+        for (sr_scene* q : parts) drop_model(q);
         g_err = why;
     }
     return rc;
@@ -1727,7 +1849,7 @@ int sr_build(sr_scene* s, uint32_t modes, int32_t max_depth, int32_t max_per_lea
         {   // the four-wide tree of the packet walks, collapsed where the binary nodes are
             SR_HIP(s->d_b4.reserve((size_t)nn * sizeof(sr::Bvh4Node)));
             int n4 = 0, d4 = 0;
-            e = sr::collapse_bvh4_device((const sr::BvhNode*)s->d_bnodes.p, nn, (sr::Bvh4Node*)s->d_b4.p, &n4, &d4, nullptr);
+            e = sr::collapse_bvh4_device((const sr::BvhNode*)s->d_bnodes.p, nn, (sr::Bvh4Node*)s->d_b4.p, &n4, &d4, nullptr, &s->b4_level_first);
             if (e != hipSuccess) { drop_bvh(s); return hip_fail(e, "collapse_bvh4_device"); }
             s->b4_num = (size_t)n4;
             s->b4_depth = d4;

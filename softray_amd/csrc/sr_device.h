@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "sr_types.h"
 
 namespace sr {
@@ -42,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_COUNT = 25 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_COUNT = 27 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -216,7 +218,10 @@ hipError_t ray_sort(const void* queue, const unsigned int* d_count, unsigned int
                     unsigned int* idx, unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
 
 // the four-wide tree collapsed from a device-resident binary tree (same rule as the host's collapse_bvh4); d_wide: >= num_nodes entries
-hipError_t collapse_bvh4_device(const BvhNode* d_nodes, int num_nodes, Bvh4Node* d_wide, int* num_wide, int* depth, hipStream_t stream);
+// level_first (nullable): the wide nodes are numbered level by level -- level L is [level_first[L], level_first[L + 1]), the last entry
+// is *num_wide (what the refit's per-level launches need)
+hipError_t collapse_bvh4_device(const BvhNode* d_nodes, int num_nodes, Bvh4Node* d_wide, int* num_wide, int* depth, hipStream_t stream,
+                                std::vector<int>* level_first = nullptr);
 
 // fp32 TriSlab records of n triangles (TriangleIndex order) computed on the device from the FP64 vertices (sr_lbvh.hip)
 hipError_t make_slabs_device(const double* d_v9, int n, const RootBox& root, TriSlab* d_out, hipStream_t stream);
@@ -227,6 +232,17 @@ hipError_t make_slabs_device(const double* d_v9, int n, const RootBox& root, Tri
 hipError_t tri_records_device(const double* d_src_v9, const uint32_t* d_src_argb, int n, double* d_v9, Rec128* d_tris, hipStream_t stream);
 size_t tri_bounds_scratch_bytes();
 hipError_t tri_bounds_device(const double* d_v9, int n, const double box_min[3], const double box_max[3], double* d_scratch, hipStream_t stream);
+
+// sr_refit_triangles_device (sr_lbvh.hip): a device-built own BVH keeps its topology, leaf order and node numbering, and everything in it
+// that describes geometry is re-made from d_v9 / d_tris (TriangleIndex order, already rewritten) and the new root: the leaf-order records
+// and TriSlabs (position -> triangle = the record's aux), then the fp32 boxes bottom-up, one launch per level, deepest first -- of the
+// binary nodes (d_depth: a byte per node, made on the tree's first call: *depths_made; tree_depth: the build's) and of the four-wide
+// nodes (level_first).  d_tbox: n x refit_box_bytes() of scratch.  phase of get_events: 0 = k_refit_leaves, 1 = the node kernels.
+size_t refit_box_bytes();
+hipError_t refit_bvh_device(const double* d_v9, const Rec128* d_tris, int n, const RootBox& root, Rec128* d_btris, TriSlab* d_bslab, BvhNode* d_nodes,
+                            int num_nodes, int tree_depth, Bvh4Node* d_wide, int num_wide, const std::vector<int>& level_first, void* d_tbox,
+                            uint8_t* d_depth, bool* depths_made, hipStream_t stream,
+                            void (*get_events)(void* user, int phase, hipEvent_t* start, hipEvent_t* stop), void* user);
 
 // Surface passes (sr_post.hip): PostProcessImage colour functions and AntiAliasImage, Renderer.cs:819-978.
 hipError_t launch_post_process(uint32_t* d_pixels, long long count, int style, uint32_t background, int num_cus, hipStream_t stream);

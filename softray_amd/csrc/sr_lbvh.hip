@@ -31,6 +31,17 @@ __device__ __forceinline__ unsigned long long spread21(unsigned long long x) {  
     return x;
 }
 
+// a triangle's conservative fp32 box from its FP64 extent: relative to the root centre, padded, rounded outward (k_lbvh_keys for the
+// build, k_refit_leaves for a refit: the same text, so that a refit box is the box a build would make)
+__device__ __forceinline__ FBox tri_box(const double lo[3], const double hi[3], const double centre[3], float pad) {
+    FBox b;
+    for (int a = 0; a < 3; ++a) {
+        b.lo[a] = __double2float_rd(lo[a] - centre[a] - (double)pad);
+        b.hi[a] = __double2float_ru(hi[a] - centre[a] + (double)pad);
+    }
+    return b;
+}
+
 // per triangle: conservative fp32 box (relative to the root centre, padded) + Morton key of its centre
 __global__ void k_lbvh_keys(const double* __restrict__ v9, int n, RootBox root, float pad, FBox* __restrict__ tbox,
                             unsigned long long* __restrict__ keys, unsigned int* __restrict__ vals) {
@@ -42,11 +53,9 @@ __global__ void k_lbvh_keys(const double* __restrict__ v9, int n, RootBox root, 
         lo[a] = fmin(fmin(p[a], p[3 + a]), p[6 + a]);
         hi[a] = fmax(fmax(p[a], p[3 + a]), p[6 + a]);
     }
-    FBox b;
+    const FBox b = tri_box(lo, hi, root.centre, pad);
     unsigned long long key = 0;
     for (int a = 0; a < 3; ++a) {
-        b.lo[a] = __double2float_rd(lo[a] - root.centre[a] - (double)pad);
-        b.hi[a] = __double2float_ru(hi[a] - root.centre[a] + (double)pad);
         const double ext = root.max[a] - root.min[a];
         double q = ext > 0 ? (0.5 * (lo[a] + hi[a]) - root.min[a]) / ext : 0.0;
         q = fmin(fmax(q, 0.0), 1.0);
@@ -178,10 +187,8 @@ struct Tmp {
 // in FP64 relative to the root centre and rounded once.  Degenerate / needle-thin triangles, and those whose "zero" normal the
 // reference replaces by (1,0,0) (Triangle.cs:42-43: it then accepts hits in the plane x = v1.x that need not be near the
 // geometric triangle), get an all-zero record = "never filtered", which is always admissible.
-__global__ void k_make_slabs(const double* __restrict__ v9, int n, double cx, double cy, double cz, TriSlab* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double* p = v9 + (size_t)i * 9;
+// (one text for k_make_slabs and k_refit_leaves: a refit record is the record a build would make)
+__device__ __forceinline__ TriSlab make_slab(const double* __restrict__ p, double cx, double cy, double cz) {
     struct V { double x, y, z; };
     auto sub = [](V a, V b) { return V{a.x - b.x, a.y - b.y, a.z - b.z}; };
     auto dot = [](V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; };
@@ -223,7 +230,13 @@ __global__ void k_make_slabs(const double* __restrict__ v9, int n, double cx, do
         t.n[0] = (float)nn.x; t.n[1] = (float)nn.y; t.n[2] = (float)nn.z;
         t.d = (float)dot(nn, a);
     }
-    out[i] = ok ? t : zero;
+    return ok ? t : zero;
+}
+
+__global__ void k_make_slabs(const double* __restrict__ v9, int n, double cx, double cy, double cz, TriSlab* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = make_slab(v9 + (size_t)i * 9, cx, cy, cz);
 }
 
 // ---- sr_set_triangles_device: the model's two TriangleIndex-order arrays made on the device from the caller's device arrays ----
@@ -284,6 +297,125 @@ __global__ void __launch_bounds__(kBoundsThreads) k_tri_bounds_fold(const double
         for (int a = 0; a < 3; ++a) { out[a] = fmin(box.v[a], lo[a]); out[3 + a] = fmax(box.v[3 + a], hi[a]); }
 }
 
+// ---- sr_refit_triangles_device: the own BVH keeps its topology, leaf order and node numbering; what describes geometry is re-made ----
+// One lane per leaf-order position p.  The triangle at p is the record's own aux (TriangleIndex): the facing partition permutes the
+// records of a leaf per frame, so no saved order would do -- and aux is the one field a refit never changes, so reading it from the
+// record that is being overwritten is no race.  The lane copies the triangle's new FP64 record (k_tri_records has made it in
+// TriangleIndex order), makes the new TriSlab (make_slab: the build's text) and leaves the triangle's fp32 box (tri_box: the build's
+// text) in tbox[p] for the node kernels.
+__global__ void __launch_bounds__(256) k_refit_leaves(int n, const double* __restrict__ v9, const Rec128* __restrict__ tris, double cx, double cy,
+                                                      double cz, float pad, Rec128* btris, TriSlab* __restrict__ bslab, FBox* __restrict__ tbox) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int tri = btris[p].aux;
+    if (tri < 0 || tri >= n) return;                                  // (never in a tree this library built: no read outside the arrays)
+    const uint4* src = (const uint4*)(tris + tri);
+    uint4* dst = (uint4*)(btris + p);
+    uint4 r[8];
+    for (int k = 0; k < 8; ++k) r[k] = src[k];
+    for (int k = 0; k < 8; ++k) dst[k] = r[k];
+    const double* q = v9 + (size_t)tri * 9;
+    double v[9];
+    for (int k = 0; k < 9; ++k) v[k] = q[k];
+    bslab[p] = make_slab(v, cx, cy, cz);
+    double lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = fmin(fmin(v[a], v[3 + a]), v[6 + a]);
+        hi[a] = fmax(fmax(v[a], v[3 + a]), v[6 + a]);
+    }
+    const double centre[3] = {cx, cy, cz};
+    tbox[p] = tri_box(lo, hi, centre, pad);
+}
+
+__device__ __forceinline__ FBox empty_box() {
+    FBox b;
+    for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
+    return b;
+}
+// box of a leaf child: the union of its records' boxes (min / max: the order inside the leaf does not matter)
+__device__ __forceinline__ FBox leaf_box(const FBox* __restrict__ tbox, int first, int count) {
+    FBox b = tbox[first];
+    for (int j = 1; j < count; ++j) b = merge(b, tbox[first + j]);
+    return b;
+}
+__device__ __forceinline__ void store_box(float* lo, float* hi, const FBox& b) {
+    for (int k = 0; k < 3; ++k) { lo[k] = b.lo[k]; hi[k] = b.hi[k]; }
+}
+__device__ __forceinline__ FBox load_box(const float* lo, const float* hi) {
+    FBox b;
+    for (int k = 0; k < 3; ++k) { b.lo[k] = lo[k]; b.hi[k] = hi[k]; }
+    return b;
+}
+
+// depth of every binary node (0: the root), made once per tree at its first refit: parents first, then every node counts its ancestors
+// (k_lbvh_emit's loop; a tree sr_build accepts is at most 62 deep)
+__global__ void k_refit_parents(int num_nodes, const BvhNode* __restrict__ nodes, int* __restrict__ parent) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_nodes) return;
+    if (i == 0) parent[0] = -1;
+    const BvhNode nd = nodes[i];
+    if (nd.n0 == 0 && nd.c0 > 0 && nd.c0 < num_nodes) parent[nd.c0] = i;
+    if (nd.n1 == 0 && nd.c1 > 0 && nd.c1 < num_nodes) parent[nd.c1] = i;
+}
+__global__ void k_refit_depths(int num_nodes, const int* __restrict__ parent, uint8_t* __restrict__ depth) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_nodes) return;
+    int d = 0;
+    for (int p = parent[i]; p >= 0 && p < num_nodes && d < 255; p = parent[p]) ++d;
+    depth[i] = (uint8_t)d;
+}
+
+// both child boxes of binary node i: a leaf child from the records' boxes, an inner child from that node's two child boxes
+__device__ __forceinline__ void refit_node2(BvhNode* nodes, int i, const FBox* __restrict__ tbox) {
+    BvhNode* nd = nodes + i;
+    const int c[2] = {nd->c0, nd->c1}, cn[2] = {nd->n0, nd->n1};
+    for (int side = 0; side < 2; ++side) {
+        if (cn[side] < 0) continue;                                   // empty child: its (inverted) box stays
+        FBox b;
+        if (cn[side] > 0) b = leaf_box(tbox, c[side], cn[side]);
+        else {
+            const BvhNode* ch = nodes + c[side];
+            b = empty_box();
+            if (ch->n0 >= 0) b = merge(b, load_box(ch->lo0, ch->hi0));
+            if (ch->n1 >= 0) b = merge(b, load_box(ch->lo1, ch->hi1));
+        }
+        if (side == 0) store_box(nd->lo0, nd->hi0, b); else store_box(nd->lo1, nd->hi1, b);
+    }
+}
+
+// The binary tree bottom-up, one launch per level, deepest first: the lanes of level `level` re-make their nodes from the records' boxes
+// and from the nodes one level down, which the launch before has finished -- no communication inside a kernel.  (The arrival-counter
+// walk of k_lbvh_boxes, one launch, was measured too: DESIGN.md 5.16.)
+__global__ void __launch_bounds__(256) k_refit_nodes2(int num_nodes, BvhNode* nodes, const FBox* __restrict__ tbox, const uint8_t* __restrict__ depth,
+                                                      int level) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_nodes || depth[i] != level) return;
+    refit_node2(nodes, i, tbox);
+}
+
+// The four-wide tree, one launch per level, deepest first (collapse_bvh4_device numbers the wide nodes level by level): no
+// communication inside a kernel.  A slot's box is the union over the same triangles as the binary child it was copied from, so the
+// wide boxes are again the binary tree's boxes bit for bit.
+__global__ void __launch_bounds__(256) k_refit_nodes4(int first, int count, Bvh4Node* wide, int num_wide, const FBox* __restrict__ tbox) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    Bvh4Node* nd = wide + first + t;
+    for (int j = 0; j < 4; ++j) {
+        const int c = nd->ch[j].c, cn = nd->ch[j].n;
+        if (cn < 0) continue;
+        FBox b;
+        if (cn > 0) b = leaf_box(tbox, c, cn);
+        else {
+            if (c <= first + t || c >= num_wide) continue;            // (children are numbered after their parent; anything else is not a tree of this library)
+            const Bvh4Node* ch = wide + c;
+            b = empty_box();
+            for (int k = 0; k < 4; ++k)
+                if (ch->ch[k].n >= 0) b = merge(b, load_box(ch->ch[k].lo, ch->ch[k].hi));
+        }
+        store_box(nd->ch[j].lo, nd->ch[j].hi, b);
+    }
+}
+
 // ---- the four-wide tree of the packet walks, collapsed on the device (same rule as sr_host.cpp collapse_bvh4: a node takes its two
 //      children and, while it has fewer than four, replaces the inner child with the largest box by that child's two children) ----
 // One launch per level of the wide tree: every item (binary node, wide-node slot) writes its wide node and appends its inner
@@ -340,8 +472,10 @@ __global__ void k_collapse_level(const BvhNode* __restrict__ nodes, const int2* 
     wide[item.y] = w;
 }
 
-hipError_t collapse_bvh4_device(const BvhNode* d_nodes, int num_nodes, Bvh4Node* d_wide, int* num_wide, int* depth, hipStream_t stream) {
+hipError_t collapse_bvh4_device(const BvhNode* d_nodes, int num_nodes, Bvh4Node* d_wide, int* num_wide, int* depth, hipStream_t stream,
+                                std::vector<int>* level_first) {
     *num_wide = 0; *depth = 0;
+    if (level_first) level_first->assign(1, 0);
     if (num_nodes <= 0) return hipSuccess;
     Tmp la, lb, ctr;
     LB_HIP(la.alloc((size_t)num_nodes * sizeof(int2)));
@@ -363,6 +497,7 @@ hipError_t collapse_bvh4_device(const BvhNode* d_nodes, int num_nodes, Bvh4Node*
         LB_HIP(hipMemcpyAsync(c, ctr.p, 8, hipMemcpyDeviceToHost, stream));
         LB_HIP(hipStreamSynchronize(stream));
         n_in = c[1];
+        if (level_first) level_first->push_back(*num_wide ? *num_wide : 1);   // this level ended where the next one's slots begin
         *num_wide = c[0];
         LB_HIP(hipMemsetAsync(ctr.as<int>() + 1, 0, 4, stream));
         std::swap(in, out);
@@ -395,6 +530,54 @@ hipError_t tri_bounds_device(const double* d_v9, int n, const double box_min[3],
     LB_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_tri_bounds_fold, dim3(1), dim3(kBoundsThreads), 0, stream, (const double*)(d_scratch + 6), blocks, box, d_scratch);
     return hipGetLastError();
+}
+
+// sr_refit_triangles_device, the tree's part.  d_tbox: n x refit_box_bytes() of scratch; d_depth: num_nodes bytes, made here when
+// !*depths_made (once per tree); tree_depth: sr_build's depth of the binary tree; level_first:
+// collapse_bvh4_device's level ranges of the wide tree.
+// get_events(user, phase, &start, &stop): optional timing, phase 0 = k_refit_leaves, 1 = the node kernels of both trees.
+size_t refit_box_bytes() { return sizeof(FBox); }
+hipError_t refit_bvh_device(const double* d_v9, const Rec128* d_tris, int n, const RootBox& root, Rec128* d_btris, TriSlab* d_bslab, BvhNode* d_nodes,
+                            int num_nodes, int tree_depth, Bvh4Node* d_wide, int num_wide, const std::vector<int>& level_first, void* d_tbox,
+                            uint8_t* d_depth, bool* depths_made, hipStream_t stream,
+                            void (*get_events)(void* user, int phase, hipEvent_t* start, hipEvent_t* stop), void* user) {
+    if (n <= 0 || num_nodes <= 0 || tree_depth < 1 || tree_depth > 255) return hipErrorInvalidValue;
+    if (level_first.size() < 2 || level_first.front() != 0 || level_first.back() != num_wide) return hipErrorInvalidValue;
+    double ext = 0;
+    for (int a = 0; a < 3; ++a) ext = std::max(ext, root.max[a] - root.min[a]);
+    const float pad = (float)std::ldexp(ext > 0 ? ext : 1.0, -16);     // build_bvh_device's pad, of the NEW root
+    const int T = 256;
+    const dim3 node_grid((unsigned)((num_nodes + T - 1) / T));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (!*depths_made) {                                               // (the parents live in d_tbox until k_refit_leaves overwrites it: 4 B x num_nodes < 24 B x n)
+        if ((size_t)num_nodes * sizeof(int) > (size_t)n * sizeof(FBox)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_refit_parents, node_grid, dim3(T), 0, stream, num_nodes, (const BvhNode*)d_nodes, (int*)d_tbox);
+        LB_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_refit_depths, node_grid, dim3(T), 0, stream, num_nodes, (const int*)d_tbox, d_depth);
+        LB_HIP(hipGetLastError());
+        *depths_made = true;
+    }
+    if (get_events) get_events(user, 0, &e0, &e1);
+    if (e0) LB_HIP(hipEventRecord(e0, stream));
+    hipLaunchKernelGGL(k_refit_leaves, dim3((unsigned)((n + T - 1) / T)), dim3(T), 0, stream, n, d_v9, d_tris, root.centre[0], root.centre[1],
+                       root.centre[2], pad, d_btris, d_bslab, (FBox*)d_tbox);
+    LB_HIP(hipGetLastError());
+    if (e1) LB_HIP(hipEventRecord(e1, stream));
+    e0 = e1 = nullptr;
+    if (get_events) get_events(user, 1, &e0, &e1);
+    if (e0) LB_HIP(hipEventRecord(e0, stream));
+    for (int level = tree_depth - 1; level >= 0; --level) {            // (a node's depth is at most tree_depth - 2: the leaf level counts)
+        hipLaunchKernelGGL(k_refit_nodes2, node_grid, dim3(T), 0, stream, num_nodes, d_nodes, (const FBox*)d_tbox, (const uint8_t*)d_depth, level);
+        LB_HIP(hipGetLastError());
+    }
+    for (size_t lv = level_first.size() - 1; lv-- > 0;) {
+        const int first = level_first[lv], count = level_first[lv + 1] - first;
+        if (count <= 0) continue;
+        hipLaunchKernelGGL(k_refit_nodes4, dim3((unsigned)((count + T - 1) / T)), dim3(T), 0, stream, first, count, d_wide, num_wide, (const FBox*)d_tbox);
+        LB_HIP(hipGetLastError());
+    }
+    if (e1) LB_HIP(hipEventRecord(e1, stream));
+    return hipSuccess;
 }
 
 // Leaf-order copies of the FP64 records and the fp32 shaft records: out[p] = in[order[p]] (the host SAH build ships only its

@@ -67,6 +67,15 @@ class GpuScene:
         hipStream_t or a torch.cuda.Stream); no host copy of the geometry is made.  v9: a contiguous float64 torch tensor [n, 3, 3] on
         the scene's device, or a raw device pointer with `n`; argb: an int32 / uint32 tensor [n] (or pointer), None = every triangle
         keeps its colour (same n as the current model).  bmin / bmax are host values."""
+        self._from_device(_lib.lib().sr_set_triangles_device, v9, argb, bmin, bmax, stream, n)
+
+    def refit_triangles_device(self, v9, argb, bmin, bmax, stream=0, n=None):
+        """sr_refit_triangles_device: new vertices for a mesh that only moves -- arguments as set_triangles_device -- with the
+        device-built own BVH REFIT instead of dropped: no build() is needed before the next MODE_BVH frame.  The tree keeps the shape
+        of its build: after a large deformation frames get slower (never wrong), and the caller decides when to build() again."""
+        self._from_device(_lib.lib().sr_refit_triangles_device, v9, argb, bmin, bmax, stream, n)
+
+    def _from_device(self, call, v9, argb, bmin, bmax, stream, n):
         def device_array(x, what, dtypes, shape_ok):
             if x is None:
                 return None, None
@@ -94,8 +103,7 @@ class GpuScene:
         if bmin.size != 3 or bmax.size != 3:
             raise ValueError("bmin and bmax are three doubles each")
         st = getattr(stream, "cuda_stream", stream)
-        _check(_lib.lib().sr_set_triangles_device(self._h, C.c_void_p(pv) if pv else None, C.c_void_p(pa) if pa else None, nv,
-                                                  _p(bmin), _p(bmax), C.c_void_p(st) if st else None))
+        _check(call(self._h, C.c_void_p(pv) if pv else None, C.c_void_p(pa) if pa else None, nv, _p(bmin), _p(bmax), C.c_void_p(st) if st else None))
 
     def load_3ds(self, data):
         buf = np.frombuffer(bytes(data), dtype=np.uint8)

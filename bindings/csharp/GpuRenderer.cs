@@ -90,6 +90,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_set_voxel_res(IntPtr scene, int n);
         [DllImport(Lib)] public static extern int sr_get_voxel_res(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_reset_light_field(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_set_light_field_shadows(IntPtr scene, int on);
+        [DllImport(Lib)] public static extern int sr_get_light_field_shadows(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_get_light_field(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_bake_light_field(IntPtr scene, ref SrFrame frame, ulong first, ulong count, out ulong filled);
@@ -426,6 +428,14 @@ namespace Engine3D.Hip
         {
             get { return Native.sr_get_light_field_res(scene); }
             set { Native.Check(Native.sr_set_light_field_res(scene, value)); }
+        }
+        /// Opt-in: SR_F_LIGHT_FIELD together with dynamic SR_F_SHADOWS (rayTraceLightField + rayTraceShadows, RendererTests.cs:240): the canonical
+        /// rays go through ShadowMethod and the table stores shadowed colours.  Off (the default): that pair is SR_ERR_UNSUPPORTED.  Static
+        /// shadows, AO, path tracing, voxels, mirror bounces, the one-kernel renderer and strips stay refused.  Does not touch the table.
+        public bool LightFieldShadows
+        {
+            get { return Native.sr_get_light_field_shadows(scene) != 0; }
+            set { Native.Check(Native.sr_set_light_field_shadows(scene, value ? 1 : 0)); }
         }
         /// A new Renderer starts with an empty light field (LightFieldColorMethod.cs:101-115)
         public void ResetLightField() { Native.Check(Native.sr_reset_light_field(scene)); }

@@ -152,7 +152,7 @@ enum {
                                      library's, so a sample whose scaled coordinate lies within an ulp or so of an integer may fall into the neighbouring cell.
                                      Works with SR_F_SHADING, the lights, sub_pixel_res, SR_F_FOCAL_BLUR, row ranges, extra geometry, all three trace modes,
                                      host- and device-built BVH and frames of more than one row band.  The frame runs as one pipeline (as with SR_F_NO_SPLIT);
-                                     a multi-device scene renders it on devices[0] alone.  SR_ERR_UNSUPPORTED together with SR_F_SHADOWS (dynamic or static),
+                                     a multi-device scene renders it on devices[0] alone.  SR_ERR_UNSUPPORTED together with SR_F_SHADOWS (static always; dynamic unless sr_set_light_field_shadows),
                                      SR_F_AMBIENT_OCCLUSION, SR_F_PATH_TRACING, SR_F_VOXELS, max_bounces > 0, SR_F_SINGLE_KERNEL, strip_count > 0 and
                                      sr_rccl_render.  Not covered: LightFieldStoresTriangles = true (LightFieldTriMethod) and quad-linear interpolation
                                      (LightFieldColorMethod.Interpolate, hard-wired false in the reference).
@@ -416,6 +416,22 @@ int  sr_set_light_field(sr_scene*, const uint32_t* in, uint64_t first, uint64_t 
  * synchronisation in between.  A multi-device scene bakes on its first device, where the table lives.  sr_last_ray_stats afterwards: [0..3] = 0,
  * [4] = canonical rays traced (one per entry written, none for NaN rays), [5..7] = what their walks counted (0 with SR_F_PRIMARY_STATS_ONLY). */
 int  sr_bake_light_field(sr_scene*, const sr_frame* frame, uint64_t first, uint64_t count, uint64_t* filled /* or NULL */);
+/* The light field over ShadowMethod, opt-in per scene.  In the reference LightFieldColorMethod is the outermost decorator (Renderer.cs:1640-1649):
+ * with rayTraceShadows a cell's canonical ray goes through ShadowMethod and the table stores SHADOWED colours (the active test
+ * RaytraceLightField_Colors, RendererTests.cs:240).  The offset table is made once from the seed and the shadow step reads only the hit point,
+ * the normal and the light, so the shadowed colour of a cell is still a function of the cell alone.  on = 1: sr_render, sr_render_device and
+ * sr_bake_light_field accept SR_F_LIGHT_FIELD | SR_F_SHADOWS without SR_F_STATIC_SHADOWS -- the canonical rays that hit are queued and take the
+ * frame's dynamic shadow stage (shadow_samples, area_light_offsets, point or directional light, SR_F_PER_LANE_SHADOWS, SR_F_LITERAL_SECONDARY
+ * as in any frame) before their colours are stored; no host synchronisation inside a frame, and the bake cuts its range into passes of at most
+ * 2^22 cells so that the stage's scratch does not depend on the size of the table.  Every other refusal of a light-field frame stays: static
+ * shadows, SR_F_AMBIENT_OCCLUSION, SR_F_PATH_TRACING, SR_F_VOXELS, max_bounces > 0, SR_F_SINGLE_KERNEL, strip_count > 0, sr_rccl_render.
+ * on = 0 (the default): SR_F_LIGHT_FIELD | SR_F_SHADOWS is SR_ERR_UNSUPPORTED, as before.  Anything else: SR_ERR_INVALID_ARG.  A setting like the
+ * resolution: it works on a host-only scene, survives sr_set_triangles* / sr_load_3ds, and a multi-device scene forwards it to its parts.  It does
+ * not touch the table: an entry keeps whatever the frame that filled it stored -- pose, lights and, now, whether it was shadowed; a frame with the
+ * switch on but without SR_F_SHADOWS runs exactly what it ran before.  Statistics of a shadowed light-field frame or bake: [4..7] grow by the
+ * canonical rays plus what the shadow stage counts for a frame; all of [4..7] stay 0 with SR_F_PRIMARY_STATS_ONLY. */
+int  sr_set_light_field_shadows(sr_scene*, int32_t on);
+int32_t sr_get_light_field_shadows(const sr_scene*);
 /* Same, but `d_pixels` is DEVICE memory on the scene's device (e.g. a torch tensor's data_ptr) and the
  * work is enqueued on `hip_stream` (a hipStream_t; NULL = the null stream) without host sync. */
 /* Ordering: the work is enqueued behind everything already on `hip_stream` and `hip_stream` continues only after it; a
@@ -552,7 +568,8 @@ int  sr_anti_alias_device(sr_scene*, const void* d_src, int32_t dst_width, int32
 /* Test / experiment hooks of ONE scene.  The library never reads the process environment: a drop-in must not change its
  * schedule with the host's env.  value < 0 restores the default.  Used by tests/ and scripts/ only. */
 enum {
-    SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands             */
+    SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
+                                    per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
     SR_DBG_SPLIT          = 3,   /* concurrent part-frame pipelines (default 2, <= 4)                                          */
@@ -565,7 +582,8 @@ enum {
                                     private per-lane walks (k_pt_finish) instead of the mirror extension's prepare / walk route; 34 the ambient-occlusion probes of a
                                     SR_MODE_BVH frame as nearest-hit walks instead of any-hit walks with the limit 2.0; 35 sr_bake_light_field on a
                                     SR_MODE_BVH frame with one packet walk per wave of 64 same-origin canonical rays instead of private per-lane
-                                    walks (same table; measured slower); 100 + T: the walk kernel
+                                    walks (same table; measured slower); 36 the shadow stage of a shadowed light-field frame's lazy fill with the
+                                    packet shaft walk instead of private per-lane shaft walks (same table; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid
                                     too (its loop form spills registers: opt-in); 84 the persistent shaft walk hands its tiles out in natural order

@@ -45,7 +45,7 @@ SYMBOLS = [
     "sr_net_random_doubles", "sr_build_voxels", "sr_get_voxels", "sr_reset_ao_cache", "sr_get_ao_cache", "sr_set_ao_cache",
     "sr_set_light_field_res", "sr_get_light_field_res", "sr_reset_light_field", "sr_get_light_field", "sr_set_light_field",
     "sr_bake_light_field", "sr_set_voxel_res", "sr_get_voxel_res", "sr_set_triangles_device",
-    "sr_refit_triangles_device",
+    "sr_refit_triangles_device", "sr_set_light_field_shadows", "sr_get_light_field_shadows",
 ]
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
@@ -173,6 +173,8 @@ def lib():
     L.sr_get_light_field.restype = i32; L.sr_get_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
     L.sr_set_light_field.restype = i32; L.sr_set_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
     L.sr_bake_light_field.restype = i32; L.sr_bake_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp]
+    L.sr_set_light_field_shadows.restype = i32; L.sr_set_light_field_shadows.argtypes = [vp, i32]
+    L.sr_get_light_field_shadows.restype = i32; L.sr_get_light_field_shadows.argtypes = [vp]
     L.sr_net_random_doubles.restype = None; L.sr_net_random_doubles.argtypes = [i32, i64, i64, vp]
     L.sr_last_error.restype = C.c_char_p; L.sr_last_error.argtypes = []
     L.sr_abi_version.restype = i32; L.sr_abi_version.argtypes = []

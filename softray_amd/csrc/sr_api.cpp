@@ -144,6 +144,7 @@ struct sr_scene {
     // entries sr_set_light_field gave it on the host (empty vector: all zeros)
     DBuf d_lf_cache, d_lf_claim, d_lf_points;
     int32_t lf_res = 64;                 // lightFieldRes, Renderer.cs:93
+    bool lf_shadows = false;             // sr_set_light_field_shadows: SR_F_LIGHT_FIELD | SR_F_SHADOWS (dynamic) is accepted; a setting, like lf_res
     int32_t lf_points_res = 0;           // the resolution d_lf_points was made for (0: none)
     bool lf_cache_empty = true;          // the device cache (and the claim bits) must be zeroed before their next use
     std::vector<uint32_t> lf_cache_host;
@@ -189,6 +190,7 @@ struct sr_scene {
         DBuf pt_flags, pt_index, pt_totals, pt_carry;   // path tracing: hit flags, hit-index scan, row-block carries (sr_pipeline.hip k_pt_*)
         DBuf ao_escapes;                   // ambient occlusion: escaped probes, then the byte, per generator (sr_pipeline.hip k_ao_*)
         DBuf lf_cells, lf_list;            // light field: cache index per sample, the cells the band fills (sr_pipeline.hip k_lf_*)
+        DBuf lf_stage;                     // ... with shadows: the staged colour of every slot of the fill's / a bake pass's hit queue
         DBuf accum;                        // escape counts per sample index of a chunked (> 128 samples) shadow stage; zero between frames
         DBuf tile_cost, tile_order;        // walk length per 8x8 tile of the last shaft launch / the next one's longest-first lists
         unsigned long long tile_order_tag = 0;   // the tile grid tile_order was made for (0: none)
@@ -198,7 +200,7 @@ struct sr_scene {
         bool used_last_frame = false;
         void release() {
             tile_cost.release(); tile_order.release(); tile_order_tag = 0;
-            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &ao_escapes, &lf_cells, &lf_list, &pt_flags, &pt_index, &pt_totals, &pt_carry};
+            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &ao_escapes, &lf_cells, &lf_list, &lf_stage, &pt_flags, &pt_index, &pt_totals, &pt_carry};
             for (DBuf* x : b) x->release();
             for (int r = 0; r < sr::kShaftRounds; ++r) { rlist[r].release(); rstate[r].release(); rcount[r].release(); rcand[r].release(); }
             if (stream) (void)hipStreamDestroy(stream);
@@ -244,6 +246,9 @@ const int kMaxShaftSamples = 1024;       // area-light samples the shaft path ta
 const long long kMaxPathTable = 256ll << 20;   // bytes of the path tracer's random table (include/softray.h SR_F_PATH_TRACING)
 const int kAoRes = 128;                  // staticShadowRes, the resolution Renderer hands AmbientOcclusionMethod (Renderer.cs:1635)
 const size_t kAoCells = (size_t)kAoRes * kAoRes * kAoRes;
+// cells per pass of sr_bake_light_field with shadows: what the pass's hit queue (64 B per cell), staging buffer and the shadow stage's
+// candidate lists (about 0.6 KB per cell) are sized for -- 2.6 GB of scratch at 2^22, whatever the size of the table
+const long long kBakeShadowPassCells = 1ll << 22;
 const int kMaxLightFieldRes = 128;       // 4 N^4 entries: 4 GiB at 128 (and the reference's coordinates are bytes: 2 N - 1 <= 255)
 size_t lf_entries(int n) { return (size_t)4 * n * n * n * n; }
 const int kMaxTreeDepth = 62;            // (depth + 2) stack levels x 256 lanes x 4 B = 64 KB of LDS per workgroup
@@ -388,9 +393,11 @@ int check_ambient_occlusion(const sr_frame* f) {
 
 // SR_F_LIGHT_FIELD: the colour light field replaces the camera rays' walk; the decorators that need a surface point per camera sample (or
 // whose caches the canonical rays would fill) are not composable with it in one sitting (include/softray.h)
-int check_light_field(const sr_frame* f) {
+// (sr_set_light_field_shadows lets DYNAMIC shadows through: the canonical rays' hits take the frame's shadow stage, the table stores
+// shadowed colours)
+int check_light_field(const sr_frame* f, bool dynamic_shadows_allowed) {
     if (!(f->flags & SR_F_LIGHT_FIELD)) return SR_OK;
-    if (f->flags & SR_F_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "light field together with shadows (dynamic or static) is not supported (a cell stores a colour, not a surface point)");
+    if ((f->flags & SR_F_SHADOWS) && !(dynamic_shadows_allowed && !(f->flags & SR_F_STATIC_SHADOWS))) return fail(SR_ERR_UNSUPPORTED, "light field together with shadows (dynamic or static) is not supported (a cell stores a colour, not a surface point)");
     if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "light field together with ambient occlusion is not supported (a cell stores a colour, not a surface point)");
     if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "light field together with path tracing is not supported (a cell stores a colour, not a surface point)");
     if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "light field together with voxel rendering is not supported");
@@ -419,7 +426,8 @@ int check_frame_mode(const sr_scene* s, const sr_frame* f) {
     return check_mode(s, f->trace_mode);
 }
 
-int validate_frame(const sr_frame* f) {
+// `s`: the scene whose settings decide what a frame may combine (nullptr: the defaults)
+int validate_frame(const sr_frame* f, const sr_scene* s = nullptr) {
     if (!f) return fail(SR_ERR_INVALID_ARG, "frame is NULL");
     if (f->width <= 0 || f->height <= 0) return fail(SR_ERR_INVALID_ARG, "surface size must be positive");
     if (f->sub_pixel_res < 1 || f->sub_pixel_res > 64) return fail(SR_ERR_INVALID_ARG, "sub_pixel_res out of range");
@@ -429,7 +437,7 @@ int validate_frame(const sr_frame* f) {
     if ((long long)f->width * f->sub_pixel_res > (1ll << 24) || (long long)f->height > (1ll << 24)) return fail(SR_ERR_INVALID_ARG, "surface too large");
     if (f->max_bounces < 0 || f->max_bounces > 16 || !(f->reflectivity >= 0.0 && f->reflectivity <= 1.0))
         return fail(SR_ERR_INVALID_ARG, "max_bounces must be 0..16 and reflectivity 0..1");
-    int rc = check_light_field(f);
+    int rc = check_light_field(f, s && s->lf_shadows);
     if (!rc) rc = check_ambient_occlusion(f);
     if (!rc) rc = check_voxels(f);
     return rc ? rc : check_path_tracing(f);
@@ -645,7 +653,11 @@ int ensure_light_field(sr_scene* s, hipStream_t stream) {
 }
 
 // pt_phase: 0, or the phase (1, 2) of a part of a path-traced frame that multi_render has split (sr_device.h PipelineLaunch::pt_phase)
-int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0) {
+// sr_bake_light_field with shadows: the bake needs everything a shadowed frame sets up (the light's records and node order, the offset
+// table, the shadow stage's scratch), so it runs through render_common with no rows to render
+struct LfBakeReq { uint64_t first, count; unsigned long long* filled; };
+
+int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0, const LfBakeReq* bake = nullptr) {
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
@@ -658,7 +670,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     if ((rc = prepare_frame(s, f, fc))) return rc;
     if ((rc = sync_geometry(s, voxels ? ~0u : (uint32_t)f->trace_mode))) return rc;
     if (voxels && (rc = ensure_voxels(s, stream))) return rc;
-    if (fc.num_rows == 0) return SR_OK;
+    if (fc.num_rows == 0 && !bake) return SR_OK;
     // ---- frames of one scene run in submission order whatever streams they are given: the scene's scratch (hit queues, candidate
     //      lists, counters) and its per-origin / per-light records belong to one frame at a time.  `pre_used` is recorded when everything
     //      a frame enqueues is on its stream; the next frame's stream waits for it (a no-op on the same stream) ----
@@ -786,7 +798,8 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     //     a hit point or a triangle can be in, no sample of no hit point is occluded: rayEscapeCount = softShadowQuality, the factor
     //     is the constant (byte)(1.0 * 255) (applied by k_primary).  Extra geometry (unbounded planes) and the static cache (its
     //     cells are renderer state) keep the literal path.
-    if ((fc.flags & SR_F_SHADOWS) && !(fc.flags & SR_F_POINT_LIGHT) && !static_shadows && s->extra_recs.empty() &&
+    // (a light-field frame keeps the literal rays: the constant factor is k_primary's)
+    if ((fc.flags & SR_F_SHADOWS) && !(fc.flags & SR_F_POINT_LIGHT) && !static_shadows && s->extra_recs.empty() && !(f->flags & SR_F_LIGHT_FIELD) &&
         !(f->flags & (SR_F_SINGLE_KERNEL | SR_F_PER_LANE_SHADOWS)) && f->max_bounces == 0 && s->dbg[SR_DBG_LITERAL_SHADOWS] <= 0) {
         double diag2 = 0, len2 = 0;
         for (int a = 0; a < 3; ++a) {
@@ -938,7 +951,8 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     int want_split = 2;
     if (s->dbg[SR_DBG_SPLIT] > 0) want_split = (int)std::min<int64_t>(s->dbg[SR_DBG_SPLIT], (int)sr_scene::kMaxSplit);   // experiment hook
     const bool ao = (f->flags & SR_F_AMBIENT_OCCLUSION) != 0, ao_uncached = ao && (f->flags & SR_F_AO_UNCACHED);
-    const bool split = (shadows || bounce_pipe) && !static_shadows && !ao && want_split > 1 && fc.num_rows >= 32 * want_split && !(f->flags & SR_F_NO_SPLIT);
+    // (a light-field frame stays whole: a band's apply reads the cells the same band's fill stored)
+    const bool split = (shadows || bounce_pipe) && !static_shadows && !ao && !lf && want_split > 1 && fc.num_rows >= 32 * want_split && !(f->flags & SR_F_NO_SPLIT);
     const int halves = split ? want_split : 1;
     const int rows_half = split ? (int)((((long long)fc.num_rows + halves - 1) / halves + 15) / 16 * 16) : fc.num_rows;
     const long long budget = kMaxBandSamples / halves;
@@ -947,7 +961,13 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     const long long wpad = ((long long)fc.width + 15) / 16 * 16;
     long long band_rows = std::max<long long>(16, (budget / (wpad * n2)) / 16 * 16);
     band_rows = std::min<long long>(band_rows, ((long long)rows_half + 15) / 16 * 16);
-    const long long band_samples = band_rows * wpad * n2;
+    long long band_samples = band_rows * wpad * n2;
+    if (bake) {
+        // a bake pass: whole origin patches (2 N^2 cells each), at most kBakeShadowPassCells cells (SR_DBG_BAND_SAMPLES shrinks the pass), at least one patch
+        const long long per_origin = 2ll * s->lf_res * s->lf_res;
+        const long long want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? (long long)s->dbg[SR_DBG_BAND_SAMPLES] : kBakeShadowPassCells;
+        band_samples = std::max<long long>(1, want / per_origin) * per_origin;
+    }
     if (shaft && band_samples >= (1ll << 25)) return fail(SR_ERR_UNSUPPORTED, "row band too large for the 25-bit fallback entry ids (surface too wide for this sub-pixel resolution)");
     if (static_shadows) {
         if (band_rows < fc.num_rows) return fail(SR_ERR_UNSUPPORTED, "static shadows: the frame does not fit one row band");
@@ -1019,10 +1039,11 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         B.used_last_frame = true;
         if (shadows || bounce_pipe || path || ao) SR_HIP(B.hits.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
         if (ao) SR_HIP(B.ao_escapes.reserve((size_t)band_samples * 4));
-        if (lf) {
+        if (lf && !bake) {
             SR_HIP(B.lf_cells.reserve((size_t)band_samples * 4));
             SR_HIP(B.lf_list.reserve((size_t)band_samples * 4));
         }
+        if (lf && shadows) SR_HIP(B.lf_stage.reserve((size_t)band_samples * 4));
         if (path || ao) {
             SR_HIP(B.hits2.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
             SR_HIP(B.pt_flags.reserve((size_t)band_samples));
@@ -1055,7 +1076,8 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             SR_HIP(B.ray_sort_temp.reserve(sr::ray_sort_temp_bytes((unsigned)band_samples)));
         }
         // (one band per part-frame pipeline: a second band would walk other tiles with the first one's lists)
-        const bool order_tiles = shaft && band_rows >= rows_half;
+        // (a light-field frame's queue is compact: no tile grid whose walk lengths the next frame could use)
+        const bool order_tiles = shaft && band_rows >= rows_half && !lf;
         if (order_tiles) {
             const size_t bytes = sr::pipeline_tile_items(fc.width, (int)band_rows, (int)n2) * 4;
             if (bytes > B.tile_cost.cap) B.tile_order_tag = 0;
@@ -1074,11 +1096,12 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
                 if (r > 0) SR_HIP(B.rstate[r].reserve((size_t)round_items[r] * sr::pipeline_round_state_bytes()));
             }
         }
-        if (n2 > 1) SR_HIP(B.samples.reserve((size_t)band_samples * 4));
+        if (n2 > 1 && !bake) SR_HIP(B.samples.reserve((size_t)band_samples * 4));
         bool accum_fresh = false;
         if (chunked_shadows) {
-            // indexed like the sample buffer: the frame (or the compact strips) for one sample per pixel, band-local otherwise
-            const size_t idx_space = n2 == 1 ? (size_t)(f->strip_count > 0 ? fc.num_rows : fc.height) * fc.width : (size_t)band_samples;
+            // indexed like the sample buffer: the frame (or the compact strips) for one sample per pixel, band-local otherwise (a light field's
+            // shadow stage: the staging buffer, one word per queue slot)
+            const size_t idx_space = (n2 == 1 && !lf) ? (size_t)(f->strip_count > 0 ? fc.num_rows : fc.height) * fc.width : (size_t)band_samples;
             if (idx_space * 4 > B.accum.cap || !B.accum.p) {
                 SR_HIP(B.accum.reserve(idx_space * 4));
                 accum_fresh = true;                                // zeroed on the half's own stream below
@@ -1121,6 +1144,14 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.lf_entries = lf ? (uint32_t)lf_entries(s->lf_res) : 0u;
         P.lf_cells = lf ? (uint32_t*)B.lf_cells.p : nullptr;
         P.lf_list = lf ? (uint32_t*)B.lf_list.p : nullptr;
+        P.lf_shadows = lf && shadows;
+        P.lf_stage = (lf && shadows) ? (uint32_t*)B.lf_stage.p : nullptr;
+        if (bake) {
+            P.lf_bake_first = bake->first; P.lf_bake_count = bake->count;
+            P.lf_bake_pass_cells = (uint64_t)band_samples;
+            P.lf_bake_filled = bake->filled;
+            P.lf_bake_packet = s->dbg[SR_DBG_KERNEL_SWITCH] == 35;
+        }
         s->ao_table_seed = f->random_seed;
         s->ao_table_rc = SR_OK;
         P.ao_table = !ao ? nullptr : [](void* user, unsigned long long generators) -> const int32_t* {
@@ -1208,7 +1239,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             sc->band_recs.push_back({e, band, row_begin, row_count});
         };
         if (accum_fresh) SR_HIP(hipMemsetAsync(B.accum.p, 0, B.accum.cap, bs));
-        if (P.row_first < P.row_limit) {
+        if (P.row_first < P.row_limit || bake) {
             const hipError_t pe = sr::launch_pipeline(P);
             if (pe == hipErrorNotSupported && s->ao_table_rc) return s->ao_table_rc;      // (the message is the callback's)
             SR_HIP(pe);
@@ -2058,6 +2089,17 @@ int32_t sr_get_light_field_res(const sr_scene* s) {
     return s ? s->lf_res : 0;
 }
 
+int sr_set_light_field_shadows(sr_scene* s, int32_t on) {
+    if (!s || (on != 0 && on != 1)) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_light_field_shadows (0 or 1)");
+    s->lf_shadows = on != 0;                                        // (the table stays: an entry keeps what the frame that filled it stored)
+    for (sr_scene* part : s->parts) part->lf_shadows = on != 0;
+    return SR_OK;
+}
+
+int32_t sr_get_light_field_shadows(const sr_scene* s) {
+    return (s && s->lf_shadows) ? 1 : 0;
+}
+
 int sr_reset_light_field(sr_scene* s) {
     if (s && !s->parts.empty()) s = s->parts[0];
     if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_reset_light_field");
@@ -2121,7 +2163,7 @@ int sr_bake_light_field(sr_scene* m, const sr_frame* f, uint64_t first, uint64_t
     if (!(f->flags & SR_F_LIGHT_FIELD)) return fail(SR_ERR_INVALID_ARG, "sr_bake_light_field: the frame must carry SR_F_LIGHT_FIELD");
     const uint64_t entries = lf_entries(s->lf_res);
     if (first > entries || count > entries - first) return fail(SR_ERR_INVALID_ARG, "sr_bake_light_field: the range exceeds the 4 N^4 entries");
-    int rc = validate_frame(f);
+    int rc = validate_frame(f, s);
     if (rc) return rc;
     if ((rc = check_frame_mode(s, f))) return rc;
     if ((rc = use_device(s))) return rc;
@@ -2137,7 +2179,12 @@ int sr_bake_light_field(sr_scene* m, const sr_frame* f, uint64_t first, uint64_t
     // [0 .. SR_STATS_COUNT) the ray statistics, [SR_STATS_COUNT] the entries written
     uint64_t back[SR_STATS_COUNT + 1];
     SR_HIP(s->d_stats.reserve(sizeof(back)));
-    {
+    if (f->flags & SR_F_SHADOWS) {
+        // with shadows (validate_frame: the scene's switch is on): a frame's set-up, then passes of canonical rays + shadow stage + k_lf_store
+        SR_HIP(hipMemsetAsync(s->d_stats.p, 0, sizeof(back), stream));
+        const LfBakeReq req{first, count, (unsigned long long*)s->d_stats.p + SR_STATS_COUNT};
+        if ((rc = render_common(s, f, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, &req))) { (void)hipStreamSynchronize(stream); return rc; }
+    } else {
         // ordered like a frame: after whatever frame is in flight (it may be filling cells), and the next frame after the bake
         if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
         struct MarkPreUsed {
@@ -2181,7 +2228,7 @@ int sr_bake_light_field(sr_scene* m, const sr_frame* f, uint64_t first, uint64_t
 }
 
 static int multi_render(sr_scene* m, const sr_frame* f, int32_t* host_pixels, void* d_pixels, hipStream_t user_stream, uint64_t* stats4, uint64_t* d_stats) {
-    int rc = validate_frame(f);
+    int rc = validate_frame(f, m);
     if (rc) return rc;
     if (d_stats) return fail(SR_ERR_UNSUPPORTED, "device-side statistics are per device: use sr_render / sr_last_ray_stats with a multi-device scene");
     const int n = (int)m->parts.size();
@@ -2366,7 +2413,7 @@ int sr_render_device(sr_scene* s, const sr_frame* f, void* d_pixels, void* hip_s
         return multi_render(s, f, nullptr, d_pixels, (hipStream_t)hip_stream, nullptr, d_stats);
     }
     if (!s || !d_pixels) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_render_device");
-    int rc = validate_frame(f);
+    int rc = validate_frame(f, s);
     if (rc) return rc;
     if ((rc = check_frame_mode(s, f))) return rc;
     if ((rc = use_device(s))) return rc;
@@ -2381,7 +2428,7 @@ int sr_render(sr_scene* s, const sr_frame* f, int32_t* pixels, uint64_t stats[4]
         return multi_render(s, f, pixels, nullptr, nullptr, stats, nullptr);
     }
     if (!s || !pixels) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_render");
-    int rc = validate_frame(f);
+    int rc = validate_frame(f, s);
     if (rc) return rc;
     if ((rc = check_frame_mode(s, f))) return rc;
     if ((rc = use_device(s))) return rc;
@@ -2560,7 +2607,7 @@ int sr_rccl_init(sr_scene* s, const uint8_t id_bytes[SR_RCCL_ID_BYTES], int32_t 
 int sr_rccl_gather(sr_scene* s, const sr_frame* f, const void* d_strips, void* d_full, void* hip_stream) {
     if (!s || !s->parts.empty()) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_rccl_gather");
     if (!s->comm) return fail(SR_ERR_NOT_BUILT, "sr_rccl_gather before sr_rccl_init");
-    int rc = validate_frame(f);
+    int rc = validate_frame(f, s);
     if (rc) return rc;
     const sr::RcclApi* api = sr::rccl_api(nullptr);
     if (!api) return fail(SR_ERR_UNSUPPORTED, "librccl is not loaded");
@@ -2606,7 +2653,7 @@ int sr_rccl_gather(sr_scene* s, const sr_frame* f, const void* d_strips, void* d
 int sr_rccl_render(sr_scene* s, const sr_frame* f, void* d_full, void* hip_stream) {
     if (!s || !s->parts.empty()) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_rccl_render");
     if (!s->comm) return fail(SR_ERR_NOT_BUILT, "sr_rccl_render before sr_rccl_init");
-    int rc = validate_frame(f);
+    int rc = validate_frame(f, s);
     if (rc) return rc;
     if (f->strip_count > 0) return fail(SR_ERR_INVALID_ARG, "sr_rccl_render splits the frame itself: strip_count must be 0");
     if ((f->flags & SR_F_STATIC_SHADOWS) && (f->flags & SR_F_SHADOWS)) return fail(SR_ERR_UNSUPPORTED, "static shadows need the whole frame on one device");
@@ -2626,7 +2673,7 @@ int sr_rccl_render(sr_scene* s, const sr_frame* f, void* d_full, void* hip_strea
 int sr_shade_points(sr_scene* s, const sr_frame* f, int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out) {
     if (s && !s->parts.empty()) s = s->parts[0];
     if (!s || n < 0 || (n > 0 && (!pos || !normal || !color || !out))) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_shade_points");
-    int rc = validate_frame(f);
+    int rc = validate_frame(f, s);
     if (rc) return rc;
     if ((rc = use_device(s))) return rc;
     if (n == 0) return SR_OK;

@@ -121,6 +121,15 @@ struct PipelineLaunch {
     uint32_t      lf_entries;   // 4 N^4
     uint32_t*     lf_cells;     // device [band samples]: cache index per sample, 0xFFFFFFFF = the sample's line misses the sphere
     uint32_t*     lf_list;      // device [band samples]: the cells the band fills
+    // ... with dynamic shadows (sr_set_light_field_shadows + SR_F_SHADOWS): the canonical rays' hits go through the frame's shadow stage as a
+    // compact queue in `hits` (sample = queue slot, pad[1] = the cell), their colours wait in lf_stage, k_lf_store writes the cells
+    bool          lf_shadows;
+    uint32_t*     lf_stage;     // device [band samples]: the staged colour of every queue slot (the shadow stage's "sample buffer")
+    // sr_bake_light_field with shadows (lf_bake_count > 0: launch_pipeline renders no rows): the range, the cells per pass -- band samples,
+    // what the queue, lf_stage and the shadow stage's lists hold -- and where the entries written are counted
+    uint64_t      lf_bake_first, lf_bake_count, lf_bake_pass_cells;
+    unsigned long long* lf_bake_filled;
+    bool          lf_bake_packet;   // BakeLaunch::packet
     void*         static_hits;  // device HitRec[min(band samples, 128^3)]: generators of a static-shadow frame
     unsigned long long* static_claim; // device [128^3]: smallest order key that asked for an empty cell
     int32_t       static_concurrency; // rayTraceConcurrency of the frame

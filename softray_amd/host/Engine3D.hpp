@@ -222,6 +222,10 @@ public:
     void ResetLightField() { sr_check(sr_reset_light_field(scene_)); }           // what a new Renderer's LightFieldColorMethod starts with
     int LightFieldResolution() const { return (int)sr_get_light_field_res(scene_); }   // lightFieldRes (Renderer.cs:93): 64
     void LightFieldResolution(int n) { sr_check(sr_set_light_field_res(scene_, n)); }
+    // library opt-in (sr_set_light_field_shadows): rayTraceLightField together with DYNAMIC rayTraceShadows -- LightFieldColorMethod is the
+    // outermost decorator (Renderer.cs:1640-1649), so the table then stores shadowed colours (RendererTests.cs:240).  Off: CheckLightField refuses
+    bool LightFieldShadows() const { return sr_get_light_field_shadows(scene_) != 0; }
+    void LightFieldShadows(bool value) { sr_check(sr_set_light_field_shadows(scene_, value ? 1 : 0)); }
     // library extension: the reference has a constant there (voxelGridSize = 64, Renderer.cs:1570).  1..256; another value drops the grid,
     // which the next voxel frame makes again (sr_set_voxel_res)
     int VoxelGridSize() const { return (int)sr_get_voxel_res(scene_); }
@@ -396,7 +400,8 @@ private:
     void CheckLightField() const {
         if (lightFieldHasTris_)
             throw std::logic_error("rayTraceLightField with LightFieldStoresTriangles = true (LightFieldTriMethod) is out of scope: set it to false (SR_F_LIGHT_FIELD)");
-        if (rayTraceShadows) throw std::logic_error("rayTraceLightField together with rayTraceShadows is out of scope (SR_F_LIGHT_FIELD)");
+        if (rayTraceShadows && !(LightFieldShadows() && !rayTraceShadowsStatic))      // (dynamic shadows only, and only with the opt-in)
+            throw std::logic_error("rayTraceLightField together with rayTraceShadows is out of scope (SR_F_LIGHT_FIELD)");
         if (rayTraceAmbientOcclusion) throw std::logic_error("rayTraceLightField together with rayTraceAmbientOcclusion is out of scope (SR_F_LIGHT_FIELD)");
         if (rayTracePathTracing) throw std::logic_error("rayTraceLightField together with rayTracePathTracing is out of scope (SR_F_LIGHT_FIELD)");
         if (rayTraceVoxels) throw std::logic_error("rayTraceLightField together with rayTraceVoxels is out of scope (SR_F_LIGHT_FIELD)");

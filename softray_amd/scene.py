@@ -253,6 +253,15 @@ class GpuScene:
     def light_field_res(self, n):
         _check(_lib.lib().sr_set_light_field_res(self._h, int(n)))
 
+    @property
+    def light_field_shadows(self):
+        """Whether SR_F_LIGHT_FIELD | SR_F_SHADOWS (dynamic) is accepted: the table then stores shadowed colours (sr_set_light_field_shadows)."""
+        return bool(_lib.lib().sr_get_light_field_shadows(self._h))
+
+    @light_field_shadows.setter
+    def light_field_shadows(self, on):
+        _check(_lib.lib().sr_set_light_field_shadows(self._h, 1 if on else 0))
+
     def reset_light_field(self):
         """Forget the light field: what a new Renderer starts with."""
         _check(_lib.lib().sr_reset_light_field(self._h))

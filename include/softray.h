@@ -506,7 +506,7 @@ int  sr_kernel_times(sr_scene*, sr_kernel_time* out, int32_t cap);
  * FP64 triangle records tested, nodes fetched per lane, leaves} (also contained in [4..7]); [20..23] the same for the mirror
  * rays of the bounce pipeline (and for the second rays of a path-traced SR_MODE_BVH frame, which take the same walk; in every mode they
  * are counted in [4..7] unless SR_F_PRIMARY_STATS_ONLY is set; with SR_DBG_KERNEL_SWITCH 94 / 95 [22] and [23] hold the shadow classification's census
- * instead: hit points classified with / without the interior-triangle shortcut).  These are the counters the roofline's algorithmic bytes are priced from (DESIGN.md "Measurement"). */
+ * instead: hit points classified with / without the interior-triangle shortcut; with switch 98 [20..23] hold the umbra hints' census, see there).  These are the counters the roofline's algorithmic bytes are priced from (DESIGN.md "Measurement"). */
 int  sr_last_ray_stats(const sr_scene*, uint64_t out[SR_STATS_COUNT]);
 
 /* Seeded synthetic triangle soup = SpatialSubdivisionTests.MakeRandomTriangles
@@ -593,7 +593,12 @@ enum {
                                     inside the root box); 94 production path, and a frame rendered with ray statistics leaves the census of that
                                     shortcut in statistics [22] (hit points classified with the shortcut) and [23] (with the per-sample box exits)
                                     instead of the mirror rays' figures; 95 = 93 and 94 together; 96 the packet shaft walk filters its triangles with the
-                                    TriSlab records (shaft_touches_wave) instead of the per-light penumbra planes (LightCone); 41 a voxel walk on a grid of at most 64 reads the
+                                    TriSlab records (shaft_touches_wave) instead of the per-light penumbra planes (LightCone); 97 the persistent packet shaft walk without
+                                    its umbra hints (no tile tries the leaf runs the previous frame left before it walks, none are left); 98 production path, and
+                                    a frame rendered with ray statistics -- which otherwise walks without hints -- uses them and leaves in statistics [20] the walk
+                                    length (2 per node step + 1 per triangle filter) of all tiles, [21] that of the tiles that ended with every valid lane in
+                                    umbra, [22] the tiles that entered the walk with a lane finished by a hint, [23] the tiles that never took a node step, instead of
+                                    the mirror rays' figures; 99 a tile tries its own hint only, not those of the other three tiles of its 16x16 parent; 41 a voxel walk on a grid of at most 64 reads the
                                     colour table instead of the occupancy bits in LDS; 42 a voxel walk on a grid above 64 reads the row-major
                                     occupancy bits in global memory, one level, instead of the two-level walk                              */
     SR_DBG_KERNEL_TIMING  = 7,   /* > 0: record a HIP event pair around every launch (sr_kernel_times); default off           */

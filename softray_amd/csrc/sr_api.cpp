@@ -194,12 +194,16 @@ struct sr_scene {
         DBuf accum;                        // escape counts per sample index of a chunked (> 128 samples) shadow stage; zero between frames
         DBuf tile_cost, tile_order;        // walk length per 8x8 tile of the last shaft launch / the next one's longest-first lists
         unsigned long long tile_order_tag = 0;   // the tile grid tile_order was made for (0: none)
+        DBuf tile_hint[2];                 // umbra hint per 8x8 tile: what the last shaft launch left / what the next one writes (sr_umbra_hint.h)
+        int tile_hint_cur = 0;             // the one the next launch writes
+        uint64_t tile_hint_epoch = 0;      // sr_scene::records_epoch the words were made under (another: both arrays are refilled with "absent")
         DBuf rlist[sr::kShaftRounds], rstate[sr::kShaftRounds], rcount[sr::kShaftRounds], rcand[sr::kShaftRounds];
         hipStream_t stream = nullptr;
         hipEvent_t  done = nullptr;
         bool used_last_frame = false;
         void release() {
             tile_cost.release(); tile_order.release(); tile_order_tag = 0;
+            tile_hint[0].release(); tile_hint[1].release(); tile_hint_cur = 0; tile_hint_epoch = 0;
             DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &ao_escapes, &lf_cells, &lf_list, &lf_stage, &pt_flags, &pt_index, &pt_totals, &pt_carry};
             for (DBuf* x : b) x->release();
             for (int r = 0; r < sr::kShaftRounds; ++r) { rlist[r].release(); rstate[r].release(); rcount[r].release(); rcand[r].release(); }
@@ -230,6 +234,9 @@ struct sr_scene {
     hipEvent_t staged = nullptr;
     int num_cus = 0;
     bool tris_dirty = true, extra_dirty = true, ref_dirty = true, bvh_dirty = true;
+    // counts the changes of the own BVH's triangle records (a new model, a new tree, a refit): whatever names records by index across frames
+    // -- the shaft walk's umbra hints -- is dropped when it changes.  Starts at 1: a fresh scratch set's 0 never matches
+    uint64_t records_epoch = 1;
     std::vector<double>  offsets_host;
     std::vector<int32_t> rowmap_host;
     // kernel timing: one HIP event pair per launch, accumulated until sr_reset_kernel_times()
@@ -280,6 +287,7 @@ int upload_wide_tree(sr_scene* s, const sr::BvhNode* nodes, size_t num_nodes) {
     s->b4cam_valid = s->b4light_valid = false;
     s->blight_valid = false;
     s->part_valid = false;
+    s->records_epoch++;
     if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still be walking the old tree's copies
     SR_HIP(s->d_b4.upload(wide));
     SR_HIP(s->d_b4cam.reserve(wide.size() * sizeof(sr::Bvh4Node)));
@@ -289,7 +297,7 @@ int upload_wide_tree(sr_scene* s, const sr::BvhNode* nodes, size_t num_nodes) {
 
 int sync_geometry(sr_scene* s, uint32_t need_mode) {
     const sr_scene* h = s->host_src ? s->host_src : s;              // where the host arrays are
-    if (s->tris_dirty) { SR_HIP(s->d_tris.upload(h->tri_recs)); SR_HIP(s->d_v9.upload(h->v9)); s->tris_dirty = false; s->cam_valid = false; s->blight_valid = false; s->interior_valid = false; }
+    if (s->tris_dirty) { SR_HIP(s->d_tris.upload(h->tri_recs)); SR_HIP(s->d_v9.upload(h->v9)); s->tris_dirty = false; s->cam_valid = false; s->blight_valid = false; s->interior_valid = false; s->records_epoch++; }
     if (s->extra_dirty) { SR_HIP(s->d_extra.upload(s->extra_recs)); s->extra_dirty = false; }
     if (need_mode == SR_MODE_REF_TREE && s->ref_dirty) {
         SR_HIP(s->d_rnodes.upload(h->ref.nodes));
@@ -316,6 +324,7 @@ int sync_geometry(sr_scene* s, uint32_t need_mode) {
         s->bvh_num_nodes = h->bvh.nodes.size();
         s->bvh_dirty = false;
         s->cam_valid = false; s->blight_valid = false; s->interior_valid = false;
+        s->records_epoch++;
         int rc = upload_wide_tree(s, h->bvh.nodes.data(), h->bvh.nodes.size());
         if (rc) return rc;
     }
@@ -1078,11 +1087,16 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         // (one band per part-frame pipeline: a second band would walk other tiles with the first one's lists)
         // (a light-field frame's queue is compact: no tile grid whose walk lengths the next frame could use)
         const bool order_tiles = shaft && band_rows >= rows_half && !lf;
+        bool hints_fresh = false;                                  // the hint arrays are new, or name another scene's records: "absent" everywhere, on the half's own stream below
         if (order_tiles) {
             const size_t bytes = sr::pipeline_tile_items(fc.width, (int)band_rows, (int)n2) * 4;
             if (bytes > B.tile_cost.cap) B.tile_order_tag = 0;
             SR_HIP(B.tile_cost.reserve(bytes));
             SR_HIP(B.tile_order.reserve(bytes));
+            hints_fresh = bytes > B.tile_hint[0].cap || bytes > B.tile_hint[1].cap || !B.tile_hint[0].p || !B.tile_hint[1].p || B.tile_hint_epoch != s->records_epoch;
+            SR_HIP(B.tile_hint[0].reserve(bytes));
+            SR_HIP(B.tile_hint[1].reserve(bytes));
+            B.tile_hint_epoch = s->records_epoch;
         }
         if (shaft) {
             SR_HIP(B.fallback.reserve((size_t)band_samples * 4));
@@ -1186,6 +1200,8 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.tile_cost = order_tiles ? (unsigned int*)B.tile_cost.p : nullptr;
         P.tile_order = order_tiles ? (unsigned int*)B.tile_order.p : nullptr;
         P.tile_order_tag = order_tiles ? &B.tile_order_tag : nullptr;
+        for (int k = 0; k < 2; ++k) P.tile_hint[k] = order_tiles ? (unsigned int*)B.tile_hint[k].p : nullptr;
+        P.tile_hint_cur = order_tiles ? &B.tile_hint_cur : nullptr;
         P.shaft_launches = &s->dbg_frame[1];
         P.static_hits = static_shadows ? s->d_static_hits.p : nullptr;
         P.static_claim = static_shadows ? (unsigned long long*)s->d_static_claim.p : nullptr;
@@ -1239,6 +1255,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             sc->band_recs.push_back({e, band, row_begin, row_count});
         };
         if (accum_fresh) SR_HIP(hipMemsetAsync(B.accum.p, 0, B.accum.cap, bs));
+        if (hints_fresh) for (DBuf& hb : B.tile_hint) SR_HIP(hipMemsetAsync(hb.p, 0xFF, hb.cap, bs));
         if (P.row_first < P.row_limit || bake) {
             const hipError_t pe = sr::launch_pipeline(P);
             if (pe == hipErrorNotSupported && s->ao_table_rc) return s->ao_table_rc;      // (the message is the callback's)
@@ -1326,6 +1343,7 @@ void share_host_model(sr_scene* d, const sr_scene* src) {
     d->ref = sr::RefTree(); d->bvh = sr::Bvh(); d->bvh_on_device = false;
     d->tris_dirty = d->ref_dirty = d->bvh_dirty = true;
     d->cam_valid = false; d->blight_valid = false; d->interior_valid = false;
+    d->records_epoch++;
 }
 // ... and its host-built structures: the numbers a part needs (built / depth / counts), not the node arrays
 void share_ref_tree(sr_scene* d, const sr_scene* src) {
@@ -1352,6 +1370,7 @@ void drop_bvh(sr_scene* s) {
     s->bdepth_valid = false;
     s->b4cam_valid = s->b4light_valid = false;
     s->cam_valid = s->blight_valid = s->interior_valid = s->part_valid = false;
+    s->records_epoch++;
 }
 
 // The host arrays of a model that sr_set_triangles_device left on the device only: vertices and records are read back (the colours
@@ -1522,6 +1541,7 @@ int refit_from_device_enqueue(sr_scene* s, const double* src_v9, const uint32_t*
     // ---- the geometry is new, the tree is the old one: everything made FROM the records or the boxes is stale ----
     s->b4cam_valid = s->b4light_valid = false;
     s->cam_valid = s->blight_valid = s->interior_valid = s->part_valid = false;
+    s->records_epoch++;
     s->bvh_dirty = false;                                 // (kept: b4_num, b4_depth, bvh.built, bvh.depth, bvh_num_nodes, bvh_on_device)
     s->tris_dirty = false;
     s->shadow_cache_empty = true;                         // a new model: what sr_set_triangles_device drops

@@ -158,6 +158,12 @@ struct PipelineLaunch {
     unsigned int* tile_cost;
     unsigned int* tile_order;
     unsigned long long* tile_order_tag;
+    // umbra hints of the same walk (sr_umbra_hint.h): one word per 8x8 tile, indexed like tile_cost, in two arrays -- a launch reads the one the
+    // previous launch wrote and writes the other, so what it does is a function of the previous launch and not of which wave ran first.
+    // `tile_hint_cur` is host state of the scratch set: the array the next launch writes (it flips it).  Both 0xFFFFFFFF-filled by the owner
+    // whenever they are (re)allocated or the scene's records change.  nullptr: no hints
+    unsigned int* tile_hint[2];
+    int* tile_hint_cur;
     uint32_t* shaft_launches;   // host [2] or nullptr: += persistent launches of the shaft walk, += those that walked tile_order (sr_debug_counters [6], [7])
     hipStream_t stream;
     void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);   // optional per-launch timing

@@ -13,6 +13,7 @@
 // device functions of sr_trace.h do all result-affecting arithmetic.
 #include "sr_trace.h"
 #include "sr_light_cone.h"
+#include "sr_umbra_hint.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -109,6 +110,10 @@ __device__ __forceinline__ T kernarg_late(size_t offset) {
 
 // the first two arguments of the pipeline kernels as the kernel-argument segment holds them
 struct SceneFrameArgs { DevScene sc; FrameConst fc; };
+// ... and of k_shaft_pkt4, whose third argument is the umbra hints of its launch (sr_umbra_hint.h): `cur` != nullptr: every tile leaves its
+// word in cur[item]; `prev` != nullptr: the previous launch's words of the same tile grid; nrec: records in DevScene::blight
+struct HintArgs { const unsigned int* prev; unsigned int* cur; unsigned int nrec; unsigned int pad; };
+struct ShaftArgs { DevScene sc; FrameConst fc; HintArgs hint; };
 
 // Work distribution of the tile kernels (k_primary, k_shaft_pkt4).  Virtual block vb of the XCD-aware tile grid is one 16x16-pixel
 // tile, its four waves vq = 0..3 are the tile's 8x8-pixel quadrants.  Direct mode (heads == nullptr): workgroup = virtual block,
@@ -1099,13 +1104,17 @@ __device__ __forceinline__ void shaft_slabs(const Bvh4Child& ch, f2 Ixy, f2 Izz,
 // CONES: the triangle filter reads the frame's LightCone records (shaft_cones_wave) instead of the TriSlab records (shaft_touches_wave;
 // SR_DBG_KERNEL_SWITCH 96, or no room for the records): same verdicts where it matters -- a superset of the hitting pairs, umbra only where proven.
 template <bool STATS, int WAVES, bool PERSIST, int KNOWN = 0, bool CONES = false>
-__global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, FrameConst fc_arg, const HitRec* __restrict__ hits,
+__global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, FrameConst fc_arg, HintArgs hint_arg, const HitRec* __restrict__ hits,
                                                     const unsigned int* __restrict__ hit_count, int cap, int levels, int tile_n2, int tile_rows,
                                                     unsigned int* __restrict__ cand_count, int32_t* __restrict__ cand,
                                                     uint32_t* __restrict__ samples, unsigned int* __restrict__ work_count,
                                                     unsigned int* __restrict__ work_list, unsigned long long* stats,
                                                     unsigned int* __restrict__ tile_heads, unsigned int virtual_blocks,
                                                     const unsigned int* __restrict__ tile_order, unsigned int* __restrict__ tile_cost) {
+    // umbra hints (PERSIST && CONES only; HintArgs): a tile tries the leaf runs that put lanes of its 16x16 parent into umbra on the
+    // previous launch before it walks, and leaves the word of the run that did so this time.  Both pointers nullptr: the kernel as it was.
+    // Like the scene and the frame they are read from the kernel-argument segment where a tile needs them, not kept across the walk.
+    constexpr bool HINTS = PERSIST && CONES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int32_t* wnode = reinterpret_cast<int32_t*>(lds_pipe) + (size_t)wave * ((size_t)levels * 33);   // [levels] stacked node
@@ -1115,6 +1124,9 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
     uint32_t nodes = 0, leaves = 0, slabs = 0, points = 0;        // wave-level (uniform)
     uint32_t walk = 0;                                            // (persistent) node steps + triangle filters of the tile being walked
     uint32_t top21 = 0, top85 = 0;                                // (STATS) node steps in the top three / four levels of the tree (level order: node < 21 / < 85)
+    // (STATS, SR_DBG_KERNEL_SWITCH 98) walk lengths of all tiles / of the tiles that end with every valid lane in umbra; tiles that enter the walk with a
+    // lane finished by a hint / that never take a node step
+    uint32_t census_walk = 0, census_umbra_walk = 0, census_hinted = 0, census_nostep = 0;
     // A work item is ONE WAVE's 64 queue entries (an 8x8-pixel tile of surface points) of virtual block vb = the block of the one-
     // workgroup-per-16x16-tile grid that k_primary filled them from.  tile_heads == nullptr: this workgroup IS virtual block
     // blockIdx.x (one item per wave).  Otherwise the grid is persistent and every WAVE pulls items from per-XCD counters (see
@@ -1127,6 +1139,12 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
     // inputs here, the epilogue's there.  Read as plain kernel arguments the compiler hoists them -- and everything it derives from
     // them -- out of this loop and keeps it live across the walk (25 spilled SGPRs + 54 VGPRs); read in one piece at the top of
     // the loop they stay live from there to their uses (42 spilled VGPRs).  The walk itself only needs two pointers.
+    // what the item leaves for the next frame when it is padding of the super-tile grid or a background tile: no walk, no hint (k_tile_order and the
+    // next launch read the words of EVERY item); a tile that walks stores its walk length at its end and its hint where it finds one
+    if (PERSIST && lane == 0) {
+        if (tile_cost) tile_cost[feed.item] = 0u;
+        if constexpr (HINTS) { const HintArgs ha = tile_arg<PERSIST>(hint_arg, offsetof(ShaftArgs, hint)); if (ha.cur) ha.cur[feed.item] = kHintAbsent; }
+    }
     const DevScene sc = tile_arg<PERSIST>(sc_arg, offsetof(SceneFrameArgs, sc));      // (prologue: root box)
     const FrameConst fc = tile_arg<PERSIST>(fc_arg, offsetof(SceneFrameArgs, fc));  // (prologue: light, width)
     unsigned int slot_i = vb * 256u + vq * 64u + (unsigned)lane;
@@ -1134,7 +1152,7 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
         // tile-indexed queue (see k_primary): block b * n2 + sub-sample of this grid <-> block b of k_primary, same XCD
         int tile_x, tile_y;
         const int pb = (int)vb / tile_n2, si = (int)vb - pb * tile_n2;
-        if (!xcd_tile(pb, fc.width, tile_rows, tile_x, tile_y)) continue;
+        if (!xcd_tile(pb, fc.width, tile_rows, tile_x, tile_y)) continue;      // padding of the super-tile grid
         const int tiles_x = (fc.width + 15) >> 4;
         slot_i = ((unsigned)(tile_y * tiles_x + tile_x) * (unsigned)tile_n2 + (unsigned)si) * 256u + vq * 64u + (unsigned)lane;
     }
@@ -1142,7 +1160,7 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
     rec.sample = kInvalidHit;
     if (slot_i < total) rec = hits[slot_i];
     const bool valid = rec.sample != kInvalidHit;
-    if (PERSIST && tile_cost) { if (lane == 0) tile_cost[feed.item] = 0u; walk = 0u; }
+    if (PERSIST && tile_cost) walk = 0u;
     if (__ballot(valid) == 0ull) continue;                         // background tile
     const D3 lpos = mk(fc.light_pos_model[0], fc.light_pos_model[1], fc.light_pos_model[2]);
     const D3 E = valid ? mk(rec.pos[0], rec.pos[1], rec.pos[2]) + mk(rec.nrm[0], rec.nrm[1], rec.nrm[2]) * 0.001 : lpos * 0.5;   // ShadowMethod.cs:151
@@ -1165,6 +1183,51 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
     // lane masks in scalar registers (vote helpers, sr_device.h): lanes whose list overflowed / that lie in a triangle's umbra / that have their verdict
     lanemask trunc_m = 0ull, umbra_m = 0ull;
     lanemask done_m = ~vote(rec.sample != kInvalidHit);
+    // ---- umbra hints: the leaf runs that shadowed lanes of this tile's 16x16 parent on the previous frame, the tile's own first.  A lane in the
+    //      umbra of ONE triangle is black whichever triangle proves it (the epilogue), and shaft_cones_wave's umbra verdict rests on the record,
+    //      the surface point and the root box alone -- nothing a node's box test establishes -- so any record may be asked.
+    //      `take` is ignored: lists are made by the walk, a lane the hints do not finish gets exactly the list it gets without them ----
+    // the word this tile leaves for the next frame is stored where it is found (nothing of it is carried across the walk: the kernel sits at its
+    // register budget); "absent" was stored at the top of the iteration, and one lane's stores to one address arrive in program order
+    const auto leave_hint = [&](const uint32_t word) __attribute__((always_inline)) {
+        const HintArgs ha = tile_arg<PERSIST>(hint_arg, offsetof(ShaftArgs, hint));
+        if (ha.cur && lane == 0) ha.cur[feed.item] = word;
+    };
+    if constexpr (HINTS) {
+        const HintArgs ha = tile_arg<PERSIST>(hint_arg, offsetof(ShaftArgs, hint));
+        const unsigned int* hint_prev = ha.prev;
+        const unsigned int nrec = ha.nrec;
+        if (hint_prev) {
+            struct alignas(16) HintQuad { uint32_t w[4]; };
+            const unsigned int own = feed.item & 3u;
+            const HintQuad hq = load_uniform(reinterpret_cast<const HintQuad*>(hint_prev + (feed.item & ~3u)));   // (not written by this launch)
+            const unsigned int words = fc.debug == 99 ? 1u : 4u;       // (SR_DBG_KERNEL_SWITCH 99: the tile's own word only)
+            uint32_t seen0 = kHintAbsent, seen1 = kHintAbsent, seen2 = kHintAbsent;
+#pragma nounroll
+            for (unsigned int k = 0; k < words; ++k) {
+                const uint32_t w = pick4((int)((own + k) & 3u), hq.w[0], hq.w[1], hq.w[2], hq.w[3]);
+                const bool repeated = w == seen0 || w == seen1 || w == seen2;       // (absent words are "repeated" from the start)
+                seen2 = seen1; seen1 = seen0; seen0 = w;
+                uint32_t hc, hn;
+                if (repeated || !hint_unpack(w, nrec, hc, hn)) continue;
+                if (tile_cost) walk += hn;
+                lanemask got_m = 0ull;
+#pragma nounroll
+                for (uint32_t q = 0; q < hn; ++q) {
+                    lanemask take_m, in_umbra_m;
+                    shaft_cones_wave(&sc_arg.blight[hc + q], sr, ~done_m, take_m, in_umbra_m);
+                    got_m |= in_umbra_m;
+                    umbra_m |= in_umbra_m;
+                    done_m |= in_umbra_m;
+                    if (~done_m == 0ull) break;
+                }
+                if (got_m != 0ull) leave_hint(w);
+                if (~done_m == 0ull) break;
+            }
+            if (STATS) census_hinted += umbra_m != 0ull ? 1u : 0u;
+        }
+    }
+    const uint32_t nodes_before = nodes;
     int sp = 0;                      // wave-uniform: entries in LDS
     // the TOP of the stack lives in registers (node: wave-uniform, bound: one encoded 16-bit value per lane): most nodes of the lowest inner level
     // have leaf children only, so every other step ends in a pop -- two dependent LDS reads (the lanes' bounds, then the node) before the next node
@@ -1231,6 +1294,9 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
                 trunc_m |= take_m & ~room_m;
                 umbra_m |= in_umbra_m;
                 done_m |= trunc_m | umbra_m;
+                if constexpr (HINTS) {
+                    if (in_umbra_m != 0ull) leave_hint(((uint32_t)cc << 4) | (uint32_t)cn);      // (rare: a tile's lanes go into umbra once or twice; hint_unpack decides what the word is worth)
+                }
             }
         };
         if (n.ch[0].n > 0) leaf(n.ch[0].n, n.ch[0].c, h0);
@@ -1284,9 +1350,16 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
         }
     }
     if (STATS) points += (uint32_t)__popcll(__ballot(valid));
+    if (STATS) {
+        const bool all_umbra = (vote(rec.sample != kInvalidHit) & ~umbra_m) == 0ull;
+        census_walk += walk; census_umbra_walk += all_umbra ? walk : 0u;
+        census_nostep += nodes == nodes_before ? 1u : 0u;
+    }
     if (PERSIST && tile_cost && lane == 0) tile_cost[feed.item] = walk;      // (the next frame walks the longest tiles first: k_tile_order)
     }   // while (feed.next)
     if (STATS) block_stat_add(&stats[6], &stats[7], &stats[10], &stats[11], nodes, leaves, slabs, points);
+    // SR_DBG_KERNEL_SWITCH 98 (persistent launches; [20] .. [23] are the mirror extension's, which never runs with shadows)
+    if (STATS && PERSIST && fc_arg.debug == 98) block_stat_add(&stats[20], &stats[21], &stats[22], &stats[23], census_walk, census_umbra_walk, census_hinted, census_nostep);
     if (STATS && lane == 0) { atomicAdd(work_count - 2, top21); atomicAdd(work_count - 1, top85); }      // diagnostics: sr_debug_counters [4], [5] (free on the shaft path)
 }
 
@@ -4428,8 +4501,16 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
                 const bool keep_cost = heads && L.tile_cost && L.tile_order && L.tile_order_tag && L.fc.debug != 84;
                 const unsigned int* order = (keep_cost && *L.tile_order_tag == order_tag) ? L.tile_order : nullptr;
                 unsigned int* cost = keep_cost ? L.tile_cost : nullptr;
+                // umbra hints (persistent walk on the penumbra-plane records): this launch reads the words the previous launch of this scratch set left -- if
+                // that launch had this tile grid -- and writes the other array; SR_DBG_KERNEL_SWITCH 97: off.  Counted launches walk without them, so
+                // the statistics stay those of the plain walk (switch 98: with them, and the census in statistics [20] .. [23])
+                const bool hints = keep_cost && L.tile_hint[0] && L.tile_hint[1] && L.tile_hint_cur && L.sc.blight && L.fc.debug != 97 &&
+                                   (!L.stats || L.fc.debug == 98) && (unsigned)L.sc.ntris < kHintMaxRecords;
+                unsigned int* hint_cur = hints ? L.tile_hint[*L.tile_hint_cur & 1] : nullptr;
+                const unsigned int* hint_prev = (hints && *L.tile_order_tag == order_tag) ? L.tile_hint[(*L.tile_hint_cur & 1) ^ 1] : nullptr;
+                const HintArgs hint_args{hint_prev, hint_cur, (unsigned)L.sc.ntris, 0u};
                 const auto go = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)L.hits, count_ptr, cap, lv4, tn2, trows, L.round_cand_count[round], L.round_cand[round], samples, work0, L.round_list[0], L.stats, heads, vblocks, order, cost);
+                    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, hint_args, (const HitRec*)L.hits, count_ptr, cap, lv4, tn2, trows, L.round_cand_count[round], L.round_cand[round], samples, work0, L.round_list[0], L.stats, heads, vblocks, order, cost);
                 };
                 // 6 waves/SIMD (85 VGPRs): 5.16 ms on the headline frame; 7 waves (72 VGPRs, spills in the node step) 5.44; 5 waves 5.61
                 // ((near, far) planes in the light-ordered copy, as in the camera-ordered one, were measured: fewer instructions, more spills at
@@ -4454,6 +4535,7 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
                     default: go_known(std::integral_constant<int, 0>()); break;
                 }
                 if (keep_cost) { order_items = (vblocks >> 3) * 4u; order_new_tag = order_tag; }
+                if (hints) *L.tile_hint_cur ^= 1;                      // (what this launch wrote is the next one's `prev`)
                 if (heads && L.shaft_launches) { L.shaft_launches[0] += 1; if (order) L.shaft_launches[1] += 1; }
             } else if (first && !(L.per_lane_shaft & 1)) {
                 // round 1 on the binary tree (cross-check): one packet walk per 64 consecutive queue entries (one 8x8-pixel tile when the queue is tile-aligned)

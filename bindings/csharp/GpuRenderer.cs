@@ -95,6 +95,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_get_light_field(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_bake_light_field(IntPtr scene, ref SrFrame frame, ulong first, ulong count, out ulong filled);
+        [DllImport(Lib)] public static extern int sr_shadow_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, uint options);
+        [DllImport(Lib)] public static extern int sr_shadow_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -373,6 +375,40 @@ namespace Engine3D.Hip
             ulong filled;
             Native.Check(Native.sr_bake_light_field(scene, ref frame, first, count, out filled));
             return filled;
+        }
+
+        /// sr_shadow_points' option bit 0: 64 consecutive points are neighbours, a pass is queued in the order given (no ray sort)
+        public const uint POINTS_COHERENT = 1;
+
+        /// ShadowMethod's soft shadow for caller-given surface points (sr_shadow_points; ShadowMethod.cs:103-119, 144-179): result[i] = color[i]
+        /// (color == null: 0xFFFFFFFF) modulated with (byte)(escapes / 100.0 * 255) for the light, the seed's area-light offsets and the root
+        /// geometry of the frame these arguments describe (the same as Render's; F_SHADOWS is implied, the surface size is validated and
+        /// otherwise unused).  pos / normal: double[n * 3] in model space, the normal as given.  F_STATIC_SHADOWS, F_AMBIENT_OCCLUSION,
+        /// F_PATH_TRACING, F_VOXELS and F_LIGHT_FIELD name no step of ShadowMethod on a bare point: SR_ERR_UNSUPPORTED ->
+        /// InvalidOperationException.  Blocks.
+        public uint[] ShadowPoints(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode, int randomSeed,
+                                   Vector lightDirView, Vector lightPosView, double[] pos, double[] normal, uint[] color = null, bool coherent = false)
+        {
+            if (pos == null || normal == null || pos.Length != normal.Length || pos.Length % 3 != 0 || (color != null && color.Length != pos.Length / 3))
+                throw new ArgumentException("ShadowPoints: pos and normal are double[n * 3], color is uint[n] or null");
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, 0, height - 1, 1, randomSeed,
+                      1.0, 1.0, 0.0, 0.0, 0.0, lightDirView, lightPosView, 4);
+            frame.flags &= ~F_PRIMARY_STATS_ONLY;                  // the call has no primary rays
+            var result = new uint[pos.Length / 3];
+            Native.Check(Native.sr_shadow_points(scene, ref frame, result.Length, pos, normal, color, result, coherent ? POINTS_COHERENT : 0));
+            return result;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_shadow_points_device): enqueued on `stream` without a host
+        /// synchronisation; dColor may be IntPtr.Zero (every point 0xFFFFFFFF) or dOut itself; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void ShadowPointsDevice(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode, int randomSeed,
+                                       Vector lightDirView, Vector lightPosView, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut,
+                                       bool coherent, IntPtr stream, IntPtr dStats)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, 0, height - 1, 1, randomSeed,
+                      1.0, 1.0, 0.0, 0.0, 0.0, lightDirView, lightPosView, 4);
+            frame.flags &= ~F_PRIMARY_STATS_ONLY;
+            Native.Check(Native.sr_shadow_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, coherent ? POINTS_COHERENT : 0, stream, dStats));
         }
 
         /// The host half of RaytraceGeometry (Renderer.cs:1510-1528, 1652-1653): copy public fields into sr_frame.

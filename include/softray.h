@@ -468,6 +468,39 @@ int  sr_trace_rays_device(sr_scene*, int32_t target, int64_t n, const double* d_
 int  sr_shade_points(sr_scene*, const sr_frame* frame, int64_t n, const double* pos, const double* normal, const uint32_t* color,
                      uint32_t* out);
 
+/* ShadowMethod.IntersectRay's step in batch (ShadowMethod.cs:103-119, 144-179 TraceRaysForSoftShadows): the soft shadow of n caller-given
+ * surface points, through the stage a shadowed frame uses (packet shaft walk, per-light penumbra planes, fp32 classification with FP64
+ * fallback).  out[i] = ModulatePackedColor(color[i], (byte)(escapes_i / (double)S * 255)), S = frame->shadow_samples (0 => 100), escapes_i =
+ * the S sample rays towards pos[i] + normal[i] * 0.001 -- point or directional light, the seed's offset table or area_light_offsets -- that are
+ * not blocked (blocked: a hit with rayFrac <= 1.0) by the frame's root geometry: the extra geometry plus the model in trace_mode.  pos and
+ * normal are [n][3] in model space; the normal is used as given (not normalised, no facing test; zero is legal).  color == NULL: every point is
+ * 0xFFFFFFFF.  out may alias color.  Only the modulated colour is returned, which is what the decorator produces.
+ * Read from `frame`: inv_transform, light_pos_view, light_dir_view, SR_F_POINT_LIGHT, shadow_samples, random_seed, area_light_offsets,
+ * trace_mode and the library options SR_F_PER_LANE_SHADOWS, SR_F_LITERAL_SECONDARY, SR_F_PRIMARY_STATS_ONLY; SR_F_SHADOWS is implied; the
+ * camera fields are validated as for a frame and otherwise unused.
+ * Refused, in this order: n < 0, a NULL pos / normal / out with n > 0, a NULL frame or scene, unknown option bits: SR_ERR_INVALID_ARG; what
+ * names no step of ShadowMethod on a bare point -- SR_F_STATIC_SHADOWS, SR_F_AMBIENT_OCCLUSION, SR_F_PATH_TRACING, SR_F_VOXELS,
+ * SR_F_LIGHT_FIELD, SR_F_SINGLE_KERNEL, max_bounces > 0, strip_count > 0: SR_ERR_UNSUPPORTED; then sr_render's validation of the frame and its
+ * trace mode (SR_ERR_NOT_BUILT ...); then a host-only scene: SR_ERR_NO_DEVICE.  n == 0 that passes these checks: SR_OK, nothing is touched.
+ * A point never reaches a walk when its probe end E' = pos + normal * 0.001 is not finite: a NaN component of E' -- no geometry answers a
+ * ray with a NaN component -- lets all S samples escape; an infinite component does too as far as the model's triangles go, but the extra
+ * geometry can block such a ray (the reference's Plane answers an infinite direction with rayFrac 0), so these points' samples are tested
+ * against the extra primitives, with the reference's arithmetic, where the points are read.
+ * SR_POINTS_COHERENT (options bit 0) is the caller's promise that 64 consecutive points are neighbours (the hit points of a tile, say): the
+ * first shaft round takes one packet walk per 64 consecutive points of a pass in the order given.  Without it a pass is first ordered by
+ * (cell of the point in the root box, octant of the normal; points outside clamp to the edge cells).  Results never depend on it; speed does.
+ * Ordered like a frame (behind a frame of the scene in flight on any stream, the next frame behind it), on the scene's scratch, in passes
+ * of at most 2^22 points that follow each other without the host waiting; a multi-device scene runs it on devices[0].  The host variant
+ * blocks and leaves the shadow stage's counters in sr_last_ray_stats ([0..3] are 0, [4..] as for a frame, all 0 with
+ * SR_F_PRIMARY_STATS_ONLY); the device variant takes device arrays, enqueues on `hip_stream` without a host synchronisation and writes the
+ * counters to d_stats when given. */
+#define SR_POINTS_COHERENT 1u
+int  sr_shadow_points(sr_scene*, const sr_frame* frame, int64_t n, const double* pos, const double* normal, const uint32_t* color /* or NULL */,
+                      uint32_t* out, uint32_t options);
+int  sr_shadow_points_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_pos, const double* d_normal,
+                             const uint32_t* d_color /* or NULL */, uint32_t* d_out, uint32_t options, void* hip_stream,
+                             uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* n NextDouble() of new System.Random(seed) after `skip` samples have been drawn (Next() and NextDouble() consume one each):
  * hosts regenerate the reference's seeded test inputs with it (rays that continue the triangle stream, SpatialSubdivisionTests.cs:141,225) */
 void sr_net_random_doubles(int32_t seed, int64_t skip, int64_t n, double* out);
@@ -569,7 +602,8 @@ int  sr_anti_alias_device(sr_scene*, const void* d_src, int32_t dst_width, int32
  * schedule with the host's env.  value < 0 restores the default.  Used by tests/ and scripts/ only. */
 enum {
     SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
-                                    per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) */
+                                    per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) and the
+                                    points per pass of sr_shadow_points (default 2^22) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
     SR_DBG_SPLIT          = 3,   /* concurrent part-frame pipelines (default 2, <= 4)                                          */
@@ -583,7 +617,9 @@ enum {
                                     SR_MODE_BVH frame as nearest-hit walks instead of any-hit walks with the limit 2.0; 35 sr_bake_light_field on a
                                     SR_MODE_BVH frame with one packet walk per wave of 64 same-origin canonical rays instead of private per-lane
                                     walks (same table; measured slower); 36 the shadow stage of a shadowed light-field frame's lazy fill with the
-                                    packet shaft walk instead of private per-lane shaft walks (same table; measured slower); 100 + T: the walk kernel
+                                    packet shaft walk instead of private per-lane shaft walks (same table; measured slower); 37 sr_shadow_points queues a pass in input
+                                    order whatever the options say (no ray sort); 38 sr_shadow_points runs the first shaft round with private per-lane walks instead of the
+                                    packet walk (both: same output); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid
                                     too (its loop form spills registers: opt-in); 84 the persistent shaft walk hands its tiles out in natural order

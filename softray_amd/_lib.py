@@ -46,7 +46,9 @@ SYMBOLS = [
     "sr_set_light_field_res", "sr_get_light_field_res", "sr_reset_light_field", "sr_get_light_field", "sr_set_light_field",
     "sr_bake_light_field", "sr_set_voxel_res", "sr_get_voxel_res", "sr_set_triangles_device",
     "sr_refit_triangles_device", "sr_set_light_field_shadows", "sr_get_light_field_shadows",
+    "sr_shadow_points", "sr_shadow_points_device",
 ]
+POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
 # sr_debug_set keys (include/softray.h)
@@ -154,6 +156,8 @@ def lib():
     L.sr_device_count.restype = i32; L.sr_device_count.argtypes = [vp]
     L.sr_last_frame_parts.restype = i32; L.sr_last_frame_parts.argtypes = [vp]
     L.sr_shade_points.restype = i32; L.sr_shade_points.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    L.sr_shadow_points.restype = i32; L.sr_shadow_points.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32]
+    L.sr_shadow_points_device.restype = i32; L.sr_shadow_points_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_trace_rays_device.restype = i32; L.sr_trace_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sr_rccl_unique_id.restype = i32; L.sr_rccl_unique_id.argtypes = [vp]
     L.sr_rccl_init.restype = i32; L.sr_rccl_init.argtypes = [vp, vp, i32, i32]

@@ -665,8 +665,14 @@ int ensure_light_field(sr_scene* s, hipStream_t stream) {
 // sr_bake_light_field with shadows: the bake needs everything a shadowed frame sets up (the light's records and node order, the offset
 // table, the shadow stage's scratch), so it runs through render_common with no rows to render
 struct LfBakeReq { uint64_t first, count; unsigned long long* filled; };
+// sr_shadow_points: the same set-up for the same reason, then passes of the caller's points through the shadow stage (device arrays)
+struct PtsReq { int64_t n; const double* pos; const double* nrm; const uint32_t* color; uint32_t* out; bool coherent; };
 
-int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0, const LfBakeReq* bake = nullptr) {
+// points per pass of sr_shadow_points: the bake's rule (SR_DBG_BAND_SAMPLES shrinks the pass)
+const long long kPtsPassPoints = 1ll << 22;
+
+int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0, const LfBakeReq* bake = nullptr,
+                  const PtsReq* pts = nullptr) {
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
@@ -679,7 +685,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     if ((rc = prepare_frame(s, f, fc))) return rc;
     if ((rc = sync_geometry(s, voxels ? ~0u : (uint32_t)f->trace_mode))) return rc;
     if (voxels && (rc = ensure_voxels(s, stream))) return rc;
-    if (fc.num_rows == 0 && !bake) return SR_OK;
+    if (fc.num_rows == 0 && !bake && !pts) return SR_OK;
     // ---- frames of one scene run in submission order whatever streams they are given: the scene's scratch (hit queues, candidate
     //      lists, counters) and its per-origin / per-light records belong to one frame at a time.  `pre_used` is recorded when everything
     //      a frame enqueues is on its stream; the next frame's stream waits for it (a no-op on the same stream) ----
@@ -808,6 +814,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     //     is the constant (byte)(1.0 * 255) (applied by k_primary).  Extra geometry (unbounded planes) and the static cache (its
     //     cells are renderer state) keep the literal path.
     // (a light-field frame keeps the literal rays: the constant factor is k_primary's)
+    bool pts_escape = false;
     if ((fc.flags & SR_F_SHADOWS) && !(fc.flags & SR_F_POINT_LIGHT) && !static_shadows && s->extra_recs.empty() && !(f->flags & SR_F_LIGHT_FIELD) &&
         !(f->flags & (SR_F_SINGLE_KERNEL | SR_F_PER_LANE_SHADOWS)) && f->max_bounces == 0 && s->dbg[SR_DBG_LITERAL_SHADOWS] <= 0) {
         double diag2 = 0, len2 = 0;
@@ -817,7 +824,10 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             len2 += fc.light_dir_model[a] * fc.light_dir_model[a];
         }
         if (1000.0 * std::sqrt(len2) - fc.light_radius > std::sqrt(diag2) * 1.001 + 0.01) {
-            fc.flags = (fc.flags & ~(uint32_t)SR_F_SHADOWS) | sr::kFlagAllSamplesEscape;
+            // (sr_shadow_points: a caller's point need not lie where a hit point does.  The proof holds for a probe end inside the box
+            // the diagonal was taken of; k_pts_ingest finishes those points and queues the others for the literal rays)
+            if (pts) pts_escape = true;
+            else fc.flags = (fc.flags & ~(uint32_t)SR_F_SHADOWS) | sr::kFlagAllSamplesEscape;
         }
     }
     // (2) a REF_TREE frame: the shadow rays only answer "is there a hit with rayFrac <= 1.0", which the own BVH answers identically
@@ -833,7 +843,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     bool rewrote = false;                                             // (frames enqueued earlier have been waited for: see pre_used above)
     // ---- which records can the frame's camera rays / shadow sample rays hit at all?  (k_facing_partition, sr_pipeline.hip) ----
     const bool lf = (f->flags & SR_F_LIGHT_FIELD) != 0;              // (no camera ray is walked: none of the packet walk's per-origin records is needed)
-    const bool pkt_primary = f->trace_mode == SR_MODE_BVH && s->dbg[SR_DBG_PER_LANE_PRIMARY] <= 0 && !((f->flags & SR_F_FOCAL_BLUR) && f->sub_pixel_res > 1) && !lf;
+    const bool pkt_primary = f->trace_mode == SR_MODE_BVH && s->dbg[SR_DBG_PER_LANE_PRIMARY] <= 0 && !((f->flags & SR_F_FOCAL_BLUR) && f->sub_pixel_res > 1) && !lf && !pts;
     const bool want_cam = wide && pkt_primary, want_light = wide && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT);
     if ((want_cam || want_light) && s->dbg[SR_DBG_KERNEL_SWITCH] != 71) {
         const auto same3 = [](const double* a, const double* b) { return a[0] == b[0] && a[1] == b[1] && a[2] == b[2]; };
@@ -961,7 +971,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     if (s->dbg[SR_DBG_SPLIT] > 0) want_split = (int)std::min<int64_t>(s->dbg[SR_DBG_SPLIT], (int)sr_scene::kMaxSplit);   // experiment hook
     const bool ao = (f->flags & SR_F_AMBIENT_OCCLUSION) != 0, ao_uncached = ao && (f->flags & SR_F_AO_UNCACHED);
     // (a light-field frame stays whole: a band's apply reads the cells the same band's fill stored)
-    const bool split = (shadows || bounce_pipe) && !static_shadows && !ao && !lf && want_split > 1 && fc.num_rows >= 32 * want_split && !(f->flags & SR_F_NO_SPLIT);
+    const bool split = (shadows || bounce_pipe) && !static_shadows && !ao && !lf && !pts && want_split > 1 && fc.num_rows >= 32 * want_split && !(f->flags & SR_F_NO_SPLIT);
     const int halves = split ? want_split : 1;
     const int rows_half = split ? (int)((((long long)fc.num_rows + halves - 1) / halves + 15) / 16 * 16) : fc.num_rows;
     const long long budget = kMaxBandSamples / halves;
@@ -977,6 +987,15 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         const long long want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? (long long)s->dbg[SR_DBG_BAND_SAMPLES] : kBakeShadowPassCells;
         band_samples = std::max<long long>(1, want / per_origin) * per_origin;
     }
+    long long pts_pass = 0;
+    if (pts) {
+        // a pass of points: at most kPtsPassPoints (SR_DBG_BAND_SAMPLES shrinks the pass), no more than the call has
+        const long long want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? (long long)s->dbg[SR_DBG_BAND_SAMPLES] : kPtsPassPoints;
+        pts_pass = std::max<long long>(1, std::min<long long>(want, pts->n));
+        band_samples = (pts_pass + 255) / 256 * 256;                    // (the scratch in whole workgroups of queue entries)
+    }
+    // (hook 37: a pass is queued in input order whatever the caller promised)
+    const bool pts_sort = pts && !pts->coherent && s->dbg[SR_DBG_KERNEL_SWITCH] != 37;
     if (shaft && band_samples >= (1ll << 25)) return fail(SR_ERR_UNSUPPORTED, "row band too large for the 25-bit fallback entry ids (surface too wide for this sub-pixel resolution)");
     if (static_shadows) {
         if (band_rows < fc.num_rows) return fail(SR_ERR_UNSUPPORTED, "static shadows: the frame does not fit one row band");
@@ -1069,6 +1088,12 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             SR_HIP(B.ray_sort.reserve((size_t)band_samples * 4 * 4));
             SR_HIP(B.ray_sort_temp.reserve(sr::ray_sort_temp_bytes((unsigned)band_samples)));
         }
+        if (pts) {
+            // the pass as k_pts_ingest leaves it, and its order: by (cell of the point, octant of the normal), or the input's
+            SR_HIP(B.hits2.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
+            SR_HIP(B.ray_sort.reserve((size_t)band_samples * 4 * 4));
+            SR_HIP(B.ray_sort_temp.reserve(sr::point_order_temp_bytes((unsigned)band_samples)));
+        }
         if (bounce_pipe) {
             // level colours are indexed like the sample buffer: the frame (or compact strip buffer) for one sample per pixel, band-local otherwise
             const size_t idx_space = n2 == 1 ? (size_t)(f->strip_count > 0 ? fc.num_rows : fc.height) * fc.width : (size_t)band_samples;
@@ -1086,7 +1111,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         }
         // (one band per part-frame pipeline: a second band would walk other tiles with the first one's lists)
         // (a light-field frame's queue is compact: no tile grid whose walk lengths the next frame could use)
-        const bool order_tiles = shaft && band_rows >= rows_half && !lf;
+        const bool order_tiles = shaft && band_rows >= rows_half && !lf && !pts;
         bool hints_fresh = false;                                  // the hint arrays are new, or name another scene's records: "absent" everywhere, on the half's own stream below
         if (order_tiles) {
             const size_t bytes = sr::pipeline_tile_items(fc.width, (int)band_rows, (int)n2) * 4;
@@ -1115,7 +1140,8 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         if (chunked_shadows) {
             // indexed like the sample buffer: the frame (or the compact strips) for one sample per pixel, band-local otherwise (a light field's
             // shadow stage: the staging buffer, one word per queue slot)
-            const size_t idx_space = (n2 == 1 && !lf) ? (size_t)(f->strip_count > 0 ? fc.num_rows : fc.height) * fc.width : (size_t)band_samples;
+            // (sr_shadow_points: a pass's part of `out`, one word per point of the pass)
+            const size_t idx_space = (n2 == 1 && !lf && !pts) ? (size_t)(f->strip_count > 0 ? fc.num_rows : fc.height) * fc.width : (size_t)band_samples;
             if (idx_space * 4 > B.accum.cap || !B.accum.p) {
                 SR_HIP(B.accum.reserve(idx_space * 4));
                 accum_fresh = true;                                // zeroed on the half's own stream below
@@ -1143,7 +1169,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.pixels = d_pixels;
         P.samples = (uint32_t*)B.samples.p;
         P.hits = B.hits.p;
-        P.hits2 = (bounce_pipe || path || ao) ? B.hits2.p : nullptr;
+        P.hits2 = (bounce_pipe || path || ao || pts) ? B.hits2.p : nullptr;
         P.pt_flags = (path || ao) ? (uint8_t*)B.pt_flags.p : nullptr;
         P.pt_index = (path || ao) ? (uint32_t*)B.pt_index.p : nullptr;
         P.pt_totals = (path || ao) ? (uint32_t*)B.pt_totals.p : nullptr;
@@ -1166,6 +1192,17 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             P.lf_bake_filled = bake->filled;
             P.lf_bake_packet = s->dbg[SR_DBG_KERNEL_SWITCH] == 35;
         }
+        if (pts) {
+            P.pts_n = pts->n; P.pts_pass = pts_pass;
+            P.pts_pos = pts->pos; P.pts_nrm = pts->nrm; P.pts_color = pts->color; P.pts_out = pts->out;
+            P.pts_sort = pts_sort;
+            P.pts_per_lane = s->dbg[SR_DBG_KERNEL_SWITCH] == 38;
+            P.pts_escape = pts_escape;
+            for (int a = 0; a < 3; ++a) {                                 // (the box of the shortcut's diagonal: model and root box, + the probe offset, both ends)
+                P.pts_escape_lo[a] = std::min(s->vmin[a], s->root.min[a]) - 0.002;
+                P.pts_escape_hi[a] = std::max(s->vmax[a], s->root.max[a]) + 0.002;
+            }
+        }
         s->ao_table_seed = f->random_seed;
         s->ao_table_rc = SR_OK;
         P.ao_table = !ao ? nullptr : [](void* user, unsigned long long generators) -> const int32_t* {
@@ -1187,9 +1224,9 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.pt_row_k0 = pt_phase ? (uint32_t*)s->d_pt_row_k0.p : nullptr;
         P.pt_range_first = pt_range_first;
         P.pt_range_rows = pt_range_rows;
-        P.ray_sort_buf = (bounce_pipe || path_walk) ? (unsigned int*)B.ray_sort.p : nullptr;
-        P.ray_sort_temp = (bounce_pipe || path_walk) ? B.ray_sort_temp.p : nullptr;
-        P.ray_sort_temp_bytes = (bounce_pipe || path_walk) ? sr::ray_sort_temp_bytes((unsigned)band_samples) : 0;
+        P.ray_sort_buf = (bounce_pipe || path_walk || pts) ? (unsigned int*)B.ray_sort.p : nullptr;
+        P.ray_sort_temp = (bounce_pipe || path_walk || pts) ? B.ray_sort_temp.p : nullptr;
+        P.ray_sort_temp_bytes = pts ? sr::point_order_temp_bytes((unsigned)band_samples) : (bounce_pipe || path_walk) ? sr::ray_sort_temp_bytes((unsigned)band_samples) : 0;
         P.bounce_levels = bounce_pipe ? (uint32_t*)B.bounce_levels.p : nullptr;
         P.bounce_nlev = bounce_pipe ? (uint8_t*)B.bounce_nlev.p : nullptr;
         P.bounce_prep = (bounce_pipe || path_walk) ? B.bounce_prep.p : nullptr;
@@ -1256,7 +1293,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         };
         if (accum_fresh) SR_HIP(hipMemsetAsync(B.accum.p, 0, B.accum.cap, bs));
         if (hints_fresh) for (DBuf& hb : B.tile_hint) SR_HIP(hipMemsetAsync(hb.p, 0xFF, hb.cap, bs));
-        if (P.row_first < P.row_limit || bake) {
+        if (P.row_first < P.row_limit || bake || pts) {
             const hipError_t pe = sr::launch_pipeline(P);
             if (pe == hipErrorNotSupported && s->ao_table_rc) return s->ao_table_rc;      // (the message is the callback's)
             SR_HIP(pe);
@@ -2707,6 +2744,66 @@ int sr_shade_points(sr_scene* s, const sr_frame* f, int64_t n, const double* pos
     SR_HIP(sr::launch_shade_points(fc, n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, (const uint32_t*)s->d_io[2].p, (uint32_t*)s->d_io[3].p, nullptr));
     SR_HIP(hipStreamSynchronize(nullptr));
     SR_HIP(hipMemcpy(out, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+// what sr_shadow_points[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the
+// first part of a multi-device scene), `fs`: the frame with SR_F_SHADOWS implied
+static int shadow_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* pos, const void* normal, const void* out, uint32_t options, sr_frame& fs) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !f || n < 0 || (n > 0 && (!pos || !normal || !out)) || (options & ~(uint32_t)SR_POINTS_COHERENT))
+        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_shadow_points");
+    if (f->flags & SR_F_STATIC_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: static shadows (SR_F_STATIC_SHADOWS) are a cache over a frame's fill order, not a step on a point");
+    if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is another decorator, not ShadowMethod's step");
+    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain ShadowMethod is part of");
+    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: voxel rendering (SR_F_VOXELS) has no shadow step");
+    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter");
+    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point");
+    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points");
+    fs = *f;
+    fs.flags |= SR_F_SHADOWS;
+    int rc = validate_frame(&fs, s);
+    if (rc) return rc;
+    return check_frame_mode(s, &fs);
+}
+
+int sr_shadow_points_device(sr_scene* m, const sr_frame* f, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color, uint32_t* d_out,
+                            uint32_t options, void* hip_stream, uint64_t* d_stats) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = shadow_points_check(s, f, n, d_pos, d_normal, d_out, options, fs);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    const PtsReq req{n, d_pos, d_normal, d_color, d_out, (options & SR_POINTS_COHERENT) != 0};
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, 0, nullptr, &req);
+}
+
+int sr_shadow_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, uint32_t options) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = shadow_points_check(s, f, n, pos, normal, out, options, fs);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    if ((rc = ensure_io_streams(s))) return rc;
+    hipStream_t stream = s->io_stream;
+    const size_t sizes[3] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 4};
+    for (int i = 0; i < 3; ++i) SR_HIP(s->d_io[i].reserve(sizes[i]));
+    SR_HIP(hipMemcpy(s->d_io[0].p, pos, sizes[0], hipMemcpyHostToDevice));
+    SR_HIP(hipMemcpy(s->d_io[1].p, normal, sizes[1], hipMemcpyHostToDevice));
+    if (color) SR_HIP(hipMemcpy(s->d_io[2].p, color, sizes[2], hipMemcpyHostToDevice));
+    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
+    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    // (the colours are modulated where they lie: the device variant's `out` aliasing `color`)
+    const PtsReq req{n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, color ? (const uint32_t*)s->d_io[2].p : nullptr, (uint32_t*)s->d_io[2].p,
+                     (options & SR_POINTS_COHERENT) != 0};
+    if ((rc = render_common(s, &fs, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, nullptr, &req))) { (void)hipStreamSynchronize(stream); return rc; }
+    SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
     return SR_OK;
 }
 

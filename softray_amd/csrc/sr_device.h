@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_COUNT = 27 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_COUNT = 29 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -130,6 +130,17 @@ struct PipelineLaunch {
     uint64_t      lf_bake_first, lf_bake_count, lf_bake_pass_cells;
     unsigned long long* lf_bake_filled;
     bool          lf_bake_packet;   // BakeLaunch::packet
+    // sr_shadow_points (pts_n > 0: launch_pipeline renders no rows): n caller-given surface points in passes of pts_pass (band samples) go through
+    // the frame's dynamic shadow stage as a compact queue in `hits`; pts_out is the stage's sample buffer (k_pts_ingest, sr_pipeline.hip)
+    int64_t       pts_n, pts_pass;
+    const double* pts_pos;      // device [n][3], model space
+    const double* pts_nrm;      // device [n][3], as given
+    const uint32_t* pts_color;  // device [n] or nullptr (every point 0xFFFFFFFF); may be pts_out
+    uint32_t*     pts_out;      // device [n]
+    bool          pts_sort;     // queue a pass in ray_sort's order (cell of the point, octant of the normal) instead of input order (point_order)
+    bool          pts_per_lane; // the first shaft round with private per-lane walks (A/B hook)
+    bool          pts_escape;   // a directional light whose samples all escape for a probe end inside [pts_escape_lo, pts_escape_hi]
+    double        pts_escape_lo[3], pts_escape_hi[3];
     void*         static_hits;  // device HitRec[min(band samples, 128^3)]: generators of a static-shadow frame
     unsigned long long* static_claim; // device [128^3]: smallest order key that asked for an empty cell
     int32_t       static_concurrency; // rayTraceConcurrency of the frame
@@ -231,6 +242,15 @@ hipError_t build_bvh_device(const double* d_v9, int n, const RootBox& root, cons
 size_t ray_sort_temp_bytes(unsigned int cap);
 hipError_t ray_sort(const void* queue, const unsigned int* d_count, unsigned int cap, const RootBox& root, unsigned int* keys, unsigned int* keys2,
                     unsigned int* idx, unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
+
+// sr_shadow_points: the order of a pass's queue.  recs: n records where their points lie (sample word 0xffffffff = not queued); order_out:
+// the queued points first -- sorted: by ray_sort's key of (position, normal), ties in input order; !sorted: in input order.  A stable
+// sort, so the queue does not depend on which wave ran first
+// (keys2 returns the sorted keys: point_order_skip_mask(sorted) is their bit that marks a point that is not queued)
+size_t point_order_temp_bytes(unsigned int cap);
+unsigned int point_order_skip_mask(bool sorted);
+hipError_t point_order(const void* recs, unsigned int n, bool sorted, const RootBox& root, unsigned int* keys, unsigned int* keys2, unsigned int* idx,
+                       unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
 
 // the four-wide tree collapsed from a device-resident binary tree (same rule as the host's collapse_bvh4); d_wide: >= num_nodes entries
 // level_first (nullable): the wide nodes are numbered level by level -- level L is [level_first[L], level_first[L + 1]), the last entry

@@ -4154,6 +4154,93 @@ __global__ __launch_bounds__(256) void k_lf_bake(DevScene sc, FrameConst fc, con
 }
 
 // --------------------------------------------------------------------------------------------------
+// k_pts_ingest (sr_shadow_points): the front door of the dynamic shadow stage for caller-given surface points.  One lane per point of a
+// pass: out[i] = the point's colour (0xFFFFFFFF without a colour array; `out` may be the colour array itself, so neither is __restrict__),
+// and recs[i] = the point -- position and normal as given -- with sample = i, its index in the pass's part of `out`, which is the stage's
+// "sample buffer": the shadow kernels modulate out[i] in place and no output kernel follows.  A point that is not queued gets sample =
+// kInvalidHit.  No slots are handed out here (lf_queue_slot's one atomicAdd per wave on ONE counter was measured: 2.7 ms for the 15 M hit
+// points of a 4096^2 frame, 234 k atomics on one address, against 0.36 ms without) -- the queue's order is point_order's (sr_raysort.hip) and
+// k_pts_gather's, a function of the input alone, so the 64 points that share a packet walk do not depend on which wave ran first.
+// What never reaches a walk, with E' = pos + normal * 0.001 as ShadowMethod computes it (the sample rays depend on E' alone):
+//   - a NaN component of E': no primitive and no tree answers a ray with a NaN component, all samples escape;
+//   - an infinite component of E': no model triangle answers such a ray (its hit point is NaN), the extra geometry can -- a plane cut at
+//     rayFrac 0 by an infinite direction blocks the sample -- so the samples are tested here against the extra primitives alone, with the
+//     arithmetic of the literal path (extra_hit);
+//   - box.on, a directional light whose samples provably escape for every E' inside `box` (sr_api.cpp: the proof of the frame's shortcut,
+//     which a hit point of the frame satisfies by construction and a caller's point need not): all samples escape.
+// All three write modulate(colour, ShadowMethod's byte) themselves and queue nothing.
+// --------------------------------------------------------------------------------------------------
+struct PtsBox { double lo[3], hi[3]; int32_t on; };
+
+template <bool EXTRA>
+__global__ __launch_bounds__(256) void k_pts_ingest(DevScene sc, FrameConst fc, const double* __restrict__ offsets, const double* __restrict__ pos,
+                                                    const double* __restrict__ nrm, const uint32_t* color, uint32_t n, PtsBox box,
+                                                    HitRec* __restrict__ recs, uint32_t* out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < n;
+    HitRec r;
+    for (int a = 0; a < 3; ++a) {
+        r.pos[a] = live ? pos[(size_t)i * 3 + a] : 0.0;
+        r.nrm[a] = live ? nrm[(size_t)i * 3 + a] : 0.0;
+    }
+    r.sample = i;
+    r.pad[0] = r.pad[1] = r.pad[2] = 0u;
+    const uint32_t c = (live && color) ? color[i] : 0xFFFFFFFFu;
+    const D3 end = mk(r.pos[0], r.pos[1], r.pos[2]) + mk(r.nrm[0], r.nrm[1], r.nrm[2]) * 0.001;      // shadowProbeOffset
+    const bool is_nan = end.x != end.x || end.y != end.y || end.z != end.z;
+    const double fin = (end.x - end.x) + (end.y - end.y) + (end.z - end.z);                          // 0 for finite components, NaN otherwise
+    const bool finite = fin == 0.0;
+    const bool inside = box.on && end.x >= box.lo[0] && end.x <= box.hi[0] && end.y >= box.lo[1] && end.y <= box.hi[1] &&
+                        end.z >= box.lo[2] && end.z <= box.hi[2];
+    int escapes = -1;                                                        // -1: the stage decides
+    if (is_nan || inside) {
+        escapes = fc.shadow_samples;
+    } else if (!finite) {
+        escapes = fc.shadow_samples;
+        if (EXTRA && live) {
+            escapes = 0;
+            for (int k = 0; k < fc.shadow_samples; ++k) {
+                const D3 off = mk(offsets[3 * k], offsets[3 * k + 1], offsets[3 * k + 2]);
+                D3 rs, rd;
+                if (fc.flags & 8u) {
+                    rs = mk(fc.light_pos_model[0] + off.x, fc.light_pos_model[1] + off.y, fc.light_pos_model[2] + off.z);
+                    rd = end - rs;
+                } else {
+                    rd = mk(fc.light_dir_model[0], fc.light_dir_model[1], fc.light_dir_model[2]);
+                    rs = end + rd * 1000.0 + off;
+                }
+                bool blocked = false;
+                for (int e = 0; e < sc.nextra && !blocked; ++e) {
+                    double t; D3 hp, hn;
+                    uint32_t tests;
+                    blocked = extra_hit(&sc.extra[e], rs, rd, t, hp, hn, tests) && t <= 1.0;
+                }
+                if (!blocked) escapes++;
+            }
+        }
+    }
+    if (live) out[i] = escapes < 0 ? c : modulate(c, to_byte((double)escapes / (double)fc.shadow_samples * 255));
+    const bool emit = live && escapes < 0;
+    if (!emit) r.sample = kInvalidHit;
+    if (live) recs[i] = r;
+}
+
+// the pass's queue in point_order's order (order[j] = the point of the j-th entry; the queued points come first): with the sort, 64
+// consecutive entries -- one packet walk of the first shaft round -- are neighbours in the root box whose normals share an octant
+// skeys: the sorted keys, `skip` their bit that marks a point that is not queued (those come last); the lane of the last queued entry
+// writes the queue's length (0 stays from the pass's counter reset)
+__global__ __launch_bounds__(256) void k_pts_gather(const HitRec* __restrict__ in, unsigned int n, const unsigned int* __restrict__ order,
+                                                    const unsigned int* __restrict__ skeys, unsigned int skip, HitRec* __restrict__ queue,
+                                                    unsigned int* __restrict__ queue_count) {
+    const unsigned int stride = gridDim.x * 256u;
+    for (unsigned int j = blockIdx.x * 256u + threadIdx.x; j < n; j += stride) {
+        if (skeys[j] & skip) continue;
+        queue[j] = in[order[j]];
+        if (j + 1u == n || (skeys[j + 1u] & skip)) *queue_count = j + 1u;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_cam_cones: per-frame pre-pass of the packet primary walk -- the CamCone record (sr_types.h) of every BVH triangle for
 // the frame's ray origin O: FP64 cross products of the FP64 vertices, rounded once to fp32.  64 B written + 72 B (gathered)
 // + 8 B read per triangle: 0.15 GB at 1 M triangles; re-run only when the origin or the tree changed.
@@ -4945,6 +5032,51 @@ static hipError_t launch_lf_bake_shadows_t(const PipelineLaunch& L) {
     return hipSuccess;
 }
 
+// sr_shadow_points (PipelineLaunch::pts_n > 0): the caller's points in passes of at most L.pts_pass points -- what the queue and the shadow
+// stage's lists are sized for.  Per pass: counters reset, k_pts_ingest, point_order (the ray sort's key unless the caller promised
+// coherence: then input order) and k_pts_gather, the shadow stage with the pass's part of `out` as its sample buffer; back to back on the stream, the host never waits.  Like a light
+// field's stage it sees nothing but a compact queue: tile_queue_n2 = tile_queue_rows = 0, 64 consecutive entries per packet walk
+template <int MODE, bool EXTRA>
+static hipError_t launch_pts_shadows_t(const PipelineLaunch& L) {
+    hipError_t e;
+    PipelineLaunch T = L;
+    if (L.primary_stats_only) T.stats = nullptr;
+    T.tile_queue_n2 = 0;
+    T.tile_queue_rows = 0;
+    if (L.pts_per_lane) T.per_lane_shaft |= 1;                          // (SR_DBG_KERNEL_SWITCH 38)
+    const bool shaft_frame = (MODE != MODE_BVH && L.shadows_on_bvh) ? shaft_path<MODE_BVH>(L) : shaft_path<MODE>(L);
+    if (!L.ray_sort_buf || !L.hits2) return hipErrorInvalidValue;
+    PtsBox box;
+    for (int a = 0; a < 3; ++a) { box.lo[a] = L.pts_escape_lo[a]; box.hi[a] = L.pts_escape_hi[a]; }
+    box.on = L.pts_escape ? 1 : 0;
+    for (int64_t first = 0; first < L.pts_n; first += L.pts_pass) {
+        const uint32_t count = (uint32_t)std::min<int64_t>(L.pts_pass, L.pts_n - first);
+        uint32_t* out = L.pts_out + first;
+        if ((e = hipMemsetAsync(L.counters, 0, kCounterWords * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
+        hipEvent_t e0, e1;
+        pipe_events(L, K_PTS_INGEST, e0, e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_pts_ingest<EXTRA>, dim3((count + 255u) / 256u), dim3(256), 0, L.stream, L.sc, L.fc, L.offsets, L.pts_pos + first * 3, L.pts_nrm + first * 3,
+                           L.pts_color ? L.pts_color + first : nullptr, count, box, (HitRec*)L.hits2, out);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        {
+            pipe_events(L, K_PTS_SORT, e0, e1);
+            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+            const unsigned cap = count;
+            unsigned int* b = L.ray_sort_buf;
+            if ((e = point_order(L.hits2, cap, L.pts_sort, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
+            const unsigned blocks = (unsigned)std::min<long long>(((long long)count + 255) / 256, (long long)L.persistent_blocks);
+            hipLaunchKernelGGL(k_pts_gather, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)L.hits2, cap, (const unsigned int*)(b + 3 * (size_t)cap), (const unsigned int*)(b + (size_t)cap),
+                               point_order_skip_mask(L.pts_sort), (HitRec*)L.hits, L.counters);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        }
+        if ((e = launch_dynamic_shadows_t<MODE, EXTRA>(L, T, shaft_frame, out, (long long)count)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // sr_bake_light_field: entries [first, first + count) of the table in launches of at most L.launch_cells cells (whole origin patches; at
 // least one), one after the other on the stream with nothing in between: no single kernel runs long, and the host never waits
 template <int MODE, bool EXTRA>
@@ -5010,6 +5142,7 @@ hipError_t launch_resolve_rows(const FrameConst& fc, const int32_t* row_map, int
 template <int MODE, bool EXTRA>
 static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     if (L.lf_bake_count > 0) return launch_lf_bake_shadows_t<MODE, EXTRA>(L);      // sr_bake_light_field with shadows: no rows, no pixels
+    if (L.pts_n > 0) return launch_pts_shadows_t<MODE, EXTRA>(L);                  // sr_shadow_points: the caller's points, no rows, no pixels
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     const bool shadows = (L.fc.flags & 2u) != 0;
     const bool path = (L.fc.flags & kFlagPathTracing) != 0;          // (sr_api.cpp: never together with shadows or mirror bounces)

@@ -40,7 +40,55 @@ __global__ __launch_bounds__(256) void k_ray_keys(const double* __restrict__ que
     idx[i] = i;
 }
 
+// sr_shadow_points: the records of a pass lie where their points do (record i = point i, 64 bytes: position, normal, then the sample word);
+// a point that is not queued has the sample word 0xffffffff.  sorted: the key of k_ray_keys from position and normal; in both cases bit
+// kPointSkipBit marks the records that are not queued, so that a STABLE sort leaves the queued ones first -- by key, ties in input order
+// (sorted), or simply in input order (!sorted: the one-bit sort is a deterministic compaction)
+constexpr int kPointSkipBit = 24;
+__global__ __launch_bounds__(256) void k_point_keys(const double* __restrict__ recs, unsigned int n, int sorted, double lx, double ly, double lz,
+                                                    double sx, double sy, double sz, unsigned int* __restrict__ keys, unsigned int* __restrict__ idx) {
+    const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const double* q = recs + (size_t)i * 8;
+    const bool queued = reinterpret_cast<const unsigned int*>(q + 6)[0] != 0xffffffffu;
+    unsigned int key = 0u;
+    if (queued && sorted) {
+        const int cx = min(127, max(0, (int)((q[0] - lx) * sx))), cy = min(127, max(0, (int)((q[1] - ly) * sy))), cz = min(127, max(0, (int)((q[2] - lz) * sz)));
+        const unsigned int oct = (q[3] < 0.0 ? 1u : 0u) | (q[4] < 0.0 ? 2u : 0u) | (q[5] < 0.0 ? 4u : 0u);
+        const unsigned int mort = (spread7((unsigned)cx) << 2) | (spread7((unsigned)cy) << 1) | spread7((unsigned)cz);
+        key = ((mort >> 6) << 9) | (oct << 6) | (mort & 63u);
+    }
+    if (!queued) key = sorted ? (1u << kPointSkipBit) : 1u;
+    keys[i] = key;
+    idx[i] = i;
+}
+
 }  // namespace
+
+unsigned int point_order_skip_mask(bool sorted) { return sorted ? (1u << kPointSkipBit) : 1u; }
+
+size_t point_order_temp_bytes(unsigned int cap) {
+    size_t a = 0, b = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
+                                             (unsigned int*)nullptr, (int)cap, 0, kPointSkipBit + 1);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
+                                             (unsigned int*)nullptr, (int)cap, 0, 1);
+    return a > b ? a : b;
+}
+
+// order_out[j] = the point whose record is the j-th of the pass's queue, keys2[j] its key; keys / idx: scratch of n entries each
+hipError_t point_order(const void* recs, unsigned int n, bool sorted, const RootBox& root, unsigned int* keys, unsigned int* keys2, unsigned int* idx,
+                       unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    double s[3];
+    for (int a = 0; a < 3; ++a) { const double e = root.max[a] - root.min[a]; s[a] = e > 0 ? 128.0 / e : 0.0; }
+    hipLaunchKernelGGL(k_point_keys, dim3((n + 255u) / 256u), dim3(256), 0, stream, (const double*)recs, n, sorted ? 1 : 0, root.min[0], root.min[1], root.min[2],
+                       s[0], s[1], s[2], keys, idx);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const unsigned int*)keys, keys2, (const unsigned int*)idx, order_out, (int)n, 0,
+                                              sorted ? kPointSkipBit + 1 : 1, stream);
+}
 
 size_t ray_sort_temp_bytes(unsigned int cap) {
     size_t bytes = 0;

@@ -340,6 +340,28 @@ public:
         sr_check(sr_bake_light_field(scene_, &f, 0, 4 * n * n * n * n, &filled));
         return filled;
     }
+    // ShadowMethod's soft shadow for n surface points of the caller (sr_shadow_points): out[i] = color[i] (nullptr: 0xFFFFFFFF) modulated with the
+    // byte of the light, the shadow samples and the root geometry of the frame Render() would build for the first instance; rayTraceShadows is
+    // implied.  pos / normal: [n][3] in model space, the normal as given.  coherent: 64 consecutive points are neighbours (SR_POINTS_COHERENT).
+    // What names no step of ShadowMethod on a bare point (static shadows, ambient occlusion, path tracing, voxels, light field, mirror
+    // bounces) is refused by the library, by name.  Does nothing without a model or points
+    void ShadowPoints(int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, bool coherent = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel() || n == 0) return;
+        if (Instances.empty()) throw InvalidOperationException("ShadowPoints: no instance to take the pose from");
+        Instance& inst = *Instances.front();
+        inst.FieldOfViewDepth = fieldOfViewDepth_;
+        PreCalculate();
+        if (Mode() == SR_MODE_REF_TREE && !(built_ & (1u << SR_MODE_BVH)) && !model_->argb.empty()) {   // (the shaft path, as for a shadowed tree frame)
+            sr_check(sr_build(scene_, 1u << SR_MODE_BVH, 0, 0));
+            built_ |= 1u << SR_MODE_BVH;
+        }
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_frame f = BuildFrame(inst);
+        f.flags &= ~(uint32_t)SR_F_PRIMARY_STATS_ONLY;     // (the call has no primary rays: sr_last_ray_stats gets the shadow stage's counters)
+        sr_check(sr_shadow_points(scene_, &f, n, pos, normal, color, out, coherent ? SR_POINTS_COHERENT : 0u));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

@@ -321,6 +321,30 @@ class GpuScene:
         _check(_lib.lib().sr_shade_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out)))
         return out
 
+    def shadow_points(self, frame, pos, normal, color=None, coherent=False):
+        """ShadowMethod's soft shadow for caller-given surface points (sr_shadow_points): uint32 [n], color[i] (None: 0xFFFFFFFF) modulated
+        with the byte of the frame's light, samples and root geometry.  coherent: 64 consecutive points are neighbours (no ray sort)."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+        if normal.shape[0] != pos.shape[0]:
+            raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
+        if color is not None:
+            color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
+            if color.size != pos.shape[0]:
+                raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
+        out = np.zeros(pos.shape[0], dtype=np.uint32)
+        _check(_lib.lib().sr_shadow_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out),
+                                           _lib.POINTS_COHERENT if coherent else 0))
+        return out
+
+    def shadow_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, coherent=False, stream=0, d_stats_ptr=None):
+        """sr_shadow_points_device: every array is a DEVICE pointer (d_color 0 / None: every point 0xFFFFFFFF; d_out may be d_color);
+        enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = getattr(stream, "cuda_stream", stream)
+        _check(_lib.lib().sr_shadow_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out),
+                                                  _lib.POINTS_COHERENT if coherent else 0, vp(st), vp(d_stats_ptr)))
+
     # ---- IRayIntersectable.IntersectRay, batched ----
     def trace(self, target, starts, dirs, counters=False):
         starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)

@@ -92,6 +92,9 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_reset_light_field(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_set_light_field_shadows(IntPtr scene, int on);
         [DllImport(Lib)] public static extern int sr_get_light_field_shadows(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_set_light_field_interpolation(IntPtr scene, int on);
+        [DllImport(Lib)] public static extern int sr_get_light_field_interpolation(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_light_field_coords(IntPtr scene, long n, [In] double[] starts, [In] double[] dirs, [Out] double[] coords, [Out] byte[] inside);
         [DllImport(Lib)] public static extern int sr_get_light_field(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_bake_light_field(IntPtr scene, ref SrFrame frame, ulong first, ulong count, out ulong filled);
@@ -472,6 +475,18 @@ namespace Engine3D.Hip
         {
             get { return Native.sr_get_light_field_shadows(scene) != 0; }
             set { Native.Check(Native.sr_set_light_field_shadows(scene, value ? 1 : 0)); }
+        }
+        /// Opt-in: LightFieldColorMethod.Interpolate (hard-wired false in the reference).  Light-field frames blend the 16 entries around a sample's
+        /// RayToFloat4D coordinate instead of taking the one its line falls into.  Off (the default): nothing changes.  Does not touch the table.
+        public bool LightFieldInterpolation
+        {
+            get { return Native.sr_get_light_field_interpolation(scene) != 0; }
+            set { Native.Check(Native.sr_set_light_field_interpolation(scene, value ? 1 : 0)); }
+        }
+        /// LightField4D.RayToFloat4D in batch, on the device at LightFieldResolution: coords [n * 4], inside [n] (0: the line misses the sphere)
+        public void LightFieldCoords(double[] starts, double[] dirs, double[] coords, byte[] inside)
+        {
+            Native.Check(Native.sr_light_field_coords(scene, inside.Length, starts, dirs, coords, inside));
         }
         /// A new Renderer starts with an empty light field (LightFieldColorMethod.cs:101-115)
         public void ResetLightField() { Native.Check(Native.sr_reset_light_field(scene)); }

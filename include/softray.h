@@ -154,8 +154,8 @@ enum {
                                      host- and device-built BVH and frames of more than one row band.  The frame runs as one pipeline (as with SR_F_NO_SPLIT);
                                      a multi-device scene renders it on devices[0] alone.  SR_ERR_UNSUPPORTED together with SR_F_SHADOWS (static always; dynamic unless sr_set_light_field_shadows),
                                      SR_F_AMBIENT_OCCLUSION, SR_F_PATH_TRACING, SR_F_VOXELS, max_bounces > 0, SR_F_SINGLE_KERNEL, strip_count > 0 and
-                                     sr_rccl_render.  Not covered: LightFieldStoresTriangles = true (LightFieldTriMethod) and quad-linear interpolation
-                                     (LightFieldColorMethod.Interpolate, hard-wired false in the reference).
+                                     sr_rccl_render.  Not covered: LightFieldStoresTriangles = true (LightFieldTriMethod).  Quad-linear interpolation
+                                     (LightFieldColorMethod.Interpolate, hard-wired false in the reference) is an opt-in per scene: sr_set_light_field_interpolation.
                                      Statistics: stats[0] = the camera samples, [1..3] = 0; sr_last_ray_stats [4] grows by one per filled cell, [5..7] by what
                                      the canonical rays' walks count (not with SR_F_PRIMARY_STATS_ONLY)                                  */
     SR_F_PRIMARY_STATS_ONLY = 1u << 12 /* library option: with `stats`, count the primary rays only -- the four statistics of sr_render
@@ -432,6 +432,30 @@ int  sr_bake_light_field(sr_scene*, const sr_frame* frame, uint64_t first, uint6
  * canonical rays plus what the shadow stage counts for a frame; all of [4..7] stay 0 with SR_F_PRIMARY_STATS_ONLY. */
 int  sr_set_light_field_shadows(sr_scene*, int32_t on);
 int32_t sr_get_light_field_shadows(const sr_scene*);
+/* Quad-linear interpolation of the colour light field, opt-in per scene (LightFieldColorMethod.Interpolate, LightFieldColorMethod.cs:142-181, which
+ * the reference ships hard-wired to false).  on = 1: the SR_F_LIGHT_FIELD frames of sr_render and sr_render_device (a multi-device scene: on devices[0])
+ * blend the 16 entries around a sample's 4-D coordinate instead of taking the one its line falls into.  FP64, no contraction:
+ *   F = RayToFloat4D (LightField4D.cs:214-245) = (u * (2N), v * N, s * (2N), t * N), u, v, s, t and the sphere test as for the nearest lookup (whose
+ *       RayToCoord4D scales by 2N - 1 and N - 1: the reference's mismatch, kept; a cell's canonical ray stays Coord4DToRay's); a line that misses
+ *       the sphere (term < 1e-10) gives the background;
+ *   b_k = (byte)F_k (truncate, & 255, NaN -> 0), frac_k = F_k - (double)b_k;
+ *   for du, dv, ds, dt in {0, 1}, du outermost and dt innermost: c = the entry of cell ((b_u + du) % 2N, (b_v + dv) % N, (b_s + ds) % 2N, (b_t + dt) % N)
+ *       -- an empty one is filled first, with exactly what a nearest-lookup frame stores for that cell --, and per channel
+ *       acc = acc + ((((byte(c) / 255.0) * wu) * wv) * ws) * wt, w = frac for offset 1 and 1 - frac for offset 0, acc from 0;
+ *   sample = 0xFF000000 | (byte)(r * 255.0) << 16 | (byte)(g * 255.0) << 8 | (byte)(b * 255.0).
+ * Colours and tables are pinned for inputs with every F_k < 256 and every channel value x * 255 in [0, 256).  on = 0 (the default): nothing changes.
+ * Anything else: SR_ERR_INVALID_ARG.  A setting like sr_set_light_field_shadows: it works on a host-only scene, survives sr_set_triangles* /
+ * sr_load_3ds, is forwarded to the parts of a multi-device scene, never touches the table, and leaves sr_bake_light_field and every refusal of a
+ * light-field frame as they are.  With sr_set_light_field_shadows on, the 16 neighbours are filled through the shadow stage like any cell.  A band
+ * lists at most min(16 x its samples, 4 N^4) cells and its scratch has that room (with shadows the bands are 1/16 as large instead): no overflow,
+ * no host synchronisation inside a frame.  Statistics as for a light-field frame: [0] = camera samples, [4..7] = the canonical rays of filled cells. */
+int  sr_set_light_field_interpolation(sr_scene*, int32_t on);
+int32_t sr_get_light_field_interpolation(const sr_scene*);
+/* LightField4D.RayToFloat4D in batch, at the scene's sr_get_light_field_res: coords[i] = F of the line (starts[i], dirs[i]) (model space, host arrays),
+ * inside[i] = 1; a line that misses the sphere: inside[i] = 0 and coords[i] = 0.  Computed on the device by the device function the interpolating
+ * frame kernels call, so a caller can reproduce such a frame exactly from these coordinates (the device's atan2 / asin differ from a host's by
+ * ulps).  Bad arguments: SR_ERR_INVALID_ARG, before the device is looked at; a host-only scene then returns SR_ERR_NO_DEVICE.  n == 0: SR_OK. */
+int  sr_light_field_coords(sr_scene*, int64_t n, const double* starts, const double* dirs, double* coords /* [n][4] */, uint8_t* inside /* [n] */);
 /* Same, but `d_pixels` is DEVICE memory on the scene's device (e.g. a torch tensor's data_ptr) and the
  * work is enqueued on `hip_stream` (a hipStream_t; NULL = the null stream) without host sync. */
 /* Ordering: the work is enqueued behind everything already on `hip_stream` and `hip_stream` continues only after it; a
@@ -619,7 +643,8 @@ enum {
                                     walks (same table; measured slower); 36 the shadow stage of a shadowed light-field frame's lazy fill with the
                                     packet shaft walk instead of private per-lane shaft walks (same table; measured slower); 37 sr_shadow_points queues a pass in input
                                     order whatever the options say (no ray sort); 38 sr_shadow_points runs the first shaft round with private per-lane walks instead of the
-                                    packet walk (both: same output); 100 + T: the walk kernel
+                                    packet walk (both: same output); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid
                                     too (its loop form spills registers: opt-in); 84 the persistent shaft walk hands its tiles out in natural order

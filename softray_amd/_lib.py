@@ -47,6 +47,7 @@ SYMBOLS = [
     "sr_bake_light_field", "sr_set_voxel_res", "sr_get_voxel_res", "sr_set_triangles_device",
     "sr_refit_triangles_device", "sr_set_light_field_shadows", "sr_get_light_field_shadows",
     "sr_shadow_points", "sr_shadow_points_device",
+    "sr_set_light_field_interpolation", "sr_get_light_field_interpolation", "sr_light_field_coords",
 ]
 POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 GATHER_COPY, GATHER_RCCL = 0, 1
@@ -179,6 +180,9 @@ def lib():
     L.sr_bake_light_field.restype = i32; L.sr_bake_light_field.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp]
     L.sr_set_light_field_shadows.restype = i32; L.sr_set_light_field_shadows.argtypes = [vp, i32]
     L.sr_get_light_field_shadows.restype = i32; L.sr_get_light_field_shadows.argtypes = [vp]
+    L.sr_set_light_field_interpolation.restype = i32; L.sr_set_light_field_interpolation.argtypes = [vp, i32]
+    L.sr_get_light_field_interpolation.restype = i32; L.sr_get_light_field_interpolation.argtypes = [vp]
+    L.sr_light_field_coords.restype = i32; L.sr_light_field_coords.argtypes = [vp, i64, vp, vp, vp, vp]
     L.sr_net_random_doubles.restype = None; L.sr_net_random_doubles.argtypes = [i32, i64, i64, vp]
     L.sr_last_error.restype = C.c_char_p; L.sr_last_error.argtypes = []
     L.sr_abi_version.restype = i32; L.sr_abi_version.argtypes = []

@@ -145,6 +145,7 @@ struct sr_scene {
     DBuf d_lf_cache, d_lf_claim, d_lf_points;
     int32_t lf_res = 64;                 // lightFieldRes, Renderer.cs:93
     bool lf_shadows = false;             // sr_set_light_field_shadows: SR_F_LIGHT_FIELD | SR_F_SHADOWS (dynamic) is accepted; a setting, like lf_res
+    bool lf_interp = false;              // sr_set_light_field_interpolation: SR_F_LIGHT_FIELD frames blend the 16 entries around a sample (a setting, like lf_shadows)
     int32_t lf_points_res = 0;           // the resolution d_lf_points was made for (0: none)
     bool lf_cache_empty = true;          // the device cache (and the claim bits) must be zeroed before their next use
     std::vector<uint32_t> lf_cache_host;
@@ -190,6 +191,7 @@ struct sr_scene {
         DBuf pt_flags, pt_index, pt_totals, pt_carry;   // path tracing: hit flags, hit-index scan, row-block carries (sr_pipeline.hip k_pt_*)
         DBuf ao_escapes;                   // ambient occlusion: escaped probes, then the byte, per generator (sr_pipeline.hip k_ao_*)
         DBuf lf_cells, lf_list;            // light field: cache index per sample, the cells the band fills (sr_pipeline.hip k_lf_*)
+        DBuf lf_fracs;                     // ... interpolating: the four fractions of every sample, from k_lfi_lookup to k_lfi_apply
         DBuf lf_stage;                     // ... with shadows: the staged colour of every slot of the fill's / a bake pass's hit queue
         DBuf accum;                        // escape counts per sample index of a chunked (> 128 samples) shadow stage; zero between frames
         DBuf tile_cost, tile_order;        // walk length per 8x8 tile of the last shaft launch / the next one's longest-first lists
@@ -204,7 +206,7 @@ struct sr_scene {
         void release() {
             tile_cost.release(); tile_order.release(); tile_order_tag = 0;
             tile_hint[0].release(); tile_hint[1].release(); tile_hint_cur = 0; tile_hint_epoch = 0;
-            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &ao_escapes, &lf_cells, &lf_list, &lf_stage, &pt_flags, &pt_index, &pt_totals, &pt_carry};
+            DBuf* b[] = {&hits, &hits2, &bounce_levels, &bounce_nlev, &bounce_prep, &bounce_res, &bounce_stack, &samples, &counters, &fallback, &fallback_state, &fallback_rays, &fallback_ovf, &ray_sort, &ray_sort_temp, &accum, &ao_escapes, &lf_cells, &lf_list, &lf_fracs, &lf_stage, &pt_flags, &pt_index, &pt_totals, &pt_carry};
             for (DBuf* x : b) x->release();
             for (int r = 0; r < sr::kShaftRounds; ++r) { rlist[r].release(); rstate[r].release(); rcount[r].release(); rcand[r].release(); }
             if (stream) (void)hipStreamDestroy(stream);
@@ -974,13 +976,21 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     const bool split = (shadows || bounce_pipe) && !static_shadows && !ao && !lf && !pts && want_split > 1 && fc.num_rows >= 32 * want_split && !(f->flags & SR_F_NO_SPLIT);
     const int halves = split ? want_split : 1;
     const int rows_half = split ? (int)((((long long)fc.num_rows + halves - 1) / halves + 15) / 16 * 16) : fc.num_rows;
-    const long long budget = kMaxBandSamples / halves;
+    // an interpolating light-field band lists up to 16 cells per sample (never more than the table has).  Without shadows only the fill list
+    // grows; with shadows every listed cell may become a hit of the shadow stage, whose scratch is 100+ bytes per hit: the band shrinks to
+    // 1/16 of the budget instead, so that the stage's scratch stays what a nearest-lookup frame reserves
+    const bool lf_interp = lf && !bake && s->lf_interp;
+    const long long budget = kMaxBandSamples / halves / ((lf_interp && shadows) ? 16 : 1);
     // queue capacity counts whole 16x16-pixel tiles: the tile-aligned hit queue of the shaft path gives every wave (8x8 pixels
     // x one sub-sample) 64 entries, also at the right / bottom edge of the frame
     const long long wpad = ((long long)fc.width + 15) / 16 * 16;
     long long band_rows = std::max<long long>(16, (budget / (wpad * n2)) / 16 * 16);
     band_rows = std::min<long long>(band_rows, ((long long)rows_half + 15) / 16 * 16);
     long long band_samples = band_rows * wpad * n2;
+    const long long lf_band_samples = band_samples;                     // per-sample scratch of a light-field band
+    const long long lf_list_cells = lf_interp ? std::min<long long>(16 * band_samples, (long long)lf_entries(s->lf_res)) : band_samples;
+    if (lf_interp && shadows) band_samples = std::max(band_samples, lf_list_cells);      // the queue, the staging buffer and the stage's lists: one slot per listed cell
+    const bool lf_carry = lf_interp && s->dbg[SR_DBG_KERNEL_SWITCH] != 39;               // (hook 39: the apply kernel computes base cell and fractions again; same frame)
     if (bake) {
         // a bake pass: whole origin patches (2 N^2 cells each), at most kBakeShadowPassCells cells (SR_DBG_BAND_SAMPLES shrinks the pass), at least one patch
         const long long per_origin = 2ll * s->lf_res * s->lf_res;
@@ -1068,8 +1078,9 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         if (shadows || bounce_pipe || path || ao) SR_HIP(B.hits.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
         if (ao) SR_HIP(B.ao_escapes.reserve((size_t)band_samples * 4));
         if (lf && !bake) {
-            SR_HIP(B.lf_cells.reserve((size_t)band_samples * 4));
-            SR_HIP(B.lf_list.reserve((size_t)band_samples * 4));
+            if (!lf_interp || lf_carry) SR_HIP(B.lf_cells.reserve((size_t)lf_band_samples * 4));
+            if (lf_carry) SR_HIP(B.lf_fracs.reserve((size_t)lf_band_samples * 32));
+            SR_HIP(B.lf_list.reserve((size_t)lf_list_cells * 4));
         }
         if (lf && shadows) SR_HIP(B.lf_stage.reserve((size_t)band_samples * 4));
         if (path || ao) {
@@ -1135,7 +1146,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
                 if (r > 0) SR_HIP(B.rstate[r].reserve((size_t)round_items[r] * sr::pipeline_round_state_bytes()));
             }
         }
-        if (n2 > 1 && !bake) SR_HIP(B.samples.reserve((size_t)band_samples * 4));
+        if (n2 > 1 && !bake) SR_HIP(B.samples.reserve((size_t)(lf ? lf_band_samples : band_samples) * 4));
         bool accum_fresh = false;
         if (chunked_shadows) {
             // indexed like the sample buffer: the frame (or the compact strips) for one sample per pixel, band-local otherwise (a light field's
@@ -1186,6 +1197,9 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.lf_list = lf ? (uint32_t*)B.lf_list.p : nullptr;
         P.lf_shadows = lf && shadows;
         P.lf_stage = (lf && shadows) ? (uint32_t*)B.lf_stage.p : nullptr;
+        P.lf_interp = lf_interp;
+        P.lf_carry = lf_carry;
+        P.lf_fracs = lf_carry ? (double*)B.lf_fracs.p : nullptr;
         if (bake) {
             P.lf_bake_first = bake->first; P.lf_bake_count = bake->count;
             P.lf_bake_pass_cells = (uint64_t)band_samples;
@@ -2155,6 +2169,34 @@ int sr_set_light_field_shadows(sr_scene* s, int32_t on) {
 
 int32_t sr_get_light_field_shadows(const sr_scene* s) {
     return (s && s->lf_shadows) ? 1 : 0;
+}
+
+int sr_set_light_field_interpolation(sr_scene* s, int32_t on) {
+    if (!s || (on != 0 && on != 1)) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_light_field_interpolation (0 or 1)");
+    s->lf_interp = on != 0;                                         // (the table stays: both lookups read and fill the same entries)
+    for (sr_scene* part : s->parts) part->lf_interp = on != 0;
+    return SR_OK;
+}
+
+int32_t sr_get_light_field_interpolation(const sr_scene* s) {
+    return (s && s->lf_interp) ? 1 : 0;
+}
+
+int sr_light_field_coords(sr_scene* s, int64_t n, const double* starts, const double* dirs, double* coords, uint8_t* inside) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || n < 0 || (n > 0 && (!starts || !dirs || !coords || !inside))) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_light_field_coords");
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (n == 0) return SR_OK;
+    size_t sizes[4] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 32, (size_t)n};
+    for (int i = 0; i < 4; ++i) SR_HIP(s->d_io[i].reserve(sizes[i]));
+    SR_HIP(hipMemcpy(s->d_io[0].p, starts, sizes[0], hipMemcpyHostToDevice));
+    SR_HIP(hipMemcpy(s->d_io[1].p, dirs, sizes[1], hipMemcpyHostToDevice));
+    SR_HIP(sr::launch_lf_coords(n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, s->lf_res, (double*)s->d_io[2].p, (uint8_t*)s->d_io[3].p, nullptr));
+    SR_HIP(hipStreamSynchronize(nullptr));
+    SR_HIP(hipMemcpy(coords, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost));
+    SR_HIP(hipMemcpy(inside, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost));
+    return SR_OK;
 }
 
 int sr_reset_light_field(sr_scene* s) {

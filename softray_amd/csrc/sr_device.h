@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_COUNT = 29 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_COUNT = 31 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -130,6 +130,11 @@ struct PipelineLaunch {
     uint64_t      lf_bake_first, lf_bake_count, lf_bake_pass_cells;
     unsigned long long* lf_bake_filled;
     bool          lf_bake_packet;   // BakeLaunch::packet
+    // quad-linear interpolation (sr_set_light_field_interpolation): k_lfi_lookup / k_lfi_apply take the places of k_lf_lookup / k_lf_apply, and
+    // lf_list (with shadows also hits, lf_stage and the shadow stage's lists) has room for min(16 x band samples, lf_entries) cells
+    bool          lf_interp;
+    bool          lf_carry;         // the lookup hands base cell (lf_cells) and fractions (lf_fracs) to the apply kernel; false (hook 39): apply computes them again
+    double*       lf_fracs;         // device [band samples][4] (lf_carry), else nullptr
     // sr_shadow_points (pts_n > 0: launch_pipeline renders no rows): n caller-given surface points in passes of pts_pass (band samples) go through
     // the frame's dynamic shadow stage as a compact queue in `hits`; pts_out is the stage's sample buffer (k_pts_ingest, sr_pipeline.hip)
     int64_t       pts_n, pts_pass;
@@ -204,6 +209,8 @@ struct BakeLaunch {
     void*       user;
 };
 hipError_t launch_lf_bake(const BakeLaunch& L);
+// sr_light_field_coords: RayToFloat4D of n rays at resolution `res` (k_lf_coords, sr_pipeline.hip: the device function of the interpolating frame kernels)
+hipError_t launch_lf_coords(long long n, const double* starts, const double* dirs, int res, double* coords, uint8_t* inside, hipStream_t stream);
 // per-frame pre-pass: a copy of the four-wide nodes with every node's children sorted by the distance of their box centres from
 // `point` (model space), nearest first (camera origin) or farthest first (light: nearest to the surface points first)
 // swap_mask (bit a): exchange lo and hi on axis a in the copy (the rays of the frame travel towards smaller coordinates there)

@@ -4084,6 +4084,154 @@ __global__ __launch_bounds__(256) void k_lf_apply(FrameConst fc, const int32_t* 
 }
 
 // --------------------------------------------------------------------------------------------------
+// Quad-linear interpolation (sr_set_light_field_interpolation; LightFieldColorMethod.Interpolate, LightFieldColorMethod.cs:142-181): the
+// colour of a camera sample is the blend of the 16 entries around its 4-D coordinate F = RayToFloat4D (LightField4D.cs:214-245; scaled by 2N
+// and N where the nearest lookup's RayToCoord4D scales by 2N - 1 and N - 1 -- the reference's mismatch, kept).  Base b_k = (byte)F_k,
+// fraction F_k - b_k; the 16 cells are ((b_u + du) % 2N, (b_v + dv) % N, (b_s + ds) % 2N, (b_t + dt) % N), du outermost, dt innermost.
+// An empty one is filled first, by the fill stage of the nearest lookup (k_lf_fill, with shadows k_lf_store) over a longer list.  Per band:
+//   k_lfi_lookup  lane = camera sample: F, then 16 neighbour steps; in each the lanes whose cell is empty claim it in the bitmap and the
+//                 winners of the wave append to the fill list with ONE atomicAdd (so 16 per wave at most, not 16 x 64)
+//   k_lfi_apply   lane = camera sample: 16 gathers, the FP64 blend in the reference's operand order, store
+// CARRY (production: measured faster): the lookup leaves the packed base cell (4 bytes) and the four fractions (32 bytes) per
+// sample for the apply kernel; !CARRY (SR_DBG_KERNEL_SWITCH 39): the apply kernel computes them again from the camera ray (two atan2, two
+// asin) and the lookup stores nothing per sample.
+// Every coordinate is reduced modulo its axis, so an index lies inside the table whatever the angles were.
+// --------------------------------------------------------------------------------------------------
+struct LfF4 { double u, v, s, t; };
+
+// Sphere.IntersectLine + LightField4D.RayToFloat4D; false: the line misses the sphere (F = 0)
+__device__ __forceinline__ bool lf_float4d(D3 start, D3 dir, int N, LfF4& F) {
+    F.u = F.v = F.s = F.t = 0.0;
+    const D3 d = normalise(dir);
+    const double proj = dot(start, d);
+    const double term = proj * proj - dot(start, start) + kLfRadius * kLfRadius;
+    if (term < kLfEpsilon) return false;
+    const double root = sqrt(term);
+    const D3 p1 = start + d * (-proj - root), p2 = start + d * (-proj + root);
+    const double u = atan2(p1.x, p1.z) / kLfPi * 0.5 + 0.5, v = asin(p1.y / kLfRadius) / kLfPi + 0.5;
+    const double s = atan2(p2.x, p2.z) / kLfPi * 0.5 + 0.5, t = asin(p2.y / kLfRadius) / kLfPi + 0.5;
+    F.u = u * (N * 2); F.v = v * N; F.s = s * (N * 2); F.t = t * N;
+    return true;
+}
+
+// the base cell, one byte per axis (u lowest), and the fractions
+__device__ __forceinline__ uint32_t lfi_base(const LfF4& F, LfF4& frac) {
+    const uint32_t bu = lf_coord(F.u), bv = lf_coord(F.v), bs = lf_coord(F.s), bt = lf_coord(F.t);
+    frac.u = F.u - (double)bu; frac.v = F.v - (double)bv; frac.s = F.s - (double)bs; frac.t = F.t - (double)bt;
+    return bu | bv << 8 | bs << 16 | bt << 24;
+}
+
+// the index of neighbour k = du * 8 + dv * 4 + ds * 2 + dt of the packed base cell
+__device__ __forceinline__ uint32_t lfi_cell(uint32_t base, int k, uint32_t n) {
+    const uint32_t u = ((base & 255u) + ((uint32_t)k >> 3 & 1u)) % (2u * n), v = ((base >> 8 & 255u) + ((uint32_t)k >> 2 & 1u)) % n;
+    const uint32_t s = ((base >> 16 & 255u) + ((uint32_t)k >> 1 & 1u)) % (2u * n), t = ((base >> 24) + ((uint32_t)k & 1u)) % n;
+    return ((u * n + v) * 2u * n + s) * n + t;
+}
+
+// sr_light_field_coords: RayToFloat4D in batch, one lane per ray
+__global__ __launch_bounds__(256) void k_lf_coords(long long n, const double* __restrict__ starts, const double* __restrict__ dirs, int N,
+                                                   double* __restrict__ coords, uint8_t* __restrict__ inside) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    LfF4 F;
+    const bool in = lf_float4d(mk(starts[i * 3], starts[i * 3 + 1], starts[i * 3 + 2]), mk(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]), N, F);
+    coords[i * 4] = F.u; coords[i * 4 + 1] = F.v; coords[i * 4 + 2] = F.s; coords[i * 4 + 3] = F.t;
+    inside[i] = in ? 1 : 0;
+}
+
+// the camera ray of sample `id` of the band (the order of the sample buffer, as k_lf_lookup)
+__device__ __forceinline__ bool lfi_sample(const FrameConst& fc, const int32_t* __restrict__ row_map, int row_begin, uint32_t id, int N, LfF4& F) {
+    const uint32_t n2 = (uint32_t)(fc.sub_pixel_res * fc.sub_pixel_res);
+    const uint32_t pix = id / n2, si = id - pix * n2;
+    const uint32_t brow = pix / (uint32_t)fc.width, col = pix - brow * (uint32_t)fc.width;
+    D3 ss, dw;
+    lf_camera_ray(fc, (int)col, row_map[row_begin + (int)brow], (int)si, ss, dw);
+    return lf_float4d(ss, dw, N, F);
+}
+
+// list: room for min(16 x band samples, 4 N^4) cells (sr_api.cpp) -- a cell has one winner per band, a sample 16 cells: it cannot overflow
+template <bool CARRY>
+__global__ __launch_bounds__(256) void k_lfi_lookup(FrameConst fc, const int32_t* __restrict__ row_map, int row_begin, uint32_t nsamples, int N,
+                                                    const uint32_t* __restrict__ cache, uint32_t* __restrict__ claim, uint32_t* __restrict__ cells,
+                                                    double* __restrict__ fracs, uint32_t* __restrict__ list, unsigned int* __restrict__ list_count,
+                                                    unsigned long long* stats) {
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+    const bool live = id < nsamples;
+    uint32_t base = kLfMiss;
+    if (live) {
+        LfF4 F, frac;
+        if (lfi_sample(fc, row_map, row_begin, id, N, F)) base = lfi_base(F, frac);
+        if (CARRY) {
+            cells[id] = base;
+            if (base != kLfMiss) {
+                double* o = fracs + (size_t)id * 4;
+                o[0] = frac.u; o[1] = frac.v; o[2] = frac.s; o[3] = frac.t;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        bool won = false;
+        uint32_t cell = 0u;
+        if (base != kLfMiss) {
+            cell = lfi_cell(base, k, (uint32_t)N);
+            if (cache[cell] == 0u) {
+                // (a look before the atomic: on an empty table thousands of samples meet in one cell, and all but the first few find the bit set)
+                const uint32_t bit = 1u << (cell & 31u);
+                if (!(__hip_atomic_load(&claim[cell >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) won = !(atomicOr(&claim[cell >> 5], bit) & bit);
+            }
+        }
+        const unsigned int slot = lf_queue_slot(won, list_count);
+        if (won) list[slot] = cell;
+    }
+    if (stats) {
+        const unsigned long long lm = __ballot(live);
+        if ((threadIdx.x & 63u) == 0u) stat_add(&stats[0], (uint32_t)__popcll(lm));
+    }
+}
+
+// no entry it reads is empty: the band's fill ran in between.  (byte) of a channel is lf_coord's (byte)
+template <bool CARRY>
+__global__ __launch_bounds__(256) void k_lfi_apply(FrameConst fc, const int32_t* __restrict__ row_map, int row_begin, uint32_t nsamples, int N,
+                                                   const uint32_t* __restrict__ cells, const double* __restrict__ fracs,
+                                                   const uint32_t* __restrict__ cache, uint32_t* __restrict__ samples) {
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= nsamples) return;
+    uint32_t base = kLfMiss;
+    LfF4 frac;
+    if (CARRY) {
+        base = cells[id];
+        const double* f = fracs + (size_t)id * 4;
+        if (base != kLfMiss) { frac.u = f[0]; frac.v = f[1]; frac.s = f[2]; frac.t = f[3]; }
+    } else {
+        LfF4 F;
+        if (lfi_sample(fc, row_map, row_begin, id, N, F)) base = lfi_base(F, frac);
+    }
+    uint32_t color = fc.background;
+    if (base != kLfMiss) {
+        uint32_t c[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) c[k] = cache[lfi_cell(base, k, (uint32_t)N)];   // (dt pairs: neighbours in memory unless t wraps; ds pairs: N apart)
+        double r = 0.0, g = 0.0, b = 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const double wu = (k & 8) ? frac.u : 1 - frac.u, wv = (k & 4) ? frac.v : 1 - frac.v;
+            const double ws = (k & 2) ? frac.s : 1 - frac.s, wt = (k & 1) ? frac.t : 1 - frac.t;
+            r = r + (double)(c[k] >> 16 & 255u) / 255.0 * wu * wv * ws * wt;
+            g = g + (double)(c[k] >> 8 & 255u) / 255.0 * wu * wv * ws * wt;
+            b = b + (double)(c[k] & 255u) / 255.0 * wu * wv * ws * wt;
+        }
+        color = 0xFF000000u | lf_coord(r * 255.0) << 16 | lf_coord(g * 255.0) << 8 | lf_coord(b * 255.0);
+    }
+    if (fc.sub_pixel_res == 1) {                                             // the sample buffer is the frame itself
+        const uint32_t brow = id / (uint32_t)fc.width, col = id - brow * (uint32_t)fc.width;
+        samples[(size_t)row_map[row_begin + (int)brow] * fc.width + col] = color;
+    } else {
+        samples[id] = color;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_lf_bake (sr_bake_light_field): the DENSE fill of the table -- every entry of [lo, hi) that is still 0 gets what k_lf_fill would store
 // for it.  Work item = one wave = one origin patch (u, v) x an 8x8 tile of target patches (s0 .. s0 + 7, t0 .. t0 + 7) clipped to 2N x N;
 // items are numbered origin-major, t tiles fastest.  Lane l holds the target (s0 + (l >> 3), t0 + (l & 7)): t is the fastest index of the
@@ -4948,7 +5096,8 @@ static hipError_t launch_lf_shadows_t(const PipelineLaunch& L, long long max_hit
 
 constexpr int kLfListCount = 16;      // counters[16]: the fill list's length of a shadowed light-field band (counters[0..15] are the shadow stage's)
 
-// the three light-field kernels of one row band (see k_lf_lookup); counters[0] is the length of the band's fill list.  Nothing waits
+// the three light-field kernels of one row band (see k_lf_lookup; L.lf_interp: k_lfi_lookup and k_lfi_apply around the same fill stage, whose
+// list then holds up to 16 cells per sample); counters[0] is the length of the band's fill list.  Nothing waits
 // for the device: k_lf_fill reads the length itself.  With shadows (L.lf_shadows) the fill list's length lives in counters[kLfListCount],
 // k_lf_fill<SHADOW> leaves the hits in the band's queue (counters[0]) and the shadow stage + k_lf_store run between fill and apply
 template <int MODE, bool EXTRA>
@@ -4961,15 +5110,25 @@ static hipError_t launch_lightfield_t(const PipelineLaunch& L, int row_begin, in
     hipError_t e;
     hipEvent_t e0, e1;
     if ((e = hipMemsetAsync(L.counters, 0, (shadowed ? (size_t)kCounterWords : 1) * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
-    pipe_events(L, K_LF_LOOKUP, e0, e1);
+    pipe_events(L, L.lf_interp ? K_LFI_LOOKUP : K_LF_LOOKUP, e0, e1);
     if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_lf_lookup, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, L.lf_entries, (const uint32_t*)L.lf_cache, L.lf_claim,
-                       L.lf_cells, L.lf_list, list_count, L.stats);
+    if (L.lf_interp) {
+        const auto lookup = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, (const uint32_t*)L.lf_cache, L.lf_claim,
+                               L.lf_cells, L.lf_fracs, L.lf_list, list_count, L.stats);
+        };
+        if (L.lf_carry) lookup(k_lfi_lookup<true>); else lookup(k_lfi_lookup<false>);
+    } else {
+        hipLaunchKernelGGL(k_lf_lookup, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, L.lf_entries, (const uint32_t*)L.lf_cache, L.lf_claim,
+                           L.lf_cells, L.lf_list, list_count, L.stats);
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
     pipe_events(L, K_LF_FILL, e0, e1);
     if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    const unsigned fblocks = std::min(blocks, (unsigned)L.persistent_blocks);
+    // (an interpolating band lists up to min(16 x samples, 4 N^4) cells)
+    const long long max_cells = L.lf_interp ? std::min<long long>(16ll * nsamples, (long long)L.lf_entries) : (long long)nsamples;
+    const unsigned fblocks = (unsigned)std::min<long long>((max_cells + 255) / 256, (long long)L.persistent_blocks);
     const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
     unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
     if (shadowed) {
@@ -4987,10 +5146,18 @@ static hipError_t launch_lightfield_t(const PipelineLaunch& L, int row_begin, in
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    if (shadowed && (e = launch_lf_shadows_t<MODE, EXTRA>(L, (long long)nsamples, L.lf_claim)) != hipSuccess) return e;
-    pipe_events(L, K_LF_APPLY, e0, e1);
+    if (shadowed && (e = launch_lf_shadows_t<MODE, EXTRA>(L, max_cells, L.lf_claim)) != hipSuccess) return e;
+    pipe_events(L, L.lf_interp ? K_LFI_APPLY : K_LF_APPLY, e0, e1);
     if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_lf_apply, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, (const uint32_t*)L.lf_cells, (const uint32_t*)L.lf_cache, samples);
+    if (L.lf_interp) {
+        const auto apply = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, (const uint32_t*)L.lf_cells, (const double*)L.lf_fracs,
+                               (const uint32_t*)L.lf_cache, samples);
+        };
+        if (L.lf_carry) apply(k_lfi_apply<true>); else apply(k_lfi_apply<false>);
+    } else {
+        hipLaunchKernelGGL(k_lf_apply, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, (const uint32_t*)L.lf_cells, (const uint32_t*)L.lf_cache, samples);
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
     return hipSuccess;
@@ -5118,6 +5285,12 @@ hipError_t launch_lf_bake(const BakeLaunch& L) {
         case MODE_BVH: return extra ? launch_lf_bake_t<MODE_BVH, true>(L) : launch_lf_bake_t<MODE_BVH, false>(L);
         default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_lf_coords(long long n, const double* starts, const double* dirs, int res, double* coords, uint8_t* inside, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lf_coords, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, starts, dirs, res, coords, inside);
+    return hipGetLastError();
 }
 
 static hipError_t launch_resolve(const PipelineLaunch& L, int row_begin, int row_count) {

@@ -226,6 +226,10 @@ public:
     // outermost decorator (Renderer.cs:1640-1649), so the table then stores shadowed colours (RendererTests.cs:240).  Off: CheckLightField refuses
     bool LightFieldShadows() const { return sr_get_light_field_shadows(scene_) != 0; }
     void LightFieldShadows(bool value) { sr_check(sr_set_light_field_shadows(scene_, value ? 1 : 0)); }
+    // LightFieldColorMethod.Interpolate (LightFieldColorMethod.cs:50, 142-181; hard-wired false in the reference): light-field frames blend the
+    // 16 entries around a sample's RayToFloat4D coordinate (sr_set_light_field_interpolation).  Does not touch the table
+    bool LightFieldInterpolate() const { return sr_get_light_field_interpolation(scene_) != 0; }
+    void LightFieldInterpolate(bool value) { sr_check(sr_set_light_field_interpolation(scene_, value ? 1 : 0)); }
     // library extension: the reference has a constant there (voxelGridSize = 64, Renderer.cs:1570).  1..256; another value drops the grid,
     // which the next voxel frame makes again (sr_set_voxel_res)
     int VoxelGridSize() const { return (int)sr_get_voxel_res(scene_); }

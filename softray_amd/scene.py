@@ -262,6 +262,27 @@ class GpuScene:
     def light_field_shadows(self, on):
         _check(_lib.lib().sr_set_light_field_shadows(self._h, 1 if on else 0))
 
+    @property
+    def light_field_interpolation(self):
+        """Whether SR_F_LIGHT_FIELD frames blend the 16 entries around a sample's 4-D coordinate (sr_set_light_field_interpolation)."""
+        return bool(_lib.lib().sr_get_light_field_interpolation(self._h))
+
+    @light_field_interpolation.setter
+    def light_field_interpolation(self, on):
+        _check(_lib.lib().sr_set_light_field_interpolation(self._h, 1 if on else 0))
+
+    def light_field_coords(self, starts, dirs):
+        """LightField4D.RayToFloat4D of every line (sr_light_field_coords), computed on the device at light_field_res: (float64 [n, 4], bool [n] --
+        False: the line misses the sphere and its coordinates are 0)."""
+        starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        if dirs.shape[0] != starts.shape[0]:
+            raise ValueError("starts and dirs must have the same length")
+        coords = np.zeros((starts.shape[0], 4), dtype=np.float64)
+        inside = np.zeros(starts.shape[0], dtype=np.uint8)
+        _check(_lib.lib().sr_light_field_coords(self._h, starts.shape[0], _p(starts), _p(dirs), _p(coords), _p(inside)))
+        return coords, inside.astype(bool)
+
     def reset_light_field(self):
         """Forget the light field: what a new Renderer starts with."""
         _check(_lib.lib().sr_reset_light_field(self._h))

@@ -94,6 +94,11 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_get_light_field_shadows(IntPtr scene);
         [DllImport(Lib)] public static extern int sr_set_light_field_interpolation(IntPtr scene, int on);
         [DllImport(Lib)] public static extern int sr_get_light_field_interpolation(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_set_light_field_triangles(IntPtr scene, int on);
+        [DllImport(Lib)] public static extern int sr_get_light_field_triangles(IntPtr scene);
+        [DllImport(Lib)] public static extern int sr_get_light_field_tris(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
+        [DllImport(Lib)] public static extern int sr_set_light_field_tris(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
+        [DllImport(Lib)] public static extern long sr_tree_handle_leaf(IntPtr scene, long tri, [Out] double[] box, [Out] int[] members, long cap);
         [DllImport(Lib)] public static extern int sr_light_field_coords(IntPtr scene, long n, [In] double[] starts, [In] double[] dirs, [Out] double[] coords, [Out] byte[] inside);
         [DllImport(Lib)] public static extern int sr_get_light_field(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
@@ -146,7 +151,7 @@ namespace Engine3D.Hip
         public const int AoCacheBytes = 128 * 128 * 128;
         /// rayTraceLightField with LightFieldStoresTriangles = false (Renderer.cs:1640-1649) = SR_F_LIGHT_FIELD: pass it in `flags`.  Not together
         /// with F_SHADOWS, F_AMBIENT_OCCLUSION, F_PATH_TRACING, F_VOXELS or mirror bounces (SR_ERR_UNSUPPORTED -> InvalidOperationException);
-        /// LightFieldStoresTriangles = true (LightFieldTriMethod) keeps the CPU chain.  The table of 4 N^4 uint entries lives in the scene:
+        /// LightFieldStoresTriangles = true (LightFieldTriMethod) is an opt-in: LightFieldTriangles = true, then the same flag runs it on the triangle table.  The table of 4 N^4 uint entries lives in the scene:
         /// LightFieldResolution is N (default 64 = lightFieldRes), ResetLightField() is what a new Renderer starts with (call it when
         /// LightFieldStoresTriangles changes, Renderer.cs:420-445), Get / SetLightField move ranges of the reference's .cache file.
         public const uint F_LIGHT_FIELD = 1u << 15;
@@ -482,6 +487,23 @@ namespace Engine3D.Hip
         {
             get { return Native.sr_get_light_field_interpolation(scene) != 0; }
             set { Native.Check(Native.sr_set_light_field_interpolation(scene, value ? 1 : 0)); }
+        }
+        /// Opt-in: LightFieldStoresTriangles = true (LightFieldTriMethod, Renderer.cs:1590-1611).  SR_F_LIGHT_FIELD frames and BakeLightField then run on the
+        /// triangle table (0 empty, 1 nothing, t + 2 triangle t), which depends on the model alone; the reference tree must be built, SR_MODE_BRUTE and
+        /// shadows are refused.  Does not touch either table (sr_set_light_field_triangles)
+        public bool LightFieldTriangles
+        {
+            get { return Native.sr_get_light_field_triangles(scene) != 0; }
+            set { Native.Check(Native.sr_set_light_field_triangles(scene, value ? 1 : 0)); }
+        }
+        /// entries.Length entries of the triangle table from index first
+        public void GetLightFieldTris(uint[] entries, ulong first)
+        {
+            Native.Check(Native.sr_get_light_field_tris(scene, entries, first, (ulong)entries.Length));
+        }
+        public void SetLightFieldTris(uint[] entries, ulong first)
+        {
+            Native.Check(Native.sr_set_light_field_tris(scene, entries, first, (ulong)entries.Length));
         }
         /// LightField4D.RayToFloat4D in batch, on the device at LightFieldResolution: coords [n * 4], inside [n] (0: the line misses the sphere)
         public void LightFieldCoords(double[] starts, double[] dirs, double[] coords, byte[] inside)

@@ -154,7 +154,7 @@ enum {
                                      host- and device-built BVH and frames of more than one row band.  The frame runs as one pipeline (as with SR_F_NO_SPLIT);
                                      a multi-device scene renders it on devices[0] alone.  SR_ERR_UNSUPPORTED together with SR_F_SHADOWS (static always; dynamic unless sr_set_light_field_shadows),
                                      SR_F_AMBIENT_OCCLUSION, SR_F_PATH_TRACING, SR_F_VOXELS, max_bounces > 0, SR_F_SINGLE_KERNEL, strip_count > 0 and
-                                     sr_rccl_render.  Not covered: LightFieldStoresTriangles = true (LightFieldTriMethod).  Quad-linear interpolation
+                                     sr_rccl_render.  LightFieldStoresTriangles = true (LightFieldTriMethod) is an opt-in per scene: sr_set_light_field_triangles.  Quad-linear interpolation
                                      (LightFieldColorMethod.Interpolate, hard-wired false in the reference) is an opt-in per scene: sr_set_light_field_interpolation.
                                      Statistics: stats[0] = the camera samples, [1..3] = 0; sr_last_ray_stats [4] grows by one per filled cell, [5..7] by what
                                      the canonical rays' walks count (not with SR_F_PRIMARY_STATS_ONLY)                                  */
@@ -366,6 +366,12 @@ int     sr_set_voxel_res(sr_scene*, int32_t n);
 int32_t sr_get_voxel_res(const sr_scene*);
 /* out = TreeDepth, NumNodes, NumLeafNodes, NumInternalNodes (SpatialSubdivision.cs:317-335) */
 int  sr_tree_stats(const sr_scene*, int32_t out[4]);
+/* diagnostics: Triangle.HandleToLeafNode of triangle `tri` -- the leaf ProcessLeafNode assigned LAST (SpatialSubdivision.cs:235-243; nodes are built
+ * normal side first, so the leaf with the highest node index whose list holds the triangle), which the second stage of the triangle light field
+ * searches (sr_set_light_field_triangles).  box = the leaf's box as the containment test uses it (min - 1e-10 x 3, max + 1e-10 x 3); members = the
+ * leaf's TriangleIndex list in the leaf's order, at most `cap` of them (members may be NULL with cap 0).  Returns the leaf's member count, or
+ * SR_ERR_NOT_BUILT without a reference tree, SR_ERR_INVALID_ARG for a bad argument.  Works on a host-only scene. */
+int64_t sr_tree_handle_leaf(const sr_scene*, int64_t tri, double box[6], int32_t* members, int64_t cap);
 /* the library's own BVH: out = depth, inner nodes, triangles, 1 if it was built on the device */
 int  sr_bvh_stats(const sr_scene*, int64_t out[4]);
 /* diagnostics: FNV-1a hashes of the host-built BVH's node array and of its leaf-ordered triangle indices (the host build must not
@@ -451,6 +457,49 @@ int32_t sr_get_light_field_shadows(const sr_scene*);
  * no host synchronisation inside a frame.  Statistics as for a light-field frame: [0] = camera samples, [4..7] = the canonical rays of filled cells. */
 int  sr_set_light_field_interpolation(sr_scene*, int32_t on);
 int32_t sr_get_light_field_interpolation(const sr_scene*);
+/* The triangle-index light field, opt-in per scene: rayTraceLightField with LightFieldStoresTriangles = true -> LightFieldTriMethod (Renderer.cs:1590-1611,
+ * LightFieldTriMethod.cs:82-231; the reference's own default).  on = 1: the SR_F_LIGHT_FIELD frames of sr_render / sr_render_device and sr_bake_light_field
+ * run this method on the TRIANGLE TABLE, a second table of 4 N^4 uint32 beside the colour table (allocated on first use; neither touches the other):
+ *   entry 0 = empty, 1 = the cell's canonical ray hit nothing, e >= 2 = triangle e - 2.  The reference's ushort wraps above 65 534 triangles (its own
+ *   TODO); the wrap is not reproduced: for n <= 65 534 triangles the low 16 bits of an entry are the reference's .cache value.
+ * LightFieldTriMethod is the INNERMOST decorator: it never consults the root geometry it wraps, so the extra geometry has no effect on such a frame.
+ * Per camera sample, ray (start, dir) in model space, unmodified:
+ *   cell    as for the colour table (same device function); a line that misses the 0.866 sphere is the background;
+ *   fill    an empty entry is filled first: the cell's canonical ray (patch centre P(u, v) towards P(s, t), as for the colour table) is traced
+ *           through the MODEL ALONE in frame->trace_mode; a hit stores TriangleIndex + 2, a miss (and the NaN ray of N = 1) 1.  The entry depends on
+ *           the cell alone: not on the pose, the lights, who fills it or in what order -- a table baked once stays valid while camera, instance
+ *           transform and lights move;
+ *   e == 1  the background;
+ *   stage 1 Triangle.IntersectRay(start, dir) on triangle e - 2 alone -- unclipped start, no root-box clip, no rayFrac offset.  A hit is the result,
+ *           even where another triangle is nearer (the reference's artefact, kept);
+ *   stage 2 (stage 1 missed) IntersectRayWithLeafNode on the triangle's HandleToLeafNode: the reference tree's leaf that listed the triangle last
+ *           (sr_tree_handle_leaf) -- its triangles in the leaf's order against the unclipped ray, nearest hit with strict < whose position lies in the
+ *           leaf's box (1e-10 slack), no offset;
+ *   stage 3 (stage 2 missed) the full trace of the model, SpatialSubdivision.IntersectRay in SR_MODE_REF_TREE; its answer, hit or miss, is the result.
+ * The colour is ShadingMethod's with SR_F_SHADING (position, plane normal, triangle colour), else the triangle's colour; sub-pixel samples, focal blur,
+ * row ranges, bands and the resolve are those of any frame.  The reference tree must be built: SR_MODE_REF_TREE is the literal method; SR_MODE_BVH is a
+ * library option whose FULL traces (canonical rays, stage 3) take the own BVH with its nearest-hit semantics while stages 1 and 2 still read the
+ * reference tree (SR_ERR_NOT_BUILT without it); SR_MODE_BRUTE is SR_ERR_UNSUPPORTED (the method never traces the triangle list).  Every combination a
+ * colour light-field frame refuses stays refused, and SR_F_SHADOWS is refused in both forms whatever sr_set_light_field_shadows says (in the reference
+ * the secondary rays go through this decorator too: not built).  sr_set_light_field_interpolation is ignored while the switch is on; a multi-device
+ * scene renders on devices[0].  A setting like sr_set_light_field_shadows: 0 or 1 (anything else SR_ERR_INVALID_ARG), works on a host-only scene,
+ * survives sr_set_triangles* / sr_load_3ds, is forwarded to the parts of a multi-device scene; default 0: nothing changes anywhere.
+ * sr_get_light_field_tris / sr_set_light_field_tris: range access like the colour table's (a host-only scene keeps a host copy); an entry that names no
+ * triangle of the model reads as 1.  Both tables are dropped by sr_reset_light_field, sr_set_light_field_res, sr_set_triangles*, sr_load_3ds and
+ * sr_refit_triangles_device.  A later sr_build with another max_depth / max_per_leaf keeps the triangle table: in SR_MODE_REF_TREE an entry is the
+ * triangle the tree's walk returns, which depends on the tree only where two leaves disagree about a hit on their common face (the leaf-face rule of
+ * SR_MODE_REF_TREE above).  sr_bake_light_field with the switch on: every empty entry of the range gets TriangleIndex + 2 or 1, *filled counts as
+ * before; the frame is needed for trace_mode only but validated as today.
+ * Statistics of such a frame: [0] camera samples; [1] triangle tests -- one per sample with e >= 2, the leaf's count per sample that reaches stage 2,
+ * what the stage-3 walks count; [2], [3] one node and one leaf per stage-2 call plus the stage-3 walks'; [4] canonical rays traced (one per cell
+ * filled; none for NaN rays), [5..7] their walks ([4..7] are 0 with SR_F_PRIMARY_STATS_ONLY in a frame; a bake counts [4] always).  Without
+ * SR_F_PRIMARY_STATS_ONLY [20..23] hold the stage census instead of the mirror rays' figures: [20] samples with no candidate triangle (sphere miss or
+ * e == 1), [21] resolved by stage 1, [22] by stage 2, [23] that reached stage 3.  [1..3] and [5..7] are pinned in SR_MODE_REF_TREE only; on the own BVH
+ * they count what the walks fetch. */
+int  sr_set_light_field_triangles(sr_scene*, int32_t on);
+int32_t sr_get_light_field_triangles(const sr_scene*);
+int  sr_get_light_field_tris(sr_scene*, uint32_t* out, uint64_t first, uint64_t count);
+int  sr_set_light_field_tris(sr_scene*, const uint32_t* in, uint64_t first, uint64_t count);
 /* LightField4D.RayToFloat4D in batch, at the scene's sr_get_light_field_res: coords[i] = F of the line (starts[i], dirs[i]) (model space, host arrays),
  * inside[i] = 1; a line that misses the sphere: inside[i] = 0 and coords[i] = 0.  Computed on the device by the device function the interpolating
  * frame kernels call, so a caller can reproduce such a frame exactly from these coordinates (the device's atan2 / asin differ from a host's by
@@ -661,7 +710,9 @@ enum {
                                     umbra, [22] the tiles that entered the walk with a lane finished by a hint, [23] the tiles that never took a node step, instead of
                                     the mirror rays' figures; 99 a tile tries its own hint only, not those of the other three tiles of its 16x16 parent; 41 a voxel walk on a grid of at most 64 reads the
                                     colour table instead of the occupancy bits in LDS; 42 a voxel walk on a grid above 64 reads the row-major
-                                    occupancy bits in global memory, one level, instead of the two-level walk                              */
+                                    occupancy bits in global memory, one level, instead of the two-level walk; 43 a triangle light-field frame
+                                    (sr_set_light_field_triangles) lists the samples that need its third stage for a kernel of their own (k_lft_trace) instead of
+                                    tracing them inside k_lft_hit (same frame and statistics; measured slower)                                                */
     SR_DBG_KERNEL_TIMING  = 7,   /* > 0: record a HIP event pair around every launch (sr_kernel_times); default off           */
     SR_DBG_EXACT_SHADOW_TESTS = 8, /* > 0: k_shadow_test decides every (sample, triangle) pair with the FP64 arithmetic (no
                                     fp32 classification): an independent schedule of the same result, kept as a cross-check */

@@ -48,6 +48,7 @@ SYMBOLS = [
     "sr_refit_triangles_device", "sr_set_light_field_shadows", "sr_get_light_field_shadows",
     "sr_shadow_points", "sr_shadow_points_device",
     "sr_set_light_field_interpolation", "sr_get_light_field_interpolation", "sr_light_field_coords",
+    "sr_set_light_field_triangles", "sr_get_light_field_triangles", "sr_get_light_field_tris", "sr_set_light_field_tris", "sr_tree_handle_leaf",
 ]
 POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 GATHER_COPY, GATHER_RCCL = 0, 1
@@ -183,6 +184,11 @@ def lib():
     L.sr_set_light_field_interpolation.restype = i32; L.sr_set_light_field_interpolation.argtypes = [vp, i32]
     L.sr_get_light_field_interpolation.restype = i32; L.sr_get_light_field_interpolation.argtypes = [vp]
     L.sr_light_field_coords.restype = i32; L.sr_light_field_coords.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.sr_set_light_field_triangles.restype = i32; L.sr_set_light_field_triangles.argtypes = [vp, i32]
+    L.sr_get_light_field_triangles.restype = i32; L.sr_get_light_field_triangles.argtypes = [vp]
+    L.sr_get_light_field_tris.restype = i32; L.sr_get_light_field_tris.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
+    L.sr_set_light_field_tris.restype = i32; L.sr_set_light_field_tris.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
+    L.sr_tree_handle_leaf.restype = i64; L.sr_tree_handle_leaf.argtypes = [vp, i64, vp, vp, i64]
     L.sr_net_random_doubles.restype = None; L.sr_net_random_doubles.argtypes = [i32, i64, i64, vp]
     L.sr_last_error.restype = C.c_char_p; L.sr_last_error.argtypes = []
     L.sr_abi_version.restype = i32; L.sr_abi_version.argtypes = []

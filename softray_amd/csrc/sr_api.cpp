@@ -149,6 +149,13 @@ struct sr_scene {
     int32_t lf_points_res = 0;           // the resolution d_lf_points was made for (0: none)
     bool lf_cache_empty = true;          // the device cache (and the claim bits) must be zeroed before their next use
     std::vector<uint32_t> lf_cache_host;
+    // LightFieldStoresTriangles = true (sr_set_light_field_triangles): SR_F_LIGHT_FIELD frames and sr_bake_light_field run LightFieldTriMethod on a SECOND
+    // table of 4 N^4 uint32 (0 empty, 1 the canonical ray hit nothing, t + 2 triangle t) with claim bits of its own; neither table touches the other.
+    // d_rhandle: Triangle.HandleToLeafNode per triangle (RefTree::handle_leaf), uploaded with the reference tree
+    bool lf_tris = false;
+    DBuf d_lft_cache, d_lft_claim, d_rhandle;
+    bool lft_cache_empty = true;
+    std::vector<uint32_t> lft_cache_host;
     // path tracing (SR_F_PATH_TRACING) and ambient occlusion: the InternalSample() ints of Random(pt_table_seed), 3 per sample of the largest row
     // block (300 per generator of the fullest one) a frame has asked for so far; made once per (seed, length) and kept for later frames
     DBuf d_pt_table;
@@ -192,7 +199,7 @@ struct sr_scene {
         DBuf ao_escapes;                   // ambient occlusion: escaped probes, then the byte, per generator (sr_pipeline.hip k_ao_*)
         DBuf lf_cells, lf_list;            // light field: cache index per sample, the cells the band fills (sr_pipeline.hip k_lf_*)
         DBuf lf_fracs;                     // ... interpolating: the four fractions of every sample, from k_lfi_lookup to k_lfi_apply
-        DBuf lf_stage;                     // ... with shadows: the staged colour of every slot of the fill's / a bake pass's hit queue
+        DBuf lf_stage;                     // ... with shadows: the staged colour of every slot of the fill's / a bake pass's hit queue (triangle table: the samples that need the full trace)
         DBuf accum;                        // escape counts per sample index of a chunked (> 128 samples) shadow stage; zero between frames
         DBuf tile_cost, tile_order;        // walk length per 8x8 tile of the last shaft launch / the next one's longest-first lists
         unsigned long long tile_order_tag = 0;   // the tile grid tile_order was made for (0: none)
@@ -305,6 +312,7 @@ int sync_geometry(sr_scene* s, uint32_t need_mode) {
         SR_HIP(s->d_rnodes.upload(h->ref.nodes));
         SR_HIP(s->d_rboxes.upload(h->ref.leaf_boxes));
         SR_HIP(s->d_rleaf.upload(h->ref.leaf_tris));
+        SR_HIP(s->d_rhandle.upload(h->ref.handle_leaf));
         s->ref_dirty = false;
     }
     if (need_mode == SR_MODE_BVH && s->bvh_dirty && !s->bvh_on_device) {
@@ -434,7 +442,10 @@ int check_frame_mode(const sr_scene* s, const sr_frame* f) {
         if (!s->have_model || s->ntris == 0) return fail(SR_ERR_NO_MODEL, "no model: Render() returns without drawing (Renderer.cs:736-739)");
         return SR_OK;
     }
-    return check_mode(s, f->trace_mode);
+    int rc = check_mode(s, f->trace_mode);
+    // LightFieldTriMethod's second stage walks Triangle.HandleToLeafNode: the reference tree, whatever traces the full rays
+    if (!rc && s->lf_tris && (f->flags & SR_F_LIGHT_FIELD)) rc = check_mode(s, SR_MODE_REF_TREE);
+    return rc;
 }
 
 // `s`: the scene whose settings decide what a frame may combine (nullptr: the defaults)
@@ -448,7 +459,13 @@ int validate_frame(const sr_frame* f, const sr_scene* s = nullptr) {
     if ((long long)f->width * f->sub_pixel_res > (1ll << 24) || (long long)f->height > (1ll << 24)) return fail(SR_ERR_INVALID_ARG, "surface too large");
     if (f->max_bounces < 0 || f->max_bounces > 16 || !(f->reflectivity >= 0.0 && f->reflectivity <= 1.0))
         return fail(SR_ERR_INVALID_ARG, "max_bounces must be 0..16 and reflectivity 0..1");
-    int rc = check_light_field(f, s && s->lf_shadows);
+    // LightFieldTriMethod (sr_set_light_field_triangles): every refusal of a colour light-field frame, shadows in both forms whatever
+    // sr_set_light_field_shadows says (the reference's shadow rays go through the decorator too: not built), and no brute-force mode -- the
+    // method never traces the triangle list
+    const bool lft = s && s->lf_tris && (f->flags & SR_F_LIGHT_FIELD);
+    int rc = check_light_field(f, s && s->lf_shadows && !lft);
+    if (!rc && lft && f->trace_mode == SR_MODE_BRUTE)
+        rc = fail(SR_ERR_UNSUPPORTED, "triangle light field (sr_set_light_field_triangles) with SR_MODE_BRUTE is not supported: LightFieldTriMethod reads the spatial subdivision");
     if (!rc) rc = check_ambient_occlusion(f);
     if (!rc) rc = check_voxels(f);
     return rc ? rc : check_path_tracing(f);
@@ -631,6 +648,7 @@ int ensure_draw_table(sr_scene* s, int32_t seed, size_t triples) {
 
 // the scene's light field on the device: the table and its claim bits (allocated on first use, zeroed on `stream` when the scene starts
 // as a new Renderer) and the patch centres of the current resolution.  What a light-field frame and sr_bake_light_field begin with
+int ensure_light_field_points(sr_scene* s);
 int ensure_light_field(sr_scene* s, hipStream_t stream) {
     const int N = s->lf_res;
     const size_t entries = lf_entries(N), claim_bytes = (entries + 31) / 32 * 4;
@@ -642,6 +660,12 @@ int ensure_light_field(sr_scene* s, hipStream_t stream) {
         SR_HIP(hipMemsetAsync(s->d_lf_claim.p, 0, claim_bytes, stream));
         s->lf_cache_empty = false;
     }
+    return ensure_light_field_points(s);
+}
+
+// the 2N x N patch centres of the current resolution (both tables' canonical rays)
+int ensure_light_field_points(sr_scene* s) {
+    const int N = s->lf_res;
     if (s->lf_points_res != N) {
         // Coord4DToRay + Sphere.ConvertLine (LightField4D.cs:253-273, Sphere.cs:122-142) with the host's sin / cos: the device calls neither
         std::vector<double> pts((size_t)2 * N * N * 3);
@@ -661,6 +685,20 @@ int ensure_light_field(sr_scene* s, hipStream_t stream) {
         s->lf_points_res = N;
     }
     return SR_OK;
+}
+
+// the same for the triangle table (sr_set_light_field_triangles): its own entries and claim bits, the patch centres are shared (read-only)
+int ensure_light_field_tris(sr_scene* s, hipStream_t stream) {
+    const size_t entries = lf_entries(s->lf_res), claim_bytes = (entries + 31) / 32 * 4;
+    if (!s->d_lft_cache.p || !s->d_lft_claim.p) s->lft_cache_empty = true;
+    SR_HIP(s->d_lft_cache.reserve(entries * 4));
+    SR_HIP(s->d_lft_claim.reserve(claim_bytes));
+    if (s->lft_cache_empty) {
+        SR_HIP(hipMemsetAsync(s->d_lft_cache.p, 0, entries * 4, stream));
+        SR_HIP(hipMemsetAsync(s->d_lft_claim.p, 0, claim_bytes, stream));
+        s->lft_cache_empty = false;
+    }
+    return ensure_light_field_points(s);
 }
 
 // pt_phase: 0, or the phase (1, 2) of a part of a path-traced frame that multi_render has split (sr_device.h PipelineLaunch::pt_phase)
@@ -686,6 +724,9 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         return fail(SR_ERR_UNSUPPORTED, "path tracing with row strips: a rank would need the hit counts of rows it does not render");
     if ((rc = prepare_frame(s, f, fc))) return rc;
     if ((rc = sync_geometry(s, voxels ? ~0u : (uint32_t)f->trace_mode))) return rc;
+    // LightFieldTriMethod: stage 2 reads the reference tree's leaves whatever trace_mode walks the full rays
+    const bool lft = s->lf_tris && (f->flags & SR_F_LIGHT_FIELD) && !bake && !pts;
+    if (lft && (rc = sync_geometry(s, SR_MODE_REF_TREE))) return rc;
     if (voxels && (rc = ensure_voxels(s, stream))) return rc;
     if (fc.num_rows == 0 && !bake && !pts) return SR_OK;
     // ---- frames of one scene run in submission order whatever streams they are given: the scene's scratch (hit queues, candidate
@@ -979,7 +1020,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     // an interpolating light-field band lists up to 16 cells per sample (never more than the table has).  Without shadows only the fill list
     // grows; with shadows every listed cell may become a hit of the shadow stage, whose scratch is 100+ bytes per hit: the band shrinks to
     // 1/16 of the budget instead, so that the stage's scratch stays what a nearest-lookup frame reserves
-    const bool lf_interp = lf && !bake && s->lf_interp;
+    const bool lf_interp = lf && !bake && s->lf_interp && !lft;          // (Interpolate belongs to the colour method)
     const long long budget = kMaxBandSamples / halves / ((lf_interp && shadows) ? 16 : 1);
     // queue capacity counts whole 16x16-pixel tiles: the tile-aligned hit queue of the shaft path gives every wave (8x8 pixels
     // x one sub-sample) 64 entries, also at the right / bottom edge of the frame
@@ -1062,7 +1103,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         }
     }
     // ---- light field: the scene's cache (allocated on first use), its claim bits and the patch centres of this resolution ----
-    if (lf && (rc = ensure_light_field(s, stream))) return rc;
+    if (lf && (rc = lft ? ensure_light_field_tris(s, stream) : ensure_light_field(s, stream))) return rc;
     const bool path_walk = path && f->trace_mode == SR_MODE_BVH;
     // (path tracing never runs as two halves: the part's rows are one band when they fit the budget)
     const bool pt_reuse = pt_phase && band_rows >= fc.num_rows;
@@ -1083,6 +1124,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             SR_HIP(B.lf_list.reserve((size_t)lf_list_cells * 4));
         }
         if (lf && shadows) SR_HIP(B.lf_stage.reserve((size_t)band_samples * 4));
+        if (lft) SR_HIP(B.lf_stage.reserve((size_t)lf_band_samples * 4));      // the samples of the band that need the full trace (k_lft_hit -> k_lft_trace)
         if (path || ao) {
             SR_HIP(B.hits2.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
             SR_HIP(B.pt_flags.reserve((size_t)band_samples));
@@ -1188,8 +1230,12 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.ao_cache = (ao && !ao_uncached) ? (uint8_t*)s->d_ao_cache.p : nullptr;
         P.ao_claim = (ao && !ao_uncached) ? (unsigned long long*)s->d_ao_claim.p : nullptr;
         P.ao_escapes = ao ? (uint32_t*)B.ao_escapes.p : nullptr;
-        P.lf_cache = lf ? (uint32_t*)s->d_lf_cache.p : nullptr;
-        P.lf_claim = lf ? (uint32_t*)s->d_lf_claim.p : nullptr;
+        P.lf_cache = lf ? (uint32_t*)(lft ? s->d_lft_cache.p : s->d_lf_cache.p) : nullptr;
+        P.lf_claim = lf ? (uint32_t*)(lft ? s->d_lft_claim.p : s->d_lf_claim.p) : nullptr;
+        P.lf_tris = lft;
+        P.lf_handle = lft ? (const int32_t*)s->d_rhandle.p : nullptr;
+        P.lf_trace_list = lft ? (uint32_t*)B.lf_stage.p : nullptr;
+        P.lf_fused = lft && s->dbg[SR_DBG_KERNEL_SWITCH] != 43;       // (hook 43: the full traces as a compact list for k_lft_trace; same frame, measured slower)
         P.lf_points = lf ? (const double*)s->d_lf_points.p : nullptr;
         P.lf_res = lf ? s->lf_res : 0;
         P.lf_entries = lf ? (uint32_t)lf_entries(s->lf_res) : 0u;
@@ -1390,6 +1436,7 @@ void share_host_model(sr_scene* d, const sr_scene* src) {
     d->shadow_cache_empty = true;
     d->ao_cache_empty = true; d->ao_cache_host.clear();
     d->lf_cache_empty = true; d->lf_cache_host.clear();
+    d->lft_cache_empty = true; d->lft_cache_host.clear();
     d->vox_valid = false;
     d->ref = sr::RefTree(); d->bvh = sr::Bvh(); d->bvh_on_device = false;
     d->tris_dirty = d->ref_dirty = d->bvh_dirty = true;
@@ -1493,6 +1540,7 @@ int set_triangles_from_device_enqueue(sr_scene* s, const double* src_v9, const u
     s->shadow_cache_empty = true;                         // a new model: what sr_set_triangles drops
     s->ao_cache_empty = true; s->ao_cache_host.clear();
     s->lf_cache_empty = true; s->lf_cache_host.clear();
+    s->lft_cache_empty = true; s->lft_cache_host.clear();
     s->vox_valid = false;
     std::vector<double>().swap(s->v9);
     std::vector<uint32_t>().swap(s->argb);
@@ -1523,7 +1571,7 @@ void drop_model(sr_scene* s) {
     s->ref = sr::RefTree();
     s->ref_dirty = true;
     drop_bvh(s);
-    s->shadow_cache_empty = s->ao_cache_empty = s->lf_cache_empty = true;
+    s->shadow_cache_empty = s->ao_cache_empty = s->lf_cache_empty = s->lft_cache_empty = true;
     s->vox_valid = false;
     s->tris_dirty = true;
 }
@@ -1598,6 +1646,7 @@ int refit_from_device_enqueue(sr_scene* s, const double* src_v9, const uint32_t*
     s->shadow_cache_empty = true;                         // a new model: what sr_set_triangles_device drops
     s->ao_cache_empty = true; s->ao_cache_host.clear();
     s->lf_cache_empty = true; s->lf_cache_host.clear();
+    s->lft_cache_empty = true; s->lft_cache_host.clear();
     s->vox_valid = false;
     std::vector<double>().swap(s->v9);
     std::vector<uint32_t>().swap(s->argb);
@@ -1704,7 +1753,7 @@ void sr_destroy(sr_scene* s) {
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
-                        &s->d_v9, &s->d_bcam, &s->d_blight, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
+                        &s->d_v9, &s->d_bcam, &s->d_blight, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_lft_cache, &s->d_lft_claim, &s->d_rhandle, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
                         &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse, &s->d_bounds, &s->d_bdepth, &s->d_tbox};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
@@ -1739,6 +1788,7 @@ int sr_set_triangles(sr_scene* s, const double* v9, const uint32_t* argb, int64_
     s->shadow_cache_empty = true;                         // new model: what a new ShadowMethod starts with
     s->ao_cache_empty = true; s->ao_cache_host.clear();   // ... and a new AmbientOcclusion
     s->lf_cache_empty = true; s->lf_cache_host.clear();   // ... and a new LightFieldColorMethod
+    s->lft_cache_empty = true; s->lft_cache_host.clear(); // ... and a new LightFieldTriMethod
     s->vox_valid = false;                                 // ... and a new VoxelGrid
     s->host_model_stale = false;
     s->v9.assign(v9, v9 + 9 * n);
@@ -2034,6 +2084,21 @@ int sr_tree_stats(const sr_scene* s, int32_t out[4]) {
     return SR_OK;
 }
 
+int64_t sr_tree_handle_leaf(const sr_scene* s, int64_t tri, double box[6], int32_t* members, int64_t cap) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !box || cap < 0 || (cap > 0 && !members)) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_tree_handle_leaf");
+    const sr_scene* h = s->host_src ? s->host_src : s;              // where the host arrays are
+    if (!h->ref.built || h->ref.handle_leaf.empty()) return fail(SR_ERR_NOT_BUILT, "reference tree not built");
+    if (tri < 0 || (size_t)tri >= h->ref.handle_leaf.size()) return fail(SR_ERR_INVALID_ARG, "sr_tree_handle_leaf: no such triangle");
+    const int32_t leaf = h->ref.handle_leaf[(size_t)tri];
+    if (leaf < 0) return fail(SR_ERR_NOT_BUILT, "sr_tree_handle_leaf: the triangle is in no leaf");
+    const sr::RefNode& n = h->ref.nodes[(size_t)leaf];
+    const sr::LeafBox& lb = h->ref.leaf_boxes[(size_t)n.box];
+    for (int a = 0; a < 3; ++a) { box[a] = lb.lo[a]; box[3 + a] = lb.hi[a]; }
+    for (int64_t k = 0; k < n.b && k < cap; ++k) members[k] = h->ref.leaf_tris[(size_t)n.a + (size_t)k];
+    return n.b;
+}
+
 int sr_bvh_stats(const sr_scene* s, int64_t out[4]) {
     if (s && !s->parts.empty()) s = s->parts[0];
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "bad argument");
@@ -2149,9 +2214,17 @@ int sr_set_light_field_res(sr_scene* s, int32_t n) {
         if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));
         s->d_lf_cache.release(); s->d_lf_claim.release();
     }
+    if (s->device >= 0 && s->d_lft_cache.p) {                       // ... and the triangle table's
+        int rc = use_device(s);
+        if (rc) return rc;
+        if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));
+        s->d_lft_cache.release(); s->d_lft_claim.release();
+    }
     s->lf_res = n;
     s->lf_cache_empty = true;
     s->lf_cache_host.clear();
+    s->lft_cache_empty = true;
+    s->lft_cache_host.clear();
     return SR_OK;
 }
 
@@ -2182,6 +2255,62 @@ int32_t sr_get_light_field_interpolation(const sr_scene* s) {
     return (s && s->lf_interp) ? 1 : 0;
 }
 
+int sr_set_light_field_triangles(sr_scene* s, int32_t on) {
+    if (!s || (on != 0 && on != 1)) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_light_field_triangles (0 or 1)");
+    s->lf_tris = on != 0;                                           // (both tables stay: the switch selects which one a frame reads and fills)
+    for (sr_scene* part : s->parts) part->lf_tris = on != 0;
+    return SR_OK;
+}
+
+int32_t sr_get_light_field_triangles(const sr_scene* s) {
+    return (s && s->lf_tris) ? 1 : 0;
+}
+
+int sr_get_light_field_tris(sr_scene* s, uint32_t* out, uint64_t first, uint64_t count) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || (!out && count)) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_get_light_field_tris");
+    const uint64_t entries = lf_entries(s->lf_res);
+    if (first > entries || count > entries - first) return fail(SR_ERR_INVALID_ARG, "sr_get_light_field_tris: the range exceeds the 4 N^4 entries");
+    if (count == 0) return SR_OK;
+    if (s->device < 0) {
+        if (s->lft_cache_host.empty()) std::memset(out, 0, (size_t)count * 4);
+        else std::memcpy(out, s->lft_cache_host.data() + first, (size_t)count * 4);
+        return SR_OK;
+    }
+    if (s->lft_cache_empty || !s->d_lft_cache.p) { std::memset(out, 0, (size_t)count * 4); return SR_OK; }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));      // a frame in flight may still be filling cells
+    SR_HIP(hipMemcpy(out, (const uint32_t*)s->d_lft_cache.p + first, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_set_light_field_tris(sr_scene* s, const uint32_t* in, uint64_t first, uint64_t count) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || (!in && count)) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_light_field_tris");
+    const uint64_t entries = lf_entries(s->lf_res);
+    if (first > entries || count > entries - first) return fail(SR_ERR_INVALID_ARG, "sr_set_light_field_tris: the range exceeds the 4 N^4 entries");
+    if (count == 0) return SR_OK;
+    if (s->device < 0) {
+        if (s->lft_cache_host.empty()) s->lft_cache_host.assign((size_t)entries, 0u);
+        std::memcpy(s->lft_cache_host.data() + first, in, (size_t)count * 4);
+        return SR_OK;
+    }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));
+    if (!s->d_lft_cache.p || !s->d_lft_claim.p) s->lft_cache_empty = true;
+    SR_HIP(s->d_lft_cache.reserve((size_t)entries * 4));
+    SR_HIP(s->d_lft_claim.reserve((size_t)((entries + 31) / 32 * 4)));
+    if (s->lft_cache_empty) {                                            // the entries outside the range are those of a new Renderer
+        SR_HIP(hipMemset(s->d_lft_cache.p, 0, (size_t)entries * 4));
+        SR_HIP(hipMemset(s->d_lft_claim.p, 0, (size_t)((entries + 31) / 32 * 4)));
+        s->lft_cache_empty = false;
+    }
+    SR_HIP(hipMemcpy((uint32_t*)s->d_lft_cache.p + first, in, (size_t)count * 4, hipMemcpyHostToDevice));
+    return SR_OK;
+}
+
 int sr_light_field_coords(sr_scene* s, int64_t n, const double* starts, const double* dirs, double* coords, uint8_t* inside) {
     if (s && !s->parts.empty()) s = s->parts[0];
     if (!s || n < 0 || (n > 0 && (!starts || !dirs || !coords || !inside))) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_light_field_coords");
@@ -2204,6 +2333,8 @@ int sr_reset_light_field(sr_scene* s) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_reset_light_field");
     s->lf_cache_empty = true;
     s->lf_cache_host.clear();
+    s->lft_cache_empty = true;                                      // (both tables: a new Renderer has neither)
+    s->lft_cache_host.clear();
     return SR_OK;
 }
 
@@ -2294,14 +2425,17 @@ int sr_bake_light_field(sr_scene* m, const sr_frame* f, uint64_t first, uint64_t
             }
         } mark_pre_used{s, stream};
         SR_HIP(hipMemsetAsync(s->d_stats.p, 0, sizeof(back), stream));
-        if ((rc = ensure_light_field(s, stream))) return rc;
+        const bool lft = s->lf_tris;
+        if (lft && (rc = sync_geometry(s, SR_MODE_REF_TREE))) return rc;
+        if ((rc = lft ? ensure_light_field_tris(s, stream) : ensure_light_field(s, stream))) return rc;
         sr::BakeLaunch B{};
+        B.tris = lft;
         B.sc = dev_scene(s);
         B.fc = fc;
         B.mode = f->trace_mode;
         B.points = (const double*)s->d_lf_points.p;
         B.res = s->lf_res;
-        B.cache = (uint32_t*)s->d_lf_cache.p;
+        B.cache = (uint32_t*)(lft ? s->d_lft_cache.p : s->d_lf_cache.p);
         B.first = first; B.count = count;
         B.launch_cells = kBakeLaunchCells;
         B.packet = s->dbg[SR_DBG_KERNEL_SWITCH] == 35;              // (hook 35: the measured-and-rejected packet walk, same table)

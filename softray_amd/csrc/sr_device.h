@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_COUNT = 31 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_COUNT = 35 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -135,6 +135,12 @@ struct PipelineLaunch {
     bool          lf_interp;
     bool          lf_carry;         // the lookup hands base cell (lf_cells) and fractions (lf_fracs) to the apply kernel; false (hook 39): apply computes them again
     double*       lf_fracs;         // device [band samples][4] (lf_carry), else nullptr
+    // triangle light field (sr_set_light_field_triangles): lf_cache / lf_claim are the TRIANGLE table's (0 empty, 1 nothing, t + 2 triangle t) and the
+    // band runs k_lf_lookup, k_lft_fill, k_lft_hit (!lf_fused: and k_lft_trace); counters[0] = the fill list's length, counters[1] = the trace list's
+    bool          lf_tris;
+    const int32_t* lf_handle;       // device [ntris]: the reference tree's node index of every triangle's handle leaf (Triangle.HandleToLeafNode)
+    uint32_t*     lf_trace_list;    // device [band samples]: the samples whose first two stages missed
+    bool          lf_fused;         // k_lft_hit runs the full trace itself (production); false (hook 43): it lists the samples for k_lft_trace, same frame
     // sr_shadow_points (pts_n > 0: launch_pipeline renders no rows): n caller-given surface points in passes of pts_pass (band samples) go through
     // the frame's dynamic shadow stage as a compact queue in `hits`; pts_out is the stage's sample buffer (k_pts_ingest, sr_pipeline.hip)
     int64_t       pts_n, pts_pass;
@@ -200,6 +206,7 @@ struct BakeLaunch {
     uint32_t*   cache;          // device [4 N^4]: the scene's light field
     uint64_t    first, count;   // the range, inside the table
     uint64_t    launch_cells;   // cells per launch (rounded down to whole origin patches, at least one)
+    bool        tris;           // `cache` is the triangle table: k_lft_bake stores triangle index + 2 / 1 (model alone, no shading)
     bool        packet;         // SR_MODE_BVH with one packet walk per wave instead of private per-lane walks (cross-check, A/B measurement)
     bool        walk_stats;     // count what the walks do in stats[5..7] too
     unsigned long long* stats;  // device [8] or nullptr: [4] += canonical rays traced, [5..7] += the walks' counters

@@ -144,6 +144,7 @@ struct RefBuilder {
         n.b = (int32_t)geom.size();
         n.box = (int32_t)t.leaf_boxes.size();
         t.leaf_tris.insert(t.leaf_tris.end(), geom.begin(), geom.end());
+        for (int32_t g : geom) t.handle_leaf[(size_t)g] = idx;             // ProcessLeafNode: the last leaf to list a triangle keeps its handle
         LeafBox lb = {{mn.x - eps, mn.y - eps, mn.z - eps}, {mx.x + eps, mx.y + eps, mx.z + eps}};
         t.leaf_boxes.push_back(lb);
         t.num_leaf_nodes++;
@@ -209,6 +210,7 @@ bool build_ref_tree(const std::vector<double>& v9, const double bmin[3], const d
         for (int a = 0; a < 3; ++a)
             if (!(bmin[a] - eps < p[a] && p[a] < bmax[a] + eps)) return false;
     }
+    out.handle_leaf.assign(n, -1);
     RefBuilder rb{v9, max_depth, max_per_leaf, out};
     std::vector<int32_t> all(n);
     for (size_t i = 0; i < n; ++i) all[i] = (int32_t)i;

@@ -40,6 +40,9 @@ struct RefTree {
     std::vector<RefNode> nodes;        // nodes[0] = root
     std::vector<LeafBox> leaf_boxes;
     std::vector<int32_t> leaf_tris;    // triangle indices, list order of the reference preserved
+    // Triangle.HandleToLeafNode per triangle: the node index of the leaf that listed it LAST (ProcessLeafNode, SpatialSubdivision.cs:235-243;
+    // nodes are numbered in creation order, normal side first, so that is the leaf with the highest index whose list holds the triangle)
+    std::vector<int32_t> handle_leaf;
     int32_t tree_depth = 0, num_nodes = 0, num_leaf_nodes = 0;
     int32_t max_stack = 1;             // deepest leaf level = traversal stack bound
     bool built = false;

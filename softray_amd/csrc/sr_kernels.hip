@@ -158,6 +158,10 @@ const char* kernel_name(int id) {
         case K_LF_LOOKUP: return "k_lf_lookup";
         case K_LF_FILL: return "k_lf_fill";
         case K_LF_APPLY: return "k_lf_apply";
+        case K_LFT_FILL: return "k_lft_fill";
+        case K_LFT_HIT: return "k_lft_hit";
+        case K_LFT_TRACE: return "k_lft_trace";
+        case K_LFT_BAKE: return "k_lft_bake";
         case K_LF_BAKE: return "k_lf_bake";
         case K_LFI_LOOKUP: return "k_lfi_lookup";             // sr_set_light_field_interpolation
         case K_LFI_APPLY: return "k_lfi_apply";

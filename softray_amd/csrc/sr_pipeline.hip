@@ -4302,6 +4302,225 @@ __global__ __launch_bounds__(256) void k_lf_bake(DevScene sc, FrameConst fc, con
 }
 
 // --------------------------------------------------------------------------------------------------
+// rayTraceLightField with LightFieldStoresTriangles = true (sr_set_light_field_triangles; LightFieldTriMethod.cs:82-231, LightField4D.cs:175-206,
+// 253-273, 304-344, SpatialSubdivision.cs:235-243, 428-452, 629-676, Triangle.cs:83-104): the table names, per cell, the TRIANGLE the cell's
+// canonical ray hits in the model alone -- entry 0 empty, 1 nothing, t + 2 triangle t -- so it depends on nothing but the model.  A camera
+// sample (ray = start, dir in model space, never clipped, no rayFrac offset) takes its cell's entry e and
+//   stage 1   Triangle.IntersectRay on triangle e - 2 alone: a hit is the result, even where another triangle is nearer (the reference's artefact)
+//   stage 2   IntersectRayWithLeafNode on the triangle's handle leaf (the leaf of the reference tree that listed it last): the leaf's triangles
+//             in the leaf's order, nearest hit with strict < whose position lies in the leaf's box (1e-10 slack)
+//   stage 3   the full trace of the model in the frame's trace mode; its answer, hit or miss, is the result
+// and is shaded like any sample.  A line that misses the sphere and e = 1 are the background.  Per row band:
+//   k_lf_lookup   unchanged, with the triangle table as its cache: cells per sample, claim bits, fill list
+//   k_lft_fill    lane = listed cell: canonical ray through the model alone, store t + 2 or 1, clear the claim bit
+//   k_lft_hit     lane = sample: stages 1 and 2, then (FUSED, production) stage 3 with the private per-lane walk of k_lf_fill; shade and write
+// !FUSED (SR_DBG_KERNEL_SWITCH 43, the first form): the samples that need stage 3 go to a compact list (one atomicAdd per wave) and
+//   k_lft_trace   lane = listed sample: the same walk, shade and write; reads the list's length itself
+// The same frame and statistics either way; the split form was measured slower (1 M triangles, 4096^2: 30.6 against 30.1 ms on the own BVH, 805 against
+// 573 ms on the reference tree -- k_lft_trace holds 157 to 177 registers and its waves have nothing else to overlap their walks with).
+// An entry that names no triangle of the model (only sr_set_light_field_tris can store one) reads as "nothing".
+// Statistics: [1] += one test per sample with e >= 2, the leaf's triangle count per stage 2, the walks' tests of stage 3; [2], [3] += one node
+// and one leaf per stage 2 and the walks' of stage 3; CENSUS: [20] samples without a candidate, [21] / [22] resolved by stage 1 / 2, [23] reached stage 3
+// --------------------------------------------------------------------------------------------------
+constexpr uint32_t kLftNothing = 1u;
+
+// the camera ray of sample `id` of the band (the order of the sample buffer, as k_lf_lookup)
+__device__ __forceinline__ void lft_sample_ray(const FrameConst& fc, const int32_t* __restrict__ row_map, int row_begin, uint32_t id, D3& ss, D3& dw) {
+    const uint32_t n2 = (uint32_t)(fc.sub_pixel_res * fc.sub_pixel_res);
+    const uint32_t pix = id / n2, si = id - pix * n2;
+    const uint32_t brow = pix / (uint32_t)fc.width, col = pix - brow * (uint32_t)fc.width;
+    lf_camera_ray(fc, (int)col, row_map[row_begin + (int)brow], (int)si, ss, dw);
+}
+
+// sample `id` of the band gets its colour (k_lf_apply's addressing: one sample per pixel writes the frame itself)
+__device__ __forceinline__ void lft_write_sample(const FrameConst& fc, const int32_t* __restrict__ row_map, int row_begin, uint32_t id, uint32_t* __restrict__ samples, uint32_t color) {
+    if (fc.sub_pixel_res == 1) {
+        const uint32_t brow = id / (uint32_t)fc.width, col = id - brow * (uint32_t)fc.width;
+        samples[(size_t)row_map[row_begin + (int)brow] * fc.width + col] = color;
+    } else {
+        samples[id] = color;
+    }
+}
+
+// (LDS: the per-lane traversal stacks of root_intersect, as k_lf_fill)
+template <int MODE, bool STATS>
+__global__ __launch_bounds__(256) void k_lft_fill(DevScene sc, const double* __restrict__ points, int N, const uint32_t* __restrict__ list,
+                                                  const unsigned int* __restrict__ list_count, uint32_t* __restrict__ table, uint32_t* __restrict__ claim,
+                                                  unsigned long long* stats) {
+    const int tid = threadIdx.x;
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    const unsigned int total = *list_count, stride = gridDim.x * 256u;
+    const uint32_t n = (uint32_t)N;
+    Ctr sec = {0, 0, 0, 0};
+    for (unsigned int r = blockIdx.x * 256u + tid; r < total; r += stride) {
+        const uint32_t cell = list[r];
+        const uint32_t t = cell % n, s = (cell / n) % (2u * n), v = (cell / (2u * n * n)) % n, u = cell / (2u * n * n * n);
+        const double* a = points + (size_t)(u * n + v) * 3, * b = points + (size_t)(s * n + t) * 3;
+        const D3 start = mk(a[0], a[1], a[2]);
+        const D3 d = mk(b[0] - a[0], b[1] - a[1], b[2] - a[2]);           // dir = P(s, t) - P(u, v), not normalised
+        const double chk = (start.x + start.y + start.z) + (d.x + d.y + d.z);
+        uint32_t e = kLftNothing;
+        if (chk == chk) {                                                    // (N = 1: the patch centres are NaN and nothing is hit)
+            Hit h;
+            sec.rays++;
+            if (root_intersect<MODE, false, false>(sc, sc.tris, sc.extra, st, start, d, h, sec)) e = (uint32_t)h.tri + 2u;
+        }
+        table[cell] = e;
+        atomicAnd(&claim[cell >> 5], ~(1u << (cell & 31u)));
+    }
+    if (STATS) {
+        uint32_t a = wave_sum(sec.rays), b = wave_sum(sec.geom), c2 = wave_sum(sec.nodes), d2 = wave_sum(sec.leaves);
+        if ((tid & 63) == 0) { stat_add(&stats[4], a); stat_add(&stats[5], b); stat_add(&stats[6], c2); stat_add(&stats[7], d2); }
+    }
+}
+
+// stages 1 and 2 for one sample; returns the stage that resolved it (1, 2), 3 when both missed, 0 without a candidate triangle.
+// `handle`: the reference tree's node index of every triangle's handle leaf
+__device__ __forceinline__ int lft_stages(const DevScene& sc, const int32_t* __restrict__ handle, uint32_t e, D3 ss, D3 dw, Hit& h, Ctr& c) {
+    if (e < 2u || e - 2u >= (uint32_t)sc.ntris) return 0;
+    const Rec128* r = &sc.tris[e - 2u];
+    double t; D3 pos;
+    c.geom++;
+    if (tri_hit(r->p, ss, dw, t, pos)) {
+        h.t = t; h.pos = pos; h.nrm = mk(r->p[0], r->p[1], r->p[2]); h.color = r->color; h.tri = r->aux;
+        return 1;
+    }
+    const RefNode nd = sc.rnodes[handle[e - 2u]];                            // a leaf: a = first entry of its list, b = count (ref_tree_intersect's leaf branch)
+    c.nodes++; c.leaves++;
+    const LeafBox* lb = &sc.rboxes[nd.box];
+    double best = DBL_MAX;
+    int32_t bestTri = -1;
+    D3 bestPos = mk(0, 0, 0);
+    for (int k = 0; k < nd.b; ++k) {
+        const int32_t ti = sc.rleaf[nd.a + k];
+        if (tri_hit(sc.tris[ti].p, ss, dw, t, pos) && t < best) {
+            if (inside(lb->lo, lb->hi, pos)) { best = t; bestTri = ti; bestPos = pos; }
+        }
+        c.geom++;
+    }
+    if (bestTri < 0) return 3;
+    r = &sc.tris[bestTri];
+    h.t = best; h.pos = bestPos; h.nrm = mk(r->p[0], r->p[1], r->p[2]); h.color = r->color; h.tri = r->aux;
+    return 2;
+}
+
+// grid: one lane per sample of the band, as k_lf_lookup.  (LDS: FUSED only -- the per-lane stacks of the full trace)
+template <int MODE, bool STATS, bool FUSED>
+__global__ __launch_bounds__(256) void k_lft_hit(DevScene sc, FrameConst fc, const int32_t* __restrict__ row_map, int row_begin, uint32_t nsamples,
+                                                 const uint32_t* __restrict__ cells, const uint32_t* __restrict__ table, const int32_t* __restrict__ handle,
+                                                 uint32_t* __restrict__ samples, uint32_t* __restrict__ trace_list, unsigned int* __restrict__ trace_count,
+                                                 unsigned long long* stats, int census) {
+    const int tid = threadIdx.x;
+    const uint32_t id = blockIdx.x * 256u + (uint32_t)tid;
+    const bool live = id < nsamples;
+    Ctr c = {0, 0, 0, 0};
+    int stage = 0;
+    bool ok = false;
+    Hit h;
+    D3 ss = mk(0, 0, 0), dw = mk(0, 0, 0);
+    if (live) {
+        const uint32_t cell = cells[id];
+        const uint32_t e = cell == kLfMiss ? kLftNothing : table[cell];
+        if (e >= 2u) {
+            lft_sample_ray(fc, row_map, row_begin, id, ss, dw);
+            stage = lft_stages(sc, handle, e, ss, dw, h, c);
+            ok = stage == 1 || stage == 2;
+        }
+    }
+    const bool deferred = stage == 3;
+    if (FUSED) {
+        if (deferred) {
+            Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+            ok = root_intersect<MODE, false, false>(sc, sc.tris, sc.extra, st, ss, dw, h, c);
+        }
+    } else {
+        const unsigned int slot = lf_queue_slot(deferred, trace_count);     // (every lane of the wave is here)
+        if (deferred) trace_list[slot] = id;
+    }
+    if (live && (FUSED || !deferred)) {
+        uint32_t color = fc.background;
+        if (ok) color = (fc.flags & 1u) ? shade(fc, h.pos, h.nrm, h.color) : h.color;
+        lft_write_sample(fc, row_map, row_begin, id, samples, color);
+    }
+    if (STATS) {
+        uint32_t g = wave_sum(c.geom), nd = wave_sum(c.nodes), lv = wave_sum(c.leaves);
+        if ((tid & 63) == 0) { stat_add(&stats[1], g); stat_add(&stats[2], nd); stat_add(&stats[3], lv); }
+        if (census) {
+            const uint32_t s0 = (uint32_t)__popcll(__ballot(live && stage == 0)), s1 = (uint32_t)__popcll(__ballot(stage == 1));
+            const uint32_t s2 = (uint32_t)__popcll(__ballot(stage == 2)), s3 = (uint32_t)__popcll(__ballot(deferred));
+            if ((tid & 63) == 0) { stat_add(&stats[20], s0); stat_add(&stats[21], s1); stat_add(&stats[22], s2); stat_add(&stats[23], s3); }
+        }
+    }
+}
+
+// stage 3 of the listed samples.  (LDS: the per-lane traversal stacks, as k_lf_fill)
+template <int MODE, bool STATS>
+__global__ __launch_bounds__(256) void k_lft_trace(DevScene sc, FrameConst fc, const int32_t* __restrict__ row_map, int row_begin,
+                                                   const uint32_t* __restrict__ trace_list, const unsigned int* __restrict__ trace_count,
+                                                   uint32_t* __restrict__ samples, unsigned long long* stats) {
+    const int tid = threadIdx.x;
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    const unsigned int total = *trace_count, stride = gridDim.x * 256u;
+    Ctr c = {0, 0, 0, 0};
+    for (unsigned int r = blockIdx.x * 256u + tid; r < total; r += stride) {
+        const uint32_t id = trace_list[r];
+        D3 ss, dw;
+        lft_sample_ray(fc, row_map, row_begin, id, ss, dw);
+        Hit h;
+        uint32_t color = fc.background;
+        if (root_intersect<MODE, false, false>(sc, sc.tris, sc.extra, st, ss, dw, h, c)) color = (fc.flags & 1u) ? shade(fc, h.pos, h.nrm, h.color) : h.color;
+        lft_write_sample(fc, row_map, row_begin, id, samples, color);
+    }
+    if (STATS) {
+        uint32_t g = wave_sum(c.geom), nd = wave_sum(c.nodes), lv = wave_sum(c.leaves);
+        if ((tid & 63) == 0) { stat_add(&stats[1], g); stat_add(&stats[2], nd); stat_add(&stats[3], lv); }
+    }
+}
+
+// the dense fill of the triangle table (sr_bake_light_field with the switch on): k_lf_bake's work items and tile order -- one wave = one origin
+// patch x an 8x8 tile of target patches, eight runs of eight consecutive entries (32 bytes) per wave, no claim bits -- with the private
+// per-lane walk through the model alone; non-zero entries are kept.  (LDS: the per-lane stacks)
+template <int MODE, bool STATS>
+__global__ __launch_bounds__(256) void k_lft_bake(DevScene sc, const double* __restrict__ points, int N, uint32_t item_first, uint32_t item_count,
+                                                  uint32_t lo, uint32_t hi, uint32_t* __restrict__ table, unsigned long long* stats, unsigned long long* filled) {
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const uint32_t local = blockIdx.x * 4u + (uint32_t)wave;
+    if (local >= item_count) return;                                         // (whole waves: nothing below synchronises the workgroup)
+    const uint32_t item = item_first + local;
+    const uint32_t n = (uint32_t)N, tiles_t = (n + 7u) / 8u, tiles = ((2u * n + 7u) / 8u) * tiles_t;
+    const uint32_t origin = item / tiles, tile = item - origin * tiles;       // origin = u * N + v: the row of `points`
+    const uint32_t s = (tile / tiles_t) * 8u + ((uint32_t)lane >> 3), t = (tile % tiles_t) * 8u + ((uint32_t)lane & 7u);
+    const bool inside_table = s < 2u * n && t < n;
+    const uint32_t cell = origin * (2u * n * n) + s * n + t;                 // < 4 N^4 <= 2^30 for a target inside the table
+    const bool active = inside_table && cell >= lo && cell < hi && table[cell] == 0u;
+    const unsigned long long am = __ballot(active);
+    if (am == 0ull) return;
+    const double* a = points + (size_t)origin * 3, * b = active ? points + (size_t)(s * n + t) * 3 : a;
+    const D3 start = mk(a[0], a[1], a[2]);
+    const D3 d = mk(b[0] - a[0], b[1] - a[1], b[2] - a[2]);               // dir = P(s, t) - P(u, v), not normalised
+    const double chk = (start.x + start.y + start.z) + (d.x + d.y + d.z);
+    const bool traced = active && chk == chk;                                // (N = 1: the patch centres are NaN and nothing is traced)
+    Ctr sec = {0, 0, 0, 0};
+    uint32_t e = kLftNothing;
+    if (traced) {
+        Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+        Hit h;
+        if (root_intersect<MODE, false, false>(sc, sc.tris, sc.extra, st, start, d, h, sec)) e = (uint32_t)h.tri + 2u;
+    }
+    if (active) table[cell] = e;
+    if (lane == 0) atomicAdd(filled, (unsigned long long)__popcll(am));
+    if (stats) {
+        const uint32_t r = (uint32_t)__popcll(__ballot(traced));
+        if (lane == 0) stat_add(&stats[4], r);
+        if (STATS) {
+            uint32_t g = wave_sum(sec.geom), c2 = wave_sum(sec.nodes), d2 = wave_sum(sec.leaves);
+            if (lane == 0) { stat_add(&stats[5], g); stat_add(&stats[6], c2); stat_add(&stats[7], d2); }
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_pts_ingest (sr_shadow_points): the front door of the dynamic shadow stage for caller-given surface points.  One lane per point of a
 // pass: out[i] = the point's colour (0xFFFFFFFF without a colour array; `out` may be the colour array itself, so neither is __restrict__),
 // and recs[i] = the point -- position and normal as given -- with sample = i, its index in the pass's part of `out`, which is the stage's
@@ -5163,6 +5382,62 @@ static hipError_t launch_lightfield_t(const PipelineLaunch& L, int row_begin, in
     return hipSuccess;
 }
 
+// the band of a triangle light-field frame (L.lf_tris; see k_lft_fill): lookup, fill, the three stages in k_lft_hit (!L.lf_fused: stage 3 in
+// k_lft_trace) -- back to back on the stream, nothing waits for the device.  counters[0] = the fill list's length, counters[1] = the trace list's.  MODE: SR_MODE_REF_TREE or SR_MODE_BVH (sr_api.cpp
+// refuses SR_MODE_BRUTE)
+template <int MODE>
+static hipError_t launch_lft_t(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples) {
+    const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
+    const uint32_t nsamples = (uint32_t)((long long)row_count * L.fc.width * n2);
+    const unsigned blocks = (nsamples + 255u) / 256u;
+    unsigned int* list_count = L.counters, * trace_count = L.counters + 1;
+    hipError_t e;
+    hipEvent_t e0, e1;
+    if ((e = hipMemsetAsync(L.counters, 0, 2 * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
+    pipe_events(L, K_LF_LOOKUP, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_lf_lookup, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, L.lf_entries, (const uint32_t*)L.lf_cache, L.lf_claim,
+                       L.lf_cells, L.lf_list, list_count, L.stats);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    const unsigned wblocks = (unsigned)std::min<long long>(((long long)nsamples + 255) / 256, (long long)L.persistent_blocks);
+    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+    unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
+    pipe_events(L, K_LFT_FILL, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    {
+        const auto fill = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)list_count, L.lf_cache, L.lf_claim, sec_stats);
+        };
+        if (sec_stats) fill(k_lft_fill<MODE, true>); else fill(k_lft_fill<MODE, false>);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    pipe_events(L, K_LFT_HIT, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    {
+        const auto hit = [&](auto kern, size_t kernel_lds) {
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), kernel_lds, L.stream, L.sc, L.fc, L.row_map, row_begin, nsamples, (const uint32_t*)L.lf_cells, (const uint32_t*)L.lf_cache,
+                               L.lf_handle, samples, L.lf_trace_list, trace_count, L.stats, sec_stats ? 1 : 0);
+        };
+        if (L.lf_fused) { if (L.stats) hit(k_lft_hit<MODE, true, true>, lds); else hit(k_lft_hit<MODE, false, true>, lds); }
+        else { if (L.stats) hit(k_lft_hit<MODE, true, false>, 0); else hit(k_lft_hit<MODE, false, false>, 0); }
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    if (!L.lf_fused) {
+        pipe_events(L, K_LFT_TRACE, e0, e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        const auto trace = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.row_map, row_begin, (const uint32_t*)L.lf_trace_list, (const unsigned int*)trace_count, samples, L.stats);
+        };
+        if (L.stats) trace(k_lft_trace<MODE, true>); else trace(k_lft_trace<MODE, false>);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // sr_bake_light_field with shadows (PipelineLaunch::lf_bake_count > 0): entries [first, first + count) in passes of at most
 // L.lf_bake_pass_cells cells (whole origin patches; at least one) -- what the pass's queue, staging buffer and the shadow stage's lists are
 // sized for.  Per pass: counters reset, k_lf_bake<SHADOW>, the shadow stage, k_lf_store; back to back on the stream, the host never waits
@@ -5276,8 +5551,34 @@ static hipError_t launch_lf_bake_t(const BakeLaunch& L) {
     return hipSuccess;
 }
 
+// ... of the triangle table (BakeLaunch::tris): the same launches of k_lft_bake
+template <int MODE>
+static hipError_t launch_lft_bake_t(const BakeLaunch& L) {
+    const uint64_t n = (uint64_t)L.res, per_origin = 2 * n * n, tiles = ((2 * n + 7) / 8) * ((n + 7) / 8);
+    const uint64_t o_first = L.first / per_origin, o_last = (L.first + L.count - 1) / per_origin;
+    const uint64_t step = std::max<uint64_t>(1, L.launch_cells / per_origin);
+    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+    hipError_t e;
+    for (uint64_t o = o_first; o <= o_last; o += step) {
+        const uint64_t origins = std::min(step, o_last - o + 1);
+        const uint32_t item_first = (uint32_t)(o * tiles), item_count = (uint32_t)(origins * tiles);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_LFT_BAKE, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        const auto bake = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((item_count + 3u) / 4u), dim3(256), lds, L.stream, L.sc, L.points, L.res, item_first, item_count, (uint32_t)L.first,
+                               (uint32_t)(L.first + L.count), L.cache, L.stats, L.filled);
+        };
+        if (L.walk_stats) bake(k_lft_bake<MODE, true>); else bake(k_lft_bake<MODE, false>);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_lf_bake(const BakeLaunch& L) {
     if (L.count == 0) return hipSuccess;
+    if (L.tris) return L.mode == MODE_REF ? launch_lft_bake_t<MODE_REF>(L) : L.mode == MODE_BVH ? launch_lft_bake_t<MODE_BVH>(L) : hipErrorInvalidValue;
     const bool extra = L.sc.nextra > 0;
     switch (L.mode) {
         case MODE_REF: return extra ? launch_lf_bake_t<MODE_REF, true>(L) : launch_lf_bake_t<MODE_REF, false>(L);
@@ -5347,7 +5648,10 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
         if (L.fc.flags & kFlagLightField) {
             // no camera ray touches geometry: the band is lookup, fill, apply (sr_api.cpp: never with AO, path tracing or mirror bounces; dynamic shadows
             // when the scene's switch allows them: the shadow stage then runs on the fill's hits)
-            if ((e = launch_lightfield_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
+            // (the triangle table, sr_set_light_field_triangles: the extra geometry plays no part, and sr_api.cpp refuses the brute-force mode)
+            if (L.lf_tris) e = MODE == MODE_BRUTE ? hipErrorInvalidValue : launch_lft_t<MODE == MODE_BRUTE ? MODE_REF : MODE>(L, row_begin, row_count, samples);
+            else e = launch_lightfield_t<MODE, EXTRA>(L, row_begin, row_count, samples);
+            if (e != hipSuccess) return e;
             if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
             if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);
             continue;

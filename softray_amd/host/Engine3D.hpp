@@ -219,7 +219,14 @@ public:
         if (value != lightFieldHasTris_) ResetLightField();
         lightFieldHasTris_ = value;
     }
-    void ResetLightField() { sr_check(sr_reset_light_field(scene_)); }           // what a new Renderer's LightFieldColorMethod starts with
+    // library opt-in (sr_set_light_field_triangles): LightFieldStoresTriangles = true runs LightFieldTriMethod on the library's triangle table
+    // instead of being refused.  Off (the default): Render() and BakeLightField() refuse LightFieldStoresTriangles = true, as they always did
+    bool LightFieldTriangles() const { return lightFieldTris_; }
+    void LightFieldTriangles(bool value) { lightFieldTris_ = value; }
+    // ranges of the triangle table (4 N^4 uint32: 0 empty, 1 nothing, t + 2 triangle t), as sr_get_light_field_tris / sr_set_light_field_tris
+    void GetLightFieldTris(uint32_t* out, uint64_t first, uint64_t count) { sr_check(sr_get_light_field_tris(scene_, out, first, count)); }
+    void SetLightFieldTris(const uint32_t* in, uint64_t first, uint64_t count) { sr_check(sr_set_light_field_tris(scene_, in, first, count)); }
+    void ResetLightField() { sr_check(sr_reset_light_field(scene_)); }           // what a new Renderer's light-field method starts with (both tables)
     int LightFieldResolution() const { return (int)sr_get_light_field_res(scene_); }   // lightFieldRes (Renderer.cs:93): 64
     void LightFieldResolution(int n) { sr_check(sr_set_light_field_res(scene_, n)); }
     // library opt-in (sr_set_light_field_shadows): rayTraceLightField together with DYNAMIC rayTraceShadows -- LightFieldColorMethod is the
@@ -297,6 +304,8 @@ public:
         if (rayTraceVoxels) want = 0u;                     // a voxel frame walks the grid the library makes from the triangles (SR_F_VOXELS)
         if (mode == SR_MODE_REF_TREE && rayTraceShadows && !rayTraceShadowsStatic && !model_->argb.empty())
             want |= 1u << SR_MODE_BVH;                     // a tree frame's shadow rays take the BVH's shaft path
+        if (rayTraceLightField && lightFieldHasTris_ && lightFieldTris_ && !rayTraceVoxels)
+            want |= 1u << SR_MODE_REF_TREE;                // LightFieldTriMethod's second stage reads the reference tree whatever walks the full rays
         if (want & ~built_) {
             sr_check(sr_build(scene_, want & ~built_, 0, 0));  // SpatialSubdivision defaults 15 / 25
             built_ |= want;
@@ -386,7 +395,7 @@ public:
                   (rayTraceAmbientOcclusion ? SR_F_AMBIENT_OCCLUSION : 0u) |                       // Renderer.cs:1631-1638; reads random_seed, concurrency
                   (rayTraceAmbientOcclusion && !ambientOcclusionEnableCache ? SR_F_AO_UNCACHED : 0u) |
                   (rayTraceVoxels ? SR_F_VOXELS : 0u) |                                            // Renderer.cs:1568-1588: the grid replaces tree and extra geometry
-                  (rayTraceLightField && !lightFieldHasTris_ ? SR_F_LIGHT_FIELD : 0u) |            // Renderer.cs:1640-1649: LightFieldColorMethod
+                  (rayTraceLightField && (!lightFieldHasTris_ || lightFieldTris_) ? SR_F_LIGHT_FIELD : 0u) |   // Renderer.cs:1590-1611, 1640-1649: the colour or (opt-in) the triangle method
                   (pointLighting ? SR_F_POINT_LIGHT : 0u) | (specularLighting ? SR_F_SPECULAR : 0u) |
                   SR_F_PRIMARY_STATS_ONLY;                 // Num* count primary rays (Renderer.cs:1916-1923)
         f.random_seed = rayTraceRandomSeed;
@@ -423,11 +432,16 @@ private:
         if (antiAliasResolution_ < 2) return;
         sr_check(sr_anti_alias(scene_, pixels_, aaWidth_, aaHeight_, antiAliasResolution_, aaPixels_));
     }
+    // what the library refuses, by name; then the scene's switch follows LightFieldStoresTriangles (only with the opt-in can it be on)
     void CheckLightField() const {
-        if (lightFieldHasTris_)
-            throw std::logic_error("rayTraceLightField with LightFieldStoresTriangles = true (LightFieldTriMethod) is out of scope: set it to false (SR_F_LIGHT_FIELD)");
-        if (rayTraceShadows && !(LightFieldShadows() && !rayTraceShadowsStatic))      // (dynamic shadows only, and only with the opt-in)
+        if (lightFieldHasTris_ && !lightFieldTris_)
+            throw std::logic_error("rayTraceLightField with LightFieldStoresTriangles = true (LightFieldTriMethod) is out of scope: set it to false (SR_F_LIGHT_FIELD), "
+                                   "or opt in with LightFieldTriangles(true) (sr_set_light_field_triangles)");
+        if (rayTraceShadows && (lightFieldHasTris_ || !(LightFieldShadows() && !rayTraceShadowsStatic)))      // (dynamic shadows only, only with the opt-in, never through LightFieldTriMethod)
             throw std::logic_error("rayTraceLightField together with rayTraceShadows is out of scope (SR_F_LIGHT_FIELD)");
+        if (lightFieldHasTris_ && !rayTraceSubdivision)
+            throw std::logic_error("rayTraceLightField with LightFieldStoresTriangles = true needs rayTraceSubdivision (LightFieldTriMethod reads the SpatialSubdivision)");
+        sr_check(sr_set_light_field_triangles(scene_, lightFieldHasTris_ ? 1 : 0));
         if (rayTraceAmbientOcclusion) throw std::logic_error("rayTraceLightField together with rayTraceAmbientOcclusion is out of scope (SR_F_LIGHT_FIELD)");
         if (rayTracePathTracing) throw std::logic_error("rayTraceLightField together with rayTracePathTracing is out of scope (SR_F_LIGHT_FIELD)");
         if (rayTraceVoxels) throw std::logic_error("rayTraceLightField together with rayTraceVoxels is out of scope (SR_F_LIGHT_FIELD)");
@@ -478,6 +492,7 @@ private:
     sr_scene* scene_ = nullptr;
     uint32_t backgroundColor_ = 0;
     bool lightFieldHasTris_ = true;                        // Renderer.cs:446
+    bool lightFieldTris_ = false;                          // LightFieldTriangles(): the library's triangle light field may run
     double fieldOfViewDepth_ = 0;
     int width_ = 1, height_ = 1;
     int32_t* pixels_ = nullptr;

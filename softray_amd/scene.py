@@ -140,6 +140,16 @@ class GpuScene:
         _check(_lib.lib().sr_tree_stats(self._h, _p(out)))
         return tuple(int(x) for x in out)
 
+    def tree_handle_leaf(self, tri):
+        """(box float64 [6] = lo x 3, hi x 3 with the containment test's 1e-10 slack, members int32 [k] in the leaf's order) of the reference tree's
+        leaf that listed triangle `tri` last: what the second stage of the triangle light field searches (sr_tree_handle_leaf)."""
+        box = np.zeros(6)
+        n = int(_lib.lib().sr_tree_handle_leaf(self._h, int(tri), _p(box), None, 0))
+        _check(min(n, 0))
+        members = np.zeros(n, dtype=np.int32)
+        _check(min(int(_lib.lib().sr_tree_handle_leaf(self._h, int(tri), _p(box), _p(members), n)), 0))
+        return box, members
+
     def bvh_stats(self):
         """(depth, inner nodes, triangles, built on device) of the library's own BVH."""
         out = np.zeros(4, dtype=np.int64)
@@ -271,6 +281,29 @@ class GpuScene:
     def light_field_interpolation(self, on):
         _check(_lib.lib().sr_set_light_field_interpolation(self._h, 1 if on else 0))
 
+    @property
+    def light_field_triangles(self):
+        """Whether SR_F_LIGHT_FIELD frames and bake_light_field run the triangle-index light field (LightFieldStoresTriangles = true) on the triangle
+        table instead of the colour light field on the colour table (sr_set_light_field_triangles)."""
+        return bool(_lib.lib().sr_get_light_field_triangles(self._h))
+
+    @light_field_triangles.setter
+    def light_field_triangles(self, on):
+        _check(_lib.lib().sr_set_light_field_triangles(self._h, 1 if on else 0))
+
+    def get_light_field_tris(self, first=0, count=None):
+        """Entries first .. first + count - 1 (default: all 4 N^4) of the triangle table as uint32: 0 empty, 1 nothing, t + 2 triangle t."""
+        total = 4 * self.light_field_res ** 4
+        if count is None:
+            count = total - first
+        out = np.zeros(int(count), dtype=np.uint32)
+        _check(_lib.lib().sr_get_light_field_tris(self._h, _p(out), int(first), int(count)))
+        return out
+
+    def set_light_field_tris(self, entries, first=0):
+        entries = np.ascontiguousarray(entries, dtype=np.uint32).reshape(-1)
+        _check(_lib.lib().sr_set_light_field_tris(self._h, _p(entries), int(first), int(entries.size)))
+
     def light_field_coords(self, starts, dirs):
         """LightField4D.RayToFloat4D of every line (sr_light_field_coords), computed on the device at light_field_res: (float64 [n, 4], bool [n] --
         False: the line misses the sphere and its coordinates are 0)."""
@@ -329,8 +362,8 @@ class GpuScene:
 
     def kernel_times(self):
         """{kernel: (total ms, launches)} since reset_kernel_times() -- HIP events on the launch stream."""
-        arr = (KernelTime * 32)()
-        n = _lib.lib().sr_kernel_times(self._h, arr, 32)
+        arr = (KernelTime * 64)()
+        n = _lib.lib().sr_kernel_times(self._h, arr, 64)
         return {arr[i].name.decode(): (float(arr[i].ms), int(arr[i].launches)) for i in range(n)}
 
     def shade_points(self, frame, pos, normal, color):

@@ -105,6 +105,10 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_bake_light_field(IntPtr scene, ref SrFrame frame, ulong first, ulong count, out ulong filled);
         [DllImport(Lib)] public static extern int sr_shadow_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, uint options);
         [DllImport(Lib)] public static extern int sr_shadow_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, uint options, IntPtr hipStream, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_shade_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr hipStream);
+        [DllImport(Lib)] public static extern long sr_frame_sample_count(ref SrFrame frame);
+        [DllImport(Lib)] public static extern int sr_render_hits(IntPtr scene, ref SrFrame frame, [Out] double[] starts, [Out] double[] dirs, [Out] byte[] hit, [Out] double[] rayFrac, [Out] double[] pos, [Out] double[] normal, [Out] uint[] color, [Out] int[] triIndex, [Out] ulong[] stats4);
+        [DllImport(Lib)] public static extern int sr_render_hits_device(IntPtr scene, ref SrFrame frame, IntPtr dStarts, IntPtr dDirs, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -417,6 +421,57 @@ namespace Engine3D.Hip
                       1.0, 1.0, 0.0, 0.0, 0.0, lightDirView, lightPosView, 4);
             frame.flags &= ~F_PRIMARY_STATS_ONLY;
             Native.Check(Native.sr_shadow_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, coherent ? POINTS_COHERENT : 0, stream, dStats));
+        }
+
+        /// The frame G-buffer (sr_render_hits): the arrays a caller wants of one frame's primary hits
+        public sealed class FrameHits
+        {
+            public double[] Starts, Dirs;          // [S * 3] camera rays in model space (null unless asked for)
+            public byte[] Hit;                     // [S] 1 hit, 0 miss (zeros and triangle -1)
+            public double[] RayFrac, Pos, Normal;  // [S], [S * 3], [S * 3]
+            public uint[] Color;                   // [S] unshaded surface colour
+            public int[] TriIndex;                 // [S] TriangleIndex, -1 for extra geometry and misses
+            public ulong[] Stats4;                 // primary {rays, tests, nodes, leaves}
+        }
+
+        /// What the primary stage of the frame these arguments describe answers per camera sample, before any decorator (sr_render_hits), in
+        /// scan order ((row - first row) * width + col) * n^2 + subX * n + subY.  The decorator flags are not read; F_VOXELS, F_LIGHT_FIELD and
+        /// F_SINGLE_KERNEL are refused: SR_ERR_UNSUPPORTED -> InvalidOperationException.  Blocks.
+        public FrameHits RenderHits(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode,
+                                    int startRow, int endRow, int subPixelRes, double fieldOfViewDepth, double focalDepth, double focalBlurStrength,
+                                    bool rays = false)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, startRow, endRow, subPixelRes, 0,
+                      fieldOfViewDepth, focalDepth, focalBlurStrength, 0.0, 0.0, new Vector(0, 0, 1), new Vector(0, 0, 0), 4);
+            long s = Native.sr_frame_sample_count(ref frame);
+            var r = new FrameHits { Hit = new byte[s], RayFrac = new double[s], Pos = new double[s * 3], Normal = new double[s * 3],
+                                    Color = new uint[s], TriIndex = new int[s], Stats4 = new ulong[4] };
+            if (rays) { r.Starts = new double[s * 3]; r.Dirs = new double[s * 3]; }
+            Native.Check(Native.sr_render_hits(scene, ref frame, r.Starts, r.Dirs, r.Hit, r.RayFrac, r.Pos, r.Normal, r.Color, r.TriIndex, r.Stats4));
+            return r;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_render_hits_device), IntPtr.Zero for an array that is not wanted;
+        /// enqueued on `stream` without a host synchronisation; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void RenderHitsDevice(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode,
+                                     int startRow, int endRow, int subPixelRes, double fieldOfViewDepth, double focalDepth, double focalBlurStrength,
+                                     IntPtr dStarts, IntPtr dDirs, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex,
+                                     IntPtr stream, IntPtr dStats)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, startRow, endRow, subPixelRes, 0,
+                      fieldOfViewDepth, focalDepth, focalBlurStrength, 0.0, 0.0, new Vector(0, 0, 1), new Vector(0, 0, 0), 4);
+            Native.Check(Native.sr_render_hits_device(scene, ref frame, dStarts, dDirs, dHit, dRayFrac, dPos, dNormal, dColor, dTriIndex, stream, dStats));
+        }
+
+        /// ShadingMethod's colour step for n recorded intersections in DEVICE memory (sr_shade_points_device): dOut[i] = dColor[i] modulated with
+        /// the frame's lighting of (dPos[i], dNormal[i]); enqueued on `stream` without a host synchronisation.
+        public void ShadePointsDevice(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags,
+                                      double fieldOfViewDepth, double ambient, double shininess, Vector lightDirView, Vector lightPosView,
+                                      long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr stream)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, MODE_BVH, 0, height - 1, 1, 0,
+                      fieldOfViewDepth, 1.0, 0.0, ambient, shininess, lightDirView, lightPosView, 4);
+            Native.Check(Native.sr_shade_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, stream));
         }
 
         /// The host half of RaytraceGeometry (Renderer.cs:1510-1528, 1652-1653): copy public fields into sr_frame.

@@ -574,6 +574,44 @@ int  sr_shadow_points_device(sr_scene*, const sr_frame* frame, int64_t n, const 
                              const uint32_t* d_color /* or NULL */, uint32_t* d_out, uint32_t options, void* hip_stream,
                              uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
+/* The same step with every array in DEVICE memory on the scene's device (a multi-device scene: devices[0]), enqueued on `hip_stream` without
+ * a host synchronisation and without the staging copies.  Validation as sr_shade_points; n == 0: SR_OK. */
+int  sr_shade_points_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color,
+                            uint32_t* d_out, void* hip_stream);
+
+/* The frame G-buffer: what the primary stage of a frame answers per camera sample, before any decorator.  Sample i of the frame is
+ * ((row - a) * width + col) * n*n + subX * n + subY, a..b the frame's row range clamped to the surface as sr_render clamps it and
+ * n = sub_pixel_res: the reference's scan order (Renderer.cs:1717-1790).  sr_frame_sample_count is the number S of samples,
+ * rows x width x n^2 (0 for start_row > end_row after clamping or a NULL frame); pure, like sr_frame_pixel_count.  All arrays are SoA
+ * with sr_trace_rays' shapes, [S][3] doubles and [S] scalars.
+ * starts / dirs: the sample's camera ray in model space, exactly what the frame's primary stage traces (the one-sample fast path, the
+ * sub-pixel form, the focal-blur form); the direction is not normalised.  The other arrays: IRayIntersectable.IntersectRay of the frame's root
+ * geometry -- the extra geometry plus the model in trace_mode -- for that ray, with sr_trace_rays' conventions: a miss writes hit 0, zeros and
+ * tri_index -1; a hit on extra geometry has tri_index -1 and the primitive's colour; color is the unshaded surface colour.  Every output
+ * pointer may be NULL and is then neither computed for nor written; all NULL is legal (the call then runs for the statistics).
+ * Read from the frame: the surface, the rows, sub_pixel_res, SR_F_FOCAL_BLUR with its fields, the matrices, position_z, fov_depth and
+ * trace_mode; the library options SR_F_PRIMARY_STATS_ONLY and SR_F_NO_SPLIT are accepted and have no effect.  The decorator switches are
+ * NOT read -- SR_F_SHADING, SR_F_SHADOWS, SR_F_STATIC_SHADOWS, SR_F_AMBIENT_OCCLUSION, SR_F_AO_UNCACHED, SR_F_PATH_TRACING, the lights,
+ * max_bounces -- so a frame about to be passed to sr_render can be passed as it is.
+ * Refused, in this order: a NULL scene or frame: SR_ERR_INVALID_ARG; what replaces the root geometry or the primary stage -- SR_F_VOXELS,
+ * SR_F_LIGHT_FIELD, SR_F_SINGLE_KERNEL, strip_count > 0: SR_ERR_UNSUPPORTED; then sr_render's validation of the frame and its trace mode
+ * (SR_ERR_INVALID_ARG, SR_ERR_NO_MODEL, SR_ERR_NOT_BUILT); then a host-only scene: SR_ERR_NO_DEVICE.  An empty row range that passes the
+ * first three: SR_OK, nothing is touched (like sr_shadow_points' n == 0, before a device is asked for).
+ * The walk is the frame's: in SR_MODE_BVH with a common ray origin the packet walk on the camera-ordered four-wide tree (one traversal per
+ * 8x8-pixel tile, camera-cone records, facing partition), per-lane walks with focal blur, in the other modes and under
+ * SR_DBG_PER_LANE_PRIMARY / SR_DBG_BVH2_PACKETS (binary-tree packets); row bands as a frame's (SR_DBG_BAND_SAMPLES).
+ * Ordered like a frame (behind a frame of the scene in flight on any stream, the next frame behind it); a multi-device scene runs it on
+ * devices[0] and sr_last_frame_parts then reads 1.  The device variant enqueues on `hip_stream` without a host synchronisation; the host
+ * variant stages through the scene's device buffers, blocks and fills sr_last_ray_stats.  Statistics: [0..3] the primary counters as a frame
+ * counts them (SR_MODE_REF_TREE / SR_MODE_BRUTE: those of sr_render of the same frame without decorators; own BVH: what a wave fetched),
+ * [4..] 0. */
+int64_t sr_frame_sample_count(const sr_frame*);
+int  sr_render_hits(sr_scene*, const sr_frame* frame, double* starts, double* dirs, uint8_t* hit, double* ray_frac, double* pos,
+                    double* normal, uint32_t* color, int32_t* tri_index, uint64_t stats[4] /* or NULL */);
+int  sr_render_hits_device(sr_scene*, const sr_frame* frame, double* d_starts, double* d_dirs, uint8_t* d_hit, double* d_ray_frac,
+                           double* d_pos, double* d_normal, uint32_t* d_color, int32_t* d_tri_index, void* hip_stream,
+                           uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* n NextDouble() of new System.Random(seed) after `skip` samples have been drawn (Next() and NextDouble() consume one each):
  * hosts regenerate the reference's seeded test inputs with it (rays that continue the triangle stream, SpatialSubdivisionTests.cs:141,225) */
 void sr_net_random_doubles(int32_t seed, int64_t skip, int64_t n, double* out);

@@ -1,5 +1,5 @@
 """sr_shadow_points_device measured on the GPU, on the unit-cube scene of the benchmark (SR_MODE_BVH, the benchmark's pose and light, 100
-area-light samples): the points are the hit points of the res x res frame, taken with sr_trace_rays_device from its camera rays.
+area-light samples): the points are the hit points of the res x res frame, taken with sr_render_hits_device.
 
     python scripts/gpu_shadow_points.py [--out profiles/shadow_points/points.json]
 
@@ -80,26 +80,16 @@ def measure():
     g.build((sa.MODE_BVH,))
     res = args.res
     fs, fp = frame(res, True), frame(res, False)
-    # the frame's camera rays (Renderer.cs:1718-1723) and their hit points, on the device
-    it = torch.tensor([fs.inv_transform[i] for i in range(12)], dtype=torch.float64, device=dev).reshape(3, 4)
-    cols = torch.arange(res, dtype=torch.float64, device=dev)
-    dv = torch.empty((res, res, 3), dtype=torch.float64, device=dev)
-    dv[:, :, 0] = -(cols / res - 0.5)[None, :]
-    dv[:, :, 1] = (-(cols / res - 0.5) * (res / res))[:, None]
-    dv[:, :, 2] = fs.fov_depth
-    dirs = (dv.reshape(-1, 3) @ it[:, :3].T).contiguous()
-    origin = it[:, :3] @ torch.tensor([0.0, 0.0, -fs.position_z], dtype=torch.float64, device=dev)
-    starts = origin[None, :].expand(dirs.shape[0], 3).contiguous()
-    n_rays = dirs.shape[0]
+    # the frame's own primary hits, on the device (sr_render_hits_device: the library's ray set-up and its packet walk)
+    n_rays = sa.GpuScene.sample_count(fs)
     hit = torch.zeros(n_rays, dtype=torch.uint8, device=dev)
     pos, nrm = torch.zeros((n_rays, 3), dtype=torch.float64, device=dev), torch.zeros((n_rays, 3), dtype=torch.float64, device=dev)
     col = torch.zeros(n_rays, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
-    g.trace_device(sa.MODE_BVH, n_rays, starts.data_ptr(), dirs.data_ptr(), d_hit=hit.data_ptr(), d_pos=pos.data_ptr(), d_normal=nrm.data_ptr(), d_color=col.data_ptr(),
-                   stream=torch.cuda.current_stream().cuda_stream)
+    g.render_hits_device(fs, d_hit=hit.data_ptr(), d_pos=pos.data_ptr(), d_normal=nrm.data_ptr(), d_color=col.data_ptr(),
+                         stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     keep = hit.bool()
-    del starts, dirs, dv
     scan = (pos[keep].contiguous(), nrm[keep].contiguous(), col[keep].contiguous())
     n = scan[0].shape[0]
     del pos, nrm, col, hit

@@ -49,6 +49,7 @@ SYMBOLS = [
     "sr_shadow_points", "sr_shadow_points_device",
     "sr_set_light_field_interpolation", "sr_get_light_field_interpolation", "sr_light_field_coords",
     "sr_set_light_field_triangles", "sr_get_light_field_triangles", "sr_get_light_field_tris", "sr_set_light_field_tris", "sr_tree_handle_leaf",
+    "sr_frame_sample_count", "sr_render_hits", "sr_render_hits_device", "sr_shade_points_device",
 ]
 POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 GATHER_COPY, GATHER_RCCL = 0, 1
@@ -158,6 +159,10 @@ def lib():
     L.sr_device_count.restype = i32; L.sr_device_count.argtypes = [vp]
     L.sr_last_frame_parts.restype = i32; L.sr_last_frame_parts.argtypes = [vp]
     L.sr_shade_points.restype = i32; L.sr_shade_points.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    L.sr_shade_points_device.restype = i32; L.sr_shade_points_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
+    L.sr_frame_sample_count.restype = i64; L.sr_frame_sample_count.argtypes = [vp]
+    L.sr_render_hits.restype = i32; L.sr_render_hits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sr_render_hits_device.restype = i32; L.sr_render_hits_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sr_shadow_points.restype = i32; L.sr_shadow_points.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32]
     L.sr_shadow_points_device.restype = i32; L.sr_shadow_points_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_trace_rays_device.restype = i32; L.sr_trace_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]

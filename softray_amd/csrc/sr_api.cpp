@@ -707,12 +707,15 @@ int ensure_light_field_tris(sr_scene* s, hipStream_t stream) {
 struct LfBakeReq { uint64_t first, count; unsigned long long* filled; };
 // sr_shadow_points: the same set-up for the same reason, then passes of the caller's points through the shadow stage (device arrays)
 struct PtsReq { int64_t n; const double* pos; const double* nrm; const uint32_t* color; uint32_t* out; bool coherent; };
+// sr_render_hits: the frame's own set-up of the primary stage (camera cones, ordered node copy, facing partition, row bands), then k_hits
+// per band into the caller's device arrays instead of the frame's kernels.  The caller has cleared the decorator switches of `f`
+struct HitsReq { sr::HitsOut out; };
 
 // points per pass of sr_shadow_points: the bake's rule (SR_DBG_BAND_SAMPLES shrinks the pass)
 const long long kPtsPassPoints = 1ll << 22;
 
 int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0, const LfBakeReq* bake = nullptr,
-                  const PtsReq* pts = nullptr) {
+                  const PtsReq* pts = nullptr, const HitsReq* hreq = nullptr) {
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
@@ -1188,7 +1191,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
                 if (r > 0) SR_HIP(B.rstate[r].reserve((size_t)round_items[r] * sr::pipeline_round_state_bytes()));
             }
         }
-        if (n2 > 1 && !bake) SR_HIP(B.samples.reserve((size_t)(lf ? lf_band_samples : band_samples) * 4));
+        if (n2 > 1 && !bake && !hreq) SR_HIP(B.samples.reserve((size_t)(lf ? lf_band_samples : band_samples) * 4));
         bool accum_fresh = false;
         if (chunked_shadows) {
             // indexed like the sample buffer: the frame (or the compact strips) for one sample per pixel, band-local otherwise (a light field's
@@ -1263,6 +1266,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
                 P.pts_escape_hi[a] = std::max(s->vmax[a], s->root.max[a]) + 0.002;
             }
         }
+        if (hreq) { P.hits_req = true; P.hits_out = hreq->out; }
         s->ao_table_seed = f->random_seed;
         s->ao_table_rc = SR_OK;
         P.ao_table = !ao ? nullptr : [](void* user, unsigned long long generators) -> const int32_t* {
@@ -2920,6 +2924,96 @@ int sr_shade_points(sr_scene* s, const sr_frame* f, int64_t n, const double* pos
     SR_HIP(sr::launch_shade_points(fc, n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, (const uint32_t*)s->d_io[2].p, (uint32_t*)s->d_io[3].p, nullptr));
     SR_HIP(hipStreamSynchronize(nullptr));
     SR_HIP(hipMemcpy(out, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_shade_points_device(sr_scene* s, const sr_frame* f, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color, uint32_t* d_out,
+                           void* hip_stream) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || n < 0 || (n > 0 && (!d_pos || !d_normal || !d_color || !d_out))) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_shade_points_device");
+    int rc = validate_frame(f, s);
+    if (rc) return rc;
+    if ((rc = use_device(s))) return rc;
+    if (n == 0) return SR_OK;
+    sr::FrameConst fc;
+    if ((rc = prepare_frame(s, f, fc))) return rc;
+    SR_HIP(sr::launch_shade_points(fc, n, d_pos, d_normal, d_color, d_out, (hipStream_t)hip_stream));
+    return SR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The frame G-buffer (sr_render_hits): the primary stage's answer per camera sample
+// ------------------------------------------------------------------------------------------------------------------
+int64_t sr_frame_sample_count(const sr_frame* f) {
+    if (!f || f->width <= 0 || f->height <= 0 || f->sub_pixel_res < 1) return 0;
+    int a, b;
+    clamp_rows(f, a, b);
+    if (b < a) return 0;
+    return (int64_t)(b - a + 1) * f->width * f->sub_pixel_res * f->sub_pixel_res;
+}
+
+// what sr_render_hits[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the first
+// part of a multi-device scene), `fs`: the frame without the decorator switches, which the call does not read
+static int render_hits_check(sr_scene*& s, const sr_frame* f, sr_frame& fs) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !f) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_render_hits");
+    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_render_hits: voxel rendering (SR_F_VOXELS) replaces the root geometry; a voxel hit has no position or triangle");
+    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_render_hits: the light field (SR_F_LIGHT_FIELD) replaces the primary stage: a cell stores a colour, not a hit");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_render_hits: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no primary stage to read");
+    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_render_hits: row strips (strip_count > 0) lay the rows out compactly; pass a row range");
+    fs = *f;
+    fs.flags &= (uint32_t)(SR_F_FOCAL_BLUR | SR_F_NO_SPLIT | SR_F_PRIMARY_STATS_ONLY);
+    fs.max_bounces = 0;
+    fs.reflectivity = 0.0;
+    fs.shadow_samples = 0;
+    fs.area_light_offsets = nullptr;
+    int rc = validate_frame(&fs, s);
+    if (rc) return rc;
+    return check_frame_mode(s, &fs);
+}
+
+int sr_render_hits_device(sr_scene* m, const sr_frame* f, double* d_starts, double* d_dirs, uint8_t* d_hit, double* d_ray_frac, double* d_pos, double* d_normal,
+                          uint32_t* d_color, int32_t* d_tri_index, void* hip_stream, uint64_t* d_stats) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = render_hits_check(s, f, fs);
+    if (rc || sr_frame_sample_count(&fs) == 0) return rc;          // (an empty row range: nothing is drawn, no device is asked for)
+    if ((rc = use_device(s))) return rc;
+    if (m != s) m->last_parts = 1;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    const HitsReq req{{d_starts, d_dirs, d_hit, d_ray_frac, d_pos, d_normal, d_color, d_tri_index}};
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, 0, nullptr, nullptr, &req);
+}
+
+int sr_render_hits(sr_scene* m, const sr_frame* f, double* starts, double* dirs, uint8_t* hit, double* ray_frac, double* pos, double* normal, uint32_t* color,
+                   int32_t* tri_index, uint64_t stats[4]) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = render_hits_check(s, f, fs);
+    const int64_t n = sr_frame_sample_count(&fs);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    if (m != s) m->last_parts = 1;
+    if ((rc = ensure_io_streams(s))) return rc;
+    hipStream_t stream = s->io_stream;
+    void* outs[8] = {starts, dirs, hit, ray_frac, pos, normal, color, tri_index};
+    const size_t sizes[8] = {(size_t)n * 24, (size_t)n * 24, (size_t)n, (size_t)n * 8, (size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n * 4};
+    void* dev[8];
+    for (int i = 0; i < 8; ++i) {
+        if (outs[i]) SR_HIP(s->d_io[i].reserve(sizes[i]));
+        dev[i] = outs[i] ? s->d_io[i].p : nullptr;
+    }
+    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
+    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    const HitsReq req{{(double*)dev[0], (double*)dev[1], (uint8_t*)dev[2], (double*)dev[3], (double*)dev[4], (double*)dev[5], (uint32_t*)dev[6], (int32_t*)dev[7]}};
+    if ((rc = render_common(s, &fs, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, nullptr, nullptr, &req))) { (void)hipStreamSynchronize(stream); return rc; }
+    for (int i = 0; i < 8; ++i)
+        if (outs[i]) SR_HIP(hipMemcpyAsync(outs[i], dev[i], sizes[i], hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    if (stats) std::memcpy(stats, s->last_stats, 4 * sizeof(uint64_t));
     return SR_OK;
 }
 

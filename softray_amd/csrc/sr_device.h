@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_COUNT = 35 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_COUNT = 36 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -60,6 +60,18 @@ struct RenderLaunch {
 
 // The one-kernel renderer: ray generation, traversal, shading, inline shadow rays, sub-pixel resolve.
 hipError_t launch_render(const RenderLaunch& L);
+
+// sr_render_hits: the caller's device arrays, one entry per camera sample in scan order ([S][3] doubles, [S] scalars); any may be nullptr
+struct HitsOut {
+    double*   starts;
+    double*   dirs;
+    uint8_t*  hit;
+    double*   ray_frac;
+    double*   pos;
+    double*   normal;
+    uint32_t* color;
+    int32_t*  tri;
+};
 
 // The default path: k_primary -> k_shadow -> k_resolve (sr_pipeline.hip).
 struct PipelineLaunch {
@@ -152,6 +164,9 @@ struct PipelineLaunch {
     bool          pts_per_lane; // the first shaft round with private per-lane walks (A/B hook)
     bool          pts_escape;   // a directional light whose samples all escape for a probe end inside [pts_escape_lo, pts_escape_hi]
     double        pts_escape_lo[3], pts_escape_hi[3];
+    // sr_render_hits (hits_req: launch_pipeline runs k_hits per row band instead of the frame's kernels and writes no pixel)
+    bool          hits_req;
+    HitsOut       hits_out;
     void*         static_hits;  // device HitRec[min(band samples, 128^3)]: generators of a static-shadow frame
     unsigned long long* static_claim; // device [128^3]: smallest order key that asked for an empty cell
     int32_t       static_concurrency; // rayTraceConcurrency of the frame

@@ -165,6 +165,7 @@ const char* kernel_name(int id) {
         case K_LF_BAKE: return "k_lf_bake";
         case K_LFI_LOOKUP: return "k_lfi_lookup";             // sr_set_light_field_interpolation
         case K_LFI_APPLY: return "k_lfi_apply";
+        case K_HITS: return "k_hits";                         // sr_render_hits: the frame G-buffer
         case K_PTS_INGEST: return "k_pts_ingest";             // sr_shadow_points: points -> the shadow stage's queue
         case K_PTS_SORT: return "k_pts_sort";                 // ... ray_sort + k_pts_gather of a pass
         case K_TRI_RECORDS: return "k_tri_records";           // sr_set_triangles_device

@@ -302,6 +302,98 @@ __global__ __launch_bounds__(256, SUB ? 5 : ((PKT >= 2 && !PERSIST) ? 7 : 6)) vo
 }
 
 // --------------------------------------------------------------------------------------------------
+// k_hits (sr_render_hits): the frame G-buffer
+// --------------------------------------------------------------------------------------------------
+// The primary stage's own answer per camera sample, written straight into the caller's arrays in the reference's scan order: sample
+// ((row - start_row) * width + col) * n^2 + subX * n + subY.  One wave per 8x8-pixel tile, four per 16x16 workgroup, direct form (one
+// workgroup per tile of the xcd_tile grid), the walk k_primary's instantiation with the same PKT takes -- and nothing after it: no shade(),
+// no pow, no hit queue, no sample buffer.  Every output pointer may be nullptr (a wave-uniform test).
+//
+// camera_sample_ray RESTATES k_primary's ray set-up (that kernel is not touched: lifting its set-up into a helper moves its register
+// allocation).  The two must agree expression by expression; tests/test_gpu_gbuffer.py compares the rays with the CPU model bit for bit and
+// the chain over this kernel's hits with sr_render's frames pixel for pixel.
+__device__ __forceinline__ void camera_sample_ray(const FrameConst& fc, int col, int row, int n, int si, bool blur, D3 start, D3 focal, D3& ss, D3& dw) {
+    const int width = fc.width, height = fc.height;
+    ss = start;
+    if (n == 1) {                                                            // fast path, Renderer.cs:1722-1743
+        D3 dv = mk(-((double)col / width - 0.5), -((double)row / height - 0.5) * fc.aspect, fc.fov_depth);
+        dw = mul3x3(fc.it, dv);
+    } else {
+        const int sx = si / n, sy = si - sx * n;                             // subX outer, subY inner (:1761-1763)
+        double fx = (double)sx / (n - 1) - 0.5;
+        double fy = (double)sy / (n - 1) - 0.5;
+        if (blur) {
+            D3 sv = mk(fx / width * fc.focal_blur_strength, fy / height * fc.focal_blur_strength, -fc.position_z);
+            ss = mul3x3(fc.it, sv);
+            dw = focal - ss;
+        } else {
+            D3 dv = mk(-((col + fx) / width - 0.5), -((row + fy) / height - 0.5) * fc.aspect, fc.fov_depth);
+            dw = mul3x3(fc.it, dv);
+        }
+    }
+}
+
+__device__ __forceinline__ void store3(double* __restrict__ a, size_t i, D3 v) { a[3 * i] = v.x; a[3 * i + 1] = v.y; a[3 * i + 2] = v.z; }
+
+// launch bounds (profiles/gbuffer/kernel_resources.txt): at 8 waves per SIMD (64 VGPRs) the packet forms on the four-wide tree spill more than
+// k_primary's do at 7 (64 against 44 bytes of scratch per lane), at 7 (72 VGPRs) less; the sub-sample loop and the per-lane walks take the
+// 5 / 6 that the walk itself needs in k_primary too
+template <int MODE, bool EXTRA, bool STATS, bool SUB, int PKT>
+__global__ __launch_bounds__(256, SUB ? 5 : (PKT >= 2 ? 7 : 6)) void k_hits(DevScene sc, FrameConst fc, const int32_t* __restrict__ row_map, int row_begin, int row_count,
+                                                                           HitsOut out, unsigned long long* stats, int levels) {
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    int32_t* wnode = reinterpret_cast<int32_t*>(lds_pipe) + (size_t)wave * levels;     // PKT: the wave's node stack
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    Ctr prim = {0, 0, 0, 0};
+    int tile_x, tile_y;
+    if (xcd_tile((int)blockIdx.x, fc.width, row_count, tile_x, tile_y)) {                // (false: padding of the super-tile grid)
+        const int col = tile_x * 16 + (wave & 1) * 8 + (lane & 7);
+        const int brow = tile_y * 16 + (wave >> 1) * 8 + (lane >> 3);                   // row inside this band
+        const bool live = col < fc.width && brow < row_count;
+        const int row = live ? row_map[row_begin + brow] : 0;
+        const int n = SUB ? fc.sub_pixel_res : 1, n2 = n * n;
+        // 64-bit from the first product on: 4096^2 pixels x 9 samples x 24 bytes is past 2^32
+        const size_t sbase = live ? ((size_t)(row - fc.start_row) * (size_t)fc.width + (size_t)col) * (size_t)n2 : 0;
+        const D3 start = mk(fc.start_world[0], fc.start_world[1], fc.start_world[2]);
+        const bool blur = (fc.flags & 4u) != 0;
+        D3 focal = mk(0, 0, 0);
+        if (n > 1 && blur) {
+            D3 dv = mk(-((double)col / fc.width - 0.5), -((double)row / fc.height - 0.5) * fc.aspect, fc.fov_depth);
+            focal = mul3x3(fc.it, dv) * fc.focal_depth + start;
+        }
+        for (int si = 0; si < n2; ++si) {
+            D3 ss, dw;
+            camera_sample_ray(fc, col, row, n, si, blur, start, focal, ss, dw);
+            Hit h;
+            bool ok = false;
+            if (PKT) {
+                if (live) prim.rays++;
+                ok = root_intersect_pkt<EXTRA, true, PKT == 3 ? 2 : (PKT == 2 ? 1 : 0)>(sc, sc.extra, wnode, live, ss, dw, h, prim);     // all 64 lanes take part
+            } else if (live) {
+                prim.rays++;
+                ok = root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, ss, dw, h, prim);
+            }
+            if (live) {                                                              // k_trace's conventions: a miss is zeros and triangle -1
+                const size_t i = sbase + (size_t)si;
+                if (out.starts) store3(out.starts, i, ss);
+                if (out.dirs) store3(out.dirs, i, dw);
+                if (out.hit) out.hit[i] = ok ? 1 : 0;
+                if (out.ray_frac) out.ray_frac[i] = ok ? h.t : 0.0;
+                if (out.pos) store3(out.pos, i, ok ? h.pos : mk(0, 0, 0));
+                if (out.normal) store3(out.normal, i, ok ? h.nrm : mk(0, 0, 0));
+                if (out.color) out.color[i] = ok ? h.color : 0u;
+                if (out.tri) out.tri[i] = ok ? h.tri : -1;
+            }
+        }
+    }
+    if (STATS) {
+        uint32_t a = wave_sum(prim.rays), b = wave_sum(prim.geom), c2 = wave_sum(prim.nodes), d2 = wave_sum(prim.leaves);
+        block_stat_add(&stats[0], &stats[1], &stats[2], &stats[3], a, b, c2, d2);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_shadow
 // --------------------------------------------------------------------------------------------------
 // one area-light sample: is the surface point occluded?  (ShadowMethod.cs:147-177)
@@ -4867,18 +4959,75 @@ static hipError_t launch_primary_p(const PipelineLaunch& L, int row_begin, int r
     return hipGetLastError();
 }
 
-template <int MODE, bool EXTRA, bool SUB>
-static hipError_t launch_primary_s(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples, int pad_tiles) {
+// the walk of a frame's primary stage (k_primary's and k_hits' PKT): 0 per-lane walks, 1 packets on the binary tree, 2 packets on the
+// four-wide tree's camera-ordered copy, 3 the same with (near, far) planes on all axes
+template <int MODE, bool SUB>
+static int primary_walk_kind(const PipelineLaunch& L) {
     if constexpr (MODE == MODE_BVH) {
         // packet walk + camera-cone filter: the rays of the frame must share their origin (focal blur moves it per sub-sample)
         const bool common_origin = !(SUB && (L.fc.flags & 4u));
         if (L.sc.bcam && common_origin && !L.per_lane_primary) {
-            if (L.sc.b4cam && !L.bvh2_packets && L.sc.b4cam_known == 7) return launch_primary_p<MODE, EXTRA, SUB, 3>(L, row_begin, row_count, samples, pad_tiles);
-            if (L.sc.b4cam && !L.bvh2_packets) return launch_primary_p<MODE, EXTRA, SUB, 2>(L, row_begin, row_count, samples, pad_tiles);
-            return launch_primary_p<MODE, EXTRA, SUB, 1>(L, row_begin, row_count, samples, pad_tiles);
+            if (L.sc.b4cam && !L.bvh2_packets && L.sc.b4cam_known == 7) return 3;
+            if (L.sc.b4cam && !L.bvh2_packets) return 2;
+            return 1;
+        }
+    }
+    return 0;
+}
+
+template <int MODE, bool EXTRA, bool SUB>
+static hipError_t launch_primary_s(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples, int pad_tiles) {
+    if constexpr (MODE == MODE_BVH) {
+        switch (primary_walk_kind<MODE, SUB>(L)) {
+            case 3: return launch_primary_p<MODE, EXTRA, SUB, 3>(L, row_begin, row_count, samples, pad_tiles);
+            case 2: return launch_primary_p<MODE, EXTRA, SUB, 2>(L, row_begin, row_count, samples, pad_tiles);
+            case 1: return launch_primary_p<MODE, EXTRA, SUB, 1>(L, row_begin, row_count, samples, pad_tiles);
+            default: break;
         }
     }
     return launch_primary_p<MODE, EXTRA, SUB, 0>(L, row_begin, row_count, samples, pad_tiles);
+}
+
+// sr_render_hits: k_hits over a row band, one workgroup per 16x16 tile of the xcd_tile grid (the direct form; LDS as k_primary's)
+template <int MODE, bool EXTRA, bool SUB, int PKT>
+static hipError_t launch_hits_p(const PipelineLaunch& L, int row_begin, int row_count) {
+    const dim3 grid((unsigned)xcd_tile_grid(L.fc.width, row_count));
+    const int levels = PKT >= 2 ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE);
+    const size_t lds = PKT ? (size_t)levels * 4 * 4 : (size_t)levels * 256 * 4;
+    const auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, L.stream, L.sc, L.fc, L.row_map, row_begin, row_count, L.hits_out, L.stats, levels);
+    };
+    if (L.stats) go(k_hits<MODE, EXTRA, true, SUB, PKT>); else go(k_hits<MODE, EXTRA, false, SUB, PKT>);
+    return hipGetLastError();
+}
+
+template <int MODE, bool EXTRA, bool SUB>
+static hipError_t launch_hits_s(const PipelineLaunch& L, int row_begin, int row_count) {
+    if constexpr (MODE == MODE_BVH) {
+        switch (primary_walk_kind<MODE, SUB>(L)) {
+            case 3: return launch_hits_p<MODE, EXTRA, SUB, 3>(L, row_begin, row_count);
+            case 2: return launch_hits_p<MODE, EXTRA, SUB, 2>(L, row_begin, row_count);
+            case 1: return launch_hits_p<MODE, EXTRA, SUB, 1>(L, row_begin, row_count);
+            default: break;
+        }
+    }
+    return launch_hits_p<MODE, EXTRA, SUB, 0>(L, row_begin, row_count);
+}
+
+// ... band by band, cut exactly as a frame's rows are
+template <int MODE, bool EXTRA>
+static hipError_t launch_hits_t(const PipelineLaunch& L) {
+    for (int row_begin = L.row_first; row_begin < L.row_limit; row_begin += L.band_rows) {
+        const int row_count = std::min(L.band_rows, L.row_limit - row_begin);
+        hipError_t e;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_HITS, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        e = L.fc.sub_pixel_res > 1 ? launch_hits_s<MODE, EXTRA, true>(L, row_begin, row_count) : launch_hits_s<MODE, EXTRA, false>(L, row_begin, row_count);
+        if (e != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 template <int MODE, bool EXTRA>
@@ -5617,6 +5766,7 @@ template <int MODE, bool EXTRA>
 static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     if (L.lf_bake_count > 0) return launch_lf_bake_shadows_t<MODE, EXTRA>(L);      // sr_bake_light_field with shadows: no rows, no pixels
     if (L.pts_n > 0) return launch_pts_shadows_t<MODE, EXTRA>(L);                  // sr_shadow_points: the caller's points, no rows, no pixels
+    if (L.hits_req) return launch_hits_t<MODE, EXTRA>(L);                          // sr_render_hits: the rows' camera samples, no pixels
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     const bool shadows = (L.fc.flags & 2u) != 0;
     const bool path = (L.fc.flags & kFlagPathTracing) != 0;          // (sr_api.cpp: never together with shadows or mirror bounces)

@@ -375,6 +375,29 @@ public:
         f.flags &= ~(uint32_t)SR_F_PRIMARY_STATS_ONLY;     // (the call has no primary rays: sr_last_ray_stats gets the shadow stage's counters)
         sr_check(sr_shadow_points(scene_, &f, n, pos, normal, color, out, coherent ? SR_POINTS_COHERENT : 0u));
     }
+    // The frame G-buffer (sr_render_hits): what the primary stage of the frame Render() would build for the first instance answers per camera
+    // sample, before any decorator, in scan order ((row - first row) * width + col) * n^2 + subX * n + subY.  Every array has
+    // RenderHitsSamples() entries ([S][3] doubles, [S] scalars) and may be nullptr; a miss is hit 0, zeros and triangle -1.  The decorator
+    // switches (shading, shadows, ambient occlusion, path tracing, gpuMaxBounces) are not read; voxels and the light field are refused by
+    // the library, by name.  Does nothing without a model
+    int64_t RenderHitsSamples() const {
+        const int a = std::min(std::max(0, rayTraceStartRow), height_ - 1), b = std::min(std::max(0, rayTraceEndRow), height_ - 1);
+        return b < a ? 0 : (int64_t)(b - a + 1) * width_ * rayTraceSubPixelRes * rayTraceSubPixelRes;
+    }
+    void RenderHits(double* starts, double* dirs, uint8_t* hit, double* ray_frac, double* pos, double* normal, uint32_t* color, int32_t* tri_index) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel()) return;
+        if (Instances.empty()) throw InvalidOperationException("RenderHits: no instance to take the pose from");
+        Instance& inst = *Instances.front();
+        inst.FieldOfViewDepth = fieldOfViewDepth_;
+        PreCalculate();
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        rayTraceStartRow = std::min(std::max(0, rayTraceStartRow), height_ - 1);   // :1652-1653, as Render() does
+        rayTraceEndRow = std::min(std::max(0, rayTraceEndRow), height_ - 1);
+        sr_frame f = BuildFrame(inst);
+        sr_check(sr_render_hits(scene_, &f, starts, dirs, hit, ray_frac, pos, normal, color, tri_index, nullptr));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

@@ -399,6 +399,43 @@ class GpuScene:
         _check(_lib.lib().sr_shadow_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out),
                                                   _lib.POINTS_COHERENT if coherent else 0, vp(st), vp(d_stats_ptr)))
 
+    def shade_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, stream=0):
+        """sr_shade_points_device: every array is a DEVICE pointer; enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = getattr(stream, "cuda_stream", stream)
+        _check(_lib.lib().sr_shade_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out), vp(st)))
+
+    # ---- the frame G-buffer: the primary stage's answer per camera sample (sr_render_hits) ----
+    @staticmethod
+    def sample_count(frame):
+        """Camera samples of the frame: rows x width x sub_pixel_res^2 of the clamped row range (sr_frame_sample_count)."""
+        return int(_lib.lib().sr_frame_sample_count(C.byref(frame)))
+
+    def render_hits(self, frame, rays=False, stats=False):
+        """Per camera sample of `frame`, in scan order ((row - first row) * width + col) * n^2 + subX * n + subY: a dict keyed like trace()'s
+        result (hit, ray_frac, pos, normal, color, tri_index), with rays=True also the camera rays (starts, dirs), with stats=True the four
+        primary counters (stats)."""
+        n = self.sample_count(frame)
+        res = dict(hit=np.zeros(n, dtype=np.uint8), ray_frac=np.zeros(n), pos=np.zeros((n, 3)),
+                   normal=np.zeros((n, 3)), color=np.zeros(n, dtype=np.uint32), tri_index=np.zeros(n, dtype=np.int32))
+        if rays:
+            res["starts"], res["dirs"] = np.zeros((n, 3)), np.zeros((n, 3))
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        _check(_lib.lib().sr_render_hits(self._h, C.byref(frame), _p(res.get("starts")), _p(res.get("dirs")), _p(res["hit"]), _p(res["ray_frac"]),
+                                         _p(res["pos"]), _p(res["normal"]), _p(res["color"]), _p(res["tri_index"]), _p(st)))
+        if stats:
+            res["stats"] = st
+        return res
+
+    def render_hits_device(self, frame, d_starts=0, d_dirs=0, d_hit=0, d_ray_frac=0, d_pos=0, d_normal=0, d_color=0, d_tri_index=0, stream=0,
+                           d_stats_ptr=None):
+        """sr_render_hits_device: every array is a DEVICE pointer (0 / None: not wanted) with room for sample_count(frame) entries; enqueued on
+        `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = getattr(stream, "cuda_stream", stream)
+        _check(_lib.lib().sr_render_hits_device(self._h, C.byref(frame), vp(d_starts), vp(d_dirs), vp(d_hit), vp(d_ray_frac), vp(d_pos), vp(d_normal),
+                                                vp(d_color), vp(d_tri_index), vp(st), vp(d_stats_ptr)))
+
     # ---- IRayIntersectable.IntersectRay, batched ----
     def trace(self, target, starts, dirs, counters=False):
         starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)

@@ -104,6 +104,9 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_bake_light_field(IntPtr scene, ref SrFrame frame, ulong first, ulong count, out ulong filled);
         [DllImport(Lib)] public static extern int sr_shadow_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, uint options);
+        [DllImport(Lib)] public static extern int sr_ao_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, [Out] byte[] amount, ulong firstGenerator, uint options, out ulong generators);
+        [DllImport(Lib)] public static extern int sr_ao_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr dAmount, ulong firstGenerator, uint options, IntPtr hipStream, IntPtr dGenerators, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_net_random_jump(int seed, ulong skip, [Out] int[] out55);
         [DllImport(Lib)] public static extern int sr_shadow_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_shade_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr hipStream);
         [DllImport(Lib)] public static extern long sr_frame_sample_count(ref SrFrame frame);
@@ -421,6 +424,40 @@ namespace Engine3D.Hip
                       1.0, 1.0, 0.0, 0.0, 0.0, lightDirView, lightPosView, 4);
             frame.flags &= ~F_PRIMARY_STATS_ONLY;
             Native.Check(Native.sr_shadow_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, coherent ? POINTS_COHERENT : 0, stream, dStats));
+        }
+
+        /// AmbientOcclusionMethod's occlusion byte for caller-given surface points, in input order (sr_ao_points; AmbientOcclusionMethod.cs:65-99,
+        /// AmbientOcclusion.cs:101-230): amount[i] = the byte of point i's cell (F_AO_UNCACHED in flags: of the point itself, every point
+        /// generates), result[i] = color[i] (color == null: 0xFFFFFFFF) modulated with it.  Generator g of the call uses draws
+        /// 300 (firstGenerator + g) .. + 299 of Random(randomSeed); `generators` receives their number, which a caller that splits a batch adds
+        /// to firstGenerator of the next call.  F_AMBIENT_OCCLUSION is implied; the cache is the scene's, the one AO frames fill.  pos / normal:
+        /// double[n * 3] in model space, the normal as given.  F_STATIC_SHADOWS, F_PATH_TRACING, F_VOXELS and F_LIGHT_FIELD:
+        /// SR_ERR_UNSUPPORTED -> InvalidOperationException.  Blocks.
+        public uint[] AoPoints(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode, int randomSeed,
+                               double[] pos, double[] normal, uint[] color, out byte[] amount, out ulong generators, ulong firstGenerator = 0)
+        {
+            if (pos == null || normal == null || pos.Length != normal.Length || pos.Length % 3 != 0 || (color != null && color.Length != pos.Length / 3))
+                throw new ArgumentException("AoPoints: pos and normal are double[n * 3], color is uint[n] or null");
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, 0, height - 1, 1, randomSeed,
+                      1.0, 1.0, 0.0, 0.0, 0.0, new Vector(0, 0, 1), new Vector(0, 0, 0), 4);
+            frame.flags &= ~F_PRIMARY_STATS_ONLY;                  // the call has no primary rays
+            var result = new uint[pos.Length / 3];
+            amount = new byte[pos.Length / 3];
+            Native.Check(Native.sr_ao_points(scene, ref frame, result.Length, pos, normal, color, result, amount, firstGenerator, 0, out generators));
+            return result;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_ao_points_device): enqueued on `stream` without a host
+        /// synchronisation; dColor may be IntPtr.Zero (every point 0xFFFFFFFF) or dOut itself; one of dOut / dAmount may be IntPtr.Zero;
+        /// dGenerators: a ulong on the device, or IntPtr.Zero; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void AoPointsDevice(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode, int randomSeed,
+                                   long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr dAmount, ulong firstGenerator,
+                                   IntPtr stream, IntPtr dGenerators, IntPtr dStats)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, 0, height - 1, 1, randomSeed,
+                      1.0, 1.0, 0.0, 0.0, 0.0, new Vector(0, 0, 1), new Vector(0, 0, 0), 4);
+            frame.flags &= ~F_PRIMARY_STATS_ONLY;
+            Native.Check(Native.sr_ao_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, dAmount, firstGenerator, 0, stream, dGenerators, dStats));
         }
 
         /// The frame G-buffer (sr_render_hits): the arrays a caller wants of one frame's primary hits

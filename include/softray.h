@@ -574,6 +574,46 @@ int  sr_shadow_points_device(sr_scene*, const sr_frame* frame, int64_t n, const 
                              const uint32_t* d_color /* or NULL */, uint32_t* d_out, uint32_t options, void* hip_stream,
                              uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
+/* AmbientOcclusionMethod.IntersectRay's step in batch (AmbientOcclusionMethod.cs:65-99, AmbientOcclusion.cs:101-230): the occlusion byte of n
+ * caller-given surface points -- what the decorator leaves when it is applied to the n intersections IN INPUT ORDER by one RenderContext whose
+ * Random is Random(frame->random_seed) advanced by 300 * first_generator draws.  Per point: pc = pos clamped per axis to [-0.5, 0.5] (a NaN
+ * component becomes 0.5; the reference would throw there), its cell in the 128^3 texture, and -- where the point GENERATES -- 100 probes from
+ * pc + normal * 0.001 with directions (2 u0 - 1, 2 u1 - 1, 2 u2 - 1), not normalised, negated when d . n < 0, through the frame's root geometry
+ * (the extra geometry plus the model in trace_mode); a probe escapes on no hit or rayFrac > 2.0; the byte is (byte)(escapes / 100.0 * 254 + 1).
+ * Generator number g of the call, counted in input order, uses draws 300 (first_generator + g) .. + 299.  The normal is used as given (not
+ * normalised, no facing test; zero is legal).
+ * Cached (the default; the scene's AO cache, the one AO frames use): point i generates iff its cell is empty when the call starts and no point
+ * j < i of the call has the same cell; the byte is stored in the cache and every point's amount is its cell's byte.  SR_F_AO_UNCACHED in
+ * frame->flags: every point generates, the cache is neither read nor written.
+ * amount[i] = the byte, out[i] = ModulatePackedColor(color[i], amount[i]); color == NULL: every point is 0xFFFFFFFF; out may alias color; out
+ * and amount are each optional, but not both NULL with n > 0.  *generators (or NULL) receives the number of generators: a caller that
+ * splits a batch passes first_generator + *generators to the next call, and the split calls equal the one call bit for bit.
+ * A probe origin that is not finite can only come from the normal and never reaches a walk: a NaN component lets all 100 probes escape; an
+ * infinite component does as far as the model goes, and the extra primitives are asked with the reference's arithmetic against the limit
+ * 2.0.  Either way the point stays a generator like any other: it consumes its 300 draws and fills its cell.
+ * Read from `frame`: random_seed, trace_mode, SR_F_AO_UNCACHED and SR_F_PRIMARY_STATS_ONLY; SR_F_AMBIENT_OCCLUSION is implied; concurrency is
+ * not read (a batch is one block); the camera fields are validated as for a frame and otherwise unused.
+ * Refused, in this order: n < 0, a NULL pos / normal with n > 0, both outputs NULL with n > 0, a NULL scene or frame, options != 0 (reserved),
+ * first_generator + n > 2^40: SR_ERR_INVALID_ARG; SR_F_STATIC_SHADOWS, SR_F_PATH_TRACING, SR_F_VOXELS, SR_F_LIGHT_FIELD, SR_F_SINGLE_KERNEL,
+ * max_bounces > 0, strip_count > 0: SR_ERR_UNSUPPORTED; then sr_render's validation of the frame and its trace mode; then a host-only scene:
+ * SR_ERR_NO_DEVICE.  n == 0 that passes these checks: SR_OK, nothing is touched, *generators = 0.
+ * Ordered like a frame (behind a frame of the scene in flight on any stream, the next frame behind it), on the scene's scratch, in passes of
+ * at most 2^17 points (SR_DBG_BAND_SAMPLES: fewer) that follow each other without the host waiting: the 300 draws per generator are made on
+ * the device, from jump-ahead states of System.Random (sr_net_random_jump).  A multi-device scene runs it on devices[0], where the cache lives.
+ * The host variant stages, blocks and fills sr_last_ray_stats; the device variant takes device arrays (d_generators too), enqueues on
+ * `hip_stream` without a host synchronisation and writes the counters to d_stats when given.  Statistics: [0..3] 0, [4] 100 per generator,
+ * [5..7] what the probe walks count; all 0 with SR_F_PRIMARY_STATS_ONLY. */
+int  sr_ao_points(sr_scene*, const sr_frame* frame, int64_t n, const double* pos, const double* normal, const uint32_t* color /* or NULL */,
+                  uint32_t* out /* or NULL */, uint8_t* amount /* or NULL */, uint64_t first_generator, uint32_t options,
+                  uint64_t* generators /* or NULL */);
+int  sr_ao_points_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color,
+                         uint32_t* d_out, uint8_t* d_amount, uint64_t first_generator, uint32_t options, void* hip_stream,
+                         uint64_t* d_generators /* or NULL */, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+/* diagnostics: the next 55 InternalSample() values of Random(seed) after `skip` draws, computed with the jump-ahead sr_ao_points uses
+ * (x^skip mod x^55 + x^21 - 1 over GF(2^31 - 1), applied to the first outputs).  SR_ERR_UNSUPPORTED: one of the seed's first 55 outputs
+ * lies outside [0, 2^31 - 2] and the generator is not that recurrence (no such seed is known; sr_ao_points then draws on the host) */
+int  sr_net_random_jump(int32_t seed, uint64_t skip, int32_t out[55]);
+
 /* The same step with every array in DEVICE memory on the scene's device (a multi-device scene: devices[0]), enqueued on `hip_stream` without
  * a host synchronisation and without the staging copies.  Validation as sr_shade_points; n == 0: SR_OK. */
 int  sr_shade_points_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color,
@@ -714,7 +754,7 @@ int  sr_anti_alias_device(sr_scene*, const void* d_src, int32_t dst_width, int32
 enum {
     SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
                                     per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) and the
-                                    points per pass of sr_shadow_points (default 2^22) */
+                                    points per pass of sr_shadow_points (default 2^22) and of sr_ao_points (default and limit 2^17) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
     SR_DBG_SPLIT          = 3,   /* concurrent part-frame pipelines (default 2, <= 4)                                          */
@@ -730,7 +770,8 @@ enum {
                                     walks (same table; measured slower); 36 the shadow stage of a shadowed light-field frame's lazy fill with the
                                     packet shaft walk instead of private per-lane shaft walks (same table; measured slower); 37 sr_shadow_points queues a pass in input
                                     order whatever the options say (no ray sort); 38 sr_shadow_points runs the first shaft round with private per-lane walks instead of the
-                                    packet walk (both: same output); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    packet walk (both: same output); 44 sr_ao_points makes every pass's draw table on the host, one draw after the
+                                    other, and waits once per pass (same output; cross-check and baseline); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
                                     fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -135,6 +136,11 @@ struct sr_scene {
     // rayTraceAmbientOcclusion (SR_F_AMBIENT_OCCLUSION): the 128^3 cache a Renderer keeps for its life and the claim words of one frame.  A host-only
     // scene keeps the bytes sr_set_ao_cache gave it on the host (empty vector: all zeros)
     DBuf d_ao_cache, d_ao_claim;
+    // sr_ao_points: a pass's draw table, the jump coefficients of its chunk strides (uploaded once) and the call's words of device state
+    DBuf d_aop_table, d_aop_rows, d_aop_state;
+    bool aop_rows_ready = false;
+    std::unique_ptr<sr::NetRandom> aop_host_random;   // (host tables) the Random of the call being enqueued, at ...
+    uint64_t aop_host_drawn = 0;                      // ... this many generators
     bool ao_cache_empty = true;          // the device cache must be zeroed before its next use (a new Renderer / a new model)
     std::vector<uint8_t> ao_cache_host;
     int32_t ao_table_seed = 0;           // random_seed of the frame being enqueued (read by PipelineLaunch::ao_table)
@@ -1757,7 +1763,7 @@ void sr_destroy(sr_scene* s) {
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
-                        &s->d_v9, &s->d_bcam, &s->d_blight, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_lft_cache, &s->d_lft_claim, &s->d_rhandle, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
+                        &s->d_v9, &s->d_bcam, &s->d_blight, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_aop_table, &s->d_aop_rows, &s->d_aop_state, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_lft_cache, &s->d_lft_claim, &s->d_rhandle, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
                         &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse, &s->d_bounds, &s->d_bdepth, &s->d_tbox};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
@@ -3074,6 +3080,197 @@ int sr_shadow_points(sr_scene* m, const sr_frame* f, int64_t n, const double* po
     SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     SR_HIP(hipStreamSynchronize(stream));
     if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    return SR_OK;
+}
+
+// ---- sr_ao_points ----
+const uint64_t kAoPointsMaxGenerators = 1ull << 40;
+// what sr_ao_points[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the first
+// part of a multi-device scene), `fs`: the frame with SR_F_AMBIENT_OCCLUSION implied
+static int ao_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* pos, const void* normal, const void* out, const void* amount,
+                           uint64_t first_generator, uint32_t options, sr_frame& fs) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (n < 0 || (n > 0 && (!pos || !normal)) || (n > 0 && !out && !amount) || !s || !f || options != 0 ||
+        first_generator > kAoPointsMaxGenerators || (uint64_t)n > kAoPointsMaxGenerators - first_generator)
+        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_ao_points");
+    if (f->flags & SR_F_STATIC_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: static shadows (SR_F_STATIC_SHADOWS) are another decorator's cache, not AmbientOcclusionMethod's step");
+    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain AmbientOcclusionMethod is part of");
+    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: voxel rendering (SR_F_VOXELS) has no occlusion step");
+    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter");
+    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point");
+    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points");
+    fs = *f;
+    fs.flags |= SR_F_AMBIENT_OCCLUSION;
+    int rc = validate_frame(&fs, s);
+    if (rc) return rc;
+    return check_frame_mode(s, &fs);
+}
+
+struct AoPtsReq { int64_t n; const double* pos; const double* nrm; const uint32_t* color; uint32_t* out; uint8_t* amount; uint64_t first_generator; unsigned long long* generators; };
+
+// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set
+static int ao_points_common(sr_scene* s, const sr_frame* f, const AoPtsReq& q, hipStream_t stream, unsigned long long* d_stats) {
+    int rc = sync_geometry(s, (uint32_t)f->trace_mode);
+    if (rc) return rc;
+    const bool cached = !(f->flags & SR_F_AO_UNCACHED);
+    sr::AoPointsLaunch L{};
+    bool host_table = s->dbg[SR_DBG_KERNEL_SWITCH] == 44;
+    if (!host_table && !sr::net_random_window(f->random_seed, L.window.s)) host_table = true;   // (not the recurrence for this seed: sr_host.h)
+    if (!host_table && !s->aop_rows_ready) {
+        // entry [j][i] = coefficient j of x^(stride + i): the 55 lanes of a product read consecutive words
+        std::vector<uint32_t> rows((size_t)2 * 55 * 55), t((size_t)55 * 55);
+        const uint64_t strides[2] = {64ull * 300ull, 64ull * 64ull * 300ull};
+        for (int k = 0; k < 2; ++k) {
+            sr::net_jump_rows(strides[k], t.data());
+            for (int i = 0; i < 55; ++i)
+                for (int j = 0; j < 55; ++j) rows[(size_t)k * 55 * 55 + (size_t)j * 55 + i] = t[(size_t)i * 55 + j];
+        }
+        SR_HIP(s->d_aop_rows.upload(rows));
+        s->aop_rows_ready = true;
+    }
+    // ---- ordered like a frame (render_common) ----
+    if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
+    struct MarkPreUsed {
+        sr_scene* s; hipStream_t st;
+        ~MarkPreUsed() {
+            if (!s->pre_used && hipEventCreateWithFlags(&s->pre_used, hipEventDisableTiming) != hipSuccess) return;
+            if (hipEventRecord(s->pre_used, st) == hipSuccess) s->pre_used_set = true;
+        }
+    } mark_pre_used{s, stream};
+    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
+    if (cached) {
+        SR_HIP(s->d_ao_cache.reserve(kAoCells));
+        SR_HIP(s->d_ao_claim.reserve(kAoCells * 8));
+        if (s->ao_cache_empty) {
+            SR_HIP(hipMemsetAsync(s->d_ao_cache.p, 0, kAoCells, stream));
+            s->ao_cache_empty = false;
+        }
+    }
+    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kAopMaxPass) : sr::kAopMaxPass;
+    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, q.n));
+    if (!s->num_cus) {
+        hipDeviceProp_t prop;
+        SR_HIP(hipGetDeviceProperties(&prop, s->device));
+        s->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    sr_scene::BandScratch& B = s->scratch[0];                        // (sr_debug_counters keeps describing the last frame: the call has no queue counters)
+    const size_t slots = (size_t)(pass + 255) / 256 * 256;
+    SR_HIP(B.hits.reserve(slots * sr::pipeline_hit_record_bytes()));
+    SR_HIP(B.hits2.reserve(slots * sr::pipeline_hit_record_bytes()));
+    SR_HIP(B.pt_flags.reserve(slots));
+    SR_HIP(B.pt_index.reserve(slots * 4));
+    SR_HIP(B.pt_totals.reserve((slots / (size_t)sr::pipeline_pt_chunk() + 2) * 4));
+    SR_HIP(B.ao_escapes.reserve(slots * 4));
+    SR_HIP(s->d_aop_table.reserve(sr::ao_points_table_bytes(pass)));
+    SR_HIP(s->d_aop_state.reserve(512));
+    L.sc = dev_scene(s);
+    L.mode = f->trace_mode;
+    L.n = q.n; L.pass = pass;
+    L.pos = q.pos; L.nrm = q.nrm; L.color = q.color; L.out = q.out; L.amount = q.amount;
+    L.first_generator = q.first_generator;
+    L.cache = cached ? (uint8_t*)s->d_ao_cache.p : nullptr;
+    L.claim = cached ? (unsigned long long*)s->d_ao_claim.p : nullptr;
+    L.recs = B.hits.p; L.gen = B.hits2.p;
+    L.flags = (uint8_t*)B.pt_flags.p; L.index = (uint32_t*)B.pt_index.p; L.totals = (uint32_t*)B.pt_totals.p;
+    L.escapes = (uint32_t*)B.ao_escapes.p;
+    L.table = (int32_t*)s->d_aop_table.p;
+    L.stride_rows = (const uint32_t*)s->d_aop_rows.p;
+    L.running = (unsigned long long*)s->d_aop_state.p;
+    L.base_window = (int32_t*)((char*)s->d_aop_state.p + 256);
+    L.generators_out = q.generators;
+    L.nearest_walks = s->dbg[SR_DBG_KERNEL_SWITCH] == 34;
+    L.stats = (f->flags & SR_F_PRIMARY_STATS_ONLY) ? nullptr : d_stats;
+    L.persistent_blocks = s->num_cus * 8;
+    L.stream = stream;
+    L.user = s;
+    L.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
+        hipEvent_t x = nullptr, y = nullptr;
+        if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
+        *a = x; *b = y;
+    };
+    if (host_table) {
+        // System.Random itself, one draw after the other, from the call's first generator on (the passes ask in ascending order)
+        s->aop_host_random.reset(new sr::NetRandom(f->random_seed));
+        for (uint64_t i = 0; i < q.first_generator * 300ull; ++i) (void)s->aop_host_random->next();
+        s->aop_host_drawn = q.first_generator;
+        L.host_table = [](void* user, uint64_t base, uint32_t count, int32_t* d_table, hipStream_t st) -> hipError_t {
+            sr_scene* sc = (sr_scene*)user;
+            if (base != sc->aop_host_drawn) return hipErrorInvalidValue;
+            if (count == 0) return hipSuccess;
+            std::vector<int32_t> ints((size_t)count * 300);
+            for (int32_t& v : ints) v = sc->aop_host_random->next();
+            sc->aop_host_drawn += count;
+            hipError_t e = hipMemcpyAsync(d_table, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) return e;
+            return hipStreamSynchronize(st);                           // (`ints` leaves scope)
+        };
+    }
+    const hipError_t pe = sr::launch_ao_points(L);
+    s->aop_host_random.reset();
+    SR_HIP(pe);
+    return SR_OK;
+}
+
+int sr_ao_points_device(sr_scene* m, const sr_frame* f, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color, uint32_t* d_out,
+                        uint8_t* d_amount, uint64_t first_generator, uint32_t options, void* hip_stream, uint64_t* d_generators, uint64_t* d_stats) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = ao_points_check(s, f, n, d_pos, d_normal, d_out, d_amount, first_generator, options, fs);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n == 0) {
+        if (d_generators && s->device >= 0) {
+            SR_HIP(hipSetDevice(s->device));
+            SR_HIP(hipMemsetAsync(d_generators, 0, sizeof(uint64_t), stream));
+        }
+        return SR_OK;
+    }
+    if ((rc = use_device(s))) return rc;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    const AoPtsReq req{n, d_pos, d_normal, d_color, d_out, d_amount, first_generator, (unsigned long long*)d_generators};
+    return ao_points_common(s, &fs, req, stream, (unsigned long long*)d_stats);
+}
+
+int sr_ao_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, uint8_t* amount,
+                 uint64_t first_generator, uint32_t options, uint64_t* generators) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = ao_points_check(s, f, n, pos, normal, out, amount, first_generator, options, fs);
+    if (rc) return rc;
+    if (n == 0) { if (generators) *generators = 0; return SR_OK; }
+    if ((rc = use_device(s))) return rc;
+    if ((rc = ensure_io_streams(s))) return rc;
+    hipStream_t stream = s->io_stream;
+    const size_t sizes[5] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n, sizeof(uint64_t)};
+    for (int i = 0; i < 5; ++i) SR_HIP(s->d_io[i].reserve(sizes[i]));
+    SR_HIP(hipMemcpy(s->d_io[0].p, pos, sizes[0], hipMemcpyHostToDevice));
+    SR_HIP(hipMemcpy(s->d_io[1].p, normal, sizes[1], hipMemcpyHostToDevice));
+    if (color) SR_HIP(hipMemcpy(s->d_io[2].p, color, sizes[2], hipMemcpyHostToDevice));
+    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
+    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    // (the colours are modulated where they lie: the device variant's `out` aliasing `color`)
+    const AoPtsReq req{n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, color ? (const uint32_t*)s->d_io[2].p : nullptr,
+                       out ? (uint32_t*)s->d_io[2].p : nullptr, amount ? (uint8_t*)s->d_io[3].p : nullptr, first_generator, (unsigned long long*)s->d_io[4].p};
+    if ((rc = ao_points_common(s, &fs, req, stream, (unsigned long long*)s->d_stats.p))) { (void)hipStreamSynchronize(stream); return rc; }
+    uint64_t made = 0;
+    if (out) SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
+    if (amount) SR_HIP(hipMemcpyAsync(amount, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(&made, s->d_io[4].p, sizes[4], hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
+    if (generators) *generators = made;
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    return SR_OK;
+}
+
+int sr_net_random_jump(int32_t seed, uint64_t skip, int32_t out[55]) {
+    if (!out) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_net_random_jump");
+    int32_t w[sr::kNetWindow];
+    if (!sr::net_random_window(seed, w)) return fail(SR_ERR_UNSUPPORTED, "sr_net_random_jump: one of the seed's first 55 outputs lies outside [0, 2^31 - 2]");
+    uint32_t c[sr::kNetLag];
+    sr::net_jump_poly(skip, c);
+    sr::net_jump_apply(w, c, out);
     return SR_OK;
 }
 

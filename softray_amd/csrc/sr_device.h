@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_COUNT = 36 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_COUNT = 38 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -233,6 +233,44 @@ struct BakeLaunch {
 hipError_t launch_lf_bake(const BakeLaunch& L);
 // sr_light_field_coords: RayToFloat4D of n rays at resolution `res` (k_lf_coords, sr_pipeline.hip: the device function of the interpolating frame kernels)
 hipError_t launch_lf_coords(long long n, const double* starts, const double* dirs, int res, double* coords, uint8_t* inside, hipStream_t stream);
+// sr_ao_points (sr_pipeline.hip k_aop_ingest): n caller-given surface points through AmbientOcclusionMethod's step in passes of `pass` points
+constexpr int64_t kAopMaxPass = 1ll << 17;     // 2^17 generators: a 150 MiB draw table
+struct NetWindow { int32_t s[109]; };           // the first 109 InternalSample() values of a Random (sr_host.h net_random_window)
+struct AoPointsLaunch {
+    DevScene    sc;
+    int32_t     mode;
+    int64_t     n, pass;
+    const double* pos;          // device [n][3], model space
+    const double* nrm;          // device [n][3], as given
+    const uint32_t* color;      // device [n] or nullptr (every point 0xFFFFFFFF); may be `out`
+    uint32_t*   out;            // device [n] or nullptr
+    uint8_t*    amount;         // device [n] or nullptr
+    uint64_t    first_generator;
+    uint8_t*    cache;          // device [128^3]: the scene's AO cache; nullptr: uncached, every point generates
+    unsigned long long* claim;  // device [128^3] (cached)
+    void*       recs;           // device HitRec[pass]: the pass's points
+    void*       gen;            // device HitRec[pass]: its generators
+    uint8_t*    flags;          // device [pass]
+    uint32_t*   index;          // device [pass]
+    uint32_t*   totals;         // device [pass / pipeline_pt_chunk() + 2]
+    uint32_t*   escapes;        // device [pass]
+    int32_t*    table;          // device, ao_points_table_bytes(pass): the pass's draws, 300 per generator
+    NetWindow   window;         // ... of Random(random_seed) (unused with host_table)
+    const uint32_t* stride_rows; // device [2][55][55]: the jump coefficients of one chunk and of 64 chunks (sr_api.cpp)
+    int32_t*    base_window;    // device [55]
+    unsigned long long* running; // device: generators of the call's earlier passes
+    unsigned long long* generators_out; // device or nullptr: receives the call's generator count
+    bool        nearest_walks;  // SR_MODE_BVH with nearest-hit walks instead of any-hit walks (hook 34)
+    // not nullptr: the host makes every pass's table -- `count` generators from draw 300 * base on -- and the call waits once per pass
+    hipError_t (*host_table)(void* user, uint64_t base, uint32_t count, int32_t* d_table, hipStream_t stream);
+    unsigned long long* stats;  // device [8] or nullptr: [4] += probes, [5..7] += what their walks count
+    int32_t     persistent_blocks;
+    hipStream_t stream;
+    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
+    void*       user;
+};
+hipError_t launch_ao_points(const AoPointsLaunch& L);
+size_t ao_points_table_bytes(int64_t pass);
 // per-frame pre-pass: a copy of the four-wide nodes with every node's children sorted by the distance of their box centres from
 // `point` (model space), nearest first (camera origin) or farthest first (light: nearest to the surface points first)
 // swap_mask (bit a): exchange lo and hi on axis a in the copy (the rays of the frame travel towards smaller coordinates there)

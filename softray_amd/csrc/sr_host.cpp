@@ -75,6 +75,65 @@ int32_t NetRandom::sample() {
 int32_t NetRandom::next() { return sample(); }
 double NetRandom::next_double() { return sample() * (1.0 / 2147483647); }
 
+bool net_random_window(int32_t seed, int32_t w[kNetWindow]) {
+    NetRandom rnd(seed);
+    bool ok = true;
+    for (int i = 0; i < kNetLag; ++i) {
+        w[i] = rnd.next();
+        ok = ok && w[i] >= 0 && (uint32_t)w[i] < kNetPrime;
+    }
+    if (!ok) return false;
+    for (int i = kNetLag; i < kNetWindow; ++i) {
+        const int32_t d = w[i - 55] - w[i - 34];
+        w[i] = d < 0 ? d + (int32_t)kNetPrime : d;
+    }
+    return true;
+}
+static inline uint32_t net_mul(uint32_t a, uint32_t b) { return (uint32_t)((uint64_t)a * b % kNetPrime); }
+static inline uint32_t net_add(uint32_t a, uint32_t b) { const uint32_t s = a + b; return s >= kNetPrime ? s - kNetPrime : s; }
+static inline uint32_t net_sub(uint32_t a, uint32_t b) { return a >= b ? a - b : a + kNetPrime - b; }
+// a <- a * b mod (x^55 + x^21 - 1): x^k = x^(k - 55) - x^(k - 34) for k >= 55, highest power first
+static void net_poly_mul(uint32_t a[kNetLag], const uint32_t b[kNetLag]) {
+    uint32_t t[kNetWindow] = {};
+    for (int i = 0; i < kNetLag; ++i) {
+        if (!a[i]) continue;
+        for (int j = 0; j < kNetLag; ++j) t[i + j] = net_add(t[i + j], net_mul(a[i], b[j]));
+    }
+    for (int k = kNetWindow - 1; k >= kNetLag; --k) {
+        t[k - 55] = net_add(t[k - 55], t[k]);
+        t[k - 34] = net_sub(t[k - 34], t[k]);
+    }
+    for (int i = 0; i < kNetLag; ++i) a[i] = t[i];
+}
+void net_jump_poly(uint64_t m, uint32_t c[kNetLag]) {
+    uint32_t sq[kNetLag] = {};
+    for (int i = 0; i < kNetLag; ++i) c[i] = 0;
+    c[0] = 1;
+    sq[1] = 1;
+    for (; m; m >>= 1) {
+        if (m & 1) net_poly_mul(c, sq);
+        if (m >> 1) net_poly_mul(sq, sq);
+    }
+}
+void net_jump_rows(uint64_t m, uint32_t rows[kNetLag * kNetLag]) {
+    uint32_t c[kNetLag];
+    net_jump_poly(m, c);
+    for (int i = 0; i < kNetLag; ++i) {
+        for (int j = 0; j < kNetLag; ++j) rows[i * kNetLag + j] = c[j];
+        const uint32_t top = c[kNetLag - 1];                     // c <- c * x
+        for (int j = kNetLag - 1; j > 0; --j) c[j] = c[j - 1];
+        c[0] = top;
+        c[21] = net_sub(c[21], top);
+    }
+}
+void net_jump_apply(const int32_t w[kNetWindow], const uint32_t c[kNetLag], int32_t out[kNetLag]) {
+    for (int i = 0; i < kNetLag; ++i) {
+        uint32_t acc = 0;
+        for (int j = 0; j < kNetLag; ++j) acc = net_add(acc, net_mul(c[j], (uint32_t)w[i + j]));
+        out[i] = (int32_t)acc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // primitive records
 // ------------------------------------------------------------------------------------------------

@@ -27,6 +27,18 @@ private:
     int32_t table_[56];
     int     inext_, inextp_;
 };
+// The jump-ahead.  Once the 55 table entries are outputs (after 55 draws) and all of them lie in [0, 2^31 - 2], sample() is exactly
+//   s[n + 55] = (s[n] - s[n + 21]) mod (2^31 - 1)
+// (its `r == int.MaxValue` branch cannot fire any more), a linear recurrence over GF(2^31 - 1): with c = x^m mod (x^55 + x^21 - 1),
+// s[n + m] = sum_j c[j] s[n + j].  Outputs are counted from 0: s[k] is what the (k + 1)-th sample() returns.
+constexpr int kNetLag = 55, kNetWindow = 2 * kNetLag - 1;
+constexpr uint32_t kNetPrime = 2147483647u;
+// s[0 .. 108] of Random(seed): 55 draws, then the recurrence.  false: one of the first 55 lies outside [0, 2^31 - 2] (the constructor's
+// wrapping arithmetic can leave such a value, at odds of about 2^-31 per entry) and nothing here applies to the seed
+bool net_random_window(int32_t seed, int32_t w[kNetWindow]);
+void net_jump_poly(uint64_t m, uint32_t c[kNetLag]);                                   // x^m mod (x^55 + x^21 - 1)
+void net_jump_rows(uint64_t m, uint32_t rows[kNetLag * kNetLag]);                      // row i = x^(m + i): the window m draws on = rows x window
+void net_jump_apply(const int32_t w[kNetWindow], const uint32_t c[kNetLag], int32_t out[kNetLag]);   // out[i] = s[m + i]
 
 // ---- primitive records ----
 Rec128 make_triangle_record(Vec3 v1, Vec3 v2, Vec3 v3, uint32_t color, int32_t aux);  // Triangle.cs:29-57

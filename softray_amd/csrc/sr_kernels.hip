@@ -155,6 +155,8 @@ const char* kernel_name(int id) {
         case K_PT_EXCHANGE: return "pathtrace_exchange";      // ... its counts out, the wait for the other parts, all counts back (copies, no kernel)
         case K_AO: return "ambient_occlusion";                // the whole stage of one frame: claim, scan, select, probes, store, apply
         case K_AO_PROBE: return "k_ao_probe";
+        case K_DRAWS: return "k_draws";                       // sr_ao_points: a pass's draw table (k_aop_base, k_aop_states, k_draws)
+        case K_AOP_PROBE: return "k_aop_probe";               // ... its probes
         case K_LF_LOOKUP: return "k_lf_lookup";
         case K_LF_FILL: return "k_lf_fill";
         case K_LF_APPLY: return "k_lf_apply";

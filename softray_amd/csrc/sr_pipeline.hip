@@ -3976,6 +3976,286 @@ __global__ __launch_bounds__(256) void k_ao_apply(PtBand band, const uint8_t* __
 }
 
 // --------------------------------------------------------------------------------------------------
+// sr_ao_points: AmbientOcclusionMethod.IntersectRay for caller-given surface points, applied in input order by one RenderContext whose
+// Random has made 300 * first_generator draws.  A batch of any size, so nothing is made on the host and the host never waits: the batch
+// runs in passes, and a pass's draw table is made on the device from jump-ahead states (sr_host.h: System.Random is a linear recurrence
+// over GF(2^31 - 1) once its table holds outputs).  Per pass of at most 2^17 points:
+//   k_aop_ingest      lane = point: clamp, cell, class of the probe origin (finite / a NaN component / an infinite one) -> a HitRec-shaped
+//                     record; cached: atomicMin(claim[cell], the point's index in the call) where the cell is empty
+//   k_aop_mark        flag = the point won its cell (uncached: every point)
+//   k_pt_scan, k_pt_scan_totals     the generators' exclusive prefix sum in input order; totals[chunks] = their number, which stays on the device
+//   k_aop_select      generator list in input order: pad[0] = cell, pad[1] = k inside the pass, pad[2] = class
+//   k_aop_base        one workgroup: x^(300 base) by square-and-multiply, base = first_generator + the generators of the earlier passes (a
+//                     number only the device knows in cached mode) -> the window of draw 300 base; then adds the pass to the running total
+//   k_aop_states      the window at the start of every chunk of 64 generators (19 200 draws) that holds a generator: a chain of products with the 55 x 55
+//                     coefficients of the stride 64 x 19 200 to the workgroup's first chunk, then of the stride 19 200 through its 64 chunks.
+//                     A window is the chunk's first 55 table entries: it is stored where k_draws finds it
+//   k_draws           one wave per chunk: 55 lanes hold the window and replace all of it per step, stores coalesced
+//   k_aop_probe       k_ao_probe with the generator count read from the device and the origin's class honoured
+//   k_aop_store       count -> byte, into the cache (cached) and the generator's slot
+//   k_aop_apply       every point: amount and / or modulate(colour, amount)
+// A pass sees the bytes the earlier passes stored, so "the lowest index wins its cell" holds across passes.
+// --------------------------------------------------------------------------------------------------
+constexpr int kAopChunkGens = 64, kAopChunkDraws = kAopChunkGens * 3 * kAoProbes;      // generators / draws per wave of k_draws
+constexpr int kAopSuper = 64;                                                          // chunks per workgroup of k_aop_states
+constexpr uint32_t kNetP = 2147483647u;                                                // 2^31 - 1
+constexpr uint32_t kAopFinite = 0u, kAopNan = 1u, kAopInf = 2u;
+
+__device__ __forceinline__ uint32_t net_fold(unsigned long long x) {                   // x < 2^62 -> congruent, < 2^32
+    return (uint32_t)(x & kNetP) + (uint32_t)(x >> 31);
+}
+__device__ __forceinline__ uint32_t net_final(unsigned long long acc) {                // a sum of < 2^20 folded products -> [0, p)
+    unsigned long long a = (acc & kNetP) + (acc >> 31);
+    a = (a & kNetP) + (a >> 31);
+    return a >= kNetP ? (uint32_t)(a - kNetP) : (uint32_t)a;
+}
+__device__ __forceinline__ uint32_t net_subm(uint32_t a, uint32_t b) { return a >= b ? a - b : a + kNetP - b; }
+
+template <bool CACHED>
+__global__ __launch_bounds__(256) void k_aop_ingest(const double* __restrict__ pos, const double* __restrict__ nrm, uint32_t n, unsigned long long first,
+                                                    const uint8_t* __restrict__ cache, unsigned long long* __restrict__ claim, HitRec* __restrict__ recs) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    HitRec r;
+    const D3 c = ao_clamp(pos + (size_t)i * 3);
+    r.pos[0] = c.x; r.pos[1] = c.y; r.pos[2] = c.z;
+    for (int a = 0; a < 3; ++a) r.nrm[a] = nrm[(size_t)i * 3 + a];
+    const D3 s = c + mk(r.nrm[0], r.nrm[1], r.nrm[2]) * kAoProbeOffset;
+    const bool is_nan = s.x != s.x || s.y != s.y || s.z != s.z;
+    const double fin = (s.x - s.x) + (s.y - s.y) + (s.z - s.z);                        // 0 for finite components, NaN otherwise
+    const uint32_t cell = ao_cell(c);
+    r.sample = i;
+    r.pad[0] = cell;
+    r.pad[1] = 0u;
+    r.pad[2] = is_nan ? kAopNan : (fin == 0.0 ? kAopFinite : kAopInf);
+    recs[i] = r;
+    if (CACHED && cache[cell] == 0) atomicMin(&claim[cell], first + (unsigned long long)i);
+}
+
+__global__ __launch_bounds__(256) void k_aop_mark(const HitRec* __restrict__ recs, uint32_t n, unsigned long long first, const uint8_t* __restrict__ cache,
+                                                  const unsigned long long* __restrict__ claim, uint8_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint8_t f = 1;
+    if (cache) {
+        const uint32_t cell = recs[i].pad[0];
+        f = (cache[cell] == 0 && claim[cell] == first + (unsigned long long)i) ? 1 : 0;
+    }
+    flags[i] = f;
+}
+
+__global__ __launch_bounds__(256) void k_aop_select(const HitRec* __restrict__ recs, uint32_t n, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ idx,
+                                                    const uint32_t* __restrict__ totals, HitRec* __restrict__ gen) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || !flags[i]) return;
+    HitRec r = recs[i];
+    const uint32_t g = pt_before(idx, totals, n, i);
+    r.pad[1] = g;
+    gen[g] = r;
+}
+
+// (LDS: 1.8 KB.  128 lanes: lane k holds coefficient k of a product before it is reduced)
+__global__ __launch_bounds__(128) void k_aop_base(NetWindow w, unsigned long long first_generator, unsigned long long* __restrict__ running,
+                                                  const uint32_t* __restrict__ pass_count, int32_t* __restrict__ base_window, unsigned long long* generators_out) {
+    __shared__ uint32_t acc[55], sq[55], prod[109];
+    const int t = threadIdx.x;
+    const unsigned long long before = *running;
+    if (*pass_count == 0u) {                                                           // (block-uniform) nothing to draw for: the total stays
+        if (t == 0 && generators_out) *generators_out = before;
+        return;
+    }
+    unsigned long long m = 300ull * (first_generator + before);
+    if (t < 55) { acc[t] = t == 0 ? 1u : 0u; sq[t] = t == 1 ? 1u : 0u; }
+    __syncthreads();
+    // a <- a * b mod (x^55 + x^21 - 1); uniform control flow: m is the same in every lane
+    const auto mul = [&](uint32_t* a, const uint32_t* b) {
+        if (t < 109) {
+            unsigned long long sum = 0;
+            const int lo = t > 54 ? t - 54 : 0, hi = t < 54 ? t : 54;
+            for (int i = lo; i <= hi; ++i) sum += net_fold((unsigned long long)a[i] * b[t - i]);
+            prod[t] = net_final(sum);
+        }
+        __syncthreads();
+        // x^k = x^(k - 55) - x^(k - 34): powers 89 .. 108 first (they feed 34 .. 53 and 55 .. 74), then 55 .. 88 (they feed 0 .. 54)
+        uint32_t v = 0;
+        if (t >= 34 && t <= 53) v = net_final((unsigned long long)prod[t] + prod[t + 55]);
+        if (t >= 55 && t <= 74) v = net_subm(prod[t], prod[t + 34]);
+        __syncthreads();
+        if ((t >= 34 && t <= 53) || (t >= 55 && t <= 74)) prod[t] = v;
+        __syncthreads();
+        if (t < 55) {
+            uint32_t r = prod[t];
+            if (t <= 33) r = net_final((unsigned long long)r + prod[t + 55]);
+            if (t >= 21) r = net_subm(r, prod[t + 34]);
+            a[t] = r;
+        }
+        __syncthreads();
+    };
+    for (; m; m >>= 1) {
+        if (m & 1ull) mul(acc, sq);
+        if (m >> 1) mul(sq, sq);
+    }
+    if (t < 55) {
+        unsigned long long sum = 0;
+        for (int j = 0; j < 55; ++j) sum += net_fold((unsigned long long)acc[j] * (uint32_t)w.s[t + j]);
+        base_window[t] = (int32_t)net_final(sum);
+    }
+    if (t == 0) {
+        const unsigned long long total = before + (unsigned long long)*pass_count;
+        *running = total;
+        if (generators_out) *generators_out = total;
+    }
+}
+
+// a pass whose table the host made: the running total alone
+__global__ void k_aop_total(unsigned long long* __restrict__ running, const uint32_t* __restrict__ pass_count, unsigned long long* generators_out) {
+    const unsigned long long total = *running + (unsigned long long)*pass_count;
+    *running = total;
+    if (generators_out) *generators_out = total;
+}
+
+// workgroup b: chunks [64 b, 64 b + 64) of the pass.  rows: [0] the stride of one chunk, [1] of 64 chunks; entry [j][i] = coefficient j of
+// x^(stride + i), so that the 55 lanes of a product read consecutive words
+// (LDS: 0.5 KB)
+__global__ __launch_bounds__(64) void k_aop_states(const int32_t* __restrict__ base_window, const uint32_t* __restrict__ rows, const uint32_t* __restrict__ pass_count,
+                                                   int32_t* __restrict__ table) {
+    __shared__ uint32_t win[2][55];
+    const int t = threadIdx.x;
+    const uint32_t chunks = (*pass_count + (uint32_t)kAopChunkGens - 1u) / (uint32_t)kAopChunkGens;     // the chunks that hold a generator
+    if (blockIdx.x * (uint32_t)kAopSuper >= chunks) return;                           // (block-uniform)
+    if (t < 55) win[0][t] = (uint32_t)base_window[t];
+    __syncthreads();
+    int cur = 0;
+    const auto step = [&](const uint32_t* m) {
+        if (t < 55) {
+            unsigned long long sum = 0;
+            for (int j = 0; j < 55; ++j) sum += net_fold((unsigned long long)m[j * 55 + t] * win[cur][j]);
+            win[cur ^ 1][t] = net_final(sum);
+        }
+        __syncthreads();
+        cur ^= 1;
+    };
+    for (uint32_t k = 0; k < blockIdx.x; ++k) step(rows + 55 * 55);
+    const uint32_t c0 = blockIdx.x * (uint32_t)kAopSuper;
+    for (uint32_t c = c0; c < c0 + (uint32_t)kAopSuper && c < chunks; ++c) {
+        if (t < 55) table[(size_t)c * kAopChunkDraws + t] = (int32_t)win[cur][t];
+        if (c + 1u < c0 + (uint32_t)kAopSuper && c + 1u < chunks) step(rows);
+    }
+}
+
+// one wave per chunk: lane l < 55 holds s[n + l] and every step replaces the window by the next 55 values,
+//   l < 34:  s[n + 55 + l] = s[n + l] - s[n + l + 21]
+//   l >= 34: s[n + 55 + l] = s[n + l] - s[n + 21 + l] where s[n + 21 + l] = s[n + l - 34] - s[n + l - 13] is new itself
+// with two register exchanges and no LDS.  Only the chunks that hold one of the pass's generators are made
+__global__ __launch_bounds__(256) void k_draws(const uint32_t* __restrict__ pass_count, uint32_t chunks, int32_t* __restrict__ table) {
+    const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (chunk >= chunks || chunk * (uint32_t)kAopChunkGens >= *pass_count) return;      // (wave-uniform)
+    int32_t* out = table + (size_t)chunk * kAopChunkDraws;
+    int32_t v = lane < 55u ? out[lane] : 0;
+    const int src_a = lane < 34u ? (int)lane + 21 : (int)lane - 34, src_b = lane < 34u ? (int)lane : (int)lane - 13;
+    for (uint32_t n = 55u; n < (uint32_t)kAopChunkDraws; n += 55u) {
+        const int32_t a = __shfl(v, src_a, 64), b = __shfl(v, src_b, 64);
+        int32_t sub = a;                                                               // l < 34: s[n + l + 21]
+        if (lane >= 34u) { sub = a - b; if (sub < 0) sub += (int32_t)kNetP; }
+        int32_t nv = v - sub;
+        if (nv < 0) nv += (int32_t)kNetP;
+        v = nv;
+        if (lane < 55u && n + lane < (uint32_t)kAopChunkDraws) out[n + lane] = v;
+    }
+}
+
+// k_ao_probe for a pass of sr_ao_points: the number of generators comes from the device, and a probe origin that is not finite never
+// reaches a walk -- a NaN component: no primitive and no tree answers, the probe escapes; an infinite component: no model triangle
+// answers (its hit point is NaN), the extra primitives are asked with the literal path's arithmetic
+// (LDS: the per-lane traversal stacks of root_intersect, stack levels x 256 lanes x 4 bytes, as k_ao_probe)
+template <int MODE, bool EXTRA, bool STATS, bool ANYHIT>
+__global__ __launch_bounds__(256) void k_aop_probe(DevScene sc, const HitRec* __restrict__ gen, const uint32_t* __restrict__ pass_count,
+                                                   const int32_t* __restrict__ table, uint32_t* __restrict__ escapes, unsigned long long* stats) {
+    const int tid = threadIdx.x;
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    const unsigned long long items = (unsigned long long)*pass_count * (unsigned long long)kAoProbes, stride = (unsigned long long)gridDim.x * 256ull;
+    Ctr sec = {0, 0, 0, 0};
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 256ull; base < items; base += stride) {     // (block-uniform trip count)
+        const unsigned long long item = base + (unsigned long long)tid;
+        const bool live = item < items;
+        const unsigned int g = (unsigned int)(item / (unsigned long long)kAoProbes);
+        bool escaped = false;
+        if (live) {
+            const unsigned int i = (unsigned int)(item - (unsigned long long)g * (unsigned long long)kAoProbes);
+            const HitRec q = gen[g];
+            const int32_t* u = table + ((size_t)q.pad[1] * (size_t)(3 * kAoProbes) + (size_t)(3u * i));
+            const double ux = u[0] * (1.0 / 2147483647.0), uy = u[1] * (1.0 / 2147483647.0), uz = u[2] * (1.0 / 2147483647.0);
+            const D3 n = mk(q.nrm[0], q.nrm[1], q.nrm[2]);
+            D3 d = mk(ux * 2 - 1, uy * 2 - 1, uz * 2 - 1);
+            if (dot(d, n) < 0.0) d = neg(d);
+            const D3 s = mk(q.pos[0], q.pos[1], q.pos[2]) + n * kAoProbeOffset;
+            Hit h;
+            sec.rays++;
+            if (q.pad[2] == kAopNan) {
+                escaped = true;
+            } else if (q.pad[2] == kAopInf) {
+                bool occluded = false;
+                if (EXTRA) {
+                    for (int e = 0; e < sc.nextra && !occluded; ++e) {
+                        double t; D3 pos, nrm;
+                        uint32_t tests;
+                        const bool ok = extra_hit(&sc.extra[e], s, d, t, pos, nrm, tests);
+                        sec.geom += tests;
+                        occluded = ok && t <= kAoProbeDist;
+                    }
+                }
+                escaped = !occluded;
+            } else if constexpr (MODE == MODE_BVH && ANYHIT) {
+                bool occluded = false;
+                if (EXTRA) {
+                    for (int e = 0; e < sc.nextra && !occluded; ++e) {
+                        double t; D3 pos, nrm;
+                        uint32_t tests;
+                        const bool ok = extra_hit(&sc.extra[e], s, d, t, pos, nrm, tests);
+                        sec.geom += tests;
+                        occluded = ok && t <= kAoProbeDist;
+                    }
+                }
+                escaped = !occluded && !bvh_intersect<true>(sc, st, s, d, h, sec, kAoProbeDist);
+            } else {
+                const bool ok = root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, s, d, h, sec);
+                escaped = !ok || h.t > kAoProbeDist;
+            }
+        }
+        const unsigned int g0 = __shfl(g, 0, 64);                                 // lane 0 holds the wave's lowest pair
+        const unsigned long long m0 = __ballot(escaped && g == g0), m1 = __ballot(escaped && g != g0);
+        if ((tid & 63) == 0) {
+            if (m0) atomicAdd(&escapes[g0], (uint32_t)__popcll(m0));
+            if (m1) atomicAdd(&escapes[g0 + 1u], (uint32_t)__popcll(m1));
+        }
+    }
+    if (STATS) {
+        uint32_t a = wave_sum(sec.rays), b = wave_sum(sec.geom), c2 = wave_sum(sec.nodes), d2 = wave_sum(sec.leaves);
+        if ((tid & 63) == 0) { stat_add(&stats[4], a); stat_add(&stats[5], b); stat_add(&stats[6], c2); stat_add(&stats[7], d2); }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_aop_store(const HitRec* __restrict__ gen, const uint32_t* __restrict__ pass_count, uint32_t* __restrict__ escapes,
+                                                   uint8_t* __restrict__ cache) {
+    const unsigned int g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= *pass_count) return;
+    const uint32_t v = to_byte((double)escapes[g] / (double)kAoProbes * 254 + 1);          // AmbientOcclusion.cs:135,151
+    escapes[g] = v;
+    if (cache) cache[gen[g].pad[0]] = (uint8_t)v;
+}
+
+// (`out` may be the colour array itself: neither is __restrict__)
+__global__ __launch_bounds__(256) void k_aop_apply(const HitRec* __restrict__ recs, uint32_t n, const uint8_t* __restrict__ cache, const uint32_t* __restrict__ idx,
+                                                   const uint32_t* __restrict__ totals, const uint32_t* __restrict__ bytes, const uint32_t* color, uint32_t* out,
+                                                   uint8_t* __restrict__ amount) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t a = cache ? (uint32_t)cache[recs[i].pad[0]] : bytes[pt_before(idx, totals, n, i)];
+    if (amount) amount[i] = (uint8_t)a;
+    if (out) out[i] = modulate(color ? color[i] : 0xFFFFFFFFu, a);                        // AmbientOcclusionMethod.cs:97
+}
+
+// --------------------------------------------------------------------------------------------------
 // rayTraceLightField with LightFieldStoresTriangles = false (SR_F_LIGHT_FIELD; LightFieldColorMethod.cs:92-217, LightField4D.cs:175-206,
 // 253-273, 304-344, Sphere.cs:69-142): the colour of a camera sample is the colour of the CELL of a 4-D table its line falls into -- the
 // two points where the line pierces the sphere of radius 0.866 about the model's origin, each as (longitude, latitude) in 2N x N patches.
@@ -5957,6 +6237,97 @@ int pipeline_round_cap_max(int round) { return round == 0 ? 64 : 1024; }
 int pipeline_bounce_lds_levels() { return kBounceLdsLevels; }
 int pipeline_pt_chunk() { return kPtChunk; }
 size_t pipeline_round_state_bytes() { return sizeof(RoundState); }
+// sr_ao_points: the passes, back to back on the stream (see k_aop_ingest).  A pass waits for the host only when the host makes its table
+// (AoPointsLaunch::host_table: SR_DBG_KERNEL_SWITCH 44, or a seed the jump-ahead does not cover)
+template <int MODE, bool EXTRA>
+static hipError_t launch_ao_points_t(const AoPointsLaunch& L) {
+    hipError_t e;
+    const bool cached = L.cache != nullptr;
+    HitRec* recs = (HitRec*)L.recs;
+    HitRec* gen = (HitRec*)L.gen;
+    if ((e = hipMemsetAsync(L.running, 0, sizeof(unsigned long long), L.stream)) != hipSuccess) return e;
+    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+    unsigned long long host_before = 0;                                   // (host tables only) generators of the earlier passes
+    for (int64_t first = 0; first < L.n; first += L.pass) {
+        const uint32_t count = (uint32_t)std::min<int64_t>(L.pass, L.n - first);
+        const unsigned blocks = (count + 255u) / 256u;
+        const uint32_t scan_chunks = (count + (uint32_t)kPtChunk - 1u) / (uint32_t)kPtChunk;
+        const uint32_t chunks = (count + (uint32_t)kAopChunkGens - 1u) / (uint32_t)kAopChunkGens;
+        const uint32_t* pass_count = L.totals + scan_chunks;
+        if (cached) {
+            if ((e = hipMemsetAsync(L.claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_aop_ingest<true>, dim3(blocks), dim3(256), 0, L.stream, L.pos + first * 3, L.nrm + first * 3, count, (unsigned long long)first,
+                               (const uint8_t*)L.cache, L.claim, recs);
+        } else {
+            hipLaunchKernelGGL(k_aop_ingest<false>, dim3(blocks), dim3(256), 0, L.stream, L.pos + first * 3, L.nrm + first * 3, count, (unsigned long long)first,
+                               (const uint8_t*)nullptr, (unsigned long long*)nullptr, recs);
+        }
+        hipLaunchKernelGGL(k_aop_mark, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)recs, count, (unsigned long long)first, (const uint8_t*)L.cache,
+                           (const unsigned long long*)L.claim, L.flags);
+        hipLaunchKernelGGL(k_pt_scan, dim3(scan_chunks), dim3(256), 0, L.stream, (const uint8_t*)L.flags, count, L.index, L.totals);
+        hipLaunchKernelGGL(k_pt_scan_totals, dim3(1), dim3(256), 0, L.stream, L.totals, scan_chunks);
+        hipLaunchKernelGGL(k_aop_select, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)recs, count, (const uint8_t*)L.flags, (const uint32_t*)L.index,
+                           (const uint32_t*)L.totals, gen);
+        if ((e = hipMemsetAsync(L.escapes, 0, (size_t)count * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipEvent_t e0, e1;
+        e0 = e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_DRAWS, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        if (L.host_table) {
+            uint32_t ngen = 0;
+            if ((e = hipMemcpyAsync(&ngen, pass_count, sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
+            if ((e = hipStreamSynchronize(L.stream)) != hipSuccess) return e;
+            if ((e = L.host_table(L.user, L.first_generator + host_before, ngen, L.table, L.stream)) != hipSuccess) return e;
+            host_before += ngen;
+            hipLaunchKernelGGL(k_aop_total, dim3(1), dim3(1), 0, L.stream, L.running, pass_count, L.generators_out);
+        } else {
+            hipLaunchKernelGGL(k_aop_base, dim3(1), dim3(128), 0, L.stream, L.window, (unsigned long long)L.first_generator, L.running, pass_count, L.base_window,
+                               L.generators_out);
+            hipLaunchKernelGGL(k_aop_states, dim3((chunks + (uint32_t)kAopSuper - 1u) / (uint32_t)kAopSuper), dim3(64), 0, L.stream, (const int32_t*)L.base_window,
+                               L.stride_rows, pass_count, L.table);
+            hipLaunchKernelGGL(k_draws, dim3((chunks + 3u) / 4u), dim3(256), 0, L.stream, pass_count, chunks, L.table);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        const unsigned long long items = (unsigned long long)count * (unsigned long long)kAoProbes;
+        const unsigned pblocks = (unsigned)std::min<unsigned long long>((items + 255) / 256, (unsigned long long)L.persistent_blocks);
+        e0 = e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_AOP_PROBE, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        const auto probe = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), lds, L.stream, L.sc, (const HitRec*)gen, pass_count, (const int32_t*)L.table, L.escapes, L.stats);
+        };
+        if (MODE == MODE_BVH && !L.nearest_walks) {                                   // (hook 34: nearest-hit walks, same bytes)
+            if (L.stats) probe(k_aop_probe<MODE, EXTRA, true, true>); else probe(k_aop_probe<MODE, EXTRA, false, true>);
+        } else {
+            if (L.stats) probe(k_aop_probe<MODE, EXTRA, true, false>); else probe(k_aop_probe<MODE, EXTRA, false, false>);
+        }
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_aop_store, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)gen, pass_count, L.escapes, L.cache);
+        hipLaunchKernelGGL(k_aop_apply, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)recs, count, (const uint8_t*)L.cache, (const uint32_t*)L.index,
+                           (const uint32_t*)L.totals, (const uint32_t*)L.escapes, L.color ? L.color + first : nullptr, L.out ? L.out + first : nullptr,
+                           L.amount ? L.amount + first : nullptr);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_ao_points(const AoPointsLaunch& L) {
+    if (L.n <= 0) return hipSuccess;
+    if (L.pass <= 0 || L.pass > kAopMaxPass) return hipErrorInvalidValue;
+    const bool extra = L.sc.nextra > 0;
+    switch (L.mode) {
+        case MODE_REF: return extra ? launch_ao_points_t<MODE_REF, true>(L) : launch_ao_points_t<MODE_REF, false>(L);
+        case MODE_BRUTE: return extra ? launch_ao_points_t<MODE_BRUTE, true>(L) : launch_ao_points_t<MODE_BRUTE, false>(L);
+        case MODE_BVH: return extra ? launch_ao_points_t<MODE_BVH, true>(L) : launch_ao_points_t<MODE_BVH, false>(L);
+        default: return hipErrorInvalidValue;
+    }
+}
+size_t ao_points_table_bytes(int64_t pass) {
+    return (size_t)((pass + kAopChunkGens - 1) / kAopChunkGens) * (size_t)kAopChunkDraws * sizeof(int32_t);
+}
+
 size_t pipeline_counter_bytes() { return (size_t)kCounterWords * sizeof(unsigned int); }
 // 8x8-pixel tiles (one wave's work items) of the padded super-tile grid of a band, all sub-samples
 size_t pipeline_tile_items(int width, int rows, int n2) { return (size_t)xcd_tile_grid(width, rows) * (size_t)n2 * 4; }

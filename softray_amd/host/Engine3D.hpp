@@ -375,6 +375,30 @@ public:
         f.flags &= ~(uint32_t)SR_F_PRIMARY_STATS_ONLY;     // (the call has no primary rays: sr_last_ray_stats gets the shadow stage's counters)
         sr_check(sr_shadow_points(scene_, &f, n, pos, normal, color, out, coherent ? SR_POINTS_COHERENT : 0u));
     }
+    // AmbientOcclusionMethod's occlusion byte for n surface points of the caller, in input order (sr_ao_points): amount[i] = the byte, out[i] =
+    // color[i] (nullptr: 0xFFFFFFFF) modulated with it; either output may be nullptr, not both.  The root geometry, the seed and the cache
+    // switch (ambientOcclusionEnableCache) are those of the frame Render() would build for the first instance; rayTraceAmbientOcclusion is
+    // implied, the cache is the one the renderer's AO frames fill.  Generator g of the call uses draws 300 (firstGenerator + g) .. + 299 of the
+    // frame's Random; returns the number of generators, which a caller that splits a batch adds to firstGenerator of the next call.
+    // Static shadows, path tracing, voxels, the light field and mirror bounces are refused by the library, by name.  Returns 0 without a
+    // model or points
+    uint64_t AmbientOcclusionPoints(int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, uint8_t* amount,
+                                    uint64_t firstGenerator = 0) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel() || n == 0) return 0;
+        if (Instances.empty()) throw InvalidOperationException("AmbientOcclusionPoints: no instance to take the pose from");
+        Instance& inst = *Instances.front();
+        inst.FieldOfViewDepth = fieldOfViewDepth_;
+        PreCalculate();
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_frame f = BuildFrame(inst);
+        f.flags &= ~(uint32_t)(SR_F_PRIMARY_STATS_ONLY | SR_F_AO_UNCACHED);     // (the call has no primary rays: sr_last_ray_stats gets the probes' counters)
+        if (!ambientOcclusionEnableCache) f.flags |= SR_F_AO_UNCACHED;          // (BuildFrame sets it for rayTraceAmbientOcclusion frames only)
+        uint64_t generators = 0;
+        sr_check(sr_ao_points(scene_, &f, n, pos, normal, color, out, amount, firstGenerator, 0u, &generators));
+        return generators;
+    }
     // The frame G-buffer (sr_render_hits): what the primary stage of the frame Render() would build for the first instance answers per camera
     // sample, before any decorator, in scan order ((row - first row) * width + col) * n^2 + subX * n + subY.  Every array has
     // RenderHitsSamples() entries ([S][3] doubles, [S] scalars) and may be nullptr; a miss is hit 0, zeros and triangle -1.  The decorator

@@ -399,6 +399,35 @@ class GpuScene:
         _check(_lib.lib().sr_shadow_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out),
                                                   _lib.POINTS_COHERENT if coherent else 0, vp(st), vp(d_stats_ptr)))
 
+    def ao_points(self, frame, pos, normal, color=None, first_generator=0, want_out=True, want_amount=True):
+        """AmbientOcclusionMethod's step for caller-given surface points, in input order (sr_ao_points): (out uint32 [n] or None, amount
+        uint8 [n] or None, generators).  Cached in the scene's AO cache unless the frame has F_AO_UNCACHED; generator g of the call uses
+        draws 300 (first_generator + g) .. + 299 of Random(frame.random_seed).  color None: every point 0xFFFFFFFF."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+        if normal.shape[0] != pos.shape[0]:
+            raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
+        if color is not None:
+            color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
+            if color.size != pos.shape[0]:
+                raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
+        out = np.zeros(pos.shape[0], dtype=np.uint32) if want_out else None
+        amount = np.zeros(pos.shape[0], dtype=np.uint8) if want_amount else None
+        made = C.c_uint64(0)
+        _check(_lib.lib().sr_ao_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out), _p(amount),
+                                       int(first_generator), 0, C.byref(made)))
+        return out, amount, int(made.value)
+
+    def ao_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, d_amount, first_generator=0, stream=0, d_generators_ptr=None,
+                         d_stats_ptr=None):
+        """sr_ao_points_device: every array is a DEVICE pointer (d_color 0 / None: every point 0xFFFFFFFF; d_out may be d_color; one of d_out /
+        d_amount may be 0 / None; d_generators_ptr: a device uint64 or None); enqueued on `stream` (a raw hipStream_t or a
+        torch.cuda.Stream), no host sync."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = getattr(stream, "cuda_stream", stream)
+        _check(_lib.lib().sr_ao_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out), vp(d_amount),
+                                              int(first_generator), 0, vp(st), vp(d_generators_ptr), vp(d_stats_ptr)))
+
     def shade_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, stream=0):
         """sr_shade_points_device: every array is a DEVICE pointer; enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
         vp = lambda x: C.c_void_p(x) if x else None
@@ -480,6 +509,13 @@ def rccl_unique_id():
     buf = (C.c_uint8 * _lib.RCCL_ID_BYTES)()
     _check(_lib.lib().sr_rccl_unique_id(buf))
     return bytes(buf)
+
+
+def net_random_jump(seed, skip):
+    """The next 55 InternalSample() values of System.Random(seed) after `skip` draws, by the jump-ahead (sr_net_random_jump): int32 [55]."""
+    out = np.zeros(55, dtype=np.int32)
+    _check(_lib.lib().sr_net_random_jump(int(seed), int(skip), _p(out)))
+    return out
 
 
 def net_random_doubles(seed, n, skip=0):

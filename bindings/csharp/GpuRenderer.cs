@@ -107,6 +107,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_ao_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, [Out] byte[] amount, ulong firstGenerator, uint options, out ulong generators);
         [DllImport(Lib)] public static extern int sr_ao_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr dAmount, ulong firstGenerator, uint options, IntPtr hipStream, IntPtr dGenerators, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_net_random_jump(int seed, ulong skip, [Out] int[] out55);
+        [DllImport(Lib)] public static extern int sr_path_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, [Out] uint[] incoming, [Out] double[] dirs, ulong firstSample, uint options);
+        [DllImport(Lib)] public static extern int sr_path_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr dIncoming, IntPtr dDirs, ulong firstSample, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_shadow_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_shade_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr hipStream);
         [DllImport(Lib)] public static extern long sr_frame_sample_count(ref SrFrame frame);
@@ -458,6 +460,44 @@ namespace Engine3D.Hip
                       1.0, 1.0, 0.0, 0.0, 0.0, new Vector(0, 0, 1), new Vector(0, 0, 0), 4);
             frame.flags &= ~F_PRIMARY_STATS_ONLY;
             Native.Check(Native.sr_ao_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, dAmount, firstGenerator, 0, stream, dGenerators, dStats));
+        }
+
+        /// PathTracingMethod's one-bounce diffuse term for caller-given surface points, in input order (sr_path_points; PathTracingMethod.cs:51-76):
+        /// point i fires one second ray from pos[i] + normal[i] * 0.001 in the direction made of draws 3 (firstSample + i) .. + 2 of
+        /// Random(randomSeed); incoming[i] = that hit's colour (0 on a miss; with F_SHADING shaded as a frame shades it, with fieldOfViewDepth,
+        /// ambient, shininess and the lights given here -- the values Render() and ShadePointsDevice take), result[i] = incoming * (normal . d) +
+        /// color[i] (color == null: 0xFFFFFFFF), dirs = the directions (double[n * 3]).  A caller that splits a batch passes firstSample + n to
+        /// the next call; averaging several rounds is the caller's loop over firstSample.  F_PATH_TRACING is implied.  pos / normal:
+        /// double[n * 3] in model space, the normal as given.  F_SHADOWS, F_AMBIENT_OCCLUSION, F_VOXELS and F_LIGHT_FIELD: SR_ERR_UNSUPPORTED ->
+        /// InvalidOperationException.  Blocks.
+        public uint[] PathPoints(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode, int randomSeed,
+                                 double fieldOfViewDepth, double ambient, double shininess, Vector lightDirView, Vector lightPosView,
+                                 double[] pos, double[] normal, uint[] color, out uint[] incoming, out double[] dirs, ulong firstSample = 0)
+        {
+            if (pos == null || normal == null || pos.Length != normal.Length || pos.Length % 3 != 0 || (color != null && color.Length != pos.Length / 3))
+                throw new ArgumentException("PathPoints: pos and normal are double[n * 3], color is uint[n] or null");
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, 0, height - 1, 1, randomSeed,
+                      fieldOfViewDepth, 1.0, 0.0, ambient, shininess, lightDirView, lightPosView, 4);
+            frame.flags &= ~F_PRIMARY_STATS_ONLY;                  // the call has no primary rays
+            var result = new uint[pos.Length / 3];
+            incoming = new uint[pos.Length / 3];
+            dirs = new double[pos.Length];
+            Native.Check(Native.sr_path_points(scene, ref frame, result.Length, pos, normal, color, result, incoming, dirs, firstSample, 0));
+            return result;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_path_points_device): enqueued on `stream` without a host
+        /// synchronisation; dColor may be IntPtr.Zero (every point 0xFFFFFFFF) or dOut itself; dOut, dIncoming and dDirs may each be
+        /// IntPtr.Zero, not all three; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void PathPointsDevice(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode, int randomSeed,
+                                     double fieldOfViewDepth, double ambient, double shininess, Vector lightDirView, Vector lightPosView,
+                                     long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr dIncoming, IntPtr dDirs, ulong firstSample,
+                                     IntPtr stream, IntPtr dStats)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, 0, height - 1, 1, randomSeed,
+                      fieldOfViewDepth, 1.0, 0.0, ambient, shininess, lightDirView, lightPosView, 4);
+            frame.flags &= ~F_PRIMARY_STATS_ONLY;
+            Native.Check(Native.sr_path_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, dIncoming, dDirs, firstSample, 0, stream, dStats));
         }
 
         /// The frame G-buffer (sr_render_hits): the arrays a caller wants of one frame's primary hits

@@ -614,6 +614,44 @@ int  sr_ao_points_device(sr_scene*, const sr_frame* frame, int64_t n, const doub
  * lies outside [0, 2^31 - 2] and the generator is not that recurrence (no such seed is known; sr_ao_points then draws on the host) */
 int  sr_net_random_jump(int32_t seed, uint64_t skip, int32_t out[55]);
 
+/* PathTracingMethod.IntersectRay's step in batch (PathTracingMethod.cs:51-76; Renderer.cs:1606-1638 puts it between shading and shadows): the
+ * one-bounce diffuse term of n caller-given surface points -- what the decorator leaves when it is applied to the n intersections IN INPUT
+ * ORDER by one RenderContext whose Random is Random(frame->random_seed) advanced by 3 * first_sample draws.  Point i uses draws
+ * 3 (first_sample + i) .. + 2 (every point is a hit): u = InternalSample * (1.0 / 2147483647.0), d = (2 u0 - 1, 2 u1 - 1, 2 u2 - 1), negated
+ * when d . normal[i] < 0.0, then multiplied by 1 / length; dirs[i] = d.  The second ray goes from pos[i] + normal[i] * 0.001 along d through
+ * the frame's root geometry (the extra geometry plus the model in trace_mode); incoming[i] = that hit's colour, shaded with the frame's
+ * transform and lights when SR_F_SHADING is set, 0 (Color.Black) on a miss; out[i], per channel, = incoming / 255.0 * (normal[i] . d) +
+ * color[i] / 255.0, all three scaled by 1 / sqrt(r^2 + g^2 + b^2) when one exceeds 1.0, stored as 0xFF000000 | (byte)(r * 255) << 16 | ...
+ * (truncating; NaN gives 0).  FP64 without contraction, in a path-traced frame's operand order.  color[i] is used as given (a caller who
+ * wants the frame's result shades it first: sr_shade_points); color == NULL: every point is 0xFFFFFFFF; out may alias color.  The normal is
+ * used as given (not normalised, no facing test; zero is legal).  out, incoming and dirs are each optional, but not all NULL with n > 0;
+ * with only dirs asked for nothing is traced.  A split batch continues the sequence bit for bit: the next call passes first_sample + n;
+ * averaging several rounds is the caller's loop over first_sample.
+ * A second-ray origin that is not finite never reaches a walk: a NaN component -- no hit; an infinite component -- no model triangle
+ * answers, the extra primitives are asked with the reference's arithmetic.  The colour step then runs on whatever IEEE gives (a NaN normal
+ * on a miss: 0xFF000000).
+ * Read from `frame`: random_seed, trace_mode, SR_F_SHADING and everything sr_shade_points reads when it is set, SR_F_PRIMARY_STATS_ONLY;
+ * SR_F_PATH_TRACING is implied; concurrency is not read (a batch is one block); the camera fields are validated as for a frame and
+ * otherwise unused.
+ * Refused, in this order: n < 0, a NULL pos / normal with n > 0, all three outputs NULL with n > 0, a NULL scene or frame, options != 0
+ * (reserved), first_sample + n > 2^40: SR_ERR_INVALID_ARG; SR_F_SHADOWS (dynamic or static), SR_F_AMBIENT_OCCLUSION, SR_F_VOXELS,
+ * SR_F_LIGHT_FIELD, SR_F_SINGLE_KERNEL, max_bounces > 0, strip_count > 0: SR_ERR_UNSUPPORTED; then sr_render's validation of the frame and
+ * its trace mode; then a host-only scene: SR_ERR_NO_DEVICE.  n == 0 that passes these checks: SR_OK, nothing is touched.
+ * Ordered like a frame (behind a frame of the scene in flight on any stream, the next frame behind it), on the scene's scratch, in passes
+ * of at most 2^22 points (SR_DBG_BAND_SAMPLES: fewer) that follow each other without the host waiting: the host knows where every pass
+ * starts in the sequence and jumps there (sr_net_random_jump), the draws themselves are made on the device.  (A seed for which
+ * sr_net_random_jump answers SR_ERR_UNSUPPORTED -- none is known -- draws on the host, one draw after the other from the seed on, and waits
+ * once per pass; first_sample + n > 2^30 is then SR_ERR_UNSUPPORTED.)  A multi-device scene runs it
+ * on devices[0].  The host variant stages, blocks and fills sr_last_ray_stats; the device variant takes device arrays, enqueues on
+ * `hip_stream` without a host synchronisation and writes the counters to d_stats when given.  Statistics: [0..3] 0, [4..7] (and [20..23]
+ * in SR_MODE_BVH) what a path-traced frame counts for the second rays of the same points; all 0 with SR_F_PRIMARY_STATS_ONLY. */
+int  sr_path_points(sr_scene*, const sr_frame* frame, int64_t n, const double* pos, const double* normal, const uint32_t* color /* or NULL */,
+                    uint32_t* out /* or NULL */, uint32_t* incoming /* or NULL */, double* dirs /* [n][3] or NULL */, uint64_t first_sample,
+                    uint32_t options);
+int  sr_path_points_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color,
+                           uint32_t* d_out, uint32_t* d_incoming, double* d_dirs, uint64_t first_sample, uint32_t options, void* hip_stream,
+                           uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* The same step with every array in DEVICE memory on the scene's device (a multi-device scene: devices[0]), enqueued on `hip_stream` without
  * a host synchronisation and without the staging copies.  Validation as sr_shade_points; n == 0: SR_OK. */
 int  sr_shade_points_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color,
@@ -754,7 +792,7 @@ int  sr_anti_alias_device(sr_scene*, const void* d_src, int32_t dst_width, int32
 enum {
     SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
                                     per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) and the
-                                    points per pass of sr_shadow_points (default 2^22) and of sr_ao_points (default and limit 2^17) */
+                                    points per pass of sr_shadow_points (default 2^22), of sr_ao_points (default and limit 2^17) and of sr_path_points (default and limit 2^22) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
     SR_DBG_SPLIT          = 3,   /* concurrent part-frame pipelines (default 2, <= 4)                                          */
@@ -771,7 +809,7 @@ enum {
                                     packet shaft walk instead of private per-lane shaft walks (same table; measured slower); 37 sr_shadow_points queues a pass in input
                                     order whatever the options say (no ray sort); 38 sr_shadow_points runs the first shaft round with private per-lane walks instead of the
                                     packet walk (both: same output); 44 sr_ao_points makes every pass's draw table on the host, one draw after the
-                                    other, and waits once per pass (same output; cross-check and baseline); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    other, and waits once per pass (same output; cross-check and baseline); 45 sr_path_points does the same, and then refuses first_sample + n > 2^30 with SR_ERR_UNSUPPORTED: the host draws its way to first_sample; 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
                                     fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid

@@ -51,6 +51,7 @@ SYMBOLS = [
     "sr_set_light_field_triangles", "sr_get_light_field_triangles", "sr_get_light_field_tris", "sr_set_light_field_tris", "sr_tree_handle_leaf",
     "sr_frame_sample_count", "sr_render_hits", "sr_render_hits_device", "sr_shade_points_device",
     "sr_ao_points", "sr_ao_points_device", "sr_net_random_jump",
+    "sr_path_points", "sr_path_points_device",
 ]
 POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 GATHER_COPY, GATHER_RCCL = 0, 1
@@ -169,6 +170,8 @@ def lib():
     L.sr_ao_points.restype = i32; L.sr_ao_points.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp]
     L.sr_ao_points_device.restype = i32; L.sr_ao_points_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp]
     L.sr_net_random_jump.restype = i32; L.sr_net_random_jump.argtypes = [i32, C.c_uint64, vp]
+    L.sr_path_points.restype = i32; L.sr_path_points.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32]
+    L.sr_path_points_device.restype = i32; L.sr_path_points_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]
     L.sr_trace_rays_device.restype = i32; L.sr_trace_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sr_rccl_unique_id.restype = i32; L.sr_rccl_unique_id.argtypes = [vp]
     L.sr_rccl_init.restype = i32; L.sr_rccl_init.argtypes = [vp, vp, i32, i32]

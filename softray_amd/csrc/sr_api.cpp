@@ -138,6 +138,7 @@ struct sr_scene {
     DBuf d_ao_cache, d_ao_claim;
     // sr_ao_points: a pass's draw table, the jump coefficients of its chunk strides (uploaded once) and the call's words of device state
     DBuf d_aop_table, d_aop_rows, d_aop_state;
+    DBuf d_pp_state;                     // sr_path_points: a pass's window, table size and ray counters
     bool aop_rows_ready = false;
     std::unique_ptr<sr::NetRandom> aop_host_random;   // (host tables) the Random of the call being enqueued, at ...
     uint64_t aop_host_drawn = 0;                      // ... this many generators
@@ -1763,7 +1764,7 @@ void sr_destroy(sr_scene* s) {
     }
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         DBuf* bufs[] = {&s->d_tris, &s->d_extra, &s->d_rnodes, &s->d_rboxes, &s->d_rleaf, &s->d_bnodes, &s->d_btris, &s->d_bslab, &s->d_binter,
-                        &s->d_v9, &s->d_bcam, &s->d_blight, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_aop_table, &s->d_aop_rows, &s->d_aop_state, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_lft_cache, &s->d_lft_claim, &s->d_rhandle, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
+                        &s->d_v9, &s->d_bcam, &s->d_blight, &s->d_b4, &s->d_b4cam, &s->d_b4light, &s->d_rng_cam, &s->d_rng_light, &s->d_shadow_cache, &s->d_static_claim, &s->d_static_hits, &s->d_ao_cache, &s->d_ao_claim, &s->d_aop_table, &s->d_aop_rows, &s->d_aop_state, &s->d_pp_state, &s->d_lf_cache, &s->d_lf_claim, &s->d_lf_points, &s->d_lft_cache, &s->d_lft_claim, &s->d_rhandle, &s->d_pt_table, &s->d_pt_row_hits, &s->d_pt_row_k0, &s->d_pixels, &s->d_aa, &s->d_stats,
                         &s->d_vox_colors, &s->d_vox_normals, &s->d_vox_mask, &s->d_vox_bricks, &s->d_vox_coarse, &s->d_bounds, &s->d_bdepth, &s->d_tbox};
         for (DBuf* b : bufs) b->release();
         for (auto& sc : s->scratch) sc.release();
@@ -3107,6 +3108,22 @@ static int ao_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const voi
     return check_frame_mode(s, &fs);
 }
 
+// the jump coefficients of the table kernels' chunk strides (k_aop_states), uploaded once per scene
+static int ensure_aop_rows(sr_scene* s) {
+    if (s->aop_rows_ready) return SR_OK;
+    // entry [j][i] = coefficient j of x^(stride + i): the 55 lanes of a product read consecutive words
+    std::vector<uint32_t> rows((size_t)2 * 55 * 55), t((size_t)55 * 55);
+    const uint64_t strides[2] = {64ull * 300ull, 64ull * 64ull * 300ull};
+    for (int k = 0; k < 2; ++k) {
+        sr::net_jump_rows(strides[k], t.data());
+        for (int i = 0; i < 55; ++i)
+            for (int j = 0; j < 55; ++j) rows[(size_t)k * 55 * 55 + (size_t)j * 55 + i] = t[(size_t)i * 55 + j];
+    }
+    SR_HIP(s->d_aop_rows.upload(rows));
+    s->aop_rows_ready = true;
+    return SR_OK;
+}
+
 struct AoPtsReq { int64_t n; const double* pos; const double* nrm; const uint32_t* color; uint32_t* out; uint8_t* amount; uint64_t first_generator; unsigned long long* generators; };
 
 // the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set
@@ -3117,18 +3134,7 @@ static int ao_points_common(sr_scene* s, const sr_frame* f, const AoPtsReq& q, h
     sr::AoPointsLaunch L{};
     bool host_table = s->dbg[SR_DBG_KERNEL_SWITCH] == 44;
     if (!host_table && !sr::net_random_window(f->random_seed, L.window.s)) host_table = true;   // (not the recurrence for this seed: sr_host.h)
-    if (!host_table && !s->aop_rows_ready) {
-        // entry [j][i] = coefficient j of x^(stride + i): the 55 lanes of a product read consecutive words
-        std::vector<uint32_t> rows((size_t)2 * 55 * 55), t((size_t)55 * 55);
-        const uint64_t strides[2] = {64ull * 300ull, 64ull * 64ull * 300ull};
-        for (int k = 0; k < 2; ++k) {
-            sr::net_jump_rows(strides[k], t.data());
-            for (int i = 0; i < 55; ++i)
-                for (int j = 0; j < 55; ++j) rows[(size_t)k * 55 * 55 + (size_t)j * 55 + i] = t[(size_t)i * 55 + j];
-        }
-        SR_HIP(s->d_aop_rows.upload(rows));
-        s->aop_rows_ready = true;
-    }
+    if (!host_table && (rc = ensure_aop_rows(s))) return rc;
     // ---- ordered like a frame (render_common) ----
     if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
     struct MarkPreUsed {
@@ -3260,6 +3266,185 @@ int sr_ao_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos, c
     SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     SR_HIP(hipStreamSynchronize(stream));
     if (generators) *generators = made;
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    return SR_OK;
+}
+
+// ---- sr_path_points ----
+const uint64_t kPathPointsMaxSamples = 1ull << 40;
+const uint64_t kPathPointsHostTableSamples = 1ull << 30;     // ... where the host makes the table: it draws its way there
+// what sr_path_points[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the first
+// part of a multi-device scene), `fs`: the frame with SR_F_PATH_TRACING implied
+static int path_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* pos, const void* normal, const void* out, const void* incoming,
+                             const void* dirs, uint64_t first_sample, uint32_t options, sr_frame& fs) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (n < 0 || (n > 0 && (!pos || !normal)) || (n > 0 && !out && !incoming && !dirs) || !s || !f || options != 0 ||
+        first_sample > kPathPointsMaxSamples || (uint64_t)n > kPathPointsMaxSamples - first_sample)
+        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_path_points");
+    if (f->flags & SR_F_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: shadows (SR_F_SHADOWS, dynamic or static) are ShadowMethod's step, which follows this one: sr_shadow_points");
+    if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is AmbientOcclusionMethod's step, which follows this one: sr_ao_points");
+    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: voxel rendering (SR_F_VOXELS) has no surface point to bounce from");
+    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter");
+    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point");
+    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points");
+    fs = *f;
+    fs.flags |= SR_F_PATH_TRACING;
+    int rc = validate_frame(&fs, s);
+    if (rc) return rc;
+    return check_frame_mode(s, &fs);
+}
+
+struct PathPtsReq { int64_t n; const double* pos; const double* nrm; const uint32_t* color; uint32_t* out; uint32_t* incoming; double* dirs; uint64_t first_sample; };
+
+// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set
+static int path_points_common(sr_scene* s, const sr_frame* f, const PathPtsReq& q, hipStream_t stream, unsigned long long* d_stats) {
+    int rc = sync_geometry(s, (uint32_t)f->trace_mode);
+    if (rc) return rc;
+    sr::PathPointsLaunch L{};
+    if ((rc = prepare_frame(s, f, L.fc))) return rc;
+    const bool trace = q.out || q.incoming;
+    const bool walked = trace && f->trace_mode == SR_MODE_BVH;
+    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kPpMaxPass) : sr::kPpMaxPass;
+    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, q.n));
+    // the window every pass starts from, by the jump-ahead: the host knows where each pass lies in the sequence
+    int32_t window[sr::kNetWindow];
+    bool host_table = s->dbg[SR_DBG_KERNEL_SWITCH] == 45;
+    if (!host_table && !sr::net_random_window(f->random_seed, window)) host_table = true;   // (not the recurrence for this seed: sr_host.h)
+    // (the host walks through every draw before the call's: a path for cross-checks, with a limit -- about ten seconds of drawing)
+    if (host_table && q.first_sample + (uint64_t)q.n > kPathPointsHostTableSamples)
+        return fail(SR_ERR_UNSUPPORTED, "sr_path_points: the draw table made on the host (SR_DBG_KERNEL_SWITCH 45, or a seed the jump-ahead does not cover) is limited to first_sample + n <= 2^30");
+    std::vector<sr::NetState> windows;
+    if (!host_table) {
+        if ((rc = ensure_aop_rows(s))) return rc;
+        windows.resize((size_t)((q.n + pass - 1) / pass));
+        for (size_t p = 0; p < windows.size(); ++p) {
+            uint32_t c[sr::kNetLag];
+            sr::net_jump_poly(3ull * (q.first_sample + (uint64_t)p * (uint64_t)pass), c);
+            sr::net_jump_apply(window, c, windows[p].s);
+        }
+    }
+    // ---- ordered like a frame (render_common) ----
+    if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
+    struct MarkPreUsed {
+        sr_scene* s; hipStream_t st;
+        ~MarkPreUsed() {
+            if (!s->pre_used && hipEventCreateWithFlags(&s->pre_used, hipEventDisableTiming) != hipSuccess) return;
+            if (hipEventRecord(s->pre_used, st) == hipSuccess) s->pre_used_set = true;
+        }
+    } mark_pre_used{s, stream};
+    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
+    if (!s->num_cus) {
+        hipDeviceProp_t prop;
+        SR_HIP(hipGetDeviceProperties(&prop, s->device));
+        s->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    sr_scene::BandScratch& B = s->scratch[0];                        // (sr_debug_counters keeps describing the last frame: the call has counters of its own)
+    const size_t slots = (size_t)(pass + 255) / 256 * 256;
+    if (trace) SR_HIP(B.hits2.reserve(slots * sr::pipeline_hit_record_bytes()));
+    if (walked) {
+        // the scratch of a SR_MODE_BVH frame's second rays (render_common)
+        SR_HIP(B.bounce_prep.reserve(slots * 64));
+        SR_HIP(B.bounce_res.reserve(slots * 16));
+        const long long deep = std::max(3 * (long long)s->b4_depth + 2, (long long)s->bvh.depth + 2) - sr::pipeline_bounce_lds_levels();
+        if (deep > 0) SR_HIP(B.bounce_stack.reserve((size_t)deep * (size_t)s->num_cus * 8 * 256 * 4));
+        SR_HIP(B.ray_sort.reserve(slots * 4 * 4));
+        SR_HIP(B.ray_sort_temp.reserve(sr::ray_sort_temp_bytes((unsigned)pass)));
+    }
+    SR_HIP(s->d_aop_table.reserve(sr::path_points_table_bytes(pass)));
+    SR_HIP(s->d_pp_state.reserve(512));
+    L.sc = dev_scene(s);
+    L.mode = f->trace_mode;
+    L.n = q.n; L.pass = pass;
+    L.pos = q.pos; L.nrm = q.nrm; L.color = q.color; L.out = q.out; L.incoming = q.incoming; L.dirs = q.dirs;
+    L.first_sample = q.first_sample;
+    L.rays = trace ? B.hits2.p : nullptr;
+    L.table = (int32_t*)s->d_aop_table.p;
+    L.windows = host_table ? nullptr : windows.data();
+    L.stride_rows = (const uint32_t*)s->d_aop_rows.p;
+    L.base_window = (int32_t*)s->d_pp_state.p;
+    L.pass_units = (uint32_t*)((char*)s->d_pp_state.p + 256);
+    L.counters = (unsigned int*)((char*)s->d_pp_state.p + 272);
+    L.ray_sort_buf = walked ? (unsigned int*)B.ray_sort.p : nullptr;
+    L.ray_sort_temp = walked ? B.ray_sort_temp.p : nullptr;
+    L.ray_sort_temp_bytes = walked ? sr::ray_sort_temp_bytes((unsigned)pass) : 0;
+    L.bounce_prep = walked ? B.bounce_prep.p : nullptr;
+    L.bounce_res = walked ? B.bounce_res.p : nullptr;
+    L.bounce_stack = walked ? (int32_t*)B.bounce_stack.p : nullptr;
+    L.bounce_stack_bytes = walked ? B.bounce_stack.cap : 0;
+    L.bvh2_packets = s->dbg[SR_DBG_BVH2_PACKETS] > 0;
+    L.stats = (f->flags & SR_F_PRIMARY_STATS_ONLY) ? nullptr : d_stats;
+    L.persistent_blocks = s->num_cus * 8;
+    L.stream = stream;
+    L.user = s;
+    L.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
+        hipEvent_t x = nullptr, y = nullptr;
+        if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
+        *a = x; *b = y;
+    };
+    if (host_table) {
+        // System.Random itself, one draw after the other, from the call's first sample on (the passes ask in ascending order)
+        s->aop_host_random.reset(new sr::NetRandom(f->random_seed));
+        for (uint64_t i = 0; i < q.first_sample * 3ull; ++i) (void)s->aop_host_random->next();
+        s->aop_host_drawn = q.first_sample;
+        L.host_table = [](void* user, uint64_t base, uint32_t count, int32_t* d_table, hipStream_t st) -> hipError_t {
+            sr_scene* sc = (sr_scene*)user;
+            if (base != sc->aop_host_drawn) return hipErrorInvalidValue;
+            std::vector<int32_t> ints((size_t)count * 3);
+            for (int32_t& v : ints) v = sc->aop_host_random->next();
+            sc->aop_host_drawn += count;
+            hipError_t e = hipMemcpyAsync(d_table, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) return e;
+            return hipStreamSynchronize(st);                           // (`ints` leaves scope)
+        };
+    }
+    const hipError_t pe = sr::launch_path_points(L);
+    s->aop_host_random.reset();
+    SR_HIP(pe);
+    return SR_OK;
+}
+
+int sr_path_points_device(sr_scene* m, const sr_frame* f, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color, uint32_t* d_out,
+                          uint32_t* d_incoming, double* d_dirs, uint64_t first_sample, uint32_t options, void* hip_stream, uint64_t* d_stats) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = path_points_check(s, f, n, d_pos, d_normal, d_out, d_incoming, d_dirs, first_sample, options, fs);
+    if (rc) return rc;
+    if (n == 0) return SR_OK;
+    if ((rc = use_device(s))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    const PathPtsReq req{n, d_pos, d_normal, d_color, d_out, d_incoming, d_dirs, first_sample};
+    return path_points_common(s, &fs, req, stream, (unsigned long long*)d_stats);
+}
+
+int sr_path_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out,
+                   uint32_t* incoming, double* dirs, uint64_t first_sample, uint32_t options) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = path_points_check(s, f, n, pos, normal, out, incoming, dirs, first_sample, options, fs);
+    if (rc) return rc;
+    if (n == 0) return SR_OK;
+    if ((rc = use_device(s))) return rc;
+    if ((rc = ensure_io_streams(s))) return rc;
+    hipStream_t stream = s->io_stream;
+    const size_t sizes[5] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n * 4, (size_t)n * 24};
+    const bool used[5] = {true, true, color || out, incoming != nullptr, dirs != nullptr};
+    for (int i = 0; i < 5; ++i) if (used[i]) SR_HIP(s->d_io[i].reserve(sizes[i]));
+    SR_HIP(hipMemcpy(s->d_io[0].p, pos, sizes[0], hipMemcpyHostToDevice));
+    SR_HIP(hipMemcpy(s->d_io[1].p, normal, sizes[1], hipMemcpyHostToDevice));
+    if (color) SR_HIP(hipMemcpy(s->d_io[2].p, color, sizes[2], hipMemcpyHostToDevice));
+    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
+    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    // (the colours are finished where they lie: the device variant's `out` aliasing `color`)
+    const PathPtsReq req{n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, color ? (const uint32_t*)s->d_io[2].p : nullptr,
+                         out ? (uint32_t*)s->d_io[2].p : nullptr, incoming ? (uint32_t*)s->d_io[3].p : nullptr, dirs ? (double*)s->d_io[4].p : nullptr, first_sample};
+    if ((rc = path_points_common(s, &fs, req, stream, (unsigned long long*)s->d_stats.p))) { (void)hipStreamSynchronize(stream); return rc; }
+    if (out) SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
+    if (incoming) SR_HIP(hipMemcpyAsync(incoming, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost, stream));
+    if (dirs) SR_HIP(hipMemcpyAsync(dirs, s->d_io[4].p, sizes[4], hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
     if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
     return SR_OK;
 }

@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_COUNT = 38 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_COUNT = 39 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -271,6 +271,47 @@ struct AoPointsLaunch {
 };
 hipError_t launch_ao_points(const AoPointsLaunch& L);
 size_t ao_points_table_bytes(int64_t pass);
+// sr_path_points (sr_pipeline.hip k_pp_ingest): n caller-given surface points through PathTracingMethod's step in passes of `pass` points
+constexpr int64_t kPpMaxPass = 1ll << 22;      // 2^22 points: a 48 MiB draw table, 256 MiB of ray records
+struct NetState { int32_t s[55]; };             // 55 consecutive InternalSample() values of a Random: all a jump-ahead needs to go on from
+struct PathPointsLaunch {
+    DevScene    sc;
+    FrameConst  fc;             // shading of the second hit (SR_F_SHADING: transform and lights)
+    int32_t     mode;
+    int64_t     n, pass;
+    const double* pos;          // device [n][3], model space
+    const double* nrm;          // device [n][3], as given
+    const uint32_t* color;      // device [n] or nullptr (every point 0xFFFFFFFF); may be `out`
+    uint32_t*   out;            // device [n] or nullptr
+    uint32_t*   incoming;       // device [n] or nullptr
+    double*     dirs;           // device [n][3] or nullptr
+    uint64_t    first_sample;
+    void*       rays;           // device HitRec[pass]: the pass's second rays (unused when only `dirs` is asked for)
+    int32_t*    table;          // device, path_points_table_bytes(pass): the pass's draws, 3 per point
+    const NetState* windows;    // HOST, one per pass: the draws 3 (first_sample + pass start) .. + 54 (nullptr with host_table)
+    const uint32_t* stride_rows; // device [2][55][55]: the jump coefficients of one chunk and of 64 chunks (as AoPointsLaunch)
+    int32_t*    base_window;    // device [55]
+    uint32_t*   pass_units;     // device: the 300-draw units of the pass's table (what k_aop_states / k_draws call generators)
+    // not nullptr: the host makes every pass's table -- 3 `count` draws from draw 3 `first_point` on -- and the call waits once per pass
+    hipError_t (*host_table)(void* user, uint64_t first_point, uint32_t count, int32_t* d_table, hipStream_t stream);
+    // SR_MODE_BVH: the incoherent-ray route of a path-traced frame (PipelineLaunch's fields of the same names)
+    unsigned int* counters;     // device [4]: [0] the pass's rays, [2] the walk's work head
+    unsigned int* ray_sort_buf; // device [4 x pass]
+    void*       ray_sort_temp;
+    size_t      ray_sort_temp_bytes;
+    void*       bounce_prep;    // device [pass] x 64 B
+    void*       bounce_res;     // device [pass] x 16 B
+    int32_t*    bounce_stack;
+    size_t      bounce_stack_bytes;
+    bool        bvh2_packets;   // SR_DBG_BVH2_PACKETS: the walk on the two-wide tree, as a frame's
+    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [4..7] (SR_MODE_BVH: [20..23] too) += what the second rays count
+    int32_t     persistent_blocks;
+    hipStream_t stream;
+    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
+    void*       user;
+};
+hipError_t launch_path_points(const PathPointsLaunch& L);
+size_t path_points_table_bytes(int64_t pass);
 // per-frame pre-pass: a copy of the four-wide nodes with every node's children sorted by the distance of their box centres from
 // `point` (model space), nearest first (camera origin) or farthest first (light: nearest to the surface points first)
 // swap_mask (bit a): exchange lo and hi on axis a in the copy (the rays of the frame travel towards smaller coordinates there)

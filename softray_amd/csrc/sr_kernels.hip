@@ -157,6 +157,7 @@ const char* kernel_name(int id) {
         case K_AO_PROBE: return "k_ao_probe";
         case K_DRAWS: return "k_draws";                       // sr_ao_points: a pass's draw table (k_aop_base, k_aop_states, k_draws)
         case K_AOP_PROBE: return "k_aop_probe";               // ... its probes
+        case K_PP_TRACE: return "path_points_rays";           // sr_path_points: the second rays of a pass, all kernels from k_pp_ingest to k_pp_finish[_walked] (its table: k_draws)
         case K_LF_LOOKUP: return "k_lf_lookup";
         case K_LF_FILL: return "k_lf_fill";
         case K_LF_APPLY: return "k_lf_apply";

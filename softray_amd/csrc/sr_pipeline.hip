@@ -4256,6 +4256,166 @@ __global__ __launch_bounds__(256) void k_aop_apply(const HitRec* __restrict__ re
 }
 
 // --------------------------------------------------------------------------------------------------
+// sr_path_points: PathTracingMethod.IntersectRay's step (PathTracingMethod.cs:51-76) for caller-given surface points, applied in input
+// order by one RenderContext whose Random has made 3 * first_sample draws.  Every point is a hit, so point i of the call uses draws
+// 3 (first_sample + i) .. + 2 and nothing has to be counted: the host knows where every pass starts in the sequence, computes that window
+// with the jump-ahead (sr_host.h) and never waits.  Per pass of at most 2^22 points:
+//   k_pp_window       the pass's window and the size of its table, from the kernel arguments into device memory
+//   k_aop_states, k_draws    sr_ao_points' table kernels, unchanged: 3 draws per point are one "generator" of 300 draws per 100 points
+//   k_pp_ingest       lane = point: the three draws -> direction (k_pt_prep's arithmetic), offset origin, its class (finite / a NaN
+//                     component / an infinite one) -> the 64-byte record the walks consume; `dirs`.  With only `dirs` asked for, that is all
+//   SR_MODE_BVH       the second rays of a path-traced frame, on its route: ray_sort, k_bounce_prep, k_bounce_walk, then
+//   k_pp_finish_walked  k_pt_finish_walked's hit selection and colour step; own colour from color[i], results by the point's index
+//   other modes       k_pp_finish: per-lane root_intersect with the stacks in LDS, as k_pt_finish
+// An origin that is not finite never reaches a walk: a NaN component -- no hit; an infinite one -- no model triangle answers (its hit
+// point would be NaN), the extra primitives are asked with the literal path's arithmetic.  On the walked route such a ray's record holds a
+// stand-in origin outside the root box, heading away from it: k_bounce_prep clips it away (offset -1) and the finish kernel takes the
+// real origin from the caller's arrays.
+// --------------------------------------------------------------------------------------------------
+constexpr int kPpUnitPoints = kAoProbes;                                               // points per 300-draw unit of the table kernels
+
+__global__ __launch_bounds__(64) void k_pp_window(NetState w, uint32_t units, int32_t* __restrict__ base_window, uint32_t* __restrict__ pass_units) {
+    const int t = threadIdx.x;
+    if (t < 55) base_window[t] = w.s[t];
+    if (t == 0) *pass_units = units;
+}
+
+// PathTracingMethod.cs:65-71 -- incoming * frac + own colour; new Color(uint): bytes / 255.0; Normalise when a channel exceeds 1.0; ToARGB truncates
+__device__ __forceinline__ uint32_t pp_colour(uint32_t incoming, double frac, uint32_t own) {
+    double cr = (double)((incoming >> 16) & 0xffu) / 255.0 * frac + (double)((own >> 16) & 0xffu) / 255.0;
+    double cg = (double)((incoming >> 8) & 0xffu) / 255.0 * frac + (double)((own >> 8) & 0xffu) / 255.0;
+    double cb = (double)(incoming & 0xffu) / 255.0 * frac + (double)(own & 0xffu) / 255.0;
+    if (cr > 1.0 || cg > 1.0 || cb > 1.0) {
+        const double inv = 1.0 / sqrt(cr * cr + cg * cg + cb * cb);
+        cr *= inv; cg *= inv; cb *= inv;
+    }
+    return (255u << 24) + (to_byte(cr * 255.0) << 16) + (to_byte(cg * 255.0) << 8) + to_byte(cb * 255.0);
+}
+
+// WALKED: the record feeds ray_sort / k_bounce_prep (see above); `count` then receives the pass's ray count.  rays == nullptr: `dirs` alone
+template <bool WALKED>
+__global__ __launch_bounds__(256) void k_pp_ingest(const double* __restrict__ pos, const double* __restrict__ nrm, uint32_t n, const int32_t* __restrict__ table,
+                                                   double cx, double cy, double cz, double away, HitRec* __restrict__ rays, unsigned int* __restrict__ count,
+                                                   double* __restrict__ dirs) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (WALKED && i == 0u) *count = n;
+    if (i >= n) return;
+    // RandomRayInHemisphere (PathTracingMethod.cs:98-103); NextDouble() = InternalSample() * (1.0 / int.MaxValue)
+    const int32_t* u = table + (size_t)i * 3;
+    const double ux = u[0] * (1.0 / 2147483647.0), uy = u[1] * (1.0 / 2147483647.0), uz = u[2] * (1.0 / 2147483647.0);
+    const D3 nv = mk(nrm[(size_t)i * 3], nrm[(size_t)i * 3 + 1], nrm[(size_t)i * 3 + 2]);
+    D3 d = mk(ux * 2 - 1, uy * 2 - 1, uz * 2 - 1);
+    if (dot(d, nv) < 0.0) d = neg(d);
+    d = normalise(d);
+    if (dirs) { dirs[(size_t)i * 3] = d.x; dirs[(size_t)i * 3 + 1] = d.y; dirs[(size_t)i * 3 + 2] = d.z; }
+    if (!rays) return;
+    D3 org = mk(pos[(size_t)i * 3], pos[(size_t)i * 3 + 1], pos[(size_t)i * 3 + 2]) + nv * 0.001;     // raySurfaceOffset
+    const bool is_nan = org.x != org.x || org.y != org.y || org.z != org.z;
+    const double fin = (org.x - org.x) + (org.y - org.y) + (org.z - org.z);            // 0 for finite components, NaN otherwise
+    const uint32_t cls = is_nan ? kAopNan : (fin == 0.0 ? kAopFinite : kAopInf);
+    if (WALKED && cls != kAopFinite) org = mk(cx, cy, cz) + d * away;                  // outside the root box, heading away
+    HitRec o;
+    o.pos[0] = org.x; o.pos[1] = org.y; o.pos[2] = org.z;
+    o.nrm[0] = d.x; o.nrm[1] = d.y; o.nrm[2] = d.z;
+    o.sample = i;
+    o.pad[0] = o.pad[1] = 0u;
+    o.pad[2] = cls;
+    rays[i] = o;
+}
+
+// (LDS: the per-lane traversal stacks of root_intersect, stack levels x 256 lanes x 4 bytes, as k_pt_finish)
+// (`out` may be the colour array itself: neither is __restrict__)
+template <int MODE, bool EXTRA, bool STATS>
+__global__ __launch_bounds__(256) void k_pp_finish(DevScene sc, FrameConst fc, const HitRec* __restrict__ rays, uint32_t n, const double* __restrict__ nrm,
+                                                   const uint32_t* color, uint32_t* out, uint32_t* __restrict__ incoming_out, unsigned long long* stats) {
+    const int tid = threadIdx.x;
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    const unsigned int stride = gridDim.x * 256u;
+    Ctr sec = {0, 0, 0, 0};
+    for (unsigned int i = blockIdx.x * 256u + tid; i < n; i += stride) {
+        const HitRec q = rays[i];
+        const D3 s = mk(q.pos[0], q.pos[1], q.pos[2]), d = mk(q.nrm[0], q.nrm[1], q.nrm[2]);
+        Hit h;
+        bool ok = false;
+        sec.rays++;
+        if (q.pad[2] == kAopFinite) {
+            ok = root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, s, d, h, sec);
+        } else if (EXTRA && q.pad[2] == kAopInf) {
+            double best = DBL_MAX;
+            for (int e = 0; e < sc.nextra; ++e) {
+                const Rec128* r = &sc.extra[e];
+                double t; D3 pos, nr;
+                uint32_t tests;
+                const bool hit = extra_hit(r, s, d, t, pos, nr, tests);
+                sec.geom += tests;
+                if (hit && t < best) { best = t; ok = true; h.t = t; h.pos = pos; h.nrm = nr; h.color = r->color; h.tri = -1; }
+            }
+        }
+        uint32_t incoming = 0u;                                                       // Color.Black
+        if (ok) incoming = (fc.flags & 1u) ? shade(fc, h.pos, h.nrm, h.color) : h.color;
+        const D3 nv = mk(nrm[(size_t)i * 3], nrm[(size_t)i * 3 + 1], nrm[(size_t)i * 3 + 2]);
+        const double frac = dot(nv, d);                                               // BRDF: surfaceNormal.DotProduct(newRayDir)
+        if (incoming_out) incoming_out[i] = incoming;
+        if (out) out[i] = pp_colour(incoming, frac, color ? color[i] : 0xFFFFFFFFu);
+    }
+    if (STATS) {
+        uint32_t a = wave_sum(sec.rays), b = wave_sum(sec.geom), c2 = wave_sum(sec.nodes), d2 = wave_sum(sec.leaves);
+        if ((tid & 63) == 0) { stat_add(&stats[4], a); stat_add(&stats[5], b); stat_add(&stats[6], c2); stat_add(&stats[7], d2); }
+    }
+}
+
+// lane = ray in walk order; `order` (nullable) maps it to its point of the pass.  No LDS.
+template <bool EXTRA, bool STATS>
+__global__ __launch_bounds__(256) void k_pp_finish_walked(DevScene sc, FrameConst fc, const HitRec* __restrict__ rays, const unsigned int* __restrict__ count,
+                                                          const unsigned int* __restrict__ order, const BounceRay* __restrict__ prep, const BounceHit* __restrict__ res,
+                                                          const double* __restrict__ pos, const double* __restrict__ nrm, const uint32_t* color, uint32_t* out,
+                                                          uint32_t* __restrict__ incoming_out, unsigned long long* stats) {
+    const unsigned int total = *count, stride = gridDim.x * 256u;
+    uint32_t n_geom = 0;
+    for (unsigned int r = blockIdx.x * 256u + threadIdx.x; r < total; r += stride) {
+        const BounceRay p = prep[r];
+        const BounceHit h = res[r];
+        const unsigned int i = order ? order[r] : r;
+        const uint32_t cls = rays[i].pad[2];
+        const D3 s = mk(p.s[0], p.s[1], p.s[2]), d = mk(p.d[0], p.d[1], p.d[2]);
+        const D3 nv = mk(nrm[(size_t)i * 3], nrm[(size_t)i * 3 + 1], nrm[(size_t)i * 3 + 2]);
+        double ex_t = DBL_MAX;
+        D3 hpos = mk(0, 0, 0), hnrm = mk(0, 0, 0);
+        uint32_t hcol = 0;
+        bool hit = false;
+        if (EXTRA && cls != kAopNan) {
+            // the unclipped origin: the record's, or -- where the record holds the stand-in -- made again as k_pp_ingest made it
+            const D3 s0 = cls == kAopFinite ? mk(rays[i].pos[0], rays[i].pos[1], rays[i].pos[2])
+                                            : mk(pos[(size_t)i * 3], pos[(size_t)i * 3 + 1], pos[(size_t)i * 3 + 2]) + nv * 0.001;
+            for (int k = 0; k < sc.nextra; ++k) {
+                const Rec128* e = &sc.extra[k];
+                double t; D3 epos, enrm;
+                uint32_t tests;
+                const bool ok = extra_hit(e, s0, d, t, epos, enrm, tests);
+                n_geom += tests;
+                if (ok && t < ex_t) { ex_t = t; hpos = epos; hnrm = enrm; hcol = e->color; hit = true; }
+            }
+        }
+        if (cls == kAopFinite && p.offset >= 0.0 && h.bestK >= 0 && (h.best + p.offset) < ex_t) {
+            const Rec128* t = &sc.btris[h.bestK];
+            hit = true;
+            hpos = s + d * h.best;
+            hnrm = mk(t->p[0], t->p[1], t->p[2]);
+            hcol = t->color;
+        }
+        uint32_t incoming = 0u;
+        if (hit) incoming = (fc.flags & 1u) ? shade(fc, hpos, hnrm, hcol) : hcol;
+        const double frac = dot(nv, d);
+        if (incoming_out) incoming_out[i] = incoming;
+        if (out) out[i] = pp_colour(incoming, frac, color ? color[i] : 0xFFFFFFFFu);
+    }
+    if (STATS && EXTRA) {
+        const uint32_t b = wave_sum(n_geom);
+        if ((threadIdx.x & 63) == 0) { stat_add(&stats[5], b); stat_add(&stats[21], b); }
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // rayTraceLightField with LightFieldStoresTriangles = false (SR_F_LIGHT_FIELD; LightFieldColorMethod.cs:92-217, LightField4D.cs:175-206,
 // 253-273, 304-344, Sphere.cs:69-142): the colour of a camera sample is the colour of the CELL of a 4-D table its line falls into -- the
 // two points where the line pierces the sphere of radius 0.866 about the model's origin, each as (longitude, latitude) in 2N x N patches.
@@ -6327,6 +6487,108 @@ hipError_t launch_ao_points(const AoPointsLaunch& L) {
 size_t ao_points_table_bytes(int64_t pass) {
     return (size_t)((pass + kAopChunkGens - 1) / kAopChunkGens) * (size_t)kAopChunkDraws * sizeof(int32_t);
 }
+
+// sr_path_points: the passes, back to back on the stream (see k_pp_ingest).  A pass waits for the host only when the host makes its table
+// (PathPointsLaunch::host_table: SR_DBG_KERNEL_SWITCH 45, or a seed the jump-ahead does not cover)
+template <int MODE, bool EXTRA>
+static hipError_t launch_path_points_t(const PathPointsLaunch& L) {
+    hipError_t e;
+    HitRec* rays = (HitRec*)L.rays;
+    const bool trace = L.out != nullptr || L.incoming != nullptr;
+    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+    // where a stand-in origin lies: further from the root box's centre than any of its points, along the ray's own direction
+    double diag = 0.0;
+    for (int a = 0; a < 3; ++a) diag += (L.sc.root.hi[a] - L.sc.root.lo[a]) * (L.sc.root.hi[a] - L.sc.root.lo[a]);
+    const double away = 2.0 * std::sqrt(diag) + 1.0;
+    int64_t p = 0;
+    for (int64_t first = 0; first < L.n; first += L.pass, ++p) {
+        const uint32_t count = (uint32_t)std::min<int64_t>(L.pass, L.n - first);
+        const unsigned blocks = (count + 255u) / 256u;
+        const uint32_t units = (count + (uint32_t)kPpUnitPoints - 1u) / (uint32_t)kPpUnitPoints;
+        const uint32_t chunks = (units + (uint32_t)kAopChunkGens - 1u) / (uint32_t)kAopChunkGens;
+        hipEvent_t e0, e1;
+        e0 = e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_DRAWS, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        if (L.host_table) {
+            if ((e = L.host_table(L.user, L.first_sample + (uint64_t)first, count, L.table, L.stream)) != hipSuccess) return e;
+        } else {
+            hipLaunchKernelGGL(k_pp_window, dim3(1), dim3(64), 0, L.stream, L.windows[p], units, L.base_window, L.pass_units);
+            hipLaunchKernelGGL(k_aop_states, dim3((chunks + (uint32_t)kAopSuper - 1u) / (uint32_t)kAopSuper), dim3(64), 0, L.stream, (const int32_t*)L.base_window,
+                               L.stride_rows, (const uint32_t*)L.pass_units, L.table);
+            hipLaunchKernelGGL(k_draws, dim3((chunks + 3u) / 4u), dim3(256), 0, L.stream, (const uint32_t*)L.pass_units, chunks, L.table);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        const double* pos = L.pos + first * 3;
+        const double* nrm = L.nrm + first * 3;
+        double* dirs = L.dirs ? L.dirs + first * 3 : nullptr;
+        const uint32_t* color = L.color ? L.color + first : nullptr;
+        uint32_t* out = L.out ? L.out + first : nullptr;
+        uint32_t* incoming = L.incoming ? L.incoming + first : nullptr;
+        if (!trace) {
+            hipLaunchKernelGGL(k_pp_ingest<false>, dim3(blocks), dim3(256), 0, L.stream, pos, nrm, count, (const int32_t*)L.table, 0.0, 0.0, 0.0, 0.0,
+                               (HitRec*)nullptr, (unsigned int*)nullptr, dirs);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            continue;
+        }
+        e0 = e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_PP_TRACE, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        const unsigned pblocks = std::min<unsigned>(blocks, (unsigned)L.persistent_blocks);
+        if constexpr (MODE == MODE_BVH) {
+            if ((e = hipMemsetAsync(L.counters, 0, 4 * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_pp_ingest<true>, dim3(blocks), dim3(256), 0, L.stream, pos, nrm, count, (const int32_t*)L.table, L.sc.root.centre[0], L.sc.root.centre[1],
+                               L.sc.root.centre[2], away, rays, L.counters, dirs);
+            // the route of a path-traced frame's second rays (launch_pathtrace_t)
+            const bool wide = L.sc.b4 != nullptr && !L.bvh2_packets;
+            const size_t wlds = (size_t)(wide ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE_BVH)) * 256 * 4;
+            unsigned int* b = L.ray_sort_buf;
+            if ((e = ray_sort(rays, L.counters, count, L.sc.root, b, b + (size_t)count, b + 2 * (size_t)count, b + 3 * (size_t)count, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
+            const unsigned int* order = b + 3 * (size_t)count;
+            BounceRay* prep = (BounceRay*)L.bounce_prep;
+            BounceHit* res = (BounceHit*)L.bounce_res;
+            hipLaunchKernelGGL(k_bounce_prep, dim3(pblocks), dim3(256), 0, L.stream, L.sc, (const HitRec*)rays, (const unsigned int*)L.counters, order, prep, res);
+            const int levels_all = (int)(wlds / (256 * 4));
+            int lds_levels = std::max(1, std::min(kBounceLdsLevels, levels_all));
+            if ((size_t)(levels_all - lds_levels) * (size_t)pblocks * 256 * 4 > L.bounce_stack_bytes || !L.bounce_stack) lds_levels = levels_all;
+            const auto walk = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), (size_t)lds_levels * 256 * 4, L.stream, L.sc, (const BounceRay*)prep, (const unsigned int*)L.counters, L.counters + 2, res,
+                                   L.stats, kWalkRefillAt, L.bounce_stack, lds_levels, kWalkNodeBurst, kWalkLeafBurst);
+            };
+            if (wide) { if (L.stats) walk(k_bounce_walk<true, true>); else walk(k_bounce_walk<false, true>); }
+            else { if (L.stats) walk(k_bounce_walk<true, false>); else walk(k_bounce_walk<false, false>); }
+            const auto finw = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), 0, L.stream, L.sc, L.fc, (const HitRec*)rays, (const unsigned int*)L.counters, order, (const BounceRay*)prep,
+                                   (const BounceHit*)res, pos, nrm, color, out, incoming, L.stats);
+            };
+            if (L.stats) finw(k_pp_finish_walked<EXTRA, true>); else finw(k_pp_finish_walked<EXTRA, false>);
+        } else {
+            hipLaunchKernelGGL(k_pp_ingest<false>, dim3(blocks), dim3(256), 0, L.stream, pos, nrm, count, (const int32_t*)L.table, 0.0, 0.0, 0.0, 0.0, rays,
+                               (unsigned int*)nullptr, dirs);
+            const auto fin = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)rays, count, nrm, color, out, incoming, L.stats);
+            };
+            if (L.stats) fin(k_pp_finish<MODE, EXTRA, true>); else fin(k_pp_finish<MODE, EXTRA, false>);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_path_points(const PathPointsLaunch& L) {
+    if (L.n <= 0) return hipSuccess;
+    if (L.pass <= 0 || L.pass > kPpMaxPass || (!L.windows && !L.host_table)) return hipErrorInvalidValue;
+    const bool extra = L.sc.nextra > 0;
+    switch (L.mode) {
+        case MODE_REF: return extra ? launch_path_points_t<MODE_REF, true>(L) : launch_path_points_t<MODE_REF, false>(L);
+        case MODE_BRUTE: return extra ? launch_path_points_t<MODE_BRUTE, true>(L) : launch_path_points_t<MODE_BRUTE, false>(L);
+        case MODE_BVH: return extra ? launch_path_points_t<MODE_BVH, true>(L) : launch_path_points_t<MODE_BVH, false>(L);
+        default: return hipErrorInvalidValue;
+    }
+}
+size_t path_points_table_bytes(int64_t pass) { return ao_points_table_bytes((pass + kPpUnitPoints - 1) / kPpUnitPoints); }
 
 size_t pipeline_counter_bytes() { return (size_t)kCounterWords * sizeof(unsigned int); }
 // 8x8-pixel tiles (one wave's work items) of the padded super-tile grid of a band, all sub-samples

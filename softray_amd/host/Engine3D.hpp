@@ -399,6 +399,29 @@ public:
         sr_check(sr_ao_points(scene_, &f, n, pos, normal, color, out, amount, firstGenerator, 0u, &generators));
         return generators;
     }
+    // PathTracingMethod's one-bounce diffuse term for n surface points of the caller, in input order (sr_path_points): point i fires one second
+    // ray from pos[i] + normal[i] * 0.001 in the direction made of draws 3 (firstSample + i) .. + 2 of the frame's Random; incoming[i] = that
+    // hit's colour (shaded when rayTraceShading is on, 0 on a miss), out[i] = incoming * (normal . d) + color[i] (nullptr: 0xFFFFFFFF),
+    // dirs[i] = d; each output may be nullptr, not all three.  The root geometry, the seed and the shading switch are those of the frame
+    // Render() would build for the first instance; rayTracePathTracing is implied, the shadow and ambient-occlusion switches are not
+    // passed on (their steps are ShadowPoints and AmbientOcclusionPoints, which follow this one in the reference's chain).  A caller that
+    // splits a batch passes firstSample + n to the next call.  Voxels, the light field and mirror bounces are refused by the library, by
+    // name.  Does nothing without a model or points
+    void PathTracePoints(int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, uint32_t* incoming, double* dirs,
+                         uint64_t firstSample = 0) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel() || n == 0) return;
+        if (Instances.empty()) throw InvalidOperationException("PathTracePoints: no instance to take the pose from");
+        Instance& inst = *Instances.front();
+        inst.FieldOfViewDepth = fieldOfViewDepth_;
+        PreCalculate();
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_frame f = BuildFrame(inst);
+        // (the call has no primary rays: sr_last_ray_stats gets the second rays' counters)
+        f.flags &= ~(uint32_t)(SR_F_PRIMARY_STATS_ONLY | SR_F_SHADOWS | SR_F_STATIC_SHADOWS | SR_F_AMBIENT_OCCLUSION | SR_F_AO_UNCACHED);
+        sr_check(sr_path_points(scene_, &f, n, pos, normal, color, out, incoming, dirs, firstSample, 0u));
+    }
     // The frame G-buffer (sr_render_hits): what the primary stage of the frame Render() would build for the first instance answers per camera
     // sample, before any decorator, in scan order ((row - first row) * width + col) * n^2 + subX * n + subY.  Every array has
     // RenderHitsSamples() entries ([S][3] doubles, [S] scalars) and may be nullptr; a miss is hit 0, zeros and triangle -1.  The decorator

@@ -428,6 +428,34 @@ class GpuScene:
         _check(_lib.lib().sr_ao_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out), vp(d_amount),
                                               int(first_generator), 0, vp(st), vp(d_generators_ptr), vp(d_stats_ptr)))
 
+    def path_points(self, frame, pos, normal, color=None, first_sample=0, want_out=True, want_incoming=True, want_dirs=True):
+        """PathTracingMethod's step for caller-given surface points, in input order (sr_path_points): (out uint32 [n], incoming uint32 [n],
+        dirs float64 [n, 3]), each None when not wanted.  Point i uses draws 3 (first_sample + i) .. + 2 of Random(frame.random_seed); a
+        split batch passes first_sample + n to the next call.  color None: every point 0xFFFFFFFF."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+        if normal.shape[0] != pos.shape[0]:
+            raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
+        if color is not None:
+            color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
+            if color.size != pos.shape[0]:
+                raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
+        out = np.zeros(pos.shape[0], dtype=np.uint32) if want_out else None
+        incoming = np.zeros(pos.shape[0], dtype=np.uint32) if want_incoming else None
+        dirs = np.zeros((pos.shape[0], 3), dtype=np.float64) if want_dirs else None
+        _check(_lib.lib().sr_path_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out), _p(incoming), _p(dirs),
+                                         int(first_sample), 0))
+        return out, incoming, dirs
+
+    def path_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, d_incoming=None, d_dirs=None, first_sample=0, stream=0, d_stats_ptr=None):
+        """sr_path_points_device: every array is a DEVICE pointer (d_color 0 / None: every point 0xFFFFFFFF; d_out may be d_color; d_out,
+        d_incoming and d_dirs may each be 0 / None, not all three); enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no
+        host sync."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = getattr(stream, "cuda_stream", stream)
+        _check(_lib.lib().sr_path_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out), vp(d_incoming),
+                                                vp(d_dirs), int(first_sample), 0, vp(st), vp(d_stats_ptr)))
+
     def shade_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, stream=0):
         """sr_shade_points_device: every array is a DEVICE pointer; enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
         vp = lambda x: C.c_void_p(x) if x else None

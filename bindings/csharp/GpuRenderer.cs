@@ -104,6 +104,10 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_bake_light_field(IntPtr scene, ref SrFrame frame, ulong first, ulong count, out ulong filled);
         [DllImport(Lib)] public static extern int sr_shadow_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, uint options);
+        [DllImport(Lib)] public static extern int sr_static_shadow_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, [Out] byte[] amount, uint options, out ulong generators);
+        [DllImport(Lib)] public static extern int sr_static_shadow_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr dAmount, uint options, IntPtr hipStream, IntPtr dGenerators, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_get_shadow_cache(IntPtr scene, [Out] byte[] out128Cubed);
+        [DllImport(Lib)] public static extern int sr_set_shadow_cache(IntPtr scene, [In] byte[] in128Cubed);
         [DllImport(Lib)] public static extern int sr_ao_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, [Out] byte[] amount, ulong firstGenerator, uint options, out ulong generators);
         [DllImport(Lib)] public static extern int sr_ao_points_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut, IntPtr dAmount, ulong firstGenerator, uint options, IntPtr hipStream, IntPtr dGenerators, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_net_random_jump(int seed, ulong skip, [Out] int[] out55);
@@ -428,6 +432,41 @@ namespace Engine3D.Hip
             Native.Check(Native.sr_shadow_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, coherent ? POINTS_COHERENT : 0, stream, dStats));
         }
 
+        /// ShadowMethod's static branch for caller-given surface points, in input order (sr_static_shadow_points; ShadowMethod.cs:106-112,
+        /// Texture3DCache.Sample): the first point of an empty cell of the scene's static shadow cache -- the one F_STATIC_SHADOWS frames fill --
+        /// generates (byte)(escapes / 100.0 * 254 + 1) for the light, the seed's area-light offsets and the root geometry of the frame these
+        /// arguments describe; amount[i] = the byte of point i's cell, result[i] = color[i] (color == null: 0xFFFFFFFF) modulated with it;
+        /// `generators` receives the number of generators.  F_SHADOWS | F_STATIC_SHADOWS are implied.  pos / normal: double[n * 3] in model
+        /// space, the normal as given.  F_AMBIENT_OCCLUSION, F_PATH_TRACING, F_VOXELS and F_LIGHT_FIELD: SR_ERR_UNSUPPORTED ->
+        /// InvalidOperationException.  Blocks.
+        public uint[] StaticShadowPoints(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode, int randomSeed,
+                                         Vector lightDirView, Vector lightPosView, double[] pos, double[] normal, uint[] color, out byte[] amount,
+                                         out ulong generators, bool coherent = false)
+        {
+            if (pos == null || normal == null || pos.Length != normal.Length || pos.Length % 3 != 0 || (color != null && color.Length != pos.Length / 3))
+                throw new ArgumentException("StaticShadowPoints: pos and normal are double[n * 3], color is uint[n] or null");
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, 0, height - 1, 1, randomSeed,
+                      1.0, 1.0, 0.0, 0.0, 0.0, lightDirView, lightPosView, 4);
+            frame.flags &= ~F_PRIMARY_STATS_ONLY;                  // the call has no primary rays
+            var result = new uint[pos.Length / 3];
+            amount = new byte[pos.Length / 3];
+            Native.Check(Native.sr_static_shadow_points(scene, ref frame, result.Length, pos, normal, color, result, amount, coherent ? POINTS_COHERENT : 0, out generators));
+            return result;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_static_shadow_points_device): enqueued on `stream` without a host
+        /// synchronisation; dColor may be IntPtr.Zero (every point 0xFFFFFFFF) or dOut itself; one of dOut / dAmount may be IntPtr.Zero;
+        /// dGenerators: a ulong on the device, or IntPtr.Zero; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void StaticShadowPointsDevice(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint flags, int mode, int randomSeed,
+                                             Vector lightDirView, Vector lightPosView, long n, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dOut,
+                                             IntPtr dAmount, bool coherent, IntPtr stream, IntPtr dGenerators, IntPtr dStats)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, 0, height - 1, 1, randomSeed,
+                      1.0, 1.0, 0.0, 0.0, 0.0, lightDirView, lightPosView, 4);
+            frame.flags &= ~F_PRIMARY_STATS_ONLY;
+            Native.Check(Native.sr_static_shadow_points_device(scene, ref frame, n, dPos, dNormal, dColor, dOut, dAmount, coherent ? POINTS_COHERENT : 0, stream, dGenerators, dStats));
+        }
+
         /// AmbientOcclusionMethod's occlusion byte for caller-given surface points, in input order (sr_ao_points; AmbientOcclusionMethod.cs:65-99,
         /// AmbientOcclusion.cs:101-230): amount[i] = the byte of point i's cell (F_AO_UNCACHED in flags: of the point itself, every point
         /// generates), result[i] = color[i] (color == null: 0xFFFFFFFF) modulated with it.  Generator g of the call uses draws
@@ -575,6 +614,18 @@ namespace Engine3D.Hip
 
         /// A new Renderer starts with an empty static shadow cache (ShadowMethod.cs:75-83)
         public void ResetShadowCache() { Native.Check(Native.sr_reset_shadow_cache(scene)); }
+        /// The static shadow cache as the reference's softShadow_..._res128.cache file holds it: 128^3 bytes, [x][y][z], 0 = empty cell
+        public byte[] GetShadowCache()
+        {
+            var data = new byte[AoCacheBytes];
+            Native.Check(Native.sr_get_shadow_cache(scene, data));
+            return data;
+        }
+        public void SetShadowCache(byte[] data)
+        {
+            if (data == null || data.Length != AoCacheBytes) throw new ArgumentException("the static shadow cache is 128^3 bytes");
+            Native.Check(Native.sr_set_shadow_cache(scene, data));
+        }
 
         /// A new Renderer starts with an empty ambient-occlusion cache (AmbientOcclusion.cs:60-75)
         public void ResetAmbientOcclusionCache() { Native.Check(Native.sr_reset_ao_cache(scene)); }

@@ -392,6 +392,14 @@ int  sr_wide_tree_stats(const sr_scene*, int64_t out[5]);
 int  sr_render(sr_scene*, const sr_frame*, int32_t* pixels, uint64_t stats[4]);
 /* forget the static shadow cache (what a new Renderer / ShadowMethod starts with); sr_set_triangles does it too */
 int  sr_reset_shadow_cache(sr_scene*);
+/* rayTraceShadowsStatic's cache (SR_F_STATIC_SHADOWS, sr_static_shadow_points): 128^3 bytes in [x][y][z] order (x * 128 * 128 + y * 128 + z),
+ * 0 = empty cell -- the bytes the reference's Texture3DCache moves to and from its softShadow_..._res128.cache file (SaveCacheToDisk /
+ * LoadCacheFromDisk), so a host can save and load that file itself (the library does no file I/O).  A set cache is what the next static
+ * frame and the next sr_static_shadow_points read, and is not zeroed by them.  sr_reset_shadow_cache, sr_set_triangles*, sr_load_3ds and
+ * sr_refit_triangles_device drop it.  Both work on a host-only scene; a scene that never rendered a static frame reads back zeros; both wait
+ * for a frame of the scene in flight.  A multi-device scene keeps the cache on devices[0]. */
+int  sr_get_shadow_cache(sr_scene*, uint8_t out[128 * 128 * 128]);
+int  sr_set_shadow_cache(sr_scene*, const uint8_t in[128 * 128 * 128]);
 /* rayTraceAmbientOcclusion's cache (SR_F_AMBIENT_OCCLUSION): 128^3 bytes in [x][y][z] order, 0 = empty cell -- exactly the array the
  * reference persists to its .ao file (AmbientOcclusion.cs:232-309), so a host can save and load that file itself (the library does no file
  * I/O).  sr_reset_ao_cache: what a new Renderer starts with; sr_set_triangles / sr_load_3ds drop the cache too.  All three work on a
@@ -573,6 +581,41 @@ int  sr_shadow_points(sr_scene*, const sr_frame* frame, int64_t n, const double*
 int  sr_shadow_points_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_pos, const double* d_normal,
                              const uint32_t* d_color /* or NULL */, uint32_t* d_out, uint32_t options, void* hip_stream,
                              uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
+/* ShadowMethod.IntersectRay's static branch in batch (rayTraceShadowsStatic; ShadowMethod.cs:75-83, 106-112, Texture3DCache.Sample): the n
+ * caller-given surface points go, IN INPUT ORDER, through the scene's static shadow cache -- the one static frames fill and read
+ * (sr_get_shadow_cache / sr_set_shadow_cache).  Per point: its cell is (int)((p + 0.5) * 127) per axis, clamped to 0 .. 127 (a point outside
+ * the unit cube takes the edge cell, where the reference asserts; a NaN coordinate takes index 0), [x][y][z] order.  Point i GENERATES iff its
+ * cell is empty when the call starts and no point j < i of the call has the same cell; a generator stores
+ * (byte)(escapes / (double)S * 254 + 1), 0 replaced by 1, where S = frame->shadow_samples (0 => 100) and `escapes` is exactly sr_shadow_points'
+ * count for that point (E' = pos + normal * 0.001, the normal as given; point or directional light; the seed's offset table or
+ * area_light_offsets; blocked = a hit with rayFrac <= 1.0 in the frame's root geometry; a NaN component of E': all S escape, byte 255; an
+ * infinite component: only the extra primitives are asked).  There is no canonical point per cell: a cell's byte is the shadow of whichever
+ * point and normal asked first, so this call is also how a host bakes the cache ahead of time.
+ * amount[i] = the byte of point i's cell, out[i] = ModulatePackedColor(color[i], amount[i]); color == NULL: every point is 0xFFFFFFFF; out may
+ * alias color; out and amount are each optional, but not both NULL with n > 0.  *generators (or NULL) receives the number of generators.  A
+ * batch split over several calls equals the one call bit for bit: the cache carries the state.
+ * Read from `frame`: what sr_shadow_points reads; SR_F_SHADOWS | SR_F_STATIC_SHADOWS are implied; concurrency is not read (a batch is one
+ * block); the camera fields are validated as for a frame and otherwise unused; shadow_samples is whatever a static frame accepts (above 128 a
+ * static frame leaves the shaft path, and so does this call).  options: SR_POINTS_COHERENT, which here speaks of the generators of a pass in
+ * input order.
+ * Refused, in this order: n < 0, a NULL pos / normal with n > 0, both outputs NULL with n > 0, a NULL scene or frame, unknown option bits:
+ * SR_ERR_INVALID_ARG; SR_F_AMBIENT_OCCLUSION, SR_F_PATH_TRACING, SR_F_VOXELS, SR_F_LIGHT_FIELD, SR_F_SINGLE_KERNEL, max_bounces > 0,
+ * strip_count > 0: SR_ERR_UNSUPPORTED; then sr_render's validation of the frame and its trace mode; then a host-only scene: SR_ERR_NO_DEVICE.
+ * n == 0 that passes these checks: SR_OK, nothing is touched, *generators = 0.
+ * Ordered like a frame (behind a frame of the scene in flight on any stream, the next frame behind it), on the scene's scratch, in passes of
+ * at most 2^22 points (SR_DBG_BAND_SAMPLES: fewer) that follow each other without the host waiting: a pass finds the bytes of the passes
+ * before it.  A multi-device scene runs it on devices[0], where the cache lives.  The host variant stages, blocks and fills
+ * sr_last_ray_stats; the device variant takes device arrays (d_generators too), enqueues on `hip_stream` without a host synchronisation and
+ * writes the counters to d_stats when given.  Statistics: [0..3] 0, [4..] what a static frame's shadow stage counts for the generators it is
+ * handed (a generator whose E' is not finite, or which a directional light provably reaches -- sr_shadow_points' shortcut -- fires no ray
+ * and counts nothing); all 0 with SR_F_PRIMARY_STATS_ONLY. */
+int  sr_static_shadow_points(sr_scene*, const sr_frame* frame, int64_t n, const double* pos, const double* normal,
+                             const uint32_t* color /* or NULL */, uint32_t* out /* or NULL */, uint8_t* amount /* or NULL */, uint32_t options,
+                             uint64_t* generators /* or NULL */);
+int  sr_static_shadow_points_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_pos, const double* d_normal,
+                                    const uint32_t* d_color, uint32_t* d_out, uint8_t* d_amount, uint32_t options, void* hip_stream,
+                                    uint64_t* d_generators /* or NULL */, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
 /* AmbientOcclusionMethod.IntersectRay's step in batch (AmbientOcclusionMethod.cs:65-99, AmbientOcclusion.cs:101-230): the occlusion byte of n
  * caller-given surface points -- what the decorator leaves when it is applied to the n intersections IN INPUT ORDER by one RenderContext whose
@@ -792,7 +835,7 @@ int  sr_anti_alias_device(sr_scene*, const void* d_src, int32_t dst_width, int32
 enum {
     SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
                                     per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) and the
-                                    points per pass of sr_shadow_points (default 2^22), of sr_ao_points (default and limit 2^17) and of sr_path_points (default and limit 2^22) */
+                                    points per pass of sr_shadow_points and sr_static_shadow_points (default 2^22), of sr_ao_points (default and limit 2^17) and of sr_path_points (default and limit 2^22) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
     SR_DBG_SPLIT          = 3,   /* concurrent part-frame pipelines (default 2, <= 4)                                          */

@@ -47,6 +47,7 @@ SYMBOLS = [
     "sr_bake_light_field", "sr_set_voxel_res", "sr_get_voxel_res", "sr_set_triangles_device",
     "sr_refit_triangles_device", "sr_set_light_field_shadows", "sr_get_light_field_shadows",
     "sr_shadow_points", "sr_shadow_points_device",
+    "sr_static_shadow_points", "sr_static_shadow_points_device", "sr_get_shadow_cache", "sr_set_shadow_cache",
     "sr_set_light_field_interpolation", "sr_get_light_field_interpolation", "sr_light_field_coords",
     "sr_set_light_field_triangles", "sr_get_light_field_triangles", "sr_get_light_field_tris", "sr_set_light_field_tris", "sr_tree_handle_leaf",
     "sr_frame_sample_count", "sr_render_hits", "sr_render_hits_device", "sr_shade_points_device",
@@ -167,6 +168,10 @@ def lib():
     L.sr_render_hits_device.restype = i32; L.sr_render_hits_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sr_shadow_points.restype = i32; L.sr_shadow_points.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32]
     L.sr_shadow_points_device.restype = i32; L.sr_shadow_points_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp, vp]
+    L.sr_static_shadow_points.restype = i32; L.sr_static_shadow_points.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_uint32, vp]
+    L.sr_static_shadow_points_device.restype = i32; L.sr_static_shadow_points_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    L.sr_get_shadow_cache.restype = i32; L.sr_get_shadow_cache.argtypes = [vp, vp]
+    L.sr_set_shadow_cache.restype = i32; L.sr_set_shadow_cache.argtypes = [vp, vp]
     L.sr_ao_points.restype = i32; L.sr_ao_points.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp]
     L.sr_ao_points_device.restype = i32; L.sr_ao_points_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp]
     L.sr_net_random_jump.restype = i32; L.sr_net_random_jump.argtypes = [i32, C.c_uint64, vp]

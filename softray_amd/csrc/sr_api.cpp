@@ -144,6 +144,7 @@ struct sr_scene {
     uint64_t aop_host_drawn = 0;                      // ... this many generators
     bool ao_cache_empty = true;          // the device cache must be zeroed before its next use (a new Renderer / a new model)
     std::vector<uint8_t> ao_cache_host;
+    std::vector<uint8_t> shadow_cache_host;   // sr_set_shadow_cache on a host-only scene (sr_get_shadow_cache reads it back)
     int32_t ao_table_seed = 0;           // random_seed of the frame being enqueued (read by PipelineLaunch::ao_table)
     int  ao_table_rc = SR_OK;            // why the frame's draw table was refused (PipelineLaunch::ao_table)
     // rayTraceLightField (SR_F_LIGHT_FIELD): the 4 N^4 uint32 entries a Renderer's LightFieldColorMethod keeps for its life (allocated on first use),
@@ -713,7 +714,11 @@ int ensure_light_field_tris(sr_scene* s, hipStream_t stream) {
 // table, the shadow stage's scratch), so it runs through render_common with no rows to render
 struct LfBakeReq { uint64_t first, count; unsigned long long* filled; };
 // sr_shadow_points: the same set-up for the same reason, then passes of the caller's points through the shadow stage (device arrays)
-struct PtsReq { int64_t n; const double* pos; const double* nrm; const uint32_t* color; uint32_t* out; bool coherent; };
+struct PtsReq {
+    int64_t n; const double* pos; const double* nrm; const uint32_t* color; uint32_t* out; bool coherent;
+    // sr_static_shadow_points: the points go through the static cache (the frame carries SR_F_STATIC_SHADOWS); out / amount each optional
+    bool through_cache = false; uint8_t* amount = nullptr; unsigned long long* generators = nullptr;
+};
 // sr_render_hits: the frame's own set-up of the primary stage (camera cones, ordered node copy, facing partition, row bands), then k_hits
 // per band into the caller's device arrays instead of the frame's kernels.  The caller has cleared the decorator switches of `f`
 struct HitsReq { sr::HitsOut out; };
@@ -868,7 +873,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     //     cells are renderer state) keep the literal path.
     // (a light-field frame keeps the literal rays: the constant factor is k_primary's)
     bool pts_escape = false;
-    if ((fc.flags & SR_F_SHADOWS) && !(fc.flags & SR_F_POINT_LIGHT) && !static_shadows && s->extra_recs.empty() && !(f->flags & SR_F_LIGHT_FIELD) &&
+    if ((fc.flags & SR_F_SHADOWS) && !(fc.flags & SR_F_POINT_LIGHT) && (!static_shadows || pts) && s->extra_recs.empty() && !(f->flags & SR_F_LIGHT_FIELD) &&
         !(f->flags & (SR_F_SINGLE_KERNEL | SR_F_PER_LANE_SHADOWS)) && f->max_bounces == 0 && s->dbg[SR_DBG_LITERAL_SHADOWS] <= 0) {
         double diag2 = 0, len2 = 0;
         for (int a = 0; a < 3; ++a) {
@@ -878,7 +883,8 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         }
         if (1000.0 * std::sqrt(len2) - fc.light_radius > std::sqrt(diag2) * 1.001 + 0.01) {
             // (sr_shadow_points: a caller's point need not lie where a hit point does.  The proof holds for a probe end inside the box
-            // the diagonal was taken of; k_pts_ingest finishes those points and queues the others for the literal rays)
+            // the diagonal was taken of; k_pts_ingest finishes those points and queues the others for the literal rays.  sr_static_shadow_points:
+            // the same for the generators, k_ssp_select stores their byte -- a static FRAME keeps the literal rays)
             if (pts) pts_escape = true;
             else fc.flags = (fc.flags & ~(uint32_t)SR_F_SHADOWS) | sr::kFlagAllSamplesEscape;
         }
@@ -1058,7 +1064,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     // (hook 37: a pass is queued in input order whatever the caller promised)
     const bool pts_sort = pts && !pts->coherent && s->dbg[SR_DBG_KERNEL_SWITCH] != 37;
     if (shaft && band_samples >= (1ll << 25)) return fail(SR_ERR_UNSUPPORTED, "row band too large for the 25-bit fallback entry ids (surface too wide for this sub-pixel resolution)");
-    if (static_shadows) {
+    if (static_shadows && !pts) {
         if (band_rows < fc.num_rows) return fail(SR_ERR_UNSUPPORTED, "static shadows: the frame does not fit one row band");
         SR_HIP(s->d_static_hits.reserve((size_t)std::min<long long>(band_samples, (long long)sr::pipeline_static_cells()) * sr::pipeline_hit_record_bytes()));
     }
@@ -1268,6 +1274,9 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             P.pts_sort = pts_sort;
             P.pts_per_lane = s->dbg[SR_DBG_KERNEL_SWITCH] == 38;
             P.pts_escape = pts_escape;
+            P.pts_static = pts->through_cache;
+            P.pts_amount = pts->amount;
+            P.pts_generators = pts->generators;
             for (int a = 0; a < 3; ++a) {                                 // (the box of the shortcut's diagonal: model and root box, + the probe offset, both ends)
                 P.pts_escape_lo[a] = std::min(s->vmin[a], s->root.min[a]) - 0.002;
                 P.pts_escape_hi[a] = std::max(s->vmax[a], s->root.max[a]) + 0.002;
@@ -1444,7 +1453,7 @@ void share_host_model(sr_scene* d, const sr_scene* src) {
     for (int a = 0; a < 3; ++a) { d->bmin[a] = src->bmin[a]; d->bmax[a] = src->bmax[a]; d->vmin[a] = src->vmin[a]; d->vmax[a] = src->vmax[a]; }
     d->have_model = src->have_model;
     d->root = src->root;
-    d->shadow_cache_empty = true;
+    d->shadow_cache_empty = true; d->shadow_cache_host.clear();
     d->ao_cache_empty = true; d->ao_cache_host.clear();
     d->lf_cache_empty = true; d->lf_cache_host.clear();
     d->lft_cache_empty = true; d->lft_cache_host.clear();
@@ -1548,7 +1557,7 @@ int set_triangles_from_device_enqueue(sr_scene* s, const double* src_v9, const u
         SR_HIP(hipMemcpyAsync(bounds, s->d_bounds.p, sizeof(bounds), hipMemcpyDeviceToHost, stream));
         SR_HIP(hipStreamSynchronize(stream));                          // the call's one host wait: the six doubles (and the temporaries are freed on return)
     }
-    s->shadow_cache_empty = true;                         // a new model: what sr_set_triangles drops
+    s->shadow_cache_empty = true; s->shadow_cache_host.clear();   // a new model: what sr_set_triangles drops
     s->ao_cache_empty = true; s->ao_cache_host.clear();
     s->lf_cache_empty = true; s->lf_cache_host.clear();
     s->lft_cache_empty = true; s->lft_cache_host.clear();
@@ -1654,7 +1663,7 @@ int refit_from_device_enqueue(sr_scene* s, const double* src_v9, const uint32_t*
     s->records_epoch++;
     s->bvh_dirty = false;                                 // (kept: b4_num, b4_depth, bvh.built, bvh.depth, bvh_num_nodes, bvh_on_device)
     s->tris_dirty = false;
-    s->shadow_cache_empty = true;                         // a new model: what sr_set_triangles_device drops
+    s->shadow_cache_empty = true; s->shadow_cache_host.clear();   // a new model: what sr_set_triangles_device drops
     s->ao_cache_empty = true; s->ao_cache_host.clear();
     s->lf_cache_empty = true; s->lf_cache_host.clear();
     s->lft_cache_empty = true; s->lft_cache_host.clear();
@@ -1796,7 +1805,7 @@ int sr_set_triangles(sr_scene* s, const double* v9, const uint32_t* argb, int64_
     }
     if (!s || n < 0 || (n > 0 && (!v9 || !argb)) || !box_min || !box_max) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_triangles");
     if (n > 0x7fffff00) return fail(SR_ERR_INVALID_ARG, "too many triangles");
-    s->shadow_cache_empty = true;                         // new model: what a new ShadowMethod starts with
+    s->shadow_cache_empty = true; s->shadow_cache_host.clear();   // new model: what a new ShadowMethod starts with
     s->ao_cache_empty = true; s->ao_cache_host.clear();   // ... and a new AmbientOcclusion
     s->lf_cache_empty = true; s->lf_cache_host.clear();   // ... and a new LightFieldColorMethod
     s->lft_cache_empty = true; s->lft_cache_host.clear(); // ... and a new LightFieldTriMethod
@@ -2171,9 +2180,42 @@ int64_t sr_frame_pixel_count(const sr_frame* f) {
 }
 
 int sr_reset_shadow_cache(sr_scene* s) {
-    if (s && !s->parts.empty()) { for (sr_scene* q : s->parts) q->shadow_cache_empty = true; return SR_OK; }
+    if (s && !s->parts.empty()) { for (sr_scene* q : s->parts) { q->shadow_cache_empty = true; q->shadow_cache_host.clear(); } return SR_OK; }
     if (!s) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_reset_shadow_cache");
     s->shadow_cache_empty = true;
+    s->shadow_cache_host.clear();
+    return SR_OK;
+}
+
+// the static shadow cache as the reference's .cache file holds it (a multi-device scene keeps it on the first part, where static frames run)
+int sr_get_shadow_cache(sr_scene* s, uint8_t* out) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_get_shadow_cache");
+    const size_t cells = sr::pipeline_static_cells();
+    if (s->device < 0) {
+        if (s->shadow_cache_host.empty()) std::memset(out, 0, cells);
+        else std::memcpy(out, s->shadow_cache_host.data(), cells);
+        return SR_OK;
+    }
+    if (s->shadow_cache_empty || !s->d_shadow_cache.p) { std::memset(out, 0, cells); return SR_OK; }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still be filling cells
+    SR_HIP(hipMemcpy(out, s->d_shadow_cache.p, cells, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_set_shadow_cache(sr_scene* s, const uint8_t* in) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !in) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_set_shadow_cache");
+    const size_t cells = sr::pipeline_static_cells();
+    if (s->device < 0) { s->shadow_cache_host.assign(in, in + cells); return SR_OK; }
+    int rc = use_device(s);
+    if (rc) return rc;
+    if (s->pre_used_set) SR_HIP(hipEventSynchronize(s->pre_used));       // a frame in flight may still read the old bytes
+    SR_HIP(s->d_shadow_cache.reserve(cells));
+    SR_HIP(hipMemcpy(s->d_shadow_cache.p, in, cells, hipMemcpyHostToDevice));
+    s->shadow_cache_empty = false;                                       // (the next static frame must not zero what was set)
     return SR_OK;
 }
 
@@ -3080,6 +3122,83 @@ int sr_shadow_points(sr_scene* m, const sr_frame* f, int64_t n, const double* po
     SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
     SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     SR_HIP(hipStreamSynchronize(stream));
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    return SR_OK;
+}
+
+// ---- sr_static_shadow_points ----
+// what sr_static_shadow_points[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the
+// first part of a multi-device scene, where the cache lives), `fs`: the frame with SR_F_SHADOWS | SR_F_STATIC_SHADOWS implied
+static int static_shadow_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* pos, const void* normal, const void* out, const void* amount,
+                                      uint32_t options, sr_frame& fs) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (n < 0 || (n > 0 && (!pos || !normal)) || (n > 0 && !out && !amount) || !s || !f || (options & ~(uint32_t)SR_POINTS_COHERENT))
+        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_static_shadow_points");
+    if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is another decorator, not ShadowMethod's step");
+    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain ShadowMethod is part of");
+    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: voxel rendering (SR_F_VOXELS) has no shadow step");
+    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points");
+    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter");
+    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point");
+    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points");
+    fs = *f;
+    fs.flags |= SR_F_SHADOWS | SR_F_STATIC_SHADOWS;
+    int rc = validate_frame(&fs, s);
+    if (rc) return rc;
+    return check_frame_mode(s, &fs);
+}
+
+int sr_static_shadow_points_device(sr_scene* m, const sr_frame* f, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color, uint32_t* d_out,
+                                   uint8_t* d_amount, uint32_t options, void* hip_stream, uint64_t* d_generators, uint64_t* d_stats) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = static_shadow_points_check(s, f, n, d_pos, d_normal, d_out, d_amount, options, fs);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n == 0) {
+        if (d_generators && s->device >= 0) {
+            SR_HIP(hipSetDevice(s->device));
+            SR_HIP(hipMemsetAsync(d_generators, 0, sizeof(uint64_t), stream));
+        }
+        return SR_OK;
+    }
+    if ((rc = use_device(s))) return rc;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    if (d_generators) SR_HIP(hipMemsetAsync(d_generators, 0, sizeof(uint64_t), stream));
+    const PtsReq req{n, d_pos, d_normal, d_color, d_out, (options & SR_POINTS_COHERENT) != 0, true, d_amount, (unsigned long long*)d_generators};
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, 0, nullptr, &req);
+}
+
+int sr_static_shadow_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, uint8_t* amount,
+                            uint32_t options, uint64_t* generators) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = static_shadow_points_check(s, f, n, pos, normal, out, amount, options, fs);
+    if (rc) return rc;
+    if (n == 0) { if (generators) *generators = 0; return SR_OK; }
+    if ((rc = use_device(s))) return rc;
+    if ((rc = ensure_io_streams(s))) return rc;
+    hipStream_t stream = s->io_stream;
+    const size_t sizes[5] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n, sizeof(uint64_t)};
+    for (int i = 0; i < 5; ++i) SR_HIP(s->d_io[i].reserve(sizes[i]));
+    SR_HIP(hipMemcpy(s->d_io[0].p, pos, sizes[0], hipMemcpyHostToDevice));
+    SR_HIP(hipMemcpy(s->d_io[1].p, normal, sizes[1], hipMemcpyHostToDevice));
+    if (color) SR_HIP(hipMemcpy(s->d_io[2].p, color, sizes[2], hipMemcpyHostToDevice));
+    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
+    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    SR_HIP(hipMemsetAsync(s->d_io[4].p, 0, sizes[4], stream));
+    // (the colours are modulated where they lie: the device variant's `out` aliasing `color`)
+    const PtsReq req{n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, color ? (const uint32_t*)s->d_io[2].p : nullptr,
+                     out ? (uint32_t*)s->d_io[2].p : nullptr, (options & SR_POINTS_COHERENT) != 0, true, amount ? (uint8_t*)s->d_io[3].p : nullptr,
+                     (unsigned long long*)s->d_io[4].p};
+    if ((rc = render_common(s, &fs, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, nullptr, &req))) { (void)hipStreamSynchronize(stream); return rc; }
+    uint64_t made = 0;
+    if (out) SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
+    if (amount) SR_HIP(hipMemcpyAsync(amount, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(&made, s->d_io[4].p, sizes[4], hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
+    if (generators) *generators = made;
     if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
     return SR_OK;
 }

@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_COUNT = 39 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_COUNT = 41 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -164,6 +164,12 @@ struct PipelineLaunch {
     bool          pts_per_lane; // the first shaft round with private per-lane walks (A/B hook)
     bool          pts_escape;   // a directional light whose samples all escape for a probe end inside [pts_escape_lo, pts_escape_hi]
     double        pts_escape_lo[3], pts_escape_hi[3];
+    // sr_static_shadow_points (pts_static, with pts_n > 0): the points go through the scene's static shadow cache instead -- the first point of an
+    // empty cell (input order: static_claim, reset once per call) generates its byte through the frame's stage with the static bit set, every point
+    // reads its cell (k_ssp_claim / k_ssp_select / k_ssp_apply, sr_pipeline.hip).  pts_out and pts_amount are each optional
+    bool          pts_static;
+    uint8_t*      pts_amount;       // device [n] or nullptr: every point's cell byte
+    unsigned long long* pts_generators; // device, or nullptr: the generators are added to it (the caller zeroes it)
     // sr_render_hits (hits_req: launch_pipeline runs k_hits per row band instead of the frame's kernels and writes no pixel)
     bool          hits_req;
     HitsOut       hits_out;

@@ -158,6 +158,8 @@ const char* kernel_name(int id) {
         case K_DRAWS: return "k_draws";                       // sr_ao_points: a pass's draw table (k_aop_base, k_aop_states, k_draws)
         case K_AOP_PROBE: return "k_aop_probe";               // ... its probes
         case K_PP_TRACE: return "path_points_rays";           // sr_path_points: the second rays of a pass, all kernels from k_pp_ingest to k_pp_finish[_walked] (its table: k_draws)
+        case K_SSP_CLAIM: return "k_ssp_claim";               // sr_static_shadow_points: a pass's cells, claims and generator records (k_ssp_claim + k_ssp_select; its order: k_pts_sort)
+        case K_SSP_APPLY: return "k_ssp_apply";               // ... every point reads its cell
         case K_LF_LOOKUP: return "k_lf_lookup";
         case K_LF_FILL: return "k_lf_fill";
         case K_LF_APPLY: return "k_lf_apply";

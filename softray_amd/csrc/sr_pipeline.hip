@@ -5140,6 +5140,112 @@ __global__ __launch_bounds__(256) void k_pts_gather(const HitRec* __restrict__ i
 }
 
 // --------------------------------------------------------------------------------------------------
+// k_ssp_claim / k_ssp_select / k_ssp_apply (sr_static_shadow_points): ShadowMethod's static branch (ShadowMethod.cs:106-112,
+// Texture3DCache.Sample) for caller-given surface points IN INPUT ORDER, on the cache static frames fill and read.  One lane per point of a pass:
+//   k_ssp_claim   recs[i] = the point as given, sample = i, pad[0] = its cell, pad[1] = the class of E' = pos + normal * 0.001 (0 the stage
+//                 decides, 1 all samples escape, 2 only the extra primitives are asked: k_pts_ingest's three cases); where the cell is
+//                 empty, atomicMin(claim[cell], index of the point in the CALL) -- behind two filters, see the kernel.  The claims are reset once per call, not per pass: a later
+//                 pass finds the bytes the earlier passes stored (same stream) and claims nothing there, so "lowest index wins" holds
+//                 across passes and an index names one point of the call
+//   k_ssp_select  the point whose index the claim holds is the cell's generator.  Class 0 stays in recs for point_order / k_pts_gather and the
+//                 frame's shadow stage, which stores cache[pad[0]] with the static bit set (finish_hit); every other point gets sample =
+//                 kInvalidHit.  Generators of class 1 and 2 store their byte here: (byte)(escapes / (double)S * 254 + 1), 0 replaced by 1
+//                 (ShadowMethod.cs:80, Texture3DCache.cs:124-126).  No other lane writes that cell in this pass, none reads it before k_ssp_apply
+//   k_ssp_apply   after the stage: amount[i] = cache[cell], out[i] = modulate(colour, amount[i]) (ShadowMethod.cs:118); `out` may be the
+//                 colour array, so neither is __restrict__
+// The cell is static_cell's; a NaN coordinate takes index 0 on its axis, said here and not left to the conversion ((-0.5 + 0.5) * 127).
+// --------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t ssp_cell(const double* pos) {
+    const double q[3] = {pos[0] != pos[0] ? -0.5 : pos[0], pos[1] != pos[1] ? -0.5 : pos[1], pos[2] != pos[2] ? -0.5 : pos[2]};
+    return static_cell(q);
+}
+
+__global__ __launch_bounds__(256) void k_ssp_claim(const uint8_t* __restrict__ cache, const double* __restrict__ pos, const double* __restrict__ nrm,
+                                                   uint32_t n, unsigned long long first, PtsBox box, HitRec* __restrict__ recs,
+                                                   unsigned long long* claim) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < n;
+    HitRec r;
+    for (int a = 0; a < 3; ++a) {
+        r.pos[a] = live ? pos[(size_t)i * 3 + a] : 0.0;
+        r.nrm[a] = live ? nrm[(size_t)i * 3 + a] : 0.0;
+    }
+    const D3 end = mk(r.pos[0], r.pos[1], r.pos[2]) + mk(r.nrm[0], r.nrm[1], r.nrm[2]) * 0.001;      // shadowProbeOffset
+    const bool is_nan = end.x != end.x || end.y != end.y || end.z != end.z;
+    const double fin = (end.x - end.x) + (end.y - end.y) + (end.z - end.z);                          // 0 for finite components, NaN otherwise
+    const bool inside = box.on && end.x >= box.lo[0] && end.x <= box.hi[0] && end.y >= box.lo[1] && end.y <= box.hi[1] &&
+                        end.z >= box.lo[2] && end.z <= box.hi[2];
+    const uint32_t cell = ssp_cell(r.pos);
+    r.sample = i;
+    r.pad[0] = cell;
+    r.pad[1] = (is_nan || inside) ? 1u : (fin == 0.0 ? 0u : 2u);
+    r.pad[2] = 0u;
+    if (live) recs[i] = r;
+    // 15 M hit points of a 4096^2 frame share 62 k cells, 240 claims per address: two filters that lose no winner.  A run of lanes with one
+    // cell (neighbours in scan order) is claimed by its first lane, which has the run's lowest index; and a claim that is already lower
+    // cannot be beaten -- claims only fall, so a stale read costs an atomic, never a generator
+    const uint32_t before = __shfl_up(cell, 1);
+    const bool lead = (threadIdx.x & 63u) == 0u || before != cell;
+    const unsigned long long idx = first + i;
+    if (live && lead && cache[cell] == 0 && claim[cell] > idx) atomicMin(&claim[cell], idx);
+}
+
+template <bool EXTRA>
+__global__ __launch_bounds__(256) void k_ssp_select(DevScene sc, FrameConst fc, const double* __restrict__ offsets, uint32_t n, unsigned long long first,
+                                                    const unsigned long long* __restrict__ claim, HitRec* __restrict__ recs,
+                                                    unsigned long long* __restrict__ generators) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool won = false;
+    if (i < n) {
+        const uint32_t cell = recs[i].pad[0], cls = recs[i].pad[1];
+        won = claim[cell] == first + i;
+        if (won && cls != 0u) {
+            int escapes = fc.shadow_samples;
+            if (EXTRA && cls == 2u) {
+                // k_pts_ingest's loop: the sample rays of an infinite E' against the extra primitives alone, with the literal path's arithmetic
+                const D3 end = mk(recs[i].pos[0], recs[i].pos[1], recs[i].pos[2]) + mk(recs[i].nrm[0], recs[i].nrm[1], recs[i].nrm[2]) * 0.001;
+                escapes = 0;
+                for (int k = 0; k < fc.shadow_samples; ++k) {
+                    const D3 off = mk(offsets[3 * k], offsets[3 * k + 1], offsets[3 * k + 2]);
+                    D3 rs, rd;
+                    if (fc.flags & 8u) {
+                        rs = mk(fc.light_pos_model[0] + off.x, fc.light_pos_model[1] + off.y, fc.light_pos_model[2] + off.z);
+                        rd = end - rs;
+                    } else {
+                        rd = mk(fc.light_dir_model[0], fc.light_dir_model[1], fc.light_dir_model[2]);
+                        rs = end + rd * 1000.0 + off;
+                    }
+                    bool blocked = false;
+                    for (int e = 0; e < sc.nextra && !blocked; ++e) {
+                        double t; D3 hp, hn;
+                        uint32_t tests;
+                        blocked = extra_hit(&sc.extra[e], rs, rd, t, hp, hn, tests) && t <= 1.0;
+                    }
+                    if (!blocked) escapes++;
+                }
+            }
+            const uint32_t v = (uint32_t)(int)((double)escapes / (double)fc.shadow_samples * 254 + 1) & 0xffu;
+            sc.shadow_cache[cell] = (uint8_t)(v ? v : 1u);
+        }
+        if (!won || cls != 0u) recs[i].sample = kInvalidHit;
+    }
+    if (generators) {
+        const uint32_t g = wave_sum(won ? 1u : 0u);
+        if ((threadIdx.x & 63) == 0) stat_add(generators, g);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ssp_apply(const uint8_t* __restrict__ cache, const double* __restrict__ pos, const uint32_t* color, uint32_t n,
+                                                   uint32_t* out, uint8_t* __restrict__ amount) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const double p[3] = {pos[(size_t)i * 3], pos[(size_t)i * 3 + 1], pos[(size_t)i * 3 + 2]};
+    const uint32_t b = cache[ssp_cell(p)];
+    if (amount) amount[i] = (uint8_t)b;
+    if (out) out[i] = modulate(color ? color[i] : 0xFFFFFFFFu, b);
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_cam_cones: per-frame pre-pass of the packet primary walk -- the CamCone record (sr_types.h) of every BVH triangle for
 // the frame's ray origin O: FP64 cross products of the FP64 vertices, rounded once to fp32.  64 B written + 72 B (gathered)
 // + 8 B read per triangle: 0.15 GB at 1 M triangles; re-run only when the origin or the tree changed.
@@ -6108,6 +6214,62 @@ static hipError_t launch_pts_shadows_t(const PipelineLaunch& L) {
     return hipSuccess;
 }
 
+// sr_static_shadow_points (PipelineLaunch::pts_static): the caller's points through the scene's static shadow cache, in passes like
+// launch_pts_shadows_t's.  Per pass: counters reset, k_ssp_claim + k_ssp_select, point_order + k_pts_gather (launched as sr_shadow_points
+// launches them: the generators the stage must decide come first), the shadow stage a static frame runs on its generator list (flags & 32:
+// its finishing sites store cache[pad[0]] and never touch the sample buffer -- it is given the dead sort scratch, not the caller's `out`),
+// k_ssp_apply.  The claims are reset once per call; a pass sees the bytes of the passes before it
+template <int MODE, bool EXTRA>
+static hipError_t launch_static_pts_t(const PipelineLaunch& L) {
+    hipError_t e;
+    if (!L.ray_sort_buf || !L.hits2 || !L.static_claim || !L.sc.shadow_cache || !(L.fc.flags & 32u) || L.fc.accum) return hipErrorInvalidValue;
+    PipelineLaunch G = L;
+    if (L.primary_stats_only) G.stats = nullptr;
+    G.tile_queue_n2 = 0;
+    G.tile_queue_rows = 0;
+    PtsBox box;
+    for (int a = 0; a < 3; ++a) { box.lo[a] = L.pts_escape_lo[a]; box.hi[a] = L.pts_escape_hi[a]; }
+    box.on = L.pts_escape ? 1 : 0;
+    const uint8_t* cache = (const uint8_t*)L.sc.shadow_cache;
+    if ((e = hipMemsetAsync(L.static_claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
+    for (int64_t first = 0; first < L.pts_n; first += L.pts_pass) {
+        const uint32_t count = (uint32_t)std::min<int64_t>(L.pts_pass, L.pts_n - first);
+        const dim3 grid((count + 255u) / 256u);
+        if ((e = hipMemsetAsync(L.counters, 0, kCounterWords * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
+        hipEvent_t e0, e1;
+        pipe_events(L, K_SSP_CLAIM, e0, e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ssp_claim, grid, dim3(256), 0, L.stream, cache, L.pts_pos + first * 3, L.pts_nrm + first * 3, count, (unsigned long long)first, box,
+                           (HitRec*)L.hits2, L.static_claim);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ssp_select<EXTRA>, grid, dim3(256), 0, L.stream, L.sc, L.fc, L.offsets, count, (unsigned long long)first,
+                           (const unsigned long long*)L.static_claim, (HitRec*)L.hits2, L.pts_generators);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        {
+            pipe_events(L, K_PTS_SORT, e0, e1);
+            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+            const unsigned cap = count;
+            unsigned int* b = L.ray_sort_buf;
+            if ((e = point_order(L.hits2, cap, L.pts_sort, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
+            const unsigned blocks = (unsigned)std::min<long long>(((long long)count + 255) / 256, (long long)L.persistent_blocks);
+            hipLaunchKernelGGL(k_pts_gather, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)L.hits2, cap, (const unsigned int*)(b + 3 * (size_t)cap), (const unsigned int*)(b + (size_t)cap),
+                               point_order_skip_mask(L.pts_sort), (HitRec*)L.hits, L.counters);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        }
+        // (at most one generator per cell: the bound a static frame gives its generator list)
+        if ((e = launch_shadow_t<MODE, EXTRA>(G, (uint32_t*)L.ray_sort_buf, std::min<long long>((long long)count, (long long)kStaticRes * kStaticRes * kStaticRes))) != hipSuccess) return e;
+        pipe_events(L, K_SSP_APPLY, e0, e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ssp_apply, grid, dim3(256), 0, L.stream, cache, L.pts_pos + first * 3, L.pts_color ? L.pts_color + first : nullptr, count,
+                           L.pts_out ? L.pts_out + first : nullptr, L.pts_amount ? L.pts_amount + first : nullptr);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // sr_bake_light_field: entries [first, first + count) of the table in launches of at most L.launch_cells cells (whole origin patches; at
 // least one), one after the other on the stream with nothing in between: no single kernel runs long, and the host never waits
 template <int MODE, bool EXTRA>
@@ -6205,6 +6367,7 @@ hipError_t launch_resolve_rows(const FrameConst& fc, const int32_t* row_map, int
 template <int MODE, bool EXTRA>
 static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     if (L.lf_bake_count > 0) return launch_lf_bake_shadows_t<MODE, EXTRA>(L);      // sr_bake_light_field with shadows: no rows, no pixels
+    if (L.pts_n > 0 && L.pts_static) return launch_static_pts_t<MODE, EXTRA>(L);   // sr_static_shadow_points: the points through the static cache
     if (L.pts_n > 0) return launch_pts_shadows_t<MODE, EXTRA>(L);                  // sr_shadow_points: the caller's points, no rows, no pixels
     if (L.hits_req) return launch_hits_t<MODE, EXTRA>(L);                          // sr_render_hits: the rows' camera samples, no pixels
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;

@@ -212,6 +212,11 @@ public:
     Renderer& operator=(const Renderer&) = delete;
     void Dispose() { if (scene_) { sr_destroy(scene_); scene_ = nullptr; } }   // Renderer.cs:236
     void ResetAmbientOcclusionCache() { sr_check(sr_reset_ao_cache(scene_)); }   // what a new Renderer's AmbientOcclusionMethod starts with
+    // the static shadow cache (rayTraceShadowsStatic): 128^3 bytes in [x][y][z] order, 0 = empty -- the content of the reference's
+    // softShadow_..._res128.cache file (Texture3DCache.SaveCacheToDisk / LoadCacheFromDisk); a new model drops what was set
+    static constexpr size_t StaticShadowCacheBytes = (size_t)128 * 128 * 128;
+    void GetStaticShadowCache(uint8_t* out) { sr_check(sr_get_shadow_cache(scene_, out)); }
+    void SetStaticShadowCache(const uint8_t* in) { sr_check(sr_set_shadow_cache(scene_, in)); }
     // Renderer.cs:420-446: true (the default, as in the reference) = LightFieldTriMethod, which Render() refuses; false = the colour light
     // field, passed on as SR_F_LIGHT_FIELD.  Setting another value disposes of both methods: the light field starts empty again
     bool LightFieldStoresTriangles() const { return lightFieldHasTris_; }
@@ -374,6 +379,28 @@ public:
         sr_frame f = BuildFrame(inst);
         f.flags &= ~(uint32_t)SR_F_PRIMARY_STATS_ONLY;     // (the call has no primary rays: sr_last_ray_stats gets the shadow stage's counters)
         sr_check(sr_shadow_points(scene_, &f, n, pos, normal, color, out, coherent ? SR_POINTS_COHERENT : 0u));
+    }
+    // ShadowMethod's static branch for n surface points of the caller, in input order (sr_static_shadow_points): the first point of an empty
+    // cell of the renderer's static shadow cache -- the one its rayTraceShadowsStatic frames fill -- generates the cell's byte, amount[i] = the
+    // byte of point i's cell, out[i] = color[i] (nullptr: 0xFFFFFFFF) modulated with it; either output may be nullptr, not both.  Light, samples
+    // and root geometry are those of the frame Render() would build for the first instance; rayTraceShadows and rayTraceShadowsStatic are
+    // implied.  coherent: SR_POINTS_COHERENT.  Returns the number of generators (0 without a model or points).  Ambient occlusion, path
+    // tracing, voxels, the light field and mirror bounces are refused by the library, by name
+    uint64_t StaticShadowPoints(int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, uint8_t* amount,
+                                bool coherent = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel() || n == 0) return 0;
+        if (Instances.empty()) throw InvalidOperationException("StaticShadowPoints: no instance to take the pose from");
+        Instance& inst = *Instances.front();
+        inst.FieldOfViewDepth = fieldOfViewDepth_;
+        PreCalculate();
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_frame f = BuildFrame(inst);
+        f.flags &= ~(uint32_t)SR_F_PRIMARY_STATS_ONLY;     // (the call has no primary rays: sr_last_ray_stats gets the shadow stage's counters)
+        uint64_t generators = 0;
+        sr_check(sr_static_shadow_points(scene_, &f, n, pos, normal, color, out, amount, coherent ? SR_POINTS_COHERENT : 0u, &generators));
+        return generators;
     }
     // AmbientOcclusionMethod's occlusion byte for n surface points of the caller, in input order (sr_ao_points): amount[i] = the byte, out[i] =
     // color[i] (nullptr: 0xFFFFFFFF) modulated with it; either output may be nullptr, not both.  The root geometry, the seed and the cache

@@ -236,6 +236,19 @@ class GpuScene:
         """Forget the static shadow cache (SR_F_STATIC_SHADOWS): what a new Renderer starts with."""
         _check(_lib.lib().sr_reset_shadow_cache(self._h))
 
+    def get_shadow_cache(self):
+        """The static shadow cache as uint8 [128, 128, 128] in x, y, z order (0 = empty cell): the bytes of the reference's
+        softShadow_..._res128.cache file."""
+        out = np.zeros((_lib.AO_RES,) * 3, dtype=np.uint8)
+        _check(_lib.lib().sr_get_shadow_cache(self._h, _p(out)))
+        return out
+
+    def set_shadow_cache(self, cache):
+        cache = np.ascontiguousarray(cache, dtype=np.uint8)
+        if cache.size != _lib.AO_RES ** 3:
+            raise ValueError("the static shadow cache is %d^3 bytes" % _lib.AO_RES)
+        _check(_lib.lib().sr_set_shadow_cache(self._h, _p(cache)))
+
     # ---- rayTraceAmbientOcclusion (SR_F_AMBIENT_OCCLUSION frames) ----
     def reset_ao_cache(self):
         """Forget the ambient-occlusion cache: what a new Renderer starts with."""
@@ -398,6 +411,37 @@ class GpuScene:
         st = getattr(stream, "cuda_stream", stream)
         _check(_lib.lib().sr_shadow_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out),
                                                   _lib.POINTS_COHERENT if coherent else 0, vp(st), vp(d_stats_ptr)))
+
+    def static_shadow_points(self, frame, pos, normal, color=None, coherent=False, want_out=True, want_amount=True):
+        """ShadowMethod's static branch for caller-given surface points, in input order (sr_static_shadow_points): (out uint32 [n] or None,
+        amount uint8 [n] or None, generators).  The first point of an empty cell of the scene's static shadow cache generates the cell's
+        byte; every point reads its cell.  color None: every point 0xFFFFFFFF.  coherent: the generators of a pass are neighbours in input
+        order (no sort)."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+        if normal.shape[0] != pos.shape[0]:
+            raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
+        if color is not None:
+            color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
+            if color.size != pos.shape[0]:
+                raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
+        out = np.zeros(pos.shape[0], dtype=np.uint32) if want_out else None
+        amount = np.zeros(pos.shape[0], dtype=np.uint8) if want_amount else None
+        made = C.c_uint64(0)
+        _check(_lib.lib().sr_static_shadow_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out), _p(amount),
+                                                  _lib.POINTS_COHERENT if coherent else 0, C.byref(made)))
+        return out, amount, int(made.value)
+
+    def static_shadow_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, d_amount, coherent=False, stream=0, d_generators_ptr=None,
+                                    d_stats_ptr=None):
+        """sr_static_shadow_points_device: every array is a DEVICE pointer (d_color 0 / None: every point 0xFFFFFFFF; d_out may be d_color; one
+        of d_out / d_amount may be 0 / None; d_generators_ptr: a device uint64 or None); enqueued on `stream` (a raw hipStream_t or a
+        torch.cuda.Stream), no host sync."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = getattr(stream, "cuda_stream", stream)
+        _check(_lib.lib().sr_static_shadow_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out),
+                                                         vp(d_amount), _lib.POINTS_COHERENT if coherent else 0, vp(st), vp(d_generators_ptr),
+                                                         vp(d_stats_ptr)))
 
     def ao_points(self, frame, pos, normal, color=None, first_generator=0, want_out=True, want_amount=True):
         """AmbientOcclusionMethod's step for caller-given surface points, in input order (sr_ao_points): (out uint32 [n] or None, amount

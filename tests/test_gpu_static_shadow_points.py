@@ -1,0 +1,384 @@
+"""sr_static_shadow_points on the GPU against the CPU model (tests/static_shadow_points_model.py, which tests/test_static_shadow_points_model.py
+pins to the reference's two static goldens): every comparison is an exact equality -- out, amount, the number of generators and the 128^3 cache
+read back with sr_get_shadow_cache.  Inputs: the 6 716 hit points of the 100x100 obj.3DS frame in a static frame's fill order, and the point set
+of tests/test_gpu_shadow_points.py (imported: hit points, points outside the cube, zero / non-unit / flipped normals, 40 copies of one point)
+with shadow_points_model.bad_points() mixed in."""
+import numpy as np
+import pytest
+import torch
+
+import lightfield_model as lfm
+import shadow_points_model as spm
+import softray_amd as sa
+import static_shadow_points_model as ssm
+import test_gpu_shadow_points as tsp
+from helpers import camera_rays, load_obj3ds, make_frame, orc
+
+pytestmark = pytest.mark.gpu
+L = sa._lib
+DEV = torch.device("cuda", 0)
+MODES = tsp.MODES
+TARGET = lfm.TRACE_ROOT_TREE
+GUARD = tsp.GUARD
+
+
+def as_sr(frame, mode="bvh", extra_flags=0):
+    return tsp.as_sr(frame, mode, extra_flags)
+
+
+def same(got, want):
+    got, want = np.asarray(got), np.asarray(want)
+    return got.shape == want.shape and int(np.count_nonzero(got != want)) == 0
+
+
+def cache_of(g):
+    return g.get_shadow_cache().reshape(-1)
+
+
+class Golden:
+    """The golden-order points of obj.3DS, the model's answers for them (computed once, read-only) and one scene on the device."""
+
+    def __init__(self):
+        self.o = orc.Scene()
+        self.o.set_triangles(*load_obj3ds())
+        assert self.o.build_tree() == 0
+        self.frame = make_frame(100, 100, shadows=True)
+        origin, dirs = camera_rays(self.frame)
+        res = self.o.trace(TARGET, np.broadcast_to(origin, dirs.shape).copy(), dirs)
+        hit = res["hit"].astype(bool)
+        order = ssm.golden_order(100, 100)
+        self.pix = order[hit[order]]
+        self.pos, self.nrm = np.ascontiguousarray(res["pos"][self.pix]), np.ascontiguousarray(res["normal"][self.pix])
+        self.color = orc.shade_points(self.frame, self.pos, self.nrm, res["color"][self.pix])
+        self.n = self.pix.size
+        self.cache = np.zeros(ssm.CELLS, dtype=np.uint8)
+        self.amount, self.out, self.made = ssm.static_shadow_points(self.o, self.frame, self.pos, self.nrm, TARGET, self.cache, self.color)
+        for a in (self.pos, self.nrm, self.color, self.cache, self.amount, self.out):
+            a.setflags(write=False)
+        self.g = sa.GpuScene(0)
+        self.g.set_triangles(*load_obj3ds())
+        self.g.build((sa.MODE_REF_TREE, sa.MODE_BVH))
+
+    def fresh(self):
+        self.g.reset_shadow_cache()
+        return self.g
+
+
+@pytest.fixture(scope="module")
+def golden():
+    G = Golden()
+    assert G.n == 6716 and G.made == 5603
+    return G
+
+
+@pytest.fixture(scope="module")
+def cases():
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = tsp.Case(name)
+        return made[name]
+    return get
+
+
+def run_device(g, f, pos, nrm, color, coherent=False, stream=None, alias=False, want_out=True, want_amount=True, pad=64):
+    """The device variant on torch tensors: dict of out, amount, the guard words behind both, generators, stats."""
+    n = pos.shape[0]
+    d_pos = torch.from_numpy(np.array(pos, dtype=np.float64)).to(DEV)         # (copies: the fixtures' arrays are read-only)
+    d_nrm = torch.from_numpy(np.array(nrm, dtype=np.float64)).to(DEV)
+    d_out = torch.full((n + pad,), GUARD, dtype=torch.int32, device=DEV)
+    d_amt = torch.full((n + pad,), 0x5A, dtype=torch.uint8, device=DEV)
+    d_col = None
+    if color is not None:
+        if alias:
+            d_out[:n] = torch.from_numpy(color.view(np.int32).copy()).to(DEV)
+            d_col = d_out
+        else:
+            d_col = torch.from_numpy(color.view(np.int32).copy()).to(DEV)
+    d_gen = torch.full((3,), -7, dtype=torch.int64, device=DEV)               # the word in the middle is the call's
+    d_stats = torch.full((24 + 2,), -1, dtype=torch.int64, device=DEV)
+    torch.cuda.synchronize(DEV)
+    g.static_shadow_points_device(f, n, d_pos.data_ptr(), d_nrm.data_ptr(), d_col.data_ptr() if d_col is not None else 0,
+                                  d_out.data_ptr() if want_out else 0, d_amt.data_ptr() if want_amount else 0, coherent=coherent,
+                                  stream=stream if stream is not None else 0, d_generators_ptr=d_gen.data_ptr() + 8, d_stats_ptr=d_stats.data_ptr() + 8)
+    if stream is not None:
+        stream.synchronize()
+    torch.cuda.synchronize(DEV)
+    out, amt, gen, stats = d_out.cpu().numpy().view(np.uint32), d_amt.cpu().numpy(), d_gen.cpu().numpy(), d_stats.cpu().numpy()
+    assert gen[0] == -7 and gen[2] == -7 and stats[0] == -1 and stats[25] == -1
+    return dict(out=out[:n], out_guard=out[n:], amount=amt[:n], amount_guard=amt[n:], generators=int(gen[1]), stats=stats[1:25].view(np.uint64))
+
+
+# ---- 1. the golden-order points, every walk ----
+VARIANTS = {"tree": ("tree", 0), "tree_literal_secondary": ("tree", L.F_LITERAL_SECONDARY), "brute": ("brute", 0), "bvh": ("bvh", 0),
+            "bvh_per_lane_shadows": ("bvh", L.F_PER_LANE_SHADOWS)}
+
+
+@pytest.mark.parametrize("coherent", [False, True], ids=["sorted", "coherent"])
+@pytest.mark.parametrize("variant", sorted(VARIANTS))
+def test_golden_order_points_equal_the_model(golden, variant, coherent):
+    mode, flags = VARIANTS[variant]
+    g = golden.fresh()
+    out, amount, made = g.static_shadow_points(as_sr(golden.frame, mode, flags), golden.pos, golden.nrm, golden.color, coherent=coherent)
+    assert made == golden.made
+    assert same(amount, golden.amount) and same(out, golden.out) and same(cache_of(g), golden.cache)
+    stats = g.ray_stats()
+    assert not stats[:4].any() and int(stats[4]) > 0                          # no primary rays; the generators' shadow rays
+
+
+def test_outputs_are_each_optional_and_white_without_colours(golden):
+    f = as_sr(golden.frame)
+    k = 1500
+    out, amount, made = golden.fresh().static_shadow_points(f, golden.pos[:k], golden.nrm[:k], None)
+    want_amount = golden.amount[:k]                                           # a prefix of the batch is the batch's own first k answers
+    assert same(amount, want_amount) and same(out, spm.ao_model.modulate(np.full(k, 0xFFFFFFFF, dtype=np.uint32), want_amount))
+    out2, none, made2 = golden.fresh().static_shadow_points(f, golden.pos[:k], golden.nrm[:k], golden.color[:k], want_amount=False)
+    assert none is None and made2 == made and same(out2, golden.out[:k])
+    none, amount3, made3 = golden.fresh().static_shadow_points(f, golden.pos[:k], golden.nrm[:k], golden.color[:k], want_out=False)
+    assert none is None and made3 == made and same(amount3, want_amount)
+
+
+# ---- 2. the point set of sr_shadow_points' tests, with points that are not finite, both lights, four sample counts ----
+def frame_for(c, name, point_light, samples):
+    if not point_light:
+        return tsp.directional(c, samples)
+    f = orc.Frame.from_buffer_copy(bytes(make_frame(48, 40, shadows=True, shadow_samples=samples)))
+    if name == "cube":                                                       # the seed's table (radius 0.2) around the cube scene's light
+        t = [f.transform[i] for i in range(12)]
+        m = tsp.EDGE["light"]
+        for r in range(3):
+            f.light_pos_view[r] = t[4 * r] * m[0] + t[4 * r + 1] * m[1] + t[4 * r + 2] * m[2] + t[4 * r + 3]
+    return f
+
+
+def mixed_points(c):
+    """The case's points with bad_points() at places of their own (none is dropped: the bad ones are inserted)."""
+    bpos, bnrm, _ = spm.bad_points()
+    rng = np.random.default_rng(11)
+    where = np.sort(rng.choice(c.n, bpos.shape[0], replace=False))
+    pos, nrm = np.insert(c.pos, where, bpos, axis=0), np.insert(c.nrm, where, bnrm, axis=0)
+    col = np.insert(c.color, where, c.color[where])
+    return np.ascontiguousarray(pos), np.ascontiguousarray(nrm), np.ascontiguousarray(col)
+
+
+@pytest.mark.parametrize("samples", [1, 17, 100, 130])
+@pytest.mark.parametrize("point_light", [True, False], ids=["point", "directional"])
+@pytest.mark.parametrize("name", ["obj", "cube"])
+def test_point_set_with_bad_points(cases, name, point_light, samples):
+    c = cases(name)
+    f = frame_for(c, name, point_light, samples)
+    pos, nrm, col = mixed_points(c)
+    cache = np.zeros(ssm.CELLS, dtype=np.uint8)
+    w_amount, w_out, w_made = ssm.static_shadow_points(c.o, f, pos, nrm, TARGET, cache, col)
+    cell = ssm.cells(pos)
+    assert w_made <= pos.shape[0] - 39 and np.count_nonzero(np.abs(c.pos).max(axis=1) > 0.5) > 50  # shared cells; points outside the cube
+    g = c.gpu()
+    for mode in ("bvh", "tree"):
+        g.reset_shadow_cache()
+        out, amount, made = g.static_shadow_points(as_sr(f, mode), pos, nrm, col)
+        bad = np.flatnonzero(amount != w_amount)
+        assert made == w_made and bad.size == 0, (mode, made, w_made, bad[:8], cell[bad[:8]])
+        assert same(out, w_out) and same(cache_of(g), cache)
+
+
+def test_brute_force_mode_on_the_point_set(cases):
+    """SR_MODE_BRUTE answers as the tree except where a probe end lies exactly on a triangle (the zero normals): the model asks the oracle's
+    brute-force root geometry."""
+    c = cases("cube")
+    pos, nrm, col = mixed_points(c)
+    cache = np.zeros(ssm.CELLS, dtype=np.uint8)
+    w_amount, w_out, w_made = ssm.static_shadow_points(c.brute, c.frame, pos, nrm, TARGET, cache, col)
+    g = c.gpu()
+    g.reset_shadow_cache()
+    out, amount, made = g.static_shadow_points(as_sr(c.frame, "brute"), pos, nrm, col, coherent=True)
+    assert made == w_made and same(amount, w_amount) and same(out, w_out) and same(cache_of(g), cache)
+
+
+# ---- 3. passes ----
+@pytest.mark.parametrize("pass_points", [256, 1000])
+def test_passes_give_the_single_pass_result(golden, pass_points):
+    g = golden.fresh()
+    g.debug_set(L.DBG_BAND_SAMPLES, pass_points)
+    try:
+        d = run_device(g, as_sr(golden.frame), golden.pos, golden.nrm, golden.color)
+        got_cache = cache_of(g).copy()
+    finally:
+        g.debug_set(L.DBG_BAND_SAMPLES, -1)
+    assert d["generators"] == golden.made and same(d["amount"], golden.amount) and same(d["out"], golden.out) and same(got_cache, golden.cache)
+    assert np.all(d["out_guard"] == GUARD) and np.all(d["amount_guard"] == 0x5A)
+
+
+@pytest.mark.parametrize("pass_points", [None, 1000])
+def test_batch_followed_by_its_reverse_generates_nothing_in_the_second_half(golden, pass_points):
+    g = golden.fresh()
+    k = 3000
+    pos = np.concatenate([golden.pos[:k], golden.pos[:k][::-1]])
+    nrm = np.concatenate([golden.nrm[:k], golden.nrm[:k][::-1]])
+    col = np.concatenate([golden.color[:k], golden.color[:k][::-1]])
+    first_made = int(ssm.generators_of(ssm.cells(golden.pos[:k]), np.zeros(ssm.CELLS, dtype=np.uint8)).sum())
+    if pass_points:
+        g.debug_set(L.DBG_BAND_SAMPLES, pass_points)
+    try:
+        out, amount, made = g.static_shadow_points(as_sr(golden.frame), pos, nrm, col)
+    finally:
+        g.debug_set(L.DBG_BAND_SAMPLES, -1)
+    assert made == first_made
+    assert same(amount[:k], golden.amount[:k]) and same(amount[k:], golden.amount[:k][::-1])
+    assert same(out[:k], golden.out[:k]) and same(out[k:], golden.out[:k][::-1])
+    assert int(np.count_nonzero(cache_of(g))) == first_made
+
+
+# ---- 4. split and warm ----
+def test_two_half_calls_equal_the_one_call_and_a_repeat_generates_nothing(golden):
+    g = golden.fresh()
+    f = as_sr(golden.frame)
+    h = golden.n // 2 + 37
+    a = g.static_shadow_points(f, golden.pos[:h], golden.nrm[:h], golden.color[:h])
+    b = g.static_shadow_points(f, golden.pos[h:], golden.nrm[h:], golden.color[h:])
+    assert a[2] + b[2] == golden.made and a[2] > 0 and b[2] > 0
+    assert same(np.concatenate([a[0], b[0]]), golden.out) and same(np.concatenate([a[1], b[1]]), golden.amount) and same(cache_of(g), golden.cache)
+    out, amount, made = g.static_shadow_points(f, golden.pos, golden.nrm, golden.color)
+    stats = g.ray_stats()
+    assert made == 0 and int(stats[4]) == 0 and not stats.any()
+    assert same(out, golden.out) and same(amount, golden.amount) and same(cache_of(g), golden.cache)
+    d = run_device(g, f, golden.pos, golden.nrm, golden.color)
+    assert d["generators"] == 0 and not d["stats"].any() and same(d["out"], golden.out)
+
+
+# ---- 5. one cache with the static frames ----
+def static_frame(mode="bvh", **kw):
+    return as_sr(make_frame(100, 100, shadows=True, static_shadows=True, **kw), mode)
+
+
+@pytest.mark.parametrize("mode", ["bvh", "tree"])
+def test_cache_is_shared_with_static_frames(golden, mode):
+    g = golden.fresh()
+    fs = static_frame(mode)
+    want_px = g.render(fs)[0].copy()                                          # the frame from a fresh cache
+    assert same(cache_of(g), golden.cache)                                    # ... fills what the model fills
+    # frame first, then the points: nothing is generated
+    out, amount, made = g.static_shadow_points(as_sr(golden.frame, mode), golden.pos, golden.nrm, golden.color)
+    assert made == 0 and same(out, golden.out) and same(amount, golden.amount)
+    # points first, then the frame of the same pose: the frame leaves the cache as it is and is the frame from a fresh cache
+    g.reset_shadow_cache()
+    assert not cache_of(g).any()
+    assert g.static_shadow_points(as_sr(golden.frame, mode), golden.pos, golden.nrm, golden.color)[2] == golden.made
+    before = cache_of(g).copy()
+    assert same(g.render(fs)[0], want_px) and same(cache_of(g), before) and same(before, golden.cache)
+    px = want_px.reshape(-1)
+    assert same(px[golden.pix], golden.out)                                   # the frame's hit pixels are the call's colours
+
+
+def test_set_cache_then_frame_and_set_then_get(golden):
+    want_px = golden.fresh().render(static_frame())[0].copy()
+    g = sa.GpuScene(0)
+    g.set_triangles(*load_obj3ds())
+    g.build((sa.MODE_BVH,))
+    assert not cache_of(g).any()                                              # a scene that never rendered a static frame reads zeros
+    g.set_shadow_cache(golden.cache)
+    assert same(cache_of(g), golden.cache)
+    assert same(g.render(static_frame())[0], want_px) and same(cache_of(g), golden.cache)          # the frame does not zero what was set
+    out, amount, made = g.static_shadow_points(as_sr(golden.frame), golden.pos, golden.nrm, golden.color)
+    assert made == 0 and same(amount, golden.amount)
+    marked = golden.cache.copy()
+    marked[golden.cache != 0] = 77                                            # bytes no shadow ray made: the frame must read them, not regenerate
+    g.set_shadow_cache(marked)
+    out, amount, made = g.static_shadow_points(as_sr(golden.frame), golden.pos, golden.nrm, None)
+    assert made == 0 and np.all(amount == 77)
+    g.reset_shadow_cache()
+    assert not cache_of(g).any()
+    g.set_shadow_cache(marked)
+    g.set_triangles(*load_obj3ds())                                           # a new model drops what was set
+    g.build((sa.MODE_BVH,))
+    assert not cache_of(g).any()
+
+
+# ---- 6. the device variant ----
+def test_device_variant_on_a_stream(golden):
+    g = golden.fresh()
+    f = as_sr(golden.frame)
+    st = torch.cuda.Stream(DEV)
+    torch.cuda.synchronize(DEV)
+    big = torch.ones((2048, 2048), dtype=torch.float64, device=DEV)
+    with torch.cuda.stream(st):
+        busy = big @ big                                                      # the call is enqueued behind work that is still running
+        d = run_device(g, f, golden.pos, golden.nrm, golden.color, stream=st, alias=True)
+    assert float(busy[0, 0]) == 2048.0
+    assert d["generators"] == golden.made and same(d["out"], golden.out) and same(d["amount"], golden.amount) and same(cache_of(g), golden.cache)
+    assert np.all(d["out_guard"] == GUARD) and np.all(d["amount_guard"] == 0x5A)
+    host = golden.fresh().static_shadow_points(f, golden.pos, golden.nrm, golden.color)
+    assert host[2] == golden.made and np.array_equal(d["stats"], g.ray_stats())
+    assert not d["stats"][:4].any() and int(d["stats"][4]) > 0
+    quiet = as_sr(golden.frame, extra_flags=L.F_PRIMARY_STATS_ONLY)
+    d = run_device(golden.fresh(), quiet, golden.pos, golden.nrm, None, stream=st, want_out=False)
+    assert d["generators"] == golden.made and same(d["amount"], golden.amount) and not d["stats"].any()
+    assert np.all(d["out"] == GUARD)                                          # an output that was not asked for is not written
+    d = run_device(golden.fresh(), f, golden.pos, golden.nrm, golden.color, stream=st, want_amount=False)
+    assert same(d["out"], golden.out) and np.all(d["amount"] == 0x5A)
+
+
+def test_multi_device_scene_keeps_the_cache_on_its_first_device(golden):
+    g = sa.GpuScene(devices=[0, 0])
+    g.set_triangles(*load_obj3ds())
+    g.build((sa.MODE_BVH,))
+    out, amount, made = g.static_shadow_points(as_sr(golden.frame), golden.pos, golden.nrm, golden.color)
+    assert made == golden.made and same(out, golden.out) and same(amount, golden.amount) and same(cache_of(g), golden.cache)
+    assert int(g.ray_stats()[4]) > 0
+
+
+# ---- 7. the chain on the device is the static frame ----
+def device_chain(g, plain, conc):
+    """hits -> ShadingMethod -> the static frame's fill order (a permutation made in torch) -> sr_static_shadow_points_device -> scatter and
+    resolve, on the null stream with nothing read back in between: uint32 [height, width]."""
+    n = sa.GpuScene.sample_count(plain)
+    nn = plain.sub_pixel_res * plain.sub_pixel_res
+    d_hit = torch.empty(n, dtype=torch.uint8, device=DEV)
+    d_pos = torch.empty((n, 3), dtype=torch.float64, device=DEV)
+    d_nrm = torch.empty((n, 3), dtype=torch.float64, device=DEV)
+    d_col = torch.empty(n, dtype=torch.int32, device=DEV)
+    g.render_hits_device(plain, d_hit=d_hit.data_ptr(), d_pos=d_pos.data_ptr(), d_normal=d_nrm.data_ptr(), d_color=d_col.data_ptr())
+    idx = torch.nonzero(d_hit, as_tuple=False).reshape(-1)
+    W, H = plain.width, plain.height
+    block_height = (H - 1 + conc) // conc
+    blocks = (H - 1 + block_height) // block_height
+    si, pixel = idx % nn, idx // nn
+    row, col = pixel // W, pixel % W
+    key = (((row % block_height) * blocks + row // block_height) * W + col) * nn + si
+    idx = idx[torch.argsort(key)]                                             # the keys are distinct
+    k = int(idx.numel())
+    hp, hn, hc = d_pos[idx].contiguous(), d_nrm[idx].contiguous(), d_col[idx].contiguous()
+    bg = (plain.background_argb | 0xFF000000) & 0xFFFFFFFF
+    samples = torch.full((n,), bg - (1 << 32) if bg >= (1 << 31) else bg, dtype=torch.int32, device=DEV)
+    d_gen = torch.zeros(1, dtype=torch.int64, device=DEV)
+    g.shade_points_device(plain, k, hp.data_ptr(), hn.data_ptr(), hc.data_ptr(), hc.data_ptr())
+    g.static_shadow_points_device(plain, k, hp.data_ptr(), hn.data_ptr(), hc.data_ptr(), hc.data_ptr(), 0, d_generators_ptr=d_gen.data_ptr())
+    samples[idx] = hc
+    if nn == 1:
+        out = samples
+    else:
+        c = samples.reshape(-1, nn).to(torch.int64) & 0xFFFFFFFF
+        r, gr, b = ((c >> 16) & 255).sum(1) // nn, ((c >> 8) & 255).sum(1) // nn, (c & 255).sum(1) // nn
+        out = (0xFF000000 | (r << 16) | (gr << 8) | b).to(torch.int32)
+    torch.cuda.synchronize(DEV)
+    return out.cpu().numpy().view(np.uint32).reshape(H, W), k, int(d_gen.cpu()[0])
+
+
+@pytest.mark.parametrize("mode", ["bvh", "tree"])
+@pytest.mark.parametrize("shape", [(100, 100, 1, 4), (64, 48, 2, 3)], ids=["100x100_c4", "64x48_2x2_c3"])
+def test_chain_on_the_device_is_the_static_frame(golden, shape, mode):
+    W, H, sub, conc = shape
+    g = golden.fresh()
+    full = as_sr(make_frame(W, H, shadows=True, static_shadows=True, sub_pixel_res=sub, concurrency=conc), mode)
+    d_px = torch.zeros(W * H, dtype=torch.int32, device=DEV)
+    g.render_device(full, d_px.data_ptr())
+    torch.cuda.synchronize(DEV)
+    want = d_px.cpu().numpy().view(np.uint32).reshape(H, W)
+    want_cache = cache_of(g).copy()
+    g.reset_shadow_cache()
+    plain = as_sr(make_frame(W, H, sub_pixel_res=sub, concurrency=conc), mode)
+    got, k, made = device_chain(g, plain, conc)
+    assert k > 2000 and made == int(np.count_nonzero(want_cache)) and 0 < made < k
+    assert same(got, want) and same(cache_of(g), want_cache)
+    if sub == 1:
+        assert same(want_cache, golden.cache)                                 # the 100x100 frame: the goldens' cache

@@ -843,7 +843,9 @@ enum {
     SR_DBG_BVH_LEAF       = 5,   /* triangles per leaf of the own BVH, host and device build (default 4, 1..15); read by the next sr_build */
     SR_DBG_KERNEL_SWITCH  = 6,   /* A/B switch of single optimisations, same pixels (0 = production): 31 the bounce pipeline walks its rays in
                                     queue order (no per-level ray sort); 61 the camera-ordered node copy keeps (lo, hi) planes; 71 no facing
-                                    partition (the packet walks see every record of a leaf); 7 counts umbra decisions of the private shaft walk;
+                                    partition (the packet walks see every record of a leaf); 72 the camera- / light-ordered node copies keep the base tree's
+                                    boxes (not fitted to their live records), 73 / 74 only the camera / light copy is fitted, 75 .. 79 both on the lowest 1 .. 5
+                                    levels of the wide tree only; 7 counts umbra decisions of the private shaft walk;
                                     32 a mirror-bounce level as ONE kernel (k_bounce) instead of prepare / walk / finish; 33 the second rays of a path-traced SR_MODE_BVH frame with
                                     private per-lane walks (k_pt_finish) instead of the mirror extension's prepare / walk route; 34 the ambient-occlusion probes of a
                                     SR_MODE_BVH frame as nearest-hit walks instead of any-hit walks with the limit 2.0; 35 sr_bake_light_field on a

@@ -70,6 +70,10 @@ struct DBuf {
 
 }  // namespace
 
+// the ordered copies' boxes are fitted to their live records (tight_boxes_device) on the lowest kTightCut levels of the wide tree
+// (< 0: all of them); SR_DBG_KERNEL_SWITCH 72: neither copy, 73: the camera copy only, 74: the light copy only, 75 .. 79: both on the lowest 1 .. 5 levels
+constexpr int kTightNone = -2, kTightCut = -1;
+
 struct sr_scene {
     int device = -1;
     // sr_create_multi: this scene only dispatches to one complete scene per device (the model is replicated, a frame is split
@@ -118,6 +122,7 @@ struct sr_scene {
     int    b4_depth = 0;
     bool   b4cam_valid = false, b4light_valid = false;
     int    b4cam_known = 0, b4light_known = 0;   // axes on which the ordered copy holds (near, far) planes (sr_device.h)
+    int    b4cam_tight = kTightNone, b4light_tight = kTightNone;   // depth cut-off the copy's boxes were fitted with (sr_tight_boxes.h), kTightNone: the base boxes
     // k_facing_partition: the leaves' records grouped by which of {camera rays, shadow sample rays} can hit them, for one (origin, light)
     DBuf   d_rng_cam, d_rng_light;
     bool   part_valid = false, part_cam = false, part_light = false;
@@ -927,6 +932,24 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         s->part_valid = false; s->b4cam_valid = false; s->b4light_valid = false;        // (hook: no live runs -- the copies are re-made without them)
         s->blight_valid = false;
     }
+    // ---- the ordered copies' boxes, fitted to the live runs the partition left (sr_tight_boxes.h): part of making a copy, so it
+    //      re-runs exactly when b4cam_valid / b4light_valid fall.  A tree without level ranges (host build) and a copy without live runs
+    //      (SR_DBG_KERNEL_SWITCH 71) keep the base boxes ----
+    const auto tight_wanted = [&](const void* runs, bool light_copy) {
+        const int64_t sw = s->dbg[SR_DBG_KERNEL_SWITCH];
+        if (!runs || sw == 72 || sw == (light_copy ? 73 : 74) || s->b4_level_first.size() < 2 || s->b4_level_first.back() != (int)s->b4_num || !s->d_v9.p) return kTightNone;
+        return sw >= 75 && sw <= 79 ? (int)(sw - 74) : kTightCut;
+    };
+    const auto tighten = [&](void* copy, const void* runs, int cut) -> int {
+        int rc2;
+        hipEvent_t e0, e1;
+        if ((rc2 = next_events(s, sr::K_TIGHT_BOXES, e0, e1))) return rc2;
+        if (e0) SR_HIP(hipEventRecord(e0, stream));
+        SR_HIP(sr::tight_boxes_device((const sr::Bvh4Node*)s->d_b4.p, (sr::Bvh4Node*)copy, (int)s->b4_num, s->b4_level_first, runs, (const sr::Rec128*)s->d_btris.p,
+                                      (const double*)s->d_v9.p, (int)s->ntris, s->root, cut, stream));
+        if (e1) SR_HIP(hipEventRecord(e1, stream));
+        return SR_OK;
+    };
     // ---- interior bytes of the records in their final order (the shadow classification's umax shortcut) ----
     if (bvh_walks && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT) && s->d_bslab.p && !s->interior_valid) {
         SR_HIP(s->d_binter.reserve(s->ntris));
@@ -946,14 +969,22 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             for (int i = 0; i < 3; ++i) s->cam_origin[i] = fc.start_world[i];
             s->cam_valid = true;
         }
+        if (wide && s->b4cam_valid && s->b4cam_tight != tight_wanted((s->part_valid && s->part_cam) ? s->d_rng_cam.p : nullptr, false)) s->b4cam_valid = false;
         if (wide && !s->b4cam_valid) {                                // the four-wide nodes, children front to back for this origin
             rewrote = true;
             int known, swap;                                      // (a camera ABOVE the box on an axis looks towards smaller coordinates: hi first)
             point_outside_axes(s->root, fc.start_world, 0.0, known, swap);
             // the camera-ordered copy holds (near, far) planes only when that is true on ALL axes (one extra instantiation of k_primary, not seven)
             if (known != 7 || s->dbg[SR_DBG_KERNEL_SWITCH] == 61) known = swap = 0;
-            SR_HIP(sr::launch_order_nodes((const sr::Bvh4Node*)s->d_b4.p, (sr::Bvh4Node*)s->d_b4cam.p, (int)s->b4_num, s->root, fc.start_world, false, swap,
-                                          (s->part_valid && s->part_cam) ? s->d_rng_cam.p : nullptr, stream));
+            const void* runs = (s->part_valid && s->part_cam) ? s->d_rng_cam.p : nullptr;
+            const int cut = tight_wanted(runs, false);
+            if (cut != kTightNone) {                                  // boxes of the camera-live records only, then sorted where they lie
+                if ((rc = tighten(s->d_b4cam.p, runs, cut))) return rc;
+                SR_HIP(sr::launch_order_nodes((const sr::Bvh4Node*)s->d_b4cam.p, (sr::Bvh4Node*)s->d_b4cam.p, (int)s->b4_num, s->root, fc.start_world, false, swap, nullptr, stream));
+            } else {
+                SR_HIP(sr::launch_order_nodes((const sr::Bvh4Node*)s->d_b4.p, (sr::Bvh4Node*)s->d_b4cam.p, (int)s->b4_num, s->root, fc.start_world, false, swap, runs, stream));
+            }
+            s->b4cam_tight = cut;
             s->b4cam_known = known;
             s->b4cam_valid = true;
         }
@@ -962,14 +993,23 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     if (wide && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT)) {
         const bool same_light = s->b4_light[0] == fc.light_pos_model[0] && s->b4_light[1] == fc.light_pos_model[1] && s->b4_light[2] == fc.light_pos_model[2] &&
                                 s->b4_light_radius == fc.light_radius;
-        if (!s->b4light_valid || !same_light) {                       // ... and nearest-to-the-surface first for this light
+        const void* lruns = (s->part_valid && s->part_light) ? s->d_rng_light.p : nullptr;
+        if (!s->b4light_valid || !same_light || s->b4light_tight != tight_wanted(lruns, true)) {   // ... and nearest-to-the-surface first for this light
             rewrote = true;
             s->b4light_valid = false;
             int known, beyond;                                    // (a light BELOW the box on an axis: every shaft travels towards smaller coordinates there, hi first)
             point_outside_axes(s->root, fc.light_pos_model, fc.light_radius, known, beyond);
             if (s->dbg[SR_DBG_KERNEL_SWITCH] == 62) known = 0;                    // (hook: (lo, hi) planes on every axis)
-            SR_HIP(sr::launch_order_nodes((const sr::Bvh4Node*)s->d_b4.p, (sr::Bvh4Node*)s->d_b4light.p, (int)s->b4_num, s->root, fc.light_pos_model, true, known & ~beyond,
-                                          (s->part_valid && s->part_light) ? s->d_rng_light.p : nullptr, stream));
+            const int cut = tight_wanted(lruns, true);
+            if (cut != kTightNone) {                                  // boxes of the light-live records only
+                if ((rc = tighten(s->d_b4light.p, lruns, cut))) return rc;
+                SR_HIP(sr::launch_order_nodes((const sr::Bvh4Node*)s->d_b4light.p, (sr::Bvh4Node*)s->d_b4light.p, (int)s->b4_num, s->root, fc.light_pos_model, true,
+                                              known & ~beyond, nullptr, stream));
+            } else {
+                SR_HIP(sr::launch_order_nodes((const sr::Bvh4Node*)s->d_b4.p, (sr::Bvh4Node*)s->d_b4light.p, (int)s->b4_num, s->root, fc.light_pos_model, true, known & ~beyond,
+                                              lruns, stream));
+            }
+            s->b4light_tight = cut;
             s->b4light_known = known;
             for (int i = 0; i < 3; ++i) s->b4_light[i] = fc.light_pos_model[i];
             s->b4_light_radius = fc.light_radius;

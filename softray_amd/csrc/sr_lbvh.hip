@@ -7,6 +7,7 @@
 // FP64 triangle arithmetic and picks the nearest (ties -> lowest TriangleIndex) whatever the tree shape.  Boxes are
 // rounded outward (directed double->float conversion) and padded by 2^-16 * extent exactly like sr_host.cpp::store().
 #include "sr_device.h"
+#include "sr_tight_boxes.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -414,6 +415,109 @@ __global__ void __launch_bounds__(256) k_refit_nodes4(int first, int count, Bvh4
         }
         store_box(nd->ch[j].lo, nd->ch[j].hi, b);
     }
+}
+
+// ---- the ordered copies' boxes, fitted to the records their rays can hit (sr_tight_boxes.h has the rule) ----
+// One lane per (node, slot) of the nodes [first, first + count) of ONE level: the slot of the base tree goes to the copy `out` with its
+// live run applied (rng: k_facing_partition's (offset, count) per slot) and, when `tighten`, with the box of what is live below it -- a
+// leaf slot from its run's records (tri_box of the record's own vertices: the build's text, so the box is the one a build would make for
+// those triangles), an inner slot from the node it links to, which the launch before has finished in `out` (levels run deepest first,
+// like k_refit_nodes4: no communication inside a kernel).  k_order_nodes then sorts `out` in place.
+struct TightArgs {
+    const Bvh4Node* base;
+    Bvh4Node*       out;
+    int             num_wide;
+    const int2*     rng;
+    const Rec128*   btris;
+    const double*   v9;
+    int             ntris;
+    double          centre[3];
+    float           pad;
+};
+__device__ __forceinline__ void tight_slot(const TightArgs& A, int node, int slot, bool tighten) {
+    Bvh4Child ch = A.base[node].ch[slot];
+    if (ch.n > 0) {
+        const int2 r = A.rng[node * 4 + slot];
+        // (records outside the array, or a record that names no triangle: not a tree of this library -- the base box stays)
+        bool ok = tighten && ch.c >= 0 && ch.n <= A.ntris - ch.c;
+        if (ok && r.x >= 0 && r.y <= ch.n - r.x)
+            for (int k = 0; k < r.y; ++k) { const int tri = A.btris[ch.c + r.x + k].aux; ok = ok && tri >= 0 && tri < A.ntris; }
+        tight_leaf_slot(ch, r.x, r.y, ok, [&](int k) {
+            const double* p = A.v9 + (size_t)A.btris[k].aux * 9;
+            double lo[3], hi[3];
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = fmin(fmin(p[a], p[3 + a]), p[6 + a]);
+                hi[a] = fmax(fmax(p[a], p[3 + a]), p[6 + a]);
+            }
+            const FBox b = tri_box(lo, hi, A.centre, A.pad);
+            TightBox t;
+            for (int a = 0; a < 3; ++a) { t.lo[a] = b.lo[a]; t.hi[a] = b.hi[a]; }
+            return t;
+        });
+    } else if (ch.n == 0 && tighten && ch.c > node && ch.c < A.num_wide) {    // (children are numbered after their parent, one level down)
+        const Bvh4Node below = A.out[ch.c];
+        tight_inner_slot(ch, below);
+    }
+    A.out[node].ch[slot] = ch;
+}
+__global__ void __launch_bounds__(256) k_tight_level(TightArgs A, int first, int count, int tighten) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count * 4) return;
+    tight_slot(A, first + (t >> 2), t & 3, tighten != 0);
+}
+// The top of the tree -- levels [0, top.levels) of a few nodes each -- by ONE workgroup, deepest level first with a barrier between two
+// levels: a launch per level costs more than the level.  Levels below first_tight are re-made, the ones above only take their live runs.
+constexpr int kTightTopLevels = 16, kTightTopNodes = 4096, kTightTopThreads = 1024;
+struct TightTop { int levels; int first_tight; int first[kTightTopLevels + 1]; };
+__global__ void __launch_bounds__(kTightTopThreads) k_tight_top(TightArgs A, TightTop top) {
+    for (int lv = top.levels - 1; lv >= 0; --lv) {
+        const int first = top.first[lv], slots = (top.first[lv + 1] - first) * 4;
+        for (int t = threadIdx.x; t < slots; t += kTightTopThreads) tight_slot(A, first + (t >> 2), t & 3, lv >= top.first_tight);
+        __syncthreads();                                              // (one workgroup: its stores to `out` are visible to its lanes behind the barrier)
+    }
+}
+
+// cut: sr_tight_boxes.h's depth cut-off (< 0: every level).  level_first: collapse_bvh4_device's level ranges of the wide tree.
+hipError_t tight_boxes_device(const Bvh4Node* d_base, Bvh4Node* d_out, int num_wide, const std::vector<int>& level_first, const void* d_live_runs,
+                              const Rec128* d_btris, const double* d_v9, int ntris, const RootBox& root, int cut, hipStream_t stream) {
+    if (num_wide <= 0 || ntris <= 0 || !d_live_runs) return hipErrorInvalidValue;
+    if (level_first.size() < 2 || level_first.front() != 0 || level_first.back() != num_wide) return hipErrorInvalidValue;
+    for (size_t lv = 0; lv + 1 < level_first.size(); ++lv)
+        if (level_first[lv] > level_first[lv + 1]) return hipErrorInvalidValue;
+    double ext = 0;
+    for (int a = 0; a < 3; ++a) ext = std::max(ext, root.max[a] - root.min[a]);
+    TightArgs A;
+    A.base = d_base; A.out = d_out; A.num_wide = num_wide; A.rng = (const int2*)d_live_runs; A.btris = d_btris; A.v9 = d_v9; A.ntris = ntris;
+    for (int a = 0; a < 3; ++a) A.centre[a] = root.centre[a];
+    A.pad = (float)std::ldexp(ext > 0 ? ext : 1.0, -16);               // build_bvh_device's pad
+    const int levels = (int)level_first.size() - 1;
+    const int first_tight = tight_first_level(levels, cut);
+    // the levels the one-workgroup kernel takes: from the root down while they are small
+    int top = 0;
+    while (top < levels && top < kTightTopLevels && level_first[top + 1] <= kTightTopNodes) ++top;
+    // a level below them that is not re-made only copies: all of those in one launch (they are contiguous: [level_first[top], level_first[first_tight]))
+    const int T = 256;
+    for (int lv = levels - 1; lv >= std::max(top, first_tight); --lv) {
+        const int first = level_first[lv], count = level_first[lv + 1] - first;
+        if (count <= 0) continue;
+        hipLaunchKernelGGL(k_tight_level, dim3((unsigned)(((size_t)count * 4 + T - 1) / T)), dim3(T), 0, stream, A, first, count, 1);
+        LB_HIP(hipGetLastError());
+    }
+    if (first_tight > top) {
+        const int first = level_first[top], count = level_first[first_tight] - first;
+        if (count > 0) {
+            hipLaunchKernelGGL(k_tight_level, dim3((unsigned)(((size_t)count * 4 + T - 1) / T)), dim3(T), 0, stream, A, first, count, 0);
+            LB_HIP(hipGetLastError());
+        }
+    }
+    if (top > 0) {
+        TightTop tt;
+        tt.levels = top; tt.first_tight = first_tight;
+        for (int lv = 0; lv <= kTightTopLevels; ++lv) tt.first[lv] = level_first[std::min(lv, top)];
+        hipLaunchKernelGGL(k_tight_top, dim3(1), dim3(kTightTopThreads), 0, stream, A, tt);
+        LB_HIP(hipGetLastError());
+    }
+    return hipSuccess;
 }
 
 // ---- the four-wide tree of the packet walks, collapsed on the device (same rule as sr_host.cpp collapse_bvh4: a node takes its two

@@ -5399,21 +5399,8 @@ hipError_t launch_facing_partition(const Bvh4Node* base, int num_nodes, Rec128* 
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void k_order_nodes(const Bvh4Node* __restrict__ in, Bvh4Node* __restrict__ out, int n, float px, float py, float pz, int far_first,
-                                                     int swap_mask, const int2* __restrict__ rng) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    Bvh4Node nd = in[i];
-    if (rng) {                                                           // the live run of every leaf for this copy's rays (k_facing_partition)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (nd.ch[k].n > 0) {
-                const int2 r = rng[i * 4 + k];
-                nd.ch[k].c += r.x;
-                nd.ch[k].n = r.y > 0 ? r.y : -1;
-            }
-        }
-    }
+// one node of an ordered copy: slots sorted, planes re-arranged (k_order_nodes, k_order_nodes_inplace)
+__device__ __forceinline__ void order_node(Bvh4Node& nd, float px, float py, float pz, int far_first, int swap_mask) {
     float key[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -5448,12 +5435,45 @@ __global__ __launch_bounds__(256) void k_order_nodes(const Bvh4Node* __restrict_
             nd.ch[k].lo[2] = hx; nd.ch[k].hi[0] = hy; nd.ch[k].hi[1] = lz;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_order_nodes(const Bvh4Node* __restrict__ in, Bvh4Node* __restrict__ out, int n, float px, float py, float pz, int far_first,
+                                                     int swap_mask, const int2* __restrict__ rng) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    Bvh4Node nd = in[i];
+    if (rng) {                                                           // the live run of every leaf for this copy's rays (k_facing_partition)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (nd.ch[k].n > 0) {
+                const int2 r = rng[i * 4 + k];
+                nd.ch[k].c += r.x;
+                nd.ch[k].n = r.y > 0 ? r.y : -1;
+            }
+        }
+    }
+    order_node(nd, px, py, pz, far_first, swap_mask);
     out[i] = nd;
+}
+// (in place: the node array the tightening step made, sr_tight_boxes.h -- its live runs are applied already.  A lane reads its whole node
+// before it writes it, and no lane reads another's.)
+__global__ __launch_bounds__(256) void k_order_nodes_inplace(Bvh4Node* nodes, int n, float px, float py, float pz, int far_first, int swap_mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    Bvh4Node nd = nodes[i];
+    order_node(nd, px, py, pz, far_first, swap_mask);
+    nodes[i] = nd;
 }
 
 hipError_t launch_order_nodes(const Bvh4Node* in, Bvh4Node* out, int num_nodes, const RootBox& root, const double point[3], bool far_first, int swap_mask,
                               const void* live_runs, hipStream_t stream) {
     if (num_nodes <= 0) return hipSuccess;
+    if (in == out) {                                                      // the tightened node array (tight_boxes_device), sorted where it lies
+        if (live_runs) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_order_nodes_inplace, dim3((unsigned)((num_nodes + 255) / 256)), dim3(256), 0, stream, out, num_nodes,
+                           (float)(point[0] - root.centre[0]), (float)(point[1] - root.centre[1]), (float)(point[2] - root.centre[2]), far_first ? 1 : 0, swap_mask);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_order_nodes, dim3((unsigned)((num_nodes + 255) / 256)), dim3(256), 0, stream, in, out, num_nodes,
                        (float)(point[0] - root.centre[0]), (float)(point[1] - root.centre[1]), (float)(point[2] - root.centre[2]), far_first ? 1 : 0, swap_mask,
                        (const int2*)live_runs);

@@ -118,6 +118,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern long sr_frame_sample_count(ref SrFrame frame);
         [DllImport(Lib)] public static extern int sr_render_hits(IntPtr scene, ref SrFrame frame, [Out] double[] starts, [Out] double[] dirs, [Out] byte[] hit, [Out] double[] rayFrac, [Out] double[] pos, [Out] double[] normal, [Out] uint[] color, [Out] int[] triIndex, [Out] ulong[] stats4);
         [DllImport(Lib)] public static extern int sr_render_hits_device(IntPtr scene, ref SrFrame frame, IntPtr dStarts, IntPtr dDirs, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, IntPtr hipStream, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_trace_origin_rays(IntPtr scene, int target, [In] double[] origin3, long n, [In] double[] dirs, [Out] byte[] hit, [Out] double[] rayFrac, [Out] double[] pos, [Out] double[] normal, [Out] uint[] color, [Out] int[] triIndex, uint options, [Out] ulong[] stats4);
+        [DllImport(Lib)] public static extern int sr_trace_origin_rays_device(IntPtr scene, int target, [In] double[] origin3, long n, IntPtr dDirs, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -577,6 +579,30 @@ namespace Engine3D.Hip
             FillFrame(width, height, instance, transform, inverseTransform, 0, flags, mode, startRow, endRow, subPixelRes, 0,
                       fieldOfViewDepth, focalDepth, focalBlurStrength, 0.0, 0.0, new Vector(0, 0, 1), new Vector(0, 0, 0), 4);
             Native.Check(Native.sr_render_hits_device(scene, ref frame, dStarts, dDirs, dHit, dRayFrac, dPos, dNormal, dColor, dTriIndex, stream, dStats));
+        }
+
+        /// Nearest hits of a batch of rays that start in one point (sr_trace_origin_rays): bit for bit what IntersectRay answers for
+        /// (origin, dirs[i]) on the root geometry (root = true) or the model alone, on the packet walk of a frame's camera rays.  dirs is
+        /// double[n * 3], not normalised; coherent: every 64 consecutive rays are neighbours (an image in 8x8-tile-major order).  The call
+        /// re-keys the scene's per-origin records to `origin`, as a camera move does.  Blocks.
+        public const uint RAYS_COHERENT = 1;
+        public FrameHits TraceOriginRays(Vector origin, double[] dirs, int mode, bool root = false, bool coherent = false)
+        {
+            long n = dirs.Length / 3;
+            var r = new FrameHits { Hit = new byte[n], RayFrac = new double[n], Pos = new double[n * 3], Normal = new double[n * 3],
+                                    Color = new uint[n], TriIndex = new int[n], Stats4 = new ulong[4] };
+            Native.Check(Native.sr_trace_origin_rays(scene, mode | (root ? 0x100 : 0), new[] { origin.x, origin.y, origin.z }, n, dirs, r.Hit, r.RayFrac, r.Pos,
+                                                     r.Normal, r.Color, r.TriIndex, coherent ? RAYS_COHERENT : 0, r.Stats4));
+            return r;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_trace_origin_rays_device), IntPtr.Zero for an output that is not
+        /// wanted; `origin` stays a host value; enqueued on `stream` without a host synchronisation; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void TraceOriginRaysDevice(Vector origin, long n, IntPtr dDirs, int mode, bool root, bool coherent, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos,
+                                          IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, IntPtr stream, IntPtr dStats)
+        {
+            Native.Check(Native.sr_trace_origin_rays_device(scene, mode | (root ? 0x100 : 0), new[] { origin.x, origin.y, origin.z }, n, dDirs, dHit, dRayFrac, dPos,
+                                                            dNormal, dColor, dTriIndex, coherent ? RAYS_COHERENT : 0, stream, dStats));
         }
 
         /// ShadingMethod's colour step for n recorded intersections in DEVICE memory (sr_shade_points_device): dOut[i] = dColor[i] modulated with

@@ -542,6 +542,49 @@ int  sr_trace_rays_device(sr_scene*, int32_t target, int64_t n, const double* d_
                           uint8_t* d_hit, double* d_ray_frac, double* d_pos, double* d_normal, uint32_t* d_color,
                           int32_t* d_tri_index, int32_t* d_counters, void* hip_stream);
 
+/* A batch of rays that START IN ONE POINT, on the walk a frame's camera rays take: for every i and every non-NULL output the result is bit
+ * for bit what sr_trace_rays(scene, target, n, starts, dirs, ...) answers with starts[i] = origin for all i -- same conventions (a miss
+ * writes hit 0, zeros and tri_index -1; a hit on extra geometry has tri_index -1 and the primitive's colour; `color` is unshaded), dirs is
+ * [n][3] and need not be normalised, every output is optional (all NULL: the call runs for the statistics).  What differs is the speed: in
+ * SR_MODE_BVH the per-origin records of a frame are set up for `origin` (facing partition, camera-cone records, fitted boxes, the ordered
+ * four-wide copy, with (near, far) planes when the origin is outside the root box's slab on all three axes: sr_debug_counters[5]) and 64
+ * rays at a time share one packet walk.  Panoramas, cube-map faces, lens models, foveated sample sets, scans.
+ * target: SR_MODE_* (the model alone) or SR_TARGET_ROOT | SR_MODE_*; SR_TARGET_VOXELS is SR_ERR_UNSUPPORTED.  SR_MODE_REF_TREE and
+ * SR_MODE_BRUTE trace every ray with a private walk, as sr_trace_rays does, and so does SR_MODE_BVH under SR_DBG_PER_LANE_PRIMARY;
+ * SR_DBG_BVH2_PACKETS selects the binary-tree packets, as in a frame.
+ * Order: SR_RAYS_COHERENT (options bit 0) is the caller's promise that every run of 64 consecutive rays is a bundle of neighbours (an image
+ * in 8x8-tile-major order, say): wave w of a pass takes rays 64 w .. 64 w + 63 as given.  Without it a pass is first ordered by direction
+ * (the cell of the unit direction in an octahedral map of 2^12 x 2^12 cells, Morton-interleaved; a stable radix sort).  Results never depend
+ * on the option or on the order; speed does.  Other option bits: SR_ERR_INVALID_ARG.
+ * A ray is REGULAR when its three components are finite and 2^-40 <= max |d_k| <= 2^40: the fp32 margins of the packet walk's slab tests
+ * and cone filter scale with |d| and hold in that range.  Every other ray (the zero vector, NaN, +-inf, 1e300, 1e-300) never enters a
+ * packet: it goes to the end of its pass (also with SR_RAYS_COHERENT) and is traced by the function sr_trace_rays calls.
+ * origin: HOST memory in both variants; not finite: SR_ERR_INVALID_ARG; any finite point is legal -- inside the root box, outside it, on a
+ * triangle's plane.  The camera-cone records are FP64 cross products of (vertex - origin) rounded once to fp32 and evaluated in fp32 against
+ * the direction: with the origin further from the root box's centre than 2^20 box diagonals on some axis the FP64 rounding of
+ * (vertex - origin) is no longer far below the filter's fp32 margin, and beyond 2^42 a product with a regular direction can overflow
+ * fp32.  A frame's camera never stands there (its rays end 10000 |d| from it); such a call runs with private walks (same results).
+ * Refusals, in this order: a NULL scene or origin, n < 0, NULL dirs with n > 0, unknown option bits, a non-finite origin:
+ * SR_ERR_INVALID_ARG; SR_TARGET_VOXELS: SR_ERR_UNSUPPORTED; sr_trace_rays' own checks (SR_ERR_NO_MODEL, SR_ERR_NOT_BUILT); a host-only
+ * scene: SR_ERR_NO_DEVICE.  n == 0 that passes the first three: SR_OK, nothing is touched.
+ * State: unlike sr_trace_rays the call REWRITES per-origin state of the scene (the facing partition moves triangle records), so it is
+ * ordered like a frame: behind a frame of the scene in flight on any stream, the next frame behind it.  The records stay keyed to `origin`:
+ * a following call or frame from the same point reuses them, a frame from elsewhere re-makes them as after any camera move (at 1 M
+ * triangles: see profiles/origin_rays) -- alternate origins and every call pays that.  Passes of at most 2^22 rays (SR_DBG_BAND_SAMPLES:
+ * fewer) follow each other without the host waiting.  A multi-device scene runs the call on devices[0].  The host variant stages through
+ * the scene's device buffers, blocks and fills sr_last_ray_stats; the device variant enqueues on `hip_stream` without a host
+ * synchronisation.  Statistics (there is no per-ray counters array: a packet walk counts per wave): [0..3] the primary counters as
+ * sr_render_hits defines them -- the reference's notions in SR_MODE_REF_TREE / SR_MODE_BRUTE (the sums of sr_trace_rays' per-ray
+ * counters), what a wave fetched on the own BVH -- and [4..] 0. */
+#define SR_RAYS_COHERENT 1u
+int  sr_trace_origin_rays(sr_scene*, int32_t target, const double origin[3], int64_t n, const double* dirs,
+                          uint8_t* hit, double* ray_frac, double* pos, double* normal, uint32_t* color, int32_t* tri_index,
+                          uint32_t options, uint64_t stats[4] /* or NULL */);
+int  sr_trace_origin_rays_device(sr_scene*, int32_t target, const double origin[3] /* HOST */, int64_t n, const double* d_dirs,
+                                 uint8_t* d_hit, double* d_ray_frac, double* d_pos, double* d_normal, uint32_t* d_color,
+                                 int32_t* d_tri_index, uint32_t options, void* hip_stream,
+                                 uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* ShadingMethod.IntersectRay's colour step in batch (ShadingMethod.cs:36-68 -> CalcLighting :110-177): for n recorded
  * intersections out[i] = ModulatePackedColor(color[i], (byte)(255 * intensity)) with the frame's transform and lights (only the
  * matrices, position_z, fov_depth, lights, ambient, shininess and the POINT_LIGHT / SPECULAR flags of `frame` are read).
@@ -835,7 +878,8 @@ int  sr_anti_alias_device(sr_scene*, const void* d_src, int32_t dst_width, int32
 enum {
     SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
                                     per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) and the
-                                    points per pass of sr_shadow_points and sr_static_shadow_points (default 2^22), of sr_ao_points (default and limit 2^17) and of sr_path_points (default and limit 2^22) */
+                                    points per pass of sr_shadow_points and sr_static_shadow_points (default 2^22), of sr_ao_points (default and limit 2^17) and of sr_path_points (default and limit 2^22),
+                                    and the rays per pass of sr_trace_origin_rays (default and limit 2^22) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
     SR_DBG_SPLIT          = 3,   /* concurrent part-frame pipelines (default 2, <= 4)                                          */

@@ -727,12 +727,15 @@ struct PtsReq {
 // sr_render_hits: the frame's own set-up of the primary stage (camera cones, ordered node copy, facing partition, row bands), then k_hits
 // per band into the caller's device arrays instead of the frame's kernels.  The caller has cleared the decorator switches of `f`
 struct HitsReq { sr::HitsOut out; };
+// sr_trace_origin_rays: the same set-up for `origin` in the camera's place (the frame `f` is a stand-in: one pixel, no decorator), then passes of
+// the caller's directions through k_origin_rays into the caller's device arrays.  with_extra: the root geometry (SR_TARGET_ROOT)
+struct OriginReq { double origin[3]; int64_t n; const double* dirs; sr::HitsOut out; bool coherent; bool with_extra; };
 
 // points per pass of sr_shadow_points: the bake's rule (SR_DBG_BAND_SAMPLES shrinks the pass)
 const long long kPtsPassPoints = 1ll << 22;
 
 int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0, const LfBakeReq* bake = nullptr,
-                  const PtsReq* pts = nullptr, const HitsReq* hreq = nullptr) {
+                  const PtsReq* pts = nullptr, const HitsReq* hreq = nullptr, const OriginReq* org = nullptr) {
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
@@ -743,12 +746,13 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     if ((f->flags & SR_F_PATH_TRACING) && f->strip_count > 1 && !pt_phase)
         return fail(SR_ERR_UNSUPPORTED, "path tracing with row strips: a rank would need the hit counts of rows it does not render");
     if ((rc = prepare_frame(s, f, fc))) return rc;
+    if (org) for (int a = 0; a < 3; ++a) fc.start_world[a] = org->origin[a];   // everything per-origin below is keyed to fc.start_world
     if ((rc = sync_geometry(s, voxels ? ~0u : (uint32_t)f->trace_mode))) return rc;
     // LightFieldTriMethod: stage 2 reads the reference tree's leaves whatever trace_mode walks the full rays
     const bool lft = s->lf_tris && (f->flags & SR_F_LIGHT_FIELD) && !bake && !pts;
     if (lft && (rc = sync_geometry(s, SR_MODE_REF_TREE))) return rc;
     if (voxels && (rc = ensure_voxels(s, stream))) return rc;
-    if (fc.num_rows == 0 && !bake && !pts) return SR_OK;
+    if (fc.num_rows == 0 && !bake && !pts && !org) return SR_OK;
     // ---- frames of one scene run in submission order whatever streams they are given: the scene's scratch (hit queues, candidate
     //      lists, counters) and its per-origin / per-light records belong to one frame at a time.  `pre_used` is recorded when everything
     //      a frame enqueues is on its stream; the next frame's stream waits for it (a no-op on the same stream) ----
@@ -907,7 +911,21 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     bool rewrote = false;                                             // (frames enqueued earlier have been waited for: see pre_used above)
     // ---- which records can the frame's camera rays / shadow sample rays hit at all?  (k_facing_partition, sr_pipeline.hip) ----
     const bool lf = (f->flags & SR_F_LIGHT_FIELD) != 0;              // (no camera ray is walked: none of the packet walk's per-origin records is needed)
-    const bool pkt_primary = f->trace_mode == SR_MODE_BVH && s->dbg[SR_DBG_PER_LANE_PRIMARY] <= 0 && !((f->flags & SR_F_FOCAL_BLUR) && f->sub_pixel_res > 1) && !lf && !pts;
+    // sr_trace_origin_rays from an origin no frame's camera stands at (include/softray.h): further from the root box's centre than 2^20 box diagonals
+    // on some axis (the FP64 rounding of k_cam_cones' vertex - origin comes within reach of the fp32 margin of cone_rejects), or so far that a
+    // cone-plane product with a direction of 2^40 can overflow fp32 (|w| |d| 3 < 2^127 needs the furthest vertex within 2^42.5).  Private walks
+    bool org_far = false;
+    if (org) {
+        double diag2 = 0, away = 0;
+        for (int a = 0; a < 3; ++a) {
+            const double e = s->root.max[a] - s->root.min[a];
+            diag2 += e * e;
+            away = std::max(away, std::fabs(org->origin[a] - s->root.centre[a]));
+        }
+        const double diag = std::sqrt(diag2);
+        org_far = !(away <= 0x1p20 * diag) || !(away * 1.7320508075688772 + 0.5 * diag <= 0x1p42);
+    }
+    const bool pkt_primary = f->trace_mode == SR_MODE_BVH && s->dbg[SR_DBG_PER_LANE_PRIMARY] <= 0 && !((f->flags & SR_F_FOCAL_BLUR) && f->sub_pixel_res > 1) && !lf && !pts && !org_far;
     const bool want_cam = wide && pkt_primary, want_light = wide && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT);
     if ((want_cam || want_light) && s->dbg[SR_DBG_KERNEL_SWITCH] != 71) {
         const auto same3 = [](const double* a, const double* b) { return a[0] == b[0] && a[1] == b[1] && a[2] == b[2]; };
@@ -1101,6 +1119,13 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         pts_pass = std::max<long long>(1, std::min<long long>(want, pts->n));
         band_samples = (pts_pass + 255) / 256 * 256;                    // (the scratch in whole workgroups of queue entries)
     }
+    long long org_pass = 0;
+    if (org) {
+        // a pass of rays: at most kPtsPassPoints (SR_DBG_BAND_SAMPLES: fewer), no more than the call has
+        const long long want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<long long>(s->dbg[SR_DBG_BAND_SAMPLES], kPtsPassPoints) : kPtsPassPoints;
+        org_pass = std::max<long long>(1, std::min<long long>(want, org->n));
+        band_samples = (org_pass + 255) / 256 * 256;                    // (the order's scratch in whole workgroups)
+    }
     // (hook 37: a pass is queued in input order whatever the caller promised)
     const bool pts_sort = pts && !pts->coherent && s->dbg[SR_DBG_KERNEL_SWITCH] != 37;
     if (shaft && band_samples >= (1ll << 25)) return fail(SR_ERR_UNSUPPORTED, "row band too large for the 25-bit fallback entry ids (surface too wide for this sub-pixel resolution)");
@@ -1200,6 +1225,11 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         if (pts) {
             // the pass as k_pts_ingest leaves it, and its order: by (cell of the point, octant of the normal), or the input's
             SR_HIP(B.hits2.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
+            SR_HIP(B.ray_sort.reserve((size_t)band_samples * 4 * 4));
+            SR_HIP(B.ray_sort_temp.reserve(sr::point_order_temp_bytes((unsigned)band_samples)));
+        }
+        if (org) {
+            // the order of a pass (dir_order): keys, sorted keys, indices, order + the device sort's own scratch
             SR_HIP(B.ray_sort.reserve((size_t)band_samples * 4 * 4));
             SR_HIP(B.ray_sort_temp.reserve(sr::point_order_temp_bytes((unsigned)band_samples)));
         }
@@ -1323,6 +1353,12 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             }
         }
         if (hreq) { P.hits_req = true; P.hits_out = hreq->out; }
+        if (org) {
+            P.org_n = org->n; P.org_pass = org_pass;
+            P.org_dirs = org->dirs; P.hits_out = org->out;
+            P.org_coherent = org->coherent;
+            if (!org->with_extra) { P.sc.extra = nullptr; P.sc.nextra = 0; }    // the model alone, whatever the scene's extra geometry
+        }
         s->ao_table_seed = f->random_seed;
         s->ao_table_rc = SR_OK;
         P.ao_table = !ao ? nullptr : [](void* user, unsigned long long generators) -> const int32_t* {
@@ -1344,9 +1380,9 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.pt_row_k0 = pt_phase ? (uint32_t*)s->d_pt_row_k0.p : nullptr;
         P.pt_range_first = pt_range_first;
         P.pt_range_rows = pt_range_rows;
-        P.ray_sort_buf = (bounce_pipe || path_walk || pts) ? (unsigned int*)B.ray_sort.p : nullptr;
-        P.ray_sort_temp = (bounce_pipe || path_walk || pts) ? B.ray_sort_temp.p : nullptr;
-        P.ray_sort_temp_bytes = pts ? sr::point_order_temp_bytes((unsigned)band_samples) : (bounce_pipe || path_walk) ? sr::ray_sort_temp_bytes((unsigned)band_samples) : 0;
+        P.ray_sort_buf = (bounce_pipe || path_walk || pts || org) ? (unsigned int*)B.ray_sort.p : nullptr;
+        P.ray_sort_temp = (bounce_pipe || path_walk || pts || org) ? B.ray_sort_temp.p : nullptr;
+        P.ray_sort_temp_bytes = (pts || org) ? sr::point_order_temp_bytes((unsigned)band_samples) : (bounce_pipe || path_walk) ? sr::ray_sort_temp_bytes((unsigned)band_samples) : 0;
         P.bounce_levels = bounce_pipe ? (uint32_t*)B.bounce_levels.p : nullptr;
         P.bounce_nlev = bounce_pipe ? (uint8_t*)B.bounce_nlev.p : nullptr;
         P.bounce_prep = (bounce_pipe || path_walk) ? B.bounce_prep.p : nullptr;
@@ -1386,7 +1422,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.per_lane_shadows = (f->flags & SR_F_PER_LANE_SHADOWS) != 0;
         P.exact_shadow_tests = s->dbg[SR_DBG_EXACT_SHADOW_TESTS] > 0;
         P.per_lane_shaft = s->dbg[SR_DBG_PER_LANE_SHAFT] > 0 ? (int32_t)(s->dbg[SR_DBG_PER_LANE_SHAFT] & 3) : 0;
-        P.per_lane_primary = s->dbg[SR_DBG_PER_LANE_PRIMARY] > 0;
+        P.per_lane_primary = s->dbg[SR_DBG_PER_LANE_PRIMARY] > 0 || org_far;
         P.bvh2_packets = s->dbg[SR_DBG_BVH2_PACKETS] > 0;
         P.shadows_on_bvh = shadows_on_bvh;
         P.primary_stats_only = (f->flags & SR_F_PRIMARY_STATS_ONLY) != 0;
@@ -1413,7 +1449,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         };
         if (accum_fresh) SR_HIP(hipMemsetAsync(B.accum.p, 0, B.accum.cap, bs));
         if (hints_fresh) for (DBuf& hb : B.tile_hint) SR_HIP(hipMemsetAsync(hb.p, 0xFF, hb.cap, bs));
-        if (P.row_first < P.row_limit || bake || pts) {
+        if (P.row_first < P.row_limit || bake || pts || org) {
             const hipError_t pe = sr::launch_pipeline(P);
             if (pe == hipErrorNotSupported && s->ao_table_rc) return s->ao_table_rc;      // (the message is the callback's)
             SR_HIP(pe);
@@ -2875,6 +2911,85 @@ int sr_trace_rays(sr_scene* s, int32_t target, int64_t n, const double* starts, 
     void* outs[7] = {hit, ray_frac, pos, normal, color, tri_index, counters};
     for (int i = 0; i < 7; ++i)
         if (outs[i]) SR_HIP(hipMemcpy(outs[i], s->d_io[2 + i].p, sizes[2 + i], hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Ray batches from one origin (sr_trace_origin_rays): sr_trace_rays' answers on the walk of a frame's primary stage
+// ------------------------------------------------------------------------------------------------------------------
+// what sr_trace_origin_rays[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the
+// first part of a multi-device scene)
+static int origin_rays_check(sr_scene*& s, int32_t target, const double* origin, int64_t n, const void* dirs, uint32_t options, int& mode, bool& with_extra) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !origin || n < 0 || (n > 0 && !dirs) || (options & ~(uint32_t)SR_RAYS_COHERENT) || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) ||
+        !std::isfinite(origin[2]))
+        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_trace_origin_rays");
+    if (target & SR_TARGET_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_trace_origin_rays: the voxel grid (SR_TARGET_VOXELS) has no tree for a packet to walk; use sr_trace_rays");
+    with_extra = (target & SR_TARGET_ROOT) != 0;
+    mode = target & 0xff;
+    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "no model");
+    return check_mode(s, mode);
+}
+
+// the frame render_common sets the call up as: one pixel, no decorator, the identity camera (render_common puts `origin` in its place)
+static void origin_rays_frame(sr_frame& fs, int mode) {
+    std::memset(&fs, 0, sizeof(fs));
+    fs.width = fs.height = 1;
+    fs.sub_pixel_res = 1;
+    fs.trace_mode = mode;
+    fs.transform[0] = fs.transform[5] = fs.transform[10] = 1.0;
+    fs.inv_transform[0] = fs.inv_transform[5] = fs.inv_transform[10] = 1.0;
+    fs.fov_depth = 1.0;
+}
+
+int sr_trace_origin_rays_device(sr_scene* m, int32_t target, const double origin[3], int64_t n, const double* d_dirs, uint8_t* d_hit, double* d_ray_frac,
+                                double* d_pos, double* d_normal, uint32_t* d_color, int32_t* d_tri_index, uint32_t options, void* hip_stream, uint64_t* d_stats) {
+    sr_scene* s = m;
+    int mode; bool with_extra;
+    int rc = origin_rays_check(s, target, origin, n, d_dirs, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    sr_frame fs;
+    origin_rays_frame(fs, mode);
+    const OriginReq req{{origin[0], origin[1], origin[2]}, n, d_dirs, {nullptr, nullptr, d_hit, d_ray_frac, d_pos, d_normal, d_color, d_tri_index},
+                        (options & SR_RAYS_COHERENT) != 0, with_extra};
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, 0, nullptr, nullptr, nullptr, &req);
+}
+
+int sr_trace_origin_rays(sr_scene* m, int32_t target, const double origin[3], int64_t n, const double* dirs, uint8_t* hit, double* ray_frac, double* pos,
+                         double* normal, uint32_t* color, int32_t* tri_index, uint32_t options, uint64_t stats[4]) {
+    sr_scene* s = m;
+    int mode; bool with_extra;
+    int rc = origin_rays_check(s, target, origin, n, dirs, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    if ((rc = ensure_io_streams(s))) return rc;
+    hipStream_t stream = s->io_stream;
+    void* outs[6] = {hit, ray_frac, pos, normal, color, tri_index};
+    const size_t sizes[6] = {(size_t)n, (size_t)n * 8, (size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n * 4};
+    void* dev[6];
+    SR_HIP(s->d_io[0].reserve((size_t)n * 24));
+    for (int i = 0; i < 6; ++i) {
+        if (outs[i]) SR_HIP(s->d_io[1 + i].reserve(sizes[i]));
+        dev[i] = outs[i] ? s->d_io[1 + i].p : nullptr;
+    }
+    SR_HIP(hipMemcpyAsync(s->d_io[0].p, dirs, (size_t)n * 24, hipMemcpyHostToDevice, stream));
+    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
+    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    sr_frame fs;
+    origin_rays_frame(fs, mode);
+    const OriginReq req{{origin[0], origin[1], origin[2]}, n, (const double*)s->d_io[0].p,
+                        {nullptr, nullptr, (uint8_t*)dev[0], (double*)dev[1], (double*)dev[2], (double*)dev[3], (uint32_t*)dev[4], (int32_t*)dev[5]},
+                        (options & SR_RAYS_COHERENT) != 0, with_extra};
+    if ((rc = render_common(s, &fs, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, nullptr, nullptr, nullptr, &req))) { (void)hipStreamSynchronize(stream); return rc; }
+    for (int i = 0; i < 6; ++i)
+        if (outs[i]) SR_HIP(hipMemcpyAsync(outs[i], dev[i], sizes[i], hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    if (stats) std::memcpy(stats, s->last_stats, 4 * sizeof(uint64_t));
     return SR_OK;
 }
 

@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_COUNT = 42 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_COUNT = 44 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -173,6 +173,12 @@ struct PipelineLaunch {
     // sr_render_hits (hits_req: launch_pipeline runs k_hits per row band instead of the frame's kernels and writes no pixel)
     bool          hits_req;
     HitsOut       hits_out;
+    // sr_trace_origin_rays (org_n > 0: launch_pipeline renders no rows): n caller-given directions from fc.start_world in passes of org_pass rays
+    // through k_origin_rays on the frame's primary walk (primary_walk_kind), answers straight into hits_out (starts / dirs unused) at the
+    // ray's input index.  A packet pass is ordered by dir_order (ray_sort_buf: 4 x the pass rounded up to 256 words, ray_sort_temp)
+    int64_t       org_n, org_pass;
+    const double* org_dirs;     // device [n][3], as given
+    bool          org_coherent; // SR_RAYS_COHERENT: a pass keeps its input order (the irregular rays still go last)
     void*         static_hits;  // device HitRec[min(band samples, 128^3)]: generators of a static-shadow frame
     unsigned long long* static_claim; // device [128^3]: smallest order key that asked for an empty cell
     int32_t       static_concurrency; // rayTraceConcurrency of the frame
@@ -370,6 +376,13 @@ size_t point_order_temp_bytes(unsigned int cap);
 unsigned int point_order_skip_mask(bool sorted);
 hipError_t point_order(const void* recs, unsigned int n, bool sorted, const RootBox& root, unsigned int* keys, unsigned int* keys2, unsigned int* idx,
                        unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
+
+// sr_trace_origin_rays: the order of a pass of n rays with a common origin (dirs: [n][3]).  order_out: the regular rays first -- sorted: by the
+// cell of the unit direction in an octahedral map of 2^12 x 2^12 cells, Morton-interleaved (24 bits), ties in input order; !sorted: in input
+// order -- then the irregular ones (a component not finite, or max |d_k| outside [2^-40, 2^40]) in input order.  A stable sort; keys2
+// returns the sorted keys: point_order_skip_mask(sorted) is their bit that marks an irregular ray.  Scratch as point_order's
+hipError_t dir_order(const double* dirs, unsigned int n, bool sorted, unsigned int* keys, unsigned int* keys2, unsigned int* idx, unsigned int* order_out,
+                     void* temp, size_t temp_bytes, hipStream_t stream);
 
 // the four-wide tree collapsed from a device-resident binary tree (same rule as the host's collapse_bvh4); d_wide: >= num_nodes entries
 // level_first (nullable): the wide nodes are numbered level by level -- level L is [level_first[L], level_first[L + 1]), the last entry

@@ -394,6 +394,59 @@ __global__ __launch_bounds__(256, SUB ? 5 : (PKT >= 2 ? 7 : 6)) void k_hits(DevS
 }
 
 // --------------------------------------------------------------------------------------------------
+// k_origin_rays (sr_trace_origin_rays): caller-given directions from one origin
+// --------------------------------------------------------------------------------------------------
+// k_hits without a camera: lane j of the launch takes ray order[j] of the pass (order == nullptr: ray j), reads its 24-byte direction and
+// starts at the common origin; one wave per 64 rays of that order, four per workgroup, the walk k_hits' instantiation with the same PKT takes
+// (PKT 0: the private walk k_trace runs, so an answer of that form is k_trace's by construction).  Answers go straight to the caller's arrays
+// at the ray's input index, k_trace's conventions, every pointer optional (a launch-uniform test).
+// A pass that a packet form walks is ordered by dir_order (sr_raysort.hip): its regular rays first, then the irregular ones, keys[j] the key
+// of the j-th; the packet launch takes the lanes whose key has no skip bit (take_skipped 0), a PKT 0 launch the others (take_skipped 1).
+// Launch bounds as k_hits', for its reason (profiles/origin_rays/kernel_resources.txt).
+template <int MODE, bool EXTRA, bool STATS, int PKT>
+__global__ __launch_bounds__(256, PKT >= 2 ? 7 : 6) void k_origin_rays(DevScene sc, double ox, double oy, double oz, const double* __restrict__ dirs, long long first,
+                                                                      unsigned int count, const unsigned int* __restrict__ order,
+                                                                      const unsigned int* __restrict__ keys, unsigned int skip_mask, int take_skipped, HitsOut out,
+                                                                      unsigned long long* stats, int levels) {
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int32_t* wnode = reinterpret_cast<int32_t*>(lds_pipe) + (size_t)wave * levels;     // PKT: the wave's node stack
+    Stack st{reinterpret_cast<int32_t*>(lds_pipe) + tid, 256};
+    Ctr prim = {0, 0, 0, 0};
+    const unsigned int j = blockIdx.x * 256u + (unsigned int)tid;                       // (a pass has at most 2^22 rays)
+    bool live = j < count;
+    unsigned int src = j;
+    if (order && live) {
+        src = order[j];
+        live = ((keys[j] & skip_mask) != 0u) == (take_skipped != 0);
+    }
+    const size_t i = (size_t)first + (size_t)src;                                       // 64-bit from here on: n x 24 bytes may pass 2^32
+    const D3 ss = mk(ox, oy, oz);
+    const D3 dw = live ? mk(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]) : mk(0.0, 0.0, 1.0);
+    Hit h;
+    bool ok = false;
+    if (PKT) {
+        if (live) prim.rays++;
+        ok = root_intersect_pkt<EXTRA, true, PKT == 3 ? 2 : (PKT == 2 ? 1 : 0)>(sc, sc.extra, wnode, live, ss, dw, h, prim);     // all 64 lanes take part
+    } else if (live) {
+        prim.rays++;
+        ok = root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, ss, dw, h, prim);
+    }
+    if (live) {                                                                          // k_trace's conventions: a miss is zeros and triangle -1
+        if (out.hit) out.hit[i] = ok ? 1 : 0;
+        if (out.ray_frac) out.ray_frac[i] = ok ? h.t : 0.0;
+        if (out.pos) store3(out.pos, i, ok ? h.pos : mk(0, 0, 0));
+        if (out.normal) store3(out.normal, i, ok ? h.nrm : mk(0, 0, 0));
+        if (out.color) out.color[i] = ok ? h.color : 0u;
+        if (out.tri) out.tri[i] = ok ? h.tri : -1;
+    }
+    if (STATS) {
+        uint32_t a = wave_sum(prim.rays), b = wave_sum(prim.geom), c2 = wave_sum(prim.nodes), d2 = wave_sum(prim.leaves);
+        block_stat_add(&stats[0], &stats[1], &stats[2], &stats[3], a, b, c2, d2);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_shadow
 // --------------------------------------------------------------------------------------------------
 // one area-light sample: is the surface point occluded?  (ShadowMethod.cs:147-177)
@@ -5596,6 +5649,62 @@ static hipError_t launch_hits_t(const PipelineLaunch& L) {
     return hipSuccess;
 }
 
+// sr_trace_origin_rays: k_origin_rays over `count` rays of a pass from ray `first` on, one workgroup per 256 of them (LDS as k_hits')
+template <int MODE, bool EXTRA, int PKT>
+static hipError_t launch_origin_p(const PipelineLaunch& L, long long first, unsigned int count, const unsigned int* order, const unsigned int* keys,
+                                  unsigned int skip_mask, int take_skipped) {
+    const dim3 grid((count + 255u) / 256u);
+    const int levels = PKT >= 2 ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE);
+    const size_t lds = PKT ? (size_t)levels * 4 * 4 : (size_t)levels * 256 * 4;
+    const auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, L.stream, L.sc, L.fc.start_world[0], L.fc.start_world[1], L.fc.start_world[2], L.org_dirs, first, count,
+                           order, keys, skip_mask, take_skipped, L.hits_out, L.stats, levels);
+    };
+    if (L.stats) go(k_origin_rays<MODE, EXTRA, true, PKT>); else go(k_origin_rays<MODE, EXTRA, false, PKT>);
+    return hipGetLastError();
+}
+
+// ... pass by pass, back to back on the stream.  The walk is the one a frame's primary stage takes for this scene state (primary_walk_kind);
+// a packet pass is ordered first (dir_order: by direction, or -- SR_RAYS_COHERENT -- only its irregular rays moved to the end), its
+// irregular tail takes the per-lane form
+template <int MODE, bool EXTRA>
+static hipError_t launch_origin_t(const PipelineLaunch& L) {
+    const int kind = primary_walk_kind<MODE, false>(L);
+    const unsigned int cap = (unsigned int)((L.org_pass + 255) / 256 * 256);
+    unsigned int* keys = L.ray_sort_buf;
+    unsigned int* keys2 = keys + cap;
+    unsigned int* idx = keys2 + cap;
+    unsigned int* order = idx + cap;
+    const unsigned int skip = point_order_skip_mask(!L.org_coherent);
+    for (int64_t first = 0; first < L.org_n; first += L.org_pass) {
+        const unsigned int count = (unsigned int)std::min<int64_t>(L.org_pass, L.org_n - first);
+        hipError_t e;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (kind != 0) {
+            if (L.get_events) L.get_events(L.user, K_ORIGIN_SORT, &e0, &e1);
+            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+            if ((e = dir_order(L.org_dirs + 3 * first, count, !L.org_coherent, keys, keys2, idx, order, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
+            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        }
+        e0 = e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_ORIGIN_RAYS, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        if constexpr (MODE == MODE_BVH) {
+            switch (kind) {
+                case 3: e = launch_origin_p<MODE, EXTRA, 3>(L, first, count, order, keys2, skip, 0); break;
+                case 2: e = launch_origin_p<MODE, EXTRA, 2>(L, first, count, order, keys2, skip, 0); break;
+                case 1: e = launch_origin_p<MODE, EXTRA, 1>(L, first, count, order, keys2, skip, 0); break;
+                default: e = hipSuccess; break;
+            }
+            if (e != hipSuccess) return e;
+        }
+        e = kind != 0 ? launch_origin_p<MODE, EXTRA, 0>(L, first, count, order, keys2, skip, 1) : launch_origin_p<MODE, EXTRA, 0>(L, first, count, nullptr, nullptr, 0u, 0);
+        if (e != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 template <int MODE, bool EXTRA>
 static hipError_t launch_shadow_lanes_t(const PipelineLaunch& L, uint32_t* samples, long long max_hits, const unsigned int* count,
                                         unsigned int* head, const unsigned int* index_list) {
@@ -6390,6 +6499,7 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     if (L.pts_n > 0 && L.pts_static) return launch_static_pts_t<MODE, EXTRA>(L);   // sr_static_shadow_points: the points through the static cache
     if (L.pts_n > 0) return launch_pts_shadows_t<MODE, EXTRA>(L);                  // sr_shadow_points: the caller's points, no rows, no pixels
     if (L.hits_req) return launch_hits_t<MODE, EXTRA>(L);                          // sr_render_hits: the rows' camera samples, no pixels
+    if (L.org_n > 0) return launch_origin_t<MODE, EXTRA>(L);                       // sr_trace_origin_rays: the caller's directions, no rows, no pixels
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     const bool shadows = (L.fc.flags & 2u) != 0;
     const bool path = (L.fc.flags & kFlagPathTracing) != 0;          // (sr_api.cpp: never together with shadows or mirror bounces)

@@ -63,7 +63,55 @@ __global__ __launch_bounds__(256) void k_point_keys(const double* __restrict__ r
     idx[i] = i;
 }
 
+__device__ __forceinline__ unsigned int spread12(unsigned int v) {         // 12 bits -> every second bit
+    v &= 0xfffu;
+    v = (v | (v << 8)) & 0x00ff00ffu;
+    v = (v | (v << 4)) & 0x0f0f0f0fu;
+    v = (v | (v << 2)) & 0x33333333u;
+    v = (v | (v << 1)) & 0x55555555u;
+    return v;
+}
+
+// sr_trace_origin_rays: the rays of a pass share their origin, so a ray's place among its neighbours is its direction alone.  Key = the cell
+// of d / (|dx| + |dy| + |dz|) in the octahedral map (the lower hemisphere folded over the diagonals), 2^12 cells per axis, Morton-interleaved:
+// 24 bits.  Bit kPointSkipBit (sorted) / bit 0 (!sorted) marks an IRREGULAR ray -- a component that is not finite, or max |d_k| outside
+// [2^-40, 2^40] -- which the packet walk never sees: the stable sort leaves those at the end of the pass, in input order.
+__global__ __launch_bounds__(256) void k_dir_keys(const double* __restrict__ dirs, unsigned int n, int sorted, unsigned int* __restrict__ keys,
+                                                  unsigned int* __restrict__ idx) {
+    const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const double dx = dirs[(size_t)i * 3], dy = dirs[(size_t)i * 3 + 1], dz = dirs[(size_t)i * 3 + 2];
+    const double ax = fabs(dx), ay = fabs(dy), az = fabs(dz);
+    const double m = fmax(fmax(ax, ay), az);
+    // (a NaN component fails the first three comparisons, an infinite one the fifth)
+    const bool regular = ax == ax && ay == ay && az == az && m >= 0x1p-40 && m <= 0x1p40;
+    unsigned int key = 0u;
+    if (regular && sorted) {
+        const double inv = 1.0 / (ax + ay + az);
+        double u = dx * inv, v = dy * inv;
+        if (dz < 0.0) {
+            const double fu = (1.0 - fabs(v)) * (u < 0.0 ? -1.0 : 1.0), fv = (1.0 - fabs(u)) * (v < 0.0 ? -1.0 : 1.0);
+            u = fu; v = fv;
+        }
+        const int cu = min(4095, max(0, (int)((u + 1.0) * 2048.0))), cv = min(4095, max(0, (int)((v + 1.0) * 2048.0)));
+        key = (spread12((unsigned)cu) << 1) | spread12((unsigned)cv);
+    }
+    if (!regular) key = sorted ? (1u << kPointSkipBit) : 1u;
+    keys[i] = key;
+    idx[i] = i;
+}
+
 }  // namespace
+
+hipError_t dir_order(const double* dirs, unsigned int n, bool sorted, unsigned int* keys, unsigned int* keys2, unsigned int* idx, unsigned int* order_out,
+                     void* temp, size_t temp_bytes, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dir_keys, dim3((n + 255u) / 256u), dim3(256), 0, stream, dirs, n, sorted ? 1 : 0, keys, idx);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const unsigned int*)keys, keys2, (const unsigned int*)idx, order_out, (int)n, 0,
+                                              sorted ? kPointSkipBit + 1 : 1, stream);
+}
 
 unsigned int point_order_skip_mask(bool sorted) { return sorted ? (1u << kPointSkipBit) : 1u; }
 

@@ -472,6 +472,19 @@ public:
         sr_frame f = BuildFrame(inst);
         sr_check(sr_render_hits(scene_, &f, starts, dirs, hit, ray_frac, pos, normal, color, tri_index, nullptr));
     }
+    // Nearest hits of n rays that start in one model-space point (sr_trace_origin_rays): IntersectRay(origin, dirs[i]) on the root geometry of
+    // the chain (extra geometry + the model in the renderer's mode), bit for bit, on the packet walk of a frame's camera rays.  dirs is [n][3],
+    // not normalised; every output may be nullptr; coherent: every 64 consecutive rays are neighbours (SR_RAYS_COHERENT).  The scene's
+    // per-origin records are re-keyed to `origin`, as by a camera move.  Does nothing without a model
+    void TraceOriginRays(const Vector& origin, int64_t n, const double* dirs, uint8_t* hit, double* ray_frac, double* pos, double* normal, uint32_t* color,
+                         int32_t* tri_index, bool coherent = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel()) return;
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        const double o[3] = {origin.x, origin.y, origin.z};
+        sr_check(sr_trace_origin_rays(scene_, SR_TARGET_ROOT | Mode(), o, n, dirs, hit, ray_frac, pos, normal, color, tri_index, coherent ? SR_RAYS_COHERENT : 0u, nullptr));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

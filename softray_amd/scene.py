@@ -558,6 +558,33 @@ class GpuScene:
         _check(_lib.lib().sr_trace_rays_device(self._h, int(target), int(n), vp(d_starts), vp(d_dirs), vp(d_hit), vp(d_ray_frac), vp(d_pos),
                                                vp(d_normal), vp(d_color), vp(d_tri_index), vp(d_counters), vp(stream)))
 
+    # ---- a ray batch from one origin on the frame's packet walk (sr_trace_origin_rays) ----
+    def trace_origin(self, target, origin, dirs, coherent=False, stats=False):
+        """trace(target, tile(origin), dirs), bit for bit, on the walk a frame's camera rays take: a dict with trace()'s keys (with
+        stats=True also the four primary counters, `stats`).  coherent: every 64 consecutive rays are neighbours (SR_RAYS_COHERENT)."""
+        origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = dirs.shape[0]
+        res = dict(hit=np.zeros(n, dtype=np.uint8), ray_frac=np.zeros(n), pos=np.zeros((n, 3)),
+                   normal=np.zeros((n, 3)), color=np.zeros(n, dtype=np.uint32), tri_index=np.zeros(n, dtype=np.int32))
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        _check(_lib.lib().sr_trace_origin_rays(self._h, int(target), _p(origin), n, _p(dirs), _p(res["hit"]), _p(res["ray_frac"]), _p(res["pos"]),
+                                               _p(res["normal"]), _p(res["color"]), _p(res["tri_index"]), _lib.RAYS_COHERENT if coherent else 0, _p(st)))
+        if stats:
+            res["stats"] = st
+        return res
+
+    def trace_origin_device(self, target, origin, n, d_dirs, d_hit=0, d_ray_frac=0, d_pos=0, d_normal=0, d_color=0, d_tri_index=0, coherent=False,
+                            stream=0, d_stats_ptr=None):
+        """sr_trace_origin_rays_device: `origin` is a host triple, every array a DEVICE pointer (0 / None: not wanted); enqueued on `stream` (a raw
+        hipStream_t or a torch.cuda.Stream), no host sync."""
+        origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = getattr(stream, "cuda_stream", stream)
+        _check(_lib.lib().sr_trace_origin_rays_device(self._h, int(target), _p(origin), int(n), vp(d_dirs), vp(d_hit), vp(d_ray_frac), vp(d_pos),
+                                                      vp(d_normal), vp(d_color), vp(d_tri_index), _lib.RAYS_COHERENT if coherent else 0, vp(st),
+                                                      vp(d_stats_ptr)))
+
     # ---- the strip gather over RCCL (include/softray.h) ----
     def set_gather(self, kind):
         """Multi-device scene: _lib.GATHER_COPY (peer copies, default) or _lib.GATHER_RCCL (grouped ncclSend / ncclRecv)."""

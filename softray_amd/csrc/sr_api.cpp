@@ -146,7 +146,8 @@ struct sr_scene {
     DBuf d_pp_state;                     // sr_path_points: a pass's window, table size and ray counters
     bool aop_rows_ready = false;
     std::unique_ptr<sr::NetRandom> aop_host_random;   // (host tables) the Random of the call being enqueued, at ...
-    uint64_t aop_host_drawn = 0;                      // ... this many generators
+    uint64_t aop_host_drawn = 0;                      // ... this many units (generators / points) of ...
+    uint32_t aop_host_ints = 0;                       // ... this many draws each
     bool ao_cache_empty = true;          // the device cache must be zeroed before its next use (a new Renderer / a new model)
     std::vector<uint8_t> ao_cache_host;
     std::vector<uint8_t> shadow_cache_host;   // sr_set_shadow_cache on a host-only scene (sr_get_shadow_cache reads it back)
@@ -577,6 +578,62 @@ int next_events(sr_scene* s, int k, hipEvent_t& a, hipEvent_t& b) {
     return SR_OK;
 }
 
+// the `get_events` of every launch struct (sr_device.h): `user` is the scene, no pair is no timing
+void timing_events(void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
+    hipEvent_t x = nullptr, y = nullptr;
+    if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
+    *a = x; *b = y;
+}
+
+int ensure_num_cus(sr_scene* s) {
+    if (s->num_cus) return SR_OK;
+    hipDeviceProp_t prop;
+    SR_HIP(hipGetDeviceProperties(&prop, s->device));
+    s->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    return SR_OK;
+}
+
+// frames of one scene run in submission order whatever streams they are given: the scene's scratch (hit queues, candidate lists,
+// counters) and its per-origin / per-light records belong to one frame -- or one batch call -- at a time.  Entering makes `stream` wait
+// for `pre_used` (a no-op on the same stream; `entered` is the refusal of that wait); leaving, by whatever return, records it again: when
+// everything the frame enqueues is on its stream
+struct StreamOrder {
+    sr_scene* s; hipStream_t st; int entered;
+    StreamOrder(sr_scene* scene, hipStream_t stream) : s(scene), st(stream), entered(wait()) {}
+    StreamOrder(const StreamOrder&) = delete;
+    ~StreamOrder() {
+        if (entered != SR_OK) return;
+        if (!s->pre_used && hipEventCreateWithFlags(&s->pre_used, hipEventDisableTiming) != hipSuccess) return;
+        if (hipEventRecord(s->pre_used, st) == hipSuccess) s->pre_used_set = true;
+    }
+private:
+    int wait() {
+        if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(st, s->pre_used, 0));
+        return SR_OK;
+    }
+};
+
+// a draw table made on the host (sr_ao_points, sr_path_points): System.Random(seed) itself, one draw after the other, from unit `first`
+// on, `ints` draws per unit (300 per generator, 3 per point).  fill_host_table is the launch structs' callback (`user`: the scene): the passes
+// ask in ascending order, and the call waits once per pass
+void start_host_table(sr_scene* s, int32_t seed, uint64_t first, uint32_t ints) {
+    s->aop_host_random.reset(new sr::NetRandom(seed));
+    for (uint64_t i = 0; i < first * ints; ++i) (void)s->aop_host_random->next();
+    s->aop_host_drawn = first;
+    s->aop_host_ints = ints;
+}
+hipError_t fill_host_table(void* user, uint64_t base, uint32_t count, int32_t* d_table, hipStream_t st) {
+    sr_scene* sc = (sr_scene*)user;
+    if (base != sc->aop_host_drawn) return hipErrorInvalidValue;
+    if (count == 0) return hipSuccess;                             // (a pass of sr_ao_points without a generator; sr_path_points has none)
+    std::vector<int32_t> ints((size_t)count * sc->aop_host_ints);
+    for (int32_t& v : ints) v = sc->aop_host_random->next();
+    sc->aop_host_drawn += count;
+    hipError_t e = hipMemcpyAsync(d_table, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(st);                               // (`ints` leaves scope)
+}
+
 // TriMeshToVoxelGrid.Convert for the scene's model, once per model.  A scene with a device runs sr_voxels.hip's voxeliser from the device triangle
 // records (on `stream`; the call waits for it: the number of (cell, triangle) pairs sizes the sort's buffers); a host-only scene runs the plain
 // host loop (sr_host.cpp voxelise_host)
@@ -734,8 +791,28 @@ struct OriginReq { double origin[3]; int64_t n; const double* dirs; sr::HitsOut 
 // points per pass of sr_shadow_points: the bake's rule (SR_DBG_BAND_SAMPLES shrinks the pass)
 const long long kPtsPassPoints = 1ll << 22;
 
-int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, int pt_phase = 0, const LfBakeReq* bake = nullptr,
-                  const PtsReq* pts = nullptr, const HitsReq* hreq = nullptr, const OriginReq* org = nullptr) {
+// what render_common is asked for besides a whole frame: nothing, a phase of a split path-traced frame, or one of the requests above (a
+// call site passes `&req`: the request's type says which)
+struct RenderAsk {
+    int pt_phase = 0;
+    const LfBakeReq* bake = nullptr;
+    const PtsReq* pts = nullptr;
+    const HitsReq* hreq = nullptr;
+    const OriginReq* org = nullptr;
+    RenderAsk() {}
+    RenderAsk(const LfBakeReq* r) : bake(r) {}
+    RenderAsk(const PtsReq* r) : pts(r) {}
+    RenderAsk(const HitsReq* r) : hreq(r) {}
+    RenderAsk(const OriginReq* r) : org(r) {}
+    static RenderAsk phase(int p) { RenderAsk a; a.pt_phase = p; return a; }
+};
+
+int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_t stream, unsigned long long* d_stats, const RenderAsk& ask = RenderAsk()) {
+    const int pt_phase = ask.pt_phase;
+    const LfBakeReq* const bake = ask.bake;
+    const PtsReq* const pts = ask.pts;
+    const HitsReq* const hreq = ask.hreq;
+    const OriginReq* const org = ask.org;
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
@@ -753,17 +830,9 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     if (lft && (rc = sync_geometry(s, SR_MODE_REF_TREE))) return rc;
     if (voxels && (rc = ensure_voxels(s, stream))) return rc;
     if (fc.num_rows == 0 && !bake && !pts && !org) return SR_OK;
-    // ---- frames of one scene run in submission order whatever streams they are given: the scene's scratch (hit queues, candidate
-    //      lists, counters) and its per-origin / per-light records belong to one frame at a time.  `pre_used` is recorded when everything
-    //      a frame enqueues is on its stream; the next frame's stream waits for it (a no-op on the same stream) ----
-    if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
-    struct MarkPreUsed {
-        sr_scene* s; hipStream_t st;
-        ~MarkPreUsed() {
-            if (!s->pre_used && hipEventCreateWithFlags(&s->pre_used, hipEventDisableTiming) != hipSuccess) return;
-            if (hipEventRecord(s->pre_used, st) == hipSuccess) s->pre_used_set = true;
-        }
-    } mark_pre_used{s, stream};
+    // ---- frames of one scene run in submission order whatever streams they are given ----
+    StreamOrder order(s, stream);
+    if (order.entered) return order.entered;
     // ---- frame tables -> device ----
     const size_t off_bytes = (s->offsets_host.size() * sizeof(double) + 255) / 256 * 256, map_bytes = s->rowmap_host.size() * sizeof(int32_t);
     {
@@ -813,11 +882,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         rows = std::min<long long>(rows, ((long long)fc.num_rows + 15) / 16 * 16);
         sr_scene::BandScratch& B = s->scratch[0];
         if (n2v > 1) SR_HIP(B.samples.reserve((size_t)(rows * fc.width * n2v) * 4));
-        if (!s->num_cus) {
-            hipDeviceProp_t prop;
-            SR_HIP(hipGetDeviceProperties(&prop, s->device));
-            s->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        }
+        if ((rc = ensure_num_cus(s))) return rc;
         sr::VoxelLaunch V{};
         V.fc = fc;
         V.box = s->vox_box;
@@ -832,11 +897,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         V.stats = d_stats;
         V.stream = stream;
         V.user = s;
-        V.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
-            hipEvent_t x = nullptr, y = nullptr;
-            if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
-            *a = x; *b = y;
-        };
+        V.get_events = timing_events;
         SR_HIP(sr::launch_voxel_frame(V));
         return SR_OK;
     }
@@ -1141,11 +1202,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     unsigned round_items[sr::kShaftRounds] = {};
     for (int r = 0; r < sr::kShaftRounds; ++r)      // round 0 sees every hit; each later round is provisioned for 1/4 of the previous one
         round_items[r] = r == 0 ? (unsigned)band_samples : (unsigned)std::max<long long>(1024, (long long)round_items[r - 1] / 4);
-    if (!s->num_cus) {
-        hipDeviceProp_t prop;
-        SR_HIP(hipGetDeviceProperties(&prop, s->device));
-        s->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if ((rc = ensure_num_cus(s))) return rc;
     if (split) {
         if (!s->fork) SR_HIP(hipEventCreateWithFlags(&s->fork, hipEventDisableTiming));
         SR_HIP(hipEventRecord(s->fork, stream));                    // the halves start after the caller's earlier work
@@ -1430,11 +1487,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         P.stats = (pt_phase == 1 && !pt_reuse) ? nullptr : d_stats;      // (a counting pass that phase 2 repeats: its rays are counted there)
         P.stream = bs;
         P.user = s;
-        P.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
-            hipEvent_t x = nullptr, y = nullptr;
-            if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
-            *a = x; *b = y;
-        };
+        P.get_events = timing_events;
         P.band_done = nullptr;
         if (s->collect_bands) P.band_done = [](void* user, int band, int row_begin, int row_count, hipStream_t st) {
             sr_scene* sc = (sr_scene*)user;
@@ -1769,6 +1822,90 @@ int refit_from_device(sr_scene* s, const double* src_v9, const uint32_t* src_arg
         g_err = why;
     }
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// What the batch calls share: one stage of the renderer on data the caller supplies, as host arrays or as device arrays on a stream
+// ------------------------------------------------------------------------------------------------------------------
+// What a batch call that takes a frame refuses before the device is looked at, in the header's order: bad arguments; the switches that
+// name no step of the call's stage, each with its sentence; (the point calls) mirror bounces and row strips; then whatever sr_render
+// refuses of the frame the call runs, and of its trace mode
+struct FlagRefusal { uint32_t flag; const char* why; };
+struct BatchCall {
+    const char* bad_argument;
+    std::vector<FlagRefusal> flags;
+    const char* bounces;          // max_bounces > 0 (nullptr: not read)
+    const char* strips;           // strip_count > 0
+    uint32_t implied;             // the switches the call's frame carries whatever the caller's says
+    bool primary_only;            // sr_render_hits: the decorator switches and their parameters are not read
+};
+
+// `s`: in, the caller's scene; out, the scene that runs the call (the first part of a multi-device scene).  `args_ok`: the call's own test
+// of its arguments.  `fs`: the frame the call runs
+int batch_call_check(const BatchCall& c, sr_scene*& s, const sr_frame* f, bool args_ok, sr_frame& fs) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s || !f || !args_ok) return fail(SR_ERR_INVALID_ARG, c.bad_argument);
+    for (const FlagRefusal& r : c.flags)
+        if (f->flags & r.flag) return fail(SR_ERR_UNSUPPORTED, r.why);
+    if (c.bounces && f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, c.bounces);
+    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, c.strips);
+    fs = *f;
+    fs.flags |= c.implied;
+    if (c.primary_only) {
+        fs.flags &= (uint32_t)(SR_F_FOCAL_BLUR | SR_F_NO_SPLIT | SR_F_PRIMARY_STATS_ONLY);
+        fs.max_bounces = 0;
+        fs.reflectivity = 0.0;
+        fs.shadow_samples = 0;
+        fs.area_light_offsets = nullptr;
+    }
+    int rc = validate_frame(&fs, s);
+    if (rc) return rc;
+    return check_frame_mode(s, &fs);
+}
+
+// One array of a host-array variant: `up` is copied to the device before the call, `down` is filled from there after it (both: the call
+// works in place, as the device variant's `out` aliasing `color` does); the helper sets `dev`, nullptr where the caller passed neither
+struct Staged { const void* up; void* down; size_t bytes; void* dev; };
+
+// The host-array variant of a batch call around its device-array form: the arrays of `io` staged in the scene's d_io buffers, the
+// statistics zeroed, `run(stream, d_stats)` -- the call's enqueue, on io_stream -- then the way back of the arrays and of last_stats (a
+// multi-device parent `m` mirrors them; stats4: the caller's four primary counters, or nullptr) and one wait for the stream, which also
+// follows a refusal of `run`.  upload_async: the uploads go on the stream instead of blocking the host one by one
+template <class Run>
+int run_staged(sr_scene* m, sr_scene* s, Staged* io, int count, bool upload_async, uint64_t* stats4, Run run) {
+    int rc = ensure_io_streams(s);
+    if (rc) return rc;
+    hipStream_t stream = s->io_stream;
+    for (int i = 0; i < count; ++i) {
+        io[i].dev = nullptr;
+        if (!io[i].up && !io[i].down) continue;
+        SR_HIP(s->d_io[i].reserve(io[i].bytes));
+        io[i].dev = s->d_io[i].p;
+    }
+    for (int i = 0; i < count; ++i) {
+        if (!io[i].up) continue;
+        if (upload_async) SR_HIP(hipMemcpyAsync(io[i].dev, io[i].up, io[i].bytes, hipMemcpyHostToDevice, stream));
+        else SR_HIP(hipMemcpy(io[i].dev, io[i].up, io[i].bytes, hipMemcpyHostToDevice));
+    }
+    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
+    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    if ((rc = run(stream, (unsigned long long*)s->d_stats.p))) { (void)hipStreamSynchronize(stream); return rc; }
+    for (int i = 0; i < count; ++i)
+        if (io[i].down) SR_HIP(hipMemcpyAsync(io[i].down, io[i].dev, io[i].bytes, hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SR_HIP(hipStreamSynchronize(stream));
+    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
+    if (stats4) std::memcpy(stats4, s->last_stats, 4 * sizeof(uint64_t));
+    return SR_OK;
+}
+
+// An empty batch of a device variant that reports generators: the count is zeroed on the caller's stream, and no device is asked for
+int zero_generators_device(const sr_scene* s, uint64_t* d_generators, hipStream_t stream) {
+    if (d_generators && s->device >= 0) {
+        SR_HIP(hipSetDevice(s->device));
+        SR_HIP(hipMemsetAsync(d_generators, 0, sizeof(uint64_t), stream));
+    }
+    return SR_OK;
 }
 
 }  // namespace
@@ -2542,17 +2679,11 @@ int sr_bake_light_field(sr_scene* m, const sr_frame* f, uint64_t first, uint64_t
         // with shadows (validate_frame: the scene's switch is on): a frame's set-up, then passes of canonical rays + shadow stage + k_lf_store
         SR_HIP(hipMemsetAsync(s->d_stats.p, 0, sizeof(back), stream));
         const LfBakeReq req{first, count, (unsigned long long*)s->d_stats.p + SR_STATS_COUNT};
-        if ((rc = render_common(s, f, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, &req))) { (void)hipStreamSynchronize(stream); return rc; }
+        if ((rc = render_common(s, f, nullptr, stream, (unsigned long long*)s->d_stats.p, &req))) { (void)hipStreamSynchronize(stream); return rc; }
     } else {
         // ordered like a frame: after whatever frame is in flight (it may be filling cells), and the next frame after the bake
-        if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
-        struct MarkPreUsed {
-            sr_scene* s; hipStream_t st;
-            ~MarkPreUsed() {
-                if (!s->pre_used && hipEventCreateWithFlags(&s->pre_used, hipEventDisableTiming) != hipSuccess) return;
-                if (hipEventRecord(s->pre_used, st) == hipSuccess) s->pre_used_set = true;
-            }
-        } mark_pre_used{s, stream};
+        StreamOrder order(s, stream);
+        if (order.entered) return order.entered;
         SR_HIP(hipMemsetAsync(s->d_stats.p, 0, sizeof(back), stream));
         const bool lft = s->lf_tris;
         if (lft && (rc = sync_geometry(s, SR_MODE_REF_TREE))) return rc;
@@ -2573,11 +2704,7 @@ int sr_bake_light_field(sr_scene* m, const sr_frame* f, uint64_t first, uint64_t
         B.filled = (unsigned long long*)s->d_stats.p + SR_STATS_COUNT;
         B.stream = stream;
         B.user = s;
-        B.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
-            hipEvent_t x = nullptr, y = nullptr;
-            if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
-            *a = x; *b = y;
-        };
+        B.get_events = timing_events;
         const hipError_t e = sr::launch_lf_bake(B);
         if (e != hipSuccess) { (void)hipStreamSynchronize(stream); SR_HIP(e); }
     }
@@ -2643,7 +2770,7 @@ static int multi_render(sr_scene* m, const sr_frame* f, int32_t* host_pixels, vo
         }
         if (path) {
             // phase 1, then the part's own rows of the counts travel to the pinned array (the rows of the other parts stay theirs)
-            if ((rc = render_common(q, &fg[g], (uint32_t*)q->d_pixels.p, q->io_stream, ds, 1))) return rc;
+            if ((rc = render_common(q, &fg[g], (uint32_t*)q->d_pixels.p, q->io_stream, ds, RenderAsk::phase(1)))) return rc;
             std::vector<StripRun> runs = strip_runs(a, b, n, g);
             for (StripRun& r : runs) { r.image_row -= a; r.compact_row = r.image_row; }
             hipEvent_t x0 = nullptr;                                // the exchange as this part sees it: its copy out, the wait for the others, the copy back
@@ -2669,7 +2796,7 @@ static int multi_render(sr_scene* m, const sr_frame* f, int32_t* host_pixels, vo
             for (int h = 0; h < n; ++h) if (h != g && counts[h]) SR_HIP(hipStreamWaitEvent(q->io_stream, m->parts[h]->pt_counted, 0));
             SR_HIP(hipMemcpyAsync(q->d_pt_row_hits.p, m->pt_counts_host, range_rows * 4, hipMemcpyHostToDevice, q->io_stream));
             if (exchanged[g]) SR_HIP(hipEventRecord(exchanged[g], q->io_stream));
-            if ((rc = render_common(q, &fg[g], (uint32_t*)q->d_pixels.p, q->io_stream, stats4 ? (unsigned long long*)q->d_stats.p : nullptr, 2))) return rc;
+            if ((rc = render_common(q, &fg[g], (uint32_t*)q->d_pixels.p, q->io_stream, stats4 ? (unsigned long long*)q->d_stats.p : nullptr, RenderAsk::phase(2)))) return rc;
             if (!q->multi_done) SR_HIP(hipEventCreateWithFlags(&q->multi_done, hipEventDisableTiming));
             SR_HIP(hipEventRecord(q->multi_done, q->io_stream));
         }
@@ -2955,7 +3082,7 @@ int sr_trace_origin_rays_device(sr_scene* m, int32_t target, const double origin
     origin_rays_frame(fs, mode);
     const OriginReq req{{origin[0], origin[1], origin[2]}, n, d_dirs, {nullptr, nullptr, d_hit, d_ray_frac, d_pos, d_normal, d_color, d_tri_index},
                         (options & SR_RAYS_COHERENT) != 0, with_extra};
-    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, 0, nullptr, nullptr, nullptr, &req);
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, &req);
 }
 
 int sr_trace_origin_rays(sr_scene* m, int32_t target, const double origin[3], int64_t n, const double* dirs, uint8_t* hit, double* ray_frac, double* pos,
@@ -2965,32 +3092,16 @@ int sr_trace_origin_rays(sr_scene* m, int32_t target, const double origin[3], in
     int rc = origin_rays_check(s, target, origin, n, dirs, options, mode, with_extra);
     if (rc || n == 0) return rc;
     if ((rc = use_device(s))) return rc;
-    if ((rc = ensure_io_streams(s))) return rc;
-    hipStream_t stream = s->io_stream;
-    void* outs[6] = {hit, ray_frac, pos, normal, color, tri_index};
-    const size_t sizes[6] = {(size_t)n, (size_t)n * 8, (size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n * 4};
-    void* dev[6];
-    SR_HIP(s->d_io[0].reserve((size_t)n * 24));
-    for (int i = 0; i < 6; ++i) {
-        if (outs[i]) SR_HIP(s->d_io[1 + i].reserve(sizes[i]));
-        dev[i] = outs[i] ? s->d_io[1 + i].p : nullptr;
-    }
-    SR_HIP(hipMemcpyAsync(s->d_io[0].p, dirs, (size_t)n * 24, hipMemcpyHostToDevice, stream));
-    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
-    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
-    sr_frame fs;
-    origin_rays_frame(fs, mode);
-    const OriginReq req{{origin[0], origin[1], origin[2]}, n, (const double*)s->d_io[0].p,
-                        {nullptr, nullptr, (uint8_t*)dev[0], (double*)dev[1], (double*)dev[2], (double*)dev[3], (uint32_t*)dev[4], (int32_t*)dev[5]},
-                        (options & SR_RAYS_COHERENT) != 0, with_extra};
-    if ((rc = render_common(s, &fs, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, nullptr, nullptr, nullptr, &req))) { (void)hipStreamSynchronize(stream); return rc; }
-    for (int i = 0; i < 6; ++i)
-        if (outs[i]) SR_HIP(hipMemcpyAsync(outs[i], dev[i], sizes[i], hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipStreamSynchronize(stream));
-    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
-    if (stats) std::memcpy(stats, s->last_stats, 4 * sizeof(uint64_t));
-    return SR_OK;
+    Staged io[] = {{dirs, nullptr, (size_t)n * 24}, {nullptr, hit, (size_t)n}, {nullptr, ray_frac, (size_t)n * 8}, {nullptr, pos, (size_t)n * 24},
+                   {nullptr, normal, (size_t)n * 24}, {nullptr, color, (size_t)n * 4}, {nullptr, tri_index, (size_t)n * 4}};
+    return run_staged(m, s, io, 7, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
+        sr_frame fs;
+        origin_rays_frame(fs, mode);
+        const OriginReq req{{origin[0], origin[1], origin[2]}, n, (const double*)io[0].dev,
+                            {nullptr, nullptr, (uint8_t*)io[1].dev, (double*)io[2].dev, (double*)io[3].dev, (double*)io[4].dev, (uint32_t*)io[5].dev, (int32_t*)io[6].dev},
+                            (options & SR_RAYS_COHERENT) != 0, with_extra};
+        return render_common(s, &fs, nullptr, stream, d_stats, &req);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -3156,90 +3267,64 @@ int64_t sr_frame_sample_count(const sr_frame* f) {
     return (int64_t)(b - a + 1) * f->width * f->sub_pixel_res * f->sub_pixel_res;
 }
 
-// what sr_render_hits[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the first
-// part of a multi-device scene), `fs`: the frame without the decorator switches, which the call does not read
-static int render_hits_check(sr_scene*& s, const sr_frame* f, sr_frame& fs) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (!s || !f) return fail(SR_ERR_INVALID_ARG, "bad argument to sr_render_hits");
-    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_render_hits: voxel rendering (SR_F_VOXELS) replaces the root geometry; a voxel hit has no position or triangle");
-    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_render_hits: the light field (SR_F_LIGHT_FIELD) replaces the primary stage: a cell stores a colour, not a hit");
-    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_render_hits: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no primary stage to read");
-    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_render_hits: row strips (strip_count > 0) lay the rows out compactly; pass a row range");
-    fs = *f;
-    fs.flags &= (uint32_t)(SR_F_FOCAL_BLUR | SR_F_NO_SPLIT | SR_F_PRIMARY_STATS_ONLY);
-    fs.max_bounces = 0;
-    fs.reflectivity = 0.0;
-    fs.shadow_samples = 0;
-    fs.area_light_offsets = nullptr;
-    int rc = validate_frame(&fs, s);
-    if (rc) return rc;
-    return check_frame_mode(s, &fs);
-}
+// `fs`: the frame without the decorator switches, which the call does not read
+static const BatchCall kRenderHitsCall = {
+    "bad argument to sr_render_hits",
+    {{SR_F_VOXELS, "sr_render_hits: voxel rendering (SR_F_VOXELS) replaces the root geometry; a voxel hit has no position or triangle"},
+     {SR_F_LIGHT_FIELD, "sr_render_hits: the light field (SR_F_LIGHT_FIELD) replaces the primary stage: a cell stores a colour, not a hit"},
+     {SR_F_SINGLE_KERNEL, "sr_render_hits: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no primary stage to read"}},
+    nullptr,
+    "sr_render_hits: row strips (strip_count > 0) lay the rows out compactly; pass a row range",
+    0, true};
 
 int sr_render_hits_device(sr_scene* m, const sr_frame* f, double* d_starts, double* d_dirs, uint8_t* d_hit, double* d_ray_frac, double* d_pos, double* d_normal,
                           uint32_t* d_color, int32_t* d_tri_index, void* hip_stream, uint64_t* d_stats) {
     sr_scene* s = m;
     sr_frame fs;
-    int rc = render_hits_check(s, f, fs);
+    int rc = batch_call_check(kRenderHitsCall, s, f, true, fs);
     if (rc || sr_frame_sample_count(&fs) == 0) return rc;          // (an empty row range: nothing is drawn, no device is asked for)
     if ((rc = use_device(s))) return rc;
     if (m != s) m->last_parts = 1;
     hipStream_t stream = (hipStream_t)hip_stream;
     if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
     const HitsReq req{{d_starts, d_dirs, d_hit, d_ray_frac, d_pos, d_normal, d_color, d_tri_index}};
-    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, 0, nullptr, nullptr, &req);
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, &req);
 }
 
 int sr_render_hits(sr_scene* m, const sr_frame* f, double* starts, double* dirs, uint8_t* hit, double* ray_frac, double* pos, double* normal, uint32_t* color,
                    int32_t* tri_index, uint64_t stats[4]) {
     sr_scene* s = m;
     sr_frame fs;
-    int rc = render_hits_check(s, f, fs);
+    int rc = batch_call_check(kRenderHitsCall, s, f, true, fs);
     const int64_t n = sr_frame_sample_count(&fs);
     if (rc || n == 0) return rc;
     if ((rc = use_device(s))) return rc;
     if (m != s) m->last_parts = 1;
-    if ((rc = ensure_io_streams(s))) return rc;
-    hipStream_t stream = s->io_stream;
-    void* outs[8] = {starts, dirs, hit, ray_frac, pos, normal, color, tri_index};
-    const size_t sizes[8] = {(size_t)n * 24, (size_t)n * 24, (size_t)n, (size_t)n * 8, (size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n * 4};
-    void* dev[8];
-    for (int i = 0; i < 8; ++i) {
-        if (outs[i]) SR_HIP(s->d_io[i].reserve(sizes[i]));
-        dev[i] = outs[i] ? s->d_io[i].p : nullptr;
-    }
-    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
-    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
-    const HitsReq req{{(double*)dev[0], (double*)dev[1], (uint8_t*)dev[2], (double*)dev[3], (double*)dev[4], (double*)dev[5], (uint32_t*)dev[6], (int32_t*)dev[7]}};
-    if ((rc = render_common(s, &fs, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, nullptr, nullptr, &req))) { (void)hipStreamSynchronize(stream); return rc; }
-    for (int i = 0; i < 8; ++i)
-        if (outs[i]) SR_HIP(hipMemcpyAsync(outs[i], dev[i], sizes[i], hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipStreamSynchronize(stream));
-    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
-    if (stats) std::memcpy(stats, s->last_stats, 4 * sizeof(uint64_t));
-    return SR_OK;
+    Staged io[] = {{nullptr, starts, (size_t)n * 24}, {nullptr, dirs, (size_t)n * 24}, {nullptr, hit, (size_t)n}, {nullptr, ray_frac, (size_t)n * 8},
+                   {nullptr, pos, (size_t)n * 24}, {nullptr, normal, (size_t)n * 24}, {nullptr, color, (size_t)n * 4}, {nullptr, tri_index, (size_t)n * 4}};
+    return run_staged(m, s, io, 8, false, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
+        const HitsReq req{{(double*)io[0].dev, (double*)io[1].dev, (uint8_t*)io[2].dev, (double*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev,
+                           (uint32_t*)io[6].dev, (int32_t*)io[7].dev}};
+        return render_common(s, &fs, nullptr, stream, d_stats, &req);
+    });
 }
 
-// what sr_shadow_points[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the
-// first part of a multi-device scene), `fs`: the frame with SR_F_SHADOWS implied
+// ---- sr_shadow_points ----
+// `fs`: the frame with SR_F_SHADOWS implied
+static const BatchCall kShadowPointsCall = {
+    "bad argument to sr_shadow_points",
+    {{SR_F_STATIC_SHADOWS, "sr_shadow_points: static shadows (SR_F_STATIC_SHADOWS) are a cache over a frame's fill order, not a step on a point"},
+     {SR_F_AMBIENT_OCCLUSION, "sr_shadow_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is another decorator, not ShadowMethod's step"},
+     {SR_F_PATH_TRACING, "sr_shadow_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain ShadowMethod is part of"},
+     {SR_F_VOXELS, "sr_shadow_points: voxel rendering (SR_F_VOXELS) has no shadow step"},
+     {SR_F_LIGHT_FIELD, "sr_shadow_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points"},
+     {SR_F_SINGLE_KERNEL, "sr_shadow_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter"}},
+    "sr_shadow_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point",
+    "sr_shadow_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points",
+    SR_F_SHADOWS, false};
 static int shadow_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* pos, const void* normal, const void* out, uint32_t options, sr_frame& fs) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (!s || !f || n < 0 || (n > 0 && (!pos || !normal || !out)) || (options & ~(uint32_t)SR_POINTS_COHERENT))
-        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_shadow_points");
-    if (f->flags & SR_F_STATIC_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: static shadows (SR_F_STATIC_SHADOWS) are a cache over a frame's fill order, not a step on a point");
-    if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is another decorator, not ShadowMethod's step");
-    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain ShadowMethod is part of");
-    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: voxel rendering (SR_F_VOXELS) has no shadow step");
-    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points");
-    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter");
-    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point");
-    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_shadow_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points");
-    fs = *f;
-    fs.flags |= SR_F_SHADOWS;
-    int rc = validate_frame(&fs, s);
-    if (rc) return rc;
-    return check_frame_mode(s, &fs);
+    const bool args_ok = n >= 0 && (n == 0 || (pos && normal && out)) && !(options & ~(uint32_t)SR_POINTS_COHERENT);
+    return batch_call_check(kShadowPointsCall, s, f, args_ok, fs);
 }
 
 int sr_shadow_points_device(sr_scene* m, const sr_frame* f, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color, uint32_t* d_out,
@@ -3252,7 +3337,7 @@ int sr_shadow_points_device(sr_scene* m, const sr_frame* f, int64_t n, const dou
     hipStream_t stream = (hipStream_t)hip_stream;
     if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
     const PtsReq req{n, d_pos, d_normal, d_color, d_out, (options & SR_POINTS_COHERENT) != 0};
-    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, 0, nullptr, &req);
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, &req);
 }
 
 int sr_shadow_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, uint32_t options) {
@@ -3261,46 +3346,31 @@ int sr_shadow_points(sr_scene* m, const sr_frame* f, int64_t n, const double* po
     int rc = shadow_points_check(s, f, n, pos, normal, out, options, fs);
     if (rc || n == 0) return rc;
     if ((rc = use_device(s))) return rc;
-    if ((rc = ensure_io_streams(s))) return rc;
-    hipStream_t stream = s->io_stream;
-    const size_t sizes[3] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 4};
-    for (int i = 0; i < 3; ++i) SR_HIP(s->d_io[i].reserve(sizes[i]));
-    SR_HIP(hipMemcpy(s->d_io[0].p, pos, sizes[0], hipMemcpyHostToDevice));
-    SR_HIP(hipMemcpy(s->d_io[1].p, normal, sizes[1], hipMemcpyHostToDevice));
-    if (color) SR_HIP(hipMemcpy(s->d_io[2].p, color, sizes[2], hipMemcpyHostToDevice));
-    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
-    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
     // (the colours are modulated where they lie: the device variant's `out` aliasing `color`)
-    const PtsReq req{n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, color ? (const uint32_t*)s->d_io[2].p : nullptr, (uint32_t*)s->d_io[2].p,
-                     (options & SR_POINTS_COHERENT) != 0};
-    if ((rc = render_common(s, &fs, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, nullptr, &req))) { (void)hipStreamSynchronize(stream); return rc; }
-    SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipStreamSynchronize(stream));
-    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
-    return SR_OK;
+    Staged io[] = {{pos, nullptr, (size_t)n * 24}, {normal, nullptr, (size_t)n * 24}, {color, out, (size_t)n * 4}};
+    return run_staged(m, s, io, 3, false, nullptr, [&](hipStream_t stream, unsigned long long* d_stats) {
+        const PtsReq req{n, (const double*)io[0].dev, (const double*)io[1].dev, color ? (const uint32_t*)io[2].dev : nullptr, (uint32_t*)io[2].dev,
+                         (options & SR_POINTS_COHERENT) != 0};
+        return render_common(s, &fs, nullptr, stream, d_stats, &req);
+    });
 }
 
 // ---- sr_static_shadow_points ----
-// what sr_static_shadow_points[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the
-// first part of a multi-device scene, where the cache lives), `fs`: the frame with SR_F_SHADOWS | SR_F_STATIC_SHADOWS implied
+// `fs`: the frame with SR_F_SHADOWS | SR_F_STATIC_SHADOWS implied (a multi-device scene: the cache lives on the first part)
+static const BatchCall kStaticShadowPointsCall = {
+    "bad argument to sr_static_shadow_points",
+    {{SR_F_AMBIENT_OCCLUSION, "sr_static_shadow_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is another decorator, not ShadowMethod's step"},
+     {SR_F_PATH_TRACING, "sr_static_shadow_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain ShadowMethod is part of"},
+     {SR_F_VOXELS, "sr_static_shadow_points: voxel rendering (SR_F_VOXELS) has no shadow step"},
+     {SR_F_LIGHT_FIELD, "sr_static_shadow_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points"},
+     {SR_F_SINGLE_KERNEL, "sr_static_shadow_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter"}},
+    "sr_static_shadow_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point",
+    "sr_static_shadow_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points",
+    SR_F_SHADOWS | SR_F_STATIC_SHADOWS, false};
 static int static_shadow_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* pos, const void* normal, const void* out, const void* amount,
                                       uint32_t options, sr_frame& fs) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (n < 0 || (n > 0 && (!pos || !normal)) || (n > 0 && !out && !amount) || !s || !f || (options & ~(uint32_t)SR_POINTS_COHERENT))
-        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_static_shadow_points");
-    if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is another decorator, not ShadowMethod's step");
-    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain ShadowMethod is part of");
-    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: voxel rendering (SR_F_VOXELS) has no shadow step");
-    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points");
-    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter");
-    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point");
-    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_static_shadow_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points");
-    fs = *f;
-    fs.flags |= SR_F_SHADOWS | SR_F_STATIC_SHADOWS;
-    int rc = validate_frame(&fs, s);
-    if (rc) return rc;
-    return check_frame_mode(s, &fs);
+    const bool args_ok = n >= 0 && (n == 0 || (pos && normal && (out || amount))) && !(options & ~(uint32_t)SR_POINTS_COHERENT);
+    return batch_call_check(kStaticShadowPointsCall, s, f, args_ok, fs);
 }
 
 int sr_static_shadow_points_device(sr_scene* m, const sr_frame* f, int64_t n, const double* d_pos, const double* d_normal, const uint32_t* d_color, uint32_t* d_out,
@@ -3310,18 +3380,12 @@ int sr_static_shadow_points_device(sr_scene* m, const sr_frame* f, int64_t n, co
     int rc = static_shadow_points_check(s, f, n, d_pos, d_normal, d_out, d_amount, options, fs);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (n == 0) {
-        if (d_generators && s->device >= 0) {
-            SR_HIP(hipSetDevice(s->device));
-            SR_HIP(hipMemsetAsync(d_generators, 0, sizeof(uint64_t), stream));
-        }
-        return SR_OK;
-    }
+    if (n == 0) return zero_generators_device(s, d_generators, stream);
     if ((rc = use_device(s))) return rc;
     if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
     if (d_generators) SR_HIP(hipMemsetAsync(d_generators, 0, sizeof(uint64_t), stream));
     const PtsReq req{n, d_pos, d_normal, d_color, d_out, (options & SR_POINTS_COHERENT) != 0, true, d_amount, (unsigned long long*)d_generators};
-    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, 0, nullptr, &req);
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, &req);
 }
 
 int sr_static_shadow_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos, const double* normal, const uint32_t* color, uint32_t* out, uint8_t* amount,
@@ -3332,54 +3396,38 @@ int sr_static_shadow_points(sr_scene* m, const sr_frame* f, int64_t n, const dou
     if (rc) return rc;
     if (n == 0) { if (generators) *generators = 0; return SR_OK; }
     if ((rc = use_device(s))) return rc;
-    if ((rc = ensure_io_streams(s))) return rc;
-    hipStream_t stream = s->io_stream;
-    const size_t sizes[5] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n, sizeof(uint64_t)};
-    for (int i = 0; i < 5; ++i) SR_HIP(s->d_io[i].reserve(sizes[i]));
-    SR_HIP(hipMemcpy(s->d_io[0].p, pos, sizes[0], hipMemcpyHostToDevice));
-    SR_HIP(hipMemcpy(s->d_io[1].p, normal, sizes[1], hipMemcpyHostToDevice));
-    if (color) SR_HIP(hipMemcpy(s->d_io[2].p, color, sizes[2], hipMemcpyHostToDevice));
-    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
-    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
-    SR_HIP(hipMemsetAsync(s->d_io[4].p, 0, sizes[4], stream));
     // (the colours are modulated where they lie: the device variant's `out` aliasing `color`)
-    const PtsReq req{n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, color ? (const uint32_t*)s->d_io[2].p : nullptr,
-                     out ? (uint32_t*)s->d_io[2].p : nullptr, (options & SR_POINTS_COHERENT) != 0, true, amount ? (uint8_t*)s->d_io[3].p : nullptr,
-                     (unsigned long long*)s->d_io[4].p};
-    if ((rc = render_common(s, &fs, nullptr, stream, (unsigned long long*)s->d_stats.p, 0, nullptr, &req))) { (void)hipStreamSynchronize(stream); return rc; }
     uint64_t made = 0;
-    if (out) SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
-    if (amount) SR_HIP(hipMemcpyAsync(amount, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipMemcpyAsync(&made, s->d_io[4].p, sizes[4], hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipStreamSynchronize(stream));
-    if (generators) *generators = made;
-    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
-    return SR_OK;
+    Staged io[] = {{pos, nullptr, (size_t)n * 24}, {normal, nullptr, (size_t)n * 24}, {color, out, (size_t)n * 4}, {nullptr, amount, (size_t)n},
+                   {nullptr, &made, sizeof(uint64_t)}};
+    rc = run_staged(m, s, io, 5, false, nullptr, [&](hipStream_t stream, unsigned long long* d_stats) {
+        SR_HIP(hipMemsetAsync(io[4].dev, 0, sizeof(uint64_t), stream));
+        const PtsReq req{n, (const double*)io[0].dev, (const double*)io[1].dev, color ? (const uint32_t*)io[2].dev : nullptr,
+                         out ? (uint32_t*)io[2].dev : nullptr, (options & SR_POINTS_COHERENT) != 0, true, (uint8_t*)io[3].dev, (unsigned long long*)io[4].dev};
+        return render_common(s, &fs, nullptr, stream, d_stats, &req);
+    });
+    if (!rc && generators) *generators = made;
+    return rc;
 }
 
 // ---- sr_ao_points ----
 const uint64_t kAoPointsMaxGenerators = 1ull << 40;
-// what sr_ao_points[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the first
-// part of a multi-device scene), `fs`: the frame with SR_F_AMBIENT_OCCLUSION implied
+// `fs`: the frame with SR_F_AMBIENT_OCCLUSION implied
+static const BatchCall kAoPointsCall = {
+    "bad argument to sr_ao_points",
+    {{SR_F_STATIC_SHADOWS, "sr_ao_points: static shadows (SR_F_STATIC_SHADOWS) are another decorator's cache, not AmbientOcclusionMethod's step"},
+     {SR_F_PATH_TRACING, "sr_ao_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain AmbientOcclusionMethod is part of"},
+     {SR_F_VOXELS, "sr_ao_points: voxel rendering (SR_F_VOXELS) has no occlusion step"},
+     {SR_F_LIGHT_FIELD, "sr_ao_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points"},
+     {SR_F_SINGLE_KERNEL, "sr_ao_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter"}},
+    "sr_ao_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point",
+    "sr_ao_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points",
+    SR_F_AMBIENT_OCCLUSION, false};
 static int ao_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* pos, const void* normal, const void* out, const void* amount,
                            uint64_t first_generator, uint32_t options, sr_frame& fs) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (n < 0 || (n > 0 && (!pos || !normal)) || (n > 0 && !out && !amount) || !s || !f || options != 0 ||
-        first_generator > kAoPointsMaxGenerators || (uint64_t)n > kAoPointsMaxGenerators - first_generator)
-        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_ao_points");
-    if (f->flags & SR_F_STATIC_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: static shadows (SR_F_STATIC_SHADOWS) are another decorator's cache, not AmbientOcclusionMethod's step");
-    if (f->flags & SR_F_PATH_TRACING) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain AmbientOcclusionMethod is part of");
-    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: voxel rendering (SR_F_VOXELS) has no occlusion step");
-    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points");
-    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter");
-    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point");
-    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_ao_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points");
-    fs = *f;
-    fs.flags |= SR_F_AMBIENT_OCCLUSION;
-    int rc = validate_frame(&fs, s);
-    if (rc) return rc;
-    return check_frame_mode(s, &fs);
+    const bool args_ok = n >= 0 && (n == 0 || (pos && normal && (out || amount))) && options == 0 && first_generator <= kAoPointsMaxGenerators &&
+                         (uint64_t)n <= kAoPointsMaxGenerators - first_generator;
+    return batch_call_check(kAoPointsCall, s, f, args_ok, fs);
 }
 
 // the jump coefficients of the table kernels' chunk strides (k_aop_states), uploaded once per scene
@@ -3410,14 +3458,8 @@ static int ao_points_common(sr_scene* s, const sr_frame* f, const AoPtsReq& q, h
     if (!host_table && !sr::net_random_window(f->random_seed, L.window.s)) host_table = true;   // (not the recurrence for this seed: sr_host.h)
     if (!host_table && (rc = ensure_aop_rows(s))) return rc;
     // ---- ordered like a frame (render_common) ----
-    if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
-    struct MarkPreUsed {
-        sr_scene* s; hipStream_t st;
-        ~MarkPreUsed() {
-            if (!s->pre_used && hipEventCreateWithFlags(&s->pre_used, hipEventDisableTiming) != hipSuccess) return;
-            if (hipEventRecord(s->pre_used, st) == hipSuccess) s->pre_used_set = true;
-        }
-    } mark_pre_used{s, stream};
+    StreamOrder order(s, stream);
+    if (order.entered) return order.entered;
     if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
     if (cached) {
         SR_HIP(s->d_ao_cache.reserve(kAoCells));
@@ -3429,11 +3471,7 @@ static int ao_points_common(sr_scene* s, const sr_frame* f, const AoPtsReq& q, h
     }
     const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kAopMaxPass) : sr::kAopMaxPass;
     const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, q.n));
-    if (!s->num_cus) {
-        hipDeviceProp_t prop;
-        SR_HIP(hipGetDeviceProperties(&prop, s->device));
-        s->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if ((rc = ensure_num_cus(s))) return rc;
     sr_scene::BandScratch& B = s->scratch[0];                        // (sr_debug_counters keeps describing the last frame: the call has no queue counters)
     const size_t slots = (size_t)(pass + 255) / 256 * 256;
     SR_HIP(B.hits.reserve(slots * sr::pipeline_hit_record_bytes()));
@@ -3464,27 +3502,10 @@ static int ao_points_common(sr_scene* s, const sr_frame* f, const AoPtsReq& q, h
     L.persistent_blocks = s->num_cus * 8;
     L.stream = stream;
     L.user = s;
-    L.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
-        hipEvent_t x = nullptr, y = nullptr;
-        if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
-        *a = x; *b = y;
-    };
+    L.get_events = timing_events;
     if (host_table) {
-        // System.Random itself, one draw after the other, from the call's first generator on (the passes ask in ascending order)
-        s->aop_host_random.reset(new sr::NetRandom(f->random_seed));
-        for (uint64_t i = 0; i < q.first_generator * 300ull; ++i) (void)s->aop_host_random->next();
-        s->aop_host_drawn = q.first_generator;
-        L.host_table = [](void* user, uint64_t base, uint32_t count, int32_t* d_table, hipStream_t st) -> hipError_t {
-            sr_scene* sc = (sr_scene*)user;
-            if (base != sc->aop_host_drawn) return hipErrorInvalidValue;
-            if (count == 0) return hipSuccess;
-            std::vector<int32_t> ints((size_t)count * 300);
-            for (int32_t& v : ints) v = sc->aop_host_random->next();
-            sc->aop_host_drawn += count;
-            hipError_t e = hipMemcpyAsync(d_table, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) return e;
-            return hipStreamSynchronize(st);                           // (`ints` leaves scope)
-        };
+        start_host_table(s, f->random_seed, q.first_generator, 300);   // from the call's first generator on
+        L.host_table = fill_host_table;
     }
     const hipError_t pe = sr::launch_ao_points(L);
     s->aop_host_random.reset();
@@ -3499,13 +3520,7 @@ int sr_ao_points_device(sr_scene* m, const sr_frame* f, int64_t n, const double*
     int rc = ao_points_check(s, f, n, d_pos, d_normal, d_out, d_amount, first_generator, options, fs);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (n == 0) {
-        if (d_generators && s->device >= 0) {
-            SR_HIP(hipSetDevice(s->device));
-            SR_HIP(hipMemsetAsync(d_generators, 0, sizeof(uint64_t), stream));
-        }
-        return SR_OK;
-    }
+    if (n == 0) return zero_generators_device(s, d_generators, stream);
     if ((rc = use_device(s))) return rc;
     if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
     const AoPtsReq req{n, d_pos, d_normal, d_color, d_out, d_amount, first_generator, (unsigned long long*)d_generators};
@@ -3520,53 +3535,38 @@ int sr_ao_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos, c
     if (rc) return rc;
     if (n == 0) { if (generators) *generators = 0; return SR_OK; }
     if ((rc = use_device(s))) return rc;
-    if ((rc = ensure_io_streams(s))) return rc;
-    hipStream_t stream = s->io_stream;
-    const size_t sizes[5] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n, sizeof(uint64_t)};
-    for (int i = 0; i < 5; ++i) SR_HIP(s->d_io[i].reserve(sizes[i]));
-    SR_HIP(hipMemcpy(s->d_io[0].p, pos, sizes[0], hipMemcpyHostToDevice));
-    SR_HIP(hipMemcpy(s->d_io[1].p, normal, sizes[1], hipMemcpyHostToDevice));
-    if (color) SR_HIP(hipMemcpy(s->d_io[2].p, color, sizes[2], hipMemcpyHostToDevice));
-    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
-    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
     // (the colours are modulated where they lie: the device variant's `out` aliasing `color`)
-    const AoPtsReq req{n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, color ? (const uint32_t*)s->d_io[2].p : nullptr,
-                       out ? (uint32_t*)s->d_io[2].p : nullptr, amount ? (uint8_t*)s->d_io[3].p : nullptr, first_generator, (unsigned long long*)s->d_io[4].p};
-    if ((rc = ao_points_common(s, &fs, req, stream, (unsigned long long*)s->d_stats.p))) { (void)hipStreamSynchronize(stream); return rc; }
     uint64_t made = 0;
-    if (out) SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
-    if (amount) SR_HIP(hipMemcpyAsync(amount, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipMemcpyAsync(&made, s->d_io[4].p, sizes[4], hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipStreamSynchronize(stream));
-    if (generators) *generators = made;
-    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
-    return SR_OK;
+    Staged io[] = {{pos, nullptr, (size_t)n * 24}, {normal, nullptr, (size_t)n * 24}, {color, out, (size_t)n * 4}, {nullptr, amount, (size_t)n},
+                   {nullptr, &made, sizeof(uint64_t)}};
+    rc = run_staged(m, s, io, 5, false, nullptr, [&](hipStream_t stream, unsigned long long* d_stats) {
+        const AoPtsReq req{n, (const double*)io[0].dev, (const double*)io[1].dev, color ? (const uint32_t*)io[2].dev : nullptr,
+                           out ? (uint32_t*)io[2].dev : nullptr, (uint8_t*)io[3].dev, first_generator, (unsigned long long*)io[4].dev};
+        return ao_points_common(s, &fs, req, stream, d_stats);
+    });
+    if (!rc && generators) *generators = made;
+    return rc;
 }
 
 // ---- sr_path_points ----
 const uint64_t kPathPointsMaxSamples = 1ull << 40;
 const uint64_t kPathPointsHostTableSamples = 1ull << 30;     // ... where the host makes the table: it draws its way there
-// what sr_path_points[_device] refuses before the device is looked at, in the header's order; `s`: the scene that runs the call (the first
-// part of a multi-device scene), `fs`: the frame with SR_F_PATH_TRACING implied
+// `fs`: the frame with SR_F_PATH_TRACING implied
+static const BatchCall kPathPointsCall = {
+    "bad argument to sr_path_points",
+    {{SR_F_SHADOWS, "sr_path_points: shadows (SR_F_SHADOWS, dynamic or static) are ShadowMethod's step, which follows this one: sr_shadow_points"},
+     {SR_F_AMBIENT_OCCLUSION, "sr_path_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is AmbientOcclusionMethod's step, which follows this one: sr_ao_points"},
+     {SR_F_VOXELS, "sr_path_points: voxel rendering (SR_F_VOXELS) has no surface point to bounce from"},
+     {SR_F_LIGHT_FIELD, "sr_path_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points"},
+     {SR_F_SINGLE_KERNEL, "sr_path_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter"}},
+    "sr_path_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point",
+    "sr_path_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points",
+    SR_F_PATH_TRACING, false};
 static int path_points_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* pos, const void* normal, const void* out, const void* incoming,
                              const void* dirs, uint64_t first_sample, uint32_t options, sr_frame& fs) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (n < 0 || (n > 0 && (!pos || !normal)) || (n > 0 && !out && !incoming && !dirs) || !s || !f || options != 0 ||
-        first_sample > kPathPointsMaxSamples || (uint64_t)n > kPathPointsMaxSamples - first_sample)
-        return fail(SR_ERR_INVALID_ARG, "bad argument to sr_path_points");
-    if (f->flags & SR_F_SHADOWS) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: shadows (SR_F_SHADOWS, dynamic or static) are ShadowMethod's step, which follows this one: sr_shadow_points");
-    if (f->flags & SR_F_AMBIENT_OCCLUSION) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is AmbientOcclusionMethod's step, which follows this one: sr_ao_points");
-    if (f->flags & SR_F_VOXELS) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: voxel rendering (SR_F_VOXELS) has no surface point to bounce from");
-    if (f->flags & SR_F_LIGHT_FIELD) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points");
-    if (f->flags & SR_F_SINGLE_KERNEL) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter");
-    if (f->max_bounces > 0) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point");
-    if (f->strip_count > 0) return fail(SR_ERR_UNSUPPORTED, "sr_path_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points");
-    fs = *f;
-    fs.flags |= SR_F_PATH_TRACING;
-    int rc = validate_frame(&fs, s);
-    if (rc) return rc;
-    return check_frame_mode(s, &fs);
+    const bool args_ok = n >= 0 && (n == 0 || (pos && normal && (out || incoming || dirs))) && options == 0 && first_sample <= kPathPointsMaxSamples &&
+                         (uint64_t)n <= kPathPointsMaxSamples - first_sample;
+    return batch_call_check(kPathPointsCall, s, f, args_ok, fs);
 }
 
 struct PathPtsReq { int64_t n; const double* pos; const double* nrm; const uint32_t* color; uint32_t* out; uint32_t* incoming; double* dirs; uint64_t first_sample; };
@@ -3599,20 +3599,10 @@ static int path_points_common(sr_scene* s, const sr_frame* f, const PathPtsReq& 
         }
     }
     // ---- ordered like a frame (render_common) ----
-    if (s->pre_used_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_used, 0));
-    struct MarkPreUsed {
-        sr_scene* s; hipStream_t st;
-        ~MarkPreUsed() {
-            if (!s->pre_used && hipEventCreateWithFlags(&s->pre_used, hipEventDisableTiming) != hipSuccess) return;
-            if (hipEventRecord(s->pre_used, st) == hipSuccess) s->pre_used_set = true;
-        }
-    } mark_pre_used{s, stream};
+    StreamOrder order(s, stream);
+    if (order.entered) return order.entered;
     if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
-    if (!s->num_cus) {
-        hipDeviceProp_t prop;
-        SR_HIP(hipGetDeviceProperties(&prop, s->device));
-        s->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if ((rc = ensure_num_cus(s))) return rc;
     sr_scene::BandScratch& B = s->scratch[0];                        // (sr_debug_counters keeps describing the last frame: the call has counters of its own)
     const size_t slots = (size_t)(pass + 255) / 256 * 256;
     if (trace) SR_HIP(B.hits2.reserve(slots * sr::pipeline_hit_record_bytes()));
@@ -3651,26 +3641,10 @@ static int path_points_common(sr_scene* s, const sr_frame* f, const PathPtsReq& 
     L.persistent_blocks = s->num_cus * 8;
     L.stream = stream;
     L.user = s;
-    L.get_events = [](void* user, int kid, hipEvent_t* a, hipEvent_t* b) {
-        hipEvent_t x = nullptr, y = nullptr;
-        if (next_events((sr_scene*)user, kid, x, y) != SR_OK) { x = y = nullptr; }
-        *a = x; *b = y;
-    };
+    L.get_events = timing_events;
     if (host_table) {
-        // System.Random itself, one draw after the other, from the call's first sample on (the passes ask in ascending order)
-        s->aop_host_random.reset(new sr::NetRandom(f->random_seed));
-        for (uint64_t i = 0; i < q.first_sample * 3ull; ++i) (void)s->aop_host_random->next();
-        s->aop_host_drawn = q.first_sample;
-        L.host_table = [](void* user, uint64_t base, uint32_t count, int32_t* d_table, hipStream_t st) -> hipError_t {
-            sr_scene* sc = (sr_scene*)user;
-            if (base != sc->aop_host_drawn) return hipErrorInvalidValue;
-            std::vector<int32_t> ints((size_t)count * 3);
-            for (int32_t& v : ints) v = sc->aop_host_random->next();
-            sc->aop_host_drawn += count;
-            hipError_t e = hipMemcpyAsync(d_table, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) return e;
-            return hipStreamSynchronize(st);                           // (`ints` leaves scope)
-        };
+        start_host_table(s, f->random_seed, q.first_sample, 3);         // from the call's first sample on
+        L.host_table = fill_host_table;
     }
     const hipError_t pe = sr::launch_path_points(L);
     s->aop_host_random.reset();
@@ -3700,27 +3674,14 @@ int sr_path_points(sr_scene* m, const sr_frame* f, int64_t n, const double* pos,
     if (rc) return rc;
     if (n == 0) return SR_OK;
     if ((rc = use_device(s))) return rc;
-    if ((rc = ensure_io_streams(s))) return rc;
-    hipStream_t stream = s->io_stream;
-    const size_t sizes[5] = {(size_t)n * 24, (size_t)n * 24, (size_t)n * 4, (size_t)n * 4, (size_t)n * 24};
-    const bool used[5] = {true, true, color || out, incoming != nullptr, dirs != nullptr};
-    for (int i = 0; i < 5; ++i) if (used[i]) SR_HIP(s->d_io[i].reserve(sizes[i]));
-    SR_HIP(hipMemcpy(s->d_io[0].p, pos, sizes[0], hipMemcpyHostToDevice));
-    SR_HIP(hipMemcpy(s->d_io[1].p, normal, sizes[1], hipMemcpyHostToDevice));
-    if (color) SR_HIP(hipMemcpy(s->d_io[2].p, color, sizes[2], hipMemcpyHostToDevice));
-    SR_HIP(s->d_stats.reserve(SR_STATS_COUNT * sizeof(uint64_t)));
-    SR_HIP(hipMemsetAsync(s->d_stats.p, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
     // (the colours are finished where they lie: the device variant's `out` aliasing `color`)
-    const PathPtsReq req{n, (const double*)s->d_io[0].p, (const double*)s->d_io[1].p, color ? (const uint32_t*)s->d_io[2].p : nullptr,
-                         out ? (uint32_t*)s->d_io[2].p : nullptr, incoming ? (uint32_t*)s->d_io[3].p : nullptr, dirs ? (double*)s->d_io[4].p : nullptr, first_sample};
-    if ((rc = path_points_common(s, &fs, req, stream, (unsigned long long*)s->d_stats.p))) { (void)hipStreamSynchronize(stream); return rc; }
-    if (out) SR_HIP(hipMemcpyAsync(out, s->d_io[2].p, sizes[2], hipMemcpyDeviceToHost, stream));
-    if (incoming) SR_HIP(hipMemcpyAsync(incoming, s->d_io[3].p, sizes[3], hipMemcpyDeviceToHost, stream));
-    if (dirs) SR_HIP(hipMemcpyAsync(dirs, s->d_io[4].p, sizes[4], hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipMemcpyAsync(s->last_stats, s->d_stats.p, SR_STATS_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipStreamSynchronize(stream));
-    if (m != s) std::memcpy(m->last_stats, s->last_stats, sizeof(m->last_stats));
-    return SR_OK;
+    Staged io[] = {{pos, nullptr, (size_t)n * 24}, {normal, nullptr, (size_t)n * 24}, {color, out, (size_t)n * 4}, {nullptr, incoming, (size_t)n * 4},
+                   {nullptr, dirs, (size_t)n * 24}};
+    return run_staged(m, s, io, 5, false, nullptr, [&](hipStream_t stream, unsigned long long* d_stats) {
+        const PathPtsReq req{n, (const double*)io[0].dev, (const double*)io[1].dev, color ? (const uint32_t*)io[2].dev : nullptr,
+                             out ? (uint32_t*)io[2].dev : nullptr, (uint32_t*)io[3].dev, (double*)io[4].dev, first_sample};
+        return path_points_common(s, &fs, req, stream, d_stats);
+    });
 }
 
 int sr_net_random_jump(int32_t seed, uint64_t skip, int32_t out[55]) {

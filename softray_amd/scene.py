@@ -23,6 +23,35 @@ def _check(rc):
         raise SoftrayError(rc, _lib.lib().sr_last_error().decode())
 
 
+def _vp(x):
+    """A device pointer (an int; 0 / None: not given) as the C ABI takes it."""
+    return C.c_void_p(x) if x else None
+
+
+def _stream(stream):
+    """A raw hipStream_t or a torch.cuda.Stream as the C ABI takes it."""
+    return _vp(getattr(stream, "cuda_stream", stream))
+
+
+def _surface_points(pos, normal, color):
+    """(pos float64 [n, 3], normal float64 [n, 3], color uint32 [n] or None, n) of a point call's arrays, one entry per point."""
+    pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+    normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+    if normal.shape[0] != pos.shape[0]:
+        raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
+    if color is not None:
+        color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
+        if color.size != pos.shape[0]:
+            raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
+    return pos, normal, color, pos.shape[0]
+
+
+def _hit_arrays(n):
+    """The six arrays a trace of n rays answers with, keyed like trace()'s result."""
+    return dict(hit=np.zeros(n, dtype=np.uint8), ray_frac=np.zeros(n), pos=np.zeros((n, 3)),
+                normal=np.zeros((n, 3)), color=np.zeros(n, dtype=np.uint32), tri_index=np.zeros(n, dtype=np.int32))
+
+
 class GpuScene:
     def __init__(self, device=0, devices=None):
         """device: one HIP ordinal (-1 = host-only scene); devices: a list of ordinals -> ONE scene over several GPUs of this
@@ -102,8 +131,7 @@ class GpuScene:
         bmax = np.ascontiguousarray(bmax, dtype=np.float64)
         if bmin.size != 3 or bmax.size != 3:
             raise ValueError("bmin and bmax are three doubles each")
-        st = getattr(stream, "cuda_stream", stream)
-        _check(call(self._h, C.c_void_p(pv) if pv else None, C.c_void_p(pa) if pa else None, nv, _p(bmin), _p(bmax), C.c_void_p(st) if st else None))
+        _check(call(self._h, _vp(pv), _vp(pa), nv, _p(bmin), _p(bmax), _stream(stream)))
 
     def load_3ds(self, data):
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
@@ -391,44 +419,28 @@ class GpuScene:
     def shadow_points(self, frame, pos, normal, color=None, coherent=False):
         """ShadowMethod's soft shadow for caller-given surface points (sr_shadow_points): uint32 [n], color[i] (None: 0xFFFFFFFF) modulated
         with the byte of the frame's light, samples and root geometry.  coherent: 64 consecutive points are neighbours (no ray sort)."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
-        normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
-        if normal.shape[0] != pos.shape[0]:
-            raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
-        if color is not None:
-            color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
-            if color.size != pos.shape[0]:
-                raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
-        out = np.zeros(pos.shape[0], dtype=np.uint32)
-        _check(_lib.lib().sr_shadow_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out),
+        pos, normal, color, n = _surface_points(pos, normal, color)
+        out = np.zeros(n, dtype=np.uint32)
+        _check(_lib.lib().sr_shadow_points(self._h, C.byref(frame), n, _p(pos), _p(normal), _p(color), _p(out),
                                            _lib.POINTS_COHERENT if coherent else 0))
         return out
 
     def shadow_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, coherent=False, stream=0, d_stats_ptr=None):
         """sr_shadow_points_device: every array is a DEVICE pointer (d_color 0 / None: every point 0xFFFFFFFF; d_out may be d_color);
         enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
-        vp = lambda x: C.c_void_p(x) if x else None
-        st = getattr(stream, "cuda_stream", stream)
-        _check(_lib.lib().sr_shadow_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out),
-                                                  _lib.POINTS_COHERENT if coherent else 0, vp(st), vp(d_stats_ptr)))
+        _check(_lib.lib().sr_shadow_points_device(self._h, C.byref(frame), int(n), _vp(d_pos), _vp(d_normal), _vp(d_color), _vp(d_out),
+                                                  _lib.POINTS_COHERENT if coherent else 0, _stream(stream), _vp(d_stats_ptr)))
 
     def static_shadow_points(self, frame, pos, normal, color=None, coherent=False, want_out=True, want_amount=True):
         """ShadowMethod's static branch for caller-given surface points, in input order (sr_static_shadow_points): (out uint32 [n] or None,
         amount uint8 [n] or None, generators).  The first point of an empty cell of the scene's static shadow cache generates the cell's
         byte; every point reads its cell.  color None: every point 0xFFFFFFFF.  coherent: the generators of a pass are neighbours in input
         order (no sort)."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
-        normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
-        if normal.shape[0] != pos.shape[0]:
-            raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
-        if color is not None:
-            color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
-            if color.size != pos.shape[0]:
-                raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
-        out = np.zeros(pos.shape[0], dtype=np.uint32) if want_out else None
-        amount = np.zeros(pos.shape[0], dtype=np.uint8) if want_amount else None
+        pos, normal, color, n = _surface_points(pos, normal, color)
+        out = np.zeros(n, dtype=np.uint32) if want_out else None
+        amount = np.zeros(n, dtype=np.uint8) if want_amount else None
         made = C.c_uint64(0)
-        _check(_lib.lib().sr_static_shadow_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out), _p(amount),
+        _check(_lib.lib().sr_static_shadow_points(self._h, C.byref(frame), n, _p(pos), _p(normal), _p(color), _p(out), _p(amount),
                                                   _lib.POINTS_COHERENT if coherent else 0, C.byref(made)))
         return out, amount, int(made.value)
 
@@ -437,28 +449,19 @@ class GpuScene:
         """sr_static_shadow_points_device: every array is a DEVICE pointer (d_color 0 / None: every point 0xFFFFFFFF; d_out may be d_color; one
         of d_out / d_amount may be 0 / None; d_generators_ptr: a device uint64 or None); enqueued on `stream` (a raw hipStream_t or a
         torch.cuda.Stream), no host sync."""
-        vp = lambda x: C.c_void_p(x) if x else None
-        st = getattr(stream, "cuda_stream", stream)
-        _check(_lib.lib().sr_static_shadow_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out),
-                                                         vp(d_amount), _lib.POINTS_COHERENT if coherent else 0, vp(st), vp(d_generators_ptr),
-                                                         vp(d_stats_ptr)))
+        _check(_lib.lib().sr_static_shadow_points_device(self._h, C.byref(frame), int(n), _vp(d_pos), _vp(d_normal), _vp(d_color), _vp(d_out),
+                                                         _vp(d_amount), _lib.POINTS_COHERENT if coherent else 0, _stream(stream), _vp(d_generators_ptr),
+                                                         _vp(d_stats_ptr)))
 
     def ao_points(self, frame, pos, normal, color=None, first_generator=0, want_out=True, want_amount=True):
         """AmbientOcclusionMethod's step for caller-given surface points, in input order (sr_ao_points): (out uint32 [n] or None, amount
         uint8 [n] or None, generators).  Cached in the scene's AO cache unless the frame has F_AO_UNCACHED; generator g of the call uses
         draws 300 (first_generator + g) .. + 299 of Random(frame.random_seed).  color None: every point 0xFFFFFFFF."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
-        normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
-        if normal.shape[0] != pos.shape[0]:
-            raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
-        if color is not None:
-            color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
-            if color.size != pos.shape[0]:
-                raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
-        out = np.zeros(pos.shape[0], dtype=np.uint32) if want_out else None
-        amount = np.zeros(pos.shape[0], dtype=np.uint8) if want_amount else None
+        pos, normal, color, n = _surface_points(pos, normal, color)
+        out = np.zeros(n, dtype=np.uint32) if want_out else None
+        amount = np.zeros(n, dtype=np.uint8) if want_amount else None
         made = C.c_uint64(0)
-        _check(_lib.lib().sr_ao_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out), _p(amount),
+        _check(_lib.lib().sr_ao_points(self._h, C.byref(frame), n, _p(pos), _p(normal), _p(color), _p(out), _p(amount),
                                        int(first_generator), 0, C.byref(made)))
         return out, amount, int(made.value)
 
@@ -467,27 +470,18 @@ class GpuScene:
         """sr_ao_points_device: every array is a DEVICE pointer (d_color 0 / None: every point 0xFFFFFFFF; d_out may be d_color; one of d_out /
         d_amount may be 0 / None; d_generators_ptr: a device uint64 or None); enqueued on `stream` (a raw hipStream_t or a
         torch.cuda.Stream), no host sync."""
-        vp = lambda x: C.c_void_p(x) if x else None
-        st = getattr(stream, "cuda_stream", stream)
-        _check(_lib.lib().sr_ao_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out), vp(d_amount),
-                                              int(first_generator), 0, vp(st), vp(d_generators_ptr), vp(d_stats_ptr)))
+        _check(_lib.lib().sr_ao_points_device(self._h, C.byref(frame), int(n), _vp(d_pos), _vp(d_normal), _vp(d_color), _vp(d_out), _vp(d_amount),
+                                              int(first_generator), 0, _stream(stream), _vp(d_generators_ptr), _vp(d_stats_ptr)))
 
     def path_points(self, frame, pos, normal, color=None, first_sample=0, want_out=True, want_incoming=True, want_dirs=True):
         """PathTracingMethod's step for caller-given surface points, in input order (sr_path_points): (out uint32 [n], incoming uint32 [n],
         dirs float64 [n, 3]), each None when not wanted.  Point i uses draws 3 (first_sample + i) .. + 2 of Random(frame.random_seed); a
         split batch passes first_sample + n to the next call.  color None: every point 0xFFFFFFFF."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
-        normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
-        if normal.shape[0] != pos.shape[0]:
-            raise ValueError("normal has %d entries for %d points" % (normal.shape[0], pos.shape[0]))
-        if color is not None:
-            color = np.ascontiguousarray(color, dtype=np.uint32).reshape(-1)
-            if color.size != pos.shape[0]:
-                raise ValueError("color has %d entries for %d points" % (color.size, pos.shape[0]))
-        out = np.zeros(pos.shape[0], dtype=np.uint32) if want_out else None
-        incoming = np.zeros(pos.shape[0], dtype=np.uint32) if want_incoming else None
-        dirs = np.zeros((pos.shape[0], 3), dtype=np.float64) if want_dirs else None
-        _check(_lib.lib().sr_path_points(self._h, C.byref(frame), pos.shape[0], _p(pos), _p(normal), _p(color), _p(out), _p(incoming), _p(dirs),
+        pos, normal, color, n = _surface_points(pos, normal, color)
+        out = np.zeros(n, dtype=np.uint32) if want_out else None
+        incoming = np.zeros(n, dtype=np.uint32) if want_incoming else None
+        dirs = np.zeros((n, 3), dtype=np.float64) if want_dirs else None
+        _check(_lib.lib().sr_path_points(self._h, C.byref(frame), n, _p(pos), _p(normal), _p(color), _p(out), _p(incoming), _p(dirs),
                                          int(first_sample), 0))
         return out, incoming, dirs
 
@@ -495,16 +489,12 @@ class GpuScene:
         """sr_path_points_device: every array is a DEVICE pointer (d_color 0 / None: every point 0xFFFFFFFF; d_out may be d_color; d_out,
         d_incoming and d_dirs may each be 0 / None, not all three); enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no
         host sync."""
-        vp = lambda x: C.c_void_p(x) if x else None
-        st = getattr(stream, "cuda_stream", stream)
-        _check(_lib.lib().sr_path_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out), vp(d_incoming),
-                                                vp(d_dirs), int(first_sample), 0, vp(st), vp(d_stats_ptr)))
+        _check(_lib.lib().sr_path_points_device(self._h, C.byref(frame), int(n), _vp(d_pos), _vp(d_normal), _vp(d_color), _vp(d_out), _vp(d_incoming),
+                                                _vp(d_dirs), int(first_sample), 0, _stream(stream), _vp(d_stats_ptr)))
 
     def shade_points_device(self, frame, n, d_pos, d_normal, d_color, d_out, stream=0):
         """sr_shade_points_device: every array is a DEVICE pointer; enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
-        vp = lambda x: C.c_void_p(x) if x else None
-        st = getattr(stream, "cuda_stream", stream)
-        _check(_lib.lib().sr_shade_points_device(self._h, C.byref(frame), int(n), vp(d_pos), vp(d_normal), vp(d_color), vp(d_out), vp(st)))
+        _check(_lib.lib().sr_shade_points_device(self._h, C.byref(frame), int(n), _vp(d_pos), _vp(d_normal), _vp(d_color), _vp(d_out), _stream(stream)))
 
     # ---- the frame G-buffer: the primary stage's answer per camera sample (sr_render_hits) ----
     @staticmethod
@@ -517,8 +507,7 @@ class GpuScene:
         result (hit, ray_frac, pos, normal, color, tri_index), with rays=True also the camera rays (starts, dirs), with stats=True the four
         primary counters (stats)."""
         n = self.sample_count(frame)
-        res = dict(hit=np.zeros(n, dtype=np.uint8), ray_frac=np.zeros(n), pos=np.zeros((n, 3)),
-                   normal=np.zeros((n, 3)), color=np.zeros(n, dtype=np.uint32), tri_index=np.zeros(n, dtype=np.int32))
+        res = _hit_arrays(n)
         if rays:
             res["starts"], res["dirs"] = np.zeros((n, 3)), np.zeros((n, 3))
         st = np.zeros(4, dtype=np.uint64) if stats else None
@@ -532,18 +521,15 @@ class GpuScene:
                            d_stats_ptr=None):
         """sr_render_hits_device: every array is a DEVICE pointer (0 / None: not wanted) with room for sample_count(frame) entries; enqueued on
         `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
-        vp = lambda x: C.c_void_p(x) if x else None
-        st = getattr(stream, "cuda_stream", stream)
-        _check(_lib.lib().sr_render_hits_device(self._h, C.byref(frame), vp(d_starts), vp(d_dirs), vp(d_hit), vp(d_ray_frac), vp(d_pos), vp(d_normal),
-                                                vp(d_color), vp(d_tri_index), vp(st), vp(d_stats_ptr)))
+        _check(_lib.lib().sr_render_hits_device(self._h, C.byref(frame), _vp(d_starts), _vp(d_dirs), _vp(d_hit), _vp(d_ray_frac), _vp(d_pos), _vp(d_normal),
+                                                _vp(d_color), _vp(d_tri_index), _stream(stream), _vp(d_stats_ptr)))
 
     # ---- IRayIntersectable.IntersectRay, batched ----
     def trace(self, target, starts, dirs, counters=False):
         starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
         dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
         n = starts.shape[0]
-        res = dict(hit=np.zeros(n, dtype=np.uint8), ray_frac=np.zeros(n), pos=np.zeros((n, 3)),
-                   normal=np.zeros((n, 3)), color=np.zeros(n, dtype=np.uint32), tri_index=np.zeros(n, dtype=np.int32))
+        res = _hit_arrays(n)
         cnt = np.zeros((n, 3), dtype=np.int32) if counters else None
         _check(_lib.lib().sr_trace_rays(self._h, int(target), n, _p(starts), _p(dirs), _p(res["hit"]), _p(res["ray_frac"]),
                                         _p(res["pos"]), _p(res["normal"]), _p(res["color"]), _p(res["tri_index"]), _p(cnt)))
@@ -554,9 +540,8 @@ class GpuScene:
 
     def trace_device(self, target, n, d_starts, d_dirs, d_hit=0, d_ray_frac=0, d_pos=0, d_normal=0, d_color=0, d_tri_index=0, d_counters=0, stream=0):
         """sr_trace_rays_device: every array is a DEVICE pointer (e.g. tensor.data_ptr()); enqueued on `stream`, no host sync."""
-        vp = lambda x: C.c_void_p(x) if x else None
-        _check(_lib.lib().sr_trace_rays_device(self._h, int(target), int(n), vp(d_starts), vp(d_dirs), vp(d_hit), vp(d_ray_frac), vp(d_pos),
-                                               vp(d_normal), vp(d_color), vp(d_tri_index), vp(d_counters), vp(stream)))
+        _check(_lib.lib().sr_trace_rays_device(self._h, int(target), int(n), _vp(d_starts), _vp(d_dirs), _vp(d_hit), _vp(d_ray_frac), _vp(d_pos),
+                                               _vp(d_normal), _vp(d_color), _vp(d_tri_index), _vp(d_counters), _vp(stream)))
 
     # ---- a ray batch from one origin on the frame's packet walk (sr_trace_origin_rays) ----
     def trace_origin(self, target, origin, dirs, coherent=False, stats=False):
@@ -565,8 +550,7 @@ class GpuScene:
         origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
         dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
         n = dirs.shape[0]
-        res = dict(hit=np.zeros(n, dtype=np.uint8), ray_frac=np.zeros(n), pos=np.zeros((n, 3)),
-                   normal=np.zeros((n, 3)), color=np.zeros(n, dtype=np.uint32), tri_index=np.zeros(n, dtype=np.int32))
+        res = _hit_arrays(n)
         st = np.zeros(4, dtype=np.uint64) if stats else None
         _check(_lib.lib().sr_trace_origin_rays(self._h, int(target), _p(origin), n, _p(dirs), _p(res["hit"]), _p(res["ray_frac"]), _p(res["pos"]),
                                                _p(res["normal"]), _p(res["color"]), _p(res["tri_index"]), _lib.RAYS_COHERENT if coherent else 0, _p(st)))
@@ -579,11 +563,9 @@ class GpuScene:
         """sr_trace_origin_rays_device: `origin` is a host triple, every array a DEVICE pointer (0 / None: not wanted); enqueued on `stream` (a raw
         hipStream_t or a torch.cuda.Stream), no host sync."""
         origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
-        vp = lambda x: C.c_void_p(x) if x else None
-        st = getattr(stream, "cuda_stream", stream)
-        _check(_lib.lib().sr_trace_origin_rays_device(self._h, int(target), _p(origin), int(n), vp(d_dirs), vp(d_hit), vp(d_ray_frac), vp(d_pos),
-                                                      vp(d_normal), vp(d_color), vp(d_tri_index), _lib.RAYS_COHERENT if coherent else 0, vp(st),
-                                                      vp(d_stats_ptr)))
+        _check(_lib.lib().sr_trace_origin_rays_device(self._h, int(target), _p(origin), int(n), _vp(d_dirs), _vp(d_hit), _vp(d_ray_frac), _vp(d_pos),
+                                                      _vp(d_normal), _vp(d_color), _vp(d_tri_index), _lib.RAYS_COHERENT if coherent else 0, _stream(stream),
+                                                      _vp(d_stats_ptr)))
 
     # ---- the strip gather over RCCL (include/softray.h) ----
     def set_gather(self, kind):

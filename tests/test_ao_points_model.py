@@ -133,21 +133,32 @@ def test_refusals_in_order_on_a_host_only_scene(device):
         for k, v in kw.items():
             setattr(f, k, v)
         return f
-    unsupported = [changed(flags=L.F_STATIC_SHADOWS), changed(flags=L.F_PATH_TRACING), changed(flags=L.F_VOXELS), changed(flags=L.F_LIGHT_FIELD),
-                   changed(flags=L.F_SINGLE_KERNEL), changed(max_bounces=1), changed(strip_rows=16, strip_count=2, strip_index=0)]
+    # (the refused frame, the whole message of sr_last_error)
+    unsupported = [(changed(flags=L.F_STATIC_SHADOWS),
+                    "sr_ao_points: static shadows (SR_F_STATIC_SHADOWS) are another decorator's cache, not AmbientOcclusionMethod's step"),
+                   (changed(flags=L.F_PATH_TRACING),
+                    "sr_ao_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain AmbientOcclusionMethod is part of"),
+                   (changed(flags=L.F_VOXELS), "sr_ao_points: voxel rendering (SR_F_VOXELS) has no occlusion step"),
+                   (changed(flags=L.F_LIGHT_FIELD),
+                    "sr_ao_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points"),
+                   (changed(flags=L.F_SINGLE_KERNEL), "sr_ao_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter"),
+                   (changed(max_bounces=1), "sr_ao_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point"),
+                   (changed(strip_rows=16, strip_count=2, strip_index=0),
+                    "sr_ao_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points")]
     # 1. SR_ERR_INVALID_ARG, whatever else is wrong with the frame (the model has no tree yet: SR_ERR_NOT_BUILT would come later)
-    bad_frame = unsupported[0]
+    bad_frame = unsupported[0][0]
     for kw in (dict(n=-1), dict(pos=False), dict(nrm=False), dict(out=False, amount=False), dict(options=1), dict(options=0x80000000),
                dict(first=2 ** 40 - 3), dict(first=2 ** 40 + 1, n=0), dict(first=2 ** 64 - 1)):
         assert call(h, bad_frame, device=device, **kw)[0] == L.SR_ERR_INVALID_ARG, kw
+        assert L.lib().sr_last_error().decode() == "bad argument to sr_ao_points", kw
     assert call(None, good, device=device)[0] == L.SR_ERR_INVALID_ARG
     assert call(h, None, device=device)[0] == L.SR_ERR_INVALID_ARG
     assert call(h, good, first=2 ** 40 - 4, device=device)[0] != L.SR_ERR_INVALID_ARG                    # first_generator + n == 2^40 is legal
     # 2. SR_ERR_UNSUPPORTED before the frame and its trace mode are validated (width 0 and no tree would be refused otherwise)
-    for f in unsupported:
+    for f, text in unsupported:
         f.width = 0
         rc, _ = call(h, f, device=device)
-        assert rc == L.SR_ERR_UNSUPPORTED and "sr_ao_points" in L.lib().sr_last_error().decode()
+        assert rc == L.SR_ERR_UNSUPPORTED and L.lib().sr_last_error().decode() == text and text.startswith("sr_ao_points: ")
     # 3. sr_render's validation of the frame, then of its trace mode
     assert call(h, changed(width=0), device=device)[0] == L.SR_ERR_INVALID_ARG
     assert call(h, changed(sub_pixel_res=0), device=device)[0] == L.SR_ERR_INVALID_ARG

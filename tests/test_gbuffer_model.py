@@ -90,8 +90,13 @@ def raw_call(s, f, arrays, device=False):
     return sa._lib.lib().sr_render_hits(h, fr, *args, None)
 
 
-REFUSED = [(dict(flags=1 << 7), "SR_F_VOXELS"), (dict(flags=1 << 15), "SR_F_LIGHT_FIELD"), (dict(flags=1 << 8), "SR_F_SINGLE_KERNEL"),
-           (dict(strips=(16, 2, 0)), "strip_count > 0")]
+# (the change, the name it is refused by, the whole message of sr_last_error)
+REFUSED = [(dict(flags=1 << 7), "SR_F_VOXELS",
+            "sr_render_hits: voxel rendering (SR_F_VOXELS) replaces the root geometry; a voxel hit has no position or triangle"),
+           (dict(flags=1 << 15), "SR_F_LIGHT_FIELD",
+            "sr_render_hits: the light field (SR_F_LIGHT_FIELD) replaces the primary stage: a cell stores a colour, not a hit"),
+           (dict(flags=1 << 8), "SR_F_SINGLE_KERNEL", "sr_render_hits: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no primary stage to read"),
+           (dict(strips=(16, 2, 0)), "strip_count > 0", "sr_render_hits: row strips (strip_count > 0) lay the rows out compactly; pass a row range")]
 
 
 @pytest.mark.parametrize("device", [False, True], ids=["host_arrays", "device_arrays"])
@@ -108,16 +113,17 @@ def test_refusals_come_in_order_on_a_host_only_scene(device):
     worst.sub_pixel_res = 0
     for fr in (f, worst):
         assert call(None, fr) == E.SR_ERR_INVALID_ARG
+        assert E.lib().sr_last_error().decode() == "bad argument to sr_render_hits"
     assert call(s, None) == E.SR_ERR_INVALID_ARG and call(s, None, none) == E.SR_ERR_INVALID_ARG
     # (2) what replaces the root geometry or the primary stage, each by name -- before the rest of the frame's validation and the mode
-    for change, name in REFUSED:
+    for change, name, text in REFUSED:
         for base in (sr_frame(), sr_frame(mode=sa.MODE_BVH)):
             fr = lfm.apply_change(base, change)
             fr.sub_pixel_res = 0 if base.trace_mode == sa.MODE_BVH else 1
             for arr in (arrays, none):
                 assert call(s, fr, arr) == E.SR_ERR_UNSUPPORTED, name
                 msg = E.lib().sr_last_error().decode()
-                assert msg.startswith("sr_render_hits:") and name in msg, (name, msg)
+                assert msg == text and msg.startswith("sr_render_hits:") and name in msg, (name, msg)
     # (3) sr_render's validation of the frame, then of its trace mode
     bad = sr_frame()
     bad.sub_pixel_res = 0

@@ -382,3 +382,44 @@ def test_chain_on_the_device_is_the_static_frame(golden, shape, mode):
     assert same(got, want) and same(cache_of(g), want_cache)
     if sub == 1:
         assert same(want_cache, golden.cache)                                 # the 100x100 frame: the goldens' cache
+
+
+# ---- 8. ordered with the frames it shares the cache with ----
+def test_call_is_ordered_with_frames_on_other_streams(cases):
+    """A static-shadow frame on one stream, the call on another at once, the frame again behind it, nothing waited for in between: the scene's
+    scratch and its cache belong to one of the three at a time, so they leave what they leave one after the other with a device synchronise
+    in between -- both images, the call's outputs and generator count and every cache byte.  (The serial sequence is bit-stable: it runs
+    twice.)"""
+    c = cases("obj")
+    g = c.gpu()
+    fr = as_sr(make_frame(256, 192, shadows=True, static_shadows=True))
+    f = as_sr(c.frame)
+    n, npx = c.n, 256 * 192
+    d_pos, d_nrm = torch.from_numpy(c.pos).to(DEV), torch.from_numpy(c.nrm).to(DEV)
+    d_col = torch.from_numpy(c.color.view(np.int32).copy()).to(DEV)
+    streams = [torch.cuda.Stream(DEV) for _ in range(3)]
+
+    def sequence(serial):
+        g.reset_shadow_cache()
+        px = [torch.zeros(npx, dtype=torch.int32, device=DEV) for _ in range(2)]
+        d_out, d_amt = torch.zeros(n, dtype=torch.int32, device=DEV), torch.zeros(n, dtype=torch.uint8, device=DEV)
+        d_gen = torch.full((1,), -7, dtype=torch.int64, device=DEV)
+        torch.cuda.synchronize(DEV)
+        g.render_device(fr, px[0].data_ptr(), streams[0].cuda_stream)
+        if serial:
+            torch.cuda.synchronize(DEV)
+        g.static_shadow_points_device(f, n, d_pos.data_ptr(), d_nrm.data_ptr(), d_col.data_ptr(), d_out.data_ptr(), d_amt.data_ptr(),
+                                      stream=streams[1], d_generators_ptr=d_gen.data_ptr())
+        if serial:
+            torch.cuda.synchronize(DEV)
+        g.render_device(fr, px[1].data_ptr(), streams[2].cuda_stream)
+        torch.cuda.synchronize(DEV)
+        return [px[0].cpu().numpy(), px[1].cpu().numpy(), d_out.cpu().numpy(), d_amt.cpu().numpy(), d_gen.cpu().numpy(), cache_of(g).copy()]
+    want, again = sequence(True), sequence(True)
+    assert all(same(a, b) for a, b in zip(want, again))
+    gens, filled = int(want[4][0]), int(np.count_nonzero(want[5]))
+    print("frame, call, frame: the call made %d generators of %d points, %d cells are filled" % (gens, n, filled))
+    assert 0 < gens < n and filled > gens and len(np.unique(want[3])) > 5          # the frame took cells, the call made others
+    got = sequence(False)
+    for name, a, b in zip(("first image", "second image", "out", "amount", "generators", "cache"), got, want):
+        assert same(a, b), name

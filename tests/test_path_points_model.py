@@ -201,20 +201,31 @@ def test_refusals_in_order_on_a_host_only_scene(device):
         for k, v in kw.items():
             setattr(f, k, v)
         return f
-    unsupported = [changed(flags=L.F_SHADOWS), changed(flags=L.F_SHADOWS | L.F_STATIC_SHADOWS), changed(flags=L.F_AMBIENT_OCCLUSION), changed(flags=L.F_VOXELS),
-                   changed(flags=L.F_LIGHT_FIELD), changed(flags=L.F_SINGLE_KERNEL), changed(max_bounces=1), changed(strip_rows=16, strip_count=2, strip_index=0)]
+    # (the refused frame, the whole message of sr_last_error)
+    shadows = "sr_path_points: shadows (SR_F_SHADOWS, dynamic or static) are ShadowMethod's step, which follows this one: sr_shadow_points"
+    unsupported = [(changed(flags=L.F_SHADOWS), shadows), (changed(flags=L.F_SHADOWS | L.F_STATIC_SHADOWS), shadows),
+                   (changed(flags=L.F_AMBIENT_OCCLUSION),
+                    "sr_path_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is AmbientOcclusionMethod's step, which follows this one: sr_ao_points"),
+                   (changed(flags=L.F_VOXELS), "sr_path_points: voxel rendering (SR_F_VOXELS) has no surface point to bounce from"),
+                   (changed(flags=L.F_LIGHT_FIELD),
+                    "sr_path_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points"),
+                   (changed(flags=L.F_SINGLE_KERNEL), "sr_path_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter"),
+                   (changed(max_bounces=1), "sr_path_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point"),
+                   (changed(strip_rows=16, strip_count=2, strip_index=0),
+                    "sr_path_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points")]
     # 1. SR_ERR_INVALID_ARG, whatever else is wrong with the frame (the model has no tree yet: SR_ERR_NOT_BUILT would come later)
-    bad_frame = unsupported[0]
+    bad_frame = unsupported[0][0]
     for kw in (dict(n=-1), dict(pos=False), dict(nrm=False), dict(out=False, incoming=False, dirs=False), dict(options=1), dict(options=0x80000000),
                dict(first=2 ** 40 - 3), dict(first=2 ** 40 + 1, n=0), dict(first=2 ** 64 - 1)):
         assert call(h, bad_frame, device=device, **kw) == L.SR_ERR_INVALID_ARG, kw
+        assert L.lib().sr_last_error().decode() == "bad argument to sr_path_points", kw
     assert call(None, good, device=device) == L.SR_ERR_INVALID_ARG
     assert call(h, None, device=device) == L.SR_ERR_INVALID_ARG
     assert call(h, good, first=2 ** 40 - 4, device=device) != L.SR_ERR_INVALID_ARG                       # first_sample + n == 2^40 is legal
     # 2. SR_ERR_UNSUPPORTED before the frame and its trace mode are validated (width 0 and no tree would be refused otherwise)
-    for f in unsupported:
+    for f, text in unsupported:
         f.width = 0
-        assert call(h, f, device=device) == L.SR_ERR_UNSUPPORTED and "sr_path_points" in L.lib().sr_last_error().decode()
+        assert call(h, f, device=device) == L.SR_ERR_UNSUPPORTED and L.lib().sr_last_error().decode() == text and text.startswith("sr_path_points: ")
     # the order inside the group: shadows are named before ambient occlusion, that before voxels
     assert call(h, changed(flags=L.F_SHADOWS | L.F_AMBIENT_OCCLUSION | L.F_VOXELS), device=device) == L.SR_ERR_UNSUPPORTED
     assert "shadows" in L.lib().sr_last_error().decode()

@@ -63,9 +63,20 @@ def raw_call(s, f, n, pos, nrm, color, out, options=0, device=False):
     return sa._lib.lib().sr_shadow_points(h, fr, n, p(pos), p(nrm), p(color), p(out), options)
 
 
-REFUSED = [(dict(flags=1 << 5), "SR_F_STATIC_SHADOWS"), (dict(flags=1 << 13), "SR_F_AMBIENT_OCCLUSION"), (dict(flags=1 << 6), "SR_F_PATH_TRACING"),
-           (dict(flags=1 << 7), "SR_F_VOXELS"), (dict(flags=1 << 15), "SR_F_LIGHT_FIELD"), (dict(flags=1 << 8), "SR_F_SINGLE_KERNEL"),
-           (dict(max_bounces=1), "max_bounces > 0"), (dict(strips=(16, 2, 0)), "strip_count > 0")]
+# (the change, the name it is refused by, the whole message of sr_last_error)
+REFUSED = [(dict(flags=1 << 5), "SR_F_STATIC_SHADOWS",
+            "sr_shadow_points: static shadows (SR_F_STATIC_SHADOWS) are a cache over a frame's fill order, not a step on a point"),
+           (dict(flags=1 << 13), "SR_F_AMBIENT_OCCLUSION",
+            "sr_shadow_points: ambient occlusion (SR_F_AMBIENT_OCCLUSION) is another decorator, not ShadowMethod's step"),
+           (dict(flags=1 << 6), "SR_F_PATH_TRACING",
+            "sr_shadow_points: path tracing (SR_F_PATH_TRACING) replaces the decorator chain ShadowMethod is part of"),
+           (dict(flags=1 << 7), "SR_F_VOXELS", "sr_shadow_points: voxel rendering (SR_F_VOXELS) has no shadow step"),
+           (dict(flags=1 << 15), "SR_F_LIGHT_FIELD",
+            "sr_shadow_points: the light field (SR_F_LIGHT_FIELD) stores colours of canonical rays, not of a caller's points"),
+           (dict(flags=1 << 8), "SR_F_SINGLE_KERNEL", "sr_shadow_points: the one-kernel renderer (SR_F_SINGLE_KERNEL) has no stage to enter"),
+           (dict(max_bounces=1), "max_bounces > 0", "sr_shadow_points: mirror bounces (max_bounces > 0) belong to a camera ray, not to a point"),
+           (dict(strips=(16, 2, 0)), "strip_count > 0",
+            "sr_shadow_points: row strips (strip_count > 0) divide a frame's rows, not a batch of points")]
 
 
 @pytest.mark.parametrize("device", [False, True], ids=["host_arrays", "device_arrays"])
@@ -82,6 +93,7 @@ def test_refusals_come_in_order_on_a_host_only_scene(device):
     worst.sub_pixel_res = 0
     for fr in (f, worst):
         assert call(s, fr, -1, pos, nrm, col, out) == E.SR_ERR_INVALID_ARG
+        assert E.lib().sr_last_error().decode() == "bad argument to sr_shadow_points"
         assert call(s, fr, 4, None, nrm, col, out) == E.SR_ERR_INVALID_ARG
         assert call(s, fr, 4, pos, None, col, out) == E.SR_ERR_INVALID_ARG
         assert call(s, fr, 4, pos, nrm, col, None) == E.SR_ERR_INVALID_ARG
@@ -91,13 +103,13 @@ def test_refusals_come_in_order_on_a_host_only_scene(device):
     assert call(s, None, 4, pos, nrm, col, out) == E.SR_ERR_INVALID_ARG
     assert call(s, None, 0, None, None, None, None) == E.SR_ERR_INVALID_ARG
     # (2) what names no step of ShadowMethod on a bare point, each by name -- before the rest of the frame's validation and the mode
-    for change, name in REFUSED:
+    for change, name, text in REFUSED:
         for base in (sr_frame(), sr_frame(mode=sa.MODE_BVH)):
             fr = lfm.apply_change(base, change)
             fr.sub_pixel_res = 0 if base.trace_mode == sa.MODE_BVH else 1
             assert call(s, fr, 4, pos, nrm, col, out) == E.SR_ERR_UNSUPPORTED, name
             msg = E.lib().sr_last_error().decode()
-            assert msg.startswith("sr_shadow_points:") and name in msg, (name, msg)
+            assert msg == text and msg.startswith("sr_shadow_points:") and name in msg, (name, msg)
             assert call(s, fr, 0, None, None, None, None) == E.SR_ERR_UNSUPPORTED, name           # n == 0 passes no check
     # (3) the rest of the frame's validation, then the trace mode
     bad = sr_frame()

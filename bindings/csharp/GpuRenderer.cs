@@ -120,6 +120,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_render_hits_device(IntPtr scene, ref SrFrame frame, IntPtr dStarts, IntPtr dDirs, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_trace_origin_rays(IntPtr scene, int target, [In] double[] origin3, long n, [In] double[] dirs, [Out] byte[] hit, [Out] double[] rayFrac, [Out] double[] pos, [Out] double[] normal, [Out] uint[] color, [Out] int[] triIndex, uint options, [Out] ulong[] stats4);
         [DllImport(Lib)] public static extern int sr_trace_origin_rays_device(IntPtr scene, int target, [In] double[] origin3, long n, IntPtr dDirs, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, uint options, IntPtr hipStream, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_occluded_rays(IntPtr scene, int target, long n, [In] double[] starts, [In] double[] dirs, [In] double[] limits, [Out] byte[] occluded, uint options, [Out] ulong[] stats4);
+        [DllImport(Lib)] public static extern int sr_occluded_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, IntPtr dOccluded, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -603,6 +605,29 @@ namespace Engine3D.Hip
         {
             Native.Check(Native.sr_trace_origin_rays_device(scene, mode | (root ? 0x100 : 0), new[] { origin.x, origin.y, origin.z }, n, dDirs, dHit, dRayFrac, dPos,
                                                             dNormal, dColor, dTriIndex, coherent ? RAYS_COHERENT : 0, stream, dStats));
+        }
+
+        /// "Is anything in the way before distance L" for a batch of rays (sr_occluded_rays): result[i] = 1 iff IntersectRay(starts[i], D_i) hits
+        /// with rayFrac &lt;= limits[i] (limits == null: 1.0 for every ray) on the root geometry (root = true) or the model alone -- the test of
+        /// ShadowMethod.cs:169-172, with early exit on the own BVH.  starts and dirs are double[n * 3]; D_i = dirs[i], or with endpoints
+        /// dirs[i] - starts[i] (dirs holds end points).  coherent: the rays are walked in the order given.  Blocks.
+        public const uint RAYS_ENDPOINTS = 2;
+        public byte[] OccludedRays(double[] starts, double[] dirs, double[] limits, int mode, bool root = false, bool endpoints = false, bool coherent = false)
+        {
+            long n = starts.Length / 3;
+            var occluded = new byte[n];
+            Native.Check(Native.sr_occluded_rays(scene, mode | (root ? 0x100 : 0), n, starts, dirs, limits, occluded,
+                                                 (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), null));
+            return occluded;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_occluded_rays_device), dLimits IntPtr.Zero for 1.0 throughout;
+        /// enqueued on `stream` without a host synchronisation; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void OccludedRaysDevice(long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, IntPtr dOccluded, int mode, bool root, bool endpoints, bool coherent,
+                                       IntPtr stream, IntPtr dStats)
+        {
+            Native.Check(Native.sr_occluded_rays_device(scene, mode | (root ? 0x100 : 0), n, dStarts, dDirs, dLimits, dOccluded,
+                                                        (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), stream, dStats));
         }
 
         /// ShadingMethod's colour step for n recorded intersections in DEVICE memory (sr_shade_points_device): dOut[i] = dColor[i] modulated with

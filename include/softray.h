@@ -585,6 +585,47 @@ int  sr_trace_origin_rays_device(sr_scene*, int32_t target, const double origin[
                                  int32_t* d_tri_index, uint32_t options, void* hip_stream,
                                  uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
+/* "Is anything in the way before distance L" for a batch of arbitrary rays: line of sight between two points, a texel's visibility from a
+ * light, a form factor, a probe of bounded length -- the question ShadowMethod.cs:169-172 asks (blocked = a hit with rayFrac <= 1.0 on a ray
+ * built as end - start) and AmbientOcclusion.cs asks with 2.0.
+ * Result: occluded[i] = 1 iff sr_trace_rays(scene, target, ...) answers the ray (starts[i], D_i) with hit == 1 and ray_frac <= limit_i, else
+ * 0; nothing else is ever written.  limit_i = limits[i], or 1.0 for every ray when `limits` is NULL.  The comparison is IEEE <=: a NaN limit
+ * gives 0, +inf means "any hit", a negative limit gives 0.
+ * Direction: D_i = dirs[i], not normalised; with SR_RAYS_ENDPOINTS (options bit 1) dirs[i] is an END POINT and D_i = dirs[i] - starts[i], one
+ * FP64 subtraction per component (ShadowMethod.cs:157) -- with the default limit that is "the segment is blocked".
+ * target: SR_MODE_* (the model alone) or SR_TARGET_ROOT | SR_MODE_* (extra geometry first, then the model); SR_TARGET_VOXELS is
+ * SR_ERR_UNSUPPORTED (a voxel hit has rayFrac 0).
+ * Why the walk may stop early: the nearest hit's rayFrac is the minimum over the ray's hits of fl(t + offset) (offset: the clip of the start
+ * to the root box; 0 for extra geometry and brute force).  min t <= L holds iff some t <= L does; fl(t + offset) is monotone in t; and
+ * Plane.IntersectRay never returns a negative t, so nothing behind the start can be nearer.  Hence "the nearest hit qualifies" iff "some hit
+ * qualifies", and on the own BVH (and in brute force) an any-hit walk that stops at the first qualifying hit, and culls every box beyond
+ * t = L - offset, gives exactly this answer.  SR_MODE_BVH does that (bvh_intersect<true>(.., limit_i)); SR_MODE_REF_TREE runs the literal walk
+ * and compares -- its leaf-face rule (the first leaf with a hit inside its box ends the walk) stays what it is -- and SR_MODE_BRUTE runs the
+ * nearest-hit loop and compares.
+ * Routing: a ray takes the any-hit walk only when its start is finite (max |s_k| <= 2^100), its limit is neither NaN nor -inf (+inf is
+ * allowed) and its direction is REGULAR by sr_trace_origin_rays' definition.  Every other ray -- a zero, NaN, +-inf, 1e300 or 1e-300
+ * direction, a non-finite start, a zero-length segment -- goes to the end of its pass and is answered by the function sr_trace_rays calls
+ * plus the comparison: equal by construction.
+ * Order: without SR_RAYS_COHERENT a pass of SR_MODE_BVH is ordered by the 7-bit Morton cell of the start in the root box, with the
+ * direction's octant between the coarse and the fine bits (a stable radix sort); with it the input order is kept, the irregular rays still
+ * last.  The other modes walk in input order.  Results never depend on the option or the order; speed does.
+ * Refusals, in this order: a NULL scene, n < 0, NULL starts / dirs / occluded with n > 0, unknown option bits: SR_ERR_INVALID_ARG;
+ * SR_TARGET_VOXELS: SR_ERR_UNSUPPORTED; sr_trace_rays' own checks (SR_ERR_NO_MODEL, SR_ERR_NOT_BUILT); a host-only scene: SR_ERR_NO_DEVICE.
+ * n == 0 that passes all of them: SR_OK, nothing is touched.
+ * State: the call rewrites no per-origin or per-light record of the scene, but it reads the triangle records a frame's set-up moves, so it
+ * is ordered like a frame: behind a frame of the scene in flight on any stream, the next frame behind it.  Passes of at most 2^22 rays
+ * (SR_DBG_BAND_SAMPLES: fewer) follow each other without the host waiting.  A multi-device scene runs the call on devices[0].  The host
+ * variant stages through the scene's device buffers, blocks and fills sr_last_ray_stats; the device variant enqueues on `hip_stream`
+ * without a host synchronisation.  Statistics: [0] = n; [1..3] in SR_MODE_REF_TREE / SR_MODE_BRUTE the sums of sr_trace_rays' per-ray
+ * counters, on the own BVH what the walks fetched (not pinned: an any-hit walk stops where it finds its hit); [4..] 0. */
+#define SR_RAYS_ENDPOINTS 2u      /* options bit 1; bit 0 is SR_RAYS_COHERENT */
+int  sr_occluded_rays(sr_scene*, int32_t target, int64_t n, const double* starts, const double* dirs,
+                      const double* limits /* [n], or NULL: 1.0 for every ray */, uint8_t* occluded,
+                      uint32_t options, uint64_t stats[4] /* or NULL */);
+int  sr_occluded_rays_device(sr_scene*, int32_t target, int64_t n, const double* d_starts, const double* d_dirs,
+                             const double* d_limits /* or NULL */, uint8_t* d_occluded, uint32_t options,
+                             void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* ShadingMethod.IntersectRay's colour step in batch (ShadingMethod.cs:36-68 -> CalcLighting :110-177): for n recorded
  * intersections out[i] = ModulatePackedColor(color[i], (byte)(255 * intensity)) with the frame's transform and lights (only the
  * matrices, position_z, fov_depth, lights, ambient, shininess and the POINT_LIGHT / SPECULAR flags of `frame` are read).
@@ -879,7 +920,7 @@ enum {
     SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
                                     per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) and the
                                     points per pass of sr_shadow_points and sr_static_shadow_points (default 2^22), of sr_ao_points (default and limit 2^17) and of sr_path_points (default and limit 2^22),
-                                    and the rays per pass of sr_trace_origin_rays (default and limit 2^22) */
+                                    and the rays per pass of sr_trace_origin_rays and of sr_occluded_rays (default and limit 2^22) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
     SR_DBG_SPLIT          = 3,   /* concurrent part-frame pipelines (default 2, <= 4)                                          */
@@ -898,7 +939,10 @@ enum {
                                     packet shaft walk instead of private per-lane shaft walks (same table; measured slower); 37 sr_shadow_points queues a pass in input
                                     order whatever the options say (no ray sort); 38 sr_shadow_points runs the first shaft round with private per-lane walks instead of the
                                     packet walk (both: same output); 44 sr_ao_points makes every pass's draw table on the host, one draw after the
-                                    other, and waits once per pass (same output; cross-check and baseline); 45 sr_path_points does the same, and then refuses first_sample + n > 2^30 with SR_ERR_UNSUPPORTED: the host draws its way to first_sample; 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    other, and waits once per pass (same output; cross-check and baseline); 45 sr_path_points does the same, and then refuses first_sample + n > 2^30 with SR_ERR_UNSUPPORTED: the host draws its way to first_sample; 46 sr_occluded_rays walks a pass in input
+                                    order whatever the options say (no ray sort); 47 sr_occluded_rays in SR_MODE_BVH answers every ray with a nearest-hit walk plus the
+                                    comparison instead of the any-hit walk (both: same output); 100 + T (T in 0..63) also makes the any-hit launch of sr_occluded_rays run on
+                                    persistent lanes that fetch new rays at T busy lanes (same output; faster on incoherent batches, slower on short coherent walks: DESIGN 5.28); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
                                     fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid

@@ -3105,6 +3105,97 @@ int sr_trace_origin_rays(sr_scene* m, int32_t target, const double origin[3], in
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Any-hit ray batches with a distance limit (sr_occluded_rays): sr_trace_rays' hit && ray_frac <= limit, with early exit on the own BVH
+// ------------------------------------------------------------------------------------------------------------------
+// what sr_occluded_rays[_device] refuses, in the header's order; `s`: the scene that runs the call (the first part of a multi-device scene)
+static int occluded_rays_check(sr_scene*& s, int32_t target, int64_t n, const void* starts, const void* dirs, const void* occluded, uint32_t options,
+                               int& mode, bool& with_extra) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_occluded_rays: the scene is NULL");
+    if (n < 0) return fail(SR_ERR_INVALID_ARG, "sr_occluded_rays: n is negative");
+    if (n > 0 && (!starts || !dirs || !occluded)) return fail(SR_ERR_INVALID_ARG, "sr_occluded_rays: starts, dirs and occluded must not be NULL when n > 0");
+    if (options & ~(uint32_t)(SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS))
+        return fail(SR_ERR_INVALID_ARG, "sr_occluded_rays: unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)");
+    if (target & SR_TARGET_VOXELS)
+        return fail(SR_ERR_UNSUPPORTED, "sr_occluded_rays: a hit on the voxel grid (SR_TARGET_VOXELS) has rayFrac 0, so a distance limit decides nothing; use sr_trace_rays");
+    with_extra = (target & SR_TARGET_ROOT) != 0;
+    mode = target & 0xff;
+    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "sr_occluded_rays: the scene has no model (sr_set_triangles, sr_load_3ds)");
+    int rc;
+    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays */ }
+    else if ((rc = check_mode(s, mode))) return rc;
+    if (s->device < 0) return fail(SR_ERR_NO_DEVICE, "sr_occluded_rays: a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
+    return SR_OK;
+}
+
+// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set's sort buffers
+static int occluded_rays_common(sr_scene* s, int mode, bool with_extra, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits,
+                                uint8_t* d_occluded, uint32_t options, hipStream_t stream, unsigned long long* d_stats) {
+    int rc = sync_geometry(s, (uint32_t)mode);
+    if (rc) return rc;
+    // ---- ordered like a frame (render_common): a frame's facing partition moves the records the walk reads ----
+    StreamOrder order(s, stream);
+    if (order.entered) return order.entered;
+    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
+    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kOcclMaxPass) : sr::kOcclMaxPass;
+    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
+    sr::OccludedLaunch L{};
+    L.sc = dev_scene(s);
+    L.mode = mode;
+    L.with_extra = with_extra && !s->extra_recs.empty();
+    L.n = n; L.pass = pass;
+    L.starts = d_starts; L.dirs = d_dirs; L.limits = d_limits; L.occluded = d_occluded;
+    L.endpoints = (options & SR_RAYS_ENDPOINTS) != 0;
+    L.input_order = (options & SR_RAYS_COHERENT) != 0 || s->dbg[SR_DBG_KERNEL_SWITCH] == 46;    // (hook: input order whatever the options say)
+    L.nearest_walks = s->dbg[SR_DBG_KERNEL_SWITCH] == 47;                                       // (hook: nearest-hit walks plus the comparison)
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
+    L.refill_at = (hook >= 100 && hook <= 163) ? (int)(hook - 100) : -1;                       // (hook: persistent lanes, refilled at T busy ones)
+    if (mode == SR_MODE_BVH) {
+        if ((rc = ensure_num_cus(s))) return rc;
+        L.persistent_blocks = s->num_cus * 4;
+        sr_scene::BandScratch& B = s->scratch[0];
+        const size_t slots = (size_t)(pass + 255) / 256 * 256;
+        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
+        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
+        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
+        L.sort_buf = (unsigned int*)B.ray_sort.p;
+        L.sort_temp = B.ray_sort_temp.p;
+    }
+    L.stats = d_stats;
+    L.stream = stream;
+    L.user = s;
+    L.get_events = timing_events;
+    SR_HIP(sr::launch_occluded(L));
+    return SR_OK;
+}
+
+int sr_occluded_rays_device(sr_scene* m, int32_t target, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits, uint8_t* d_occluded,
+                            uint32_t options, void* hip_stream, uint64_t* d_stats) {
+    sr_scene* s = m;
+    int mode; bool with_extra;
+    int rc = occluded_rays_check(s, target, n, d_starts, d_dirs, d_occluded, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    return occluded_rays_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, d_occluded, options, stream, (unsigned long long*)d_stats);
+}
+
+int sr_occluded_rays(sr_scene* m, int32_t target, int64_t n, const double* starts, const double* dirs, const double* limits, uint8_t* occluded,
+                     uint32_t options, uint64_t stats[4]) {
+    sr_scene* s = m;
+    int mode; bool with_extra;
+    int rc = occluded_rays_check(s, target, n, starts, dirs, occluded, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    Staged io[] = {{starts, nullptr, (size_t)n * 24}, {dirs, nullptr, (size_t)n * 24}, {limits, nullptr, (size_t)n * 8}, {nullptr, occluded, (size_t)n}};
+    return run_staged(m, s, io, 4, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
+        return occluded_rays_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev, (uint8_t*)io[3].dev,
+                                    options, stream, d_stats);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The RCCL strip gather, native: no PyTorch in the data path.
 // ------------------------------------------------------------------------------------------------------------------
 int sr_set_gather(sr_scene* m, int32_t kind) {

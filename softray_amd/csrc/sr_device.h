@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_COUNT = 44 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_COUNT = 46 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -383,6 +383,40 @@ hipError_t point_order(const void* recs, unsigned int n, bool sorted, const Root
 // returns the sorted keys: point_order_skip_mask(sorted) is their bit that marks an irregular ray.  Scratch as point_order's
 hipError_t dir_order(const double* dirs, unsigned int n, bool sorted, unsigned int* keys, unsigned int* keys2, unsigned int* idx, unsigned int* order_out,
                      void* temp, size_t temp_bytes, hipStream_t stream);
+
+// sr_occluded_rays: the order of a pass of n arbitrary rays (starts, dirs: [n][3]; limits: [n] or nullptr = 1.0; endpoints: the direction is
+// dirs - starts).  A ray is REGULAR when its start is finite (max |s_k| <= 2^100), its limit is neither NaN nor -inf and its direction is
+// regular by dir_order's definition.  order_out: the regular rays first -- sorted: by ray_sort's key of (start, direction), ties in input
+// order; !sorted: in input order -- then the others in input order.  A stable sort; keys2 returns the sorted keys:
+// point_order_skip_mask(sorted) is their bit that marks an irregular ray.  Scratch as point_order's
+hipError_t occl_order(const double* starts, const double* dirs, const double* limits, unsigned int n, bool endpoints, bool sorted, const RootBox& root,
+                      unsigned int* keys, unsigned int* keys2, unsigned int* idx, unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
+
+// sr_occluded_rays (sr_occluded.hip): occluded[i] = sr_trace_rays' hit && ray_frac <= limit for n caller-given rays, in passes of `pass` rays
+constexpr int64_t kOcclMaxPass = 1ll << 22;
+struct OccludedLaunch {
+    DevScene    sc;
+    int32_t     mode;           // SR_MODE_*
+    bool        with_extra;     // root geometry of the chain (extra + model)
+    int64_t     n, pass;
+    const double* starts;       // device [n][3]
+    const double* dirs;         // device [n][3]: directions, or end points (endpoints)
+    const double* limits;       // device [n] or nullptr (every ray 1.0)
+    uint8_t*    occluded;       // device [n]
+    bool        endpoints;      // SR_RAYS_ENDPOINTS
+    bool        input_order;    // SR_RAYS_COHERENT / hook 46: a pass keeps its input order (the irregular rays still go last)
+    bool        nearest_walks;  // SR_MODE_BVH with nearest-hit walks plus the comparison for every ray (hook 47)
+    int         refill_at;      // >= 0 (hook 100 + T): the any-hit launch with persistent lanes that fetch new rays at T busy lanes; < 0: one lane per ray
+    int32_t     persistent_blocks;
+    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words, and one more for the refill form's work head (SR_MODE_BVH)
+    void*       sort_temp;
+    size_t      sort_temp_bytes; // point_order_temp_bytes
+    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += rays, [1..3] += what their walks count
+    hipStream_t stream;
+    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
+    void*       user;
+};
+hipError_t launch_occluded(const OccludedLaunch& L);
 
 // the four-wide tree collapsed from a device-resident binary tree (same rule as the host's collapse_bvh4); d_wide: >= num_nodes entries
 // level_first (nullable): the wide nodes are numbered level by level -- level L is [level_first[L], level_first[L + 1]), the last entry

@@ -180,6 +180,8 @@ const char* kernel_name(int id) {
         case K_TIGHT_BOXES: return "k_tight_boxes";           // the ordered copies' boxes fitted to their live records: k_tight_level per level + k_tight_top, per copy
         case K_ORIGIN_RAYS: return "k_origin_rays";           // sr_trace_origin_rays: a pass's walks (the packet launch + the per-lane one for its irregular rays)
         case K_ORIGIN_SORT: return "k_origin_sort";           // ... its order: k_dir_keys + the radix sort
+        case K_OCCLUDED: return "k_occluded";                 // sr_occluded_rays: a pass's walks (the any-hit launch + the nearest-hit one for its irregular rays)
+        case K_OCCL_SORT: return "k_occl_sort";               // ... its order: k_occl_keys + the radix sort
         case K_VOXEL_WALK: return "k_voxel_walk";
         case K_VOXELISE: return "voxelise";                   // count, scan, emit, sort, per-cell sums of one sr_build_voxels
         case K_SHAFT2: return "k_shaft_round2";

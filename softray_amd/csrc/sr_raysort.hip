@@ -101,7 +101,52 @@ __global__ __launch_bounds__(256) void k_dir_keys(const double* __restrict__ dir
     idx[i] = i;
 }
 
+// sr_occluded_rays: arbitrary rays as three arrays (starts, dirs or end points, limits).  Key = k_ray_keys' key of (start, direction): the
+// 7-bit Morton cell of the start in the root box with the direction's octant between the coarse and the fine bits.  Bit kPointSkipBit (sorted)
+// / bit 0 (!sorted) marks an IRREGULAR ray -- a start that is not finite or beyond 2^100, a limit that is NaN or -inf, a direction that is
+// irregular by k_dir_keys' rule (a zero-length segment among them) -- which the any-hit walk never sees: the stable sort leaves those at the
+// end of the pass, in input order.
+__global__ __launch_bounds__(256) void k_occl_keys(const double* __restrict__ starts, const double* __restrict__ dirs, const double* __restrict__ limits,
+                                                   unsigned int n, int endpoints, int sorted, double lx, double ly, double lz, double sx, double sy, double sz,
+                                                   unsigned int* __restrict__ keys, unsigned int* __restrict__ idx) {
+    const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const double px = starts[(size_t)i * 3], py = starts[(size_t)i * 3 + 1], pz = starts[(size_t)i * 3 + 2];
+    double dx = dirs[(size_t)i * 3], dy = dirs[(size_t)i * 3 + 1], dz = dirs[(size_t)i * 3 + 2];
+    if (endpoints) { dx = dx - px; dy = dy - py; dz = dz - pz; }                    // the subtraction k_occluded does
+    const double lim = limits ? limits[i] : 1.0;
+    const double ax = fabs(dx), ay = fabs(dy), az = fabs(dz);
+    const double m = fmax(fmax(ax, ay), az);
+    // (a NaN component fails the comparison with itself, an infinite one the upper bound; a NaN limit fails lim >= -DBL_MAX, and so does -inf)
+    const bool dir_ok = ax == ax && ay == ay && az == az && m >= 0x1p-40 && m <= 0x1p40;
+    const bool start_ok = fabs(px) <= 0x1p100 && fabs(py) <= 0x1p100 && fabs(pz) <= 0x1p100;
+    const bool regular = dir_ok && start_ok && lim >= -1.7976931348623157e308;
+    unsigned int key = 0u;
+    if (regular && sorted) {
+        const int cx = (int)fmin(127.0, fmax(0.0, (px - lx) * sx)), cy = (int)fmin(127.0, fmax(0.0, (py - ly) * sy)), cz = (int)fmin(127.0, fmax(0.0, (pz - lz) * sz));
+        const unsigned int oct = (dx < 0.0 ? 1u : 0u) | (dy < 0.0 ? 2u : 0u) | (dz < 0.0 ? 4u : 0u);
+        const unsigned int mort = (spread7((unsigned)cx) << 2) | (spread7((unsigned)cy) << 1) | spread7((unsigned)cz);
+        key = ((mort >> 6) << 9) | (oct << 6) | (mort & 63u);
+    }
+    if (!regular) key = sorted ? (1u << kPointSkipBit) : 1u;
+    keys[i] = key;
+    idx[i] = i;
+}
+
 }  // namespace
+
+hipError_t occl_order(const double* starts, const double* dirs, const double* limits, unsigned int n, bool endpoints, bool sorted, const RootBox& root,
+                      unsigned int* keys, unsigned int* keys2, unsigned int* idx, unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    double s[3];
+    for (int a = 0; a < 3; ++a) { const double e = root.max[a] - root.min[a]; s[a] = e > 0 ? 128.0 / e : 0.0; }
+    hipLaunchKernelGGL(k_occl_keys, dim3((n + 255u) / 256u), dim3(256), 0, stream, starts, dirs, limits, n, endpoints ? 1 : 0, sorted ? 1 : 0, root.min[0], root.min[1],
+                       root.min[2], s[0], s[1], s[2], keys, idx);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const unsigned int*)keys, keys2, (const unsigned int*)idx, order_out, (int)n, 0,
+                                              sorted ? kPointSkipBit + 1 : 1, stream);
+}
 
 hipError_t dir_order(const double* dirs, unsigned int n, bool sorted, unsigned int* keys, unsigned int* keys2, unsigned int* idx, unsigned int* order_out,
                      void* temp, size_t temp_bytes, hipStream_t stream) {

@@ -485,6 +485,19 @@ public:
         const double o[3] = {origin.x, origin.y, origin.z};
         sr_check(sr_trace_origin_rays(scene_, SR_TARGET_ROOT | Mode(), o, n, dirs, hit, ray_frac, pos, normal, color, tri_index, coherent ? SR_RAYS_COHERENT : 0u, nullptr));
     }
+    // "Is anything in the way before distance L" for n rays of the caller's (sr_occluded_rays): occluded[i] = 1 iff IntersectRay(starts[i], D_i) on
+    // the root geometry of the chain hits with rayFrac <= limits[i] (limits == nullptr: 1.0 for every ray), else 0 -- the test of ShadowMethod.cs:
+    // 169-172, with early exit on the own BVH.  D_i = dirs[i], or with endpoints dirs[i] - starts[i] (dirs holds end points: "the segment is
+    // blocked").  coherent: the rays are walked in the order given (SR_RAYS_COHERENT).  Does nothing without a model
+    void OccludedRays(int64_t n, const double* starts, const double* dirs, const double* limits, uint8_t* occluded, bool endpoints = false, bool coherent = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel()) return;
+        PreCalculate();                                    // the model and the tree of Mode() are in the scene
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_check(sr_occluded_rays(scene_, SR_TARGET_ROOT | Mode(), n, starts, dirs, limits, occluded,
+                                  (endpoints ? SR_RAYS_ENDPOINTS : 0u) | (coherent ? SR_RAYS_COHERENT : 0u), nullptr));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

@@ -567,6 +567,34 @@ class GpuScene:
                                                       _vp(d_normal), _vp(d_color), _vp(d_tri_index), _lib.RAYS_COHERENT if coherent else 0, _stream(stream),
                                                       _vp(d_stats_ptr)))
 
+    # ---- any-hit ray batches with a distance limit (sr_occluded_rays) ----
+    @staticmethod
+    def _ray_options(endpoints, coherent):
+        return (_lib.RAYS_ENDPOINTS if endpoints else 0) | (_lib.RAYS_COHERENT if coherent else 0)
+
+    def occluded(self, target, starts, dirs, limits=None, endpoints=False, coherent=False, stats=False):
+        """uint8 [n]: trace(target, starts, D) answers hit and ray_frac <= limit (limits None: 1.0 for every ray), with early exit on the own
+        BVH.  D = dirs, or dirs - starts with endpoints=True (dirs are end points).  stats=True: (occluded, the four counters)."""
+        starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = starts.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("dirs has %d entries for %d rays" % (dirs.shape[0], n))
+        if limits is not None:
+            limits = np.ascontiguousarray(limits, dtype=np.float64).reshape(-1)
+            if limits.size != n:
+                raise ValueError("limits has %d entries for %d rays" % (limits.size, n))
+        out = np.zeros(n, dtype=np.uint8)
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        _check(_lib.lib().sr_occluded_rays(self._h, int(target), n, _p(starts), _p(dirs), _p(limits), _p(out), self._ray_options(endpoints, coherent), _p(st)))
+        return (out, st) if stats else out
+
+    def occluded_device(self, target, n, d_starts, d_dirs, d_limits=0, d_occluded=0, endpoints=False, coherent=False, stream=0, d_stats_ptr=None):
+        """sr_occluded_rays_device: every array is a DEVICE pointer (d_limits 0 / None: 1.0 for every ray); enqueued on `stream` (a raw
+        hipStream_t or a torch.cuda.Stream), no host sync."""
+        _check(_lib.lib().sr_occluded_rays_device(self._h, int(target), int(n), _vp(d_starts), _vp(d_dirs), _vp(d_limits), _vp(d_occluded),
+                                                  self._ray_options(endpoints, coherent), _stream(stream), _vp(d_stats_ptr)))
+
     # ---- the strip gather over RCCL (include/softray.h) ----
     def set_gather(self, kind):
         """Multi-device scene: _lib.GATHER_COPY (peer copies, default) or _lib.GATHER_RCCL (grouped ncclSend / ncclRecv)."""

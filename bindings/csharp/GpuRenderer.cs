@@ -102,6 +102,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_light_field_coords(IntPtr scene, long n, [In] double[] starts, [In] double[] dirs, [Out] double[] coords, [Out] byte[] inside);
         [DllImport(Lib)] public static extern int sr_get_light_field(IntPtr scene, [Out] uint[] entries, ulong first, ulong count);
         [DllImport(Lib)] public static extern int sr_set_light_field(IntPtr scene, [In] uint[] entries, ulong first, ulong count);
+        [DllImport(Lib)] public static extern int sr_light_field_rays(IntPtr scene, ref SrFrame frame, long n, [In] double[] starts, [In] double[] dirs, [Out] uint[] result, [Out] byte[] inside, uint options, out ulong filled);
+        [DllImport(Lib)] public static extern int sr_light_field_rays_device(IntPtr scene, ref SrFrame frame, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dOut, IntPtr dInside, uint options, IntPtr hipStream, IntPtr dFilled, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_bake_light_field(IntPtr scene, ref SrFrame frame, ulong first, ulong count, out ulong filled);
         [DllImport(Lib)] public static extern int sr_shadow_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, uint options);
         [DllImport(Lib)] public static extern int sr_static_shadow_points(IntPtr scene, ref SrFrame frame, long n, [In] double[] pos, [In] double[] normal, [In] uint[] color, [Out] uint[] result, [Out] byte[] amount, uint options, out ulong generators);
@@ -400,6 +402,37 @@ namespace Engine3D.Hip
             ulong filled;
             Native.Check(Native.sr_bake_light_field(scene, ref frame, first, count, out filled));
             return filled;
+        }
+
+        /// The colour light field for caller-given lines (sr_light_field_rays; LightFieldColorMethod.IntersectRay): result[i] = the colour a
+        /// F_LIGHT_FIELD frame gives a camera sample whose ray is (starts[i], dirs[i]) -- double[n * 3] in model space, the direction not
+        /// normalised -- for the frame these arguments describe (the same as Render's; F_LIGHT_FIELD is implied, the surface size is validated and
+        /// otherwise unused).  Empty entries of the scene's table are filled first, as a frame fills them: `filled` receives their number.
+        /// inside (byte[n] or null): 1 where the line pierces the sphere; a line that misses it gets the background.  The triangle light field
+        /// and what a light-field frame refuses: SR_ERR_UNSUPPORTED -> InvalidOperationException.  Blocks.
+        public uint[] LightFieldRays(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint backgroundColor, uint flags,
+                                     int mode, int randomSeed, double fieldOfViewDepth, double ambient, double shininess, Vector lightDirView,
+                                     Vector lightPosView, double[] starts, double[] dirs, out ulong filled, byte[] inside = null)
+        {
+            if (starts == null || dirs == null || starts.Length != dirs.Length || starts.Length % 3 != 0 || (inside != null && inside.Length != starts.Length / 3))
+                throw new ArgumentException("LightFieldRays: starts and dirs are double[n * 3], inside is byte[n] or null");
+            FillFrame(width, height, instance, transform, inverseTransform, backgroundColor, flags, mode, 0, height - 1, 1, randomSeed,
+                      fieldOfViewDepth, 1.0, 0.0, ambient, shininess, lightDirView, lightPosView, 4);
+            var result = new uint[starts.Length / 3];
+            Native.Check(Native.sr_light_field_rays(scene, ref frame, result.Length, starts, dirs, result, inside, 0, out filled));
+            return result;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_light_field_rays_device): enqueued on `stream` without a host
+        /// synchronisation; dInside and dFilled (a ulong on the device) may be IntPtr.Zero; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void LightFieldRaysDevice(int width, int height, Instance instance, Matrix transform, Matrix inverseTransform, uint backgroundColor, uint flags,
+                                         int mode, int randomSeed, double fieldOfViewDepth, double ambient, double shininess, Vector lightDirView,
+                                         Vector lightPosView, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dOut, IntPtr dInside, IntPtr stream,
+                                         IntPtr dFilled, IntPtr dStats)
+        {
+            FillFrame(width, height, instance, transform, inverseTransform, backgroundColor, flags, mode, 0, height - 1, 1, randomSeed,
+                      fieldOfViewDepth, 1.0, 0.0, ambient, shininess, lightDirView, lightPosView, 4);
+            Native.Check(Native.sr_light_field_rays_device(scene, ref frame, n, dStarts, dDirs, dOut, dInside, 0, stream, dFilled, dStats));
         }
 
         /// sr_shadow_points' option bit 0: 64 consecutive points are neighbours, a pass is queued in the order given (no ray sort)

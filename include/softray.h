@@ -513,6 +513,34 @@ int  sr_set_light_field_tris(sr_scene*, const uint32_t* in, uint64_t first, uint
  * frame kernels call, so a caller can reproduce such a frame exactly from these coordinates (the device's atan2 / asin differ from a host's by
  * ulps).  Bad arguments: SR_ERR_INVALID_ARG, before the device is looked at; a host-only scene then returns SR_ERR_NO_DEVICE.  n == 0: SR_OK. */
 int  sr_light_field_coords(sr_scene*, int64_t n, const double* starts, const double* dirs, double* coords /* [n][4] */, uint8_t* inside /* [n] */);
+/* LightFieldColorMethod.IntersectRay in batch (LightFieldColorMethod.cs:92-217): the colour light field for n lines of the caller's -- a panorama, a
+ * cube-map face, a fisheye, the second rays of a pipeline -- where SR_F_LIGHT_FIELD serves the pinhole camera of a frame.  starts[i], dirs[i]: [n][3]
+ * in model space, the direction not normalised (sr_trace_rays' and sr_light_field_coords' conventions).  out[i] is the colour a light-field frame
+ * gives a camera sample whose ray is (starts[i], dirs[i]): the sphere test, the cell and the entry exactly as SR_F_LIGHT_FIELD defines them; a line
+ * with term < 1e-10 gets frame->background_argb | 0xFF000000.  inside[i] (optional) = 1 when the line pierces the sphere, else 0.
+ * An empty entry is filled first with what a frame would store for the cell: the canonical ray through `frame`'s root geometry in
+ * frame->trace_mode, shaded with SR_F_SHADING, through the dynamic shadow stage when the scene has sr_set_light_field_shadows on and the frame
+ * carries SR_F_SHADOWS -- in the scene's table, the one frames and sr_bake_light_field use, so a batch split over several calls equals the one
+ * call bit for bit and a batch may follow or precede frames.  *filled = the entries written, as the bake counts them (N = 1: its one cell, whose
+ * canonical ray is NaN, stores the background).  With sr_set_light_field_interpolation on, out[i] is the quad-linear blend of the 16 neighbours
+ * as an interpolating frame computes it; empty neighbours are filled first.
+ * SR_F_LIGHT_FIELD is implied; the camera fields of `frame` are validated as for a frame and otherwise unused.
+ * Refused, in this order: n < 0, a NULL starts / dirs / out with n > 0, a NULL frame or scene, options != 0 (reserved): SR_ERR_INVALID_ARG;
+ * sr_set_light_field_triangles on (LightFieldTriMethod's three stages per ray are not part of this): SR_ERR_UNSUPPORTED; the switches a light-field
+ * frame refuses -- SR_F_AMBIENT_OCCLUSION, SR_F_PATH_TRACING, SR_F_VOXELS, SR_F_SINGLE_KERNEL -- and max_bounces > 0, strip_count > 0:
+ * SR_ERR_UNSUPPORTED; then sr_render's validation of the frame (shadows without the scene's switch, static shadows) and of its trace mode
+ * (SR_ERR_NOT_BUILT ...); then a host-only scene: SR_ERR_NO_DEVICE.  n == 0 that passes these checks: SR_OK, nothing is touched, *filled = 0.
+ * Ordered like a frame (behind a frame of the scene in flight on any stream, the next frame behind it), in passes of at most 2^22 rays (1/16 of
+ * that with interpolation and shadows together, as the frame's bands; SR_DBG_BAND_SAMPLES makes them smaller) that follow each other without the
+ * host waiting; a later pass reads what an earlier one filled.  A multi-device scene runs it on devices[0].  The host variant blocks and leaves
+ * the statistics in sr_last_ray_stats: [0] n, [1..3] 0, [4] canonical rays traced (none for a NaN ray), [5..7] their walks, [4..] also the
+ * shadow stage's counts when shadowed; [4..] are 0 with SR_F_PRIMARY_STATS_ONLY.  The device variant takes device arrays, enqueues on `hip_stream`
+ * without a host synchronisation and writes *d_filled and d_stats when given. */
+int  sr_light_field_rays(sr_scene*, const sr_frame* frame, int64_t n, const double* starts, const double* dirs, uint32_t* out,
+                         uint8_t* inside /* or NULL */, uint32_t options, uint64_t* filled /* or NULL */);
+int  sr_light_field_rays_device(sr_scene*, const sr_frame* frame, int64_t n, const double* d_starts, const double* d_dirs, uint32_t* d_out,
+                                uint8_t* d_inside /* or NULL */, uint32_t options, void* hip_stream, uint64_t* d_filled /* or NULL */,
+                                uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 /* Same, but `d_pixels` is DEVICE memory on the scene's device (e.g. a torch tensor's data_ptr) and the
  * work is enqueued on `hip_stream` (a hipStream_t; NULL = the null stream) without host sync. */
 /* Ordering: the work is enqueued behind everything already on `hip_stream` and `hip_stream` continues only after it; a
@@ -920,7 +948,8 @@ enum {
     SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
                                     per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) and the
                                     points per pass of sr_shadow_points and sr_static_shadow_points (default 2^22), of sr_ao_points (default and limit 2^17) and of sr_path_points (default and limit 2^22),
-                                    and the rays per pass of sr_trace_origin_rays and of sr_occluded_rays (default and limit 2^22) */
+                                    and the rays per pass of sr_trace_origin_rays, of sr_occluded_rays and of sr_light_field_rays (default and limit 2^22;
+                                    sr_light_field_rays with interpolation and shadows together: 1/16 of the value, as a frame's bands) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
     SR_DBG_SPLIT          = 3,   /* concurrent part-frame pipelines (default 2, <= 4)                                          */

@@ -787,6 +787,9 @@ struct HitsReq { sr::HitsOut out; };
 // sr_trace_origin_rays: the same set-up for `origin` in the camera's place (the frame `f` is a stand-in: one pixel, no decorator), then passes of
 // the caller's directions through k_origin_rays into the caller's device arrays.  with_extra: the root geometry (SR_TARGET_ROOT)
 struct OriginReq { double origin[3]; int64_t n; const double* dirs; sr::HitsOut out; bool coherent; bool with_extra; };
+// sr_light_field_rays: a light-field frame's set-up (the table, the patch centres, with shadows the shadow stage's records and scratch), then
+// passes of the caller's rays through the fused lookup, the frame's fill stage and the finish kernel (device arrays)
+struct LfRaysReq { int64_t n; const double* starts; const double* dirs; uint32_t* out; uint8_t* inside; unsigned long long* filled; };
 
 // points per pass of sr_shadow_points: the bake's rule (SR_DBG_BAND_SAMPLES shrinks the pass)
 const long long kPtsPassPoints = 1ll << 22;
@@ -799,11 +802,13 @@ struct RenderAsk {
     const PtsReq* pts = nullptr;
     const HitsReq* hreq = nullptr;
     const OriginReq* org = nullptr;
+    const LfRaysReq* lfr = nullptr;
     RenderAsk() {}
     RenderAsk(const LfBakeReq* r) : bake(r) {}
     RenderAsk(const PtsReq* r) : pts(r) {}
     RenderAsk(const HitsReq* r) : hreq(r) {}
     RenderAsk(const OriginReq* r) : org(r) {}
+    RenderAsk(const LfRaysReq* r) : lfr(r) {}
     static RenderAsk phase(int p) { RenderAsk a; a.pt_phase = p; return a; }
 };
 
@@ -813,6 +818,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     const PtsReq* const pts = ask.pts;
     const HitsReq* const hreq = ask.hreq;
     const OriginReq* const org = ask.org;
+    const LfRaysReq* const lfr = ask.lfr;
     for (uint32_t& c : s->dbg_frame) c = 0;
     sr::FrameConst fc;
     int rc = check_path_tracing(f);                                 // (sr_rccl_render makes strips of its own after validate_frame)
@@ -829,7 +835,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     const bool lft = s->lf_tris && (f->flags & SR_F_LIGHT_FIELD) && !bake && !pts;
     if (lft && (rc = sync_geometry(s, SR_MODE_REF_TREE))) return rc;
     if (voxels && (rc = ensure_voxels(s, stream))) return rc;
-    if (fc.num_rows == 0 && !bake && !pts && !org) return SR_OK;
+    if (fc.num_rows == 0 && !bake && !pts && !org && !lfr) return SR_OK;
     // ---- frames of one scene run in submission order whatever streams they are given ----
     StreamOrder order(s, stream);
     if (order.entered) return order.entered;
@@ -1163,10 +1169,18 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
     long long band_rows = std::max<long long>(16, (budget / (wpad * n2)) / 16 * 16);
     band_rows = std::min<long long>(band_rows, ((long long)rows_half + 15) / 16 * 16);
     long long band_samples = band_rows * wpad * n2;
+    long long lfr_pass = 0;
+    if (lfr) {
+        // a pass of rays in a band's place: at most kPtsPassPoints (SR_DBG_BAND_SAMPLES: fewer), 1/16 of that where a band shrinks, no more than the call has
+        const long long want = (s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<long long>(s->dbg[SR_DBG_BAND_SAMPLES], kPtsPassPoints) : kPtsPassPoints) / ((lf_interp && shadows) ? 16 : 1);
+        lfr_pass = std::max<long long>(1, std::min<long long>(want, lfr->n));
+        band_samples = (lfr_pass + 255) / 256 * 256;                    // (the scratch in whole workgroups)
+    }
     const long long lf_band_samples = band_samples;                     // per-sample scratch of a light-field band
     const long long lf_list_cells = lf_interp ? std::min<long long>(16 * band_samples, (long long)lf_entries(s->lf_res)) : band_samples;
     if (lf_interp && shadows) band_samples = std::max(band_samples, lf_list_cells);      // the queue, the staging buffer and the stage's lists: one slot per listed cell
-    const bool lf_carry = lf_interp && s->dbg[SR_DBG_KERNEL_SWITCH] != 39;               // (hook 39: the apply kernel computes base cell and fractions again; same frame)
+    // (sr_light_field_rays: its finish kernel computes them again from the ray)
+    const bool lf_carry = lf_interp && !lfr && s->dbg[SR_DBG_KERNEL_SWITCH] != 39;               // (hook 39: the apply kernel computes base cell and fractions again; same frame)
     if (bake) {
         // a bake pass: whole origin patches (2 N^2 cells each), at most kBakeShadowPassCells cells (SR_DBG_BAND_SAMPLES shrinks the pass), at least one patch
         const long long per_origin = 2ll * s->lf_res * s->lf_res;
@@ -1256,7 +1270,11 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         B.used_last_frame = true;
         if (shadows || bounce_pipe || path || ao) SR_HIP(B.hits.reserve((size_t)band_samples * sr::pipeline_hit_record_bytes()));
         if (ao) SR_HIP(B.ao_escapes.reserve((size_t)band_samples * 4));
-        if (lf && !bake) {
+        if (lfr) {
+            // the pending list: its length, then (ray, cell) per ray that met an empty entry (interpolating: the ray alone)
+            SR_HIP(B.lf_cells.reserve(((size_t)lf_band_samples * 2 + 2) * 4));
+            SR_HIP(B.lf_list.reserve((size_t)lf_list_cells * 4));
+        } else if (lf && !bake) {
             if (!lf_interp || lf_carry) SR_HIP(B.lf_cells.reserve((size_t)lf_band_samples * 4));
             if (lf_carry) SR_HIP(B.lf_fracs.reserve((size_t)lf_band_samples * 32));
             SR_HIP(B.lf_list.reserve((size_t)lf_list_cells * 4));
@@ -1331,7 +1349,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
                 if (r > 0) SR_HIP(B.rstate[r].reserve((size_t)round_items[r] * sr::pipeline_round_state_bytes()));
             }
         }
-        if (n2 > 1 && !bake && !hreq) SR_HIP(B.samples.reserve((size_t)(lf ? lf_band_samples : band_samples) * 4));
+        if (n2 > 1 && !bake && !hreq && !lfr) SR_HIP(B.samples.reserve((size_t)(lf ? lf_band_samples : band_samples) * 4));
         bool accum_fresh = false;
         if (chunked_shadows) {
             // indexed like the sample buffer: the frame (or the compact strips) for one sample per pixel, band-local otherwise (a light field's
@@ -1410,6 +1428,11 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             }
         }
         if (hreq) { P.hits_req = true; P.hits_out = hreq->out; }
+        if (lfr) {
+            P.lfr_n = lfr->n; P.lfr_pass = lfr_pass;
+            P.lfr_starts = lfr->starts; P.lfr_dirs = lfr->dirs; P.lfr_out = lfr->out; P.lfr_inside = lfr->inside;
+            P.lfr_filled = lfr->filled;
+        }
         if (org) {
             P.org_n = org->n; P.org_pass = org_pass;
             P.org_dirs = org->dirs; P.hits_out = org->out;
@@ -1502,7 +1525,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
         };
         if (accum_fresh) SR_HIP(hipMemsetAsync(B.accum.p, 0, B.accum.cap, bs));
         if (hints_fresh) for (DBuf& hb : B.tile_hint) SR_HIP(hipMemsetAsync(hb.p, 0xFF, hb.cap, bs));
-        if (P.row_first < P.row_limit || bake || pts || org) {
+        if (P.row_first < P.row_limit || bake || pts || org || lfr) {
             const hipError_t pe = sr::launch_pipeline(P);
             if (pe == hipErrorNotSupported && s->ao_table_rc) return s->ao_table_rc;      // (the message is the callback's)
             SR_HIP(pe);
@@ -3398,6 +3421,60 @@ int sr_render_hits(sr_scene* m, const sr_frame* f, double* starts, double* dirs,
                            (uint32_t*)io[6].dev, (int32_t*)io[7].dev}};
         return render_common(s, &fs, nullptr, stream, d_stats, &req);
     });
+}
+
+// ---- sr_light_field_rays ----
+// `fs`: the frame with SR_F_LIGHT_FIELD implied.  (Shadows are validate_frame's to refuse: the scene's switch decides)
+static const BatchCall kLightFieldRaysCall = {
+    "bad argument to sr_light_field_rays",
+    {{SR_F_AMBIENT_OCCLUSION, "sr_light_field_rays: ambient occlusion (SR_F_AMBIENT_OCCLUSION) needs a surface point per ray; a cell stores a colour"},
+     {SR_F_PATH_TRACING, "sr_light_field_rays: path tracing (SR_F_PATH_TRACING) needs a surface point per ray; a cell stores a colour"},
+     {SR_F_VOXELS, "sr_light_field_rays: voxel rendering (SR_F_VOXELS) replaces the root geometry the canonical rays are traced through"},
+     {SR_F_SINGLE_KERNEL, "sr_light_field_rays: the light field is not built into the one-kernel renderer (SR_F_SINGLE_KERNEL)"}},
+    "sr_light_field_rays: mirror bounces (max_bounces > 0) need a surface point per ray; a cell stores a colour",
+    "sr_light_field_rays: row strips (strip_count > 0) divide a frame's rows, not a batch of rays",
+    SR_F_LIGHT_FIELD, false};
+static int light_field_rays_check(sr_scene*& s, const sr_frame* f, int64_t n, const void* starts, const void* dirs, const void* out, uint32_t options, sr_frame& fs) {
+    const bool args_ok = n >= 0 && (n == 0 || (starts && dirs && out)) && options == 0u;
+    sr_scene* q = (s && !s->parts.empty()) ? s->parts[0] : s;
+    if (q && f && args_ok && q->lf_tris)
+        return fail(SR_ERR_UNSUPPORTED, "sr_light_field_rays: the triangle light field (sr_set_light_field_triangles) runs LightFieldTriMethod's three stages per ray, which is not part of this call");
+    return batch_call_check(kLightFieldRaysCall, s, f, args_ok, fs);
+}
+
+int sr_light_field_rays_device(sr_scene* m, const sr_frame* f, int64_t n, const double* d_starts, const double* d_dirs, uint32_t* d_out, uint8_t* d_inside,
+                               uint32_t options, void* hip_stream, uint64_t* d_filled, uint64_t* d_stats) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = light_field_rays_check(s, f, n, d_starts, d_dirs, d_out, options, fs);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n == 0) return zero_generators_device(s, d_filled, stream);
+    if ((rc = use_device(s))) return rc;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    if (d_filled) SR_HIP(hipMemsetAsync(d_filled, 0, sizeof(uint64_t), stream));
+    const LfRaysReq req{n, d_starts, d_dirs, d_out, d_inside, (unsigned long long*)d_filled};
+    return render_common(s, &fs, nullptr, stream, (unsigned long long*)d_stats, &req);
+}
+
+int sr_light_field_rays(sr_scene* m, const sr_frame* f, int64_t n, const double* starts, const double* dirs, uint32_t* out, uint8_t* inside, uint32_t options,
+                        uint64_t* filled) {
+    sr_scene* s = m;
+    sr_frame fs;
+    int rc = light_field_rays_check(s, f, n, starts, dirs, out, options, fs);
+    if (rc) return rc;
+    if (n == 0) { if (filled) *filled = 0; return SR_OK; }
+    if ((rc = use_device(s))) return rc;
+    uint64_t made = 0;
+    Staged io[] = {{starts, nullptr, (size_t)n * 24}, {dirs, nullptr, (size_t)n * 24}, {nullptr, out, (size_t)n * 4}, {nullptr, inside, (size_t)n},
+                   {nullptr, &made, sizeof(uint64_t)}};
+    rc = run_staged(m, s, io, 5, false, nullptr, [&](hipStream_t stream, unsigned long long* d_stats) {
+        SR_HIP(hipMemsetAsync(io[4].dev, 0, sizeof(uint64_t), stream));
+        const LfRaysReq req{n, (const double*)io[0].dev, (const double*)io[1].dev, (uint32_t*)io[2].dev, (uint8_t*)io[3].dev, (unsigned long long*)io[4].dev};
+        return render_common(s, &fs, nullptr, stream, d_stats, &req);
+    });
+    if (!rc && filled) *filled = made;
+    return rc;
 }
 
 // ---- sr_shadow_points ----

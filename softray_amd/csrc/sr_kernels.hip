@@ -180,6 +180,10 @@ const char* kernel_name(int id) {
         case K_TIGHT_BOXES: return "k_tight_boxes";           // the ordered copies' boxes fitted to their live records: k_tight_level per level + k_tight_top, per copy
         case K_ORIGIN_RAYS: return "k_origin_rays";           // sr_trace_origin_rays: a pass's walks (the packet launch + the per-lane one for its irregular rays)
         case K_ORIGIN_SORT: return "k_origin_sort";           // ... its order: k_dir_keys + the radix sort
+        case K_LFR_LOOKUP: return "k_lfr_lookup";             // sr_light_field_rays: a pass's fused lookup / the rays that waited for its fill
+        case K_LFR_FINISH: return "k_lfr_finish";
+        case K_LFRI_LOOKUP: return "k_lfri_lookup";           // ... with sr_set_light_field_interpolation
+        case K_LFRI_FINISH: return "k_lfri_finish";
         case K_OCCLUDED: return "k_occluded";                 // sr_occluded_rays: a pass's walks (the any-hit launch + the nearest-hit one for its irregular rays)
         case K_OCCL_SORT: return "k_occl_sort";               // ... its order: k_occl_keys + the radix sort
         case K_VOXEL_WALK: return "k_voxel_walk";

@@ -4817,6 +4817,144 @@ __global__ __launch_bounds__(256) void k_lfi_apply(FrameConst fc, const int32_t*
 }
 
 // --------------------------------------------------------------------------------------------------
+// sr_light_field_rays: LightFieldColorMethod.IntersectRay for n rays of the caller's (starts, dirs: [n][3] doubles, model space, the
+// direction not normalised -- k_lf_coords' conventions).  A frame runs lookup, fill, apply per band and reads every cell and entry twice;
+// a batch has no resolve after it, so the lookup stores the colour at once and only the rays that met an empty entry are looked at again.
+// Per pass:
+//   k_lfr_lookup   lane = ray: cell (lf_cell), gather; a sphere miss or a non-empty entry is stored to out[i].  A lane that found an empty
+//                  entry claims the cell (a look before the atomic, as k_lfi_lookup) -- the winners append the cell to the fill list -- and
+//                  appends (i, cell) to the pending list; one wave-aggregated atomicAdd per list (lf_queue_slot)
+//   the fill stage of a frame, unchanged (k_lf_fill; with shadows its SHADOW form, the shadow stage and k_lf_store)
+//   k_lfr_finish   grid-stride over the pending list, whose length it reads itself: out[i] = cache[cell]; the fill list's length is added
+//                  to `filled` (every listed cell is written exactly once by the fill stage)
+// k_lfri_lookup / k_lfri_finish are the same split with sr_set_light_field_interpolation: a ray whose 16 neighbours are all there blends
+// and stores in the lookup; the others claim what is empty and append their INDEX to the pending list -- the finish kernel computes base
+// cell and fractions again from the ray (lf_float4d on the same operands: the same bits).  Carrying them would write and read 36 bytes
+// per pending ray where the ray itself is 48 bytes read once, and on a baked table, the case the call is for, the list is empty.
+// pending: [0] the list's length (zeroed per pass on the stream), [2 ..] the entries
+// --------------------------------------------------------------------------------------------------
+__device__ __forceinline__ D3 lfr_load3(const double* __restrict__ p, uint32_t i) {
+    const double* a = p + (size_t)i * 3;
+    return mk(a[0], a[1], a[2]);
+}
+
+// claims an empty cell for the pass's fill list: true for the one lane (of the whole grid) that set the bit
+__device__ __forceinline__ bool lfr_claim(uint32_t* __restrict__ claim, uint32_t cell) {
+    const uint32_t bit = 1u << (cell & 31u);
+    if (__hip_atomic_load(&claim[cell >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) return false;
+    return !(atomicOr(&claim[cell >> 5], bit) & bit);
+}
+
+// LightFieldColorMethod.Interpolate's blend of the 16 gathered entries (k_lfi_apply's arithmetic in its operand order)
+__device__ __forceinline__ uint32_t lfr_blend(const uint32_t (&c)[16], const LfF4& frac) {
+    double r = 0.0, g = 0.0, b = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const double wu = (k & 8) ? frac.u : 1 - frac.u, wv = (k & 4) ? frac.v : 1 - frac.v;
+        const double ws = (k & 2) ? frac.s : 1 - frac.s, wt = (k & 1) ? frac.t : 1 - frac.t;
+        r = r + (double)(c[k] >> 16 & 255u) / 255.0 * wu * wv * ws * wt;
+        g = g + (double)(c[k] >> 8 & 255u) / 255.0 * wu * wv * ws * wt;
+        b = b + (double)(c[k] & 255u) / 255.0 * wu * wv * ws * wt;
+    }
+    return 0xFF000000u | lf_coord(r * 255.0) << 16 | lf_coord(g * 255.0) << 8 | lf_coord(b * 255.0);
+}
+
+// grid: one lane per ray of the pass.  list: room for `count` cells; pending: 2 + 2 x count words
+__global__ __launch_bounds__(256) void k_lfr_lookup(uint32_t count, const double* __restrict__ starts, const double* __restrict__ dirs, int N, uint32_t entries,
+                                                    uint32_t background, const uint32_t* __restrict__ cache, uint32_t* __restrict__ claim,
+                                                    uint32_t* __restrict__ out, uint8_t* __restrict__ inside, uint32_t* __restrict__ list,
+                                                    unsigned int* __restrict__ list_count, uint32_t* __restrict__ pending, unsigned long long* stats) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < count;
+    uint32_t cell = kLfMiss;
+    bool empty = false, won = false;
+    if (live) {
+        cell = lf_cell(lfr_load3(starts, i), lfr_load3(dirs, i), N, entries);
+        uint32_t color = background;
+        if (cell != kLfMiss) {
+            color = cache[cell];
+            empty = color == 0u;
+            if (empty) won = lfr_claim(claim, cell);
+        }
+        if (!empty) out[i] = color;
+        if (inside) inside[i] = cell != kLfMiss ? 1 : 0;
+    }
+    const unsigned int fslot = lf_queue_slot(won, list_count);               // (every lane of the wave is here)
+    if (won) list[fslot] = cell;
+    const unsigned int pslot = lf_queue_slot(empty, pending);
+    if (empty) { pending[2 + 2 * (size_t)pslot] = i; pending[3 + 2 * (size_t)pslot] = cell; }
+    if (stats) {                                                             // NumRaysFired counts the caller's rays; none of them walks anything
+        const unsigned long long lm = __ballot(live);
+        if ((threadIdx.x & 63u) == 0u) stat_add(&stats[0], (uint32_t)__popcll(lm));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lfr_finish(const uint32_t* __restrict__ pending, const uint32_t* __restrict__ cache, uint32_t* __restrict__ out,
+                                                    const unsigned int* __restrict__ list_count, unsigned long long* filled) {
+    const unsigned int total = pending[0], stride = gridDim.x * 256u;
+    for (unsigned int slot = blockIdx.x * 256u + threadIdx.x; slot < total; slot += stride)
+        out[pending[2 + 2 * (size_t)slot]] = cache[pending[3 + 2 * (size_t)slot]];
+    if (filled && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(filled, (unsigned long long)*list_count);
+}
+
+// list: room for min(16 x count, 4 N^4) cells, as k_lfi_lookup's; pending: 2 + count words
+__global__ __launch_bounds__(256) void k_lfri_lookup(uint32_t count, const double* __restrict__ starts, const double* __restrict__ dirs, int N, uint32_t background,
+                                                     const uint32_t* __restrict__ cache, uint32_t* __restrict__ claim, uint32_t* __restrict__ out,
+                                                     uint8_t* __restrict__ inside, uint32_t* __restrict__ list, unsigned int* __restrict__ list_count,
+                                                     uint32_t* __restrict__ pending, unsigned long long* stats) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < count;
+    uint32_t base = kLfMiss;
+    LfF4 frac;
+    frac.u = frac.v = frac.s = frac.t = 0.0;
+    if (live) {
+        LfF4 F;
+        if (lf_float4d(lfr_load3(starts, i), lfr_load3(dirs, i), N, F)) base = lfi_base(F, frac);
+        if (inside) inside[i] = base != kLfMiss ? 1 : 0;
+    }
+    uint32_t c[16];
+    bool empty = false;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        bool won = false;
+        uint32_t cell = 0u;
+        c[k] = 0u;
+        if (base != kLfMiss) {
+            cell = lfi_cell(base, k, (uint32_t)N);
+            c[k] = cache[cell];
+            if (c[k] == 0u) { empty = true; won = lfr_claim(claim, cell); }
+        }
+        const unsigned int slot = lf_queue_slot(won, list_count);
+        if (won) list[slot] = cell;
+    }
+    if (live && !empty) out[i] = base != kLfMiss ? lfr_blend(c, frac) : background;
+    const unsigned int pslot = lf_queue_slot(empty, pending);
+    if (empty) pending[2 + (size_t)pslot] = i;
+    if (stats) {
+        const unsigned long long lm = __ballot(live);
+        if ((threadIdx.x & 63u) == 0u) stat_add(&stats[0], (uint32_t)__popcll(lm));
+    }
+}
+
+// no entry it reads is empty: the pass's fill ran in between
+__global__ __launch_bounds__(256) void k_lfri_finish(const uint32_t* __restrict__ pending, const double* __restrict__ starts, const double* __restrict__ dirs, int N,
+                                                     const uint32_t* __restrict__ cache, uint32_t* __restrict__ out,
+                                                     const unsigned int* __restrict__ list_count, unsigned long long* filled) {
+    const unsigned int total = pending[0], stride = gridDim.x * 256u;
+    for (unsigned int slot = blockIdx.x * 256u + threadIdx.x; slot < total; slot += stride) {
+        const uint32_t i = pending[2 + (size_t)slot];
+        LfF4 F, frac;
+        if (!lf_float4d(lfr_load3(starts, i), lfr_load3(dirs, i), N, F)) continue;      // (listed: it pierced the sphere in the lookup)
+        const uint32_t base = lfi_base(F, frac);
+        uint32_t c[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) c[k] = cache[lfi_cell(base, k, (uint32_t)N)];
+        out[i] = lfr_blend(c, frac);
+    }
+    if (filled && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(filled, (unsigned long long)*list_count);
+}
+
+// --------------------------------------------------------------------------------------------------
 // k_lf_bake (sr_bake_light_field): the DENSE fill of the table -- every entry of [lo, hi) that is still 0 gets what k_lf_fill would store
 // for it.  Work item = one wave = one origin patch (u, v) x an 8x8 tile of target patches (s0 .. s0 + 7, t0 .. t0 + 7) clipped to 2N x N;
 // items are numbered origin-major, t tiles fastest.  Lane l holds the target (s0 + (l >> 3), t0 + (l & 7)): t is the fastest index of the
@@ -6139,6 +6277,36 @@ static hipError_t launch_lf_shadows_t(const PipelineLaunch& L, long long max_hit
 
 constexpr int kLfListCount = 16;      // counters[16]: the fill list's length of a shadowed light-field band (counters[0..15] are the shadow stage's)
 
+// the fill stage of a light-field band, or of a pass of sr_light_field_rays: k_lf_fill over the list (at most max_cells cells; the kernel reads
+// the length itself), with shadows its SHADOW form, the shadow stage on the hits it queued and k_lf_store
+template <int MODE, bool EXTRA>
+static hipError_t launch_lf_fill_t(const PipelineLaunch& L, long long max_cells, unsigned int* list_count, bool shadowed) {
+    hipError_t e;
+    hipEvent_t e0, e1;
+    pipe_events(L, K_LF_FILL, e0, e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    const unsigned fblocks = (unsigned)std::min<long long>((max_cells + 255) / 256, (long long)L.persistent_blocks);
+    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+    unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
+    if (shadowed) {
+        const auto fill = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(fblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)list_count, L.lf_cache,
+                               L.lf_claim, sec_stats, (HitRec*)L.hits, L.counters, L.lf_stage);
+        };
+        if (sec_stats) fill(k_lf_fill<MODE, EXTRA, true, true>); else fill(k_lf_fill<MODE, EXTRA, false, true>);
+    } else {
+        const auto fill = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(fblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)list_count, L.lf_cache,
+                               L.lf_claim, sec_stats, (HitRec*)nullptr, (unsigned int*)nullptr, (uint32_t*)nullptr);
+        };
+        if (sec_stats) fill(k_lf_fill<MODE, EXTRA, true>); else fill(k_lf_fill<MODE, EXTRA, false>);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    if (shadowed && (e = launch_lf_shadows_t<MODE, EXTRA>(L, max_cells, L.lf_claim)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
 // the three light-field kernels of one row band (see k_lf_lookup; L.lf_interp: k_lfi_lookup and k_lfi_apply around the same fill stage, whose
 // list then holds up to 16 cells per sample); counters[0] is the length of the band's fill list.  Nothing waits
 // for the device: k_lf_fill reads the length itself.  With shadows (L.lf_shadows) the fill list's length lives in counters[kLfListCount],
@@ -6167,29 +6335,9 @@ static hipError_t launch_lightfield_t(const PipelineLaunch& L, int row_begin, in
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    pipe_events(L, K_LF_FILL, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
     // (an interpolating band lists up to min(16 x samples, 4 N^4) cells)
     const long long max_cells = L.lf_interp ? std::min<long long>(16ll * nsamples, (long long)L.lf_entries) : (long long)nsamples;
-    const unsigned fblocks = (unsigned)std::min<long long>((max_cells + 255) / 256, (long long)L.persistent_blocks);
-    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
-    unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
-    if (shadowed) {
-        const auto fill = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(fblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)list_count, L.lf_cache,
-                               L.lf_claim, sec_stats, (HitRec*)L.hits, L.counters, L.lf_stage);
-        };
-        if (sec_stats) fill(k_lf_fill<MODE, EXTRA, true, true>); else fill(k_lf_fill<MODE, EXTRA, false, true>);
-    } else {
-        const auto fill = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(fblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)list_count, L.lf_cache,
-                               L.lf_claim, sec_stats, (HitRec*)nullptr, (unsigned int*)nullptr, (uint32_t*)nullptr);
-        };
-        if (sec_stats) fill(k_lf_fill<MODE, EXTRA, true>); else fill(k_lf_fill<MODE, EXTRA, false>);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    if (shadowed && (e = launch_lf_shadows_t<MODE, EXTRA>(L, max_cells, L.lf_claim)) != hipSuccess) return e;
+    if ((e = launch_lf_fill_t<MODE, EXTRA>(L, max_cells, list_count, shadowed)) != hipSuccess) return e;
     pipe_events(L, L.lf_interp ? K_LFI_APPLY : K_LF_APPLY, e0, e1);
     if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
     if (L.lf_interp) {
@@ -6203,6 +6351,53 @@ static hipError_t launch_lightfield_t(const PipelineLaunch& L, int row_begin, in
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
+// sr_light_field_rays (PipelineLaunch::lfr_n > 0): the caller's rays in passes of at most L.lfr_pass rays -- what the fill list, the pending
+// list (lf_cells) and, with shadows, the queue, the staging buffer and the shadow stage's lists are sized for.  Per pass: the counters and the
+// pending list's length reset on the stream, the fused lookup, the frame's fill stage, the finish kernel (see k_lfr_lookup); back to back on
+// the stream, the host never waits.  A later pass reads what an earlier one filled
+template <int MODE, bool EXTRA>
+static hipError_t launch_lf_rays_t(const PipelineLaunch& L) {
+    const bool shadowed = L.lf_shadows && (L.fc.flags & 2u);
+    unsigned int* list_count = shadowed ? L.counters + kLfListCount : L.counters;
+    uint32_t* pending = L.lf_cells;
+    hipError_t e;
+    for (int64_t first = 0; first < L.lfr_n; first += L.lfr_pass) {
+        const uint32_t count = (uint32_t)std::min<int64_t>(L.lfr_pass, L.lfr_n - first);
+        const unsigned blocks = (count + 255u) / 256u;
+        const double* starts = L.lfr_starts + first * 3;
+        const double* dirs = L.lfr_dirs + first * 3;
+        uint32_t* out = L.lfr_out + first;
+        uint8_t* inside = L.lfr_inside ? L.lfr_inside + first : nullptr;
+        if ((e = hipMemsetAsync(L.counters, 0, (shadowed ? (size_t)kCounterWords : 1) * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(pending, 0, sizeof(uint32_t), L.stream)) != hipSuccess) return e;
+        hipEvent_t e0, e1;
+        pipe_events(L, L.lf_interp ? K_LFRI_LOOKUP : K_LFR_LOOKUP, e0, e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        if (L.lf_interp)
+            hipLaunchKernelGGL(k_lfri_lookup, dim3(blocks), dim3(256), 0, L.stream, count, starts, dirs, L.lf_res, L.fc.background, (const uint32_t*)L.lf_cache, L.lf_claim, out, inside,
+                               L.lf_list, list_count, pending, L.stats);
+        else
+            hipLaunchKernelGGL(k_lfr_lookup, dim3(blocks), dim3(256), 0, L.stream, count, starts, dirs, L.lf_res, L.lf_entries, L.fc.background, (const uint32_t*)L.lf_cache, L.lf_claim, out,
+                               inside, L.lf_list, list_count, pending, L.stats);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        const long long max_cells = L.lf_interp ? std::min<long long>(16ll * count, (long long)L.lf_entries) : (long long)count;
+        if ((e = launch_lf_fill_t<MODE, EXTRA>(L, max_cells, list_count, shadowed)) != hipSuccess) return e;
+        pipe_events(L, L.lf_interp ? K_LFRI_FINISH : K_LFR_FINISH, e0, e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        const unsigned pblocks = std::min<unsigned>(blocks, (unsigned)L.persistent_blocks);
+        if (L.lf_interp)
+            hipLaunchKernelGGL(k_lfri_finish, dim3(pblocks), dim3(256), 0, L.stream, (const uint32_t*)pending, starts, dirs, L.lf_res, (const uint32_t*)L.lf_cache, out,
+                               (const unsigned int*)list_count, L.lfr_filled);
+        else
+            hipLaunchKernelGGL(k_lfr_finish, dim3(pblocks), dim3(256), 0, L.stream, (const uint32_t*)pending, (const uint32_t*)L.lf_cache, out, (const unsigned int*)list_count,
+                               L.lfr_filled);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 
@@ -6500,6 +6695,7 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     if (L.pts_n > 0) return launch_pts_shadows_t<MODE, EXTRA>(L);                  // sr_shadow_points: the caller's points, no rows, no pixels
     if (L.hits_req) return launch_hits_t<MODE, EXTRA>(L);                          // sr_render_hits: the rows' camera samples, no pixels
     if (L.org_n > 0) return launch_origin_t<MODE, EXTRA>(L);                       // sr_trace_origin_rays: the caller's directions, no rows, no pixels
+    if (L.lfr_n > 0) return launch_lf_rays_t<MODE, EXTRA>(L);                      // sr_light_field_rays: the caller's rays through the colour light field
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     const bool shadows = (L.fc.flags & 2u) != 0;
     const bool path = (L.fc.flags & kFlagPathTracing) != 0;          // (sr_api.cpp: never together with shadows or mirror bounces)

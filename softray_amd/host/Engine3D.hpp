@@ -358,6 +358,28 @@ public:
         sr_check(sr_bake_light_field(scene_, &f, 0, 4 * n * n * n * n, &filled));
         return filled;
     }
+    // The colour light field for n lines of the caller's (sr_light_field_rays): out[i] = the colour LightFieldColorMethod.IntersectRay gives the ray
+    // (starts[i], dirs[i]) -- [n][3] in model space, the direction not normalised -- with the frame Render() would build for the first instance:
+    // its geometry, shading, pose and lights; rayTraceLightField is implied.  An empty entry of the renderer's light field -- the one its frames
+    // and BakeLightField() fill -- is filled first.  inside (or nullptr): 1 where the line pierces the sphere; a line that misses it gets the
+    // background.  Returns the number of entries written (0 without a model or rays).  LightFieldStoresTriangles = true is refused by the
+    // library, by name, like everything Render() refuses of a light-field frame
+    uint64_t LightFieldRays(int64_t n, const double* starts, const double* dirs, uint32_t* out, uint8_t* inside = nullptr) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel() || n == 0) return 0;
+        if (Instances.empty()) throw InvalidOperationException("LightFieldRays: no instance to take the pose from");
+        Instance& inst = *Instances.front();
+        inst.FieldOfViewDepth = fieldOfViewDepth_;
+        PreCalculate();
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_frame f = BuildFrame(inst);
+        f.flags &= ~(uint32_t)SR_F_PRIMARY_STATS_ONLY;     // (sr_last_ray_stats gets the canonical rays' counters)
+        sr_check(sr_set_light_field_triangles(scene_, lightFieldHasTris_ ? 1 : 0));   // (as CheckLightField: true is the library's to refuse)
+        uint64_t filled = 0;
+        sr_check(sr_light_field_rays(scene_, &f, n, starts, dirs, out, inside, 0u, &filled));
+        return filled;
+    }
     // ShadowMethod's soft shadow for n surface points of the caller (sr_shadow_points): out[i] = color[i] (nullptr: 0xFFFFFFFF) modulated with the
     // byte of the light, the shadow samples and the root geometry of the frame Render() would build for the first instance; rayTraceShadows is
     // implied.  pos / normal: [n][3] in model space, the normal as given.  coherent: 64 consecutive points are neighbours (SR_POINTS_COHERENT).

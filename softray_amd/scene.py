@@ -595,6 +595,28 @@ class GpuScene:
         _check(_lib.lib().sr_occluded_rays_device(self._h, int(target), int(n), _vp(d_starts), _vp(d_dirs), _vp(d_limits), _vp(d_occluded),
                                                   self._ray_options(endpoints, coherent), _stream(stream), _vp(d_stats_ptr)))
 
+    # ---- the colour light field for caller-given rays (sr_light_field_rays) ----
+    def light_field_rays(self, frame, starts, dirs, want_inside=True):
+        """LightFieldColorMethod.IntersectRay for n lines of the caller's (sr_light_field_rays): (out uint32 [n], inside uint8 [n] or None,
+        filled).  out[i] is the colour a light-field frame gives a sample whose ray is (starts[i], dirs[i]) -- model space, the direction not
+        normalised; empty entries of the scene's table are filled first, as a frame fills them, and `filled` counts them."""
+        starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = starts.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("dirs has %d entries for %d rays" % (dirs.shape[0], n))
+        out = np.zeros(n, dtype=np.uint32)
+        inside = np.zeros(n, dtype=np.uint8) if want_inside else None
+        filled = C.c_uint64(0)
+        _check(_lib.lib().sr_light_field_rays(self._h, C.byref(frame), n, _p(starts), _p(dirs), _p(out), _p(inside), 0, C.byref(filled)))
+        return out, inside, int(filled.value)
+
+    def light_field_rays_device(self, frame, n, d_starts, d_dirs, d_out, d_inside=0, stream=0, d_filled_ptr=None, d_stats_ptr=None):
+        """sr_light_field_rays_device: every array is a DEVICE pointer (d_inside 0 / None: not wanted; d_filled_ptr: a device uint64 or None);
+        enqueued on `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
+        _check(_lib.lib().sr_light_field_rays_device(self._h, C.byref(frame), int(n), _vp(d_starts), _vp(d_dirs), _vp(d_out), _vp(d_inside), 0,
+                                                     _stream(stream), _vp(d_filled_ptr), _vp(d_stats_ptr)))
+
     # ---- the strip gather over RCCL (include/softray.h) ----
     def set_gather(self, kind):
         """Multi-device scene: _lib.GATHER_COPY (peer copies, default) or _lib.GATHER_RCCL (grouped ncclSend / ncclRecv)."""

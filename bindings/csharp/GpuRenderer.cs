@@ -124,6 +124,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_trace_origin_rays_device(IntPtr scene, int target, [In] double[] origin3, long n, IntPtr dDirs, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_occluded_rays(IntPtr scene, int target, long n, [In] double[] starts, [In] double[] dirs, [In] double[] limits, [Out] byte[] occluded, uint options, [Out] ulong[] stats4);
         [DllImport(Lib)] public static extern int sr_occluded_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, IntPtr dOccluded, uint options, IntPtr hipStream, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_nearest_rays(IntPtr scene, int target, long n, [In] double[] starts, [In] double[] dirs, [In] double[] limits, [Out] byte[] hit, [Out] double[] rayFrac, [Out] double[] pos, [Out] double[] normal, [Out] uint[] color, [Out] int[] triIndex, uint options, [Out] ulong[] stats4);
+        [DllImport(Lib)] public static extern int sr_nearest_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -661,6 +663,30 @@ namespace Engine3D.Hip
         {
             Native.Check(Native.sr_occluded_rays_device(scene, mode | (root ? 0x100 : 0), n, dStarts, dDirs, dLimits, dOccluded,
                                                         (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), stream, dStats));
+        }
+
+        /// The nearest hit of a batch of arbitrary rays within a distance (sr_nearest_rays): bit for bit what IntersectRay answers for
+        /// (starts[i], D_i) on the root geometry (root = true) or the model alone where that is a hit with rayFrac &lt;= limits[i] (limits == null:
+        /// no limit), a miss otherwise -- on the walk a mirror level's rays take.  starts and dirs are double[n * 3]; D_i = dirs[i], or with
+        /// endpoints dirs[i] - starts[i].  coherent: the rays are walked in the order given.  Blocks.
+        public FrameHits NearestRays(double[] starts, double[] dirs, double[] limits, int mode, bool root = false, bool endpoints = false, bool coherent = false)
+        {
+            long n = starts.Length / 3;
+            var r = new FrameHits { Hit = new byte[n], RayFrac = new double[n], Pos = new double[n * 3], Normal = new double[n * 3],
+                                    Color = new uint[n], TriIndex = new int[n], Stats4 = new ulong[4] };
+            Native.Check(Native.sr_nearest_rays(scene, mode | (root ? 0x100 : 0), n, starts, dirs, limits, r.Hit, r.RayFrac, r.Pos, r.Normal, r.Color, r.TriIndex,
+                                                (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), r.Stats4));
+            return r;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_nearest_rays_device), dLimits IntPtr.Zero for no limit and
+        /// IntPtr.Zero for an output that is not wanted; enqueued on `stream` without a host synchronisation; dStats: ulong[24] on the device, or
+        /// IntPtr.Zero.
+        public void NearestRaysDevice(long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, int mode, bool root, bool endpoints, bool coherent, IntPtr dHit,
+                                      IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, IntPtr stream, IntPtr dStats)
+        {
+            Native.Check(Native.sr_nearest_rays_device(scene, mode | (root ? 0x100 : 0), n, dStarts, dDirs, dLimits, dHit, dRayFrac, dPos, dNormal, dColor,
+                                                       dTriIndex, (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), stream, dStats));
         }
 
         /// ShadingMethod's colour step for n recorded intersections in DEVICE memory (sr_shade_points_device): dOut[i] = dColor[i] modulated with

@@ -654,6 +654,49 @@ int  sr_occluded_rays_device(sr_scene*, int32_t target, int64_t n, const double*
                              const double* d_limits /* or NULL */, uint8_t* d_occluded, uint32_t options,
                              void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
+/* The NEAREST HIT of a batch of arbitrary rays, with a per-ray distance limit, on the walk the library keeps for incoherent rays: what a
+ * reflection, a refraction, a gather or the second bounce of a caller's pipeline asks.  More than one bounce and mirror chains are the
+ * caller's loop over this call (see sr_render_hits, sr_shade_points, sr_path_points for the other steps).
+ * Result: for every ray and every non-NULL output, bit for bit what sr_trace_rays(scene, target, ...) answers for (starts[i], D_i), provided
+ * that answer is a hit with ray_frac <= limit_i; otherwise sr_trace_rays' miss (hit 0, zeros, tri_index -1).  limits == NULL: no limit, i.e.
+ * sr_trace_rays exactly.  The comparison is IEEE <=: NaN, -inf and negative limits give a miss, +inf any hit.  Every output is optional
+ * (all NULL: the call runs for the statistics).  A hit on extra geometry has tri_index -1 and the primitive's colour; `color` is unshaded.
+ * Direction: D_i = dirs[i], not normalised; with SR_RAYS_ENDPOINTS dirs[i] is an END POINT and D_i = dirs[i] - starts[i], one FP64
+ * subtraction per component as in sr_occluded_rays -- a limit of 1.0 then means "up to the end point".
+ * target: SR_MODE_* (the model alone) or SR_TARGET_ROOT | SR_MODE_*; SR_TARGET_VOXELS is SR_ERR_UNSUPPORTED.
+ * Why culling at the limit is exact: ray_frac = fl(t + offset) is monotone in t, so if the nearest hit does not qualify no hit does, and "the
+ * nearest hit, if it qualifies" is "the nearest qualifying hit".  The walk on the own BVH culls every box beyond t = limit - offset, inflated
+ * as bvh_intersect<true> does it (sr_occluded_rays above); whatever it then finds beyond the limit fails the final FP64 test
+ * best + offset <= limit.  SR_MODE_REF_TREE and SR_MODE_BRUTE run sr_trace_rays' walk and compare afterwards; the reference tree's leaf-face
+ * rule stays what it is.
+ * Routing in SR_MODE_BVH: a ray that is REGULAR by sr_occluded_rays' definition (finite start with max |s_k| <= 2^100, regular direction, a
+ * limit that is neither NaN nor -inf) takes three kernels: k_nr_prep (FP64 clip to the root box, offset, the fp32 cull bound), k_nr_walk
+ * (persistent lanes refilled at 24 busy ones, the four-wide tree with up to eight pending leaves, the first 24 stack levels in LDS, the fp32
+ * pre-test, the reference's FP64 triangle test with the lowest-index tie rule) and k_nr_finish (extra geometry from the unclipped start, the
+ * limit, the outputs).  Every other ray goes to the end of its pass and is answered by the function sr_trace_rays calls plus the comparison:
+ * equal by construction.
+ * Order: without SR_RAYS_COHERENT a pass of SR_MODE_BVH is ordered as sr_occluded_rays orders it (start cell, direction octant, a stable radix
+ * sort); with it the input order is kept, the irregular rays still last.  Results never depend on the option or the order; speed does.
+ * Refusals, in this order: a NULL scene, n < 0, NULL starts / dirs with n > 0, unknown option bits: SR_ERR_INVALID_ARG; SR_TARGET_VOXELS:
+ * SR_ERR_UNSUPPORTED; sr_trace_rays' own checks (SR_ERR_NO_MODEL, SR_ERR_NOT_BUILT); a host-only scene: SR_ERR_NO_DEVICE.  n == 0 that passes
+ * all of them: SR_OK, nothing is touched.
+ * State: as sr_occluded_rays -- no per-origin or per-light record is rewritten, the call is ordered like a frame.  Passes of at most 2^22 rays
+ * (SR_DBG_BAND_SAMPLES: fewer) follow each other without the host waiting.  A multi-device scene runs the call on devices[0].  Scratch per
+ * pass of p rays in SR_MODE_BVH, from the scene's first scratch set: 64 p bytes of ray records, 16 p of walk results, 16 p + 256 of sort keys
+ * and order plus the radix sort's own scratch, and for trees deeper than the LDS levels (max(3 x four-wide depth + 2, depth + 2) - 24 levels)
+ * x 8 workgroups per CU x 256 lanes x 4 bytes of stack.  The host variant stages through the scene's device buffers, blocks and fills
+ * sr_last_ray_stats; the device variant enqueues on `hip_stream` without a host synchronisation.  Statistics (there is no per-ray counters
+ * array): [0] = n; [1..3] in SR_MODE_REF_TREE / SR_MODE_BRUTE the sums of sr_trace_rays' per-ray counters, on the own BVH what the walks
+ * fetched (not pinned); [4..] 0. */
+int  sr_nearest_rays(sr_scene*, int32_t target, int64_t n, const double* starts, const double* dirs,
+                     const double* limits /* [n], or NULL: no limit */,
+                     uint8_t* hit, double* ray_frac, double* pos, double* normal, uint32_t* color, int32_t* tri_index,
+                     uint32_t options, uint64_t stats[4] /* or NULL */);
+int  sr_nearest_rays_device(sr_scene*, int32_t target, int64_t n, const double* d_starts, const double* d_dirs,
+                            const double* d_limits /* or NULL */,
+                            uint8_t* d_hit, double* d_ray_frac, double* d_pos, double* d_normal, uint32_t* d_color, int32_t* d_tri_index,
+                            uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* ShadingMethod.IntersectRay's colour step in batch (ShadingMethod.cs:36-68 -> CalcLighting :110-177): for n recorded
  * intersections out[i] = ModulatePackedColor(color[i], (byte)(255 * intensity)) with the frame's transform and lights (only the
  * matrices, position_z, fov_depth, lights, ambient, shininess and the POINT_LIGHT / SPECULAR flags of `frame` are read).
@@ -948,7 +991,7 @@ enum {
     SR_DBG_BAND_SAMPLES   = 0,   /* samples per row band (default 16 Mi / 32 Mi): small values force several bands; also the cells
                                     per pass of sr_bake_light_field with shadows (default 2^22; whole origin patches, at least one) and the
                                     points per pass of sr_shadow_points and sr_static_shadow_points (default 2^22), of sr_ao_points (default and limit 2^17) and of sr_path_points (default and limit 2^22),
-                                    and the rays per pass of sr_trace_origin_rays, of sr_occluded_rays and of sr_light_field_rays (default and limit 2^22;
+                                    and the rays per pass of sr_trace_origin_rays, of sr_occluded_rays, of sr_nearest_rays and of sr_light_field_rays (default and limit 2^22;
                                     sr_light_field_rays with interpolation and shadows together: 1/16 of the value, as a frame's bands) */
     SR_DBG_ROUND_CAP0     = 1,   /* candidate-list length of shaft round 1 (default 40, <= 64)                                 */
     SR_DBG_ROUND_CAP1     = 2,   /* ... of round 2 (default 64, <= 1024): tiny lists force round 2 and the exact fallback      */
@@ -971,7 +1014,10 @@ enum {
                                     other, and waits once per pass (same output; cross-check and baseline); 45 sr_path_points does the same, and then refuses first_sample + n > 2^30 with SR_ERR_UNSUPPORTED: the host draws its way to first_sample; 46 sr_occluded_rays walks a pass in input
                                     order whatever the options say (no ray sort); 47 sr_occluded_rays in SR_MODE_BVH answers every ray with a nearest-hit walk plus the
                                     comparison instead of the any-hit walk (both: same output); 100 + T (T in 0..63) also makes the any-hit launch of sr_occluded_rays run on
-                                    persistent lanes that fetch new rays at T busy lanes (same output; faster on incoherent batches, slower on short coherent walks: DESIGN 5.28); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    persistent lanes that fetch new rays at T busy lanes (same output; faster on incoherent batches, slower on short coherent walks: DESIGN 5.28); 48 sr_nearest_rays walks a pass
+                                    in input order whatever the options say (no ray sort); 49 sr_nearest_rays answers every ray with one private walk per lane (k_nr_lane) in input
+                                    order, also in SR_MODE_BVH (same output; baseline and cross-check); 100 + T and 200 + K also set the refill threshold and the LDS
+                                    stack levels of sr_nearest_rays' walk kernel, as the bounce walk reads them below; 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
                                     fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid

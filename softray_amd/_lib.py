@@ -55,11 +55,12 @@ SYMBOLS = [
     "sr_path_points", "sr_path_points_device",
     "sr_trace_origin_rays", "sr_trace_origin_rays_device",
     "sr_occluded_rays", "sr_occluded_rays_device",
+    "sr_nearest_rays", "sr_nearest_rays_device",
     "sr_light_field_rays", "sr_light_field_rays_device",
 ]
 POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 RAYS_COHERENT = 1                      # SR_RAYS_COHERENT
-RAYS_ENDPOINTS = 2                     # SR_RAYS_ENDPOINTS (sr_occluded_rays)
+RAYS_ENDPOINTS = 2                     # SR_RAYS_ENDPOINTS (sr_occluded_rays, sr_nearest_rays)
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
 # sr_debug_set keys (include/softray.h)
@@ -187,6 +188,8 @@ def lib():
     L.sr_trace_origin_rays_device.restype = i32; L.sr_trace_origin_rays_device.argtypes = [vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_occluded_rays.restype = i32; L.sr_occluded_rays.argtypes = [vp, i32, i64, vp, vp, vp, vp, C.c_uint32, vp]
     L.sr_occluded_rays_device.restype = i32; L.sr_occluded_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, C.c_uint32, vp, vp]
+    L.sr_nearest_rays.restype = i32; L.sr_nearest_rays.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp]
+    L.sr_nearest_rays_device.restype = i32; L.sr_nearest_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_light_field_rays.restype = i32; L.sr_light_field_rays.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp]
     L.sr_light_field_rays_device.restype = i32; L.sr_light_field_rays_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.sr_rccl_unique_id.restype = i32; L.sr_rccl_unique_id.argtypes = [vp]

@@ -3219,6 +3219,115 @@ int sr_occluded_rays(sr_scene* m, int32_t target, int64_t n, const double* start
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Nearest-hit ray batches with a distance limit (sr_nearest_rays): sr_trace_rays' answers on the mirror extension's incoherent-ray route
+// ------------------------------------------------------------------------------------------------------------------
+// what sr_nearest_rays[_device] refuses, in the header's order; `s`: the scene that runs the call (the first part of a multi-device scene)
+static int nearest_rays_check(sr_scene*& s, int32_t target, int64_t n, const void* starts, const void* dirs, uint32_t options, int& mode, bool& with_extra) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_nearest_rays: the scene is NULL");
+    if (n < 0) return fail(SR_ERR_INVALID_ARG, "sr_nearest_rays: n is negative");
+    if (n > 0 && (!starts || !dirs)) return fail(SR_ERR_INVALID_ARG, "sr_nearest_rays: starts and dirs must not be NULL when n > 0");
+    if (options & ~(uint32_t)(SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS))
+        return fail(SR_ERR_INVALID_ARG, "sr_nearest_rays: unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)");
+    if (target & SR_TARGET_VOXELS)
+        return fail(SR_ERR_UNSUPPORTED, "sr_nearest_rays: the voxel grid (SR_TARGET_VOXELS) has no tree to walk and its hits have rayFrac 0; use sr_trace_rays");
+    with_extra = (target & SR_TARGET_ROOT) != 0;
+    mode = target & 0xff;
+    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "sr_nearest_rays: the scene has no model (sr_set_triangles, sr_load_3ds)");
+    int rc;
+    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays */ }
+    else if ((rc = check_mode(s, mode))) return rc;
+    if (s->device < 0) return fail(SR_ERR_NO_DEVICE, "sr_nearest_rays: a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
+    return SR_OK;
+}
+
+struct NearestOut { uint8_t* hit; double* ray_frac; double* pos; double* normal; uint32_t* color; int32_t* tri; };
+
+// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set's sort and bounce buffers
+static int nearest_rays_common(sr_scene* s, int mode, bool with_extra, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits,
+                               const NearestOut& out, uint32_t options, hipStream_t stream, unsigned long long* d_stats) {
+    int rc = sync_geometry(s, (uint32_t)mode);
+    if (rc) return rc;
+    // ---- ordered like a frame (render_common): a frame's facing partition moves the records the walk reads ----
+    StreamOrder order(s, stream);
+    if (order.entered) return order.entered;
+    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
+    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kNearestMaxPass) : sr::kNearestMaxPass;
+    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
+    sr::NearestLaunch L{};
+    L.sc = dev_scene(s);
+    L.mode = mode;
+    L.with_extra = with_extra && !s->extra_recs.empty();
+    L.n = n; L.pass = pass;
+    L.starts = d_starts; L.dirs = d_dirs; L.limits = d_limits;
+    L.hit = out.hit; L.ray_frac = out.ray_frac; L.pos = out.pos; L.normal = out.normal; L.color = out.color; L.tri = out.tri;
+    L.endpoints = (options & SR_RAYS_ENDPOINTS) != 0;
+    L.input_order = (options & SR_RAYS_COHERENT) != 0 || hook == 48;                            // (hook: input order whatever the options say)
+    L.lane_walks = hook == 49;                                                                  // (hook: every ray through k_nr_lane)
+    L.bvh2 = s->dbg[SR_DBG_BVH2_PACKETS] > 0;
+    L.refill_at = (hook >= 100 && hook <= 163) ? (int)(hook - 100) : sr::kNearestRefillAt;     // (hook)
+    L.lds_levels = (hook >= 200 && hook < 300) ? std::max(1, (int)(hook - 200)) : sr::pipeline_bounce_lds_levels();   // (hook)
+    if (mode == SR_MODE_BVH && !L.lane_walks) {
+        if ((rc = ensure_num_cus(s))) return rc;
+        L.persistent_blocks = s->num_cus * 8;
+        sr_scene::BandScratch& B = s->scratch[0];
+        const size_t slots = (size_t)(pass + 255) / 256 * 256;
+        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
+        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
+        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
+        SR_HIP(B.bounce_prep.reserve(slots * 64));
+        SR_HIP(B.bounce_res.reserve(slots * 16));
+        // (k_nr_walk keeps L.lds_levels stack levels per lane in LDS, the rest of the worst case here: [level][lane of the grid])
+        const long long deep = std::max(3 * (long long)s->b4_depth + 2, (long long)s->bvh.depth + 2) - L.lds_levels;
+        if (deep > 0) SR_HIP(B.bounce_stack.reserve((size_t)deep * (size_t)s->num_cus * 8 * 256 * 4));
+        L.sort_buf = (unsigned int*)B.ray_sort.p;
+        L.sort_temp = B.ray_sort_temp.p;
+        L.prep = B.bounce_prep.p;
+        L.res = B.bounce_res.p;
+        L.deep = (int32_t*)B.bounce_stack.p;
+        L.deep_bytes = B.bounce_stack.cap;
+    }
+    L.stats = d_stats;
+    L.stream = stream;
+    L.user = s;
+    L.get_events = timing_events;
+    SR_HIP(sr::launch_nearest(L));
+    return SR_OK;
+}
+
+int sr_nearest_rays_device(sr_scene* m, int32_t target, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits, uint8_t* d_hit,
+                           double* d_ray_frac, double* d_pos, double* d_normal, uint32_t* d_color, int32_t* d_tri_index, uint32_t options, void* hip_stream,
+                           uint64_t* d_stats) {
+    sr_scene* s = m;
+    int mode; bool with_extra;
+    int rc = nearest_rays_check(s, target, n, d_starts, d_dirs, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    const NearestOut out{d_hit, d_ray_frac, d_pos, d_normal, d_color, d_tri_index};
+    return nearest_rays_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, out, options, stream, (unsigned long long*)d_stats);
+}
+
+int sr_nearest_rays(sr_scene* m, int32_t target, int64_t n, const double* starts, const double* dirs, const double* limits, uint8_t* hit, double* ray_frac,
+                    double* pos, double* normal, uint32_t* color, int32_t* tri_index, uint32_t options, uint64_t stats[4]) {
+    sr_scene* s = m;
+    int mode; bool with_extra;
+    int rc = nearest_rays_check(s, target, n, starts, dirs, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    Staged io[] = {{starts, nullptr, (size_t)n * 24}, {dirs, nullptr, (size_t)n * 24}, {limits, nullptr, (size_t)n * 8}, {nullptr, hit, (size_t)n},
+                   {nullptr, ray_frac, (size_t)n * 8}, {nullptr, pos, (size_t)n * 24}, {nullptr, normal, (size_t)n * 24}, {nullptr, color, (size_t)n * 4},
+                   {nullptr, tri_index, (size_t)n * 4}};
+    return run_staged(m, s, io, 9, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
+        const NearestOut out{(uint8_t*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev, (double*)io[6].dev, (uint32_t*)io[7].dev, (int32_t*)io[8].dev};
+        return nearest_rays_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev, out, options, stream,
+                                   d_stats);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The RCCL strip gather, native: no PyTorch in the data path.
 // ------------------------------------------------------------------------------------------------------------------
 int sr_set_gather(sr_scene* m, int32_t kind) {

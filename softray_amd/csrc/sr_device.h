@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_LFR_LOOKUP = 46, K_LFR_FINISH = 47, K_LFRI_LOOKUP = 48, K_LFRI_FINISH = 49, K_COUNT = 50 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_LFR_LOOKUP = 46, K_LFR_FINISH = 47, K_LFRI_LOOKUP = 48, K_LFRI_FINISH = 49, K_NEAREST = 50, K_NEAREST_SORT = 51, K_COUNT = 52 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -427,6 +427,40 @@ struct OccludedLaunch {
     void*       user;
 };
 hipError_t launch_occluded(const OccludedLaunch& L);
+
+// sr_nearest_rays (sr_nearest.hip): sr_trace_rays' answer where it is a hit with ray_frac <= limit, its miss otherwise, for n caller-given
+// rays in passes of `pass` rays.  SR_MODE_BVH: occl_order's order, then k_nr_prep / k_nr_walk / k_nr_finish for the regular rays
+constexpr int64_t kNearestMaxPass = 1ll << 22;
+constexpr int kNearestRefillAt = 24;    // k_nr_walk fetches new rays when at most this many lanes of a wave are still walking (k_bounce_walk's)
+struct NearestLaunch {
+    DevScene    sc;
+    int32_t     mode;           // SR_MODE_*
+    bool        with_extra;     // root geometry of the chain (extra + model)
+    int64_t     n, pass;
+    const double* starts;       // device [n][3]
+    const double* dirs;         // device [n][3]: directions, or end points (endpoints)
+    const double* limits;       // device [n] or nullptr (no limit)
+    uint8_t* hit; double* ray_frac; double* pos; double* normal; uint32_t* color; int32_t* tri;    // device [n] each, or nullptr
+    bool        endpoints;      // SR_RAYS_ENDPOINTS
+    bool        input_order;    // SR_RAYS_COHERENT / hook 48: a pass keeps its input order (the irregular rays still go last)
+    bool        lane_walks;     // SR_MODE_BVH with one private walk per lane for every ray, in input order (hook 49)
+    bool        bvh2;           // SR_DBG_BVH2_PACKETS: the walk on the two-wide tree
+    int         refill_at;      // k_nr_walk's refill threshold (hook 100 + T)
+    int         lds_levels;     // stack levels per lane k_nr_walk keeps in LDS (hook 200 + K)
+    int32_t     persistent_blocks;
+    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words, and one more for the walk's work head (SR_MODE_BVH)
+    void*       sort_temp;
+    size_t      sort_temp_bytes; // point_order_temp_bytes
+    void*       prep;           // device [pass] x 64 B
+    void*       res;            // device [pass] x 16 B
+    int32_t*    deep;           // device: the stack levels beyond lds_levels, [level][lane of the grid]
+    size_t      deep_bytes;
+    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += rays, [1..3] += what their walks count
+    hipStream_t stream;
+    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
+    void*       user;
+};
+hipError_t launch_nearest(const NearestLaunch& L);
 
 // the four-wide tree collapsed from a device-resident binary tree (same rule as the host's collapse_bvh4); d_wide: >= num_nodes entries
 // level_first (nullable): the wide nodes are numbered level by level -- level L is [level_first[L], level_first[L + 1]), the last entry

@@ -3215,17 +3215,7 @@ constexpr int kWalkRefillAt = 24;        // k_bounce_walk fetches new rays when 
 // incoherent walk lives on the number of waves that wait side by side.  Only the first kBounceLdsLevels live in LDS; the deeper
 // ones (rare) in global memory, [level][lane].
 constexpr int kBounceLdsLevels = 24;     // C5, four bounces: all 59 levels in LDS 44.1 ms, 32: 41.1, 24: 41.0, 16: 44.1, 12: 44.1
-struct SplitStack {
-    int32_t* lds;        // &lds[threadIdx], stride 256
-    int32_t* deep;       // &deep[global lane], stride = lanes of the grid
-    int32_t  lds_levels, deep_stride;
-    __device__ __forceinline__ void put(int level, int32_t v) {
-        if (level < lds_levels) lds[level * 256] = v; else deep[(size_t)(level - lds_levels) * (size_t)deep_stride] = v;
-    }
-    __device__ __forceinline__ int32_t get(int level) const {
-        return level < lds_levels ? lds[level * 256] : deep[(size_t)(level - lds_levels) * (size_t)deep_stride];
-    }
-};
+// (SplitStack: sr_trace.h)
 
 __global__ __launch_bounds__(256) void k_bounce_prep(DevScene sc, const HitRec* __restrict__ qin, const unsigned int* __restrict__ qin_count,
                                                      const unsigned int* __restrict__ order, BounceRay* __restrict__ prep, BounceHit* __restrict__ res) {

@@ -194,6 +194,19 @@ struct Stack {
     __device__ __forceinline__ void put(int level, int32_t v) { base[level * stride] = v; }
     __device__ __forceinline__ int32_t get(int level) const { return base[level * stride]; }
 };
+// The stack of the persistent-lane walks (k_bounce_walk, k_nr_walk): the first lds_levels levels in LDS, the deeper ones (rare) in global
+// memory, [level][lane of the grid].
+struct SplitStack {
+    int32_t* lds;        // &lds[threadIdx], stride 256
+    int32_t* deep;       // &deep[global lane], stride = lanes of the grid
+    int32_t  lds_levels, deep_stride;
+    __device__ __forceinline__ void put(int level, int32_t v) {
+        if (level < lds_levels) lds[level * 256] = v; else deep[(size_t)(level - lds_levels) * (size_t)deep_stride] = v;
+    }
+    __device__ __forceinline__ int32_t get(int level) const {
+        return level < lds_levels ? lds[level * 256] : deep[(size_t)(level - lds_levels) * (size_t)deep_stride];
+    }
+};
 
 // --------------------------------------------------------------------------------------------------
 // SpatialSubdivision.IntersectRay -- literal traversal of the reference tree

@@ -520,6 +520,20 @@ public:
         sr_check(sr_occluded_rays(scene_, SR_TARGET_ROOT | Mode(), n, starts, dirs, limits, occluded,
                                   (endpoints ? SR_RAYS_ENDPOINTS : 0u) | (coherent ? SR_RAYS_COHERENT : 0u), nullptr));
     }
+    // The nearest hit of n rays of the caller's within a distance (sr_nearest_rays): IntersectRay(starts[i], D_i) on the root geometry of the
+    // chain where it hits with rayFrac <= limits[i] (limits == nullptr: no limit), a miss (hit 0, zeros, tri_index -1) otherwise, bit for bit, on
+    // the walk a mirror level's rays take.  D_i = dirs[i], or with endpoints dirs[i] - starts[i]; every output may be nullptr; coherent: the rays
+    // are walked in the order given (SR_RAYS_COHERENT).  Reflections, refractions, gathers, a second bounce.  Does nothing without a model
+    void NearestRays(int64_t n, const double* starts, const double* dirs, const double* limits, uint8_t* hit, double* ray_frac, double* pos, double* normal,
+                     uint32_t* color, int32_t* tri_index, bool endpoints = false, bool coherent = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel()) return;
+        PreCalculate();                                    // the model and the tree of Mode() are in the scene
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_check(sr_nearest_rays(scene_, SR_TARGET_ROOT | Mode(), n, starts, dirs, limits, hit, ray_frac, pos, normal, color, tri_index,
+                                 (endpoints ? SR_RAYS_ENDPOINTS : 0u) | (coherent ? SR_RAYS_COHERENT : 0u), nullptr));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

@@ -595,6 +595,36 @@ class GpuScene:
         _check(_lib.lib().sr_occluded_rays_device(self._h, int(target), int(n), _vp(d_starts), _vp(d_dirs), _vp(d_limits), _vp(d_occluded),
                                                   self._ray_options(endpoints, coherent), _stream(stream), _vp(d_stats_ptr)))
 
+    # ---- nearest-hit ray batches with a distance limit (sr_nearest_rays) ----
+    def nearest(self, target, starts, dirs, limits=None, endpoints=False, coherent=False, stats=False):
+        """trace(target, starts, D) where that is a hit with ray_frac <= limit, trace()'s miss otherwise (limits None: no limit), on the walk the
+        library keeps for incoherent rays: a dict with trace()'s keys (with stats=True also the four counters, `stats`).  D = dirs, or
+        dirs - starts with endpoints=True (dirs are end points)."""
+        starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = starts.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("dirs has %d entries for %d rays" % (dirs.shape[0], n))
+        if limits is not None:
+            limits = np.ascontiguousarray(limits, dtype=np.float64).reshape(-1)
+            if limits.size != n:
+                raise ValueError("limits has %d entries for %d rays" % (limits.size, n))
+        res = _hit_arrays(n)
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        _check(_lib.lib().sr_nearest_rays(self._h, int(target), n, _p(starts), _p(dirs), _p(limits), _p(res["hit"]), _p(res["ray_frac"]), _p(res["pos"]),
+                                          _p(res["normal"]), _p(res["color"]), _p(res["tri_index"]), self._ray_options(endpoints, coherent), _p(st)))
+        if stats:
+            res["stats"] = st
+        return res
+
+    def nearest_device(self, target, n, d_starts, d_dirs, d_limits=0, d_hit=0, d_ray_frac=0, d_pos=0, d_normal=0, d_color=0, d_tri_index=0, endpoints=False,
+                       coherent=False, stream=0, d_stats_ptr=None):
+        """sr_nearest_rays_device: every array is a DEVICE pointer (d_limits 0 / None: no limit; an output 0 / None: not wanted); enqueued on
+        `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
+        _check(_lib.lib().sr_nearest_rays_device(self._h, int(target), int(n), _vp(d_starts), _vp(d_dirs), _vp(d_limits), _vp(d_hit), _vp(d_ray_frac),
+                                                 _vp(d_pos), _vp(d_normal), _vp(d_color), _vp(d_tri_index), self._ray_options(endpoints, coherent),
+                                                 _stream(stream), _vp(d_stats_ptr)))
+
     # ---- the colour light field for caller-given rays (sr_light_field_rays) ----
     def light_field_rays(self, frame, starts, dirs, want_inside=True):
         """LightFieldColorMethod.IntersectRay for n lines of the caller's (sr_light_field_rays): (out uint32 [n], inside uint8 [n] or None,

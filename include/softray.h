@@ -1023,7 +1023,8 @@ enum {
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid
                                     too (its loop form spills registers: opt-in); 84 the persistent shaft walk hands its tiles out in natural order
                                     (no longest-first lists); 830 + n: n resident workgroups per CU for it; 840 + q: a walk is long at q / 4 x the
-                                    mean; 91 the first classification round on k_shadow_cls instead of k_shadow_cls_g; 93 the shadow classification
+                                    mean; 63 the packet shaft walk's loop as it was before its scalar diet (the instantiations counted launches run; same frame,
+                                    DESIGN 5.8); 630 + n: 830 + n with that loop; 91 the first classification round on k_shadow_cls instead of k_shadow_cls_g; 93 the shadow classification
                                     computes the per-sample box exits for every hit point (no shortcut for candidate lists whose triangles all lie
                                     inside the root box); 94 production path, and a frame rendered with ray statistics leaves the census of that
                                     shortcut in statistics [22] (hit points classified with the shortcut) and [23] (with the per-sample box exits)

@@ -12,6 +12,11 @@ v_readlane / v_writelane (SGPR spills to VGPR lanes), and the VOTE PAIRS
 __ballot(a && b) costs on this toolchain (sr_device.h, vote helpers) -- with the loop each pair sits in.  A loop is named by the label of
 its header, innermost first; "node128" = a block of the loop reads a 128-byte node with scalar loads, i.e. the walk loop of the packet
 walks.  Without --all only the headline instantiations are listed in full, the others in one line each.
+
+For a headline instantiation every node128 loop also gets its static INSTRUCTION MIX (all blocks of the loop, nested loops included), by
+mnemonic class only: scalar ALU, scalar memory, branches, s_nop, s_waitcnt -- the scalar side: one scalar unit serves the four SIMDs of
+a CU -- then vector moves, other vector instructions, vector memory / LDS.  Static counts: a loop that gains branches to
+skip work may count more and execute less; the SQ_INSTS_* counters are the executed side (profiles/r10_scalar_walks).
 """
 import argparse
 import os
@@ -24,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "softray_amd", "csrc")
 KERNELS = ("k_shaft_pkt4", "k_primary", "k_shadow_cls_g")
 # the instantiations the default frames run (every KNOWN subset of the light / both forms of the camera-ordered copy): listed pair by pair
-HEADLINE = re.compile(r"^(k_shaft_pkt4<false, 6, true, \d(?:, (?:true|false))?>|k_primary<2, false, false, false, [23], false>|k_shadow_cls_g<false, false>)$")
+HEADLINE = re.compile(r"^(k_shaft_pkt4<false, 6, true, \d(?:, (?:true|false)){0,2}>|k_primary<2, false, false, false, [23], false>|k_shadow_cls_g<false, false>)$")
 
 
 def makefile_flags():
@@ -55,11 +60,35 @@ CNDMASK01 = re.compile(r"^\s*(v\d+), 0, 1, (s\[\d+:\d+\]|vcc)\s*$")
 CMPNE0 = re.compile(r"^\s*(?:vcc|s\[\d+:\d+\]), 0, (v\d+)\s*$")
 
 
+MIX_CLASSES = ("scalar ALU", "scalar memory", "branches", "s_nop", "s_waitcnt", "vector moves", "other vector", "vector memory / LDS")
+SCALAR_SIDE = MIX_CLASSES[:5]
+
+
+def mix_class(op):
+    """Class of an instruction by its mnemonic alone (no operands looked at)."""
+    if op == "s_nop":
+        return "s_nop"
+    if op.startswith("s_waitcnt"):
+        return "s_waitcnt"
+    if op.startswith(("s_branch", "s_cbranch", "s_setpc", "s_swappc", "s_call")):
+        return "branches"
+    if op.startswith(("s_load_", "s_buffer_load_", "s_scratch_load_")):
+        return "scalar memory"
+    if op.startswith("s_"):
+        return "scalar ALU"
+    if op.startswith("v_mov_"):
+        return "vector moves"
+    if op.startswith("v_"):
+        return "other vector"
+    return "vector memory / LDS"
+
+
 def census(lines):
     """lines: the body of one function.  Returns counts and the list of (pair line, loop label chain)."""
     # loops: LLVM's asm printer comments every block with the loop it is in: "=>This Loop Header: Depth=d", "Parent Loop BBx_y Depth=d",
     # "in Loop: Header=BBx_y Depth=d" (innermost loop of a non-header block)
     valu = salu = lanes = 0
+    mix = {}                            # block -> {class of MIX_CLASSES: instructions}
     block, block_loop = None, {}        # label -> innermost loop header label ('' outside loops)
     header_parent = {}                  # loop header -> parent header
     loaded = {}                         # block -> dwords it reads with scalar loads
@@ -90,6 +119,9 @@ def census(lines):
         m = INSN.match(ln)
         if m:
             op, args = m.group(1), m.group(2).split(";")[0]
+            if block:
+                per = mix.setdefault(block, {})
+                per[mix_class(op)] = per.get(mix_class(op), 0) + 1
             if op.startswith("v_"):
                 valu += 1
                 if op.startswith(("v_readlane", "v_writelane")):
@@ -130,7 +162,16 @@ def census(lines):
         if n >= 32 and block_loop.get(b):
             node_loops.add(block_loop[b])
     lanes_in_walk = sum(1 for b in lane_blocks if any(h in node_loops for h in chain(b)))
-    return valu, salu, lanes, lanes_in_walk, [(b, chain(b)) for b in pairs], node_loops
+    # instruction mix of every node-loading loop: all blocks of the loop, those of the loops nested in it included
+    loop_mix = {}
+    for h in node_loops:
+        tot = dict.fromkeys(MIX_CLASSES, 0)
+        for b, per in mix.items():
+            if h in chain(b):
+                for k, v in per.items():
+                    tot[k] += v
+        loop_mix[h] = tot
+    return valu, salu, lanes, lanes_in_walk, [(b, chain(b)) for b in pairs], node_loops, loop_mix
 
 
 def main():
@@ -166,7 +207,7 @@ def main():
     print("# kernel | VGPR / SGPR / spilled V / spilled S / scratch B / occupancy | static VALU / SALU | v_readlane+v_writelane (in node128 walk loops) | vote pairs (in node128 walk loops)")
     for mangled in sorted(funcs, key=lambda k: pretty[k]):
         s, e, res = funcs[mangled]
-        valu, salu, lanes, lanes_in_walk, pairs, node_loops = census(lines[s:e])
+        valu, salu, lanes, lanes_in_walk, pairs, node_loops, loop_mix = census(lines[s:e])
         ss, vs = spills.get(mangled, (-1, -1))
         in_walk = sum(1 for _, ch in pairs if any(h in node_loops for h in ch))
         print("%s | %d / %d / %d / %d / %d / %d | %d / %d | %d (%d) | %d (%d)" % (
@@ -176,6 +217,10 @@ def main():
             for b, ch in pairs:
                 where = " < ".join("%s%s" % (h, " [node128]" if h in node_loops else "") for h in ch) or "outside every loop"
                 print("    pair in block %s: %s" % (b, where))
+            for h in sorted(loop_mix):
+                tot = loop_mix[h]
+                print("    loop %s [node128] holds %d instructions, %d on the scalar side: %s" % (
+                    h, sum(tot.values()), sum(tot[k] for k in SCALAR_SIDE), ", ".join("%s %d" % (k, tot[k]) for k in MIX_CLASSES)))
     return 0
 
 

@@ -1248,7 +1248,9 @@ __device__ __forceinline__ void shaft_slabs(const Bvh4Child& ch, f2 Ixy, f2 Izz,
 // --------------------------------------------------------------------------------------------------
 // CONES: the triangle filter reads the frame's LightCone records (shaft_cones_wave) instead of the TriSlab records (shaft_touches_wave;
 // SR_DBG_KERNEL_SWITCH 96, or no room for the records): same verdicts where it matters -- a superset of the hitting pairs, umbra only where proven.
-template <bool STATS, int WAVES, bool PERSIST, int KNOWN = 0, bool CONES = false>
+// LEAN: the walk loop with fewer scalar instructions per node step and record (profiles/r10_scalar_walks) -- same loads, same
+// lanes, same verdicts; !LEAN is the loop as it was (counted launches and SR_DBG_KERNEL_SWITCH 63, the A/B).
+template <bool STATS, int WAVES, bool PERSIST, int KNOWN = 0, bool CONES = false, bool LEAN = false>
 __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, FrameConst fc_arg, HintArgs hint_arg, const HitRec* __restrict__ hits,
                                                     const unsigned int* __restrict__ hit_count, int cap, int levels, int tile_n2, int tile_rows,
                                                     unsigned int* __restrict__ cand_count, int32_t* __restrict__ cand,
@@ -1416,8 +1418,10 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
         shaft_slabs<KNOWN>(n.ch[3], Ixy, Izz, B0, B1, B2, a3, b3);
         b0 = fminf(b0, nu); b1 = fminf(b1, nu); b2 = fminf(b2, nu); b3 = fminf(b3, nu);
         // the lanes whose shaft touches child k's box; `& ~done_m` where a mask is used: lanes drop out in the leaves
-        const lanemask h0 = lanes_if(n.ch[0].n >= 0) & vote(fmaxf(a0, umin) <= b0), h1 = lanes_if(n.ch[1].n >= 0) & vote(fmaxf(a1, umin) <= b1);
-        const lanemask h2 = lanes_if(n.ch[2].n >= 0) & vote(fmaxf(a2, umin) <= b2), h3 = lanes_if(n.ch[3].n >= 0) & vote(fmaxf(a3, umin) <= b3);
+        // (an empty slot, n < 0, needs no mask of its own: h_k is only read where n_k > 0 -- the leaf blocks -- or n_k == 0 -- the inner children;
+        //  !LEAN keeps the three scalar instructions per slot that cleared it, for the A/B)
+        const lanemask h0 = (LEAN ? ~0ull : lanes_if(n.ch[0].n >= 0)) & vote(fmaxf(a0, umin) <= b0), h1 = (LEAN ? ~0ull : lanes_if(n.ch[1].n >= 0)) & vote(fmaxf(a1, umin) <= b1);
+        const lanemask h2 = (LEAN ? ~0ull : lanes_if(n.ch[2].n >= 0)) & vote(fmaxf(a2, umin) <= b2), h3 = (LEAN ? ~0ull : lanes_if(n.ch[3].n >= 0)) & vote(fmaxf(a3, umin) <= b3);
         // ---- leaf children in slot order: every interested lane filters the (broadcast) triangles with its own shaft.  Four copies of
         //      the filter loop (one per slot, everything static) rather than one loop over a slot index: selecting a slot's count, link
         //      and lane mask by a run-time index costs a chain of scalar branches per slot and step ----
@@ -1433,6 +1437,9 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
                     const TriSlab s = load_uniform(&sc_arg.bslab[cc + q]); // scalar load
                     shaft_touches_wave(s, sr, hc & ~done_m, take_m, in_umbra_m);
                 }
+                // no lane takes the record, none lies in its umbra (most records of a leaf, for most tiles): the list, the three masks and the
+                // hint stay as they are -- go on to the next record without the dozen scalar instructions that would say so
+                if (LEAN && (take_m | in_umbra_m) == 0ull) continue;
                 const lanemask room_m = vote(count < cap);
                 if (lane_of(take_m & room_m)) out[count] = cc + q;
                 count += lane_of(take_m & room_m) ? 1 : 0;
@@ -1455,7 +1462,19 @@ __global__ __launch_bounds__(256, WAVES) void k_shaft_pkt4(DevScene sc_arg, Fram
             if (has_top) { wnode[sp] = top_ni; wbound[sp * 64] = (uint16_t)top_b; sp++; }      // the old top moves to LDS
             top_ni = pn; top_b = (uint32_t)enc(pu); has_top = true;
         };
-        {
+        if constexpr (LEAN) {
+            // the slot's kind first, as a scalar branch (most slots of the lowest inner level are leaves), then the lanes that want it
+            const auto inner = [&](const int32_t cc, const lanemask h, const float b) __attribute__((always_inline)) {
+                const lanemask w = h & ~done_m;
+                if (w == 0ull) return;
+                if (next >= 0) push(next, next_u);
+                next = cc; next_u = lane_of(w) ? b : -1.0f;
+            };
+            if (n.ch[3].n == 0) inner(n.ch[3].c, h3, b3);
+            if (n.ch[2].n == 0) inner(n.ch[2].c, h2, b2);
+            if (n.ch[1].n == 0) inner(n.ch[1].c, h1, b1);
+            if (n.ch[0].n == 0) inner(n.ch[0].c, h0, b0);
+        } else {
             const lanemask w3 = lanes_if(n.ch[3].n == 0) & h3 & ~done_m;
             if (w3 != 0ull) { next = n.ch[3].c; next_u = lane_of(w3) ? b3 : -1.0f; }
             const lanemask w2 = lanes_if(n.ch[2].n == 0) & h2 & ~done_m;
@@ -5901,7 +5920,8 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
                 if (tn2 > 0) blocks = (unsigned)(xcd_tile_grid(L.fc.width, trows) * tn2);      // the grid of k_primary (x sub-samples)
                 unsigned int* heads;
                 const unsigned vblocks = blocks;
-                blocks = tile_grid(L, vblocks, (L.fc.debug >= 830 && L.fc.debug <= 836) ? L.fc.debug - 830 : (L.shaft_wgs_per_cu > 0 ? L.shaft_wgs_per_cu : 6), L.counters + kHeadsShaft, &heads);          // ... or the resident grid pulling its tiles (hook 830 + n: n workgroups per CU)
+                const bool hook63x = L.fc.debug >= 630 && L.fc.debug <= 636;          // (hook 630 + n: hook 830 + n together with switch 63, see `lean` below)
+                blocks = tile_grid(L, vblocks, (L.fc.debug >= 830 && L.fc.debug <= 836) ? L.fc.debug - 830 : (hook63x ? L.fc.debug - 630 : (L.shaft_wgs_per_cu > 0 ? L.shaft_wgs_per_cu : 6)), L.counters + kHeadsShaft, &heads);          // ... or the resident grid pulling its tiles (hook 830 + n: n workgroups per CU)
                 // (persistent) longest walks first: the lists k_tile_order made from the previous frame's walk lengths, if that frame had this tile grid
                 const unsigned long long order_tag = ((unsigned long long)vblocks << 32) | ((unsigned long long)(unsigned)L.fc.width << 12) | (unsigned long long)(unsigned)tn2;
                 const bool keep_cost = heads && L.tile_cost && L.tile_order && L.tile_order_tag && L.fc.debug != 84;
@@ -5922,13 +5942,16 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
                 // ((near, far) planes in the light-ordered copy, as in the camera-ordered one, were measured: fewer instructions, more spills at
                 //  this kernel's register budget -- 5.17 -> 5.30 ms; 5.49 ms at 5 waves/SIMD)
                 // one instantiation per set of axes on which the light-ordered copy holds (near, far) planes (the light lies outside the root box there)
+                // the loop with fewer scalar instructions per step (LEAN) unless the launch is counted or SR_DBG_KERNEL_SWITCH 63 / hook 630 + n asks for the
+                // loop as it was (the A/B)
+                const bool lean = !L.stats && L.fc.debug != 63 && !hook63x;
                 const auto go_known = [&](auto known) {
                     constexpr int K = decltype(known)::value;
                     if (L.sc.blight) {                         // the frame's penumbra-plane records are there: filter with them
-                        if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K, true>); else go(k_shaft_pkt4<false, 6, true, K, true>); }
-                        else { if (L.stats) go(k_shaft_pkt4<true, 6, false, K, true>); else go(k_shaft_pkt4<false, 6, false, K, true>); }
-                    } else if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K>); else go(k_shaft_pkt4<false, 6, true, K>); }
-                    else { if (L.stats) go(k_shaft_pkt4<true, 6, false, K>); else go(k_shaft_pkt4<false, 6, false, K>); }
+                        if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K, true>); else if (lean) go(k_shaft_pkt4<false, 6, true, K, true, true>); else go(k_shaft_pkt4<false, 6, true, K, true>); }
+                        else { if (L.stats) go(k_shaft_pkt4<true, 6, false, K, true>); else if (lean) go(k_shaft_pkt4<false, 6, false, K, true, true>); else go(k_shaft_pkt4<false, 6, false, K, true>); }
+                    } else if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K>); else if (lean) go(k_shaft_pkt4<false, 6, true, K, false, true>); else go(k_shaft_pkt4<false, 6, true, K>); }
+                    else { if (L.stats) go(k_shaft_pkt4<true, 6, false, K>); else if (lean) go(k_shaft_pkt4<false, 6, false, K, false, true>); else go(k_shaft_pkt4<false, 6, false, K>); }
                 };
                 switch (L.sc.b4light_known & 7) {
                     case 1: go_known(std::integral_constant<int, 1>()); break;

@@ -684,8 +684,10 @@ __device__ bool bvh4_packet_nearest(const DevScene& sc, int32_t* wnode, bool liv
             child_slabs<KNOWN>(n.ch[1], I01, I20, I12, B0, B1, B2, t1, x1);
             child_slabs<KNOWN>(n.ch[2], I01, I20, I12, B0, B1, B2, t2, x2);
             child_slabs<KNOWN>(n.ch[3], I01, I20, I12, B0, B1, B2, t3, x3);
-            const lanemask h0 = act_m & lanes_if(n.ch[0].n >= 0) & vote(t0 <= x0) & vote(x0 >= 0.0f), h1 = act_m & lanes_if(n.ch[1].n >= 0) & vote(t1 <= x1) & vote(x1 >= 0.0f);
-            const lanemask h2 = act_m & lanes_if(n.ch[2].n >= 0) & vote(t2 <= x2) & vote(x2 >= 0.0f), h3 = act_m & lanes_if(n.ch[3].n >= 0) & vote(t3 <= x3) & vote(x3 >= 0.0f);
+            // (no term for an empty slot, n < 0: h_k is only read where n_k > 0 -- the leaf blocks -- or n_k == 0 -- the inner children below;
+            //  clearing it took three scalar instructions per slot and step)
+            const lanemask h0 = act_m & vote(t0 <= x0) & vote(x0 >= 0.0f), h1 = act_m & vote(t1 <= x1) & vote(x1 >= 0.0f);
+            const lanemask h2 = act_m & vote(t2 <= x2) & vote(x2 >= 0.0f), h3 = act_m & vote(t3 <= x3) & vote(x3 >= 0.0f);
             // ---- leaf children in slot order (front to back for this origin).  One copy of the triangle loop per slot, everything
             //      static: picking a slot's count / link / lane mask by a run-time index costs a chain of scalar branches per slot ----
             const auto leaf = [&](const int cn, const int cc, const lanemask h, const float t) __attribute__((always_inline)) {

@@ -126,6 +126,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_occluded_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, IntPtr dOccluded, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_nearest_rays(IntPtr scene, int target, long n, [In] double[] starts, [In] double[] dirs, [In] double[] limits, [Out] byte[] hit, [Out] double[] rayFrac, [Out] double[] pos, [Out] double[] normal, [Out] uint[] color, [Out] int[] triIndex, uint options, [Out] ulong[] stats4);
         [DllImport(Lib)] public static extern int sr_nearest_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, uint options, IntPtr hipStream, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_all_hits_rays(IntPtr scene, int target, long n, [In] double[] starts, [In] double[] dirs, [In] double[] limits, int maxHits, [Out] uint[] count, [Out] int[] index, [Out] double[] rayFrac, uint options, [Out] ulong[] stats4);
+        [DllImport(Lib)] public static extern int sr_all_hits_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, int maxHits, IntPtr dCount, IntPtr dIndex, IntPtr dRayFrac, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -687,6 +689,33 @@ namespace Engine3D.Hip
         {
             Native.Check(Native.sr_nearest_rays_device(scene, mode | (root ? 0x100 : 0), n, dStarts, dDirs, dLimits, dHit, dRayFrac, dPos, dNormal, dColor,
                                                        dTriIndex, (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), stream, dStats));
+        }
+
+        /// Every hit along each ray of a batch, nearest first, with a count (sr_all_hits_rays).  Count[i]: the hits with rayFrac &lt;= limits[i]
+        /// (limits == null: no limit), not capped by maxHits; rows i of Index / RayFrac ([n * maxHits]) hold the first min(count, maxHits) of them
+        /// by (rayFrac, extra elements first, index) -- TriangleIndex, or -2 - e for extra element e -- and -1 / 0.0 in the unused slots.
+        /// mode is MODE_BVH or MODE_BRUTE (the literal reference tree has no notion of all hits).  Blocks.
+        public const int HITS_MAX = 64;
+        public sealed class RayHitLists { public int MaxHits; public uint[] Count; public int[] Index; public double[] RayFrac; public ulong[] Stats4; }
+        public RayHitLists AllHitRays(double[] starts, double[] dirs, double[] limits, int maxHits, int mode, bool root = false, bool endpoints = false,
+                                      bool coherent = false)
+        {
+            long n = starts.Length / 3;
+            var r = new RayHitLists { MaxHits = maxHits, Count = new uint[n], Index = new int[n * Math.Max(0, maxHits)],
+                                      RayFrac = new double[n * Math.Max(0, maxHits)], Stats4 = new ulong[4] };
+            Native.Check(Native.sr_all_hits_rays(scene, mode | (root ? 0x100 : 0), n, starts, dirs, limits, maxHits, r.Count, r.Index, r.RayFrac,
+                                                 (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), r.Stats4));
+            return r;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_all_hits_rays_device), dLimits IntPtr.Zero for no limit and
+        /// IntPtr.Zero for an output that is not wanted (dCount IntPtr.Zero with maxHits &gt; 0: a K-nearest query); enqueued on `stream` without a
+        /// host synchronisation; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void AllHitRaysDevice(long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, int maxHits, int mode, bool root, bool endpoints, bool coherent,
+                                     IntPtr dCount, IntPtr dIndex, IntPtr dRayFrac, IntPtr stream, IntPtr dStats)
+        {
+            Native.Check(Native.sr_all_hits_rays_device(scene, mode | (root ? 0x100 : 0), n, dStarts, dDirs, dLimits, maxHits, dCount, dIndex, dRayFrac,
+                                                        (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), stream, dStats));
         }
 
         /// ShadingMethod's colour step for n recorded intersections in DEVICE memory (sr_shade_points_device): dOut[i] = dColor[i] modulated with

@@ -697,6 +697,55 @@ int  sr_nearest_rays_device(sr_scene*, int32_t target, int64_t n, const double* 
                             uint8_t* d_hit, double* d_ray_frac, double* d_pos, double* d_normal, uint32_t* d_color, int32_t* d_tri_index,
                             uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
+/* ALL HITS along each ray of a batch, nearest first, with a count: what transparency and X-ray compositing, thickness and path length inside a
+ * solid, inside/outside classification, CSG and picking through layers ask -- without peeling (K calls of sr_nearest_rays with an epsilon).
+ * Direction and options: as sr_occluded_rays / sr_nearest_rays (SR_RAYS_COHERENT, SR_RAYS_ENDPOINTS; D_i = dirs[i], or dirs[i] - starts[i] with
+ * one FP64 subtraction per component).
+ * The hit set of ray i.  SR_MODE_BVH: every triangle j whose record passes the per-record test of the own BVH's walk -- the start clipped to
+ * the root box (ClipLineSegment), offset = |original - s| / |D|, then Triangle.IntersectRay(rec_j, s, D) with the hit position strictly inside
+ * the root box; its ray_frac is the one FP64 sum t + offset.  Equivalently: j is in the set iff a scene that holds triangle j alone, in the
+ * same box, answers the ray with a hit, and ray_frac is that answer's.  SR_MODE_BRUTE: the per-record loop of GeometryCollection --
+ * Triangle.IntersectRay from the unclipped start, ray_frac = t, no box test.  Triangles are one-sided, as everywhere.  SR_TARGET_ROOT | mode:
+ * every element e of the extra geometry adds at most one hit, its own IntersectRay answer from the unclipped start (a rayFrac of DBL_MAX or
+ * more does not count), reported with index = -2 - e.  SR_MODE_REF_TREE is SR_ERR_UNSUPPORTED: the literal walk ends in the first leaf that
+ * holds a hit inside its box, a triangle lives in several leaves, and "all hits" is not a notion of SpatialSubdivision.  SR_TARGET_VOXELS is
+ * SR_ERR_UNSUPPORTED as in the sibling calls.
+ * A hit QUALIFIES iff ray_frac <= limit_i (IEEE <=).  A NaN, -inf or negative limit qualifies nothing, +inf every hit whose ray_frac is a number.
+ * limits == NULL: no limit -- no comparison is made, as in sr_nearest_rays: an irregular ray whose ray_frac is NaN (offset 0 / 0) still counts, and
+ * sorts behind every number.
+ * Outputs: count[i] = the number of qualifying hits, NOT capped by max_hits (K).  Row i of index / ray_frac ([n][K]) holds the min(count, K)
+ * qualifying hits that come first in the order: ray_frac ascending; at equal ray_frac extra elements before triangles; then element /
+ * TriangleIndex ascending.  Every remaining slot of every row is written: index -1, ray_frac 0.0 -- the caller clears nothing.  The order is
+ * defined on the reported values.  Relations: count > 0 equals sr_occluded_rays with the same explicit limits; ray_frac[i][0] and count > 0
+ * equal sr_nearest_rays' ray_frac and hit; index[i][0] equals its tri_index whenever no other qualifying hit shares that ray_frac
+ * (sr_trace_rays breaks ties on t, before the offset is added).
+ * NULL arrays: max_hits == 0 is the counting call (index and ray_frac are ignored).  Any of the three arrays may be NULL; all NULL: the call
+ * runs for the statistics.  A row the caller does not ask for is kept in the scene's first scratch set (ray_frac is needed for the order), in
+ * passes of at most 2^24 / K rays.  With count == NULL and K > 0 the walk culls every box beyond the K-th hit it holds -- a K-nearest query --
+ * with count != NULL only beyond limit - offset; the rows are bit for bit the same either way.  The cull bound is bvh_intersect<true>'s,
+ * (float)(bound - offset) * (1 + 2^-20) + 1e-30f, with the FP64 room widened by 2^-51 (|bound| + offset) first.
+ * Routing in SR_MODE_BVH: a ray that is REGULAR by sr_occluded_rays' definition walks the tree (k_ah_walk) in a pass ordered by start cell and
+ * direction octant (SR_RAYS_COHERENT: input order).  Every other ray -- a zero, NaN, +-inf, 1e+-300 direction, a non-finite start, a
+ * zero-length segment, a NaN or -inf limit -- goes to the end of its pass and runs the per-record loop (k_ah_loop): the same FP64 predicate over
+ * every record, no fp32 stage, O(triangles) per ray.  SR_MODE_BRUTE runs that loop (unclipped) for every ray in input order.
+ * Refusals, in this order: a NULL scene, n < 0, NULL starts / dirs with n > 0, max_hits outside 0 .. SR_HITS_MAX, unknown option bits:
+ * SR_ERR_INVALID_ARG; SR_TARGET_VOXELS: SR_ERR_UNSUPPORTED; SR_MODE_REF_TREE: SR_ERR_UNSUPPORTED; sr_trace_rays' own checks (SR_ERR_NO_MODEL,
+ * SR_ERR_NOT_BUILT); a host-only scene: SR_ERR_NO_DEVICE.  n == 0 that passes all of them: SR_OK, nothing is touched.
+ * State: as sr_nearest_rays -- no per-origin or per-light record is rewritten, the call is ordered like a frame.  Passes of at most 2^22 rays
+ * (SR_DBG_BAND_SAMPLES: fewer) follow each other without the host waiting.  A multi-device scene runs the call on devices[0].  The host variant
+ * stages 24 n + 24 n + 8 n bytes in and 4 n + 12 K n bytes out through the scene's device buffers, blocks and fills sr_last_ray_stats; the
+ * device variant enqueues on `hip_stream` without a host synchronisation.  Statistics: [0] = n; [1..3] what the walks fetched (in brute force
+ * the sums of the per-record tests); [4..] 0. */
+#define SR_HITS_MAX 64
+int  sr_all_hits_rays(sr_scene*, int32_t target, int64_t n, const double* starts, const double* dirs,
+                      const double* limits /* [n], or NULL: no limit */, int32_t max_hits /* K, 0..SR_HITS_MAX */,
+                      uint32_t* count /* [n] or NULL */, int32_t* index /* [n][K] or NULL */, double* ray_frac /* [n][K] or NULL */,
+                      uint32_t options, uint64_t stats[4] /* or NULL */);
+int  sr_all_hits_rays_device(sr_scene*, int32_t target, int64_t n, const double* d_starts, const double* d_dirs,
+                             const double* d_limits /* or NULL */, int32_t max_hits,
+                             uint32_t* d_count /* or NULL */, int32_t* d_index /* or NULL */, double* d_ray_frac /* or NULL */,
+                             uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* ShadingMethod.IntersectRay's colour step in batch (ShadingMethod.cs:36-68 -> CalcLighting :110-177): for n recorded
  * intersections out[i] = ModulatePackedColor(color[i], (byte)(255 * intensity)) with the frame's transform and lights (only the
  * matrices, position_z, fov_depth, lights, ambient, shininess and the POINT_LIGHT / SPECULAR flags of `frame` are read).
@@ -1017,7 +1066,9 @@ enum {
                                     persistent lanes that fetch new rays at T busy lanes (same output; faster on incoherent batches, slower on short coherent walks: DESIGN 5.28); 48 sr_nearest_rays walks a pass
                                     in input order whatever the options say (no ray sort); 49 sr_nearest_rays answers every ray with one private walk per lane (k_nr_lane) in input
                                     order, also in SR_MODE_BVH (same output; baseline and cross-check); 100 + T and 200 + K also set the refill threshold and the LDS
-                                    stack levels of sr_nearest_rays' walk kernel, as the bounce walk reads them below; 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    stack levels of sr_nearest_rays' walk kernel, as the bounce walk reads them below; 50 sr_all_hits_rays walks a pass in input order whatever the options say
+                                    (no ray sort); 51 sr_all_hits_rays answers every ray of SR_MODE_BVH with the per-record loop of its irregular rays (both: same output;
+                                    cross-check); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
                                     fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid

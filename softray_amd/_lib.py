@@ -57,10 +57,12 @@ SYMBOLS = [
     "sr_occluded_rays", "sr_occluded_rays_device",
     "sr_nearest_rays", "sr_nearest_rays_device",
     "sr_light_field_rays", "sr_light_field_rays_device",
+    "sr_all_hits_rays", "sr_all_hits_rays_device",
 ]
 POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 RAYS_COHERENT = 1                      # SR_RAYS_COHERENT
-RAYS_ENDPOINTS = 2                     # SR_RAYS_ENDPOINTS (sr_occluded_rays, sr_nearest_rays)
+RAYS_ENDPOINTS = 2                     # SR_RAYS_ENDPOINTS (sr_occluded_rays, sr_nearest_rays, sr_all_hits_rays)
+HITS_MAX = 64                          # SR_HITS_MAX (sr_all_hits_rays)
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
 # sr_debug_set keys (include/softray.h)
@@ -190,6 +192,8 @@ def lib():
     L.sr_occluded_rays_device.restype = i32; L.sr_occluded_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_nearest_rays.restype = i32; L.sr_nearest_rays.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp]
     L.sr_nearest_rays_device.restype = i32; L.sr_nearest_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
+    L.sr_all_hits_rays.restype = i32; L.sr_all_hits_rays.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, C.c_uint32, vp]
+    L.sr_all_hits_rays_device.restype = i32; L.sr_all_hits_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_light_field_rays.restype = i32; L.sr_light_field_rays.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp]
     L.sr_light_field_rays_device.restype = i32; L.sr_light_field_rays_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.sr_rccl_unique_id.restype = i32; L.sr_rccl_unique_id.argtypes = [vp]

@@ -3328,6 +3328,119 @@ int sr_nearest_rays(sr_scene* m, int32_t target, int64_t n, const double* starts
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// All hits along a ray, nearest first, with a count (sr_all_hits_rays): the walk that never stops at the first hit
+// ------------------------------------------------------------------------------------------------------------------
+// what sr_all_hits_rays[_device] refuses, in the header's order; `s`: the scene that runs the call (the first part of a multi-device scene)
+static int all_hits_check(sr_scene*& s, int32_t target, int64_t n, const void* starts, const void* dirs, int32_t max_hits, uint32_t options, int& mode,
+                          bool& with_extra) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: the scene is NULL");
+    if (n < 0) return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: n is negative");
+    if (n > 0 && (!starts || !dirs)) return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: starts and dirs must not be NULL when n > 0");
+    if (max_hits < 0 || max_hits > SR_HITS_MAX) return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: max_hits must be 0 .. SR_HITS_MAX (64)");
+    if (options & ~(uint32_t)(SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS))
+        return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)");
+    if (target & SR_TARGET_VOXELS)
+        return fail(SR_ERR_UNSUPPORTED, "sr_all_hits_rays: the voxel grid (SR_TARGET_VOXELS) has no tree to walk and its hits have rayFrac 0; use sr_trace_rays");
+    with_extra = (target & SR_TARGET_ROOT) != 0;
+    mode = target & 0xff;
+    if (mode == SR_MODE_REF_TREE)
+        return fail(SR_ERR_UNSUPPORTED, "sr_all_hits_rays: SR_MODE_REF_TREE has no notion of all hits (the literal walk ends in the first leaf that holds a hit inside "
+                                        "its box, and a triangle lives in several leaves); use SR_MODE_BVH or SR_MODE_BRUTE");
+    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "sr_all_hits_rays: the scene has no model (sr_set_triangles, sr_load_3ds)");
+    int rc;
+    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays */ }
+    else if ((rc = check_mode(s, mode))) return rc;
+    if (s->device < 0) return fail(SR_ERR_NO_DEVICE, "sr_all_hits_rays: a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
+    return SR_OK;
+}
+
+struct AllHitsOut { uint32_t* count; int32_t* index; double* ray_frac; };
+
+// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set's sort buffers; a row the
+// caller does not want lives in that set's bounce buffers
+static int all_hits_common(sr_scene* s, int mode, bool with_extra, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits,
+                           int32_t max_hits, const AllHitsOut& out, uint32_t options, hipStream_t stream, unsigned long long* d_stats) {
+    int rc = sync_geometry(s, (uint32_t)mode);
+    if (rc) return rc;
+    // ---- ordered like a frame (render_common): a frame's facing partition moves the records the walk reads ----
+    StreamOrder order(s, stream);
+    if (order.entered) return order.entered;
+    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
+    int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kAllHitsMaxPass) : sr::kAllHitsMaxPass;
+    const bool own_rows = max_hits > 0 && (!out.index || !out.ray_frac);
+    if (own_rows) want = std::min<int64_t>(want, (1ll << 24) / max_hits);            // (at most 2^24 slots of scratch rows: 128 + 64 MiB)
+    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
+    sr::AllHitsLaunch L{};
+    L.sc = dev_scene(s);
+    L.mode = mode;
+    L.with_extra = with_extra && !s->extra_recs.empty();
+    L.n = n; L.pass = pass;
+    L.starts = d_starts; L.dirs = d_dirs; L.limits = d_limits;
+    L.max_hits = max_hits;
+    L.count = out.count;
+    L.index = max_hits > 0 ? out.index : nullptr;
+    L.ray_frac = max_hits > 0 ? out.ray_frac : nullptr;
+    L.endpoints = (options & SR_RAYS_ENDPOINTS) != 0;
+    L.input_order = (options & SR_RAYS_COHERENT) != 0 || hook == 50;                            // (hook: input order whatever the options say)
+    L.loop_all = hook == 51;                                                                    // (hook: every ray through the per-record loop)
+    sr_scene::BandScratch& B = s->scratch[0];
+    const size_t slots = (size_t)(pass + 255) / 256 * 256;
+    if (mode == SR_MODE_BVH) {
+        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
+        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
+        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
+        L.sort_buf = (unsigned int*)B.ray_sort.p;
+        L.sort_temp = B.ray_sort_temp.p;
+    }
+    if (max_hits > 0 && !out.index) {
+        SR_HIP(B.bounce_res.reserve(slots * (size_t)max_hits * sizeof(int32_t)));
+        L.scratch_index = (int32_t*)B.bounce_res.p;
+    }
+    if (max_hits > 0 && !out.ray_frac) {
+        SR_HIP(B.bounce_prep.reserve(slots * (size_t)max_hits * sizeof(double)));
+        L.scratch_frac = (double*)B.bounce_prep.p;
+    }
+    L.stats = d_stats;
+    L.stream = stream;
+    L.user = s;
+    L.get_events = timing_events;
+    SR_HIP(sr::launch_all_hits(L));
+    return SR_OK;
+}
+
+int sr_all_hits_rays_device(sr_scene* m, int32_t target, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits, int32_t max_hits,
+                            uint32_t* d_count, int32_t* d_index, double* d_ray_frac, uint32_t options, void* hip_stream, uint64_t* d_stats) {
+    sr_scene* s = m;
+    int mode; bool with_extra;
+    int rc = all_hits_check(s, target, n, d_starts, d_dirs, max_hits, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    const AllHitsOut out{d_count, d_index, d_ray_frac};
+    return all_hits_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, max_hits, out, options, stream, (unsigned long long*)d_stats);
+}
+
+int sr_all_hits_rays(sr_scene* m, int32_t target, int64_t n, const double* starts, const double* dirs, const double* limits, int32_t max_hits, uint32_t* count,
+                     int32_t* index, double* ray_frac, uint32_t options, uint64_t stats[4]) {
+    sr_scene* s = m;
+    int mode; bool with_extra;
+    int rc = all_hits_check(s, target, n, starts, dirs, max_hits, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    const size_t rows = (size_t)n * (size_t)max_hits;
+    Staged io[] = {{starts, nullptr, (size_t)n * 24}, {dirs, nullptr, (size_t)n * 24}, {limits, nullptr, (size_t)n * 8}, {nullptr, count, (size_t)n * 4},
+                   {nullptr, max_hits > 0 ? index : nullptr, rows * 4}, {nullptr, max_hits > 0 ? ray_frac : nullptr, rows * 8}};
+    return run_staged(m, s, io, 6, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
+        const AllHitsOut out{(uint32_t*)io[3].dev, (int32_t*)io[4].dev, (double*)io[5].dev};
+        return all_hits_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev, max_hits, out, options,
+                               stream, d_stats);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The RCCL strip gather, native: no PyTorch in the data path.
 // ------------------------------------------------------------------------------------------------------------------
 int sr_set_gather(sr_scene* m, int32_t kind) {

@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_LFR_LOOKUP = 46, K_LFR_FINISH = 47, K_LFRI_LOOKUP = 48, K_LFRI_FINISH = 49, K_NEAREST = 50, K_NEAREST_SORT = 51, K_COUNT = 52 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_LFR_LOOKUP = 46, K_LFR_FINISH = 47, K_LFRI_LOOKUP = 48, K_LFRI_FINISH = 49, K_NEAREST = 50, K_NEAREST_SORT = 51, K_ALL_HITS = 52, K_ALL_HITS_SORT = 53, K_COUNT = 54 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -461,6 +461,38 @@ struct NearestLaunch {
     void*       user;
 };
 hipError_t launch_nearest(const NearestLaunch& L);
+
+// sr_all_hits_rays (sr_allhits.hip): every qualifying hit of n caller-given rays -- count, and the first max_hits of them by (ray_frac, extra
+// elements before triangles, element / TriangleIndex) -- in passes of `pass` rays.  SR_MODE_BVH: occl_order's order, k_ah_walk for the regular
+// rays, k_ah_loop (the per-record loop) for the others; SR_MODE_BRUTE: k_ah_loop in input order
+constexpr int64_t kAllHitsMaxPass = 1ll << 22;
+constexpr int kAllHitsMax = 64;         // SR_HITS_MAX
+struct AllHitsLaunch {
+    DevScene    sc;
+    int32_t     mode;           // SR_MODE_BVH or SR_MODE_BRUTE
+    bool        with_extra;     // root geometry of the chain (extra + model)
+    int64_t     n, pass;
+    const double* starts;       // device [n][3]
+    const double* dirs;         // device [n][3]: directions, or end points (endpoints)
+    const double* limits;       // device [n] or nullptr (no limit)
+    int32_t     max_hits;       // K, 0 .. kAllHitsMax
+    uint32_t*   count;          // device [n] or nullptr (nullptr and K > 0: the walk culls at the K-th kept hit)
+    int32_t*    index;          // device [n][K] or nullptr
+    double*     ray_frac;       // device [n][K] or nullptr
+    int32_t*    scratch_index;  // device [pass][K]: a lane's row where index is nullptr (K > 0)
+    double*     scratch_frac;   // device [pass][K]: ... where ray_frac is nullptr
+    bool        endpoints;      // SR_RAYS_ENDPOINTS
+    bool        input_order;    // SR_RAYS_COHERENT / hook 50: a pass keeps its input order (the irregular rays still go last)
+    bool        loop_all;       // SR_MODE_BVH with the per-record loop for every ray (hook 51)
+    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words (SR_MODE_BVH)
+    void*       sort_temp;
+    size_t      sort_temp_bytes; // point_order_temp_bytes
+    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += rays, [1..3] += what their walks count
+    hipStream_t stream;
+    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
+    void*       user;
+};
+hipError_t launch_all_hits(const AllHitsLaunch& L);
 
 // the four-wide tree collapsed from a device-resident binary tree (same rule as the host's collapse_bvh4); d_wide: >= num_nodes entries
 // level_first (nullable): the wide nodes are numbered level by level -- level L is [level_first[L], level_first[L + 1]), the last entry

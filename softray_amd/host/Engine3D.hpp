@@ -534,6 +534,21 @@ public:
         sr_check(sr_nearest_rays(scene_, SR_TARGET_ROOT | Mode(), n, starts, dirs, limits, hit, ray_frac, pos, normal, color, tri_index,
                                  (endpoints ? SR_RAYS_ENDPOINTS : 0u) | (coherent ? SR_RAYS_COHERENT : 0u), nullptr));
     }
+    // Every hit of n rays of the caller's, nearest first, with a count (sr_all_hits_rays) on the root geometry of the chain: count[i] = the hits
+    // with rayFrac <= limits[i] (limits == nullptr: no limit; not capped by max_hits), rows i of index / ray_frac ([n][max_hits]) the first
+    // min(count, max_hits) of them by (rayFrac, extra elements first, index) -- TriangleIndex, or -2 - e for extra element e -- the rest of a row
+    // -1 / 0.0.  Any output may be nullptr (count == nullptr: a K-nearest query); max_hits 0 .. SR_HITS_MAX.  Needs the own BVH or brute force:
+    // the literal reference tree has no notion of all hits (the library refuses it).  Does nothing without a model
+    void AllHitRays(int64_t n, const double* starts, const double* dirs, const double* limits, int32_t max_hits, uint32_t* count, int32_t* index,
+                    double* ray_frac, bool endpoints = false, bool coherent = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel()) return;
+        PreCalculate();                                    // the model and the tree of Mode() are in the scene
+        std::vector<sr_prim> prims = ExtraGeometryToRaytrace.ToPrims();
+        sr_check(sr_set_extra_geometry(scene_, prims.data(), (int32_t)prims.size()));
+        sr_check(sr_all_hits_rays(scene_, SR_TARGET_ROOT | Mode(), n, starts, dirs, limits, max_hits, count, index, ray_frac,
+                                  (endpoints ? SR_RAYS_ENDPOINTS : 0u) | (coherent ? SR_RAYS_COHERENT : 0u), nullptr));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

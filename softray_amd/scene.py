@@ -625,6 +625,41 @@ class GpuScene:
                                                  _vp(d_pos), _vp(d_normal), _vp(d_color), _vp(d_tri_index), self._ray_options(endpoints, coherent),
                                                  _stream(stream), _vp(d_stats_ptr)))
 
+    # ---- all hits along a ray, nearest first, with a count (sr_all_hits_rays) ----
+    def all_hits(self, target, starts, dirs, limits=None, max_hits=8, want_count=True, endpoints=False, coherent=False, stats=False):
+        """Every hit of every ray with ray_frac <= limit (limits None: no limit): a dict with `count` (uint32 [n], not capped by max_hits; None
+        with want_count=False, which lets the walk cull beyond the max_hits-th hit), `index` (int32 [n][max_hits]: TriangleIndex, -2 - e for extra
+        element e, -1 in unused slots) and `ray_frac` (float64 [n][max_hits], 0.0 in unused slots), rows ordered by (ray_frac, extra elements
+        first, index); with stats=True also the four counters, `stats`.  max_hits=0 is the counting call.  D = dirs, or dirs - starts with
+        endpoints=True."""
+        starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = starts.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("dirs has %d entries for %d rays" % (dirs.shape[0], n))
+        if limits is not None:
+            limits = np.ascontiguousarray(limits, dtype=np.float64).reshape(-1)
+            if limits.size != n:
+                raise ValueError("limits has %d entries for %d rays" % (limits.size, n))
+        k = int(max_hits)
+        rows = max(0, min(k, _lib.HITS_MAX))
+        res = {"count": np.zeros(n, dtype=np.uint32) if want_count else None,
+               "index": np.full((n, rows), -1, dtype=np.int32), "ray_frac": np.zeros((n, rows), dtype=np.float64)}
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        _check(_lib.lib().sr_all_hits_rays(self._h, int(target), n, _p(starts), _p(dirs), _p(limits), k, _p(res["count"]),
+                                           _p(res["index"]) if rows else None, _p(res["ray_frac"]) if rows else None,
+                                           self._ray_options(endpoints, coherent), _p(st)))
+        if stats:
+            res["stats"] = st
+        return res
+
+    def all_hits_device(self, target, n, d_starts, d_dirs, d_limits=0, max_hits=8, d_count=0, d_index=0, d_ray_frac=0, endpoints=False, coherent=False,
+                        stream=0, d_stats_ptr=None):
+        """sr_all_hits_rays_device: every array is a DEVICE pointer (d_limits 0 / None: no limit; an output 0 / None: not wanted); enqueued on
+        `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
+        _check(_lib.lib().sr_all_hits_rays_device(self._h, int(target), int(n), _vp(d_starts), _vp(d_dirs), _vp(d_limits), int(max_hits), _vp(d_count),
+                                                  _vp(d_index), _vp(d_ray_frac), self._ray_options(endpoints, coherent), _stream(stream), _vp(d_stats_ptr)))
+
     # ---- the colour light field for caller-given rays (sr_light_field_rays) ----
     def light_field_rays(self, frame, starts, dirs, want_inside=True):
         """LightFieldColorMethod.IntersectRay for n lines of the caller's (sr_light_field_rays): (out uint32 [n], inside uint8 [n] or None,

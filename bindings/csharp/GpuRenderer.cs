@@ -128,6 +128,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_nearest_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, IntPtr dHit, IntPtr dRayFrac, IntPtr dPos, IntPtr dNormal, IntPtr dColor, IntPtr dTriIndex, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_all_hits_rays(IntPtr scene, int target, long n, [In] double[] starts, [In] double[] dirs, [In] double[] limits, int maxHits, [Out] uint[] count, [Out] int[] index, [Out] double[] rayFrac, uint options, [Out] ulong[] stats4);
         [DllImport(Lib)] public static extern int sr_all_hits_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, int maxHits, IntPtr dCount, IntPtr dIndex, IntPtr dRayFrac, uint options, IntPtr hipStream, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_closest_points(IntPtr scene, int target, long n, [In] double[] points, [In] double[] maxDist, [Out] int[] triIndex, [Out] double[] dist, [Out] double[] pos, [Out] double[] uv, uint options, [Out] ulong[] stats4);
+        [DllImport(Lib)] public static extern int sr_closest_points_device(IntPtr scene, int target, long n, IntPtr dPoints, IntPtr dMaxDist, IntPtr dTriIndex, IntPtr dDist, IntPtr dPos, IntPtr dUv, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -716,6 +718,29 @@ namespace Engine3D.Hip
         {
             Native.Check(Native.sr_all_hits_rays_device(scene, mode | (root ? 0x100 : 0), n, dStarts, dDirs, dLimits, maxHits, dCount, dIndex, dRayFrac,
                                                         (endpoints ? RAYS_ENDPOINTS : 0) | (coherent ? RAYS_COHERENT : 0), stream, dStats));
+        }
+
+        /// The closest point of the mesh for each point of a batch (sr_closest_points).  TriIndex[i]: the triangle that minimises (squared
+        /// distance, TriangleIndex), Dist[i] its distance, Pos ([n * 3]) the point of it nearest to points[i], Uv ([n * 2]) that point's weights of
+        /// vertices 2 and 3 -- where Dist &lt;= maxDist[i] (maxDist == null: no limit); -1 and zeros otherwise.  mode is MODE_BVH or MODE_BRUTE
+        /// (the reference tree has no distance query); the model alone, no extra geometry.  Blocks.
+        public sealed class ClosestPointResult { public int[] TriIndex; public double[] Dist; public double[] Pos; public double[] Uv; public ulong[] Stats4; }
+        public ClosestPointResult ClosestPoints(double[] points, double[] maxDist, int mode, bool coherent = false)
+        {
+            long n = points.Length / 3;
+            var r = new ClosestPointResult { TriIndex = new int[n], Dist = new double[n], Pos = new double[n * 3], Uv = new double[n * 2], Stats4 = new ulong[4] };
+            Native.Check(Native.sr_closest_points(scene, mode, n, points, maxDist, r.TriIndex, r.Dist, r.Pos, r.Uv, coherent ? POINTS_COHERENT : 0, r.Stats4));
+            return r;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_closest_points_device), dMaxDist IntPtr.Zero for no limit and
+        /// IntPtr.Zero for an output that is not wanted; enqueued on `stream` without a host synchronisation; dStats: ulong[24] on the device, or
+        /// IntPtr.Zero.
+        public void ClosestPointsDevice(long n, IntPtr dPoints, IntPtr dMaxDist, int mode, bool coherent, IntPtr dTriIndex, IntPtr dDist, IntPtr dPos,
+                                        IntPtr dUv, IntPtr stream, IntPtr dStats)
+        {
+            Native.Check(Native.sr_closest_points_device(scene, mode, n, dPoints, dMaxDist, dTriIndex, dDist, dPos, dUv, coherent ? POINTS_COHERENT : 0, stream,
+                                                         dStats));
         }
 
         /// ShadingMethod's colour step for n recorded intersections in DEVICE memory (sr_shade_points_device): dOut[i] = dColor[i] modulated with

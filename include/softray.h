@@ -746,6 +746,50 @@ int  sr_all_hits_rays_device(sr_scene*, int32_t target, int64_t n, const double*
                              uint32_t* d_count /* or NULL */, int32_t* d_index /* or NULL */, double* d_ray_frac /* or NULL */,
                              uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
+/* THE CLOSEST POINT of the mesh for each point of a batch -- which point of which triangle is nearest, and how far away: what distance
+ * fields, proximity and collision tests against a moving mesh (sr_refit_triangles_device), snapping to a surface, attribute transfer and the
+ * magnitude of a signed distance ask (its sign: the parity of sr_all_hits_rays counts).  No composition of the ray calls answers it.
+ * The distance of point q = points[i] to triangle j.  (a, b, c) = the three vertices of triangle j as the scene holds them (FP64, TriangleIndex
+ * order).  closest(q, a, b, c) is the Voronoi-region routine (Ericson, Real-Time Collision Detection 5.1.5; csrc/sr_closest.h, one text for the
+ * kernels and the host): with ab = b - a, ac = c - a, ap = q - a, bp = q - b, cp = q - c, d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp,
+ * d5 = ab.cp, d6 = ac.cp (every dot product x + y + z, left to right), vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, the first of
+ * these that holds decides:  d1 <= 0 && d2 <= 0: vertex a, (v, w) = (0, 0).  d3 >= 0 && d4 <= d3: vertex b, (1, 0).  vc <= 0 && d1 >= 0 && d3 <= 0:
+ * edge ab, v = d1 / (d1 - d3), w = 0, the point a + ab v.  d6 >= 0 && d5 <= d6: vertex c, (0, 1).  vb <= 0 && d2 >= 0 && d6 <= 0: edge ac, v = 0,
+ * w = d2 / (d2 - d6), a + ac w.  va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0: edge bc, w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w, b + (c - b) w.
+ * Otherwise the face: v = vb / (va + vb + vc), w = vc / (va + vb + vc), (a + ab v) + ac w.  Fixed operand order, no contraction, only + - * / and
+ * comparisons.  (v, w) are the weights of vertices 2 and 3 -- exactly 0 or 1 where a region pins them -- and in a vertex region the point is the
+ * vertex itself, bit for bit.  d2_j = (q - c_j).x^2 + (q - c_j).y^2 + (q - c_j).z^2, summed in that order; dist_j = sqrt(d2_j).
+ * The answer for q is the j that minimises (d2_j, j) lexicographically over all triangles whose d2_j is a number: a NaN d2_j (a collinear
+ * triangle can divide 0 by 0) never wins, equal d2 goes to the lowest TriangleIndex.  It QUALIFIES iff max_dist is NULL or dist <= max_dist[i]
+ * (IEEE <=): a NaN, -inf or negative limit qualifies nothing, +inf every number.  A point with no qualifying answer -- no triangle with a
+ * numeric distance, a NaN point, a limit that cuts the answer -- gets tri_index -1 and zeros in dist, pos and uv, as a miss does in the sibling calls.
+ * Outputs: tri_index[i] = j, dist[i] = dist_j, pos[i] = c_j, uv[i] = (v, w).  Every output is optional; all four NULL: the call runs for the statistics.
+ * Targets: SR_MODE_BVH walks the own BVH, SR_MODE_BRUTE runs the per-record loop over the vertices in index order; both give the same answers bit
+ * for bit.  SR_MODE_REF_TREE is SR_ERR_UNSUPPORTED (the reference tree duplicates triangles across leaves and has no distance query), and so are
+ * SR_TARGET_ROOT | mode (the extra primitives' closest points are not part of the call) and SR_TARGET_VOXELS.
+ * Routing in SR_MODE_BVH: a point is REGULAR when it is finite and no component lies further from the root box's centre than
+ * min(2^20 box diagonals, 2^60).  A pass is ordered by the 7-bit Morton cell of the point in the root box (points outside clamp to the edge
+ * cells; a stable radix sort; SR_POINTS_COHERENT, options bit 0: the input order is kept), and its regular points walk the tree (k_cp_walk): at a
+ * node an fp32 LOWER bound of the squared distance to each child's box, the nearer child first, a box skipped only when its bound strictly
+ * exceeds min(best d2, max_dist^2) with every rounding on the way covered -- equality never culls, so an equal-distance triangle
+ * with a lower index is always found.  Every other point goes to the end of its pass either way and runs the per-record loop (k_cp_loop): the
+ * same FP64 routine over every triangle, no fp32 stage, O(triangles) per point.  SR_MODE_BRUTE runs that loop for every point in input order.
+ * Refusals, in this order: a NULL scene, n < 0, NULL points with n > 0, unknown option bits: SR_ERR_INVALID_ARG; SR_TARGET_VOXELS,
+ * SR_TARGET_ROOT, SR_MODE_REF_TREE: SR_ERR_UNSUPPORTED; sr_trace_rays' own checks (SR_ERR_NO_MODEL, SR_ERR_NOT_BUILT); a host-only scene:
+ * SR_ERR_NO_DEVICE.  A refusal writes nothing.  n == 0 that passes all of them: SR_OK, nothing is touched.
+ * State: no per-origin or per-light record is rewritten, the call is ordered like a frame.  Passes of at most 2^22 points
+ * (SR_DBG_BAND_SAMPLES: fewer) follow each other without the host waiting.  A multi-device scene runs the call on devices[0].  The host variant
+ * stages 24 n + 8 n bytes in and 52 n bytes out through the scene's device buffers, blocks and fills sr_last_ray_stats; the device variant
+ * enqueues on `hip_stream` without a host synchronisation.  Statistics: [0] = n; [1..3] = triangles tested, nodes and leaves visited (pinned in
+ * brute force only: n x triangles, 0, 0); [4..] 0. */
+int  sr_closest_points(sr_scene*, int32_t target, int64_t n, const double* points /* [n][3] */,
+                       const double* max_dist /* [n], or NULL: no limit */,
+                       int32_t* tri_index /* [n] */, double* dist /* [n] */, double* pos /* [n][3] */, double* uv /* [n][2] */,
+                       uint32_t options, uint64_t stats[4] /* or NULL */);
+int  sr_closest_points_device(sr_scene*, int32_t target, int64_t n, const double* d_points, const double* d_max_dist /* or NULL */,
+                              int32_t* d_tri_index, double* d_dist, double* d_pos, double* d_uv /* each may be NULL */,
+                              uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* ShadingMethod.IntersectRay's colour step in batch (ShadingMethod.cs:36-68 -> CalcLighting :110-177): for n recorded
  * intersections out[i] = ModulatePackedColor(color[i], (byte)(255 * intensity)) with the frame's transform and lights (only the
  * matrices, position_z, fov_depth, lights, ambient, shininess and the POINT_LIGHT / SPECULAR flags of `frame` are read).
@@ -1068,7 +1112,8 @@ enum {
                                     order, also in SR_MODE_BVH (same output; baseline and cross-check); 100 + T and 200 + K also set the refill threshold and the LDS
                                     stack levels of sr_nearest_rays' walk kernel, as the bounce walk reads them below; 50 sr_all_hits_rays walks a pass in input order whatever the options say
                                     (no ray sort); 51 sr_all_hits_rays answers every ray of SR_MODE_BVH with the per-record loop of its irregular rays (both: same output;
-                                    cross-check); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    cross-check); 52 sr_closest_points walks a pass in input order whatever the options say (no point sort); 53 sr_closest_points
+                                    answers every point of SR_MODE_BVH with the per-record loop of its irregular points (both: same output; cross-check); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
                                     fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid

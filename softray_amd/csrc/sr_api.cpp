@@ -3441,6 +3441,99 @@ int sr_all_hits_rays(sr_scene* m, int32_t target, int64_t n, const double* start
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The closest point of the mesh for a batch of points (sr_closest_points): the distance query of the own BVH
+// ------------------------------------------------------------------------------------------------------------------
+// what sr_closest_points[_device] refuses, in the header's order; `s`: the scene that runs the call (the first part of a multi-device scene)
+static int closest_check(sr_scene*& s, int32_t target, int64_t n, const void* points, uint32_t options, int& mode) {
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_closest_points: the scene is NULL");
+    if (n < 0) return fail(SR_ERR_INVALID_ARG, "sr_closest_points: n is negative");
+    if (n > 0 && !points) return fail(SR_ERR_INVALID_ARG, "sr_closest_points: points must not be NULL when n > 0");
+    if (options & ~(uint32_t)SR_POINTS_COHERENT) return fail(SR_ERR_INVALID_ARG, "sr_closest_points: unknown option bits (SR_POINTS_COHERENT is the only option)");
+    if (target & SR_TARGET_VOXELS)
+        return fail(SR_ERR_UNSUPPORTED, "sr_closest_points: the voxel grid (SR_TARGET_VOXELS) has no triangles to measure a distance to");
+    if (target & SR_TARGET_ROOT)
+        return fail(SR_ERR_UNSUPPORTED, "sr_closest_points: the closest points of the extra geometry (SR_TARGET_ROOT) are not part of the call; pass the mode alone");
+    mode = target & 0xff;
+    if (mode == SR_MODE_REF_TREE)
+        return fail(SR_ERR_UNSUPPORTED, "sr_closest_points: SR_MODE_REF_TREE has no distance query (a triangle lives in several leaves of the reference tree); use "
+                                        "SR_MODE_BVH or SR_MODE_BRUTE");
+    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "sr_closest_points: the scene has no model (sr_set_triangles, sr_load_3ds)");
+    int rc;
+    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays: every point misses */ }
+    else if ((rc = check_mode(s, mode))) return rc;
+    if (s->device < 0) return fail(SR_ERR_NO_DEVICE, "sr_closest_points: a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
+    return SR_OK;
+}
+
+struct ClosestOut { int32_t* tri; double* dist; double* pos; double* uv; };
+
+// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set's sort buffers
+static int closest_common(sr_scene* s, int mode, int64_t n, const double* d_points, const double* d_limits, const ClosestOut& out, uint32_t options,
+                          hipStream_t stream, unsigned long long* d_stats) {
+    int rc = sync_geometry(s, (uint32_t)mode);
+    if (rc) return rc;
+    // ---- ordered like a frame (render_common): a frame's facing partition moves the records the walk reads ----
+    StreamOrder order(s, stream);
+    if (order.entered) return order.entered;
+    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
+    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kClosestMaxPass) : sr::kClosestMaxPass;
+    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
+    sr::ClosestLaunch L{};
+    L.sc = dev_scene(s);
+    L.mode = mode;
+    L.n = n; L.pass = pass;
+    L.points = d_points; L.limits = d_limits;
+    L.tri = out.tri; L.dist = out.dist; L.pos = out.pos; L.uv = out.uv;
+    L.input_order = (options & SR_POINTS_COHERENT) != 0 || hook == 52;                          // (hook: input order whatever the options say)
+    L.loop_all = hook == 53;                                                                    // (hook: every point through the per-record loop)
+    if (mode == SR_MODE_BVH) {
+        sr_scene::BandScratch& B = s->scratch[0];
+        const size_t slots = (size_t)(pass + 255) / 256 * 256;
+        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
+        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
+        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
+        L.sort_buf = (unsigned int*)B.ray_sort.p;
+        L.sort_temp = B.ray_sort_temp.p;
+    }
+    L.stats = d_stats;
+    L.stream = stream;
+    L.user = s;
+    L.get_events = timing_events;
+    SR_HIP(sr::launch_closest(L));
+    return SR_OK;
+}
+
+int sr_closest_points_device(sr_scene* m, int32_t target, int64_t n, const double* d_points, const double* d_max_dist, int32_t* d_tri_index, double* d_dist,
+                             double* d_pos, double* d_uv, uint32_t options, void* hip_stream, uint64_t* d_stats) {
+    sr_scene* s = m;
+    int mode;
+    int rc = closest_check(s, target, n, d_points, options, mode);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    const ClosestOut out{d_tri_index, d_dist, d_pos, d_uv};
+    return closest_common(s, mode, n, d_points, d_max_dist, out, options, stream, (unsigned long long*)d_stats);
+}
+
+int sr_closest_points(sr_scene* m, int32_t target, int64_t n, const double* points, const double* max_dist, int32_t* tri_index, double* dist, double* pos,
+                      double* uv, uint32_t options, uint64_t stats[4]) {
+    sr_scene* s = m;
+    int mode;
+    int rc = closest_check(s, target, n, points, options, mode);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    Staged io[] = {{points, nullptr, (size_t)n * 24}, {max_dist, nullptr, (size_t)n * 8}, {nullptr, tri_index, (size_t)n * 4}, {nullptr, dist, (size_t)n * 8},
+                   {nullptr, pos, (size_t)n * 24}, {nullptr, uv, (size_t)n * 16}};
+    return run_staged(m, s, io, 6, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
+        const ClosestOut out{(int32_t*)io[2].dev, (double*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev};
+        return closest_common(s, mode, n, (const double*)io[0].dev, (const double*)io[1].dev, out, options, stream, d_stats);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The RCCL strip gather, native: no PyTorch in the data path.
 // ------------------------------------------------------------------------------------------------------------------
 int sr_set_gather(sr_scene* m, int32_t kind) {

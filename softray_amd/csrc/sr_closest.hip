@@ -1,0 +1,311 @@
+// sr_closest.hip -- sr_closest_points: the nearest point of the mesh, its triangle and its distance, for a batch of points (gfx950).
+//
+// The answer for q is the triangle j that minimises (d2_j, j) over every triangle whose d2_j is a number, with c_j = closest_point_triangle
+// (sr_closest.h) on the FP64 vertices v9[j] and d2_j = closest_d2(q, c_j); it qualifies iff there is no limit or sqrt(d2_j) <= limit.
+// A REGULAR point (closest_regular) walks the own BVH: one lane per point, a while-while walk in k_ah_walk's frame that prunes by an fp32
+// LOWER bound of the squared distance to a child's box instead of a ray's slab interval, nearer child first.  Every other point of a pass,
+// and every point of brute force, runs the per-record loop over v9 in index order with the same FP64 routine and no fp32 stage.
+// The cull is exact: a box is skipped only when its deflated bound strictly exceeds the best squared distance found so far
+// (or the squared limit, inflated), so a triangle that ties the answer with a lower index is always visited.
+// A translation unit of its own: no other kernel is touched.
+#include <hipcub/hipcub.hpp>
+
+#include "sr_closest.h"
+#include "sr_trace.h"
+
+#include <algorithm>
+
+namespace sr {
+
+extern __shared__ __attribute__((aligned(16))) unsigned char lds_closest[];
+
+__device__ __forceinline__ unsigned int cp_spread7(unsigned int v) {       // 7 bits -> every third bit (k_ray_keys' spread)
+    v &= 0x7fu;
+    v = (v | (v << 8)) & 0x700fu;
+    v = (v | (v << 4)) & 0x430c3u;
+    v = (v | (v << 2)) & 0x49249u;
+    return v;
+}
+
+// Key of a pass's point: the 7-bit Morton cell of the point in the root box (points outside clamp to the edge cells), 21 bits; `skip`
+// (point_order_skip_mask) marks an IRREGULAR point, which the walk never sees: the stable sort leaves those at the end of the pass in input
+// order.  !sorted: the key is that bit alone (a deterministic compaction that keeps the input order).
+__global__ __launch_bounds__(256) void k_cp_keys(const double* __restrict__ points, unsigned int n, int sorted, unsigned int skip, double lx, double ly,
+                                                 double lz, double sx, double sy, double sz, double cx, double cy, double cz, double diag,
+                                                 unsigned int* __restrict__ keys, unsigned int* __restrict__ idx) {
+    const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const double q[3] = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
+    const double centre[3] = {cx, cy, cz};
+    unsigned int key = 0u;
+    if (!closest_regular(q, centre, diag)) key = skip;
+    else if (sorted) {
+        const int kx = (int)fmin(127.0, fmax(0.0, (q[0] - lx) * sx)), ky = (int)fmin(127.0, fmax(0.0, (q[1] - ly) * sy)), kz = (int)fmin(127.0, fmax(0.0, (q[2] - lz) * sz));
+        key = (cp_spread7((unsigned)kx) << 2) | (cp_spread7((unsigned)ky) << 1) | cp_spread7((unsigned)kz);
+    }
+    keys[i] = key;
+    idx[i] = i;
+}
+
+struct CpArgs {
+    const double* points; const double* limits;
+    long long first; unsigned int count;
+    const unsigned int* order; const unsigned int* keys; unsigned int skip_mask; int take;
+    int32_t* out_tri; double* out_dist; double* out_pos; double* out_uv;
+    unsigned long long* stats;
+};
+
+// lane j of the pass takes point order[j] (order == nullptr: point j); take 0: the regular points, 1: the others, 2: all
+__device__ __forceinline__ bool cp_pick(const CpArgs& a, unsigned int j, unsigned int& src) {
+    bool live = j < a.count;
+    src = j;
+    if (a.order && live) {
+        src = a.order[j];
+        if (a.take != 2) live = ((a.keys[j] & a.skip_mask) != 0u) == (a.take == 1);
+    }
+    return live;
+}
+
+// (d2, j) of one triangle against the running best: a NaN d2 fails both comparisons, equal d2 goes to the lower TriangleIndex
+__device__ __forceinline__ bool cp_better(double d2, int32_t j, double best, int32_t bj) { return d2 < best || (d2 == best && j < bj); }
+
+// The answer of point i once the best triangle is known: the routine runs once more for the winner (the loops keep (d2, j) only), the limit
+// is applied to the rounded square root, a point without a qualifying answer gets -1 and zeros
+__device__ __forceinline__ void cp_store(const DevScene& sc, const CpArgs& a, size_t i, const double q[3], int32_t bj, bool no_lim, double lim) {
+    double c[3] = {0.0, 0.0, 0.0}, v = 0.0, w = 0.0, dist = 0.0;
+    int32_t tri = -1;
+    if (bj != INT32_MAX) {
+        double cc[3], vv, ww;
+        closest_point_triangle(q, sc.v9 + (size_t)bj * 9, cc, vv, ww);
+        const double d = sqrt(closest_d2(q, cc));
+        if (no_lim || d <= lim) { tri = bj; dist = d; c[0] = cc[0]; c[1] = cc[1]; c[2] = cc[2]; v = vv; w = ww; }
+    }
+    if (a.out_tri) a.out_tri[i] = tri;
+    if (a.out_dist) a.out_dist[i] = dist;
+    if (a.out_pos) { a.out_pos[3 * i] = c[0]; a.out_pos[3 * i + 1] = c[1]; a.out_pos[3 * i + 2] = c[2]; }
+    if (a.out_uv) { a.out_uv[2 * i] = v; a.out_uv[2 * i + 1] = w; }
+}
+
+// block_stat_add's sums (sr_trace.h) in the first four words of the kernel's DYNAMIC LDS instead of a static array: the walk's stacks are
+// dead once every lane has arrived, and at the depth limit they are the whole 64 KiB a workgroup may ask for.  Every thread must call it.
+__device__ __forceinline__ void cp_stat_add(unsigned long long* stats, const Ctr& c) {
+    unsigned int* acc = reinterpret_cast<unsigned int*>(lds_closest);
+    const uint32_t r = wave_sum(c.rays), g = wave_sum(c.geom), n2 = wave_sum(c.nodes), l2 = wave_sum(c.leaves);
+    __syncthreads();                                                      // no lane reads its stack any more
+    if (threadIdx.x < 4) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        if (r) atomicAdd(&acc[0], r);
+        if (g) atomicAdd(&acc[1], g);
+        if (n2) atomicAdd(&acc[2], n2);
+        if (l2) atomicAdd(&acc[3], l2);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { stat_add(&stats[0], acc[0]); stat_add(&stats[1], acc[1]); stat_add(&stats[2], acc[2]); stat_add(&stats[3], acc[3]); }
+}
+
+// fp32 lower bound of the squared distance from the point (p = (float)(q - centre), e = 2^-23 |p| per axis) to the stored box [lo, hi]:
+// per axis the gap max(lo - p, p - hi, 0) less e, squared and summed, times (1 - 2^-19).  DESIGN 5.32 proves that it is at most the FP64
+// d2 of every triangle below the box whose closest point the routine placed inside the triangle.
+__device__ __forceinline__ float cp_bound(const float lo[3], const float hi[3], float px, float py, float pz, float ex, float ey, float ez) {
+    const float gx = fmaxf(fmaxf(fmaxf(lo[0] - px, px - hi[0]), 0.0f) - ex, 0.0f);
+    const float gy = fmaxf(fmaxf(fmaxf(lo[1] - py, py - hi[1]), 0.0f) - ey, 0.0f);
+    const float gz = fmaxf(fmaxf(fmaxf(lo[2] - pz, pz - hi[2]), 0.0f) - ez, 0.0f);
+    return (gx * gx + gy * gy + gz * gz) * (1.0f - 1.9073486328125e-6f);
+}
+// the fp32 value a bound must EXCEED to cull: at least `cull` whatever the rounding (an overflow gives +inf: nothing is culled)
+__device__ __forceinline__ float cp_cullf(double cull) { return (float)cull * (1.0f + 2.384185791015625e-7f) + 1e-30f; }
+
+// The tree walk of the regular points.  Stack word = node | the bound's float bits with their low bnode_bits cleared (a lower bound still),
+// one word per level per lane in LDS.
+template <bool STATS>
+__global__ __launch_bounds__(256) void k_cp_walk(DevScene sc, CpArgs a) {
+    const int tid = threadIdx.x;
+    Stack st{reinterpret_cast<int32_t*>(lds_closest) + tid, 256};
+    unsigned int src;
+    const bool live = cp_pick(a, blockIdx.x * 256u + (unsigned int)tid, src);
+    Ctr c = {0, 0, 0, 0};
+    if (live) {
+        const size_t i = (size_t)a.first + (size_t)src;
+        const double q[3] = {a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]};
+        const bool no_lim = a.limits == nullptr;
+        const double lim = no_lim ? (double)INFINITY : a.limits[i];
+        // d2 > lim2 implies sqrt(d2) > lim: fl(lim lim) (1 + 2^-48) >= lim^2 (1 + 2^-49).  A NaN limit gives NaN: fmin ignores it (no cull)
+        const double lim2 = (lim * lim) * (1.0 + 3.552713678800501e-15);
+        c.rays = 1;
+        double best = (double)INFINITY, trusted = (double)INFINITY;        // the answer's d2; the least d2 whose point lies in its triangle
+        int32_t bj = INT32_MAX;
+        float cullf = cp_cullf(fmin(trusted, lim2));
+        const float px = (float)(q[0] - sc.root.centre[0]), py = (float)(q[1] - sc.root.centre[1]), pz = (float)(q[2] - sc.root.centre[2]);
+        const float ex = fabsf(px) * 1.1920928955078125e-7f, ey = fabsf(py) * 1.1920928955078125e-7f, ez = fabsf(pz) * 1.1920928955078125e-7f;
+        const int nbits = sc.bnode_bits;
+        const uint32_t nmask = (1u << nbits) - 1u;
+        int sp = 0;
+        int32_t ni = 0, leafA = -1, leafB = -1;
+        float boundB = 0.0f;
+        for (;;) {
+            while (ni >= 0 && leafA < 0) {
+                const BvhNode n = sc.bnodes[ni];
+                c.nodes++;
+                const float b0 = cp_bound(n.lo0, n.hi0, px, py, pz, ex, ey, ez), b1 = cp_bound(n.lo1, n.hi1, px, py, pz, ex, ey, ez);
+                const bool h0 = n.n0 >= 0 && !(b0 > cullf), h1 = n.n1 >= 0 && !(b1 > cullf);
+                const bool first0 = b0 <= b1;                             // nearer child first
+                const bool l0 = h0 && n.n0 > 0, l1 = h1 && n.n1 > 0;
+                if (l0 && l1) {
+                    leafA = (first0 ? n.c0 : n.c1) | ((first0 ? n.n0 : n.n1) << kLeafShift);
+                    leafB = (first0 ? n.c1 : n.c0) | ((first0 ? n.n1 : n.n0) << kLeafShift);
+                    boundB = first0 ? b1 : b0;
+                } else if (l0) leafA = n.c0 | (n.n0 << kLeafShift);
+                else if (l1) leafA = n.c1 | (n.n1 << kLeafShift);
+                const bool i0 = h0 && n.n0 == 0, i1 = h1 && n.n1 == 0;
+                if (i0 && i1) {
+                    const uint32_t far_bits = __float_as_uint(first0 ? b1 : b0) & ~nmask;
+                    st.put(sp++, (int32_t)(far_bits | (uint32_t)(first0 ? n.c1 : n.c0)));
+                    ni = first0 ? n.c0 : n.c1;
+                } else if (i0) ni = n.c0;
+                else if (i1) ni = n.c1;
+                else {
+                    ni = -1;                                              // a popped node is re-tested against the best found since it was pushed
+                    while (sp > 0) {
+                        const uint32_t word = (uint32_t)st.get(--sp);
+                        if (!(__uint_as_float(word & ~nmask) > cullf)) { ni = (int32_t)(word & nmask); break; }
+                    }
+                }
+            }
+            if (leafA < 0) break;
+            while (leafA >= 0) {
+                const int32_t lfirst = leafA & kLeafMask, cn = (leafA >> kLeafShift) & 15;
+                leafA = (leafB >= 0 && !(boundB > cullf)) ? leafB : -1;
+                leafB = -1;
+                c.leaves++;
+                for (int k = 0; k < cn; ++k) {
+                    const int32_t j = sc.btris[lfirst + k].aux;
+                    double cc[3], v, w;
+                    c.geom++;
+                    closest_point_triangle(q, sc.v9 + (size_t)j * 9, cc, v, w);
+                    const double d2 = closest_d2(q, cc);
+                    if (cp_better(d2, j, best, bj)) { best = d2; bj = j; }
+                    // only a point inside its triangle may tighten the cull (the face region of a sliver can place it anywhere)
+                    if (v >= 0.0 && w >= 0.0 && v + w <= 1.0 + 0x1p-40 && d2 < trusted) {
+                        trusted = d2;
+                        cullf = cp_cullf(fmin(trusted, lim2));
+                    }
+                }
+            }
+        }
+        cp_store(sc, a, i, q, bj, no_lim, lim);
+    }
+    if (STATS) cp_stat_add(a.stats, c);                                   // (every thread of the workgroup arrives here)
+}
+
+// The per-record loop over v9 in index order: brute force (every point, input order) and the irregular tail of a SR_MODE_BVH pass.
+// O(triangles) per point.
+template <bool STATS>
+__global__ __launch_bounds__(256) void k_cp_loop(DevScene sc, CpArgs a) {
+    unsigned int src;
+    const bool live = cp_pick(a, blockIdx.x * 256u + threadIdx.x, src);
+    Ctr c = {0, 0, 0, 0};
+    if (live) {
+        const size_t i = (size_t)a.first + (size_t)src;
+        const double q[3] = {a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]};
+        const bool no_lim = a.limits == nullptr;
+        const double lim = no_lim ? (double)INFINITY : a.limits[i];
+        c.rays = 1;
+        double best = (double)INFINITY;
+        int32_t bj = INT32_MAX;
+        for (int32_t j = 0; j < sc.ntris; ++j) {
+            double cc[3], v, w;
+            c.geom++;
+            closest_point_triangle(q, sc.v9 + (size_t)j * 9, cc, v, w);
+            const double d2 = closest_d2(q, cc);
+            if (cp_better(d2, j, best, bj)) { best = d2; bj = j; }
+        }
+        cp_store(sc, a, i, q, bj, no_lim, lim);
+    }
+    if (STATS) cp_stat_add(a.stats, c);
+}
+
+namespace {
+
+hipError_t launch_cp_walk(const ClosestLaunch& L, const CpArgs& a) {
+    const dim3 grid((a.count + 255u) / 256u);
+    const size_t lds = (size_t)(L.sc.bdepth + 2) * 256 * 4;
+    if (L.stats) hipLaunchKernelGGL((k_cp_walk<true>), grid, dim3(256), lds, L.stream, L.sc, a);
+    else hipLaunchKernelGGL((k_cp_walk<false>), grid, dim3(256), lds, L.stream, L.sc, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cp_loop(const ClosestLaunch& L, const CpArgs& a) {
+    const dim3 grid((a.count + 255u) / 256u);
+    if (L.stats) hipLaunchKernelGGL((k_cp_loop<true>), grid, dim3(256), 16, L.stream, L.sc, a);             // (cp_stat_add's four words)
+    else hipLaunchKernelGGL((k_cp_loop<false>), grid, dim3(256), 0, L.stream, L.sc, a);
+    return hipGetLastError();
+}
+
+// the order of a pass: the regular points first -- sorted: by Morton cell, ties in input order; !sorted: in input order -- then the others
+hipError_t cp_order(const ClosestLaunch& L, const double* points, unsigned int n, bool sorted, unsigned int* keys, unsigned int* keys2, unsigned int* idx,
+                    unsigned int* order_out) {
+    const RootBox& root = L.sc.root;
+    double s[3];
+    for (int k = 0; k < 3; ++k) { const double e = root.max[k] - root.min[k]; s[k] = e > 0 ? 128.0 / e : 0.0; }
+    const unsigned int skip = point_order_skip_mask(sorted);
+    int end_bit = 0;
+    while ((skip >> end_bit) != 0u) ++end_bit;                            // the skip bit is the key's highest
+    hipLaunchKernelGGL(k_cp_keys, dim3((n + 255u) / 256u), dim3(256), 0, L.stream, points, n, sorted ? 1 : 0, skip, root.min[0], root.min[1], root.min[2], s[0],
+                       s[1], s[2], root.centre[0], root.centre[1], root.centre[2], closest_diag(root.min, root.max), keys, idx);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    size_t temp_bytes = L.sort_temp_bytes;
+    return hipcub::DeviceRadixSort::SortPairs(L.sort_temp, temp_bytes, (const unsigned int*)keys, keys2, (const unsigned int*)idx, order_out, (int)n, 0, end_bit,
+                                              L.stream);
+}
+
+}  // namespace
+
+// pass by pass, back to back on the stream.  SR_MODE_BVH: a pass is ordered first, the regular points walk the tree, the tail runs the
+// per-record loop (loop_all: every point does).  SR_MODE_BRUTE: the per-record loop in input order
+hipError_t launch_closest(const ClosestLaunch& L) {
+    if (L.n <= 0) return hipSuccess;
+    if (L.pass <= 0 || L.pass > kClosestMaxPass) return hipErrorInvalidValue;
+    if (L.mode != MODE_BVH && L.mode != MODE_BRUTE) return hipErrorInvalidValue;
+    if (L.mode == MODE_BVH && (L.sc.bdepth + 2) * 256 * 4 > 65536) return hipErrorInvalidValue;
+    const unsigned int cap = (unsigned int)((L.pass + 255) / 256 * 256);
+    unsigned int* keys = L.sort_buf;
+    unsigned int* keys2 = keys + cap;
+    unsigned int* idx = keys2 + cap;
+    unsigned int* order = idx + cap;
+    for (int64_t first = 0; first < L.n; first += L.pass) {
+        const unsigned int count = (unsigned int)std::min<int64_t>(L.pass, L.n - first);
+        hipError_t e;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        CpArgs a{};
+        a.points = L.points; a.limits = L.limits;
+        a.first = first; a.count = count;
+        a.out_tri = L.tri; a.out_dist = L.dist; a.out_pos = L.pos; a.out_uv = L.uv;
+        a.stats = L.stats;
+        a.take = 2;
+        if (L.mode == MODE_BVH) {
+            if (L.get_events) L.get_events(L.user, K_CLOSEST_SORT, &e0, &e1);
+            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+            if ((e = cp_order(L, L.points + 3 * first, count, !L.input_order, keys, keys2, idx, order)) != hipSuccess) return e;
+            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+            a.order = order; a.keys = keys2; a.skip_mask = point_order_skip_mask(!L.input_order);
+        }
+        e0 = e1 = nullptr;
+        if (L.get_events) L.get_events(L.user, K_CLOSEST, &e0, &e1);
+        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+        if (L.mode == MODE_BVH && !L.loop_all) {
+            a.take = 0;
+            e = launch_cp_walk(L, a);
+            a.take = 1;
+            if (e == hipSuccess) e = launch_cp_loop(L, a);
+        } else {
+            e = launch_cp_loop(L, a);
+        }
+        if (e != hipSuccess) return e;
+        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace sr

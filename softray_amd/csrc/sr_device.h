@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_LFR_LOOKUP = 46, K_LFR_FINISH = 47, K_LFRI_LOOKUP = 48, K_LFRI_FINISH = 49, K_NEAREST = 50, K_NEAREST_SORT = 51, K_ALL_HITS = 52, K_ALL_HITS_SORT = 53, K_COUNT = 54 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_LFR_LOOKUP = 46, K_LFR_FINISH = 47, K_LFRI_LOOKUP = 48, K_LFRI_FINISH = 49, K_NEAREST = 50, K_NEAREST_SORT = 51, K_ALL_HITS = 52, K_ALL_HITS_SORT = 53, K_CLOSEST = 54, K_CLOSEST_SORT = 55, K_COUNT = 56 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -493,6 +493,30 @@ struct AllHitsLaunch {
     void*       user;
 };
 hipError_t launch_all_hits(const AllHitsLaunch& L);
+
+// sr_closest_points (sr_closest.hip): for n caller-given points the triangle that minimises (squared distance, TriangleIndex), its distance,
+// the closest point and its weights, where the distance is within the limit -- in passes of `pass` points.  SR_MODE_BVH: k_cp_keys + the
+// radix sort, k_cp_walk for the regular points (closest_regular, sr_closest.h), k_cp_loop (the per-record loop) for the others;
+// SR_MODE_BRUTE: k_cp_loop in input order
+constexpr int64_t kClosestMaxPass = 1ll << 22;
+struct ClosestLaunch {
+    DevScene    sc;
+    int32_t     mode;           // SR_MODE_BVH or SR_MODE_BRUTE
+    int64_t     n, pass;
+    const double* points;       // device [n][3]
+    const double* limits;       // device [n] or nullptr (no limit)
+    int32_t* tri; double* dist; double* pos; double* uv;      // device [n], [n], [n][3], [n][2]; each may be nullptr
+    bool        input_order;    // SR_POINTS_COHERENT / hook 52: a pass keeps its input order (the irregular points still go last)
+    bool        loop_all;       // SR_MODE_BVH with the per-record loop for every point (hook 53)
+    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words (SR_MODE_BVH)
+    void*       sort_temp;
+    size_t      sort_temp_bytes; // point_order_temp_bytes
+    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += points, [1..3] += what their walks count
+    hipStream_t stream;
+    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
+    void*       user;
+};
+hipError_t launch_closest(const ClosestLaunch& L);
 
 // the four-wide tree collapsed from a device-resident binary tree (same rule as the host's collapse_bvh4); d_wide: >= num_nodes entries
 // level_first (nullable): the wide nodes are numbered level by level -- level L is [level_first[L], level_first[L + 1]), the last entry

@@ -549,6 +549,18 @@ public:
         sr_check(sr_all_hits_rays(scene_, SR_TARGET_ROOT | Mode(), n, starts, dirs, limits, max_hits, count, index, ray_frac,
                                   (endpoints ? SR_RAYS_ENDPOINTS : 0u) | (coherent ? SR_RAYS_COHERENT : 0u), nullptr));
     }
+    // The closest point of the model for n points of the caller's (sr_closest_points): tri_index[i] = the triangle that minimises (squared
+    // distance, TriangleIndex), dist[i] its distance, pos[i] ([n][3]) the point of it nearest to points[i], uv[i] ([n][2]) that point's weights
+    // of vertices 2 and 3 -- where dist <= max_dist[i] (max_dist == nullptr: no limit); -1 and zeros otherwise.  Any output may be nullptr.
+    // The model alone (no extra geometry); needs the own BVH or brute force: the reference tree has no distance query (the library refuses
+    // it).  coherent: SR_POINTS_COHERENT.  Does nothing without a model
+    void ClosestPoints(int64_t n, const double* points, const double* max_dist, int32_t* tri_index, double* dist, double* pos, double* uv,
+                       bool coherent = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel()) return;
+        PreCalculate();                                    // the model and the tree of Mode() are in the scene
+        sr_check(sr_closest_points(scene_, Mode(), n, points, max_dist, tri_index, dist, pos, uv, coherent ? SR_POINTS_COHERENT : 0u, nullptr));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

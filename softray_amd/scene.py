@@ -660,6 +660,35 @@ class GpuScene:
         _check(_lib.lib().sr_all_hits_rays_device(self._h, int(target), int(n), _vp(d_starts), _vp(d_dirs), _vp(d_limits), int(max_hits), _vp(d_count),
                                                   _vp(d_index), _vp(d_ray_frac), self._ray_options(endpoints, coherent), _stream(stream), _vp(d_stats_ptr)))
 
+    # ---- the closest point of the mesh for a batch of points (sr_closest_points) ----
+    def closest_points(self, target, points, max_dist=None, want=("tri_index", "dist", "pos", "uv"), coherent=False, stats=False):
+        """For every point the triangle that minimises (squared distance, TriangleIndex), where its distance is <= max_dist (None: no limit):
+        a dict with `tri_index` (int32 [n], -1: no qualifying answer), `dist` (float64 [n]), `pos` (float64 [n][3], the closest point) and `uv`
+        (float64 [n][2], the weights of vertices 2 and 3); zeros where tri_index is -1.  `want` names the outputs asked for (the others are
+        None); with stats=True also the four counters, `stats`.  target: MODE_BVH or MODE_BRUTE."""
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = points.shape[0]
+        if max_dist is not None:
+            max_dist = np.ascontiguousarray(max_dist, dtype=np.float64).reshape(-1)
+            if max_dist.size != n:
+                raise ValueError("max_dist has %d entries for %d points" % (max_dist.size, n))
+        res = {"tri_index": np.full(n, -1, dtype=np.int32) if "tri_index" in want else None,
+               "dist": np.zeros(n, dtype=np.float64) if "dist" in want else None,
+               "pos": np.zeros((n, 3), dtype=np.float64) if "pos" in want else None,
+               "uv": np.zeros((n, 2), dtype=np.float64) if "uv" in want else None}
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        _check(_lib.lib().sr_closest_points(self._h, int(target), n, _p(points), _p(max_dist), _p(res["tri_index"]), _p(res["dist"]), _p(res["pos"]),
+                                            _p(res["uv"]), _lib.POINTS_COHERENT if coherent else 0, _p(st)))
+        if stats:
+            res["stats"] = st
+        return res
+
+    def closest_points_device(self, target, n, d_points, d_max_dist=0, d_tri_index=0, d_dist=0, d_pos=0, d_uv=0, coherent=False, stream=0, d_stats_ptr=None):
+        """sr_closest_points_device: every array is a DEVICE pointer (d_max_dist 0 / None: no limit; an output 0 / None: not wanted); enqueued on
+        `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
+        _check(_lib.lib().sr_closest_points_device(self._h, int(target), int(n), _vp(d_points), _vp(d_max_dist), _vp(d_tri_index), _vp(d_dist), _vp(d_pos),
+                                                   _vp(d_uv), _lib.POINTS_COHERENT if coherent else 0, _stream(stream), _vp(d_stats_ptr)))
+
     # ---- the colour light field for caller-given rays (sr_light_field_rays) ----
     def light_field_rays(self, frame, starts, dirs, want_inside=True):
         """LightFieldColorMethod.IntersectRay for n lines of the caller's (sr_light_field_rays): (out uint32 [n], inside uint8 [n] or None,

@@ -370,8 +370,9 @@ sr::DevScene dev_scene(const sr_scene* s) {
     // the four-wide walks stack up to three entries per level: a private walk needs (3 depth + 2) x 1 KB of LDS per workgroup, a packet
     // walk (3 depth + 2) x 528 B; a tree too deep for that is walked in its binary form (a pathological scene, not a large one:
     // 10 M triangles give depth 14).  Seen so far: private walks off the wide tree (b4depth >= 21) from a chain of shrinking triangles
-    // at one per leaf and from the device build's deepest accepted tree; packet walks off it (b4depth >= 41) from no tree that sr_build
-    // accepts (depth <= 62) -- a path of the binary tree collapses three levels into one -- though nothing excludes it
+    // at one per leaf and from the device build's deepest accepted tree; packet walks off it (b4depth >= 41) from the cluster staircase
+    // of the tests (wide_deep: depth 60, wide depth 48 on the MI355X), where the partition, the cone records and both ordered copies are
+    // still made and k_primary / k_hits / k_origin_rays and the first shaft round take the binary packet walks
     const size_t lv4 = (size_t)(3 * s->b4_depth + 2);
     const bool wide_private = s->b4_num > 0 && lv4 * 1024 <= 65536, wide_packets = s->b4_num > 0 && lv4 * 528 <= 65536;
     d.b4 = wide_private ? (const sr::Bvh4Node*)s->d_b4.p : nullptr;
@@ -1073,7 +1074,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             s->b4cam_known = known;
             s->b4cam_valid = true;
         }
-        if (wide) s->dbg_frame[0] |= (uint32_t)s->b4cam_known << 4;
+        if (wide && dev_scene(s).b4cam) s->dbg_frame[0] |= (uint32_t)s->b4cam_known << 4;      // (a copy the tree is too deep to walk is no copy walked)
     }
     if (wide && (fc.flags & SR_F_SHADOWS) && (fc.flags & SR_F_POINT_LIGHT)) {
         const bool same_light = s->b4_light[0] == fc.light_pos_model[0] && s->b4_light[1] == fc.light_pos_model[1] && s->b4_light[2] == fc.light_pos_model[2] &&
@@ -1100,7 +1101,7 @@ int render_common(sr_scene* s, const sr_frame* f, uint32_t* d_pixels, hipStream_
             s->b4_light_radius = fc.light_radius;
             s->b4light_valid = true;
         }
-        s->dbg_frame[0] |= (uint32_t)s->b4light_known;
+        if (dev_scene(s).b4light) s->dbg_frame[0] |= (uint32_t)s->b4light_known;
     }
     // ---- penumbra-plane records of the packet shaft walk's triangle filter: one pre-pass per (tree, record order, light ball) ----
     const bool shadows = (fc.flags & SR_F_SHADOWS) != 0;

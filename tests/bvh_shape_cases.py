@@ -22,6 +22,11 @@ DEEP_POSE = dict(yaw_deg=160.0, pitch_deg=-35.0, depth=0.8)
 DEEP_LIGHT = (0.0, bs.CHAIN_Y, 1.2)           # model space: the segments from the soup to the light cross z = 0 around the chain's small end
 LIMIT_SOUP = dict(n=100, centre=(0.25, 0.1, 0.2), extent=0.3, seed=5)
 LIMIT_CORNER = 4
+# cluster_staircase(m): steps 0 .. m - 1 and the cluster in the point's own cell, m + 1 clusters of three
+WIDE_DEEP_STEPS = 56                          # device-built, one triangle per leaf: depth 60, wide depth 48 (bvh_shapes.wide_depth_model)
+WIDE_EDGE_STEPS = 48                          # ... depth 52, wide depth 40: (3 x 40 + 2) x 528 B, the largest packet-walk stack there is
+PRIVATE_EDGE_STEPS = 28                       # ... depth 32, wide depth 20: (3 x 20 + 2) x 1 KB, the largest stack of a four-wide private walk
+WIDE_LEAF = 1                                 # SR_DBG_BVH_LEAF of both
 TIE_POSE = dict()                             # the RendererTests pose
 
 
@@ -60,6 +65,12 @@ def scene(name):
         return bs.shrinking_chain(CHAIN_REFUSED_N, extra=bs.soup(**DEEP_SOUP))
     if name == "limit":
         return bs.morton_staircase(limit_staircase_length(), np.concatenate([bs.corner_cluster(LIMIT_CORNER), bs.soup(**LIMIT_SOUP)]))
+    if name == "wide_deep":
+        return bs.cluster_staircase(WIDE_DEEP_STEPS, extra=bs.soup(**LIMIT_SOUP))
+    if name == "wide_edge":
+        return bs.cluster_staircase(WIDE_EDGE_STEPS, extra=bs.soup(**LIMIT_SOUP))
+    if name == "private_edge":
+        return bs.cluster_staircase(PRIVATE_EDGE_STEPS, extra=bs.soup(**LIMIT_SOUP))
     if name == "same_centre":
         return bs.same_centre(300)
     if name == "duplicates":
@@ -73,6 +84,7 @@ def scene(name):
     raise KeyError(name)
 
 
+WIDE_STEPS = {"wide_deep": WIDE_DEEP_STEPS, "wide_edge": WIDE_EDGE_STEPS, "private_edge": PRIVATE_EDGE_STEPS}
 TIE_SCENES = ("same_centre", "duplicates", "flat_thin", "flat_thick")
 
 
@@ -134,8 +146,8 @@ def pixel_classes(scene_name):
 @functools.lru_cache(maxsize=None)
 def ray_batch(scene_name, family):
     v9 = scene(scene_name)[0]
-    if scene_name in ("chain", "chain_hittable"):
-        n = v9.shape[0]
+    if scene_name in ("chain", "chain_hittable", "deep"):
+        n = min(v9.shape[0], CHAIN_N)                                   # (the chain comes first in `deep`, its soup after it)
         if family == "at_triangles":
             s, d = bs.rays_at_triangles(v9, np.arange(n), 5)
         elif family == "through_point":
@@ -144,8 +156,26 @@ def ray_batch(scene_name, family):
             s, d = bs.rays_missing_by_less_than_the_pad(v9, np.arange(min(n, CHAIN_HITTABLE)), ext=1.25)
         else:
             raise KeyError(family)
-    elif scene_name == "limit" and family == "at_triangles":
-        s, d = bs.rays_at_triangles(v9, np.arange(limit_staircase_length()), 3)
+    elif scene_name == "limit":
+        m = limit_staircase_length()
+        if family == "at_triangles":
+            s, d = bs.rays_at_triangles(v9, np.arange(m), 3)
+        elif family == "through_point":                                 # the middle of a step two thirds down the staircase
+            s, d = bs.rays_through_point(0.5 * (v9[m // 3].min(axis=0) + v9[m // 3].max(axis=0)), 64)
+        elif family == "near_miss":
+            s, d = bs.rays_missing_by_less_than_the_pad(v9, np.arange(m))
+        else:
+            raise KeyError(family)
+    elif scene_name in WIDE_STEPS:
+        stairs = np.arange(3 * (WIDE_STEPS[scene_name] + 1))
+        if family == "at_triangles":
+            s, d = bs.rays_at_triangles(v9, stairs, 3)
+        elif family == "through_point":
+            s, d = bs.rays_through_point(bs.cluster_point(), 64)
+        elif family == "near_miss":
+            s, d = bs.rays_missing_by_less_than_the_pad(v9, stairs)
+        else:
+            raise KeyError(family)
     elif scene_name == "duplicates" and family == "at_triangles":
         s, d = bs.rays_at_triangles(v9, np.arange(0, v9.shape[0], 2), 3)
     else:

@@ -1,9 +1,11 @@
 """Adversarial geometry for the library's own BVH, and a plain model of the device build.
 
 Generators (deterministic, numpy only) of the shapes a BVH builder and its walks usually get wrong -- trees as deep as the traversal
-stacks allow, triangles with equal Morton keys, exact duplicates, an axis on which every box centre coincides -- and `lbvh_model`, a
-restatement of the device LBVH's keys, radix tree and leaf collapse (sr_lbvh.hip: k_lbvh_keys, k_lbvh_tree, k_lbvh_mark) that never
-calls into the library.  Every generator returns (v9 [n, 3, 3], argb [n], bmin [3], bmax [3]) with a distinct colour per triangle.
+stacks allow, a four-wide tree as deep as its binary one, triangles with equal Morton keys, exact duplicates, an axis on which every box
+centre coincides -- and `lbvh_model`, a restatement of the device LBVH's keys, radix tree and leaf collapse (sr_lbvh.hip: k_lbvh_keys,
+k_lbvh_tree, k_lbvh_mark) that never calls into the library; with it `lbvh_nodes` (the same tree with its fp32 boxes), `sah_nodes` (the
+host's binned-SAH builder) and `wide_depth_model` (the collapse into the four-wide tree).  Every generator returns (v9 [n, 3, 3],
+argb [n], bmin [3], bmax [3]) with a distinct colour per triangle.
 """
 import math
 
@@ -86,6 +88,40 @@ def corner_cluster(n):
     r = 0.2 * cell
     v1 = c + np.array([-r, -r, -r]); v2 = c + np.array([r, -r, r]); v3 = c + np.array([0.0, r, -r])
     return np.stack([v1, v2, v3], axis=1)
+
+
+CLUSTER_CELL = 2 ** 20 - 1                   # the cell 0111..1 on every axis: the cluster staircase converges to the box's middle
+
+
+def cluster_point():
+    """The point the cluster staircase converges to: the middle of the Morton cell (CLUSTER_CELL,) * 3 of the unit box."""
+    return UNIT_MIN + (np.full(3, CLUSTER_CELL) + 0.5) / MORTON_CELLS
+
+
+def cluster_staircase(m, r0=0.34, ratio=0.85, per=3, extra=None):
+    """A staircase whose every step is a cluster of `per` oversized triangles, for a device build with one triangle per leaf whose
+    FOUR-WIDE tree is about as deep as the binary one.  Step i = 0 .. m - 1 lies in the sibling of the cell of cluster_point() at key
+    bit 61 - i (the one key bit flipped, every lower bit of that axis set towards the point: the cell nearest to it), step m in the
+    point's own cell; the triangles of a step share their box centre (equal keys) and have box half extents r0 ratio^i 0.9^k.  The radix
+    tree is a path with one step hanging off every node; the step's box is larger than that of everything below it, and so is its
+    two-triangle half, so the collapse (wide_depth_model) spends both expansions of a wide node on the step and the path goes on one
+    wide level per binary level.  The steps of the second and third key bit of an axis lie a quarter and an eighth of the box from the
+    point, so r0 = 0.34 is what keeps step 2 inside the box, and a few of the highest steps do cost a second binary level.  The
+    triangles' normals alternate between (-4, 2, 4) and (4, 2, -4) from step to step: the triangles are one-sided, so a ray through
+    the point with a direction of positive product with both hits none of them and walks every level."""
+    centres, radii, signs = [], [], []
+    for i in range(m + 1):
+        cell = [CLUSTER_CELL] * 3
+        if i < m:
+            a, t = (i + 1) % 3, (i + 1) // 3                            # key bit 61 - i is bit 20 - t of axis a
+            cell[a] = 2 ** 20 if t == 0 else CLUSTER_CELL - 2 ** (20 - t)
+        for k in range(per):
+            centres.append(UNIT_MIN + (np.array(cell) + 0.5) / MORTON_CELLS)
+            radii.append(r0 * ratio ** i * 0.9 ** k)
+            signs.append([1, 1 - 2 * (i & 1), 1])
+    c, r, s = np.array(centres), np.array(radii)[:, None], np.array(signs, dtype=np.float64)
+    stairs = np.stack([c - r * s, c + r * s * np.array([1.0, -1.0, 1.0]), c + r * s * np.array([0.0, 1.0, -1.0])], axis=1)
+    return _pack([stairs] if extra is None else [stairs, extra])
 
 
 SAME_CENTRE = np.array([0.125, -0.0625, 0.03125])
@@ -195,6 +231,173 @@ def lbvh_model(v9, bmin, bmax, leaf_max=4):
         todo.append((first, lo, level + 1))
         todo.append((hi, last, level + 1))
     return depth + 1, nodes, order.astype(np.int64)
+
+
+def _f32_down(x):
+    f = np.asarray(x, dtype=np.float64).astype(np.float32)
+    return np.where(f.astype(np.float64) > x, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+def _f32_up(x):
+    f = np.asarray(x, dtype=np.float64).astype(np.float32)
+    return np.where(f.astype(np.float64) < x, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+
+
+def node_boxes32(lo, hi, bmin, bmax):
+    """The builders' fp32 boxes of FP64 extents lo, hi [n, 3]: relative to the root centre, padded by 2^-16 of the root's largest
+    extent, rounded outward (sr_host.cpp store(), sr_lbvh.hip tri_box)."""
+    bmin = np.asarray(bmin, dtype=np.float64); bmax = np.asarray(bmax, dtype=np.float64)
+    ext = float(np.max(bmax - bmin))
+    pad = math.ldexp(ext if ext > 0 else 1.0, -16)
+    centre = (bmin + bmax) * 0.5
+    return _f32_down(lo - centre - pad), _f32_up(hi - centre + pad)
+
+
+def lbvh_nodes(v9, bmin, bmax, leaf_max=4):
+    """The device-built binary tree as wide_depth_model takes it: node i = ((lo, hi, child), (lo, hi, child)) with the children's fp32
+    boxes (unions of the triangles' boxes, k_lbvh_boxes) and child = the index of an inner node, -1 for a leaf; node 0 is the root.
+    Topology as lbvh_model.  A scene that fits one leaf has a root with that leaf alone."""
+    v = np.asarray(v9, dtype=np.float64).reshape(-1, 3, 3)
+    keys = morton_keys(v, bmin, bmax)
+    order = np.argsort(keys, kind="stable")
+    aug = [(int(k) << 32) | i for i, k in enumerate(keys[order])]
+    tlo, thi = node_boxes32(v.min(axis=1)[order], v.max(axis=1)[order], bmin, bmax)
+    nodes = []
+
+    def build(first, last):
+        box = (tlo[first:last + 1].min(axis=0), thi[first:last + 1].max(axis=0))
+        if last - first + 1 <= leaf_max:
+            return box + (-1,)
+        idx = len(nodes)
+        nodes.append(None)
+        bit = (aug[first] ^ aug[last]).bit_length() - 1
+        lo, hi = first, last
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if (aug[mid] >> bit) & 1:
+                hi = mid
+            else:
+                lo = mid
+        nodes[idx] = (build(first, lo), build(hi, last))
+        return box + (idx,)
+
+    top = build(0, len(aug) - 1)
+    return nodes if nodes else [(top,)]
+
+
+SAH_BINS = 16
+
+
+def sah_nodes(v9, bmin, bmax, leaf_max=4):
+    """The host-built binary tree (sr_host.cpp BvhBuilder::build), in lbvh_nodes' form, with its depth: (nodes, depth).  The widest
+    axis of the centroids' box (the first on a tie), 16 bins over it, the split of least sum of half area x count (the first on a
+    tie), a stable partition; where no bin boundary separates the range, the halves by index of the order by (centre, index)."""
+    v = np.asarray(v9, dtype=np.float64).reshape(-1, 3, 3)
+    plo, phi = v.min(axis=1), v.max(axis=1)
+    pc = 0.5 * (plo + phi)
+    nodes = []
+    deepest = [0]
+
+    def half_area(lo, hi):
+        d = hi - lo
+        return d[0] * d[1] + d[1] * d[2] + d[2] * d[0]
+
+    def build(ids, depth):
+        deepest[0] = max(deepest[0], depth)
+        lo, hi = plo[ids].min(axis=0), phi[ids].max(axis=0)
+        flo, fhi = node_boxes32(lo, hi, bmin, bmax)
+        if len(ids) <= leaf_max:
+            return (flo, fhi, -1)
+        c = pc[ids]
+        clo, chi = c.min(axis=0), c.max(axis=0)
+        axis, ext = 0, chi[0] - clo[0]
+        for a in (1, 2):
+            if chi[a] - clo[a] > ext:
+                axis, ext = a, chi[a] - clo[a]
+        left = right = None
+        if ext > 0:
+            k1 = SAH_BINS * (1.0 - 1e-9) / ext
+            bins = np.clip(((c[:, axis] - clo[axis]) * k1).astype(np.int64), 0, SAH_BINS - 1)
+            best, bestk = None, -1
+            for k in range(SAH_BINS - 1):
+                l, r = ids[bins <= k], ids[bins > k]
+                if len(l) == 0 or len(r) == 0:
+                    continue
+                cost = half_area(plo[l].min(axis=0), phi[l].max(axis=0)) * len(l) + half_area(plo[r].min(axis=0), phi[r].max(axis=0)) * len(r)
+                if best is None or cost < best:
+                    best, bestk = cost, k
+            if bestk >= 0:
+                left, right = ids[bins <= bestk], ids[bins > bestk]
+        if left is None:
+            by = sorted(ids.tolist(), key=lambda i: (pc[i, axis], i))
+            mid = len(by) // 2
+            left, right = np.array(by[:mid]), np.array(by[mid:])
+        idx = len(nodes)
+        nodes.append(None)
+        l = build(left, depth + 1)
+        r = build(right, depth + 1)
+        nodes[idx] = (l, r)
+        return (flo, fhi, idx)
+
+    top = build(np.arange(v.shape[0]), 1)
+    return (nodes if nodes else [(top,)]), deepest[0]
+
+
+def wide_depth_model(nodes, fp32=False):
+    """Depth of the four-wide tree collapsed from a binary one (collapse_bvh4 in sr_host.cpp, k_collapse_level in sr_lbvh.hip), as
+    sr_wide_tree_stats()[0] reports it.  A wide node takes a binary node's two children and, while it has fewer than four, replaces
+    the inner child of largest box area dx dy + dy dz + dz dx (the first of equals) by that child's two children; every inner child
+    left is a wide node one level down.  The host takes the areas of the fp32 boxes in FP64, the device (fp32=True) in fp32."""
+    t = np.float32 if fp32 else np.float64
+
+    def area(child):
+        d = child[1].astype(t) - child[0].astype(t)
+        return d[0] * d[1] + d[1] * d[2] + d[2] * d[0]
+
+    depth = 0
+    todo = [(0, 1)]
+    while todo:
+        src, level = todo.pop()
+        depth = max(depth, level)
+        ch = list(nodes[src])
+        while len(ch) < 4:
+            best, best_area = -1, -1.0
+            for i, c in enumerate(ch):
+                if c[2] >= 0 and area(c) > best_area:
+                    best, best_area = i, area(c)
+            if best < 0:
+                break
+            ch[best:best + 1] = list(nodes[ch[best][2]])
+        todo.extend((c[2], level + 1) for c in ch if c[2] >= 0)
+    return depth
+
+
+def levels_crossed_model(nodes, bmin, bmax, start, direction):
+    """The deepest level (root = 1) of an inner node of `nodes` (lbvh_nodes / sah_nodes) whose box the line start + t direction
+    crosses, its ancestors' boxes with it: a ray that hits nothing visits at least that many nodes, on whichever form of the tree."""
+    centre = (np.asarray(bmin, dtype=np.float64) + np.asarray(bmax, dtype=np.float64)) * 0.5
+    s = np.asarray(start, dtype=np.float64) - centre
+    d = np.asarray(direction, dtype=np.float64)
+
+    def crosses(child):
+        t0, t1 = -np.inf, np.inf
+        for a in range(3):
+            lo, hi = float(child[0][a]), float(child[1][a])
+            if d[a] == 0.0:
+                if not lo <= s[a] <= hi:
+                    return False
+                continue
+            ta, tb = (lo - s[a]) / d[a], (hi - s[a]) / d[a]
+            t0, t1 = max(t0, min(ta, tb)), min(t1, max(ta, tb))
+        return t0 <= t1
+
+    deepest = 0
+    todo = [(0, 1)]
+    while todo:
+        i, level = todo.pop()
+        deepest = max(deepest, level)
+        todo.extend((c[2], level + 1) for c in nodes[i] if c[2] >= 0 and crosses(c))
+    return deepest
 
 
 def balanced_position_depth(n, leaf_max):

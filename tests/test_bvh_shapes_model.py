@@ -1,7 +1,7 @@
 """Adversarial geometry for the own BVH, CPU side: the model of the device build on trees that can be written down, the generators'
 promises, the host builder (through a host-only scene) on the deep and the tied scenes -- with the refused build that must leave no
-tree behind -- and the oracle's agreement with itself on every scene, frame and ray batch tests/test_gpu_bvh_shapes.py compares the
-library with."""
+tree behind, and with its restatement and that of the four-wide collapse pinned to sr_bvh_stats and sr_wide_tree_stats -- and the
+oracle's agreement with itself on every scene, frame and ray batch tests/test_gpu_bvh_shapes.py compares the library with."""
 import math
 
 import numpy as np
@@ -78,7 +78,7 @@ def test_generators_keep_their_promises():
     def inside(v9, bmin, bmax):
         v = v9.reshape(-1, 3)
         return bool(np.all(v >= bmin) and np.all(v <= bmax))
-    for name in ("deep", "chain", "chain_hittable", "chain_refused", "limit") + cases.TIE_SCENES:
+    for name in ("deep", "chain", "chain_hittable", "chain_refused", "limit", "wide_deep", "wide_edge", "private_edge") + cases.TIE_SCENES:
         v9, argb, bmin, bmax = cases.scene(name)
         assert inside(v9, bmin, bmax), name
         assert len(set(argb.tolist())) == len(argb) == v9.shape[0], name
@@ -104,6 +104,28 @@ def test_generators_keep_their_promises():
     assert bmax[2] - bmin[2] == 1.0 and np.all(0.5 * (v9[:, :, 2].min(axis=1) + v9[:, :, 2].max(axis=1)) == 0.0)
     assert len(set((bs.morton_keys(v9, bmin, bmax) & np.uint64(0x1249249249249249)).tolist())) == 1
     assert cases.chain_hittable() == cases.CHAIN_HITTABLE
+
+
+def test_cluster_staircase_is_a_path_with_a_cluster_on_every_node():
+    """One kept node per step under one triangle per leaf, a cluster's three equal keys two levels below it; the steps' boxes shrink
+    towards the point, so the wide tree (wide_depth_model) is nearly as deep: the two scenes' depths are those the GPU test prints."""
+    for m in (9, cases.PRIVATE_EDGE_STEPS, cases.WIDE_EDGE_STEPS, cases.WIDE_DEEP_STEPS):
+        v9, _, bmin, bmax = bs.cluster_staircase(m)
+        keys = bs.morton_keys(v9, bmin, bmax).reshape(m + 1, 3)
+        assert np.all(keys == keys[:, :1]) and len(set(keys[:, 0].tolist())) == m + 1
+        point = int(keys[m, 0])
+        assert [(int(k) ^ point).bit_length() - 1 for k in keys[:m, 0]] == [61 - i for i in range(m)]      # step i leaves the path at key bit 61 - i
+        depth, nodes, _ = bs.lbvh_model(v9, bmin, bmax, 1)
+        assert (depth, nodes) == (m + 3, 3 * (m + 1) - 1)
+    for name, want_depth, want_wide in (("wide_deep", 60, 48), ("wide_edge", 52, 40), ("private_edge", 32, 20)):
+        v9, _, bmin, bmax = cases.scene(name)
+        assert v9.shape[0] <= 400
+        depth, nodes, _ = bs.lbvh_model(v9, bmin, bmax, cases.WIDE_LEAF)
+        tree = bs.lbvh_nodes(v9, bmin, bmax, cases.WIDE_LEAF)
+        assert len(tree) == nodes and depth == want_depth <= 62
+        assert bs.wide_depth_model(tree, fp32=True) == bs.wide_depth_model(tree) == want_wide      # no comparison of areas is close
+    assert (3 * 40 + 2) * 528 <= 65536 < (3 * 41 + 2) * 528              # wide_edge: the deepest tree the packet walks take in its four-wide form
+    assert (3 * 20 + 2) * 1024 <= 65536 < (3 * 21 + 2) * 1024            # private_edge: ... and the private walks
 
 
 # ---- the host builder, through a host-only scene ----
@@ -143,6 +165,48 @@ def test_host_builder_on_the_shrinking_chain():
     s = host_scene("deep", 4)
     s.build((sa.MODE_BVH,))
     assert s.bvh_stats()[0] <= 62 and s.wide_tree_stats()[0] < 21
+
+
+@pytest.mark.parametrize("leaf", [1, 4])
+@pytest.mark.parametrize("name", ["soup", "deep", "chain", "limit", "wide_deep", "same_centre", "duplicates", "flat_thin", "flat_thick"])
+def test_wide_depth_model_equals_the_host_collapse(name, leaf):
+    """sah_nodes restates the host builder and wide_depth_model the collapse: depth, inner nodes and the wide depth of sr_bvh_stats and
+    sr_wide_tree_stats on host-only, host-built scenes."""
+    if name == "soup":
+        tris = (bs.soup(1000, (0.0, 0.0, 0.0), 0.9, 21), bs.colours(1000), bs.UNIT_MIN, bs.UNIT_MAX)
+    else:
+        tris = cases.scene(name)
+    s = sa.GpuScene(device=-1)
+    s.set_triangles(*tris)
+    s.debug_set(L.DBG_BVH_LEAF, leaf)
+    s.build((sa.MODE_BVH,))
+    nodes, depth = bs.sah_nodes(tris[0], tris[2], tris[3], leaf)
+    assert s.bvh_stats()[:2] == (depth, len(nodes))
+    assert s.wide_tree_stats()[0] == bs.wide_depth_model(nodes)
+
+
+def test_rays_through_the_point_cross_every_level():
+    """A ray that hits nothing visits a node on every level whose box it crosses.  The host-built chains: one of the rays through the
+    point the chain converges to crosses depth - 1 levels of inner nodes; the cluster staircases: every ray through their point crosses
+    all of them, more than the wide depth, and the rays that see the steps from behind hit nothing (bvh_shapes.cluster_staircase).
+    The oracle's own counters cannot say this: its nearest mode tests every triangle and its tree mode walks the reference tree, so the
+    levels are counted on the restated trees here, and the library's counters are asserted on the GPU."""
+    for name in ("chain", "deep"):
+        v9, _, bmin, bmax = cases.scene(name)
+        s, d = cases.ray_batch(name, "through_point")
+        miss = np.flatnonzero(~cases.oracle_trace(name, "through_point")["hit"].astype(bool))
+        for leaf in (1, 4):
+            nodes, depth = bs.sah_nodes(v9, bmin, bmax, leaf)
+            assert max(bs.levels_crossed_model(nodes, bmin, bmax, s[i], d[i]) for i in miss) >= depth - 1, (name, leaf)
+    for name in ("wide_deep", "wide_edge", "private_edge"):
+        v9, _, bmin, bmax = cases.scene(name)
+        nodes = bs.lbvh_nodes(v9, bmin, bmax, cases.WIDE_LEAF)
+        depth, wide = bs.lbvh_model(v9, bmin, bmax, cases.WIDE_LEAF)[0], bs.wide_depth_model(nodes, fp32=True)
+        s, d = cases.ray_batch(name, "through_point")
+        miss = np.flatnonzero(~cases.oracle_trace(name, "through_point")["hit"].astype(bool))
+        assert miss.size >= 4
+        for i in miss:
+            assert bs.levels_crossed_model(nodes, bmin, bmax, s[i], d[i]) >= depth - 1 > wide, (name, i)
 
 
 def _assert_no_tree(s):
@@ -198,6 +262,7 @@ def test_host_builder_on_equal_centres(name):
 
 # ---- the oracle agrees with itself on everything the GPU tests use ----
 FRAME_CASES = [("deep", f) for f in cases.DEEP_FRAMES] + [("limit", f) for f in ("plain", "shadows")] + \
+              [(s, f) for s in ("wide_deep", "private_edge") for f in cases.DEEP_FRAMES] + [("wide_edge", f) for f in ("plain", "shadows")] + \
               [(s, f) for s in cases.TIE_SCENES for f in cases.TIE_FRAMES] + [("chain_refused", "shadows"), ("obj", "plain"), ("obj", "shadows")]
 
 
@@ -218,7 +283,7 @@ def test_oracle_modes_agree_on_the_frames(scene_name, frame_name):
     assert 0 < np.count_nonzero(want != cases.BACKGROUND) < want.size
 
 
-@pytest.mark.parametrize("scene_name", ["deep", "limit", "chain_refused"] + list(cases.TIE_SCENES))
+@pytest.mark.parametrize("scene_name", ["deep", "limit", "chain_refused", "wide_deep", "wide_edge", "private_edge"] + list(cases.TIE_SCENES))
 def test_frames_show_background_lit_and_shadowed_pixels(scene_name):
     background, lit, shadowed = cases.pixel_classes(scene_name)
     assert background > 20 and lit > 20 and shadowed > 20, (background, lit, shadowed)
@@ -226,7 +291,8 @@ def test_frames_show_background_lit_and_shadowed_pixels(scene_name):
         assert np.count_nonzero(cases.oracle_frame("deep", "mirror") != cases.oracle_frame("deep", "plain")) > 20
 
 
-RAY_CASES = [(s, f) for s in ("chain", "chain_hittable") for f in cases.RAY_FAMILIES] + [("limit", "at_triangles")]
+RAY_CASES = [(s, f) for s in ("chain", "chain_hittable") for f in cases.RAY_FAMILIES] + [("limit", "at_triangles")] + \
+            [(s, f) for s in ("wide_deep", "wide_edge", "private_edge") for f in cases.RAY_FAMILIES]
 
 
 @pytest.mark.parametrize("scene_name,family", RAY_CASES)
@@ -245,6 +311,11 @@ def test_oracle_modes_agree_on_the_ray_batches(scene_name, family):
         # the low steps of the staircase are smaller than 1e-7: "zero" normals like the chain's small end (cases.chain_hittable), never hit
         m = cases.limit_staircase_length()
         assert len(np.unique(near["tri_index"][hit & (near["tri_index"] < m)])) >= 20
+    elif scene_name in cases.WIDE_STEPS:
+        # the steps hide one another; the small ones have "zero" normals like the chain's small end
+        stairs = 3 * (cases.WIDE_STEPS[scene_name] + 1)                   # (a fifth of them: half face away from the rays' start, the larger hide the smaller)
+        assert len(np.unique(near["tri_index"][hit])) >= (10 if family == "through_point" else stairs // 5)
+        assert (~hit).sum() >= (4 if family == "through_point" else 1)
     elif family == "at_triangles":
         n = cases.CHAIN_HITTABLE                                          # of the 200 as of the 29: triangles 0 .. 28
         aimed = np.repeat(np.arange(cases.scene(scene_name)[0].shape[0]), 5)

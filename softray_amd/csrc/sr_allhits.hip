@@ -8,10 +8,9 @@
 // of the own BVH and every ray of brute force runs the per-record loop with the same FP64 predicate and no fp32 stage.
 // The list of a ray lives in the lane's own ROW of memory (the caller's index / ray_frac rows, or rows of the scene's scratch where the
 // caller passed NULL): the fill count and the worst kept key stay in registers, no array is indexed in private memory.
-// A translation unit of its own: nothing in sr_kernels.hip / sr_pipeline.hip / sr_occluded.hip / sr_nearest.hip is touched.
-#include "sr_trace.h"
-
-#include <algorithm>
+// The pass driver, the lane's pick, the ray fetch and the walk's ray frame and node step are sr_batch.h's, shared with the other batch calls;
+// the list, the cull at the K-th hit, the two kernels and the walk / loop split of a pass are this file's.
+#include "sr_batch.h"
 
 namespace sr {
 
@@ -90,14 +89,13 @@ struct AhList {
 __device__ __forceinline__ float ah_tlim(double bound, double offset) {
     const double room = (bound - offset) + (fabs(bound) + offset) * 4.440892098500626e-16;
     if (!(room < 3.0e38)) return FLT_MAX;                    // (+inf, 1e300: no bound)
-    return (float)room * (1.0f + 9.5367431640625e-7f) + 1e-30f;
+    return cull_tlim(room);
 }
 
 struct AhArgs {
-    const double* starts; const double* dirs; const double* limits;
-    long long first; unsigned int count;
-    const unsigned int* order; const unsigned int* keys; unsigned int skip_mask; int take;
-    int endpoints, K, cull_k;
+    BatchRays rays;
+    PassSlice pass;
+    int K, cull_k;
     uint32_t* out_count;         // [n] or nullptr
     int32_t*  out_index;         // [n][K] or nullptr: then the rows of s_index, [pass][K]
     double*   out_frac;          // [n][K] or nullptr: then the rows of s_frac
@@ -105,16 +103,6 @@ struct AhArgs {
     unsigned long long* stats;
 };
 
-// lane j of the pass takes ray order[j] (order == nullptr: ray j); `take` as k_occluded's (0: the regular rays, 1: the others, 2: all)
-__device__ __forceinline__ bool ah_pick(const AhArgs& a, unsigned int j, unsigned int& src) {
-    bool live = j < a.count;
-    src = j;
-    if (a.order && live) {
-        src = a.order[j];
-        if (a.take != 2) live = ((a.keys[j] & a.skip_mask) != 0u) == (a.take == 1);
-    }
-    return live;
-}
 __device__ __forceinline__ void ah_rows(const AhArgs& a, size_t i, unsigned int src, AhList& L) {
     int32_t* ir = nullptr;
     double* fr = nullptr;
@@ -143,15 +131,14 @@ __global__ __launch_bounds__(256) void k_ah_walk(DevScene sc, AhArgs a) {
     const int tid = threadIdx.x;
     Stack st{reinterpret_cast<int32_t*>(lds_allhits) + tid, 256};
     unsigned int src;
-    const bool live = ah_pick(a, blockIdx.x * 256u + (unsigned int)tid, src);
+    const bool live = pass_pick(a.pass, blockIdx.x * 256u + (unsigned int)tid, src);
     Ctr c = {0, 0, 0, 0};
     if (live) {
-        const size_t i = (size_t)a.first + (size_t)src;
-        D3 s = mk(a.starts[3 * i], a.starts[3 * i + 1], a.starts[3 * i + 2]);
-        const D3 e = mk(a.dirs[3 * i], a.dirs[3 * i + 1], a.dirs[3 * i + 2]);
-        const D3 d = a.endpoints ? e - s : e;
-        const bool no_lim = a.limits == nullptr;                          // no limit: no comparison is made (a NaN ray_frac counts)
-        const double lim = no_lim ? (double)INFINITY : a.limits[i];
+        const size_t i = (size_t)a.pass.first + (size_t)src;
+        D3 s, d;
+        double lim;
+        fetch_ray(a.rays, i, (double)INFINITY, s, d, lim);
+        const bool no_lim = a.rays.limits == nullptr;                     // no limit: no comparison is made (a NaN ray_frac counts)
         c.rays = 1;
         AhList L;
         ah_rows(a, i, src, L);
@@ -167,36 +154,17 @@ __global__ __launch_bounds__(256) void k_ah_walk(DevScene sc, AhArgs a) {
         if (walk) {
             const bool cull_k = a.cull_k != 0 && a.K > 0;
             float tlim = ah_tlim((cull_k && L.full()) ? fmin(lim, L.wfrac) : lim, offset);
-            const float ox = (float)(s.x - sc.root.centre[0]), oy = (float)(s.y - sc.root.centre[1]), oz = (float)(s.z - sc.root.centre[2]);
-            const float ix = slab_inv((float)d.x), iy = slab_inv((float)d.y), iz = slab_inv((float)d.z);
-            const f2 I01 = {ix, iy}, I20 = {iz, ix}, I12 = {iy, iz};
-            const f2 B0 = {-ox * ix, -oy * iy}, B1 = {-oz * iz, -ox * ix}, B2 = {-oy * iy, -oz * iz};
-            const RayF rf = make_ray_f(sc, s, d);
+            SlabRay ray;
+            set_slab_ray(sc, s, d, ray);
             int sp = 0;
             int32_t ni = 0, leafA = -1, leafB = -1;
             for (;;) {
                 while (ni >= 0 && leafA < 0) {
                     const BvhNode n = sc.bnodes[ni];
                     c.nodes++;
-                    float t0, x0, t1, x1;
-                    node_slabs(n, I01, I20, I12, B0, B1, B2, t0, x0, t1, x1);
-                    const bool h0 = n.n0 >= 0 && t0 <= x0 && x0 >= 0.0f && t0 <= tlim;
-                    const bool h1 = n.n1 >= 0 && t1 <= x1 && x1 >= 0.0f && t1 <= tlim;
-                    const bool l0 = h0 && n.n0 > 0, l1 = h1 && n.n1 > 0;
-                    if (l0 && l1) {                                   // nearer leaf first
-                        const bool first0 = t0 <= t1;
-                        leafA = (first0 ? n.c0 : n.c1) | ((first0 ? n.n0 : n.n1) << kLeafShift);
-                        leafB = (first0 ? n.c1 : n.c0) | ((first0 ? n.n1 : n.n0) << kLeafShift);
-                    } else if (l0) leafA = n.c0 | (n.n0 << kLeafShift);
-                    else if (l1) leafA = n.c1 | (n.n1 << kLeafShift);
-                    const bool i0 = h0 && n.n0 == 0, i1 = h1 && n.n1 == 0;
-                    if (i0 && i1) {
-                        const bool first0 = t0 <= t1;
-                        st.put(sp++, first0 ? n.c1 : n.c0);           // the far child is re-tested against tlim when it is popped
-                        ni = first0 ? n.c0 : n.c1;
-                    } else if (i0) ni = n.c0;
-                    else if (i1) ni = n.c1;
-                    else ni = (sp > 0) ? st.get(--sp) : -1;
+                    bool h0, h1, first0;
+                    ray_node_hits(n, ray, tlim, h0, h1, first0);
+                    walk_step(n, h0, h1, first0, st, sp, ni, leafA, leafB);
                 }
                 if (leafA < 0) break;
                 while (leafA >= 0) {
@@ -204,7 +172,7 @@ __global__ __launch_bounds__(256) void k_ah_walk(DevScene sc, AhArgs a) {
                     leafA = leafB;
                     leafB = -1;
                     c.leaves++;
-                    for (uint32_t m = leaf_survivors(sc, lfirst, cn, rf, tlim); m; m &= m - 1u) {
+                    for (uint32_t m = leaf_survivors(sc, lfirst, cn, ray.rf, tlim); m; m &= m - 1u) {
                         const Rec128* r = &sc.btris[lfirst + (__ffs((int)m) - 1)];
                         double t; D3 pos;
                         c.geom++;
@@ -219,10 +187,7 @@ __global__ __launch_bounds__(256) void k_ah_walk(DevScene sc, AhArgs a) {
         L.finish();
         if (a.out_count) a.out_count[i] = L.count;
     }
-    if (STATS) {                                                      // (every thread of the workgroup arrives here)
-        uint32_t r = wave_sum(c.rays), g = wave_sum(c.geom), n2 = wave_sum(c.nodes), l2 = wave_sum(c.leaves);
-        block_stat_add(&a.stats[0], &a.stats[1], &a.stats[2], &a.stats[3], r, g, n2, l2);
-    }
+    if (STATS) block_stat_add(a.stats, c);                            // (every thread of the workgroup arrives here)
 }
 
 // The per-record loop.  CLIP = false, brute force: GeometryCollection's loop, tri_hit from the unclipped start, ray_frac = t, no box test.
@@ -231,15 +196,14 @@ __global__ __launch_bounds__(256) void k_ah_walk(DevScene sc, AhArgs a) {
 template <bool CLIP, bool EXTRA, bool STATS>
 __global__ __launch_bounds__(256) void k_ah_loop(DevScene sc, AhArgs a) {
     unsigned int src;
-    const bool live = ah_pick(a, blockIdx.x * 256u + threadIdx.x, src);
+    const bool live = pass_pick(a.pass, blockIdx.x * 256u + threadIdx.x, src);
     Ctr c = {0, 0, 0, 0};
     if (live) {
-        const size_t i = (size_t)a.first + (size_t)src;
-        D3 s = mk(a.starts[3 * i], a.starts[3 * i + 1], a.starts[3 * i + 2]);
-        const D3 e = mk(a.dirs[3 * i], a.dirs[3 * i + 1], a.dirs[3 * i + 2]);
-        const D3 d = a.endpoints ? e - s : e;
-        const bool no_lim = a.limits == nullptr;                          // no limit: no comparison is made (a NaN ray_frac counts)
-        const double lim = no_lim ? (double)INFINITY : a.limits[i];
+        const size_t i = (size_t)a.pass.first + (size_t)src;
+        D3 s, d;
+        double lim;
+        fetch_ray(a.rays, i, (double)INFINITY, s, d, lim);
+        const bool no_lim = a.rays.limits == nullptr;                     // no limit: no comparison is made (a NaN ray_frac counts)
         c.rays = 1;
         AhList L;
         ah_rows(a, i, src, L);
@@ -266,89 +230,57 @@ __global__ __launch_bounds__(256) void k_ah_loop(DevScene sc, AhArgs a) {
         L.finish();
         if (a.out_count) a.out_count[i] = L.count;
     }
-    if (STATS) {
-        uint32_t r = wave_sum(c.rays), g = wave_sum(c.geom), n2 = wave_sum(c.nodes), l2 = wave_sum(c.leaves);
-        block_stat_add(&a.stats[0], &a.stats[1], &a.stats[2], &a.stats[3], r, g, n2, l2);
-    }
+    if (STATS) block_stat_add(a.stats, c);
 }
 
 namespace {
 
 template <bool EXTRA>
 hipError_t launch_ah_walk(const AllHitsLaunch& L, const DevScene& sc, const AhArgs& a) {
-    const dim3 grid((a.count + 255u) / 256u);
-    const size_t lds = (size_t)(sc.bdepth + 2) * 256 * 4;
-    if (L.stats) hipLaunchKernelGGL((k_ah_walk<EXTRA, true>), grid, dim3(256), lds, L.stream, sc, a);
-    else hipLaunchKernelGGL((k_ah_walk<EXTRA, false>), grid, dim3(256), lds, L.stream, sc, a);
+    const size_t lds = (size_t)stack_levels(sc, MODE_BVH) * 256 * 4;
+    if (L.stats) hipLaunchKernelGGL((k_ah_walk<EXTRA, true>), lane_grid(a.pass), dim3(256), lds, L.stream, sc, a);
+    else hipLaunchKernelGGL((k_ah_walk<EXTRA, false>), lane_grid(a.pass), dim3(256), lds, L.stream, sc, a);
     return hipGetLastError();
 }
 
 template <bool CLIP, bool EXTRA>
 hipError_t launch_ah_loop(const AllHitsLaunch& L, const DevScene& sc, const AhArgs& a) {
-    const dim3 grid((a.count + 255u) / 256u);
-    if (L.stats) hipLaunchKernelGGL((k_ah_loop<CLIP, EXTRA, true>), grid, dim3(256), 0, L.stream, sc, a);
-    else hipLaunchKernelGGL((k_ah_loop<CLIP, EXTRA, false>), grid, dim3(256), 0, L.stream, sc, a);
+    if (L.stats) hipLaunchKernelGGL((k_ah_loop<CLIP, EXTRA, true>), lane_grid(a.pass), dim3(256), 0, L.stream, sc, a);
+    else hipLaunchKernelGGL((k_ah_loop<CLIP, EXTRA, false>), lane_grid(a.pass), dim3(256), 0, L.stream, sc, a);
     return hipGetLastError();
 }
 
-// pass by pass, back to back on the stream.  SR_MODE_BVH: a pass is ordered first (occl_order), the regular rays walk the tree, the tail runs
-// the per-record loop (loop_all: every ray does).  SR_MODE_BRUTE: the per-record loop in input order
+// SR_MODE_BVH: a pass is ordered first (occl_order), the regular rays walk the tree, the tail runs the per-record loop (loop_all: every ray
+// does).  SR_MODE_BRUTE: the per-record loop in input order
 template <bool EXTRA>
 hipError_t launch_all_hits_t(const AllHitsLaunch& L) {
     DevScene sc = L.sc;
     if (!EXTRA) { sc.extra = nullptr; sc.nextra = 0; }                                  // the model alone, whatever the scene's extra geometry
-    const unsigned int cap = (unsigned int)((L.pass + 255) / 256 * 256);
-    unsigned int* keys = L.sort_buf;
-    unsigned int* keys2 = keys + cap;
-    unsigned int* idx = keys2 + cap;
-    unsigned int* order = idx + cap;
-    const unsigned int skip = point_order_skip_mask(!L.input_order);
-    for (int64_t first = 0; first < L.n; first += L.pass) {
-        const unsigned int count = (unsigned int)std::min<int64_t>(L.pass, L.n - first);
-        hipError_t e;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        AhArgs a{};
-        a.starts = L.starts; a.dirs = L.dirs; a.limits = L.limits;
-        a.first = first; a.count = count;
-        a.endpoints = L.endpoints ? 1 : 0; a.K = L.max_hits; a.cull_k = (!L.count && L.max_hits > 0) ? 1 : 0;
-        a.out_count = L.count; a.out_index = L.index; a.out_frac = L.ray_frac;
-        a.s_index = L.scratch_index; a.s_frac = L.scratch_frac;
-        a.stats = L.stats;
-        a.take = 2;
-        if (L.mode == MODE_BVH) {
-            if (L.get_events) L.get_events(L.user, K_ALL_HITS_SORT, &e0, &e1);
-            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-            if ((e = occl_order(L.starts + 3 * first, L.dirs + 3 * first, L.limits ? L.limits + first : nullptr, count, L.endpoints, !L.input_order, sc.root, keys,
-                                keys2, idx, order, L.sort_temp, L.sort_temp_bytes, L.stream)) != hipSuccess)
-                return e;
-            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-            a.order = order; a.keys = keys2; a.skip_mask = skip;
-        }
-        e0 = e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_ALL_HITS, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        if (L.mode == MODE_BVH) {
-            if (L.loop_all) e = launch_ah_loop<true, EXTRA>(L, sc, a);
-            else {
-                a.take = 0;
-                e = launch_ah_walk<EXTRA>(L, sc, a);
-                a.take = 1;
-                if (e == hipSuccess) e = launch_ah_loop<true, EXTRA>(L, sc, a);
-            }
-        } else {
-            e = launch_ah_loop<false, EXTRA>(L, sc, a);
-        }
-        if (e != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    AhArgs a{};
+    a.rays = batch_rays(L.starts, L.dirs, L.limits, L.endpoints);
+    a.K = L.max_hits; a.cull_k = (!L.count && L.max_hits > 0) ? 1 : 0;
+    a.out_count = L.count; a.out_index = L.index; a.out_frac = L.ray_frac;
+    a.s_index = L.scratch_index; a.s_frac = L.scratch_frac;
+    a.stats = L.stats;
+    return run_passes(
+        L, L.mode == MODE_BVH, K_ALL_HITS_SORT, K_ALL_HITS,
+        [&](int64_t first, unsigned int count, const PassBuffers& b) { return order_ray_pass(L, a.rays, sc.root, first, count, b); },
+        [&](const PassSlice& p, const PassBuffers&) {
+            a.pass = p;
+            if (L.mode != MODE_BVH) return launch_ah_loop<false, EXTRA>(L, sc, a);
+            if (L.loop_all) return launch_ah_loop<true, EXTRA>(L, sc, a);
+            a.pass.take = 0;
+            const hipError_t e = launch_ah_walk<EXTRA>(L, sc, a);
+            a.pass.take = 1;
+            return e != hipSuccess ? e : launch_ah_loop<true, EXTRA>(L, sc, a);
+        });
 }
 
 }  // namespace
 
 hipError_t launch_all_hits(const AllHitsLaunch& L) {
     if (L.n <= 0) return hipSuccess;
-    if (L.pass <= 0 || L.pass > kAllHitsMaxPass || L.max_hits < 0 || L.max_hits > kAllHitsMax) return hipErrorInvalidValue;
+    if (L.pass <= 0 || L.pass > kBatchMaxPass || L.max_hits < 0 || L.max_hits > kAllHitsMax) return hipErrorInvalidValue;
     if (L.mode != MODE_BVH && L.mode != MODE_BRUTE) return hipErrorInvalidValue;
     if (L.max_hits > 0 && ((!L.index && !L.scratch_index) || (!L.ray_frac && !L.scratch_frac))) return hipErrorInvalidValue;
     return L.with_extra ? launch_all_hits_t<true>(L) : launch_all_hits_t<false>(L);

@@ -1923,6 +1923,94 @@ int run_staged(sr_scene* m, sr_scene* s, Staged* io, int count, bool upload_asyn
     return SR_OK;
 }
 
+// ---- The batch calls without a frame (sr_occluded_rays, sr_nearest_rays, sr_all_hits_rays, sr_closest_points): one refusal ladder, one entry
+// path for the host-array and the device-array variant, one setup of the passes
+// What such a call refuses before the device is looked at, in the header's order.  Every sentence follows "<name>: "
+struct ItemCall {
+    const char* name;
+    const char* null_args;        // a NULL array although n > 0
+    bool        max_hits;         // max_hits is an argument (0 .. SR_HITS_MAX)
+    uint32_t    options;          // the option bits the call knows
+    const char* unknown_options;
+    const char* voxels;           // SR_TARGET_VOXELS
+    const char* root;             // SR_TARGET_ROOT (nullptr: the call takes the extra geometry)
+    const char* ref_tree;         // SR_MODE_REF_TREE (nullptr: the call runs on the reference tree)
+};
+
+// `s`: in, the caller's scene; out, the scene that runs the call (the first part of a multi-device scene).  `args_ok`: no array the call
+// needs is NULL
+int item_call_check(const ItemCall& c, sr_scene*& s, int32_t target, int64_t n, bool args_ok, int32_t max_hits, uint32_t options, int& mode,
+                           bool& with_extra) {
+    const auto refuse = [&](int code, const char* why) { return fail(code, std::string(c.name) + ": " + why); };
+    if (s && !s->parts.empty()) s = s->parts[0];
+    if (!s) return refuse(SR_ERR_INVALID_ARG, "the scene is NULL");
+    if (n < 0) return refuse(SR_ERR_INVALID_ARG, "n is negative");
+    if (n > 0 && !args_ok) return refuse(SR_ERR_INVALID_ARG, c.null_args);
+    if (c.max_hits && (max_hits < 0 || max_hits > SR_HITS_MAX)) return refuse(SR_ERR_INVALID_ARG, "max_hits must be 0 .. SR_HITS_MAX (64)");
+    if (options & ~c.options) return refuse(SR_ERR_INVALID_ARG, c.unknown_options);
+    if (target & SR_TARGET_VOXELS) return refuse(SR_ERR_UNSUPPORTED, c.voxels);
+    if (c.root && (target & SR_TARGET_ROOT)) return refuse(SR_ERR_UNSUPPORTED, c.root);
+    with_extra = (target & SR_TARGET_ROOT) != 0;
+    mode = target & 0xff;
+    if (c.ref_tree && mode == SR_MODE_REF_TREE) return refuse(SR_ERR_UNSUPPORTED, c.ref_tree);
+    if (!s->have_model) return refuse(SR_ERR_NO_MODEL, "the scene has no model (sr_set_triangles, sr_load_3ds)");
+    int rc;
+    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays */ }
+    else if ((rc = check_mode(s, mode))) return rc;
+    if (s->device < 0) return refuse(SR_ERR_NO_DEVICE, "a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
+    return SR_OK;
+}
+
+// Where a call's arrays are.  The host-array variant: `io`, staged by run_staged, and the caller's four counters; the device-array variant
+// (io == nullptr): the caller's stream and statistics words, which are zeroed first
+struct ItemIo { Staged* io; int count; uint64_t* stats4; void* hip_stream; uint64_t* d_stats; };
+
+// An entry point: the refusals, the empty batch, the device, then run(s, mode, with_extra, stream, d_stats) -- the call's enqueue
+template <class Run>
+int item_call(const ItemCall& c, sr_scene* m, int32_t target, int64_t n, bool args_ok, int32_t max_hits, uint32_t options, const ItemIo& io, Run run) {
+    sr_scene* s = m;
+    int mode = 0; bool with_extra = false;
+    int rc = item_call_check(c, s, target, n, args_ok, max_hits, options, mode, with_extra);
+    if (rc || n == 0) return rc;
+    if ((rc = use_device(s))) return rc;
+    if (io.io)
+        return run_staged(m, s, io.io, io.count, true, io.stats4,
+                          [&](hipStream_t stream, unsigned long long* d_stats) { return run(s, mode, with_extra, stream, d_stats); });
+    hipStream_t stream = (hipStream_t)io.hip_stream;
+    if (io.d_stats) SR_HIP(hipMemsetAsync(io.d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
+    return run(s, mode, with_extra, stream, (unsigned long long*)io.d_stats);
+}
+
+// What the passes of such a call need before their launch, enqueued on `stream`: the geometry on the device; the call ordered like a frame
+// (render_common: a frame's facing partition moves the records the walk reads) -- `order` must live until the launch is enqueued; the pass
+// size, at most max_pass; `slots`, the pass rounded up to 256; (ordered: the call sorts its passes) the first scratch set's sort buffers; and
+// the launch fields every call has.  L.limits and L.input_order are the caller's to set
+int item_call_setup(sr_scene* s, int mode, int64_t n, int64_t max_pass, bool ordered, hipStream_t stream, unsigned long long* d_stats,
+                           std::unique_ptr<StreamOrder>& order, sr::BatchLaunch& L, size_t& slots) {
+    int rc = sync_geometry(s, (uint32_t)mode);
+    if (rc) return rc;
+    order.reset(new StreamOrder(s, stream));
+    if (order->entered) return order->entered;
+    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
+    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], max_pass) : max_pass;
+    L.n = n;
+    L.pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
+    slots = (size_t)(L.pass + 255) / 256 * 256;
+    if (ordered) {
+        sr_scene::BandScratch& B = s->scratch[0];
+        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
+        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
+        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
+        L.sort_buf = (unsigned int*)B.ray_sort.p;
+        L.sort_temp = B.ray_sort_temp.p;
+    }
+    L.stats = d_stats;
+    L.stream = stream;
+    L.user = s;
+    L.get_events = timing_events;
+    return SR_OK;
+}
+
 // An empty batch of a device variant that reports generators: the count is zeroed on the caller's stream, and no device is asked for
 int zero_generators_device(const sr_scene* s, uint64_t* d_generators, hipStream_t stream) {
     if (d_generators && s->device >= 0) {
@@ -3129,170 +3217,99 @@ int sr_trace_origin_rays(sr_scene* m, int32_t target, const double origin[3], in
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Any-hit ray batches with a distance limit (sr_occluded_rays): sr_trace_rays' hit && ray_frac <= limit, with early exit on the own BVH
+// The batch calls without a frame, on item_call_check / item_call / item_call_setup (above)
 // ------------------------------------------------------------------------------------------------------------------
-// what sr_occluded_rays[_device] refuses, in the header's order; `s`: the scene that runs the call (the first part of a multi-device scene)
-static int occluded_rays_check(sr_scene*& s, int32_t target, int64_t n, const void* starts, const void* dirs, const void* occluded, uint32_t options,
-                               int& mode, bool& with_extra) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_occluded_rays: the scene is NULL");
-    if (n < 0) return fail(SR_ERR_INVALID_ARG, "sr_occluded_rays: n is negative");
-    if (n > 0 && (!starts || !dirs || !occluded)) return fail(SR_ERR_INVALID_ARG, "sr_occluded_rays: starts, dirs and occluded must not be NULL when n > 0");
-    if (options & ~(uint32_t)(SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS))
-        return fail(SR_ERR_INVALID_ARG, "sr_occluded_rays: unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)");
-    if (target & SR_TARGET_VOXELS)
-        return fail(SR_ERR_UNSUPPORTED, "sr_occluded_rays: a hit on the voxel grid (SR_TARGET_VOXELS) has rayFrac 0, so a distance limit decides nothing; use sr_trace_rays");
-    with_extra = (target & SR_TARGET_ROOT) != 0;
-    mode = target & 0xff;
-    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "sr_occluded_rays: the scene has no model (sr_set_triangles, sr_load_3ds)");
-    int rc;
-    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays */ }
-    else if ((rc = check_mode(s, mode))) return rc;
-    if (s->device < 0) return fail(SR_ERR_NO_DEVICE, "sr_occluded_rays: a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
-    return SR_OK;
-}
+// ---- Any-hit ray batches with a distance limit (sr_occluded_rays): sr_trace_rays' hit && ray_frac <= limit, with early exit on the own BVH
+static const ItemCall kOccludedRaysCall = {
+    "sr_occluded_rays", "starts, dirs and occluded must not be NULL when n > 0", false,
+    SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS, "unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)",
+    "a hit on the voxel grid (SR_TARGET_VOXELS) has rayFrac 0, so a distance limit decides nothing; use sr_trace_rays", nullptr, nullptr};
 
-// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set's sort buffers
 static int occluded_rays_common(sr_scene* s, int mode, bool with_extra, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits,
                                 uint8_t* d_occluded, uint32_t options, hipStream_t stream, unsigned long long* d_stats) {
-    int rc = sync_geometry(s, (uint32_t)mode);
-    if (rc) return rc;
-    // ---- ordered like a frame (render_common): a frame's facing partition moves the records the walk reads ----
-    StreamOrder order(s, stream);
-    if (order.entered) return order.entered;
-    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
-    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kOcclMaxPass) : sr::kOcclMaxPass;
-    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
     sr::OccludedLaunch L{};
+    std::unique_ptr<StreamOrder> order;
+    size_t slots;
+    int rc = item_call_setup(s, mode, n, sr::kBatchMaxPass, mode == SR_MODE_BVH, stream, d_stats, order, L, slots);
+    if (rc) return rc;
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
     L.sc = dev_scene(s);
     L.mode = mode;
     L.with_extra = with_extra && !s->extra_recs.empty();
-    L.n = n; L.pass = pass;
     L.starts = d_starts; L.dirs = d_dirs; L.limits = d_limits; L.occluded = d_occluded;
     L.endpoints = (options & SR_RAYS_ENDPOINTS) != 0;
-    L.input_order = (options & SR_RAYS_COHERENT) != 0 || s->dbg[SR_DBG_KERNEL_SWITCH] == 46;    // (hook: input order whatever the options say)
-    L.nearest_walks = s->dbg[SR_DBG_KERNEL_SWITCH] == 47;                                       // (hook: nearest-hit walks plus the comparison)
-    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
+    L.input_order = (options & SR_RAYS_COHERENT) != 0 || hook == 46;                            // (hook: input order whatever the options say)
+    L.nearest_walks = hook == 47;                                                               // (hook: nearest-hit walks plus the comparison)
     L.refill_at = (hook >= 100 && hook <= 163) ? (int)(hook - 100) : -1;                       // (hook: persistent lanes, refilled at T busy ones)
     if (mode == SR_MODE_BVH) {
         if ((rc = ensure_num_cus(s))) return rc;
         L.persistent_blocks = s->num_cus * 4;
-        sr_scene::BandScratch& B = s->scratch[0];
-        const size_t slots = (size_t)(pass + 255) / 256 * 256;
-        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
-        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
-        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
-        L.sort_buf = (unsigned int*)B.ray_sort.p;
-        L.sort_temp = B.ray_sort_temp.p;
     }
-    L.stats = d_stats;
-    L.stream = stream;
-    L.user = s;
-    L.get_events = timing_events;
     SR_HIP(sr::launch_occluded(L));
     return SR_OK;
 }
 
 int sr_occluded_rays_device(sr_scene* m, int32_t target, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits, uint8_t* d_occluded,
                             uint32_t options, void* hip_stream, uint64_t* d_stats) {
-    sr_scene* s = m;
-    int mode; bool with_extra;
-    int rc = occluded_rays_check(s, target, n, d_starts, d_dirs, d_occluded, options, mode, with_extra);
-    if (rc || n == 0) return rc;
-    if ((rc = use_device(s))) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
-    return occluded_rays_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, d_occluded, options, stream, (unsigned long long*)d_stats);
+    return item_call(kOccludedRaysCall, m, target, n, d_starts && d_dirs && d_occluded, 0, options, {nullptr, 0, nullptr, hip_stream, d_stats},
+                     [&](sr_scene* s, int mode, bool with_extra, hipStream_t stream, unsigned long long* stats) {
+                         return occluded_rays_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, d_occluded, options, stream, stats);
+                     });
 }
 
 int sr_occluded_rays(sr_scene* m, int32_t target, int64_t n, const double* starts, const double* dirs, const double* limits, uint8_t* occluded,
                      uint32_t options, uint64_t stats[4]) {
-    sr_scene* s = m;
-    int mode; bool with_extra;
-    int rc = occluded_rays_check(s, target, n, starts, dirs, occluded, options, mode, with_extra);
-    if (rc || n == 0) return rc;
-    if ((rc = use_device(s))) return rc;
     Staged io[] = {{starts, nullptr, (size_t)n * 24}, {dirs, nullptr, (size_t)n * 24}, {limits, nullptr, (size_t)n * 8}, {nullptr, occluded, (size_t)n}};
-    return run_staged(m, s, io, 4, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
-        return occluded_rays_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev, (uint8_t*)io[3].dev,
-                                    options, stream, d_stats);
-    });
+    return item_call(kOccludedRaysCall, m, target, n, starts && dirs && occluded, 0, options, {io, 4, stats, nullptr, nullptr},
+                     [&](sr_scene* s, int mode, bool with_extra, hipStream_t stream, unsigned long long* d_stats) {
+                         return occluded_rays_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev,
+                                                     (uint8_t*)io[3].dev, options, stream, d_stats);
+                     });
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// Nearest-hit ray batches with a distance limit (sr_nearest_rays): sr_trace_rays' answers on the mirror extension's incoherent-ray route
-// ------------------------------------------------------------------------------------------------------------------
-// what sr_nearest_rays[_device] refuses, in the header's order; `s`: the scene that runs the call (the first part of a multi-device scene)
-static int nearest_rays_check(sr_scene*& s, int32_t target, int64_t n, const void* starts, const void* dirs, uint32_t options, int& mode, bool& with_extra) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_nearest_rays: the scene is NULL");
-    if (n < 0) return fail(SR_ERR_INVALID_ARG, "sr_nearest_rays: n is negative");
-    if (n > 0 && (!starts || !dirs)) return fail(SR_ERR_INVALID_ARG, "sr_nearest_rays: starts and dirs must not be NULL when n > 0");
-    if (options & ~(uint32_t)(SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS))
-        return fail(SR_ERR_INVALID_ARG, "sr_nearest_rays: unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)");
-    if (target & SR_TARGET_VOXELS)
-        return fail(SR_ERR_UNSUPPORTED, "sr_nearest_rays: the voxel grid (SR_TARGET_VOXELS) has no tree to walk and its hits have rayFrac 0; use sr_trace_rays");
-    with_extra = (target & SR_TARGET_ROOT) != 0;
-    mode = target & 0xff;
-    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "sr_nearest_rays: the scene has no model (sr_set_triangles, sr_load_3ds)");
-    int rc;
-    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays */ }
-    else if ((rc = check_mode(s, mode))) return rc;
-    if (s->device < 0) return fail(SR_ERR_NO_DEVICE, "sr_nearest_rays: a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
-    return SR_OK;
-}
+// ---- Nearest-hit ray batches with a distance limit (sr_nearest_rays): sr_trace_rays' answers on the mirror extension's incoherent-ray route
+static const ItemCall kNearestRaysCall = {
+    "sr_nearest_rays", "starts and dirs must not be NULL when n > 0", false,
+    SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS, "unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)",
+    "the voxel grid (SR_TARGET_VOXELS) has no tree to walk and its hits have rayFrac 0; use sr_trace_rays", nullptr, nullptr};
 
 struct NearestOut { uint8_t* hit; double* ray_frac; double* pos; double* normal; uint32_t* color; int32_t* tri; };
 
-// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set's sort and bounce buffers
+// (on the first scratch set's bounce buffers too)
 static int nearest_rays_common(sr_scene* s, int mode, bool with_extra, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits,
                                const NearestOut& out, uint32_t options, hipStream_t stream, unsigned long long* d_stats) {
-    int rc = sync_geometry(s, (uint32_t)mode);
-    if (rc) return rc;
-    // ---- ordered like a frame (render_common): a frame's facing partition moves the records the walk reads ----
-    StreamOrder order(s, stream);
-    if (order.entered) return order.entered;
-    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
-    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kNearestMaxPass) : sr::kNearestMaxPass;
-    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
     const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
     sr::NearestLaunch L{};
+    L.lane_walks = hook == 49;                                                                  // (hook: every ray through k_nr_lane)
+    const bool walked = mode == SR_MODE_BVH && !L.lane_walks;
+    std::unique_ptr<StreamOrder> order;
+    size_t slots;
+    int rc = item_call_setup(s, mode, n, sr::kBatchMaxPass, walked, stream, d_stats, order, L, slots);
+    if (rc) return rc;
     L.sc = dev_scene(s);
     L.mode = mode;
     L.with_extra = with_extra && !s->extra_recs.empty();
-    L.n = n; L.pass = pass;
     L.starts = d_starts; L.dirs = d_dirs; L.limits = d_limits;
     L.hit = out.hit; L.ray_frac = out.ray_frac; L.pos = out.pos; L.normal = out.normal; L.color = out.color; L.tri = out.tri;
     L.endpoints = (options & SR_RAYS_ENDPOINTS) != 0;
     L.input_order = (options & SR_RAYS_COHERENT) != 0 || hook == 48;                            // (hook: input order whatever the options say)
-    L.lane_walks = hook == 49;                                                                  // (hook: every ray through k_nr_lane)
     L.bvh2 = s->dbg[SR_DBG_BVH2_PACKETS] > 0;
     L.refill_at = (hook >= 100 && hook <= 163) ? (int)(hook - 100) : sr::kNearestRefillAt;     // (hook)
     L.lds_levels = (hook >= 200 && hook < 300) ? std::max(1, (int)(hook - 200)) : sr::pipeline_bounce_lds_levels();   // (hook)
-    if (mode == SR_MODE_BVH && !L.lane_walks) {
+    if (walked) {
         if ((rc = ensure_num_cus(s))) return rc;
         L.persistent_blocks = s->num_cus * 8;
         sr_scene::BandScratch& B = s->scratch[0];
-        const size_t slots = (size_t)(pass + 255) / 256 * 256;
-        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
-        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
-        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
         SR_HIP(B.bounce_prep.reserve(slots * 64));
         SR_HIP(B.bounce_res.reserve(slots * 16));
         // (k_nr_walk keeps L.lds_levels stack levels per lane in LDS, the rest of the worst case here: [level][lane of the grid])
         const long long deep = std::max(3 * (long long)s->b4_depth + 2, (long long)s->bvh.depth + 2) - L.lds_levels;
         if (deep > 0) SR_HIP(B.bounce_stack.reserve((size_t)deep * (size_t)s->num_cus * 8 * 256 * 4));
-        L.sort_buf = (unsigned int*)B.ray_sort.p;
-        L.sort_temp = B.ray_sort_temp.p;
         L.prep = B.bounce_prep.p;
         L.res = B.bounce_res.p;
         L.deep = (int32_t*)B.bounce_stack.p;
         L.deep_bytes = B.bounce_stack.cap;
     }
-    L.stats = d_stats;
-    L.stream = stream;
-    L.user = s;
-    L.get_events = timing_events;
     SR_HIP(sr::launch_nearest(L));
     return SR_OK;
 }
@@ -3300,84 +3317,50 @@ static int nearest_rays_common(sr_scene* s, int mode, bool with_extra, int64_t n
 int sr_nearest_rays_device(sr_scene* m, int32_t target, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits, uint8_t* d_hit,
                            double* d_ray_frac, double* d_pos, double* d_normal, uint32_t* d_color, int32_t* d_tri_index, uint32_t options, void* hip_stream,
                            uint64_t* d_stats) {
-    sr_scene* s = m;
-    int mode; bool with_extra;
-    int rc = nearest_rays_check(s, target, n, d_starts, d_dirs, options, mode, with_extra);
-    if (rc || n == 0) return rc;
-    if ((rc = use_device(s))) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
-    const NearestOut out{d_hit, d_ray_frac, d_pos, d_normal, d_color, d_tri_index};
-    return nearest_rays_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, out, options, stream, (unsigned long long*)d_stats);
+    return item_call(kNearestRaysCall, m, target, n, d_starts && d_dirs, 0, options, {nullptr, 0, nullptr, hip_stream, d_stats},
+                     [&](sr_scene* s, int mode, bool with_extra, hipStream_t stream, unsigned long long* stats) {
+                         const NearestOut out{d_hit, d_ray_frac, d_pos, d_normal, d_color, d_tri_index};
+                         return nearest_rays_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, out, options, stream, stats);
+                     });
 }
 
 int sr_nearest_rays(sr_scene* m, int32_t target, int64_t n, const double* starts, const double* dirs, const double* limits, uint8_t* hit, double* ray_frac,
                     double* pos, double* normal, uint32_t* color, int32_t* tri_index, uint32_t options, uint64_t stats[4]) {
-    sr_scene* s = m;
-    int mode; bool with_extra;
-    int rc = nearest_rays_check(s, target, n, starts, dirs, options, mode, with_extra);
-    if (rc || n == 0) return rc;
-    if ((rc = use_device(s))) return rc;
     Staged io[] = {{starts, nullptr, (size_t)n * 24}, {dirs, nullptr, (size_t)n * 24}, {limits, nullptr, (size_t)n * 8}, {nullptr, hit, (size_t)n},
                    {nullptr, ray_frac, (size_t)n * 8}, {nullptr, pos, (size_t)n * 24}, {nullptr, normal, (size_t)n * 24}, {nullptr, color, (size_t)n * 4},
                    {nullptr, tri_index, (size_t)n * 4}};
-    return run_staged(m, s, io, 9, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
-        const NearestOut out{(uint8_t*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev, (double*)io[6].dev, (uint32_t*)io[7].dev, (int32_t*)io[8].dev};
-        return nearest_rays_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev, out, options, stream,
-                                   d_stats);
-    });
+    return item_call(kNearestRaysCall, m, target, n, starts && dirs, 0, options, {io, 9, stats, nullptr, nullptr},
+                     [&](sr_scene* s, int mode, bool with_extra, hipStream_t stream, unsigned long long* d_stats) {
+                         const NearestOut out{(uint8_t*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev, (double*)io[6].dev, (uint32_t*)io[7].dev, (int32_t*)io[8].dev};
+                         return nearest_rays_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev, out, options,
+                                                    stream, d_stats);
+                     });
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// All hits along a ray, nearest first, with a count (sr_all_hits_rays): the walk that never stops at the first hit
-// ------------------------------------------------------------------------------------------------------------------
-// what sr_all_hits_rays[_device] refuses, in the header's order; `s`: the scene that runs the call (the first part of a multi-device scene)
-static int all_hits_check(sr_scene*& s, int32_t target, int64_t n, const void* starts, const void* dirs, int32_t max_hits, uint32_t options, int& mode,
-                          bool& with_extra) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: the scene is NULL");
-    if (n < 0) return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: n is negative");
-    if (n > 0 && (!starts || !dirs)) return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: starts and dirs must not be NULL when n > 0");
-    if (max_hits < 0 || max_hits > SR_HITS_MAX) return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: max_hits must be 0 .. SR_HITS_MAX (64)");
-    if (options & ~(uint32_t)(SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS))
-        return fail(SR_ERR_INVALID_ARG, "sr_all_hits_rays: unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)");
-    if (target & SR_TARGET_VOXELS)
-        return fail(SR_ERR_UNSUPPORTED, "sr_all_hits_rays: the voxel grid (SR_TARGET_VOXELS) has no tree to walk and its hits have rayFrac 0; use sr_trace_rays");
-    with_extra = (target & SR_TARGET_ROOT) != 0;
-    mode = target & 0xff;
-    if (mode == SR_MODE_REF_TREE)
-        return fail(SR_ERR_UNSUPPORTED, "sr_all_hits_rays: SR_MODE_REF_TREE has no notion of all hits (the literal walk ends in the first leaf that holds a hit inside "
-                                        "its box, and a triangle lives in several leaves); use SR_MODE_BVH or SR_MODE_BRUTE");
-    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "sr_all_hits_rays: the scene has no model (sr_set_triangles, sr_load_3ds)");
-    int rc;
-    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays */ }
-    else if ((rc = check_mode(s, mode))) return rc;
-    if (s->device < 0) return fail(SR_ERR_NO_DEVICE, "sr_all_hits_rays: a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
-    return SR_OK;
-}
+// ---- All hits along a ray, nearest first, with a count (sr_all_hits_rays): the walk that never stops at the first hit
+static const ItemCall kAllHitsRaysCall = {
+    "sr_all_hits_rays", "starts and dirs must not be NULL when n > 0", true,
+    SR_RAYS_COHERENT | SR_RAYS_ENDPOINTS, "unknown option bits (SR_RAYS_COHERENT and SR_RAYS_ENDPOINTS are the options)",
+    "the voxel grid (SR_TARGET_VOXELS) has no tree to walk and its hits have rayFrac 0; use sr_trace_rays", nullptr,
+    "SR_MODE_REF_TREE has no notion of all hits (the literal walk ends in the first leaf that holds a hit inside its box, and a triangle lives in several "
+    "leaves); use SR_MODE_BVH or SR_MODE_BRUTE"};
 
 struct AllHitsOut { uint32_t* count; int32_t* index; double* ray_frac; };
 
-// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set's sort buffers; a row the
-// caller does not want lives in that set's bounce buffers
+// (a row the caller does not want lives in the first scratch set's bounce buffers)
 static int all_hits_common(sr_scene* s, int mode, bool with_extra, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits,
                            int32_t max_hits, const AllHitsOut& out, uint32_t options, hipStream_t stream, unsigned long long* d_stats) {
-    int rc = sync_geometry(s, (uint32_t)mode);
-    if (rc) return rc;
-    // ---- ordered like a frame (render_common): a frame's facing partition moves the records the walk reads ----
-    StreamOrder order(s, stream);
-    if (order.entered) return order.entered;
-    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
-    int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kAllHitsMaxPass) : sr::kAllHitsMaxPass;
     const bool own_rows = max_hits > 0 && (!out.index || !out.ray_frac);
-    if (own_rows) want = std::min<int64_t>(want, (1ll << 24) / max_hits);            // (at most 2^24 slots of scratch rows: 128 + 64 MiB)
-    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
-    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
+    const int64_t max_pass = own_rows ? std::min<int64_t>(sr::kBatchMaxPass, (1ll << 24) / max_hits) : sr::kBatchMaxPass;   // (at most 2^24 slots of scratch rows: 128 + 64 MiB)
     sr::AllHitsLaunch L{};
+    std::unique_ptr<StreamOrder> order;
+    size_t slots;
+    int rc = item_call_setup(s, mode, n, max_pass, mode == SR_MODE_BVH, stream, d_stats, order, L, slots);
+    if (rc) return rc;
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
     L.sc = dev_scene(s);
     L.mode = mode;
     L.with_extra = with_extra && !s->extra_recs.empty();
-    L.n = n; L.pass = pass;
     L.starts = d_starts; L.dirs = d_dirs; L.limits = d_limits;
     L.max_hits = max_hits;
     L.count = out.count;
@@ -3387,14 +3370,6 @@ static int all_hits_common(sr_scene* s, int mode, bool with_extra, int64_t n, co
     L.input_order = (options & SR_RAYS_COHERENT) != 0 || hook == 50;                            // (hook: input order whatever the options say)
     L.loop_all = hook == 51;                                                                    // (hook: every ray through the per-record loop)
     sr_scene::BandScratch& B = s->scratch[0];
-    const size_t slots = (size_t)(pass + 255) / 256 * 256;
-    if (mode == SR_MODE_BVH) {
-        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
-        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
-        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
-        L.sort_buf = (unsigned int*)B.ray_sort.p;
-        L.sort_temp = B.ray_sort_temp.p;
-    }
     if (max_hits > 0 && !out.index) {
         SR_HIP(B.bounce_res.reserve(slots * (size_t)max_hits * sizeof(int32_t)));
         L.scratch_index = (int32_t*)B.bounce_res.p;
@@ -3403,135 +3378,78 @@ static int all_hits_common(sr_scene* s, int mode, bool with_extra, int64_t n, co
         SR_HIP(B.bounce_prep.reserve(slots * (size_t)max_hits * sizeof(double)));
         L.scratch_frac = (double*)B.bounce_prep.p;
     }
-    L.stats = d_stats;
-    L.stream = stream;
-    L.user = s;
-    L.get_events = timing_events;
     SR_HIP(sr::launch_all_hits(L));
     return SR_OK;
 }
 
 int sr_all_hits_rays_device(sr_scene* m, int32_t target, int64_t n, const double* d_starts, const double* d_dirs, const double* d_limits, int32_t max_hits,
                             uint32_t* d_count, int32_t* d_index, double* d_ray_frac, uint32_t options, void* hip_stream, uint64_t* d_stats) {
-    sr_scene* s = m;
-    int mode; bool with_extra;
-    int rc = all_hits_check(s, target, n, d_starts, d_dirs, max_hits, options, mode, with_extra);
-    if (rc || n == 0) return rc;
-    if ((rc = use_device(s))) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
-    const AllHitsOut out{d_count, d_index, d_ray_frac};
-    return all_hits_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, max_hits, out, options, stream, (unsigned long long*)d_stats);
+    return item_call(kAllHitsRaysCall, m, target, n, d_starts && d_dirs, max_hits, options, {nullptr, 0, nullptr, hip_stream, d_stats},
+                     [&](sr_scene* s, int mode, bool with_extra, hipStream_t stream, unsigned long long* stats) {
+                         const AllHitsOut out{d_count, d_index, d_ray_frac};
+                         return all_hits_common(s, mode, with_extra, n, d_starts, d_dirs, d_limits, max_hits, out, options, stream, stats);
+                     });
 }
 
 int sr_all_hits_rays(sr_scene* m, int32_t target, int64_t n, const double* starts, const double* dirs, const double* limits, int32_t max_hits, uint32_t* count,
                      int32_t* index, double* ray_frac, uint32_t options, uint64_t stats[4]) {
-    sr_scene* s = m;
-    int mode; bool with_extra;
-    int rc = all_hits_check(s, target, n, starts, dirs, max_hits, options, mode, with_extra);
-    if (rc || n == 0) return rc;
-    if ((rc = use_device(s))) return rc;
     const size_t rows = (size_t)n * (size_t)max_hits;
     Staged io[] = {{starts, nullptr, (size_t)n * 24}, {dirs, nullptr, (size_t)n * 24}, {limits, nullptr, (size_t)n * 8}, {nullptr, count, (size_t)n * 4},
                    {nullptr, max_hits > 0 ? index : nullptr, rows * 4}, {nullptr, max_hits > 0 ? ray_frac : nullptr, rows * 8}};
-    return run_staged(m, s, io, 6, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
-        const AllHitsOut out{(uint32_t*)io[3].dev, (int32_t*)io[4].dev, (double*)io[5].dev};
-        return all_hits_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev, max_hits, out, options,
-                               stream, d_stats);
-    });
+    return item_call(kAllHitsRaysCall, m, target, n, starts && dirs, max_hits, options, {io, 6, stats, nullptr, nullptr},
+                     [&](sr_scene* s, int mode, bool with_extra, hipStream_t stream, unsigned long long* d_stats) {
+                         const AllHitsOut out{(uint32_t*)io[3].dev, (int32_t*)io[4].dev, (double*)io[5].dev};
+                         return all_hits_common(s, mode, with_extra, n, (const double*)io[0].dev, (const double*)io[1].dev, (const double*)io[2].dev, max_hits, out,
+                                                options, stream, d_stats);
+                     });
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// The closest point of the mesh for a batch of points (sr_closest_points): the distance query of the own BVH
-// ------------------------------------------------------------------------------------------------------------------
-// what sr_closest_points[_device] refuses, in the header's order; `s`: the scene that runs the call (the first part of a multi-device scene)
-static int closest_check(sr_scene*& s, int32_t target, int64_t n, const void* points, uint32_t options, int& mode) {
-    if (s && !s->parts.empty()) s = s->parts[0];
-    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_closest_points: the scene is NULL");
-    if (n < 0) return fail(SR_ERR_INVALID_ARG, "sr_closest_points: n is negative");
-    if (n > 0 && !points) return fail(SR_ERR_INVALID_ARG, "sr_closest_points: points must not be NULL when n > 0");
-    if (options & ~(uint32_t)SR_POINTS_COHERENT) return fail(SR_ERR_INVALID_ARG, "sr_closest_points: unknown option bits (SR_POINTS_COHERENT is the only option)");
-    if (target & SR_TARGET_VOXELS)
-        return fail(SR_ERR_UNSUPPORTED, "sr_closest_points: the voxel grid (SR_TARGET_VOXELS) has no triangles to measure a distance to");
-    if (target & SR_TARGET_ROOT)
-        return fail(SR_ERR_UNSUPPORTED, "sr_closest_points: the closest points of the extra geometry (SR_TARGET_ROOT) are not part of the call; pass the mode alone");
-    mode = target & 0xff;
-    if (mode == SR_MODE_REF_TREE)
-        return fail(SR_ERR_UNSUPPORTED, "sr_closest_points: SR_MODE_REF_TREE has no distance query (a triangle lives in several leaves of the reference tree); use "
-                                        "SR_MODE_BVH or SR_MODE_BRUTE");
-    if (!s->have_model) return fail(SR_ERR_NO_MODEL, "sr_closest_points: the scene has no model (sr_set_triangles, sr_load_3ds)");
-    int rc;
-    if (s->ntris == 0 && mode == SR_MODE_BRUTE) { /* an empty model is fine for brute force, as in sr_trace_rays: every point misses */ }
-    else if ((rc = check_mode(s, mode))) return rc;
-    if (s->device < 0) return fail(SR_ERR_NO_DEVICE, "sr_closest_points: a host-only scene has no HIP device to walk on (compute is never emulated on the CPU)");
-    return SR_OK;
-}
+// ---- The closest point of the mesh for a batch of points (sr_closest_points): the distance query of the own BVH
+static const ItemCall kClosestPointsCall = {
+    "sr_closest_points", "points must not be NULL when n > 0", false,
+    SR_POINTS_COHERENT, "unknown option bits (SR_POINTS_COHERENT is the only option)",
+    "the voxel grid (SR_TARGET_VOXELS) has no triangles to measure a distance to",
+    "the closest points of the extra geometry (SR_TARGET_ROOT) are not part of the call; pass the mode alone",
+    "SR_MODE_REF_TREE has no distance query (a triangle lives in several leaves of the reference tree); use SR_MODE_BVH or SR_MODE_BRUTE"};
 
 struct ClosestOut { int32_t* tri; double* dist; double* pos; double* uv; };
 
-// the passes of one call, enqueued on `stream` (device arrays): ordered like a frame, on the first scratch set's sort buffers
 static int closest_common(sr_scene* s, int mode, int64_t n, const double* d_points, const double* d_limits, const ClosestOut& out, uint32_t options,
                           hipStream_t stream, unsigned long long* d_stats) {
-    int rc = sync_geometry(s, (uint32_t)mode);
-    if (rc) return rc;
-    // ---- ordered like a frame (render_common): a frame's facing partition moves the records the walk reads ----
-    StreamOrder order(s, stream);
-    if (order.entered) return order.entered;
-    if (s->pre_ready_set) SR_HIP(hipStreamWaitEvent(stream, s->pre_ready, 0));      // the records' order, written on another stream perhaps
-    const int64_t want = s->dbg[SR_DBG_BAND_SAMPLES] > 0 ? std::min<int64_t>(s->dbg[SR_DBG_BAND_SAMPLES], sr::kClosestMaxPass) : sr::kClosestMaxPass;
-    const int64_t pass = std::max<int64_t>(1, std::min<int64_t>(want, n));
-    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
     sr::ClosestLaunch L{};
+    std::unique_ptr<StreamOrder> order;
+    size_t slots;
+    int rc = item_call_setup(s, mode, n, sr::kBatchMaxPass, mode == SR_MODE_BVH, stream, d_stats, order, L, slots);
+    if (rc) return rc;
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
     L.sc = dev_scene(s);
     L.mode = mode;
-    L.n = n; L.pass = pass;
     L.points = d_points; L.limits = d_limits;
     L.tri = out.tri; L.dist = out.dist; L.pos = out.pos; L.uv = out.uv;
     L.input_order = (options & SR_POINTS_COHERENT) != 0 || hook == 52;                          // (hook: input order whatever the options say)
     L.loop_all = hook == 53;                                                                    // (hook: every point through the per-record loop)
-    if (mode == SR_MODE_BVH) {
-        sr_scene::BandScratch& B = s->scratch[0];
-        const size_t slots = (size_t)(pass + 255) / 256 * 256;
-        L.sort_temp_bytes = sr::point_order_temp_bytes((unsigned)slots);
-        SR_HIP(B.ray_sort.reserve((4 * slots + 64) * sizeof(unsigned int)));
-        SR_HIP(B.ray_sort_temp.reserve(L.sort_temp_bytes));
-        L.sort_buf = (unsigned int*)B.ray_sort.p;
-        L.sort_temp = B.ray_sort_temp.p;
-    }
-    L.stats = d_stats;
-    L.stream = stream;
-    L.user = s;
-    L.get_events = timing_events;
     SR_HIP(sr::launch_closest(L));
     return SR_OK;
 }
 
 int sr_closest_points_device(sr_scene* m, int32_t target, int64_t n, const double* d_points, const double* d_max_dist, int32_t* d_tri_index, double* d_dist,
                              double* d_pos, double* d_uv, uint32_t options, void* hip_stream, uint64_t* d_stats) {
-    sr_scene* s = m;
-    int mode;
-    int rc = closest_check(s, target, n, d_points, options, mode);
-    if (rc || n == 0) return rc;
-    if ((rc = use_device(s))) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (d_stats) SR_HIP(hipMemsetAsync(d_stats, 0, SR_STATS_COUNT * sizeof(uint64_t), stream));
-    const ClosestOut out{d_tri_index, d_dist, d_pos, d_uv};
-    return closest_common(s, mode, n, d_points, d_max_dist, out, options, stream, (unsigned long long*)d_stats);
+    return item_call(kClosestPointsCall, m, target, n, d_points != nullptr, 0, options, {nullptr, 0, nullptr, hip_stream, d_stats},
+                     [&](sr_scene* s, int mode, bool, hipStream_t stream, unsigned long long* stats) {
+                         const ClosestOut out{d_tri_index, d_dist, d_pos, d_uv};
+                         return closest_common(s, mode, n, d_points, d_max_dist, out, options, stream, stats);
+                     });
 }
 
 int sr_closest_points(sr_scene* m, int32_t target, int64_t n, const double* points, const double* max_dist, int32_t* tri_index, double* dist, double* pos,
                       double* uv, uint32_t options, uint64_t stats[4]) {
-    sr_scene* s = m;
-    int mode;
-    int rc = closest_check(s, target, n, points, options, mode);
-    if (rc || n == 0) return rc;
-    if ((rc = use_device(s))) return rc;
     Staged io[] = {{points, nullptr, (size_t)n * 24}, {max_dist, nullptr, (size_t)n * 8}, {nullptr, tri_index, (size_t)n * 4}, {nullptr, dist, (size_t)n * 8},
                    {nullptr, pos, (size_t)n * 24}, {nullptr, uv, (size_t)n * 16}};
-    return run_staged(m, s, io, 6, true, stats, [&](hipStream_t stream, unsigned long long* d_stats) {
-        const ClosestOut out{(int32_t*)io[2].dev, (double*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev};
-        return closest_common(s, mode, n, (const double*)io[0].dev, (const double*)io[1].dev, out, options, stream, d_stats);
-    });
+    return item_call(kClosestPointsCall, m, target, n, points != nullptr, 0, options, {io, 6, stats, nullptr, nullptr},
+                     [&](sr_scene* s, int mode, bool, hipStream_t stream, unsigned long long* d_stats) {
+                         const ClosestOut out{(int32_t*)io[2].dev, (double*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev};
+                         return closest_common(s, mode, n, (const double*)io[0].dev, (const double*)io[1].dev, out, options, stream, d_stats);
+                     });
 }
 
 // ------------------------------------------------------------------------------------------------------------------

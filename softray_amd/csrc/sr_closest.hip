@@ -7,13 +7,13 @@
 // and every point of brute force, runs the per-record loop over v9 in index order with the same FP64 routine and no fp32 stage.
 // The cull is exact: a box is skipped only when its deflated bound strictly exceeds the best squared distance found so far
 // (or the squared limit, inflated), so a triangle that ties the answer with a lower index is always visited.
-// A translation unit of its own: no other kernel is touched.
+// The pass driver and the lane's pick are sr_batch.h's, shared with the other batch calls; the keys and the sort of a pass, the bound, the
+// walk's node step (its stack word carries a bound that a pop re-tests; sharing the leaf half cost the lattice 0.5 %: profiles/batch_refactor)
+// and the two kernels are this file's.
 #include <hipcub/hipcub.hpp>
 
+#include "sr_batch.h"
 #include "sr_closest.h"
-#include "sr_trace.h"
-
-#include <algorithm>
 
 namespace sr {
 
@@ -49,22 +49,10 @@ __global__ __launch_bounds__(256) void k_cp_keys(const double* __restrict__ poin
 
 struct CpArgs {
     const double* points; const double* limits;
-    long long first; unsigned int count;
-    const unsigned int* order; const unsigned int* keys; unsigned int skip_mask; int take;
+    PassSlice pass;
     int32_t* out_tri; double* out_dist; double* out_pos; double* out_uv;
     unsigned long long* stats;
 };
-
-// lane j of the pass takes point order[j] (order == nullptr: point j); take 0: the regular points, 1: the others, 2: all
-__device__ __forceinline__ bool cp_pick(const CpArgs& a, unsigned int j, unsigned int& src) {
-    bool live = j < a.count;
-    src = j;
-    if (a.order && live) {
-        src = a.order[j];
-        if (a.take != 2) live = ((a.keys[j] & a.skip_mask) != 0u) == (a.take == 1);
-    }
-    return live;
-}
 
 // (d2, j) of one triangle against the running best: a NaN d2 fails both comparisons, equal d2 goes to the lower TriangleIndex
 __device__ __forceinline__ bool cp_better(double d2, int32_t j, double best, int32_t bj) { return d2 < best || (d2 == best && j < bj); }
@@ -123,10 +111,10 @@ __global__ __launch_bounds__(256) void k_cp_walk(DevScene sc, CpArgs a) {
     const int tid = threadIdx.x;
     Stack st{reinterpret_cast<int32_t*>(lds_closest) + tid, 256};
     unsigned int src;
-    const bool live = cp_pick(a, blockIdx.x * 256u + (unsigned int)tid, src);
+    const bool live = pass_pick(a.pass, blockIdx.x * 256u + (unsigned int)tid, src);
     Ctr c = {0, 0, 0, 0};
     if (live) {
-        const size_t i = (size_t)a.first + (size_t)src;
+        const size_t i = (size_t)a.pass.first + (size_t)src;
         const double q[3] = {a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]};
         const bool no_lim = a.limits == nullptr;
         const double lim = no_lim ? (double)INFINITY : a.limits[i];
@@ -203,10 +191,10 @@ __global__ __launch_bounds__(256) void k_cp_walk(DevScene sc, CpArgs a) {
 template <bool STATS>
 __global__ __launch_bounds__(256) void k_cp_loop(DevScene sc, CpArgs a) {
     unsigned int src;
-    const bool live = cp_pick(a, blockIdx.x * 256u + threadIdx.x, src);
+    const bool live = pass_pick(a.pass, blockIdx.x * 256u + threadIdx.x, src);
     Ctr c = {0, 0, 0, 0};
     if (live) {
-        const size_t i = (size_t)a.first + (size_t)src;
+        const size_t i = (size_t)a.pass.first + (size_t)src;
         const double q[3] = {a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]};
         const bool no_lim = a.limits == nullptr;
         const double lim = no_lim ? (double)INFINITY : a.limits[i];
@@ -228,23 +216,21 @@ __global__ __launch_bounds__(256) void k_cp_loop(DevScene sc, CpArgs a) {
 namespace {
 
 hipError_t launch_cp_walk(const ClosestLaunch& L, const CpArgs& a) {
-    const dim3 grid((a.count + 255u) / 256u);
-    const size_t lds = (size_t)(L.sc.bdepth + 2) * 256 * 4;
-    if (L.stats) hipLaunchKernelGGL((k_cp_walk<true>), grid, dim3(256), lds, L.stream, L.sc, a);
-    else hipLaunchKernelGGL((k_cp_walk<false>), grid, dim3(256), lds, L.stream, L.sc, a);
+    const size_t lds = (size_t)stack_levels(L.sc, MODE_BVH) * 256 * 4;
+    if (L.stats) hipLaunchKernelGGL((k_cp_walk<true>), lane_grid(a.pass), dim3(256), lds, L.stream, L.sc, a);
+    else hipLaunchKernelGGL((k_cp_walk<false>), lane_grid(a.pass), dim3(256), lds, L.stream, L.sc, a);
     return hipGetLastError();
 }
 
 hipError_t launch_cp_loop(const ClosestLaunch& L, const CpArgs& a) {
-    const dim3 grid((a.count + 255u) / 256u);
-    if (L.stats) hipLaunchKernelGGL((k_cp_loop<true>), grid, dim3(256), 16, L.stream, L.sc, a);             // (cp_stat_add's four words)
-    else hipLaunchKernelGGL((k_cp_loop<false>), grid, dim3(256), 0, L.stream, L.sc, a);
+    if (L.stats) hipLaunchKernelGGL((k_cp_loop<true>), lane_grid(a.pass), dim3(256), 16, L.stream, L.sc, a);    // (cp_stat_add's four words)
+    else hipLaunchKernelGGL((k_cp_loop<false>), lane_grid(a.pass), dim3(256), 0, L.stream, L.sc, a);
     return hipGetLastError();
 }
 
 // the order of a pass: the regular points first -- sorted: by Morton cell, ties in input order; !sorted: in input order -- then the others
-hipError_t cp_order(const ClosestLaunch& L, const double* points, unsigned int n, bool sorted, unsigned int* keys, unsigned int* keys2, unsigned int* idx,
-                    unsigned int* order_out) {
+hipError_t cp_order(const ClosestLaunch& L, const double* points, unsigned int n, const PassBuffers& b) {
+    const bool sorted = !L.input_order;
     const RootBox& root = L.sc.root;
     double s[3];
     for (int k = 0; k < 3; ++k) { const double e = root.max[k] - root.min[k]; s[k] = e > 0 ? 128.0 / e : 0.0; }
@@ -252,60 +238,38 @@ hipError_t cp_order(const ClosestLaunch& L, const double* points, unsigned int n
     int end_bit = 0;
     while ((skip >> end_bit) != 0u) ++end_bit;                            // the skip bit is the key's highest
     hipLaunchKernelGGL(k_cp_keys, dim3((n + 255u) / 256u), dim3(256), 0, L.stream, points, n, sorted ? 1 : 0, skip, root.min[0], root.min[1], root.min[2], s[0],
-                       s[1], s[2], root.centre[0], root.centre[1], root.centre[2], closest_diag(root.min, root.max), keys, idx);
+                       s[1], s[2], root.centre[0], root.centre[1], root.centre[2], closest_diag(root.min, root.max), b.keys, b.idx);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     size_t temp_bytes = L.sort_temp_bytes;
-    return hipcub::DeviceRadixSort::SortPairs(L.sort_temp, temp_bytes, (const unsigned int*)keys, keys2, (const unsigned int*)idx, order_out, (int)n, 0, end_bit,
+    return hipcub::DeviceRadixSort::SortPairs(L.sort_temp, temp_bytes, (const unsigned int*)b.keys, b.keys2, (const unsigned int*)b.idx, b.order, (int)n, 0, end_bit,
                                               L.stream);
 }
 
 }  // namespace
 
-// pass by pass, back to back on the stream.  SR_MODE_BVH: a pass is ordered first, the regular points walk the tree, the tail runs the
-// per-record loop (loop_all: every point does).  SR_MODE_BRUTE: the per-record loop in input order
+// SR_MODE_BVH: a pass is ordered first, the regular points walk the tree, the tail runs the per-record loop (loop_all: every point does).
+// SR_MODE_BRUTE: the per-record loop in input order
 hipError_t launch_closest(const ClosestLaunch& L) {
     if (L.n <= 0) return hipSuccess;
-    if (L.pass <= 0 || L.pass > kClosestMaxPass) return hipErrorInvalidValue;
+    if (L.pass <= 0 || L.pass > kBatchMaxPass) return hipErrorInvalidValue;
     if (L.mode != MODE_BVH && L.mode != MODE_BRUTE) return hipErrorInvalidValue;
-    if (L.mode == MODE_BVH && (L.sc.bdepth + 2) * 256 * 4 > 65536) return hipErrorInvalidValue;
-    const unsigned int cap = (unsigned int)((L.pass + 255) / 256 * 256);
-    unsigned int* keys = L.sort_buf;
-    unsigned int* keys2 = keys + cap;
-    unsigned int* idx = keys2 + cap;
-    unsigned int* order = idx + cap;
-    for (int64_t first = 0; first < L.n; first += L.pass) {
-        const unsigned int count = (unsigned int)std::min<int64_t>(L.pass, L.n - first);
-        hipError_t e;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        CpArgs a{};
-        a.points = L.points; a.limits = L.limits;
-        a.first = first; a.count = count;
-        a.out_tri = L.tri; a.out_dist = L.dist; a.out_pos = L.pos; a.out_uv = L.uv;
-        a.stats = L.stats;
-        a.take = 2;
-        if (L.mode == MODE_BVH) {
-            if (L.get_events) L.get_events(L.user, K_CLOSEST_SORT, &e0, &e1);
-            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-            if ((e = cp_order(L, L.points + 3 * first, count, !L.input_order, keys, keys2, idx, order)) != hipSuccess) return e;
-            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-            a.order = order; a.keys = keys2; a.skip_mask = point_order_skip_mask(!L.input_order);
-        }
-        e0 = e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_CLOSEST, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        if (L.mode == MODE_BVH && !L.loop_all) {
-            a.take = 0;
-            e = launch_cp_walk(L, a);
-            a.take = 1;
-            if (e == hipSuccess) e = launch_cp_loop(L, a);
-        } else {
-            e = launch_cp_loop(L, a);
-        }
-        if (e != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    if (L.mode == MODE_BVH && stack_levels(L.sc, MODE_BVH) * 256 * 4 > 65536) return hipErrorInvalidValue;
+    CpArgs a{};
+    a.points = L.points; a.limits = L.limits;
+    a.out_tri = L.tri; a.out_dist = L.dist; a.out_pos = L.pos; a.out_uv = L.uv;
+    a.stats = L.stats;
+    return run_passes(
+        L, L.mode == MODE_BVH, K_CLOSEST_SORT, K_CLOSEST,
+        [&](int64_t first, unsigned int count, const PassBuffers& b) { return cp_order(L, L.points + 3 * first, count, b); },
+        [&](const PassSlice& p, const PassBuffers&) {
+            a.pass = p;
+            if (L.mode != MODE_BVH || L.loop_all) return launch_cp_loop(L, a);
+            a.pass.take = 0;
+            const hipError_t e = launch_cp_walk(L, a);
+            a.pass.take = 1;
+            return e != hipSuccess ? e : launch_cp_loop(L, a);
+        });
 }
 
 }  // namespace sr

@@ -402,79 +402,70 @@ hipError_t dir_order(const double* dirs, unsigned int n, bool sorted, unsigned i
 hipError_t occl_order(const double* starts, const double* dirs, const double* limits, unsigned int n, bool endpoints, bool sorted, const RootBox& root,
                       unsigned int* keys, unsigned int* keys2, unsigned int* idx, unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
 
-// sr_occluded_rays (sr_occluded.hip): occluded[i] = sr_trace_rays' hit && ray_frac <= limit for n caller-given rays, in passes of `pass` rays
-constexpr int64_t kOcclMaxPass = 1ll << 22;
-struct OccludedLaunch {
-    DevScene    sc;
-    int32_t     mode;           // SR_MODE_*
-    bool        with_extra;     // root geometry of the chain (extra + model)
+// What the launches of the four batch calls below share (sr_batch.h holds the pass driver that reads it).  A call runs its n items in passes
+// of `pass`; on the own BVH a pass is ordered first, the regular items in front and the irregular tail last
+constexpr int64_t kBatchMaxPass = 1ll << 22;
+struct BatchLaunch {
     int64_t     n, pass;
-    const double* starts;       // device [n][3]
-    const double* dirs;         // device [n][3]: directions, or end points (endpoints)
-    const double* limits;       // device [n] or nullptr (every ray 1.0)
-    uint8_t*    occluded;       // device [n]
-    bool        endpoints;      // SR_RAYS_ENDPOINTS
-    bool        input_order;    // SR_RAYS_COHERENT / hook 46: a pass keeps its input order (the irregular rays still go last)
-    bool        nearest_walks;  // SR_MODE_BVH with nearest-hit walks plus the comparison for every ray (hook 47)
-    int         refill_at;      // >= 0 (hook 100 + T): the any-hit launch with persistent lanes that fetch new rays at T busy lanes; < 0: one lane per ray
-    int32_t     persistent_blocks;
-    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words, and one more for the refill form's work head (SR_MODE_BVH)
+    const double* limits;       // device [n] or nullptr (what that means is the call's own)
+    bool        input_order;    // SR_RAYS_COHERENT / SR_POINTS_COHERENT / the call's hook: a pass keeps its input order (the irregular items still go last)
+    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words, and one more for a persistent walk's work head (ordered passes)
     void*       sort_temp;
     size_t      sort_temp_bytes; // point_order_temp_bytes
-    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += rays, [1..3] += what their walks count
+    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += items, [1..3] += what their walks count
     hipStream_t stream;
     void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
     void*       user;
 };
-hipError_t launch_occluded(const OccludedLaunch& L);
 
-// sr_nearest_rays (sr_nearest.hip): sr_trace_rays' answer where it is a hit with ray_frac <= limit, its miss otherwise, for n caller-given
-// rays in passes of `pass` rays.  SR_MODE_BVH: occl_order's order, then k_nr_prep / k_nr_walk / k_nr_finish for the regular rays
-constexpr int64_t kNearestMaxPass = 1ll << 22;
-constexpr int kNearestRefillAt = 24;    // k_nr_walk fetches new rays when at most this many lanes of a wave are still walking (k_bounce_walk's)
-struct NearestLaunch {
+// sr_occluded_rays (sr_occluded.hip): occluded[i] = sr_trace_rays' hit && ray_frac <= limit for n caller-given rays (no limits: every ray 1.0)
+struct OccludedLaunch : BatchLaunch {
     DevScene    sc;
     int32_t     mode;           // SR_MODE_*
     bool        with_extra;     // root geometry of the chain (extra + model)
-    int64_t     n, pass;
     const double* starts;       // device [n][3]
     const double* dirs;         // device [n][3]: directions, or end points (endpoints)
-    const double* limits;       // device [n] or nullptr (no limit)
+    uint8_t*    occluded;       // device [n]
+    bool        endpoints;      // SR_RAYS_ENDPOINTS
+    bool        nearest_walks;  // SR_MODE_BVH with nearest-hit walks plus the comparison for every ray (hook 47)
+    int         refill_at;      // >= 0 (hook 100 + T): the any-hit launch with persistent lanes that fetch new rays at T busy lanes; < 0: one lane per ray
+    int32_t     persistent_blocks;
+};
+hipError_t launch_occluded(const OccludedLaunch& L);
+
+// sr_nearest_rays (sr_nearest.hip): sr_trace_rays' answer where it is a hit with ray_frac <= limit (no limits: no comparison), its miss
+// otherwise, for n caller-given rays.  SR_MODE_BVH: occl_order's order, then k_nr_prep / k_nr_walk / k_nr_finish for the regular rays
+constexpr int kNearestRefillAt = 24;    // k_nr_walk fetches new rays when at most this many lanes of a wave are still walking (k_bounce_walk's)
+struct NearestLaunch : BatchLaunch {
+    DevScene    sc;
+    int32_t     mode;           // SR_MODE_*
+    bool        with_extra;     // root geometry of the chain (extra + model)
+    const double* starts;       // device [n][3]
+    const double* dirs;         // device [n][3]: directions, or end points (endpoints)
     uint8_t* hit; double* ray_frac; double* pos; double* normal; uint32_t* color; int32_t* tri;    // device [n] each, or nullptr
     bool        endpoints;      // SR_RAYS_ENDPOINTS
-    bool        input_order;    // SR_RAYS_COHERENT / hook 48: a pass keeps its input order (the irregular rays still go last)
     bool        lane_walks;     // SR_MODE_BVH with one private walk per lane for every ray, in input order (hook 49)
     bool        bvh2;           // SR_DBG_BVH2_PACKETS: the walk on the two-wide tree
     int         refill_at;      // k_nr_walk's refill threshold (hook 100 + T)
     int         lds_levels;     // stack levels per lane k_nr_walk keeps in LDS (hook 200 + K)
     int32_t     persistent_blocks;
-    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words, and one more for the walk's work head (SR_MODE_BVH)
-    void*       sort_temp;
-    size_t      sort_temp_bytes; // point_order_temp_bytes
     void*       prep;           // device [pass] x 64 B
     void*       res;            // device [pass] x 16 B
     int32_t*    deep;           // device: the stack levels beyond lds_levels, [level][lane of the grid]
     size_t      deep_bytes;
-    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += rays, [1..3] += what their walks count
-    hipStream_t stream;
-    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
-    void*       user;
 };
 hipError_t launch_nearest(const NearestLaunch& L);
 
-// sr_all_hits_rays (sr_allhits.hip): every qualifying hit of n caller-given rays -- count, and the first max_hits of them by (ray_frac, extra
-// elements before triangles, element / TriangleIndex) -- in passes of `pass` rays.  SR_MODE_BVH: occl_order's order, k_ah_walk for the regular
-// rays, k_ah_loop (the per-record loop) for the others; SR_MODE_BRUTE: k_ah_loop in input order
-constexpr int64_t kAllHitsMaxPass = 1ll << 22;
+// sr_all_hits_rays (sr_allhits.hip): every qualifying hit of n caller-given rays (no limits: no comparison) -- count, and the first max_hits
+// of them by (ray_frac, extra elements before triangles, element / TriangleIndex).  SR_MODE_BVH: occl_order's order, k_ah_walk for the
+// regular rays, k_ah_loop (the per-record loop) for the others; SR_MODE_BRUTE: k_ah_loop in input order
 constexpr int kAllHitsMax = 64;         // SR_HITS_MAX
-struct AllHitsLaunch {
+struct AllHitsLaunch : BatchLaunch {
     DevScene    sc;
     int32_t     mode;           // SR_MODE_BVH or SR_MODE_BRUTE
     bool        with_extra;     // root geometry of the chain (extra + model)
-    int64_t     n, pass;
     const double* starts;       // device [n][3]
     const double* dirs;         // device [n][3]: directions, or end points (endpoints)
-    const double* limits;       // device [n] or nullptr (no limit)
     int32_t     max_hits;       // K, 0 .. kAllHitsMax
     uint32_t*   count;          // device [n] or nullptr (nullptr and K > 0: the walk culls at the K-th kept hit)
     int32_t*    index;          // device [n][K] or nullptr
@@ -482,39 +473,20 @@ struct AllHitsLaunch {
     int32_t*    scratch_index;  // device [pass][K]: a lane's row where index is nullptr (K > 0)
     double*     scratch_frac;   // device [pass][K]: ... where ray_frac is nullptr
     bool        endpoints;      // SR_RAYS_ENDPOINTS
-    bool        input_order;    // SR_RAYS_COHERENT / hook 50: a pass keeps its input order (the irregular rays still go last)
     bool        loop_all;       // SR_MODE_BVH with the per-record loop for every ray (hook 51)
-    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words (SR_MODE_BVH)
-    void*       sort_temp;
-    size_t      sort_temp_bytes; // point_order_temp_bytes
-    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += rays, [1..3] += what their walks count
-    hipStream_t stream;
-    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
-    void*       user;
 };
 hipError_t launch_all_hits(const AllHitsLaunch& L);
 
 // sr_closest_points (sr_closest.hip): for n caller-given points the triangle that minimises (squared distance, TriangleIndex), its distance,
-// the closest point and its weights, where the distance is within the limit -- in passes of `pass` points.  SR_MODE_BVH: k_cp_keys + the
+// the closest point and its weights, where the distance is within the limit (no limits: no comparison).  SR_MODE_BVH: k_cp_keys + the
 // radix sort, k_cp_walk for the regular points (closest_regular, sr_closest.h), k_cp_loop (the per-record loop) for the others;
 // SR_MODE_BRUTE: k_cp_loop in input order
-constexpr int64_t kClosestMaxPass = 1ll << 22;
-struct ClosestLaunch {
+struct ClosestLaunch : BatchLaunch {
     DevScene    sc;
     int32_t     mode;           // SR_MODE_BVH or SR_MODE_BRUTE
-    int64_t     n, pass;
     const double* points;       // device [n][3]
-    const double* limits;       // device [n] or nullptr (no limit)
     int32_t* tri; double* dist; double* pos; double* uv;      // device [n], [n], [n][3], [n][2]; each may be nullptr
-    bool        input_order;    // SR_POINTS_COHERENT / hook 52: a pass keeps its input order (the irregular points still go last)
     bool        loop_all;       // SR_MODE_BVH with the per-record loop for every point (hook 53)
-    unsigned int* sort_buf;     // device: 4 x the pass rounded up to 256 words (SR_MODE_BVH)
-    void*       sort_temp;
-    size_t      sort_temp_bytes; // point_order_temp_bytes
-    unsigned long long* stats;  // device [SR_STATS_COUNT] or nullptr: [0] += points, [1..3] += what their walks count
-    hipStream_t stream;
-    void (*get_events)(void* user, int kernel_id, hipEvent_t* start, hipEvent_t* stop);
-    void*       user;
 };
 hipError_t launch_closest(const ClosestLaunch& L);
 

@@ -7,10 +7,9 @@
 // _finish): k_nr_prep (FP64 clip, offset, cull bound), k_nr_walk (persistent lanes on the four-wide tree, the stack split between LDS and
 // global memory), k_nr_finish (extra geometry, the limit, the outputs).  Every other ray, and every ray of the reference tree and of brute
 // force, is answered by the function k_trace calls (root_intersect<MODE, false, EXTRA>) plus the comparison: equal to sr_trace_rays by
-// construction.  A translation unit of its own: no kernel of sr_kernels.hip / sr_pipeline.hip / sr_occluded.hip is touched.
-#include "sr_trace.h"
-
-#include <algorithm>
+// construction.  The pass driver, the lane's pick, the ray fetch, the walk's ray frame and its binary node step are sr_batch.h's, shared with
+// the other batch calls; the three-kernel route, the four-wide walk, the split stack and the per-lane tail are this file's.
+#include "sr_batch.h"
 
 namespace sr {
 
@@ -43,22 +42,20 @@ __device__ __forceinline__ void nr_store(const NrOut& o, size_t i, bool ok, cons
     if (o.tri) o.tri[i] = ok ? h.tri : -1;
 }
 
-// lane = position j in the pass's order: ray order[j] of the pass that starts at ray `first`.  keys[j] is the sorted key of that ray: its
-// bit skip_mask marks an irregular ray, which gets a record without a walk (k_nr_lane answers it).
-__global__ __launch_bounds__(256) void k_nr_prep(DevScene sc, const double* __restrict__ starts, const double* __restrict__ dirs, const double* __restrict__ limits,
-                                                 long long first, unsigned int count, const unsigned int* __restrict__ order, const unsigned int* __restrict__ keys,
-                                                 unsigned int skip_mask, int endpoints, NrRay* __restrict__ prep, NrHit* __restrict__ res) {
-    const unsigned int j = blockIdx.x * 256u + threadIdx.x;                             // (a pass has at most 2^22 rays)
-    if (j >= count) return;
-    const unsigned int src = order[j];
+// lane = position j in the pass's order (p.take is 0, the order is never nullptr here): an irregular ray gets a record without a walk
+// (k_nr_lane answers it).
+__global__ __launch_bounds__(256) void k_nr_prep(DevScene sc, BatchRays rays, PassSlice p, NrRay* __restrict__ prep, NrHit* __restrict__ res) {
+    const unsigned int j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= p.count) return;
+    unsigned int src;
+    const bool regular = pass_pick(p, j, src);
     NrRay o;
     o.s[0] = o.s[1] = o.s[2] = 0.0; o.d[0] = o.d[1] = o.d[2] = 0.0;
     o.offset = -1.0; o.index = src; o.tlim = 0.0f;
-    if ((keys[j] & skip_mask) == 0u) {
-        const size_t i = (size_t)first + (size_t)src;                                   // 64-bit from here on: n x 24 bytes may pass 2^32
-        const D3 s0 = mk(starts[3 * i], starts[3 * i + 1], starts[3 * i + 2]);
-        const D3 e = mk(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
-        const D3 d = endpoints ? e - s0 : e;                                            // one FP64 subtraction per component, as sr_occluded_rays
+    if (regular) {
+        D3 s0, d;
+        double lim;
+        fetch_ray(rays, (size_t)p.first + (size_t)src, 0.0, s0, d, lim);                // (no limits: lim is not read)
         D3 s = s0;
         D3 end = s + d * 10000.0;
         bool walking = clip_segment<false>(sc.root, s, end);
@@ -66,12 +63,10 @@ __global__ __launch_bounds__(256) void k_nr_prep(DevScene sc, const double* __re
         double offset = -1.0;
         if (walking) {
             offset = length(s0 - s) / length(d);
-            if (limits) {
-                // a hit counts <=> fl(t + offset) <= limit: nothing beyond t = limit - offset (inflated) can (bvh_intersect<true>)
-                const float kInfl = 1.0f + 9.5367431640625e-7f;          // 1 + 2^-20
-                const double room = limits[i] - offset;
+            if (rays.limits) {
+                const double room = lim - offset;
                 walking = !(room < 0.0);
-                tlim = (float)room * kInfl + 1e-30f;
+                tlim = cull_tlim(room);
             }
         }
         o.s[0] = s.x; o.s[1] = s.y; o.s[2] = s.z;
@@ -97,14 +92,12 @@ __global__ __launch_bounds__(256, 4) void k_nr_walk(DevScene sc, const NrRay* __
                                                     NrHit* __restrict__ res, unsigned long long* stats, int refill_at, int32_t* __restrict__ deep, int lds_levels) {
     const int tid = threadIdx.x, lane = tid & 63;
     SplitStack st{reinterpret_cast<int32_t*>(lds_nr) + tid, deep + (size_t)blockIdx.x * 256u + (unsigned)tid, lds_levels, (int32_t)(gridDim.x * 256u)};
-    const float kInfl = 1.0f + 9.5367431640625e-7f;          // 1 + 2^-20
     Ctr c = {0, 0, 0, 0};
     // ---- per ray ----
     unsigned int mine = 0;                     // position of the lane's ray in prep / res
     double best = DBL_MAX;
     int32_t bestIdx = 0x7fffffff, bestK = -1;
-    f2 I01 = splat(0.0f), I20 = I01, I12 = I01, B0 = I01, B1 = I01, B2 = I01;
-    RayF rf = {};
+    SlabRay ray = {};
     float tlim = FLT_MAX;
     int sp = 0;
     int32_t ni = -1, leafA = -1, leafB = -1, leafC = -1, leafD = -1, leafE = -1, leafF = -1, leafG = -1, leafH = -1;
@@ -127,12 +120,8 @@ __global__ __launch_bounds__(256, 4) void k_nr_walk(DevScene sc, const NrRay* __
                         mine = r;
                         const D3 s = mk(q.s[0], q.s[1], q.s[2]), d = mk(q.d[0], q.d[1], q.d[2]);   // (not carried through the walk: see the FP64 tests)
                         best = DBL_MAX; bestIdx = 0x7fffffff; bestK = -1;
-                        const float ox = (float)(s.x - sc.root.centre[0]), oy = (float)(s.y - sc.root.centre[1]), oz = (float)(s.z - sc.root.centre[2]);
-                        const float ix = slab_inv((float)d.x), iy = slab_inv((float)d.y), iz = slab_inv((float)d.z);
-                        I01 = (f2){ix, iy}; I20 = (f2){iz, ix}; I12 = (f2){iy, iz};
-                        B0 = (f2){-ox * ix, -oy * iy}; B1 = (f2){-oz * iz, -ox * ix}; B2 = (f2){-oy * iy, -oz * iz};
+                        set_slab_ray(sc, s, d, ray);
                         tlim = q.tlim;
-                        rf = make_ray_f(sc, s, d);
                         sp = 0; ni = 0; leafA = -1; leafB = -1; leafC = -1; leafD = -1; leafE = leafF = leafG = leafH = -1;
                         active = true;
                     }
@@ -153,7 +142,7 @@ __global__ __launch_bounds__(256, 4) void k_nr_walk(DevScene sc, const NrRay* __
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     float t, x;
-                    child_slabs(n.ch[k], I01, I20, I12, B0, B1, B2, t, x);
+                    child_slabs(n.ch[k], ray.I01, ray.I20, ray.I12, ray.B0, ray.B1, ray.B2, t, x);
                     const bool h = n.ch[k].n >= 0 && t <= x && x >= 0.0f && t <= tlim;
                     tk[k] = (h && n.ch[k].n == 0) ? t : FLT_MAX;
                     ck[k] = n.ch[k].c;
@@ -174,25 +163,9 @@ __global__ __launch_bounds__(256, 4) void k_nr_walk(DevScene sc, const NrRay* __
             while (!WIDE && ni >= 0 && leafA < 0) {
                 const BvhNode n = sc.bnodes[ni];
                 c.nodes++;
-                float t0, x0, t1, x1;
-                node_slabs(n, I01, I20, I12, B0, B1, B2, t0, x0, t1, x1);
-                const bool h0 = n.n0 >= 0 && t0 <= x0 && x0 >= 0.0f && t0 <= tlim;
-                const bool h1 = n.n1 >= 0 && t1 <= x1 && x1 >= 0.0f && t1 <= tlim;
-                const bool l0 = h0 && n.n0 > 0, l1 = h1 && n.n1 > 0;
-                if (l0 && l1) {
-                    const bool first0 = t0 <= t1;
-                    leafA = (first0 ? n.c0 : n.c1) | ((first0 ? n.n0 : n.n1) << kLeafShift);
-                    leafB = (first0 ? n.c1 : n.c0) | ((first0 ? n.n1 : n.n0) << kLeafShift);
-                } else if (l0) leafA = n.c0 | (n.n0 << kLeafShift);
-                else if (l1) leafA = n.c1 | (n.n1 << kLeafShift);
-                const bool i0 = h0 && n.n0 == 0, i1 = h1 && n.n1 == 0;
-                if (i0 && i1) {
-                    const bool first0 = t0 <= t1;
-                    st.put(sp++, first0 ? n.c1 : n.c0);
-                    ni = first0 ? n.c0 : n.c1;
-                } else if (i0) ni = n.c0;
-                else if (i1) ni = n.c1;
-                else ni = (sp > 0) ? st.get(--sp) : -1;
+                bool h0, h1, first0;
+                ray_node_hits(n, ray, tlim, h0, h1, first0);
+                walk_step(n, h0, h1, first0, st, sp, ni, leafA, leafB);
             }
             while (leafA >= 0) {
                 const int32_t first = leafA & kLeafMask, cn = (leafA >> kLeafShift) & 15;
@@ -200,7 +173,7 @@ __global__ __launch_bounds__(256, 4) void k_nr_walk(DevScene sc, const NrRay* __
                 leafB = WIDE ? leafC : -1;
                 if (WIDE) { leafC = leafD; leafD = leafE; leafE = leafF; leafF = leafG; leafG = leafH; leafH = -1; }
                 c.leaves++;
-                uint32_t m = leaf_survivors(sc, first, cn, rf, tlim);
+                uint32_t m = leaf_survivors(sc, first, cn, ray.rf, tlim);
                 if (m) {
                     // As k_bounce_walk: the FP64 record and the FP64 ray are the register peak, so the ray is read from the prepared array
                     // here and the fp32 frames -- dead while the test runs -- are made again from it with the refill's expressions.
@@ -215,15 +188,11 @@ __global__ __launch_bounds__(256, 4) void k_nr_walk(DevScene sc, const NrRay* __
                             const int32_t idx = r->aux;
                             if (t < best || (t == best && idx < bestIdx)) {
                                 best = t; bestIdx = idx; bestK = k;
-                                tlim = fminf(tlim, (float)best * kInfl + 1e-30f);             // (never beyond the ray's limit)
+                                tlim = fminf(tlim, cull_tlim(best));                       // (never beyond the ray's limit)
                             }
                         }
                     }
-                    const float ox = (float)(s.x - sc.root.centre[0]), oy = (float)(s.y - sc.root.centre[1]), oz = (float)(s.z - sc.root.centre[2]);
-                    const float ix = slab_inv((float)d.x), iy = slab_inv((float)d.y), iz = slab_inv((float)d.z);
-                    I01 = (f2){ix, iy}; I20 = (f2){iz, ix}; I12 = (f2){iy, iz};
-                    B0 = (f2){-ox * ix, -oy * iy}; B1 = (f2){-oz * iz, -ox * ix}; B2 = (f2){-oy * iy, -oz * iz};
-                    rf = make_ray_f(sc, s, d);
+                    set_slab_ray(sc, s, d, ray);
                 }
             }
             if (ni < 0 && leafA < 0) {                            // the walk is over
@@ -243,16 +212,15 @@ __global__ __launch_bounds__(256, 4) void k_nr_walk(DevScene sc, const NrRay* __
 // lane = position j in the pass's order, regular rays only: root_intersect's choice between the extra geometry (from the UNCLIPPED start, in
 // collection order, strict '<') and the walk's triangle, the limit, and sr_trace_rays' stores at the ray's input index.
 template <bool EXTRA, bool STATS>
-__global__ __launch_bounds__(256) void k_nr_finish(DevScene sc, const double* __restrict__ starts, const double* __restrict__ limits, long long first,
-                                                   unsigned int count, const unsigned int* __restrict__ keys, unsigned int skip_mask,
+__global__ __launch_bounds__(256) void k_nr_finish(DevScene sc, const double* __restrict__ starts, const double* __restrict__ limits, PassSlice p,
                                                    const NrRay* __restrict__ prep, const NrHit* __restrict__ res, NrOut out, unsigned long long* stats) {
     const unsigned int j = blockIdx.x * 256u + threadIdx.x;
     uint32_t n_rays = 0, n_geom = 0;
-    if (j < count && (keys[j] & skip_mask) == 0u) {
-        const NrRay p = prep[j];
+    if (j < p.count && (p.keys[j] & p.skip_mask) == 0u) {
+        const NrRay q = prep[j];
         const NrHit w = res[j];
-        const size_t i = (size_t)first + (size_t)p.index;
-        const D3 s = mk(p.s[0], p.s[1], p.s[2]), d = mk(p.d[0], p.d[1], p.d[2]);
+        const size_t i = (size_t)p.first + (size_t)q.index;
+        const D3 s = mk(q.s[0], q.s[1], q.s[2]), d = mk(q.d[0], q.d[1], q.d[2]);
         n_rays = 1;
         Hit h;
         h.t = 0; h.pos = mk(0, 0, 0); h.nrm = mk(0, 0, 0); h.color = 0; h.tri = -1;
@@ -269,10 +237,10 @@ __global__ __launch_bounds__(256) void k_nr_finish(DevScene sc, const double* __
                 if (hit && t < ex_t) { ex_t = t; ok = true; h.t = t; h.pos = pos; h.nrm = nrm; h.color = e->color; h.tri = -1; }
             }
         }
-        if (p.offset >= 0.0 && w.bestK >= 0 && (w.best + p.offset) < ex_t) {
+        if (q.offset >= 0.0 && w.bestK >= 0 && (w.best + q.offset) < ex_t) {
             const Rec128* t = &sc.btris[w.bestK];
             ok = true;
-            h.t = w.best + p.offset;
+            h.t = w.best + q.offset;
             h.pos = s + d * w.best;          // the expression plane_hit evaluated for the winning triangle (pos = start + dir * rayFrac)
             h.nrm = mk(t->p[0], t->p[1], t->p[2]);
             h.color = t->color;
@@ -287,147 +255,102 @@ __global__ __launch_bounds__(256) void k_nr_finish(DevScene sc, const double* __
     }
 }
 
-// One lane per ray, the function k_trace calls plus the comparison: the irregular rays of a SR_MODE_BVH pass (take 1: the lanes whose key has
-// the bit skip_mask), and every ray of the other modes and of hook 49 (order == nullptr: lane j takes ray j).
+// One lane per ray, the function k_trace calls plus the comparison: the irregular rays of a SR_MODE_BVH pass (take 1), and every ray of the
+// other modes and of hook 49 (input order).
 // LDS: the per-lane traversal stacks, stack levels x 256 lanes x 4 bytes, as k_trace.
 template <int MODE, bool EXTRA, bool STATS>
-__global__ __launch_bounds__(256) void k_nr_lane(DevScene sc, const double* __restrict__ starts, const double* __restrict__ dirs, const double* __restrict__ limits,
-                                                 long long first, unsigned int count, const unsigned int* __restrict__ order, const unsigned int* __restrict__ keys,
-                                                 unsigned int skip_mask, int endpoints, NrOut out, unsigned long long* stats) {
+__global__ __launch_bounds__(256) void k_nr_lane(DevScene sc, BatchRays rays, PassSlice p, NrOut out, unsigned long long* stats) {
     const int tid = threadIdx.x;
     Stack st{reinterpret_cast<int32_t*>(lds_nr) + tid, 256};
-    const unsigned int j = blockIdx.x * 256u + (unsigned int)tid;
-    bool live = j < count;
-    unsigned int src = j;
-    if (order && live) {
-        src = order[j];
-        live = (keys[j] & skip_mask) != 0u;
-    }
+    unsigned int src;
+    const bool live = pass_pick(p, blockIdx.x * 256u + (unsigned int)tid, src);
     Ctr c = {0, 0, 0, 0};
     if (live) {
-        const size_t i = (size_t)first + (size_t)src;
-        const D3 s = mk(starts[3 * i], starts[3 * i + 1], starts[3 * i + 2]);
-        const D3 e = mk(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
-        const D3 d = endpoints ? e - s : e;
+        const size_t i = (size_t)p.first + (size_t)src;
+        D3 s, d;
+        fetch_ray(rays, i, s, d);                                                       // (the limit is read after the walk: held across it, it costs two VGPRs)
         c.rays = 1;
         Hit h;
         h.t = 0; h.pos = mk(0, 0, 0); h.nrm = mk(0, 0, 0); h.color = 0; h.tri = -1;
         bool ok = root_intersect<MODE, false, EXTRA>(sc, sc.tris, sc.extra, st, s, d, h, c);
-        if (limits) ok = ok && h.t <= limits[i];                                        // IEEE <=: a NaN limit is a miss
+        if (rays.limits) ok = ok && h.t <= rays.limits[i];                              // IEEE <=: a NaN limit is a miss
         nr_store(out, i, ok, h);
     }
-    if (STATS) {                                                                        // (every thread of the workgroup arrives here)
-        uint32_t a = wave_sum(c.rays), b = wave_sum(c.geom), c2 = wave_sum(c.nodes), d2 = wave_sum(c.leaves);
-        block_stat_add(&stats[0], &stats[1], &stats[2], &stats[3], a, b, c2, d2);
-    }
+    if (STATS) block_stat_add(stats, c);                                                // (every thread of the workgroup arrives here)
 }
 
 namespace {
 
-int nr_stack_levels(const DevScene& sc, int mode) {
-    if (mode == MODE_REF) return sc.rdepth + 2;
-    if (mode == MODE_BVH) return sc.bdepth + 2;
-    return 1;
-}
-
 NrOut nr_out(const NearestLaunch& L) { return NrOut{L.hit, L.ray_frac, L.pos, L.normal, L.color, L.tri}; }
 
 template <int MODE, bool EXTRA>
-hipError_t launch_nr_lane(const NearestLaunch& L, const DevScene& sc, long long first, unsigned int count, const unsigned int* order, const unsigned int* keys,
-                          unsigned int skip_mask) {
-    const dim3 grid((count + 255u) / 256u);
-    const size_t lds = (size_t)nr_stack_levels(sc, MODE) * 256 * 4;
-    const auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, L.stream, sc, L.starts, L.dirs, L.limits, first, count, order, keys, skip_mask, L.endpoints ? 1 : 0, nr_out(L),
-                           L.stats);
-    };
+hipError_t launch_nr_lane(const NearestLaunch& L, const DevScene& sc, const BatchRays& rays, PassSlice p) {
+    p.take = 1;
+    const size_t lds = (size_t)stack_levels(sc, MODE) * 256 * 4;
+    const auto go = [&](auto kern) { hipLaunchKernelGGL(kern, lane_grid(p), dim3(256), lds, L.stream, sc, rays, p, nr_out(L), L.stats); };
     if (L.stats) go(k_nr_lane<MODE, EXTRA, true>); else go(k_nr_lane<MODE, EXTRA, false>);
     return hipGetLastError();
 }
 
 // prep, walk, finish of a pass's regular rays; `head`: the walk's work head
 template <bool EXTRA>
-hipError_t launch_nr_walked(const NearestLaunch& L, const DevScene& sc, long long first, unsigned int count, const unsigned int* order, const unsigned int* keys,
-                            unsigned int skip_mask, unsigned int* head) {
+hipError_t launch_nr_walked(const NearestLaunch& L, const DevScene& sc, const BatchRays& rays, PassSlice p, unsigned int* head) {
+    p.take = 0;
     hipError_t e = hipMemsetAsync(head, 0, sizeof(unsigned int), L.stream);
     if (e != hipSuccess) return e;
-    const unsigned int blocks = (count + 255u) / 256u;
+    const unsigned int blocks = (p.count + 255u) / 256u;
     NrRay* prep = (NrRay*)L.prep;
     NrHit* res = (NrHit*)L.res;
-    hipLaunchKernelGGL(k_nr_prep, dim3(blocks), dim3(256), 0, L.stream, sc, L.starts, L.dirs, L.limits, first, count, order, keys, skip_mask, L.endpoints ? 1 : 0, prep, res);
+    hipLaunchKernelGGL(k_nr_prep, dim3(blocks), dim3(256), 0, L.stream, sc, rays, p, prep, res);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const bool wide = sc.b4 != nullptr && !L.bvh2;
-    const int levels_all = wide ? 3 * sc.b4depth + 2 : nr_stack_levels(sc, MODE_BVH);
+    const int levels_all = wide ? 3 * sc.b4depth + 2 : stack_levels(sc, MODE_BVH);
     const unsigned int wblocks = std::max(1u, std::min(blocks, (unsigned int)std::max(1, L.persistent_blocks)));
     // stack levels in LDS: L.lds_levels when the rest of the worst case fits the overflow buffer, all of them otherwise
     int lds_levels = std::max(1, std::min(L.lds_levels, levels_all));
     if (!L.deep || (size_t)(levels_all - lds_levels) * (size_t)wblocks * 256 * 4 > L.deep_bytes) lds_levels = levels_all;
     const int refill_at = std::min(63, std::max(0, L.refill_at));
     const auto walk = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(wblocks), dim3(256), (size_t)lds_levels * 256 * 4, L.stream, sc, (const NrRay*)prep, count, head, res, L.stats, refill_at, L.deep,
+        hipLaunchKernelGGL(kern, dim3(wblocks), dim3(256), (size_t)lds_levels * 256 * 4, L.stream, sc, (const NrRay*)prep, p.count, head, res, L.stats, refill_at, L.deep,
                            lds_levels);
     };
     if (wide) { if (L.stats) walk(k_nr_walk<true, true>); else walk(k_nr_walk<false, true>); }
     else { if (L.stats) walk(k_nr_walk<true, false>); else walk(k_nr_walk<false, false>); }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const auto fin = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, sc, L.starts, L.limits, first, count, keys, skip_mask, (const NrRay*)prep, (const NrHit*)res,
-                           nr_out(L), L.stats);
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, sc, rays.starts, rays.limits, p, (const NrRay*)prep, (const NrHit*)res, nr_out(L), L.stats);
     };
     if (L.stats) fin(k_nr_finish<EXTRA, true>); else fin(k_nr_finish<EXTRA, false>);
     return hipGetLastError();
 }
 
-// pass by pass, back to back on the stream.  SR_MODE_BVH: a pass is ordered first (occl_order: by the start's cell and the direction's octant,
-// or -- input_order -- only its irregular rays moved to the end); the regular rays take prep / walk / finish, the tail the per-lane form
-// (lane_walks: one per-lane launch over the pass in input order, no sort).  The other modes walk per lane in input order
+// SR_MODE_BVH: a pass is ordered first (occl_order: by the start's cell and the direction's octant, or -- input_order -- only its irregular
+// rays moved to the end); the regular rays take prep / walk / finish, the tail the per-lane form (lane_walks: one per-lane launch over the
+// pass in input order, no sort).  The other modes walk per lane in input order
 template <int MODE, bool EXTRA>
 hipError_t launch_nearest_t(const NearestLaunch& L) {
     DevScene sc = L.sc;
     if (!EXTRA) { sc.extra = nullptr; sc.nextra = 0; }                                  // the model alone, whatever the scene's extra geometry
-    const unsigned int cap = (unsigned int)((L.pass + 255) / 256 * 256);
-    unsigned int* keys = L.sort_buf;
-    unsigned int* keys2 = keys + cap;
-    unsigned int* idx = keys2 + cap;
-    unsigned int* order = idx + cap;
-    const unsigned int skip = point_order_skip_mask(!L.input_order);
-    const bool walked = MODE == MODE_BVH && !L.lane_walks;
-    for (int64_t first = 0; first < L.n; first += L.pass) {
-        const unsigned int count = (unsigned int)std::min<int64_t>(L.pass, L.n - first);
-        hipError_t e;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (walked) {
-            if (L.get_events) L.get_events(L.user, K_NEAREST_SORT, &e0, &e1);
-            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-            if ((e = occl_order(L.starts + 3 * first, L.dirs + 3 * first, L.limits ? L.limits + first : nullptr, count, L.endpoints, !L.input_order, sc.root, keys,
-                                keys2, idx, order, L.sort_temp, L.sort_temp_bytes, L.stream)) != hipSuccess)
-                return e;
-            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        }
-        e0 = e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_NEAREST, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        if constexpr (MODE == MODE_BVH) {
-            if (walked) {
-                e = launch_nr_walked<EXTRA>(L, sc, first, count, order, keys2, skip, order + cap);
-                if (e == hipSuccess) e = launch_nr_lane<MODE, EXTRA>(L, sc, first, count, order, keys2, skip);
-            } else {
-                e = launch_nr_lane<MODE, EXTRA>(L, sc, first, count, nullptr, nullptr, 0u);
+    const BatchRays rays = batch_rays(L.starts, L.dirs, L.limits, L.endpoints);
+    return run_passes(
+        L, MODE == MODE_BVH && !L.lane_walks, K_NEAREST_SORT, K_NEAREST,
+        [&](int64_t first, unsigned int count, const PassBuffers& b) { return order_ray_pass(L, rays, sc.root, first, count, b); },
+        [&](const PassSlice& p, const PassBuffers& b) {
+            if constexpr (MODE == MODE_BVH) {
+                if (!L.lane_walks) {
+                    const hipError_t e = launch_nr_walked<EXTRA>(L, sc, rays, p, b.head);
+                    if (e != hipSuccess) return e;
+                }
             }
-        } else {
-            e = launch_nr_lane<MODE, EXTRA>(L, sc, first, count, nullptr, nullptr, 0u);
-        }
-        if (e != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    }
-    return hipSuccess;
+            return launch_nr_lane<MODE, EXTRA>(L, sc, rays, p);
+        });
 }
 
 }  // namespace
 
 hipError_t launch_nearest(const NearestLaunch& L) {
     if (L.n <= 0) return hipSuccess;
-    if (L.pass <= 0 || L.pass > kNearestMaxPass) return hipErrorInvalidValue;
+    if (L.pass <= 0 || L.pass > kBatchMaxPass) return hipErrorInvalidValue;
     switch (L.mode) {
         case MODE_REF: return L.with_extra ? launch_nearest_t<MODE_REF, true>(L) : launch_nearest_t<MODE_REF, false>(L);
         case MODE_BRUTE: return L.with_extra ? launch_nearest_t<MODE_BRUTE, true>(L) : launch_nearest_t<MODE_BRUTE, false>(L);

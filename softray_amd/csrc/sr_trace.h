@@ -397,6 +397,7 @@ __device__ __forceinline__ uint32_t leaf_survivors(const DevScene& sc, int32_t f
 }
 
 // ANY: is there a hit with rayFrac <= any_limit?  (1.0: a shadow sample ray ends at the light; the ambient-occlusion probes pass 2.0)
+// (the node step below has one other copy: walk_step, sr_batch.h, for the batch calls' walks)
 template <bool ANY>
 __device__ bool bvh_intersect(const DevScene& sc, Stack st, D3 s, D3 d, Hit& out, Ctr& c, double any_limit = 1.0) {
     D3 end = s + d * 10000.0;

@@ -175,6 +175,21 @@ def test_passes_of_100_and_257_points(scenes, scene):
                 got = with_pass(g, per_pass, lambda: call(g, mode, sc.points, limits=lim, coherent=coherent, stats=stats))
                 assert same(got, want), (per_pass, mode, coherent)
                 assert stats[0] == sc.n
+    # the walk and the sort are recorded once per pass; brute force sorts nothing
+    for mode in MODES:
+        g.reset_kernel_times()
+        g.debug_set(L.DBG_KERNEL_TIMING, 1)
+        try:
+            with_pass(g, 100, lambda: call(g, mode, sc.points, limits=lim))
+            times = g.kernel_times()
+        finally:
+            g.debug_set(L.DBG_KERNEL_TIMING, -1)
+        passes = (sc.n + 99) // 100
+        assert times["k_closest"][1] == passes, mode
+        if mode == sa.MODE_BVH:
+            assert times["k_closest_sort"][1] == passes
+        else:
+            assert "k_closest_sort" not in times
 
 
 # ---- 5. any subset of the outputs ----

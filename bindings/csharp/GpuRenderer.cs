@@ -130,6 +130,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_all_hits_rays_device(IntPtr scene, int target, long n, IntPtr dStarts, IntPtr dDirs, IntPtr dLimits, int maxHits, IntPtr dCount, IntPtr dIndex, IntPtr dRayFrac, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_closest_points(IntPtr scene, int target, long n, [In] double[] points, [In] double[] maxDist, [Out] int[] triIndex, [Out] double[] dist, [Out] double[] pos, [Out] double[] uv, uint options, [Out] ulong[] stats4);
         [DllImport(Lib)] public static extern int sr_closest_points_device(IntPtr scene, int target, long n, IntPtr dPoints, IntPtr dMaxDist, IntPtr dTriIndex, IntPtr dDist, IntPtr dPos, IntPtr dUv, uint options, IntPtr hipStream, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_near_triangles(IntPtr scene, int target, long n, [In] double[] points, [In] double[] maxDist, int maxHits, [Out] uint[] count, [Out] int[] index, [Out] double[] dist, [Out] double[] pos, [Out] double[] uv, uint options, [Out] ulong[] stats4);
+        [DllImport(Lib)] public static extern int sr_near_triangles_device(IntPtr scene, int target, long n, IntPtr dPoints, IntPtr dMaxDist, int maxHits, IntPtr dCount, IntPtr dIndex, IntPtr dDist, IntPtr dPos, IntPtr dUv, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -741,6 +743,33 @@ namespace Engine3D.Hip
         {
             Native.Check(Native.sr_closest_points_device(scene, mode, n, dPoints, dMaxDist, dTriIndex, dDist, dPos, dUv, coherent ? POINTS_COHERENT : 0, stream,
                                                          dStats));
+        }
+
+        /// The triangles within reach of each point of a batch, nearest first, with a count (sr_near_triangles).  Count[i]: the triangles whose
+        /// distance is a number &lt;= maxDist[i] (maxDist == null: no limit; not capped by maxHits); rows i of Index / Dist ([n * maxHits]), Pos
+        /// ([n * maxHits * 3]) and Uv ([n * maxHits * 2]): the first min(Count, maxHits) of them by (squared distance, TriangleIndex) -- slot 0 is
+        /// ClosestPoints' answer -- the rest of a row -1 / zeros.  wantCount false: a K-nearest query (Count is null).  mode is MODE_BVH or
+        /// MODE_BRUTE; the model alone, no extra geometry.  Blocks.
+        public sealed class NearTriangleLists { public int MaxHits; public uint[] Count; public int[] Index; public double[] Dist; public double[] Pos; public double[] Uv; public ulong[] Stats4; }
+        public NearTriangleLists NearTriangles(double[] points, double[] maxDist, int maxHits, int mode, bool wantCount = true, bool coherent = false)
+        {
+            long n = points.Length / 3;
+            long rows = n * Math.Max(0, maxHits);
+            var r = new NearTriangleLists { MaxHits = maxHits, Count = wantCount ? new uint[n] : null, Index = new int[rows], Dist = new double[rows],
+                                            Pos = new double[rows * 3], Uv = new double[rows * 2], Stats4 = new ulong[4] };
+            Native.Check(Native.sr_near_triangles(scene, mode, n, points, maxDist, maxHits, r.Count, r.Index, r.Dist, r.Pos, r.Uv, coherent ? POINTS_COHERENT : 0,
+                                                  r.Stats4));
+            return r;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_near_triangles_device), dMaxDist IntPtr.Zero for no limit and
+        /// IntPtr.Zero for an output that is not wanted (dCount IntPtr.Zero with maxHits &gt; 0: a K-nearest query); enqueued on `stream` without a
+        /// host synchronisation; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void NearTrianglesDevice(long n, IntPtr dPoints, IntPtr dMaxDist, int maxHits, int mode, bool coherent, IntPtr dCount, IntPtr dIndex, IntPtr dDist,
+                                        IntPtr dPos, IntPtr dUv, IntPtr stream, IntPtr dStats)
+        {
+            Native.Check(Native.sr_near_triangles_device(scene, mode, n, dPoints, dMaxDist, maxHits, dCount, dIndex, dDist, dPos, dUv,
+                                                         coherent ? POINTS_COHERENT : 0, stream, dStats));
         }
 
         /// ShadingMethod's colour step for n recorded intersections in DEVICE memory (sr_shade_points_device): dOut[i] = dColor[i] modulated with

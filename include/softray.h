@@ -790,6 +790,47 @@ int  sr_closest_points_device(sr_scene*, int32_t target, int64_t n, const double
                               int32_t* d_tri_index, double* d_dist, double* d_pos, double* d_uv /* each may be NULL */,
                               uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
+/* THE TRIANGLES WITHIN REACH of each point of a batch, nearest first, with a count -- the point-side counterpart of sr_all_hits_rays: contact and
+ * collision candidates against a moving mesh (sr_refit_triangles_device), k-nearest smoothing and attribute transfer, the surface inside a probe
+ * sphere.  sr_closest_points gives one triangle per point, and no second call can exclude the triangle the first one found.
+ * Per-triangle values: for point q = points[i] and triangle j, c_j, (v, w), d2_j and dist_j = sqrt(d2_j) are exactly sr_closest_points' values
+ * (the routine of csrc/sr_closest.h, nothing new).
+ * The SET of q: every j whose d2_j is a number (a NaN never counts) and, where max_dist is given, dist_j <= max_dist[i] (IEEE <=): a NaN, -inf or
+ * negative limit admits nothing, +inf every number.  max_dist == NULL: no comparison is made.
+ * Outputs: count[i] = the size of the set, NOT capped by max_hits (K).  Row i of index / dist / pos / uv ([n][K], [n][K], [n][K][3], [n][K][2])
+ * holds the first min(count, K) members ordered by (d2_j, j) ascending: index = j, dist = dist_j, pos = c_j, uv = (v, w).  Every other slot of
+ * every row is written: index -1, zeros elsewhere -- the caller clears nothing.  The order is on d2, not on the rounded distance, so slot 0 is
+ * sr_closest_points' answer under the same limit, bit for bit in all four outputs; dist is non-decreasing along a row, and two slots with equal
+ * dist may come from distinct d2.
+ * NULL arrays: max_hits == 0 is the counting call (the four row arrays are ignored).  Any of the five arrays may be NULL; all NULL: the call runs
+ * for the statistics.  An index or dist row the caller does not ask for is kept in the scene's first scratch set (both are needed for the order),
+ * in passes of at most 2^24 / K points.  With count == NULL and K > 0 the walk also culls every box beyond the K-th entry it holds -- a K-nearest
+ * query; the rows are bit for bit the same as with count.
+ * Targets: SR_MODE_BVH and SR_MODE_BRUTE, the same answers bit for bit.  SR_MODE_REF_TREE (a triangle lives in several leaves and would be listed
+ * twice), SR_TARGET_ROOT | mode (the extra primitives have no triangle indices) and SR_TARGET_VOXELS are SR_ERR_UNSUPPORTED.
+ * Routing in SR_MODE_BVH: sr_closest_points' -- the regular points of a pass, ordered by Morton cell (SR_POINTS_COHERENT: input order), walk the
+ * tree (k_nt_walk); a box is skipped only when its fp32 lower bound strictly exceeds min(max_dist^2 inflated, the K-nearest cut) with every
+ * rounding covered, the cut being +inf until the row is full and whenever count is wanted, max(worst kept d2, least d2 seen whose
+ * closest point lies inside its triangle) otherwise: equality never culls, so the (d2, j) order at the cut is exact.  Every other point runs
+ * the per-record loop (k_nt_loop), as every point of SR_MODE_BRUTE does in input order.  The limit per candidate is the exact test
+ * fl(sqrt(d2)) <= max_dist, made as d2 <= the largest double whose rounded square root is <= max_dist (found once per point).
+ * Refusals, in this order: a NULL scene, n < 0, NULL points with n > 0, max_hits outside 0 .. SR_HITS_MAX, unknown option bits:
+ * SR_ERR_INVALID_ARG; SR_TARGET_VOXELS, SR_TARGET_ROOT, SR_MODE_REF_TREE: SR_ERR_UNSUPPORTED; sr_trace_rays' own checks (SR_ERR_NO_MODEL,
+ * SR_ERR_NOT_BUILT); a host-only scene: SR_ERR_NO_DEVICE.  A refusal writes nothing.  n == 0 that passes all of them: SR_OK, nothing is touched.
+ * State: as sr_closest_points -- the call is ordered like a frame, passes of at most 2^22 points (SR_DBG_BAND_SAMPLES: fewer) follow each other
+ * without the host waiting, a multi-device scene runs the call on devices[0].  The host variant stages 24 n + 8 n bytes in and 4 n + 52 K n bytes
+ * out through the scene's device buffers, blocks and fills sr_last_ray_stats; the device variant enqueues on `hip_stream` without a host
+ * synchronisation.  Statistics: [0] = n; [1..3] = triangles tested, nodes and leaves visited (pinned in brute force only: n x triangles, 0, 0);
+ * [4..] 0. */
+int  sr_near_triangles(sr_scene*, int32_t target, int64_t n, const double* points /* [n][3] */,
+                       const double* max_dist /* [n], or NULL: no limit */, int32_t max_hits /* K, 0..SR_HITS_MAX */,
+                       uint32_t* count /* [n] or NULL */, int32_t* index /* [n][K] or NULL */, double* dist /* [n][K] or NULL */,
+                       double* pos /* [n][K][3] or NULL */, double* uv /* [n][K][2] or NULL */,
+                       uint32_t options, uint64_t stats[4] /* or NULL */);
+int  sr_near_triangles_device(sr_scene*, int32_t target, int64_t n, const double* d_points, const double* d_max_dist /* or NULL */,
+                              int32_t max_hits, uint32_t* d_count, int32_t* d_index, double* d_dist, double* d_pos, double* d_uv /* each may be NULL */,
+                              uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* ShadingMethod.IntersectRay's colour step in batch (ShadingMethod.cs:36-68 -> CalcLighting :110-177): for n recorded
  * intersections out[i] = ModulatePackedColor(color[i], (byte)(255 * intensity)) with the frame's transform and lights (only the
  * matrices, position_z, fov_depth, lights, ambient, shininess and the POINT_LIGHT / SPECULAR flags of `frame` are read).
@@ -1113,7 +1154,8 @@ enum {
                                     stack levels of sr_nearest_rays' walk kernel, as the bounce walk reads them below; 50 sr_all_hits_rays walks a pass in input order whatever the options say
                                     (no ray sort); 51 sr_all_hits_rays answers every ray of SR_MODE_BVH with the per-record loop of its irregular rays (both: same output;
                                     cross-check); 52 sr_closest_points walks a pass in input order whatever the options say (no point sort); 53 sr_closest_points
-                                    answers every point of SR_MODE_BVH with the per-record loop of its irregular points (both: same output; cross-check, DESIGN 5.32); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    answers every point of SR_MODE_BVH with the per-record loop of its irregular points (both: same output; cross-check); 54 sr_near_triangles walks a pass in input order whatever the options say (no point sort); 55 sr_near_triangles
+                                    answers every point of SR_MODE_BVH with the per-record loop of its irregular points (both: same output; cross-check, DESIGN 5.34); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
                                     fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid

@@ -58,7 +58,7 @@ SYMBOLS = [
     "sr_nearest_rays", "sr_nearest_rays_device",
     "sr_light_field_rays", "sr_light_field_rays_device",
     "sr_all_hits_rays", "sr_all_hits_rays_device",
-    "sr_closest_points", "sr_closest_points_device",
+    "sr_closest_points", "sr_closest_points_device", "sr_near_triangles", "sr_near_triangles_device",
 ]
 POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 RAYS_COHERENT = 1                      # SR_RAYS_COHERENT
@@ -197,6 +197,8 @@ def lib():
     L.sr_all_hits_rays_device.restype = i32; L.sr_all_hits_rays_device.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_closest_points.restype = i32; L.sr_closest_points.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, C.c_uint32, vp]
     L.sr_closest_points_device.restype = i32; L.sr_closest_points_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
+    L.sr_near_triangles.restype = i32; L.sr_near_triangles.argtypes = [vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, C.c_uint32, vp]
+    L.sr_near_triangles_device.restype = i32; L.sr_near_triangles_device.argtypes = [vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_light_field_rays.restype = i32; L.sr_light_field_rays.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp]
     L.sr_light_field_rays_device.restype = i32; L.sr_light_field_rays_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.sr_rccl_unique_id.restype = i32; L.sr_rccl_unique_id.argtypes = [vp]

@@ -1923,7 +1923,7 @@ int run_staged(sr_scene* m, sr_scene* s, Staged* io, int count, bool upload_asyn
     return SR_OK;
 }
 
-// ---- The batch calls without a frame (sr_occluded_rays, sr_nearest_rays, sr_all_hits_rays, sr_closest_points): one refusal ladder, one entry
+// ---- The batch calls without a frame (sr_occluded_rays, sr_nearest_rays, sr_all_hits_rays, sr_closest_points, sr_near_triangles): one refusal ladder, one entry
 // path for the host-array and the device-array variant, one setup of the passes
 // What such a call refuses before the device is looked at, in the header's order.  Every sentence follows "<name>: "
 struct ItemCall {
@@ -3449,6 +3449,74 @@ int sr_closest_points(sr_scene* m, int32_t target, int64_t n, const double* poin
                      [&](sr_scene* s, int mode, bool, hipStream_t stream, unsigned long long* d_stats) {
                          const ClosestOut out{(int32_t*)io[2].dev, (double*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev};
                          return closest_common(s, mode, n, (const double*)io[0].dev, (const double*)io[1].dev, out, options, stream, d_stats);
+                     });
+}
+
+// ---- The triangles within reach of a point, nearest first, with a count (sr_near_triangles): sr_closest_points with a list
+static const ItemCall kNearTrianglesCall = {
+    "sr_near_triangles", "points must not be NULL when n > 0", true,
+    SR_POINTS_COHERENT, "unknown option bits (SR_POINTS_COHERENT is the only option)",
+    "the voxel grid (SR_TARGET_VOXELS) has no triangles to be near to",
+    "the extra geometry (SR_TARGET_ROOT) has no triangle indices to list; pass the mode alone",
+    "SR_MODE_REF_TREE has no distance query (a triangle lives in several leaves of the reference tree and would be listed twice); use SR_MODE_BVH or "
+    "SR_MODE_BRUTE"};
+
+struct NearOut { uint32_t* count; int32_t* index; double* dist; double* pos; double* uv; };
+
+// (a row the walk needs and the caller does not want lives in the first scratch set's bounce buffers, as sr_all_hits_rays' rows)
+static int near_common(sr_scene* s, int mode, int64_t n, const double* d_points, const double* d_limits, int32_t max_hits, const NearOut& out,
+                       uint32_t options, hipStream_t stream, unsigned long long* d_stats) {
+    const bool own_rows = max_hits > 0 && (!out.index || !out.dist);
+    const int64_t max_pass = own_rows ? std::min<int64_t>(sr::kBatchMaxPass, (1ll << 24) / max_hits) : sr::kBatchMaxPass;   // (at most 2^24 slots of scratch rows)
+    sr::NearLaunch L{};
+    std::unique_ptr<StreamOrder> order;
+    size_t slots;
+    int rc = item_call_setup(s, mode, n, max_pass, mode == SR_MODE_BVH, stream, d_stats, order, L, slots);
+    if (rc) return rc;
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
+    L.sc = dev_scene(s);
+    L.mode = mode;
+    L.points = d_points; L.limits = d_limits;
+    L.max_hits = max_hits;
+    L.count = out.count;
+    L.index = max_hits > 0 ? out.index : nullptr;
+    L.dist = max_hits > 0 ? out.dist : nullptr;
+    L.pos = max_hits > 0 ? out.pos : nullptr;
+    L.uv = max_hits > 0 ? out.uv : nullptr;
+    L.input_order = (options & SR_POINTS_COHERENT) != 0 || hook == 54;                          // (hook: input order whatever the options say)
+    L.loop_all = hook == 55;                                                                    // (hook: every point through the per-record loop)
+    sr_scene::BandScratch& B = s->scratch[0];
+    if (max_hits > 0 && !out.index) {
+        SR_HIP(B.bounce_res.reserve(slots * (size_t)max_hits * sizeof(int32_t)));
+        L.scratch_index = (int32_t*)B.bounce_res.p;
+    }
+    if (max_hits > 0 && !out.dist) {
+        SR_HIP(B.bounce_prep.reserve(slots * (size_t)max_hits * sizeof(double)));
+        L.scratch_dist = (double*)B.bounce_prep.p;
+    }
+    SR_HIP(sr::launch_near(L));
+    return SR_OK;
+}
+
+int sr_near_triangles_device(sr_scene* m, int32_t target, int64_t n, const double* d_points, const double* d_max_dist, int32_t max_hits, uint32_t* d_count,
+                             int32_t* d_index, double* d_dist, double* d_pos, double* d_uv, uint32_t options, void* hip_stream, uint64_t* d_stats) {
+    return item_call(kNearTrianglesCall, m, target, n, d_points != nullptr, max_hits, options, {nullptr, 0, nullptr, hip_stream, d_stats},
+                     [&](sr_scene* s, int mode, bool, hipStream_t stream, unsigned long long* stats) {
+                         const NearOut out{d_count, d_index, d_dist, d_pos, d_uv};
+                         return near_common(s, mode, n, d_points, d_max_dist, max_hits, out, options, stream, stats);
+                     });
+}
+
+int sr_near_triangles(sr_scene* m, int32_t target, int64_t n, const double* points, const double* max_dist, int32_t max_hits, uint32_t* count, int32_t* index,
+                      double* dist, double* pos, double* uv, uint32_t options, uint64_t stats[4]) {
+    const size_t rows = (size_t)n * (size_t)max_hits;
+    const bool k = max_hits > 0;
+    Staged io[] = {{points, nullptr, (size_t)n * 24}, {max_dist, nullptr, (size_t)n * 8}, {nullptr, count, (size_t)n * 4}, {nullptr, k ? index : nullptr, rows * 4},
+                   {nullptr, k ? dist : nullptr, rows * 8}, {nullptr, k ? pos : nullptr, rows * 24}, {nullptr, k ? uv : nullptr, rows * 16}};
+    return item_call(kNearTrianglesCall, m, target, n, points != nullptr, max_hits, options, {io, 7, stats, nullptr, nullptr},
+                     [&](sr_scene* s, int mode, bool, hipStream_t stream, unsigned long long* d_stats) {
+                         const NearOut out{(uint32_t*)io[2].dev, (int32_t*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev, (double*)io[6].dev};
+                         return near_common(s, mode, n, (const double*)io[0].dev, (const double*)io[1].dev, max_hits, out, options, stream, d_stats);
                      });
 }
 

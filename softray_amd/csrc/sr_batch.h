@@ -1,4 +1,4 @@
-// sr_batch.h -- what the batch calls without a frame share (sr_occluded.hip, sr_nearest.hip, sr_allhits.hip, sr_closest.hip; nothing else
+// sr_batch.h -- what the batch calls without a frame share (sr_occluded.hip, sr_nearest.hip, sr_allhits.hip, sr_closest.hip, sr_near.hip; nothing else
 // includes it).  Device side: which item a lane of a pass takes, an item's ray, the fp32 frame of a ray for the private binary walk and that
 // walk's node step, the statistics epilogue.  Host side: the pass driver.  A call keeps what is its own: its kernels, how a pass is
 // ordered and what is launched for one.
@@ -89,6 +89,41 @@ __device__ __forceinline__ void block_stat_add(unsigned long long* stats, const 
     block_stat_add(&stats[0], &stats[1], &stats[2], &stats[3], r, g, n, l);
 }
 
+// ---- the point calls (sr_closest.hip, sr_near.hip): what their walks and loops share
+// (d2, j) of one triangle against the running best: a NaN d2 fails both comparisons, equal d2 goes to the lower TriangleIndex
+__device__ __forceinline__ bool cp_better(double d2, int32_t j, double best, int32_t bj) { return d2 < best || (d2 == best && j < bj); }
+
+// block_stat_add's sums (sr_trace.h) in the first four words of the kernel's DYNAMIC LDS (`lds`: its base) instead of a static array: the
+// walk's stacks are dead once every lane has arrived, and at the depth limit they are the whole 64 KiB a workgroup may ask for.  Every
+// thread must call it.
+__device__ __forceinline__ void cp_stat_add(unsigned char* lds, unsigned long long* stats, const Ctr& c) {
+    unsigned int* acc = reinterpret_cast<unsigned int*>(lds);
+    const uint32_t r = wave_sum(c.rays), g = wave_sum(c.geom), n2 = wave_sum(c.nodes), l2 = wave_sum(c.leaves);
+    __syncthreads();                                                      // no lane reads its stack any more
+    if (threadIdx.x < 4) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        if (r) atomicAdd(&acc[0], r);
+        if (g) atomicAdd(&acc[1], g);
+        if (n2) atomicAdd(&acc[2], n2);
+        if (l2) atomicAdd(&acc[3], l2);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { stat_add(&stats[0], acc[0]); stat_add(&stats[1], acc[1]); stat_add(&stats[2], acc[2]); stat_add(&stats[3], acc[3]); }
+}
+
+// fp32 lower bound of the squared distance from the point (p = (float)(q - centre), e = 2^-23 |p| per axis) to the stored box [lo, hi]:
+// per axis the gap max(lo - p, p - hi, 0) less e, squared and summed, times (1 - 2^-19).  DESIGN 5.32 proves that it is at most the FP64
+// d2 of every triangle below the box whose closest point the routine placed inside the triangle.
+__device__ __forceinline__ float cp_bound(const float lo[3], const float hi[3], float px, float py, float pz, float ex, float ey, float ez) {
+    const float gx = fmaxf(fmaxf(fmaxf(lo[0] - px, px - hi[0]), 0.0f) - ex, 0.0f);
+    const float gy = fmaxf(fmaxf(fmaxf(lo[1] - py, py - hi[1]), 0.0f) - ey, 0.0f);
+    const float gz = fmaxf(fmaxf(fmaxf(lo[2] - pz, pz - hi[2]), 0.0f) - ez, 0.0f);
+    return (gx * gx + gy * gy + gz * gz) * (1.0f - 1.9073486328125e-6f);
+}
+// the fp32 value a bound must EXCEED to cull: at least `cull` whatever the rounding (an overflow gives +inf: nothing is culled)
+__device__ __forceinline__ float cp_cullf(double cull) { return (float)cull * (1.0f + 2.384185791015625e-7f) + 1e-30f; }
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 // per-lane traversal stack levels of a private walk in `mode` (x 256 lanes x 4 bytes of LDS)
 inline int stack_levels(const DevScene& sc, int mode) {
@@ -138,6 +173,10 @@ inline hipError_t order_ray_pass(const BatchLaunch& L, const BatchRays& r, const
     return occl_order(r.starts + 3 * first, r.dirs + 3 * first, r.limits ? r.limits + first : nullptr, count, r.endpoints != 0, !L.input_order, root, b.keys, b.keys2,
                       b.idx, b.order, L.sort_temp, L.sort_temp_bytes, L.stream);
 }
+
+// The order of a pass of a point call (sr_closest.hip defines it: k_cp_keys + the radix sort): the regular points (closest_regular) first --
+// sorted by the Morton cell in `root`, or in input order (L.input_order) -- then the others in input order
+hipError_t cp_order(const BatchLaunch& L, const RootBox& root, const double* points, unsigned int n, const PassBuffers& b);
 
 // a launch with one lane per item of the slice
 inline dim3 lane_grid(const PassSlice& p) { return dim3((p.count + 255u) / 256u); }

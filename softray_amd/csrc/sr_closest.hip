@@ -7,9 +7,10 @@
 // and every point of brute force, runs the per-record loop over v9 in index order with the same FP64 routine and no fp32 stage.
 // The cull is exact: a box is skipped only when its deflated bound strictly exceeds the best squared distance found so far
 // (or the squared limit, inflated), so a triangle that ties the answer with a lower index is always visited.
-// The pass driver and the lane's pick are sr_batch.h's, shared with the other batch calls; the keys and the sort of a pass, the bound, the
-// walk's node step (its stack word carries a bound that a pop re-tests; sharing the leaf half cost the lattice 0.5 %: profiles/batch_refactor)
-// and the two kernels are this file's.
+// The pass driver and the lane's pick are sr_batch.h's, shared with the other batch calls, and so are the bound, its cull value and the
+// statistics epilogue, shared with sr_near.hip; the keys and the sort of a pass (cp_order, which sr_near.hip calls too), the walk's node
+// step (its stack word carries a bound that a pop re-tests; sharing the leaf half cost the lattice 0.5 %: profiles/batch_refactor) and the
+// two kernels are this file's.
 #include <hipcub/hipcub.hpp>
 
 #include "sr_batch.h"
@@ -54,9 +55,6 @@ struct CpArgs {
     unsigned long long* stats;
 };
 
-// (d2, j) of one triangle against the running best: a NaN d2 fails both comparisons, equal d2 goes to the lower TriangleIndex
-__device__ __forceinline__ bool cp_better(double d2, int32_t j, double best, int32_t bj) { return d2 < best || (d2 == best && j < bj); }
-
 // The answer of point i once the best triangle is known: the routine runs once more for the winner (the loops keep (d2, j) only), the limit
 // is applied to the rounded square root, a point without a qualifying answer gets -1 and zeros
 __device__ __forceinline__ void cp_store(const DevScene& sc, const CpArgs& a, size_t i, const double q[3], int32_t bj, bool no_lim, double lim) {
@@ -73,36 +71,6 @@ __device__ __forceinline__ void cp_store(const DevScene& sc, const CpArgs& a, si
     if (a.out_pos) { a.out_pos[3 * i] = c[0]; a.out_pos[3 * i + 1] = c[1]; a.out_pos[3 * i + 2] = c[2]; }
     if (a.out_uv) { a.out_uv[2 * i] = v; a.out_uv[2 * i + 1] = w; }
 }
-
-// block_stat_add's sums (sr_trace.h) in the first four words of the kernel's DYNAMIC LDS instead of a static array: the walk's stacks are
-// dead once every lane has arrived, and at the depth limit they are the whole 64 KiB a workgroup may ask for.  Every thread must call it.
-__device__ __forceinline__ void cp_stat_add(unsigned long long* stats, const Ctr& c) {
-    unsigned int* acc = reinterpret_cast<unsigned int*>(lds_closest);
-    const uint32_t r = wave_sum(c.rays), g = wave_sum(c.geom), n2 = wave_sum(c.nodes), l2 = wave_sum(c.leaves);
-    __syncthreads();                                                      // no lane reads its stack any more
-    if (threadIdx.x < 4) acc[threadIdx.x] = 0u;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        if (r) atomicAdd(&acc[0], r);
-        if (g) atomicAdd(&acc[1], g);
-        if (n2) atomicAdd(&acc[2], n2);
-        if (l2) atomicAdd(&acc[3], l2);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) { stat_add(&stats[0], acc[0]); stat_add(&stats[1], acc[1]); stat_add(&stats[2], acc[2]); stat_add(&stats[3], acc[3]); }
-}
-
-// fp32 lower bound of the squared distance from the point (p = (float)(q - centre), e = 2^-23 |p| per axis) to the stored box [lo, hi]:
-// per axis the gap max(lo - p, p - hi, 0) less e, squared and summed, times (1 - 2^-19).  DESIGN 5.32 proves that it is at most the FP64
-// d2 of every triangle below the box whose closest point the routine placed inside the triangle.
-__device__ __forceinline__ float cp_bound(const float lo[3], const float hi[3], float px, float py, float pz, float ex, float ey, float ez) {
-    const float gx = fmaxf(fmaxf(fmaxf(lo[0] - px, px - hi[0]), 0.0f) - ex, 0.0f);
-    const float gy = fmaxf(fmaxf(fmaxf(lo[1] - py, py - hi[1]), 0.0f) - ey, 0.0f);
-    const float gz = fmaxf(fmaxf(fmaxf(lo[2] - pz, pz - hi[2]), 0.0f) - ez, 0.0f);
-    return (gx * gx + gy * gy + gz * gz) * (1.0f - 1.9073486328125e-6f);
-}
-// the fp32 value a bound must EXCEED to cull: at least `cull` whatever the rounding (an overflow gives +inf: nothing is culled)
-__device__ __forceinline__ float cp_cullf(double cull) { return (float)cull * (1.0f + 2.384185791015625e-7f) + 1e-30f; }
 
 // The tree walk of the regular points.  Stack word = node | the bound's float bits with their low bnode_bits cleared (a lower bound still),
 // one word per level per lane in LDS.
@@ -183,7 +151,7 @@ __global__ __launch_bounds__(256) void k_cp_walk(DevScene sc, CpArgs a) {
         }
         cp_store(sc, a, i, q, bj, no_lim, lim);
     }
-    if (STATS) cp_stat_add(a.stats, c);                                   // (every thread of the workgroup arrives here)
+    if (STATS) cp_stat_add(lds_closest, a.stats, c);                      // (every thread of the workgroup arrives here)
 }
 
 // The per-record loop over v9 in index order: brute force (every point, input order) and the irregular tail of a SR_MODE_BVH pass.
@@ -210,7 +178,7 @@ __global__ __launch_bounds__(256) void k_cp_loop(DevScene sc, CpArgs a) {
         }
         cp_store(sc, a, i, q, bj, no_lim, lim);
     }
-    if (STATS) cp_stat_add(a.stats, c);
+    if (STATS) cp_stat_add(lds_closest, a.stats, c);
 }
 
 namespace {
@@ -228,10 +196,11 @@ hipError_t launch_cp_loop(const ClosestLaunch& L, const CpArgs& a) {
     return hipGetLastError();
 }
 
-// the order of a pass: the regular points first -- sorted: by Morton cell, ties in input order; !sorted: in input order -- then the others
-hipError_t cp_order(const ClosestLaunch& L, const double* points, unsigned int n, const PassBuffers& b) {
+}  // namespace
+
+// (sr_batch.h) the order of a pass: the regular points first -- sorted: by Morton cell, ties in input order; !sorted: in input order -- then the others
+hipError_t cp_order(const BatchLaunch& L, const RootBox& root, const double* points, unsigned int n, const PassBuffers& b) {
     const bool sorted = !L.input_order;
-    const RootBox& root = L.sc.root;
     double s[3];
     for (int k = 0; k < 3; ++k) { const double e = root.max[k] - root.min[k]; s[k] = e > 0 ? 128.0 / e : 0.0; }
     const unsigned int skip = point_order_skip_mask(sorted);
@@ -246,8 +215,6 @@ hipError_t cp_order(const ClosestLaunch& L, const double* points, unsigned int n
                                               L.stream);
 }
 
-}  // namespace
-
 // SR_MODE_BVH: a pass is ordered first, the regular points walk the tree, the tail runs the per-record loop (loop_all: every point does).
 // SR_MODE_BRUTE: the per-record loop in input order
 hipError_t launch_closest(const ClosestLaunch& L) {
@@ -261,7 +228,7 @@ hipError_t launch_closest(const ClosestLaunch& L) {
     a.stats = L.stats;
     return run_passes(
         L, L.mode == MODE_BVH, K_CLOSEST_SORT, K_CLOSEST,
-        [&](int64_t first, unsigned int count, const PassBuffers& b) { return cp_order(L, L.points + 3 * first, count, b); },
+        [&](int64_t first, unsigned int count, const PassBuffers& b) { return cp_order(L, L.sc.root, L.points + 3 * first, count, b); },
         [&](const PassSlice& p, const PassBuffers&) {
             a.pass = p;
             if (L.mode != MODE_BVH || L.loop_all) return launch_cp_loop(L, a);

@@ -192,6 +192,8 @@ const char* kernel_name(int id) {
         case K_ALL_HITS_SORT: return "k_all_hits_sort";       // ... its order: k_occl_keys + the radix sort
         case K_CLOSEST: return "k_closest";                   // sr_closest_points: a pass's walk and the per-record loop for its irregular points
         case K_CLOSEST_SORT: return "k_closest_sort";         // ... its order: k_cp_keys + the radix sort
+        case K_NEAR: return "k_near";                         // sr_near_triangles: a pass's walk and the per-record loop for its irregular points
+        case K_NEAR_SORT: return "k_near_sort";               // ... its order: sr_closest_points' (k_cp_keys + the radix sort)
         case K_VOXEL_WALK: return "k_voxel_walk";
         case K_VOXELISE: return "voxelise";                   // count, scan, emit, sort, per-cell sums of one sr_build_voxels
         case K_SHAFT2: return "k_shaft_round2";

@@ -561,6 +561,19 @@ public:
         PreCalculate();                                    // the model and the tree of Mode() are in the scene
         sr_check(sr_closest_points(scene_, Mode(), n, points, max_dist, tri_index, dist, pos, uv, coherent ? SR_POINTS_COHERENT : 0u, nullptr));
     }
+    // The triangles within reach of n points of the caller's, nearest first, with a count (sr_near_triangles): count[i] = the triangles whose
+    // distance is a number <= max_dist[i] (max_dist == nullptr: no limit; not capped by max_hits), rows i of index / dist / pos / uv
+    // ([n][max_hits], [n][max_hits], [n][max_hits][3], [n][max_hits][2]) the first min(count, max_hits) of them by (squared distance,
+    // TriangleIndex) -- slot 0 is ClosestPoints' answer -- the rest of a row -1 / zeros.  Any output may be nullptr (count == nullptr: a
+    // K-nearest query); max_hits 0 .. SR_HITS_MAX.  The model alone; needs the own BVH or brute force (the library refuses the reference
+    // tree).  coherent: SR_POINTS_COHERENT.  Does nothing without a model
+    void NearTriangles(int64_t n, const double* points, const double* max_dist, int32_t max_hits, uint32_t* count, int32_t* index, double* dist, double* pos,
+                       double* uv, bool coherent = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel()) return;
+        PreCalculate();                                    // the model and the tree of Mode() are in the scene
+        sr_check(sr_near_triangles(scene_, Mode(), n, points, max_dist, max_hits, count, index, dist, pos, uv, coherent ? SR_POINTS_COHERENT : 0u, nullptr));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

@@ -689,6 +689,42 @@ class GpuScene:
         _check(_lib.lib().sr_closest_points_device(self._h, int(target), int(n), _vp(d_points), _vp(d_max_dist), _vp(d_tri_index), _vp(d_dist), _vp(d_pos),
                                                    _vp(d_uv), _lib.POINTS_COHERENT if coherent else 0, _stream(stream), _vp(d_stats_ptr)))
 
+    # ---- the triangles within reach of a point, nearest first, with a count (sr_near_triangles) ----
+    def near_triangles(self, target, points, max_dist=None, max_hits=8, want=("count", "index", "dist", "pos", "uv"), coherent=False, stats=False):
+        """For every point the triangles whose distance is a number <= max_dist (None: no limit): a dict with `count` (uint32 [n], not capped
+        by max_hits), and rows ordered by (squared distance, TriangleIndex): `index` (int32 [n][max_hits], -1 in unused slots), `dist` (float64
+        [n][max_hits]), `pos` (float64 [n][max_hits][3], the closest points) and `uv` (float64 [n][max_hits][2], the weights of vertices 2 and
+        3), zeros in unused slots.  Slot 0 is closest_points' answer.  `want` names the outputs asked for (the others are None; without
+        "count" the walk also culls beyond the max_hits-th entry: a K-nearest query); with stats=True also the four counters, `stats`.
+        max_hits=0 is the counting call.  target: MODE_BVH or MODE_BRUTE."""
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = points.shape[0]
+        if max_dist is not None:
+            max_dist = np.ascontiguousarray(max_dist, dtype=np.float64).reshape(-1)
+            if max_dist.size != n:
+                raise ValueError("max_dist has %d entries for %d points" % (max_dist.size, n))
+        k = int(max_hits)
+        rows = max(0, min(k, _lib.HITS_MAX))
+        res = {"count": np.zeros(n, dtype=np.uint32) if "count" in want else None,
+               "index": np.full((n, rows), -1, dtype=np.int32) if "index" in want else None,
+               "dist": np.zeros((n, rows), dtype=np.float64) if "dist" in want else None,
+               "pos": np.zeros((n, rows, 3), dtype=np.float64) if "pos" in want else None,
+               "uv": np.zeros((n, rows, 2), dtype=np.float64) if "uv" in want else None}
+        row = lambda name: _p(res[name]) if rows else None                                   # noqa: E731
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        _check(_lib.lib().sr_near_triangles(self._h, int(target), n, _p(points), _p(max_dist), k, _p(res["count"]), row("index"), row("dist"), row("pos"),
+                                            row("uv"), _lib.POINTS_COHERENT if coherent else 0, _p(st)))
+        if stats:
+            res["stats"] = st
+        return res
+
+    def near_triangles_device(self, target, n, d_points, d_max_dist=0, max_hits=8, d_count=0, d_index=0, d_dist=0, d_pos=0, d_uv=0, coherent=False, stream=0,
+                              d_stats_ptr=None):
+        """sr_near_triangles_device: every array is a DEVICE pointer (d_max_dist 0 / None: no limit; an output 0 / None: not wanted); enqueued on
+        `stream` (a raw hipStream_t or a torch.cuda.Stream), no host sync."""
+        _check(_lib.lib().sr_near_triangles_device(self._h, int(target), int(n), _vp(d_points), _vp(d_max_dist), int(max_hits), _vp(d_count), _vp(d_index),
+                                                   _vp(d_dist), _vp(d_pos), _vp(d_uv), _lib.POINTS_COHERENT if coherent else 0, _stream(stream), _vp(d_stats_ptr)))
+
     # ---- the colour light field for caller-given rays (sr_light_field_rays) ----
     def light_field_rays(self, frame, starts, dirs, want_inside=True):
         """LightFieldColorMethod.IntersectRay for n lines of the caller's (sr_light_field_rays): (out uint32 [n], inside uint8 [n] or None,

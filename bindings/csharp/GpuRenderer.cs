@@ -132,6 +132,8 @@ namespace Engine3D.Hip
         [DllImport(Lib)] public static extern int sr_closest_points_device(IntPtr scene, int target, long n, IntPtr dPoints, IntPtr dMaxDist, IntPtr dTriIndex, IntPtr dDist, IntPtr dPos, IntPtr dUv, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_near_triangles(IntPtr scene, int target, long n, [In] double[] points, [In] double[] maxDist, int maxHits, [Out] uint[] count, [Out] int[] index, [Out] double[] dist, [Out] double[] pos, [Out] double[] uv, uint options, [Out] ulong[] stats4);
         [DllImport(Lib)] public static extern int sr_near_triangles_device(IntPtr scene, int target, long n, IntPtr dPoints, IntPtr dMaxDist, int maxHits, IntPtr dCount, IntPtr dIndex, IntPtr dDist, IntPtr dPos, IntPtr dUv, uint options, IntPtr hipStream, IntPtr dStats);
+        [DllImport(Lib)] public static extern int sr_overlap_triangles(IntPtr scene, int target, long n, [In] double[] tris, int maxHits, [Out] uint[] count, [Out] int[] index, [Out] byte[] mask, uint options, [Out] ulong[] stats4);
+        [DllImport(Lib)] public static extern int sr_overlap_triangles_device(IntPtr scene, int target, long n, IntPtr dTris, int maxHits, IntPtr dCount, IntPtr dIndex, IntPtr dMask, uint options, IntPtr hipStream, IntPtr dStats);
         [DllImport(Lib)] public static extern int sr_load_3ds(IntPtr scene, byte[] data, UIntPtr len);
         [DllImport(Lib)] public static extern int sr_post_process(IntPtr scene, [In, Out] int[] pixels, long count, int style, uint backgroundColor);
         [DllImport(Lib)] public static extern int sr_anti_alias(IntPtr scene, [In] int[] src, int dstWidth, int dstHeight, int resolution, [In, Out] int[] dst);
@@ -770,6 +772,32 @@ namespace Engine3D.Hip
         {
             Native.Check(Native.sr_near_triangles_device(scene, mode, n, dPoints, dMaxDist, maxHits, dCount, dIndex, dDist, dPos, dUv,
                                                          coherent ? POINTS_COHERENT : 0, stream, dStats));
+        }
+
+        /// The triangles of the model that cross each triangle of a batch (sr_overlap_triangles; tris: [n * 9]).  Count[i]: the triangles that the
+        /// pair predicate of softray.h reports (not capped by maxHits); rows i of Index / Mask ([n * maxHits]): the first min(Count, maxHits) of
+        /// them by ascending TriangleIndex with the masks of their pairs (bit e: the query's edge e meets the scene triangle; bit 3 + e: the scene
+        /// triangle's edge e meets the query), the rest of a row -1 / 0.  anyHit (SR_OVERLAP_ANY, maxHits must be 0): Count is 0 or 1.  mode is
+        /// MODE_BVH or MODE_BRUTE; the model alone, no extra geometry.  Blocks.
+        public const uint OVERLAP_ANY = 4;
+        public sealed class OverlapTriangleLists { public int MaxHits; public uint[] Count; public int[] Index; public byte[] Mask; public ulong[] Stats4; }
+        public OverlapTriangleLists OverlapTriangles(double[] tris, int maxHits, int mode, bool coherent = false, bool anyHit = false)
+        {
+            long n = tris.Length / 9;
+            long rows = n * Math.Max(0, maxHits);
+            var r = new OverlapTriangleLists { MaxHits = maxHits, Count = new uint[n], Index = new int[rows], Mask = new byte[rows], Stats4 = new ulong[4] };
+            Native.Check(Native.sr_overlap_triangles(scene, mode, n, tris, maxHits, r.Count, r.Index, r.Mask, (coherent ? POINTS_COHERENT : 0) | (anyHit ? OVERLAP_ANY : 0),
+                                                     r.Stats4));
+            return r;
+        }
+
+        /// The same with every array in DEVICE memory on the scene's device (sr_overlap_triangles_device), IntPtr.Zero for an output that is not
+        /// wanted; enqueued on `stream` without a host synchronisation; dStats: ulong[24] on the device, or IntPtr.Zero.
+        public void OverlapTrianglesDevice(long n, IntPtr dTris, int maxHits, int mode, bool coherent, bool anyHit, IntPtr dCount, IntPtr dIndex, IntPtr dMask,
+                                           IntPtr stream, IntPtr dStats)
+        {
+            Native.Check(Native.sr_overlap_triangles_device(scene, mode, n, dTris, maxHits, dCount, dIndex, dMask,
+                                                            (coherent ? POINTS_COHERENT : 0) | (anyHit ? OVERLAP_ANY : 0), stream, dStats));
         }
 
         /// ShadingMethod's colour step for n recorded intersections in DEVICE memory (sr_shade_points_device): dOut[i] = dColor[i] modulated with

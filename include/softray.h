@@ -831,6 +831,57 @@ int  sr_near_triangles_device(sr_scene*, int32_t target, int64_t n, const double
                               int32_t max_hits, uint32_t* d_count, int32_t* d_index, double* d_dist, double* d_pos, double* d_uv /* each may be NULL */,
                               uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
 
+/* THE TRIANGLES OF THE MODEL THAT CROSS each triangle of a batch, with a count and, per pair, which edges pierce -- mesh against mesh, the
+ * fifth question next to the rays' and the points': contact against a mesh that moves (sr_refit_triangles_device), a tool against a surface, "is
+ * it colliding at all".  The edges of a query sent through sr_all_hits_rays find where the query pierces the scene; the other half, scene edges
+ * that pierce the query, has no other route, and ray hits are one-sided and clipped to the root box.
+ * The pair predicate (csrc/sr_tri_overlap.h: one text for the kernels and the host, FP64, only + - * and comparisons in a fixed operand order, no
+ * contraction):
+ *   vol(a, b, c, d): u = b - a, v = c - a, w = d - a, n = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x); the value n.x w.x + n.y w.y +
+ *   n.z w.z, summed left to right.  WHEN ANY TWO OF THE FOUR POINTS ARE EQUAL (== on all three components) vol IS EXACTLY 0.
+ *   Edge (p, q) MEETS triangle (a, b, c): sp = vol(a, b, c, p), sq = vol(a, b, c, q); no when sp and sq are both > 0, both < 0, both == 0 (the edge
+ *   lies in the plane) or either is NaN; otherwise s1 = vol(p, q, a, b), s2 = vol(p, q, b, c), s3 = vol(p, q, c, a) and the edge meets the triangle
+ *   iff all three are >= 0 or all three are <= 0.  Closed: touching counts.  A NaN fails every comparison.
+ *   The MASK of the pair (query A = tris[i], scene B = the vertices of triangle j as the scene holds them): bit e (0..2): edge (A[e], A[(e + 1) % 3])
+ *   meets B; bit 3 + e: edge (B[e], B[(e + 1) % 3]) meets A.
+ *   The pair is REPORTED iff all 18 coordinates are finite, the FP64 bounding boxes of A and B overlap on every axis (closed <= on the coordinates
+ *   as given) and the mask is not 0.  The box condition never changes a true answer; it makes the tree's cull conservative by construction.
+ * Consequences: coplanar pairs are never reported; a triangle without area can be pierced by nothing, but its edges can pierce; a triangle never
+ * crosses itself or an exact copy; two triangles of a mesh that share exactly one vertex are reported (a touch), two that share an edge are
+ * reported unless they are coplanar in FP64; swapping the roles swaps the two halves of the mask.
+ * Outputs: count[i] = the number of reported triangles, NOT capped by max_hits (K).  Row index[i][0..K): the first min(count, K) of them by
+ * ascending TriangleIndex; mask[i][k]: the mask of that pair.  Every other slot of every row is written: index -1, mask 0.  max_hits == 0 is the
+ * counting call.  Any of the three arrays may be NULL; all NULL: the call runs for the statistics.  An index row that the masks need and the caller
+ * does not ask for is kept in the scene's first scratch set, in passes of at most 2^24 / K queries.
+ * Options: SR_POINTS_COHERENT (bit 0): 64 consecutive queries are neighbours, the input order is kept.  SR_OVERLAP_ANY (4u; bit 1 is
+ * SR_RAYS_ENDPOINTS elsewhere): count[i] is 1 if any triangle is reported and 0 otherwise, and the query stops at the first one; max_hits must be 0.
+ * Targets: SR_MODE_BVH and SR_MODE_BRUTE, the same answers bit for bit.  SR_MODE_REF_TREE (a triangle lives in several leaves), SR_TARGET_ROOT | mode
+ * (the extra primitives are not triangles with indices) and SR_TARGET_VOXELS are SR_ERR_UNSUPPORTED.
+ * Routing in SR_MODE_BVH: a query is REGULAR when each of its vertices passes sr_closest_points' test (finite, within 2^20 box diagonals of the
+ * centre).  The regular queries of a pass, ordered by the Morton cell of the centre of their box (SR_POINTS_COHERENT: input order), walk the own
+ * BVH one lane each (k_ot_walk): the query's box relative to the root centre is rounded to fp32 and widened outward, and a child is entered iff it
+ * overlaps the child's stored box on all three axes -- every leaf triangle whose FP64 box overlaps the query's is reached whatever the rounding
+ * of the build or of a refit.  Every other query runs the per-record loop (k_ot_loop), as every query of SR_MODE_BRUTE does in
+ * input order.
+ * Refusals, in this order: a NULL scene, n < 0, NULL tris with n > 0, max_hits outside 0 .. SR_HITS_MAX, unknown option bits, SR_OVERLAP_ANY with
+ * max_hits > 0: SR_ERR_INVALID_ARG; SR_TARGET_VOXELS, SR_TARGET_ROOT, SR_MODE_REF_TREE: SR_ERR_UNSUPPORTED; sr_trace_rays' own checks
+ * (SR_ERR_NO_MODEL, SR_ERR_NOT_BUILT); a host-only scene: SR_ERR_NO_DEVICE.  A refusal writes nothing.  n == 0 that passes all of them: SR_OK,
+ * nothing is touched.
+ * State: as sr_near_triangles -- the call is ordered like a frame and rewrites no per-origin or per-light record, passes of at most 2^22 queries
+ * (SR_DBG_BAND_SAMPLES: fewer) follow each other without the host waiting, a multi-device scene runs the call on devices[0].  The host variant
+ * stages 72 n bytes in and 4 n + 5 K n bytes out through the scene's device buffers, blocks and fills sr_last_ray_stats; the device variant
+ * enqueues on `hip_stream` without a host synchronisation.  Statistics: [0] = n; [1..3] = pairs on which the predicate ran, nodes and leaves
+ * visited (pinned in brute force without SR_OVERLAP_ANY only: n x triangles, 0, 0); [4..] 0.
+ * Out of scope: the intersection segment or contact points; penetration depth; excluding the neighbours in a self-query (the caller drops the
+ * pairs that share vertices); the four-wide tree and persistent lanes; a split over devices; coplanar overlap. */
+#define SR_OVERLAP_ANY 4u
+int  sr_overlap_triangles(sr_scene*, int32_t target, int64_t n, const double* tris /* [n][3][3] */, int32_t max_hits /* K, 0..SR_HITS_MAX */,
+                          uint32_t* count /* [n] or NULL */, int32_t* index /* [n][K] or NULL */, uint8_t* mask /* [n][K] or NULL */,
+                          uint32_t options, uint64_t stats[4] /* or NULL */);
+int  sr_overlap_triangles_device(sr_scene*, int32_t target, int64_t n, const double* d_tris, int32_t max_hits,
+                                 uint32_t* d_count, int32_t* d_index, uint8_t* d_mask /* each may be NULL */,
+                                 uint32_t options, void* hip_stream, uint64_t* d_stats /* device uint64[SR_STATS_COUNT] or NULL */);
+
 /* ShadingMethod.IntersectRay's colour step in batch (ShadingMethod.cs:36-68 -> CalcLighting :110-177): for n recorded
  * intersections out[i] = ModulatePackedColor(color[i], (byte)(255 * intensity)) with the frame's transform and lights (only the
  * matrices, position_z, fov_depth, lights, ambient, shininess and the POINT_LIGHT / SPECULAR flags of `frame` are read).
@@ -1155,7 +1206,8 @@ enum {
                                     (no ray sort); 51 sr_all_hits_rays answers every ray of SR_MODE_BVH with the per-record loop of its irregular rays (both: same output;
                                     cross-check); 52 sr_closest_points walks a pass in input order whatever the options say (no point sort); 53 sr_closest_points
                                     answers every point of SR_MODE_BVH with the per-record loop of its irregular points (both: same output; cross-check); 54 sr_near_triangles walks a pass in input order whatever the options say (no point sort); 55 sr_near_triangles
-                                    answers every point of SR_MODE_BVH with the per-record loop of its irregular points (both: same output; cross-check); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
+                                    answers every point of SR_MODE_BVH with the per-record loop of its irregular points (both: same output; cross-check); 56 sr_overlap_triangles walks a pass in input order whatever the options say (no sort); 57 sr_overlap_triangles
+                                    answers every query of SR_MODE_BVH with the per-record loop of its irregular queries (both: same output; cross-check); 39 the apply kernel of an interpolating light-field frame (sr_set_light_field_interpolation) computes base cell and
                                     fractions again instead of taking them from the lookup kernel (same frame; measured slower); 100 + T: the walk kernel
                                     fetches new rays at T busy lanes (default 24); 200 + K: K stack levels per lane in LDS (default 24);
                                     81 the tile kernels with one workgroup per 16x16 tile (no persistent grid); 82 k_primary on the persistent grid

@@ -59,11 +59,13 @@ SYMBOLS = [
     "sr_light_field_rays", "sr_light_field_rays_device",
     "sr_all_hits_rays", "sr_all_hits_rays_device",
     "sr_closest_points", "sr_closest_points_device", "sr_near_triangles", "sr_near_triangles_device",
+    "sr_overlap_triangles", "sr_overlap_triangles_device",
 ]
 POINTS_COHERENT = 1                    # SR_POINTS_COHERENT
 RAYS_COHERENT = 1                      # SR_RAYS_COHERENT
 RAYS_ENDPOINTS = 2                     # SR_RAYS_ENDPOINTS (sr_occluded_rays, sr_nearest_rays, sr_all_hits_rays)
 HITS_MAX = 64                          # SR_HITS_MAX (sr_all_hits_rays)
+OVERLAP_ANY = 4                        # SR_OVERLAP_ANY (sr_overlap_triangles)
 GATHER_COPY, GATHER_RCCL = 0, 1
 RCCL_ID_BYTES = 128
 # sr_debug_set keys (include/softray.h)
@@ -199,6 +201,8 @@ def lib():
     L.sr_closest_points_device.restype = i32; L.sr_closest_points_device.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_near_triangles.restype = i32; L.sr_near_triangles.argtypes = [vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, C.c_uint32, vp]
     L.sr_near_triangles_device.restype = i32; L.sr_near_triangles_device.argtypes = [vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
+    L.sr_overlap_triangles.restype = i32; L.sr_overlap_triangles.argtypes = [vp, i32, i64, vp, i32, vp, vp, vp, C.c_uint32, vp]
+    L.sr_overlap_triangles_device.restype = i32; L.sr_overlap_triangles_device.argtypes = [vp, i32, i64, vp, i32, vp, vp, vp, C.c_uint32, vp, vp]
     L.sr_light_field_rays.restype = i32; L.sr_light_field_rays.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp]
     L.sr_light_field_rays_device.restype = i32; L.sr_light_field_rays_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.sr_rccl_unique_id.restype = i32; L.sr_rccl_unique_id.argtypes = [vp]

@@ -1923,7 +1923,7 @@ int run_staged(sr_scene* m, sr_scene* s, Staged* io, int count, bool upload_asyn
     return SR_OK;
 }
 
-// ---- The batch calls without a frame (sr_occluded_rays, sr_nearest_rays, sr_all_hits_rays, sr_closest_points, sr_near_triangles): one refusal ladder, one entry
+// ---- The batch calls without a frame (sr_occluded_rays, sr_nearest_rays, sr_all_hits_rays, sr_closest_points, sr_near_triangles, sr_overlap_triangles): one refusal ladder, one entry
 // path for the host-array and the device-array variant, one setup of the passes
 // What such a call refuses before the device is looked at, in the header's order.  Every sentence follows "<name>: "
 struct ItemCall {
@@ -1935,6 +1935,8 @@ struct ItemCall {
     const char* voxels;           // SR_TARGET_VOXELS
     const char* root;             // SR_TARGET_ROOT (nullptr: the call takes the extra geometry)
     const char* ref_tree;         // SR_MODE_REF_TREE (nullptr: the call runs on the reference tree)
+    uint32_t    counting;         // option bits that need max_hits == 0 (0: none)
+    const char* counting_rows;    // ... one of them with max_hits > 0
 };
 
 // `s`: in, the caller's scene; out, the scene that runs the call (the first part of a multi-device scene).  `args_ok`: no array the call
@@ -1948,6 +1950,7 @@ int item_call_check(const ItemCall& c, sr_scene*& s, int32_t target, int64_t n, 
     if (n > 0 && !args_ok) return refuse(SR_ERR_INVALID_ARG, c.null_args);
     if (c.max_hits && (max_hits < 0 || max_hits > SR_HITS_MAX)) return refuse(SR_ERR_INVALID_ARG, "max_hits must be 0 .. SR_HITS_MAX (64)");
     if (options & ~c.options) return refuse(SR_ERR_INVALID_ARG, c.unknown_options);
+    if ((options & c.counting) && max_hits > 0) return refuse(SR_ERR_INVALID_ARG, c.counting_rows);
     if (target & SR_TARGET_VOXELS) return refuse(SR_ERR_UNSUPPORTED, c.voxels);
     if (c.root && (target & SR_TARGET_ROOT)) return refuse(SR_ERR_UNSUPPORTED, c.root);
     with_extra = (target & SR_TARGET_ROOT) != 0;
@@ -3517,6 +3520,69 @@ int sr_near_triangles(sr_scene* m, int32_t target, int64_t n, const double* poin
                      [&](sr_scene* s, int mode, bool, hipStream_t stream, unsigned long long* d_stats) {
                          const NearOut out{(uint32_t*)io[2].dev, (int32_t*)io[3].dev, (double*)io[4].dev, (double*)io[5].dev, (double*)io[6].dev};
                          return near_common(s, mode, n, (const double*)io[0].dev, (const double*)io[1].dev, max_hits, out, options, stream, d_stats);
+                     });
+}
+
+// ---- The triangles of the model that cross a triangle of the caller's, with a count and the masks of the pairs (sr_overlap_triangles)
+static const ItemCall kOverlapTrianglesCall = {
+    "sr_overlap_triangles", "tris must not be NULL when n > 0", true,
+    SR_POINTS_COHERENT | SR_OVERLAP_ANY, "unknown option bits (SR_POINTS_COHERENT and SR_OVERLAP_ANY are the options)",
+    "the voxel grid (SR_TARGET_VOXELS) has no triangles to cross",
+    "the extra geometry (SR_TARGET_ROOT) is not made of triangles with indices; pass the mode alone",
+    "SR_MODE_REF_TREE has no overlap query (a triangle lives in several leaves of the reference tree and would be listed twice); use SR_MODE_BVH or "
+    "SR_MODE_BRUTE",
+    SR_OVERLAP_ANY, "SR_OVERLAP_ANY answers with a count of 0 or 1 and keeps no rows: max_hits must be 0"};
+
+struct OverlapOut { uint32_t* count; int32_t* index; uint8_t* mask; };
+
+// (an index row the masks need and the caller does not want lives in the first scratch set's bounce buffer, as sr_near_triangles' rows)
+static int overlap_common(sr_scene* s, int mode, int64_t n, const double* d_tris, int32_t max_hits, const OverlapOut& out, uint32_t options, hipStream_t stream,
+                          unsigned long long* d_stats) {
+    const bool own_rows = max_hits > 0 && !out.index && out.mask;
+    const int64_t max_pass = own_rows ? std::min<int64_t>(sr::kBatchMaxPass, (1ll << 24) / max_hits) : sr::kBatchMaxPass;   // (at most 2^24 slots of scratch rows)
+    sr::OverlapLaunch L{};
+    std::unique_ptr<StreamOrder> order;
+    size_t slots;
+    int rc = item_call_setup(s, mode, n, max_pass, mode == SR_MODE_BVH, stream, d_stats, order, L, slots);
+    if (rc) return rc;
+    const int64_t hook = s->dbg[SR_DBG_KERNEL_SWITCH];
+    L.sc = dev_scene(s);
+    L.mode = mode;
+    L.tris = d_tris;
+    L.max_hits = max_hits;
+    L.any = (options & SR_OVERLAP_ANY) != 0;
+    L.count = out.count;
+    L.index = max_hits > 0 ? out.index : nullptr;
+    L.mask = max_hits > 0 ? out.mask : nullptr;
+    L.input_order = (options & SR_POINTS_COHERENT) != 0 || hook == 56;                          // (hook: input order whatever the options say)
+    L.loop_all = hook == 57;                                                                    // (hook: every query through the per-record loop)
+    if (own_rows) {
+        sr_scene::BandScratch& B = s->scratch[0];
+        SR_HIP(B.bounce_res.reserve(slots * (size_t)max_hits * sizeof(int32_t)));
+        L.scratch_index = (int32_t*)B.bounce_res.p;
+    }
+    SR_HIP(sr::launch_overlap(L));
+    return SR_OK;
+}
+
+int sr_overlap_triangles_device(sr_scene* m, int32_t target, int64_t n, const double* d_tris, int32_t max_hits, uint32_t* d_count, int32_t* d_index, uint8_t* d_mask,
+                                uint32_t options, void* hip_stream, uint64_t* d_stats) {
+    return item_call(kOverlapTrianglesCall, m, target, n, d_tris != nullptr, max_hits, options, {nullptr, 0, nullptr, hip_stream, d_stats},
+                     [&](sr_scene* s, int mode, bool, hipStream_t stream, unsigned long long* stats) {
+                         const OverlapOut out{d_count, d_index, d_mask};
+                         return overlap_common(s, mode, n, d_tris, max_hits, out, options, stream, stats);
+                     });
+}
+
+int sr_overlap_triangles(sr_scene* m, int32_t target, int64_t n, const double* tris, int32_t max_hits, uint32_t* count, int32_t* index, uint8_t* mask,
+                         uint32_t options, uint64_t stats[4]) {
+    const size_t rows = (size_t)n * (size_t)max_hits;
+    const bool k = max_hits > 0;
+    Staged io[] = {{tris, nullptr, (size_t)n * 72}, {nullptr, count, (size_t)n * 4}, {nullptr, k ? index : nullptr, rows * 4}, {nullptr, k ? mask : nullptr, rows}};
+    return item_call(kOverlapTrianglesCall, m, target, n, tris != nullptr, max_hits, options, {io, 4, stats, nullptr, nullptr},
+                     [&](sr_scene* s, int mode, bool, hipStream_t stream, unsigned long long* d_stats) {
+                         const OverlapOut out{(uint32_t*)io[1].dev, (int32_t*)io[2].dev, (uint8_t*)io[3].dev};
+                         return overlap_common(s, mode, n, (const double*)io[0].dev, max_hits, out, options, stream, d_stats);
                      });
 }
 

@@ -1,4 +1,4 @@
-// sr_batch.h -- what the batch calls without a frame share (sr_occluded.hip, sr_nearest.hip, sr_allhits.hip, sr_closest.hip, sr_near.hip; nothing else
+// sr_batch.h -- what the batch calls without a frame share (sr_occluded.hip, sr_nearest.hip, sr_allhits.hip, sr_closest.hip, sr_near.hip, sr_overlap.hip; nothing else
 // includes it).  Device side: which item a lane of a pass takes, an item's ray, the fp32 frame of a ray for the private binary walk and that
 // walk's node step, the statistics epilogue.  Host side: the pass driver.  A call keeps what is its own: its kernels, how a pass is
 // ordered and what is launched for one.
@@ -89,7 +89,7 @@ __device__ __forceinline__ void block_stat_add(unsigned long long* stats, const 
     block_stat_add(&stats[0], &stats[1], &stats[2], &stats[3], r, g, n, l);
 }
 
-// ---- the point calls (sr_closest.hip, sr_near.hip): what their walks and loops share
+// ---- the point calls (sr_closest.hip, sr_near.hip; sr_overlap.hip takes cp_stat_add): what their walks and loops share
 // (d2, j) of one triangle against the running best: a NaN d2 fails both comparisons, equal d2 goes to the lower TriangleIndex
 __device__ __forceinline__ bool cp_better(double d2, int32_t j, double best, int32_t bj) { return d2 < best || (d2 == best && j < bj); }
 

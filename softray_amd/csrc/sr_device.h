@@ -44,7 +44,7 @@ struct DevScene {
 };
 
 constexpr int kShaftRounds = 2;
-enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_LFR_LOOKUP = 46, K_LFR_FINISH = 47, K_LFRI_LOOKUP = 48, K_LFRI_FINISH = 49, K_NEAREST = 50, K_NEAREST_SORT = 51, K_ALL_HITS = 52, K_ALL_HITS_SORT = 53, K_CLOSEST = 54, K_CLOSEST_SORT = 55, K_NEAR = 56, K_NEAR_SORT = 57, K_COUNT = 58 };
+enum KernelId { K_RENDER = 0, K_TRACE = 1, K_PRIMARY = 2, K_SHADOW = 3, K_RESOLVE = 4, K_SHAFT = 5, K_FALLBACK = 6, K_SHAFT2 = 7, K_SHADOW2 = 8, K_POST = 9, K_ANTI_ALIAS = 10, K_BOUNCE = 11, K_PATHTRACE = 12, K_PT_COUNT = 13, K_PT_EXCHANGE = 14, K_VOXEL_WALK = 15, K_VOXELISE = 16, K_AO = 17, K_AO_PROBE = 18, K_LF_LOOKUP = 19, K_LF_FILL = 20, K_LF_APPLY = 21, K_LF_BAKE = 22, K_TRI_RECORDS = 23, K_TRI_BOUNDS = 24, K_REFIT_LEAVES = 25, K_REFIT_NODES = 26, K_PTS_INGEST = 27, K_PTS_SORT = 28, K_LFI_LOOKUP = 29, K_LFI_APPLY = 30, K_LFT_FILL = 31, K_LFT_HIT = 32, K_LFT_TRACE = 33, K_LFT_BAKE = 34, K_HITS = 35, K_DRAWS = 36, K_AOP_PROBE = 37, K_PP_TRACE = 38, K_SSP_CLAIM = 39, K_SSP_APPLY = 40, K_TIGHT_BOXES = 41, K_ORIGIN_RAYS = 42, K_ORIGIN_SORT = 43, K_OCCLUDED = 44, K_OCCL_SORT = 45, K_LFR_LOOKUP = 46, K_LFR_FINISH = 47, K_LFRI_LOOKUP = 48, K_LFRI_FINISH = 49, K_NEAREST = 50, K_NEAREST_SORT = 51, K_ALL_HITS = 52, K_ALL_HITS_SORT = 53, K_CLOSEST = 54, K_CLOSEST_SORT = 55, K_NEAR = 56, K_NEAR_SORT = 57, K_OVERLAP = 58, K_OVERLAP_SORT = 59, K_COUNT = 60 };
 const char* kernel_name(int id);
 
 struct RenderLaunch {
@@ -402,7 +402,7 @@ hipError_t dir_order(const double* dirs, unsigned int n, bool sorted, unsigned i
 hipError_t occl_order(const double* starts, const double* dirs, const double* limits, unsigned int n, bool endpoints, bool sorted, const RootBox& root,
                       unsigned int* keys, unsigned int* keys2, unsigned int* idx, unsigned int* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
 
-// What the launches of the five batch calls below share (sr_batch.h holds the pass driver that reads it).  A call runs its n items in passes
+// What the launches of the six batch calls below share (sr_batch.h holds the pass driver that reads it).  A call runs its n items in passes
 // of `pass`; on the own BVH a pass is ordered first, the regular items in front and the irregular tail last
 constexpr int64_t kBatchMaxPass = 1ll << 22;
 struct BatchLaunch {
@@ -509,6 +509,24 @@ struct NearLaunch : BatchLaunch {
     bool        loop_all;       // SR_MODE_BVH with the per-record loop for every point (hook 55)
 };
 hipError_t launch_near(const NearLaunch& L);
+
+// sr_overlap_triangles (sr_overlap.hip): for n caller-given triangles every triangle of the model that the pair predicate of
+// sr_tri_overlap.h reports -- count, and the first max_hits of them by TriangleIndex with the masks of their pairs.  SR_MODE_BVH: a pass
+// ordered by the Morton cell of the centre of the query's box (k_ot_keys), k_ot_walk for the regular queries, k_ot_loop (the per-record
+// loop) for the others; SR_MODE_BRUTE: k_ot_loop in input order
+struct OverlapLaunch : BatchLaunch {
+    DevScene    sc;
+    int32_t     mode;           // SR_MODE_BVH or SR_MODE_BRUTE
+    const double* tris;         // device [n][3][3]
+    int32_t     max_hits;       // K, 0 .. kAllHitsMax
+    bool        any;            // SR_OVERLAP_ANY: count is 0 or 1 and a query stops at its first reported triangle (max_hits == 0)
+    uint32_t*   count;          // device [n] or nullptr
+    int32_t*    index;          // device [n][K] or nullptr
+    uint8_t*    mask;           // device [n][K] or nullptr
+    int32_t*    scratch_index;  // device [pass][K]: a lane's row where index is nullptr and mask is not (K > 0)
+    bool        loop_all;       // SR_MODE_BVH with the per-record loop for every query (hook 57)
+};
+hipError_t launch_overlap(const OverlapLaunch& L);
 
 // the four-wide tree collapsed from a device-resident binary tree (same rule as the host's collapse_bvh4); d_wide: >= num_nodes entries
 // level_first (nullable): the wide nodes are numbered level by level -- level L is [level_first[L], level_first[L + 1]), the last entry

@@ -194,6 +194,8 @@ const char* kernel_name(int id) {
         case K_CLOSEST_SORT: return "k_closest_sort";         // ... its order: k_cp_keys + the radix sort
         case K_NEAR: return "k_near";                         // sr_near_triangles: a pass's walk and the per-record loop for its irregular points
         case K_NEAR_SORT: return "k_near_sort";               // ... its order: sr_closest_points' (k_cp_keys + the radix sort)
+        case K_OVERLAP: return "k_overlap";                   // sr_overlap_triangles: a pass's walk and the per-record loop for its irregular queries
+        case K_OVERLAP_SORT: return "k_overlap_sort";         // ... its order: k_ot_keys + the radix sort
         case K_VOXEL_WALK: return "k_voxel_walk";
         case K_VOXELISE: return "voxelise";                   // count, scan, emit, sort, per-cell sums of one sr_build_voxels
         case K_SHAFT2: return "k_shaft_round2";

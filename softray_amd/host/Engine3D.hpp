@@ -574,6 +574,20 @@ public:
         PreCalculate();                                    // the model and the tree of Mode() are in the scene
         sr_check(sr_near_triangles(scene_, Mode(), n, points, max_dist, max_hits, count, index, dist, pos, uv, coherent ? SR_POINTS_COHERENT : 0u, nullptr));
     }
+    // The triangles of the model that cross n triangles of the caller's (sr_overlap_triangles; tris [n][3][3]): count[i] = the triangles that
+    // the pair predicate of softray.h reports (not capped by max_hits), rows i of index / mask ([n][max_hits]) the first min(count, max_hits)
+    // of them by ascending TriangleIndex with the masks of their pairs (bit e: the query's edge e meets the scene triangle; bit 3 + e: the
+    // scene triangle's edge e meets the query), the rest of a row -1 / 0.  Any output may be nullptr; max_hits 0 .. SR_HITS_MAX.  any_hit:
+    // SR_OVERLAP_ANY (count is 0 or 1; max_hits must be 0).  The model alone; needs the own BVH or brute force (the library refuses the
+    // reference tree).  coherent: SR_POINTS_COHERENT.  Does nothing without a model
+    void OverlapTriangles(int64_t n, const double* tris, int32_t max_hits, uint32_t* count, int32_t* index, uint8_t* mask, bool coherent = false,
+                          bool any_hit = false) {
+        if (!rayTrace) throw std::logic_error("the scan-line rasteriser is out of scope of the MI355X hot path");
+        if (!PinModel()) return;
+        PreCalculate();                                    // the model and the tree of Mode() are in the scene
+        sr_check(sr_overlap_triangles(scene_, Mode(), n, tris, max_hits, count, index, mask, (coherent ? SR_POINTS_COHERENT : 0u) | (any_hit ? SR_OVERLAP_ANY : 0u),
+                                      nullptr));
+    }
     // Renderer.cs:465-504
     int64_t NumRaysFired() const { return (int64_t)stats_[0]; }
     int64_t NumGeometryTests() const { return Counter(1, "NumGeometryTests"); }

@@ -725,6 +725,36 @@ class GpuScene:
         _check(_lib.lib().sr_near_triangles_device(self._h, int(target), int(n), _vp(d_points), _vp(d_max_dist), int(max_hits), _vp(d_count), _vp(d_index),
                                                    _vp(d_dist), _vp(d_pos), _vp(d_uv), _lib.POINTS_COHERENT if coherent else 0, _stream(stream), _vp(d_stats_ptr)))
 
+    # ---- the triangles of the model that cross a triangle of the caller's (sr_overlap_triangles) ----
+    def overlap_triangles(self, target, tris, max_hits=8, want=("count", "index", "mask"), coherent=False, any_hit=False, stats=False):
+        """For every triangle of `tris` ([n][3][3]) the triangles of the model that cross it (the pair predicate of include/softray.h): a dict
+        with `count` (uint32 [n], not capped by max_hits) and rows by ascending TriangleIndex: `index` (int32 [n][max_hits], -1 in unused
+        slots) and `mask` (uint8 [n][max_hits]: bit e, the query's edge e meets the scene triangle; bit 3 + e, the scene triangle's edge e
+        meets the query; 0 in unused slots).  `want` names the outputs asked for (the others are None); with stats=True also the four
+        counters, `stats`.  max_hits=0 is the counting call; any_hit=True (SR_OVERLAP_ANY, max_hits must be 0): count is 0 or 1 and a query
+        stops at its first triangle.  target: MODE_BVH or MODE_BRUTE."""
+        tris = np.ascontiguousarray(tris, dtype=np.float64).reshape(-1, 3, 3)
+        n = tris.shape[0]
+        k = int(max_hits)
+        rows = max(0, min(k, _lib.HITS_MAX))
+        res = {"count": np.zeros(n, dtype=np.uint32) if "count" in want else None,
+               "index": np.full((n, rows), -1, dtype=np.int32) if "index" in want else None,
+               "mask": np.zeros((n, rows), dtype=np.uint8) if "mask" in want else None}
+        row = lambda name: _p(res[name]) if rows else None                                   # noqa: E731
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        options = (_lib.POINTS_COHERENT if coherent else 0) | (_lib.OVERLAP_ANY if any_hit else 0)
+        _check(_lib.lib().sr_overlap_triangles(self._h, int(target), n, _p(tris), k, _p(res["count"]), row("index"), row("mask"), options, _p(st)))
+        if stats:
+            res["stats"] = st
+        return res
+
+    def overlap_triangles_device(self, target, n, d_tris, max_hits=8, d_count=0, d_index=0, d_mask=0, coherent=False, any_hit=False, stream=0, d_stats_ptr=None):
+        """sr_overlap_triangles_device: every array is a DEVICE pointer (an output 0 / None: not wanted); enqueued on `stream` (a raw
+        hipStream_t or a torch.cuda.Stream), no host sync."""
+        options = (_lib.POINTS_COHERENT if coherent else 0) | (_lib.OVERLAP_ANY if any_hit else 0)
+        _check(_lib.lib().sr_overlap_triangles_device(self._h, int(target), int(n), _vp(d_tris), int(max_hits), _vp(d_count), _vp(d_index), _vp(d_mask), options,
+                                                      _stream(stream), _vp(d_stats_ptr)))
+
     # ---- the colour light field for caller-given rays (sr_light_field_rays) ----
     def light_field_rays(self, frame, starts, dirs, want_inside=True):
         """LightFieldColorMethod.IntersectRay for n lines of the caller's (sr_light_field_rays): (out uint32 [n], inside uint8 [n] or None,

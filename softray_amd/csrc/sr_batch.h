@@ -137,18 +137,6 @@ inline BatchRays batch_rays(const double* starts, const double* dirs, const doub
 // L.sort_buf of an ordered pass: the sort's keys, the sorted keys, the indices, the order, and the work head of a persistent walk
 struct PassBuffers { unsigned int *keys, *keys2, *idx, *order, *head; };
 
-// `enqueue()` between the two timing events of kernel_id, where the caller wants them
-template <class Enqueue>
-hipError_t timed(const BatchLaunch& L, int kernel_id, Enqueue enqueue) {
-    hipError_t e;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (L.get_events) L.get_events(L.user, kernel_id, &e0, &e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    if ((e = enqueue()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    return hipSuccess;
-}
-
 // The passes of a call, back to back on the stream.  ordered: order_pass(first, count, buffers) orders a pass first (timed as sort_id) and
 // the slice carries that order; otherwise a pass runs in input order with take 2.  walk_pass(slice, buffers) launches the pass (walk_id)
 template <class Order, class Walk>

@@ -617,6 +617,19 @@ hipError_t launch_voxel_frame(const VoxelLaunch& L);
 hipError_t launch_voxel_trace(const TraceLaunch& L, const RootBox& box, const VoxelGridDev& grid, int max_blocks, bool flat_mask);
 hipError_t launch_shade_points(const FrameConst& fc, long long n, const double* pos, const double* nrm, const uint32_t* color, uint32_t* out, hipStream_t stream);
 
+// `enqueue()` between the two timing events of kernel_id, where the caller wants them: for every launch struct above (get_events, user,
+// stream).  The stop event is recorded on every exit from the body -- a pair that was opened stays a pair -- and the body's error wins
+template <class Launch, class Enqueue>
+hipError_t timed(const Launch& L, int kernel_id, Enqueue enqueue) {
+    hipError_t e;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (L.get_events) L.get_events(L.user, kernel_id, &e0, &e1);
+    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
+    e = enqueue();
+    const hipError_t stop = e1 ? hipEventRecord(e1, L.stream) : hipSuccess;
+    return e != hipSuccess ? e : stop;
+}
+
 // --------------------------------------------------------------------------------------------------
 // Wave votes of the packet walks.  THE RULE: a vote is a test of an INTEGER, and __ballot only ever sees ONE comparison.
 // A lane predicate that is only voted on or used to gate per-lane work lives as a 64-bit mask in a scalar register pair:

@@ -5690,6 +5690,38 @@ hipError_t launch_cam_cones(const DevScene& sc, int ntris, const double origin[3
 // --------------------------------------------------------------------------------------------------
 // launchers
 // --------------------------------------------------------------------------------------------------
+// What every launcher below is made of:
+//   launch(kern, grid, block, lds, stream, args...)   enqueue one kernel, return hipGetLastError()
+//   timed(L, K_X, body)                               (sr_device.h) body() between the timing events of K_X, where the caller wants them
+//   with_flag(b, f), with_index<N>(i, f)              f(std::true_type / std::false_type), f(std::integral_constant<int, i>): a run-time value
+//                                                     as a template argument -- a kernel template is named at ONE launch site per argument list
+//   for_mode(mode, extra, f)                          f(MODE, EXTRA) as integral constants; any other mode is hipErrorInvalidValue
+template <class Kernel, class... Args>
+static hipError_t launch(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
+template <class F>
+static hipError_t with_flag(bool on, F f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+
+// (an index outside 0 .. N - 1 counts as 0)
+template <int N, class F>
+static hipError_t with_index(int i, F f) {
+    if constexpr (N <= 1) return f(std::integral_constant<int, 0>{});
+    else return i == N - 1 ? f(std::integral_constant<int, N - 1>{}) : with_index<N - 1>(i, f);
+}
+
+template <class F>
+static hipError_t for_mode(int mode, bool extra, F f) {
+    switch (mode) {
+        case MODE_REF: return with_flag(extra, [&](auto x) { return f(std::integral_constant<int, MODE_REF>{}, x); });
+        case MODE_BRUTE: return with_flag(extra, [&](auto x) { return f(std::integral_constant<int, MODE_BRUTE>{}, x); });
+        case MODE_BVH: return with_flag(extra, [&](auto x) { return f(std::integral_constant<int, MODE_BVH>{}, x); });
+        default: return hipErrorInvalidValue;
+    }
+}
+
 static int pipe_stack_levels(const DevScene& sc, int mode) {
     if (mode == MODE_REF) return sc.rdepth + 2;
     if (mode == MODE_BVH) return sc.bdepth + 2;
@@ -5705,24 +5737,6 @@ static unsigned tile_grid(const PipelineLaunch& L, unsigned virtual_blocks, int 
     const bool persistent = virtual_blocks > resident && L.fc.debug != 81 && (virtual_blocks & 7u) == 0u;
     *heads_out = persistent ? heads : nullptr;
     return persistent ? resident : virtual_blocks;
-}
-
-template <int MODE, bool EXTRA, bool SUB, int PKT>
-static hipError_t launch_primary_p(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples, int pad_tiles) {
-    // 1-D grid over the padded super-tile grid (see the tile order in k_primary), or the resident grid pulling its tiles (TileFeed)
-    const unsigned vblocks = (unsigned)xcd_tile_grid(L.fc.width, row_count);
-    unsigned int* heads;
-    dim3 grid(tile_grid(L, vblocks, SUB ? 5 : 6, L.counters + kHeadsPrimary, &heads));
-    if (heads && L.fc.debug != 82) { heads = nullptr; grid = dim3(vblocks); }      // (k_primary's persistent form is opt-in: SR_DBG_KERNEL_SWITCH 82)
-    const int levels = PKT >= 2 ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE);
-    size_t lds = PKT ? (size_t)levels * 4 * 4 : (size_t)levels * 256 * 4;
-    const auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, L.stream, L.sc, L.fc, L.row_map, row_begin, row_count,
-                           samples, (HitRec*)L.hits, L.counters, L.bounce_levels, L.bounce_nlev, L.stats, pad_tiles, levels, heads, vblocks);
-    };
-    if (heads) { if (L.stats) go(k_primary<MODE, EXTRA, true, SUB, PKT, true>); else go(k_primary<MODE, EXTRA, false, SUB, PKT, true>); }
-    else { if (L.stats) go(k_primary<MODE, EXTRA, true, SUB, PKT, false>); else go(k_primary<MODE, EXTRA, false, SUB, PKT, false>); }
-    return hipGetLastError();
 }
 
 // the walk of a frame's primary stage (k_primary's and k_hits' PKT): 0 per-lane walks, 1 packets on the binary tree, 2 packets on the
@@ -5741,57 +5755,57 @@ static int primary_walk_kind(const PipelineLaunch& L) {
     return 0;
 }
 
-template <int MODE, bool EXTRA, bool SUB>
-static hipError_t launch_primary_s(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples, int pad_tiles) {
-    if constexpr (MODE == MODE_BVH) {
-        switch (primary_walk_kind<MODE, SUB>(L)) {
-            case 3: return launch_primary_p<MODE, EXTRA, SUB, 3>(L, row_begin, row_count, samples, pad_tiles);
-            case 2: return launch_primary_p<MODE, EXTRA, SUB, 2>(L, row_begin, row_count, samples, pad_tiles);
-            case 1: return launch_primary_p<MODE, EXTRA, SUB, 1>(L, row_begin, row_count, samples, pad_tiles);
-            default: break;
-        }
-    }
-    return launch_primary_p<MODE, EXTRA, SUB, 0>(L, row_begin, row_count, samples, pad_tiles);
+// f(SUB, PKT) for a band of the frame: with sub-samples or without, on the walk primary_walk_kind names (the packet walks exist on the own BVH only)
+template <int MODE, class F>
+static hipError_t for_primary_walk(const PipelineLaunch& L, F f) {
+    return with_flag(L.fc.sub_pixel_res > 1, [&](auto sub) {
+        if constexpr (MODE == MODE_BVH) return with_index<4>(primary_walk_kind<MODE, decltype(sub)::value>(L), [&](auto pkt) { return f(sub, pkt); });
+        else return f(sub, std::integral_constant<int, 0>{});
+    });
 }
 
-// sr_render_hits: k_hits over a row band, one workgroup per 16x16 tile of the xcd_tile grid (the direct form; LDS as k_primary's)
-template <int MODE, bool EXTRA, bool SUB, int PKT>
-static hipError_t launch_hits_p(const PipelineLaunch& L, int row_begin, int row_count) {
-    const dim3 grid((unsigned)xcd_tile_grid(L.fc.width, row_count));
-    const int levels = PKT >= 2 ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE);
-    const size_t lds = PKT ? (size_t)levels * 4 * 4 : (size_t)levels * 256 * 4;
-    const auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, L.stream, L.sc, L.fc, L.row_map, row_begin, row_count, L.hits_out, L.stats, levels);
-    };
-    if (L.stats) go(k_hits<MODE, EXTRA, true, SUB, PKT>); else go(k_hits<MODE, EXTRA, false, SUB, PKT>);
-    return hipGetLastError();
+// per-lane stacks (256 lanes) or one stack per wave of a packet walk (LDS of k_primary, k_hits and k_origin_rays)
+template <int MODE, int PKT>
+static int primary_levels(const DevScene& sc) { return PKT >= 2 ? 3 * sc.b4depth + 2 : pipe_stack_levels(sc, MODE); }
+template <int PKT>
+static size_t primary_lds(int levels) { return PKT ? (size_t)levels * 4 * 4 : (size_t)levels * 256 * 4; }
+
+template <int MODE, bool EXTRA>
+static hipError_t launch_primary(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples, int pad_tiles) {
+    return for_primary_walk<MODE>(L, [&](auto sub, auto pkt) {
+        constexpr bool SUB = decltype(sub)::value;
+        constexpr int PKT = decltype(pkt)::value;
+        // 1-D grid over the padded super-tile grid (see the tile order in k_primary), or the resident grid pulling its tiles (TileFeed)
+        const unsigned vblocks = (unsigned)xcd_tile_grid(L.fc.width, row_count);
+        unsigned int* heads;
+        dim3 grid(tile_grid(L, vblocks, SUB ? 5 : 6, L.counters + kHeadsPrimary, &heads));
+        if (heads && L.fc.debug != 82) { heads = nullptr; grid = dim3(vblocks); }      // (k_primary's persistent form is opt-in: SR_DBG_KERNEL_SWITCH 82)
+        const int levels = primary_levels<MODE, PKT>(L.sc);
+        return with_flag(heads != nullptr, [&](auto persist) { return with_flag(L.stats != nullptr, [&](auto stats) {
+            return launch(k_primary<MODE, EXTRA, decltype(stats)::value, SUB, PKT, decltype(persist)::value>, grid, dim3(256), primary_lds<PKT>(levels), L.stream, L.sc, L.fc,
+                          L.row_map, row_begin, row_count, samples, (HitRec*)L.hits, L.counters, L.bounce_levels, L.bounce_nlev, L.stats, pad_tiles, levels, heads, vblocks);
+        }); });
+    });
 }
 
-template <int MODE, bool EXTRA, bool SUB>
-static hipError_t launch_hits_s(const PipelineLaunch& L, int row_begin, int row_count) {
-    if constexpr (MODE == MODE_BVH) {
-        switch (primary_walk_kind<MODE, SUB>(L)) {
-            case 3: return launch_hits_p<MODE, EXTRA, SUB, 3>(L, row_begin, row_count);
-            case 2: return launch_hits_p<MODE, EXTRA, SUB, 2>(L, row_begin, row_count);
-            case 1: return launch_hits_p<MODE, EXTRA, SUB, 1>(L, row_begin, row_count);
-            default: break;
-        }
-    }
-    return launch_hits_p<MODE, EXTRA, SUB, 0>(L, row_begin, row_count);
-}
-
-// ... band by band, cut exactly as a frame's rows are
+// sr_render_hits: k_hits over the rows band by band, cut exactly as a frame's rows are; one workgroup per 16x16 tile of the xcd_tile grid
+// (the direct form; LDS as k_primary's)
 template <int MODE, bool EXTRA>
 static hipError_t launch_hits_t(const PipelineLaunch& L) {
     for (int row_begin = L.row_first; row_begin < L.row_limit; row_begin += L.band_rows) {
         const int row_count = std::min(L.band_rows, L.row_limit - row_begin);
-        hipError_t e;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_HITS, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        e = L.fc.sub_pixel_res > 1 ? launch_hits_s<MODE, EXTRA, true>(L, row_begin, row_count) : launch_hits_s<MODE, EXTRA, false>(L, row_begin, row_count);
+        const hipError_t e = timed(L, K_HITS, [&] {
+            return for_primary_walk<MODE>(L, [&](auto sub, auto pkt) {
+                constexpr int PKT = decltype(pkt)::value;
+                const dim3 grid((unsigned)xcd_tile_grid(L.fc.width, row_count));
+                const int levels = primary_levels<MODE, PKT>(L.sc);
+                return with_flag(L.stats != nullptr, [&](auto stats) {
+                    return launch(k_hits<MODE, EXTRA, decltype(stats)::value, decltype(sub)::value, PKT>, grid, dim3(256), primary_lds<PKT>(levels), L.stream, L.sc, L.fc, L.row_map,
+                                  row_begin, row_count, L.hits_out, L.stats, levels);
+                });
+            });
+        });
         if (e != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -5801,14 +5815,11 @@ template <int MODE, bool EXTRA, int PKT>
 static hipError_t launch_origin_p(const PipelineLaunch& L, long long first, unsigned int count, const unsigned int* order, const unsigned int* keys,
                                   unsigned int skip_mask, int take_skipped) {
     const dim3 grid((count + 255u) / 256u);
-    const int levels = PKT >= 2 ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE);
-    const size_t lds = PKT ? (size_t)levels * 4 * 4 : (size_t)levels * 256 * 4;
-    const auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, L.stream, L.sc, L.fc.start_world[0], L.fc.start_world[1], L.fc.start_world[2], L.org_dirs, first, count,
-                           order, keys, skip_mask, take_skipped, L.hits_out, L.stats, levels);
-    };
-    if (L.stats) go(k_origin_rays<MODE, EXTRA, true, PKT>); else go(k_origin_rays<MODE, EXTRA, false, PKT>);
-    return hipGetLastError();
+    const int levels = primary_levels<MODE, PKT>(L.sc);
+    return with_flag(L.stats != nullptr, [&](auto stats) {
+        return launch(k_origin_rays<MODE, EXTRA, decltype(stats)::value, PKT>, grid, dim3(256), primary_lds<PKT>(levels), L.stream, L.sc, L.fc.start_world[0], L.fc.start_world[1],
+                      L.fc.start_world[2], L.org_dirs, first, count, order, keys, skip_mask, take_skipped, L.hits_out, L.stats, levels);
+    });
 }
 
 // ... pass by pass, back to back on the stream.  The walk is the one a frame's primary stage takes for this scene state (primary_walk_kind);
@@ -5826,28 +5837,21 @@ static hipError_t launch_origin_t(const PipelineLaunch& L) {
     for (int64_t first = 0; first < L.org_n; first += L.org_pass) {
         const unsigned int count = (unsigned int)std::min<int64_t>(L.org_pass, L.org_n - first);
         hipError_t e;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (kind != 0) {
-            if (L.get_events) L.get_events(L.user, K_ORIGIN_SORT, &e0, &e1);
-            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-            if ((e = dir_order(L.org_dirs + 3 * first, count, !L.org_coherent, keys, keys2, idx, order, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
-            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        }
-        e0 = e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_ORIGIN_RAYS, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        if constexpr (MODE == MODE_BVH) {
-            switch (kind) {
-                case 3: e = launch_origin_p<MODE, EXTRA, 3>(L, first, count, order, keys2, skip, 0); break;
-                case 2: e = launch_origin_p<MODE, EXTRA, 2>(L, first, count, order, keys2, skip, 0); break;
-                case 1: e = launch_origin_p<MODE, EXTRA, 1>(L, first, count, order, keys2, skip, 0); break;
-                default: e = hipSuccess; break;
+        if (kind != 0 && (e = timed(L, K_ORIGIN_SORT, [&] {
+                return dir_order(L.org_dirs + 3 * first, count, !L.org_coherent, keys, keys2, idx, order, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream);
+            })) != hipSuccess) return e;
+        e = timed(L, K_ORIGIN_RAYS, [&] {
+            if (kind == 0) return launch_origin_p<MODE, EXTRA, 0>(L, first, count, nullptr, nullptr, 0u, 0);
+            hipError_t e = hipSuccess;
+            if constexpr (MODE == MODE_BVH) {
+                e = with_index<4>(kind, [&](auto pkt) {
+                    if constexpr (decltype(pkt)::value != 0) return launch_origin_p<MODE, EXTRA, decltype(pkt)::value>(L, first, count, order, keys2, skip, 0);
+                    else return hipSuccess;
+                });
             }
-            if (e != hipSuccess) return e;
-        }
-        e = kind != 0 ? launch_origin_p<MODE, EXTRA, 0>(L, first, count, order, keys2, skip, 1) : launch_origin_p<MODE, EXTRA, 0>(L, first, count, nullptr, nullptr, 0u, 0);
+            return e != hipSuccess ? e : launch_origin_p<MODE, EXTRA, 0>(L, first, count, order, keys2, skip, 1);
+        });
         if (e != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -5860,18 +5864,10 @@ static hipError_t launch_shadow_lanes_t(const PipelineLaunch& L, uint32_t* sampl
     long long want = (max_hits + 255) / 256;
     unsigned blocks = (unsigned)std::min<long long>(want, (long long)L.persistent_blocks);
     if (blocks == 0) return hipSuccess;
-    if (L.stats)
-        hipLaunchKernelGGL((k_shadow<MODE, EXTRA, true>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits,
-                           count, head, index_list, samples, levels, L.stats);
-    else
-        hipLaunchKernelGGL((k_shadow<MODE, EXTRA, false>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits,
-                           count, head, index_list, samples, levels, L.stats);
-    return hipGetLastError();
-}
-
-static void pipe_events(const PipelineLaunch& L, int kid, hipEvent_t& e0, hipEvent_t& e1) {
-    e0 = e1 = nullptr;
-    if (L.get_events) L.get_events(L.user, kid, &e0, &e1);
+    return with_flag(L.stats != nullptr, [&](auto stats) {
+        return launch(k_shadow<MODE, EXTRA, decltype(stats)::value>, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, count, head, index_list,
+                      samples, levels, L.stats);
+    });
 }
 
 template <int MODE>
@@ -5883,19 +5879,12 @@ static bool shaft_path(const PipelineLaunch& L) {
 template <int MODE, bool EXTRA>
 static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, long long max_hits) {
     hipError_t e;
-    hipEvent_t e0, e1;
-    const bool shaft = shaft_path<MODE>(L);
-    if (!shaft) {
-        pipe_events(L, K_SHADOW, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        e = launch_shadow_lanes_t<MODE, EXTRA>(L, samples, max_hits, L.counters, L.counters + 1, nullptr);
-        if (e != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        return hipSuccess;
-    }
+    if (!shaft_path<MODE>(L))
+        return timed(L, K_SHADOW, [&] { return launch_shadow_lanes_t<MODE, EXTRA>(L, samples, max_hits, L.counters, L.counters + 1, nullptr); });
     // counters: [0] hits  [1] k_shadow head  [2..] items entering round 1, 2, ..  [2+R-1] fallback count  [6] round-0 work items
     unsigned int* fb_count = L.counters + 2 + (kShaftRounds - 1);
     unsigned int* work0 = L.counters + 6;
+    const HitRec* hits = (const HitRec*)L.hits;
     unsigned int order_items = 0;                 // > 0: the persistent shaft walk left its tiles' walk lengths behind (see below)
     unsigned long long order_new_tag = 0;
     for (int round = 0; round < kShaftRounds; ++round) {
@@ -5907,9 +5896,7 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
         if (max_items <= 0) break;
         const int cap = L.round_cap[round];
         // ---- k_shaft ----
-        pipe_events(L, first ? K_SHAFT : K_SHAFT2, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        {
+        e = timed(L, first ? K_SHAFT : K_SHAFT2, [&] {
             const int levels = pipe_stack_levels(L.sc, MODE_BVH);
             unsigned blocks = (unsigned)((max_items + 255) / 256);
             if (first && !(L.per_lane_shaft & 1) && L.sc.b4light && !L.bvh2_packets) {
@@ -5936,44 +5923,41 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
                 const unsigned int* hint_prev = (hints && *L.tile_order_tag == order_tag) ? L.tile_hint[(*L.tile_hint_cur & 1) ^ 1] : nullptr;
                 const HintArgs hint_args{hint_prev, hint_cur, (unsigned)L.sc.ntris, 0u};
                 const auto go = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, hint_args, (const HitRec*)L.hits, count_ptr, cap, lv4, tn2, trows, L.round_cand_count[round], L.round_cand[round], samples, work0, L.round_list[0], L.stats, heads, vblocks, order, cost);
+                    return launch(kern, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, hint_args, hits, count_ptr, cap, lv4, tn2, trows, L.round_cand_count[round], L.round_cand[round],
+                                  samples, work0, L.round_list[0], L.stats, heads, vblocks, order, cost);
                 };
                 // 6 waves/SIMD (85 VGPRs): 5.16 ms on the headline frame; 7 waves (72 VGPRs, spills in the node step) 5.44; 5 waves 5.61
                 // ((near, far) planes in the light-ordered copy, as in the camera-ordered one, were measured: fewer instructions, more spills at
                 //  this kernel's register budget -- 5.17 -> 5.30 ms; 5.49 ms at 5 waves/SIMD)
-                // one instantiation per set of axes on which the light-ordered copy holds (near, far) planes (the light lies outside the root box there)
-                // the loop with fewer scalar instructions per step (LEAN) unless the launch is counted or SR_DBG_KERNEL_SWITCH 63 / hook 630 + n asks for the
-                // loop as it was (the A/B)
+                // KNOWN: one instantiation per set of axes on which the light-ordered copy holds (near, far) planes (the light lies outside the root box there)
+                // CONES: the frame's penumbra-plane records are there: filter with them
+                // LEAN: the loop with fewer scalar instructions per step -- only when the launch is not counted, and not when SR_DBG_KERNEL_SWITCH 63 /
+                // hook 630 + n asks for the loop as it was (the A/B)
                 const bool lean = !L.stats && L.fc.debug != 63 && !hook63x;
-                const auto go_known = [&](auto known) {
-                    constexpr int K = decltype(known)::value;
-                    if (L.sc.blight) {                         // the frame's penumbra-plane records are there: filter with them
-                        if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K, true>); else if (lean) go(k_shaft_pkt4<false, 6, true, K, true, true>); else go(k_shaft_pkt4<false, 6, true, K, true>); }
-                        else { if (L.stats) go(k_shaft_pkt4<true, 6, false, K, true>); else if (lean) go(k_shaft_pkt4<false, 6, false, K, true, true>); else go(k_shaft_pkt4<false, 6, false, K, true>); }
-                    } else if (heads) { if (L.stats) go(k_shaft_pkt4<true, 6, true, K>); else if (lean) go(k_shaft_pkt4<false, 6, true, K, false, true>); else go(k_shaft_pkt4<false, 6, true, K>); }
-                    else { if (L.stats) go(k_shaft_pkt4<true, 6, false, K>); else if (lean) go(k_shaft_pkt4<false, 6, false, K, false, true>); else go(k_shaft_pkt4<false, 6, false, K>); }
-                };
-                switch (L.sc.b4light_known & 7) {
-                    case 1: go_known(std::integral_constant<int, 1>()); break;
-                    case 2: go_known(std::integral_constant<int, 2>()); break;
-                    case 3: go_known(std::integral_constant<int, 3>()); break;
-                    case 4: go_known(std::integral_constant<int, 4>()); break;
-                    case 5: go_known(std::integral_constant<int, 5>()); break;
-                    case 6: go_known(std::integral_constant<int, 6>()); break;
-                    case 7: go_known(std::integral_constant<int, 7>()); break;
-                    default: go_known(std::integral_constant<int, 0>()); break;
-                }
+                const hipError_t e = with_index<8>(L.sc.b4light_known & 7, [&](auto known) { return with_flag(L.sc.blight != nullptr, [&](auto cones) {
+                    return with_flag(heads != nullptr, [&](auto persist) { return with_flag(L.stats != nullptr, [&](auto stats) {
+                        constexpr int KNOWN = decltype(known)::value;
+                        constexpr bool CONES = decltype(cones)::value, PERSIST = decltype(persist)::value;
+                        if constexpr (decltype(stats)::value) return go(k_shaft_pkt4<true, 6, PERSIST, KNOWN, CONES, false>);
+                        else return with_flag(lean, [&](auto l) { return go(k_shaft_pkt4<false, 6, PERSIST, KNOWN, CONES, decltype(l)::value>); });
+                    }); });
+                }); });
                 if (keep_cost) { order_items = (vblocks >> 3) * 4u; order_new_tag = order_tag; }
                 if (hints) *L.tile_hint_cur ^= 1;                      // (what this launch wrote is the next one's `prev`)
                 if (heads && L.shaft_launches) { L.shaft_launches[0] += 1; if (order) L.shaft_launches[1] += 1; }
-            } else if (first && !(L.per_lane_shaft & 1)) {
+                return e;
+            }
+            if (first && !(L.per_lane_shaft & 1)) {
                 // round 1 on the binary tree (cross-check): one packet walk per 64 consecutive queue entries (one 8x8-pixel tile when the queue is tile-aligned)
                 size_t lds = ((size_t)levels * 4 + (size_t)levels * 64 * 2) * 4;
                 const int tn2 = L.tile_queue_n2, trows = L.tile_queue_rows;
                 if (tn2 > 0) blocks = (unsigned)(xcd_tile_grid(L.fc.width, trows) * tn2);      // the grid of k_primary (x sub-samples)
-                if (L.stats) hipLaunchKernelGGL((k_shaft_pkt<true>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)L.hits, count_ptr, cap, levels, tn2, trows, L.round_cand_count[round], L.round_cand[round], samples, work0, L.round_list[0], L.stats);
-                else hipLaunchKernelGGL((k_shaft_pkt<false>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)L.hits, count_ptr, cap, levels, tn2, trows, L.round_cand_count[round], L.round_cand[round], samples, work0, L.round_list[0], L.stats);
-            } else if (!first && !(L.per_lane_shaft & 2)) {
+                return with_flag(L.stats != nullptr, [&](auto stats) {
+                    return launch(k_shaft_pkt<decltype(stats)::value>, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, hits, count_ptr, cap, levels, tn2, trows, L.round_cand_count[round],
+                                  L.round_cand[round], samples, work0, L.round_list[0], L.stats);
+                });
+            }
+            if (!first && !(L.per_lane_shaft & 2)) {
                 // later rounds (scattered hit points): one wave per hit point, see k_shaft_coop.  They collect from scratch (skip = 0):
                 // the order in which round 1 met a hit point's candidates was its wave's, so "skip the first cap" would not name
                 // the same triangles; re-testing a candidate is harmless (it did not block the samples that are still undecided)
@@ -5981,24 +5965,23 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
                 // 32 KB of LDS per workgroup = 5 resident per CU; a grid of ~6 times that many lets the dispatcher balance the walks
                 // (headline frame: 1280 workgroups 0.90 ms, 2048 0.78, 8192 0.73)
                 const unsigned cblocks = (unsigned)std::min<long long>((max_items + 3) / 4, (long long)L.persistent_blocks * 4);
-                if (L.stats) hipLaunchKernelGGL((k_shaft_coop<true>), dim3(cblocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)L.hits, count_ptr, count_cap, ilist, cap, L.round_cand_count[round], L.round_cand[round], L.stats);
-                else hipLaunchKernelGGL((k_shaft_coop<false>), dim3(cblocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)L.hits, count_ptr, count_cap, ilist, cap, L.round_cand_count[round], L.round_cand[round], L.stats);
-            } else {
-                // private per-lane walks: the first round as a cross-check of the packet walk, the later rounds as one of k_shaft_coop
-                size_t lds = (size_t)levels * 256 * 4;
-                unsigned int* wc = first ? work0 : nullptr;
-                unsigned int* wl = first ? L.round_list[0] : nullptr;
-                if (L.stats) hipLaunchKernelGGL((k_shaft<true>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)L.hits, count_ptr, count_cap, ilist, first ? 0 : L.round2_node_budget, cap, L.round_cand_count[round], L.round_cand[round], samples, wc, wl, L.stats, L.counters);
-                else hipLaunchKernelGGL((k_shaft<false>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)L.hits, count_ptr, count_cap, ilist, first ? 0 : L.round2_node_budget, cap, L.round_cand_count[round], L.round_cand[round], samples, wc, wl, L.stats, L.counters);
+                return with_flag(L.stats != nullptr, [&](auto stats) {
+                    return launch(k_shaft_coop<decltype(stats)::value>, dim3(cblocks), dim3(256), lds, L.stream, L.sc, L.fc, hits, count_ptr, count_cap, ilist, cap,
+                                  L.round_cand_count[round], L.round_cand[round], L.stats);
+                });
             }
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+            // private per-lane walks: the first round as a cross-check of the packet walk, the later rounds as one of k_shaft_coop
+            size_t lds = (size_t)levels * 256 * 4;
+            unsigned int* wc = first ? work0 : nullptr;
+            unsigned int* wl = first ? L.round_list[0] : nullptr;
+            return with_flag(L.stats != nullptr, [&](auto stats) {
+                return launch(k_shaft<decltype(stats)::value>, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, hits, count_ptr, count_cap, ilist, first ? 0 : L.round2_node_budget, cap,
+                              L.round_cand_count[round], L.round_cand[round], samples, wc, wl, L.stats, L.counters);
+            });
+        });
+        if (e != hipSuccess) return e;
         // ---- k_shadow_test ----
-        pipe_events(L, first ? K_SHADOW : K_SHADOW2, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        {
-            size_t lds = 4 * ((size_t)kRecordsPerPass * kRecStride16 * 16 + (size_t)kTailSlots * kRayStride8 * 8);
+        e = timed(L, first ? K_SHADOW : K_SHADOW2, [&] {
             long long want = (max_items + 3) / 4;
             unsigned blocks = (unsigned)std::min<long long>(want, (long long)L.persistent_blocks * 2);
             const RoundState* st_in = first ? nullptr : (const RoundState*)L.round_state[round];
@@ -6009,58 +5992,60 @@ static hipError_t launch_shadow_t(const PipelineLaunch& L, uint32_t* samples, lo
             // round 0 iterates the compacted list of hits that k_shaft could not decide by itself
             const unsigned int* t_count = first ? work0 : count_ptr;
             const unsigned int* t_list = first ? L.round_list[0] : ilist;
-            if (!L.exact_shadow_tests) {
-                // default: fp32 classification, FP64 only for the pairs it cannot decide
-                const size_t lds_c = 4 * (size_t)kClsWaveF4 * sizeof(float4) + 128 * 3 * sizeof(float) + (64 * kPacketSlots + 1) * sizeof(uint32_t);
-                const auto args = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds_c, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, t_count, count_cap, t_list, st_in, cap, first ? 1 : 0, L.round_cand_count[round], L.round_cand[round], next_count, next_cap, next_list, st_out, fb_count, L.fallback, (RoundState*)L.fallback_state, samples, L.stats);
-                };
-                if (first && L.fc.debug != 91 && cap <= kGrpRecs) {
-                    // first round: the per-hit-point preparation done for groups of hit points (k_shadow_cls_g)
-                    const size_t lds_g = 4 * (size_t)kGrpWaveF4 * sizeof(float4) + (64 * kPacketSlots + 1) * sizeof(uint32_t);
-                    const auto args_g = [&](auto kern) {
-                        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds_g, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, t_count, count_cap, t_list, cap, L.round_cand_count[round], L.round_cand[round], next_count, next_cap, next_list, st_out, fb_count, L.fallback, (RoundState*)L.fallback_state, samples, L.stats);
-                    };
-                    if (L.stats) args_g(k_shadow_cls_g<EXTRA, true>); else args_g(k_shadow_cls_g<EXTRA, false>);
-                } else if (first) { if (L.stats) args(k_shadow_cls<EXTRA, true, false>); else args(k_shadow_cls<EXTRA, false, false>); }
-                else { if (L.stats) args(k_shadow_cls<EXTRA, true, true>); else args(k_shadow_cls<EXTRA, false, true>); }
-            } else if (L.stats) hipLaunchKernelGGL((k_shadow_test<EXTRA, true>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, t_count, count_cap, t_list, st_in, cap, first ? 1 : 0, L.round_cand_count[round], L.round_cand[round], next_count, next_cap, next_list, st_out, fb_count, L.fallback, (RoundState*)L.fallback_state, samples, L.stats);
-            else hipLaunchKernelGGL((k_shadow_test<EXTRA, false>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, t_count, count_cap, t_list, st_in, cap, first ? 1 : 0, L.round_cand_count[round], L.round_cand[round], next_count, next_cap, next_list, st_out, fb_count, L.fallback, (RoundState*)L.fallback_state, samples, L.stats);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+            const auto round_kernel = [&](auto kern, size_t lds) {      // k_shadow_test's and k_shadow_cls' arguments
+                return launch(kern, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, hits, t_count, count_cap, t_list, st_in, cap, first ? 1 : 0, L.round_cand_count[round],
+                              L.round_cand[round], next_count, next_cap, next_list, st_out, fb_count, L.fallback, (RoundState*)L.fallback_state, samples, L.stats);
+            };
+            if (L.exact_shadow_tests) {
+                const size_t lds = 4 * ((size_t)kRecordsPerPass * kRecStride16 * 16 + (size_t)kTailSlots * kRayStride8 * 8);
+                return with_flag(L.stats != nullptr, [&](auto stats) { return round_kernel(k_shadow_test<EXTRA, decltype(stats)::value>, lds); });
+            }
+            // default: fp32 classification, FP64 only for the pairs it cannot decide
+            if (first && L.fc.debug != 91 && cap <= kGrpRecs) {
+                // first round: the per-hit-point preparation done for groups of hit points (k_shadow_cls_g)
+                const size_t lds_g = 4 * (size_t)kGrpWaveF4 * sizeof(float4) + (64 * kPacketSlots + 1) * sizeof(uint32_t);
+                return with_flag(L.stats != nullptr, [&](auto stats) {
+                    return launch(k_shadow_cls_g<EXTRA, decltype(stats)::value>, dim3(blocks), dim3(256), lds_g, L.stream, L.sc, L.fc, L.offsets, hits, t_count, count_cap, t_list, cap,
+                                  L.round_cand_count[round], L.round_cand[round], next_count, next_cap, next_list, st_out, fb_count, L.fallback, (RoundState*)L.fallback_state, samples, L.stats);
+                });
+            }
+            const size_t lds_c = 4 * (size_t)kClsWaveF4 * sizeof(float4) + 128 * 3 * sizeof(float) + (64 * kPacketSlots + 1) * sizeof(uint32_t);
+            return with_flag(!first, [&](auto later) { return with_flag(L.stats != nullptr, [&](auto stats) {
+                return round_kernel(k_shadow_cls<EXTRA, decltype(stats)::value, decltype(later)::value>, lds_c);
+            }); });
+        });
+        if (e != hipSuccess) return e;
     }
     // ---- fallback: hits that are still undecided after the longest list ----
-    pipe_events(L, K_FALLBACK, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    {
+    e = timed(L, K_FALLBACK, [&] {
+        hipError_t e;
         // counters: [10] rays in the fallback ray list  [11] entries the list had no room for  [12] k_shadow_rays' work head
         unsigned int* ray_count = L.counters + 10;
         unsigned int* ovf_count = L.counters + 11;
         RoundState* fst = (RoundState*)L.fallback_state;
         size_t lds = (size_t)pipe_stack_levels(L.sc, MODE_BVH) * 256 * 4;
         unsigned small = (unsigned)std::min<long long>((max_hits + 255) / 256, (long long)L.persistent_blocks);
-        hipLaunchKernelGGL(k_fb_expand, dim3(small), dim3(256), 0, L.stream, fb_count, L.fallback, (const RoundState*)fst, L.fallback_rays,
-                           L.fallback_ray_cap, ray_count, L.fallback_overflow, ovf_count);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch(k_fb_expand, dim3(small), dim3(256), 0, L.stream, fb_count, L.fallback, (const RoundState*)fst, L.fallback_rays, L.fallback_ray_cap, ray_count,
+                        L.fallback_overflow, ovf_count)) != hipSuccess) return e;
         unsigned blocks = (unsigned)std::min<long long>(((long long)L.fallback_ray_cap + 255) / 256, (long long)L.persistent_blocks);
-        if (L.stats) hipLaunchKernelGGL((k_shadow_rays<EXTRA, true>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, L.fallback, fst, L.fallback_rays, L.fallback_ray_cap, ray_count, L.counters + 12, L.stats);
-        else hipLaunchKernelGGL((k_shadow_rays<EXTRA, false>), dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, L.fallback, fst, L.fallback_rays, L.fallback_ray_cap, ray_count, L.counters + 12, L.stats);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_fb_resolve, dim3(small), dim3(256), 0, L.stream, L.sc, L.fc, (const HitRec*)L.hits, fb_count, L.fallback, (const RoundState*)fst, samples);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = with_flag(L.stats != nullptr, [&](auto stats) {
+                return launch(k_shadow_rays<EXTRA, decltype(stats)::value>, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, hits, L.fallback, fst, L.fallback_rays,
+                              L.fallback_ray_cap, ray_count, L.counters + 12, L.stats);
+            })) != hipSuccess) return e;
+        if ((e = launch(k_fb_resolve, dim3(small), dim3(256), 0, L.stream, L.sc, L.fc, hits, fb_count, L.fallback, (const RoundState*)fst, samples)) != hipSuccess) return e;
         unsigned wblocks = (unsigned)std::min<long long>((max_hits + 3) / 4, (long long)L.persistent_blocks * 2);
-        if (L.stats) hipLaunchKernelGGL((k_shadow_wave<EXTRA, true>), dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, ovf_count, L.fallback_overflow, L.fallback, (const RoundState*)fst, samples, L.stats);
-        else hipLaunchKernelGGL((k_shadow_wave<EXTRA, false>), dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, (const HitRec*)L.hits, ovf_count, L.fallback_overflow, L.fallback, (const RoundState*)fst, samples, L.stats);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        return with_flag(L.stats != nullptr, [&](auto stats) {
+            return launch(k_shadow_wave<EXTRA, decltype(stats)::value>, dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.offsets, hits, ovf_count, L.fallback_overflow, L.fallback,
+                          (const RoundState*)fst, samples, L.stats);
+        });
+    });
+    if (e != hipSuccess) return e;
     // the next frame's longest-first tile lists, from this frame's walk lengths: last in the stage (nothing of this frame waits for it)
     if (order_items) {
-        hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(kOrderWaves * 64), 0, L.stream, (const unsigned int*)L.tile_cost, L.tile_order, order_items,
-                           (L.fc.debug >= 840 && L.fc.debug < 880) ? (unsigned)(L.fc.debug - 840) : 12u,   // longest = >= 3 x the mean (2 x: 1.41 ms per rank of 8, 3 x: 1.37, 4 x: 1.40)
-                           (L.fc.debug > 880 && L.fc.debug <= 880 + kOrderClasses) ? L.fc.debug - 880 : 3);   // classes (hook 880 + n): 2 / 3 / 4: slowest rank of 8 1.40 / 1.31 / 1.32 ms at 3 workgroups per CU (1.37 / 1.40 / 1.42 at 6)
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        e = launch(k_tile_order, dim3(8), dim3(kOrderWaves * 64), 0, L.stream, (const unsigned int*)L.tile_cost, L.tile_order, order_items,
+                   (L.fc.debug >= 840 && L.fc.debug < 880) ? (unsigned)(L.fc.debug - 840) : 12u,   // longest = >= 3 x the mean (2 x: 1.41 ms per rank of 8, 3 x: 1.37, 4 x: 1.40)
+                   (L.fc.debug > 880 && L.fc.debug <= 880 + kOrderClasses) ? L.fc.debug - 880 : 3);   // classes (hook 880 + n): 2 / 3 / 4: slowest rank of 8 1.40 / 1.31 / 1.32 ms at 3 workgroups per CU (1.37 / 1.40 / 1.42 at 6)
+        if (e != hipSuccess) return e;
         *L.tile_order_tag = order_new_tag;
     }
     return hipSuccess;
@@ -6090,20 +6075,14 @@ static hipError_t launch_dynamic_shadows_t(const PipelineLaunch& L, PipelineLaun
     }
     if (chunks > 1) {
         const unsigned blocks = (unsigned)std::min<long long>((max_hits + 255) / 256, (long long)L.persistent_blocks);
-        hipLaunchKernelGGL(k_accum_finish, dim3(blocks), dim3(256), 0, L.stream, T.fc, (const HitRec*)L.hits, L.counters, samples, S);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch(k_accum_finish, dim3(blocks), dim3(256), 0, L.stream, T.fc, (const HitRec*)L.hits, L.counters, samples, S)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-// the path-tracing stage of one row band (see k_pt_mark): counters [0] = the band's hit count, left by k_primary
-template <int MODE, bool EXTRA>
-static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples) {
+// a row band as the compaction kernels of the path-tracing and ambient-occlusion stages see it
+static PtBand make_pt_band(const PipelineLaunch& L, int row_begin, int row_count) {
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
-    hipError_t e;
-    hipEvent_t e0, e1;
-    pipe_events(L, L.pt_phase == 1 ? K_PT_COUNT : K_PATHTRACE, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
     PtBand band;
     band.n = (uint32_t)((long long)row_count * L.fc.width * n2);
     band.row_samples = (uint32_t)(L.fc.width * n2);
@@ -6111,79 +6090,102 @@ static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int
     band.sample_base = n2 == 1 ? (uint32_t)((long long)((L.fc.strip_count > 0 ? 0 : L.fc.first_row) + row_begin) * L.fc.width) : 0u;
     band.row_begin = row_begin;
     band.block_height = L.pt_block_height;
-    const uint32_t chunks = (band.n + (uint32_t)kPtChunk - 1u) / (uint32_t)kPtChunk;
-    const unsigned blocks = (unsigned)std::min<long long>(((long long)band.n + 255) / 256, (long long)L.persistent_blocks);
-    const HitRec* hits = (const HitRec*)L.hits;
-    HitRec* rays = (HitRec*)L.hits2;
-    // a part of a split frame (L.pt_phase, sr_device.h): phase 1 ends with the rows' hit counts; phase 2 starts from the scan that
-    // phase 1 left when the part is one band (L.pt_reuse), and reads row_k0 where the whole frame reads the blocks' carries
-    if (L.pt_phase != 2 || !L.pt_reuse) {
-        if ((e = hipMemsetAsync(L.pt_flags, 0, band.n, L.stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_pt_mark, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, L.pt_flags);
-        hipLaunchKernelGGL(k_pt_scan, dim3(chunks), dim3(256), 0, L.stream, (const uint8_t*)L.pt_flags, band.n, L.pt_index, L.pt_totals);
-        hipLaunchKernelGGL(k_pt_scan_totals, dim3(1), dim3(256), 0, L.stream, L.pt_totals, chunks);
-    }
-    if (L.pt_phase == 1) {
-        hipLaunchKernelGGL(k_pt_row_hits, dim3((unsigned)((row_count + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
-                           L.row_map, L.pt_range_first, L.pt_row_hits);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        return hipSuccess;
-    }
-    if (L.pt_phase == 2) {
-        hipLaunchKernelGGL(k_pt_prep<true>, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
-                           (const uint32_t*)L.pt_row_k0, L.pt_table, rays);
-    } else {
-        hipLaunchKernelGGL(k_pt_prep<false>, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
-                           (const uint32_t*)L.pt_carry, L.pt_table, rays);
-        hipLaunchKernelGGL(k_pt_carry, dim3((unsigned)((L.pt_blocks + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
-                           L.pt_carry, (int)L.pt_blocks);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
-    if constexpr (MODE == MODE_BVH) {
-        // the second rays on the incoherent-ray route of the mirror extension (see k_pt_finish_walked); SR_DBG_KERNEL_SWITCH 33 keeps
-        // the per-lane form below (same pixels: cross-check)
-        if (L.bounce_prep && L.bounce_res && L.fc.debug != 33) {
-            const bool wide = L.sc.b4 != nullptr && !L.bvh2_packets;
-            const size_t wlds = (size_t)(wide ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE_BVH)) * 256 * 4;
-            const unsigned int* order = nullptr;
-            if (L.ray_sort_buf && L.fc.debug != 31) {
-                const unsigned cap = band.n;
-                unsigned int* b = L.ray_sort_buf;
-                if ((e = ray_sort(rays, L.counters, cap, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
-                order = b + 3 * (size_t)cap;
-            }
-            BounceRay* prep = (BounceRay*)L.bounce_prep;
-            BounceHit* res = (BounceHit*)L.bounce_res;
-            hipLaunchKernelGGL(k_bounce_prep, dim3(blocks), dim3(256), 0, L.stream, L.sc, (const HitRec*)rays, L.counters, order, prep, res);
-            const int levels_all = (int)(wlds / (256 * 4));
-            int lds_levels = std::max(1, std::min(kBounceLdsLevels, levels_all));
-            if ((size_t)(levels_all - lds_levels) * (size_t)blocks * 256 * 4 > L.bounce_stack_bytes || !L.bounce_stack) lds_levels = levels_all;
-            const auto walk = [&](auto kern) {                         // counters [2]: the walk's work head (zero since the band's reset)
-                hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), (size_t)lds_levels * 256 * 4, L.stream, L.sc, (const BounceRay*)prep, L.counters, L.counters + 2, res, sec_stats,
-                                   kWalkRefillAt, L.bounce_stack, lds_levels, kWalkNodeBurst, kWalkLeafBurst);
-            };
-            if (wide) { if (sec_stats) walk(k_bounce_walk<true, true>); else walk(k_bounce_walk<false, true>); }
-            else { if (sec_stats) walk(k_bounce_walk<true, false>); else walk(k_bounce_walk<false, false>); }
-            const auto finw = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, L.sc, L.fc, hits, (const HitRec*)rays, L.counters, order, (const BounceRay*)prep,
-                                   (const BounceHit*)res, samples, sec_stats);
-            };
-            if (sec_stats) finw(k_pt_finish_walked<EXTRA, true>); else finw(k_pt_finish_walked<EXTRA, false>);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-            return hipSuccess;
+    return band;
+}
+
+// the scan of n flag bytes: index[p] = the flags set before p inside its chunk of kPtChunk positions, totals[c] = those before chunk c,
+// totals[chunks] = all of them
+static uint32_t flag_scan_chunks(uint32_t n) { return (n + (uint32_t)kPtChunk - 1u) / (uint32_t)kPtChunk; }
+static hipError_t flag_scan(const uint8_t* flags, uint32_t n, uint32_t* index, uint32_t* totals, hipStream_t stream) {
+    hipError_t e;
+    if ((e = launch(k_pt_scan, dim3(flag_scan_chunks(n)), dim3(256), 0, stream, flags, n, index, totals)) != hipSuccess) return e;
+    return launch(k_pt_scan_totals, dim3(1), dim3(256), 0, stream, totals, flag_scan_chunks(n));
+}
+
+// a level's rays in (origin cell, direction octant) order -- neighbouring lanes walk neighbouring subtrees: the order ray_sort leaves in the
+// launch's sort scratch (PipelineLaunch or PathPointsLaunch), `cap` entries per array
+template <class Launch>
+static hipError_t sorted_ray_order(const Launch& L, const HitRec* rays, const unsigned int* count, unsigned cap, const unsigned int** order) {
+    unsigned int* b = L.ray_sort_buf;
+    *order = b + 3 * (size_t)cap;
+    return ray_sort(rays, count, cap, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream);
+}
+
+// what the hooks of a mirror level may change in the walk below (nobody else has hooks)
+struct WalkTuning { int lds_levels = kBounceLdsLevels, refill_at = kWalkRefillAt, node_burst = kWalkNodeBurst, leaf_burst = kWalkLeafBurst; };
+
+// the walk's stack levels of a private walk on the tree the incoherent rays take: the four-wide tree unless SR_DBG_BVH2_PACKETS
+template <class Launch>
+static int bounce_walk_levels(const Launch& L) { return (L.sc.b4 != nullptr && !L.bvh2_packets) ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE_BVH); }
+
+// The route of incoherent rays on the own BVH -- a mirror level's, a path-traced frame's second rays, sr_path_points': the rays of the
+// queue (*count of them, at most cap) sorted (`sorted`; *order: the order, or nullptr), k_bounce_prep, k_bounce_walk with counters[2] as its
+// work head (zero since the caller's reset).  The caller's finish kernel reads L.bounce_prep / L.bounce_res in *order
+template <class Launch>
+static hipError_t bounce_walk(const Launch& L, const HitRec* rays, const unsigned int* count, unsigned cap, bool sorted, unsigned blocks, unsigned long long* stats,
+                              const WalkTuning& tuning, const unsigned int** order) {
+    hipError_t e;
+    *order = nullptr;
+    if (sorted && (e = sorted_ray_order(L, rays, count, cap, order)) != hipSuccess) return e;
+    BounceRay* prep = (BounceRay*)L.bounce_prep;
+    BounceHit* res = (BounceHit*)L.bounce_res;
+    if ((e = launch(k_bounce_prep, dim3(blocks), dim3(256), 0, L.stream, L.sc, rays, count, *order, prep, res)) != hipSuccess) return e;
+    // stack levels in LDS: kBounceLdsLevels when the rest of the worst case fits the overflow buffer, all of them otherwise
+    const int levels_all = bounce_walk_levels(L);
+    int lds_levels = std::max(1, std::min(tuning.lds_levels, levels_all));
+    if ((size_t)(levels_all - lds_levels) * (size_t)blocks * 256 * 4 > L.bounce_stack_bytes || !L.bounce_stack) lds_levels = levels_all;
+    return with_flag(stats != nullptr, [&](auto counted) { return with_flag(L.sc.b4 != nullptr && !L.bvh2_packets, [&](auto wide) {
+        return launch(k_bounce_walk<decltype(counted)::value, decltype(wide)::value>, dim3(blocks), dim3(256), (size_t)lds_levels * 256 * 4, L.stream, L.sc, (const BounceRay*)prep, count,
+                      L.counters + 2, res, stats, tuning.refill_at, L.bounce_stack, lds_levels, tuning.node_burst, tuning.leaf_burst);
+    }); });
+}
+
+// the path-tracing stage of one row band (see k_pt_mark): counters [0] = the band's hit count, left by k_primary
+template <int MODE, bool EXTRA>
+static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples) {
+    return timed(L, L.pt_phase == 1 ? K_PT_COUNT : K_PATHTRACE, [&] {
+        hipError_t e;
+        const PtBand band = make_pt_band(L, row_begin, row_count);
+        const unsigned blocks = (unsigned)std::min<long long>(((long long)band.n + 255) / 256, (long long)L.persistent_blocks);
+        const HitRec* hits = (const HitRec*)L.hits;
+        HitRec* rays = (HitRec*)L.hits2;
+        // a part of a split frame (L.pt_phase, sr_device.h): phase 1 ends with the rows' hit counts; phase 2 starts from the scan that
+        // phase 1 left when the part is one band (L.pt_reuse), and reads row_k0 where the whole frame reads the blocks' carries
+        if (L.pt_phase != 2 || !L.pt_reuse) {
+            if ((e = hipMemsetAsync(L.pt_flags, 0, band.n, L.stream)) != hipSuccess) return e;
+            if ((e = launch(k_pt_mark, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, L.pt_flags)) != hipSuccess) return e;
+            if ((e = flag_scan(L.pt_flags, band.n, L.pt_index, L.pt_totals, L.stream)) != hipSuccess) return e;
         }
-    }
-    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
-    const auto fin = [&](auto kern, unsigned long long* stats) {
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, hits, (const HitRec*)rays, L.counters, samples, stats);
-    };
-    if (sec_stats) fin(k_pt_finish<MODE, EXTRA, true>, sec_stats); else fin(k_pt_finish<MODE, EXTRA, false>, nullptr);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    return hipSuccess;
+        if (L.pt_phase == 1)
+            return launch(k_pt_row_hits, dim3((unsigned)((row_count + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals, L.row_map,
+                          L.pt_range_first, L.pt_row_hits);
+        if (L.pt_phase == 2) {
+            if ((e = launch(k_pt_prep<true>, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                            (const uint32_t*)L.pt_row_k0, L.pt_table, rays)) != hipSuccess) return e;
+        } else {
+            if ((e = launch(k_pt_prep<false>, dim3(blocks), dim3(256), 0, L.stream, band, hits, L.counters, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                            (const uint32_t*)L.pt_carry, L.pt_table, rays)) != hipSuccess) return e;
+            if ((e = launch(k_pt_carry, dim3((unsigned)((L.pt_blocks + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals, L.pt_carry,
+                            (int)L.pt_blocks)) != hipSuccess) return e;
+        }
+        unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
+        if constexpr (MODE == MODE_BVH) {
+            // the second rays on the incoherent-ray route of the mirror extension (see k_pt_finish_walked); SR_DBG_KERNEL_SWITCH 33 keeps
+            // the per-lane form below (same pixels: cross-check)
+            if (L.bounce_prep && L.bounce_res && L.fc.debug != 33) {
+                const unsigned int* order;
+                if ((e = bounce_walk(L, rays, L.counters, band.n, L.ray_sort_buf && L.fc.debug != 31, blocks, sec_stats, WalkTuning{}, &order)) != hipSuccess) return e;
+                return with_flag(sec_stats != nullptr, [&](auto stats) {
+                    return launch(k_pt_finish_walked<EXTRA, decltype(stats)::value>, dim3(blocks), dim3(256), 0, L.stream, L.sc, L.fc, hits, (const HitRec*)rays, L.counters, order,
+                                  (const BounceRay*)L.bounce_prep, (const BounceHit*)L.bounce_res, samples, sec_stats);
+                });
+            }
+        }
+        const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+        return with_flag(sec_stats != nullptr, [&](auto stats) {
+            return launch(k_pt_finish<MODE, EXTRA, decltype(stats)::value>, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, hits, (const HitRec*)rays, L.counters, samples, sec_stats);
+        });
+    });
 }
 
 // the ambient-occlusion stage of a frame's one row band (see k_ao_claim): `count` = the entries of the band's hit queue (invalid
@@ -6191,78 +6193,59 @@ static hipError_t launch_pathtrace_t(const PipelineLaunch& L, int row_begin, int
 // generators in a row block.  hipErrorNotSupported: the host refused the table (L.ao_table has left the reason)
 template <int MODE, bool EXTRA>
 static hipError_t launch_ao_t(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples, long long max_hits) {
-    const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
-    const bool cached = !(L.fc.flags & kFlagAoUncached);
-    hipError_t e;
-    hipEvent_t e0, e1;
-    pipe_events(L, K_AO, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    PtBand band;
-    band.n = (uint32_t)((long long)row_count * L.fc.width * n2);
-    band.row_samples = (uint32_t)(L.fc.width * n2);
-    band.sample_base = n2 == 1 ? (uint32_t)((long long)(L.fc.first_row + row_begin) * L.fc.width) : 0u;      // (no strips: sr_api.cpp)
-    band.row_begin = row_begin;
-    band.block_height = L.pt_block_height;
-    const uint32_t chunks = (band.n + (uint32_t)kPtChunk - 1u) / (uint32_t)kPtChunk;
-    const unsigned blocks = (unsigned)std::min<long long>((max_hits + 255) / 256, (long long)L.persistent_blocks);
-    const HitRec* hits = (const HitRec*)L.hits;
-    HitRec* gen = (HitRec*)L.hits2;
-    const unsigned int* count = L.counters;
-    if ((e = hipMemsetAsync(L.pt_flags, 0, band.n, L.stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(L.pt_carry, 0, (size_t)L.pt_blocks * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
-    if (cached) {
-        if ((e = hipMemsetAsync(L.ao_claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ao_claim, dim3(blocks), dim3(256), 0, L.stream, L.fc, (const uint8_t*)L.ao_cache, hits, count, L.ao_claim, L.pt_block_height, L.pt_blocks);
-        hipLaunchKernelGGL(k_ao_mark, dim3(blocks), dim3(256), 0, L.stream, L.fc, band, (const uint8_t*)L.ao_cache, hits, count, (const unsigned long long*)L.ao_claim,
-                           L.pt_block_height, L.pt_blocks, L.pt_flags);
-    } else {
-        hipLaunchKernelGGL(k_pt_mark, dim3(blocks), dim3(256), 0, L.stream, band, hits, count, L.pt_flags);
-    }
-    hipLaunchKernelGGL(k_pt_scan, dim3(chunks), dim3(256), 0, L.stream, (const uint8_t*)L.pt_flags, band.n, L.pt_index, L.pt_totals);
-    hipLaunchKernelGGL(k_pt_scan_totals, dim3(1), dim3(256), 0, L.stream, L.pt_totals, chunks);
-    hipLaunchKernelGGL(k_pt_carry, dim3((unsigned)((L.pt_blocks + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
-                       L.pt_carry, (int)L.pt_blocks);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    // ---- how many generators, and how many in the fullest row block? ----
-    std::vector<uint32_t> per_block((size_t)L.pt_blocks + 1, 0u);
-    if ((e = hipMemcpyAsync(per_block.data(), L.pt_carry, (size_t)L.pt_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(&per_block[(size_t)L.pt_blocks], L.pt_totals + chunks, sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(L.stream)) != hipSuccess) return e;
-    const unsigned int ngen = per_block[(size_t)L.pt_blocks];
-    const unsigned int block_max = *std::max_element(per_block.begin(), per_block.end() - 1);
-    if (ngen > 0) {
-        const int32_t* table = L.ao_table ? L.ao_table(L.user, block_max) : nullptr;
-        if (!table) {
-            if (e1) (void)hipEventRecord(e1, L.stream);                       // (the stage's event pair stays a pair)
-            return hipErrorNotSupported;
-        }
-        if ((e = hipMemsetAsync(L.ao_escapes, 0, (size_t)ngen * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ao_select, dim3(blocks), dim3(256), 0, L.stream, band, hits, count, (const uint8_t*)L.pt_flags, (const uint32_t*)L.pt_index,
-                           (const uint32_t*)L.pt_totals, gen);
-        const unsigned long long items = (unsigned long long)ngen * (unsigned long long)kAoProbes;
-        const unsigned pblocks = (unsigned)std::min<unsigned long long>((items + 255) / 256, (unsigned long long)L.persistent_blocks);
-        const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
-        unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
-        hipEvent_t p0, p1;
-        pipe_events(L, K_AO_PROBE, p0, p1);
-        if (p0 && (e = hipEventRecord(p0, L.stream)) != hipSuccess) return e;
-        const auto probe = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), lds, L.stream, L.sc, (const HitRec*)gen, ngen, table, L.ao_escapes, sec_stats);
-        };
-        if (MODE == MODE_BVH && L.fc.debug != 34) {                                   // (hook 34: nearest-hit walks, same bytes)
-            if (sec_stats) probe(k_ao_probe<MODE, EXTRA, true, true>); else probe(k_ao_probe<MODE, EXTRA, false, true>);
+    return timed(L, K_AO, [&] {
+        hipError_t e;
+        const bool cached = !(L.fc.flags & kFlagAoUncached);
+        const PtBand band = make_pt_band(L, row_begin, row_count);                                     // (no strips: sr_api.cpp)
+        const unsigned blocks = (unsigned)std::min<long long>((max_hits + 255) / 256, (long long)L.persistent_blocks);
+        const HitRec* hits = (const HitRec*)L.hits;
+        HitRec* gen = (HitRec*)L.hits2;
+        const unsigned int* count = L.counters;
+        if ((e = hipMemsetAsync(L.pt_flags, 0, band.n, L.stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(L.pt_carry, 0, (size_t)L.pt_blocks * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
+        if (cached) {
+            if ((e = hipMemsetAsync(L.ao_claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
+            if ((e = launch(k_ao_claim, dim3(blocks), dim3(256), 0, L.stream, L.fc, (const uint8_t*)L.ao_cache, hits, count, L.ao_claim, L.pt_block_height, L.pt_blocks)) != hipSuccess) return e;
+            if ((e = launch(k_ao_mark, dim3(blocks), dim3(256), 0, L.stream, L.fc, band, (const uint8_t*)L.ao_cache, hits, count, (const unsigned long long*)L.ao_claim, L.pt_block_height,
+                            L.pt_blocks, L.pt_flags)) != hipSuccess) return e;
         } else {
-            if (sec_stats) probe(k_ao_probe<MODE, EXTRA, true, false>); else probe(k_ao_probe<MODE, EXTRA, false, false>);
+            if ((e = launch(k_pt_mark, dim3(blocks), dim3(256), 0, L.stream, band, hits, count, L.pt_flags)) != hipSuccess) return e;
         }
-        if (p1 && (e = hipEventRecord(p1, L.stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ao_store, dim3((ngen + 255u) / 256u), dim3(256), 0, L.stream, (const HitRec*)gen, ngen, L.ao_escapes, cached ? L.ao_cache : nullptr);
-    }
-    if (cached || ngen > 0)
-        hipLaunchKernelGGL(k_ao_apply, dim3(blocks), dim3(256), 0, L.stream, band, cached ? (const uint8_t*)L.ao_cache : nullptr, hits, count,
-                           (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals, (const uint32_t*)L.ao_escapes, samples);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    return hipSuccess;
+        if ((e = flag_scan(L.pt_flags, band.n, L.pt_index, L.pt_totals, L.stream)) != hipSuccess) return e;
+        if ((e = launch(k_pt_carry, dim3((unsigned)((L.pt_blocks + 255) / 256)), dim3(256), 0, L.stream, band, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals, L.pt_carry,
+                        (int)L.pt_blocks)) != hipSuccess) return e;
+        // ---- how many generators, and how many in the fullest row block? ----
+        std::vector<uint32_t> per_block((size_t)L.pt_blocks + 1, 0u);
+        if ((e = hipMemcpyAsync(per_block.data(), L.pt_carry, (size_t)L.pt_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(&per_block[(size_t)L.pt_blocks], L.pt_totals + flag_scan_chunks(band.n), sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(L.stream)) != hipSuccess) return e;
+        const unsigned int ngen = per_block[(size_t)L.pt_blocks];
+        const unsigned int block_max = *std::max_element(per_block.begin(), per_block.end() - 1);
+        if (ngen > 0) {
+            const int32_t* table = L.ao_table ? L.ao_table(L.user, block_max) : nullptr;
+            if (!table) return hipErrorNotSupported;
+            if ((e = hipMemsetAsync(L.ao_escapes, 0, (size_t)ngen * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
+            if ((e = launch(k_ao_select, dim3(blocks), dim3(256), 0, L.stream, band, hits, count, (const uint8_t*)L.pt_flags, (const uint32_t*)L.pt_index, (const uint32_t*)L.pt_totals,
+                            gen)) != hipSuccess) return e;
+            const unsigned long long items = (unsigned long long)ngen * (unsigned long long)kAoProbes;
+            const unsigned pblocks = (unsigned)std::min<unsigned long long>((items + 255) / 256, (unsigned long long)L.persistent_blocks);
+            const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+            unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
+            e = timed(L, K_AO_PROBE, [&] {
+                // (hook 34: nearest-hit walks, same bytes)
+                return with_flag(MODE == MODE_BVH && L.fc.debug != 34, [&](auto any_hit) { return with_flag(sec_stats != nullptr, [&](auto stats) {
+                    return launch(k_ao_probe<MODE, EXTRA, decltype(stats)::value, decltype(any_hit)::value>, dim3(pblocks), dim3(256), lds, L.stream, L.sc, (const HitRec*)gen, ngen, table,
+                                  L.ao_escapes, sec_stats);
+                }); });
+            });
+            if (e != hipSuccess) return e;
+            if ((e = launch(k_ao_store, dim3((ngen + 255u) / 256u), dim3(256), 0, L.stream, (const HitRec*)gen, ngen, L.ao_escapes, cached ? L.ao_cache : nullptr)) != hipSuccess) return e;
+        }
+        if (cached || ngen > 0)
+            return launch(k_ao_apply, dim3(blocks), dim3(256), 0, L.stream, band, cached ? (const uint8_t*)L.ao_cache : nullptr, hits, count, (const uint32_t*)L.pt_index,
+                          (const uint32_t*)L.pt_totals, (const uint32_t*)L.ao_escapes, samples);
+        return hipSuccess;
+    });
 }
 
 // the stage a shadowed fill or bake pass runs between its canonical rays and k_lf_store: the frame's dynamic shadow stage over the compact
@@ -6284,8 +6267,7 @@ static hipError_t launch_lf_shadows_t(const PipelineLaunch& L, long long max_hit
     const bool shaft_frame = (MODE != MODE_BVH && L.shadows_on_bvh) ? shaft_path<MODE_BVH>(L) : shaft_path<MODE>(L);
     if ((e = launch_dynamic_shadows_t<MODE, EXTRA>(L, T, shaft_frame, L.lf_stage, max_hits)) != hipSuccess) return e;
     const unsigned blocks = (unsigned)std::min<long long>((max_hits + 255) / 256, (long long)L.persistent_blocks);
-    hipLaunchKernelGGL(k_lf_store, dim3(std::max(blocks, 1u)), dim3(256), 0, L.stream, (const HitRec*)L.hits, (const unsigned int*)L.counters, (const uint32_t*)L.lf_stage, L.lf_cache, claim);
-    return hipGetLastError();
+    return launch(k_lf_store, dim3(std::max(blocks, 1u)), dim3(256), 0, L.stream, (const HitRec*)L.hits, (const unsigned int*)L.counters, (const uint32_t*)L.lf_stage, L.lf_cache, claim);
 }
 
 constexpr int kLfListCount = 16;      // counters[16]: the fill list's length of a shadowed light-field band (counters[0..15] are the shadow stage's)
@@ -6294,30 +6276,20 @@ constexpr int kLfListCount = 16;      // counters[16]: the fill list's length of
 // the length itself), with shadows its SHADOW form, the shadow stage on the hits it queued and k_lf_store
 template <int MODE, bool EXTRA>
 static hipError_t launch_lf_fill_t(const PipelineLaunch& L, long long max_cells, unsigned int* list_count, bool shadowed) {
-    hipError_t e;
-    hipEvent_t e0, e1;
-    pipe_events(L, K_LF_FILL, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    const unsigned fblocks = (unsigned)std::min<long long>((max_cells + 255) / 256, (long long)L.persistent_blocks);
-    const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
-    unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
-    if (shadowed) {
-        const auto fill = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(fblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)list_count, L.lf_cache,
-                               L.lf_claim, sec_stats, (HitRec*)L.hits, L.counters, L.lf_stage);
-        };
-        if (sec_stats) fill(k_lf_fill<MODE, EXTRA, true, true>); else fill(k_lf_fill<MODE, EXTRA, false, true>);
-    } else {
-        const auto fill = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(fblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)list_count, L.lf_cache,
-                               L.lf_claim, sec_stats, (HitRec*)nullptr, (unsigned int*)nullptr, (uint32_t*)nullptr);
-        };
-        if (sec_stats) fill(k_lf_fill<MODE, EXTRA, true>); else fill(k_lf_fill<MODE, EXTRA, false>);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    if (shadowed && (e = launch_lf_shadows_t<MODE, EXTRA>(L, max_cells, L.lf_claim)) != hipSuccess) return e;
-    return hipSuccess;
+    hipError_t e = timed(L, K_LF_FILL, [&] {
+        const unsigned fblocks = (unsigned)std::min<long long>((max_cells + 255) / 256, (long long)L.persistent_blocks);
+        const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
+        unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
+        // SHADOW: the hits go to the band's queue and the staging buffer
+        return with_flag(shadowed, [&](auto shadow) { return with_flag(sec_stats != nullptr, [&](auto stats) {
+            constexpr bool SHADOW = decltype(shadow)::value;
+            return launch(k_lf_fill<MODE, EXTRA, decltype(stats)::value, SHADOW>, dim3(fblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list,
+                          (const unsigned int*)list_count, L.lf_cache, L.lf_claim, sec_stats, SHADOW ? (HitRec*)L.hits : nullptr, SHADOW ? L.counters : nullptr,
+                          SHADOW ? L.lf_stage : nullptr);
+        }); });
+    });
+    if (e != hipSuccess) return e;
+    return shadowed ? launch_lf_shadows_t<MODE, EXTRA>(L, max_cells, L.lf_claim) : hipSuccess;
 }
 
 // the three light-field kernels of one row band (see k_lf_lookup; L.lf_interp: k_lfi_lookup and k_lfi_apply around the same fill stage, whose
@@ -6328,43 +6300,32 @@ template <int MODE, bool EXTRA>
 static hipError_t launch_lightfield_t(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples) {
     const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
     const uint32_t nsamples = (uint32_t)((long long)row_count * L.fc.width * n2);
-    const unsigned blocks = (nsamples + 255u) / 256u;
+    const dim3 grid((nsamples + 255u) / 256u);
     const bool shadowed = L.lf_shadows && (L.fc.flags & 2u);
     unsigned int* list_count = shadowed ? L.counters + kLfListCount : L.counters;
     hipError_t e;
-    hipEvent_t e0, e1;
     if ((e = hipMemsetAsync(L.counters, 0, (shadowed ? (size_t)kCounterWords : 1) * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
-    pipe_events(L, L.lf_interp ? K_LFI_LOOKUP : K_LF_LOOKUP, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    if (L.lf_interp) {
-        const auto lookup = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, (const uint32_t*)L.lf_cache, L.lf_claim,
-                               L.lf_cells, L.lf_fracs, L.lf_list, list_count, L.stats);
-        };
-        if (L.lf_carry) lookup(k_lfi_lookup<true>); else lookup(k_lfi_lookup<false>);
-    } else {
-        hipLaunchKernelGGL(k_lf_lookup, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, L.lf_entries, (const uint32_t*)L.lf_cache, L.lf_claim,
-                           L.lf_cells, L.lf_list, list_count, L.stats);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    e = timed(L, L.lf_interp ? K_LFI_LOOKUP : K_LF_LOOKUP, [&] {
+        if (L.lf_interp)
+            return with_flag(L.lf_carry, [&](auto carry) {
+                return launch(k_lfi_lookup<decltype(carry)::value>, grid, dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, (const uint32_t*)L.lf_cache, L.lf_claim,
+                              L.lf_cells, L.lf_fracs, L.lf_list, list_count, L.stats);
+            });
+        return launch(k_lf_lookup, grid, dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, L.lf_entries, (const uint32_t*)L.lf_cache, L.lf_claim, L.lf_cells,
+                      L.lf_list, list_count, L.stats);
+    });
+    if (e != hipSuccess) return e;
     // (an interpolating band lists up to min(16 x samples, 4 N^4) cells)
     const long long max_cells = L.lf_interp ? std::min<long long>(16ll * nsamples, (long long)L.lf_entries) : (long long)nsamples;
     if ((e = launch_lf_fill_t<MODE, EXTRA>(L, max_cells, list_count, shadowed)) != hipSuccess) return e;
-    pipe_events(L, L.lf_interp ? K_LFI_APPLY : K_LF_APPLY, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    if (L.lf_interp) {
-        const auto apply = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, (const uint32_t*)L.lf_cells, (const double*)L.lf_fracs,
-                               (const uint32_t*)L.lf_cache, samples);
-        };
-        if (L.lf_carry) apply(k_lfi_apply<true>); else apply(k_lfi_apply<false>);
-    } else {
-        hipLaunchKernelGGL(k_lf_apply, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, (const uint32_t*)L.lf_cells, (const uint32_t*)L.lf_cache, samples);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    return hipSuccess;
+    return timed(L, L.lf_interp ? K_LFI_APPLY : K_LF_APPLY, [&] {
+        if (L.lf_interp)
+            return with_flag(L.lf_carry, [&](auto carry) {
+                return launch(k_lfi_apply<decltype(carry)::value>, grid, dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, (const uint32_t*)L.lf_cells,
+                              (const double*)L.lf_fracs, (const uint32_t*)L.lf_cache, samples);
+            });
+        return launch(k_lf_apply, grid, dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, (const uint32_t*)L.lf_cells, (const uint32_t*)L.lf_cache, samples);
+    });
 }
 
 // sr_light_field_rays (PipelineLaunch::lfr_n > 0): the caller's rays in passes of at most L.lfr_pass rays -- what the fill list, the pending
@@ -6386,30 +6347,24 @@ static hipError_t launch_lf_rays_t(const PipelineLaunch& L) {
         uint8_t* inside = L.lfr_inside ? L.lfr_inside + first : nullptr;
         if ((e = hipMemsetAsync(L.counters, 0, (shadowed ? (size_t)kCounterWords : 1) * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(pending, 0, sizeof(uint32_t), L.stream)) != hipSuccess) return e;
-        hipEvent_t e0, e1;
-        pipe_events(L, L.lf_interp ? K_LFRI_LOOKUP : K_LFR_LOOKUP, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        if (L.lf_interp)
-            hipLaunchKernelGGL(k_lfri_lookup, dim3(blocks), dim3(256), 0, L.stream, count, starts, dirs, L.lf_res, L.fc.background, (const uint32_t*)L.lf_cache, L.lf_claim, out, inside,
-                               L.lf_list, list_count, pending, L.stats);
-        else
-            hipLaunchKernelGGL(k_lfr_lookup, dim3(blocks), dim3(256), 0, L.stream, count, starts, dirs, L.lf_res, L.lf_entries, L.fc.background, (const uint32_t*)L.lf_cache, L.lf_claim, out,
-                               inside, L.lf_list, list_count, pending, L.stats);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        e = timed(L, L.lf_interp ? K_LFRI_LOOKUP : K_LFR_LOOKUP, [&] {
+            if (L.lf_interp)
+                return launch(k_lfri_lookup, dim3(blocks), dim3(256), 0, L.stream, count, starts, dirs, L.lf_res, L.fc.background, (const uint32_t*)L.lf_cache, L.lf_claim, out, inside,
+                              L.lf_list, list_count, pending, L.stats);
+            return launch(k_lfr_lookup, dim3(blocks), dim3(256), 0, L.stream, count, starts, dirs, L.lf_res, L.lf_entries, L.fc.background, (const uint32_t*)L.lf_cache, L.lf_claim, out,
+                          inside, L.lf_list, list_count, pending, L.stats);
+        });
+        if (e != hipSuccess) return e;
         const long long max_cells = L.lf_interp ? std::min<long long>(16ll * count, (long long)L.lf_entries) : (long long)count;
         if ((e = launch_lf_fill_t<MODE, EXTRA>(L, max_cells, list_count, shadowed)) != hipSuccess) return e;
-        pipe_events(L, L.lf_interp ? K_LFRI_FINISH : K_LFR_FINISH, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        const unsigned pblocks = std::min<unsigned>(blocks, (unsigned)L.persistent_blocks);
-        if (L.lf_interp)
-            hipLaunchKernelGGL(k_lfri_finish, dim3(pblocks), dim3(256), 0, L.stream, (const uint32_t*)pending, starts, dirs, L.lf_res, (const uint32_t*)L.lf_cache, out,
-                               (const unsigned int*)list_count, L.lfr_filled);
-        else
-            hipLaunchKernelGGL(k_lfr_finish, dim3(pblocks), dim3(256), 0, L.stream, (const uint32_t*)pending, (const uint32_t*)L.lf_cache, out, (const unsigned int*)list_count,
-                               L.lfr_filled);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        e = timed(L, L.lf_interp ? K_LFRI_FINISH : K_LFR_FINISH, [&] {
+            const unsigned pblocks = std::min<unsigned>(blocks, (unsigned)L.persistent_blocks);
+            if (L.lf_interp)
+                return launch(k_lfri_finish, dim3(pblocks), dim3(256), 0, L.stream, (const uint32_t*)pending, starts, dirs, L.lf_res, (const uint32_t*)L.lf_cache, out,
+                              (const unsigned int*)list_count, L.lfr_filled);
+            return launch(k_lfr_finish, dim3(pblocks), dim3(256), 0, L.stream, (const uint32_t*)pending, (const uint32_t*)L.lf_cache, out, (const unsigned int*)list_count, L.lfr_filled);
+        });
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -6424,50 +6379,43 @@ static hipError_t launch_lft_t(const PipelineLaunch& L, int row_begin, int row_c
     const unsigned blocks = (nsamples + 255u) / 256u;
     unsigned int* list_count = L.counters, * trace_count = L.counters + 1;
     hipError_t e;
-    hipEvent_t e0, e1;
     if ((e = hipMemsetAsync(L.counters, 0, 2 * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
-    pipe_events(L, K_LF_LOOKUP, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_lf_lookup, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, L.lf_entries, (const uint32_t*)L.lf_cache, L.lf_claim,
-                       L.lf_cells, L.lf_list, list_count, L.stats);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+    e = timed(L, K_LF_LOOKUP, [&] {
+        return launch(k_lf_lookup, dim3(blocks), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, nsamples, L.lf_res, L.lf_entries, (const uint32_t*)L.lf_cache, L.lf_claim, L.lf_cells,
+                      L.lf_list, list_count, L.stats);
+    });
+    if (e != hipSuccess) return e;
     const unsigned wblocks = (unsigned)std::min<long long>(((long long)nsamples + 255) / 256, (long long)L.persistent_blocks);
     const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
     unsigned long long* sec_stats = (L.stats && !L.primary_stats_only) ? L.stats : nullptr;
-    pipe_events(L, K_LFT_FILL, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    {
-        const auto fill = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list, (const unsigned int*)list_count, L.lf_cache, L.lf_claim, sec_stats);
-        };
-        if (sec_stats) fill(k_lft_fill<MODE, true>); else fill(k_lft_fill<MODE, false>);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    pipe_events(L, K_LFT_HIT, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    {
-        const auto hit = [&](auto kern, size_t kernel_lds) {
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), kernel_lds, L.stream, L.sc, L.fc, L.row_map, row_begin, nsamples, (const uint32_t*)L.lf_cells, (const uint32_t*)L.lf_cache,
-                               L.lf_handle, samples, L.lf_trace_list, trace_count, L.stats, sec_stats ? 1 : 0);
-        };
-        if (L.lf_fused) { if (L.stats) hit(k_lft_hit<MODE, true, true>, lds); else hit(k_lft_hit<MODE, false, true>, lds); }
-        else { if (L.stats) hit(k_lft_hit<MODE, true, false>, 0); else hit(k_lft_hit<MODE, false, false>, 0); }
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    if (!L.lf_fused) {
-        pipe_events(L, K_LFT_TRACE, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        const auto trace = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.row_map, row_begin, (const uint32_t*)L.lf_trace_list, (const unsigned int*)trace_count, samples, L.stats);
-        };
-        if (L.stats) trace(k_lft_trace<MODE, true>); else trace(k_lft_trace<MODE, false>);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    e = timed(L, K_LFT_FILL, [&] {
+        return with_flag(sec_stats != nullptr, [&](auto stats) {
+            return launch(k_lft_fill<MODE, decltype(stats)::value>, dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.lf_points, L.lf_res, (const uint32_t*)L.lf_list,
+                          (const unsigned int*)list_count, L.lf_cache, L.lf_claim, sec_stats);
+        });
+    });
+    if (e != hipSuccess) return e;
+    e = timed(L, K_LFT_HIT, [&] {
+        return with_flag(L.lf_fused, [&](auto fused) { return with_flag(L.stats != nullptr, [&](auto stats) {
+            return launch(k_lft_hit<MODE, decltype(stats)::value, decltype(fused)::value>, dim3(blocks), dim3(256), decltype(fused)::value ? lds : 0, L.stream, L.sc, L.fc, L.row_map,
+                          row_begin, nsamples, (const uint32_t*)L.lf_cells, (const uint32_t*)L.lf_cache, L.lf_handle, samples, L.lf_trace_list, trace_count, L.stats, sec_stats ? 1 : 0);
+        }); });
+    });
+    if (e != hipSuccess || L.lf_fused) return e;
+    return timed(L, K_LFT_TRACE, [&] {
+        return with_flag(L.stats != nullptr, [&](auto stats) {
+            return launch(k_lft_trace<MODE, decltype(stats)::value>, dim3(wblocks), dim3(256), lds, L.stream, L.sc, L.fc, L.row_map, row_begin, (const uint32_t*)L.lf_trace_list,
+                          (const unsigned int*)trace_count, samples, L.stats);
+        });
+    });
+}
+
+// k_lf_bake (SHADOW: with the pass's queue and staging buffer) / k_lft_bake over `origins` whole origin patches from patch `o` on: the items
+// of a launch of either bake
+struct BakeItems { uint32_t first, count; };
+static BakeItems bake_items(uint64_t res, uint64_t o, uint64_t origins) {
+    const uint64_t tiles = ((2 * res + 7) / 8) * ((res + 7) / 8);
+    return BakeItems{(uint32_t)(o * tiles), (uint32_t)(origins * tiles)};      // (2 N^2 x tiles <= 2^24 items in all)
 }
 
 // sr_bake_light_field with shadows (PipelineLaunch::lf_bake_count > 0): entries [first, first + count) in passes of at most
@@ -6475,7 +6423,7 @@ static hipError_t launch_lft_t(const PipelineLaunch& L, int row_begin, int row_c
 // sized for.  Per pass: counters reset, k_lf_bake<SHADOW>, the shadow stage, k_lf_store; back to back on the stream, the host never waits
 template <int MODE, bool EXTRA>
 static hipError_t launch_lf_bake_shadows_t(const PipelineLaunch& L) {
-    const uint64_t n = (uint64_t)L.lf_res, per_origin = 2 * n * n, tiles = ((2 * n + 7) / 8) * ((n + 7) / 8);
+    const uint64_t n = (uint64_t)L.lf_res, per_origin = 2 * n * n;
     const uint64_t first = L.lf_bake_first, count = L.lf_bake_count;
     const uint64_t o_first = first / per_origin, o_last = (first + count - 1) / per_origin;
     const uint64_t step = std::max<uint64_t>(1, L.lf_bake_pass_cells / per_origin);
@@ -6485,30 +6433,46 @@ static hipError_t launch_lf_bake_shadows_t(const PipelineLaunch& L) {
     hipError_t e;
     for (uint64_t o = o_first; o <= o_last; o += step) {
         const uint64_t origins = std::min(step, o_last - o + 1);
-        const uint32_t item_first = (uint32_t)(o * tiles), item_count = (uint32_t)(origins * tiles);
+        const BakeItems items = bake_items(n, o, origins);
         if ((e = hipMemsetAsync(L.counters, 0, kCounterWords * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
-        hipEvent_t e0, e1;
-        pipe_events(L, K_LF_BAKE, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        const auto bake = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((item_count + 3u) / 4u), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points, L.lf_res, item_first, item_count, (uint32_t)first,
-                               (uint32_t)(first + count), L.lf_cache, stats, L.lf_bake_filled, levels, (HitRec*)L.hits, L.counters, L.lf_stage);
-        };
-        if (MODE == MODE_BVH && L.lf_bake_packet) {
-            if (stats) bake(k_lf_bake<MODE_BVH, EXTRA, true, true, true>); else bake(k_lf_bake<MODE_BVH, EXTRA, false, true, true>);
-        } else {
-            if (stats) bake(k_lf_bake<MODE, EXTRA, true, false, true>); else bake(k_lf_bake<MODE, EXTRA, false, false, true>);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        e = timed(L, K_LF_BAKE, [&] {
+            return with_flag(MODE == MODE_BVH && L.lf_bake_packet, [&](auto pkt) { return with_flag(stats != nullptr, [&](auto counted) {
+                constexpr bool PKT = decltype(pkt)::value;
+                return launch(k_lf_bake<PKT ? MODE_BVH : MODE, EXTRA, decltype(counted)::value, PKT, true>, dim3((items.count + 3u) / 4u), dim3(256), lds, L.stream, L.sc, L.fc, L.lf_points,
+                              L.lf_res, items.first, items.count, (uint32_t)first, (uint32_t)(first + count), L.lf_cache, stats, L.lf_bake_filled, levels, (HitRec*)L.hits, L.counters,
+                              L.lf_stage);
+            }); });
+        });
+        if (e != hipSuccess) return e;
         if ((e = launch_lf_shadows_t<MODE, EXTRA>(L, (long long)(origins * per_origin), nullptr)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
+// the order of a pass of points (point_order: the ray sort's key unless the caller promised coherence: then input order) and k_pts_gather:
+// the pass's records from hits2 into the queue (L.hits, counters[0]) in that order
+static hipError_t launch_pts_order(const PipelineLaunch& L, uint32_t count) {
+    return timed(L, K_PTS_SORT, [&] {
+        hipError_t e;
+        const unsigned cap = count;
+        unsigned int* b = L.ray_sort_buf;
+        if ((e = point_order(L.hits2, cap, L.pts_sort, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
+        const unsigned blocks = (unsigned)std::min<long long>(((long long)count + 255) / 256, (long long)L.persistent_blocks);
+        return launch(k_pts_gather, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)L.hits2, cap, (const unsigned int*)(b + 3 * (size_t)cap), (const unsigned int*)(b + (size_t)cap),
+                      point_order_skip_mask(L.pts_sort), (HitRec*)L.hits, L.counters);
+    });
+}
+
+static PtsBox pts_escape_box(const PipelineLaunch& L) {
+    PtsBox box;
+    for (int a = 0; a < 3; ++a) { box.lo[a] = L.pts_escape_lo[a]; box.hi[a] = L.pts_escape_hi[a]; }
+    box.on = L.pts_escape ? 1 : 0;
+    return box;
+}
+
 // sr_shadow_points (PipelineLaunch::pts_n > 0): the caller's points in passes of at most L.pts_pass points -- what the queue and the shadow
-// stage's lists are sized for.  Per pass: counters reset, k_pts_ingest, point_order (the ray sort's key unless the caller promised
-// coherence: then input order) and k_pts_gather, the shadow stage with the pass's part of `out` as its sample buffer; back to back on the stream, the host never waits.  Like a light
+// stage's lists are sized for.  Per pass: counters reset, k_pts_ingest, launch_pts_order, the shadow stage with the pass's part of `out` as
+// its sample buffer; back to back on the stream, the host never waits.  Like a light
 // field's stage it sees nothing but a compact queue: tile_queue_n2 = tile_queue_rows = 0, 64 consecutive entries per packet walk
 template <int MODE, bool EXTRA>
 static hipError_t launch_pts_shadows_t(const PipelineLaunch& L) {
@@ -6520,40 +6484,25 @@ static hipError_t launch_pts_shadows_t(const PipelineLaunch& L) {
     if (L.pts_per_lane) T.per_lane_shaft |= 1;                          // (SR_DBG_KERNEL_SWITCH 38)
     const bool shaft_frame = (MODE != MODE_BVH && L.shadows_on_bvh) ? shaft_path<MODE_BVH>(L) : shaft_path<MODE>(L);
     if (!L.ray_sort_buf || !L.hits2) return hipErrorInvalidValue;
-    PtsBox box;
-    for (int a = 0; a < 3; ++a) { box.lo[a] = L.pts_escape_lo[a]; box.hi[a] = L.pts_escape_hi[a]; }
-    box.on = L.pts_escape ? 1 : 0;
+    const PtsBox box = pts_escape_box(L);
     for (int64_t first = 0; first < L.pts_n; first += L.pts_pass) {
         const uint32_t count = (uint32_t)std::min<int64_t>(L.pts_pass, L.pts_n - first);
         uint32_t* out = L.pts_out + first;
         if ((e = hipMemsetAsync(L.counters, 0, kCounterWords * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
-        hipEvent_t e0, e1;
-        pipe_events(L, K_PTS_INGEST, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_pts_ingest<EXTRA>, dim3((count + 255u) / 256u), dim3(256), 0, L.stream, L.sc, L.fc, L.offsets, L.pts_pos + first * 3, L.pts_nrm + first * 3,
-                           L.pts_color ? L.pts_color + first : nullptr, count, box, (HitRec*)L.hits2, out);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        {
-            pipe_events(L, K_PTS_SORT, e0, e1);
-            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-            const unsigned cap = count;
-            unsigned int* b = L.ray_sort_buf;
-            if ((e = point_order(L.hits2, cap, L.pts_sort, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
-            const unsigned blocks = (unsigned)std::min<long long>(((long long)count + 255) / 256, (long long)L.persistent_blocks);
-            hipLaunchKernelGGL(k_pts_gather, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)L.hits2, cap, (const unsigned int*)(b + 3 * (size_t)cap), (const unsigned int*)(b + (size_t)cap),
-                               point_order_skip_mask(L.pts_sort), (HitRec*)L.hits, L.counters);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        }
+        e = timed(L, K_PTS_INGEST, [&] {
+            return launch(k_pts_ingest<EXTRA>, dim3((count + 255u) / 256u), dim3(256), 0, L.stream, L.sc, L.fc, L.offsets, L.pts_pos + first * 3, L.pts_nrm + first * 3,
+                          L.pts_color ? L.pts_color + first : nullptr, count, box, (HitRec*)L.hits2, out);
+        });
+        if (e != hipSuccess) return e;
+        if ((e = launch_pts_order(L, count)) != hipSuccess) return e;
         if ((e = launch_dynamic_shadows_t<MODE, EXTRA>(L, T, shaft_frame, out, (long long)count)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
 // sr_static_shadow_points (PipelineLaunch::pts_static): the caller's points through the scene's static shadow cache, in passes like
-// launch_pts_shadows_t's.  Per pass: counters reset, k_ssp_claim + k_ssp_select, point_order + k_pts_gather (launched as sr_shadow_points
-// launches them: the generators the stage must decide come first), the shadow stage a static frame runs on its generator list (flags & 32:
+// launch_pts_shadows_t's.  Per pass: counters reset, k_ssp_claim + k_ssp_select, launch_pts_order (as sr_shadow_points
+// orders them: the generators the stage must decide come first), the shadow stage a static frame runs on its generator list (flags & 32:
 // its finishing sites store cache[pad[0]] and never touch the sample buffer -- it is given the dead sort scratch, not the caller's `out`),
 // k_ssp_apply.  The claims are reset once per call; a pass sees the bytes of the passes before it
 template <int MODE, bool EXTRA>
@@ -6564,141 +6513,163 @@ static hipError_t launch_static_pts_t(const PipelineLaunch& L) {
     if (L.primary_stats_only) G.stats = nullptr;
     G.tile_queue_n2 = 0;
     G.tile_queue_rows = 0;
-    PtsBox box;
-    for (int a = 0; a < 3; ++a) { box.lo[a] = L.pts_escape_lo[a]; box.hi[a] = L.pts_escape_hi[a]; }
-    box.on = L.pts_escape ? 1 : 0;
+    const PtsBox box = pts_escape_box(L);
     const uint8_t* cache = (const uint8_t*)L.sc.shadow_cache;
     if ((e = hipMemsetAsync(L.static_claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
     for (int64_t first = 0; first < L.pts_n; first += L.pts_pass) {
         const uint32_t count = (uint32_t)std::min<int64_t>(L.pts_pass, L.pts_n - first);
         const dim3 grid((count + 255u) / 256u);
         if ((e = hipMemsetAsync(L.counters, 0, kCounterWords * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
-        hipEvent_t e0, e1;
-        pipe_events(L, K_SSP_CLAIM, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ssp_claim, grid, dim3(256), 0, L.stream, cache, L.pts_pos + first * 3, L.pts_nrm + first * 3, count, (unsigned long long)first, box,
-                           (HitRec*)L.hits2, L.static_claim);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ssp_select<EXTRA>, grid, dim3(256), 0, L.stream, L.sc, L.fc, L.offsets, count, (unsigned long long)first,
-                           (const unsigned long long*)L.static_claim, (HitRec*)L.hits2, L.pts_generators);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        {
-            pipe_events(L, K_PTS_SORT, e0, e1);
-            if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-            const unsigned cap = count;
-            unsigned int* b = L.ray_sort_buf;
-            if ((e = point_order(L.hits2, cap, L.pts_sort, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
-            const unsigned blocks = (unsigned)std::min<long long>(((long long)count + 255) / 256, (long long)L.persistent_blocks);
-            hipLaunchKernelGGL(k_pts_gather, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)L.hits2, cap, (const unsigned int*)(b + 3 * (size_t)cap), (const unsigned int*)(b + (size_t)cap),
-                               point_order_skip_mask(L.pts_sort), (HitRec*)L.hits, L.counters);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        }
+        e = timed(L, K_SSP_CLAIM, [&] {
+            hipError_t e;
+            if ((e = launch(k_ssp_claim, grid, dim3(256), 0, L.stream, cache, L.pts_pos + first * 3, L.pts_nrm + first * 3, count, (unsigned long long)first, box, (HitRec*)L.hits2,
+                            L.static_claim)) != hipSuccess) return e;
+            return launch(k_ssp_select<EXTRA>, grid, dim3(256), 0, L.stream, L.sc, L.fc, L.offsets, count, (unsigned long long)first, (const unsigned long long*)L.static_claim,
+                          (HitRec*)L.hits2, L.pts_generators);
+        });
+        if (e != hipSuccess) return e;
+        if ((e = launch_pts_order(L, count)) != hipSuccess) return e;
         // (at most one generator per cell: the bound a static frame gives its generator list)
         if ((e = launch_shadow_t<MODE, EXTRA>(G, (uint32_t*)L.ray_sort_buf, std::min<long long>((long long)count, (long long)kStaticRes * kStaticRes * kStaticRes))) != hipSuccess) return e;
-        pipe_events(L, K_SSP_APPLY, e0, e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ssp_apply, grid, dim3(256), 0, L.stream, cache, L.pts_pos + first * 3, L.pts_color ? L.pts_color + first : nullptr, count,
-                           L.pts_out ? L.pts_out + first : nullptr, L.pts_amount ? L.pts_amount + first : nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        e = timed(L, K_SSP_APPLY, [&] {
+            return launch(k_ssp_apply, grid, dim3(256), 0, L.stream, cache, L.pts_pos + first * 3, L.pts_color ? L.pts_color + first : nullptr, count,
+                          L.pts_out ? L.pts_out + first : nullptr, L.pts_amount ? L.pts_amount + first : nullptr);
+        });
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
 // sr_bake_light_field: entries [first, first + count) of the table in launches of at most L.launch_cells cells (whole origin patches; at
-// least one), one after the other on the stream with nothing in between: no single kernel runs long, and the host never waits
-template <int MODE, bool EXTRA>
-static hipError_t launch_lf_bake_t(const BakeLaunch& L) {
-    const uint64_t n = (uint64_t)L.res, per_origin = 2 * n * n, tiles = ((2 * n + 7) / 8) * ((n + 7) / 8);
+// least one), one after the other on the stream with nothing in between: no single kernel runs long, and the host never waits.
+// bake(items): the launch of one of them
+template <class Bake>
+static hipError_t for_bake_launches(const BakeLaunch& L, int kernel_id, Bake bake) {
+    const uint64_t n = (uint64_t)L.res, per_origin = 2 * n * n;
     const uint64_t o_first = L.first / per_origin, o_last = (L.first + L.count - 1) / per_origin;
     const uint64_t step = std::max<uint64_t>(1, L.launch_cells / per_origin);
-    const int levels = pipe_stack_levels(L.sc, MODE);
-    const size_t lds = (size_t)levels * 256 * 4;
-    const bool pkt = MODE == MODE_BVH && L.packet;
-    hipError_t e;
     for (uint64_t o = o_first; o <= o_last; o += step) {
-        const uint64_t origins = std::min(step, o_last - o + 1);
-        const uint32_t item_first = (uint32_t)(o * tiles), item_count = (uint32_t)(origins * tiles);      // (2 N^2 x tiles <= 2^24 items in all)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_LF_BAKE, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        const auto bake = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((item_count + 3u) / 4u), dim3(256), lds, L.stream, L.sc, L.fc, L.points, L.res, item_first, item_count, (uint32_t)L.first,
-                               (uint32_t)(L.first + L.count), L.cache, L.stats, L.filled, levels, (HitRec*)nullptr, (unsigned int*)nullptr, (uint32_t*)nullptr);
-        };
-        if (MODE == MODE_BVH && pkt) {
-            if (L.walk_stats) bake(k_lf_bake<MODE_BVH, EXTRA, true, true>); else bake(k_lf_bake<MODE_BVH, EXTRA, false, true>);
-        } else {
-            if (L.walk_stats) bake(k_lf_bake<MODE, EXTRA, true, false>); else bake(k_lf_bake<MODE, EXTRA, false, false>);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        const BakeItems items = bake_items(n, o, std::min(step, o_last - o + 1));
+        const hipError_t e = timed(L, kernel_id, [&] { return bake(items); });
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+template <int MODE, bool EXTRA>
+static hipError_t launch_lf_bake_t(const BakeLaunch& L) {
+    const int levels = pipe_stack_levels(L.sc, MODE);
+    const size_t lds = (size_t)levels * 256 * 4;
+    return for_bake_launches(L, K_LF_BAKE, [&](const BakeItems& items) {
+        return with_flag(MODE == MODE_BVH && L.packet, [&](auto pkt) { return with_flag(L.walk_stats, [&](auto counted) {
+            constexpr bool PKT = decltype(pkt)::value;
+            return launch(k_lf_bake<PKT ? MODE_BVH : MODE, EXTRA, decltype(counted)::value, PKT>, dim3((items.count + 3u) / 4u), dim3(256), lds, L.stream, L.sc, L.fc, L.points, L.res,
+                          items.first, items.count, (uint32_t)L.first, (uint32_t)(L.first + L.count), L.cache, L.stats, L.filled, levels, (HitRec*)nullptr, (unsigned int*)nullptr,
+                          (uint32_t*)nullptr);
+        }); });
+    });
 }
 
 // ... of the triangle table (BakeLaunch::tris): the same launches of k_lft_bake
 template <int MODE>
 static hipError_t launch_lft_bake_t(const BakeLaunch& L) {
-    const uint64_t n = (uint64_t)L.res, per_origin = 2 * n * n, tiles = ((2 * n + 7) / 8) * ((n + 7) / 8);
-    const uint64_t o_first = L.first / per_origin, o_last = (L.first + L.count - 1) / per_origin;
-    const uint64_t step = std::max<uint64_t>(1, L.launch_cells / per_origin);
     const size_t lds = (size_t)pipe_stack_levels(L.sc, MODE) * 256 * 4;
-    hipError_t e;
-    for (uint64_t o = o_first; o <= o_last; o += step) {
-        const uint64_t origins = std::min(step, o_last - o + 1);
-        const uint32_t item_first = (uint32_t)(o * tiles), item_count = (uint32_t)(origins * tiles);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_LFT_BAKE, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        const auto bake = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((item_count + 3u) / 4u), dim3(256), lds, L.stream, L.sc, L.points, L.res, item_first, item_count, (uint32_t)L.first,
-                               (uint32_t)(L.first + L.count), L.cache, L.stats, L.filled);
-        };
-        if (L.walk_stats) bake(k_lft_bake<MODE, true>); else bake(k_lft_bake<MODE, false>);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return for_bake_launches(L, K_LFT_BAKE, [&](const BakeItems& items) {
+        return with_flag(L.walk_stats, [&](auto counted) {
+            return launch(k_lft_bake<MODE, decltype(counted)::value>, dim3((items.count + 3u) / 4u), dim3(256), lds, L.stream, L.sc, L.points, L.res, items.first, items.count,
+                          (uint32_t)L.first, (uint32_t)(L.first + L.count), L.cache, L.stats, L.filled);
+        });
+    });
 }
 
 hipError_t launch_lf_bake(const BakeLaunch& L) {
     if (L.count == 0) return hipSuccess;
     if (L.tris) return L.mode == MODE_REF ? launch_lft_bake_t<MODE_REF>(L) : L.mode == MODE_BVH ? launch_lft_bake_t<MODE_BVH>(L) : hipErrorInvalidValue;
-    const bool extra = L.sc.nextra > 0;
-    switch (L.mode) {
-        case MODE_REF: return extra ? launch_lf_bake_t<MODE_REF, true>(L) : launch_lf_bake_t<MODE_REF, false>(L);
-        case MODE_BRUTE: return extra ? launch_lf_bake_t<MODE_BRUTE, true>(L) : launch_lf_bake_t<MODE_BRUTE, false>(L);
-        case MODE_BVH: return extra ? launch_lf_bake_t<MODE_BVH, true>(L) : launch_lf_bake_t<MODE_BVH, false>(L);
-        default: return hipErrorInvalidValue;
-    }
+    return for_mode(L.mode, L.sc.nextra > 0, [&](auto mode, auto extra) { return launch_lf_bake_t<decltype(mode)::value, decltype(extra)::value>(L); });
 }
 
 hipError_t launch_lf_coords(long long n, const double* starts, const double* dirs, int res, double* coords, uint8_t* inside, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_lf_coords, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, starts, dirs, res, coords, inside);
-    return hipGetLastError();
-}
-
-static hipError_t launch_resolve(const PipelineLaunch& L, int row_begin, int row_count) {
-    hipError_t e;
-    hipEvent_t e0, e1;
-    pipe_events(L, K_RESOLVE, e0, e1);
-    if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-    long long npx = (long long)row_count * L.fc.width;
-    hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, L.stream, L.fc, L.row_map, row_begin, row_count,
-                       (const uint32_t*)L.samples, L.pixels);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-    return hipSuccess;
+    return launch(k_lf_coords, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, starts, dirs, res, coords, inside);
 }
 
 hipError_t launch_resolve_rows(const FrameConst& fc, const int32_t* row_map, int row_begin, int row_count, const uint32_t* samples, uint32_t* pixels, hipStream_t stream) {
     const long long npx = (long long)row_count * fc.width;
-    hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, fc, row_map, row_begin, row_count, samples, pixels);
-    return hipGetLastError();
+    return launch(k_resolve, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, fc, row_map, row_begin, row_count, samples, pixels);
+}
+
+static hipError_t launch_resolve(const PipelineLaunch& L, int row_begin, int row_count) {
+    return timed(L, K_RESOLVE, [&] { return launch_resolve_rows(L.fc, L.row_map, row_begin, row_count, L.samples, L.pixels, L.stream); });
+}
+
+// the mirror bounces of a band as a wavefront pipeline: one level after the other, the queues (L.hits, L.hits2) ping-pong, k_fold at the end
+// counters: [0] / [1] ray counts of the two queues  [2] the level's work head
+template <bool EXTRA>
+static hipError_t launch_bounces(const PipelineLaunch& L, int row_begin, int row_count, uint32_t* samples) {
+    hipError_t e;
+    const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
+    const long long band_n = (long long)row_count * L.fc.width * n2;
+    const size_t lds = (size_t)bounce_walk_levels(L) * 256 * 4;                                  // private walks on the four-wide tree
+    const unsigned blocks = (unsigned)std::min<long long>((band_n + 255) / 256, (long long)L.persistent_blocks);
+    const bool sorted = L.ray_sort_buf && L.fc.debug != 31;
+    int cur = 0;
+    for (int level = 1; level <= L.fc.max_bounces; ++level, cur = 1 - cur) {
+        if ((e = hipMemsetAsync(L.counters + (1 - cur), 0, 4, L.stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(L.counters + 2, 0, 4, L.stream)) != hipSuccess) return e;
+        const HitRec* qin = (const HitRec*)(cur == 0 ? L.hits : L.hits2);
+        HitRec* qout = (HitRec*)(cur == 0 ? L.hits2 : L.hits);
+        const unsigned int* order = nullptr;
+        if (L.fc.debug == 32 || !L.bounce_prep || !L.bounce_res) {      // (hook: the level as one kernel)
+            if (sorted && (e = sorted_ray_order(L, qin, L.counters + cur, (unsigned)band_n, &order)) != hipSuccess) return e;
+            e = with_flag(L.sc.b4 != nullptr && !L.bvh2_packets, [&](auto wide) { return with_flag(L.stats != nullptr, [&](auto stats) {
+                return launch(k_bounce<EXTRA, decltype(stats)::value, decltype(wide)::value>, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, qin, L.counters + cur, qout,
+                              L.counters + (1 - cur), L.counters + 2, L.bounce_levels, L.bounce_nlev, L.stats, order);
+            }); });
+            if (e != hipSuccess) return e;
+            continue;
+        }
+        WalkTuning hooks;
+        if (L.fc.debug >= 200 && L.fc.debug < 300) hooks.lds_levels = L.fc.debug - 200;
+        if (L.fc.debug >= 100 && L.fc.debug < 164) hooks.refill_at = L.fc.debug - 100;
+        if (L.fc.debug >= 300 && L.fc.debug < 400) {
+            hooks.node_burst = (L.fc.debug - 300) / 10 ? (L.fc.debug - 300) / 10 : -1;
+            hooks.leaf_burst = (L.fc.debug - 300) % 10 ? (L.fc.debug - 300) % 10 : -1;
+        }
+        if ((e = bounce_walk(L, qin, L.counters + cur, (unsigned)band_n, sorted, blocks, L.stats, hooks, &order)) != hipSuccess) return e;
+        e = with_flag(L.stats != nullptr, [&](auto stats) {
+            return launch(k_bounce_finish<EXTRA, decltype(stats)::value>, dim3(blocks), dim3(256), 0, L.stream, L.sc, L.fc, qin, L.counters + cur, order, (const BounceRay*)L.bounce_prep,
+                          (const BounceHit*)L.bounce_res, qout, L.counters + (1 - cur), L.bounce_levels, L.bounce_nlev, L.stats);
+        });
+        if (e != hipSuccess) return e;
+    }
+    return launch(k_fold, dim3((unsigned)((band_n / n2 * n2 + 255) / 256)), dim3(256), 0, L.stream, L.fc, band_n, (const uint32_t*)L.bounce_levels, (const uint8_t*)L.bounce_nlev, samples,
+                  L.row_map, row_begin, row_count);
+}
+
+// a static frame's shadow stage for one band: claim cells, run the shadow kernels on the generators only, apply the cache
+// counters: [0] hit points of the band  [13] generators  [14] copy of [0] while the generators are processed
+template <int MODE, bool EXTRA>
+static hipError_t launch_static_shadows_t(const PipelineLaunch& L, int row_count, uint32_t* samples) {
+    hipError_t e;
+    const int n2 = L.fc.sub_pixel_res * L.fc.sub_pixel_res;
+    const long long max_hits = (long long)row_count * L.fc.width * n2;
+    const int conc = L.static_concurrency > 0 ? L.static_concurrency : 4;        // Renderer.cs:92
+    const int block_height = (L.fc.num_rows - 1 + conc) / conc;                    // :1661
+    const int nblocks = (L.fc.num_rows - 1 + block_height) / block_height;
+    const unsigned blocks = (unsigned)std::min<long long>((max_hits + 255) / 256, (long long)L.persistent_blocks);
+    const uint8_t* cache = (const uint8_t*)L.sc.shadow_cache;
+    if ((e = hipMemsetAsync(L.static_claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
+    if ((e = launch(k_static_claim, dim3(blocks), dim3(256), 0, L.stream, L.fc, cache, (const HitRec*)L.hits, L.counters, L.static_claim, block_height, nblocks)) != hipSuccess) return e;
+    if ((e = launch(k_static_select, dim3(blocks), dim3(256), 0, L.stream, L.fc, cache, (const HitRec*)L.hits, L.counters, (const unsigned long long*)L.static_claim, block_height, nblocks,
+                    (HitRec*)L.static_hits, L.counters + 13)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(L.counters + 14, L.counters, 4, hipMemcpyDeviceToDevice, L.stream)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(L.counters, L.counters + 13, 4, hipMemcpyDeviceToDevice, L.stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(L.counters + kHeadsShaft, 0, 8 * kTileHeadStride * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
+    PipelineLaunch G = L;
+    G.hits = L.static_hits;
+    if (L.primary_stats_only) G.stats = nullptr;
+    if ((e = launch_shadow_t<MODE, EXTRA>(G, samples, std::min<long long>(max_hits, (long long)kStaticRes * kStaticRes * kStaticRes))) != hipSuccess) return e;
+    return launch(k_static_apply, dim3(blocks), dim3(256), 0, L.stream, cache, (const HitRec*)L.hits, L.counters + 14, samples);
 }
 
 template <int MODE, bool EXTRA>
@@ -6713,28 +6684,29 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
     const bool shadows = (L.fc.flags & 2u) != 0;
     const bool path = (L.fc.flags & kFlagPathTracing) != 0;          // (sr_api.cpp: never together with shadows or mirror bounces)
     const bool ao = (L.fc.flags & kFlagAmbientOcclusion) != 0;       // (sr_api.cpp: one band, never with path tracing, the static cache or mirror bounces)
-    if (path && L.pt_phase == 0) {
-        hipError_t e = hipMemsetAsync(L.pt_carry, 0, (size_t)L.pt_blocks * sizeof(uint32_t), L.stream);
-        if (e != hipSuccess) return e;
-    }
+    hipError_t e;
+    if (path && L.pt_phase == 0 && (e = hipMemsetAsync(L.pt_carry, 0, (size_t)L.pt_blocks * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
     if (path && L.pt_phase == 2) {
         // the part's row bases from the merged per-row counts of all parts: one workgroup per row block of the range
         const unsigned nblocks = (unsigned)((L.pt_range_rows + L.pt_block_height - 1) / L.pt_block_height);
-        hipLaunchKernelGGL(k_pt_row_base, dim3(nblocks), dim3(256), 0, L.stream, (const uint32_t*)L.pt_row_hits, L.pt_range_rows, L.pt_block_height, L.pt_range_first,
-                           L.row_map, L.fc.num_rows, L.pt_row_k0);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        if ((e = launch(k_pt_row_base, dim3(nblocks), dim3(256), 0, L.stream, (const uint32_t*)L.pt_row_hits, L.pt_range_rows, L.pt_block_height, L.pt_range_first, L.row_map,
+                        L.fc.num_rows, L.pt_row_k0)) != hipSuccess) return e;
     }
     const bool pt_second_pass = path && L.pt_phase == 2 && L.pt_reuse;       // the band's primary pass and scan are phase 1's
     // rows are processed in bands so that the hit queue / sample buffer stay within their allocation
     for (int row_begin = L.row_first; row_begin < L.row_limit; row_begin += L.band_rows) {
         int row_count = std::min(L.band_rows, L.row_limit - row_begin);
         uint32_t* samples = (n2 == 1) ? L.pixels : L.samples;
-        hipError_t e;
-        if (pt_second_pass) {
-            if ((e = launch_pathtrace_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
+        // the end of every band whose pixels are this launch's
+        const auto finish_band = [&]() -> hipError_t {
+            hipError_t e;
             if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
             if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);
+            return hipSuccess;
+        };
+        if (pt_second_pass) {
+            if ((e = launch_pathtrace_t<MODE, EXTRA>(L, row_begin, row_count, samples)) != hipSuccess) return e;
+            if ((e = finish_band()) != hipSuccess) return e;
             continue;
         }
         if (L.fc.flags & kFlagLightField) {
@@ -6744,119 +6716,34 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
             if (L.lf_tris) e = MODE == MODE_BRUTE ? hipErrorInvalidValue : launch_lft_t<MODE == MODE_BRUTE ? MODE_REF : MODE>(L, row_begin, row_count, samples);
             else e = launch_lightfield_t<MODE, EXTRA>(L, row_begin, row_count, samples);
             if (e != hipSuccess) return e;
-            if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
-            if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);
+            if ((e = finish_band()) != hipSuccess) return e;
             continue;
         }
         e = hipMemsetAsync(L.counters, 0, kCounterWords * sizeof(unsigned int), L.stream);   // the band's counters and both kernels' tile heads
         if (e != hipSuccess) return e;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_PRIMARY, &e0, &e1);
-        if (e0) { e = hipEventRecord(e0, L.stream); if (e != hipSuccess) return e; }
         // the shaft path of a dynamic-shadow frame reads the hit queue tile by tile (k_shaft_pkt): 64-aligned entries
         const bool shaft_frame = (MODE != MODE_BVH && L.shadows_on_bvh) ? shaft_path<MODE_BVH>(L) : shaft_path<MODE>(L);
         const int pad_tiles = (shadows && !(L.fc.flags & 32u) && L.fc.max_bounces == 0 && shaft_frame) ? 1 : 0;
-        if (path || (ao && !shadows)) {
-            // the primary pass of a shadowed frame is what the path tracer (and the ambient-occlusion stage of a frame without shadow rays)
-            // needs: shaded sample colours + the compacted hit queue
-            PipelineLaunch Q = L;
-            Q.fc.flags |= 2u;
-            e = L.fc.sub_pixel_res > 1 ? launch_primary_s<MODE, EXTRA, true>(Q, row_begin, row_count, samples, 0)
-                                       : launch_primary_s<MODE, EXTRA, false>(Q, row_begin, row_count, samples, 0);
-        } else
-        e = L.fc.sub_pixel_res > 1 ? launch_primary_s<MODE, EXTRA, true>(L, row_begin, row_count, samples, pad_tiles)
-                                   : launch_primary_s<MODE, EXTRA, false>(L, row_begin, row_count, samples, pad_tiles);
-        if (e == hipSuccess && pad_tiles) {
+        e = timed(L, K_PRIMARY, [&] {
+            if (path || (ao && !shadows)) {
+                // the primary pass of a shadowed frame is what the path tracer (and the ambient-occlusion stage of a frame without shadow rays)
+                // needs: shaded sample colours + the compacted hit queue
+                PipelineLaunch Q = L;
+                Q.fc.flags |= 2u;
+                return launch_primary<MODE, EXTRA>(Q, row_begin, row_count, samples, 0);
+            }
+            const hipError_t e = launch_primary<MODE, EXTRA>(L, row_begin, row_count, samples, pad_tiles);
+            if (e != hipSuccess || !pad_tiles) return e;
             // the tile-indexed queue has one slot per pixel of every (whole) 16x16 tile and sub-sample: its "count" is its size
             const unsigned int slots = (unsigned)(((L.fc.width + 15) / 16) * ((row_count + 15) / 16)) * 256u * (unsigned)n2;
-            e = hipMemsetD32Async((hipDeviceptr_t)L.counters, (int)slots, 1, L.stream);
-        }
+            return hipMemsetD32Async((hipDeviceptr_t)L.counters, (int)slots, 1, L.stream);
+        });
         if (e != hipSuccess) return e;
-        if (e1) { e = hipEventRecord(e1, L.stream); if (e != hipSuccess) return e; }
         if (L.fc.max_bounces > 0 && L.bounce_levels) {
-            // ---- mirror bounces as a wavefront pipeline: one k_bounce per level, the queues ping-pong ----
-            // counters: [0] / [1] ray counts of the two queues  [2] k_bounce's work head
-            const long long band_n = (long long)row_count * L.fc.width * n2;
-            hipEvent_t b0 = nullptr, b1 = nullptr;
-            if (L.get_events) L.get_events(L.user, K_BOUNCE, &b0, &b1);         // all levels' k_bounce launches + k_fold of this band
-            if (b0 && (e = hipEventRecord(b0, L.stream)) != hipSuccess) return e;
-            const bool wide = L.sc.b4 != nullptr && !L.bvh2_packets;                     // private walks on the four-wide tree
-            const size_t lds = (size_t)(wide ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE_BVH)) * 256 * 4;
-            const unsigned blocks = (unsigned)std::min<long long>((band_n + 255) / 256, (long long)L.persistent_blocks);
-            int cur = 0;
-            for (int level = 1; level <= L.fc.max_bounces; ++level) {
-                if ((e = hipMemsetAsync(L.counters + (1 - cur), 0, 4, L.stream)) != hipSuccess) return e;
-                if ((e = hipMemsetAsync(L.counters + 2, 0, 4, L.stream)) != hipSuccess) return e;
-                const HitRec* qin = (const HitRec*)(cur == 0 ? L.hits : L.hits2);
-                HitRec* qout = (HitRec*)(cur == 0 ? L.hits2 : L.hits);
-                // the level's rays in (origin cell, direction octant) order: neighbouring lanes walk neighbouring subtrees
-                const unsigned int* order = nullptr;
-                if (L.ray_sort_buf && L.fc.debug != 31) {
-                    const unsigned cap = (unsigned)band_n;
-                    unsigned int* b = L.ray_sort_buf;
-                    if ((e = ray_sort(qin, L.counters + cur, cap, L.sc.root, b, b + (size_t)cap, b + 2 * (size_t)cap, b + 3 * (size_t)cap, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
-                    order = b + 3 * (size_t)cap;
-                }
-                if (L.fc.debug == 32 || !L.bounce_prep || !L.bounce_res) {      // (hook: the level as one kernel)
-                    const auto go = [&](auto kern) {
-                        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, L.stream, L.sc, L.fc, qin, L.counters + cur, qout, L.counters + (1 - cur), L.counters + 2, L.bounce_levels, L.bounce_nlev, L.stats, order);
-                    };
-                    if (wide) { if (L.stats) go(k_bounce<EXTRA, true, true>); else go(k_bounce<EXTRA, false, true>); }
-                    else { if (L.stats) go(k_bounce<EXTRA, true, false>); else go(k_bounce<EXTRA, false, false>); }
-                } else {
-                    BounceRay* prep = (BounceRay*)L.bounce_prep;
-                    BounceHit* res = (BounceHit*)L.bounce_res;
-                    hipLaunchKernelGGL(k_bounce_prep, dim3(blocks), dim3(256), 0, L.stream, L.sc, qin, L.counters + cur, order, prep, res);
-                    // stack levels in LDS: kBounceLdsLevels when the rest of the worst case fits the overflow buffer, all of them otherwise
-                    const int levels_all = (int)(lds / (256 * 4));
-                    int lds_levels = (L.fc.debug >= 200 && L.fc.debug < 300) ? L.fc.debug - 200 : kBounceLdsLevels;      // (hook)
-                    lds_levels = std::max(1, std::min(lds_levels, levels_all));
-                    if ((size_t)(levels_all - lds_levels) * (size_t)blocks * 256 * 4 > L.bounce_stack_bytes || !L.bounce_stack) lds_levels = levels_all;
-                    const auto walk = [&](auto kern) {
-                        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), (size_t)lds_levels * 256 * 4, L.stream, L.sc, (const BounceRay*)prep, L.counters + cur, L.counters + 2, res, L.stats,
-                                           (L.fc.debug >= 100 && L.fc.debug < 164) ? L.fc.debug - 100 : kWalkRefillAt, L.bounce_stack, lds_levels,
-                                           (L.fc.debug >= 300 && L.fc.debug < 400) ? ((L.fc.debug - 300) / 10 ? (L.fc.debug - 300) / 10 : -1) : kWalkNodeBurst,
-                                           (L.fc.debug >= 300 && L.fc.debug < 400) ? ((L.fc.debug - 300) % 10 ? (L.fc.debug - 300) % 10 : -1) : kWalkLeafBurst);
-                    };
-                    if (wide) { if (L.stats) walk(k_bounce_walk<true, true>); else walk(k_bounce_walk<false, true>); }
-                    else { if (L.stats) walk(k_bounce_walk<true, false>); else walk(k_bounce_walk<false, false>); }
-                    const auto fin = [&](auto kern) {
-                        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, L.stream, L.sc, L.fc, qin, L.counters + cur, order, (const BounceRay*)prep, (const BounceHit*)res,
-                                           qout, L.counters + (1 - cur), L.bounce_levels, L.bounce_nlev, L.stats);
-                    };
-                    if (L.stats) fin(k_bounce_finish<EXTRA, true>); else fin(k_bounce_finish<EXTRA, false>);
-                }
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                cur = 1 - cur;
-            }
-            hipLaunchKernelGGL(k_fold, dim3((unsigned)((band_n / n2 * n2 + 255) / 256)), dim3(256), 0, L.stream, L.fc, band_n, (const uint32_t*)L.bounce_levels,
-                               (const uint8_t*)L.bounce_nlev, samples, L.row_map, row_begin, row_count);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            if (b1 && (e = hipEventRecord(b1, L.stream)) != hipSuccess) return e;
+            // (one pair around all levels' launches + k_fold of this band)
+            if ((e = timed(L, K_BOUNCE, [&] { return launch_bounces<EXTRA>(L, row_begin, row_count, samples); })) != hipSuccess) return e;
         } else if (shadows && (L.fc.flags & 32u)) {
-            // ---- static frame: claim cells, run the shadow kernels on the generators only, apply the cache ----
-            // counters: [0] hit points of the band  [13] generators  [14] copy of [0] while the generators are processed
-            const long long max_hits = (long long)row_count * L.fc.width * n2;
-            const int conc = L.static_concurrency > 0 ? L.static_concurrency : 4;        // Renderer.cs:92
-            const int block_height = (L.fc.num_rows - 1 + conc) / conc;                    // :1661
-            const int nblocks = (L.fc.num_rows - 1 + block_height) / block_height;
-            const unsigned blocks = (unsigned)std::min<long long>((max_hits + 255) / 256, (long long)L.persistent_blocks);
-            if ((e = hipMemsetAsync(L.static_claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
-            hipLaunchKernelGGL(k_static_claim, dim3(blocks), dim3(256), 0, L.stream, L.fc, (const uint8_t*)L.sc.shadow_cache, (const HitRec*)L.hits, L.counters,
-                               L.static_claim, block_height, nblocks);
-            hipLaunchKernelGGL(k_static_select, dim3(blocks), dim3(256), 0, L.stream, L.fc, (const uint8_t*)L.sc.shadow_cache, (const HitRec*)L.hits, L.counters,
-                               (const unsigned long long*)L.static_claim, block_height, nblocks, (HitRec*)L.static_hits, L.counters + 13);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            if ((e = hipMemcpyAsync(L.counters + 14, L.counters, 4, hipMemcpyDeviceToDevice, L.stream)) != hipSuccess) return e;
-            if ((e = hipMemcpyAsync(L.counters, L.counters + 13, 4, hipMemcpyDeviceToDevice, L.stream)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(L.counters + kHeadsShaft, 0, 8 * kTileHeadStride * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
-            PipelineLaunch G = L;
-            G.hits = L.static_hits;
-            if (L.primary_stats_only) G.stats = nullptr;
-            e = launch_shadow_t<MODE, EXTRA>(G, samples, std::min<long long>(max_hits, (long long)kStaticRes * kStaticRes * kStaticRes));
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k_static_apply, dim3(blocks), dim3(256), 0, L.stream, (const uint8_t*)L.sc.shadow_cache, (const HitRec*)L.hits, L.counters + 14, samples);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if ((e = launch_static_shadows_t<MODE, EXTRA>(L, row_count, samples)) != hipSuccess) return e;
         } else if (shadows) {
             // (queue entries are counted in whole tiles: see pad_tiles)
             PipelineLaunch T = L;                                    // this band's queue is tile-indexed (k_primary above)
@@ -6874,20 +6761,13 @@ static hipError_t launch_pipeline_t(const PipelineLaunch& L) {
             const long long max_hits = (long long)((row_count + 15) / 16 * 16) * ((L.fc.width + 15) / 16 * 16) * n2;
             if ((e = launch_ao_t<MODE, EXTRA>(L, row_begin, row_count, samples, max_hits)) != hipSuccess) return e;
         }
-        if (n2 > 1 && (e = launch_resolve(L, row_begin, row_count)) != hipSuccess) return e;
-        if (L.band_done) L.band_done(L.user, (row_begin - L.row_first) / L.band_rows, row_begin, row_count, L.stream);
+        if ((e = finish_band()) != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
 hipError_t launch_pipeline(const PipelineLaunch& L) {
-    const bool extra = L.sc.nextra > 0;
-    switch (L.mode) {
-        case MODE_REF: return extra ? launch_pipeline_t<MODE_REF, true>(L) : launch_pipeline_t<MODE_REF, false>(L);
-        case MODE_BRUTE: return extra ? launch_pipeline_t<MODE_BRUTE, true>(L) : launch_pipeline_t<MODE_BRUTE, false>(L);
-        case MODE_BVH: return extra ? launch_pipeline_t<MODE_BVH, true>(L) : launch_pipeline_t<MODE_BVH, false>(L);
-        default: return hipErrorInvalidValue;
-    }
+    return for_mode(L.mode, L.sc.nextra > 0, [&](auto mode, auto extra) { return launch_pipeline_t<decltype(mode)::value, decltype(extra)::value>(L); });
 }
 
 size_t pipeline_hit_record_bytes() { return sizeof(HitRec); }
@@ -6899,6 +6779,15 @@ int pipeline_round_cap_max(int round) { return round == 0 ? 64 : 1024; }
 int pipeline_bounce_lds_levels() { return kBounceLdsLevels; }
 int pipeline_pt_chunk() { return kPtChunk; }
 size_t pipeline_round_state_bytes() { return sizeof(RoundState); }
+
+// the draw table of a pass from the window the jump-ahead left in base_window: k_aop_states (the state of every chunk of units) and k_draws
+// (300 draws per unit); *units: the pass's units, on the device
+static hipError_t draws_table(const int32_t* base_window, const uint32_t* stride_rows, const uint32_t* units, uint32_t chunks, int32_t* table, hipStream_t stream) {
+    hipError_t e;
+    if ((e = launch(k_aop_states, dim3((chunks + (uint32_t)kAopSuper - 1u) / (uint32_t)kAopSuper), dim3(64), 0, stream, base_window, stride_rows, units, table)) != hipSuccess) return e;
+    return launch(k_draws, dim3((chunks + 3u) / 4u), dim3(256), 0, stream, units, chunks, table);
+}
+
 // sr_ao_points: the passes, back to back on the stream (see k_aop_ingest).  A pass waits for the host only when the host makes its table
 // (AoPointsLaunch::host_table: SR_DBG_KERNEL_SWITCH 44, or a seed the jump-ahead does not cover)
 template <int MODE, bool EXTRA>
@@ -6912,65 +6801,47 @@ static hipError_t launch_ao_points_t(const AoPointsLaunch& L) {
     unsigned long long host_before = 0;                                   // (host tables only) generators of the earlier passes
     for (int64_t first = 0; first < L.n; first += L.pass) {
         const uint32_t count = (uint32_t)std::min<int64_t>(L.pass, L.n - first);
-        const unsigned blocks = (count + 255u) / 256u;
-        const uint32_t scan_chunks = (count + (uint32_t)kPtChunk - 1u) / (uint32_t)kPtChunk;
+        const dim3 grid((count + 255u) / 256u);
         const uint32_t chunks = (count + (uint32_t)kAopChunkGens - 1u) / (uint32_t)kAopChunkGens;
-        const uint32_t* pass_count = L.totals + scan_chunks;
-        if (cached) {
-            if ((e = hipMemsetAsync(L.claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
-            hipLaunchKernelGGL(k_aop_ingest<true>, dim3(blocks), dim3(256), 0, L.stream, L.pos + first * 3, L.nrm + first * 3, count, (unsigned long long)first,
-                               (const uint8_t*)L.cache, L.claim, recs);
-        } else {
-            hipLaunchKernelGGL(k_aop_ingest<false>, dim3(blocks), dim3(256), 0, L.stream, L.pos + first * 3, L.nrm + first * 3, count, (unsigned long long)first,
-                               (const uint8_t*)nullptr, (unsigned long long*)nullptr, recs);
-        }
-        hipLaunchKernelGGL(k_aop_mark, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)recs, count, (unsigned long long)first, (const uint8_t*)L.cache,
-                           (const unsigned long long*)L.claim, L.flags);
-        hipLaunchKernelGGL(k_pt_scan, dim3(scan_chunks), dim3(256), 0, L.stream, (const uint8_t*)L.flags, count, L.index, L.totals);
-        hipLaunchKernelGGL(k_pt_scan_totals, dim3(1), dim3(256), 0, L.stream, L.totals, scan_chunks);
-        hipLaunchKernelGGL(k_aop_select, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)recs, count, (const uint8_t*)L.flags, (const uint32_t*)L.index,
-                           (const uint32_t*)L.totals, gen);
+        const uint32_t* pass_count = L.totals + flag_scan_chunks(count);
+        if (cached && (e = hipMemsetAsync(L.claim, 0xff, (size_t)kStaticRes * kStaticRes * kStaticRes * 8, L.stream)) != hipSuccess) return e;
+        e = with_flag(cached, [&](auto c) {
+            return launch(k_aop_ingest<decltype(c)::value>, grid, dim3(256), 0, L.stream, L.pos + first * 3, L.nrm + first * 3, count, (unsigned long long)first,
+                          decltype(c)::value ? (const uint8_t*)L.cache : nullptr, decltype(c)::value ? L.claim : nullptr, recs);
+        });
+        if (e != hipSuccess) return e;
+        if ((e = launch(k_aop_mark, grid, dim3(256), 0, L.stream, (const HitRec*)recs, count, (unsigned long long)first, (const uint8_t*)L.cache, (const unsigned long long*)L.claim,
+                        L.flags)) != hipSuccess) return e;
+        if ((e = flag_scan(L.flags, count, L.index, L.totals, L.stream)) != hipSuccess) return e;
+        if ((e = launch(k_aop_select, grid, dim3(256), 0, L.stream, (const HitRec*)recs, count, (const uint8_t*)L.flags, (const uint32_t*)L.index, (const uint32_t*)L.totals, gen)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(L.escapes, 0, (size_t)count * sizeof(uint32_t), L.stream)) != hipSuccess) return e;
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipEvent_t e0, e1;
-        e0 = e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_DRAWS, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        if (L.host_table) {
-            uint32_t ngen = 0;
-            if ((e = hipMemcpyAsync(&ngen, pass_count, sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
-            if ((e = hipStreamSynchronize(L.stream)) != hipSuccess) return e;
-            if ((e = L.host_table(L.user, L.first_generator + host_before, ngen, L.table, L.stream)) != hipSuccess) return e;
-            host_before += ngen;
-            hipLaunchKernelGGL(k_aop_total, dim3(1), dim3(1), 0, L.stream, L.running, pass_count, L.generators_out);
-        } else {
-            hipLaunchKernelGGL(k_aop_base, dim3(1), dim3(128), 0, L.stream, L.window, (unsigned long long)L.first_generator, L.running, pass_count, L.base_window,
-                               L.generators_out);
-            hipLaunchKernelGGL(k_aop_states, dim3((chunks + (uint32_t)kAopSuper - 1u) / (uint32_t)kAopSuper), dim3(64), 0, L.stream, (const int32_t*)L.base_window,
-                               L.stride_rows, pass_count, L.table);
-            hipLaunchKernelGGL(k_draws, dim3((chunks + 3u) / 4u), dim3(256), 0, L.stream, pass_count, chunks, L.table);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        e = timed(L, K_DRAWS, [&] {
+            hipError_t e;
+            if (L.host_table) {
+                uint32_t ngen = 0;
+                if ((e = hipMemcpyAsync(&ngen, pass_count, sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
+                if ((e = hipStreamSynchronize(L.stream)) != hipSuccess) return e;
+                if ((e = L.host_table(L.user, L.first_generator + host_before, ngen, L.table, L.stream)) != hipSuccess) return e;
+                host_before += ngen;
+                return launch(k_aop_total, dim3(1), dim3(1), 0, L.stream, L.running, pass_count, L.generators_out);
+            }
+            if ((e = launch(k_aop_base, dim3(1), dim3(128), 0, L.stream, L.window, (unsigned long long)L.first_generator, L.running, pass_count, L.base_window, L.generators_out)) != hipSuccess) return e;
+            return draws_table(L.base_window, L.stride_rows, pass_count, chunks, L.table, L.stream);
+        });
+        if (e != hipSuccess) return e;
         const unsigned long long items = (unsigned long long)count * (unsigned long long)kAoProbes;
         const unsigned pblocks = (unsigned)std::min<unsigned long long>((items + 255) / 256, (unsigned long long)L.persistent_blocks);
-        e0 = e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_AOP_PROBE, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        const auto probe = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), lds, L.stream, L.sc, (const HitRec*)gen, pass_count, (const int32_t*)L.table, L.escapes, L.stats);
-        };
-        if (MODE == MODE_BVH && !L.nearest_walks) {                                   // (hook 34: nearest-hit walks, same bytes)
-            if (L.stats) probe(k_aop_probe<MODE, EXTRA, true, true>); else probe(k_aop_probe<MODE, EXTRA, false, true>);
-        } else {
-            if (L.stats) probe(k_aop_probe<MODE, EXTRA, true, false>); else probe(k_aop_probe<MODE, EXTRA, false, false>);
-        }
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_aop_store, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)gen, pass_count, L.escapes, L.cache);
-        hipLaunchKernelGGL(k_aop_apply, dim3(blocks), dim3(256), 0, L.stream, (const HitRec*)recs, count, (const uint8_t*)L.cache, (const uint32_t*)L.index,
-                           (const uint32_t*)L.totals, (const uint32_t*)L.escapes, L.color ? L.color + first : nullptr, L.out ? L.out + first : nullptr,
-                           L.amount ? L.amount + first : nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        e = timed(L, K_AOP_PROBE, [&] {
+            // (hook 34: nearest-hit walks, same bytes)
+            return with_flag(MODE == MODE_BVH && !L.nearest_walks, [&](auto any_hit) { return with_flag(L.stats != nullptr, [&](auto stats) {
+                return launch(k_aop_probe<MODE, EXTRA, decltype(stats)::value, decltype(any_hit)::value>, dim3(pblocks), dim3(256), lds, L.stream, L.sc, (const HitRec*)gen, pass_count,
+                              (const int32_t*)L.table, L.escapes, L.stats);
+            }); });
+        });
+        if (e != hipSuccess) return e;
+        if ((e = launch(k_aop_store, grid, dim3(256), 0, L.stream, (const HitRec*)gen, pass_count, L.escapes, L.cache)) != hipSuccess) return e;
+        if ((e = launch(k_aop_apply, grid, dim3(256), 0, L.stream, (const HitRec*)recs, count, (const uint8_t*)L.cache, (const uint32_t*)L.index, (const uint32_t*)L.totals,
+                        (const uint32_t*)L.escapes, L.color ? L.color + first : nullptr, L.out ? L.out + first : nullptr, L.amount ? L.amount + first : nullptr)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -6978,13 +6849,7 @@ static hipError_t launch_ao_points_t(const AoPointsLaunch& L) {
 hipError_t launch_ao_points(const AoPointsLaunch& L) {
     if (L.n <= 0) return hipSuccess;
     if (L.pass <= 0 || L.pass > kAopMaxPass) return hipErrorInvalidValue;
-    const bool extra = L.sc.nextra > 0;
-    switch (L.mode) {
-        case MODE_REF: return extra ? launch_ao_points_t<MODE_REF, true>(L) : launch_ao_points_t<MODE_REF, false>(L);
-        case MODE_BRUTE: return extra ? launch_ao_points_t<MODE_BRUTE, true>(L) : launch_ao_points_t<MODE_BRUTE, false>(L);
-        case MODE_BVH: return extra ? launch_ao_points_t<MODE_BVH, true>(L) : launch_ao_points_t<MODE_BVH, false>(L);
-        default: return hipErrorInvalidValue;
-    }
+    return for_mode(L.mode, L.sc.nextra > 0, [&](auto mode, auto extra) { return launch_ao_points_t<decltype(mode)::value, decltype(extra)::value>(L); });
 }
 size_t ao_points_table_bytes(int64_t pass) {
     return (size_t)((pass + kAopChunkGens - 1) / kAopChunkGens) * (size_t)kAopChunkDraws * sizeof(int32_t);
@@ -7005,76 +6870,51 @@ static hipError_t launch_path_points_t(const PathPointsLaunch& L) {
     int64_t p = 0;
     for (int64_t first = 0; first < L.n; first += L.pass, ++p) {
         const uint32_t count = (uint32_t)std::min<int64_t>(L.pass, L.n - first);
-        const unsigned blocks = (count + 255u) / 256u;
+        const dim3 grid((count + 255u) / 256u);
         const uint32_t units = (count + (uint32_t)kPpUnitPoints - 1u) / (uint32_t)kPpUnitPoints;
         const uint32_t chunks = (units + (uint32_t)kAopChunkGens - 1u) / (uint32_t)kAopChunkGens;
-        hipEvent_t e0, e1;
-        e0 = e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_DRAWS, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        if (L.host_table) {
-            if ((e = L.host_table(L.user, L.first_sample + (uint64_t)first, count, L.table, L.stream)) != hipSuccess) return e;
-        } else {
-            hipLaunchKernelGGL(k_pp_window, dim3(1), dim3(64), 0, L.stream, L.windows[p], units, L.base_window, L.pass_units);
-            hipLaunchKernelGGL(k_aop_states, dim3((chunks + (uint32_t)kAopSuper - 1u) / (uint32_t)kAopSuper), dim3(64), 0, L.stream, (const int32_t*)L.base_window,
-                               L.stride_rows, (const uint32_t*)L.pass_units, L.table);
-            hipLaunchKernelGGL(k_draws, dim3((chunks + 3u) / 4u), dim3(256), 0, L.stream, (const uint32_t*)L.pass_units, chunks, L.table);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        e = timed(L, K_DRAWS, [&] {
+            if (L.host_table) return L.host_table(L.user, L.first_sample + (uint64_t)first, count, L.table, L.stream);
+            const hipError_t e = launch(k_pp_window, dim3(1), dim3(64), 0, L.stream, L.windows[p], units, L.base_window, L.pass_units);
+            return e != hipSuccess ? e : draws_table(L.base_window, L.stride_rows, L.pass_units, chunks, L.table, L.stream);
+        });
+        if (e != hipSuccess) return e;
         const double* pos = L.pos + first * 3;
         const double* nrm = L.nrm + first * 3;
         double* dirs = L.dirs ? L.dirs + first * 3 : nullptr;
         const uint32_t* color = L.color ? L.color + first : nullptr;
         uint32_t* out = L.out ? L.out + first : nullptr;
         uint32_t* incoming = L.incoming ? L.incoming + first : nullptr;
+        // (without a stand-in origin: the directions alone, or the per-lane walks of the other modes)
+        const auto ingest_plain = [&](HitRec* to) {
+            return launch(k_pp_ingest<false>, grid, dim3(256), 0, L.stream, pos, nrm, count, (const int32_t*)L.table, 0.0, 0.0, 0.0, 0.0, to, (unsigned int*)nullptr, dirs);
+        };
         if (!trace) {
-            hipLaunchKernelGGL(k_pp_ingest<false>, dim3(blocks), dim3(256), 0, L.stream, pos, nrm, count, (const int32_t*)L.table, 0.0, 0.0, 0.0, 0.0,
-                               (HitRec*)nullptr, (unsigned int*)nullptr, dirs);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if ((e = ingest_plain(nullptr)) != hipSuccess) return e;
             continue;
         }
-        e0 = e1 = nullptr;
-        if (L.get_events) L.get_events(L.user, K_PP_TRACE, &e0, &e1);
-        if (e0 && (e = hipEventRecord(e0, L.stream)) != hipSuccess) return e;
-        const unsigned pblocks = std::min<unsigned>(blocks, (unsigned)L.persistent_blocks);
-        if constexpr (MODE == MODE_BVH) {
-            if ((e = hipMemsetAsync(L.counters, 0, 4 * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
-            hipLaunchKernelGGL(k_pp_ingest<true>, dim3(blocks), dim3(256), 0, L.stream, pos, nrm, count, (const int32_t*)L.table, L.sc.root.centre[0], L.sc.root.centre[1],
-                               L.sc.root.centre[2], away, rays, L.counters, dirs);
-            // the route of a path-traced frame's second rays (launch_pathtrace_t)
-            const bool wide = L.sc.b4 != nullptr && !L.bvh2_packets;
-            const size_t wlds = (size_t)(wide ? 3 * L.sc.b4depth + 2 : pipe_stack_levels(L.sc, MODE_BVH)) * 256 * 4;
-            unsigned int* b = L.ray_sort_buf;
-            if ((e = ray_sort(rays, L.counters, count, L.sc.root, b, b + (size_t)count, b + 2 * (size_t)count, b + 3 * (size_t)count, L.ray_sort_temp, L.ray_sort_temp_bytes, L.stream)) != hipSuccess) return e;
-            const unsigned int* order = b + 3 * (size_t)count;
-            BounceRay* prep = (BounceRay*)L.bounce_prep;
-            BounceHit* res = (BounceHit*)L.bounce_res;
-            hipLaunchKernelGGL(k_bounce_prep, dim3(pblocks), dim3(256), 0, L.stream, L.sc, (const HitRec*)rays, (const unsigned int*)L.counters, order, prep, res);
-            const int levels_all = (int)(wlds / (256 * 4));
-            int lds_levels = std::max(1, std::min(kBounceLdsLevels, levels_all));
-            if ((size_t)(levels_all - lds_levels) * (size_t)pblocks * 256 * 4 > L.bounce_stack_bytes || !L.bounce_stack) lds_levels = levels_all;
-            const auto walk = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), (size_t)lds_levels * 256 * 4, L.stream, L.sc, (const BounceRay*)prep, (const unsigned int*)L.counters, L.counters + 2, res,
-                                   L.stats, kWalkRefillAt, L.bounce_stack, lds_levels, kWalkNodeBurst, kWalkLeafBurst);
-            };
-            if (wide) { if (L.stats) walk(k_bounce_walk<true, true>); else walk(k_bounce_walk<false, true>); }
-            else { if (L.stats) walk(k_bounce_walk<true, false>); else walk(k_bounce_walk<false, false>); }
-            const auto finw = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), 0, L.stream, L.sc, L.fc, (const HitRec*)rays, (const unsigned int*)L.counters, order, (const BounceRay*)prep,
-                                   (const BounceHit*)res, pos, nrm, color, out, incoming, L.stats);
-            };
-            if (L.stats) finw(k_pp_finish_walked<EXTRA, true>); else finw(k_pp_finish_walked<EXTRA, false>);
-        } else {
-            hipLaunchKernelGGL(k_pp_ingest<false>, dim3(blocks), dim3(256), 0, L.stream, pos, nrm, count, (const int32_t*)L.table, 0.0, 0.0, 0.0, 0.0, rays,
-                               (unsigned int*)nullptr, dirs);
-            const auto fin = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(pblocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)rays, count, nrm, color, out, incoming, L.stats);
-            };
-            if (L.stats) fin(k_pp_finish<MODE, EXTRA, true>); else fin(k_pp_finish<MODE, EXTRA, false>);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (e1 && (e = hipEventRecord(e1, L.stream)) != hipSuccess) return e;
+        e = timed(L, K_PP_TRACE, [&] {
+            hipError_t e;
+            const unsigned pblocks = std::min<unsigned>(grid.x, (unsigned)L.persistent_blocks);
+            if constexpr (MODE == MODE_BVH) {
+                if ((e = hipMemsetAsync(L.counters, 0, 4 * sizeof(unsigned int), L.stream)) != hipSuccess) return e;
+                if ((e = launch(k_pp_ingest<true>, grid, dim3(256), 0, L.stream, pos, nrm, count, (const int32_t*)L.table, L.sc.root.centre[0], L.sc.root.centre[1], L.sc.root.centre[2], away,
+                                rays, L.counters, dirs)) != hipSuccess) return e;
+                const unsigned int* order;
+                if ((e = bounce_walk(L, rays, L.counters, count, true, pblocks, L.stats, WalkTuning{}, &order)) != hipSuccess) return e;
+                return with_flag(L.stats != nullptr, [&](auto stats) {
+                    return launch(k_pp_finish_walked<EXTRA, decltype(stats)::value>, dim3(pblocks), dim3(256), 0, L.stream, L.sc, L.fc, (const HitRec*)rays, (const unsigned int*)L.counters,
+                                  order, (const BounceRay*)L.bounce_prep, (const BounceHit*)L.bounce_res, pos, nrm, color, out, incoming, L.stats);
+                });
+            } else {
+                if ((e = ingest_plain(rays)) != hipSuccess) return e;
+                return with_flag(L.stats != nullptr, [&](auto stats) {
+                    return launch(k_pp_finish<MODE, EXTRA, decltype(stats)::value>, dim3(pblocks), dim3(256), lds, L.stream, L.sc, L.fc, (const HitRec*)rays, count, nrm, color, out, incoming,
+                                  L.stats);
+                });
+            }
+        });
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -7082,13 +6922,7 @@ static hipError_t launch_path_points_t(const PathPointsLaunch& L) {
 hipError_t launch_path_points(const PathPointsLaunch& L) {
     if (L.n <= 0) return hipSuccess;
     if (L.pass <= 0 || L.pass > kPpMaxPass || (!L.windows && !L.host_table)) return hipErrorInvalidValue;
-    const bool extra = L.sc.nextra > 0;
-    switch (L.mode) {
-        case MODE_REF: return extra ? launch_path_points_t<MODE_REF, true>(L) : launch_path_points_t<MODE_REF, false>(L);
-        case MODE_BRUTE: return extra ? launch_path_points_t<MODE_BRUTE, true>(L) : launch_path_points_t<MODE_BRUTE, false>(L);
-        case MODE_BVH: return extra ? launch_path_points_t<MODE_BVH, true>(L) : launch_path_points_t<MODE_BVH, false>(L);
-        default: return hipErrorInvalidValue;
-    }
+    return for_mode(L.mode, L.sc.nextra > 0, [&](auto mode, auto extra) { return launch_path_points_t<decltype(mode)::value, decltype(extra)::value>(L); });
 }
 size_t path_points_table_bytes(int64_t pass) { return ao_points_table_bytes((pass + kPpUnitPoints - 1) / kPpUnitPoints); }
 
